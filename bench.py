@@ -3,9 +3,17 @@
 4K P010 + YUV420 pairs (BASELINE.json metric; workload = configs[2], "Batch 64 x 4K P010 frames,
 generate+apply on 1 MI355X"; with N GPUs every rank holds its own 64 frames = configs[3]'s sharding).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, ramps the clocks, warms up, times the K steps and prints the line (value, ms_per_step, the apply launches'
+roofline).  --full adds everything else the line has carried: the cold-start and fixed-batch passes, generate's own launch time,
+the other placement policy, the measured memory ceilings, the CPU baseline, the other BASELINE configs and, for N > 1, the
+collective report.
+
+--dump-outputs DIR writes what the last timed step computed on rank 0 (its batch's gain maps, 1010102 outputs, per-image content
+min/max and metadata) as float32 / float64 .npy files; a fixed, seeded sample of the pixels keeps it under 64 MB.
 
 Started without torch.distributed.run and with --gpus N > 1, this file launches the N ranks itself (fresh child processes through
 torch.distributed.run, started before anything here has touched a GPU) and relays rank 0's JSON line.
@@ -90,7 +98,14 @@ def parse():
     ap.add_argument("--cpu-frames", type=int, default=3, help="frames of the same batch timed on the host CPU")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous / reductions only, no GPU work and no measurement "
                     "(tests/test_bench_launcher.py: the N-rank launch on a box without GPUs); prints value null")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beyond `value`: cold_start, fixed_batch, "
+                    "generate's launch time, the other placement policy, measured ceilings, cpu_baseline, other_configs, the collective "
+                    "report (the --no-* options above pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (rank 0) to DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def sources_sha16():
@@ -308,6 +323,32 @@ class Batch:
             if events is not None:
                 e1.record()
                 events.append((e0, e1, m))
+
+
+MAP_SAMPLES, OUT_SAMPLES, DUMP_SEED = 65536, 16384, 2024   # positions sampled per frame (of 518 400 map bytes, 8 294 400 pixels)
+
+
+def dump_outputs(batch, dirname):
+    """--dump-outputs: what generate + apply handed their caller for `batch`, at fixed seeded positions (the same for every frame,
+    run and build): gain_map [frames, MAP_SAMPLES] map bytes, rgba1010102 [frames, OUT_SAMPLES, 4] the R, G, B, A fields of the
+    output pixels, content_minmax [frames, 2] (when the stats pass ran) and metadata [7], as float32 / float64 (~34 MB at 64 frames)."""
+    torch.cuda.synchronize()
+    rng = np.random.default_rng(DUMP_SEED)
+    mpos = torch.from_numpy(np.sort(rng.choice((W // 4) * (H // 4), MAP_SAMPLES, replace=False))).cuda()
+    ppos = np.sort(rng.choice(W * H, OUT_SAMPLES, replace=False))
+    bpos = torch.from_numpy((ppos[:, None] * 4 + np.arange(4)).ravel()).cuda()   # the 4 bytes of each sampled pixel
+    maps = torch.stack([m[mpos] for m in batch.maps]).cpu().numpy()
+    px = torch.stack([o[bpos] for o in batch.outs]).cpu().numpy().view("<u4")
+    rgba = np.stack([(px >> 0) & 0x3ff, (px >> 10) & 0x3ff, (px >> 20) & 0x3ff, px >> 30], axis=-1)
+    md = batch.md
+    out = {"gain_map": maps.astype(np.float32), "rgba1010102": rgba.astype(np.float32),
+           "metadata": np.array([md.maxContentBoost, md.minContentBoost, md.gamma, md.offsetSdr, md.offsetHdr, md.hdrCapacityMin,
+                                 md.hdrCapacityMax], np.float64)}
+    if batch.stats:
+        out["content_minmax"] = batch.minmax.view(-1, 2).cpu().numpy().astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), arr)
 
 
 def other_configs(lib, stream):
@@ -746,27 +787,31 @@ def main():
         return dt
 
     # Setup takes a fraction of a second (the frames are written by one kernel each), so the card arrives here at idle clocks, and
-    # it raises them only under sustained load.  Both states are measured with the same protocol and both are reported: first the
-    # card as it comes (`cold_start`), then -- after the step has run for ramp_ms -- the state a service under load is in (`value`).
-    cold_elapsed = timed_steps() if a.ramp_ms > 0 else None
+    # it raises them only under sustained load.  Both states are measured with the same protocol (the first with --full only): first
+    # the card as it comes (`cold_start`), then -- after the step has run for ramp_ms -- the state a service under load is in (`value`).
+    cold_elapsed = timed_steps() if a.full and a.ramp_ms > 0 else None
     t_ramp = time.perf_counter()
     while (time.perf_counter() - t_ramp) * 1e3 < a.ramp_ms:
         for _ in range(8):
             step(exchange=False)   # (a time-bounded loop: ranks run different counts, so nothing collective in it)
         torch.cuda.synchronize()
+    while turn[0] % R:             # the timed steps start on batch 0, so the batch of the last one depends on W and K alone
+        step(exchange=False)
     ev_gen, ev_app = [], []
     elapsed = timed_steps(ev_gen if a.events == "all" else None, ev_app if a.events != "none" else None)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(batches[(turn[0] - 1) % R], a.dump_outputs)
     # the same protocol on ONE batch, step after step (rounds 1-3's `value`): reported beside `value`, never as it
-    fixed_elapsed = timed_steps(rotate=False) if R > 1 and not a.no_fixed_batch else None
+    fixed_elapsed = timed_steps(rotate=False) if a.full and R > 1 and not a.no_fixed_batch else None
     gen_from_side_pass = False
-    if a.events == "apply":   # generate's launch time: a pass of its own, both kernels bracketed (never part of `value`)
+    if a.full and a.events == "apply":   # generate's launch time: a pass of its own, both kernels bracketed (never part of `value`)
         side_gen, side_app = [], []
         timed_steps(side_gen, side_app)
         ev_gen, gen_from_side_pass = side_gen, True
 
     # the other placement policy, same protocol, right behind (never `value`): the batches again from torch's allocator
     other_elapsed = None
-    if pool is not None and not a.no_placement_ab:
+    if a.full and pool is not None and not a.no_placement_ab:
         mine = list(batches)
         batches[:] = [Batch(lib, a.frames, rank, seed_offset=65536 * r) for r in range(R)]
         for bt in batches:
@@ -783,7 +828,7 @@ def main():
     gen_ms, gen_tot, gen_frames = avg_ms_per_launch(ev_gen)
     app_ms, app_tot, app_frames = avg_ms_per_launch(ev_app)
     coll = None
-    if multi:   # (outside the timed region; every rank takes part)
+    if multi and a.full:   # (outside the timed region; every rank takes part)
         mine = sharding.reduce_content_minmax(batch.minmax)             # this rank's own (min, max): no collective
         glob = sharding.reduce_content_minmax(batch.minmax, dist)       # the step's exchange once more, joined
         exch = None
@@ -800,8 +845,8 @@ def main():
                                  path="capi: libuhdr_hip_comm.so (uhdr_hip_comm_allreduce_minmax -> ncclAllReduce), id through torch.distributed" if clib is not None
                                  else "torch.distributed")
         coll["path_note"] = comm_note
-        if clib is not None:
-            clib.uhdr_hip_comm_destroy(chandle)
+    if clib is not None:
+        clib.uhdr_hip_comm_destroy(chandle)
 
     if rank == 0:
         mpix_frame = W * H / 1e6
@@ -826,12 +871,13 @@ def main():
                 pass
         # the box's own ceilings beside the 8 TB/s specification (torch kernels over 1 GiB buffers; < 1 s)
         ceilings = None
-        try:
-            sys.path.insert(0, os.path.join(ROOT, "scripts"))
-            import mem_ceiling
-            ceilings = {k: round(v, 1) for k, v in mem_ceiling.measure(1 << 30).items()}
-        except Exception:
-            pass
+        if a.full:
+            try:
+                sys.path.insert(0, os.path.join(ROOT, "scripts"))
+                import mem_ceiling
+                ceilings = {k: round(v, 1) for k, v in mem_ceiling.measure(1 << 30).items()}
+            except Exception:
+                pass
         read_gbs = (GEN_READ_BYTES + APP_READ_BYTES) * total_frames / world / elapsed / 1e9
         out = {
             "metric": "MPixels/sec gain-map generate+apply, 4K P010 batch", "value": round(value, 1), "unit": "MPix/s",
@@ -880,7 +926,8 @@ def main():
                                        "bytes_per_frame_pair": GEN_READ_BYTES + APP_READ_BYTES, "scope": "generate+apply step, per GPU"},
                          "measured_ceilings_this_box_GBs": ceilings},
             "kernels": {
-                "generate": {"avg_launch_ms": round(gen_ms, 4), "GB/s": round(gen_gbs, 1), "frac_of_8TBs": round(gen_gbs / HBM_PEAK_GBS, 4),
+                "generate": None if not ev_gen else {  # (plain run with --events apply: measured by --full only)
+                             "avg_launch_ms": round(gen_ms, 4), "GB/s": round(gen_gbs, 1), "frac_of_8TBs": round(gen_gbs / HBM_PEAK_GBS, 4),
                              "bytes_per_frame": GEN_BYTES,
                              "measured_in": "a pass of its own behind the timed region, both kernels bracketed by events" if gen_from_side_pass
                                             else "the timed region"},
@@ -892,9 +939,9 @@ def main():
         }
         if coll is not None:
             out["collective"] = coll
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(batch, fmt, max(1, min(a.cpu_frames, a.frames)))
-        if world == 1 and not a.no_other_configs:
+        if a.full and world == 1 and not a.no_other_configs:
             out["other_configs"] = other_configs(lib, stream)
         print(json.dumps(out), flush=True)
     if multi:

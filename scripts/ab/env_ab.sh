@@ -3,7 +3,7 @@
 #   SETTINGS="HIP_FORCE_DEV_KERNARG=0 HIP_FORCE_DEV_KERNARG=1" bash scripts/ab/env_ab.sh
 for round in $(seq 1 ${ROUNDS:-4}); do
 for v in ${SETTINGS:-HIP_FORCE_DEV_KERNARG=0 HIP_FORCE_DEV_KERNARG=1}; do
-  env $v python bench.py --steps ${STEPS:-100} --warmup 5 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', d['value'], d['kernels']['generate']['avg_launch_ms'], d['kernels']['apply']['avg_launch_ms'], d['fixed_batch']['value'], d['cold_start']['value'])"
+  env $v python bench.py --full --steps ${STEPS:-100} --warmup 5 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', d['value'], d['kernels']['generate']['avg_launch_ms'], d['kernels']['apply']['avg_launch_ms'], d['fixed_batch']['value'], d['cold_start']['value'])"
 done
 done | tee /tmp/env_ab_runs.txt
 python - <<'PY'

@@ -6,5 +6,5 @@ for knobs in "A=shipped" "UHDR_X_MINBLK=900" "UHDR_X_MINBLK=1800" "UHDR_X_MINBLK
   echo -n "$knobs  "; env $knobs python scripts/time_single_formats.py 2>/dev/null
 done; done
 echo "--no-stats:"; unset UHDR_HIP_LIB
-python bench.py --steps 60 --no-cpu-baseline --no-other-configs --no-stats 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('no-stats', d['value'], d['kernels']['generate']['avg_launch_ms'], d['kernels']['apply']['avg_launch_ms'])"
-python bench.py --steps 60 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('stats   ', d['value'], d['kernels']['generate']['avg_launch_ms'], d['kernels']['apply']['avg_launch_ms'])"
+python bench.py --full --steps 60 --no-cpu-baseline --no-other-configs --no-stats 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('no-stats', d['value'], d['kernels']['generate']['avg_launch_ms'], d['kernels']['apply']['avg_launch_ms'])"
+python bench.py --full --steps 60 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('stats   ', d['value'], d['kernels']['generate']['avg_launch_ms'], d['kernels']['apply']['avg_launch_ms'])"

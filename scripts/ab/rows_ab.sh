@@ -3,7 +3,7 @@
 # 2 rows with the images of the launch interleaved): value, generate ms, apply ms per run, medians at the end.
 for round in $(seq 1 ${ROUNDS:-3}); do
 for v in ${POLICIES:-0 1 2}; do
-  UHDR_HIP_APPLY_ROWS=$v python bench.py --steps ${STEPS:-60} --warmup 5 --no-cpu-baseline --no-other-configs $EXTRA 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('rows=$v', d['value'], d['kernels']['generate']['avg_launch_ms'], d['kernels']['apply']['avg_launch_ms'], d['fixed_batch']['value'], d['cold_start']['value'])"
+  UHDR_HIP_APPLY_ROWS=$v python bench.py --full --steps ${STEPS:-60} --warmup 5 --no-cpu-baseline --no-other-configs $EXTRA 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('rows=$v', d['value'], d['kernels']['generate']['avg_launch_ms'], d['kernels']['apply']['avg_launch_ms'], d['fixed_batch']['value'], d['cold_start']['value'])"
 done
 done | tee /tmp/rows_ab.txt
 python - <<'PY'

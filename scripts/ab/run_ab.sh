@@ -4,7 +4,7 @@
 V=${VARIANTS:-A B}
 for round in $(seq 1 ${ROUNDS:-3}); do
 for v in $V; do
-  UHDR_HIP_LIB=$PWD/scripts/ab/libvar_$v.so python bench.py --steps ${STEPS:-50} --warmup 5 --no-cpu-baseline --no-other-configs $EXTRA 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', d['value'], d['kernels']['generate']['avg_launch_ms'], d['kernels']['apply']['avg_launch_ms'], d['cold_start']['value'])"
+  UHDR_HIP_LIB=$PWD/scripts/ab/libvar_$v.so python bench.py --full --steps ${STEPS:-50} --warmup 5 --no-cpu-baseline --no-other-configs $EXTRA 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$v', d['value'], d['kernels']['generate']['avg_launch_ms'], d['kernels']['apply']['avg_launch_ms'], d['cold_start']['value'])"
 done
 done | tee /tmp/ab_runs.txt
 python - <<'PY'

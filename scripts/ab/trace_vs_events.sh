@@ -6,7 +6,7 @@ P='import json,sys
 for l in sys.stdin:
     if l.startswith("{"):
         d=json.loads(l); print(sys.argv[1], "value", d["value"], "ms_per_step", d["ms_per_step"], "generate", d["kernels"]["generate"]["avg_launch_ms"], "apply", d["kernels"]["apply"]["avg_launch_ms"])'
-ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-other-configs"
+ARGS="--full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs"
 python3 $R/bench.py $ARGS 2>/dev/null | python3 -c "$P" plain
 OUT=/tmp/tve_$$; rm -rf $OUT; mkdir -p $OUT
 ( cd /tmp && TMPDIR=/tmp rocprofv3 --kernel-trace --output-format csv -d $OUT -- python3 $R/bench.py $ARGS > $OUT/log 2>&1 )

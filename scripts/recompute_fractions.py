@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Every fraction of the bench line, recomputed from files of ONE box:
     python scripts/recompute_fractions.py gpurun_out/bench_TAG.json gpurun_out/prof_TAG.json
-bench_TAG.json: the plain `python bench.py` line; prof_TAG.json: scripts/profile_bench.sh's summary of the same box (kernel trace of
+bench_TAG.json: the `python bench.py --full` line; prof_TAG.json: scripts/profile_bench.sh's summary of the same box (kernel trace of
 `bench.py --steps 20 --warmup 5`, the JSON line that traced process printed, the PMC passes)."""
 import json
 import sys

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -65,3 +67,37 @@ def test_single_rank_dry_run_and_gpus_mismatch():
     # under torch.distributed.run the flag has to agree with the number of ranks that were started
     r = _run(["--gpus", "4", "--dry-run"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "--gpus 4" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_line_and_dumped_outputs(orc, tmp_path):
+    """a plain run (no --full) prints the headline fields and none of the --full extras; --dump-outputs writes the last timed step's
+    outputs -- here W + K = 4 steps over 2 batches end on batch 1 (seeds 1234 + 65536 + i) -- as float32 / float64 samples that
+    match the CPU oracle on that batch's first frame: map bytes bit-exact, 1010102 fields within 1 LSB"""
+    import numpy as np
+    from libultrahdr_dev_amd import api, sharding
+    d = tmp_path / "dump"
+    r = _run(["--frames", "2", "--rotate", "2", "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--dump-outputs", str(d)], timeout=600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "MPix/s" and line["higher_is_better"] is True
+    assert line["dtype"] and line["metric"].startswith("MPixels/sec")
+    assert line["cold_start"] is None and line["fixed_batch"] is None and line["placement"]["hipmalloc"] is None
+    assert "cpu_baseline" not in line and "other_configs" not in line and line["kernels"]["generate"] is None
+    arrs = {n[:-4]: np.load(os.path.join(d, n)) for n in os.listdir(d)}
+    assert sorted(arrs) == ["content_minmax", "gain_map", "metadata", "rgba1010102"]
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) < 64 << 20
+    import bench
+    W, H = bench.W, bench.H
+    assert arrs["gain_map"].shape == (2, bench.MAP_SAMPLES) and arrs["rgba1010102"].shape == (2, bench.OUT_SAMPLES, 4)
+    rng = np.random.default_rng(bench.DUMP_SEED)
+    mpos = np.sort(rng.choice((W // 4) * (H // 4), bench.MAP_SAMPLES, replace=False))
+    ppos = np.sort(rng.choice(W * H, bench.OUT_SAMPLES, replace=False))
+    p010, yuv = orc.lcg_frame(W, H, sharding.image_seed(65536))
+    yi, pi = orc.yuv420_image(yuv, W, H, orc.CG_BT709), orc.p010_image(p010, W, H, orc.CG_BT2100)
+    st, omap, omd = orc.generate("orc_", yi, pi, orc.TF_HLG)
+    assert st == 0 and np.array_equal(arrs["gain_map"][0], omap.ravel()[mpos])
+    st, ref, _ = orc.apply("orc_", yi, omap, omd, orc.OUT_HDR_HLG, api.FLT_MAX)
+    ref = ref.view("<u4")[ppos]
+    want = np.stack([ref & 0x3ff, (ref >> 10) & 0x3ff, (ref >> 20) & 0x3ff, ref >> 30], axis=-1).astype(np.int64)
+    assert st == 0 and np.abs(arrs["rgba1010102"][0].astype(np.int64) - want).max() <= 1

@@ -133,7 +133,8 @@ def test_bench_takes_the_c_library_path_with_comm_capi():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "4", "--steps", "3", "--warmup", "1", "--ramp-ms", "0", "--rotate", "2",
-                        "--exchange-with-one-rank", "--comm", "capi", "--no-cpu-baseline", "--no-other-configs"], capture_output=True, text=True, env=env, timeout=600)
+                        "--exchange-with-one-rank", "--comm", "capi", "--full", "--no-cpu-baseline", "--no-other-configs"], capture_output=True, text=True, env=env,
+                       timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     c = d["collective"]
