@@ -377,6 +377,18 @@ int uhdr_hip_jpegr_encode_api0(const uhdr_hip_image_t* p010_image, int hdr_tf, i
 int uhdr_hip_jpegr_encode_api1(const uhdr_hip_image_t* p010_image, const uhdr_hip_image_t* yuv420_image, int hdr_tf, int quality,
                                const void* exif, size_t exif_size, void* out, size_t out_capacity, size_t* out_size, int mem_space,
                                void* stream);
+/* encodeJPEGR API-1 (yuv420_images != NULL) or API-0 (yuv420_images == NULL) for n pairs in one call (no reference
+ * counterpart).  Arrays are indexed by file; out[i] (HOST memory) receives file i, out_size[i] its size.  Every file's status,
+ * size and bytes are those of the single call with the same arguments (ERROR_INSUFFICIENT_RESOURCE with the exact size included);
+ * status (optional) receives them, the return value is the first one that is not NO_ERROR.  hdr_tf and quality are shared; gamuts
+ * and sizes may differ per file.  exif == NULL: no file has EXIF (exif[i] / exif_size[i] otherwise, host memory).  Call-level
+ * errors, before any file is looked at: n < 0, a NULL array where n > 0, a quality outside 0..100.  A file that fails its checks
+ * is not processed and does not disturb the others.  Planes in mem_space; host planes are staged to the device first.  The files'
+ * toneMap / generate / convertYuv and all 2 n JPEG compressions share their kernel launches, one synchronisation per round of up
+ * to 64 files. */
+int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf,
+                                int quality, const void* const* exif, const size_t* exif_size, void* const* out,
+                                const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream);
 int uhdr_hip_jpegr_encode_api2(const uhdr_hip_image_t* p010_image, const uhdr_hip_image_t* yuv420_image, const void* sdr_jpeg,
                                size_t sdr_jpeg_size, int sdr_jpeg_gamut, int hdr_tf, void* out, size_t out_capacity,
                                size_t* out_size, int mem_space, void* stream);

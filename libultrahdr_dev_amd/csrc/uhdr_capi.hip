@@ -13,6 +13,7 @@
 #include <chrono>
 #include <mutex>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "../../include/uhdr_hip.h"
@@ -57,6 +58,9 @@ struct DeviceState : StageSet {
   // uhdr_hip_jpegr_decode[_batch]: per-file decoder workspaces and planes
   std::vector<void*> pool;
   std::vector<size_t> pool_bytes;
+  // uhdr_hip_jpegr_encode_batch: page-locked host memory the compressed streams land in (grow-only)
+  void* host_pool = nullptr;
+  size_t host_pool_bytes = 0;
   // encodeJPEGR: the gain-map JPEG is compressed on a stream of its own, next to the SDR image's conversion and compression
   hipStream_t aux = nullptr;
   hipEvent_t map_ready = nullptr;
@@ -960,6 +964,7 @@ int uhdr_hip_shutdown(void) {
     if (kv.second.aux) (void)hipStreamDestroy(kv.second.aux);
     for (auto& cx : kv.second.codec_sets) {   // the leased codec contexts (their tables are this state's: not freed here)
       for (void* q : cx->pool) if (q) (void)hipFree(q);
+      if (cx->host_pool) (void)hipHostFree(cx->host_pool);
       for (int i = 0; i < 14; ++i)
         if (cx->stage[i]) (void)hipFree(cx->stage[i]);
       if (cx->map_ready) (void)hipEventDestroy(cx->map_ready);
@@ -1760,6 +1765,221 @@ int resolve_gainmap_jpeg(const EncodeCtx& c, size_t* n) {
   return jpeg_collect(c, pending_gainmap(), n) == UHDR_HIP_NO_ERROR ? UHDR_HIP_NO_ERROR : UHDR_HIP_ERROR_ENCODE_ERROR;
 }
 
+
+// ---- encodeJPEGR for n files (uhdr_hip_jpegr_encode_batch) ---------------------------------------------------------------------
+// Files go through in rounds of up to kEncRound (2 JPEGs each: the batched encoder's job limit); every device buffer of a round is
+// a slice of one grow-only pool slot of the leased context, the compressed streams land in its page-locked host pool.
+constexpr int kEncRound = jpeg::kMaxBatchJobs / 2;
+enum : size_t { kEncWs = 0, kEncDesc, kEncSdr, kEncMap, kEncP010, kEncYuv };
+
+int host_pool_reserve(DeviceState* st, size_t bytes) {
+  if (st->host_pool_bytes >= bytes) return UHDR_HIP_NO_ERROR;
+  if (st->host_pool) HIP_TRY(hipHostFree(st->host_pool));
+  st->host_pool = nullptr;
+  st->host_pool_bytes = 0;
+  HIP_TRY(hipHostMalloc(&st->host_pool, bytes, hipHostMallocDefault));
+  st->host_pool_bytes = bytes;
+  return UHDR_HIP_NO_ERROR;
+}
+
+struct EncFile {
+  int idx = 0;                 // the caller's index
+  uhdr_hip_image_t p010, yuv;  // defaulted (yuv: API-1 only); device planes once staged
+  uhdr_hip_image_t caller_yuv; // API-1: the caller's SDR planes as given (a P3 image is compressed from them)
+  uhdr_hip_image_t enc, map;   // the planes the two JPEGs compress (device)
+  size_t pad_ls = 0, pad_cs = 0;   // the strides that decide the encoder's column padding (the caller's for a P3 image)
+  bool own_copy = false;       // enc is a private zero-padded copy with 16-aligned strides
+  std::vector<uint8_t> icc;
+  size_t sdr_off = 0, sdr_cap = 0, gm_off = 0, gm_cap = 0;
+  std::vector<uint8_t> sdr_big, gm_big;   // a stream that outgrew its staging, compressed again on its own
+  const uint8_t* sdr = nullptr;
+  const uint8_t* gm = nullptr;
+  size_t sdr_n = 0, gm_n = 0;
+};
+
+// the encoder job of one image, as jpeg_enqueue_device builds it; ls / cs: the strides that decide the padding
+jpeg::Job batch_job(const uhdr_hip_image_t& img, int q, size_t pad_ls, size_t pad_cs) {
+  const bool gray = img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
+  const size_t w = img.width, h = img.height, aw = (w + 15) / 16 * 16, acw = (w / 2 + 7) / 8 * 8;
+  jpeg::Job j;
+  encode_job_tables(w, h, gray, q, &j);
+  const uint8_t* py = static_cast<const uint8_t*>(img.data);
+  j.plane[0] = encode_plane(py, w, h, img.luma_stride, pad_ls < aw);
+  if (!gray) {
+    const uint8_t* pu = static_cast<const uint8_t*>(img.chroma_data);
+    const size_t cs = img.chroma_stride;
+    j.plane[1] = encode_plane(pu, w / 2, h / 2, cs, pad_cs < acw);
+    j.plane[2] = encode_plane(pu + cs * (h / 2), w / 2, h / 2, cs, pad_cs < acw);
+  }
+  return j;
+}
+
+// One round: staging (host callers), toneMap (API-0), generateGainMap, BT.601 re-encode, the 2 m compressions -- one launch per
+// step for the round's files -- then one synchronisation.  Leaves each file's two JPEGs in f[k].sdr / f[k].gm.  A non-zero return
+// is an error of the device or the runtime (every file of the round fails with it).
+int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_tf, int quality, EncFile* f, int m, uhdr_hip_metadata_t* md) {
+  auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
+  int rc;
+  // sizes of the round's slices
+  size_t ws_total = 0, sdr_total = 0, map_total = 0, p010_total = 0, yuv_total = 0, hp_total = al256(jpeg::batch_desc_bytes(2 * m)) + al256(16 * (size_t)m);
+  std::vector<jpeg::Job> jobs(2 * (size_t)m);
+  std::vector<jpeg::Layout> lay(2 * (size_t)m);
+  std::vector<size_t> ws_off(2 * (size_t)m);
+  for (int k = 0; k < m; ++k) {
+    const size_t w = f[k].p010.width, h = f[k].p010.height, aw = (w + 15) / 16 * 16, mw = w / 4, mh = h / 4;
+    if (host) {
+      p010_total += al256(round_up(w, 64) * h * 2) + al256(round_up(w, 64) * (h / 2) * 2);
+      if (!api0) yuv_total += al256(round_up(aw, 64) * h) + al256(round_up(aw, 64) * h);
+    }
+    if (f[k].own_copy) sdr_total += al256(aw * h * 3 / 2 + 64);
+    map_total += al256(mw * mh + 64);
+    f[k].sdr_cap = w * h + 65536;   // the first guesses of the single calls
+    f[k].gm_cap = mw * mh + 65536;
+    f[k].sdr_off = hp_total; hp_total += al256(f[k].sdr_cap);
+    f[k].gm_off = hp_total; hp_total += al256(f[k].gm_cap);
+  }
+  if ((rc = host_pool_reserve(st, hp_total)) != 0) return rc;
+  if ((rc = pool_reserve(st, kEncMap, map_total)) != 0) return rc;
+  if (sdr_total && (rc = pool_reserve(st, kEncSdr, sdr_total)) != 0) return rc;
+  if (p010_total && (rc = pool_reserve(st, kEncP010, p010_total)) != 0) return rc;
+  if (yuv_total && (rc = pool_reserve(st, kEncYuv, yuv_total)) != 0) return rc;
+  uint8_t* hp = static_cast<uint8_t*>(st->host_pool);
+  uint8_t* hdesc = hp;
+  uint64_t* sizes = reinterpret_cast<uint64_t*>(hp + al256(jpeg::batch_desc_bytes(2 * m)));
+
+  // planes: staged inputs (host callers), private copies, maps
+  size_t o_p010 = 0, o_yuv = 0, o_sdr = 0, o_map = 0;
+  for (int k = 0; k < m; ++k) {
+    EncFile& e = f[k];
+    const size_t w = e.p010.width, h = e.p010.height, aw = (w + 15) / 16 * 16, acw = (w / 2 + 7) / 8 * 8;
+    if (host) {   // the same bytes the single calls stage
+      uint8_t* d = static_cast<uint8_t*>(st->pool[kEncP010]) + o_p010;
+      const size_t lp = round_up(w, 64), cp = round_up(w, 64);
+      if ((rc = h2d_plane(d, lp, e.p010.data, e.p010.luma_stride, w, h, 2, s)) != 0) return rc;
+      uint8_t* dc = d + al256(lp * h * 2);
+      if ((rc = h2d_plane(dc, cp, e.p010.chroma_data, e.p010.chroma_stride, w, h / 2, 2, s)) != 0) return rc;
+      o_p010 += al256(lp * h * 2) + al256(cp * (h / 2) * 2);
+      e.p010.data = d; e.p010.chroma_data = dc; e.p010.luma_stride = lp; e.p010.chroma_stride = cp;
+      if (!api0) {
+        const size_t ls = e.yuv.luma_stride, cs = e.yuv.chroma_stride;
+        const size_t ycols = ls < aw ? w : aw, ccols = cs < acw ? w / 2 : acw, dls = round_up(ycols, 64), dcs = round_up(ccols, 64);
+        uint8_t* y = static_cast<uint8_t*>(st->pool[kEncYuv]) + o_yuv;
+        uint8_t* u = y + al256(dls * h);
+        const uint8_t* hu = static_cast<const uint8_t*>(e.yuv.chroma_data);
+        if ((rc = h2d_plane(y, dls, e.yuv.data, ls, ycols, h, 1, s)) != 0) return rc;
+        if ((rc = h2d_plane(u, dcs, hu, cs, ccols, h / 2, 1, s)) != 0) return rc;
+        if ((rc = h2d_plane(u + dcs * (h / 2), dcs, hu + cs * (h / 2), cs, ccols, h / 2, 1, s)) != 0) return rc;
+        o_yuv += al256(round_up(aw, 64) * h) + al256(round_up(aw, 64) * h);
+        e.yuv.data = y; e.yuv.chroma_data = u; e.yuv.luma_stride = dls; e.yuv.chroma_stride = dcs;
+      }
+    }
+    if (e.own_copy) {   // 16-aligned strides, zero padded (a width of whole 16-column batches has no padding: the kernels write it all)
+      uint8_t* d = static_cast<uint8_t*>(st->pool[kEncSdr]) + o_sdr;
+      o_sdr += al256(aw * h * 3 / 2 + 64);
+      if (aw != w) HIP_TRY(hipMemsetAsync(d, 0, aw * h * 3 / 2, s));
+      memset(&e.enc, 0, sizeof(e.enc));
+      e.enc.data = d; e.enc.chroma_data = d + aw * h; e.enc.width = w; e.enc.height = h;
+      e.enc.luma_stride = aw; e.enc.chroma_stride = aw >> 1; e.enc.pixelFormat = UHDR_HIP_PIX_FMT_YUV420;
+      e.enc.colorGamut = api0 ? e.p010.colorGamut : e.yuv.colorGamut;
+      e.pad_ls = aw; e.pad_cs = aw >> 1;
+    } else {
+      e.enc = e.yuv;   // P3: compressed as it is, padded by the caller's strides
+      e.pad_ls = e.caller_yuv.luma_stride; e.pad_cs = e.caller_yuv.chroma_stride;
+    }
+    if (api0) e.yuv = e.enc;
+    e.map = e.yuv;
+    e.map.data = static_cast<uint8_t*>(st->pool[kEncMap]) + o_map;
+    o_map += al256((w / 4) * (h / 4) + 64);
+  }
+  std::vector<uhdr_hip_image_t> a((size_t)m), b((size_t)m), c((size_t)m);
+  if (api0) {   // :208-226
+    for (int k = 0; k < m; ++k) { a[k] = f[k].p010; b[k] = f[k].enc; }
+    if ((rc = uhdr_hip_tonemap_batch(m, a.data(), b.data(), s)) != UHDR_HIP_NO_ERROR) return rc;
+  }
+  // generateGainMap: the files are sorted by size and gamuts, so equal ones share its launches
+  for (int k = 0; k < m; ++k) { a[k] = f[k].yuv; b[k] = f[k].p010; c[k] = f[k].map; }
+  if ((rc = uhdr_hip_generate_gainmap_batch(m, a.data(), b.data(), hdr_tf, md, c.data(), 0, nullptr, s)) != UHDR_HIP_NO_ERROR) return rc;
+  // convertYuv to BT.601 unless P3: API-0 in place, API-1 into the private copy; equal sizes and gamuts share a launch
+  for (int k = 0; k < m;) {
+    if (f[k].enc.colorGamut == UHDR_HIP_CG_P3) { ++k; continue; }
+    CvtBatch cb;
+    bool aligned = true;
+    int cnt = 0;
+    while (k + cnt < m && cnt < kToneChunk) {
+      const EncFile& e = f[k + cnt];
+      if (e.enc.colorGamut != f[k].enc.colorGamut || e.enc.width != f[k].enc.width || e.enc.height != f[k].enc.height) break;
+      bool al_;
+      const CvtImage t = cvt_image(api0 ? e.enc : e.yuv, e.enc, yuv_matrix(e.enc.colorGamut, UHDR_HIP_CG_P3), &al_);
+      if (cnt == 0) aligned = al_;
+      else if (al_ != aligned) break;
+      cb.img[cnt++] = t;
+    }
+    HIP_TRY(launch_convert_yuv(cb, cnt, aligned, s));
+    k += cnt;
+  }
+  // the 2 m compressions: headers written into the page-locked staging, the streams behind them by the kernels
+  std::vector<jpeg::BatchOut> outs(2 * (size_t)m);
+  std::vector<uint8_t*> wss(2 * (size_t)m);
+  std::vector<uint8_t> header;
+  for (int k = 0; k < m; ++k) {
+    EncFile& e = f[k];
+    uhdr_hip_image_t g = e.map;
+    g.width = e.enc.width / 4; g.height = e.enc.height / 4; g.luma_stride = g.width;
+    g.chroma_data = nullptr; g.chroma_stride = 0; g.pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
+    e.map = g;
+    jobs[2 * k] = batch_job(e.enc, quality, e.pad_ls, e.pad_cs);
+    jobs[2 * k + 1] = batch_job(g, 85, g.luma_stride, 0);   // compressGainMap: kMapCompressQuality (jpegr.cpp:806-821)
+    for (int t = 0; t < 2; ++t) {
+      const size_t jk = 2 * (size_t)k + t;
+      const uhdr_hip_image_t& im = t == 0 ? e.enc : g;
+      jpeg::build_header((int)im.width, (int)im.height, t == 1, t == 0 ? quality : 85, t == 0 ? e.icc.data() : nullptr, t == 0 ? e.icc.size() : 0,
+                         header);
+      uint8_t* dst = hp + (t == 0 ? e.sdr_off : e.gm_off);
+      memcpy(dst, header.data(), header.size());
+      sizes[jk] = 0;
+      outs[jk] = jpeg::BatchOut{dst, t == 0 ? e.sdr_cap : e.gm_cap, header.size(), &sizes[jk]};
+      ws_off[jk] = ws_total;
+      ws_total += al256(jpeg::workspace_bytes(jobs[jk].nblk, &lay[jk]));
+    }
+  }
+  if ((rc = pool_reserve(st, kEncWs, ws_total)) != 0) return rc;
+  if ((rc = pool_reserve(st, kEncDesc, jpeg::batch_desc_bytes(2 * m))) != 0) return rc;
+  for (size_t jk = 0; jk < wss.size(); ++jk) wss[jk] = static_cast<uint8_t*>(st->pool[kEncWs]) + ws_off[jk];
+  HIP_TRY(jpeg::encode_batch_async(2 * m, jobs.data(), lay.data(), wss.data(), outs.data(), hdesc, static_cast<uint8_t*>(st->pool[kEncDesc]), s));
+  HIP_TRY(hipStreamSynchronize(s));
+
+  // a stream larger than its staging was cut off: that image is compressed again on its own (as jpeg_collect does)
+  for (int k = 0; k < m; ++k) {
+    EncFile& e = f[k];
+    for (int t = 0; t < 2; ++t) {
+      const uint64_t total = sizes[2 * (size_t)k + t];
+      if (total == 0) return UHDR_HIP_ERROR_ENCODE_ERROR;
+      const size_t cap = t == 0 ? e.sdr_cap : e.gm_cap;
+      uint8_t* at = hp + (t == 0 ? e.sdr_off : e.gm_off);
+      if (total <= cap) {
+        (t == 0 ? e.sdr : e.gm) = at;
+        (t == 0 ? e.sdr_n : e.gm_n) = (size_t)total;
+        continue;
+      }
+      // the compression again: a P3 image of a host caller from its own planes (the single call's staging and padding)
+      const bool from_caller = t == 0 && !e.own_copy && host;
+      EncodeCtx ctx{st, s, from_caller ? UHDR_HIP_MEM_HOST : UHDR_HIP_MEM_DEVICE};
+      const uhdr_hip_image_t& im = t == 0 ? (from_caller ? e.caller_yuv : e.enc) : e.map;
+      HostBytes tmp;
+      tmp.resize((size_t)total + 16);
+      size_t n2 = 0;
+      std::vector<uint8_t> icc_copy = e.icc;
+      const int r = jpeg_to_host(ctx, im, t == 0 ? quality : 85, t == 0 ? &icc_copy : nullptr, tmp, &n2);
+      if (r == UHDR_HIP_NO_ERROR) (t == 0 ? e.sdr_big : e.gm_big).assign(tmp.data(), tmp.data() + n2);
+      if (tmp.p) (void)hipHostFree(tmp.p);
+      if (r != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
+      (t == 0 ? e.sdr : e.gm) = (t == 0 ? e.sdr_big : e.gm_big).data();
+      (t == 0 ? e.sdr_n : e.gm_n) = n2;
+    }
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1855,6 +2075,92 @@ int uhdr_hip_jpegr_encode_api1(const uhdr_hip_image_t* p010_in, const uhdr_hip_i
     enc.chroma_data = static_cast<uint8_t*>(enc.data) + ls * h;
   }
   return finish_from_planes(c, enc, quality, exif, exif_size, gm_jpeg, gm_n, md, out, out_capacity, out_size, converted);
+}
+
+// encodeJPEGR API-1 (yuv420_images != NULL) or API-0 for n pairs in one call: the files' kernels share their launches, the call
+// synchronises once per round of up to kEncRound files, and the containers are assembled by a few host threads
+int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                                const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
+                                int* status, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
+  const bool api0 = yuv420_images == nullptr;
+  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
+  std::vector<EncFile> files;
+  for (int i = 0; i < n; ++i) {   // the single call's checks, in its order; a file that fails them is not processed
+    const void* ex = exif ? exif[i] : nullptr;
+    const size_t exn = exif ? exif_size[i] : 0;
+    int rc = check_encode_inputs(&p010_images[i], api0 ? nullptr : &yuv420_images[i], hdr_tf, out[i], &out_size[i]);
+    if (rc == UHDR_HIP_NO_ERROR && ex == nullptr && exn != 0) rc = UHDR_HIP_ERROR_BAD_PTR;                     // :190-193 / :258-261
+    if (rc != UHDR_HIP_NO_ERROR) { st_[i] = rc; continue; }
+    EncFile e;
+    e.idx = i;
+    e.p010 = p010_images[i];
+    default_p010(&e.p010);
+    memset(&e.yuv, 0, sizeof(e.yuv));
+    if (!api0) { e.yuv = yuv420_images[i]; default_yuv(&e.yuv); }
+    e.caller_yuv = e.yuv;
+    const int sdr_gamut = api0 ? e.p010.colorGamut : e.yuv.colorGamut;
+    e.own_copy = api0 || sdr_gamut != UHDR_HIP_CG_P3;
+    if (!jpegr::icc_profile_srgb_transfer(sdr_gamut, e.icc)) { st_[i] = UHDR_HIP_ERROR_INVALID_COLORGAMUT; continue; }
+    files.push_back(std::move(e));
+  }
+  auto result = [&]() {
+    int first = UHDR_HIP_NO_ERROR;
+    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
+    return first;
+  };
+  if (files.empty()) return result();
+  DeviceState* st = nullptr;
+  int rc = current_state(&st);
+  if (rc == UHDR_HIP_NO_ERROR) {
+    CodecLease lease(st);
+    st = lease.get();
+    rc = st == nullptr ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // runs of equal size and gamuts, whatever the caller's order: equal files share the launches of toneMap, generate and convertYuv
+    auto key = [&](const EncFile& e) {
+      return std::make_tuple(e.p010.width, e.p010.height, api0 ? e.p010.colorGamut : e.yuv.colorGamut, e.p010.colorGamut);
+    };
+    std::stable_sort(files.begin(), files.end(), [&](const EncFile& x, const EncFile& y) { return key(x) < key(y); });
+    struct SyncOnExit {   // an error half-way through a round must not leave kernels writing into the pools
+      hipStream_t s;
+      ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+    } sync_on_exit{s};
+    size_t r0 = 0;   // files [0, r0) are finished
+    for (; rc == UHDR_HIP_NO_ERROR && r0 < files.size(); r0 += kEncRound) {
+      const int m = (int)std::min(files.size() - r0, (size_t)kEncRound);
+      EncFile* f = &files[r0];
+      uhdr_hip_metadata_t md;
+      rc = encode_round(st, s, api0, mem_space != UHDR_HIP_MEM_DEVICE, hdr_tf, quality, f, m, &md);
+      if (rc != UHDR_HIP_NO_ERROR) break;
+      // appendGainMap (jpegr.cpp:951-1130) straight into the caller's buffers, a few host threads side by side
+      auto assemble = [&](int lo, int hi) {
+        for (int k = lo; k < hi; ++k) {
+          const EncFile& e = f[k];
+          const int i = e.idx;
+          st_[i] = jpegr::append_gainmap_to(e.sdr, e.sdr_n, e.gm, e.gm_n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
+                                            nullptr, 0, md, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i]);
+        }
+      };
+      const int nthreads = m >= 2 ? std::min(m, 8) : 1;
+      if (nthreads <= 1) {
+        assemble(0, m);
+      } else {
+        std::vector<std::thread> workers;
+        for (int t = 0; t < nthreads; ++t) workers.emplace_back(assemble, (int)((long)m * t / nthreads), (int)((long)m * (t + 1) / nthreads));
+        for (auto& w : workers) w.join();
+      }
+      for (int k = 0; k < m; ++k) { std::vector<uint8_t>().swap(f[k].sdr_big); std::vector<uint8_t>().swap(f[k].gm_big); }
+    }
+    if (rc != UHDR_HIP_NO_ERROR)   // the files of the failed round and of those behind it
+      for (size_t k = r0; k < files.size(); ++k) st_[files[k].idx] = rc;
+    return result();
+  }
+  for (const EncFile& e : files) st_[e.idx] = rc;
+  return result();
 }
 
 // JpegR::encodeJPEGR API-4 (jpegr.cpp:502-560): host bytes only, nothing runs on the device

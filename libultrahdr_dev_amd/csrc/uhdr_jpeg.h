@@ -48,6 +48,21 @@ size_t workspace_bytes(uint32_t nblk, Layout* l);
 hipError_t encode_async(Job j, const Layout& l, uint8_t* ws, uint8_t* out, uint64_t out_cap, uint64_t header_len, hipStream_t s,
                         uint64_t* out_size = nullptr);
 
+// ---- batched encoder: n JPEGs, one launch per encoder step for all of them ----------------------------------------------
+constexpr int kMaxBatchJobs = 128;      // jobs per encode_batch_async (their starts are searched in LDS)
+constexpr uint32_t kStuffWgPerJob = 64; // byte-stuffing workgroups per job; they stride over the stream's 16 KiB pieces
+struct BatchOut {                       // where job k's JPEG goes: header at out[0, header_len) written by the caller
+  uint8_t* out;                         // device-accessible (device or page-locked host memory)
+  uint64_t out_cap, header_len;
+  uint64_t* out_size;                   // the file's size, header included (device-accessible)
+};
+size_t batch_desc_bytes(int n);
+// jobs: tables, geometry and planes as for encode_async; job k works in ws[k] (workspace_bytes(jobs[k].nblk, &l[k]) bytes).  The
+// descriptors are assembled in host_desc (page-locked, batch_desc_bytes(n); not to be touched until the stream has passed this
+// point) and copied to dev_desc (device, the same size).  n <= kMaxBatchJobs.
+hipError_t encode_batch_async(int n, const Job* jobs, const Layout* l, uint8_t* const* ws, const BatchOut* outs, uint8_t* host_desc,
+                              uint8_t* dev_desc, hipStream_t s);
+
 // ---- decoder (uhdr_jpeg_dec.hip) -------------------------------------------------------------------------------------
 struct HuffSpec {            // one DHT table in canonical form (T.81 Annex C)
   uint16_t first_code[17];   // first code of each length (index = length)

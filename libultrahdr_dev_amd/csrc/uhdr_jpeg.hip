@@ -319,16 +319,18 @@ __device__ __forceinline__ int comp_of(const Job& j, uint32_t i) { return j.gray
 // the quantised DC of the component's previous block, which another thread computes: the islow DC is the plain sum of the 64
 // level-shifted samples (pass 1 scales the row sums by 4, pass 2 descales by 4: exact), so it is had from that block's 64 bytes.
 __device__ __forceinline__ uint32_t fdct_quant_count_block(const Job& j, const uint32_t i);
-__global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count(const Job j) {
-  const uint32_t i = blockIdx.x * 128u + threadIdx.x;
+// workgroup wg of the image's grid (blockIdx.x of the single-image launch; the batched launch passes its workgroup inside the job)
+__device__ __forceinline__ void fdct_quant_count_wg(const Job& j, const uint32_t wg) {
+  const uint32_t i = wg * 128u + threadIdx.x;
   __shared__ uint32_t s_part[2];
   uint32_t my_bits = 0;
   if (i < j.nblk) my_bits = fdct_quant_count_block(j, i);
   // bits_blk[g]: the bits of workgroup g's 128 blocks.  k_jpeg_emit needs the bit offset of every block: inside a workgroup a block
   // scan, across workgroups the sum of the totals in front (a 4K frame has 1519), formed by every workgroup of the emit for itself
   const uint32_t total = block_sum<128>(my_bits, s_part);
-  if (threadIdx.x == 0u) j.bits_blk[blockIdx.x] = total;
+  if (threadIdx.x == 0u) j.bits_blk[wg] = total;
 }
+__global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count(const Job j) { fdct_quant_count_wg(j, blockIdx.x); }
 
 // the work of one thread of k_jpeg_fdct_quant_count: block i's coefficients to memory, its number of bits returned
 __device__ __forceinline__ uint32_t fdct_quant_count_block(const Job& j, const uint32_t i) {
@@ -411,12 +413,12 @@ struct EmitSink {
   }
 };
 
-__global__ void __launch_bounds__(128) k_jpeg_emit(const Job j) {
+__device__ __forceinline__ void emit_wg(const Job& j, const uint32_t wg) {
   __shared__ uint64_t s_part[2];
   __shared__ uint64_t s_base;
-  const uint32_t i = blockIdx.x * 128u + threadIdx.x;
+  const uint32_t i = wg * 128u + threadIdx.x;
   uint64_t before = 0;
-  for (uint32_t g = threadIdx.x; g < blockIdx.x; g += 128u) before += j.bits_blk[g];
+  for (uint32_t g = threadIdx.x; g < wg; g += 128u) before += j.bits_blk[g];
   before = block_sum<128>(before, s_part);
   if (threadIdx.x == 0u) s_base = before;
   __syncthreads();
@@ -440,18 +442,19 @@ __global__ void __launch_bounds__(128) k_jpeg_emit(const Job j) {
   }
   s.finish();
 }
+__global__ void __launch_bounds__(128) k_jpeg_emit(const Job j) { emit_wg(j, blockIdx.x); }
 
 // ---- byte stuffing -------------------------------------------------------------------------------------------------
 constexpr uint32_t kChunk = 64;
 // ff_count[t]: 0xFF bytes in chunk t; ff_blk[g]: in the 256 chunks of workgroup g.  The copy needs the number of stuffed zeros in
 // front of every chunk: inside a workgroup a block scan of 256 counts, across workgroups the sum of the totals in front, which
 // every workgroup of the copy forms for itself (a 4K frame has ~100 of them) -- no device-wide scan between the two kernels.
-__global__ void __launch_bounds__(256) k_jpeg_stuff_count(const Job j, const uint64_t* total_bits) {
+__device__ __forceinline__ void stuff_count_wg(const Job& j, const uint64_t* total_bits, const uint32_t wg) {
   __shared__ uint32_t s_part[4];
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t t = wg * 256u + threadIdx.x;
   const uint64_t nbytes = (*total_bits + 7u) >> 3;
   const uint64_t b0 = (uint64_t)t * kChunk;
-  if ((uint64_t)blockIdx.x * 256u * kChunk >= nbytes) return;   // uniform per workgroup: behind the end of the stream
+  if ((uint64_t)wg * 256u * kChunk >= nbytes) return;   // uniform per workgroup: behind the end of the stream
   uint32_t n = 0;
   if (t < j.max_chunks && b0 < nbytes) {
     const uint8_t* p = reinterpret_cast<const uint8_t*>(j.stream) + b0;
@@ -460,23 +463,24 @@ __global__ void __launch_bounds__(256) k_jpeg_stuff_count(const Job j, const uin
     j.ff_count[t] = n;
   }
   const uint32_t total = block_sum<256>(n, s_part);
-  if (threadIdx.x == 0u) j.ff_blk[blockIdx.x] = total;
+  if (threadIdx.x == 0u) j.ff_blk[wg] = total;
 }
+__global__ void __launch_bounds__(256) k_jpeg_stuff_count(const Job j, const uint64_t* total_bits) { stuff_count_wg(j, total_bits, blockIdx.x); }
 // One workgroup = 256 chunks = 16 KiB of the packed stream.  Every thread expands its chunk into LDS (0x00 after each
 // 0xFF), then the workgroup writes the expanded run to the output as aligned dwords: the run's start in the output is
 // arbitrary (header length + stuffed bytes before it), so a thread per chunk writing its own bytes would scatter byte
 // stores over 256 cache lines per instruction (28 us per 4K frame measured; this form: see DESIGN.md).
-__global__ void __launch_bounds__(256) k_jpeg_stuff_copy(const Job j, const uint64_t* total_bits, uint8_t* out, uint64_t out_cap,
-                                                         uint64_t header_len, uint64_t* out_size) {
+__device__ __forceinline__ void stuff_copy_wg(const Job& j, const uint64_t* total_bits, uint8_t* out, uint64_t out_cap, uint64_t header_len,
+                                              uint64_t* out_size, const uint32_t wg) {
   __shared__ uint32_t s_part[4];
   __shared__ uint8_t s_buf[256 * kChunk * 2 + 8];
   __shared__ uint32_t s_len, s_base;
-  const uint32_t first = blockIdx.x * 256u, t = first + threadIdx.x;
+  const uint32_t first = wg * 256u, t = first + threadIdx.x;
   const uint64_t nbytes = (*total_bits + 7u) >> 3;
   const uint64_t blk_b0 = (uint64_t)first * kChunk;
   if (blk_b0 >= nbytes) return;                       // uniform per workgroup
   uint32_t before = 0;
-  for (uint32_t g = threadIdx.x; g < blockIdx.x; g += 256u) before += j.ff_blk[g];
+  for (uint32_t g = threadIdx.x; g < wg; g += 256u) before += j.ff_blk[g];
   before = block_sum<256>(before, s_part);
   if (threadIdx.x == 0) { s_len = 0u; s_base = before; }
   __syncthreads();
@@ -522,6 +526,95 @@ __global__ void __launch_bounds__(256) k_jpeg_stuff_copy(const Job j, const uint
   const uint32_t tail0 = head_n + 4u * nwords;
   if (threadIdx.x < len - tail0 && dst0 + tail0 + threadIdx.x < out_cap) out[dst0 + tail0 + threadIdx.x] = s_buf[tail0 + threadIdx.x];
 }
+__global__ void __launch_bounds__(256) k_jpeg_stuff_copy(const Job j, const uint64_t* total_bits, uint8_t* out, uint64_t out_cap,
+                                                         uint64_t header_len, uint64_t* out_size) {
+  stuff_copy_wg(j, total_bits, out, out_cap, header_len, out_size, blockIdx.x);
+}
+
+// ---- batched form ---------------------------------------------------------------------------------------------------
+// All JPEGs of a call -- colour and grey, large and small -- share one launch per encoder step.  The grid is the concatenation of
+// the jobs' own grids: job k owns workgroups [start[k], start[k + 1]), so a gain map (64 workgroups at 4K) does not dispatch the
+// 1519 of its SDR image.  A Job is ~900 B, so the descriptors are read from device memory rather than the kernarg segment; the
+// per-workgroup bodies are the single-image kernels' own, so both forms write the same bytes.
+// The workgroup's job: the starts into LDS with one round of loads, a binary search there (<= 7 steps), the result made uniform.
+template <int NT>
+__device__ __forceinline__ uint32_t job_of(const uint32_t* __restrict__ start, uint32_t n, uint32_t* first, uint32_t* count) {
+  __shared__ uint32_t s_start[kMaxBatchJobs + 1];
+  for (uint32_t t = threadIdx.x; t <= n; t += NT) s_start[t] = start[t];
+  __syncthreads();
+  const uint32_t g = blockIdx.x;
+  uint32_t lo = 0, hi = n;   // s_start[lo] <= g < s_start[hi]
+  while (hi - lo > 1u) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (s_start[mid] <= g) lo = mid;
+    else hi = mid;
+  }
+  lo = __builtin_amdgcn_readfirstlane(lo);
+  *first = s_start[lo];
+  *count = s_start[lo + 1u] - s_start[lo];
+  return lo;
+}
+// the job's descriptor through the constant address space: its fields (the 128 quantisation entries and multipliers among them) are
+// read with scalar loads into SGPRs, as from the single-image kernels' kernarg segment, instead of into VGPRs
+template <class T>
+__device__ __forceinline__ const T& uniform_ref(const T* p, uint32_t k) {
+  return *(const T*)((const __attribute__((address_space(4))) T*)p + k);
+}
+
+__global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count_multi(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  fdct_quant_count_wg(uniform_ref(jobs, k), blockIdx.x - first);
+}
+
+// The single-image path clears the whole worst-case stream area (208 B per block, 40 MB for a 4K frame) before the emit ORs into
+// it.  Here every workgroup clears the words whose first bit falls into its own blocks' bit range [before, before + bits): over a
+// job's workgroups that is exactly the words [0, ceil(total_bits / 32)) the emit writes, the padding of the last byte included.
+__global__ void __launch_bounds__(128) k_jpeg_clear_multi(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint64_t s_part[2];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  const uint32_t wg = blockIdx.x - first;
+  uint64_t before = 0;
+  for (uint32_t g = threadIdx.x; g < wg; g += 128u) before += j.bits_blk[g];
+  before = block_sum<128>(before, s_part);
+  const uint64_t end = before + j.bits_blk[wg];
+  const uint64_t w1 = (end + 31u) >> 5;
+  for (uint64_t w = ((before + 31u) >> 5) + threadIdx.x; w < w1; w += 128u) j.stream[w] = 0u;
+}
+
+__global__ void __launch_bounds__(128) k_jpeg_emit_multi(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  emit_wg(uniform_ref(jobs, k), blockIdx.x - first);
+}
+
+// The stuffing grid of a job cannot be sized by its stream, which is only known on the device: each job gets up to
+// kStuffWgPerJob workgroups, and they walk the stream's 16 KiB pieces with that stride until its end.
+__global__ void __launch_bounds__(256) k_jpeg_stuff_count_multi(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<256>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  const uint64_t nbytes = (*j.total_bits + 7u) >> 3;
+  for (uint32_t wg = blockIdx.x - first; (uint64_t)wg * 256u * kChunk < nbytes; wg += count) {
+    stuff_count_wg(j, j.total_bits, wg);
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(256) k_jpeg_stuff_copy_multi(const Job* __restrict__ jobs, const BatchOut* __restrict__ outs,
+                                                               const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<256>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  const BatchOut& o = uniform_ref(outs, k);
+  const uint64_t nbytes = (*j.total_bits + 7u) >> 3;
+  for (uint32_t wg = blockIdx.x - first; (uint64_t)wg * 256u * kChunk < nbytes; wg += count) {
+    stuff_copy_wg(j, j.total_bits, o.out, o.out_cap, o.header_len, o.out_size, wg);
+    __syncthreads();   // (s_buf and s_len are the next piece's)
+  }
+}
 
 // ---- host side -----------------------------------------------------------------------------------------------------
 size_t workspace_bytes(uint32_t nblk, Layout* l) {
@@ -561,6 +654,56 @@ hipError_t encode_async(Job j, const Layout& l, uint8_t* ws, uint8_t* out, uint6
   const dim3 gc((j.max_chunks + 255u) / 256u), bc(256);
   hipLaunchKernelGGL(k_jpeg_stuff_count, gc, bc, 0, s, j, total_bits);
   hipLaunchKernelGGL(k_jpeg_stuff_copy, gc, bc, 0, s, j, total_bits, out, out_cap, header_len, out_size != nullptr ? out_size : totals + 1);
+  return hipGetLastError();
+}
+
+namespace {
+size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+}  // namespace
+
+size_t batch_desc_bytes(int n) {
+  return up256((size_t)n * sizeof(Job)) + up256((size_t)n * sizeof(BatchOut)) + 2 * up256(((size_t)n + 1) * 4);
+}
+
+hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_t* const* ws, const BatchOut* outs, uint8_t* host_desc,
+                              uint8_t* dev_desc, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (n > kMaxBatchJobs) return hipErrorInvalidValue;
+  Job* jobs = reinterpret_cast<Job*>(host_desc);
+  BatchOut* o = reinterpret_cast<BatchOut*>(host_desc + up256((size_t)n * sizeof(Job)));
+  uint32_t* blk_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(o) + up256((size_t)n * sizeof(BatchOut)));
+  uint32_t* stuff_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(blk_start) + up256(((size_t)n + 1) * 4));
+  blk_start[0] = stuff_start[0] = 0;
+  for (int k = 0; k < n; ++k) {
+    Job& j = jobs[k];
+    j = jobs_in[k];
+    uint8_t* w = ws[k];
+    j.coef = reinterpret_cast<int16_t*>(w + l[k].coef);
+    j.bits = reinterpret_cast<uint32_t*>(w + l[k].bits);
+    j.bits_blk = reinterpret_cast<uint32_t*>(w + l[k].bits_blk);
+    j.stream = reinterpret_cast<uint32_t*>(w + l[k].stream);
+    j.ff_count = reinterpret_cast<uint32_t*>(w + l[k].ff_count);
+    j.ff_blk = reinterpret_cast<uint32_t*>(w + l[k].ff_blk);
+    j.max_chunks = l[k].max_chunks;
+    j.total_bits = reinterpret_cast<uint64_t*>(w + l[k].totals);
+    o[k] = outs[k];
+    const uint32_t stuff_wgs = (j.max_chunks + 255u) / 256u;
+    blk_start[k + 1] = blk_start[k] + (j.nblk + 127u) / 128u;
+    stuff_start[k + 1] = stuff_start[k] + (stuff_wgs < kStuffWgPerJob ? stuff_wgs : kStuffWgPerJob);
+  }
+  hipError_t e;
+  if ((e = hipMemcpyAsync(dev_desc, host_desc, batch_desc_bytes(n), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  const Job* dj = reinterpret_cast<const Job*>(dev_desc);
+  const BatchOut* dout = reinterpret_cast<const BatchOut*>(dev_desc + (reinterpret_cast<uint8_t*>(o) - host_desc));
+  const uint32_t* dblk = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(blk_start) - host_desc));
+  const uint32_t* dstuff = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(stuff_start) - host_desc));
+  const uint32_t nj = (uint32_t)n;
+  const dim3 gb(blk_start[n]), bb(128), gc(stuff_start[n]), bc(256);
+  hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi, gb, bb, 0, s, dj, dblk, nj);
+  hipLaunchKernelGGL(k_jpeg_clear_multi, gb, bb, 0, s, dj, dblk, nj);
+  hipLaunchKernelGGL(k_jpeg_emit_multi, gb, bb, 0, s, dj, dblk, nj);
+  hipLaunchKernelGGL(k_jpeg_stuff_count_multi, gc, bc, 0, s, dj, dstuff, nj);
+  hipLaunchKernelGGL(k_jpeg_stuff_copy_multi, gc, bc, 0, s, dj, dout, dstuff, nj);
   return hipGetLastError();
 }
 

@@ -1,0 +1,71 @@
+"""GPU: uhdr_hip_jpegr_encode_batch against a loop of single calls (uhdr_hip_jpegr_encode_api1 / api0) in the same process: smooth 4K
+frames on the device, HLG, q95, n in {1, 4, 16, 64} (or the n given with --n), a distinct frame per file.  Wall ms per file (the
+call returns once the files are on the host).  Run under rocprofv3 --kernel-trace --stats (with --n 16) for the kernels' split."""
+import argparse
+import ctypes as C
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+from libultrahdr_dev_amd import api, synth
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--n", type=int, nargs="*", default=[1, 4, 16, 64])
+ap.add_argument("--iters", type=int, default=10)
+args = ap.parse_args()
+
+lib = api.init(0)
+W, H = 3840, 2160
+NMAX = max(args.n)
+frames = [synth.smooth_frame(W, H, 200 + i) for i in range(NMAX)]
+pis = [api.p010_image(p.data_ptr(), W, H, api.CG_BT2100) for p, _ in frames]
+yis = [api.yuv420_image(y.data_ptr(), W, H, api.CG_BT709) for _, y in frames]
+CAP = W * H * 3
+outs = [np.zeros(CAP, np.uint8) for _ in range(NMAX)]
+torch.cuda.synchronize()
+
+
+def timed(fn, iters):
+    for _ in range(2):
+        assert fn() == 0
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters * 1e3
+
+
+for api0 in (False, True):
+    name = "API-0" if api0 else "API-1"
+    for n in args.n:
+        P = api.image_array(pis[:n])
+        Y = None if api0 else api.image_array(yis[:n])
+        optr = (C.c_void_p * n)(*[o.ctypes.data for o in outs[:n]])
+        cap = (C.c_size_t * n)(*[CAP] * n)
+        size = (C.c_size_t * n)()
+        status = (C.c_int * n)()
+        sz = C.c_size_t()
+
+        def batch():
+            return lib.uhdr_hip_jpegr_encode_batch(n, P, Y, api.TF_HLG, 95, None, None, optr, cap, size, status, api.MEM_DEVICE, None)
+
+        def singles():
+            for i in range(n):
+                o = C.c_void_p(outs[i].ctypes.data)
+                if api0:
+                    rc = lib.uhdr_hip_jpegr_encode_api0(C.byref(pis[i]), api.TF_HLG, 95, None, 0, o, CAP, C.byref(sz), api.MEM_DEVICE, None)
+                else:
+                    rc = lib.uhdr_hip_jpegr_encode_api1(C.byref(pis[i]), C.byref(yis[i]), api.TF_HLG, 95, None, 0, o, CAP, C.byref(sz), api.MEM_DEVICE, None)
+                if rc != 0:
+                    return rc
+            return 0
+
+        iters = max(2, args.iters * 4 // max(n, 4))
+        ts = timed(singles, iters)
+        tb = timed(batch, iters)
+        print("%s n=%2d 4K: batch %.3f ms per file (%.3f ms per call), single-call loop %.3f ms per file, speed-up %.2fx (%d bytes per file)"
+              % (name, n, tb / n, tb, ts / n, ts / tb, size[0]), flush=True)
