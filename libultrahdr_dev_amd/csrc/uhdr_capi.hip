@@ -44,9 +44,10 @@ void set_err(const char* where, hipError_t e) {
 // grow-only device staging buffers of one UHDR_HIP_MEM_HOST call.  The four pixel-path entry points (generate, apply, toneMap,
 // convertYuv) lease a set of their own for the duration of a call, so host callers on different streams overlap their copies and
 // kernels; the codec entry points lease a whole context (CodecLease).
+constexpr int kStageSlots = 12;
 struct StageSet {
-  void* stage[14] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  size_t stage_bytes[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  void* stage[kStageSlots] = {};
+  size_t stage_bytes[kStageSlots] = {};
 };
 struct DeviceState : StageSet {
   bool ready = false;
@@ -58,12 +59,9 @@ struct DeviceState : StageSet {
   // uhdr_hip_jpegr_decode[_batch]: per-file decoder workspaces and planes
   std::vector<void*> pool;
   std::vector<size_t> pool_bytes;
-  // uhdr_hip_jpegr_encode_batch: page-locked host memory the compressed streams land in (grow-only)
+  // encodeJPEGR (compress_to_host): page-locked host memory the encoder's descriptors, sizes and compressed streams land in (grow-only)
   void* host_pool = nullptr;
   size_t host_pool_bytes = 0;
-  // encodeJPEGR: the gain-map JPEG is compressed on a stream of its own, next to the SDR image's conversion and compression
-  hipStream_t aux = nullptr;
-  hipEvent_t map_ready = nullptr;
   // generate with statistics: the candidate lists of one launch (kStatWsBytes), one workspace per stream the caller has used --
   // launches of one stream follow each other, launches of different streams may overlap
   std::map<hipStream_t, uint32_t*> stat_ws;
@@ -71,7 +69,7 @@ struct DeviceState : StageSet {
   struct ExWs { uint32_t* p = nullptr; size_t bytes = 0; };
   std::map<hipStream_t, ExWs> ex_ws;
   // the codec entry points (jpeg_*, jpegr_*, effects and tables through host memory) each lease a context of their own for the
-  // duration of a call -- staging slots, decoder pool, side stream and event -- so that callers on different streams overlap
+  // duration of a call -- staging slots, device and host pools -- so that callers on different streams overlap
   // (CodecLease); a context is a DeviceState that borrows this one's tables
   std::vector<std::unique_ptr<DeviceState>> codec_sets;   // every context ever leased ...
   std::vector<DeviceState*> free_codec;                    // ... and those not in use (both under g_mu)
@@ -954,21 +952,17 @@ int uhdr_hip_shutdown(void) {
     for (void* q : kv.second.pool) if (q) (void)hipFree(q);
     for (auto& w : kv.second.stat_ws) if (w.second) (void)hipFree(w.second);
     for (auto& w : kv.second.ex_ws) if (w.second.p) (void)hipFree(w.second.p);
-    for (int i = 0; i < 14; ++i)
+    for (int i = 0; i < kStageSlots; ++i)
       if (kv.second.stage[i]) (void)hipFree(kv.second.stage[i]);
     for (auto& set : kv.second.sets)
-      for (int i = 0; i < 14; ++i)
+      for (int i = 0; i < kStageSlots; ++i)
         if (set->stage[i]) (void)hipFree(set->stage[i]);
     for (auto& q : kv.second.retired) (void)hipFree(q.second);
-    if (kv.second.map_ready) (void)hipEventDestroy(kv.second.map_ready);
-    if (kv.second.aux) (void)hipStreamDestroy(kv.second.aux);
     for (auto& cx : kv.second.codec_sets) {   // the leased codec contexts (their tables are this state's: not freed here)
       for (void* q : cx->pool) if (q) (void)hipFree(q);
       if (cx->host_pool) (void)hipHostFree(cx->host_pool);
-      for (int i = 0; i < 14; ++i)
+      for (int i = 0; i < kStageSlots; ++i)
         if (cx->stage[i]) (void)hipFree(cx->stage[i]);
-      if (cx->map_ready) (void)hipEventDestroy(cx->map_ready);
-      if (cx->aux) (void)hipStreamDestroy(cx->aux);
     }
   }
   g_dev.clear();
@@ -1033,6 +1027,142 @@ jpeg::Plane encode_plane(const uint8_t* p, size_t pw, size_t ph, size_t stride, 
   q.aligned4 = (reinterpret_cast<uintptr_t>(p) % 4 == 0 && stride % 4 == 0) ? 1 : 0;
   return q;
 }
+// the encoder job of one image with device planes (luma_stride set); pad_ls / pad_cs: the strides that decide the column padding,
+// the caller's for planes staged from host memory
+jpeg::Job encode_job(const uhdr_hip_image_t& img, int q, size_t pad_ls, size_t pad_cs) {
+  const bool gray = img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
+  const size_t w = img.width, h = img.height, aw = (w + 15) / 16 * 16, acw = (w / 2 + 7) / 8 * 8;
+  jpeg::Job j;
+  encode_job_tables(w, h, gray, q, &j);
+  j.plane[0] = encode_plane(static_cast<const uint8_t*>(img.data), w, h, img.luma_stride, pad_ls < aw);
+  if (!gray) {
+    const uint8_t* pu = static_cast<const uint8_t*>(img.chroma_data);
+    const size_t cs = img.chroma_stride;
+    j.plane[1] = encode_plane(pu, w / 2, h / 2, cs, pad_cs < acw);
+    j.plane[2] = encode_plane(pu + cs * (h / 2), w / 2, h / 2, cs, pad_cs < acw);   // chromaStride * height / 2 (jpegencoderhelper.cpp:140)
+  }
+  return j;
+}
+// the sizes compressImage takes: libjpeg's JPEG_MAX_DIMENSION, and whole 2x2 blocks for 4:2:0
+bool encodable(const uhdr_hip_image_t& img) {
+  const size_t w = img.width, h = img.height;
+  return w != 0 && h != 0 && w <= 65500 && h <= 65500 && (img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME || ((w | h) & 1) == 0);
+}
+
+// device copy of a host image for the encoder in slots [slot, slot+1] (luma_stride set): exactly the bytes the reference would
+// touch -- w columns when it pads, the 16-aligned width otherwise
+int stage_encoder_in(StageSet* st, int slot, const uhdr_hip_image_t& h, uhdr_hip_image_t* d, hipStream_t s) {
+  const size_t w = h.width, hh = h.height, ls = h.luma_stride, cs = h.chroma_stride;
+  const size_t aw = (w + 15) / 16 * 16, acw = (w / 2 + 7) / 8 * 8;
+  const size_t ycols = ls < aw ? w : aw, ccols = cs < acw ? w / 2 : acw;
+  const size_t dls = round_up(ycols, 64), dcs = round_up(ccols ? ccols : 1, 64);
+  int rc;
+  if ((rc = stage_reserve(st, slot, dls * hh)) != 0) return rc;
+  if ((rc = h2d_plane(st->stage[slot], dls, h.data, ls, ycols, hh, 1, s)) != 0) return rc;
+  *d = h;
+  d->data = st->stage[slot];
+  d->luma_stride = dls;
+  if (h.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME) return UHDR_HIP_NO_ERROR;
+  if ((rc = stage_reserve(st, slot + 1, dcs * hh + 64)) != 0) return rc;
+  const uint8_t* hu = static_cast<const uint8_t*>(h.chroma_data);
+  uint8_t* du = static_cast<uint8_t*>(st->stage[slot + 1]);
+  if ((rc = h2d_plane(du, dcs, hu, cs, ccols, hh / 2, 1, s)) != 0) return rc;
+  if ((rc = h2d_plane(du + dcs * (hh / 2), dcs, hu + cs * hh / 2, cs, ccols, hh / 2, 1, s)) != 0) return rc;
+  d->chroma_data = du;
+  d->chroma_stride = dcs;
+  return UHDR_HIP_NO_ERROR;
+}
+
+// grow-only buffers of the caller's leased context: device memory (the JPEG/R decode and encode entry points) ...
+int pool_reserve(DeviceState* st, size_t idx, size_t bytes) {
+  if (st->pool.size() <= idx) { st->pool.resize(idx + 1, nullptr); st->pool_bytes.resize(idx + 1, 0); }
+  if (bytes == 0) bytes = 256;
+  if (st->pool_bytes[idx] >= bytes) return UHDR_HIP_NO_ERROR;
+  if (st->pool[idx]) HIP_TRY(hipFree(st->pool[idx]));
+  st->pool[idx] = nullptr; st->pool_bytes[idx] = 0;
+  HIP_TRY(hipMalloc(&st->pool[idx], bytes));
+  st->pool_bytes[idx] = bytes;
+  return UHDR_HIP_NO_ERROR;
+}
+// ... and page-locked host memory (the JPEG encoder's descriptors, sizes and compressed streams)
+int host_pool_reserve(DeviceState* st, size_t bytes) {
+  if (st->host_pool_bytes >= bytes) return UHDR_HIP_NO_ERROR;
+  if (st->host_pool) HIP_TRY(hipHostFree(st->host_pool));
+  st->host_pool = nullptr;
+  st->host_pool_bytes = 0;
+  HIP_TRY(hipHostMalloc(&st->host_pool, bytes, hipHostMallocDefault));
+  st->host_pool_bytes = bytes;
+  return UHDR_HIP_NO_ERROR;
+}
+// the JPEG encoder's pool slots, then encodeJPEGR's planes
+enum : size_t { kEncWs = 0, kEncDesc, kEncSdr, kEncMap, kEncP010, kEncYuv };
+
+// one image of compress_to_host: device planes and how to compress them in, the JPEG out
+struct EncJpeg {
+  uhdr_hip_image_t img;                  // luma_stride set; MONOCHROME: one plane
+  int quality;
+  const std::vector<uint8_t>* icc;       // nullptr: none
+  size_t pad_ls, pad_cs;                 // the strides that decide the column padding (encode_job)
+  size_t cap = 0;                        // host staging of the file; 0: the single calls' first guess, w * h + 64 KiB
+  const uint8_t* bytes = nullptr;        // the JPEG: in the context's host pool, or in `big`
+  size_t n = 0;
+  std::vector<uint8_t> big;              // a file larger than its staging, compressed again on its own
+};
+
+// JpegEncoderHelper::compressImage (jpegencoderhelper.cpp:39-52) of k images in the leased context st: the headers are written into
+// its page-locked host pool, one jpeg::encode_batch_async writes the streams behind them and their sizes, and one synchronisation
+// ends it.  A file larger than its staging was cut off: it is compressed again in a context of its own, so that this one's host
+// pool, which holds the other files, is left alone.  A non-zero return is an error of the device or the runtime.
+int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool may_retry = true) {
+  std::vector<jpeg::Job> jobs((size_t)k);
+  std::vector<jpeg::Layout> lay((size_t)k);
+  std::vector<jpeg::BatchOut> outs((size_t)k);
+  std::vector<uint8_t*> wss((size_t)k);
+  std::vector<size_t> ws_off((size_t)k), off((size_t)k);
+  const size_t desc = round_up(jpeg::batch_desc_bytes(k), 256);
+  size_t hp_total = desc + round_up(8 * (size_t)k, 256), ws_total = 0;
+  for (int i = 0; i < k; ++i) {
+    jobs[i] = encode_job(im[i].img, im[i].quality, im[i].pad_ls, im[i].pad_cs);
+    ws_off[i] = ws_total;
+    ws_total += round_up(jpeg::workspace_bytes(jobs[i].nblk, &lay[i]), 256);
+    if (im[i].cap == 0) im[i].cap = im[i].img.width * im[i].img.height + 65536;
+    off[i] = hp_total;
+    hp_total += round_up(im[i].cap, 256);
+  }
+  int rc;
+  if ((rc = host_pool_reserve(st, hp_total)) != 0) return rc;
+  if ((rc = pool_reserve(st, kEncWs, ws_total)) != 0) return rc;
+  if ((rc = pool_reserve(st, kEncDesc, jpeg::batch_desc_bytes(k))) != 0) return rc;
+  uint8_t* hp = static_cast<uint8_t*>(st->host_pool);
+  uint64_t* sizes = reinterpret_cast<uint64_t*>(hp + desc);
+  std::vector<uint8_t> header;
+  for (int i = 0; i < k; ++i) {
+    const EncJpeg& e = im[i];
+    jpeg::build_header((int)e.img.width, (int)e.img.height, jobs[i].gray != 0, e.quality, e.icc ? e.icc->data() : nullptr,
+                       e.icc ? e.icc->size() : 0, header);
+    memcpy(hp + off[i], header.data(), header.size());
+    sizes[i] = 0;
+    outs[i] = jpeg::BatchOut{hp + off[i], e.cap, header.size(), &sizes[i]};
+    wss[i] = static_cast<uint8_t*>(st->pool[kEncWs]) + ws_off[i];
+  }
+  HIP_TRY(jpeg::encode_batch_async(k, jobs.data(), lay.data(), wss.data(), outs.data(), hp, static_cast<uint8_t*>(st->pool[kEncDesc]), s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int i = 0; i < k; ++i) {
+    EncJpeg& e = im[i];
+    const uint64_t total = sizes[i];
+    if (total != 0 && total <= e.cap) { e.bytes = hp + off[i]; e.n = (size_t)total; continue; }
+    if (total == 0 || !may_retry) return UHDR_HIP_ERROR_ENCODE_ERROR;
+    DeviceState* root = nullptr;
+    if (current_state(&root) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
+    CodecLease lease(root);
+    EncJpeg one{e.img, e.quality, e.icc, e.pad_ls, e.pad_cs, (size_t)total};
+    if (lease.get() == nullptr || compress_to_host(lease.get(), s, 1, &one, false) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
+    e.big.assign(one.bytes, one.bytes + one.n);
+    e.bytes = e.big.data();
+    e.n = e.big.size();
+  }
+  return UHDR_HIP_NO_ERROR;
+}
 }  // namespace
 
 extern "C" {
@@ -1044,9 +1174,7 @@ int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void*
   const bool gray = image->pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
   if (!gray && image->chroma_data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
   if (out == nullptr && out_capacity != 0) return UHDR_HIP_ERROR_BAD_PTR;
-  const size_t w = image->width, h = image->height;
-  if (w == 0 || h == 0 || w > 65500 || h > 65500) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;   // libjpeg's JPEG_MAX_DIMENSION
-  if (!gray && ((w | h) & 1)) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
+  if (!encodable(*image)) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
   DeviceState* st = nullptr;
   int rc = current_state(&st);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
@@ -1054,47 +1182,21 @@ int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void*
   CodecLease lease(st);   // the encoder workspace: this call's own
   if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
 
-  const size_t ls = image->luma_stride ? image->luma_stride : w;
-  const size_t cs = gray ? 0 : image->chroma_stride;
-  const size_t aw = (w + 15) / 16 * 16, acw = (w / 2 + 7) / 8 * 8;
-  jpeg::Job j;
-  encode_job_tables(w, h, gray, quality, &j);
-
-  const uint8_t* py = static_cast<const uint8_t*>(image->data);
-  const uint8_t* pu = static_cast<const uint8_t*>(image->chroma_data);
-  size_t dls = ls, dcs = cs;
-  if (mem_space != UHDR_HIP_MEM_DEVICE) {
-    // stage exactly the bytes the reference would touch: w columns when it pads, the 16-aligned width otherwise
-    const size_t ycols = ls < aw ? w : aw, ccols = cs < acw ? w / 2 : acw;
-    dls = round_up(ycols, 64); dcs = round_up(ccols ? ccols : 1, 64);
-    if ((rc = stage_reserve(st, 0, dls * h)) != 0) return rc;
-    if ((rc = h2d_plane(st->stage[0], dls, py, ls, ycols, h, 1, s)) != 0) return rc;
-    py = static_cast<const uint8_t*>(st->stage[0]);
-    if (!gray) {
-      if ((rc = stage_reserve(st, 1, dcs * h + 64)) != 0) return rc;
-      uint8_t* du = static_cast<uint8_t*>(st->stage[1]);
-      if ((rc = h2d_plane(du, dcs, pu, cs, ccols, h / 2, 1, s)) != 0) return rc;
-      if ((rc = h2d_plane(du + dcs * (h / 2), dcs, pu + cs * h / 2, cs, ccols, h / 2, 1, s)) != 0) return rc;
-      pu = du;
-    }
-  }
-  auto plane = encode_plane;
-  j.plane[0] = plane(py, w, h, dls, ls < aw);
-  if (!gray) {
-    const size_t v_off = mem_space != UHDR_HIP_MEM_DEVICE ? dcs * (h / 2) : cs * h / 2;   // chromaStride * height / 2 (:140)
-    j.plane[1] = plane(pu, w / 2, h / 2, dcs, cs < acw);
-    j.plane[2] = plane(pu + v_off, w / 2, h / 2, dcs, cs < acw);
-  }
-
+  const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
+  uhdr_hip_image_t img = *image;
+  if (img.luma_stride == 0) img.luma_stride = img.width;
+  if (gray) img.chroma_stride = 0;
+  uhdr_hip_image_t d = img;
+  if (host && (rc = stage_encoder_in(st, 0, img, &d, s)) != 0) return rc;
+  const jpeg::Job j = encode_job(d, quality, img.luma_stride, img.chroma_stride);
   std::vector<uint8_t> header;
-  jpeg::build_header((int)w, (int)h, gray, quality, icc, icc_size, header);
+  jpeg::build_header((int)img.width, (int)img.height, gray, quality, icc, icc_size, header);
   jpeg::Layout l;
-  const size_t ws_bytes = jpeg::workspace_bytes(j.nblk, &l);
-  if ((rc = stage_reserve(st, 7, ws_bytes)) != 0) return rc;
+  if ((rc = stage_reserve(st, 7, jpeg::workspace_bytes(j.nblk, &l))) != 0) return rc;
   uint8_t* ws = static_cast<uint8_t*>(st->stage[7]);
   uint8_t* dout = static_cast<uint8_t*>(out);
   size_t dcap = out_capacity;
-  if (mem_space != UHDR_HIP_MEM_DEVICE) {   // worst case: every stream byte stuffed
+  if (host) {   // worst case: every stream byte stuffed
     dcap = header.size() + 2 * l.stream_bytes + 2;
     if ((rc = stage_reserve(st, 5, dcap)) != 0) return rc;
     dout = static_cast<uint8_t*>(st->stage[5]);
@@ -1106,7 +1208,7 @@ int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void*
   HIP_TRY(hipStreamSynchronize(s));
   *out_size = (size_t)total;
   if (total > out_capacity) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  if (mem_space != UHDR_HIP_MEM_DEVICE) {
+  if (host) {
     HIP_TRY(hipMemcpyAsync(out, dout, total, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
   }
@@ -1296,17 +1398,6 @@ int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bo
   return UHDR_HIP_NO_ERROR;
 }
 
-// grow-only device buffers of the JPEG/R decode entry points (the caller's leased context)
-int pool_reserve(DeviceState* st, size_t idx, size_t bytes) {
-  if (st->pool.size() <= idx) { st->pool.resize(idx + 1, nullptr); st->pool_bytes.resize(idx + 1, 0); }
-  if (bytes == 0) bytes = 256;
-  if (st->pool_bytes[idx] >= bytes) return UHDR_HIP_NO_ERROR;
-  if (st->pool[idx]) HIP_TRY(hipFree(st->pool[idx]));
-  st->pool[idx] = nullptr; st->pool_bytes[idx] = 0;
-  HIP_TRY(hipMalloc(&st->pool[idx], bytes));
-  st->pool_bytes[idx] = bytes;
-  return UHDR_HIP_NO_ERROR;
-}
 }  // namespace
 
 extern "C" {
@@ -1545,156 +1636,6 @@ void default_yuv(uhdr_hip_image_t* im) {
   im->pixelFormat = UHDR_HIP_PIX_FMT_YUV420;
 }
 
-struct EncodeCtx {
-  DeviceState* st;
-  void* stream;
-  int mem_space;
-  bool host() const { return mem_space != UHDR_HIP_MEM_DEVICE; }
-  hipStream_t s() const { return static_cast<hipStream_t>(stream); }
-};
-
-// Host bytes a compressed stream comes down into: page-locked (the copy runs at DMA speed instead of through the runtime's staging
-// buffer) and kept between calls by their thread_local owners -- a fresh multi-megabyte std::vector costs a memset and a page fault
-// per 4 KiB on every call, which was more than half of a 4K encodeJPEGR call.  Never freed: the process owns them until it ends.
-struct HostBytes {
-  uint8_t* p = nullptr;
-  size_t n = 0, cap = 0;
-  uint8_t* data() const { return p; }
-  size_t size() const { return n; }
-  void resize(size_t want) {
-    if (want > cap) {
-      if (p) (void)hipHostFree(p);
-      p = nullptr; cap = 0;
-      void* q = nullptr;
-      if (hipHostMalloc(&q, want, hipHostMallocDefault) == hipSuccess) { p = static_cast<uint8_t*>(q); cap = want; }
-    }
-    n = p ? want : 0;
-  }
-};
-
-// JpegEncoderHelper::compressImage with the bytes landing in host memory whichever side the planes live on
-int jpeg_to_host(const EncodeCtx& c, const uhdr_hip_image_t& img, int q, const std::vector<uint8_t>* icc, HostBytes& dst, size_t* n) {
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    if (dst.data() == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-    int r;
-    if (c.host()) {
-      r = uhdr_hip_jpeg_encode(&img, q, icc ? icc->data() : nullptr, icc ? icc->size() : 0, dst.data(), dst.size(), n, UHDR_HIP_MEM_HOST, c.stream);
-    } else {   // device planes in, bytes to a device buffer, then down
-      int r2;
-      if ((r2 = stage_reserve(c.st, 10, dst.size())) != 0) return r2;
-      r = uhdr_hip_jpeg_encode(&img, q, icc ? icc->data() : nullptr, icc ? icc->size() : 0, c.st->stage[10], dst.size(), n, UHDR_HIP_MEM_DEVICE, c.stream);
-      if (r == UHDR_HIP_NO_ERROR) {
-        HIP_TRY(hipMemcpyAsync(dst.data(), c.st->stage[10], *n, hipMemcpyDeviceToHost, c.s()));
-        HIP_TRY(hipStreamSynchronize(c.s()));
-      }
-    }
-    if (r != UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE) return r;
-    dst.resize(*n + 16);
-  }
-  return UHDR_HIP_ERROR_ENCODE_ERROR;
-}
-
-// The same for planes that live on the device, without a round trip: the kernels write the stream straight into the page-locked
-// host buffer (the device reaches it over the bus; that replaces the device-to-host copy) and its size into a page-locked word, so a
-// call can enqueue all its compressions and synchronise ONCE.  The size is valid after the stream has been synchronised; `dst` must
-// not be touched before.  ws_slot: encoder workspace, 12 or 13 (two compressions in flight need two; uhdr_hip_jpeg_encode has its own).
-constexpr size_t kPendingSize = ~(size_t)0;
-struct PendingJpeg {
-  HostBytes* dst = nullptr;
-  uint64_t* total = nullptr;
-  uhdr_hip_image_t img;
-  int q = 0;
-  std::vector<uint8_t> icc;
-  bool has_icc = false;
-};
-uint64_t* pinned_totals() {   // two page-locked size words per host thread
-  static thread_local HostBytes words;
-  if (words.size() < 64) words.resize(64);
-  return reinterpret_cast<uint64_t*>(words.data());
-}
-int jpeg_enqueue_device(const EncodeCtx& c, const uhdr_hip_image_t& img, int q, const std::vector<uint8_t>* icc, HostBytes& dst, int ws_slot,
-                        uint64_t* total, PendingJpeg* pend) {
-  if (dst.data() == nullptr || total == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  const bool gray = img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
-  const size_t w = img.width, h = img.height;
-  if (w == 0 || h == 0 || w > 65500 || h > 65500 || (!gray && ((w | h) & 1))) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
-  const size_t ls = img.luma_stride ? img.luma_stride : w, cs = gray ? 0 : img.chroma_stride;
-  const size_t aw = (w + 15) / 16 * 16, acw = (w / 2 + 7) / 8 * 8;
-  jpeg::Job j;
-  encode_job_tables(w, h, gray, q, &j);
-  const uint8_t* py = static_cast<const uint8_t*>(img.data);
-  const uint8_t* pu = static_cast<const uint8_t*>(img.chroma_data);
-  j.plane[0] = encode_plane(py, w, h, ls, ls < aw);
-  if (!gray) {
-    j.plane[1] = encode_plane(pu, w / 2, h / 2, cs, cs < acw);
-    j.plane[2] = encode_plane(pu + cs * h / 2, w / 2, h / 2, cs, cs < acw);   // chromaStride * height / 2 (jpegencoderhelper.cpp:140)
-  }
-  std::vector<uint8_t> header;
-  jpeg::build_header((int)w, (int)h, gray, q, icc ? icc->data() : nullptr, icc ? icc->size() : 0, header);
-  if (dst.size() < header.size()) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  jpeg::Layout l;
-  const size_t ws_bytes = jpeg::workspace_bytes(j.nblk, &l);
-  int rc;
-  if ((rc = stage_reserve(c.st, ws_slot, ws_bytes)) != 0) return rc;   // slots 12 / 13 of the caller's leased context
-  uint8_t* ws = static_cast<uint8_t*>(c.st->stage[ws_slot]);
-  memcpy(dst.data(), header.data(), header.size());   // host memory: no copy to enqueue
-  *total = 0;
-  HIP_TRY(jpeg::encode_async(j, l, ws, dst.data(), dst.size(), header.size(), c.s(), total));   // (the size goes where the bytes go: page-locked host memory)
-  pend->dst = &dst; pend->total = total; pend->img = img; pend->q = q;
-  pend->has_icc = icc != nullptr;
-  if (icc) pend->icc = *icc;
-  return UHDR_HIP_NO_ERROR;
-}
-// after the stream has been synchronised: the size, or (a stream larger than the buffer: it was cut off) the compression again
-int jpeg_collect(const EncodeCtx& c, PendingJpeg& p, size_t* n) {
-  const uint64_t total = *p.total;
-  if (total != 0 && total <= p.dst->size()) { *n = (size_t)total; return UHDR_HIP_NO_ERROR; }
-  if (total == 0) return UHDR_HIP_ERROR_ENCODE_ERROR;
-  p.dst->resize((size_t)total + 16);
-  return jpeg_to_host(c, p.img, p.q, p.has_icc ? &p.icc : nullptr, *p.dst, n);
-}
-PendingJpeg& pending_gainmap() { static thread_local PendingJpeg p; return p; }
-
-// compressGainMap (jpegr.cpp:806-821): one plane at kMapCompressQuality = 85
-int gainmap_to_jpeg(const EncodeCtx& c, const uhdr_hip_image_t& map, HostBytes& jpeg, size_t* n) {
-  uhdr_hip_image_t g = map;
-  g.chroma_data = nullptr; g.chroma_stride = 0; g.pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
-  // an earlier call that left on an error path may still have kernels writing into this (page-locked, thread-local) buffer on
-  // the side stream: they must have finished before a growing resize frees it
-  if (c.st->aux != nullptr) HIP_TRY(hipStreamSynchronize(c.st->aux));
-  jpeg.resize(map.width * map.height + 65536);
-  if (!c.host()) {   // enqueued; *n == kPendingSize until resolve_gainmap_jpeg() (or finish_from_planes) has synchronised
-    // On a stream of its own behind the kernel that wrote the map: nothing the caller's stream does next (the SDR image's BT.601
-    // re-encode and compression) depends on it, and its ~12 small launches fit next to those (the context is this call's own).
-    if (c.st->aux == nullptr) {
-      HIP_TRY(hipStreamCreateWithFlags(&c.st->aux, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&c.st->map_ready, hipEventDisableTiming));
-    }
-    HIP_TRY(hipEventRecord(c.st->map_ready, c.s()));
-    HIP_TRY(hipStreamWaitEvent(c.st->aux, c.st->map_ready, 0));
-    EncodeCtx side = c;
-    side.stream = c.st->aux;
-    *n = kPendingSize;
-    return jpeg_enqueue_device(side, g, 85, nullptr, jpeg, 13, pinned_totals(), &pending_gainmap()) == UHDR_HIP_NO_ERROR ? UHDR_HIP_NO_ERROR : UHDR_HIP_ERROR_ENCODE_ERROR;
-  }
-  return jpeg_to_host(c, g, 85, nullptr, jpeg, n) == UHDR_HIP_NO_ERROR ? UHDR_HIP_NO_ERROR : UHDR_HIP_ERROR_ENCODE_ERROR;
-}
-
-// generateGainMap followed by compressGainMap: the block every one of API-0..3 contains (e.g. jpegr.cpp:277-292)
-int make_gainmap_jpeg(const EncodeCtx& c, const uhdr_hip_image_t& yuv, const uhdr_hip_image_t& p010, int hdr_tf, int sdr_is_601,
-                      uhdr_hip_metadata_t* md, HostBytes& jpeg, size_t* n) {
-  const size_t mw = yuv.width / 4, mh = yuv.height / 4;
-  std::vector<uint8_t> host_map;
-  uhdr_hip_image_t map = yuv;
-  int rc;
-  if ((rc = stage_reserve(c.st, 9, mw * mh + 64)) != 0) return rc;
-  if (c.host()) { host_map.resize(mw * mh ? mw * mh : 1); map.data = host_map.data(); } else map.data = c.st->stage[9];
-  rc = uhdr_hip_generate_gainmap(&yuv, &p010, hdr_tf, md, &map, sdr_is_601, c.mem_space, c.stream);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
-  map.width = mw; map.height = mh; map.luma_stride = mw;
-  return gainmap_to_jpeg(c, map, jpeg, n);
-}
-
 // the 3x3 of JpegR::convertYuv for a pair of different encodings (jpegr.cpp:1134-1197)
 const float* yuv_matrix(int src_encoding, int dest_encoding) {
   switch (src_encoding) {
@@ -1703,8 +1644,6 @@ const float* yuv_matrix(int src_encoding, int dest_encoding) {
     default: return dest_encoding == UHDR_HIP_CG_BT709 ? kYuv2100To709 : kYuv2100To601;
   }
 }
-// convertYuv of `src` into the planes of `dst` (device memory, same size): the private copy API-1 converts is written by the
-// conversion itself instead of by three plane copies in front of it
 // descriptor of one convertYuv: `src`'s samples through m into `dst`'s planes (the same image for the in-place form)
 CvtImage cvt_image(const uhdr_hip_image_t& src, const uhdr_hip_image_t& dst, const float* m, bool* aligned) {
   CvtImage t;
@@ -1729,102 +1668,49 @@ int convert_yuv_into(const uhdr_hip_image_t& src, const uhdr_hip_image_t& dst, c
   HIP_TRY(launch_convert_yuv(b, 1, aligned, s));
   return UHDR_HIP_NO_ERROR;
 }
-
-// the tail API-0 and API-1 share (jpegr.cpp:210-247 / :294-380): ICC for the SDR gamut, BT.601 re-encode unless P3, JPEG at `quality`,
-// appendGainMap.  `enc` must be private to the call when it is not P3 (it is converted in place).
-int finish_from_planes(const EncodeCtx& c, uhdr_hip_image_t enc, int quality, const void* exif, size_t exif_size,
-                       const HostBytes& gm_jpeg, size_t gm_n, const uhdr_hip_metadata_t& md, void* out, size_t out_capacity,
-                       size_t* out_size, bool converted = false) {   // gm_n may be kPendingSize: the gain-map JPEG is still being written (device callers)
-  std::vector<uint8_t> icc;
-  if (!jpegr::icc_profile_srgb_transfer(enc.colorGamut, icc)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
-  int rc;
-  if (!converted && enc.colorGamut != UHDR_HIP_CG_P3 &&
-      (rc = uhdr_hip_convert_yuv(&enc, enc.colorGamut, UHDR_HIP_CG_P3, c.mem_space, c.stream)) != UHDR_HIP_NO_ERROR)
-    return rc;
-  static thread_local HostBytes sdr_jpeg;
-  sdr_jpeg.resize(enc.width * enc.height + 65536);
-  size_t sdr_n = 0;
-  if (!c.host()) {   // both compressions in flight, one synchronisation for the call
-    PendingJpeg sdr;
-    if (jpeg_enqueue_device(c, enc, quality, &icc, sdr_jpeg, 12, pinned_totals() + 1, &sdr) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
-    HIP_TRY(hipStreamSynchronize(c.s()));
-    if (gm_n == kPendingSize) HIP_TRY(hipStreamSynchronize(c.st->aux));
-    if (gm_n == kPendingSize && jpeg_collect(c, pending_gainmap(), &gm_n) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
-    if (jpeg_collect(c, sdr, &sdr_n) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
-  } else if (jpeg_to_host(c, enc, quality, &icc, sdr_jpeg, &sdr_n) != UHDR_HIP_NO_ERROR) {
-    return UHDR_HIP_ERROR_ENCODE_ERROR;
-  }
-  return jpegr::append_gainmap_to(sdr_jpeg.data(), sdr_n, gm_jpeg.data(), gm_n, static_cast<const uint8_t*>(exif), exif_size, nullptr, 0, md,
-                                  static_cast<uint8_t*>(out), out_capacity, out_size);
-}
-
-// for the callers that need the gain-map JPEG at once (API-2 / API-3 / API-x): wait for it
-int resolve_gainmap_jpeg(const EncodeCtx& c, size_t* n) {
-  if (*n != kPendingSize) return UHDR_HIP_NO_ERROR;
-  HIP_TRY(hipStreamSynchronize(c.st->aux));
-  return jpeg_collect(c, pending_gainmap(), n) == UHDR_HIP_NO_ERROR ? UHDR_HIP_NO_ERROR : UHDR_HIP_ERROR_ENCODE_ERROR;
-}
-
-
 // ---- encodeJPEGR for n files (uhdr_hip_jpegr_encode_batch) ---------------------------------------------------------------------
 // Files go through in rounds of up to kEncRound (2 JPEGs each: the batched encoder's job limit); every device buffer of a round is
 // a slice of one grow-only pool slot of the leased context, the compressed streams land in its page-locked host pool.
 constexpr int kEncRound = jpeg::kMaxBatchJobs / 2;
-enum : size_t { kEncWs = 0, kEncDesc, kEncSdr, kEncMap, kEncP010, kEncYuv };
-
-int host_pool_reserve(DeviceState* st, size_t bytes) {
-  if (st->host_pool_bytes >= bytes) return UHDR_HIP_NO_ERROR;
-  if (st->host_pool) HIP_TRY(hipHostFree(st->host_pool));
-  st->host_pool = nullptr;
-  st->host_pool_bytes = 0;
-  HIP_TRY(hipHostMalloc(&st->host_pool, bytes, hipHostMallocDefault));
-  st->host_pool_bytes = bytes;
-  return UHDR_HIP_NO_ERROR;
-}
 
 struct EncFile {
   int idx = 0;                 // the caller's index
   uhdr_hip_image_t p010, yuv;  // defaulted (yuv: API-1 only); device planes once staged
-  uhdr_hip_image_t caller_yuv; // API-1: the caller's SDR planes as given (a P3 image is compressed from them)
   uhdr_hip_image_t enc, map;   // the planes the two JPEGs compress (device)
   size_t pad_ls = 0, pad_cs = 0;   // the strides that decide the encoder's column padding (the caller's for a P3 image)
   bool own_copy = false;       // enc is a private zero-padded copy with 16-aligned strides
   std::vector<uint8_t> icc;
-  size_t sdr_off = 0, sdr_cap = 0, gm_off = 0, gm_cap = 0;
-  std::vector<uint8_t> sdr_big, gm_big;   // a stream that outgrew its staging, compressed again on its own
-  const uint8_t* sdr = nullptr;
-  const uint8_t* gm = nullptr;
-  size_t sdr_n = 0, gm_n = 0;
 };
 
-// the encoder job of one image, as jpeg_enqueue_device builds it; ls / cs: the strides that decide the padding
-jpeg::Job batch_job(const uhdr_hip_image_t& img, int q, size_t pad_ls, size_t pad_cs) {
-  const bool gray = img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
-  const size_t w = img.width, h = img.height, aw = (w + 15) / 16 * 16, acw = (w / 2 + 7) / 8 * 8;
-  jpeg::Job j;
-  encode_job_tables(w, h, gray, q, &j);
-  const uint8_t* py = static_cast<const uint8_t*>(img.data);
-  j.plane[0] = encode_plane(py, w, h, img.luma_stride, pad_ls < aw);
-  if (!gray) {
-    const uint8_t* pu = static_cast<const uint8_t*>(img.chroma_data);
-    const size_t cs = img.chroma_stride;
-    j.plane[1] = encode_plane(pu, w / 2, h / 2, cs, pad_cs < acw);
-    j.plane[2] = encode_plane(pu + cs * (h / 2), w / 2, h / 2, cs, pad_cs < acw);
-  }
-  return j;
+// compressGainMap (jpegr.cpp:806-821): one plane at kMapCompressQuality = 85
+EncJpeg gainmap_jpeg(uhdr_hip_image_t map, size_t pad_ls) {
+  map.chroma_data = nullptr; map.chroma_stride = 0; map.pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
+  return EncJpeg{map, 85, nullptr, pad_ls, 0};
 }
 
-// One round: staging (host callers), toneMap (API-0), generateGainMap, BT.601 re-encode, the 2 m compressions -- one launch per
-// step for the round's files -- then one synchronisation.  Leaves each file's two JPEGs in f[k].sdr / f[k].gm.  A non-zero return
-// is an error of the device or the runtime (every file of the round fails with it).
-int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_tf, int quality, EncFile* f, int m, uhdr_hip_metadata_t* md) {
+// generateGainMap followed by compressGainMap on device planes: the block API-2 and API-3 contain (e.g. jpegr.cpp:416-434)
+int make_gainmap_jpeg(DeviceState* st, hipStream_t s, const uhdr_hip_image_t& yuv, const uhdr_hip_image_t& p010, int hdr_tf, int sdr_is_601,
+                      uhdr_hip_metadata_t* md, EncJpeg* gm) {
+  const size_t mw = yuv.width / 4, mh = yuv.height / 4;
+  int rc;
+  if ((rc = stage_reserve(st, 9, mw * mh + 64)) != 0) return rc;
+  uhdr_hip_image_t map = yuv;
+  map.data = st->stage[9];
+  if ((rc = uhdr_hip_generate_gainmap(&yuv, &p010, hdr_tf, md, &map, sdr_is_601, UHDR_HIP_MEM_DEVICE, s)) != UHDR_HIP_NO_ERROR) return rc;
+  map.width = mw; map.height = mh; map.luma_stride = mw;
+  *gm = gainmap_jpeg(map, mw);
+  return compress_to_host(st, s, 1, gm) == UHDR_HIP_NO_ERROR ? UHDR_HIP_NO_ERROR : UHDR_HIP_ERROR_ENCODE_ERROR;
+}
+
+// One round: staging (host callers), toneMap (API-0), generateGainMap, BT.601 re-encode -- one launch per step for the round's
+// files -- then the 2 m compressions with one synchronisation (compress_to_host).  Leaves file k's JPEGs in (*jpg)[2 k] (SDR) and
+// (*jpg)[2 k + 1] (gain map).  A non-zero return is an error of the device or the runtime (every file of the round fails with it).
+int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_tf, int quality, EncFile* f, int m, uhdr_hip_metadata_t* md,
+                 std::vector<EncJpeg>* jpg) {
   auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
   int rc;
   // sizes of the round's slices
-  size_t ws_total = 0, sdr_total = 0, map_total = 0, p010_total = 0, yuv_total = 0, hp_total = al256(jpeg::batch_desc_bytes(2 * m)) + al256(16 * (size_t)m);
-  std::vector<jpeg::Job> jobs(2 * (size_t)m);
-  std::vector<jpeg::Layout> lay(2 * (size_t)m);
-  std::vector<size_t> ws_off(2 * (size_t)m);
+  size_t sdr_total = 0, map_total = 0, p010_total = 0, yuv_total = 0;
   for (int k = 0; k < m; ++k) {
     const size_t w = f[k].p010.width, h = f[k].p010.height, aw = (w + 15) / 16 * 16, mw = w / 4, mh = h / 4;
     if (host) {
@@ -1833,19 +1719,11 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
     }
     if (f[k].own_copy) sdr_total += al256(aw * h * 3 / 2 + 64);
     map_total += al256(mw * mh + 64);
-    f[k].sdr_cap = w * h + 65536;   // the first guesses of the single calls
-    f[k].gm_cap = mw * mh + 65536;
-    f[k].sdr_off = hp_total; hp_total += al256(f[k].sdr_cap);
-    f[k].gm_off = hp_total; hp_total += al256(f[k].gm_cap);
   }
-  if ((rc = host_pool_reserve(st, hp_total)) != 0) return rc;
   if ((rc = pool_reserve(st, kEncMap, map_total)) != 0) return rc;
   if (sdr_total && (rc = pool_reserve(st, kEncSdr, sdr_total)) != 0) return rc;
   if (p010_total && (rc = pool_reserve(st, kEncP010, p010_total)) != 0) return rc;
   if (yuv_total && (rc = pool_reserve(st, kEncYuv, yuv_total)) != 0) return rc;
-  uint8_t* hp = static_cast<uint8_t*>(st->host_pool);
-  uint8_t* hdesc = hp;
-  uint64_t* sizes = reinterpret_cast<uint64_t*>(hp + al256(jpeg::batch_desc_bytes(2 * m)));
 
   // planes: staged inputs (host callers), private copies, maps
   size_t o_p010 = 0, o_yuv = 0, o_sdr = 0, o_map = 0;
@@ -1884,7 +1762,6 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
       e.pad_ls = aw; e.pad_cs = aw >> 1;
     } else {
       e.enc = e.yuv;   // P3: compressed as it is, padded by the caller's strides
-      e.pad_ls = e.caller_yuv.luma_stride; e.pad_cs = e.caller_yuv.chroma_stride;
     }
     if (api0) e.yuv = e.enc;
     e.map = e.yuv;
@@ -1917,182 +1794,31 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
     HIP_TRY(launch_convert_yuv(cb, cnt, aligned, s));
     k += cnt;
   }
-  // the 2 m compressions: headers written into the page-locked staging, the streams behind them by the kernels
-  std::vector<jpeg::BatchOut> outs(2 * (size_t)m);
-  std::vector<uint8_t*> wss(2 * (size_t)m);
-  std::vector<uint8_t> header;
+  // the 2 m compressions
+  jpg->clear();
+  jpg->reserve(2 * (size_t)m);
   for (int k = 0; k < m; ++k) {
-    EncFile& e = f[k];
+    const EncFile& e = f[k];
     uhdr_hip_image_t g = e.map;
     g.width = e.enc.width / 4; g.height = e.enc.height / 4; g.luma_stride = g.width;
-    g.chroma_data = nullptr; g.chroma_stride = 0; g.pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
-    e.map = g;
-    jobs[2 * k] = batch_job(e.enc, quality, e.pad_ls, e.pad_cs);
-    jobs[2 * k + 1] = batch_job(g, 85, g.luma_stride, 0);   // compressGainMap: kMapCompressQuality (jpegr.cpp:806-821)
-    for (int t = 0; t < 2; ++t) {
-      const size_t jk = 2 * (size_t)k + t;
-      const uhdr_hip_image_t& im = t == 0 ? e.enc : g;
-      jpeg::build_header((int)im.width, (int)im.height, t == 1, t == 0 ? quality : 85, t == 0 ? e.icc.data() : nullptr, t == 0 ? e.icc.size() : 0,
-                         header);
-      uint8_t* dst = hp + (t == 0 ? e.sdr_off : e.gm_off);
-      memcpy(dst, header.data(), header.size());
-      sizes[jk] = 0;
-      outs[jk] = jpeg::BatchOut{dst, t == 0 ? e.sdr_cap : e.gm_cap, header.size(), &sizes[jk]};
-      ws_off[jk] = ws_total;
-      ws_total += al256(jpeg::workspace_bytes(jobs[jk].nblk, &lay[jk]));
-    }
+    jpg->push_back(EncJpeg{e.enc, quality, &e.icc, e.pad_ls, e.pad_cs});
+    jpg->push_back(gainmap_jpeg(g, g.luma_stride));
   }
-  if ((rc = pool_reserve(st, kEncWs, ws_total)) != 0) return rc;
-  if ((rc = pool_reserve(st, kEncDesc, jpeg::batch_desc_bytes(2 * m))) != 0) return rc;
-  for (size_t jk = 0; jk < wss.size(); ++jk) wss[jk] = static_cast<uint8_t*>(st->pool[kEncWs]) + ws_off[jk];
-  HIP_TRY(jpeg::encode_batch_async(2 * m, jobs.data(), lay.data(), wss.data(), outs.data(), hdesc, static_cast<uint8_t*>(st->pool[kEncDesc]), s));
-  HIP_TRY(hipStreamSynchronize(s));
-
-  // a stream larger than its staging was cut off: that image is compressed again on its own (as jpeg_collect does)
-  for (int k = 0; k < m; ++k) {
-    EncFile& e = f[k];
-    for (int t = 0; t < 2; ++t) {
-      const uint64_t total = sizes[2 * (size_t)k + t];
-      if (total == 0) return UHDR_HIP_ERROR_ENCODE_ERROR;
-      const size_t cap = t == 0 ? e.sdr_cap : e.gm_cap;
-      uint8_t* at = hp + (t == 0 ? e.sdr_off : e.gm_off);
-      if (total <= cap) {
-        (t == 0 ? e.sdr : e.gm) = at;
-        (t == 0 ? e.sdr_n : e.gm_n) = (size_t)total;
-        continue;
-      }
-      // the compression again: a P3 image of a host caller from its own planes (the single call's staging and padding)
-      const bool from_caller = t == 0 && !e.own_copy && host;
-      EncodeCtx ctx{st, s, from_caller ? UHDR_HIP_MEM_HOST : UHDR_HIP_MEM_DEVICE};
-      const uhdr_hip_image_t& im = t == 0 ? (from_caller ? e.caller_yuv : e.enc) : e.map;
-      HostBytes tmp;
-      tmp.resize((size_t)total + 16);
-      size_t n2 = 0;
-      std::vector<uint8_t> icc_copy = e.icc;
-      const int r = jpeg_to_host(ctx, im, t == 0 ? quality : 85, t == 0 ? &icc_copy : nullptr, tmp, &n2);
-      if (r == UHDR_HIP_NO_ERROR) (t == 0 ? e.sdr_big : e.gm_big).assign(tmp.data(), tmp.data() + n2);
-      if (tmp.p) (void)hipHostFree(tmp.p);
-      if (r != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
-      (t == 0 ? e.sdr : e.gm) = (t == 0 ? e.sdr_big : e.gm_big).data();
-      (t == 0 ? e.sdr_n : e.gm_n) = n2;
-    }
-  }
-  return UHDR_HIP_NO_ERROR;
+  return compress_to_host(st, s, 2 * m, jpg->data());
 }
 
-}  // namespace
-
-extern "C" {
-
-// JpegR::encodeJPEGR API-0 (jpegr.cpp:186-247)
-int uhdr_hip_jpegr_encode_api0(const uhdr_hip_image_t* p010_in, int hdr_tf, int quality, const void* exif, size_t exif_size, void* out,
-                               size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
-  int rc = check_encode_inputs(p010_in, nullptr, hdr_tf, out, out_size);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
-  if (exif == nullptr && exif_size != 0) return UHDR_HIP_ERROR_BAD_PTR;                                          // :190-193
-  uhdr_hip_image_t p010 = *p010_in;
-  default_p010(&p010);
-  EncodeCtx c{nullptr, stream, mem_space};
-  if ((rc = current_state(&c.st)) != UHDR_HIP_NO_ERROR) return rc;
-  CodecLease lease(c.st);
-  if ((c.st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-
-  // :208-223: the tone-mapped SDR image, luma stride rounded up to the encoder's 16-column batch, zero-initialised
-  const size_t w = p010.width, h = p010.height, ls = (w + 15) / 16 * 16, total = ls * h * 3 / 2;
-  std::vector<uint8_t> host_yuv;
-  uhdr_hip_image_t yuv;
-  memset(&yuv, 0, sizeof(yuv));
-  yuv.width = w; yuv.height = h; yuv.colorGamut = p010.colorGamut;
-  yuv.luma_stride = ls; yuv.chroma_stride = ls >> 1; yuv.pixelFormat = UHDR_HIP_PIX_FMT_YUV420;
-  if (c.host()) {
-    host_yuv.assign(total, 0);
-    yuv.data = host_yuv.data();
-  } else {
-    if ((rc = stage_reserve(c.st, 8, total + 64)) != 0) return rc;
-    HIP_TRY(hipMemsetAsync(c.st->stage[8], 0, total, c.s()));
-    yuv.data = c.st->stage[8];
-  }
-  yuv.chroma_data = static_cast<uint8_t*>(yuv.data) + ls * h;
-  if ((rc = uhdr_hip_tonemap(&p010, &yuv, mem_space, stream)) != UHDR_HIP_NO_ERROR) return rc;                    // :226
-
-  uhdr_hip_metadata_t md;
-  static thread_local HostBytes gm_jpeg;
-  size_t gm_n = 0;
-  if ((rc = make_gainmap_jpeg(c, yuv, p010, hdr_tf, 0, &md, gm_jpeg, &gm_n)) != UHDR_HIP_NO_ERROR) return rc;     // :228-244
-  return finish_from_planes(c, yuv, quality, exif, exif_size, gm_jpeg, gm_n, md, out, out_capacity, out_size);
-}
-
-// JpegR::encodeJPEGR API-1 (jpegr.cpp:249-381)
-int uhdr_hip_jpegr_encode_api1(const uhdr_hip_image_t* p010_in, const uhdr_hip_image_t* yuv_in, int hdr_tf, int quality, const void* exif,
-                               size_t exif_size, void* out, size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
-  if (yuv_in == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                           // :253-256
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
-  int rc = check_encode_inputs(p010_in, yuv_in, hdr_tf, out, out_size);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
-  if (exif == nullptr && exif_size != 0) return UHDR_HIP_ERROR_BAD_PTR;                                          // :258-261
-  uhdr_hip_image_t p010 = *p010_in, yuv = *yuv_in;
-  default_p010(&p010);
-  default_yuv(&yuv);
-  EncodeCtx c{nullptr, stream, mem_space};
-  if ((rc = current_state(&c.st)) != UHDR_HIP_NO_ERROR) return rc;
-  CodecLease lease(c.st);
-  if ((c.st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  const size_t w = yuv.width, h = yuv.height;
-
-  uhdr_hip_metadata_t md;
-  static thread_local HostBytes gm_jpeg;
-  size_t gm_n = 0;
-  if ((rc = make_gainmap_jpeg(c, yuv, p010, hdr_tf, 0, &md, gm_jpeg, &gm_n)) != UHDR_HIP_NO_ERROR) return rc;     // :277-292
-
-  // :297-358: unless the SDR image is P3 (= BT.601 encoding) already, a copy with 16-aligned strides, zero padded, is what gets converted
-  uhdr_hip_image_t enc = yuv;
-  std::vector<uint8_t> host_601;
-  bool converted = false;
-  if (yuv.colorGamut != UHDR_HIP_CG_P3) {
-    const size_t ls = (w + 15) / 16 * 16, cs = ls >> 1, total = ls * h * 3 / 2;
-    enc.luma_stride = ls; enc.chroma_stride = cs;
-    const uint8_t* src_u = static_cast<const uint8_t*>(yuv.chroma_data);
-    const uint8_t* src_v = src_u + yuv.chroma_stride * h / 2;
-    if (c.host()) {
-      host_601.assign(total ? total : 1, 0);
-      enc.data = host_601.data();
-      uint8_t* du = host_601.data() + ls * h;
-      uint8_t* dv = du + cs * h / 2;
-      for (size_t r = 0; r < h; ++r) memcpy(host_601.data() + r * ls, static_cast<const uint8_t*>(yuv.data) + r * yuv.luma_stride, w);
-      for (size_t r = 0; r < h / 2; ++r) { memcpy(du + r * cs, src_u + r * yuv.chroma_stride, w / 2); memcpy(dv + r * cs, src_v + r * yuv.chroma_stride, w / 2); }
-    } else {
-      if ((rc = stage_reserve(c.st, 8, total + 64)) != 0) return rc;
-      uint8_t* d = static_cast<uint8_t*>(c.st->stage[8]);
-      if (ls != w) HIP_TRY(hipMemsetAsync(d, 0, total, c.s()));   // the padding columns (a width of whole 16-column batches has none)
-      enc.data = d;
-      enc.chroma_data = d + ls * h;
-      // the copy is written by the conversion (the same arithmetic on the same samples as a copy followed by the in-place form)
-      if (!valid_gamut(yuv.colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
-      if ((rc = convert_yuv_into(yuv, enc, yuv_matrix(yuv.colorGamut, UHDR_HIP_CG_P3), c.s())) != UHDR_HIP_NO_ERROR) return rc;
-      converted = true;
-    }
-    enc.chroma_data = static_cast<uint8_t*>(enc.data) + ls * h;
-  }
-  return finish_from_planes(c, enc, quality, exif, exif_size, gm_jpeg, gm_n, md, out, out_capacity, out_size, converted);
-}
-
-// encodeJPEGR API-1 (yuv420_images != NULL) or API-0 for n pairs in one call: the files' kernels share their launches, the call
-// synchronises once per round of up to kEncRound files, and the containers are assembled by a few host threads
-int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
-                                const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
-                                int* status, int mem_space, void* stream) {
-  if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (exif != nullptr && exif_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
+// encodeJPEGR API-1 (yuv420_images != NULL) or API-0 for n pairs, the quality checked: the files' kernels share their launches, the
+// call synchronises once per round of up to kEncRound files, and the containers are assembled by a few host threads
+int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                 const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
+                 int* status, int mem_space, void* stream) {
   const bool api0 = yuv420_images == nullptr;
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
   std::vector<EncFile> files;
   for (int i = 0; i < n; ++i) {   // the single call's checks, in its order; a file that fails them is not processed
     const void* ex = exif ? exif[i] : nullptr;
     const size_t exn = exif ? exif_size[i] : 0;
-    int rc = check_encode_inputs(&p010_images[i], api0 ? nullptr : &yuv420_images[i], hdr_tf, out[i], &out_size[i]);
+    int rc = check_encode_inputs(p010_images + i, api0 ? nullptr : yuv420_images + i, hdr_tf, out[i], out_size + i);
     if (rc == UHDR_HIP_NO_ERROR && ex == nullptr && exn != 0) rc = UHDR_HIP_ERROR_BAD_PTR;                     // :190-193 / :258-261
     if (rc != UHDR_HIP_NO_ERROR) { st_[i] = rc; continue; }
     EncFile e;
@@ -2101,7 +1827,7 @@ int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, cons
     default_p010(&e.p010);
     memset(&e.yuv, 0, sizeof(e.yuv));
     if (!api0) { e.yuv = yuv420_images[i]; default_yuv(&e.yuv); }
-    e.caller_yuv = e.yuv;
+    e.pad_ls = e.yuv.luma_stride; e.pad_cs = e.yuv.chroma_stride;
     const int sdr_gamut = api0 ? e.p010.colorGamut : e.yuv.colorGamut;
     e.own_copy = api0 || sdr_gamut != UHDR_HIP_CG_P3;
     if (!jpegr::icc_profile_srgb_transfer(sdr_gamut, e.icc)) { st_[i] = UHDR_HIP_ERROR_INVALID_COLORGAMUT; continue; }
@@ -2134,14 +1860,17 @@ int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, cons
       const int m = (int)std::min(files.size() - r0, (size_t)kEncRound);
       EncFile* f = &files[r0];
       uhdr_hip_metadata_t md;
-      rc = encode_round(st, s, api0, mem_space != UHDR_HIP_MEM_DEVICE, hdr_tf, quality, f, m, &md);
+      std::vector<EncJpeg> jpg;
+      rc = encode_round(st, s, api0, mem_space != UHDR_HIP_MEM_DEVICE, hdr_tf, quality, f, m, &md, &jpg);
       if (rc != UHDR_HIP_NO_ERROR) break;
       // appendGainMap (jpegr.cpp:951-1130) straight into the caller's buffers, a few host threads side by side
       auto assemble = [&](int lo, int hi) {
         for (int k = lo; k < hi; ++k) {
           const EncFile& e = f[k];
           const int i = e.idx;
-          st_[i] = jpegr::append_gainmap_to(e.sdr, e.sdr_n, e.gm, e.gm_n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
+          const EncJpeg& sdr = jpg[2 * (size_t)k];
+          const EncJpeg& gm = jpg[2 * (size_t)k + 1];
+          st_[i] = jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
                                             nullptr, 0, md, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i]);
         }
       };
@@ -2153,7 +1882,6 @@ int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, cons
         for (int t = 0; t < nthreads; ++t) workers.emplace_back(assemble, (int)((long)m * t / nthreads), (int)((long)m * (t + 1) / nthreads));
         for (auto& w : workers) w.join();
       }
-      for (int k = 0; k < m; ++k) { std::vector<uint8_t>().swap(f[k].sdr_big); std::vector<uint8_t>().swap(f[k].gm_big); }
     }
     if (rc != UHDR_HIP_NO_ERROR)   // the files of the failed round and of those behind it
       for (size_t k = r0; k < files.size(); ++k) st_[files[k].idx] = rc;
@@ -2161,6 +1889,35 @@ int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, cons
   }
   for (const EncFile& e : files) st_[e.idx] = rc;
   return result();
+}
+
+}  // namespace
+
+extern "C" {
+
+int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                                const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
+                                int* status, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
+  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream);
+}
+
+// JpegR::encodeJPEGR API-0 (jpegr.cpp:186-247): a batch of one file
+int uhdr_hip_jpegr_encode_api0(const uhdr_hip_image_t* p010_in, int hdr_tf, int quality, const void* exif, size_t exif_size, void* out,
+                               size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
+  return encode_files(1, p010_in, nullptr, hdr_tf, quality, &exif, &exif_size, &out, &out_capacity, out_size, nullptr, mem_space, stream);
+}
+
+// JpegR::encodeJPEGR API-1 (jpegr.cpp:249-381): a batch of one file
+int uhdr_hip_jpegr_encode_api1(const uhdr_hip_image_t* p010_in, const uhdr_hip_image_t* yuv_in, int hdr_tf, int quality, const void* exif,
+                               size_t exif_size, void* out, size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
+  if (yuv_in == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                           // :253-256
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
+  return encode_files(1, p010_in, yuv_in, hdr_tf, quality, &exif, &exif_size, &out, &out_capacity, out_size, nullptr, mem_space, stream);
 }
 
 // JpegR::encodeJPEGR API-4 (jpegr.cpp:502-560): host bytes only, nothing runs on the device
@@ -2192,18 +1949,20 @@ int uhdr_hip_jpegr_encode_api2(const uhdr_hip_image_t* p010_in, const uhdr_hip_i
   uhdr_hip_image_t p010 = *p010_in, yuv = *yuv_in;
   default_p010(&p010);
   default_yuv(&yuv);
-  EncodeCtx c{nullptr, stream, mem_space};
-  if ((rc = current_state(&c.st)) != UHDR_HIP_NO_ERROR) return rc;
-  uhdr_hip_metadata_t md;
-  static thread_local HostBytes gm_jpeg;
-  size_t gm_n = 0;
-  {
-    CodecLease lease(c.st);
-    if ((c.st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-    if ((rc = make_gainmap_jpeg(c, yuv, p010, hdr_tf, 0, &md, gm_jpeg, &gm_n)) != UHDR_HIP_NO_ERROR) return rc;   // :416-434
-    if ((rc = resolve_gainmap_jpeg(c, &gm_n)) != UHDR_HIP_NO_ERROR) return rc;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  CodecLease lease(st);
+  if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uhdr_hip_image_t dy = yuv, dp = p010;
+  if (mem_space != UHDR_HIP_MEM_DEVICE) {   // the staging of generateGainMap's host path
+    if ((rc = stage_yuv420_in(st, 0, yuv, &dy, s)) != 0) return rc;
+    if ((rc = stage_p010_in(st, 2, p010, &dp, s)) != 0) return rc;
   }
-  return uhdr_hip_jpegr_encode_api4(sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, gm_jpeg.data(), gm_n, &md, out, out_capacity, out_size);
+  uhdr_hip_metadata_t md;
+  EncJpeg gm;
+  if ((rc = make_gainmap_jpeg(st, s, dy, dp, hdr_tf, 0, &md, &gm)) != UHDR_HIP_NO_ERROR) return rc;                // :416-434
+  return uhdr_hip_jpegr_encode_api4(sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, gm.bytes, gm.n, &md, out, out_capacity, out_size);
 }
 
 // JpegR::encodeJPEGR API-3 (jpegr.cpp:439-500): the SDR rendition arrives as a JPEG only and is decoded on the device
@@ -2223,36 +1982,33 @@ int uhdr_hip_jpegr_encode_api3(const uhdr_hip_image_t* p010_in, const void* sdr_
   if (rc == UHDR_HIP_ERROR_UNSUPPORTED_FEATURE) return rc;
   if (rc != UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE || ydesc.pixelFormat != UHDR_HIP_PIX_FMT_YUV420 || ydesc.width == 0 || ydesc.height == 0)
     return UHDR_HIP_ERROR_DECODE_ERROR;
-  EncodeCtx c{nullptr, stream, mem_space};
-  if ((rc = current_state(&c.st)) != UHDR_HIP_NO_ERROR) return rc;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  CodecLease lease(st);
+  if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t w = ydesc.width, h = ydesc.height, ybytes = w * h + 2 * (w * h / 4);
-  uhdr_hip_metadata_t md;
-  static thread_local HostBytes gm_jpeg;
-  size_t gm_n = 0;
-  {
-    CodecLease lease(c.st);
-    if ((c.st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-    std::vector<uint8_t> host_yuv;
-    void* planes;
-    if (c.host()) { host_yuv.resize(ybytes); planes = host_yuv.data(); }
-    else { if ((rc = stage_reserve(c.st, 8, ybytes + 64)) != 0) return rc; planes = c.st->stage[8]; }
-    if (uhdr_hip_jpeg_decode(pj, sdr_jpeg_size, planes, ybytes, &ydesc, mem_space, stream) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_DECODE_ERROR;
-    // :467-488 the gamut: the ICC profile's when there is one (and it must agree with a configured gamut), else the configured one
-    const uint8_t* icc = nullptr;
-    size_t icc_len = 0;
-    if (jpegr::first_icc(pj, sdr_jpeg_size, &icc, &icc_len)) {
-      const int cg = jpegr::gamut_from_icc(icc, icc_len);
-      if (cg == UHDR_HIP_CG_UNSPECIFIED || (sdr_jpeg_gamut != UHDR_HIP_CG_UNSPECIFIED && sdr_jpeg_gamut != cg)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
-      ydesc.colorGamut = cg;
-    } else {
-      if (sdr_jpeg_gamut <= UHDR_HIP_CG_UNSPECIFIED || sdr_jpeg_gamut > UHDR_HIP_CG_BT2100) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
-      ydesc.colorGamut = sdr_jpeg_gamut;
-    }
-    if (p010.width != w || p010.height != h) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;                           // :496-499
-    if ((rc = make_gainmap_jpeg(c, ydesc, p010, hdr_tf, 1 /* sdr_is_601 */, &md, gm_jpeg, &gm_n)) != UHDR_HIP_NO_ERROR) return rc;
-    if ((rc = resolve_gainmap_jpeg(c, &gm_n)) != UHDR_HIP_NO_ERROR) return rc;
+  if ((rc = stage_reserve(st, 8, ybytes + 64)) != 0) return rc;
+  if (uhdr_hip_jpeg_decode(pj, sdr_jpeg_size, st->stage[8], ybytes, &ydesc, UHDR_HIP_MEM_DEVICE, stream) != UHDR_HIP_NO_ERROR)
+    return UHDR_HIP_ERROR_DECODE_ERROR;
+  // :467-488 the gamut: the ICC profile's when there is one (and it must agree with a configured gamut), else the configured one
+  const uint8_t* icc = nullptr;
+  size_t icc_len = 0;
+  if (jpegr::first_icc(pj, sdr_jpeg_size, &icc, &icc_len)) {
+    const int cg = jpegr::gamut_from_icc(icc, icc_len);
+    if (cg == UHDR_HIP_CG_UNSPECIFIED || (sdr_jpeg_gamut != UHDR_HIP_CG_UNSPECIFIED && sdr_jpeg_gamut != cg)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+    ydesc.colorGamut = cg;
+  } else {
+    if (sdr_jpeg_gamut <= UHDR_HIP_CG_UNSPECIFIED || sdr_jpeg_gamut > UHDR_HIP_CG_BT2100) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+    ydesc.colorGamut = sdr_jpeg_gamut;
   }
-  return uhdr_hip_jpegr_encode_api4(sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, gm_jpeg.data(), gm_n, &md, out, out_capacity, out_size);
+  if (p010.width != w || p010.height != h) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;                             // :496-499
+  uhdr_hip_image_t dp = p010;
+  if (mem_space != UHDR_HIP_MEM_DEVICE && (rc = stage_p010_in(st, 2, p010, &dp, s)) != 0) return rc;
+  uhdr_hip_metadata_t md;
+  EncJpeg gm;
+  if ((rc = make_gainmap_jpeg(st, s, ydesc, dp, hdr_tf, 1 /* sdr_is_601 */, &md, &gm)) != UHDR_HIP_NO_ERROR) return rc;
+  return uhdr_hip_jpegr_encode_api4(sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, gm.bytes, gm.n, &md, out, out_capacity, out_size);
 }
 
 // JpegR::encodeJPEGR "API-x" (jpegr.cpp:562-631): SDR planes + a ready gain map + its metadata; no BT.601 re-encode on this path
@@ -2265,22 +2021,26 @@ int uhdr_hip_jpegr_encode_apix(const uhdr_hip_image_t* yuv_in, const uhdr_hip_im
   if (out == nullptr || out_size == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
   uhdr_hip_image_t yuv = *yuv_in;
   default_yuv(&yuv);
-  EncodeCtx c{nullptr, stream, mem_space};
+  DeviceState* st = nullptr;
   int rc;
-  if ((rc = current_state(&c.st)) != UHDR_HIP_NO_ERROR) return rc;
-  CodecLease lease(c.st);
-  if ((c.st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  static thread_local HostBytes gm_jpeg;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  CodecLease lease(st);
+  if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uhdr_hip_image_t map = *gainmap;
+  if (map.luma_stride == 0) map.luma_stride = map.width;
   std::vector<uint8_t> icc;
-  size_t gm_n = 0;
-  if ((rc = gainmap_to_jpeg(c, *gainmap, gm_jpeg, &gm_n)) != UHDR_HIP_NO_ERROR) return rc;                        // :590-597
-  if ((rc = resolve_gainmap_jpeg(c, &gm_n)) != UHDR_HIP_NO_ERROR) return rc;
+  EncJpeg jpg[2] = {EncJpeg{yuv, quality, &icc, yuv.luma_stride, yuv.chroma_stride}, gainmap_jpeg(map, map.luma_stride)};
+  if (!encodable(jpg[1].img)) return UHDR_HIP_ERROR_ENCODE_ERROR;                                                 // :590-597
   if (!jpegr::icc_profile_srgb_transfer(yuv.colorGamut, icc)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;           // :599-600
-  static thread_local HostBytes sdr_jpeg;
-  sdr_jpeg.resize(yuv.width * yuv.height + 65536);
-  size_t sdr_n = 0;
-  if (jpeg_to_host(c, yuv, quality, &icc, sdr_jpeg, &sdr_n) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;   // :602-611
-  return jpegr::append_gainmap_to(sdr_jpeg.data(), sdr_n, gm_jpeg.data(), gm_n, static_cast<const uint8_t*>(exif), exif_size, nullptr, 0, *metadata,
+  if (!encodable(yuv)) return UHDR_HIP_ERROR_ENCODE_ERROR;                                                        // :602-611
+  if (mem_space != UHDR_HIP_MEM_DEVICE) {   // staged planes, padded by the caller's strides
+    const uhdr_hip_image_t g = jpg[1].img;
+    if ((rc = stage_encoder_in(st, 0, yuv, &jpg[0].img, s)) != 0) return rc;
+    if ((rc = stage_encoder_in(st, 2, g, &jpg[1].img, s)) != 0) return rc;
+  }
+  if (compress_to_host(st, s, 2, jpg) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
+  return jpegr::append_gainmap_to(jpg[0].bytes, jpg[0].n, jpg[1].bytes, jpg[1].n, static_cast<const uint8_t*>(exif), exif_size, nullptr, 0, *metadata,
                                   static_cast<uint8_t*>(out), out_capacity, out_size);
 }
 

@@ -635,7 +635,7 @@ size_t workspace_bytes(uint32_t nblk, Layout* l) {
   return o;
 }
 
-hipError_t encode_async(Job j, const Layout& l, uint8_t* ws, uint8_t* out, uint64_t out_cap, uint64_t header_len, hipStream_t s, uint64_t* out_size) {
+hipError_t encode_async(Job j, const Layout& l, uint8_t* ws, uint8_t* out, uint64_t out_cap, uint64_t header_len, hipStream_t s) {
   j.coef = reinterpret_cast<int16_t*>(ws + l.coef);
   j.bits = reinterpret_cast<uint32_t*>(ws + l.bits);
   j.bits_blk = reinterpret_cast<uint32_t*>(ws + l.bits_blk);
@@ -653,7 +653,7 @@ hipError_t encode_async(Job j, const Layout& l, uint8_t* ws, uint8_t* out, uint6
   hipLaunchKernelGGL(k_jpeg_emit, gb, bb, 0, s, j);
   const dim3 gc((j.max_chunks + 255u) / 256u), bc(256);
   hipLaunchKernelGGL(k_jpeg_stuff_count, gc, bc, 0, s, j, total_bits);
-  hipLaunchKernelGGL(k_jpeg_stuff_copy, gc, bc, 0, s, j, total_bits, out, out_cap, header_len, out_size != nullptr ? out_size : totals + 1);
+  hipLaunchKernelGGL(k_jpeg_stuff_copy, gc, bc, 0, s, j, total_bits, out, out_cap, header_len, totals + 1);
   return hipGetLastError();
 }
 
