@@ -97,6 +97,9 @@ extern "C" {
  * decode nearly twice as many files per second as one). */
 #define UHDR_HIP_MEM_HOST 0
 #define UHDR_HIP_MEM_DEVICE 1
+/* uhdr_hip_jpeg_encode_batch only: planes and outputs in different memory spaces */
+#define UHDR_HIP_MEM_DEVICE_TO_HOST 2   /* planes in device memory, outputs in host memory */
+#define UHDR_HIP_MEM_HOST_TO_DEVICE 3   /* planes in host memory, outputs in device memory */
 
 /* arithmetic mode of uhdr_hip_apply_gainmap*:
  *   FAST  : transfer functions from line-segment tables in LDS (special-function unit where a call can exceed 1.0); every
@@ -279,6 +282,22 @@ int uhdr_hip_add_effects(const uhdr_hip_image_t* in_img, const uhdr_hip_effect_t
  * the stream.  Returns ERROR_INSUFFICIENT_RESOURCE with *out_size set when out_capacity is too small. */
 int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void* icc, size_t icc_size, void* out,
                          size_t out_capacity, size_t* out_size, int mem_space, void* stream);
+/* uhdr_hip_jpeg_encode for n images in one call (no reference counterpart).  Arrays are indexed by file; out[i] (capacity
+ * out_capacity[i]) receives file i, out_size[i] (HOST) its size.  Every file's status, size and bytes are those of the single call
+ * with the same arguments: its check order (BAD_PTR for NULL data, NULL chroma on 4:2:0 or out[i] == NULL with a capacity;
+ * RESOLUTION_MISMATCH), its quality clamping, ERROR_INSUFFICIENT_RESOURCE with the exact size (out[i] == NULL with capacity 0
+ * is a size probe).  status (optional) receives them, the return value is the first one that is not NO_ERROR; a file that fails its
+ * checks is not processed and does not disturb the others.  YUV420 and MONOCHROME images, sizes, strides, qualities and ICC
+ * profiles may differ per file.  icc == NULL: no file has a profile (icc[i] / icc_size[i] otherwise, HOST memory).  Call-level
+ * errors, before any file is looked at: BAD_PTR for n < 0, a NULL images / quality / out / out_capacity / out_size where n > 0, or
+ * icc != NULL with icc_size == NULL.  mem_space: UHDR_HIP_MEM_HOST or UHDR_HIP_MEM_DEVICE for planes and outputs alike, or
+ * UHDR_HIP_MEM_DEVICE_TO_HOST / UHDR_HIP_MEM_HOST_TO_DEVICE; host planes are staged to the device first, device outputs are
+ * written in place, host outputs arrive through page-locked staging.  The files go through in rounds: one launch per encoder step
+ * for every image of a round and one synchronisation.  A round holds at most 128 images and at most 2 GiB of device workspace
+ * and page-locked staging (a larger image gets a round of its own).  The call waits for the stream; a batch whose every file fails
+ * its checks does not touch the device. */
+int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                               void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream);
 
 /* Diagnostics, host only (no GPU): the quantised coefficients of a progressive (SOF2) file after all of its scans -- what the
  * host-side entropy decoder hands to the device: blocks in MCU order (4:2:0: Y00 Y01 Y10 Y11 Cb Cr), zigzag order inside a block.
@@ -309,6 +328,22 @@ int uhdr_hip_jpeg_decode(const void* jpeg, size_t jpeg_size, void* out, size_t o
  * JPEG is UNKNOWN_ERROR (the reference's call returns false). */
 int uhdr_hip_jpeg_decode_rgba(const void* jpeg, size_t jpeg_size, void* out, size_t out_capacity, uhdr_hip_image_t* desc, int mem_space,
                               void* stream);
+
+/* uhdr_hip_jpeg_decode (decode_to = UHDR_HIP_DECODE_TO_YCBCR) or uhdr_hip_jpeg_decode_rgba (UHDR_HIP_DECODE_TO_RGBA) for n files
+ * in one call (no reference counterpart; the values are those of the reference's decode_mode_t, jpegdecoderhelper.h:45-49).
+ * Arrays are indexed by file; jpeg[i] (HOST memory) is file i, out[i] (memory space mem_space, capacity out_capacity[i]) receives
+ * its pixels, descs[i] its descriptor.  Every file's status, bytes and descriptor are those of the single call with the same
+ * arguments, size probes and early failures included; status (optional) receives them, the return value is the first one that is
+ * not NO_ERROR; a file that fails does not disturb the others.  out or out_capacity may be NULL: every file is a size probe.
+ * Call-level errors: BAD_PTR for n < 0 or a NULL jpeg / jpeg_size / descs where n > 0; ERROR_UNSUPPORTED_FEATURE for any other
+ * decode_to.  The headers are parsed by up to 8 host threads; baseline, progressive, restart-interval and grayscale files of a round
+ * share every decoder launch, so their latency-bound synchronisation rounds run side by side, and (RGBA) one conversion launch.  A
+ * round holds at most 64 files and at most 2 GiB of device workspace (a larger file gets a round of its own).  The call waits for
+ * the stream; a batch whose every file stops at its checks or its size probe does not touch the device. */
+#define UHDR_HIP_DECODE_TO_RGBA 1
+#define UHDR_HIP_DECODE_TO_YCBCR 2
+int uhdr_hip_jpeg_decode_batch(int n, const void* const* jpeg, const size_t* jpeg_size, int decode_to, void* const* out,
+                               const size_t* out_capacity, uhdr_hip_image_t* descs, int* status, int mem_space, void* stream);
 
 /* JpegR::decodeJPEGR (lib/src/jpegr.cpp:655-822) for the HDR output formats: a JPEG/R file (HOST memory: primary JPEG + gain
  * map JPEG, the gain map's APP1 carrying the hdrgm:* XMP attributes) -> the HDR rendition applyGainMap produces.  Container

@@ -24,6 +24,8 @@ ERROR_INVALID_DISPLAY_BOOST, ERROR_INVALID_OUTPUT_FORMAT = -10008, -10009
 ERROR_ENCODE_ERROR, ERROR_DECODE_ERROR, ERROR_GAIN_MAP_IMAGE_NOT_FOUND, ERROR_METADATA_ERROR = -20001, -20002, -20003, -20005
 ERROR_NO_IMAGES_FOUND, ERROR_MULTIPLE_EXIFS_RECEIVED = -20006, -20007
 MEM_HOST, MEM_DEVICE = 0, 1
+MEM_DEVICE_TO_HOST, MEM_HOST_TO_DEVICE = 2, 3   # uhdr_hip_jpeg_encode_batch: planes and outputs apart
+DECODE_TO_RGBA, DECODE_TO_YCBCR = 1, 2          # uhdr_hip_jpeg_decode_batch
 APPLY_FAST, APPLY_EXACT, APPLY_LUT, APPLY_EXACT_UNFILTERED = 0, 1, 2, 3
 GENERATE_EXACT, GENERATE_LUT, GENERATE_UNFILTERED = 0, 1, 2
 ABI_VERSION = 3
@@ -90,6 +92,8 @@ SIGNATURES = {
     "uhdr_hip_jpeg_progressive_coefficients": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
                                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "uhdr_hip_jpeg_encode": (C.c_int, [_IP, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_void_p]),
+    "uhdr_hip_jpeg_encode_batch": (C.c_int, [C.c_int, _IP, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                             C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "uhdr_hip_jpeg_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _IP, C.c_int, C.c_void_p]),
     "uhdr_hip_jpegr_decode": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p, C.c_size_t, _IP, _MP, C.c_int, C.c_int, C.c_void_p]),
     "uhdr_hip_jpegr_append_gainmap": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _MP,
@@ -106,6 +110,8 @@ SIGNATURES = {
     "uhdr_hip_jpegr_encode_api4": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, _MP, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "uhdr_hip_jpegr_encode_apix": (C.c_int, [_IP, _IP, _MP, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_void_p]),
     "uhdr_hip_jpeg_decode_rgba": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _IP, C.c_int, C.c_void_p]),
+    "uhdr_hip_jpeg_decode_batch": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                             _IP, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "uhdr_hip_jpegr_decode_batch": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_float, C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_size_t), _IP, _MP, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p]),
     "uhdr_hip_jpegr_metadata": (C.c_int, [C.c_void_p, C.c_size_t, _MP]),

@@ -1049,13 +1049,23 @@ bool encodable(const uhdr_hip_image_t& img) {
   return w != 0 && h != 0 && w <= 65500 && h <= 65500 && (img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME || ((w | h) & 1) == 0);
 }
 
+// the columns of a host image the encoder reads -- w when it pads, the 16-aligned width otherwise -- and the pitches they are staged at
+struct EncStageCols {
+  size_t ycols, ccols, dls, dcs;
+};
+EncStageCols enc_stage_cols(const uhdr_hip_image_t& h) {
+  const size_t w = h.width, ls = h.luma_stride, cs = h.chroma_stride;
+  const size_t aw = (w + 15) / 16 * 16, acw = (w / 2 + 7) / 8 * 8;
+  const size_t ycols = ls < aw ? w : aw, ccols = cs < acw ? w / 2 : acw;
+  return EncStageCols{ycols, ccols, round_up(ycols, 64), round_up(ccols ? ccols : 1, 64)};
+}
+
 // device copy of a host image for the encoder in slots [slot, slot+1] (luma_stride set): exactly the bytes the reference would
 // touch -- w columns when it pads, the 16-aligned width otherwise
 int stage_encoder_in(StageSet* st, int slot, const uhdr_hip_image_t& h, uhdr_hip_image_t* d, hipStream_t s) {
-  const size_t w = h.width, hh = h.height, ls = h.luma_stride, cs = h.chroma_stride;
-  const size_t aw = (w + 15) / 16 * 16, acw = (w / 2 + 7) / 8 * 8;
-  const size_t ycols = ls < aw ? w : aw, ccols = cs < acw ? w / 2 : acw;
-  const size_t dls = round_up(ycols, 64), dcs = round_up(ccols ? ccols : 1, 64);
+  const size_t hh = h.height, ls = h.luma_stride, cs = h.chroma_stride;
+  const EncStageCols g = enc_stage_cols(h);
+  const size_t ycols = g.ycols, ccols = g.ccols, dls = g.dls, dcs = g.dcs;
   int rc;
   if ((rc = stage_reserve(st, slot, dls * hh)) != 0) return rc;
   if ((rc = h2d_plane(st->stage[slot], dls, h.data, ls, ycols, hh, 1, s)) != 0) return rc;
@@ -1107,6 +1117,10 @@ struct EncJpeg {
   const uint8_t* bytes = nullptr;        // the JPEG: in the context's host pool, or in `big`
   size_t n = 0;
   std::vector<uint8_t> big;              // a file larger than its staging, compressed again on its own
+  size_t keep_max = SIZE_MAX;            // a file larger than this is not wanted (its size is): it is not compressed again
+  bool to_dev = false;                   // the JPEG goes to dev_out (device memory, dev_cap bytes; the header only if it fits) instead
+  uint8_t* dev_out = nullptr;
+  size_t dev_cap = 0;
 };
 
 // JpegEncoderHelper::compressImage (jpegencoderhelper.cpp:39-52) of k images in the leased context st: the headers are written into
@@ -1121,13 +1135,17 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
   std::vector<size_t> ws_off((size_t)k), off((size_t)k);
   const size_t desc = round_up(jpeg::batch_desc_bytes(k), 256);
   size_t hp_total = desc + round_up(8 * (size_t)k, 256), ws_total = 0;
+  std::vector<std::vector<uint8_t>> header((size_t)k);
   for (int i = 0; i < k; ++i) {
-    jobs[i] = encode_job(im[i].img, im[i].quality, im[i].pad_ls, im[i].pad_cs);
+    const EncJpeg& e = im[i];
+    jobs[i] = encode_job(e.img, e.quality, e.pad_ls, e.pad_cs);
     ws_off[i] = ws_total;
     ws_total += round_up(jpeg::workspace_bytes(jobs[i].nblk, &lay[i]), 256);
+    jpeg::build_header((int)e.img.width, (int)e.img.height, jobs[i].gray != 0, e.quality, e.icc ? e.icc->data() : nullptr,
+                       e.icc ? e.icc->size() : 0, header[i]);
     if (im[i].cap == 0) im[i].cap = im[i].img.width * im[i].img.height + 65536;
     off[i] = hp_total;
-    hp_total += round_up(im[i].cap, 256);
+    hp_total += round_up(e.to_dev ? header[i].size() : im[i].cap, 256);   // a device destination: the header's way there only
   }
   int rc;
   if ((rc = host_pool_reserve(st, hp_total)) != 0) return rc;
@@ -1135,14 +1153,18 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
   if ((rc = pool_reserve(st, kEncDesc, jpeg::batch_desc_bytes(k))) != 0) return rc;
   uint8_t* hp = static_cast<uint8_t*>(st->host_pool);
   uint64_t* sizes = reinterpret_cast<uint64_t*>(hp + desc);
-  std::vector<uint8_t> header;
   for (int i = 0; i < k; ++i) {
     const EncJpeg& e = im[i];
-    jpeg::build_header((int)e.img.width, (int)e.img.height, jobs[i].gray != 0, e.quality, e.icc ? e.icc->data() : nullptr,
-                       e.icc ? e.icc->size() : 0, header);
-    memcpy(hp + off[i], header.data(), header.size());
+    const size_t hn = header[i].size();
+    memcpy(hp + off[i], header[i].data(), hn);
     sizes[i] = 0;
-    outs[i] = jpeg::BatchOut{hp + off[i], e.cap, header.size(), &sizes[i]};
+    if (e.to_dev) {   // as uhdr_hip_jpeg_encode into device memory: the header only where it fits, no stream byte otherwise
+      const bool fits = e.dev_cap >= hn;
+      if (fits) HIP_TRY(hipMemcpyAsync(e.dev_out, hp + off[i], hn, hipMemcpyHostToDevice, s));
+      outs[i] = jpeg::BatchOut{e.dev_out, fits ? e.dev_cap : 0, hn, &sizes[i]};
+    } else {
+      outs[i] = jpeg::BatchOut{hp + off[i], e.cap, hn, &sizes[i]};
+    }
     wss[i] = static_cast<uint8_t*>(st->pool[kEncWs]) + ws_off[i];
   }
   HIP_TRY(jpeg::encode_batch_async(k, jobs.data(), lay.data(), wss.data(), outs.data(), hp, static_cast<uint8_t*>(st->pool[kEncDesc]), s));
@@ -1150,7 +1172,9 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
   for (int i = 0; i < k; ++i) {
     EncJpeg& e = im[i];
     const uint64_t total = sizes[i];
+    if (total != 0 && e.to_dev) { e.bytes = nullptr; e.n = (size_t)total; continue; }   // the kernels kept to dev_cap
     if (total != 0 && total <= e.cap) { e.bytes = hp + off[i]; e.n = (size_t)total; continue; }
+    if (total != 0 && total > e.keep_max) { e.bytes = nullptr; e.n = (size_t)total; continue; }
     if (total == 0 || !may_retry) return UHDR_HIP_ERROR_ENCODE_ERROR;
     DeviceState* root = nullptr;
     if (current_state(&root) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
@@ -1160,6 +1184,112 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     e.big.assign(one.bytes, one.bytes + one.n);
     e.bytes = e.big.data();
     e.n = e.big.size();
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
+// ---- plain JPEG for n files (uhdr_hip_jpeg_encode_batch, uhdr_hip_jpeg_decode_batch) -----------------------------------------------
+// A round's device workspace and page-locked staging are held to kCodecRoundBytes (a file larger than that gets a round of its own)
+constexpr size_t kCodecRoundBytes = size_t(2) << 30;
+
+// uhdr_hip_jpeg_encode's image as it compresses it: luma_stride defaulted, no chroma stride for a single plane
+uhdr_hip_image_t enc_image(const uhdr_hip_image_t& in) {
+  uhdr_hip_image_t img = in;
+  if (img.luma_stride == 0) img.luma_stride = img.width;
+  if (img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME) img.chroma_stride = 0;
+  return img;
+}
+// bytes of the staged planes of a host image (luma, then chroma, each 256-aligned)
+size_t enc_stage_bytes(const uhdr_hip_image_t& img) {
+  const EncStageCols g = enc_stage_cols(img);
+  const size_t luma = round_up(g.dls * img.height, 256);
+  return img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME ? luma : luma + round_up(g.dcs * img.height + 64, 256);
+}
+// what one image holds of its round: encoder workspace, staged planes, page-locked staging of the file
+size_t enc_round_bytes(const uhdr_hip_image_t& img, bool host_in, bool host_out) {
+  jpeg::Job j;
+  encode_job_tables(img.width, img.height, img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME, 75, &j);
+  jpeg::Layout l;
+  size_t b = jpeg::workspace_bytes(j.nblk, &l);
+  if (host_in) b += enc_stage_bytes(img);
+  if (host_out) b += img.width * img.height + 65536;
+  return b;
+}
+
+// One round of uhdr_hip_jpeg_encode_batch: files idx[0, m), their planes staged at the slot kEncYuv (host planes), every
+// compression through one compress_to_host.  Statuses and sizes of the round's files go to st_ / out_size.  A non-zero return is an
+// error of the device or the runtime.
+int jpeg_encode_round(DeviceState* st, hipStream_t s, bool host_in, bool host_out, const uhdr_hip_image_t* images, const int* quality,
+                      const void* const* icc, const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size,
+                      const int* idx, int m, int* st_) {
+  std::vector<EncJpeg> im((size_t)m);
+  std::vector<std::vector<uint8_t>> iccs((size_t)m);
+  size_t stage_total = 0;
+  if (host_in) {
+    for (int k = 0; k < m; ++k) stage_total += enc_stage_bytes(enc_image(images[idx[k]]));
+    int rc;
+    if ((rc = pool_reserve(st, kEncYuv, stage_total)) != 0) return rc;
+  }
+  size_t o = 0;
+  for (int k = 0; k < m; ++k) {
+    const int i = idx[k];
+    const uhdr_hip_image_t img = enc_image(images[i]);
+    uhdr_hip_image_t d = img;
+    if (host_in) {   // stage_encoder_in's bytes and pitches, into the round's slice
+      const EncStageCols g = enc_stage_cols(img);
+      const size_t hh = img.height;
+      uint8_t* dy = static_cast<uint8_t*>(st->pool[kEncYuv]) + o;
+      int rc;
+      if ((rc = h2d_plane(dy, g.dls, img.data, img.luma_stride, g.ycols, hh, 1, s)) != 0) return rc;
+      d.data = dy;
+      d.luma_stride = g.dls;
+      if (img.pixelFormat != UHDR_HIP_PIX_FMT_MONOCHROME) {
+        const uint8_t* hu = static_cast<const uint8_t*>(img.chroma_data);
+        const size_t cs = img.chroma_stride;
+        uint8_t* du = dy + round_up(g.dls * hh, 256);
+        if ((rc = h2d_plane(du, g.dcs, hu, cs, g.ccols, hh / 2, 1, s)) != 0) return rc;
+        if ((rc = h2d_plane(du + g.dcs * (hh / 2), g.dcs, hu + cs * hh / 2, cs, g.ccols, hh / 2, 1, s)) != 0) return rc;
+        d.chroma_data = du;
+        d.chroma_stride = g.dcs;
+      }
+      o += enc_stage_bytes(img);
+    }
+    const void* ip = icc ? icc[i] : nullptr;
+    const size_t in = icc ? icc_size[i] : 0;
+    if (ip != nullptr && in > 0) iccs[k].assign(static_cast<const uint8_t*>(ip), static_cast<const uint8_t*>(ip) + in);
+    EncJpeg& e = im[k];
+    e.img = d;
+    e.quality = quality[i];
+    e.icc = iccs[k].empty() ? nullptr : &iccs[k];
+    e.pad_ls = img.luma_stride;
+    e.pad_cs = img.chroma_stride;
+    if (host_out) {
+      e.keep_max = out_capacity[i];   // a file that will not fit is only measured
+    } else {
+      e.to_dev = true;
+      e.dev_out = static_cast<uint8_t*>(out[i]);
+      e.dev_cap = out_capacity[i];
+    }
+  }
+  const int rc = compress_to_host(st, s, m, im.data());
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  // the files from the page-locked staging into the caller's buffers: megabytes per 4K file, so a few host threads side by side
+  auto deliver = [&](int lo, int hi) {
+    for (int k = lo; k < hi; ++k) {
+      const int i = idx[k];
+      out_size[i] = im[k].n;
+      if (im[k].n > out_capacity[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
+      if (host_out) memcpy(out[i], im[k].bytes, im[k].n);
+      st_[i] = UHDR_HIP_NO_ERROR;
+    }
+  };
+  const int nthreads = host_out && m >= 2 ? std::min(m, 8) : 1;
+  if (nthreads <= 1) {
+    deliver(0, m);
+  } else {
+    std::vector<std::thread> workers;
+    for (int t = 0; t < nthreads; ++t) workers.emplace_back(deliver, (int)((long)m * t / nthreads), (int)((long)m * (t + 1) / nthreads));
+    for (auto& w : workers) w.join();
   }
   return UHDR_HIP_NO_ERROR;
 }
@@ -1213,6 +1343,59 @@ int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void*
     HIP_TRY(hipStreamSynchronize(s));
   }
   return UHDR_HIP_NO_ERROR;
+}
+
+// uhdr_hip_jpeg_encode for n images in one call: every file's status, size and bytes those of the single call; the files of a round
+// share one jpeg::encode_batch_async launch set and one synchronisation (compress_to_host)
+int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                               void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (icc != nullptr && icc_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
+  std::vector<int> live;
+  for (int i = 0; i < n; ++i) {   // uhdr_hip_jpeg_encode's checks, in its order; a file that fails them is not processed
+    const uhdr_hip_image_t& im = images[i];
+    if (im.data == nullptr || (im.pixelFormat != UHDR_HIP_PIX_FMT_MONOCHROME && im.chroma_data == nullptr) ||
+        (out[i] == nullptr && out_capacity[i] != 0))
+      st_[i] = UHDR_HIP_ERROR_BAD_PTR;
+    else if (!encodable(im))
+      st_[i] = UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
+    else
+      live.push_back(i);
+  }
+  auto result = [&]() {
+    int first = UHDR_HIP_NO_ERROR;
+    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
+    return first;
+  };
+  if (live.empty()) return result();
+  DeviceState* st = nullptr;
+  int rc = current_state(&st);
+  size_t r0 = 0;   // live files [0, r0) are finished
+  if (rc == UHDR_HIP_NO_ERROR) {
+    CodecLease lease(st);
+    st = lease.get();
+    rc = st == nullptr ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool host_in = mem_space == UHDR_HIP_MEM_HOST || mem_space == UHDR_HIP_MEM_HOST_TO_DEVICE;
+    const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE && mem_space != UHDR_HIP_MEM_HOST_TO_DEVICE;
+    while (rc == UHDR_HIP_NO_ERROR && r0 < live.size()) {   // rounds of <= kMaxBatchJobs files and <= kCodecRoundBytes
+      size_t r1 = r0, bytes = 0;
+      while (r1 < live.size() && r1 - r0 < (size_t)jpeg::kMaxBatchJobs) {
+        const size_t b = enc_round_bytes(enc_image(images[live[r1]]), host_in, host_out);
+        if (r1 > r0 && bytes + b > kCodecRoundBytes) break;
+        bytes += b;
+        ++r1;
+      }
+      rc = jpeg_encode_round(st, s, host_in, host_out, images, quality, icc, icc_size, out, out_capacity, out_size, &live[r0], (int)(r1 - r0),
+                             st_.data());
+      if (rc == UHDR_HIP_NO_ERROR) r0 = r1;
+    }
+    if (rc != UHDR_HIP_NO_ERROR) (void)hipStreamSynchronize(s);   // nothing of a failed round may still be writing into the pools
+  }
+  for (size_t k = r0; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
+  return result();
 }
 
 // Diagnostics (host only, no GPU): the quantised coefficients of a PROGRESSIVE file after all of its scans, as the host-side
@@ -1398,6 +1581,138 @@ int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bo
   return UHDR_HIP_NO_ERROR;
 }
 
+// The host part of uhdr_hip_jpeg_decode (rgba false) or uhdr_hip_jpeg_decode_rgba (rgba true) for one file: the single call's checks
+// in its order, the header parsed into *info, *desc left as the single call leaves it.  NO_ERROR: the file is decoded on the device
+// into `need` bytes at out.
+int jpeg_decode_host(const void* jpeg, size_t jpeg_size, bool rgba, void* out, size_t out_capacity, uhdr_hip_image_t* desc,
+                     jpeg::DecInfo* info, size_t* need) {
+  if (jpeg == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  if (!rgba) memset(desc, 0, sizeof(*desc));   // the RGBA call leaves *desc alone until its header probe has passed
+  const int prc = jpeg::parse_header(static_cast<const uint8_t*>(jpeg), jpeg_size, info);
+  if (prc == -3) return UHDR_HIP_UNKNOWN_ERROR;
+  if (prc == -2) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (prc != 0 || info->w <= 0 || info->h <= 0) return UHDR_HIP_UNKNOWN_ERROR;
+  const size_t w = (size_t)info->w, h = (size_t)info->h, luma = w * h, chroma = luma / 4;
+  if (w > 8192 || h > 8192) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;   // kMaxWidth / kMaxHeight, jpegdecoderhelper.h:42-43
+  if (!rgba) {
+    *need = info->gray ? luma : luma + 2 * chroma;
+    desc->data = out;
+    desc->width = w; desc->height = h;
+    desc->colorGamut = UHDR_HIP_CG_UNSPECIFIED;
+    desc->luma_stride = w;
+    desc->chroma_data = info->gray ? nullptr : static_cast<uint8_t*>(out) + luma;
+    desc->chroma_stride = info->gray ? 0 : w / 2;
+    desc->pixelFormat = info->gray ? UHDR_HIP_PIX_FMT_MONOCHROME : UHDR_HIP_PIX_FMT_YUV420;
+    return out == nullptr || out_capacity < *need ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
+  }
+  if (info->gray) return UHDR_HIP_UNKNOWN_ERROR;   // jpegdecoderhelper.cpp:258-270: YCbCr 4:2:0 only
+  *need = luma * 4;
+  memset(desc, 0, sizeof(*desc));
+  desc->data = out; desc->width = w; desc->height = h; desc->colorGamut = UHDR_HIP_CG_UNSPECIFIED; desc->luma_stride = w;
+  desc->pixelFormat = UHDR_HIP_PIX_FMT_UNSPECIFIED;
+  if (out == nullptr || out_capacity < *need) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  if ((w | h) & 1) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return UHDR_HIP_NO_ERROR;
+}
+
+// the decode batch's pool slots: decoder workspaces, YCbCr planes (of an RGBA decode or a host caller), RGBA staging of a host
+// caller, jpeg::decode_device_batch's scratch
+enum : size_t { kDecWs = 0, kDecPlanes, kDecRgba, kDecScratch };
+constexpr int kDecRound = kRgbaChunk;   // files per decode round: their RGBA conversion is one launch
+
+size_t dec_ycc_bytes(const jpeg::DecInfo& info) {
+  const size_t luma = (size_t)info.w * (size_t)info.h;
+  return info.gray ? luma : luma + 2 * (luma / 4);
+}
+// what one file holds of its round
+size_t dec_round_bytes(const jpeg::DecInfo& info, bool rgba, bool host_out, size_t need) {
+  jpeg::DecLayout l;
+  size_t b = jpeg::dec_workspace_bytes(info, &l);
+  if (rgba || host_out) b += dec_ycc_bytes(info) + 64;
+  if (rgba && host_out) b += need;
+  return b;
+}
+
+// One round of uhdr_hip_jpeg_decode_batch: files idx[0, m) (m <= kDecRound) through one jpeg::decode_device_batch, their RGBA
+// conversion through one k_ycc420_rgba_batch launch, then one synchronisation.  A file whose device decode fails gets UNKNOWN_ERROR
+// in st_; a non-zero return is an error of the device or the runtime.
+int jpeg_decode_round(DeviceState* st, hipStream_t s, bool rgba, bool host_out, const void* const* jpeg, void* const* out,
+                      const jpeg::DecInfo* info, const size_t* need, const int* idx, int m, int* st_) {
+  std::vector<jpeg::DecLayout> lay((size_t)m);
+  std::vector<size_t> ws_off((size_t)m), pl_off((size_t)m), rg_off((size_t)m);
+  size_t ws_total = 0, pl_total = 0, rg_total = 0;
+  for (int k = 0; k < m; ++k) {
+    const int i = idx[k];
+    ws_off[k] = ws_total;
+    ws_total += round_up(jpeg::dec_workspace_bytes(info[i], &lay[k]), 256);
+    pl_off[k] = pl_total;
+    if (rgba || host_out) pl_total += round_up(dec_ycc_bytes(info[i]) + 64, 256);
+    rg_off[k] = rg_total;
+    if (rgba && host_out) rg_total += round_up(need[i], 256);
+  }
+  int rc;
+  if ((rc = pool_reserve(st, kDecWs, ws_total)) != 0) return rc;
+  if ((rc = pool_reserve(st, kDecPlanes, pl_total)) != 0) return rc;
+  if ((rc = pool_reserve(st, kDecRgba, rg_total)) != 0) return rc;
+  if ((rc = pool_reserve(st, kDecScratch, jpeg::dec_batch_scratch_bytes(m, lay.data()))) != 0) return rc;
+  std::vector<const jpeg::DecInfo*> infos((size_t)m);
+  std::vector<uint8_t*> wss((size_t)m);
+  std::vector<jpeg::DecPlane> planes(3 * (size_t)m);
+  std::vector<jpeg::DecPlane (*)[3]> pl((size_t)m);
+  std::vector<uint8_t*> ycc((size_t)m);
+  auto mk = [](uint8_t* p, size_t pw, size_t ph) {
+    jpeg::DecPlane q;
+    q.p = p; q.w = (int)pw; q.h = (int)ph; q.stride = (int)pw;
+    q.aligned8 = (reinterpret_cast<uintptr_t>(p) % 8 == 0 && pw % 8 == 0) ? 1 : 0;
+    return q;
+  };
+  for (int k = 0; k < m; ++k) {
+    const int i = idx[k];
+    const jpeg::DecInfo& in = info[i];
+    const size_t w = (size_t)in.w, h = (size_t)in.h, luma = w * h, chroma = luma / 4;
+    infos[k] = &in;
+    wss[k] = static_cast<uint8_t*>(st->pool[kDecWs]) + ws_off[k];
+    if (in.scan_bytes)
+      HIP_TRY(hipMemcpyAsync(wss[k] + lay[k].src, static_cast<const uint8_t*>(jpeg[i]) + in.scan_offset, in.scan_bytes, hipMemcpyHostToDevice, s));
+    // YCbCr to a device caller: straight into its buffer
+    ycc[k] = rgba || host_out ? static_cast<uint8_t*>(st->pool[kDecPlanes]) + pl_off[k] : static_cast<uint8_t*>(out[i]);
+    jpeg::DecPlane* p = &planes[3 * (size_t)k];
+    memset(p, 0, 3 * sizeof(jpeg::DecPlane));
+    p[0] = mk(ycc[k], w, h);
+    if (!in.gray) { p[1] = mk(ycc[k] + luma, w / 2, h / 2); p[2] = mk(ycc[k] + luma + chroma, w / 2, h / 2); }
+    pl[k] = reinterpret_cast<jpeg::DecPlane (*)[3]>(p);
+  }
+  std::vector<int> image_rc((size_t)m, 0);
+  hipError_t herr = hipSuccess;
+  const int drc = jpeg::decode_device_batch(m, infos.data(), lay.data(), wss.data(), pl.data(), s, static_cast<uint8_t*>(st->pool[kDecScratch]), &herr,
+                                            image_rc.data());
+  if (drc > 0) { set_err("uhdr_hip_jpeg_decode_batch", herr); return UHDR_HIP_UNKNOWN_ERROR; }
+  YccRgbaBatch b;
+  int nb = 0;
+  std::vector<uint8_t*> res((size_t)m, nullptr);   // where each good file's output lies on the device
+  for (int k = 0; k < m; ++k) {
+    const int i = idx[k];
+    if (image_rc[k] != 0) {
+      st_[i] = UHDR_HIP_UNKNOWN_ERROR;
+      snprintf(t_err, sizeof(t_err), "uhdr_hip_jpeg_decode_batch: corrupt entropy-coded data");
+      continue;
+    }
+    res[k] = ycc[k];
+    if (rgba) {   // libjpeg-turbo's DECODE_TO_RGBA on the planes just decoded
+      const uint32_t w = (uint32_t)info[i].w, h = (uint32_t)info[i].h;
+      const size_t luma = (size_t)w * h;
+      res[k] = host_out ? static_cast<uint8_t*>(st->pool[kDecRgba]) + rg_off[k] : static_cast<uint8_t*>(out[i]);
+      b.img[nb++] = YccRgbaImage{ycc[k], ycc[k] + luma, ycc[k] + luma + luma / 4, res[k], w, h, w, w / 2};
+    }
+  }
+  HIP_TRY(launch_ycc420_to_rgba_batch(b, nb, s));
+  if (host_out)
+    for (int k = 0; k < m; ++k)
+      if (res[k] != nullptr) HIP_TRY(hipMemcpyAsync(out[idx[k]], res[k], need[idx[k]], hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return UHDR_HIP_NO_ERROR;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1433,6 +1748,73 @@ int uhdr_hip_jpeg_decode_rgba(const void* jpeg, size_t jpeg_size, void* out, siz
   if (host) HIP_TRY(hipMemcpyAsync(out, dst, need, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return UHDR_HIP_NO_ERROR;
+}
+
+// uhdr_hip_jpeg_decode (YCBCR) or uhdr_hip_jpeg_decode_rgba (RGBA) for n files in one call: every file's status, bytes and
+// descriptor those of the single call; the headers are parsed by a few host threads, the files of a round share every decoder
+// launch (jpeg::decode_device_batch) and one RGBA conversion launch
+int uhdr_hip_jpeg_decode_batch(int n, const void* const* jpeg, const size_t* jpeg_size, int decode_to, void* const* out, const size_t* out_capacity,
+                               uhdr_hip_image_t* descs, int* status, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (jpeg == nullptr || jpeg_size == nullptr || descs == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
+  if (decode_to != UHDR_HIP_DECODE_TO_RGBA && decode_to != UHDR_HIP_DECODE_TO_YCBCR) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  const bool rgba = decode_to == UHDR_HIP_DECODE_TO_RGBA;
+  std::vector<jpeg::DecInfo> info((size_t)n);
+  std::vector<size_t> need((size_t)n, 0);
+  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
+  {
+    auto parse_range = [&](int lo, int hi) {
+      for (int i = lo; i < hi; ++i) {
+        void* o = out != nullptr ? out[i] : nullptr;
+        const size_t cap = out != nullptr && out_capacity != nullptr ? out_capacity[i] : 0;
+        try {
+          st_[i] = jpeg_decode_host(jpeg[i], jpeg_size[i], rgba, o, cap, &descs[i], &info[i], &need[i]);
+        } catch (const std::bad_alloc&) {
+          st_[i] = UHDR_HIP_UNKNOWN_ERROR;
+        }
+      }
+    };
+    const int nthreads = n >= 2 ? std::min(n, 8) : 1;
+    if (nthreads <= 1) {
+      parse_range(0, n);
+    } else {
+      std::vector<std::thread> workers;
+      for (int t = 0; t < nthreads; ++t) workers.emplace_back(parse_range, (int)((long)n * t / nthreads), (int)((long)n * (t + 1) / nthreads));
+      for (auto& w : workers) w.join();
+    }
+  }
+  std::vector<int> live;
+  for (int i = 0; i < n; ++i)
+    if (st_[i] == UHDR_HIP_NO_ERROR) live.push_back(i);
+  auto result = [&]() {
+    int first = UHDR_HIP_NO_ERROR;
+    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
+    return first;
+  };
+  if (live.empty()) return result();   // every file stopped at its checks or its size probe: the device is not touched
+  DeviceState* st = nullptr;
+  int rc = current_state(&st);
+  size_t r0 = 0;   // live files [0, r0) are finished
+  if (rc == UHDR_HIP_NO_ERROR) {
+    CodecLease lease(st);
+    st = lease.get();
+    rc = st == nullptr ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE;
+    while (rc == UHDR_HIP_NO_ERROR && r0 < live.size()) {   // rounds of <= kDecRound files and <= kCodecRoundBytes
+      size_t r1 = r0, bytes = 0;
+      while (r1 < live.size() && r1 - r0 < (size_t)kDecRound) {
+        const size_t b = dec_round_bytes(info[live[r1]], rgba, host_out, need[live[r1]]);
+        if (r1 > r0 && bytes + b > kCodecRoundBytes) break;
+        bytes += b;
+        ++r1;
+      }
+      rc = jpeg_decode_round(st, s, rgba, host_out, jpeg, out, info.data(), need.data(), &live[r0], (int)(r1 - r0), st_.data());
+      if (rc == UHDR_HIP_NO_ERROR) r0 = r1;
+    }
+    if (rc != UHDR_HIP_NO_ERROR) (void)hipStreamSynchronize(s);   // nothing of a failed round may still be writing into the pools
+  }
+  for (size_t k = r0; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
+  return result();
 }
 
 // JpegR::decodeJPEGR (jpegr.cpp:655-822) for n files at once.  A JPEG decode on the device is latency-bound (tens of synchronisation

@@ -229,6 +229,20 @@ static_assert(sizeof(CvtBatch) <= 4096 && sizeof(ToneBatch) <= 4096, "toneMap / 
 // decoded 4:2:0 planes -> RGBA8888 with libjpeg-turbo's arithmetic (k_ycc420_rgba); w, h even, strides in bytes
 hipError_t launch_ycc420_to_rgba(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t w, uint32_t h, uint32_t y_stride,
                                  uint32_t c_stride, uint8_t* rgba, hipStream_t s);
+// the same for up to kRgbaChunk images of any (even) sizes in one launch (k_ycc420_rgba_batch: grid.z = image)
+constexpr int kRgbaChunk = 64;
+struct YccRgbaImage {
+  const uint8_t* y;
+  const uint8_t* cb;
+  const uint8_t* cr;
+  uint8_t* rgba;        // w * h * 4 bytes, rows packed
+  uint32_t w, h, ys, cs;
+};
+struct YccRgbaBatch {
+  YccRgbaImage img[kRgbaChunk];
+};
+static_assert(sizeof(YccRgbaBatch) <= 4096, "k_ycc420_rgba_batch's kernel arguments exceed the kernarg segment");
+hipError_t launch_ycc420_to_rgba_batch(const YccRgbaBatch& b, int n, hipStream_t s);
 hipError_t upload_idw4(const float* tables /* 4*64 floats */);
 hipError_t launch_effect(const FxJobs& j, hipStream_t s);
 hipError_t launch_eval_transfer(int fn, const float* in, float* out, size_t n, const EvalConsts& ec, hipStream_t s);
