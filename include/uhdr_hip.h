@@ -424,6 +424,28 @@ int uhdr_hip_jpegr_encode_api1(const uhdr_hip_image_t* p010_image, const uhdr_hi
 int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf,
                                 int quality, const void* const* exif, const size_t* exif_size, void* const* out,
                                 const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream);
+/* encodeJPEGR API-2 (yuv420_images != NULL) or API-3 (yuv420_images == NULL) for n files in one call, and API-x for n files in one
+ * call (no reference counterparts).  The conventions of uhdr_hip_jpegr_encode_batch: arrays indexed by file, hdr_tf / quality shared,
+ * everything else per file; planes in mem_space, compressed inputs, exif and out[i] HOST memory; every file's status, size and bytes
+ * those of uhdr_hip_jpegr_encode_api2 / _api3 / _apix with the same arguments (ERROR_INSUFFICIENT_RESOURCE with the exact size
+ * included); status optional, the return value the first status that is not NO_ERROR; a file that fails does not disturb the others.
+ * Call-level errors, before any file is looked at (status untouched): BAD_PTR for n < 0 or a NULL required array where n > 0
+ * (API-2/3: p010_images, sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, out, out_capacity, out_size; API-x: yuv420_images,
+ * gainmap_images, metadata, out, out_capacity, out_size; exif != NULL with exif_size == NULL), then API-x's
+ * INVALID_QUALITY_FACTOR.  Every per-file check that needs no device runs first, also those the single calls make after their
+ * device work (API-2's checks of the SDR JPEG, API-x's after its NULL pointers); only API-3's gamut and size checks follow its
+ * decode, as in the single call.  A batch whose every file stops at such a check does not touch the device.  Rounds of up to 64
+ * files and 2 GiB of workspace and staging, sorted into runs of equal size and gamuts: API-3's JPEGs share one decoder launch
+ * set, the generate launches are shared by equal files, every JPEG compression of a round goes through one launch set, one
+ * synchronisation per round (plus the decoder's own), and the containers are assembled by up to 8 host threads. */
+int uhdr_hip_jpegr_encode_sdr_jpeg_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images,
+                                         const void* const* sdr_jpeg, const size_t* sdr_jpeg_size, const int* sdr_jpeg_gamut,
+                                         int hdr_tf, void* const* out, const size_t* out_capacity, size_t* out_size,
+                                         int* status, int mem_space, void* stream);
+int uhdr_hip_jpegr_encode_apix_batch(int n, const uhdr_hip_image_t* yuv420_images, const uhdr_hip_image_t* gainmap_images,
+                                     const uhdr_hip_metadata_t* metadata, int quality, const void* const* exif,
+                                     const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
+                                     int* status, int mem_space, void* stream);
 int uhdr_hip_jpegr_encode_api2(const uhdr_hip_image_t* p010_image, const uhdr_hip_image_t* yuv420_image, const void* sdr_jpeg,
                                size_t sdr_jpeg_size, int sdr_jpeg_gamut, int hdr_tf, void* out, size_t out_capacity,
                                size_t* out_size, int mem_space, void* stream);

@@ -104,6 +104,11 @@ SIGNATURES = {
                                              C.c_void_p]),
     "uhdr_hip_jpegr_encode_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "uhdr_hip_jpegr_encode_sdr_jpeg_batch": (C.c_int, [C.c_int, _IP, _IP, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int,
+                                                       C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int,
+                                                       C.c_void_p]),
+    "uhdr_hip_jpegr_encode_apix_batch": (C.c_int, [C.c_int, _IP, _IP, _MP, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                                   C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "uhdr_hip_jpegr_encode_api2": (C.c_int, [_IP, _IP, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int,
                                              C.c_void_p]),
     "uhdr_hip_jpegr_encode_api3": (C.c_int, [_IP, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_void_p]),

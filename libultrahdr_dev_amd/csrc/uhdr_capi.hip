@@ -1205,6 +1205,25 @@ size_t enc_stage_bytes(const uhdr_hip_image_t& img) {
   const size_t luma = round_up(g.dls * img.height, 256);
   return img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME ? luma : luma + round_up(g.dcs * img.height + 64, 256);
 }
+// stage_encoder_in's bytes and pitches for a host image (luma_stride set), into the enc_stage_bytes(img) bytes at dy; *d: the staged image
+int stage_encoder_slice(uint8_t* dy, const uhdr_hip_image_t& img, uhdr_hip_image_t* d, hipStream_t s) {
+  const EncStageCols g = enc_stage_cols(img);
+  const size_t hh = img.height;
+  int rc;
+  if ((rc = h2d_plane(dy, g.dls, img.data, img.luma_stride, g.ycols, hh, 1, s)) != 0) return rc;
+  *d = img;
+  d->data = dy;
+  d->luma_stride = g.dls;
+  if (img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME) return UHDR_HIP_NO_ERROR;
+  const uint8_t* hu = static_cast<const uint8_t*>(img.chroma_data);
+  const size_t cs = img.chroma_stride;
+  uint8_t* du = dy + round_up(g.dls * hh, 256);
+  if ((rc = h2d_plane(du, g.dcs, hu, cs, g.ccols, hh / 2, 1, s)) != 0) return rc;
+  if ((rc = h2d_plane(du + g.dcs * (hh / 2), g.dcs, hu + cs * hh / 2, cs, g.ccols, hh / 2, 1, s)) != 0) return rc;
+  d->chroma_data = du;
+  d->chroma_stride = g.dcs;
+  return UHDR_HIP_NO_ERROR;
+}
 // what one image holds of its round: encoder workspace, staged planes, page-locked staging of the file
 size_t enc_round_bytes(const uhdr_hip_image_t& img, bool host_in, bool host_out) {
   jpeg::Job j;
@@ -1235,23 +1254,9 @@ int jpeg_encode_round(DeviceState* st, hipStream_t s, bool host_in, bool host_ou
     const int i = idx[k];
     const uhdr_hip_image_t img = enc_image(images[i]);
     uhdr_hip_image_t d = img;
-    if (host_in) {   // stage_encoder_in's bytes and pitches, into the round's slice
-      const EncStageCols g = enc_stage_cols(img);
-      const size_t hh = img.height;
-      uint8_t* dy = static_cast<uint8_t*>(st->pool[kEncYuv]) + o;
+    if (host_in) {   // into the round's slice
       int rc;
-      if ((rc = h2d_plane(dy, g.dls, img.data, img.luma_stride, g.ycols, hh, 1, s)) != 0) return rc;
-      d.data = dy;
-      d.luma_stride = g.dls;
-      if (img.pixelFormat != UHDR_HIP_PIX_FMT_MONOCHROME) {
-        const uint8_t* hu = static_cast<const uint8_t*>(img.chroma_data);
-        const size_t cs = img.chroma_stride;
-        uint8_t* du = dy + round_up(g.dls * hh, 256);
-        if ((rc = h2d_plane(du, g.dcs, hu, cs, g.ccols, hh / 2, 1, s)) != 0) return rc;
-        if ((rc = h2d_plane(du + g.dcs * (hh / 2), g.dcs, hu + cs * hh / 2, cs, g.ccols, hh / 2, 1, s)) != 0) return rc;
-        d.chroma_data = du;
-        d.chroma_stride = g.dcs;
-      }
+      if ((rc = stage_encoder_slice(static_cast<uint8_t*>(st->pool[kEncYuv]) + o, img, &d, s)) != 0) return rc;
       o += enc_stage_bytes(img);
     }
     const void* ip = icc ? icc[i] : nullptr;
@@ -2273,6 +2278,82 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
   return result();
 }
 
+// ---- the host-side checks of API-2, API-3, API-4 and API-x, shared by the single calls and the batches ----------------------------
+// API-4's checks on the SDR JPEG (jpegr.cpp:520-541), which API-2 and API-3 make as well: *icc receives the ICC profile the container
+// adds to a JPEG that carries none
+int sdr_jpeg_check(const void* sdr_jpeg, size_t sdr_jpeg_size, int sdr_jpeg_gamut, std::vector<uint8_t>* icc) {
+  const uint8_t* pj = static_cast<const uint8_t*>(sdr_jpeg);
+  if (!jpegr::has_valid_header(pj, sdr_jpeg_size)) return UHDR_HIP_ERROR_DECODE_ERROR;                            // :520-524
+  const uint8_t* have = nullptr;
+  size_t have_len = 0;
+  icc->clear();
+  if (!jpegr::first_icc(pj, sdr_jpeg_size, &have, &have_len)) {          // :527-541
+    if (sdr_jpeg_gamut <= UHDR_HIP_CG_UNSPECIFIED || sdr_jpeg_gamut > UHDR_HIP_CG_BT2100) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+    jpegr::icc_profile_srgb_transfer(sdr_jpeg_gamut, *icc);
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
+// API-2's checks before its device work (jpegr.cpp:390-397, then areInputArgumentsValid)
+int api2_check(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, const void* sdr_jpeg, int hdr_tf, const void* out, const size_t* out_size) {
+  if (yuv == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                              // :390-393
+  if (sdr_jpeg == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                         // :394-397
+  return check_encode_inputs(p010, yuv, hdr_tf, out, out_size);
+}
+
+// API-3's checks before its device decode (jpegr.cpp:443-462): uhdr_hip_jpeg_decode's size probe on the SDR JPEG, host work, its
+// header into *info
+int api3_check(const uhdr_hip_image_t* p010, const void* sdr_jpeg, size_t sdr_jpeg_size, int hdr_tf, const void* out, const size_t* out_size,
+               jpeg::DecInfo* info) {
+  if (sdr_jpeg == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                         // :443-446
+  int rc = check_encode_inputs(p010, nullptr, hdr_tf, out, out_size);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  uhdr_hip_image_t desc;
+  size_t need = 0;
+  try {
+    rc = jpeg_decode_host(sdr_jpeg, sdr_jpeg_size, false, nullptr, 0, &desc, info, &need);
+  } catch (const std::bad_alloc&) {
+    rc = UHDR_HIP_UNKNOWN_ERROR;
+  }
+  if (rc == UHDR_HIP_ERROR_UNSUPPORTED_FEATURE) return rc;
+  if (rc != UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE || desc.pixelFormat != UHDR_HIP_PIX_FMT_YUV420 || desc.width == 0 || desc.height == 0)
+    return UHDR_HIP_ERROR_DECODE_ERROR;
+  return UHDR_HIP_NO_ERROR;
+}
+
+// API-3's checks after its decode of a w x h JPEG (jpegr.cpp:467-499): the SDR gamut into *gamut -- the ICC profile's when there is
+// one (it must agree with a configured gamut), else the configured one -- then the P010 size against the JPEG's
+int api3_check_decoded(const uhdr_hip_image_t& p010, const void* sdr_jpeg, size_t sdr_jpeg_size, int sdr_jpeg_gamut, size_t w, size_t h,
+                       int* gamut) {
+  const uint8_t* icc = nullptr;
+  size_t icc_len = 0;
+  if (jpegr::first_icc(static_cast<const uint8_t*>(sdr_jpeg), sdr_jpeg_size, &icc, &icc_len)) {
+    const int cg = jpegr::gamut_from_icc(icc, icc_len);
+    if (cg == UHDR_HIP_CG_UNSPECIFIED || (sdr_jpeg_gamut != UHDR_HIP_CG_UNSPECIFIED && sdr_jpeg_gamut != cg)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+    *gamut = cg;
+  } else {
+    if (sdr_jpeg_gamut <= UHDR_HIP_CG_UNSPECIFIED || sdr_jpeg_gamut > UHDR_HIP_CG_BT2100) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+    *gamut = sdr_jpeg_gamut;
+  }
+  if (p010.width != w || p010.height != h) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;                             // :496-499
+  return UHDR_HIP_NO_ERROR;
+}
+
+// API-x's checks after its NULL pointers (jpegr.cpp:590-611): *yuv and *map come back as they are compressed (strides and chroma
+// defaulted, the map a single plane), *icc holds the SDR image's ICC profile
+int apix_check(const uhdr_hip_image_t& yuv_in, const uhdr_hip_image_t& gainmap, uhdr_hip_image_t* yuv, uhdr_hip_image_t* map,
+               std::vector<uint8_t>* icc) {
+  *yuv = yuv_in;
+  default_yuv(yuv);
+  uhdr_hip_image_t g = gainmap;
+  if (g.luma_stride == 0) g.luma_stride = g.width;
+  *map = gainmap_jpeg(g, g.luma_stride).img;
+  if (!encodable(*map)) return UHDR_HIP_ERROR_ENCODE_ERROR;                                                       // :590-597
+  if (!jpegr::icc_profile_srgb_transfer(yuv->colorGamut, *icc)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;          // :599-600
+  if (!encodable(*yuv)) return UHDR_HIP_ERROR_ENCODE_ERROR;                                                       // :602-611
+  return UHDR_HIP_NO_ERROR;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2307,26 +2388,18 @@ int uhdr_hip_jpegr_encode_api4(const void* sdr_jpeg, size_t sdr_jpeg_size, int s
                                const uhdr_hip_metadata_t* metadata, void* out, size_t out_capacity, size_t* out_size) {
   if (sdr_jpeg == nullptr || gainmap_jpeg == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                              // :505-512
   if (out == nullptr || out_size == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                       // :513-516
-  const uint8_t* pj = static_cast<const uint8_t*>(sdr_jpeg);
-  if (!jpegr::has_valid_header(pj, sdr_jpeg_size)) return UHDR_HIP_ERROR_DECODE_ERROR;                            // :520-524
-  const uint8_t* have = nullptr;
-  size_t have_len = 0;
   std::vector<uint8_t> icc;
-  if (!jpegr::first_icc(pj, sdr_jpeg_size, &have, &have_len)) {          // :527-541
-    if (sdr_jpeg_gamut <= UHDR_HIP_CG_UNSPECIFIED || sdr_jpeg_gamut > UHDR_HIP_CG_BT2100) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
-    jpegr::icc_profile_srgb_transfer(sdr_jpeg_gamut, icc);
-  }
+  const int rc = sdr_jpeg_check(sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, &icc);                                   // :520-541
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   if (metadata == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                         // :955-958
-  return jpegr::append_gainmap_to(pj, sdr_jpeg_size, static_cast<const uint8_t*>(gainmap_jpeg), gainmap_jpeg_size, nullptr, 0,
-                                  icc.empty() ? nullptr : icc.data(), icc.size(), *metadata, static_cast<uint8_t*>(out), out_capacity, out_size);
+  return jpegr::append_gainmap_to(static_cast<const uint8_t*>(sdr_jpeg), sdr_jpeg_size, static_cast<const uint8_t*>(gainmap_jpeg), gainmap_jpeg_size,
+                                  nullptr, 0, icc.empty() ? nullptr : icc.data(), icc.size(), *metadata, static_cast<uint8_t*>(out), out_capacity, out_size);
 }
 
 // JpegR::encodeJPEGR API-2 (jpegr.cpp:384-437)
 int uhdr_hip_jpegr_encode_api2(const uhdr_hip_image_t* p010_in, const uhdr_hip_image_t* yuv_in, const void* sdr_jpeg, size_t sdr_jpeg_size,
                                int sdr_jpeg_gamut, int hdr_tf, void* out, size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
-  if (yuv_in == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                           // :390-393
-  if (sdr_jpeg == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                         // :394-397
-  int rc = check_encode_inputs(p010_in, yuv_in, hdr_tf, out, out_size);
+  int rc = api2_check(p010_in, yuv_in, sdr_jpeg, hdr_tf, out, out_size);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   uhdr_hip_image_t p010 = *p010_in, yuv = *yuv_in;
   default_p010(&p010);
@@ -2350,41 +2423,27 @@ int uhdr_hip_jpegr_encode_api2(const uhdr_hip_image_t* p010_in, const uhdr_hip_i
 // JpegR::encodeJPEGR API-3 (jpegr.cpp:439-500): the SDR rendition arrives as a JPEG only and is decoded on the device
 int uhdr_hip_jpegr_encode_api3(const uhdr_hip_image_t* p010_in, const void* sdr_jpeg, size_t sdr_jpeg_size, int sdr_jpeg_gamut, int hdr_tf,
                                void* out, size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
-  if (sdr_jpeg == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                         // :443-446
-  int rc = check_encode_inputs(p010_in, nullptr, hdr_tf, out, out_size);
+  jpeg::DecInfo info;
+  int rc = api3_check(p010_in, sdr_jpeg, sdr_jpeg_size, hdr_tf, out, out_size, &info);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   uhdr_hip_image_t p010 = *p010_in;
   default_p010(&p010);
   const uint8_t* pj = static_cast<const uint8_t*>(sdr_jpeg);
 
-  // :457-462 decode; a header probe first for the size (host work: an unreadable file is reported without a device)
-  uhdr_hip_image_t ydesc;
-  memset(&ydesc, 0, sizeof(ydesc));
-  rc = uhdr_hip_jpeg_decode(pj, sdr_jpeg_size, nullptr, 0, &ydesc, UHDR_HIP_MEM_DEVICE, stream);
-  if (rc == UHDR_HIP_ERROR_UNSUPPORTED_FEATURE) return rc;
-  if (rc != UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE || ydesc.pixelFormat != UHDR_HIP_PIX_FMT_YUV420 || ydesc.width == 0 || ydesc.height == 0)
-    return UHDR_HIP_ERROR_DECODE_ERROR;
+  // :457-462 decode
   DeviceState* st = nullptr;
   if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   CodecLease lease(st);
   if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t w = ydesc.width, h = ydesc.height, ybytes = w * h + 2 * (w * h / 4);
+  const size_t w = (size_t)info.w, h = (size_t)info.h, ybytes = w * h + 2 * (w * h / 4);
   if ((rc = stage_reserve(st, 8, ybytes + 64)) != 0) return rc;
+  uhdr_hip_image_t ydesc;
   if (uhdr_hip_jpeg_decode(pj, sdr_jpeg_size, st->stage[8], ybytes, &ydesc, UHDR_HIP_MEM_DEVICE, stream) != UHDR_HIP_NO_ERROR)
     return UHDR_HIP_ERROR_DECODE_ERROR;
-  // :467-488 the gamut: the ICC profile's when there is one (and it must agree with a configured gamut), else the configured one
-  const uint8_t* icc = nullptr;
-  size_t icc_len = 0;
-  if (jpegr::first_icc(pj, sdr_jpeg_size, &icc, &icc_len)) {
-    const int cg = jpegr::gamut_from_icc(icc, icc_len);
-    if (cg == UHDR_HIP_CG_UNSPECIFIED || (sdr_jpeg_gamut != UHDR_HIP_CG_UNSPECIFIED && sdr_jpeg_gamut != cg)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
-    ydesc.colorGamut = cg;
-  } else {
-    if (sdr_jpeg_gamut <= UHDR_HIP_CG_UNSPECIFIED || sdr_jpeg_gamut > UHDR_HIP_CG_BT2100) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
-    ydesc.colorGamut = sdr_jpeg_gamut;
-  }
-  if (p010.width != w || p010.height != h) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;                             // :496-499
+  int gamut = UHDR_HIP_CG_UNSPECIFIED;
+  if ((rc = api3_check_decoded(p010, sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, w, h, &gamut)) != UHDR_HIP_NO_ERROR) return rc;  // :467-499
+  ydesc.colorGamut = gamut;
   uhdr_hip_image_t dp = p010;
   if (mem_space != UHDR_HIP_MEM_DEVICE && (rc = stage_p010_in(st, 2, p010, &dp, s)) != 0) return rc;
   uhdr_hip_metadata_t md;
@@ -2401,29 +2460,372 @@ int uhdr_hip_jpegr_encode_apix(const uhdr_hip_image_t* yuv_in, const uhdr_hip_im
   if (gainmap == nullptr || gainmap->data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
   if (metadata == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
   if (out == nullptr || out_size == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  uhdr_hip_image_t yuv = *yuv_in;
-  default_yuv(&yuv);
   DeviceState* st = nullptr;
   int rc;
   if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   CodecLease lease(st);
   if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  uhdr_hip_image_t map = *gainmap;
-  if (map.luma_stride == 0) map.luma_stride = map.width;
+  uhdr_hip_image_t yuv, map;
   std::vector<uint8_t> icc;
+  if ((rc = apix_check(*yuv_in, *gainmap, &yuv, &map, &icc)) != UHDR_HIP_NO_ERROR) return rc;                     // :590-611
   EncJpeg jpg[2] = {EncJpeg{yuv, quality, &icc, yuv.luma_stride, yuv.chroma_stride}, gainmap_jpeg(map, map.luma_stride)};
-  if (!encodable(jpg[1].img)) return UHDR_HIP_ERROR_ENCODE_ERROR;                                                 // :590-597
-  if (!jpegr::icc_profile_srgb_transfer(yuv.colorGamut, icc)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;           // :599-600
-  if (!encodable(yuv)) return UHDR_HIP_ERROR_ENCODE_ERROR;                                                        // :602-611
   if (mem_space != UHDR_HIP_MEM_DEVICE) {   // staged planes, padded by the caller's strides
-    const uhdr_hip_image_t g = jpg[1].img;
     if ((rc = stage_encoder_in(st, 0, yuv, &jpg[0].img, s)) != 0) return rc;
-    if ((rc = stage_encoder_in(st, 2, g, &jpg[1].img, s)) != 0) return rc;
+    if ((rc = stage_encoder_in(st, 2, map, &jpg[1].img, s)) != 0) return rc;
   }
   if (compress_to_host(st, s, 2, jpg) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
   return jpegr::append_gainmap_to(jpg[0].bytes, jpg[0].n, jpg[1].bytes, jpg[1].n, static_cast<const uint8_t*>(exif), exif_size, nullptr, 0, *metadata,
                                   static_cast<uint8_t*>(out), out_capacity, out_size);
+}
+
+}  // extern "C"
+
+namespace {
+// ---- encodeJPEGR API-2 / API-3 / API-x for n files (uhdr_hip_jpegr_encode_sdr_jpeg_batch, uhdr_hip_jpegr_encode_apix_batch) -------
+// Their rounds' pool slots: jpeg_decode_round holds kDecWs .. kDecScratch (0-3) and compress_to_host kEncWs and kEncDesc (0, 1), so
+// the staged P010 planes, the SDR planes (staged, or decoded by API-3) and the gain maps lie in slots that neither touches.  Every slot
+// of a round is reserved before its first enqueue.
+enum : size_t { kSjP010 = kEncP010, kSjSdr = kEncYuv, kSjMap };
+
+// one API-2 / API-3 file
+struct SjFile {
+  int idx = 0;                 // the caller's index
+  uhdr_hip_image_t p010, sdr;  // defaulted P010 and SDR planes (API-2: the caller's YUV420, API-3: the decoded JPEG); device once staged
+  int sdr_gamut = 0;           // what the runs are sorted by (API-3: the ICC profile's gamut, else the configured one)
+  std::vector<uint8_t> icc;    // the ICC profile the container adds (the SDR JPEG carries none)
+  size_t o_p010 = 0, o_sdr = 0, o_map = 0;   // the file's slices of its round
+};
+
+// the staging of stage_p010_in / stage_yuv420_in (pitches 64-aligned; the V plane at u + cp * (h / 2)), as one slice each
+size_t sj_p010_bytes(size_t w, size_t h) { return round_up(round_up(w, 64) * h * 2, 256) + round_up(round_up(w, 64) * (h / 2) * 2, 256); }
+size_t sj_yuv_bytes(size_t w, size_t h) { return round_up(round_up(w, 64) * h, 256) + round_up(round_up(w / 2, 64) * (h + 1), 256); }
+size_t sj_map_bytes(size_t w, size_t h) { return round_up((w / 4) * (h / 4) + 64, 256); }
+// what one file holds of its round: P010 / SDR planes, decoder workspace, gain map, its encoder workspace and page-locked staging
+size_t sj_round_bytes(const SjFile& e, const jpeg::DecInfo* info, bool host) {
+  const size_t w = e.p010.width, h = e.p010.height;
+  uhdr_hip_image_t map;
+  memset(&map, 0, sizeof(map));
+  map.width = w / 4; map.height = h / 4; map.pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
+  size_t b = sj_map_bytes(w, h) + enc_round_bytes(map, false, true);
+  if (host) b += sj_p010_bytes(w, h) + (info ? 0 : sj_yuv_bytes(w, h));
+  if (info) {
+    jpeg::DecLayout l;
+    b += jpeg::dec_workspace_bytes(*info, &l) + round_up(dec_ycc_bytes(*info) + 64, 256);
+  }
+  return b;
+}
+
+// runs fn(lo, hi) over [0, n) on up to 8 host threads
+template <class F>
+void on_host_threads(int n, F fn) {
+  const int nthreads = n >= 2 ? std::min(n, 8) : 1;
+  if (nthreads <= 1) { fn(0, n); return; }
+  std::vector<std::thread> workers;
+  for (int t = 0; t < nthreads; ++t) workers.emplace_back(fn, (int)((long)n * t / nthreads), (int)((long)n * (t + 1) / nthreads));
+  for (auto& w : workers) w.join();
+}
+
+// One round of API-2 / API-3 files f[0, m): API-3's decode (one jpeg::decode_device_batch through jpeg_decode_round, with its own
+// synchronisations) and the checks that follow it, the staging of host planes, generateGainMap for the files still live (equal files
+// share a launch), their gain maps through one compress_to_host, then the containers around the caller's SDR JPEGs.  Statuses go
+// to st_; a non-zero return is an error of the device or the runtime.
+int sdr_jpeg_round(DeviceState* st, hipStream_t s, bool api3, bool host, int hdr_tf, SjFile* f, int m, const void* const* sdr_jpeg,
+                   const size_t* sdr_jpeg_size, const int* sdr_jpeg_gamut, const jpeg::DecInfo* info, void** dec_out, const size_t* dec_need,
+                   void* const* out, const size_t* out_capacity, size_t* out_size, int* st_) {
+  int rc;
+  size_t p010_total = 0, sdr_total = 0, map_total = 0;
+  for (int k = 0; k < m; ++k) {
+    SjFile& e = f[k];
+    const size_t w = e.p010.width, h = e.p010.height;
+    e.o_p010 = p010_total; e.o_sdr = sdr_total; e.o_map = map_total;
+    if (host) p010_total += sj_p010_bytes(w, h);
+    if (api3) sdr_total += round_up(dec_ycc_bytes(info[e.idx]) + 64, 256);
+    else if (host) sdr_total += sj_yuv_bytes(w, h);
+    map_total += sj_map_bytes(w, h);
+  }
+  if ((rc = pool_reserve(st, kSjMap, map_total)) != 0) return rc;   // (the last slot: the pool has all of them from here on)
+  if (p010_total && (rc = pool_reserve(st, kSjP010, p010_total)) != 0) return rc;
+  if (sdr_total && (rc = pool_reserve(st, kSjSdr, sdr_total)) != 0) return rc;
+  uint8_t* const p010_pool = static_cast<uint8_t*>(st->pool[kSjP010]);
+  uint8_t* const sdr_pool = static_cast<uint8_t*>(st->pool[kSjSdr]);
+  uint8_t* const map_pool = static_cast<uint8_t*>(st->pool[kSjMap]);
+
+  std::vector<int> live;   // the round's files that reach generateGainMap
+  if (api3) {   // :457-462, every file of the round in one decode; the planes as uhdr_hip_jpeg_decode lays them out
+    std::vector<int> idx((size_t)m);
+    for (int k = 0; k < m; ++k) {
+      idx[k] = f[k].idx;
+      dec_out[f[k].idx] = sdr_pool + f[k].o_sdr;
+    }
+    if ((rc = jpeg_decode_round(st, s, false, false, sdr_jpeg, dec_out, info, dec_need, idx.data(), m, st_)) != 0) return rc;
+    for (int k = 0; k < m; ++k) {
+      SjFile& e = f[k];
+      const int i = e.idx;
+      if (st_[i] != UHDR_HIP_NO_ERROR) { st_[i] = UHDR_HIP_ERROR_DECODE_ERROR; continue; }   // corrupt entropy-coded data
+      const size_t w = (size_t)info[i].w, h = (size_t)info[i].h;
+      uint8_t* y = sdr_pool + e.o_sdr;
+      memset(&e.sdr, 0, sizeof(e.sdr));
+      e.sdr.data = y; e.sdr.chroma_data = y + w * h;
+      e.sdr.width = w; e.sdr.height = h; e.sdr.luma_stride = w; e.sdr.chroma_stride = w / 2;
+      e.sdr.pixelFormat = UHDR_HIP_PIX_FMT_YUV420;
+      int gamut = UHDR_HIP_CG_UNSPECIFIED;
+      rc = api3_check_decoded(e.p010, sdr_jpeg[i], sdr_jpeg_size[i], sdr_jpeg_gamut[i], w, h, &gamut);   // :467-499
+      if (rc == UHDR_HIP_NO_ERROR) rc = sdr_jpeg_check(sdr_jpeg[i], sdr_jpeg_size[i], sdr_jpeg_gamut[i], &e.icc);
+      st_[i] = rc;
+      if (rc != UHDR_HIP_NO_ERROR) continue;
+      e.sdr.colorGamut = gamut;
+      live.push_back(k);
+    }
+  } else {
+    for (int k = 0; k < m; ++k) live.push_back(k);
+  }
+  if (live.empty()) return UHDR_HIP_NO_ERROR;
+
+  // host planes: the bytes the single calls stage
+  if (host) {
+    for (const int k : live) {
+      SjFile& e = f[k];
+      const size_t w = e.p010.width, h = e.p010.height, lp = round_up(w, 64);
+      uint8_t* d = p010_pool + e.o_p010;
+      uint8_t* dc = d + round_up(lp * h * 2, 256);
+      if ((rc = h2d_plane(d, lp, e.p010.data, e.p010.luma_stride, w, h, 2, s)) != 0) return rc;
+      if ((rc = h2d_plane(dc, lp, e.p010.chroma_data, e.p010.chroma_stride, w, h / 2, 2, s)) != 0) return rc;
+      e.p010.data = d; e.p010.chroma_data = dc; e.p010.luma_stride = lp; e.p010.chroma_stride = lp;
+      if (api3) continue;
+      const size_t cp = round_up(w / 2, 64), cs = e.sdr.chroma_stride;
+      uint8_t* y = sdr_pool + e.o_sdr;
+      uint8_t* u = y + round_up(lp * h, 256);
+      const uint8_t* hu = static_cast<const uint8_t*>(e.sdr.chroma_data);
+      if ((rc = h2d_plane(y, lp, e.sdr.data, e.sdr.luma_stride, w, h, 1, s)) != 0) return rc;
+      if ((rc = h2d_plane(u, cp, hu, cs, w / 2, h / 2, 1, s)) != 0) return rc;
+      if ((rc = h2d_plane(u + cp * (h / 2), cp, hu + cs * (h / 2), cs, w / 2, h / 2, 1, s)) != 0) return rc;
+      e.sdr.data = y; e.sdr.chroma_data = u; e.sdr.luma_stride = lp; e.sdr.chroma_stride = cp;
+    }
+  }
+  // generateGainMap (:416-427 / :490-492): the files are sorted by size and gamuts, so equal ones share its launches
+  const int ml = (int)live.size();
+  std::vector<uhdr_hip_image_t> a((size_t)ml), b((size_t)ml), c((size_t)ml);
+  for (int j = 0; j < ml; ++j) {
+    const SjFile& e = f[live[j]];
+    a[j] = e.sdr; b[j] = e.p010; c[j] = e.sdr;
+    c[j].data = map_pool + e.o_map;
+  }
+  uhdr_hip_metadata_t md;
+  if ((rc = uhdr_hip_generate_gainmap_batch(ml, a.data(), b.data(), hdr_tf, &md, c.data(), api3 ? 1 : 0, nullptr, s)) != UHDR_HIP_NO_ERROR) return rc;
+  // compressGainMap (:428-434), every map of the round in one compress_to_host
+  std::vector<EncJpeg> gm((size_t)ml);
+  for (int j = 0; j < ml; ++j) {
+    uhdr_hip_image_t g = c[j];
+    g.width = a[j].width / 4; g.height = a[j].height / 4; g.luma_stride = g.width;
+    gm[j] = gainmap_jpeg(g, g.luma_stride);
+  }
+  if (compress_to_host(st, s, ml, gm.data()) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
+  // appendGainMap around the caller's SDR JPEG (API-4, :543-559), straight into the caller's buffers
+  on_host_threads(ml, [&](int lo, int hi) {
+    for (int j = lo; j < hi; ++j) {
+      const SjFile& e = f[live[j]];
+      const int i = e.idx;
+      st_[i] = jpegr::append_gainmap_to(static_cast<const uint8_t*>(sdr_jpeg[i]), sdr_jpeg_size[i], gm[j].bytes, gm[j].n, nullptr, 0,
+                                        e.icc.empty() ? nullptr : e.icc.data(), e.icc.size(), md, static_cast<uint8_t*>(out[i]), out_capacity[i],
+                                        &out_size[i]);
+    }
+  });
+  return UHDR_HIP_NO_ERROR;
+}
+
+// encodeJPEGR API-2 (yuv420_images != NULL) or API-3 for n files: every host check first (API-3's header probes on a few threads),
+// then rounds of up to kEncRound files and kCodecRoundBytes, sorted into runs of equal size and gamuts
+int sdr_jpeg_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, const void* const* sdr_jpeg,
+                   const size_t* sdr_jpeg_size, const int* sdr_jpeg_gamut, int hdr_tf, void* const* out, const size_t* out_capacity,
+                   size_t* out_size, int* status, int mem_space, void* stream) {
+  const bool api3 = yuv420_images == nullptr;
+  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
+  std::vector<jpeg::DecInfo> info(api3 ? (size_t)n : 0);
+  std::vector<void*> dec_out(api3 ? (size_t)n : 0, nullptr);   // API-3: where each file is decoded, and its bytes
+  std::vector<size_t> dec_need(api3 ? (size_t)n : 0, 0);
+  std::vector<std::vector<uint8_t>> icc(api3 ? 0 : (size_t)n);
+  on_host_threads(n, [&](int lo, int hi) {   // the single call's checks, in its order; API-2's checks of the SDR JPEG included
+    for (int i = lo; i < hi; ++i) {
+      if (api3) {
+        st_[i] = api3_check(p010_images + i, sdr_jpeg[i], sdr_jpeg_size[i], hdr_tf, out[i], out_size + i, &info[i]);
+        if (st_[i] == UHDR_HIP_NO_ERROR) dec_need[i] = dec_ycc_bytes(info[i]);
+      } else {
+        st_[i] = api2_check(p010_images + i, yuv420_images + i, sdr_jpeg[i], hdr_tf, out[i], out_size + i);
+        if (st_[i] == UHDR_HIP_NO_ERROR) st_[i] = sdr_jpeg_check(sdr_jpeg[i], sdr_jpeg_size[i], sdr_jpeg_gamut[i], &icc[i]);
+      }
+    }
+  });
+  std::vector<SjFile> files;
+  for (int i = 0; i < n; ++i) {
+    if (st_[i] != UHDR_HIP_NO_ERROR) continue;
+    SjFile e;
+    e.idx = i;
+    e.p010 = p010_images[i];
+    default_p010(&e.p010);
+    memset(&e.sdr, 0, sizeof(e.sdr));
+    if (api3) {
+      const uint8_t* ip = nullptr;
+      size_t in = 0;
+      e.sdr_gamut = jpegr::first_icc(static_cast<const uint8_t*>(sdr_jpeg[i]), sdr_jpeg_size[i], &ip, &in) ? jpegr::gamut_from_icc(ip, in) : sdr_jpeg_gamut[i];
+    } else {
+      e.sdr = yuv420_images[i];
+      default_yuv(&e.sdr);
+      e.sdr_gamut = e.sdr.colorGamut;
+      e.icc = std::move(icc[i]);
+    }
+    files.push_back(std::move(e));
+  }
+  auto result = [&]() {
+    int first = UHDR_HIP_NO_ERROR;
+    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
+    return first;
+  };
+  if (files.empty()) return result();   // every file stopped at its checks: the device is not touched
+  DeviceState* st = nullptr;
+  int rc = current_state(&st);
+  size_t r0 = 0;   // files [0, r0) are finished
+  if (rc == UHDR_HIP_NO_ERROR) {
+    CodecLease lease(st);
+    st = lease.get();
+    rc = st == nullptr ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
+    auto key = [](const SjFile& e) { return std::make_tuple(e.p010.width, e.p010.height, e.sdr_gamut, e.p010.colorGamut); };
+    std::stable_sort(files.begin(), files.end(), [&](const SjFile& x, const SjFile& y) { return key(x) < key(y); });
+    struct SyncOnExit {   // an error half-way through a round must not leave kernels writing into the pools
+      hipStream_t s;
+      ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+    } sync_on_exit{s};
+    while (rc == UHDR_HIP_NO_ERROR && r0 < files.size()) {
+      size_t r1 = r0, bytes = 0;
+      while (r1 < files.size() && r1 - r0 < (size_t)kEncRound) {
+        const size_t b = sj_round_bytes(files[r1], api3 ? &info[files[r1].idx] : nullptr, host);
+        if (r1 > r0 && bytes + b > kCodecRoundBytes) break;
+        bytes += b;
+        ++r1;
+      }
+      rc = sdr_jpeg_round(st, s, api3, host, hdr_tf, &files[r0], (int)(r1 - r0), sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, api3 ? info.data() : nullptr,
+                          dec_out.data(), dec_need.data(), out, out_capacity, out_size, st_.data());
+      if (rc == UHDR_HIP_NO_ERROR) r0 = r1;
+    }
+  }
+  for (size_t k = r0; k < files.size(); ++k)   // the files of a failed round still open, and those behind it
+    if (st_[files[k].idx] == UHDR_HIP_NO_ERROR) st_[files[k].idx] = rc;
+  return result();
+}
+
+// one API-x file
+struct XFile {
+  int idx = 0;
+  uhdr_hip_image_t yuv, map;   // as apix_check leaves them; device once staged
+  std::vector<uint8_t> icc;
+};
+
+// One round of API-x files f[0, m): host planes staged by stage_encoder_in's rules, the 2 m JPEGs (the SDR image at `quality` with its ICC
+// profile, the gain map at 85) through one compress_to_host, then the containers.  A non-zero return is an error of the device or the runtime.
+int apix_round(DeviceState* st, hipStream_t s, bool host, int quality, const XFile* f, int m, const uhdr_hip_metadata_t* metadata,
+               const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* st_) {
+  std::vector<EncJpeg> jpg;
+  jpg.reserve(2 * (size_t)m);
+  int rc;
+  if (host) {
+    size_t total = 0;
+    for (int k = 0; k < m; ++k) total += enc_stage_bytes(f[k].yuv) + enc_stage_bytes(f[k].map);
+    if ((rc = pool_reserve(st, kEncYuv, total)) != 0) return rc;
+  }
+  size_t o = 0;
+  for (int k = 0; k < m; ++k) {
+    const XFile& e = f[k];
+    jpg.push_back(EncJpeg{e.yuv, quality, &e.icc, e.yuv.luma_stride, e.yuv.chroma_stride});
+    jpg.push_back(gainmap_jpeg(e.map, e.map.luma_stride));
+    if (!host) continue;
+    uint8_t* pool = static_cast<uint8_t*>(st->pool[kEncYuv]);
+    if ((rc = stage_encoder_slice(pool + o, e.yuv, &jpg[2 * (size_t)k].img, s)) != 0) return rc;
+    o += enc_stage_bytes(e.yuv);
+    if ((rc = stage_encoder_slice(pool + o, e.map, &jpg[2 * (size_t)k + 1].img, s)) != 0) return rc;
+    o += enc_stage_bytes(e.map);
+  }
+  if (compress_to_host(st, s, 2 * m, jpg.data()) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
+  on_host_threads(m, [&](int lo, int hi) {   // appendGainMap (:613-630) straight into the caller's buffers
+    for (int k = lo; k < hi; ++k) {
+      const int i = f[k].idx;
+      const EncJpeg& sdr = jpg[2 * (size_t)k];
+      const EncJpeg& gm = jpg[2 * (size_t)k + 1];
+      st_[i] = jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
+                                        nullptr, 0, metadata[i], static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i]);
+    }
+  });
+  return UHDR_HIP_NO_ERROR;
+}
+}  // namespace
+
+extern "C" {
+
+int uhdr_hip_jpegr_encode_sdr_jpeg_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images,
+                                         const void* const* sdr_jpeg, const size_t* sdr_jpeg_size, const int* sdr_jpeg_gamut, int hdr_tf,
+                                         void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (p010_images == nullptr || sdr_jpeg == nullptr || sdr_jpeg_size == nullptr || sdr_jpeg_gamut == nullptr || out == nullptr ||
+                          out_capacity == nullptr || out_size == nullptr)))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  return sdr_jpeg_files(n, p010_images, yuv420_images, sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, hdr_tf, out, out_capacity, out_size, status,
+                        mem_space, stream);
+}
+
+int uhdr_hip_jpegr_encode_apix_batch(int n, const uhdr_hip_image_t* yuv420_images, const uhdr_hip_image_t* gainmap_images,
+                                     const uhdr_hip_metadata_t* metadata, int quality, const void* const* exif, const size_t* exif_size,
+                                     void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (yuv420_images == nullptr || gainmap_images == nullptr || metadata == nullptr || out == nullptr || out_capacity == nullptr ||
+                          out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :566-568
+  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
+  std::vector<XFile> files;
+  for (int i = 0; i < n; ++i) {   // the single call's checks, in its order, then appendGainMap's metadata checks (:961-984)
+    const uhdr_hip_image_t& y = yuv420_images[i];
+    const uhdr_hip_image_t& g = gainmap_images[i];
+    if (y.data == nullptr || g.data == nullptr || out[i] == nullptr) { st_[i] = UHDR_HIP_ERROR_BAD_PTR; continue; }
+    XFile e;
+    e.idx = i;
+    int rc = apix_check(y, g, &e.yuv, &e.map, &e.icc);
+    if (rc == UHDR_HIP_NO_ERROR && !jpegr::metadata_valid(metadata[i])) rc = UHDR_HIP_ERROR_BAD_METADATA;
+    if (rc != UHDR_HIP_NO_ERROR) { st_[i] = rc; continue; }
+    files.push_back(std::move(e));
+  }
+  auto result = [&]() {
+    int first = UHDR_HIP_NO_ERROR;
+    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
+    return first;
+  };
+  if (files.empty()) return result();   // every file stopped at its checks: the device is not touched
+  DeviceState* st = nullptr;
+  int rc = current_state(&st);
+  size_t r0 = 0;   // files [0, r0) are finished
+  if (rc == UHDR_HIP_NO_ERROR) {
+    CodecLease lease(st);
+    st = lease.get();
+    rc = st == nullptr ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
+    struct SyncOnExit {   // an error half-way through a round must not leave copies or kernels writing into the pools
+      hipStream_t s;
+      ~SyncOnExit() { (void)hipStreamSynchronize(s); }
+    } sync_on_exit{s};
+    while (rc == UHDR_HIP_NO_ERROR && r0 < files.size()) {   // rounds of <= kEncRound files and <= kCodecRoundBytes
+      size_t r1 = r0, bytes = 0;
+      while (r1 < files.size() && r1 - r0 < (size_t)kEncRound) {
+        const size_t b = enc_round_bytes(files[r1].yuv, host, true) + enc_round_bytes(files[r1].map, host, true);
+        if (r1 > r0 && bytes + b > kCodecRoundBytes) break;
+        bytes += b;
+        ++r1;
+      }
+      rc = apix_round(st, s, host, quality, &files[r0], (int)(r1 - r0), metadata, exif, exif_size, out, out_capacity, out_size, st_.data());
+      if (rc == UHDR_HIP_NO_ERROR) r0 = r1;
+    }
+  }
+  for (size_t k = r0; k < files.size(); ++k) st_[files[k].idx] = rc;   // the files of a failed round and of those behind it
+  return result();
 }
 
 // JpegR::getJPEGRInfo (jpegr.cpp:633-653)

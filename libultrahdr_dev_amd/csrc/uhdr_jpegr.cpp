@@ -431,16 +431,20 @@ bool has_valid_header(const uint8_t* jpg, size_t n) {
   return extract_exif(jpg, n, &pos, &e, &el);
 }
 
+bool metadata_valid(const uhdr_hip_metadata_t& md) {   // jpegr.cpp:961-984 (a NaN passes where the reference's comparisons let it)
+  if (strncmp(md.version, "1.0", sizeof(md.version)) != 0) return false;
+  if (md.maxContentBoost < md.minContentBoost) return false;
+  if (md.hdrCapacityMax < md.hdrCapacityMin || md.hdrCapacityMin < 1.0f) return false;
+  if (md.offsetSdr < 0.0f || md.offsetHdr < 0.0f) return false;
+  return !(md.gamma <= 0.0f);
+}
+
 // appendGainMap (jpegr.cpp:951-1130): 0 ok, else the reference's status.  The file is written straight into the caller's buffer
 // (the two compressed streams are megabytes: one copy each, no intermediate container); *size is set whenever the size is known,
 // ERROR_INSUFFICIENT_RESOURCE when cap is smaller (Write() running past maxLength, jpegr.cpp:46-61).
 int append_gainmap_to(const uint8_t* primary_in, size_t n1, const uint8_t* gainmap, size_t n2, const uint8_t* exif, size_t exif_len,
                       const uint8_t* icc, size_t icc_len, const uhdr_hip_metadata_t& md, uint8_t* dst, size_t cap, size_t* size) {
-  if (strncmp(md.version, "1.0", sizeof(md.version)) != 0) return UHDR_HIP_ERROR_BAD_METADATA;                  // :961-964
-  if (md.maxContentBoost < md.minContentBoost) return UHDR_HIP_ERROR_BAD_METADATA;
-  if (md.hdrCapacityMax < md.hdrCapacityMin || md.hdrCapacityMin < 1.0f) return UHDR_HIP_ERROR_BAD_METADATA;
-  if (md.offsetSdr < 0.0f || md.offsetHdr < 0.0f) return UHDR_HIP_ERROR_BAD_METADATA;
-  if (md.gamma <= 0.0f) return UHDR_HIP_ERROR_BAD_METADATA;
+  if (!metadata_valid(md)) return UHDR_HIP_ERROR_BAD_METADATA;
   if (n2 < 2) return UHDR_HIP_ERROR_BAD_PTR;
   static const char kNs[] = "http://ns.adobe.com/xap/1.0/";   // sizeof counts the terminator, as nameSpaceLength does
   const std::string xs = xmp_secondary(md);

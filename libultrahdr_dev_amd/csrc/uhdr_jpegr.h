@@ -29,6 +29,8 @@ bool first_xmp(const uint8_t* jpg, size_t n, const uint8_t** payload, size_t* pa
 bool first_icc(const uint8_t* jpg, size_t n, const uint8_t** payload, size_t* payload_len);
 void first_packets(const uint8_t* jpg, size_t n, size_t* xmp_off, size_t* xmp_len, size_t* exif_off, size_t* exif_len, size_t* icc_off,
                    size_t* icc_len);
+// appendGainMap's metadata checks (BAD_METADATA when false)
+bool metadata_valid(const uhdr_hip_metadata& md);
 // ... written straight into dst[0, cap); *size receives the file size (ERROR_INSUFFICIENT_RESOURCE when cap is smaller)
 int append_gainmap_to(const uint8_t* primary, size_t n1, const uint8_t* gainmap, size_t n2, const uint8_t* exif, size_t exif_len,
                       const uint8_t* icc, size_t icc_len, const uhdr_hip_metadata& md, uint8_t* dst, size_t cap, size_t* size);
