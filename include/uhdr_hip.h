@@ -270,6 +270,38 @@ typedef struct uhdr_hip_effect {
 int uhdr_hip_add_effects(const uhdr_hip_image_t* in_img, const uhdr_hip_effect_t* effects, int n, uhdr_hip_image_t* out_img,
                          int mem_space, void* stream);
 
+/* uhdr_hip_add_effects for n images in DEVICE memory, one chain shared by all of them (no reference counterpart; it is what
+ * UltraHdr::convert does to the SDR image and to the gain map of every file, ultrahdr.cpp:933-1045).  Enqueued on `stream`; the
+ * descriptor arrays are HOST memory and consumed before the call returns.  Sizes, strides and formats (YUV420 or MONOCHROME) may
+ * differ per image.  All four effects are index maps, so the chain is composed on the host into one map per output plane, source
+ * offset = A[row] + B[column], and a round of up to 64 images costs one upload of those tables and ONE launch whatever n_effects
+ * is: the input is read once and the result written once.  The few chains whose map is not of that form (a crop that cuts the
+ * stacked U|V planes at different columns after a quarter turn) run step by step inside the same call; the bytes are the same.
+ * Per image, out[i][0 .. packed(w', h')) holds exactly what uhdr_hip_add_effects leaves there for the same image and chain
+ * (packed = w'*h' for MONOCHROME, w'*h'*3/2 for YUV420) and out_imgs[i] is that call's descriptor (data = out[i], YUV420:
+ * chroma_data = data + luma_stride * height).  Differences from the single call:
+ *  - bytes of out[i] beyond packed(w', h') are NOT touched (the single call leaves the tails of larger intermediates there), so
+ *    out_capacity[i] >= packed(w', h') suffices;
+ *  - ERROR_UNSUPPORTED_FEATURE for a YUV420 image whose input or any intermediate or final image has an odd width or height: the
+ *    reference reads chroma rows it never wrote there;
+ *  - ERROR_INSUFFICIENT_RESOURCE with out_imgs[i] filled when out_capacity[i] < packed(w', h'); out[i] == NULL with capacity 0 is
+ *    a size probe; out[i] == NULL with a capacity is BAD_PTR.
+ * Inputs and outputs must not overlap.  status (optional) receives every image's status, the return value is the first that is not
+ * NO_ERROR; a failing image does not disturb the others, and a batch whose every image stops at a check does not touch the device.
+ * Call-level errors (status untouched): BAD_PTR for n < 0, n_effects < 0, NULL effects with n_effects > 0, or a NULL in_imgs / out /
+ * out_capacity / out_imgs where n > 0. */
+int uhdr_hip_add_effects_batch(int n, const uhdr_hip_image_t* in_imgs, const uhdr_hip_effect_t* effects, int n_effects,
+                               void* const* out, const size_t* out_capacity, uhdr_hip_image_t* out_imgs, int* status, void* stream);
+
+/* Host-only diagnostic of the composition above (needs no GPU): the image is width x height with chroma right behind luma
+ * (chroma_data == NULL semantics; strides of 0 mean tight).  Fills the final descriptor (data NULL), *fused = 1 when the chain is
+ * one A[row] + B[column] map per plane and 0 when uhdr_hip_add_effects_batch would run it step by step, *count = packed(w', h').
+ * When fused and capacity >= *count, offsets[k] is the byte offset into the input allocation of output byte k, expanded from the
+ * very tables the kernel would get.  Statuses as above. */
+int uhdr_hip_effect_chain_map(size_t width, size_t height, size_t luma_stride, size_t chroma_stride, int pixel_format,
+                              const uhdr_hip_effect_t* effects, int n_effects, uhdr_hip_image_t* out_desc, int* fused,
+                              uint32_t* offsets, size_t capacity, size_t* count);
+
 /* ---- JPEG compression of the path's outputs (encode side) -------------------------------
  * JpegEncoderHelper::compressImage (lib/src/jpegencoderhelper.cpp:39-283; lib/include/ultrahdr/jpegencoderhelper.h:43-60):
  * baseline JPEG of a YUV420 image (image->data = Y, image->chroma_data = U, V at chroma_stride * height / 2) or, when
@@ -446,6 +478,27 @@ int uhdr_hip_jpegr_encode_apix_batch(int n, const uhdr_hip_image_t* yuv420_image
                                      const uhdr_hip_metadata_t* metadata, int quality, const void* const* exif,
                                      const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
                                      int* status, int mem_space, void* stream);
+/* n JPEG/R files in, n edited JPEG/R files out (no reference counterpart; it is UltraHdr::convert's edit flow, ultrahdr.cpp:933-1045:
+ * decode, addEffects on the SDR image and on the gain map, encodeJPEGR API-x).  Compressed data is HOST memory; the call waits for
+ * the stream.  Per file: the container is split, the primary JPEG is decoded to YCbCr planes and the gain-map JPEG to one plane in
+ * device memory by the batched decoder (all 2 n JPEGs of a round share its launches), the metadata is read from the gain map's XMP,
+ * sdr_effects runs on the primary's planes and gainmap_effects on the map through uhdr_hip_add_effects_batch's machinery (all
+ * planes of the round in one launch), and the round is encoded by uhdr_hip_jpegr_encode_apix_batch.  Nothing uncompressed crosses
+ * PCIe.  out[i] receives what uhdr_hip_jpegr_encode_apix writes for the edited planes, the parsed metadata, `quality`, the primary's
+ * EXIF payload (the range uhdr_hip_jpegr_info reports; none if it has none) and colorGamut = the gamut of the primary's ICC profile
+ * when it has a readable one, otherwise sdr_gamut[i] (sdr_gamut == NULL: UNSPECIFIED for every file).  The reference passes one
+ * chain to both images (ultrahdr.cpp:951-952); two are taken because the map is usually a quarter of the size, callers who want the
+ * reference's behaviour pass the same array twice.  Orientation tags inside the EXIF payload are NOT rewritten.
+ * Per-file status, in this order: BAD_PTR (jpegr[i] == NULL, or out[i] == NULL with a capacity); NO_IMAGES_FOUND or
+ * GAIN_MAP_IMAGE_NOT_FOUND; DECODE_ERROR (either JPEG unreadable, or a single-plane primary); METADATA_ERROR; the SDR chain's status;
+ * the gain-map chain's status (both as in uhdr_hip_add_effects_batch); API-x's own; ERROR_INSUFFICIENT_RESOURCE with the exact size
+ * in out_size[i] (out[i] == NULL with capacity 0 is a size probe).  status is optional, the return value is the first status that is
+ * not NO_ERROR, a failing file does not disturb the others.  Call-level errors (status untouched): BAD_PTR for n < 0, a NULL
+ * jpegr / jpegr_size / out / out_capacity / out_size where n > 0, a negative effect count or a NULL chain with a positive one; then
+ * INVALID_QUALITY_FACTOR.  A round holds at most 64 files and 2 GiB of workspace. */
+int uhdr_hip_jpegr_edit_batch(int n, const void* const* jpegr, const size_t* jpegr_size, const uhdr_hip_effect_t* sdr_effects,
+                              int n_sdr_effects, const uhdr_hip_effect_t* gainmap_effects, int n_gainmap_effects, const int* sdr_gamut,
+                              int quality, void* const* out, const size_t* out_capacity, size_t* out_size, int* status, void* stream);
 int uhdr_hip_jpegr_encode_api2(const uhdr_hip_image_t* p010_image, const uhdr_hip_image_t* yuv420_image, const void* sdr_jpeg,
                                size_t sdr_jpeg_size, int sdr_jpeg_gamut, int hdr_tf, void* out, size_t out_capacity,
                                size_t* out_size, int mem_space, void* stream);

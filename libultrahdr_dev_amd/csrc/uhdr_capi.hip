@@ -68,6 +68,10 @@ struct DeviceState : StageSet {
   // EXACT apply behind its pre-filter: the lists of pixels in doubt (uhdr_kernels.h: ex_ws_bytes), per stream, grown on demand
   struct ExWs { uint32_t* p = nullptr; size_t bytes = 0; };
   std::map<hipStream_t, ExWs> ex_ws;
+  // uhdr_hip_add_effects_batch: the jobs and tables of one round, per stream -- page-locked host memory the round is composed in
+  // and its device copy.  `ev` follows the upload on the stream: the host side is rewritten only behind it.
+  struct FxWs { void* host = nullptr; size_t host_bytes = 0; void* dev = nullptr; size_t dev_bytes = 0; hipEvent_t ev = nullptr; bool pending = false; };
+  std::map<hipStream_t, FxWs> fx_ws;
   // the codec entry points (jpeg_*, jpegr_*, effects and tables through host memory) each lease a context of their own for the
   // duration of a call -- staging slots, device and host pools -- so that callers on different streams overlap
   // (CodecLease); a context is a DeviceState that borrows this one's tables
@@ -773,6 +777,13 @@ int uhdr_hip_stream_release(void* stream) {
   if (a != st->stat_ws.end()) { if (a->second) (void)hipFree(a->second); st->stat_ws.erase(a); }
   auto b = st->ex_ws.find(s);
   if (b != st->ex_ws.end()) { if (b->second.p) (void)hipFree(b->second.p); st->ex_ws.erase(b); }
+  auto f = st->fx_ws.find(s);
+  if (f != st->fx_ws.end()) {
+    if (f->second.dev) (void)hipFree(f->second.dev);
+    if (f->second.host) (void)hipHostFree(f->second.host);
+    if (f->second.ev) (void)hipEventDestroy(f->second.ev);
+    st->fx_ws.erase(f);
+  }
   // ... and the lists of this stream that EXACT launches outgrew (kept allocated until nothing on the stream can name them: now)
   size_t keep = 0;
   for (size_t i = 0; i < st->retired.size(); ++i) {
@@ -952,6 +963,11 @@ int uhdr_hip_shutdown(void) {
     for (void* q : kv.second.pool) if (q) (void)hipFree(q);
     for (auto& w : kv.second.stat_ws) if (w.second) (void)hipFree(w.second);
     for (auto& w : kv.second.ex_ws) if (w.second.p) (void)hipFree(w.second.p);
+    for (auto& w : kv.second.fx_ws) {
+      if (w.second.dev) (void)hipFree(w.second.dev);
+      if (w.second.host) (void)hipHostFree(w.second.host);
+      if (w.second.ev) (void)hipEventDestroy(w.second.ev);
+    }
     for (int i = 0; i < kStageSlots; ++i)
       if (kv.second.stage[i]) (void)hipFree(kv.second.stage[i]);
     for (auto& set : kv.second.sets)
@@ -3549,6 +3565,636 @@ int uhdr_hip_add_effects(const uhdr_hip_image_t* in, const uhdr_hip_effect_t* ef
     HIP_TRY(hipStreamSynchronize(s));
   }
   return UHDR_HIP_NO_ERROR;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// A chain as one gather (uhdr_hip_add_effects_batch).  fx_compose() walks the chain with fx_plan() over images that exist as
+// address ranges only: every step's jobs say which bytes of the step's input each output byte comes from, and the input's bytes
+// are known, region by region, as source offset a[row] + b[col] of the caller's image.  A step whose jobs keep that form for
+// every region (checked, not assumed: a job that reads rows of two regions must find their column tables a constant apart)
+// yields the next image's regions; one that does not ends the composition and the image runs step by step.
+// ---------------------------------------------------------------------------------------------------
+namespace {
+struct FxcRegion {          // `rows` rows of `cols` bytes at address `addr`, `stride` apart: byte (r, c) is source byte a[r] + b[c] of plane `base`
+  uint64_t addr = 0;
+  size_t rows = 0, cols = 0, stride = 0;
+  int base = 0;             // 0: offsets from the luma pointer, 1: from the chroma pointer
+  std::vector<int64_t> a, b;
+};
+struct FxcPlan {
+  int status = UHDR_HIP_NO_ERROR;
+  bool fused = false;
+  uhdr_hip_image_t out = {};       // the final descriptor, data == NULL
+  size_t packed = 0;               // bytes of the result
+  std::vector<FxcRegion> planes;   // fused: the result's regions, addr = offset from out[i]
+  std::vector<int> cls;            // ... and their classes, after fx_finish
+  std::vector<uint32_t> lo, hi;
+};
+constexpr uint64_t kFxcLuma = 1ull << 40, kFxcChroma = 2ull << 40, kFxcOut = 3ull << 40;   // where the imaginary images lie
+
+size_t fx_packed(bool mono, size_t w, size_t h) { return mono ? w * h : w * h * 3 / 2; }
+
+// one step: `cur` describes the bytes fx_plan's jobs read; false: the step's map is not of the form a[i] + b[j]
+bool fx_compose_step(const std::vector<FxcRegion>& cur, const FxJobs& jobs, std::vector<FxcRegion>* next) {
+  next->clear();
+  for (int k = 0; k < jobs.n; ++k) {
+    const FxJob& j = jobs.job[k];
+    if (j.rows == 0 || j.cols == 0) continue;
+    const bool transposed = j.op == FX_ROT90 || j.op == FX_ROT270;
+    // source row of output row i (of output column i when transposed) and source column of output column i (row when transposed)
+    const size_t nr = transposed ? j.cols : j.rows, nc = transposed ? j.rows : j.cols;
+    auto src_row = [&](size_t i) -> size_t {
+      switch (j.op) {
+        case FX_FLIP_V: return j.rows - 1 - i;
+        case FX_ROT180: case FX_ROT90: return j.in_h - 1 - i;
+        case FX_RESIZE: return (size_t)((uint64_t)i * j.row_num / j.row_den);
+        default: return i;   // FX_COPY, FX_FLIP_H, FX_ROT270
+      }
+    };
+    auto src_col = [&](size_t i) -> size_t {
+      switch (j.op) {
+        case FX_FLIP_H: case FX_ROT180: case FX_ROT270: return j.in_w - 1 - i;
+        case FX_RESIZE: return (size_t)((uint64_t)i * j.col_num / j.col_den);
+        default: return i;   // FX_COPY, FX_FLIP_V, FX_ROT90
+      }
+    };
+    size_t max_col = 0;
+    for (size_t i = 0; i < nc; ++i) max_col = std::max(max_col, src_col(i));
+    FxcRegion r;
+    r.addr = reinterpret_cast<uint64_t>(j.dst);
+    r.rows = j.rows; r.cols = j.cols; r.stride = j.dst_stride;
+    std::vector<int64_t> va(nr), vb(nc);
+    // the (region, first column) pairs the job's source rows fall into, and how far each pair's column table lies from the first one's
+    struct Key { int region; size_t x0; int64_t delta; };
+    std::vector<Key> keys;
+    const uint64_t src0 = reinterpret_cast<uint64_t>(j.src);
+    for (size_t i = 0; i < nr; ++i) {
+      const uint64_t addr = src0 + (uint64_t)src_row(i) * j.src_stride;
+      int reg = -1;
+      for (size_t q = 0; q < cur.size(); ++q)
+        if (addr >= cur[q].addr && addr < cur[q].addr + (uint64_t)cur[q].rows * cur[q].stride) { reg = (int)q; break; }
+      if (reg < 0) return false;
+      const FxcRegion& c = cur[reg];
+      if (c.stride != j.src_stride && nr > 1) return false;
+      const size_t rr = (size_t)((addr - c.addr) / c.stride), x0 = (size_t)((addr - c.addr) % c.stride);
+      if (x0 + max_col >= c.cols) return false;
+      size_t kk = 0;
+      while (kk < keys.size() && !(keys[kk].region == reg && keys[kk].x0 == x0)) ++kk;
+      if (kk == keys.size()) {
+        if (keys.empty()) {
+          r.base = c.base;
+          for (size_t q = 0; q < nc; ++q) vb[q] = c.b[x0 + src_col(q)];
+          keys.push_back({reg, x0, 0});
+        } else {
+          if (transposed || c.base != r.base) return false;
+          const int64_t delta = c.b[x0 + src_col(0)] - vb[0];
+          for (size_t q = 0; q < nc; ++q)
+            if (c.b[x0 + src_col(q)] - vb[q] != delta) return false;   // the two regions' columns are not a constant apart
+          keys.push_back({reg, x0, delta});
+        }
+      }
+      va[i] = c.a[rr] + keys[kk].delta;
+    }
+    if (transposed) { r.a = std::move(vb); r.b = std::move(va); }
+    else { r.a = std::move(va); r.b = std::move(vb); }
+    next->push_back(std::move(r));
+  }
+  return true;
+}
+
+// classes and bounds of a fused plan's regions.  ext[base]: bytes of the source plane the caller described
+int fx_finish(FxcPlan* p, const size_t ext[2]) {
+  for (FxcRegion& r : p->planes) {
+    int64_t amin = r.a[0], amax = r.a[0], bmin = r.b[0], bmax = r.b[0];
+    for (int64_t v : r.a) { amin = std::min(amin, v); amax = std::max(amax, v); }
+    for (int64_t v : r.b) { bmin = std::min(bmin, v); bmax = std::max(bmax, v); }
+    // the guard: nothing is launched that could read outside the caller's plane
+    if (amin + bmin < 0 || amax + bmax < 0 || (uint64_t)(amax + bmax) >= ext[r.base] || (uint64_t)(amax + bmax) > 0xFFFFFFFFull ||
+        r.rows > 0x7FFFFFFFull || r.cols > 0x7FFFFFF0ull || r.stride > 0xFFFFFFFFull)
+      return UHDR_HIP_UNKNOWN_ERROR;
+    for (int64_t& v : r.a) v += bmin;     // both tables non-negative
+    for (int64_t& v : r.b) v -= bmin;
+    p->lo.push_back((uint32_t)(amin + bmin));
+    p->hi.push_back((uint32_t)(amax + bmax));
+    bool asc = true, desc = true, bup = true, bdown = true, aup = true, adown = true;
+    for (size_t q = 1; q < r.cols; ++q) {
+      const int64_t d = r.b[q] - r.b[q - 1];
+      asc = asc && d == 1; desc = desc && d == -1; bup = bup && d >= 0; bdown = bdown && d <= 0;
+    }
+    for (size_t q = 1; q < r.rows; ++q) {
+      const int64_t d = r.a[q] - r.a[q - 1];
+      aup = aup && d >= 0; adown = adown && d <= 0;
+    }
+    int cls = FXC_GATHER;
+    if (asc) cls = FXC_ASC;
+    else if (desc) cls = FXC_DESC;
+    else {
+      bool lds = bup || bdown;      // at most 4 source bytes per output byte in every block of 4096 columns (k_effect's bound for resize)
+      for (size_t c0 = 0; lds && c0 < r.cols; c0 += 4096) {
+        const size_t c1 = std::min(c0 + 4095, r.cols - 1);
+        lds = (uint64_t)std::llabs(r.b[c1] - r.b[c0]) <= 4ull * (c1 - c0 + 1);
+      }
+      bool tile = aup || adown;     // the rows of every 64-row tile less than 256 bytes apart
+      for (size_t i0 = 0; tile && i0 < r.rows; i0 += 64) tile = std::llabs(r.a[std::min(i0 + 63, r.rows - 1)] - r.a[i0]) < 256;
+      cls = lds ? FXC_LDS : tile ? FXC_TILE : FXC_GATHER;
+    }
+    p->cls.push_back(cls);
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
+// Checks in uhdr_hip_add_effects' order, then the composition.  `in` holds the caller's descriptor (its pointers are not followed).
+void fx_compose(const uhdr_hip_image_t& in, const uhdr_hip_effect_t* fx, int n, FxcPlan* p) {
+  p->status = UHDR_HIP_NO_ERROR;
+  p->fused = false;
+  if (in.pixelFormat != UHDR_HIP_PIX_FMT_YUV420 && in.pixelFormat != UHDR_HIP_PIX_FMT_MONOCHROME) { p->status = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; return; }
+  const bool mono = in.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
+  for (int i = 0; i < n; ++i) {
+    const uhdr_hip_effect_t& e = fx[i];
+    if (e.type == 0) { if (e.b < e.a || e.d < e.c) { p->status = UHDR_HIP_ERROR_INVALID_CROPPING_PARAMETERS; return; } }
+    else if (e.type == 3) { if (e.a <= 0 || e.b <= 0) { p->status = UHDR_HIP_ERROR_INVALID_CROPPING_PARAMETERS; return; } }
+    else if (e.type != 1 && e.type != 2) { p->status = UHDR_HIP_ERROR_BAD_PTR; return; }
+  }
+  const size_t iw = in.width, ih = in.height;
+  const size_t ls0 = in.luma_stride != 0 ? in.luma_stride : iw;
+  const size_t cs0 = in.chroma_stride != 0 ? in.chroma_stride : (ls0 >> 1);
+  bool odd = !mono && ((iw | ih) & 1u) != 0;
+  bool additive = iw != 0 && ih != 0 && iw < (1u << 30) && ih < (1u << 30) && ls0 < (1ull << 31) && cs0 < (1ull << 31);
+  std::vector<FxcRegion> cur, next;
+  if (additive && !odd) {
+    FxcRegion y;
+    y.addr = kFxcLuma; y.rows = ih; y.cols = iw; y.stride = ls0; y.base = 0;
+    y.a.resize(ih); y.b.resize(iw);
+    for (size_t i = 0; i < ih; ++i) y.a[i] = (int64_t)(i * ls0);
+    for (size_t i = 0; i < iw; ++i) y.b[i] = (int64_t)i;
+    cur.push_back(std::move(y));
+    for (int pl = 0; pl < 2 && !mono; ++pl) {   // U, then V at chroma + chroma_stride * (height / 2)
+      FxcRegion c;
+      c.addr = kFxcChroma + (pl ? cs0 * (ih / 2) : 0); c.rows = ih / 2; c.cols = iw / 2; c.stride = cs0; c.base = 1;
+      c.a.resize(c.rows); c.b.resize(c.cols);
+      for (size_t i = 0; i < c.rows; ++i) c.a[i] = (int64_t)((i + (pl ? ih / 2 : 0)) * cs0);
+      for (size_t i = 0; i < c.cols; ++i) c.b[i] = (int64_t)i;
+      cur.push_back(std::move(c));
+    }
+  }
+  // the chain as uhdr_hip_add_effects walks it
+  uhdr_hip_image_t last = in;
+  last.data = reinterpret_cast<void*>(kFxcLuma);
+  last.chroma_data = mono ? nullptr : reinterpret_cast<void*>(kFxcChroma);
+  uhdr_hip_image_t out = in;
+  out.data = nullptr;
+  for (int i = 0; i < n; ++i) {
+    const uhdr_hip_effect_t& e = fx[i];
+    const size_t lls = last.luma_stride != 0 ? last.luma_stride : last.width;
+    const bool keeps_stride = e.type == 1 || (e.type == 2 && e.a == 180);
+    if (keeps_stride && (lls != last.width || (!mono && last.chroma_stride != 0 && last.chroma_stride != last.width / 2))) { p->status = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; return; }
+    if (e.type == 0 && (e.a < 0 || (size_t)e.b >= last.width || e.c < 0 || (size_t)e.d >= last.height)) { p->status = UHDR_HIP_ERROR_INVALID_CROPPING_PARAMETERS; return; }
+    if (e.type == 2 && e.a != 90 && e.a != 180 && e.a != 270) { p->status = UHDR_HIP_ERROR_INVALID_CROPPING_PARAMETERS; return; }
+    uhdr_hip_image_t tmp = out;
+    tmp.data = reinterpret_cast<void*>(kFxcOut);
+    FxJobs jobs;
+    const int kind = e.type == 0 ? FXK_CROP : e.type == 1 ? FXK_MIRROR : e.type == 2 ? FXK_ROTATE : FXK_RESIZE;
+    fx_plan(kind, last, e.a, e.b, e.c, e.d, &tmp, &jobs);
+    if (additive && !odd) {
+      additive = fx_compose_step(cur, jobs, &next);
+      cur.swap(next);
+    }
+    out = tmp;
+    last = tmp;   // the next step reads what this one wrote: tightly packed at kFxcOut, chroma behind luma
+    last.chroma_data = mono ? nullptr : reinterpret_cast<void*>(kFxcOut + last.luma_stride * last.height);
+    odd = odd || (!mono && ((last.width | last.height) & 1u) != 0);
+  }
+  if (odd) { p->status = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; return; }   // the reference reads chroma rows it never wrote
+  out.data = nullptr;
+  out.chroma_data = nullptr;
+  p->out = out;
+  p->packed = fx_packed(mono, out.width, out.height);
+  if (n == 0 || !additive) return;
+  size_t ext[2];
+  ext[0] = ls0 * (ih - 1) + iw;
+  ext[1] = mono ? 0 : cs0 * (ih - 1) + iw / 2;
+  for (FxcRegion& r : cur) r.addr -= kFxcOut;
+  p->planes = std::move(cur);
+  p->status = fx_finish(p, ext);
+  p->fused = p->status == UHDR_HIP_NO_ERROR;
+}
+}  // namespace
+
+namespace {
+// the tables the kernel gets for one region: a[rows], b[cols rounded up to 16] (the padding repeats the last entry)
+void fx_tables(const FxcRegion& r, uint32_t* a, uint32_t* b) {
+  for (size_t i = 0; i < r.rows; ++i) a[i] = (uint32_t)r.a[i];
+  const size_t padded = round_up(r.cols, 16);
+  for (size_t i = 0; i < padded; ++i) b[i] = (uint32_t)r.b[std::min(i, r.cols - 1)];
+}
+
+// the stream's workspace with room for `bytes`, its host side free to be rewritten
+int fx_workspace(DeviceState* st, hipStream_t s, size_t bytes, DeviceState::FxWs** out) {
+  DeviceState::FxWs* w = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(g_mu);
+    try {
+      w = &st->fx_ws[s];
+      st->retired.reserve(st->retired.size() + 1);
+    } catch (const std::bad_alloc&) {
+      return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+    }
+  }
+  if (w->ev == nullptr) HIP_TRY(hipEventCreateWithFlags(&w->ev, hipEventDisableTiming));
+  if (w->pending) { HIP_TRY(hipEventSynchronize(w->ev)); w->pending = false; }   // the last round's upload has left the host side
+  if (w->host_bytes < bytes) {
+    if (w->host) HIP_TRY(hipHostFree(w->host));
+    w->host = nullptr; w->host_bytes = 0;
+    const size_t grown = std::max(bytes, (size_t)1 << 16);
+    HIP_TRY(hipHostMalloc(&w->host, grown, hipHostMallocDefault));
+    w->host_bytes = grown;
+  }
+  if (w->dev_bytes < bytes) {
+    if (w->dev) {   // a launch already on the stream may name it: kept until the stream is released
+      std::lock_guard<std::mutex> lk(g_mu);
+      st->retired.emplace_back(s, w->dev);
+      w->dev = nullptr; w->dev_bytes = 0;
+    }
+    const size_t grown = std::max(bytes, 2 * w->host_bytes);
+    HIP_TRY(hipMalloc(&w->dev, grown));
+    w->dev_bytes = grown;
+  }
+  *out = w;
+  return UHDR_HIP_NO_ERROR;
+}
+
+struct FxcItem {
+  const uhdr_hip_image_t* in;
+  const uhdr_hip_effect_t* fx;
+  int n_fx;
+  void* out;
+  size_t cap;
+  uhdr_hip_image_t* out_img;
+  int status;
+  FxcPlan plan;
+};
+
+// every check of one image that needs no device, and its plan
+void fx_item_prepare(FxcItem* it) {
+  it->status = UHDR_HIP_NO_ERROR;
+  if (it->in->data == nullptr || (it->out == nullptr && it->cap != 0)) { it->status = UHDR_HIP_ERROR_BAD_PTR; return; }
+  fx_compose(*it->in, it->fx, it->n_fx, &it->plan);
+  if (it->plan.status != UHDR_HIP_NO_ERROR) { it->status = it->plan.status; return; }
+  uhdr_hip_image_t d = it->plan.out;
+  d.data = it->out;
+  if (d.pixelFormat == UHDR_HIP_PIX_FMT_YUV420 && it->out != nullptr) d.chroma_data = static_cast<uint8_t*>(it->out) + d.luma_stride * d.height;
+  *it->out_img = d;
+  if (it->out == nullptr || it->cap < it->plan.packed) it->status = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;   // (out == NULL: a size probe)
+}
+
+// the prepared images that passed their checks, in rounds of `round` images: one upload and one launch per round, the images
+// whose chain is not one gather step by step behind it.  Enqueues on s; statuses of images that fail here are updated.
+int fx_items_run(std::vector<FxcItem>& items, int round, hipStream_t s) {
+  std::vector<size_t> todo;
+  for (size_t i = 0; i < items.size(); ++i)
+    if (items[i].status == UHDR_HIP_NO_ERROR && items[i].plan.packed != 0) todo.push_back(i);
+  if (todo.empty()) return UHDR_HIP_NO_ERROR;
+  DeviceState* st = nullptr;
+  int rc = current_state(&st);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  std::lock_guard<std::mutex> pl(g_pair_mu);   // workspace, upload and launch of a stream as one unit
+  for (size_t r0 = 0; r0 < todo.size(); r0 += (size_t)round) {
+    const size_t r1 = std::min(todo.size(), r0 + (size_t)round);
+    // layout of the round: the jobs, then every job's two tables, 16-byte aligned
+    size_t n_jobs = 0, words = 0;
+    for (size_t q = r0; q < r1; ++q) {
+      const FxcItem& it = items[todo[q]];
+      if (it.n_fx == 0 || !it.plan.fused) continue;
+      for (const FxcRegion& g : it.plan.planes) { ++n_jobs; words += round_up(g.rows, 4) + round_up(g.cols, 16); }
+    }
+    if (n_jobs != 0) {
+      const size_t job_bytes = round_up(n_jobs * sizeof(FxChainJob), 256), bytes = job_bytes + words * 4;
+      DeviceState::FxWs* w = nullptr;
+      if ((rc = fx_workspace(st, s, bytes, &w)) != UHDR_HIP_NO_ERROR) return rc;
+      FxChainJob* hj = static_cast<FxChainJob*>(w->host);
+      uint32_t* ht = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(w->host) + job_bytes);
+      const uint32_t* dt = reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(w->dev) + job_bytes);
+      size_t k = 0, at = 0;
+      for (size_t q = r0; q < r1; ++q) {
+        const FxcItem& it = items[todo[q]];
+        if (it.n_fx == 0 || !it.plan.fused) continue;
+        const uhdr_hip_image_t& in = *it.in;
+        const size_t ls = in.luma_stride != 0 ? in.luma_stride : in.width;
+        const uint8_t* sy = static_cast<const uint8_t*>(in.data);
+        const uint8_t* sc = in.chroma_data ? static_cast<const uint8_t*>(in.chroma_data) : sy + ls * in.height;
+        for (size_t g = 0; g < it.plan.planes.size(); ++g) {
+          const FxcRegion& reg = it.plan.planes[g];
+          FxChainJob& j = hj[k++];
+          j.src = reg.base ? sc : sy;
+          j.dst = static_cast<uint8_t*>(it.out) + reg.addr;
+          j.rows = (uint32_t)reg.rows; j.cols = (uint32_t)reg.cols; j.dst_stride = (uint32_t)reg.stride;
+          j.lo = it.plan.lo[g]; j.hi = it.plan.hi[g]; j.cls = it.plan.cls[g];
+          fx_tables(reg, ht + at, ht + at + round_up(reg.rows, 4));
+          j.a = dt + at;
+          j.b = dt + at + round_up(reg.rows, 4);
+          at += round_up(reg.rows, 4) + round_up(reg.cols, 16);
+        }
+      }
+      HIP_TRY(hipMemcpyAsync(w->dev, w->host, bytes, hipMemcpyHostToDevice, s));
+      HIP_TRY(hipEventRecord(w->ev, s));
+      w->pending = true;
+      HIP_TRY(launch_effect_chain(static_cast<const FxChainJob*>(w->dev), hj, (int)n_jobs, s));
+    }
+    for (size_t q = r0; q < r1; ++q) {
+      FxcItem& it = items[todo[q]];
+      if (it.n_fx == 0) {   // addEffects without effects: the packed extent, copied as it lies (editorhelper.cpp:383-390)
+        HIP_TRY(hipMemcpyAsync(it.out, it.in->data, it.plan.packed, hipMemcpyDeviceToDevice, s));
+      } else if (!it.plan.fused) {
+        // step by step, as uhdr_hip_add_effects does it, into a temporary the size of the largest intermediate image; only the
+        // result's own bytes reach out[i]
+        const bool mono = it.in->pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
+        size_t w2 = it.in->width, h2 = it.in->height, max_bytes = fx_packed(mono, w2, h2);
+        for (int e = 0; e < it.n_fx; ++e) {
+          const uhdr_hip_effect_t& f = it.fx[e];
+          if (f.type == 0) { w2 = (size_t)(f.b - f.a + 1); h2 = (size_t)(f.d - f.c + 1); }
+          else if (f.type == 2 && f.a != 180) std::swap(w2, h2);
+          else if (f.type == 3) { w2 = (size_t)f.a; h2 = (size_t)f.b; }
+          max_bytes = std::max(max_bytes, fx_packed(mono, w2, h2));
+        }
+        CodecLease lease(st);
+        DeviceState* cx = lease.get();
+        if (cx == nullptr) { it.status = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
+        if ((rc = stage_reserve(cx, 3, max_bytes + 64)) != 0) { it.status = rc; continue; }
+        uhdr_hip_image_t tmp = {};
+        tmp.data = cx->stage[3];
+        rc = uhdr_hip_add_effects(it.in, it.fx, it.n_fx, &tmp, UHDR_HIP_MEM_DEVICE, s);
+        if (rc != UHDR_HIP_NO_ERROR) { it.status = rc; continue; }
+        HIP_TRY(hipMemcpyAsync(it.out, tmp.data, it.plan.packed, hipMemcpyDeviceToDevice, s));
+      }
+    }
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+}  // namespace
+
+extern "C" {
+
+int uhdr_hip_add_effects_batch(int n, const uhdr_hip_image_t* in_imgs, const uhdr_hip_effect_t* effects, int n_effects, void* const* out,
+                               const size_t* out_capacity, uhdr_hip_image_t* out_imgs, int* status, void* stream) {
+  if (n < 0 || n_effects < 0 || (n_effects > 0 && effects == nullptr) ||
+      (n > 0 && (in_imgs == nullptr || out == nullptr || out_capacity == nullptr || out_imgs == nullptr)))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  std::vector<FxcItem> items;
+  try {
+    items.resize((size_t)n);
+    for (int i = 0; i < n; ++i) {
+      FxcItem& it = items[i];
+      it.in = &in_imgs[i]; it.fx = effects; it.n_fx = n_effects; it.out = out[i]; it.cap = out_capacity[i]; it.out_img = &out_imgs[i];
+      fx_item_prepare(&it);
+    }
+  } catch (const std::bad_alloc&) {
+    return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  }
+  int rc = UHDR_HIP_NO_ERROR;
+  try {
+    rc = fx_items_run(items, kFxChainRound, static_cast<hipStream_t>(stream));
+  } catch (const std::bad_alloc&) {
+    rc = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  }
+  int first = UHDR_HIP_NO_ERROR;
+  for (int i = 0; i < n; ++i) {
+    if (status) status[i] = items[i].status;
+    if (first == UHDR_HIP_NO_ERROR) first = items[i].status;
+  }
+  return first != UHDR_HIP_NO_ERROR ? first : rc;
+}
+
+int uhdr_hip_effect_chain_map(size_t width, size_t height, size_t luma_stride, size_t chroma_stride, int pixel_format,
+                              const uhdr_hip_effect_t* effects, int n_effects, uhdr_hip_image_t* out_desc, int* fused, uint32_t* offsets,
+                              size_t capacity, size_t* count) {
+  if (out_desc == nullptr || fused == nullptr || count == nullptr || n_effects < 0 || (n_effects > 0 && effects == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  try {
+    uhdr_hip_image_t in = {};
+    in.width = width; in.height = height; in.luma_stride = luma_stride; in.chroma_stride = chroma_stride;
+    in.colorGamut = UHDR_HIP_CG_UNSPECIFIED; in.pixelFormat = pixel_format;
+    FxcPlan plan;
+    fx_compose(in, effects, n_effects, &plan);
+    if (plan.status != UHDR_HIP_NO_ERROR) return plan.status;
+    *out_desc = plan.out;
+    *count = plan.packed;
+    *fused = (n_effects == 0 || plan.fused) ? 1 : 0;
+    if (!*fused || offsets == nullptr || capacity < plan.packed) return UHDR_HIP_NO_ERROR;
+    if (n_effects == 0) {
+      for (size_t k = 0; k < plan.packed; ++k) offsets[k] = (uint32_t)k;
+      return UHDR_HIP_NO_ERROR;
+    }
+    const size_t ls = luma_stride != 0 ? luma_stride : width;
+    std::vector<uint32_t> a, b;
+    for (const FxcRegion& r : plan.planes) {
+      a.assign(r.rows, 0);
+      b.assign(round_up(r.cols, 16), 0);
+      fx_tables(r, a.data(), b.data());
+      const uint32_t base = r.base ? (uint32_t)(ls * height) : 0u;   // chroma right behind luma
+      for (size_t i = 0; i < r.rows; ++i)
+        for (size_t c = 0; c < r.cols; ++c) offsets[r.addr + i * r.stride + c] = base + a[i] + b[c];
+    }
+    return UHDR_HIP_NO_ERROR;
+  } catch (const std::bad_alloc&) {
+    return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  }
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------
+// n JPEG/R files in, n edited JPEG/R files out: split, decode both JPEGs of every file into device memory (one decoder launch set
+// per round), the two chains over all 2 m images of the round in one launch, API-x encode of the round.  Nothing uncompressed
+// crosses PCIe.
+// ---------------------------------------------------------------------------------------------------
+namespace {
+struct EditFile {
+  int idx;
+  const uint8_t* jpg[2];
+  size_t len[2];
+  uhdr_hip_metadata_t md;
+  int gamut;
+  const uint8_t* exif;
+  size_t exif_len;
+  uhdr_hip_image_t dec[2];     // the decoded primary image and gain map
+  size_t dec_bytes[2], out_bytes[2];
+};
+size_t edit_file_bytes(const EditFile& f) {
+  return round_up(f.dec_bytes[0], 256) + round_up(f.dec_bytes[1], 256) + round_up(f.out_bytes[0], 256) + round_up(f.out_bytes[1], 256);
+}
+
+int edit_round(DeviceState* cx, hipStream_t s, EditFile* f, int m, const uhdr_hip_effect_t* const fx[2], const int n_fx[2], int quality,
+               void* const* out, const size_t* out_capacity, size_t* out_size, int* st_) {
+  size_t bytes = 0;
+  for (int k = 0; k < m; ++k) bytes += edit_file_bytes(f[k]);
+  int rc;
+  if ((rc = stage_reserve(cx, 4, bytes)) != 0) return rc;
+  uint8_t* ws = static_cast<uint8_t*>(cx->stage[4]);
+  // 1. the 2 m JPEGs through the batched decoder
+  std::vector<const void*> jp(2 * (size_t)m);
+  std::vector<size_t> jn(2 * (size_t)m), cap(2 * (size_t)m);
+  std::vector<void*> dst(2 * (size_t)m), fxo(2 * (size_t)m);
+  std::vector<uhdr_hip_image_t> dec(2 * (size_t)m), edited(2 * (size_t)m);
+  std::vector<int> dst_st(2 * (size_t)m, 0);
+  size_t o = 0;
+  for (int k = 0; k < m; ++k)
+    for (int p = 0; p < 2; ++p) {
+      const size_t q = 2 * (size_t)k + p;
+      jp[q] = f[k].jpg[p]; jn[q] = f[k].len[p];
+      dst[q] = ws + o; cap[q] = f[k].dec_bytes[p];
+      o += round_up(f[k].dec_bytes[p], 256);
+      fxo[q] = ws + o;
+      o += round_up(f[k].out_bytes[p], 256);
+    }
+  (void)uhdr_hip_jpeg_decode_batch(2 * m, jp.data(), jn.data(), UHDR_HIP_DECODE_TO_YCBCR, dst.data(), cap.data(), dec.data(), dst_st.data(),
+                                   UHDR_HIP_MEM_DEVICE, s);
+  // 2. both chains of every file that decoded: one launch
+  std::vector<FxcItem> items(2 * (size_t)m);
+  for (int k = 0; k < m; ++k) {
+    const size_t q = 2 * (size_t)k;
+    if (dst_st[q] != UHDR_HIP_NO_ERROR || dst_st[q + 1] != UHDR_HIP_NO_ERROR) st_[f[k].idx] = UHDR_HIP_ERROR_DECODE_ERROR;
+    dec[q + 1].pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;   // (a gain map with chroma planes: its luma)
+    dec[q + 1].chroma_data = nullptr;
+    for (int p = 0; p < 2; ++p) {
+      FxcItem& it = items[q + p];
+      it.in = &dec[q + p]; it.fx = fx[p]; it.n_fx = n_fx[p]; it.out = fxo[q + p]; it.cap = f[k].out_bytes[p]; it.out_img = &edited[q + p];
+      if (st_[f[k].idx] == UHDR_HIP_NO_ERROR) fx_item_prepare(&it);
+      else it.status = st_[f[k].idx];
+    }
+  }
+  if ((rc = fx_items_run(items, 2 * kFxChainRound, s)) != UHDR_HIP_NO_ERROR) return rc;
+  // 3. API-x over the files still standing
+  std::vector<uhdr_hip_image_t> yuv, map;
+  std::vector<uhdr_hip_metadata_t> md;
+  std::vector<const void*> exif;
+  std::vector<size_t> exif_n, ocap, osize;
+  std::vector<void*> optr;
+  std::vector<int> who, xst;
+  uint8_t probe_byte = 0;
+  for (int k = 0; k < m; ++k) {
+    const size_t q = 2 * (size_t)k;
+    const int i = f[k].idx;
+    if (st_[i] == UHDR_HIP_NO_ERROR) st_[i] = items[q].status != UHDR_HIP_NO_ERROR ? items[q].status : items[q + 1].status;
+    if (st_[i] != UHDR_HIP_NO_ERROR) continue;
+    edited[q].colorGamut = f[k].gamut;
+    yuv.push_back(edited[q]); map.push_back(edited[q + 1]); md.push_back(f[k].md);
+    exif.push_back(f[k].exif_len ? f[k].exif : nullptr); exif_n.push_back(f[k].exif_len);
+    optr.push_back(out[i] ? out[i] : &probe_byte); ocap.push_back(out[i] ? out_capacity[i] : 0); osize.push_back(0);
+    who.push_back(i); xst.push_back(0);
+  }
+  if (!who.empty()) {
+    (void)uhdr_hip_jpegr_encode_apix_batch((int)who.size(), yuv.data(), map.data(), md.data(), quality, exif.data(), exif_n.data(), optr.data(),
+                                           ocap.data(), osize.data(), xst.data(), UHDR_HIP_MEM_DEVICE, s);
+    for (size_t k = 0; k < who.size(); ++k) { st_[who[k]] = xst[k]; out_size[who[k]] = osize[k]; }
+  }
+  HIP_TRY(hipStreamSynchronize(s));   // the workspace is the next round's
+  return UHDR_HIP_NO_ERROR;
+}
+}  // namespace
+
+extern "C" {
+
+int uhdr_hip_jpegr_edit_batch(int n, const void* const* jpegr, const size_t* jpegr_size, const uhdr_hip_effect_t* sdr_effects, int n_sdr_effects,
+                              const uhdr_hip_effect_t* gainmap_effects, int n_gainmap_effects, const int* sdr_gamut, int quality, void* const* out,
+                              const size_t* out_capacity, size_t* out_size, int* status, void* stream) {
+  if (n < 0 || n_sdr_effects < 0 || n_gainmap_effects < 0 || (n_sdr_effects > 0 && sdr_effects == nullptr) ||
+      (n_gainmap_effects > 0 && gainmap_effects == nullptr) ||
+      (n > 0 && (jpegr == nullptr || jpegr_size == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  const uhdr_hip_effect_t* const fx[2] = {sdr_effects, gainmap_effects};
+  const int n_fx[2] = {n_sdr_effects, n_gainmap_effects};
+  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
+  auto result = [&]() {
+    int first = UHDR_HIP_NO_ERROR;
+    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
+    return first;
+  };
+  try {
+    // everything that needs no device: the split, the two headers, the metadata, the chains' own checks
+    std::vector<EditFile> files;
+    for (int i = 0; i < n; ++i) {
+      out_size[i] = 0;
+      if (jpegr[i] == nullptr || (out[i] == nullptr && out_capacity[i] != 0)) { st_[i] = UHDR_HIP_ERROR_BAD_PTR; continue; }
+      const uint8_t* file = static_cast<const uint8_t*>(jpegr[i]);
+      jpegr::Range img[2];
+      const int found = jpegr::find_images(file, jpegr_size[i], img);
+      if (found < 2) { st_[i] = found == 0 ? UHDR_HIP_ERROR_NO_IMAGES_FOUND : UHDR_HIP_ERROR_GAIN_MAP_IMAGE_NOT_FOUND; continue; }
+      EditFile f = {};
+      f.idx = i;
+      for (int p = 0; p < 2; ++p) { f.jpg[p] = file + img[p].begin; f.len[p] = img[p].len; }
+      files.push_back(f);
+    }
+    if (!files.empty()) {   // the headers, as size probes of the batched decoder (host work)
+      const size_t m2 = 2 * files.size();
+      std::vector<const void*> jp(m2);
+      std::vector<size_t> jn(m2);
+      std::vector<uhdr_hip_image_t> desc(m2);
+      std::vector<int> pst(m2, 0);
+      for (size_t k = 0; k < files.size(); ++k)
+        for (int p = 0; p < 2; ++p) { jp[2 * k + p] = files[k].jpg[p]; jn[2 * k + p] = files[k].len[p]; }
+      (void)uhdr_hip_jpeg_decode_batch((int)m2, jp.data(), jn.data(), UHDR_HIP_DECODE_TO_YCBCR, nullptr, nullptr, desc.data(), pst.data(),
+                                       UHDR_HIP_MEM_DEVICE, stream);
+      std::vector<EditFile> live;
+      for (size_t k = 0; k < files.size(); ++k) {
+        EditFile& f = files[k];
+        const int i = f.idx;
+        if (pst[2 * k] != UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE || pst[2 * k + 1] != UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE ||
+            desc[2 * k].pixelFormat != UHDR_HIP_PIX_FMT_YUV420) { st_[i] = UHDR_HIP_ERROR_DECODE_ERROR; continue; }
+        const uint8_t* xmp = nullptr;
+        size_t xmp_len = 0;
+        if (!jpegr::first_xmp(f.jpg[1], f.len[1], &xmp, &xmp_len) || !jpegr::metadata_from_xmp(xmp, xmp_len, &f.md)) { st_[i] = UHDR_HIP_ERROR_METADATA_ERROR; continue; }
+        for (int p = 0; p < 2 && st_[i] == UHDR_HIP_NO_ERROR; ++p) {
+          uhdr_hip_image_t d = desc[2 * k + p];
+          f.dec_bytes[p] = fx_packed(d.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME, d.width, d.height);
+          if (p == 1) d.pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
+          FxcPlan plan;
+          fx_compose(d, fx[p], n_fx[p], &plan);
+          st_[i] = plan.status;
+          f.out_bytes[p] = plan.packed;
+        }
+        if (st_[i] != UHDR_HIP_NO_ERROR) continue;
+        const uint8_t* icc = nullptr;
+        size_t icc_len = 0;
+        f.gamut = jpegr::first_icc(f.jpg[0], f.len[0], &icc, &icc_len) ? jpegr::gamut_from_icc(icc, icc_len) : UHDR_HIP_CG_UNSPECIFIED;
+        if (f.gamut == UHDR_HIP_CG_UNSPECIFIED) f.gamut = sdr_gamut ? sdr_gamut[i] : UHDR_HIP_CG_UNSPECIFIED;
+        size_t a, b, eo = 0, el = 0, c, d2;
+        jpegr::first_packets(f.jpg[0], f.len[0], &a, &b, &eo, &el, &c, &d2);
+        f.exif = el ? f.jpg[0] + eo : nullptr;
+        f.exif_len = el;
+        live.push_back(f);
+      }
+      if (!live.empty()) {
+        DeviceState* st = nullptr;
+        int rc = current_state(&st);
+        size_t r0 = 0;
+        if (rc == UHDR_HIP_NO_ERROR) {
+          CodecLease lease(st);
+          DeviceState* cx = lease.get();
+          rc = cx == nullptr ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
+          hipStream_t s = static_cast<hipStream_t>(stream);
+          while (rc == UHDR_HIP_NO_ERROR && r0 < live.size()) {   // rounds of <= 64 files and <= 2 GiB of workspace
+            size_t r1 = r0, bytes = 0;
+            while (r1 < live.size() && r1 - r0 < (size_t)kFxChainRound) {
+              const size_t b = edit_file_bytes(live[r1]);
+              if (r1 > r0 && bytes + b > kCodecRoundBytes) break;
+              bytes += b;
+              ++r1;
+            }
+            rc = edit_round(cx, s, &live[r0], (int)(r1 - r0), fx, n_fx, quality, out, out_capacity, out_size, st_.data());
+            if (rc == UHDR_HIP_NO_ERROR) r0 = r1;
+          }
+          if (rc != UHDR_HIP_NO_ERROR) (void)hipStreamSynchronize(s);
+        }
+        for (size_t k = r0; k < live.size(); ++k) st_[live[k].idx] = rc;
+      }
+    }
+  } catch (const std::bad_alloc&) {
+    return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  }
+  return result();
 }
 
 }  // extern "C"

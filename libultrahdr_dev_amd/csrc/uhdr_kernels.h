@@ -201,6 +201,27 @@ struct FxJobs {
   int n;
 };
 
+// A whole chain of effects as one gather: dst[i][j] = src[a[i] + b[j]], one job per output plane (k_effect_chain).  The tables hold
+// byte offsets from `src`; `b` is padded to a multiple of 16 entries.  The host picks the column-pattern class and has checked,
+// before the launch, that every a[i] + b[j] lies in [lo, hi] and that [lo, hi] lies inside the plane the caller described.
+enum FxChainClass : int {
+  FXC_GATHER = 0,  // anything: one byte load per output byte
+  FXC_ASC,         // b[j] = b[0] + j: aligned 16-byte pieces
+  FXC_DESC,        // b[j] = b[0] - j: 16-byte pieces, bytes reversed
+  FXC_LDS,         // b monotone, at most 16 KiB between the ends of any 4096 columns (resize): gathered from a copy of the row stretch in LDS
+  FXC_TILE         // a monotone, less than 256 bytes between the ends of any 64 rows, b far apart (odd number of quarter turns): 64 x 64 LDS tile
+};
+struct FxChainJob {
+  const uint8_t* src;
+  uint8_t* dst;
+  const uint32_t* a;   // [rows]
+  const uint32_t* b;   // [cols rounded up to 16]
+  uint32_t rows, cols, dst_stride;
+  uint32_t lo, hi;     // the smallest and the largest source offset of the job: nothing outside [src + lo, src + hi] is ever read
+  int cls;
+};
+constexpr int kFxChainRound = 64;   // images per round of uhdr_hip_add_effects_batch (three plane jobs each)
+
 static_assert(sizeof(GenConsts) + sizeof(GenBatch) <= 4096, "generate kernel arguments exceed the kernarg segment");
 static_assert(sizeof(AppConsts) + sizeof(AppBatch) <= 4096, "apply kernel arguments exceed the kernarg segment");
 
@@ -245,6 +266,9 @@ static_assert(sizeof(YccRgbaBatch) <= 4096, "k_ycc420_rgba_batch's kernel argume
 hipError_t launch_ycc420_to_rgba_batch(const YccRgbaBatch& b, int n, hipStream_t s);
 hipError_t upload_idw4(const float* tables /* 4*64 floats */);
 hipError_t launch_effect(const FxJobs& j, hipStream_t s);
+// dev_jobs: n descriptors in DEVICE memory (a round is not bounded by the kernarg segment); host_jobs: the same descriptors, read
+// here for the grid's size only
+hipError_t launch_effect_chain(const FxChainJob* dev_jobs, const FxChainJob* host_jobs, int n, hipStream_t s);
 hipError_t launch_eval_transfer(int fn, const float* in, float* out, size_t n, const EvalConsts& ec, hipStream_t s);
 hipError_t launch_synth_lcg(uint16_t* p010, uint8_t* yuv, uint32_t n_luma, uint32_t n, uint32_t seed, hipStream_t s);
 

@@ -9,6 +9,7 @@
 //   k_convert_yuv<ALIGNED>   JpegR::convertYuv + transformYuv420  (lib/src/jpegr.cpp:1199-1203,
 //                                                                  lib/src/gainmapmath.cpp:483-520)
 //   k_effect, k_effect_rot   crop / mirror / rotate / resize      (lib/src/editorhelper.cpp:26-360)
+//   k_effect_chain           a whole chain of them as one gather  (lib/src/editorhelper.cpp:362-446)
 //   k_eval_transfer          scalar transfer functions over arrays (diagnostics for the exhaustive tests)
 //
 // All of it is pointwise byte/float work: no MFMA.  Measured: generate runs within 10 % of what its own
@@ -2848,6 +2849,168 @@ hipError_t launch_effect(const FxJobs& j, hipStream_t s) {
     return hipGetLastError();
   }
   hipLaunchKernelGGL(k_effect, dim3(((cols + 15u) / 16u + 255u) / 256u, rows < 65535u ? rows : 65535u, (unsigned)j.n), dim3(256), 0, s, j);
+  return hipGetLastError();
+}
+
+// =================================================================================================
+// A chain of effects as ONE gather (uhdr_hip_add_effects_batch): every effect is an index map, so a chain is one as well, and for
+// all but a handful of chains the source offset of output byte (i, j) of a plane is a[i] + b[j].  The host composes the two tables
+// (uhdr_capi.hip: fx_compose) and picks the job's class from them; one launch moves every plane of every image of a round, reading
+// the input once and writing the result once.  The classes restate what k_effect and k_effect_rot do for a single step; a class
+// only selects the faster route, every route yields dst[i][j] = src[a[i] + b[j]] and none reads outside [src + lo, src + hi].
+// =================================================================================================
+// the dword at p (p a multiple of 4); bytes outside [vlo, vhi] are not read and come back as 0
+__device__ __forceinline__ uint32_t fxc_load4(const uint8_t* p, const uint8_t* vlo, const uint8_t* vhi) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), lo = reinterpret_cast<uintptr_t>(vlo), hi = reinterpret_cast<uintptr_t>(vhi);
+  if (a >= lo && a + 3u <= hi) return *reinterpret_cast<const uint32_t*>(p);
+  uint32_t v = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < 4u; ++k)
+    if (a + k >= lo && a + k <= hi) v |= (uint32_t)p[k] << (8u * k);
+  return v;
+}
+
+// 16 output bytes at column c0 (a multiple of 16) gathered byte by byte from `base` (global memory or LDS) through b[] - sub.
+// whole: all 16 columns exist and d is 16-byte aligned -> one store; otherwise dword stores where d allows them, byte stores else.
+template <typename Ptr>
+__device__ __forceinline__ void fxc_gather16(Ptr base, const uint32_t* __restrict__ b, uint32_t sub, uint32_t c0, uint32_t cols, bool whole,
+                                             uint8_t* d) {
+  if (whole) {
+    uint32_t w[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const uint4 bb = *reinterpret_cast<const uint4*>(b + c0 + 4 * g);   // (b is padded to a multiple of 16 entries and 16-byte aligned)
+      w[g] = (uint32_t)base[bb.x - sub] | ((uint32_t)base[bb.y - sub] << 8) | ((uint32_t)base[bb.z - sub] << 16) | ((uint32_t)base[bb.w - sub] << 24);
+    }
+    *reinterpret_cast<uint4*>(d) = make_uint4(w[0], w[1], w[2], w[3]);
+    return;
+  }
+#pragma unroll 1
+  for (uint32_t q = 0; q < 4u; ++q) {
+    const uint32_t c = c0 + 4u * q;
+    if (c >= cols) break;
+    const uint4 bb = *reinterpret_cast<const uint4*>(b + c);
+    if (c + 4u <= cols && (reinterpret_cast<uintptr_t>(d + 4u * q) & 3u) == 0u) {
+      *reinterpret_cast<uint32_t*>(d + 4u * q) =
+          (uint32_t)base[bb.x - sub] | ((uint32_t)base[bb.y - sub] << 8) | ((uint32_t)base[bb.z - sub] << 16) | ((uint32_t)base[bb.w - sub] << 24);
+    } else {
+      d[4u * q] = base[bb.x - sub];
+      if (c + 1u < cols) d[4u * q + 1u] = base[bb.y - sub];
+      if (c + 2u < cols) d[4u * q + 2u] = base[bb.z - sub];
+      if (c + 3u < cols) d[4u * q + 3u] = base[bb.w - sub];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) k_effect_chain(const FxChainJob* __restrict__ jobs, int n_jobs) {
+  __shared__ uint32_t s_mem[64u * 65u];   // FXC_LDS: the row stretch of 4096 columns (at most 16 KiB + 4); FXC_TILE: uint8_t[64][260]
+  if ((int)blockIdx.z >= n_jobs) return;
+  const FxChainJob j = jobs[blockIdx.z];
+  const uint8_t* vlo = j.src + j.lo;
+  const uint8_t* vhi = j.src + j.hi;
+  const uint32_t t = threadIdx.x;
+
+  if (j.cls == FXC_TILE) {
+    // Output tile rows i0 .. i0+63, columns j0 .. j0+63.  For one column the 64 source bytes lie within a[] 's span of the tile's rows,
+    // less than 256 bytes (64 for a plain quarter turn, more behind a reduction): that run (at most 65 dwords with its alignment
+    // slack) is read by 16 adjacent lanes, parked as row jj of the tile and picked up transposed, so neither side of the copy walks a
+    // column of an image in HBM.  (A tile row is 65 dwords: the transposed reads of 16 lanes fall into 16 banks.)
+    uint8_t(*tile)[260] = reinterpret_cast<uint8_t(*)[260]>(s_mem);
+    const uint32_t j0 = blockIdx.x * 64u;
+    if (j0 >= j.cols) return;                               // (block-uniform)
+    const uint32_t src_lsb = (uint32_t)reinterpret_cast<uintptr_t>(j.src);
+    for (uint32_t i0 = blockIdx.y * 64u; i0 < j.rows; i0 += gridDim.y * 64u) {
+      const uint32_t il = min(i0 + 63u, j.rows - 1u);
+      const uint32_t a0 = j.a[i0], a1 = j.a[il];
+      const uint32_t alo = min(a0, a1), span = max(a0, a1) - alo;   // (a is monotone: the ends bound the tile's rows; span < 256)
+      __syncthreads();                                      // (the previous tile has been written out)
+#pragma unroll
+      for (uint32_t p = 0; p < 4u; ++p) {
+        const uint32_t jj = p * 16u + (t >> 4);
+        if (j0 + jj < j.cols) {
+          const uint8_t* s0 = j.src + alo + j.b[j0 + jj];
+          const uint32_t off = (uint32_t)(reinterpret_cast<uintptr_t>(s0) & 3u);
+          const uint8_t* sal = s0 - off;
+          for (uint32_t q = t & 15u; q < 65u && 4u * q <= off + span; q += 16u)
+            *reinterpret_cast<uint32_t*>(&tile[jj][4u * q]) = fxc_load4(sal + 4u * q, vlo, vhi);
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (uint32_t p = 0; p < 4u; ++p) {
+        const uint32_t r = p * 16u + (t >> 4), c = 4u * (t & 15u);
+        const uint32_t oi = i0 + r;
+        if (oi >= j.rows || j0 + c >= j.cols) continue;
+        const uint32_t ar = j.a[oi] - alo;
+        const uint4 bb = *reinterpret_cast<const uint4*>(j.b + j0 + c);
+        const uint32_t base = src_lsb + alo;
+        const uint32_t v0 = tile[c][((base + bb.x) & 3u) + ar], v1 = tile[c + 1u][((base + bb.y) & 3u) + ar];
+        const uint32_t v2 = tile[c + 2u][((base + bb.z) & 3u) + ar], v3 = tile[c + 3u][((base + bb.w) & 3u) + ar];
+        uint8_t* d = j.dst + (size_t)oi * j.dst_stride + j0 + c;
+        if (j0 + c + 4u <= j.cols && (reinterpret_cast<uintptr_t>(d) & 3u) == 0u) {
+          *reinterpret_cast<uint32_t*>(d) = v0 | (v1 << 8) | (v2 << 16) | (v3 << 24);
+        } else {
+          d[0] = (uint8_t)v0;
+          if (j0 + c + 1u < j.cols) d[1] = (uint8_t)v1;
+          if (j0 + c + 2u < j.cols) d[2] = (uint8_t)v2;
+          if (j0 + c + 3u < j.cols) d[3] = (uint8_t)v3;
+        }
+      }
+    }
+    return;
+  }
+
+  // the row classes: one thread produces 16 consecutive output bytes of one row, a block 4096 columns
+  const uint32_t cb = blockIdx.x * 4096u;
+  if (cb >= j.cols) return;                                 // (block-uniform)
+  const uint32_t c0 = cb + t * 16u;
+  const bool active = c0 < j.cols;
+  for (uint32_t i = blockIdx.y; i < j.rows; i += gridDim.y) {
+    const uint32_t ai = j.a[i];
+    uint8_t* d = j.dst + (size_t)i * j.dst_stride + c0;
+    const bool whole = active && c0 + 16u <= j.cols && (reinterpret_cast<uintptr_t>(d) & 15u) == 0u;
+    if (j.cls == FXC_LDS) {
+      // b is monotone over the block's columns: its ends bound the stretch of the source row, at most 16 KiB + 1 bytes (host-checked)
+      const uint32_t c_last = min(cb + 4095u, j.cols - 1u);
+      const uint32_t b0 = j.b[cb], b1 = j.b[c_last];
+      const uint32_t s_lo = min(b0, b1), s_hi = max(b0, b1);
+      const uint8_t* first = j.src + ai + s_lo;
+      const uint32_t off0 = (uint32_t)(reinterpret_cast<uintptr_t>(first) & 3u);
+      const uint8_t* p_al = first - off0;
+      const uint32_t nbytes = s_hi - s_lo + 1u + off0;
+      __syncthreads();                                      // (the previous row's gathers are done)
+      for (uint32_t k = t; k < (nbytes + 3u) / 4u; k += 256u) s_mem[k] = fxc_load4(p_al + 4u * k, vlo, vhi);
+      __syncthreads();
+      if (active) fxc_gather16(reinterpret_cast<const uint8_t*>(s_mem) + off0, j.b, s_lo, c0, j.cols, whole, d);
+      continue;
+    }
+    if (!active) continue;
+    if (whole && (j.cls == FXC_ASC || j.cls == FXC_DESC)) {
+      const bool rev = j.cls == FXC_DESC;
+      const uint8_t* sp = j.src + ai + j.b[c0] - (rev ? 15u : 0u);
+      if ((reinterpret_cast<uintptr_t>(sp) & 15u) == 0u) {
+        const uint4 v = *reinterpret_cast<const uint4*>(sp);
+        *reinterpret_cast<uint4*>(d) = rev ? make_uint4(bswap32(v.w), bswap32(v.z), bswap32(v.y), bswap32(v.x)) : v;
+        continue;
+      }
+    }
+    fxc_gather16(j.src + ai, j.b, 0u, c0, j.cols, whole, d);
+  }
+}
+
+hipError_t launch_effect_chain(const FxChainJob* dev_jobs, const FxChainJob* host_jobs, int n, hipStream_t s) {
+  uint32_t gx = 0, gy = 0;
+  for (int k = 0; k < n; ++k) {
+    const FxChainJob& j = host_jobs[k];
+    if (j.rows == 0 || j.cols == 0) continue;
+    const bool tile = j.cls == FXC_TILE;
+    const uint32_t x = tile ? (j.cols + 63u) / 64u : (j.cols + 4095u) / 4096u;
+    const uint32_t y = tile ? (j.rows + 63u) / 64u : j.rows;
+    gx = gx > x ? gx : x;
+    gy = gy > y ? gy : y;
+  }
+  if (n <= 0 || gx == 0 || gy == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_effect_chain, dim3(gx, gy < 65535u ? gy : 65535u, (unsigned)n), dim3(256), 0, s, dev_jobs, n);
   return hipGetLastError();
 }
 
