@@ -555,6 +555,61 @@ int uhdr_hip_apply_gainmap_batch(int n, const uhdr_hip_image_t* yuv420_images,
                                  float max_display_boost, uhdr_hip_image_t* dests, int apply_mode,
                                  void* stream);
 
+/* ---- content-adaptive gain maps (no reference counterpart) ---------------------------------
+ * The reference encodes every map against minContentBoost = 1, maxContentBoost = hdr_white / 203 (ultrahdr.cpp:250-257): 255 codes
+ * over 2.3 stops (HLG, LINEAR) or 5.6 stops (PQ) whatever the picture holds, gains below 1 clipped.  The adaptive calls encode
+ * against the range the content has.  With (g_min, g_max) the min and max over map pixels of the reference's unclamped f32 gain
+ * (gainmapmath.cpp:531-534: 1 where y_sdr <= 0, else y_hdr / y_sdr -- the content_minmax statistic above), in f32:
+ *     cap = (hdr_tf == PQ ? 10000.0f : 1000.0f) / 203.0f
+ *     lo  = fminf(fmaxf(g_min, 0.25f),   1.0f)
+ *     hi  = fminf(fmaxf(g_max, 1.0625f), cap)
+ * so lo <= 1 < hi always (never a degenerate range, gain 1 always inside, never beyond the reference's maximum; a NaN or negative
+ * g_min gives 0.25).  Metadata: version "1.0", minContentBoost = hdrCapacityMin = lo, maxContentBoost = hdrCapacityMax = hi,
+ * gamma 1, offsets 0.  Map byte: the reference's three-argument encodeGain(y_sdr, y_hdr, metadata) (gainmapmath.cpp:524-541) with
+ * log2MinContentBoost = (float)log2((double)lo), likewise for hi, on exactly the luminances generate computes.  Every decoder of the
+ * format takes such a map: applyGainMap reads the range from the metadata.
+ * boost_scope: PER_IMAGE -- every image its own range; PER_CALL -- one range for all n images of the call, the rule applied to
+ * (min of the g_min, max of the g_max): bursts and frame sequences that must share metadata. */
+#define UHDR_HIP_BOOST_PER_IMAGE 0
+#define UHDR_HIP_BOOST_PER_CALL 1
+/* The rule by itself, host code.  INVALID_TRANS_FUNC for a transfer function generate refuses, BAD_PTR for NULL. */
+int uhdr_hip_adaptive_boost_range(int hdr_tf, float g_min, float g_max, float* lo, float* hi);
+int uhdr_hip_adaptive_metadata(int hdr_tf, float g_min, float g_max, uhdr_hip_metadata_t* metadata);
+/* generateGainMap for n pairs against the measured range.  Device memory only; the call only enqueues kernels on `stream` -- no
+ * allocation, no copy, no host synchronisation -- and can be captured into a graph.  The range never visits the host: pass 1
+ * (k_generate_gains) stores every map pixel's unclamped f32 gain, 4 bytes per map pixel, into `workspace` and finds the exact
+ * extremes; one small launch (k_adaptive_consts) applies the rule and derives the encode constants per image, or once for the call;
+ * pass 2 (k_encode_gains) turns the stored gains into bytes.  Pass 1 evaluates every pixel on the exact (f64) path.
+ *   content_minmax  DEVICE, 2 n floats, optional: every image's own (g_min, g_max), in either scope
+ *   boost_range     DEVICE, 2 n floats, required: the (lo, hi) map i was encoded against (PER_CALL: n equal pairs)
+ *   workspace       DEVICE, 16-byte aligned, at least what uhdr_hip_generate_adaptive_workspace_bytes answers for the same n and
+ *                   images (it reads their sizes only; 0 for n == 0); its contents before and after the call mean nothing
+ * dests[i] is filled as by uhdr_hip_generate_gainmap_batch.  Checks, in this order: those of uhdr_hip_generate_gainmap_batch_ex;
+ * UNSUPPORTED_FEATURE for an unknown boost_scope; BAD_PTR for a NULL (or misaligned) workspace or a NULL boost_range where n > 0;
+ * ERROR_INSUFFICIENT_RESOURCE for a workspace smaller than the query's answer.  Nothing is written by a call that fails them. */
+int uhdr_hip_generate_adaptive_workspace_bytes(int n, const uhdr_hip_image_t* yuv420_images, size_t* bytes);
+int uhdr_hip_generate_gainmap_adaptive_batch(int n, const uhdr_hip_image_t* yuv420_images, const uhdr_hip_image_t* p010_images,
+                                             int hdr_tf, uhdr_hip_image_t* dests, int sdr_is_601, int boost_scope,
+                                             float* content_minmax, float* boost_range, void* workspace, size_t workspace_bytes,
+                                             void* stream);
+/* One image through the adaptive batch with the measured metadata returned to the host: planes in mem_space (host planes are staged
+ * like uhdr_hip_generate_gainmap's), the workspace is the library's, and the call waits for `stream` in either memory space. */
+int uhdr_hip_generate_gainmap_adaptive(const uhdr_hip_image_t* yuv420_image, const uhdr_hip_image_t* p010_image, int hdr_tf,
+                                       uhdr_hip_metadata_t* metadata, uhdr_hip_image_t* dest, int sdr_is_601, int mem_space,
+                                       void* stream);
+/* uhdr_hip_jpegr_encode_batch with the generate step replaced by the adaptive one: the same checks in the same order, the same
+ * rounds, the same single synchronisation per round, the same per-file status semantics; the primary JPEG of every file is the one
+ * uhdr_hip_jpegr_encode_batch writes.  An unknown boost_scope is UNSUPPORTED_FEATURE, right after INVALID_QUALITY_FACTOR.  A round's
+ * boost_range pairs come down with its compressed streams; the containers carry the measured range in the gain map's XMP, and
+ * metadata (HOST, n entries, optional) receives it for every file that was processed.  The workspace is a pool slot of the call's
+ * codec context.  PER_CALL pools the files that passed their checks; with more than one round (more than 64 such files) the
+ * statistic of ALL rounds is taken before any map is encoded: every round is staged and measured once, then staged again and
+ * encoded. */
+int uhdr_hip_jpegr_encode_adaptive_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images,
+                                         int hdr_tf, int quality, const void* const* exif, const size_t* exif_size,
+                                         void* const* out, const size_t* out_capacity, size_t* out_size,
+                                         uhdr_hip_metadata_t* metadata, int* status, int boost_scope, int mem_space, void* stream);
+
 /* ---- introspection for tests -------------------------------------------------------------- */
 /* copies the 4 Shepard IDW weight tables (standard, no-right, no-bottom, corner; each
  * scale*scale*4 floats; gainmapmath.h:184-228) the apply kernels use for `scale` into out[] */
@@ -574,6 +629,8 @@ int uhdr_hip_gain_lut(const uhdr_hip_metadata_t* metadata, int with_display_boos
  *   fn 20/24/25 apply-FAST sRGB EOTF / HLG OETF / PQ OETF;  21/22 the f32 HLG / PQ inverse OETF of generate's pre-filter; 23 v_log_f32
  *   fn 40/41/42/44/45 srgbInvOetfLUT / hlgInvOetfLUT / pqInvOetfLUT / hlgOetfLUT / pqOetfLUT; 46 GainLUT(min, max,
  *              displayBoost = max).getGainFactor(in[i])
+ *   fn 60      (float)log2((double)in[i]): the log2 constant the content-adaptive path derives on the device for boost in[i]
+ *              (50-54 read FAST apply's line-segment tables)
  *   fn 30/31   gain-map byte -> float through the constant division / the IEEE division (in[i] = byte as float)
  *   fn 100/101 1.0 where the lean path of fn 0/1 passed its rounding test, else 0.0
  * Used by the exhaustive transfer-function tests. */

@@ -90,6 +90,12 @@ class UltraHdrHip {
                            ultrahdr_transfer_function hdr_tf, ultrahdr_metadata_ptr metadata,
                            uhdr_uncompressed_ptr dest, bool sdr_is_601 = false);
 
+  // generateGainMap against the range the content has (include/uhdr_hip.h, "content-adaptive gain maps"): the same arguments,
+  // checks and new[] contract; *metadata receives the measured range instead of the reference's constants
+  status_t generateGainMapAdaptive(uhdr_uncompressed_ptr yuv420_image_ptr, uhdr_uncompressed_ptr p010_image_ptr,
+                                   ultrahdr_transfer_function hdr_tf, ultrahdr_metadata_ptr metadata,
+                                   uhdr_uncompressed_ptr dest, bool sdr_is_601 = false);
+
   status_t applyGainMap(uhdr_uncompressed_ptr yuv420_image_ptr, uhdr_uncompressed_ptr gainmap_image_ptr,
                         ultrahdr_metadata_ptr metadata, ultrahdr_output_format output_format,
                         float max_display_boost, uhdr_uncompressed_ptr dest);
@@ -106,6 +112,8 @@ class UltraHdrHip {
 
  private:
   status_t ensureInit();
+  status_t generateImpl(uhdr_uncompressed_ptr yuv420_image_ptr, uhdr_uncompressed_ptr p010_image_ptr, ultrahdr_transfer_function hdr_tf,
+                        ultrahdr_metadata_ptr metadata, uhdr_uncompressed_ptr dest, bool sdr_is_601, bool adaptive);
   int mDevice;
   bool mReady = false;
   int mApplyMode = 0;
@@ -219,9 +227,13 @@ class JpegRHip {
   status_t getJPEGRInfo(uhdr_compressed_ptr jpegr_image_ptr, uhdr_info_ptr jpeg_image_info_ptr);
 
   void setApplyMode(int mode) { mApplyMode = mode; }   // UHDR_HIP_APPLY_EXACT (default here: decoded files equal the reference's), FAST, LUT
+  // -1 (default): the reference's constant boost range.  UHDR_HIP_BOOST_PER_IMAGE / UHDR_HIP_BOOST_PER_CALL: the API-0 and API-1
+  // overloads encode the gain map against the range the content has (uhdr_hip_jpegr_encode_adaptive_batch); the others are unchanged
+  void setContentBoost(int scope_or_minus_one) { mContentBoost = scope_or_minus_one; }
 
  private:
   int mApplyMode = 1;
+  int mContentBoost = -1;
 };
 
 }  // namespace ultrahdr

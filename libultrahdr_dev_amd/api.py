@@ -28,6 +28,7 @@ MEM_DEVICE_TO_HOST, MEM_HOST_TO_DEVICE = 2, 3   # uhdr_hip_jpeg_encode_batch: pl
 DECODE_TO_RGBA, DECODE_TO_YCBCR = 1, 2          # uhdr_hip_jpeg_decode_batch
 APPLY_FAST, APPLY_EXACT, APPLY_LUT, APPLY_EXACT_UNFILTERED = 0, 1, 2, 3
 GENERATE_EXACT, GENERATE_LUT, GENERATE_UNFILTERED = 0, 1, 2
+BOOST_PER_IMAGE, BOOST_PER_CALL = 0, 1          # content-adaptive gain maps: one boost range per image / per call
 ABI_VERSION = 3
 FLT_MAX = 3.4028234663852886e38
 
@@ -132,6 +133,15 @@ SIGNATURES = {
     "uhdr_hip_idw_tables": (C.c_int, [C.c_int, C.POINTER(C.c_float)]),
     "uhdr_hip_eval_transfer": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p]),
     "uhdr_hip_synth_lcg_frame": (C.c_int, [C.c_size_t, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uhdr_hip_adaptive_boost_range": (C.c_int, [C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "uhdr_hip_adaptive_metadata": (C.c_int, [C.c_int, C.c_float, C.c_float, _MP]),
+    "uhdr_hip_generate_adaptive_workspace_bytes": (C.c_int, [C.c_int, _IP, C.POINTER(C.c_size_t)]),
+    "uhdr_hip_generate_gainmap_adaptive_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _IP, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_size_t, C.c_void_p]),
+    "uhdr_hip_generate_gainmap_adaptive": (C.c_int, [_IP, _IP, C.c_int, _MP, _IP, C.c_int, C.c_int, C.c_void_p]),
+    "uhdr_hip_jpegr_encode_adaptive_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                       C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _MP, C.POINTER(C.c_int),
+                                                       C.c_int, C.c_int, C.c_void_p]),
 }
 
 _lib = None
@@ -253,6 +263,24 @@ def image_array(images):
 
 def metadata(max_boost, min_boost=1.0, version=b"1.0"):
     return Metadata(version, float(max_boost), float(min_boost), 1.0, 0.0, 0.0, float(min_boost), float(max_boost))
+
+
+def adaptive_boost_range(hdr_tf, g_min, g_max):
+    """uhdr_hip_adaptive_boost_range: the (lo, hi) a content-adaptive map with extremes (g_min, g_max) is encoded against"""
+    lo, hi = C.c_float(), C.c_float()
+    rc = load().uhdr_hip_adaptive_boost_range(hdr_tf, g_min, g_max, C.byref(lo), C.byref(hi))
+    if rc != NO_ERROR:
+        raise UhdrHipError("uhdr_hip_adaptive_boost_range -> %d" % rc)
+    return lo.value, hi.value
+
+
+def adaptive_workspace_bytes(yuv_images):
+    """uhdr_hip_generate_adaptive_workspace_bytes for a list of Image descriptors"""
+    n = C.c_size_t()
+    rc = load().uhdr_hip_generate_adaptive_workspace_bytes(len(yuv_images), image_array(yuv_images) if yuv_images else None, C.byref(n))
+    if rc != NO_ERROR:
+        raise UhdrHipError("uhdr_hip_generate_adaptive_workspace_bytes -> %d" % rc)
+    return n.value
 
 
 class MemPool:

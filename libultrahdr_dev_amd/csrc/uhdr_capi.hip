@@ -329,6 +329,104 @@ bool gen_aligned(const GenImage& g, uint32_t w, uint32_t h) {
          al(g.y, 8) && g.y_stride % 8u == 0 && al(g.u, 4) && al(v, 4) && g.c_stride % 4u == 0 && al(g.map, 2);
 }
 
+// ---- content-adaptive generate ---------------------------------------------------------------------
+// the range rule of include/uhdr_hip.h, in f32; k_adaptive_consts performs the same operations on the device
+float adaptive_cap(int hdr_tf) { return (hdr_tf == UHDR_HIP_TF_PQ ? 10000.0f : 1000.0f) / 203.0f; }
+void adaptive_range(int hdr_tf, float g_min, float g_max, float* lo, float* hi) {
+  *lo = fminf(fmaxf(g_min, 0.25f), 1.0f);
+  *hi = fminf(fmaxf(g_max, 1.0625f), adaptive_cap(hdr_tf));
+}
+void fill_adaptive_metadata(float lo, float hi, uhdr_hip_metadata_t* md) {
+  memset(md->version, 0, sizeof(md->version));
+  strcpy(md->version, "1.0");
+  md->maxContentBoost = hi;
+  md->minContentBoost = lo;
+  md->gamma = 1.0f;
+  md->offsetSdr = 0.0f;
+  md->offsetHdr = 0.0f;
+  md->hdrCapacityMin = lo;
+  md->hdrCapacityMax = hi;
+}
+bool valid_boost_scope(int scope) { return scope == UHDR_HIP_BOOST_PER_IMAGE || scope == UHDR_HIP_BOOST_PER_CALL; }
+
+// the caller's workspace: the images' key pairs, their constants, then every image's gains (4 bytes per map pixel), each piece
+// a multiple of 256 bytes
+struct AdaptLayout {
+  size_t keys = 0, consts = 0, total = 0;
+  std::vector<size_t> gains;
+};
+AdaptLayout adaptive_layout(int n, const uhdr_hip_image_t* yuvs) {
+  AdaptLayout l;
+  if (n <= 0) return l;
+  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
+  l.keys = 0;
+  l.consts = up(sizeof(uint32_t) * 2 * (size_t)n);
+  size_t o = l.consts + up(sizeof(AdaptConsts) * (size_t)n);
+  l.gains.resize((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    l.gains[(size_t)i] = o;
+    o += up(sizeof(float) * (yuvs[i].width / 4) * (yuvs[i].height / 4));
+  }
+  l.total = o;
+  return l;
+}
+
+// The two passes of uhdr_hip_generate_gainmap_adaptive_batch on checked arguments, enqueue only.  carry_in / carry_out (DEVICE, two
+// key words, or null; PER_CALL only): the pooled extremes of earlier calls join this call's, and the joined pair is left behind --
+// a statistic taken over several calls.  encode == false stops after the constants: the call only measures.
+int adaptive_enqueue(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf, uhdr_hip_image_t* dests,
+                     int sdr_is_601, int boost_scope, float* content_minmax, float* boost_range, void* workspace,
+                     const uint32_t* carry_in, uint32_t* carry_out, bool encode, hipStream_t s) {
+  if (n <= 0) return UHDR_HIP_NO_ERROR;
+  const AdaptLayout lay = adaptive_layout(n, yuvs);
+  uint8_t* ws = static_cast<uint8_t*>(workspace);
+  uint32_t* keys = reinterpret_cast<uint32_t*>(ws + lay.keys);
+  AdaptConsts* consts = reinterpret_cast<AdaptConsts*>(ws + lay.consts);
+  uhdr_hip_metadata_t md;
+  fill_generate_metadata(hdr_tf, &md);   // (pass 1 stores gains, no bytes: what generate_consts derives from the range is not used)
+  HIP_TRY(launch_adaptive_init(keys, 2u * (uint32_t)n, s));
+  std::vector<std::pair<int, int>> chunks;   // (first image, images) of every launch
+  int i = 0;
+  while (i < n) {
+    // chunk = up to kMaxChunk consecutive images of identical size, gamuts and alignment class, as uhdr_hip_generate_gainmap_batch_ex
+    const uhdr_hip_image_t& y0 = yuvs[i];
+    GenConsts c = generate_consts(y0.colorGamut, p010s[i].colorGamut, hdr_tf, sdr_is_601, y0.width, y0.height, md);
+    c.stat_keys = keys + 2 * i;
+    c.stat_stride = 2;
+    GenBatch b;
+    int m = 0;
+    bool aligned = true;
+    while (i + m < n && m < kMaxChunk) {
+      const uhdr_hip_image_t& y = yuvs[i + m];
+      if (y.width != y0.width || y.height != y0.height || y.colorGamut != y0.colorGamut || p010s[i + m].colorGamut != p010s[i].colorGamut)
+        break;
+      b.img[m] = gen_image(y, p010s[i + m], ws + lay.gains[(size_t)(i + m)]);
+      const bool a = gen_aligned(b.img[m], c.width, c.height);
+      if (m == 0) aligned = a;
+      else if (a != aligned) break;
+      ++m;
+    }
+    HIP_TRY(launch_generate_gains(c, b, m, hdr_tf, aligned, s));
+    chunks.emplace_back(i, m);
+    i += m;
+  }
+  HIP_TRY(launch_adaptive_consts(keys, n, boost_scope == UHDR_HIP_BOOST_PER_CALL ? 1 : 0, adaptive_cap(hdr_tf), consts, content_minmax,
+                                 boost_range, carry_in, carry_out, s));
+  if (!encode) return UHDR_HIP_NO_ERROR;
+  for (const auto& ch : chunks) {
+    EncGainBatch eb;
+    for (int k = 0; k < ch.second; ++k) {
+      const size_t j = (size_t)(ch.first + k);
+      eb.img[k].gains = reinterpret_cast<const float*>(ws + lay.gains[j]);
+      eb.img[k].map = static_cast<uint8_t*>(dests[j].data);
+      fill_generate_dest(&yuvs[j], &dests[j]);
+    }
+    const uhdr_hip_image_t& y0 = yuvs[ch.first];
+    HIP_TRY(launch_encode_gains(consts + ch.first, eb, ch.second, (uint32_t)((y0.width / 4) * (y0.height / 4)), s));
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
 // ---- FAST apply's line-segment tables (uhdr_kernels.h, k_apply_s4) ---------------------------------
 // An entry is the chord of the function over its cell, lowered by half its largest deviation, as (c0, c1): f ~ c0 + c1 * argument.
 template <class F>
@@ -1122,6 +1220,8 @@ int host_pool_reserve(DeviceState* st, size_t bytes) {
 }
 // the JPEG encoder's pool slots, then encodeJPEGR's planes
 enum : size_t { kEncWs = 0, kEncDesc, kEncSdr, kEncMap, kEncP010, kEncYuv };
+// the adaptive encode's workspace and the key pair it carries from round to round: slots no other codec path of a context names
+enum : size_t { kEncAdaptWs = 8, kEncAdaptCarry = 9 };
 
 // one image of compress_to_host: device planes and how to compress them in, the JPEG out
 struct EncJpeg {
@@ -1143,7 +1243,10 @@ struct EncJpeg {
 // its page-locked host pool, one jpeg::encode_batch_async writes the streams behind them and their sizes, and one synchronisation
 // ends it.  A file larger than its staging was cut off: it is compressed again in a context of its own, so that this one's host
 // pool, which holds the other files, is left alone.  A non-zero return is an error of the device or the runtime.
-int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool may_retry = true) {
+// dev_extra (or null): extra_bytes of device memory that come down with the streams -- copied into the host pool behind the same
+// synchronisation, then to host_extra (the adaptive encode's boost ranges).
+int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool may_retry = true, const void* dev_extra = nullptr,
+                     size_t extra_bytes = 0, void* host_extra = nullptr) {
   std::vector<jpeg::Job> jobs((size_t)k);
   std::vector<jpeg::Layout> lay((size_t)k);
   std::vector<jpeg::BatchOut> outs((size_t)k);
@@ -1163,6 +1266,8 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     off[i] = hp_total;
     hp_total += round_up(e.to_dev ? header[i].size() : im[i].cap, 256);   // a device destination: the header's way there only
   }
+  const size_t extra_off = hp_total;
+  if (dev_extra != nullptr) hp_total += round_up(extra_bytes, 256);
   int rc;
   if ((rc = host_pool_reserve(st, hp_total)) != 0) return rc;
   if ((rc = pool_reserve(st, kEncWs, ws_total)) != 0) return rc;
@@ -1184,7 +1289,9 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     wss[i] = static_cast<uint8_t*>(st->pool[kEncWs]) + ws_off[i];
   }
   HIP_TRY(jpeg::encode_batch_async(k, jobs.data(), lay.data(), wss.data(), outs.data(), hp, static_cast<uint8_t*>(st->pool[kEncDesc]), s));
+  if (dev_extra != nullptr) HIP_TRY(hipMemcpyAsync(hp + extra_off, dev_extra, extra_bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  if (dev_extra != nullptr) memcpy(host_extra, hp + extra_off, extra_bytes);
   for (int i = 0; i < k; ++i) {
     EncJpeg& e = im[i];
     const uint64_t total = sizes[i];
@@ -2108,8 +2215,11 @@ int make_gainmap_jpeg(DeviceState* st, hipStream_t s, const uhdr_hip_image_t& yu
 // One round: staging (host callers), toneMap (API-0), generateGainMap, BT.601 re-encode -- one launch per step for the round's
 // files -- then the 2 m compressions with one synchronisation (compress_to_host).  Leaves file k's JPEGs in (*jpg)[2 k] (SDR) and
 // (*jpg)[2 k + 1] (gain map).  A non-zero return is an error of the device or the runtime (every file of the round fails with it).
+// boost_scope >= 0: the adaptive generate instead; range (2 m floats) receives the files' (lo, hi) behind the round's synchronisation.
+// carry != 0 (PER_CALL over several rounds): the rounds' pooled extremes travel in the context's carry slot; carry == 1 measures
+// only -- staging, toneMap and pass 1, no map, no compression, no synchronisation --, carry == 2 encodes against the carried pair.
 int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_tf, int quality, EncFile* f, int m, uhdr_hip_metadata_t* md,
-                 std::vector<EncJpeg>* jpg) {
+                 std::vector<EncJpeg>* jpg, int boost_scope = -1, float* range = nullptr, int carry = 0) {
   auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
   int rc;
   // sizes of the round's slices
@@ -2178,7 +2288,20 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
   }
   // generateGainMap: the files are sorted by size and gamuts, so equal ones share its launches
   for (int k = 0; k < m; ++k) { a[k] = f[k].yuv; b[k] = f[k].p010; c[k] = f[k].map; }
-  if ((rc = uhdr_hip_generate_gainmap_batch(m, a.data(), b.data(), hdr_tf, md, c.data(), 0, nullptr, s)) != UHDR_HIP_NO_ERROR) return rc;
+  float* dev_range = nullptr;
+  if (boost_scope < 0) {
+    if ((rc = uhdr_hip_generate_gainmap_batch(m, a.data(), b.data(), hdr_tf, md, c.data(), 0, nullptr, s)) != UHDR_HIP_NO_ERROR) return rc;
+  } else {
+    const size_t ws_bytes = adaptive_layout(m, a.data()).total;
+    if ((rc = pool_reserve(st, kEncAdaptWs, ws_bytes + 256 + round_up(8 * (size_t)m, 256))) != 0) return rc;
+    uint8_t* ws = static_cast<uint8_t*>(st->pool[kEncAdaptWs]);
+    dev_range = reinterpret_cast<float*>(ws + ws_bytes + 256);
+    uint32_t* cw = carry != 0 ? static_cast<uint32_t*>(st->pool[kEncAdaptCarry]) : nullptr;
+    if ((rc = adaptive_enqueue(m, a.data(), b.data(), hdr_tf, c.data(), 0, boost_scope, nullptr, dev_range, ws, cw, carry == 1 ? cw : nullptr,
+                               carry != 1, s)) != UHDR_HIP_NO_ERROR)
+      return rc;
+    if (carry == 1) return UHDR_HIP_NO_ERROR;
+  }
   // convertYuv to BT.601 unless P3: API-0 in place, API-1 into the private copy; equal sizes and gamuts share a launch
   for (int k = 0; k < m;) {
     if (f[k].enc.colorGamut == UHDR_HIP_CG_P3) { ++k; continue; }
@@ -2207,14 +2330,14 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
     jpg->push_back(EncJpeg{e.enc, quality, &e.icc, e.pad_ls, e.pad_cs});
     jpg->push_back(gainmap_jpeg(g, g.luma_stride));
   }
-  return compress_to_host(st, s, 2 * m, jpg->data());
+  return compress_to_host(st, s, 2 * m, jpg->data(), true, dev_range, dev_range ? 8 * (size_t)m : 0, range);
 }
 
 // encodeJPEGR API-1 (yuv420_images != NULL) or API-0 for n pairs, the quality checked: the files' kernels share their launches, the
 // call synchronises once per round of up to kEncRound files, and the containers are assembled by a few host threads
 int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
                  const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
-                 int* status, int mem_space, void* stream) {
+                 int* status, int mem_space, void* stream, int boost_scope = -1, uhdr_hip_metadata_t* metadata = nullptr) {
   const bool api0 = yuv420_images == nullptr;
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
   std::vector<EncFile> files;
@@ -2259,13 +2382,39 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
       ~SyncOnExit() { (void)hipStreamSynchronize(s); }
     } sync_on_exit{s};
     size_t r0 = 0;   // files [0, r0) are finished
+    // PER_CALL over several rounds: the statistic of all rounds first (every round staged and measured, the pooled extremes carried
+    // along in device memory), then the rounds proper, encoded against the carried pair
+    const int carry = boost_scope == UHDR_HIP_BOOST_PER_CALL && files.size() > (size_t)kEncRound ? 2 : 0;
+    if (rc == UHDR_HIP_NO_ERROR && carry != 0) {
+      rc = pool_reserve(st, kEncAdaptCarry, 256);
+      if (rc == UHDR_HIP_NO_ERROR) {
+        const hipError_t e = launch_adaptive_init(static_cast<uint32_t*>(st->pool[kEncAdaptCarry]), 2u, s);
+        if (e != hipSuccess) { set_err("launch_adaptive_init", e); rc = UHDR_HIP_UNKNOWN_ERROR; }
+      }
+      for (size_t q0 = 0; rc == UHDR_HIP_NO_ERROR && q0 < files.size(); q0 += kEncRound) {
+        const int m = (int)std::min(files.size() - q0, (size_t)kEncRound);
+        std::vector<EncFile> probe(files.begin() + (long)q0, files.begin() + (long)q0 + m);   // (a round rewrites its files' descriptors)
+        uhdr_hip_metadata_t md;
+        std::vector<EncJpeg> jpg;
+        rc = encode_round(st, s, api0, mem_space != UHDR_HIP_MEM_DEVICE, hdr_tf, quality, probe.data(), m, &md, &jpg, boost_scope, nullptr, 1);
+      }
+    }
+    std::vector<float> range(2 * (size_t)kEncRound);
     for (; rc == UHDR_HIP_NO_ERROR && r0 < files.size(); r0 += kEncRound) {
       const int m = (int)std::min(files.size() - r0, (size_t)kEncRound);
       EncFile* f = &files[r0];
       uhdr_hip_metadata_t md;
       std::vector<EncJpeg> jpg;
-      rc = encode_round(st, s, api0, mem_space != UHDR_HIP_MEM_DEVICE, hdr_tf, quality, f, m, &md, &jpg);
+      rc = encode_round(st, s, api0, mem_space != UHDR_HIP_MEM_DEVICE, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry);
       if (rc != UHDR_HIP_NO_ERROR) break;
+      std::vector<uhdr_hip_metadata_t> mds;   // adaptive: every file's own
+      if (boost_scope >= 0) {
+        mds.resize((size_t)m);
+        for (int k = 0; k < m; ++k) {
+          fill_adaptive_metadata(range[2 * (size_t)k], range[2 * (size_t)k + 1], &mds[(size_t)k]);
+          if (metadata) metadata[f[k].idx] = mds[(size_t)k];
+        }
+      }
       // appendGainMap (jpegr.cpp:951-1130) straight into the caller's buffers, a few host threads side by side
       auto assemble = [&](int lo, int hi) {
         for (int k = lo; k < hi; ++k) {
@@ -2274,7 +2423,8 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
           const EncJpeg& sdr = jpg[2 * (size_t)k];
           const EncJpeg& gm = jpg[2 * (size_t)k + 1];
           st_[i] = jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
-                                            nullptr, 0, md, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i]);
+                                            nullptr, 0, boost_scope >= 0 ? mds[(size_t)k] : md, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i],
+                                            boost_scope >= 0);
         }
       };
       const int nthreads = m >= 2 ? std::min(m, 8) : 1;
@@ -2382,6 +2532,19 @@ int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, cons
     return UHDR_HIP_ERROR_BAD_PTR;
   if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
   return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream);
+}
+
+int uhdr_hip_jpegr_encode_adaptive_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf,
+                                         int quality, const void* const* exif, const size_t* exif_size, void* const* out,
+                                         const size_t* out_capacity, size_t* out_size, uhdr_hip_metadata_t* metadata, int* status,
+                                         int boost_scope, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
+  if (!valid_boost_scope(boost_scope)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream,
+                      boost_scope, metadata);
 }
 
 // JpegR::encodeJPEGR API-0 (jpegr.cpp:186-247): a batch of one file
@@ -3022,6 +3185,52 @@ int uhdr_hip_generate_gainmap_batch_ex(int n, const uhdr_hip_image_t* yuvs, cons
   return UHDR_HIP_NO_ERROR;
 }
 
+// ---- content-adaptive generate -----------------------------------------------------------------------
+int uhdr_hip_adaptive_boost_range(int hdr_tf, float g_min, float g_max, float* lo, float* hi) {
+  if (lo == nullptr || hi == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  adaptive_range(hdr_tf, g_min, g_max, lo, hi);
+  return UHDR_HIP_NO_ERROR;
+}
+
+int uhdr_hip_adaptive_metadata(int hdr_tf, float g_min, float g_max, uhdr_hip_metadata_t* metadata) {
+  if (metadata == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  float lo, hi;
+  const int rc = uhdr_hip_adaptive_boost_range(hdr_tf, g_min, g_max, &lo, &hi);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  fill_adaptive_metadata(lo, hi, metadata);
+  return UHDR_HIP_NO_ERROR;
+}
+
+int uhdr_hip_generate_adaptive_workspace_bytes(int n, const uhdr_hip_image_t* yuvs, size_t* bytes) {
+  if (n < 0 || (n > 0 && yuvs == nullptr) || bytes == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  *bytes = adaptive_layout(n, yuvs).total;
+  return UHDR_HIP_NO_ERROR;
+}
+
+int uhdr_hip_generate_gainmap_adaptive_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf,
+                                             uhdr_hip_image_t* dests, int sdr_is_601, int boost_scope, float* content_minmax,
+                                             float* boost_range, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n < 0 || (n > 0 && (yuvs == nullptr || p010s == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
+  uhdr_hip_metadata_t md;   // (the checks of uhdr_hip_generate_gainmap_batch_ex take one)
+  for (int i = 0; i < n; ++i) {
+    const int rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, &md, &dests[i]);
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
+    if (dests[i].data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  }
+  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ)
+    return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (!valid_boost_scope(boost_scope)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (n > 0 && (boost_range == nullptr || workspace == nullptr || !al(workspace, 16))) return UHDR_HIP_ERROR_BAD_PTR;
+  if (workspace_bytes < adaptive_layout(n, yuvs).total) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  if (n == 0) return UHDR_HIP_NO_ERROR;
+  DeviceState* st = nullptr;
+  const int rc = current_state(&st);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return adaptive_enqueue(n, yuvs, p010s, hdr_tf, dests, sdr_is_601, boost_scope, content_minmax, boost_range, workspace, nullptr,
+                          nullptr, true, static_cast<hipStream_t>(stream));
+}
+
 int uhdr_hip_apply_gainmap_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* maps,
                                  const uhdr_hip_metadata_t* metadata, int output_format, float max_display_boost,
                                  uhdr_hip_image_t* dests, int apply_mode, void* stream) {
@@ -3122,6 +3331,43 @@ int uhdr_hip_generate_gainmap_ex(const uhdr_hip_image_t* yuv, const uhdr_hip_ima
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   if (mw * mh) HIP_TRY(hipMemcpyAsync(dest->data, dm.data, mw * mh, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  fill_generate_dest(yuv, dest);
+  return UHDR_HIP_NO_ERROR;
+}
+
+// one image through the adaptive batch, the measured metadata back on the host: the call waits for the stream in either memory space
+int uhdr_hip_generate_gainmap_adaptive(const uhdr_hip_image_t* yuv, const uhdr_hip_image_t* p010, int hdr_tf,
+                                       uhdr_hip_metadata_t* metadata, uhdr_hip_image_t* dest, int sdr_is_601, int mem_space,
+                                       void* stream) {
+  int rc = validate_generate(yuv, p010, hdr_tf, metadata, dest);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if (dest->data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  StageLease lease(st);
+  StageSet* ss = lease.get();
+  if (ss == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
+  uhdr_hip_image_t dy = *yuv, dp = *p010, dm = *dest;
+  const size_t mw = yuv->width / 4, mh = yuv->height / 4;
+  if (host) {
+    if ((rc = stage_yuv420_in(ss, 0, *yuv, &dy, s)) != 0) return rc;
+    if ((rc = stage_p010_in(ss, 2, *p010, &dp, s)) != 0) return rc;
+    if ((rc = stage_reserve(ss, 4, mw * mh)) != 0) return rc;
+    dm.data = ss->stage[4];
+  }
+  const size_t ws_bytes = adaptive_layout(1, &dy).total;
+  if ((rc = stage_reserve(ss, 5, ws_bytes + 256)) != 0) return rc;
+  uint8_t* ws = static_cast<uint8_t*>(ss->stage[5]);
+  float* dev_range = reinterpret_cast<float*>(ws + ws_bytes);
+  rc = adaptive_enqueue(1, &dy, &dp, hdr_tf, &dm, sdr_is_601, UHDR_HIP_BOOST_PER_IMAGE, nullptr, dev_range, ws, nullptr, nullptr, true, s);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  float range[2];
+  if (host && mw * mh) HIP_TRY(hipMemcpyAsync(dest->data, dm.data, mw * mh, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipMemcpyAsync(range, dev_range, sizeof(range), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  fill_adaptive_metadata(range[0], range[1], metadata);
   fill_generate_dest(yuv, dest);
   return UHDR_HIP_NO_ERROR;
 }

@@ -478,6 +478,10 @@ __device__ __forceinline__ uint8_t encode_gain_guarded(float gain, float min_boo
   return (uint8_t)(uint32_t)fl;
 }
 
+// (float)log2((double)boost): log2MinContentBoost / log2MaxContentBoost (ultrahdr.cpp:259-260) derived on the device, for ranges
+// that are measured there (k_adaptive_consts; uhdr_hip_eval_transfer fn 60 evaluates it by itself)
+__device__ __forceinline__ float log2_to_float(float boost) { return (float)log2((double)boost); }
+
 // ---- output packing (gainmapmath.cpp:722-732, gainmapmath.h:136-147) ---------------------------
 __device__ __forceinline__ uint32_t pack_1010102(float r, float g, float b) {
   return (0x3ffu & (uint32_t)(r * 1023.0f)) | ((0x3ffu & (uint32_t)(g * 1023.0f)) << 10) |

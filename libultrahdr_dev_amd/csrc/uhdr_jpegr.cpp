@@ -443,8 +443,13 @@ bool metadata_valid(const uhdr_hip_metadata_t& md) {   // jpegr.cpp:961-984 (a N
 // (the two compressed streams are megabytes: one copy each, no intermediate container); *size is set whenever the size is known,
 // ERROR_INSUFFICIENT_RESOURCE when cap is smaller (Write() running past maxLength, jpegr.cpp:46-61).
 int append_gainmap_to(const uint8_t* primary_in, size_t n1, const uint8_t* gainmap, size_t n2, const uint8_t* exif, size_t exif_len,
-                      const uint8_t* icc, size_t icc_len, const uhdr_hip_metadata_t& md, uint8_t* dst, size_t cap, size_t* size) {
-  if (!metadata_valid(md)) return UHDR_HIP_ERROR_BAD_METADATA;
+                      const uint8_t* icc, size_t icc_len, const uhdr_hip_metadata_t& md, uint8_t* dst, size_t cap, size_t* size,
+                      bool measured_range) {
+  // measured_range (the adaptive encode's own metadata): hdrCapacityMin = minContentBoost may lie below 1, which :971 refuses for a
+  // caller's metadata; applyGainMap (ultrahdr.cpp:381) wants exactly that equality, so such a file decodes
+  uhdr_hip_metadata_t chk = md;
+  if (measured_range && chk.hdrCapacityMin == chk.minContentBoost && chk.hdrCapacityMin < 1.0f) chk.hdrCapacityMin = 1.0f;
+  if (!metadata_valid(chk)) return UHDR_HIP_ERROR_BAD_METADATA;
   if (n2 < 2) return UHDR_HIP_ERROR_BAD_PTR;
   static const char kNs[] = "http://ns.adobe.com/xap/1.0/";   // sizeof counts the terminator, as nameSpaceLength does
   const std::string xs = xmp_secondary(md);

@@ -114,6 +114,24 @@ struct GenBatch {
   GenImage img[kMaxChunk];
 };
 
+// ---- content-adaptive generate ---------------------------------------------
+// Two passes over a caller-provided workspace: k_generate_gains leaves every map pixel's exact unclamped f32 gain there and the
+// images' extremes as keys; k_adaptive_consts turns the extremes into each image's boost range and encodeGain constants -- on the
+// device, the range never visits the host --; k_encode_gains turns the stored gains into bytes.
+struct AdaptConsts {   // what generate_consts / encode_constants compute on the host for a fixed range
+  float min_boost, max_boost, log2_min, log2_max;
+  double enc_scale;
+  uint32_t enc_byte_min, enc_byte_max;
+};
+struct EncGainImage {
+  const float* gains;   // map_w * map_h floats, 16-byte aligned
+  uint8_t* map;
+};
+struct EncGainBatch {
+  EncGainImage img[kMaxChunk];
+};
+static_assert(sizeof(AdaptConsts) == 32, "one image's constants are read as two 16-byte pieces");
+
 // ---- apply -------------------------------------------------------------------------------------
 // constants of the FAST scale-4 kernel (see k_apply_s4): wD[oy][pair][k-2] = (w_k(ox=2*pair), w_k(ox=2*pair+1)) * A / 255
 // E = B + A255 * m1 + sum_{k=2..4} (m_k - m1) * wD[.][.][k-2][.]   (m: the four map bytes as floats; the weights of a cell sum to 1)
@@ -237,6 +255,16 @@ hipError_t launch_stats_init(uint32_t* keys, int n, hipStream_t s);
 hipError_t launch_stats_resolve(const GenConsts& c, const GenBatch& b, int n, int hdr_tf, bool aligned, hipStream_t s);
 constexpr size_t kStatWsBytes = sizeof(uint32_t) * kStatWords * (size_t)kMaxChunk;
 hipError_t launch_stats_finalize(uint32_t* keys, int n, hipStream_t s);
+// content-adaptive generate.  Keys: two words per image, ~key(min) and key(max), both only grow from 0 (publish_minmax).
+hipError_t launch_adaptive_init(uint32_t* keys, uint32_t words, hipStream_t s);   // keys[0 .. words) = 0, as a kernel
+// pass 1 of n <= kMaxChunk images of one size: GenImage::map points at the image's GAINS (float, 16-byte aligned), c.stat_keys at its keys
+hipError_t launch_generate_gains(const GenConsts& c, const GenBatch& b, int n, int hdr_tf, bool aligned, hipStream_t s);
+// the range rule and the encode constants of n images from their keys.  per_call: one range from the extremes of all n images and of
+// carry_in (two key words of earlier launches, or null); carry_out (or null) receives the merged pair.  content_minmax may be null.
+hipError_t launch_adaptive_consts(const uint32_t* keys, int n, int per_call, float cap, AdaptConsts* consts, float* content_minmax,
+                                  float* boost_range, const uint32_t* carry_in, uint32_t* carry_out, hipStream_t s);
+// pass 2 of n <= kMaxChunk images of `pixels` map pixels each; consts[i] belongs to b.img[i]
+hipError_t launch_encode_gains(const AdaptConsts* consts, const EncGainBatch& b, int n, uint32_t pixels, hipStream_t s);
 // mode: 0 FAST, 1 EXACT, 2 LUT
 hipError_t launch_apply(const AppConsts& c, const AppBatch& b, int n, int fmt, int mode,
                         bool fast_s4, hipStream_t s);

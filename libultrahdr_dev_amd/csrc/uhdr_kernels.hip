@@ -967,6 +967,166 @@ hipError_t launch_stats_finalize(uint32_t* keys, int n, hipStream_t s) {
 }
 
 // =================================================================================================
+// content-adaptive generate (uhdr_hip_generate_gainmap_adaptive_batch)
+// =================================================================================================
+__global__ void __launch_bounds__(256) k_adaptive_init(uint32_t* keys, uint32_t words) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < words) keys[i] = 0u;
+}
+hipError_t launch_adaptive_init(uint32_t* keys, uint32_t words, hipStream_t s) {
+  if (words == 0u) return hipSuccess;
+  hipLaunchKernelGGL(k_adaptive_init, dim3((words + 255u) / 256u), dim3(256), 0, s, keys, words);
+  return hipGetLastError();
+}
+
+// Pass 1: k_generate's front end on the exact path -- the same sampling, the same luminances -- but what a thread stores is the
+// unclamped f32 gain of its two map pixels (raw_gain: 1 where the SDR luminance is 0), 4 bytes per map pixel into the image's part
+// of the workspace (GenImage::map), and no byte: the range they are encoded against is not known before the whole image has been
+// seen.  The image's extremes are the extremes of exactly these floats (publish_minmax on the image's two key words).
+template <int TF, bool ALIGNED, int TILES>
+__global__ void __launch_bounds__(kGenBlock, 1) k_generate_gains(const GenConsts c, const GenBatch b) {
+  const uint32_t img_i = blockIdx.x, blk = blockIdx.y;
+  const GenImage& im = b.img[img_i];
+  const uint8_t* im_v = im.u + (size_t)im.c_stride * (c.height / 2u);
+  float* gains = reinterpret_cast<float*>(im.map);
+  const uint32_t pairs_per_row = (c.map_w + 1u) >> 1;
+  const uint32_t total = pairs_per_row * c.map_h;
+  float emin = __builtin_inff(), emax = -__builtin_inff();
+#pragma unroll 1
+  for (uint32_t t = 0; t < (uint32_t)TILES; ++t) {
+    const uint32_t idx = (blk * (uint32_t)TILES + t) * (uint32_t)kGenBlock + threadIdx.x;
+    if (idx >= total) break;
+    const uint32_t my = idx / pairs_per_row;
+    const uint32_t pr = idx - my * pairs_per_row;
+    const uint32_t mx = pr * 2u;
+    const bool two = ALIGNED || (mx + 1u < c.map_w);
+    uint32_t hy[2][4][2], huv[2][2][2], y8[2][4], u8[2][2], v8[2][2];
+    load_pair<ALIGNED>(c, im, im_v, my, pr, two, hy, huv, y8, u8, v8);
+    uint8_t o[2];
+    float gn[2];
+    gen_pair<TF, false, false>(c, hy, huv, y8, u8, v8, o, gn, nullptr, nullptr);   // (a missing second pixel is computed on zeros and dropped)
+    emin = fminf(emin, gn[0]); emax = fmaxf(emax, gn[0]);
+    if (two) { emin = fminf(emin, gn[1]); emax = fmaxf(emax, gn[1]); }
+    float* gp = gains + (size_t)my * c.map_w + mx;
+    if (ALIGNED) {   // map_w is even and the image's gains are 16-byte aligned: the pair is one 8-byte store
+      *reinterpret_cast<float2*>(gp) = make_float2(gn[0], gn[1]);
+    } else {
+      gp[0] = gn[0];
+      if (two) gp[1] = gn[1];
+    }
+  }
+  wave_minmax(emin, emax);   // (every lane arrives here)
+  publish_minmax(emin, emax, c.stat_keys + (size_t)c.stat_stride * img_i);
+}
+template <int TF>
+static hipError_t launch_generate_gains_tf(const GenConsts& c, const GenBatch& b, int n, bool aligned, hipStream_t s) {
+  const uint32_t total = ((c.map_w + 1u) >> 1) * c.map_h;
+  if (total == 0 || n == 0) return hipSuccess;
+  const bool small = generate_is_small(c, n);   // spans per block as launch_generate_t chooses them
+  const unsigned per = (unsigned)kGenBlock * (small ? 1u : (unsigned)kGenTiles);
+  const dim3 g((unsigned)n, (total + per - 1u) / per, 1), blk(kGenBlock, 1, 1);
+  if (small) {
+    if (aligned) hipLaunchKernelGGL((k_generate_gains<TF, true, 1>), g, blk, 0, s, c, b);
+    else hipLaunchKernelGGL((k_generate_gains<TF, false, 1>), g, blk, 0, s, c, b);
+  } else {
+    if (aligned) hipLaunchKernelGGL((k_generate_gains<TF, true, kGenTiles>), g, blk, 0, s, c, b);
+    else hipLaunchKernelGGL((k_generate_gains<TF, false, kGenTiles>), g, blk, 0, s, c, b);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_generate_gains(const GenConsts& c, const GenBatch& b, int n, int hdr_tf, bool aligned, hipStream_t s) {
+  if (c.stat_keys == nullptr) return hipErrorInvalidValue;
+  switch (hdr_tf) {
+    case 0: return launch_generate_gains_tf<0>(c, b, n, aligned, s);
+    case 1: return launch_generate_gains_tf<1>(c, b, n, aligned, s);
+    case 2: return launch_generate_gains_tf<2>(c, b, n, aligned, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// The range rule (include/uhdr_hip.h, uhdr_hip_adaptive_boost_range: the same f32 operations) and, from the range, what
+// generate_consts / encode_constants derive on the host for a fixed one: the two logarithms as (float)log2((double)boost), the
+// scale of encode_gain_guarded's in-range path and the bytes encodeGain yields for a gain on either clamp.  One block: image i is
+// thread i's (strided).  per_call: every image gets the range of the pooled extremes -- the keys are ~key(min) and key(max), so
+// pooling is a maximum of both words -- joined with carry_in's; the pooled pair goes to carry_out.
+__global__ void __launch_bounds__(256) k_adaptive_consts(const uint32_t* keys, int n, int per_call, float cap, AdaptConsts* consts,
+                                                         float* content_minmax, float* boost_range, const uint32_t* carry_in,
+                                                         uint32_t* carry_out) {
+  __shared__ uint32_t s_k[2];
+  if (threadIdx.x < 2u) s_k[threadIdx.x] = (per_call && carry_in != nullptr) ? carry_in[threadIdx.x] : 0u;
+  __syncthreads();
+  if (per_call) {
+    uint32_t k0 = 0u, k1 = 0u;
+    for (int i = (int)threadIdx.x; i < n; i += 256) { k0 = max(k0, keys[2 * i]); k1 = max(k1, keys[2 * i + 1]); }
+    if (k1 != 0u) { atomicMax(&s_k[0], k0); atomicMax(&s_k[1], k1); }
+    __syncthreads();
+    if (carry_out != nullptr && threadIdx.x < 2u) carry_out[threadIdx.x] = s_k[threadIdx.x];
+  }
+  for (int i = (int)threadIdx.x; i < n; i += 256) {
+    uint32_t k0 = keys[2 * i], k1 = keys[2 * i + 1];
+    if (content_minmax != nullptr) {   // the image's own extremes in either scope (an image without map pixels: +inf, -inf)
+      content_minmax[2 * i] = k1 != 0u ? key_to_float(~k0) : __builtin_inff();
+      content_minmax[2 * i + 1] = k1 != 0u ? key_to_float(k1) : -__builtin_inff();
+    }
+    if (per_call) { k0 = s_k[0]; k1 = s_k[1]; }
+    const float g_min = k1 != 0u ? key_to_float(~k0) : __builtin_inff(), g_max = k1 != 0u ? key_to_float(k1) : -__builtin_inff();
+    AdaptConsts a;
+    a.min_boost = fminf(fmaxf(g_min, 0.25f), 1.0f);
+    a.max_boost = fminf(fmaxf(g_max, 1.0625f), cap);
+    a.log2_min = log2_to_float(a.min_boost);
+    a.log2_max = log2_to_float(a.max_boost);
+    a.enc_scale = (double)255.0f / (double)(a.log2_max - a.log2_min);
+    a.enc_byte_min = encode_gain(a.min_boost, a.min_boost, a.max_boost, a.log2_min, a.log2_max);
+    a.enc_byte_max = encode_gain(a.max_boost, a.min_boost, a.max_boost, a.log2_min, a.log2_max);
+    consts[i] = a;
+    boost_range[2 * i] = a.min_boost;
+    boost_range[2 * i + 1] = a.max_boost;
+  }
+}
+hipError_t launch_adaptive_consts(const uint32_t* keys, int n, int per_call, float cap, AdaptConsts* consts, float* content_minmax,
+                                  float* boost_range, const uint32_t* carry_in, uint32_t* carry_out, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_adaptive_consts, dim3(1), dim3(256), 0, s, keys, n, per_call, cap, consts, content_minmax, boost_range, carry_in,
+                     carry_out);
+  return hipGetLastError();
+}
+
+// Pass 2: the reference's three-argument encodeGain on the stored gains with the image's constants from device memory
+// (encode_gain_guarded: the clamp bytes, the lean f64 log2 and its distance-to-integer test, the exact path behind it).  A thread
+// takes four consecutive map pixels: one 16-byte load, one 4-byte store where the map allows it.
+__global__ void __launch_bounds__(256) k_encode_gains(const AdaptConsts* consts, const EncGainBatch b, uint32_t pixels) {
+  const EncGainImage& im = b.img[blockIdx.y];
+  const uint32_t p = (blockIdx.x * 256u + threadIdx.x) * 4u;
+  if (p >= pixels) return;
+  const AdaptConsts a = consts[blockIdx.y];
+  const uint32_t cnt = min(4u, pixels - p);
+  float g[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+  if (cnt == 4u) {
+    const float4 v = *reinterpret_cast<const float4*>(im.gains + p);
+    g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w;
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; ++k) if (k < cnt) g[k] = im.gains[p + k];
+  }
+  uint32_t o[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    o[k] = encode_gain_guarded(g[k], a.min_boost, a.max_boost, a.log2_min, a.log2_max, a.enc_scale, a.enc_byte_min, a.enc_byte_max);
+  uint8_t* mp = im.map + p;
+  if (cnt == 4u && (reinterpret_cast<uintptr_t>(mp) & 3u) == 0u) {
+    *reinterpret_cast<uint32_t*>(mp) = o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24);
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) if (k < cnt) mp[k] = (uint8_t)o[k];
+  }
+}
+hipError_t launch_encode_gains(const AdaptConsts* consts, const EncGainBatch& b, int n, uint32_t pixels, hipStream_t s) {
+  if (n <= 0 || pixels == 0u) return hipSuccess;
+  hipLaunchKernelGGL(k_encode_gains, dim3((pixels + 1023u) / 1024u, (unsigned)n), dim3(256), 0, s, consts, b, pixels);
+  return hipGetLastError();
+}
+
+// =================================================================================================
 // apply
 // =================================================================================================
 
@@ -3066,6 +3226,7 @@ __global__ void __launch_bounds__(256) k_eval_transfer(int fn, const float* in, 
       const float2 t = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(ec.lut + (fn == 51 ? kTabS2Hlg : kTabS2Pq)) + (s2_address(s, 0u) >> 5));
       const double v = -(((double)t.y * (double)s + (double)t.x) + 2.0) * 4194304.0;
       y = (float)(long long)v + (v < 0.0 ? -1000.0f : 0.0f); break; }   // (a negative sum would leave the binade: flagged)
+    case 60: y = log2_to_float(x); break;   // the log2 constant the content-adaptive path derives on the device for boost x
     case 30: y = map_to_float_fast((uint32_t)x); break;
     case 31: y = map_to_float((uint32_t)x); break;
     // 1.0 where the lean f64 path was accepted by the rounding test, 0.0 where the exact path ran

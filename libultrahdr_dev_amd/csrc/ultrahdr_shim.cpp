@@ -65,6 +65,18 @@ status_t UltraHdrHip::ensureInit() {
 status_t UltraHdrHip::generateGainMap(uhdr_uncompressed_ptr yuv420_image_ptr, uhdr_uncompressed_ptr p010_image_ptr,
                                       ultrahdr_transfer_function hdr_tf, ultrahdr_metadata_ptr metadata,
                                       uhdr_uncompressed_ptr dest, bool sdr_is_601) {
+  return generateImpl(yuv420_image_ptr, p010_image_ptr, hdr_tf, metadata, dest, sdr_is_601, false);
+}
+
+status_t UltraHdrHip::generateGainMapAdaptive(uhdr_uncompressed_ptr yuv420_image_ptr, uhdr_uncompressed_ptr p010_image_ptr,
+                                              ultrahdr_transfer_function hdr_tf, ultrahdr_metadata_ptr metadata,
+                                              uhdr_uncompressed_ptr dest, bool sdr_is_601) {
+  return generateImpl(yuv420_image_ptr, p010_image_ptr, hdr_tf, metadata, dest, sdr_is_601, true);
+}
+
+status_t UltraHdrHip::generateImpl(uhdr_uncompressed_ptr yuv420_image_ptr, uhdr_uncompressed_ptr p010_image_ptr,
+                                   ultrahdr_transfer_function hdr_tf, ultrahdr_metadata_ptr metadata,
+                                   uhdr_uncompressed_ptr dest, bool sdr_is_601, bool adaptive) {
   // pointer checks first, exactly as ultrahdr.cpp:189-194, so a null argument never reaches the device
   if (yuv420_image_ptr == nullptr || p010_image_ptr == nullptr || metadata == nullptr || dest == nullptr ||
       yuv420_image_ptr->data == nullptr || yuv420_image_ptr->chroma_data == nullptr ||
@@ -86,8 +98,10 @@ status_t UltraHdrHip::generateGainMap(uhdr_uncompressed_ptr yuv420_image_ptr, uh
   d.data = map_data.get();
   uhdr_hip_metadata_t md;
   std::memset(&md, 0, sizeof(md));
-  const int rc = uhdr_hip_generate_gainmap_ex(&y, &p, static_cast<int>(hdr_tf), &md, &d, sdr_is_601 ? 1 : 0,
-                                              mGenerateMode, UHDR_HIP_MEM_HOST, nullptr);
+  const int rc = adaptive ? uhdr_hip_generate_gainmap_adaptive(&y, &p, static_cast<int>(hdr_tf), &md, &d, sdr_is_601 ? 1 : 0,
+                                                               UHDR_HIP_MEM_HOST, nullptr)
+                          : uhdr_hip_generate_gainmap_ex(&y, &p, static_cast<int>(hdr_tf), &md, &d, sdr_is_601 ? 1 : 0,
+                                                         mGenerateMode, UHDR_HIP_MEM_HOST, nullptr);
   if (rc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(rc);
   metadata->version = md.version;
   metadata->maxContentBoost = md.maxContentBoost;
@@ -274,12 +288,26 @@ status_t encode_into(uhdr_compressed_ptr dest, Fn&& call) {
 const void* exif_ptr(uhdr_exif_ptr e) { return e ? e->data : nullptr; }
 // "exif != nullptr && exif->data == nullptr -> BAD_PTR" (jpegr.cpp:190-193) travels as (NULL, nonzero size)
 size_t exif_len(uhdr_exif_ptr e) { return e ? (e->data ? e->length : 1) : 0; }
+// one file through uhdr_hip_jpegr_encode_adaptive_batch (setContentBoost): the single calls' status is the file's
+int adaptive_one(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, int hdr_tf, int quality, uhdr_exif_ptr exif, void* out, size_t cap,
+                 size_t* n, int scope) {
+  uhdr_hip_image_t none;
+  std::memset(&none, 0, sizeof(none));   // (a NULL image travels as one without data: BAD_PTR, the single call's first check)
+  const void* ex = exif_ptr(exif);
+  const size_t exn = exif_len(exif);
+  return uhdr_hip_jpegr_encode_adaptive_batch(1, p010 ? p010 : &none, yuv, hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, nullptr, scope,
+                                              UHDR_HIP_MEM_HOST, nullptr);
+}
 }  // namespace
 
 status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, ultrahdr_transfer_function hdr_tf, uhdr_compressed_ptr dest, int quality,
                                uhdr_exif_ptr exif) {
   uhdr_hip_image_t p;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
+  if (mContentBoost >= 0)
+    return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
+      return adaptive_one(p010_image_ptr ? &p : nullptr, nullptr, (int)hdr_tf, quality, exif, out, cap, n, mContentBoost);
+    });
   return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
     return uhdr_hip_jpegr_encode_api0(p010_image_ptr ? &p : nullptr, (int)hdr_tf, quality, exif_ptr(exif), exif_len(exif), out, cap, n, UHDR_HIP_MEM_HOST, nullptr);
   });
@@ -290,6 +318,12 @@ status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, uhdr_uncomp
   uhdr_hip_image_t p, y;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
   if (yuv420_image_ptr) y = to_c(*yuv420_image_ptr);
+  if (mContentBoost >= 0) {
+    if (yuv420_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;   // jpegr.cpp:253-256 (a NULL array would mean API-0 to the batch)
+    return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
+      return adaptive_one(p010_image_ptr ? &p : nullptr, &y, (int)hdr_tf, quality, exif, out, cap, n, mContentBoost);
+    });
+  }
   return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
     return uhdr_hip_jpegr_encode_api1(p010_image_ptr ? &p : nullptr, yuv420_image_ptr ? &y : nullptr, (int)hdr_tf, quality, exif_ptr(exif), exif_len(exif), out,
                                       cap, n, UHDR_HIP_MEM_HOST, nullptr);
