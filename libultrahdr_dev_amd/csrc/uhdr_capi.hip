@@ -10,7 +10,6 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
-#include <chrono>
 #include <mutex>
 #include <thread>
 #include <tuple>
@@ -44,7 +43,7 @@ void set_err(const char* where, hipError_t e) {
 // grow-only device staging buffers of one UHDR_HIP_MEM_HOST call.  The four pixel-path entry points (generate, apply, toneMap,
 // convertYuv) lease a set of their own for the duration of a call, so host callers on different streams overlap their copies and
 // kernels; the codec entry points lease a whole context (CodecLease).
-constexpr int kStageSlots = 12;
+constexpr int kStageSlots = 8;
 struct StageSet {
   void* stage[kStageSlots] = {};
   size_t stage_bytes[kStageSlots] = {};
@@ -682,6 +681,62 @@ class CodecLease {
   DeviceState* ctx_ = nullptr;
 };
 
+// ---- what every batched codec call shares ------------------------------------------------------------------------------------------
+// runs fn(lo, hi) over [0, n) on up to 8 host threads
+template <class F>
+void on_host_threads(int n, F fn) {
+  const int nthreads = n >= 2 ? std::min(n, 8) : 1;
+  if (nthreads <= 1) { fn(0, n); return; }
+  std::vector<std::thread> workers;
+  for (int t = 0; t < nthreads; ++t) workers.emplace_back(fn, (int)((long)n * t / nthreads), (int)((long)n * (t + 1) / nthreads));
+  for (auto& w : workers) w.join();
+}
+
+// the end of a batched call: every file's status into the caller's array (if it gave one), the first error as the call's own
+int finish_statuses(const std::vector<int>& st_, int* status) {
+  int first = UHDR_HIP_NO_ERROR;
+  for (size_t i = 0; i < st_.size(); ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
+  return first;
+}
+
+// a single JPEG call's mem_space as the batches read it: every value other than UHDR_HIP_MEM_DEVICE means host memory (the batches give
+// UHDR_HIP_MEM_DEVICE_TO_HOST and UHDR_HIP_MEM_HOST_TO_DEVICE their split meaning)
+int single_mem_space(int mem_space) { return mem_space == UHDR_HIP_MEM_DEVICE ? UHDR_HIP_MEM_DEVICE : UHDR_HIP_MEM_HOST; }
+
+// A round's device workspace and page-locked staging are held to kCodecRoundBytes (a file larger than that gets a round of its own)
+constexpr size_t kCodecRoundBytes = size_t(2) << 30;
+
+// The device part of a batched codec call over its `live` files, in their order: a context of the call's own (CodecLease), then greedy
+// rounds of at most `cap` files and kCodecRoundBytes -- bytes_of(k) is what file k holds of its round, the first file of a round is
+// always admitted --, each through run(ctx, s, first, m).  The first non-zero round status ends the call behind a stream
+// synchronisation, so that nothing of the failed round is still writing into the pools, and is returned; files [0, *done) are
+// finished, the others (the failed round's and those behind it) are the caller's to mark.  A round that returns 0 must leave the
+// stream idle -- every round here ends in compress_to_host's or jpeg_decode_round's synchronisation --, since the lease, and with it
+// the pools the round's kernels and copies use, is released without another one.
+template <class B, class R>
+int run_rounds(size_t live, size_t cap, void* stream, B bytes_of, R run, size_t* done) {
+  *done = 0;
+  DeviceState* st = nullptr;
+  int rc = current_state(&st);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  CodecLease lease(st);
+  if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  while (rc == UHDR_HIP_NO_ERROR && *done < live) {
+    size_t r1 = *done, bytes = 0;
+    while (r1 < live && r1 - *done < cap) {
+      const size_t b = bytes_of(r1);
+      if (r1 > *done && bytes + b > kCodecRoundBytes) break;
+      bytes += b;
+      ++r1;
+    }
+    rc = run(st, s, *done, (int)(r1 - *done));
+    if (rc == UHDR_HIP_NO_ERROR) *done = r1;
+  }
+  if (rc != UHDR_HIP_NO_ERROR) (void)hipStreamSynchronize(s);
+  return rc;
+}
+
 // copy `rows` rows of `row_elems` elements of `esz` bytes from a strided host plane into a device
 // plane with pitch dpitch_elems.  Only bytes the reference itself would touch are read.
 int h2d_plane(void* d, size_t dpitch_elems, const void* h, size_t hstride_elems, size_t row_elems, size_t rows,
@@ -1312,9 +1367,6 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
 }
 
 // ---- plain JPEG for n files (uhdr_hip_jpeg_encode_batch, uhdr_hip_jpeg_decode_batch) -----------------------------------------------
-// A round's device workspace and page-locked staging are held to kCodecRoundBytes (a file larger than that gets a round of its own)
-constexpr size_t kCodecRoundBytes = size_t(2) << 30;
-
 // uhdr_hip_jpeg_encode's image as it compresses it: luma_stride defaulted, no chroma stride for a single plane
 uhdr_hip_image_t enc_image(const uhdr_hip_image_t& in) {
   uhdr_hip_image_t img = in;
@@ -1411,21 +1463,17 @@ int jpeg_encode_round(DeviceState* st, hipStream_t s, bool host_in, bool host_ou
       st_[i] = UHDR_HIP_NO_ERROR;
     }
   };
-  const int nthreads = host_out && m >= 2 ? std::min(m, 8) : 1;
-  if (nthreads <= 1) {
-    deliver(0, m);
-  } else {
-    std::vector<std::thread> workers;
-    for (int t = 0; t < nthreads; ++t) workers.emplace_back(deliver, (int)((long)m * t / nthreads), (int)((long)m * (t + 1) / nthreads));
-    for (auto& w : workers) w.join();
-  }
+  if (host_out) on_host_threads(m, deliver);
+  else deliver(0, m);
   return UHDR_HIP_NO_ERROR;
 }
 }  // namespace
 
 extern "C" {
 
-// JpegEncoderHelper::compressImage (jpegencoderhelper.cpp:39-52) on the device
+// JpegEncoderHelper::compressImage (jpegencoderhelper.cpp:39-52) on the device.  The one single call that is not a batch of one: a
+// 4K q95 file into host memory takes 0.49 ms through compress_to_host's page-locked staging and 0.43 ms staged in device memory at its
+// worst-case size and copied down once, as here (profiles/r06_single_calls.txt)
 int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void* icc, size_t icc_size, void* out,
                          size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
   if (image == nullptr || out_size == nullptr || image->data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
@@ -1473,7 +1521,7 @@ int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void*
   return UHDR_HIP_NO_ERROR;
 }
 
-// uhdr_hip_jpeg_encode for n images in one call: every file's status, size and bytes those of the single call; the files of a round
+// uhdr_hip_jpeg_encode for n images in one call: a file that fails the single call's checks is not processed; the files of a round
 // share one jpeg::encode_batch_async launch set and one synchronisation (compress_to_host)
 int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
                                void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream) {
@@ -1482,7 +1530,7 @@ int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int*
     return UHDR_HIP_ERROR_BAD_PTR;
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
   std::vector<int> live;
-  for (int i = 0; i < n; ++i) {   // uhdr_hip_jpeg_encode's checks, in its order; a file that fails them is not processed
+  for (int i = 0; i < n; ++i) {   // the single call's checks, in its order; a file that fails them is not processed
     const uhdr_hip_image_t& im = images[i];
     if (im.data == nullptr || (im.pixelFormat != UHDR_HIP_PIX_FMT_MONOCHROME && im.chroma_data == nullptr) ||
         (out[i] == nullptr && out_capacity[i] != 0))
@@ -1492,38 +1540,19 @@ int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int*
     else
       live.push_back(i);
   }
-  auto result = [&]() {
-    int first = UHDR_HIP_NO_ERROR;
-    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
-    return first;
-  };
-  if (live.empty()) return result();
-  DeviceState* st = nullptr;
-  int rc = current_state(&st);
-  size_t r0 = 0;   // live files [0, r0) are finished
-  if (rc == UHDR_HIP_NO_ERROR) {
-    CodecLease lease(st);
-    st = lease.get();
-    rc = st == nullptr ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool host_in = mem_space == UHDR_HIP_MEM_HOST || mem_space == UHDR_HIP_MEM_HOST_TO_DEVICE;
-    const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE && mem_space != UHDR_HIP_MEM_HOST_TO_DEVICE;
-    while (rc == UHDR_HIP_NO_ERROR && r0 < live.size()) {   // rounds of <= kMaxBatchJobs files and <= kCodecRoundBytes
-      size_t r1 = r0, bytes = 0;
-      while (r1 < live.size() && r1 - r0 < (size_t)jpeg::kMaxBatchJobs) {
-        const size_t b = enc_round_bytes(enc_image(images[live[r1]]), host_in, host_out);
-        if (r1 > r0 && bytes + b > kCodecRoundBytes) break;
-        bytes += b;
-        ++r1;
-      }
-      rc = jpeg_encode_round(st, s, host_in, host_out, images, quality, icc, icc_size, out, out_capacity, out_size, &live[r0], (int)(r1 - r0),
-                             st_.data());
-      if (rc == UHDR_HIP_NO_ERROR) r0 = r1;
-    }
-    if (rc != UHDR_HIP_NO_ERROR) (void)hipStreamSynchronize(s);   // nothing of a failed round may still be writing into the pools
-  }
-  for (size_t k = r0; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
-  return result();
+  if (live.empty()) return finish_statuses(st_, status);
+  const bool host_in = mem_space == UHDR_HIP_MEM_HOST || mem_space == UHDR_HIP_MEM_HOST_TO_DEVICE;
+  const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE && mem_space != UHDR_HIP_MEM_HOST_TO_DEVICE;
+  size_t done = 0;
+  const int rc = run_rounds(
+      live.size(), (size_t)jpeg::kMaxBatchJobs, stream,
+      [&](size_t k) { return enc_round_bytes(enc_image(images[live[k]]), host_in, host_out); },
+      [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
+        return jpeg_encode_round(st, s, host_in, host_out, images, quality, icc, icc_size, out, out_capacity, out_size, &live[r0], m, st_.data());
+      },
+      &done);
+  for (size_t k = done; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
+  return finish_statuses(st_, status);
 }
 
 // Diagnostics (host only, no GPU): the quantised coefficients of a PROGRESSIVE file after all of its scans, as the host-side
@@ -1547,88 +1576,6 @@ int uhdr_hip_jpeg_progressive_coefficients(const void* jpeg, size_t jpeg_size, i
     const int c = info.gray ? 0 : ((b % 6u) < 4u ? 0 : (int)(b % 6u) - 3);
     prev[c] += coef[b * 64u];
     coef[b * 64u] = (int16_t)prev[c];
-  }
-  return UHDR_HIP_NO_ERROR;
-}
-
-// JpegDecoderHelper::decompressImage(..., DECODE_TO_YCBCR) (jpegdecoderhelper.cpp:188-327) on the device
-int uhdr_hip_jpeg_decode(const void* jpeg, size_t jpeg_size, void* out, size_t out_capacity, uhdr_hip_image_t* desc,
-                         int mem_space, void* stream) {
-  if (jpeg == nullptr || desc == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  // INSUFFICIENT_RESOURCE is this call's size-probe answer (out == NULL / capacity too small: the header parsed and *desc is
-  // filled); every status returned before that point leaves *desc zeroed, and a host allocation failure inside the parser
-  // (std::bad_alloc, -3: a progressive file's coefficient array) is reported as UNKNOWN_ERROR so that it cannot be taken for it
-  memset(desc, 0, sizeof(*desc));
-  jpeg::DecInfo info;
-#ifdef UHDR_JD_TIMING
-  const auto T0 = std::chrono::steady_clock::now();
-#endif
-  const int prc = jpeg::parse_header(static_cast<const uint8_t*>(jpeg), jpeg_size, &info);
-#ifdef UHDR_JD_TIMING
-  const auto T1 = std::chrono::steady_clock::now();
-#endif
-  if (prc == -3) return UHDR_HIP_UNKNOWN_ERROR;
-  if (prc == -2) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  if (prc != 0 || info.w <= 0 || info.h <= 0) return UHDR_HIP_UNKNOWN_ERROR;
-  const size_t w = (size_t)info.w, h = (size_t)info.h;
-  if (w > 8192 || h > 8192) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;   // kMaxWidth / kMaxHeight, jpegdecoderhelper.h:42-43
-  const size_t luma = w * h, chroma = luma / 4, need = info.gray ? luma : luma + 2 * chroma;
-  desc->data = out;
-  desc->width = w; desc->height = h;
-  desc->colorGamut = UHDR_HIP_CG_UNSPECIFIED;
-  desc->luma_stride = w;
-  desc->chroma_data = info.gray ? nullptr : static_cast<uint8_t*>(out) + luma;
-  desc->chroma_stride = info.gray ? 0 : w / 2;
-  desc->pixelFormat = info.gray ? UHDR_HIP_PIX_FMT_MONOCHROME : UHDR_HIP_PIX_FMT_YUV420;
-  if (out == nullptr || out_capacity < need) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  DeviceState* st = nullptr;
-  int rc = current_state(&st);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  CodecLease lease(st);
-  if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-
-  jpeg::DecLayout l;
-  const size_t ws_bytes = jpeg::dec_workspace_bytes(info, &l);
-  if ((rc = stage_reserve(st, 7, ws_bytes)) != 0) return rc;
-  uint8_t* ws = static_cast<uint8_t*>(st->stage[7]);
-  HIP_TRY(hipMemcpyAsync(ws + l.src, static_cast<const uint8_t*>(jpeg) + info.scan_offset, info.scan_bytes, hipMemcpyHostToDevice, s));
-#ifdef UHDR_JD_TIMING
-  const auto T2 = std::chrono::steady_clock::now();
-#endif
-  uint8_t* dout = static_cast<uint8_t*>(out);
-  if (mem_space != UHDR_HIP_MEM_DEVICE) {
-    if ((rc = stage_reserve(st, 5, need)) != 0) return rc;
-    dout = static_cast<uint8_t*>(st->stage[5]);
-  }
-  jpeg::DecPlane planes[3];
-  memset(planes, 0, sizeof(planes));
-  auto mk = [](uint8_t* p, size_t pw, size_t ph) {
-    jpeg::DecPlane q;
-    q.p = p; q.w = (int)pw; q.h = (int)ph; q.stride = (int)pw;
-    q.aligned8 = (reinterpret_cast<uintptr_t>(p) % 8 == 0 && pw % 8 == 0) ? 1 : 0;
-    return q;
-  };
-  planes[0] = mk(dout, w, h);
-  if (!info.gray) { planes[1] = mk(dout + luma, w / 2, h / 2); planes[2] = mk(dout + luma + chroma, w / 2, h / 2); }
-  hipError_t herr = hipSuccess;
-  if ((rc = stage_reserve(st, 11, jpeg::dec_batch_scratch_bytes(1, &l))) != 0) return rc;
-  const jpeg::DecInfo* infos[1] = {&info};
-  uint8_t* wss[1] = {ws};
-  jpeg::DecPlane (*pl[1])[3] = {&planes};
-  const int drc = jpeg::decode_device_batch(1, infos, &l, wss, pl, s, static_cast<uint8_t*>(st->stage[11]), &herr, nullptr);
-#ifdef UHDR_JD_TIMING
-  {
-    const auto T3 = std::chrono::steady_clock::now();
-    auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    fprintf(stderr, "[jd] parse %.0f  lock+reserve+src copy %.0f  device %.0f us\n", us(T0, T1), us(T1, T2), us(T2, T3));
-  }
-#endif
-  if (drc > 0) { set_err("uhdr_hip_jpeg_decode", herr); return UHDR_HIP_UNKNOWN_ERROR; }
-  if (drc < 0) { snprintf(t_err, sizeof(t_err), "uhdr_hip_jpeg_decode: corrupt entropy-coded data"); return UHDR_HIP_UNKNOWN_ERROR; }
-  if (mem_space != UHDR_HIP_MEM_DEVICE) {
-    HIP_TRY(hipMemcpyAsync(out, dout, need, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
   }
   return UHDR_HIP_NO_ERROR;
 }
@@ -1709,13 +1656,15 @@ int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bo
   return UHDR_HIP_NO_ERROR;
 }
 
-// The host part of uhdr_hip_jpeg_decode (rgba false) or uhdr_hip_jpeg_decode_rgba (rgba true) for one file: the single call's checks
-// in its order, the header parsed into *info, *desc left as the single call leaves it.  NO_ERROR: the file is decoded on the device
-// into `need` bytes at out.
+// The host part of uhdr_hip_jpeg_decode (rgba false) or uhdr_hip_jpeg_decode_rgba (rgba true) for one file: the checks in their
+// order, the header parsed into *info, *desc filled.  NO_ERROR: the file is decoded on the device into `need` bytes at out.
+// INSUFFICIENT_RESOURCE is the size-probe answer (out == NULL / capacity too small: the header parsed and *desc is filled); every
+// status returned before that point leaves *desc zeroed (the RGBA call: untouched), and a host allocation failure inside the parser
+// (std::bad_alloc, -3: a progressive file's coefficient array) is reported as UNKNOWN_ERROR so that it cannot be taken for it.
 int jpeg_decode_host(const void* jpeg, size_t jpeg_size, bool rgba, void* out, size_t out_capacity, uhdr_hip_image_t* desc,
                      jpeg::DecInfo* info, size_t* need) {
   if (jpeg == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  if (!rgba) memset(desc, 0, sizeof(*desc));   // the RGBA call leaves *desc alone until its header probe has passed
+  if (!rgba) memset(desc, 0, sizeof(*desc));
   const int prc = jpeg::parse_header(static_cast<const uint8_t*>(jpeg), jpeg_size, info);
   if (prc == -3) return UHDR_HIP_UNKNOWN_ERROR;
   if (prc == -2) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
@@ -1748,6 +1697,13 @@ int jpeg_decode_host(const void* jpeg, size_t jpeg_size, bool rgba, void* out, s
 enum : size_t { kDecWs = 0, kDecPlanes, kDecRgba, kDecScratch };
 constexpr int kDecRound = kRgbaChunk;   // files per decode round: their RGBA conversion is one launch
 
+// a packed w x h plane at p for the decoder to write
+jpeg::DecPlane dec_plane(uint8_t* p, size_t w, size_t h) {
+  jpeg::DecPlane q;
+  q.p = p; q.w = (int)w; q.h = (int)h; q.stride = (int)w;
+  q.aligned8 = (reinterpret_cast<uintptr_t>(p) % 8 == 0 && w % 8 == 0) ? 1 : 0;
+  return q;
+}
 size_t dec_ycc_bytes(const jpeg::DecInfo& info) {
   const size_t luma = (size_t)info.w * (size_t)info.h;
   return info.gray ? luma : luma + 2 * (luma / 4);
@@ -1788,12 +1744,6 @@ int jpeg_decode_round(DeviceState* st, hipStream_t s, bool rgba, bool host_out, 
   std::vector<jpeg::DecPlane> planes(3 * (size_t)m);
   std::vector<jpeg::DecPlane (*)[3]> pl((size_t)m);
   std::vector<uint8_t*> ycc((size_t)m);
-  auto mk = [](uint8_t* p, size_t pw, size_t ph) {
-    jpeg::DecPlane q;
-    q.p = p; q.w = (int)pw; q.h = (int)ph; q.stride = (int)pw;
-    q.aligned8 = (reinterpret_cast<uintptr_t>(p) % 8 == 0 && pw % 8 == 0) ? 1 : 0;
-    return q;
-  };
   for (int k = 0; k < m; ++k) {
     const int i = idx[k];
     const jpeg::DecInfo& in = info[i];
@@ -1806,15 +1756,15 @@ int jpeg_decode_round(DeviceState* st, hipStream_t s, bool rgba, bool host_out, 
     ycc[k] = rgba || host_out ? static_cast<uint8_t*>(st->pool[kDecPlanes]) + pl_off[k] : static_cast<uint8_t*>(out[i]);
     jpeg::DecPlane* p = &planes[3 * (size_t)k];
     memset(p, 0, 3 * sizeof(jpeg::DecPlane));
-    p[0] = mk(ycc[k], w, h);
-    if (!in.gray) { p[1] = mk(ycc[k] + luma, w / 2, h / 2); p[2] = mk(ycc[k] + luma + chroma, w / 2, h / 2); }
+    p[0] = dec_plane(ycc[k], w, h);
+    if (!in.gray) { p[1] = dec_plane(ycc[k] + luma, w / 2, h / 2); p[2] = dec_plane(ycc[k] + luma + chroma, w / 2, h / 2); }
     pl[k] = reinterpret_cast<jpeg::DecPlane (*)[3]>(p);
   }
   std::vector<int> image_rc((size_t)m, 0);
   hipError_t herr = hipSuccess;
   const int drc = jpeg::decode_device_batch(m, infos.data(), lay.data(), wss.data(), pl.data(), s, static_cast<uint8_t*>(st->pool[kDecScratch]), &herr,
                                             image_rc.data());
-  if (drc > 0) { set_err("uhdr_hip_jpeg_decode_batch", herr); return UHDR_HIP_UNKNOWN_ERROR; }
+  if (drc > 0) { set_err("uhdr_hip_jpeg_decode", herr); return UHDR_HIP_UNKNOWN_ERROR; }
   YccRgbaBatch b;
   int nb = 0;
   std::vector<uint8_t*> res((size_t)m, nullptr);   // where each good file's output lies on the device
@@ -1822,7 +1772,7 @@ int jpeg_decode_round(DeviceState* st, hipStream_t s, bool rgba, bool host_out, 
     const int i = idx[k];
     if (image_rc[k] != 0) {
       st_[i] = UHDR_HIP_UNKNOWN_ERROR;
-      snprintf(t_err, sizeof(t_err), "uhdr_hip_jpeg_decode_batch: corrupt entropy-coded data");
+      snprintf(t_err, sizeof(t_err), "uhdr_hip_jpeg_decode: corrupt entropy-coded data");
       continue;
     }
     res[k] = ycc[k];
@@ -1845,42 +1795,8 @@ int jpeg_decode_round(DeviceState* st, hipStream_t s, bool rgba, bool host_out, 
 
 extern "C" {
 
-// JpegDecoderHelper::decompressImage(..., DECODE_TO_RGBA) (jpegdecoderhelper.cpp:251-281): a 4:2:0 JPEG -> RGBA8888
-int uhdr_hip_jpeg_decode_rgba(const void* jpeg, size_t jpeg_size, void* out, size_t out_capacity, uhdr_hip_image_t* desc, int mem_space, void* stream) {
-  if (jpeg == nullptr || desc == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  uhdr_hip_image_t planes;
-  memset(&planes, 0, sizeof(planes));
-  int rc = uhdr_hip_jpeg_decode(jpeg, jpeg_size, nullptr, 0, &planes, UHDR_HIP_MEM_DEVICE, stream);   // header probe
-  if (rc != UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE) return rc;
-  if (planes.width == 0 || planes.height == 0) return UHDR_HIP_UNKNOWN_ERROR;                        // (a probe answer always carries the size)
-  if (planes.pixelFormat != UHDR_HIP_PIX_FMT_YUV420) return UHDR_HIP_UNKNOWN_ERROR;                    // :258-270: YCbCr 4:2:0 only
-  const size_t w = planes.width, h = planes.height, need = w * h * 4;
-  memset(desc, 0, sizeof(*desc));
-  desc->data = out; desc->width = w; desc->height = h; desc->colorGamut = UHDR_HIP_CG_UNSPECIFIED; desc->luma_stride = w;
-  desc->pixelFormat = UHDR_HIP_PIX_FMT_UNSPECIFIED;
-  if (out == nullptr || out_capacity < need) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  if ((w | h) & 1) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  DeviceState* st = nullptr;
-  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  CodecLease lease(st);
-  if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
-  const size_t ybytes = w * h + 2 * (w * h / 4);
-  if ((rc = stage_reserve(st, 8, ybytes + 64)) != 0) return rc;
-  if (host && (rc = stage_reserve(st, 10, need)) != 0) return rc;
-  if ((rc = uhdr_hip_jpeg_decode(jpeg, jpeg_size, st->stage[8], ybytes, &planes, UHDR_HIP_MEM_DEVICE, stream)) != UHDR_HIP_NO_ERROR) return rc;
-  const uint8_t* yp = static_cast<const uint8_t*>(st->stage[8]);
-  uint8_t* dst = static_cast<uint8_t*>(host ? st->stage[10] : out);
-  HIP_TRY(launch_ycc420_to_rgba(yp, yp + w * h, yp + w * h + (w / 2) * (h / 2), (uint32_t)w, (uint32_t)h, (uint32_t)w, (uint32_t)(w / 2), dst, s));
-  if (host) HIP_TRY(hipMemcpyAsync(out, dst, need, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  return UHDR_HIP_NO_ERROR;
-}
-
-// uhdr_hip_jpeg_decode (YCBCR) or uhdr_hip_jpeg_decode_rgba (RGBA) for n files in one call: every file's status, bytes and
-// descriptor those of the single call; the headers are parsed by a few host threads, the files of a round share every decoder
-// launch (jpeg::decode_device_batch) and one RGBA conversion launch
+// uhdr_hip_jpeg_decode (YCBCR) or uhdr_hip_jpeg_decode_rgba (RGBA) for n files in one call: the headers are parsed by a few host
+// threads, the files of a round share every decoder launch (jpeg::decode_device_batch) and one RGBA conversion launch
 int uhdr_hip_jpeg_decode_batch(int n, const void* const* jpeg, const size_t* jpeg_size, int decode_to, void* const* out, const size_t* out_capacity,
                                uhdr_hip_image_t* descs, int* status, int mem_space, void* stream) {
   if (n < 0 || (n > 0 && (jpeg == nullptr || jpeg_size == nullptr || descs == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
@@ -1889,60 +1805,44 @@ int uhdr_hip_jpeg_decode_batch(int n, const void* const* jpeg, const size_t* jpe
   std::vector<jpeg::DecInfo> info((size_t)n);
   std::vector<size_t> need((size_t)n, 0);
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
-  {
-    auto parse_range = [&](int lo, int hi) {
-      for (int i = lo; i < hi; ++i) {
-        void* o = out != nullptr ? out[i] : nullptr;
-        const size_t cap = out != nullptr && out_capacity != nullptr ? out_capacity[i] : 0;
-        try {
-          st_[i] = jpeg_decode_host(jpeg[i], jpeg_size[i], rgba, o, cap, &descs[i], &info[i], &need[i]);
-        } catch (const std::bad_alloc&) {
-          st_[i] = UHDR_HIP_UNKNOWN_ERROR;
-        }
+  on_host_threads(n, [&](int lo, int hi) {
+    for (int i = lo; i < hi; ++i) {
+      void* o = out != nullptr ? out[i] : nullptr;
+      const size_t cap = out != nullptr && out_capacity != nullptr ? out_capacity[i] : 0;
+      try {
+        st_[i] = jpeg_decode_host(jpeg[i], jpeg_size[i], rgba, o, cap, &descs[i], &info[i], &need[i]);
+      } catch (const std::bad_alloc&) {
+        st_[i] = UHDR_HIP_UNKNOWN_ERROR;
       }
-    };
-    const int nthreads = n >= 2 ? std::min(n, 8) : 1;
-    if (nthreads <= 1) {
-      parse_range(0, n);
-    } else {
-      std::vector<std::thread> workers;
-      for (int t = 0; t < nthreads; ++t) workers.emplace_back(parse_range, (int)((long)n * t / nthreads), (int)((long)n * (t + 1) / nthreads));
-      for (auto& w : workers) w.join();
     }
-  }
+  });
   std::vector<int> live;
   for (int i = 0; i < n; ++i)
     if (st_[i] == UHDR_HIP_NO_ERROR) live.push_back(i);
-  auto result = [&]() {
-    int first = UHDR_HIP_NO_ERROR;
-    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
-    return first;
-  };
-  if (live.empty()) return result();   // every file stopped at its checks or its size probe: the device is not touched
-  DeviceState* st = nullptr;
-  int rc = current_state(&st);
-  size_t r0 = 0;   // live files [0, r0) are finished
-  if (rc == UHDR_HIP_NO_ERROR) {
-    CodecLease lease(st);
-    st = lease.get();
-    rc = st == nullptr ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE;
-    while (rc == UHDR_HIP_NO_ERROR && r0 < live.size()) {   // rounds of <= kDecRound files and <= kCodecRoundBytes
-      size_t r1 = r0, bytes = 0;
-      while (r1 < live.size() && r1 - r0 < (size_t)kDecRound) {
-        const size_t b = dec_round_bytes(info[live[r1]], rgba, host_out, need[live[r1]]);
-        if (r1 > r0 && bytes + b > kCodecRoundBytes) break;
-        bytes += b;
-        ++r1;
-      }
-      rc = jpeg_decode_round(st, s, rgba, host_out, jpeg, out, info.data(), need.data(), &live[r0], (int)(r1 - r0), st_.data());
-      if (rc == UHDR_HIP_NO_ERROR) r0 = r1;
-    }
-    if (rc != UHDR_HIP_NO_ERROR) (void)hipStreamSynchronize(s);   // nothing of a failed round may still be writing into the pools
-  }
-  for (size_t k = r0; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
-  return result();
+  if (live.empty()) return finish_statuses(st_, status);   // every file stopped at its checks or its size probe: the device is not touched
+  const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE;
+  size_t done = 0;
+  const int rc = run_rounds(
+      live.size(), (size_t)kDecRound, stream, [&](size_t k) { return dec_round_bytes(info[live[k]], rgba, host_out, need[live[k]]); },
+      [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
+        return jpeg_decode_round(st, s, rgba, host_out, jpeg, out, info.data(), need.data(), &live[r0], m, st_.data());
+      },
+      &done);
+  for (size_t k = done; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
+  return finish_statuses(st_, status);
+}
+
+// JpegDecoderHelper::decompressImage(..., DECODE_TO_YCBCR) (jpegdecoderhelper.cpp:188-327) on the device: a batch of one file
+int uhdr_hip_jpeg_decode(const void* jpeg, size_t jpeg_size, void* out, size_t out_capacity, uhdr_hip_image_t* desc,
+                         int mem_space, void* stream) {
+  if (jpeg == nullptr || desc == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  return uhdr_hip_jpeg_decode_batch(1, &jpeg, &jpeg_size, UHDR_HIP_DECODE_TO_YCBCR, &out, &out_capacity, desc, nullptr, single_mem_space(mem_space), stream);
+}
+
+// JpegDecoderHelper::decompressImage(..., DECODE_TO_RGBA) (jpegdecoderhelper.cpp:251-281), a 4:2:0 JPEG -> RGBA8888: a batch of one file
+int uhdr_hip_jpeg_decode_rgba(const void* jpeg, size_t jpeg_size, void* out, size_t out_capacity, uhdr_hip_image_t* desc, int mem_space, void* stream) {
+  if (jpeg == nullptr || desc == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  return uhdr_hip_jpeg_decode_batch(1, &jpeg, &jpeg_size, UHDR_HIP_DECODE_TO_RGBA, &out, &out_capacity, desc, nullptr, single_mem_space(mem_space), stream);
 }
 
 // JpegR::decodeJPEGR (jpegr.cpp:655-822) for n files at once.  A JPEG decode on the device is latency-bound (tens of synchronisation
@@ -1958,22 +1858,12 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
   std::vector<size_t> out_bytes((size_t)n, 0);
   int live = 0;
-  {
-    // walking a 2 MB file's markers (memchr over the entropy-coded data, twice: container split and scan length) costs ~0.2 ms of
-    // host time per file and touches nothing shared: the files of a batch are parsed by a few threads side by side
-    auto parse_range = [&](int lo, int hi) {
-      for (int i = lo; i < hi; ++i)
-        st_[i] = jpegr[i] == nullptr ? UHDR_HIP_ERROR_BAD_PTR : parse_jpegr_file(jpegr[i], jpegr_size[i], output_format, metadata != nullptr, &files[i]);
-    };
-    const int nthreads = n >= 2 ? std::min(n, 8) : 1;
-    if (nthreads <= 1) {
-      parse_range(0, n);
-    } else {
-      std::vector<std::thread> workers;
-      for (int t = 0; t < nthreads; ++t) workers.emplace_back(parse_range, (int)((long)n * t / nthreads), (int)((long)n * (t + 1) / nthreads));
-      for (auto& w : workers) w.join();
-    }
-  }
+  // walking a 2 MB file's markers (memchr over the entropy-coded data, twice: container split and scan length) costs ~0.2 ms of
+  // host time per file and touches nothing shared: the files of a batch are parsed by a few threads side by side
+  on_host_threads(n, [&](int lo, int hi) {
+    for (int i = lo; i < hi; ++i)
+      st_[i] = jpegr[i] == nullptr ? UHDR_HIP_ERROR_BAD_PTR : parse_jpegr_file(jpegr[i], jpegr_size[i], output_format, metadata != nullptr, &files[i]);
+  });
   for (int i = 0; i < n; ++i) {
     if (st_[i] != UHDR_HIP_NO_ERROR) continue;
     if (metadata != nullptr) metadata[i] = files[i].md;
@@ -1982,12 +1872,7 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
     if (dest_data == nullptr || dest_capacity == nullptr || dest_data[i] == nullptr || dest_capacity[i] < out_bytes[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
     ++live;
   }
-  auto result = [&]() {
-    int first = UHDR_HIP_NO_ERROR;
-    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
-    return first;
-  };
-  if (live == 0) return result();
+  if (live == 0) return finish_statuses(st_, status);
 
   DeviceState* st = nullptr;
   int rc;
@@ -2006,12 +1891,6 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
   const bool sdr = output_format == UHDR_HIP_OUTPUT_SDR;
   const int per_file = sdr ? 1 : 2;          // the SDR rendition is the primary image alone (:768-786)
   infos.reserve(2 * live); layouts.reserve(2 * live); wss.reserve(2 * live); planes.reserve(6 * live);
-  auto mk = [](uint8_t* p, size_t pw, size_t ph) {
-    jpeg::DecPlane q;
-    q.p = p; q.w = (int)pw; q.h = (int)ph; q.stride = (int)pw;
-    q.aligned8 = (reinterpret_cast<uintptr_t>(p) % 8 == 0 && pw % 8 == 0) ? 1 : 0;
-    return q;
-  };
   for (int i = 0; i < n; ++i) {
     if (st_[i] != UHDR_HIP_NO_ERROR) continue;
     const JpegrFile& f = files[i];
@@ -2025,9 +1904,9 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
       uint8_t* out = static_cast<uint8_t*>(st->pool[5 * (size_t)i + 2 + k]);
       infos.push_back(&f.info[k]); layouts.push_back(l); wss.push_back(ws); owner.push_back(i);
       srcs.push_back(f.jpg[k] + f.info[k].scan_offset);
-      planes.push_back(mk(out, w, h));
-      planes.push_back(f.info[k].gray ? jpeg::DecPlane{} : mk(out + luma, w / 2, h / 2));
-      planes.push_back(f.info[k].gray ? jpeg::DecPlane{} : mk(out + luma + chroma, w / 2, h / 2));
+      planes.push_back(dec_plane(out, w, h));
+      planes.push_back(f.info[k].gray ? jpeg::DecPlane{} : dec_plane(out + luma, w / 2, h / 2));
+      planes.push_back(f.info[k].gray ? jpeg::DecPlane{} : dec_plane(out + luma + chroma, w / 2, h / 2));
     }
     if (host && (rc = pool_reserve(st, 5 * (size_t)i + 4, out_bytes[i])) != 0) return rc;
   }
@@ -2047,18 +1926,30 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
   for (int k = 0; k < nimg; ++k)
     if (image_rc[k] != 0) st_[owner[k]] = UHDR_HIP_ERROR_DECODE_ERROR;
 
+  // the SDR rendition: the conversions of up to kRgbaChunk files share a launch, a host caller's copies follow it
+  YccRgbaBatch rgb;
+  int rgb_file[kRgbaChunk], nrgb = 0;
+  auto convert = [&]() {
+    HIP_TRY(launch_ycc420_to_rgba_batch(rgb, nrgb, s));
+    for (int k = 0; host && k < nrgb; ++k)
+      HIP_TRY(hipMemcpyAsync(dest_data[rgb_file[k]], rgb.img[k].rgba, out_bytes[rgb_file[k]], hipMemcpyDeviceToHost, s));
+    nrgb = 0;
+    return UHDR_HIP_NO_ERROR;
+  };
   // :796-801: the decoded planes as a YUV420 image with the ICC gamut; the gain map is the first plane of its JPEG
   for (int i = 0; i < n; ++i) {
     if (st_[i] != UHDR_HIP_NO_ERROR) continue;
     const JpegrFile& f = files[i];
-    if (sdr) {   // libjpeg-turbo's DECODE_TO_RGBA on the planes just decoded (k_ycc420_rgba)
-      const size_t w = (size_t)f.info[0].w, h = (size_t)f.info[0].h;
+    if (sdr) {   // libjpeg-turbo's DECODE_TO_RGBA on the planes just decoded (k_ycc420_rgba_batch)
+      const uint32_t w = (uint32_t)f.info[0].w, h = (uint32_t)f.info[0].h;
       if ((w | h) & 1) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }
       const uint8_t* yp = static_cast<const uint8_t*>(st->pool[5 * (size_t)i + 2]);
+      const size_t luma = (size_t)w * h;
       uint8_t* out = static_cast<uint8_t*>(host ? st->pool[5 * (size_t)i + 4] : dest_data[i]);
-      HIP_TRY(launch_ycc420_to_rgba(yp, yp + w * h, yp + w * h + (w / 2) * (h / 2), (uint32_t)w, (uint32_t)h, (uint32_t)w, (uint32_t)(w / 2), out, s));
+      rgb_file[nrgb] = i;
+      rgb.img[nrgb++] = YccRgbaImage{yp, yp + luma, yp + luma + luma / 4, out, w, h, w, w / 2};
+      if (nrgb == kRgbaChunk && (rc = convert()) != UHDR_HIP_NO_ERROR) return rc;
       dests[i].data = dest_data[i];
-      if (host) HIP_TRY(hipMemcpyAsync(dest_data[i], out, out_bytes[i], hipMemcpyDeviceToHost, s));
       continue;
     }
     const size_t w = (size_t)f.info[0].w, h = (size_t)f.info[0].h, gw = (size_t)f.info[1].w, gh = (size_t)f.info[1].h;
@@ -2078,8 +1969,9 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
     dests[i].width = ddev.width; dests[i].height = ddev.height;
     if (host) HIP_TRY(hipMemcpyAsync(dest_data[i], ddev.data, out_bytes[i], hipMemcpyDeviceToHost, s));
   }
+  if ((rc = convert()) != UHDR_HIP_NO_ERROR) return rc;
   HIP_TRY(hipStreamSynchronize(s));
-  return result();
+  return finish_statuses(st_, status);
 }
 
 int uhdr_hip_jpegr_decode(const void* jpegr, size_t jpegr_size, int output_format, float max_display_boost, void* dest_data,
@@ -2196,20 +2088,6 @@ struct EncFile {
 EncJpeg gainmap_jpeg(uhdr_hip_image_t map, size_t pad_ls) {
   map.chroma_data = nullptr; map.chroma_stride = 0; map.pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
   return EncJpeg{map, 85, nullptr, pad_ls, 0};
-}
-
-// generateGainMap followed by compressGainMap on device planes: the block API-2 and API-3 contain (e.g. jpegr.cpp:416-434)
-int make_gainmap_jpeg(DeviceState* st, hipStream_t s, const uhdr_hip_image_t& yuv, const uhdr_hip_image_t& p010, int hdr_tf, int sdr_is_601,
-                      uhdr_hip_metadata_t* md, EncJpeg* gm) {
-  const size_t mw = yuv.width / 4, mh = yuv.height / 4;
-  int rc;
-  if ((rc = stage_reserve(st, 9, mw * mh + 64)) != 0) return rc;
-  uhdr_hip_image_t map = yuv;
-  map.data = st->stage[9];
-  if ((rc = uhdr_hip_generate_gainmap(&yuv, &p010, hdr_tf, md, &map, sdr_is_601, UHDR_HIP_MEM_DEVICE, s)) != UHDR_HIP_NO_ERROR) return rc;
-  map.width = mw; map.height = mh; map.luma_stride = mw;
-  *gm = gainmap_jpeg(map, mw);
-  return compress_to_host(st, s, 1, gm) == UHDR_HIP_NO_ERROR ? UHDR_HIP_NO_ERROR : UHDR_HIP_ERROR_ENCODE_ERROR;
 }
 
 // One round: staging (host callers), toneMap (API-0), generateGainMap, BT.601 re-encode -- one launch per step for the round's
@@ -2359,89 +2237,66 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
     if (!jpegr::icc_profile_srgb_transfer(sdr_gamut, e.icc)) { st_[i] = UHDR_HIP_ERROR_INVALID_COLORGAMUT; continue; }
     files.push_back(std::move(e));
   }
-  auto result = [&]() {
-    int first = UHDR_HIP_NO_ERROR;
-    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
-    return first;
+  if (files.empty()) return finish_statuses(st_, status);
+  // runs of equal size and gamuts, whatever the caller's order: equal files share the launches of toneMap, generate and convertYuv
+  auto key = [&](const EncFile& e) {
+    return std::make_tuple(e.p010.width, e.p010.height, api0 ? e.p010.colorGamut : e.yuv.colorGamut, e.p010.colorGamut);
   };
-  if (files.empty()) return result();
-  DeviceState* st = nullptr;
-  int rc = current_state(&st);
-  if (rc == UHDR_HIP_NO_ERROR) {
-    CodecLease lease(st);
-    st = lease.get();
-    rc = st == nullptr ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    // runs of equal size and gamuts, whatever the caller's order: equal files share the launches of toneMap, generate and convertYuv
-    auto key = [&](const EncFile& e) {
-      return std::make_tuple(e.p010.width, e.p010.height, api0 ? e.p010.colorGamut : e.yuv.colorGamut, e.p010.colorGamut);
-    };
-    std::stable_sort(files.begin(), files.end(), [&](const EncFile& x, const EncFile& y) { return key(x) < key(y); });
-    struct SyncOnExit {   // an error half-way through a round must not leave kernels writing into the pools
-      hipStream_t s;
-      ~SyncOnExit() { (void)hipStreamSynchronize(s); }
-    } sync_on_exit{s};
-    size_t r0 = 0;   // files [0, r0) are finished
-    // PER_CALL over several rounds: the statistic of all rounds first (every round staged and measured, the pooled extremes carried
-    // along in device memory), then the rounds proper, encoded against the carried pair
-    const int carry = boost_scope == UHDR_HIP_BOOST_PER_CALL && files.size() > (size_t)kEncRound ? 2 : 0;
-    if (rc == UHDR_HIP_NO_ERROR && carry != 0) {
-      rc = pool_reserve(st, kEncAdaptCarry, 256);
-      if (rc == UHDR_HIP_NO_ERROR) {
-        const hipError_t e = launch_adaptive_init(static_cast<uint32_t*>(st->pool[kEncAdaptCarry]), 2u, s);
-        if (e != hipSuccess) { set_err("launch_adaptive_init", e); rc = UHDR_HIP_UNKNOWN_ERROR; }
-      }
-      for (size_t q0 = 0; rc == UHDR_HIP_NO_ERROR && q0 < files.size(); q0 += kEncRound) {
-        const int m = (int)std::min(files.size() - q0, (size_t)kEncRound);
-        std::vector<EncFile> probe(files.begin() + (long)q0, files.begin() + (long)q0 + m);   // (a round rewrites its files' descriptors)
-        uhdr_hip_metadata_t md;
-        std::vector<EncJpeg> jpg;
-        rc = encode_round(st, s, api0, mem_space != UHDR_HIP_MEM_DEVICE, hdr_tf, quality, probe.data(), m, &md, &jpg, boost_scope, nullptr, 1);
-      }
-    }
-    std::vector<float> range(2 * (size_t)kEncRound);
-    for (; rc == UHDR_HIP_NO_ERROR && r0 < files.size(); r0 += kEncRound) {
-      const int m = (int)std::min(files.size() - r0, (size_t)kEncRound);
-      EncFile* f = &files[r0];
+  std::stable_sort(files.begin(), files.end(), [&](const EncFile& x, const EncFile& y) { return key(x) < key(y); });
+  const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
+  // PER_CALL over several rounds: the statistic of all rounds first (every round staged and measured, the pooled extremes carried
+  // along in device memory), then the rounds proper, encoded against the carried pair
+  const int carry = boost_scope == UHDR_HIP_BOOST_PER_CALL && files.size() > (size_t)kEncRound ? 2 : 0;
+  auto measure_all = [&](DeviceState* st, hipStream_t s) {
+    int rc = pool_reserve(st, kEncAdaptCarry, 256);
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
+    const hipError_t e = launch_adaptive_init(static_cast<uint32_t*>(st->pool[kEncAdaptCarry]), 2u, s);
+    if (e != hipSuccess) { set_err("launch_adaptive_init", e); return UHDR_HIP_UNKNOWN_ERROR; }
+    for (size_t q0 = 0; rc == UHDR_HIP_NO_ERROR && q0 < files.size(); q0 += kEncRound) {
+      const int m = (int)std::min(files.size() - q0, (size_t)kEncRound);
+      std::vector<EncFile> probe(files.begin() + (long)q0, files.begin() + (long)q0 + m);   // (a round rewrites its files' descriptors)
       uhdr_hip_metadata_t md;
       std::vector<EncJpeg> jpg;
-      rc = encode_round(st, s, api0, mem_space != UHDR_HIP_MEM_DEVICE, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry);
-      if (rc != UHDR_HIP_NO_ERROR) break;
-      std::vector<uhdr_hip_metadata_t> mds;   // adaptive: every file's own
-      if (boost_scope >= 0) {
-        mds.resize((size_t)m);
-        for (int k = 0; k < m; ++k) {
-          fill_adaptive_metadata(range[2 * (size_t)k], range[2 * (size_t)k + 1], &mds[(size_t)k]);
-          if (metadata) metadata[f[k].idx] = mds[(size_t)k];
-        }
-      }
-      // appendGainMap (jpegr.cpp:951-1130) straight into the caller's buffers, a few host threads side by side
-      auto assemble = [&](int lo, int hi) {
-        for (int k = lo; k < hi; ++k) {
-          const EncFile& e = f[k];
-          const int i = e.idx;
-          const EncJpeg& sdr = jpg[2 * (size_t)k];
-          const EncJpeg& gm = jpg[2 * (size_t)k + 1];
-          st_[i] = jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
-                                            nullptr, 0, boost_scope >= 0 ? mds[(size_t)k] : md, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i],
-                                            boost_scope >= 0);
-        }
-      };
-      const int nthreads = m >= 2 ? std::min(m, 8) : 1;
-      if (nthreads <= 1) {
-        assemble(0, m);
-      } else {
-        std::vector<std::thread> workers;
-        for (int t = 0; t < nthreads; ++t) workers.emplace_back(assemble, (int)((long)m * t / nthreads), (int)((long)m * (t + 1) / nthreads));
-        for (auto& w : workers) w.join();
-      }
+      rc = encode_round(st, s, api0, host, hdr_tf, quality, probe.data(), m, &md, &jpg, boost_scope, nullptr, 1);
     }
-    if (rc != UHDR_HIP_NO_ERROR)   // the files of the failed round and of those behind it
-      for (size_t k = r0; k < files.size(); ++k) st_[files[k].idx] = rc;
-    return result();
-  }
-  for (const EncFile& e : files) st_[e.idx] = rc;
-  return result();
+    return rc;
+  };
+  std::vector<float> range(2 * (size_t)kEncRound);
+  size_t done = 0;
+  const int rc = run_rounds(
+      files.size(), (size_t)kEncRound, stream, [](size_t) { return (size_t)0; },   // rounds by count alone
+      [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
+        // the measuring pass needs the leased context, which the driver hands over with a round: it goes in front of the first one
+        int rc = carry != 0 && r0 == 0 ? measure_all(st, s) : UHDR_HIP_NO_ERROR;
+        if (rc != UHDR_HIP_NO_ERROR) return rc;
+        EncFile* f = &files[r0];
+        uhdr_hip_metadata_t md;
+        std::vector<EncJpeg> jpg;
+        if ((rc = encode_round(st, s, api0, host, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry)) != UHDR_HIP_NO_ERROR) return rc;
+        std::vector<uhdr_hip_metadata_t> mds;   // adaptive: every file's own
+        if (boost_scope >= 0) {
+          mds.resize((size_t)m);
+          for (int k = 0; k < m; ++k) {
+            fill_adaptive_metadata(range[2 * (size_t)k], range[2 * (size_t)k + 1], &mds[(size_t)k]);
+            if (metadata) metadata[f[k].idx] = mds[(size_t)k];
+          }
+        }
+        // appendGainMap (jpegr.cpp:951-1130) straight into the caller's buffers, a few host threads side by side
+        on_host_threads(m, [&](int lo, int hi) {
+          for (int k = lo; k < hi; ++k) {
+            const int i = f[k].idx;
+            const EncJpeg& sdr = jpg[2 * (size_t)k];
+            const EncJpeg& gm = jpg[2 * (size_t)k + 1];
+            st_[i] = jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
+                                              nullptr, 0, boost_scope >= 0 ? mds[(size_t)k] : md, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i],
+                                              boost_scope >= 0);
+          }
+        });
+        return UHDR_HIP_NO_ERROR;
+      },
+      &done);
+  for (size_t k = done; k < files.size(); ++k) st_[files[k].idx] = rc;   // the files of the failed round and of those behind it
+  return finish_statuses(st_, status);
 }
 
 // ---- the host-side checks of API-2, API-3, API-4 and API-x, shared by the single calls and the batches ----------------------------
@@ -2575,89 +2430,6 @@ int uhdr_hip_jpegr_encode_api4(const void* sdr_jpeg, size_t sdr_jpeg_size, int s
                                   nullptr, 0, icc.empty() ? nullptr : icc.data(), icc.size(), *metadata, static_cast<uint8_t*>(out), out_capacity, out_size);
 }
 
-// JpegR::encodeJPEGR API-2 (jpegr.cpp:384-437)
-int uhdr_hip_jpegr_encode_api2(const uhdr_hip_image_t* p010_in, const uhdr_hip_image_t* yuv_in, const void* sdr_jpeg, size_t sdr_jpeg_size,
-                               int sdr_jpeg_gamut, int hdr_tf, void* out, size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
-  int rc = api2_check(p010_in, yuv_in, sdr_jpeg, hdr_tf, out, out_size);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
-  uhdr_hip_image_t p010 = *p010_in, yuv = *yuv_in;
-  default_p010(&p010);
-  default_yuv(&yuv);
-  DeviceState* st = nullptr;
-  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
-  CodecLease lease(st);
-  if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  uhdr_hip_image_t dy = yuv, dp = p010;
-  if (mem_space != UHDR_HIP_MEM_DEVICE) {   // the staging of generateGainMap's host path
-    if ((rc = stage_yuv420_in(st, 0, yuv, &dy, s)) != 0) return rc;
-    if ((rc = stage_p010_in(st, 2, p010, &dp, s)) != 0) return rc;
-  }
-  uhdr_hip_metadata_t md;
-  EncJpeg gm;
-  if ((rc = make_gainmap_jpeg(st, s, dy, dp, hdr_tf, 0, &md, &gm)) != UHDR_HIP_NO_ERROR) return rc;                // :416-434
-  return uhdr_hip_jpegr_encode_api4(sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, gm.bytes, gm.n, &md, out, out_capacity, out_size);
-}
-
-// JpegR::encodeJPEGR API-3 (jpegr.cpp:439-500): the SDR rendition arrives as a JPEG only and is decoded on the device
-int uhdr_hip_jpegr_encode_api3(const uhdr_hip_image_t* p010_in, const void* sdr_jpeg, size_t sdr_jpeg_size, int sdr_jpeg_gamut, int hdr_tf,
-                               void* out, size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
-  jpeg::DecInfo info;
-  int rc = api3_check(p010_in, sdr_jpeg, sdr_jpeg_size, hdr_tf, out, out_size, &info);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
-  uhdr_hip_image_t p010 = *p010_in;
-  default_p010(&p010);
-  const uint8_t* pj = static_cast<const uint8_t*>(sdr_jpeg);
-
-  // :457-462 decode
-  DeviceState* st = nullptr;
-  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
-  CodecLease lease(st);
-  if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t w = (size_t)info.w, h = (size_t)info.h, ybytes = w * h + 2 * (w * h / 4);
-  if ((rc = stage_reserve(st, 8, ybytes + 64)) != 0) return rc;
-  uhdr_hip_image_t ydesc;
-  if (uhdr_hip_jpeg_decode(pj, sdr_jpeg_size, st->stage[8], ybytes, &ydesc, UHDR_HIP_MEM_DEVICE, stream) != UHDR_HIP_NO_ERROR)
-    return UHDR_HIP_ERROR_DECODE_ERROR;
-  int gamut = UHDR_HIP_CG_UNSPECIFIED;
-  if ((rc = api3_check_decoded(p010, sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, w, h, &gamut)) != UHDR_HIP_NO_ERROR) return rc;  // :467-499
-  ydesc.colorGamut = gamut;
-  uhdr_hip_image_t dp = p010;
-  if (mem_space != UHDR_HIP_MEM_DEVICE && (rc = stage_p010_in(st, 2, p010, &dp, s)) != 0) return rc;
-  uhdr_hip_metadata_t md;
-  EncJpeg gm;
-  if ((rc = make_gainmap_jpeg(st, s, ydesc, dp, hdr_tf, 1 /* sdr_is_601 */, &md, &gm)) != UHDR_HIP_NO_ERROR) return rc;
-  return uhdr_hip_jpegr_encode_api4(sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, gm.bytes, gm.n, &md, out, out_capacity, out_size);
-}
-
-// JpegR::encodeJPEGR "API-x" (jpegr.cpp:562-631): SDR planes + a ready gain map + its metadata; no BT.601 re-encode on this path
-int uhdr_hip_jpegr_encode_apix(const uhdr_hip_image_t* yuv_in, const uhdr_hip_image_t* gainmap, const uhdr_hip_metadata_t* metadata, int quality,
-                               const void* exif, size_t exif_size, void* out, size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :566-568
-  if (yuv_in == nullptr || yuv_in->data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  if (gainmap == nullptr || gainmap->data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  if (metadata == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  if (out == nullptr || out_size == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  DeviceState* st = nullptr;
-  int rc;
-  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
-  CodecLease lease(st);
-  if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  uhdr_hip_image_t yuv, map;
-  std::vector<uint8_t> icc;
-  if ((rc = apix_check(*yuv_in, *gainmap, &yuv, &map, &icc)) != UHDR_HIP_NO_ERROR) return rc;                     // :590-611
-  EncJpeg jpg[2] = {EncJpeg{yuv, quality, &icc, yuv.luma_stride, yuv.chroma_stride}, gainmap_jpeg(map, map.luma_stride)};
-  if (mem_space != UHDR_HIP_MEM_DEVICE) {   // staged planes, padded by the caller's strides
-    if ((rc = stage_encoder_in(st, 0, yuv, &jpg[0].img, s)) != 0) return rc;
-    if ((rc = stage_encoder_in(st, 2, map, &jpg[1].img, s)) != 0) return rc;
-  }
-  if (compress_to_host(st, s, 2, jpg) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
-  return jpegr::append_gainmap_to(jpg[0].bytes, jpg[0].n, jpg[1].bytes, jpg[1].n, static_cast<const uint8_t*>(exif), exif_size, nullptr, 0, *metadata,
-                                  static_cast<uint8_t*>(out), out_capacity, out_size);
-}
-
 }  // extern "C"
 
 namespace {
@@ -2693,16 +2465,6 @@ size_t sj_round_bytes(const SjFile& e, const jpeg::DecInfo* info, bool host) {
     b += jpeg::dec_workspace_bytes(*info, &l) + round_up(dec_ycc_bytes(*info) + 64, 256);
   }
   return b;
-}
-
-// runs fn(lo, hi) over [0, n) on up to 8 host threads
-template <class F>
-void on_host_threads(int n, F fn) {
-  const int nthreads = n >= 2 ? std::min(n, 8) : 1;
-  if (nthreads <= 1) { fn(0, n); return; }
-  std::vector<std::thread> workers;
-  for (int t = 0; t < nthreads; ++t) workers.emplace_back(fn, (int)((long)n * t / nthreads), (int)((long)n * (t + 1) / nthreads));
-  for (auto& w : workers) w.join();
 }
 
 // One round of API-2 / API-3 files f[0, m): API-3's decode (one jpeg::decode_device_batch through jpeg_decode_round, with its own
@@ -2855,43 +2617,21 @@ int sdr_jpeg_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_im
     }
     files.push_back(std::move(e));
   }
-  auto result = [&]() {
-    int first = UHDR_HIP_NO_ERROR;
-    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
-    return first;
-  };
-  if (files.empty()) return result();   // every file stopped at its checks: the device is not touched
-  DeviceState* st = nullptr;
-  int rc = current_state(&st);
-  size_t r0 = 0;   // files [0, r0) are finished
-  if (rc == UHDR_HIP_NO_ERROR) {
-    CodecLease lease(st);
-    st = lease.get();
-    rc = st == nullptr ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
-    auto key = [](const SjFile& e) { return std::make_tuple(e.p010.width, e.p010.height, e.sdr_gamut, e.p010.colorGamut); };
-    std::stable_sort(files.begin(), files.end(), [&](const SjFile& x, const SjFile& y) { return key(x) < key(y); });
-    struct SyncOnExit {   // an error half-way through a round must not leave kernels writing into the pools
-      hipStream_t s;
-      ~SyncOnExit() { (void)hipStreamSynchronize(s); }
-    } sync_on_exit{s};
-    while (rc == UHDR_HIP_NO_ERROR && r0 < files.size()) {
-      size_t r1 = r0, bytes = 0;
-      while (r1 < files.size() && r1 - r0 < (size_t)kEncRound) {
-        const size_t b = sj_round_bytes(files[r1], api3 ? &info[files[r1].idx] : nullptr, host);
-        if (r1 > r0 && bytes + b > kCodecRoundBytes) break;
-        bytes += b;
-        ++r1;
-      }
-      rc = sdr_jpeg_round(st, s, api3, host, hdr_tf, &files[r0], (int)(r1 - r0), sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, api3 ? info.data() : nullptr,
-                          dec_out.data(), dec_need.data(), out, out_capacity, out_size, st_.data());
-      if (rc == UHDR_HIP_NO_ERROR) r0 = r1;
-    }
-  }
-  for (size_t k = r0; k < files.size(); ++k)   // the files of a failed round still open, and those behind it
+  if (files.empty()) return finish_statuses(st_, status);   // every file stopped at its checks: the device is not touched
+  const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
+  auto key = [](const SjFile& e) { return std::make_tuple(e.p010.width, e.p010.height, e.sdr_gamut, e.p010.colorGamut); };
+  std::stable_sort(files.begin(), files.end(), [&](const SjFile& x, const SjFile& y) { return key(x) < key(y); });
+  size_t done = 0;
+  const int rc = run_rounds(
+      files.size(), (size_t)kEncRound, stream, [&](size_t k) { return sj_round_bytes(files[k], api3 ? &info[files[k].idx] : nullptr, host); },
+      [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
+        return sdr_jpeg_round(st, s, api3, host, hdr_tf, &files[r0], m, sdr_jpeg, sdr_jpeg_size, sdr_jpeg_gamut, api3 ? info.data() : nullptr,
+                              dec_out.data(), dec_need.data(), out, out_capacity, out_size, st_.data());
+      },
+      &done);
+  for (size_t k = done; k < files.size(); ++k)   // the files of a failed round still open, and those behind it
     if (st_[files[k].idx] == UHDR_HIP_NO_ERROR) st_[files[k].idx] = rc;
-  return result();
+  return finish_statuses(st_, status);
 }
 
 // one API-x file
@@ -2972,39 +2712,42 @@ int uhdr_hip_jpegr_encode_apix_batch(int n, const uhdr_hip_image_t* yuv420_image
     if (rc != UHDR_HIP_NO_ERROR) { st_[i] = rc; continue; }
     files.push_back(std::move(e));
   }
-  auto result = [&]() {
-    int first = UHDR_HIP_NO_ERROR;
-    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
-    return first;
-  };
-  if (files.empty()) return result();   // every file stopped at its checks: the device is not touched
-  DeviceState* st = nullptr;
-  int rc = current_state(&st);
-  size_t r0 = 0;   // files [0, r0) are finished
-  if (rc == UHDR_HIP_NO_ERROR) {
-    CodecLease lease(st);
-    st = lease.get();
-    rc = st == nullptr ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
-    struct SyncOnExit {   // an error half-way through a round must not leave copies or kernels writing into the pools
-      hipStream_t s;
-      ~SyncOnExit() { (void)hipStreamSynchronize(s); }
-    } sync_on_exit{s};
-    while (rc == UHDR_HIP_NO_ERROR && r0 < files.size()) {   // rounds of <= kEncRound files and <= kCodecRoundBytes
-      size_t r1 = r0, bytes = 0;
-      while (r1 < files.size() && r1 - r0 < (size_t)kEncRound) {
-        const size_t b = enc_round_bytes(files[r1].yuv, host, true) + enc_round_bytes(files[r1].map, host, true);
-        if (r1 > r0 && bytes + b > kCodecRoundBytes) break;
-        bytes += b;
-        ++r1;
-      }
-      rc = apix_round(st, s, host, quality, &files[r0], (int)(r1 - r0), metadata, exif, exif_size, out, out_capacity, out_size, st_.data());
-      if (rc == UHDR_HIP_NO_ERROR) r0 = r1;
-    }
-  }
-  for (size_t k = r0; k < files.size(); ++k) st_[files[k].idx] = rc;   // the files of a failed round and of those behind it
-  return result();
+  if (files.empty()) return finish_statuses(st_, status);   // every file stopped at its checks: the device is not touched
+  const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
+  size_t done = 0;
+  const int rc = run_rounds(
+      files.size(), (size_t)kEncRound, stream,
+      [&](size_t k) { return enc_round_bytes(files[k].yuv, host, true) + enc_round_bytes(files[k].map, host, true); },
+      [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
+        return apix_round(st, s, host, quality, &files[r0], m, metadata, exif, exif_size, out, out_capacity, out_size, st_.data());
+      },
+      &done);
+  for (size_t k = done; k < files.size(); ++k) st_[files[k].idx] = rc;   // the files of a failed round and of those behind it
+  return finish_statuses(st_, status);
+}
+
+// JpegR::encodeJPEGR API-2 (jpegr.cpp:384-437): a batch of one file
+int uhdr_hip_jpegr_encode_api2(const uhdr_hip_image_t* p010_in, const uhdr_hip_image_t* yuv_in, const void* sdr_jpeg, size_t sdr_jpeg_size,
+                               int sdr_jpeg_gamut, int hdr_tf, void* out, size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
+  if (yuv_in == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                           // :390-393
+  return sdr_jpeg_files(1, p010_in, yuv_in, &sdr_jpeg, &sdr_jpeg_size, &sdr_jpeg_gamut, hdr_tf, &out, &out_capacity, out_size, nullptr, mem_space,
+                        stream);
+}
+
+// JpegR::encodeJPEGR API-3 (jpegr.cpp:439-500), the SDR rendition arrives as a JPEG only and is decoded on the device: a batch of one file
+int uhdr_hip_jpegr_encode_api3(const uhdr_hip_image_t* p010_in, const void* sdr_jpeg, size_t sdr_jpeg_size, int sdr_jpeg_gamut, int hdr_tf,
+                               void* out, size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
+  return sdr_jpeg_files(1, p010_in, nullptr, &sdr_jpeg, &sdr_jpeg_size, &sdr_jpeg_gamut, hdr_tf, &out, &out_capacity, out_size, nullptr, mem_space,
+                        stream);
+}
+
+// JpegR::encodeJPEGR "API-x" (jpegr.cpp:562-631), SDR planes + a ready gain map + its metadata, no BT.601 re-encode: a batch of one file
+int uhdr_hip_jpegr_encode_apix(const uhdr_hip_image_t* yuv_in, const uhdr_hip_image_t* gainmap, const uhdr_hip_metadata_t* metadata, int quality,
+                               const void* exif, size_t exif_size, void* out, size_t out_capacity, size_t* out_size, int mem_space, void* stream) {
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :566-568
+  if (yuv_in == nullptr || gainmap == nullptr || metadata == nullptr || out_size == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  return uhdr_hip_jpegr_encode_apix_batch(1, yuv_in, gainmap, metadata, quality, &exif, &exif_size, &out, &out_capacity, out_size, nullptr, mem_space,
+                                          stream);
 }
 
 // JpegR::getJPEGRInfo (jpegr.cpp:633-653)
@@ -4353,11 +4096,6 @@ int uhdr_hip_jpegr_edit_batch(int n, const void* const* jpegr, const size_t* jpe
   const uhdr_hip_effect_t* const fx[2] = {sdr_effects, gainmap_effects};
   const int n_fx[2] = {n_sdr_effects, n_gainmap_effects};
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
-  auto result = [&]() {
-    int first = UHDR_HIP_NO_ERROR;
-    for (int i = 0; i < n; ++i) { if (status) status[i] = st_[i]; if (first == UHDR_HIP_NO_ERROR) first = st_[i]; }
-    return first;
-  };
   try {
     // everything that needs no device: the split, the two headers, the metadata, the chains' own checks
     std::vector<EditFile> files;
@@ -4413,34 +4151,20 @@ int uhdr_hip_jpegr_edit_batch(int n, const void* const* jpegr, const size_t* jpe
         live.push_back(f);
       }
       if (!live.empty()) {
-        DeviceState* st = nullptr;
-        int rc = current_state(&st);
-        size_t r0 = 0;
-        if (rc == UHDR_HIP_NO_ERROR) {
-          CodecLease lease(st);
-          DeviceState* cx = lease.get();
-          rc = cx == nullptr ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
-          hipStream_t s = static_cast<hipStream_t>(stream);
-          while (rc == UHDR_HIP_NO_ERROR && r0 < live.size()) {   // rounds of <= 64 files and <= 2 GiB of workspace
-            size_t r1 = r0, bytes = 0;
-            while (r1 < live.size() && r1 - r0 < (size_t)kFxChainRound) {
-              const size_t b = edit_file_bytes(live[r1]);
-              if (r1 > r0 && bytes + b > kCodecRoundBytes) break;
-              bytes += b;
-              ++r1;
-            }
-            rc = edit_round(cx, s, &live[r0], (int)(r1 - r0), fx, n_fx, quality, out, out_capacity, out_size, st_.data());
-            if (rc == UHDR_HIP_NO_ERROR) r0 = r1;
-          }
-          if (rc != UHDR_HIP_NO_ERROR) (void)hipStreamSynchronize(s);
-        }
-        for (size_t k = r0; k < live.size(); ++k) st_[live[k].idx] = rc;
+        size_t done = 0;
+        const int rc = run_rounds(
+            live.size(), (size_t)kFxChainRound, stream, [&](size_t k) { return edit_file_bytes(live[k]); },
+            [&](DeviceState* cx, hipStream_t s, size_t r0, int m) {
+              return edit_round(cx, s, &live[r0], m, fx, n_fx, quality, out, out_capacity, out_size, st_.data());
+            },
+            &done);
+        for (size_t k = done; k < live.size(); ++k) st_[live[k].idx] = rc;
       }
     }
   } catch (const std::bad_alloc&) {
     return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
   }
-  return result();
+  return finish_statuses(st_, status);
 }
 
 }  // extern "C"

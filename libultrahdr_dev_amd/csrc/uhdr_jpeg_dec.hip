@@ -43,7 +43,6 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -808,13 +807,6 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
                         uint8_t* batch_ws, hipError_t* herr, int* image_rc) {
 #define JD_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { *herr = _e; (void)hipStreamSynchronize(s); return 1; } } while (0)
   if (n < 1) return -1;
-#ifdef UHDR_JD_TIMING
-  auto TT = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) { const auto t = std::chrono::steady_clock::now(); fprintf(stderr, "[jd]   %-28s %.0f us\n", what, std::chrono::duration<double, std::micro>(t - TT).count()); TT = t; };
-#define JD_LAP(x) lap(x)
-#else
-#define JD_LAP(x) do {} while (0)
-#endif
   // jobs and offset tables are assembled in page-locked memory that lives across calls (per host thread): their upload is then a
   // real asynchronous copy and needs no synchronisation of its own (every call ends with the stream idle, so reuse is safe)
   static thread_local void* t_pinned = nullptr;
@@ -906,7 +898,6 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
   }
   JD_TRY(hipMemcpyAsync(djobs, jobs, (size_t)n * sizeof(DecBatchJob) + noffs * 4, hipMemcpyHostToDevice, s));   // jobs + offset tables (adjacent on both sides)
   if (!keep.empty()) JD_TRY(hipStreamSynchronize(s));   // restart tables are in pageable host memory
-  JD_LAP("jobs assembled + uploaded");
   const SegOf sseg{doffs + (n + 1), n}, bseg{doffs + 2 * (n + 1), n};
   const CountIt cnt0(0u);
   uint8_t* stmp = batch_ws + B.tmp;
@@ -919,7 +910,6 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
       JD_TRY(hipMemcpyAsync(jobs[k].j.coef, info[k]->coef.data(), info[k]->coef.size() * sizeof(int16_t), hipMemcpyHostToDevice, s));
   hipLaunchKernelGGL(k_jd_unstuff_copy_multi, dim3(gu, ny), b256, 0, s, (const DecBatchJob*)djobs);
   hipLaunchKernelGGL(k_jd_sync_multi<0>, dim3(gsync, ny), b256, 0, s, (const DecBatchJob*)djobs, 0, 0u);
-  JD_LAP("enqueued through sync<0>");
   std::vector<uint32_t> flags((size_t)n * kFlagWords, 0u);
   uint32_t max_nsub = 0;
   for (int k = 0; k < n; ++k) max_nsub = std::max(max_nsub, jobs[k].j.nsub);
@@ -932,14 +922,6 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
     }
     JD_TRY(hipMemcpyAsync(flags.data(), dflags, flags.size() * 4, hipMemcpyDeviceToHost, s));
     JD_TRY(hipStreamSynchronize(s));
-    JD_LAP("round batch synced");
-#ifdef UHDR_JD_TIMING
-    for (int k = 0; k < n; ++k) {   // which launches of rounds still changed an end state
-      uint32_t last = 0;
-      for (uint32_t r = 1; r < round; ++r) if (flags[(size_t)k * kFlagWords + 64u + (r & 63u)] != 0u) last = r;
-      fprintf(stderr, "[jd]   image %d: %u subsequences, last launch of rounds that changed a state: %u of %u\n", k, jobs[k].j.nsub, last, round - 1u);
-    }
-#endif
     bool any = false;
     for (int k = 0; k < n; ++k) any = any || flags[(size_t)k * kFlagWords + 64u + ((round - 1u) & 63u)] != 0u;
     if (!any) break;
@@ -957,10 +939,8 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
                                           reinterpret_cast<Dc3*>(batch_ws + B.dc), (size_t)boff[n], Dc3Sum(), rocprim::equal_to<uint64_t>(), s));
   }
   hipLaunchKernelGGL(k_jd_idct_multi, dim3(gidct, ny), dim3(128), 0, s, (const DecBatchJob*)djobs);
-  JD_LAP("tail enqueued");
   JD_TRY(hipMemcpyAsync(flags.data(), dflags, flags.size() * 4, hipMemcpyDeviceToHost, s));
   JD_TRY(hipStreamSynchronize(s));
-  JD_LAP("final sync");
   JD_TRY(hipGetLastError());
   int out = 0;
   for (int k = 0; k < n; ++k) {

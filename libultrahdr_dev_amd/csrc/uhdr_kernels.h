@@ -275,10 +275,8 @@ hipError_t launch_build_gain_lut(float* table, double log2_min, double log2_max,
 hipError_t launch_tonemap(const ToneBatch& b, int n, bool aligned, hipStream_t s);      // n <= kToneChunk images of equal width / height
 hipError_t launch_convert_yuv(const CvtBatch& b, int n, bool aligned, hipStream_t s);
 static_assert(sizeof(CvtBatch) <= 4096 && sizeof(ToneBatch) <= 4096, "toneMap / convertYuv kernel arguments exceed the kernarg segment");
-// decoded 4:2:0 planes -> RGBA8888 with libjpeg-turbo's arithmetic (k_ycc420_rgba); w, h even, strides in bytes
-hipError_t launch_ycc420_to_rgba(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t w, uint32_t h, uint32_t y_stride,
-                                 uint32_t c_stride, uint8_t* rgba, hipStream_t s);
-// the same for up to kRgbaChunk images of any (even) sizes in one launch (k_ycc420_rgba_batch: grid.z = image)
+// decoded 4:2:0 planes -> RGBA8888 with libjpeg-turbo's arithmetic; w, h even, strides in bytes: up to kRgbaChunk images of any
+// (even) sizes in one launch (k_ycc420_rgba_batch: grid.z = image)
 constexpr int kRgbaChunk = 64;
 struct YccRgbaImage {
   const uint8_t* y;

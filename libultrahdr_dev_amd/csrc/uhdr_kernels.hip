@@ -2585,7 +2585,7 @@ hipError_t launch_apply(const AppConsts& c, const AppBatch& b, int n, int fmt, i
 // One thread per horizontal pixel pair (they share the centre chroma column).  Restated in oracle/jpeg_oracle.c and pinned there
 // against libjpeg-turbo itself (Pillow's).
 // =================================================================================================
-// the pixel pair (2c, 2c+1) of row r: both kernels below run this body, so the one-image and the batched form write the same bytes
+// the pixel pair (2c, 2c+1) of row r
 __device__ __forceinline__ void ycc420_rgba_pair(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cbp, const uint8_t* __restrict__ crp,
                                                  uint32_t w, uint32_t h, uint32_t ys, uint32_t cs, uint8_t* __restrict__ rgba, uint32_t c, uint32_t r) {
   const uint32_t cw = w >> 1, ch = h >> 1;
@@ -2617,26 +2617,12 @@ __device__ __forceinline__ void ycc420_rgba_pair(const uint8_t* __restrict__ yp,
   *reinterpret_cast<uint2*>(rgba + ((size_t)r * w + 2u * c) * 4u) = make_uint2(px[0], px[1]);
 }
 
-__global__ void __launch_bounds__(256) k_ycc420_rgba(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cbp, const uint8_t* __restrict__ crp,
-                                                     uint32_t w, uint32_t h, uint32_t ys, uint32_t cs, uint8_t* __restrict__ rgba) {
-  const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-  if (c >= (w >> 1)) return;
-  ycc420_rgba_pair(yp, cbp, crp, w, h, ys, cs, rgba, c, blockIdx.y);
-}
-
 // n images of any sizes in one launch: grid.z = image, grid.x over the widest image's pixel pairs, rows strided by grid.y
 __global__ void __launch_bounds__(256) k_ycc420_rgba_batch(const YccRgbaBatch b) {
   const YccRgbaImage& im = b.img[blockIdx.z];
   const uint32_t c = blockIdx.x * 256u + threadIdx.x;
   if (c >= (im.w >> 1)) return;
   for (uint32_t r = blockIdx.y; r < im.h; r += gridDim.y) ycc420_rgba_pair(im.y, im.cb, im.cr, im.w, im.h, im.ys, im.cs, im.rgba, c, r);
-}
-
-hipError_t launch_ycc420_to_rgba(const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t w, uint32_t h, uint32_t y_stride,
-                                 uint32_t c_stride, uint8_t* rgba, hipStream_t s) {
-  if (w == 0 || h == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_ycc420_rgba, dim3((w / 2u + 255u) / 256u, h), dim3(256), 0, s, y, cb, cr, w, h, y_stride, c_stride, rgba);
-  return hipGetLastError();
 }
 
 hipError_t launch_ycc420_to_rgba_batch(const YccRgbaBatch& b, int n, hipStream_t s) {

@@ -97,6 +97,35 @@ def test_4k_frame_and_its_gain_map(hip, orc, q):
     assert rc == 0 and got == orc.jpeg_encode("orc", gm, None, w // 4, h // 4, q)
 
 
+_NOISE_Q100 = []
+
+
+def _noise_q100(orc):
+    """a 512x256 4:2:0 noise image and its oracle file at quality 100 (made once): longer than w * h + 64 KiB, the encoder's first guess
+    at the page-locked staging of a file that goes to host memory, so the image is compressed a second time into staging of its size"""
+    if not _NOISE_Q100:
+        rng = np.random.RandomState(23)
+        w, h = 512, 256
+        y, u, v = _content("noise", w, h, rng)
+        yb, ub = _planes(y, u, v, w, w // 2, rng)
+        _NOISE_Q100.append((yb, ub, w, h, orc.jpeg_encode("orc", yb, ub, w, h, 100, w, w // 2)))
+    return _NOISE_Q100[0]
+
+
+def test_host_file_larger_than_its_first_staging(hip, orc):
+    yb, ub, w, h, want = _noise_q100(orc)
+    assert len(want) > w * h + 65536
+    rc, n, got = _gpu_encode(hip.load(), hip, yb, ub, w, h, 100, w, w // 2, False)
+    assert rc == 0 and n == len(want) and got == want
+
+
+def test_host_file_larger_than_its_first_staging_and_the_buffer(hip, orc):
+    yb, ub, w, h, want = _noise_q100(orc)
+    assert len(want) > w * h + 65536
+    rc, n, _ = _gpu_encode(hip.load(), hip, yb, ub, w, h, 100, w, w // 2, False, cap=len(want) - 1)
+    assert rc == hip.ERROR_INSUFFICIENT_RESOURCE and n == len(want)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # decoder: uhdr_hip_jpeg_decode = JpegDecoderHelper::decompressImage(..., DECODE_TO_YCBCR)
 # ---------------------------------------------------------------------------------------------------------------------

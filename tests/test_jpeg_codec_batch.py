@@ -535,6 +535,44 @@ def test_decode_batch_rgba_equals_single_calls_and_oracle(hip, orc, tmp_path, ou
         assert np.array_equal(got[i].reshape(h, w, 4), orc.ycc420_to_rgba(planes, w, h)), name
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [(16, 16), (200, 120)])
+def test_single_rgba_decode_equals_oracle(hip, orc, size):
+    """uhdr_hip_jpeg_decode_rgba on its own, into device and into host memory: libjpeg-turbo's RGBA of the oracle's planes"""
+    from tests.gpu_util import dev_empty, stream_ptr
+    lib = hip.load()
+    w, h = size
+    y, u, v = _content("smooth", w, h, np.random.RandomState(w + h))
+    data = orc.jpeg_encode("orc", np.ascontiguousarray(y), np.ascontiguousarray(np.concatenate([u.reshape(-1), v.reshape(-1)])), w, h, 90)
+    st, planes, dw, dh, _ = orc.jpeg_decode("orc", data)
+    assert st > 0 and (dw, dh) == (w, h)
+    want = orc.ycc420_to_rgba(planes, w, h)
+    need = w * h * 4
+    dout = dev_empty(need + 64, 0xCD)
+    s, d = _single_decode(lib, data, True, C.c_void_p(dout.data_ptr()), need, api.MEM_DEVICE, stream_ptr())
+    assert s == 0 and (d.data, d.width, d.height, d.luma_stride, d.pixelFormat) == (dout.data_ptr(), w, h, w, -1)
+    got = dout.cpu().numpy()
+    assert np.array_equal(got[:need].reshape(h, w, 4), want) and (got[need:] == 0xCD).all()
+    s, out, d = _dec_single_host(lib, data, True)
+    assert s == 0 and (d.width, d.height) == (w, h)
+    assert np.array_equal(out[:need].reshape(h, w, 4), want) and (out[need:] == 0xCD).all()
+
+
+@pytest.mark.gpu
+def test_single_rgba_decode_of_an_odd_size_answers_its_probe_first(hip, orc):
+    lib = hip.load()
+    y, u, v = _content("smooth", 16, 16, np.random.RandomState(32))
+    data = _with_size(orc.jpeg_encode("orc", np.ascontiguousarray(y), np.ascontiguousarray(np.concatenate([u.reshape(-1), v.reshape(-1)])), 16, 16, 90), 15, 16)
+    need = 15 * 16 * 4
+    out = np.full(need, 0xCD, np.uint8)
+    for o, cap, want in ((None, 0, api.ERROR_INSUFFICIENT_RESOURCE), (C.c_void_p(out.ctypes.data), need - 1, api.ERROR_INSUFFICIENT_RESOURCE),
+                         (C.c_void_p(out.ctypes.data), need, api.ERROR_UNSUPPORTED_FEATURE)):
+        s, d = _single_decode(lib, data, True, o, cap, api.MEM_HOST)
+        assert s == want, (cap, s)
+        assert _desc_tuple(d) == (None if o is None else out.ctypes.data, 15, 16, api.CG_UNSPECIFIED, None, 15, 0, -1)
+    assert (out == 0xCD).all()
+
+
 def _corrupt_entropy(lib, orc):
     """a file whose header parses but whose entropy-coded data the device decoder rejects (found with the single call)"""
     rng = np.random.RandomState(41)

@@ -540,6 +540,25 @@ def test_apix_mixed_batch_equals_oracle_and_single_calls(hip, mem):
         assert b.file(i) == s2[i][1] and (cases2[i]["pad"] or b.file(i) == cases2[i]["oracle"](90))
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("mem", [api.MEM_DEVICE, api.MEM_HOST])
+def test_single_calls_equal_the_oracle_at_the_smallest_map_of_16x12(hip, orc, mem):
+    """uhdr_hip_jpegr_encode_api2, _api3 and _apix on their own, one 64 x 48 file each: the CPU restatement's bytes"""
+    lib = hip.load()
+    w, h = 64, 48
+    cap = w * h * 3 + 65536
+    c = Case(orc, w, h, api.CG_BT709, api.CG_BT2100, 900)
+    pi, yi = c.images(mem)
+    for api3 in (False, True):
+        rc, got, n = single_sdr(lib, pi, None if api3 else yi, c.jpeg, c.cfg, api.TF_HLG, cap, mem)
+        want = c.oracle(api3, api.TF_HLG)
+        assert rc == 0 and n == len(want) and got == want, api3
+    x = _xcase(w, h, w // 4, h // 4, api.CG_BT709, 9, exif=b"Exif\0\0apix-single")
+    rc, got, n = single_x(lib, *x["images"](mem), x["md"], 90, x["exif"], cap, mem)
+    want = x["oracle"](90)
+    assert rc == 0 and n == len(want) and got == want
+
+
 def _many(orc, count):
     return [Case(orc, 72, 40, (api.CG_BT709, api.CG_P3, api.CG_BT2100)[i % 3], api.CG_BT2100, 700 + i, icc=i % 2 == 0) for i in range(count)]
 
