@@ -74,6 +74,12 @@ extern "C" {
 #define UHDR_HIP_PIX_FMT_P010 0
 #define UHDR_HIP_PIX_FMT_YUV420 1
 #define UHDR_HIP_PIX_FMT_MONOCHROME 2
+/* (no counterpart in the reference) 8-bit YCbCr at other samplings: what the UHDR_HIP_DECODE_ANY_SAMPLING decodes return and
+ * uhdr_hip_apply_gainmap[_batch] reads as the SDR image.  As for YUV420, data = Y, chroma_data = Cb, and Cr sits
+ * chroma_stride * chroma_height bytes behind Cb; the chroma extent is libjpeg's downsampled size, rounded up (any width / height): */
+#define UHDR_HIP_PIX_FMT_YUV444 3               /* chroma width x height */
+#define UHDR_HIP_PIX_FMT_YUV422 4               /* chroma ceil(width / 2) x height */
+#define UHDR_HIP_PIX_FMT_YUV440 5               /* chroma width x ceil(height / 2) */
 /* status_t, ultrahdr.h:91-120 */
 #define UHDR_HIP_NO_ERROR 0
 #define UHDR_HIP_UNKNOWN_ERROR (-1)
@@ -377,6 +383,28 @@ int uhdr_hip_jpeg_decode_rgba(const void* jpeg, size_t jpeg_size, void* out, siz
 int uhdr_hip_jpeg_decode_batch(int n, const void* const* jpeg, const size_t* jpeg_size, int decode_to, void* const* out,
                                const size_t* out_capacity, uhdr_hip_image_t* descs, int* status, int mem_space, void* stream);
 
+/* Opt-in decode of samplings the reference refuses.  The *_ex calls are the calls above plus `flags`; with flags == 0 every status,
+ * byte and descriptor is that of the call without the suffix, and a bit this header does not define is ERROR_UNSUPPORTED_FEATURE at
+ * call level.  UHDR_HIP_DECODE_ANY_SAMPLING: a three-component YCbCr file (baseline, restart intervals or progressive) is also read
+ * when its luma sampling is 1x1 (4:4:4), 2x1 (4:2:2) or 1x2 (4:4:0) and both chroma components are 1x1 -- what editors write at high
+ * quality, many cameras, and a lossless rotation of a 4:2:2 file.  Any other sampling (4:1:1, chroma factors above 1) stays
+ * UNKNOWN_ERROR (JPEG/R: ERROR_DECODE_ERROR).  The planes are byte-identical to libjpeg's raw_data_out, packed: width x height luma,
+ * then Cb, then Cr of the chroma extent given at UHDR_HIP_PIX_FMT_YUV444 / 422 / 440 with chroma_stride = chroma width, i.e.
+ * width * height + 2 * chroma_width * chroma_height bytes; descs[i].pixelFormat names the layout.  Odd widths and heights are
+ * read for these three samplings (4:2:0 keeps its even-size rule).  UHDR_HIP_DECODE_TO_RGBA is byte-identical to libjpeg-turbo's
+ * decode: no upsampling (4:4:4), h2v1 (4:2:2) or h1v2 (4:4:0) "fancy" upsampling, then the colour conversion of the 4:2:0 path.
+ * Size probes work as in the calls without flags.  The decoder's steps are the same kernels with the MCU shape per image, so files
+ * of every sampling share a batch's launches.  Measured on one MI355X (profiles/r06_jpeg_sampling.txt): a 4K quality-95 file decodes in
+ * 382 us as 4:4:4 and 428 us as 4:2:2, beside 682 us as 4:2:0; against the commit before this interface a single 4:2:0 decode and a
+ * 16-file 4:2:0 batch cost the same (within 0.5 %, inside that commit's own run-to-run spread, four sessions). */
+#define UHDR_HIP_DECODE_ANY_SAMPLING 1
+int uhdr_hip_jpeg_decode_batch_ex(int n, const void* const* jpeg, const size_t* jpeg_size, int decode_to, void* const* out,
+                                  const size_t* out_capacity, uhdr_hip_image_t* descs, int* status, int mem_space, void* stream,
+                                  int flags);
+/* uhdr_hip_jpeg_decode (decode_to = UHDR_HIP_DECODE_TO_YCBCR) or uhdr_hip_jpeg_decode_rgba (UHDR_HIP_DECODE_TO_RGBA) with flags */
+int uhdr_hip_jpeg_decode_ex(const void* jpeg, size_t jpeg_size, int decode_to, void* out, size_t out_capacity, uhdr_hip_image_t* desc,
+                            int mem_space, void* stream, int flags);
+
 /* JpegR::decodeJPEGR (lib/src/jpegr.cpp:655-822) for the HDR output formats: a JPEG/R file (HOST memory: primary JPEG + gain
  * map JPEG, the gain map's APP1 carrying the hdrgm:* XMP attributes) -> the HDR rendition applyGainMap produces.  Container
  * scan (extractPrimaryImageAndGainMap, :823-876), XMP metadata (getMetadataFromXMP, jpegrutils.cpp:436-545) and the ICC gamut
@@ -407,6 +435,18 @@ int uhdr_hip_jpegr_decode(const void* jpegr, size_t jpegr_size, int output_forma
 int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
                                 void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests,
                                 uhdr_hip_metadata_t* metadata, int* status, int apply_mode, int mem_space, void* stream);
+
+/* uhdr_hip_jpegr_decode[_batch] with flags (see UHDR_HIP_DECODE_ANY_SAMPLING; flags == 0: the calls above).  With the flag the
+ * primary image may be 4:4:4, 4:2:2 or 4:4:0: UHDR_HIP_OUTPUT_SDR is libjpeg-turbo's RGBA of it, the HDR outputs are applyGainMap
+ * over its planes with every pixel reading the chroma sample libjpeg's downsampled grid gives it (the rule of the reference's
+ * getYuv420Pixel, no interpolation), through the general per-pixel kernels in every apply_mode (the scale-4 fast kernels are
+ * 4:2:0's).  A gain-map JPEG with chroma of any accepted sampling contributes its luma. */
+int uhdr_hip_jpegr_decode_ex(const void* jpegr, size_t jpegr_size, int output_format, float max_display_boost, void* dest_data,
+                             size_t dest_capacity, uhdr_hip_image_t* dest, uhdr_hip_metadata_t* metadata, int apply_mode,
+                             int mem_space, void* stream, int flags);
+int uhdr_hip_jpegr_decode_batch_ex(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
+                                   void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests,
+                                   uhdr_hip_metadata_t* metadata, int* status, int apply_mode, int mem_space, void* stream, int flags);
 
 /* JpegR::appendGainMap (lib/src/jpegr.cpp:951-1130): primary JPEG + gain-map JPEG + metadata -> JPEG/R container (XMP packets of
  * jpegrutils.cpp:547-611, MPF segment of multipictureformat.cpp:30-92).  exif / icc: payloads of an APP1 / APP2 segment to add, or

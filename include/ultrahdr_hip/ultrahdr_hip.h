@@ -230,10 +230,14 @@ class JpegRHip {
   // -1 (default): the reference's constant boost range.  UHDR_HIP_BOOST_PER_IMAGE / UHDR_HIP_BOOST_PER_CALL: the API-0 and API-1
   // overloads encode the gain map against the range the content has (uhdr_hip_jpegr_encode_adaptive_batch); the others are unchanged
   void setContentBoost(int scope_or_minus_one) { mContentBoost = scope_or_minus_one; }
+  // false (default): decodeJPEGR reads what the reference reads, 4:2:0 primaries.  true: also 4:4:4, 4:2:2 and 4:4:0 ones
+  // (UHDR_HIP_DECODE_ANY_SAMPLING)
+  void setDecodeAnySampling(bool on) { mDecodeAnySampling = on; }
 
  private:
   int mApplyMode = 1;
   int mContentBoost = -1;
+  bool mDecodeAnySampling = false;
 };
 
 }  // namespace ultrahdr

@@ -14,6 +14,7 @@ CG_UNSPECIFIED, CG_BT709, CG_P3, CG_BT2100 = -1, 0, 1, 2
 TF_LINEAR, TF_HLG, TF_PQ, TF_SRGB = 0, 1, 2, 3
 OUTPUT_SDR, OUTPUT_HDR_LINEAR, OUTPUT_HDR_PQ, OUTPUT_HDR_HLG, OUTPUT_HDR_LINEAR_RGB_10BIT = 0, 1, 2, 3, 4
 PIX_FMT_P010, PIX_FMT_YUV420, PIX_FMT_MONOCHROME = 0, 1, 2
+PIX_FMT_YUV444, PIX_FMT_YUV422, PIX_FMT_YUV440 = 3, 4, 5   # what the DECODE_ANY_SAMPLING decodes return and apply reads
 NO_ERROR, UNKNOWN_ERROR = 0, -1
 ERROR_BAD_PTR, ERROR_INVALID_COLORGAMUT, ERROR_INVALID_TRANS_FUNC = -10001, -10003, -10005
 ERROR_RESOLUTION_MISMATCH, ERROR_BAD_METADATA = -10006, -10010
@@ -26,6 +27,7 @@ ERROR_NO_IMAGES_FOUND, ERROR_MULTIPLE_EXIFS_RECEIVED = -20006, -20007
 MEM_HOST, MEM_DEVICE = 0, 1
 MEM_DEVICE_TO_HOST, MEM_HOST_TO_DEVICE = 2, 3   # uhdr_hip_jpeg_encode_batch: planes and outputs apart
 DECODE_TO_RGBA, DECODE_TO_YCBCR = 1, 2          # uhdr_hip_jpeg_decode_batch
+DECODE_ANY_SAMPLING = 1                         # flags bit of the *_decode*_ex calls: also 4:4:4, 4:2:2 and 4:4:0 files
 APPLY_FAST, APPLY_EXACT, APPLY_LUT, APPLY_EXACT_UNFILTERED = 0, 1, 2, 3
 GENERATE_EXACT, GENERATE_LUT, GENERATE_UNFILTERED = 0, 1, 2
 BOOST_PER_IMAGE, BOOST_PER_CALL = 0, 1          # content-adaptive gain maps: one boost range per image / per call
@@ -126,6 +128,13 @@ SIGNATURES = {
                                              _IP, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "uhdr_hip_jpegr_decode_batch": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_float, C.POINTER(C.c_void_p),
                                               C.POINTER(C.c_size_t), _IP, _MP, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p]),
+    "uhdr_hip_jpeg_decode_batch_ex": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                _IP, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int]),
+    "uhdr_hip_jpeg_decode_ex": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, _IP, C.c_int, C.c_void_p, C.c_int]),
+    "uhdr_hip_jpegr_decode_ex": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p, C.c_size_t, _IP, _MP, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_int]),
+    "uhdr_hip_jpegr_decode_batch_ex": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_float, C.POINTER(C.c_void_p),
+                                                 C.POINTER(C.c_size_t), _IP, _MP, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "uhdr_hip_jpegr_metadata": (C.c_int, [C.c_void_p, C.c_size_t, _MP]),
     "uhdr_hip_jpegr_info": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(JpegInfo), C.POINTER(JpegInfo)]),
     "uhdr_hip_lut_table": (C.c_int, [C.c_int, C.POINTER(C.c_float), C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -238,6 +247,20 @@ def p010_image(ptr, w, h, gamut, luma_stride=None, chroma_stride=None, chroma_pt
     cs = ls if chroma_stride is None else chroma_stride
     cp = ptr + ls * h * 2 if chroma_ptr is None else chroma_ptr
     return Image(ptr, w, h, gamut, cp, ls, cs, PIX_FMT_P010)
+
+
+def chroma_size(pix_fmt, w, h):
+    """(width, height) of a chroma plane of an 8-bit YCbCr image: libjpeg's downsampled size for YUV444 / YUV422 / YUV440"""
+    return {PIX_FMT_YUV444: (w, h), PIX_FMT_YUV422: ((w + 1) // 2, h), PIX_FMT_YUV440: (w, (h + 1) // 2)}.get(pix_fmt, (w // 2, h // 2))
+
+
+def ycbcr_image(ptr, w, h, gamut, pix_fmt, luma_stride=None, chroma_stride=None, chroma_ptr=None):
+    """descriptor of a YUV444 / YUV422 / YUV440 image as the any-sampling decode lays it out: Y, then Cb, then Cr chroma_stride *
+    chroma height behind Cb"""
+    ls = w if luma_stride is None else luma_stride
+    cs = chroma_size(pix_fmt, w, h)[0] if chroma_stride is None else chroma_stride
+    cp = ptr + ls * h if chroma_ptr is None else chroma_ptr
+    return Image(ptr, w, h, gamut, cp, ls, cs, pix_fmt)
 
 
 def mono_image(ptr, w, h):

@@ -580,11 +580,26 @@ AppConsts apply_consts(const uhdr_hip_image_t& yuv, const uhdr_hip_image_t& map,
   c.step_x = c.step_y = 0;
   return c;
 }
+// The chroma geometry of an 8-bit YCbCr image by its pixelFormat: the shifts from a pixel to its chroma sample and the rows of a
+// chroma plane (Cr sits chroma_stride * rows behind Cb).  YUV444 / YUV422 / YUV440 are what the any-sampling decode returns
+// (libjpeg's downsampled sizes: rounded up); every other value is 4:2:0 with the reference's height / 2 rows.
+struct ChromaGeom { uint32_t csx, csy; size_t rows; };
+ChromaGeom chroma_geom(const uhdr_hip_image_t& yuv) {
+  switch (yuv.pixelFormat) {
+    case UHDR_HIP_PIX_FMT_YUV444: return ChromaGeom{0u, 0u, yuv.height};
+    case UHDR_HIP_PIX_FMT_YUV422: return ChromaGeom{1u, 0u, yuv.height};
+    case UHDR_HIP_PIX_FMT_YUV440: return ChromaGeom{0u, 1u, (yuv.height + 1) / 2};
+    default: return ChromaGeom{1u, 1u, yuv.height / 2};
+  }
+}
+bool is_420(const uhdr_hip_image_t& yuv) { const ChromaGeom g = chroma_geom(yuv); return g.csx == 1u && g.csy == 1u; }
 AppImage app_image(const uhdr_hip_image_t& yuv, const uhdr_hip_image_t& map, void* dst) {
   AppImage a;
+  const ChromaGeom g = chroma_geom(yuv);
   a.y = static_cast<const uint8_t*>(yuv.data);
   a.u = static_cast<const uint8_t*>(yuv.chroma_data);
-  a.v = a.u + yuv.chroma_stride * (yuv.height / 2);
+  a.v = a.u + yuv.chroma_stride * g.rows;
+  a.csx = g.csx; a.csy = g.csy;
   a.map = static_cast<const uint8_t*>(map.data);
   a.dst = dst;
   a.y_stride = (uint32_t)yuv.luma_stride;
@@ -592,6 +607,7 @@ AppImage app_image(const uhdr_hip_image_t& yuv, const uhdr_hip_image_t& map, voi
   return a;
 }
 bool app_fast_s4(const AppConsts& c, const AppImage& a) {
+  if (a.csx != 1u || a.csy != 1u) return false;   // the scale-4 kernels load 4:2:0 chroma
   // the fast kernels index planes with 32-bit byte offsets (the widest output is 8 bytes per pixel)
   if ((uint64_t)a.y_stride * c.height >= (1ull << 32) || (uint64_t)c.width * c.height >= (1ull << 29)) return false;
   return c.scale == 4 && c.width == 4u * c.map_w && c.height == 4u * c.map_h && al(a.y, 4) && a.y_stride % 4u == 0 &&
@@ -757,6 +773,28 @@ int d2h_plane(void* h, size_t hstride_elems, const void* d, size_t dpitch_elems,
   return UHDR_HIP_NO_ERROR;
 }
 
+int stage_yuv420_in(StageSet* st, int slot, const uhdr_hip_image_t& h, uhdr_hip_image_t* d, hipStream_t s);
+// device copy of the host SDR image of applyGainMap, by its pixelFormat: YUV444 / YUV422 / YUV440 with their own chroma extent (Cr
+// right behind Cb's rows), anything else as stage_yuv420_in
+int stage_ycbcr_in(StageSet* st, int slot, const uhdr_hip_image_t& h, uhdr_hip_image_t* d, hipStream_t s) {
+  if (is_420(h)) return stage_yuv420_in(st, slot, h, d, s);
+  {
+    const ChromaGeom g = chroma_geom(h);
+    const size_t w = h.width, cw = (w + g.csx) >> g.csx, ch = g.rows;
+    const size_t lp = round_up(w ? w : 1, 64), cp = round_up(cw ? cw : 1, 64);
+    int rc;
+    if ((rc = stage_reserve(st, slot, lp * (h.height ? h.height : 1))) != 0) return rc;
+    if ((rc = stage_reserve(st, slot + 1, cp * (2 * ch + 1))) != 0) return rc;
+    *d = h;
+    d->data = st->stage[slot]; d->chroma_data = st->stage[slot + 1];
+    d->luma_stride = lp; d->chroma_stride = cp;
+    if ((rc = h2d_plane(d->data, lp, h.data, h.luma_stride, w, h.height, 1, s)) != 0) return rc;
+    const uint8_t* hu = static_cast<const uint8_t*>(h.chroma_data);
+    uint8_t* du = static_cast<uint8_t*>(d->chroma_data);
+    if ((rc = h2d_plane(du, cp, hu, h.chroma_stride, cw, ch, 1, s)) != 0) return rc;
+    return h2d_plane(du + cp * ch, cp, hu + h.chroma_stride * ch, h.chroma_stride, cw, ch, 1, s);
+  }
+}
 // device copy of a host YUV420 image in slots [slot, slot+1]: Y then U|V (pitch = 64-aligned)
 int stage_yuv420_in(StageSet* st, int slot, const uhdr_hip_image_t& h, uhdr_hip_image_t* d, hipStream_t s) {
   const size_t w = h.width, hh = h.height, cw = (w + 1) / 2, ch = (hh + 1) / 2;
@@ -1595,15 +1633,15 @@ struct JpegrFile {
 // The image that starts at `begin`, found through its header: the header parser's walk over the (only) scan of a baseline file
 // ends at EOI, and that is where the image ends.  Anything else -- more scans, other markers behind the scan, a header this decoder
 // does not read -- is left to the container's own marker walk (jpegr::find_images), which then walks the scan a second time.
-bool image_by_header(const uint8_t* file, size_t n, size_t begin, jpeg::DecInfo* info, size_t* len) {
-  if (begin + 4 > n || jpeg::parse_header(file + begin, n - begin, info) != 0) return false;
+bool image_by_header(const uint8_t* file, size_t n, size_t begin, jpeg::DecInfo* info, size_t* len, bool any_sampling) {
+  if (begin + 4 > n || jpeg::parse_header(file + begin, n - begin, info, any_sampling) != 0) return false;
   const size_t e = begin + info->scan_offset + info->scan_bytes;
   if (e + 2 > n || file[e] != 0xFF || file[e + 1] != 0xD9) return false;
   *len = e + 2 - begin;
   return true;
 }
 
-int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bool want_metadata, JpegrFile* f) {
+int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bool want_metadata, JpegrFile* f, bool any_sampling) {
   const uint8_t* file = static_cast<const uint8_t*>(jpegr);
   const bool sdr = output_format == UHDR_HIP_OUTPUT_SDR;   // the gain map is neither decompressed nor (unless asked for) read (:728, :754)
   jpegr::Range img[2];
@@ -1611,7 +1649,7 @@ int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bo
   bool have0 = false;       // the primary image at least (kept when the second image needs the container's walk: a progressive
                             // primary has had all its scans entropy-decoded by then, once is enough)
   size_t len0 = 0;
-  if (file != nullptr && jpegr_size >= 4 && file[0] == 0xFF && file[1] == 0xD8 && image_by_header(file, jpegr_size, 0, &f->info[0], &img[0].len)) {
+  if (file != nullptr && jpegr_size >= 4 && file[0] == 0xFF && file[1] == 0xD8 && image_by_header(file, jpegr_size, 0, &f->info[0], &img[0].len, any_sampling)) {
     have0 = true; len0 = img[0].len;
     img[0].begin = 0;
     size_t pos = img[0].len;
@@ -1620,7 +1658,7 @@ int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bo
       if (q == nullptr) break;
       pos = (size_t)(static_cast<const uint8_t*>(q) - file);
       if (file[pos + 1] == 0xD8) {
-        by_header = image_by_header(file, jpegr_size, pos, &f->info[1], &img[1].len);
+        by_header = image_by_header(file, jpegr_size, pos, &f->info[1], &img[1].len, any_sampling);
         img[1].begin = pos;
         break;
       }
@@ -1635,7 +1673,7 @@ int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bo
   for (int k = 0; k < (sdr ? 1 : 2); ++k) {   // the headers, parsed once (jpeg_read_header of either decompressImage call, :690-694 / :731-733)
     f->jpg[k] = file + img[k].begin; f->len[k] = img[k].len;
     const bool parsed = by_header || (k == 0 && have0 && img[0].begin == 0 && img[0].len == len0);
-    const int prc = parsed ? 0 : jpeg::parse_header(f->jpg[k], f->len[k], &f->info[k]);
+    const int prc = parsed ? 0 : jpeg::parse_header(f->jpg[k], f->len[k], &f->info[k], any_sampling);
     if (prc == -3) return UHDR_HIP_UNKNOWN_ERROR;   // host allocation failed (never the capacity-probe status)
     if (prc == -2) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     if (prc != 0 || f->info[k].w > 8192 || f->info[k].h > 8192) return UHDR_HIP_ERROR_DECODE_ERROR;
@@ -1656,30 +1694,65 @@ int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bo
   return UHDR_HIP_NO_ERROR;
 }
 
+// What a decoded image looks like in memory: the w x h luma plane, then Cb and Cr of cw x ch samples each, cbytes apart.  4:2:0
+// keeps the reference's (w / 2) x (h / 2) planes luma / 4 bytes apart (even sizes; odd ones as before); the samplings only the
+// any-sampling decode parses get libjpeg's downsampled sizes, ceil(w / hs) x ceil(h / vs), packed.
+struct DecGeom { size_t cw, ch, cbytes; int fmt; };
+DecGeom dec_geom(const jpeg::DecInfo& info) {
+  const size_t w = (size_t)info.w, h = (size_t)info.h;
+  if (info.gray) return DecGeom{0, 0, 0, UHDR_HIP_PIX_FMT_MONOCHROME};
+  if (info.hs == 2 && info.vs == 2) return DecGeom{w / 2, h / 2, w * h / 4, UHDR_HIP_PIX_FMT_YUV420};
+  const size_t cw = (w + info.hs - 1) / info.hs, ch = (h + info.vs - 1) / info.vs;
+  return DecGeom{cw, ch, cw * ch, info.hs == 2 ? UHDR_HIP_PIX_FMT_YUV422 : info.vs == 2 ? UHDR_HIP_PIX_FMT_YUV440 : UHDR_HIP_PIX_FMT_YUV444};
+}
+// the three planes of a decode into the packed buffer at p
+void dec_planes(const jpeg::DecInfo& info, uint8_t* p, jpeg::DecPlane out[3]);
+// an image's entry in either RGBA conversion batch (4:2:0: k_ycc420_rgba_batch, the other samplings: k_yccx_rgba_batch)
+struct RgbaBatches {
+  YccRgbaBatch b420; int n420 = 0;
+  YccxRgbaBatch bx; int nx = 0;
+  uint8_t* add(const jpeg::DecInfo& info, const uint8_t* ycc, uint8_t* rgba) {
+    const DecGeom g = dec_geom(info);
+    const size_t luma = (size_t)info.w * (size_t)info.h;
+    const YccRgbaImage im{ycc, ycc + luma, ycc + luma + g.cbytes, rgba, (uint32_t)info.w, (uint32_t)info.h, (uint32_t)info.w, (uint32_t)g.cw};
+    if (g.fmt == UHDR_HIP_PIX_FMT_YUV420) b420.img[n420++] = im;
+    else bx.img[nx++] = YccxRgbaImage{im, (uint32_t)info.hs, (uint32_t)info.vs};
+    return rgba;
+  }
+  int size() const { return n420 + nx; }
+  hipError_t launch(hipStream_t s) {
+    hipError_t e = launch_ycc420_to_rgba_batch(b420, n420, s);
+    if (e == hipSuccess) e = launch_yccx_to_rgba_batch(bx, nx, s);
+    n420 = nx = 0;
+    return e;
+  }
+};
+
 // The host part of uhdr_hip_jpeg_decode (rgba false) or uhdr_hip_jpeg_decode_rgba (rgba true) for one file: the checks in their
 // order, the header parsed into *info, *desc filled.  NO_ERROR: the file is decoded on the device into `need` bytes at out.
 // INSUFFICIENT_RESOURCE is the size-probe answer (out == NULL / capacity too small: the header parsed and *desc is filled); every
 // status returned before that point leaves *desc zeroed (the RGBA call: untouched), and a host allocation failure inside the parser
 // (std::bad_alloc, -3: a progressive file's coefficient array) is reported as UNKNOWN_ERROR so that it cannot be taken for it.
-int jpeg_decode_host(const void* jpeg, size_t jpeg_size, bool rgba, void* out, size_t out_capacity, uhdr_hip_image_t* desc,
+int jpeg_decode_host(const void* jpeg, size_t jpeg_size, bool rgba, bool any_sampling, void* out, size_t out_capacity, uhdr_hip_image_t* desc,
                      jpeg::DecInfo* info, size_t* need) {
   if (jpeg == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
   if (!rgba) memset(desc, 0, sizeof(*desc));
-  const int prc = jpeg::parse_header(static_cast<const uint8_t*>(jpeg), jpeg_size, info);
+  const int prc = jpeg::parse_header(static_cast<const uint8_t*>(jpeg), jpeg_size, info, any_sampling);
   if (prc == -3) return UHDR_HIP_UNKNOWN_ERROR;
   if (prc == -2) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (prc != 0 || info->w <= 0 || info->h <= 0) return UHDR_HIP_UNKNOWN_ERROR;
-  const size_t w = (size_t)info->w, h = (size_t)info->h, luma = w * h, chroma = luma / 4;
+  const size_t w = (size_t)info->w, h = (size_t)info->h, luma = w * h;
   if (w > 8192 || h > 8192) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;   // kMaxWidth / kMaxHeight, jpegdecoderhelper.h:42-43
+  const DecGeom g = dec_geom(*info);
   if (!rgba) {
-    *need = info->gray ? luma : luma + 2 * chroma;
+    *need = luma + 2 * g.cbytes;
     desc->data = out;
     desc->width = w; desc->height = h;
     desc->colorGamut = UHDR_HIP_CG_UNSPECIFIED;
     desc->luma_stride = w;
     desc->chroma_data = info->gray ? nullptr : static_cast<uint8_t*>(out) + luma;
-    desc->chroma_stride = info->gray ? 0 : w / 2;
-    desc->pixelFormat = info->gray ? UHDR_HIP_PIX_FMT_MONOCHROME : UHDR_HIP_PIX_FMT_YUV420;
+    desc->chroma_stride = g.cw;
+    desc->pixelFormat = g.fmt;
     return out == nullptr || out_capacity < *need ? UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE : UHDR_HIP_NO_ERROR;
   }
   if (info->gray) return UHDR_HIP_UNKNOWN_ERROR;   // jpegdecoderhelper.cpp:258-270: YCbCr 4:2:0 only
@@ -1688,7 +1761,7 @@ int jpeg_decode_host(const void* jpeg, size_t jpeg_size, bool rgba, void* out, s
   desc->data = out; desc->width = w; desc->height = h; desc->colorGamut = UHDR_HIP_CG_UNSPECIFIED; desc->luma_stride = w;
   desc->pixelFormat = UHDR_HIP_PIX_FMT_UNSPECIFIED;
   if (out == nullptr || out_capacity < *need) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  if ((w | h) & 1) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (g.fmt == UHDR_HIP_PIX_FMT_YUV420 && ((w | h) & 1)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   return UHDR_HIP_NO_ERROR;
 }
 
@@ -1704,9 +1777,13 @@ jpeg::DecPlane dec_plane(uint8_t* p, size_t w, size_t h) {
   q.aligned8 = (reinterpret_cast<uintptr_t>(p) % 8 == 0 && w % 8 == 0) ? 1 : 0;
   return q;
 }
-size_t dec_ycc_bytes(const jpeg::DecInfo& info) {
+size_t dec_ycc_bytes(const jpeg::DecInfo& info) { return (size_t)info.w * (size_t)info.h + 2 * dec_geom(info).cbytes; }
+void dec_planes(const jpeg::DecInfo& info, uint8_t* p, jpeg::DecPlane out[3]) {
+  const DecGeom g = dec_geom(info);
   const size_t luma = (size_t)info.w * (size_t)info.h;
-  return info.gray ? luma : luma + 2 * (luma / 4);
+  memset(out, 0, 3 * sizeof(jpeg::DecPlane));
+  out[0] = dec_plane(p, (size_t)info.w, (size_t)info.h);
+  if (!info.gray) { out[1] = dec_plane(p + luma, g.cw, g.ch); out[2] = dec_plane(p + luma + g.cbytes, g.cw, g.ch); }
 }
 // what one file holds of its round
 size_t dec_round_bytes(const jpeg::DecInfo& info, bool rgba, bool host_out, size_t need) {
@@ -1747,7 +1824,6 @@ int jpeg_decode_round(DeviceState* st, hipStream_t s, bool rgba, bool host_out, 
   for (int k = 0; k < m; ++k) {
     const int i = idx[k];
     const jpeg::DecInfo& in = info[i];
-    const size_t w = (size_t)in.w, h = (size_t)in.h, luma = w * h, chroma = luma / 4;
     infos[k] = &in;
     wss[k] = static_cast<uint8_t*>(st->pool[kDecWs]) + ws_off[k];
     if (in.scan_bytes)
@@ -1755,9 +1831,7 @@ int jpeg_decode_round(DeviceState* st, hipStream_t s, bool rgba, bool host_out, 
     // YCbCr to a device caller: straight into its buffer
     ycc[k] = rgba || host_out ? static_cast<uint8_t*>(st->pool[kDecPlanes]) + pl_off[k] : static_cast<uint8_t*>(out[i]);
     jpeg::DecPlane* p = &planes[3 * (size_t)k];
-    memset(p, 0, 3 * sizeof(jpeg::DecPlane));
-    p[0] = dec_plane(ycc[k], w, h);
-    if (!in.gray) { p[1] = dec_plane(ycc[k] + luma, w / 2, h / 2); p[2] = dec_plane(ycc[k] + luma + chroma, w / 2, h / 2); }
+    dec_planes(in, ycc[k], p);
     pl[k] = reinterpret_cast<jpeg::DecPlane (*)[3]>(p);
   }
   std::vector<int> image_rc((size_t)m, 0);
@@ -1765,8 +1839,7 @@ int jpeg_decode_round(DeviceState* st, hipStream_t s, bool rgba, bool host_out, 
   const int drc = jpeg::decode_device_batch(m, infos.data(), lay.data(), wss.data(), pl.data(), s, static_cast<uint8_t*>(st->pool[kDecScratch]), &herr,
                                             image_rc.data());
   if (drc > 0) { set_err("uhdr_hip_jpeg_decode", herr); return UHDR_HIP_UNKNOWN_ERROR; }
-  YccRgbaBatch b;
-  int nb = 0;
+  RgbaBatches b;
   std::vector<uint8_t*> res((size_t)m, nullptr);   // where each good file's output lies on the device
   for (int k = 0; k < m; ++k) {
     const int i = idx[k];
@@ -1776,14 +1849,10 @@ int jpeg_decode_round(DeviceState* st, hipStream_t s, bool rgba, bool host_out, 
       continue;
     }
     res[k] = ycc[k];
-    if (rgba) {   // libjpeg-turbo's DECODE_TO_RGBA on the planes just decoded
-      const uint32_t w = (uint32_t)info[i].w, h = (uint32_t)info[i].h;
-      const size_t luma = (size_t)w * h;
-      res[k] = host_out ? static_cast<uint8_t*>(st->pool[kDecRgba]) + rg_off[k] : static_cast<uint8_t*>(out[i]);
-      b.img[nb++] = YccRgbaImage{ycc[k], ycc[k] + luma, ycc[k] + luma + luma / 4, res[k], w, h, w, w / 2};
-    }
+    if (rgba)   // libjpeg-turbo's DECODE_TO_RGBA on the planes just decoded
+      res[k] = b.add(info[i], ycc[k], host_out ? static_cast<uint8_t*>(st->pool[kDecRgba]) + rg_off[k] : static_cast<uint8_t*>(out[i]));
   }
-  HIP_TRY(launch_ycc420_to_rgba_batch(b, nb, s));
+  HIP_TRY(b.launch(s));
   if (host_out)
     for (int k = 0; k < m; ++k)
       if (res[k] != nullptr) HIP_TRY(hipMemcpyAsync(out[idx[k]], res[k], need[idx[k]], hipMemcpyDeviceToHost, s));
@@ -1799,6 +1868,14 @@ extern "C" {
 // threads, the files of a round share every decoder launch (jpeg::decode_device_batch) and one RGBA conversion launch
 int uhdr_hip_jpeg_decode_batch(int n, const void* const* jpeg, const size_t* jpeg_size, int decode_to, void* const* out, const size_t* out_capacity,
                                uhdr_hip_image_t* descs, int* status, int mem_space, void* stream) {
+  return uhdr_hip_jpeg_decode_batch_ex(n, jpeg, jpeg_size, decode_to, out, out_capacity, descs, status, mem_space, stream, 0);
+}
+
+// the same with flags: UHDR_HIP_DECODE_ANY_SAMPLING also reads 4:4:4, 4:2:2 and 4:4:0 files (descs[i].pixelFormat names the layout)
+int uhdr_hip_jpeg_decode_batch_ex(int n, const void* const* jpeg, const size_t* jpeg_size, int decode_to, void* const* out, const size_t* out_capacity,
+                                  uhdr_hip_image_t* descs, int* status, int mem_space, void* stream, int flags) {
+  if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  const bool any_sampling = (flags & UHDR_HIP_DECODE_ANY_SAMPLING) != 0;
   if (n < 0 || (n > 0 && (jpeg == nullptr || jpeg_size == nullptr || descs == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
   if (decode_to != UHDR_HIP_DECODE_TO_RGBA && decode_to != UHDR_HIP_DECODE_TO_YCBCR) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   const bool rgba = decode_to == UHDR_HIP_DECODE_TO_RGBA;
@@ -1810,7 +1887,7 @@ int uhdr_hip_jpeg_decode_batch(int n, const void* const* jpeg, const size_t* jpe
       void* o = out != nullptr ? out[i] : nullptr;
       const size_t cap = out != nullptr && out_capacity != nullptr ? out_capacity[i] : 0;
       try {
-        st_[i] = jpeg_decode_host(jpeg[i], jpeg_size[i], rgba, o, cap, &descs[i], &info[i], &need[i]);
+        st_[i] = jpeg_decode_host(jpeg[i], jpeg_size[i], rgba, any_sampling, o, cap, &descs[i], &info[i], &need[i]);
       } catch (const std::bad_alloc&) {
         st_[i] = UHDR_HIP_UNKNOWN_ERROR;
       }
@@ -1845,12 +1922,30 @@ int uhdr_hip_jpeg_decode_rgba(const void* jpeg, size_t jpeg_size, void* out, siz
   return uhdr_hip_jpeg_decode_batch(1, &jpeg, &jpeg_size, UHDR_HIP_DECODE_TO_RGBA, &out, &out_capacity, desc, nullptr, single_mem_space(mem_space), stream);
 }
 
+// either single decode with flags (decode_to: UHDR_HIP_DECODE_TO_YCBCR / _RGBA): a batch of one file
+int uhdr_hip_jpeg_decode_ex(const void* jpeg, size_t jpeg_size, int decode_to, void* out, size_t out_capacity, uhdr_hip_image_t* desc, int mem_space,
+                            void* stream, int flags) {
+  if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (jpeg == nullptr || desc == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  return uhdr_hip_jpeg_decode_batch_ex(1, &jpeg, &jpeg_size, decode_to, &out, &out_capacity, desc, nullptr, single_mem_space(mem_space), stream, flags);
+}
+
 // JpegR::decodeJPEGR (jpegr.cpp:655-822) for n files at once.  A JPEG decode on the device is latency-bound (tens of synchronisation
 // rounds of one lane's work each, uhdr_jpeg_dec.hip), so all images of the call share every kernel launch (blockIdx.y = image) and
 // their rounds run side by side.
 int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
                                 void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
                                 int* status, int apply_mode, int mem_space, void* stream) {
+  return uhdr_hip_jpegr_decode_batch_ex(n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status,
+                                        apply_mode, mem_space, stream, 0);
+}
+
+// the same with flags: UHDR_HIP_DECODE_ANY_SAMPLING also reads files whose primary image (or gain map) is 4:4:4, 4:2:2 or 4:4:0
+int uhdr_hip_jpegr_decode_batch_ex(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
+                                   void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
+                                   int* status, int apply_mode, int mem_space, void* stream, int flags) {
+  if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  const bool any_sampling = (flags & UHDR_HIP_DECODE_ANY_SAMPLING) != 0;
   if (n < 0 || (n > 0 && (jpegr == nullptr || jpegr_size == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
   if (max_display_boost < 1.0f) return UHDR_HIP_ERROR_INVALID_DISPLAY_BOOST;                             // :666-669
   if (output_format < UHDR_HIP_OUTPUT_SDR || output_format > UHDR_HIP_OUTPUT_HDR_LINEAR_RGB_10BIT) return UHDR_HIP_ERROR_INVALID_OUTPUT_FORMAT;
@@ -1862,7 +1957,7 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
   // host time per file and touches nothing shared: the files of a batch are parsed by a few threads side by side
   on_host_threads(n, [&](int lo, int hi) {
     for (int i = lo; i < hi; ++i)
-      st_[i] = jpegr[i] == nullptr ? UHDR_HIP_ERROR_BAD_PTR : parse_jpegr_file(jpegr[i], jpegr_size[i], output_format, metadata != nullptr, &files[i]);
+      st_[i] = jpegr[i] == nullptr ? UHDR_HIP_ERROR_BAD_PTR : parse_jpegr_file(jpegr[i], jpegr_size[i], output_format, metadata != nullptr, &files[i], any_sampling);
   });
   for (int i = 0; i < n; ++i) {
     if (st_[i] != UHDR_HIP_NO_ERROR) continue;
@@ -1895,18 +1990,17 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
     if (st_[i] != UHDR_HIP_NO_ERROR) continue;
     const JpegrFile& f = files[i];
     for (int k = 0; k < per_file; ++k) {
-      const size_t w = (size_t)f.info[k].w, h = (size_t)f.info[k].h, luma = w * h, chroma = luma / 4;
       jpeg::DecLayout l;
       const size_t bytes = jpeg::dec_workspace_bytes(f.info[k], &l);
       if ((rc = pool_reserve(st, 5 * (size_t)i + k, bytes)) != 0) return rc;
-      if ((rc = pool_reserve(st, 5 * (size_t)i + 2 + k, (f.info[k].gray ? luma : luma + 2 * chroma) + 64)) != 0) return rc;
+      if ((rc = pool_reserve(st, 5 * (size_t)i + 2 + k, dec_ycc_bytes(f.info[k]) + 64)) != 0) return rc;
       uint8_t* ws = static_cast<uint8_t*>(st->pool[5 * (size_t)i + k]);
       uint8_t* out = static_cast<uint8_t*>(st->pool[5 * (size_t)i + 2 + k]);
       infos.push_back(&f.info[k]); layouts.push_back(l); wss.push_back(ws); owner.push_back(i);
       srcs.push_back(f.jpg[k] + f.info[k].scan_offset);
-      planes.push_back(dec_plane(out, w, h));
-      planes.push_back(f.info[k].gray ? jpeg::DecPlane{} : dec_plane(out + luma, w / 2, h / 2));
-      planes.push_back(f.info[k].gray ? jpeg::DecPlane{} : dec_plane(out + luma + chroma, w / 2, h / 2));
+      jpeg::DecPlane p3[3];
+      dec_planes(f.info[k], out, p3);
+      planes.insert(planes.end(), p3, p3 + 3);
     }
     if (host && (rc = pool_reserve(st, 5 * (size_t)i + 4, out_bytes[i])) != 0) return rc;
   }
@@ -1927,12 +2021,13 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
     if (image_rc[k] != 0) st_[owner[k]] = UHDR_HIP_ERROR_DECODE_ERROR;
 
   // the SDR rendition: the conversions of up to kRgbaChunk files share a launch, a host caller's copies follow it
-  YccRgbaBatch rgb;
+  RgbaBatches rgb;
   int rgb_file[kRgbaChunk], nrgb = 0;
+  uint8_t* rgb_out[kRgbaChunk];
   auto convert = [&]() {
-    HIP_TRY(launch_ycc420_to_rgba_batch(rgb, nrgb, s));
+    HIP_TRY(rgb.launch(s));
     for (int k = 0; host && k < nrgb; ++k)
-      HIP_TRY(hipMemcpyAsync(dest_data[rgb_file[k]], rgb.img[k].rgba, out_bytes[rgb_file[k]], hipMemcpyDeviceToHost, s));
+      HIP_TRY(hipMemcpyAsync(dest_data[rgb_file[k]], rgb_out[k], out_bytes[rgb_file[k]], hipMemcpyDeviceToHost, s));
     nrgb = 0;
     return UHDR_HIP_NO_ERROR;
   };
@@ -1942,12 +2037,11 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
     const JpegrFile& f = files[i];
     if (sdr) {   // libjpeg-turbo's DECODE_TO_RGBA on the planes just decoded (k_ycc420_rgba_batch)
       const uint32_t w = (uint32_t)f.info[0].w, h = (uint32_t)f.info[0].h;
-      if ((w | h) & 1) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }
+      if (dec_geom(f.info[0]).fmt == UHDR_HIP_PIX_FMT_YUV420 && ((w | h) & 1)) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }
       const uint8_t* yp = static_cast<const uint8_t*>(st->pool[5 * (size_t)i + 2]);
-      const size_t luma = (size_t)w * h;
       uint8_t* out = static_cast<uint8_t*>(host ? st->pool[5 * (size_t)i + 4] : dest_data[i]);
       rgb_file[nrgb] = i;
-      rgb.img[nrgb++] = YccRgbaImage{yp, yp + luma, yp + luma + luma / 4, out, w, h, w, w / 2};
+      rgb_out[nrgb++] = rgb.add(f.info[0], yp, out);
       if (nrgb == kRgbaChunk && (rc = convert()) != UHDR_HIP_NO_ERROR) return rc;
       dests[i].data = dest_data[i];
       continue;
@@ -1958,7 +2052,8 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
     memset(&gimg, 0, sizeof(gimg));
     uint8_t* yp = static_cast<uint8_t*>(st->pool[5 * (size_t)i + 2]);
     ydesc.data = yp; ydesc.width = w; ydesc.height = h; ydesc.luma_stride = w; ydesc.colorGamut = f.gamut;
-    ydesc.chroma_data = yp + w * h; ydesc.chroma_stride = w / 2; ydesc.pixelFormat = UHDR_HIP_PIX_FMT_YUV420;
+    const DecGeom pg = dec_geom(f.info[0]);   // (a 4:2:0 primary: chroma_stride w / 2, Cr behind (w / 2) * (h / 2) bytes, as ever)
+    ydesc.chroma_data = yp + w * h; ydesc.chroma_stride = pg.cw; ydesc.pixelFormat = pg.fmt;
     gimg.data = st->pool[5 * (size_t)i + 3]; gimg.width = gw; gimg.height = gh; gimg.luma_stride = gw; gimg.colorGamut = UHDR_HIP_CG_UNSPECIFIED;
     gimg.pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
     uhdr_hip_image_t ddev = dests[i];
@@ -1977,10 +2072,18 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
 int uhdr_hip_jpegr_decode(const void* jpegr, size_t jpegr_size, int output_format, float max_display_boost, void* dest_data,
                           size_t dest_capacity, uhdr_hip_image_t* dest, uhdr_hip_metadata_t* metadata, int apply_mode,
                           int mem_space, void* stream) {
+  return uhdr_hip_jpegr_decode_ex(jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dest, metadata, apply_mode,
+                                  mem_space, stream, 0);
+}
+
+int uhdr_hip_jpegr_decode_ex(const void* jpegr, size_t jpegr_size, int output_format, float max_display_boost, void* dest_data,
+                             size_t dest_capacity, uhdr_hip_image_t* dest, uhdr_hip_metadata_t* metadata, int apply_mode,
+                             int mem_space, void* stream, int flags) {
+  if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (jpegr == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                   // :658-661
   if (dest == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                    // :662-665
-  return uhdr_hip_jpegr_decode_batch(1, &jpegr, &jpegr_size, output_format, max_display_boost, &dest_data, &dest_capacity, dest, metadata, nullptr,
-                                     apply_mode, mem_space, stream);
+  return uhdr_hip_jpegr_decode_batch_ex(1, &jpegr, &jpegr_size, output_format, max_display_boost, &dest_data, &dest_capacity, dest, metadata, nullptr,
+                                        apply_mode, mem_space, stream, flags);
 }
 
 int uhdr_hip_jpegr_append_gainmap(const void* primary_jpeg, size_t primary_size, const void* gainmap_jpeg, size_t gainmap_size,
@@ -2332,7 +2435,7 @@ int api3_check(const uhdr_hip_image_t* p010, const void* sdr_jpeg, size_t sdr_jp
   uhdr_hip_image_t desc;
   size_t need = 0;
   try {
-    rc = jpeg_decode_host(sdr_jpeg, sdr_jpeg_size, false, nullptr, 0, &desc, info, &need);
+    rc = jpeg_decode_host(sdr_jpeg, sdr_jpeg_size, false, false, nullptr, 0, &desc, info, &need);
   } catch (const std::bad_alloc&) {
     rc = UHDR_HIP_UNKNOWN_ERROR;
   }
@@ -3132,7 +3235,7 @@ int uhdr_hip_apply_gainmap(const uhdr_hip_image_t* yuv, const uhdr_hip_image_t* 
   if (ss == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
   hipStream_t s = static_cast<hipStream_t>(stream);
   uhdr_hip_image_t dy, dm = *map, dd = *dest;
-  if ((rc = stage_yuv420_in(ss, 0, *yuv, &dy, s)) != 0) return rc;
+  if ((rc = stage_ycbcr_in(ss, 0, *yuv, &dy, s)) != 0) return rc;
   const size_t map_bytes = map->width * map->height;  // the reference reads the map with stride == width
   if ((rc = stage_reserve(ss, 4, map_bytes)) != 0) return rc;
   HIP_TRY(hipMemcpyAsync(ss->stage[4], map->data, map_bytes, hipMemcpyHostToDevice, s));

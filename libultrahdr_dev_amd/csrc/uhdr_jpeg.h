@@ -77,6 +77,9 @@ struct DecPlane {
 };
 struct DecInfo {
   int w = 0, h = 0, gray = 0;
+  // luma sampling factors of a three-component frame (both chroma components are 1x1): 2x2 = 4:2:0, 1x1 = 4:4:4, 2x1 = 4:2:2,
+  // 1x2 = 4:4:0.  An MCU is hs * vs luma blocks (rows of hs) followed by Cb and Cr; a single plane: 1x1 and one block.
+  int hs = 2, vs = 2;
   uint16_t quant[3][64] = {};     // per component, zigzag order (as stored in the file)
   DecTables tables = {};
   int td[2] = {0, 0}, ta[2] = {0, 0};
@@ -96,6 +99,7 @@ struct DecLayout {
   size_t src, raw, lut, adv, st_a, st_b, dirty_a, dirty_b, coef;
   size_t sub_start, sub_end, sub_key;   // restart-interval files only
   uint32_t nchunks, nsub_max, nblk, mcus_x;
+  uint32_t hs, vs;           // luma blocks per MCU row / column (a single plane: 1, 1)
 };
 struct DecJob {
   const uint32_t* raw;       // unstuffed entropy-coded bits, big-endian words, zero padded
@@ -109,15 +113,19 @@ struct DecJob {
   const uint32_t* sub_key;
   uint32_t restart_blocks;
   int gray;
+  uint32_t hs, vs;           // luma blocks per MCU row / column
+  uint32_t bpm, chroma_at;   // blocks per MCU (hs * vs + 2; a single plane: 1) and the first chroma block in it (a single plane: 0xFF, never reached)
   uint32_t dc_tbl[2], ac_tbl[2];
   int16_t* coef;             // nblk x 64, zigzag order
   DecPlane plane[3];
   uint16_t quant[3][64];
 };
-// 0 ok, -1 malformed, -2 outside what this decoder (or the reference: sampling) supports
-int parse_header(const uint8_t* jpg, size_t n, DecInfo* info);
+// 0 ok, -1 malformed, -2 outside what this decoder (or the reference: sampling) supports.  any_sampling false: three components
+// must be 4:2:0, as in the reference; true: luma 1x1, 2x1, 1x2 or 2x2 over 1x1 chroma (DecInfo::hs, vs)
+int parse_header(const uint8_t* jpg, size_t n, DecInfo* info, bool any_sampling = false);
 // the same for a progressive file, all scans decoded (parse_header calls it when it meets SOF2)
-int decode_progressive(const uint8_t* jpg, size_t n, DecInfo* info);
+int decode_progressive(const uint8_t* jpg, size_t n, DecInfo* info, bool any_sampling = false);
+bool sampling_accepted(int nc, const int hs[3], const int vs[3], bool any_sampling);   // what both parsers accept of a frame header
 // the walk over an entropy-coded segment on its own (the container scan uses it): position of the 0xFF of the first marker at or
 // behind `e` that is neither a stuffed zero, a fill byte nor an RSTn; n if there is none
 size_t skip_entropy_coded(const uint8_t* p, size_t e, size_t n);

@@ -34,7 +34,15 @@
 // JPEGs and a server decodes many files at once, and since a decode is latency-bound the images of a call cost little more than one.
 // Progressive files: their scans are entropy-decoded on the host (uhdr_jpeg_prog.cpp) and join the batch at the coefficient blocks
 // (DC prefix sum + IDCT here).  Arithmetic-coded / lossless files return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; samplings other than
-// 4:2:0 / grayscale fail as they do in the reference.
+// 4:2:0 / grayscale fail as they do in the reference -- unless the caller opts in (UHDR_HIP_DECODE_ANY_SAMPLING): then luma 1x1
+// (4:4:4), 2x1 (4:2:2) and 1x2 (4:4:0) over 1x1 chroma decode too.  The only sampling-specific state is the block-in-MCU index, so
+// the MCU's shape is per-image data (DecJob::hs, vs, bpm = hs * vs + 2, chroma_at = hs * vs): the passes pick the table by
+// c >= chroma_at and wrap the index at bpm, the DC scan keys a block's component by b % bpm, the IDCT places luma block k of MCU
+// (mr, mc) at block (mr * vs + k / hs, mc * hs + k % hs) and crops each plane to its own extent.  The convergence and round-limit
+// logic is untouched by this.  What a 3-block (4:4:4) or 4-block (4:2:2 / 4:4:0) MCU does to the number of rounds is unmeasured (there
+// is no round counter); measured is the time: a 4K quality-95 frame decodes in 382 us as 4:4:4 and 428 us as 4:2:2 beside 682 us as
+// 4:2:0, planes equal to libjpeg-turbo's (profiles/r06_jpeg_sampling.txt) -- fewer states for the block-in-MCU index to fall in
+// step over is a hypothesis for that, not a finding.
 #include <hip/hip_runtime.h>
 #include <cstring>
 
@@ -273,12 +281,12 @@ struct Reader {
 // rare long-code lookup and the window refill.  A bit pattern that is no code (only possible off-sync, or in a corrupt file)
 // consumes one bit -- any deterministic rule will do for the synchronisation -- and is reported (returns false), as is a run
 // that leaves the block.
-// gray: the job's field by value -- read through the job it would be loaded again after every coefficient store (the compiler
-// must assume the store hit it), and the wait for that load would sit out the store.
-__device__ __forceinline__ bool step_coef(const bool gray, const LongCodes& lc, const uint32_t (*s_lut)[1u << kFastBits], Reader& rd, DState& s,
+// bpm, chroma_at: the job's fields by value -- read through the job they would be loaded again after every coefficient store (the
+// compiler must assume the store hit them), and the wait for that load would sit out the store.
+__device__ __forceinline__ bool step_coef(const uint32_t bpm, const uint32_t chroma_at, const LongCodes& lc, const uint32_t (*s_lut)[1u << kFastBits], Reader& rd, DState& s,
                                           bool& block_done, uint32_t& zpos, int& val, bool& has) {
   const uint32_t c = s.cz >> 8, z = s.cz & 0xFFu;
-  const uint32_t tb = (gray ? 0u : (c >= 4u ? 2u : 0u)) + (z != 0u ? 1u : 0u);   // slots: 0 DC luma, 1 AC luma, 2 DC chroma, 3 AC chroma
+  const uint32_t tb = (c >= chroma_at ? 2u : 0u) + (z != 0u ? 1u : 0u);   // slots: 0 DC luma, 1 AC luma, 2 DC chroma, 3 AC chroma
   const uint32_t sh = s.p - rd.base;
   const uint64_t w = rd.win;
   const uint32_t peek = (uint32_t)(w >> (48u - sh)) & 0xFFFFu;
@@ -298,7 +306,6 @@ __device__ __forceinline__ bool step_coef(const bool gray, const LongCodes& lc, 
   uint32_t nz = z + dz;
   block_done = nz >= 64u;
   nz = block_done ? 0u : nz;
-  const uint32_t bpm = gray ? 1u : 6u;
   const uint32_t nc = block_done ? (c + 1u == bpm ? 0u : c + 1u) : c;
   s.cz = (nc << 8) | nz;
   return ok;
@@ -355,7 +362,6 @@ __device__ __forceinline__ uint32_t stage_bits(const DecJob& j, uint32_t i0, uin
 __device__ __forceinline__ void decode_positions(const DecJob& j, const LongCodes& lc, const uint32_t (*s_adv)[1u << kFastBits], const uint32_t* s_bits,
                                                  uint32_t w0, uint32_t i, DState& s, uint32_t& nb) {
   const uint32_t end = sub_end_bit(j, i);
-  const bool gray = j.gray != 0;
   nb = 0;
   if (!((s.p >> 5) >= w0 && (s.p >> 5) - w0 + 3u < kStageWords && end > s.p && end - s.p <= kSubBits + 32u)) return;
   const uint32_t* next_word = s_bits + ((s.p >> 5) - w0);
@@ -365,7 +371,7 @@ __device__ __forceinline__ void decode_positions(const DecJob& j, const LongCode
   int32_t down = 48 - (int32_t)(s.p & 31u);            // win >> down: the next 16 bits of the stream in bits 15..0; 17 <= down <= 48
   int32_t left = (int32_t)(end - s.p);                 // > 0 while the subsequence's end has not been crossed
   uint32_t c = s.cz >> 8, z = s.cz & 0xFFu;
-  const uint32_t bpm = gray ? 1u : 6u, chroma_at = gray ? 0xFFu : 4u;
+  const uint32_t bpm = j.bpm, chroma_at = j.chroma_at;   // 4:2:0: 6 and 4; a single plane: 1 and never
   const char* tables = reinterpret_cast<const char*>(&s_adv[0][0]);
   constexpr uint32_t kIndexMask = (1u << (kFastBits + 2u)) - 4u;   // byte offset of a 32-bit entry inside one table
   // The loop carries the table entry of the NEXT symbol: looked up at the end of a step, in the AC table of the same component
@@ -540,10 +546,10 @@ __device__ __forceinline__ void write_body(const DecJob& j, const DecTables& tab
   // A global store is waited for by nothing in this loop (which is why the loop must not load from memory either).
   typedef __attribute__((address_space(1))) int16_t GlobalI16;
   GlobalI16* coef = (GlobalI16*)j.coef;
-  const bool gray = j.gray != 0;
+  const uint32_t bpm = j.bpm, chroma_at = j.chroma_at;
   bool bad = false;
   while (s.p < end && blk < blk_end) {   // (stops in front of the 1-bits that pad an interval to its byte boundary)
-    const bool ok = step_coef(gray, s_long, s_lut, rd, s, bd, zp, v, has);
+    const bool ok = step_coef(bpm, chroma_at, s_long, s_lut, rd, s, bd, zp, v, has);
     bad = bad || !ok;
     if (has) coef[(size_t)blk * 64u + zp] = (int16_t)v;
     blk += bd;
@@ -598,16 +604,25 @@ __device__ __forceinline__ void idct8(int (&d)[64], int base, int stride) {   //
   d[base + 3 * stride] = dscale(tmp13 + tmp0, sh); d[base + 4 * stride] = dscale(tmp13 - tmp0, sh);
 }
 
+// the MCU block b lies in.  bpm is 1, 3, 4 or 6: every division is by a constant (a multiplication, as 4:2:0's always was) and the
+// choice among them a select -- straight-line code, so that the DC scan's functor, which rocprim unrolls over a thread's items, keeps
+// the loads of all its items in flight together (a branch here, or a division by a run-time value, puts a wait between them)
+__host__ __device__ __forceinline__ uint32_t mcu_of(uint32_t b, uint32_t bpm) {
+  const uint32_t q6 = b / 6u, q3 = b / 3u, q4 = b >> 2;
+  return bpm == 6u ? q6 : (bpm == 4u ? q4 : (bpm == 3u ? q3 : b));
+}
+
 __device__ __forceinline__ void idct_body(const DecJob& j, const Dc3* dc) {
   const uint32_t b = blockIdx.x * 128u + threadIdx.x;
   if (b >= j.nblk) return;
   int comp, br, bc;
   if (j.gray) { comp = 0; br = (int)(b / j.mcus_x); bc = (int)(b - (uint32_t)br * j.mcus_x); }
   else {
-    const uint32_t mcu = b / 6u, k = b - mcu * 6u;
+    // luma block k of MCU (mr, mc) is block (mr * vs + k / hs, mc * hs + k % hs) of its plane (hs, vs: 1 or 2), chroma is (mr, mc)
+    const uint32_t mcu = mcu_of(b, j.bpm), k = b - mcu * j.bpm;
     const int mr = (int)(mcu / j.mcus_x), mc = (int)(mcu - (uint32_t)mr * j.mcus_x);
-    if (k < 4u) { comp = 0; br = 2 * mr + (int)(k >> 1); bc = 2 * mc + (int)(k & 1u); }
-    else { comp = (int)k - 3; br = mr; bc = mc; }
+    if (k < j.chroma_at) { comp = 0; br = (int)j.vs * mr + (int)(k >> (j.hs - 1u)); bc = (int)j.hs * mc + (int)(k & (j.hs - 1u)); }
+    else { comp = (int)(k - j.chroma_at) + 1; br = mr; bc = mc; }
   }
   const DecPlane& pl = j.plane[comp];
   if (br * 8 >= pl.h || bc * 8 >= pl.w) return;      // a dummy block of the encoder: nothing of it is inside the image
@@ -688,7 +703,8 @@ struct DcPickBatch {   // the DC difference of block g of the concatenation, in 
   __host__ __device__ Dc3 operator()(uint32_t g) const {
     const uint32_t img = seg(g), b = g - seg.off[img];
     const DecJob& j = jobs[img].j;
-    const int c = j.gray ? 0 : ((b % 6u) < 4u ? 0 : (int)(b % 6u) - 3);
+    const uint32_t k = b - mcu_of(b, j.bpm) * j.bpm;   // a block's component goes by its place in the MCU
+    const int c = k < j.chroma_at ? 0 : (int)(k - j.chroma_at) + 1;
     Dc3 r; r.v[0] = r.v[1] = r.v[2] = 0;
     r.v[c] = (int)j.coef[(size_t)b * 64u];
     return r;
@@ -741,9 +757,10 @@ __global__ void __launch_bounds__(128) k_jd_idct_multi(const DecBatchJob* jobs) 
 size_t dec_workspace_bytes(const DecInfo& info, DecLayout* l) {
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
   const uint32_t w = (uint32_t)info.w, h = (uint32_t)info.h;
-  l->mcus_x = info.gray ? (w + 7) / 8 : (w + 15) / 16;
-  const uint32_t mcus_y = info.gray ? (h + 7) / 8 : (h + 15) / 16;
-  l->nblk = l->mcus_x * mcus_y * (info.gray ? 1u : 6u);
+  l->hs = info.gray ? 1u : (uint32_t)info.hs; l->vs = info.gray ? 1u : (uint32_t)info.vs;
+  l->mcus_x = (w + 8u * l->hs - 1u) / (8u * l->hs);
+  const uint32_t mcus_y = (h + 8u * l->vs - 1u) / (8u * l->vs);
+  l->nblk = l->mcus_x * mcus_y * (info.gray ? 1u : l->hs * l->vs + 2u);
   const size_t nbytes = info.scan_bytes;
   l->nchunks = (uint32_t)((nbytes + kUnstuffChunk - 1) / kUnstuffChunk);
   const uint32_t nint = (uint32_t)info.interval_start.size();   // 0 without restart intervals; each interval may end in a short subsequence
@@ -853,6 +870,8 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
     j.total_bits = in.raw_bytes * 8u;
     j.nsub = (j.total_bits + kSubBits - 1u) / kSubBits;
     j.gray = in.gray; j.nblk = L.nblk; j.mcus_x = L.mcus_x;
+    j.hs = L.hs; j.vs = L.vs;
+    j.bpm = in.gray ? 1u : L.hs * L.vs + 2u; j.chroma_at = in.gray ? 0xFFu : L.hs * L.vs;
     j.dc_tbl[0] = 0; j.ac_tbl[0] = 1; j.dc_tbl[1] = 2; j.ac_tbl[1] = 3;
     j.coef = reinterpret_cast<int16_t*>(w + L.coef);
     for (int c = 0; c < 3; ++c) { j.plane[c] = (*planes[k])[c]; memcpy(j.quant[c], in.quant[c], sizeof(j.quant[c])); }
@@ -874,7 +893,7 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
         j.sub_start = reinterpret_cast<const uint32_t*>(w + L.sub_start);
         j.sub_end = reinterpret_cast<const uint32_t*>(w + L.sub_end);
         j.sub_key = reinterpret_cast<const uint32_t*>(w + L.sub_key);
-        j.restart_blocks = in.restart_interval * (in.gray ? 1u : 6u);
+        j.restart_blocks = in.restart_interval * j.bpm;
       }
     }
     // a progressive file arrives with its coefficients decoded (uhdr_jpeg_prog.cpp): no segment, no subsequences -- every

@@ -114,17 +114,26 @@ size_t skip_entropy_coded(const uint8_t* p, size_t e, size_t n) {
   }
 }
 
-static int parse_header_impl(const uint8_t* jpg, size_t n, DecInfo* info);
+// The samplings a frame may have.  One component: any factors (its MCU is one block).  Three: 4:2:0, which is all the reference
+// reads; with any_sampling also luma 1x1 (4:4:4), 2x1 (4:2:2) or 1x2 (4:4:0) over 1x1 chroma.
+bool sampling_accepted(int nc, const int hs[3], const int vs[3], bool any_sampling) {
+  if (nc == 1) return true;
+  if (!(hs[1] == 1 && vs[1] == 1 && hs[2] == 1 && vs[2] == 1)) return false;
+  if (hs[0] == 2 && vs[0] == 2) return true;
+  return any_sampling && (hs[0] == 1 || hs[0] == 2) && (vs[0] == 1 || vs[0] == 2);
+}
+
+static int parse_header_impl(const uint8_t* jpg, size_t n, DecInfo* info, bool any_sampling);
 // 0 ok, -1 malformed, -2 outside what is supported, -3 out of memory (the vectors of DecInfo; a progressive frame's coefficients):
 // the callers are extern "C" entry points, nothing may throw through them
-int parse_header(const uint8_t* jpg, size_t n, DecInfo* info) {
+int parse_header(const uint8_t* jpg, size_t n, DecInfo* info, bool any_sampling) {
   try {
-    return parse_header_impl(jpg, n, info);
+    return parse_header_impl(jpg, n, info, any_sampling);
   } catch (const std::bad_alloc&) {
     return -3;
   }
 }
-static int parse_header_impl(const uint8_t* jpg, size_t n, DecInfo* info) {
+static int parse_header_impl(const uint8_t* jpg, size_t n, DecInfo* info, bool any_sampling) {
   if (jpg == nullptr || n < 4 || jpg[0] != 0xFF || jpg[1] != 0xD8) return -1;
   *info = DecInfo();
   static const uint8_t nat[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -182,7 +191,7 @@ static int parse_header_impl(const uint8_t* jpg, size_t n, DecInfo* info) {
       if (len < (size_t)(8 + 3 * nc)) return -1;
       for (int c = 0; c < nc; ++c) { cid[c] = seg[6 + 3 * c]; hs[c] = seg[7 + 3 * c] >> 4; vs[c] = seg[7 + 3 * c] & 15; tq[c] = seg[8 + 3 * c]; }
     } else if (m == 0xC2) {
-      return decode_progressive(jpg, n, info);   // every scan on the host, the device takes over at the coefficients (uhdr_jpeg_prog.cpp)
+      return decode_progressive(jpg, n, info, any_sampling);   // every scan on the host, the device takes over at the coefficients (uhdr_jpeg_prog.cpp)
     } else if (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
       return -2;   // lossless, arithmetic, hierarchical: libjpeg reads some of these, this decoder does not
     } else if (m == 0xDD) {
@@ -191,7 +200,8 @@ static int parse_header_impl(const uint8_t* jpg, size_t n, DecInfo* info) {
     } else if (m == 0xDA) {
       if (nc == 0 || len < (size_t)(6 + 2 * nc) || seg[0] != nc) return -2;   // (the length first: seg[0] of a 2-byte segment at the end of the file is past the buffer)
       info->gray = nc == 1;
-      if (!info->gray && !(hs[0] == 2 && vs[0] == 2 && hs[1] == 1 && vs[1] == 1 && hs[2] == 1 && vs[2] == 1)) return -1;   // the reference fails too, jpegdecoderhelper.cpp:283-289
+      if (!sampling_accepted(nc, hs, vs, any_sampling)) return -1;   // (4:2:0 only: the reference fails too, jpegdecoderhelper.cpp:283-289)
+      info->hs = info->gray ? 1 : hs[0]; info->vs = info->gray ? 1 : vs[0];
       if (info->w <= 0 || info->h <= 0) return -1;
       for (int c = 0; c < nc; ++c) {
         if (seg[1 + 2 * c] != cid[c]) return -2;
@@ -231,8 +241,7 @@ static int parse_header_impl(const uint8_t* jpg, size_t n, DecInfo* info) {
       info->scan_bytes = e - info->scan_offset;
       info->raw_bytes = (uint32_t)(info->scan_bytes - stuffed - 2u * markers);
       if (info->restart_interval != 0) {   // every interval but the last holds restart_interval MCUs: their number is fixed by the image size
-        const uint64_t mcus = info->gray ? (uint64_t)((info->w + 7) / 8) * (uint64_t)((info->h + 7) / 8)
-                                         : (uint64_t)((info->w + 15) / 16) * (uint64_t)((info->h + 15) / 16);
+        const uint64_t mcus = (uint64_t)((info->w + 8 * info->hs - 1) / (8 * info->hs)) * (uint64_t)((info->h + 8 * info->vs - 1) / (8 * info->vs));
         if (info->interval_start.size() != (mcus + info->restart_interval - 1) / info->restart_interval) return -1;
       }
       return 0;

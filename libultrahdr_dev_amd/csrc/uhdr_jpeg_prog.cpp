@@ -12,7 +12,8 @@
 // included: the same warnings-become-zeros tolerance is not reproduced -- a scan that violates the progression rules fails).
 //
 // Output (DecInfo): w, h, gray, quant (as latched when a component's first scan starts, like jdinput.c's latch_quant_tables),
-// coef = nblk x 64 coefficients in zigzag order, blocks in the baseline decoder's order (4:2:0: Y00 Y01 Y10 Y11 Cb Cr per MCU),
+// coef = nblk x 64 coefficients in zigzag order, blocks in the baseline decoder's order (per MCU: its hs x vs luma blocks row by
+// row, then Cb, Cr -- 4:2:0: Y00 Y01 Y10 Y11 Cb Cr; the other samplings only with any_sampling, as in parse_header),
 // the DC term as the DIFFERENCE to the previous block of its component in that order (what a baseline scan would carry and the
 // device's prefix sum undoes).  Complete files only: a file whose scans leave a coefficient short of full precision is what
 // libjpeg smooths across blocks (jdcoefct.c: smoothing_ok); it is refused (-2).
@@ -107,7 +108,7 @@ inline uint32_t rd16(const uint8_t* p) { return ((uint32_t)p[0] << 8) | p[1]; }
 }  // namespace
 
 // 0 ok, -1 malformed, -2 outside what is supported
-int decode_progressive(const uint8_t* jpg, size_t n, DecInfo* info) {
+int decode_progressive(const uint8_t* jpg, size_t n, DecInfo* info, bool any_sampling) {
   if (n < 4 || jpg[0] != 0xFF || jpg[1] != 0xD8) return -1;
   uint16_t quant[4][64];
   bool have_q[4] = {false, false, false, false};
@@ -118,6 +119,7 @@ int decode_progressive(const uint8_t* jpg, size_t n, DecInfo* info) {
   uint32_t restart_interval = 0;
   int w = 0, h = 0;
   uint32_t mcus_x = 0, mcus_y = 0, nblk = 0;
+  uint32_t lh = 1, lv = 1, bpm = 1;                // luma blocks per MCU row / column, blocks per MCU
   uint32_t bw[3] = {0, 0, 0}, bh[3] = {0, 0, 0};   // blocks a non-interleaved scan of the component covers
   // coef_bits[c][k]: -1 = not seen yet, else the Al the coefficient is known down to (jdphuff.c)
   int coef_bits[3][64];
@@ -168,16 +170,18 @@ int decode_progressive(const uint8_t* jpg, size_t n, DecInfo* info) {
       if (nc != 1 && nc != 3) return -2;
       if (len < (size_t)(8 + 3 * nc) || w <= 0 || h <= 0) return -1;
       for (int c = 0; c < nc; ++c) { cid[c] = seg[6 + 3 * c]; hs[c] = seg[7 + 3 * c] >> 4; vs[c] = seg[7 + 3 * c] & 15; tq[c] = seg[8 + 3 * c]; if (tq[c] > 3) return -1; }
-      if (nc == 3 && !(hs[0] == 2 && vs[0] == 2 && hs[1] == 1 && vs[1] == 1 && hs[2] == 1 && vs[2] == 1)) return -1;   // the reference fails too (:283-289)
+      if (!sampling_accepted(nc, hs, vs, any_sampling)) return -1;   // (4:2:0 only: the reference fails too, :283-289)
       // (a single-component frame: sampling factors are irrelevant, every scan is non-interleaved -- T.81 A.2.2)
       info->w = w; info->h = h; info->gray = nc == 1;
+      if (nc == 3) { lh = (uint32_t)hs[0]; lv = (uint32_t)vs[0]; bpm = lh * lv + 2u; }
+      info->hs = (int)lh; info->vs = (int)lv;
       if (w > 65535 || h > 65535) return -1;
       if (w > 8192 || h > 8192) { info->progressive = true; info->scan_offset = 0; info->scan_bytes = 0; return 0; }   // the caller refuses the size (kMaxWidth)
-      mcus_x = (uint32_t)(nc == 1 ? (w + 7) / 8 : (w + 15) / 16);
-      mcus_y = (uint32_t)(nc == 1 ? (h + 7) / 8 : (h + 15) / 16);
-      nblk = mcus_x * mcus_y * (nc == 1 ? 1u : 6u);
+      mcus_x = ((uint32_t)w + 8u * lh - 1u) / (8u * lh);
+      mcus_y = ((uint32_t)h + 8u * lv - 1u) / (8u * lv);
+      nblk = mcus_x * mcus_y * bpm;
       bw[0] = (uint32_t)((w + 7) / 8); bh[0] = (uint32_t)((h + 7) / 8);
-      bw[1] = bw[2] = (uint32_t)(((w + 1) / 2 + 7) / 8); bh[1] = bh[2] = (uint32_t)(((h + 1) / 2 + 7) / 8);
+      bw[1] = bw[2] = mcus_x; bh[1] = bh[2] = mcus_y;   // (libjpeg's width_in_blocks of a 1x1 component: ceil(w / (8 hs)))
       frame = true;   // (the coefficient array -- up to 200 MB for an 8192 x 8192 frame -- is allocated at the first valid scan header)
     } else if (m == 0xC0 || m == 0xC1 || (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC)) {
       return -2;
@@ -230,8 +234,8 @@ int decode_progressive(const uint8_t* jpg, size_t n, DecInfo* info) {
       const int p1 = 1 << Al, m1 = -(1 << Al);
       auto block_of = [&](int c, uint32_t br_, uint32_t bc_) -> int16_t* {   // component c's block (row, col) in the device decoder's order
         if (nc == 1) return coef.data() + ((size_t)br_ * mcus_x + bc_) * 64u;
-        if (c == 0) return coef.data() + (((size_t)(br_ >> 1) * mcus_x + (bc_ >> 1)) * 6u + ((br_ & 1u) * 2u + (bc_ & 1u))) * 64u;
-        return coef.data() + (((size_t)br_ * mcus_x + bc_) * 6u + 3u + (uint32_t)c) * 64u;
+        if (c == 0) return coef.data() + (((size_t)(br_ / lv) * mcus_x + bc_ / lh) * bpm + ((br_ % lv) * lh + bc_ % lh)) * 64u;
+        return coef.data() + (((size_t)br_ * mcus_x + bc_) * bpm + lh * lv - 1u + (uint32_t)c) * 64u;
       };
       for (uint32_t u = 0; u < total_units; ++u) {
         if (restart_interval != 0 && until_rst == 0) {
@@ -246,10 +250,10 @@ int decode_progressive(const uint8_t* jpg, size_t n, DecInfo* info) {
         if (is_dc) {
           for (int i = 0; i < ns; ++i) {
             const int c = sc[i];
-            const uint32_t nb = interleaved ? (c == 0 ? 4u : 1u) : 1u;
+            const uint32_t nb = interleaved && c == 0 ? lh * lv : 1u;
             for (uint32_t k = 0; k < nb; ++k) {
               uint32_t rr = ur, cc = uc;
-              if (interleaved && c == 0) { rr = 2 * ur + (k >> 1); cc = 2 * uc + (k & 1u); }
+              if (interleaved && c == 0) { rr = lv * ur + k / lh; cc = lh * uc + k % lh; }
               int16_t* blk = block_of(c, rr, cc);
               if (Ah == 0) {
                 const int s = dc_t[i].decode(br);
@@ -344,7 +348,7 @@ int decode_progressive(const uint8_t* jpg, size_t n, DecInfo* info) {
   {
     int prev[3] = {0, 0, 0};
     for (uint32_t b = 0; b < nblk; ++b) {
-      const int c = nc == 1 ? 0 : ((b % 6u) < 4u ? 0 : (int)(b % 6u) - 3);
+      const int c = (b % bpm) < lh * lv ? 0 : (int)(b % bpm) - (int)(lh * lv) + 1;
       int16_t* blk = coef.data() + (size_t)b * 64u;
       const int v = blk[0];
       blk[0] = (int16_t)(uint16_t)((unsigned)v - (unsigned)prev[c]);   // modulo 2^16: k_jd_idct reads the running sum as int16

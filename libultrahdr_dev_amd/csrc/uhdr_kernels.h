@@ -170,6 +170,9 @@ struct AppImage {
   const uint8_t* map;
   void* dst;
   uint32_t y_stride, c_stride;
+  // pixel (x, y) takes the chroma sample (x >> csx, y >> csy): 1, 1 for 4:2:0; 0, 0 for 4:4:4; 1, 0 for 4:2:2; 0, 1 for 4:4:0.  Only
+  // the per-pixel kernels read them: the scale-4 kernels are 4:2:0's (app_fast_s4)
+  uint32_t csx, csy;
 };
 struct AppBatch {
   AppImage img[kMaxChunk];
@@ -290,6 +293,17 @@ struct YccRgbaBatch {
 };
 static_assert(sizeof(YccRgbaBatch) <= 4096, "k_ycc420_rgba_batch's kernel arguments exceed the kernarg segment");
 hipError_t launch_ycc420_to_rgba_batch(const YccRgbaBatch& b, int n, hipStream_t s);
+// the same for decoded 4:4:4, 4:2:2 and 4:4:0 planes of any size, odd ones included (k_yccx_rgba_batch); an image's sampling is
+// (hs, vs) = the luma samples per chroma sample across and down, its chroma planes are ceil(w / hs) x ceil(h / vs)
+struct YccxRgbaImage {
+  YccRgbaImage im;
+  uint32_t hs, vs;
+};
+struct YccxRgbaBatch {
+  YccxRgbaImage img[kRgbaChunk];
+};
+static_assert(sizeof(YccxRgbaBatch) <= 4096, "k_yccx_rgba_batch's kernel arguments exceed the kernarg segment");
+hipError_t launch_yccx_to_rgba_batch(const YccxRgbaBatch& b, int n, hipStream_t s);
 hipError_t upload_idw4(const float* tables /* 4*64 floats */);
 hipError_t launch_effect(const FxJobs& j, hipStream_t s);
 // dev_jobs: n descriptors in DEVICE memory (a round is not bounded by the kernarg segment); host_jobs: the same descriptors, read

@@ -1800,7 +1800,7 @@ struct PxIn { float yf, u, v, gain; };
 __device__ __forceinline__ PxIn px_inputs(const AppConsts& c, const AppImage& im, uint32_t x, uint32_t y) {
   PxIn in;
   in.yf = (float)im.y[(size_t)y * im.y_stride + x] * k255;
-  const size_t ci = (size_t)(y >> 1) * im.c_stride + (x >> 1);
+  const size_t ci = (size_t)(y >> im.csy) * im.c_stride + (x >> im.csx);   // 4:2:0: (x >> 1, y >> 1), as getYuv420Pixel
   in.u = (float)((int)im.u[ci] - 128) * k255;
   in.v = (float)((int)im.v[ci] - 128) * k255;
 
@@ -2266,7 +2266,7 @@ __global__ void __launch_bounds__(256) k_apply_lut(const AppConsts c, const AppB
     const uint32_t y = (uint32_t)(idx / c.width);
     const uint32_t x = (uint32_t)(idx - (size_t)y * c.width);
     const float yf = (float)im.y[(size_t)y * im.y_stride + x] * k255;
-    const size_t ci = (size_t)(y >> 1) * im.c_stride + (x >> 1);
+    const size_t ci = (size_t)(y >> im.csy) * im.c_stride + (x >> im.csx);
     const float u = (float)((int)im.u[ci] - 128) * k255;
     const float v = (float)((int)im.v[ci] - 128) * k255;
     // sampleMap (gainmapmath.cpp:686-720), as in k_apply_px
@@ -2585,6 +2585,15 @@ hipError_t launch_apply(const AppConsts& c, const AppBatch& b, int n, int fmt, i
 // One thread per horizontal pixel pair (they share the centre chroma column).  Restated in oracle/jpeg_oracle.c and pinned there
 // against libjpeg-turbo itself (Pillow's).
 // =================================================================================================
+// libjpeg-turbo's conversion of one pixel: R, G, B in bytes 0..2, alpha 0xFF
+__device__ __forceinline__ uint32_t ycc_rgba_px(int y, int cb, int cr) {
+  const int xb = cb - 128, xr = cr - 128;
+  int R = y + ((91881 * xr + 32768) >> 16);
+  int G = y + ((-22554 * xb + 32768 - 46802 * xr) >> 16);
+  int B = y + ((116130 * xb + 32768) >> 16);
+  R = min(max(R, 0), 255); G = min(max(G, 0), 255); B = min(max(B, 0), 255);
+  return (uint32_t)R | ((uint32_t)G << 8) | ((uint32_t)B << 16) | 0xFF000000u;
+}
 // the pixel pair (2c, 2c+1) of row r
 __device__ __forceinline__ void ycc420_rgba_pair(const uint8_t* __restrict__ yp, const uint8_t* __restrict__ cbp, const uint8_t* __restrict__ crp,
                                                  uint32_t w, uint32_t h, uint32_t ys, uint32_t cs, uint8_t* __restrict__ rgba, uint32_t c, uint32_t r) {
@@ -2606,15 +2615,73 @@ __device__ __forceinline__ void ycc420_rgba_pair(const uint8_t* __restrict__ yp,
   const uint32_t y2 = (uint32_t)yrow[0] | ((uint32_t)yrow[1] << 8);
   uint32_t px[2];
 #pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int y = (int)((y2 >> (8 * k)) & 0xffu), xb = cb[k] - 128, xr = cr[k] - 128;
-    int R = y + ((91881 * xr + 32768) >> 16);
-    int G = y + ((-22554 * xb + 32768 - 46802 * xr) >> 16);
-    int B = y + ((116130 * xb + 32768) >> 16);
-    R = min(max(R, 0), 255); G = min(max(G, 0), 255); B = min(max(B, 0), 255);
-    px[k] = (uint32_t)R | ((uint32_t)G << 8) | ((uint32_t)B << 16) | 0xFF000000u;
-  }
+  for (int k = 0; k < 2; ++k) px[k] = ycc_rgba_px((int)((y2 >> (8 * k)) & 0xffu), cb[k], cr[k]);
   *reinterpret_cast<uint2*>(rgba + ((size_t)r * w + 2u * c) * 4u) = make_uint2(px[0], px[1]);
+}
+
+// The chroma sample libjpeg-turbo's upsampler (jdsample.c) puts under pixel (x, y) of a plane subsampled in ONE direction:
+//   4:4:4  the sample itself
+//   4:2:2  h2v1_fancy_upsample along the row: even columns (3 c[i] + c[i-1] + 1) >> 2, odd ones (3 c[i] + c[i+1] + 2) >> 2, the first
+//          and the last output column of the (even-width) upsampled row the end samples themselves; rows of at most 2 samples
+//          are replicated (jinit_upsampler takes h2v1_upsample for them)
+//   4:4:0  h1v2_fancy_upsample down the column: even rows (3 c[j] + c[j-1] + 1) >> 2, odd ones (3 c[j] + c[j+1] + 2) >> 2, the
+//          neighbour clamped to the plane
+__device__ __forceinline__ int yccx_chroma(const uint8_t* __restrict__ p, uint32_t cs, uint32_t cw, uint32_t ch, uint32_t hs, uint32_t vs,
+                                           uint32_t x, uint32_t y) {
+  if (hs == 2u) {
+    const uint32_t i = x >> 1;
+    const uint8_t* row = p + (size_t)y * cs;
+    const int c = row[i];
+    if (cw <= 2u) return c;
+    if (x & 1u) return i + 1u < cw ? (3 * c + (int)row[i + 1u] + 2) >> 2 : c;
+    return i ? (3 * c + (int)row[i - 1u] + 1) >> 2 : c;
+  }
+  if (vs == 2u) {
+    const uint32_t j = y >> 1;
+    const int c = p[(size_t)j * cs + x];
+    const uint32_t o = (y & 1u) ? min(j + 1u, ch - 1u) : (j ? j - 1u : 0u);
+    return (3 * c + (int)p[(size_t)o * cs + x] + ((y & 1u) ? 2 : 1)) >> 2;
+  }
+  return p[(size_t)y * cs + x];
+}
+// 4:4:4 / 4:2:2 / 4:4:0 planes -> RGBA: a thread converts pixels [4g, 4g + 4) of the packed w * h output, so that its store is one
+// aligned 16 bytes whatever the width (the four may lie in two rows); a tail of w * h % 4 pixels, and an output that is not 16-byte
+// aligned, go out pixel by pixel.  grid.z = image, grid.x strided over the image's groups.
+__global__ void __launch_bounds__(256) k_yccx_rgba_batch(const YccxRgbaBatch b) {
+  const YccRgbaImage& im = b.img[blockIdx.z].im;
+  const uint32_t hs = b.img[blockIdx.z].hs, vs = b.img[blockIdx.z].vs;
+  const uint32_t cw = (im.w + hs - 1u) / hs, ch = (im.h + vs - 1u) / vs;
+  const uint32_t total = im.w * im.h, groups = (total + 3u) >> 2;   // (w, h <= 8192: 2^26 pixels)
+  const bool aligned = (reinterpret_cast<uintptr_t>(im.rgba) & 15u) == 0u;
+  for (uint32_t g = blockIdx.x * 256u + threadIdx.x; g < groups; g += gridDim.x * 256u) {
+    const uint32_t p0 = 4u * g, cnt = min(4u, total - p0);
+    uint32_t y = p0 / im.w, x = p0 - y * im.w;
+    uint32_t px[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) {
+      if (k < cnt) {
+        px[k] = ycc_rgba_px((int)im.y[(size_t)y * im.ys + x], yccx_chroma(im.cb, im.cs, cw, ch, hs, vs, x, y),
+                            yccx_chroma(im.cr, im.cs, cw, ch, hs, vs, x, y));
+        if (++x == im.w) { x = 0u; ++y; }
+      }
+    }
+    uint32_t* out = reinterpret_cast<uint32_t*>(im.rgba) + p0;
+    if (aligned && cnt == 4u) *reinterpret_cast<uint4*>(out) = make_uint4(px[0], px[1], px[2], px[3]);
+    else {
+#pragma unroll
+      for (uint32_t k = 0; k < 4u; ++k)
+        if (k < cnt) out[k] = px[k];
+    }
+  }
+}
+
+hipError_t launch_yccx_to_rgba_batch(const YccxRgbaBatch& b, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (n > kRgbaChunk) return hipErrorInvalidValue;
+  uint32_t groups = 1;
+  for (int k = 0; k < n; ++k) groups = std::max(groups, (b.img[k].im.w * b.img[k].im.h + 3u) / 4u);
+  hipLaunchKernelGGL(k_yccx_rgba_batch, dim3(std::min((groups + 255u) / 256u, 4096u), 1, (unsigned)n), dim3(256), 0, s, b);
+  return hipGetLastError();
 }
 
 // n images of any sizes in one launch: grid.z = image, grid.x over the widest image's pixel pairs, rows strided by grid.y

@@ -431,8 +431,8 @@ status_t JpegRHip::decodeJPEGR(uhdr_compressed_ptr jpegr_image_ptr, uhdr_uncompr
   uhdr_hip_metadata_t md;
   const size_t bpp = output_format == ULTRAHDR_OUTPUT_HDR_LINEAR ? 8 : output_format == ULTRAHDR_OUTPUT_HDR_LINEAR_RGB_10BIT ? 6 : 4;
   const bool want_md = metadata != nullptr || output_format != ULTRAHDR_OUTPUT_SDR;   // jpegr.cpp:754
-  rc = uhdr_hip_jpegr_decode(file, n, (int)output_format, max_display_boost, dest->data, a.width * a.height * bpp, &d, want_md ? &md : nullptr, mApplyMode,
-                             UHDR_HIP_MEM_HOST, nullptr);
+  rc = uhdr_hip_jpegr_decode_ex(file, n, (int)output_format, max_display_boost, dest->data, a.width * a.height * bpp, &d, want_md ? &md : nullptr,
+                                mApplyMode, UHDR_HIP_MEM_HOST, nullptr, mDecodeAnySampling ? UHDR_HIP_DECODE_ANY_SAMPLING : 0);
   if (rc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(rc);
   dest->width = d.width; dest->height = d.height;
   dest->colorGamut = static_cast<ultrahdr_color_gamut>(d.colorGamut);
