@@ -650,6 +650,65 @@ int uhdr_hip_jpegr_encode_adaptive_batch(int n, const uhdr_hip_image_t* p010_ima
                                          void* const* out, const size_t* out_capacity, size_t* out_size,
                                          uhdr_hip_metadata_t* metadata, int* status, int boost_scope, int mem_space, void* stream);
 
+/* ---- tone-mapped SDR base image for API-0 (no reference counterpart) -------------------------
+ * UltraHdr::toneMap shifts the P010 code values to 8 bits: the PQ- or HLG-encoded signal becomes the "SDR" image, which a legacy
+ * viewer shows washed out and against which most of the gain map clips to the floor of its range.  REINHARD_MAXRGB derives an SDR
+ * rendition instead.  For an HDR image with transfer function hdr_tf (HLG, PQ, LINEAR, as generate accepts) and gamut G, in f32:
+ *   1. per pixel: yuv = getP010Pixel(x, y) (a 2x2 block shares its chroma sample), rgb' = <G>YuvToRgb(yuv), clamped to [0, 1]
+ *   2. lin = invOETF_hdr_tf(rgb') per channel -- generate's exact functions; LINEAR is the identity; no HLG OOTF, as in generate
+ *   3. white = 10000 for PQ, else 1000;  k = white / 203.0f;  cap = k
+ *   4. the image's headroom H.  Given (hdr_peak_nits[i] > 0):  H = fminf(fmaxf(hdr_peak_nits[i] / 203.0f, 1.0f), cap).
+ *      Measured (hdr_peak_nits == NULL or hdr_peak_nits[i] == 0):  m' = the maximum over all pixels and the three channels of the
+ *      clamped rgb' of step 1 -- taken before linearisation: the inverse OETFs are monotone --,
+ *      H = fminf(fmaxf(invOETF(m') * k, 1.0f), cap)
+ *   5. extended Reinhard on the maximum channel: v = lin * k; M = max(v.r, v.g, v.b); s = M > 0 ? (1 + M / (H * H)) / (1 + M) : 1;
+ *      o = clamp(v * s, 0, 1).  H == 1 is the identity on [0, 1]; the gain the map has to restore is 1 / s, in [1, H], inside the
+ *      reference's constant boost range
+ *   6. e = sRGB OETF(o) per channel: o <= 0.0031308f ? 12.92f * o : 1.055f * powf(o, 1 / 2.4f) - 0.055f
+ *   7. yuv_out = <G>RgbToYuv(e): the SDR image keeps the HDR image's gamut, as API-0's does today
+ *   8. quantised like transformYuv420 (gainmapmath.cpp:513-519): Y = (uint8)CLIP3(y * 255.0f + 0.5f, 0, 255) per pixel; per 2x2
+ *      block u = (((u00 + u01) + u10) + u11) * 0.25f, U = (uint8)CLIP3(u * 255.0f + 128.0f + 0.5f, 0, 255), V likewise
+ * The destination is laid out like uhdr_hip_tonemap's: planar Y, U, V, V chroma_stride * height / 2 behind U, the padding columns
+ * [width, stride) zeroed, dest->colorGamut = src->colorGamut.  Step 2 is bit-exact; the steps behind it run on the f32 units. */
+#define UHDR_HIP_TONEMAP_SHIFT 0            /* the reference's toneMap: what every other call does */
+#define UHDR_HIP_TONEMAP_REINHARD_MAXRGB 1  /* the operator above */
+/* The headroom rule by itself, host code: gamma_max = m' of step 4 (ignored when peak_nits > 0).  BAD_PTR for NULL,
+ * INVALID_TRANS_FUNC for a transfer function generate refuses, UNSUPPORTED_FEATURE for a negative or non-finite peak_nits. */
+int uhdr_hip_tonemap_headroom(int hdr_tf, float gamma_max, float peak_nits, float* headroom);
+/* n images in DEVICE memory.  The call only enqueues kernels on `stream` -- no allocation, no copy, no host synchronisation -- and
+ * the headroom never visits the host: the slots are set (0 or the given H), k_tonemap_peak reduces m' of the measured images into
+ * them, one small launch turns m' into H, k_tonemap_sdr writes the planes.  Images of equal size and gamut that follow each other
+ * share launches (grid.z = image, up to 32).
+ *   hdr_peak_nits  HOST, n floats, or NULL (every headroom measured)
+ *   headroom       DEVICE, n floats, required for REINHARD_MAXRGB: image i's H
+ * Checks, in this order, all before any launch (a failing call writes nothing): those of uhdr_hip_tonemap_batch;
+ * INVALID_TRANS_FUNC; UNSUPPORTED_FEATURE for an unknown tonemap_op -- TONEMAP_SHIFT is uhdr_hip_tonemap_batch from here --;
+ * UNSUPPORTED_FEATURE for a negative or non-finite hdr_peak_nits[i]; BAD_PTR for a NULL headroom where n > 0; then per image
+ * UNSUPPORTED_WIDTH_HEIGHT for an odd width or height, INVALID_COLORGAMUT, INVALID_STRIDE for a stride shorter than its row.
+ * Strides: a source luma_stride of 0 means width, as getP010Pixel reads it (gainmapmath.cpp:585).  Nothing else is defaulted:
+ * chroma_data is required (uhdr_hip_tonemap_batch's check), and beside a chroma pointer a chroma_stride below width -- 0 included
+ * -- is INVALID_STRIDE, as in the encode calls' areInputArgumentsValid, which default the chroma stride only together with a NULL
+ * chroma pointer; the destination strides are the caller's, as for uhdr_hip_tonemap. */
+int uhdr_hip_tonemap_sdr_batch(int n, const uhdr_hip_image_t* p010_images, uhdr_hip_image_t* dests, int hdr_tf, int tonemap_op,
+                               const float* hdr_peak_nits, float* headroom, void* stream);
+/* One image, planes in mem_space (host planes are staged like uhdr_hip_tonemap's); waits for `stream` in either memory space and
+ * returns H to the host (headroom: HOST, optional; untouched by TONEMAP_SHIFT). */
+int uhdr_hip_tonemap_sdr(const uhdr_hip_image_t* p010_image, uhdr_hip_image_t* dest, int hdr_tf, int tonemap_op, float hdr_peak_nits,
+                         float* headroom, int mem_space, void* stream);
+/* encodeJPEGR API-0 for n files with the chosen operator: uhdr_hip_jpegr_encode_batch with yuv420_images == NULL whose toneMap step
+ * is uhdr_hip_tonemap_sdr_batch (the headroom array is a pool slot of the round's codec context); generate, the BT.601 re-encode,
+ * the compressions, the single synchronisation per round and the containers are that call's.  boost_scope = -1: the reference's
+ * constant range; UHDR_HIP_BOOST_PER_IMAGE / PER_CALL: the adaptive generate of uhdr_hip_jpegr_encode_adaptive_batch.  metadata
+ * (HOST, n entries, optional) receives what every processed file's container carries.  Checks: those of
+ * uhdr_hip_jpegr_encode_batch, then UNSUPPORTED_FEATURE for an unknown tonemap_op or boost_scope; per file, behind that call's
+ * checks, UNSUPPORTED_FEATURE for a negative or non-finite hdr_peak_nits[i] (REINHARD_MAXRGB only).  With TONEMAP_SHIFT and
+ * boost_scope = -1 the call is uhdr_hip_jpegr_encode_batch. */
+int uhdr_hip_jpegr_encode_api0_tonemapped_batch(int n, const uhdr_hip_image_t* p010_images, int hdr_tf, int quality,
+                                                const void* const* exif, const size_t* exif_size, void* const* out,
+                                                const size_t* out_capacity, size_t* out_size, uhdr_hip_metadata_t* metadata,
+                                                int* status, int tonemap_op, const float* hdr_peak_nits, int boost_scope,
+                                                int mem_space, void* stream);
+
 /* ---- introspection for tests -------------------------------------------------------------- */
 /* copies the 4 Shepard IDW weight tables (standard, no-right, no-bottom, corner; each
  * scale*scale*4 floats; gainmapmath.h:184-228) the apply kernels use for `scale` into out[] */

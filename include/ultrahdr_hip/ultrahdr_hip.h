@@ -120,6 +120,12 @@ class UltraHdrHip {
   int mGenerateMode = 0;
 };
 
+// The SDR base image of a P010 image tone-mapped from linear light (include/uhdr_hip.h, "tone-mapped SDR base image"; no reference
+// counterpart): host images in and out like toneMap's, executed on HIP device 0.  tonemap_op: UHDR_HIP_TONEMAP_SHIFT (toneMap) or
+// UHDR_HIP_TONEMAP_REINHARD_MAXRGB; hdr_peak_nits = 0 measures the image's headroom, which *headroom (optional) receives.
+status_t toneMapSdr(uhdr_uncompressed_ptr src, uhdr_uncompressed_ptr dest, ultrahdr_transfer_function hdr_tf, int tonemap_op,
+                    float hdr_peak_nits = 0.0f, float* headroom = nullptr);
+
 // ---- editing effects: the free functions of lib/include/ultrahdr/editorhelper.h:49-63, same signatures ----------
 enum ultrahdr_mirroring_direction : int { ULTRAHDR_MIRROR_VERTICAL = 0, ULTRAHDR_MIRROR_HORIZONTAL = 1 };
 
@@ -230,6 +236,10 @@ class JpegRHip {
   // -1 (default): the reference's constant boost range.  UHDR_HIP_BOOST_PER_IMAGE / UHDR_HIP_BOOST_PER_CALL: the API-0 and API-1
   // overloads encode the gain map against the range the content has (uhdr_hip_jpegr_encode_adaptive_batch); the others are unchanged
   void setContentBoost(int scope_or_minus_one) { mContentBoost = scope_or_minus_one; }
+  // UHDR_HIP_TONEMAP_SHIFT (default): the API-0 overload derives its SDR image like the reference, by bit shift.
+  // UHDR_HIP_TONEMAP_REINHARD_MAXRGB: tone-mapped from linear light against the image's headroom -- measured, or hdr_peak_nits / 203
+  // when hdr_peak_nits > 0 (uhdr_hip_jpegr_encode_api0_tonemapped_batch); combines with setContentBoost.  The others are unchanged
+  void setToneMap(int tonemap_op, float hdr_peak_nits = 0.0f) { mToneMapOp = tonemap_op; mHdrPeakNits = hdr_peak_nits; }
   // false (default): decodeJPEGR reads what the reference reads, 4:2:0 primaries.  true: also 4:4:4, 4:2:2 and 4:4:0 ones
   // (UHDR_HIP_DECODE_ANY_SAMPLING)
   void setDecodeAnySampling(bool on) { mDecodeAnySampling = on; }
@@ -237,6 +247,8 @@ class JpegRHip {
  private:
   int mApplyMode = 1;
   int mContentBoost = -1;
+  int mToneMapOp = 0;
+  float mHdrPeakNits = 0.0f;
   bool mDecodeAnySampling = false;
 };
 

@@ -31,6 +31,7 @@ DECODE_ANY_SAMPLING = 1                         # flags bit of the *_decode*_ex 
 APPLY_FAST, APPLY_EXACT, APPLY_LUT, APPLY_EXACT_UNFILTERED = 0, 1, 2, 3
 GENERATE_EXACT, GENERATE_LUT, GENERATE_UNFILTERED = 0, 1, 2
 BOOST_PER_IMAGE, BOOST_PER_CALL = 0, 1          # content-adaptive gain maps: one boost range per image / per call
+TONEMAP_SHIFT, TONEMAP_REINHARD_MAXRGB = 0, 1   # API-0's SDR base image: the reference's bit shift / tone-mapped from linear light
 ABI_VERSION = 3
 FLT_MAX = 3.4028234663852886e38
 
@@ -151,6 +152,12 @@ SIGNATURES = {
     "uhdr_hip_jpegr_encode_adaptive_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                        C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _MP, C.POINTER(C.c_int),
                                                        C.c_int, C.c_int, C.c_void_p]),
+    "uhdr_hip_tonemap_headroom": (C.c_int, [C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float)]),
+    "uhdr_hip_tonemap_sdr_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "uhdr_hip_tonemap_sdr": (C.c_int, [_IP, _IP, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "uhdr_hip_jpegr_encode_api0_tonemapped_batch": (C.c_int, [C.c_int, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                              C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _MP,
+                                                              C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p]),
 }
 
 _lib = None
@@ -295,6 +302,15 @@ def adaptive_boost_range(hdr_tf, g_min, g_max):
     if rc != NO_ERROR:
         raise UhdrHipError("uhdr_hip_adaptive_boost_range -> %d" % rc)
     return lo.value, hi.value
+
+
+def tonemap_headroom(hdr_tf, gamma_max, peak_nits=0.0):
+    """uhdr_hip_tonemap_headroom: the headroom H the tone-mapped SDR base image is compressed against"""
+    h = C.c_float()
+    rc = load().uhdr_hip_tonemap_headroom(hdr_tf, gamma_max, peak_nits, C.byref(h))
+    if rc != NO_ERROR:
+        raise UhdrHipError("uhdr_hip_tonemap_headroom -> %d" % rc)
+    return h.value
 
 
 def adaptive_workspace_bytes(yuv_images):

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <thread>
@@ -347,6 +348,8 @@ void fill_adaptive_metadata(float lo, float hi, uhdr_hip_metadata_t* md) {
   md->hdrCapacityMax = hi;
 }
 bool valid_boost_scope(int scope) { return scope == UHDR_HIP_BOOST_PER_IMAGE || scope == UHDR_HIP_BOOST_PER_CALL; }
+// hdr_peak_nits of the tone-mapped SDR base image: 0 (the headroom is measured) or a positive finite figure
+bool valid_peak_nits(float peak) { return peak >= 0.0f && std::isfinite(peak); }
 
 // the caller's workspace: the images' key pairs, their constants, then every image's gains (4 bytes per map pixel), each piece
 // a multiple of 256 bytes
@@ -1315,6 +1318,8 @@ int host_pool_reserve(DeviceState* st, size_t bytes) {
 enum : size_t { kEncWs = 0, kEncDesc, kEncSdr, kEncMap, kEncP010, kEncYuv };
 // the adaptive encode's workspace and the key pair it carries from round to round: slots no other codec path of a context names
 enum : size_t { kEncAdaptWs = 8, kEncAdaptCarry = 9 };
+// the tone-mapped API-0 encode's headroom array (one float per file of the round): likewise
+enum : size_t { kEncToneHead = 10 };
 
 // one image of compress_to_host: device planes and how to compress them in, the JPEG out
 struct EncJpeg {
@@ -2184,6 +2189,7 @@ struct EncFile {
   uhdr_hip_image_t enc, map;   // the planes the two JPEGs compress (device)
   size_t pad_ls = 0, pad_cs = 0;   // the strides that decide the encoder's column padding (the caller's for a P3 image)
   bool own_copy = false;       // enc is a private zero-padded copy with 16-aligned strides
+  float peak = 0.0f;           // tone-mapped API-0: the caller's hdr_peak_nits (0: the headroom is measured)
   std::vector<uint8_t> icc;
 };
 
@@ -2199,8 +2205,10 @@ EncJpeg gainmap_jpeg(uhdr_hip_image_t map, size_t pad_ls) {
 // boost_scope >= 0: the adaptive generate instead; range (2 m floats) receives the files' (lo, hi) behind the round's synchronisation.
 // carry != 0 (PER_CALL over several rounds): the rounds' pooled extremes travel in the context's carry slot; carry == 1 measures
 // only -- staging, toneMap and pass 1, no map, no compression, no synchronisation --, carry == 2 encodes against the carried pair.
+// tonemap_op (API-0): the operator that derives the SDR planes; its headroom array is a pool slot of the context.
 int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_tf, int quality, EncFile* f, int m, uhdr_hip_metadata_t* md,
-                 std::vector<EncJpeg>* jpg, int boost_scope = -1, float* range = nullptr, int carry = 0) {
+                 std::vector<EncJpeg>* jpg, int boost_scope = -1, float* range = nullptr, int carry = 0,
+                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT) {
   auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
   int rc;
   // sizes of the round's slices
@@ -2218,6 +2226,8 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
   if (sdr_total && (rc = pool_reserve(st, kEncSdr, sdr_total)) != 0) return rc;
   if (p010_total && (rc = pool_reserve(st, kEncP010, p010_total)) != 0) return rc;
   if (yuv_total && (rc = pool_reserve(st, kEncYuv, yuv_total)) != 0) return rc;
+  const bool tone_sdr = api0 && tonemap_op != UHDR_HIP_TONEMAP_SHIFT;
+  if (tone_sdr && (rc = pool_reserve(st, kEncToneHead, round_up(sizeof(float) * (size_t)m, 256))) != 0) return rc;
 
   // planes: staged inputs (host callers), private copies, maps
   size_t o_p010 = 0, o_yuv = 0, o_sdr = 0, o_map = 0;
@@ -2265,7 +2275,14 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
   std::vector<uhdr_hip_image_t> a((size_t)m), b((size_t)m), c((size_t)m);
   if (api0) {   // :208-226
     for (int k = 0; k < m; ++k) { a[k] = f[k].p010; b[k] = f[k].enc; }
-    if ((rc = uhdr_hip_tonemap_batch(m, a.data(), b.data(), s)) != UHDR_HIP_NO_ERROR) return rc;
+    if (tone_sdr) {
+      std::vector<float> peaks((size_t)m);
+      for (int k = 0; k < m; ++k) peaks[(size_t)k] = f[k].peak;
+      rc = uhdr_hip_tonemap_sdr_batch(m, a.data(), b.data(), hdr_tf, tonemap_op, peaks.data(), static_cast<float*>(st->pool[kEncToneHead]), s);
+    } else {
+      rc = uhdr_hip_tonemap_batch(m, a.data(), b.data(), s);
+    }
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
   }
   // generateGainMap: the files are sorted by size and gamuts, so equal ones share its launches
   for (int k = 0; k < m; ++k) { a[k] = f[k].yuv; b[k] = f[k].p010; c[k] = f[k].map; }
@@ -2318,7 +2335,8 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
 // call synchronises once per round of up to kEncRound files, and the containers are assembled by a few host threads
 int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
                  const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
-                 int* status, int mem_space, void* stream, int boost_scope = -1, uhdr_hip_metadata_t* metadata = nullptr) {
+                 int* status, int mem_space, void* stream, int boost_scope = -1, uhdr_hip_metadata_t* metadata = nullptr,
+                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, const float* hdr_peak_nits = nullptr) {
   const bool api0 = yuv420_images == nullptr;
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
   std::vector<EncFile> files;
@@ -2327,9 +2345,12 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
     const size_t exn = exif ? exif_size[i] : 0;
     int rc = check_encode_inputs(p010_images + i, api0 ? nullptr : yuv420_images + i, hdr_tf, out[i], out_size + i);
     if (rc == UHDR_HIP_NO_ERROR && ex == nullptr && exn != 0) rc = UHDR_HIP_ERROR_BAD_PTR;                     // :190-193 / :258-261
+    const float peak = tonemap_op != UHDR_HIP_TONEMAP_SHIFT && hdr_peak_nits ? hdr_peak_nits[i] : 0.0f;
+    if (rc == UHDR_HIP_NO_ERROR && !valid_peak_nits(peak)) rc = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     if (rc != UHDR_HIP_NO_ERROR) { st_[i] = rc; continue; }
     EncFile e;
     e.idx = i;
+    e.peak = peak;
     e.p010 = p010_images[i];
     default_p010(&e.p010);
     memset(&e.yuv, 0, sizeof(e.yuv));
@@ -2360,7 +2381,7 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
       std::vector<EncFile> probe(files.begin() + (long)q0, files.begin() + (long)q0 + m);   // (a round rewrites its files' descriptors)
       uhdr_hip_metadata_t md;
       std::vector<EncJpeg> jpg;
-      rc = encode_round(st, s, api0, host, hdr_tf, quality, probe.data(), m, &md, &jpg, boost_scope, nullptr, 1);
+      rc = encode_round(st, s, api0, host, hdr_tf, quality, probe.data(), m, &md, &jpg, boost_scope, nullptr, 1, tonemap_op);
     }
     return rc;
   };
@@ -2375,8 +2396,11 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
         EncFile* f = &files[r0];
         uhdr_hip_metadata_t md;
         std::vector<EncJpeg> jpg;
-        if ((rc = encode_round(st, s, api0, host, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry)) != UHDR_HIP_NO_ERROR) return rc;
+        if ((rc = encode_round(st, s, api0, host, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry, tonemap_op)) != UHDR_HIP_NO_ERROR)
+          return rc;
         std::vector<uhdr_hip_metadata_t> mds;   // adaptive: every file's own
+        if (boost_scope < 0 && metadata)
+          for (int k = 0; k < m; ++k) metadata[f[k].idx] = md;
         if (boost_scope >= 0) {
           mds.resize((size_t)m);
           for (int k = 0; k < m; ++k) {
@@ -2503,6 +2527,20 @@ int uhdr_hip_jpegr_encode_adaptive_batch(int n, const uhdr_hip_image_t* p010_ima
   if (!valid_boost_scope(boost_scope)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream,
                       boost_scope, metadata);
+}
+
+int uhdr_hip_jpegr_encode_api0_tonemapped_batch(int n, const uhdr_hip_image_t* p010_images, int hdr_tf, int quality, const void* const* exif,
+                                                const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
+                                                uhdr_hip_metadata_t* metadata, int* status, int tonemap_op, const float* hdr_peak_nits,
+                                                int boost_scope, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
+  if (tonemap_op != UHDR_HIP_TONEMAP_SHIFT && tonemap_op != UHDR_HIP_TONEMAP_REINHARD_MAXRGB) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (boost_scope != -1 && !valid_boost_scope(boost_scope)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return encode_files(n, p010_images, nullptr, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream,
+                      boost_scope, metadata, tonemap_op, hdr_peak_nits);
 }
 
 // JpegR::encodeJPEGR API-0 (jpegr.cpp:186-247): a batch of one file
@@ -3274,6 +3312,29 @@ int tonemap_check(const uhdr_hip_image_t* src, const uhdr_hip_image_t* dest) {  
     return UHDR_HIP_ERROR_BAD_PTR;  // (the reference would dereference them)
   return UHDR_HIP_NO_ERROR;
 }
+// A toneMap through host memory, for both operators: the P010 planes staged into slots 2 and 3 of `ss`, destination planes in
+// slots 0 and 1, run(staged source, staged destination) enqueued between, then what the reference writes copied back --
+// luma_stride bytes per luma row, chroma_stride bytes per chroma row, V chroma_stride * height / 2 behind U.  Enqueues only.
+int tonemap_through_stage(StageSet* ss, const uhdr_hip_image_t* src, uhdr_hip_image_t* dest, hipStream_t s,
+                          const std::function<int(const uhdr_hip_image_t&, uhdr_hip_image_t&)>& run) {
+  int rc;
+  uhdr_hip_image_t ds, dd = *dest;
+  if ((rc = stage_p010_in(ss, 2, *src, &ds, s)) != 0) return rc;
+  const size_t h = dest->height, ls = dest->luma_stride, cs = dest->chroma_stride;
+  if ((rc = stage_reserve(ss, 0, ls * h)) != 0) return rc;
+  if ((rc = stage_reserve(ss, 1, cs * h + cs)) != 0) return rc;
+  dd.data = ss->stage[0];
+  dd.chroma_data = ss->stage[1];
+  if ((rc = run(ds, dd)) != 0) return rc;
+  if (ls * h) HIP_TRY(hipMemcpyAsync(dest->data, dd.data, ls * h, hipMemcpyDeviceToHost, s));
+  const size_t v_off = cs * h / 2;
+  if (cs * (h / 2)) {
+    HIP_TRY(hipMemcpyAsync(dest->chroma_data, dd.chroma_data, cs * (h / 2), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(dest->chroma_data) + v_off, static_cast<uint8_t*>(dd.chroma_data) + v_off,
+                           cs * (h / 2), hipMemcpyDeviceToHost, s));
+  }
+  return UHDR_HIP_NO_ERROR;
+}
 }  // namespace
 
 // UltraHdr::toneMap over n images in device memory: images of equal size (and equal alignment class) share a launch, grid.z = image
@@ -3325,24 +3386,192 @@ int uhdr_hip_tonemap(const uhdr_hip_image_t* src, uhdr_hip_image_t* dest, int me
   StageLease lease(st);
   StageSet* ss = lease.get();
   if (ss == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  uhdr_hip_image_t ds, dd = *dest;
-  if ((rc = stage_p010_in(ss, 2, *src, &ds, s)) != 0) return rc;
-  const size_t h = dest->height, ls = dest->luma_stride, cs = dest->chroma_stride;
-  if ((rc = stage_reserve(ss, 0, ls * h)) != 0) return rc;
-  if ((rc = stage_reserve(ss, 1, cs * h + cs)) != 0) return rc;
-  dd.data = ss->stage[0];
-  dd.chroma_data = ss->stage[1];
-  if ((rc = run(ds, dd)) != 0) return rc;
-  // the reference writes luma_stride bytes per luma row and chroma_stride bytes per chroma row
-  if (ls * h) HIP_TRY(hipMemcpyAsync(dest->data, dd.data, ls * h, hipMemcpyDeviceToHost, s));
-  const size_t v_off = cs * h / 2;
-  if (cs * (h / 2)) {
-    HIP_TRY(hipMemcpyAsync(dest->chroma_data, dd.chroma_data, cs * (h / 2), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(dest->chroma_data) + v_off, static_cast<uint8_t*>(dd.chroma_data) + v_off,
-                           cs * (h / 2), hipMemcpyDeviceToHost, s));
-  }
+  if ((rc = tonemap_through_stage(ss, src, dest, s, run)) != 0) return rc;
   HIP_TRY(hipStreamSynchronize(s));
   dest->colorGamut = src->colorGamut;
+  return UHDR_HIP_NO_ERROR;
+}
+
+// ---- tone-mapped SDR base image (include/uhdr_hip.h) -------------------------------------------------
+namespace {
+// the inverse OETFs on the host, for the headroom rule by itself: the reference's expressions (gainmapmath.cpp:279-286, :326-338)
+// with libm in double, like the reference -- the values the device's exact functions return
+float hlg_inv_oetf_host(float e) {
+  const float a = 0.17883277f, b = 0.28466892f, c = (float)0.55991073;
+  if (e <= 0.5f) return (float)(std::pow((double)e, (double)2.0f) / (double)3.0f);
+  return (float)((std::exp((double)((e - c) / a)) + (double)b) / (double)12.0f);
+}
+float pq_inv_oetf_host(float e) {
+  if (e <= 0.0001f) return 0.0f;
+  const double p = std::pow((double)e, (double)0.0126833f);
+  return (float)std::pow(((double)128.0f * p - (double)107.0f) / ((double)2413.0f - (double)2392.0f * p), (double)6.2773946361f);
+}
+// H of include/uhdr_hip.h, in f32; k_tonemap_head_finish performs the measured branch's operations on the device
+float tone_headroom(int hdr_tf, float gamma_max, float peak_nits) {
+  const float k = adaptive_cap(hdr_tf), cap = k;
+  if (peak_nits > 0.0f) return fminf(fmaxf(peak_nits / 203.0f, 1.0f), cap);
+  const float lin = hdr_tf == UHDR_HIP_TF_HLG ? hlg_inv_oetf_host(gamma_max) : hdr_tf == UHDR_HIP_TF_PQ ? pq_inv_oetf_host(gamma_max) : gamma_max;
+  return fminf(fmaxf(lin * k, 1.0f), cap);
+}
+bool valid_tonemap_op(int op) { return op == UHDR_HIP_TONEMAP_SHIFT || op == UHDR_HIP_TONEMAP_REINHARD_MAXRGB; }
+
+// what the operator asks of an image pair beyond tonemap_check: whole 2x2 blocks, a gamut, rows no shorter than the image
+int tonemap_sdr_check(const uhdr_hip_image_t& src, const uhdr_hip_image_t& dest) {
+  if ((src.width | src.height) & 1) return UHDR_HIP_ERROR_UNSUPPORTED_WIDTH_HEIGHT;
+  if (!valid_gamut(src.colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+  if ((src.luma_stride != 0 && src.luma_stride < src.width) || src.chroma_stride < src.width || dest.luma_stride < dest.width ||
+      dest.chroma_stride < dest.width / 2)
+    return UHDR_HIP_ERROR_INVALID_STRIDE;
+  return UHDR_HIP_NO_ERROR;
+}
+ToneImage tone_sdr_image(const uhdr_hip_image_t& sd, const uhdr_hip_image_t& dd, bool* aligned) {
+  bool unused;
+  ToneImage t = tone_image(sd, dd, &unused);
+  if (sd.luma_stride == 0) t.sy_stride = (uint32_t)sd.width;  // gainmapmath.cpp:585
+  *aligned = t.width % 16u == 0 && al(t.sy, 16) && t.sy_stride % 8u == 0 && al(t.suv, 16) && t.suv_stride % 8u == 0 && al(t.dy, 16) &&
+             t.dy_stride % 16u == 0 && al(t.du, 8) && al(t.dv, 8) && t.dc_stride % 8u == 0;
+  return t;
+}
+ToneSdrConsts tone_sdr_consts(int gamut, int hdr_tf, float* headroom) {
+  ToneSdrConsts c;
+  const YuvRgb m = yuv_rgb_coeffs(gamut);
+  c.cr = m.cr; c.gcb = m.gcb; c.gcr = m.gcr; c.cb = m.cb;
+  float l[3] = {0.299f, 0.587f, 0.114f};   // p3RgbToYuv takes the BT.601 weights (gainmapmath.cpp:187-190)
+  if (gamut != UHDR_HIP_CG_P3) luminance_coeffs(gamut, l);
+  c.lr = l[0]; c.lg = l[1]; c.lb = l[2];
+  c.ycb = m.cb; c.rycb = 1.0f / m.cb; c.ycr = m.cr; c.rycr = 1.0f / m.cr;
+  c.k = adaptive_cap(hdr_tf);
+  c.headroom = headroom;
+  for (int i = 0; i < kToneChunk; ++i) c.slot[i] = 0u;
+  return c;
+}
+}  // namespace
+
+int uhdr_hip_tonemap_headroom(int hdr_tf, float gamma_max, float peak_nits, float* headroom) {
+  if (headroom == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (!valid_peak_nits(peak_nits)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  *headroom = tone_headroom(hdr_tf, gamma_max, peak_nits);
+  return UHDR_HIP_NO_ERROR;
+}
+
+// n images in device memory: the slots set, pass 1 over the measured images, the slots finished, pass 2 -- images of equal size,
+// gamut and alignment class that follow each other share the launches of either pass (grid.z = image)
+int uhdr_hip_tonemap_sdr_batch(int n, const uhdr_hip_image_t* srcs, uhdr_hip_image_t* dests, int hdr_tf, int tonemap_op,
+                               const float* hdr_peak_nits, float* headroom, void* stream) {
+  if (n < 0 || (n > 0 && (srcs == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
+  for (int i = 0; i < n; ++i) {
+    const int rc = tonemap_check(&srcs[i], &dests[i]);
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
+  }
+  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (!valid_tonemap_op(tonemap_op)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (tonemap_op == UHDR_HIP_TONEMAP_SHIFT) return uhdr_hip_tonemap_batch(n, srcs, dests, stream);
+  for (int i = 0; hdr_peak_nits != nullptr && i < n; ++i)
+    if (!valid_peak_nits(hdr_peak_nits[i])) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (n > 0 && headroom == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  for (int i = 0; i < n; ++i) {
+    const int rc = tonemap_sdr_check(srcs[i], dests[i]);
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
+  }
+  DeviceState* st = nullptr;
+  int rc = current_state(&st);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const float k = adaptive_cap(hdr_tf);
+  auto given = [&](int i) { return hdr_peak_nits != nullptr && hdr_peak_nits[i] > 0.0f; };
+  auto head_init = [&](int base, ToneHeadInit* v) {
+    const int cnt = std::min(n - base, kToneHeadChunk);
+    for (int j = 0; j < cnt; ++j) v->h[j] = given(base + j) ? tone_headroom(hdr_tf, 0.0f, hdr_peak_nits[base + j]) : 0.0f;
+    return cnt;
+  };
+  bool any_measured = false;
+  for (int base = 0; base < n; base += kToneHeadChunk) {
+    ToneHeadInit v;
+    const int cnt = head_init(base, &v);
+    HIP_TRY(launch_tonemap_head_init(headroom + base, v, cnt, s));
+  }
+  // the runs of images that share launches
+  auto run_at = [&](int i, ToneBatch* b, bool* aligned) {
+    int m = 0;
+    while (i + m < n && m < kToneChunk) {
+      bool a;
+      const ToneImage t = tone_sdr_image(srcs[i + m], dests[i + m], &a);
+      if (m == 0) *aligned = a;
+      else if (a != *aligned || t.width != b->img[0].width || t.height != b->img[0].height || srcs[i + m].colorGamut != srcs[i].colorGamut) break;
+      b->img[m++] = t;
+    }
+    return m;
+  };
+  for (int i = 0; i < n;) {   // pass 1
+    ToneBatch b, mb;
+    bool aligned = true;
+    const int m = run_at(i, &b, &aligned);
+    ToneSdrConsts c = tone_sdr_consts(srcs[i].colorGamut, hdr_tf, headroom);
+    int cnt = 0;
+    for (int j = 0; j < m; ++j)
+      if (!given(i + j)) { mb.img[cnt] = b.img[j]; c.slot[cnt++] = (uint32_t)(i + j); }
+    if (cnt) {
+      any_measured = true;
+      HIP_TRY(launch_tonemap_peak(c, mb, cnt, aligned, s));
+    }
+    i += m;
+  }
+  for (int base = 0; any_measured && base < n; base += kToneHeadChunk) {
+    ToneHeadInit v;
+    const int cnt = head_init(base, &v);
+    HIP_TRY(launch_tonemap_head_finish(headroom + base, v, cnt, hdr_tf, k, k, s));
+  }
+  for (int i = 0; i < n;) {   // pass 2
+    ToneBatch b;
+    bool aligned = true;
+    const int m = run_at(i, &b, &aligned);
+    ToneSdrConsts c = tone_sdr_consts(srcs[i].colorGamut, hdr_tf, headroom);
+    for (int j = 0; j < m; ++j) c.slot[j] = (uint32_t)(i + j);
+    HIP_TRY(launch_tonemap_sdr(c, b, m, hdr_tf, aligned, s));
+    for (int j = 0; j < m; ++j) dests[i + j].colorGamut = srcs[i + j].colorGamut;
+    i += m;
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
+int uhdr_hip_tonemap_sdr(const uhdr_hip_image_t* src, uhdr_hip_image_t* dest, int hdr_tf, int tonemap_op, float hdr_peak_nits, float* headroom,
+                         int mem_space, void* stream) {
+  int rc = tonemap_check(src, dest);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (!valid_tonemap_op(tonemap_op)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (tonemap_op == UHDR_HIP_TONEMAP_SHIFT) {   // no headroom to report
+    if ((rc = uhdr_hip_tonemap(src, dest, mem_space, stream)) != UHDR_HIP_NO_ERROR) return rc;
+    if (mem_space == UHDR_HIP_MEM_DEVICE) HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    return UHDR_HIP_NO_ERROR;
+  }
+  if (!valid_peak_nits(hdr_peak_nits)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if ((rc = tonemap_sdr_check(*src, *dest)) != UHDR_HIP_NO_ERROR) return rc;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  StageLease lease(st);
+  StageSet* ss = lease.get();
+  if (ss == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  if ((rc = stage_reserve(ss, 4, 256)) != 0) return rc;
+  float* dh = static_cast<float*>(ss->stage[4]);
+  float h_out = 0.0f;
+  if (mem_space == UHDR_HIP_MEM_DEVICE) {
+    if ((rc = uhdr_hip_tonemap_sdr_batch(1, src, dest, hdr_tf, tonemap_op, &hdr_peak_nits, dh, stream)) != UHDR_HIP_NO_ERROR) return rc;
+    HIP_TRY(hipMemcpyAsync(&h_out, dh, sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (headroom) *headroom = h_out;
+    return UHDR_HIP_NO_ERROR;
+  }
+  auto run = [&](const uhdr_hip_image_t& sd, uhdr_hip_image_t& dd) -> int {
+    return uhdr_hip_tonemap_sdr_batch(1, &sd, &dd, hdr_tf, tonemap_op, &hdr_peak_nits, dh, stream);
+  };
+  if ((rc = tonemap_through_stage(ss, src, dest, s, run)) != 0) return rc;
+  HIP_TRY(hipMemcpyAsync(&h_out, dh, sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  dest->colorGamut = src->colorGamut;
+  if (headroom) *headroom = h_out;
   return UHDR_HIP_NO_ERROR;
 }
 

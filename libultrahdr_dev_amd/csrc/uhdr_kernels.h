@@ -192,6 +192,21 @@ constexpr int kToneChunk = 32;  // images per toneMap / convertYuv launch (grid.
 struct ToneBatch {
   ToneImage img[kToneChunk];
 };
+// Tone-mapped SDR base image (no reference counterpart): the launches take a ToneBatch of equally sized
+// images of one gamut and these constants.  Image z of a launch owns headroom[slot[z]].
+struct ToneSdrConsts {
+  float cr, gcb, gcr, cb;       // the HDR gamut's YUV -> RGB (gainmapmath.cpp:142-146 and its siblings)
+  float lr, lg, lb;             // the same gamut's RGB -> YUV (:131-134): luma weights,
+  float ycb, rycb, ycr, rycr;   // the Cb and Cr divisors and their reciprocals
+  float k;                      // hdr white / 203
+  float* headroom;              // the caller's array: max of the gamma-domain channels (k_tonemap_peak), then H
+  uint32_t slot[kToneChunk];
+};
+// the headroom slots are set and finished kToneHeadChunk at a time: h[i] = 0 (measured) or the given H of slot i
+constexpr int kToneHeadChunk = 512;
+struct ToneHeadInit {
+  float h[kToneHeadChunk];
+};
 struct CvtImage {
   uint8_t* y;   // where the converted planes go ...
   uint8_t* u;
@@ -278,6 +293,15 @@ hipError_t launch_build_gain_lut(float* table, double log2_min, double log2_max,
 hipError_t launch_tonemap(const ToneBatch& b, int n, bool aligned, hipStream_t s);      // n <= kToneChunk images of equal width / height
 hipError_t launch_convert_yuv(const CvtBatch& b, int n, bool aligned, hipStream_t s);
 static_assert(sizeof(CvtBatch) <= 4096 && sizeof(ToneBatch) <= 4096, "toneMap / convertYuv kernel arguments exceed the kernarg segment");
+// tone-mapped SDR base image.  headroom[0 .. n) = v.h (n <= kToneHeadChunk) ...
+hipError_t launch_tonemap_head_init(float* headroom, const ToneHeadInit& v, int n, hipStream_t s);
+// ... pass 1 over the measured images (n <= kToneChunk of equal width / height, both even): headroom[slot] = max(headroom[slot], m') ...
+hipError_t launch_tonemap_peak(const ToneSdrConsts& c, const ToneBatch& b, int n, bool aligned, hipStream_t s);
+// ... every slot with v.h[i] == 0 from m' to H = min(max(invOETF(m') * k, 1), cap) ...
+hipError_t launch_tonemap_head_finish(float* headroom, const ToneHeadInit& v, int n, int hdr_tf, float k, float cap, hipStream_t s);
+// ... and the planes of n <= kToneChunk images
+hipError_t launch_tonemap_sdr(const ToneSdrConsts& c, const ToneBatch& b, int n, int hdr_tf, bool aligned, hipStream_t s);
+static_assert(sizeof(ToneSdrConsts) + sizeof(ToneBatch) <= 4096 && sizeof(ToneHeadInit) + 64 <= 4096, "tone-map kernel arguments exceed the kernarg segment");
 // decoded 4:2:0 planes -> RGBA8888 with libjpeg-turbo's arithmetic; w, h even, strides in bytes: up to kRgbaChunk images of any
 // (even) sizes in one launch (k_ycc420_rgba_batch: grid.z = image)
 constexpr int kRgbaChunk = 64;

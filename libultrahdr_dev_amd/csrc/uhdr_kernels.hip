@@ -496,15 +496,22 @@ template <int CTRL, int ROWS>
 __device__ __forceinline__ float dpp_move(float v) {
   return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROWS, 0xF, false));
 }
+// one value's ladder: MAX ? the wave's maximum : its minimum
+template <bool MAX>
+__device__ __forceinline__ float wave_extreme(float v) {
+#define UHDR_EXT(CTRL, ROWS) v = MAX ? fmaxf(v, dpp_move<CTRL, ROWS>(v)) : fminf(v, dpp_move<CTRL, ROWS>(v))
+  UHDR_EXT(0xB1, 0xF);    // quad_perm:[1,0,3,2]
+  UHDR_EXT(0x4E, 0xF);    // quad_perm:[2,3,0,1]
+  UHDR_EXT(0x141, 0xF);   // row_half_mirror
+  UHDR_EXT(0x140, 0xF);   // row_mirror
+  UHDR_EXT(0x142, 0xA);   // row_bcast:15 -> rows 1, 3
+  UHDR_EXT(0x143, 0xC);   // row_bcast:31 -> rows 2, 3
+#undef UHDR_EXT
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
+}
 __device__ __forceinline__ void wave_minmax(float& vmin, float& vmax) {
-  vmin = fminf(vmin, dpp_move<0xB1, 0xF>(vmin));  vmax = fmaxf(vmax, dpp_move<0xB1, 0xF>(vmax));    // quad_perm:[1,0,3,2]
-  vmin = fminf(vmin, dpp_move<0x4E, 0xF>(vmin));  vmax = fmaxf(vmax, dpp_move<0x4E, 0xF>(vmax));    // quad_perm:[2,3,0,1]
-  vmin = fminf(vmin, dpp_move<0x141, 0xF>(vmin)); vmax = fmaxf(vmax, dpp_move<0x141, 0xF>(vmax));   // row_half_mirror
-  vmin = fminf(vmin, dpp_move<0x140, 0xF>(vmin)); vmax = fmaxf(vmax, dpp_move<0x140, 0xF>(vmax));   // row_mirror
-  vmin = fminf(vmin, dpp_move<0x142, 0xA>(vmin)); vmax = fmaxf(vmax, dpp_move<0x142, 0xA>(vmax));   // row_bcast:15 -> rows 1, 3
-  vmin = fminf(vmin, dpp_move<0x143, 0xC>(vmin)); vmax = fmaxf(vmax, dpp_move<0x143, 0xC>(vmax));   // row_bcast:31 -> rows 2, 3
-  vmin = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vmin), 63));
-  vmax = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vmax), 63));
+  vmin = wave_extreme<false>(vmin);
+  vmax = wave_extreme<true>(vmax);
 }
 // one lane per wave publishes; keys[0] holds ~key(min), keys[1] holds key(max); both only grow, both start at 0
 __device__ __forceinline__ void publish_minmax(float gmin, float gmax, uint32_t* keys) {
@@ -2887,6 +2894,278 @@ hipError_t launch_convert_yuv(const CvtBatch& b, int n, bool aligned, hipStream_
   const uint32_t rows = ch < 65535u ? ch : 65535u;
   if (aligned) hipLaunchKernelGGL((k_convert_yuv<true>), dim3((cw / 4u + 255u) / 256u, rows, n), dim3(256), 0, s, b);
   else hipLaunchKernelGGL((k_convert_yuv<false>), dim3((cw + 255u) / 256u, rows, n), dim3(256), 0, s, b);
+  return hipGetLastError();
+}
+
+// =================================================================================================
+// Tone-mapped SDR base image for encodeJPEGR API-0 (no reference counterpart): P010 -> linear light with
+// generate's exact inverse OETFs -> extended Reinhard on the maximum channel against the image's headroom H -> sRGB OETF -> 8-bit
+// YUV420 in the HDR image's gamut, quantised like transformYuv420 (gainmapmath.cpp:513-519).
+//   k_tonemap_head_init    headroom[i] = 0 (H is measured) or the given H
+//   k_tonemap_peak         measured images only: max over pixels and channels of the clamped gamma-domain r', g', b' -- the matrix
+//                          alone, no special function: the inverse OETFs are monotone, so the largest r' is the largest linear value
+//   k_tonemap_head_finish  measured slots from m' to H = min(max(invOETF(m') * k, 1), cap)
+//   k_tonemap_sdr          the planes
+// A lane owns whole 2x2 blocks (ALIGNED: eight of them, 2 rows x 16 columns, read and written as 16-byte pieces; otherwise one), so
+// every P010 chroma sample is read once and the four pixels' output chroma is averaged in registers.
+// =================================================================================================
+
+// getP010Pixel (gainmapmath.cpp:583-601) of one 16-bit word
+__device__ __forceinline__ float p010_luma(uint32_t w) { return (float)((int)(w >> 6) - 64) * k876; }
+__device__ __forceinline__ float p010_chroma(uint32_t w) { return (float)((int)(w >> 6) - 64) * k896 - 0.5f; }
+// <gamut>YuvToRgb (gainmapmath.cpp:142-146, :198-202, :250-254): the reference's operations in its order, clamped as it clamps
+__device__ __forceinline__ void tone_rgb(const ToneSdrConsts& c, float y, float u, float v, float& r, float& g, float& b) {
+  r = clamp01(y + c.cr * v);
+  g = clamp01(y - c.gcb * u - c.gcr * v);
+  b = clamp01(y + c.cb * u);
+}
+__device__ __forceinline__ float tone_block_max(const ToneSdrConsts& c, const uint32_t (&yw)[4], uint32_t uw, uint32_t vw) {
+  const float u = p010_chroma(uw), v = p010_chroma(vw);
+  float m = 0.0f;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    float r, g, b;
+    tone_rgb(c, p010_luma(yw[p]), u, v, r, g, b);
+    m = fmaxf(m, fmaxf(r, fmaxf(g, b)));
+  }
+  return m;
+}
+
+// sRGB OETF on the special-function unit: o^(1/2.4) = 2^(log2(o) / 2.4), |log2 o| <= 8.4 on the branch that uses it, so v_log_f32's
+// and v_exp_f32's errors leave the result within ~1e-6 relative: 3e-4 of an 8-bit code
+__device__ __forceinline__ float srgb_oetf_fast(float o) {
+  const float lo = 12.92f * o;
+  const float hi = 1.055f * __builtin_amdgcn_exp2f((1.0f / 2.4f) * __builtin_amdgcn_logf(o)) - 0.055f;
+  return (o <= 0.0031308f) ? lo : hi;
+}
+
+// one 2x2 block: yw[0..3] the P010 luma words of (0,0) (0,1) (1,0) (1,1), uw / vw its chroma words; ihh = 1 / (H * H).
+// Returns the four luma bytes in yo, the block's chroma bytes in uo / vo.
+template <int TF>
+__device__ __forceinline__ void tone_block(const ToneSdrConsts& c, float ihh, const uint32_t (&yw)[4], uint32_t uw, uint32_t vw,
+                                           uint32_t (&yo)[4], uint32_t& uo, uint32_t& vo) {
+  const float u = p010_chroma(uw), v = p010_chroma(vw);
+  float ch[12];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) tone_rgb(c, p010_luma(yw[p]), u, v, ch[3 * p], ch[3 * p + 1], ch[3 * p + 2]);
+  if (TF != 0) {   // generate's exact inverse OETFs, six evaluations in lock step (see gen_pair)
+#pragma unroll
+    for (int i = 0; i < 12; i += 6) {
+      float part[6];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) part[j] = ch[i + j];
+      if (TF == 1) hlg_inv_oetf_guarded_n<6>(part);
+      else pq_inv_oetf_guarded_n<6>(part);
+#pragma unroll
+      for (int j = 0; j < 6; ++j) ch[i + j] = part[j];
+    }
+  }
+  float su = 0.0f, sv = 0.0f;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const float vr = ch[3 * p] * c.k, vg = ch[3 * p + 1] * c.k, vb = ch[3 * p + 2] * c.k;   // SDR-white-relative
+    const float M = fmaxf(vr, fmaxf(vg, vb));
+    const float s = (M > 0.0f) ? (1.0f + M * ihh) * __builtin_amdgcn_rcpf(1.0f + M) : 1.0f;
+    const float er = srgb_oetf_fast(clamp01(vr * s)), eg = srgb_oetf_fast(clamp01(vg * s)), eb = srgb_oetf_fast(clamp01(vb * s));
+    const float y = c.lr * er + c.lg * eg + c.lb * eb;
+    const float pu = div_const(eb - y, c.ycb, c.rycb), pv = div_const(er - y, c.ycr, c.rycr);
+    yo[p] = round_u8(y * 255.0f + 0.5f);
+    su = (p == 0) ? pu : su + pu;   // ((u00 + u01) + u10) + u11
+    sv = (p == 0) ? pv : sv + pv;
+  }
+  uo = round_u8(((su * 0.25f) * 255.0f + 128.0f) + 0.5f);
+  vo = round_u8(((sv * 0.25f) * 255.0f + 128.0f) + 0.5f);
+}
+
+__global__ void __launch_bounds__(256) k_tonemap_head_init(float* headroom, const ToneHeadInit v, int n) {
+  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (i < n) headroom[i] = v.h[i];
+}
+hipError_t launch_tonemap_head_init(float* headroom, const ToneHeadInit& v, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (n > kToneHeadChunk) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_tonemap_head_init, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, s, headroom, v, n);
+  return hipGetLastError();
+}
+template <int TF>
+__global__ void __launch_bounds__(256) k_tonemap_head_finish(float* headroom, const ToneHeadInit v, int n, float k, float cap) {
+  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (i < n && v.h[i] == 0.0f) headroom[i] = fminf(fmaxf(hdr_inv_oetf<TF>(headroom[i]) * k, 1.0f), cap);
+}
+hipError_t launch_tonemap_head_finish(float* headroom, const ToneHeadInit& v, int n, int hdr_tf, float k, float cap, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (n > kToneHeadChunk) return hipErrorInvalidValue;
+  const dim3 grid(((unsigned)n + 255u) / 256u), block(256);
+  if (hdr_tf == 1) hipLaunchKernelGGL((k_tonemap_head_finish<1>), grid, block, 0, s, headroom, v, n, k, cap);
+  else if (hdr_tf == 2) hipLaunchKernelGGL((k_tonemap_head_finish<2>), grid, block, 0, s, headroom, v, n, k, cap);
+  else hipLaunchKernelGGL((k_tonemap_head_finish<0>), grid, block, 0, s, headroom, v, n, k, cap);
+  return hipGetLastError();
+}
+
+// the 16-bit word `k` (0 .. 7) of a 16-byte piece
+__device__ __forceinline__ uint32_t word_of(const uint4& q, int k) {
+  const uint32_t d = (k >> 1) == 0 ? q.x : (k >> 1) == 1 ? q.y : (k >> 1) == 2 ? q.z : q.w;
+  return (k & 1) ? d >> 16 : d & 0xffffu;
+}
+
+// grid.x: the lanes' columns, grid.y: block rows (strided), grid.z: image.  One atomicMax per workgroup, on the bit pattern: the
+// values are non-negative floats, which order as unsigned integers.
+template <bool ALIGNED>
+__global__ void __launch_bounds__(256) k_tonemap_peak(const ToneSdrConsts c, const ToneBatch b) {
+  const ToneImage& t = b.img[blockIdx.z];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  float m = 0.0f;
+  for (uint32_t cyr = blockIdx.y; cyr < t.height / 2u; cyr += gridDim.y) {
+    const uint16_t* y0 = t.sy + (size_t)(2u * cyr) * t.sy_stride;
+    const uint16_t* y1 = y0 + t.sy_stride;
+    const uint16_t* uv = t.suv + (size_t)cyr * t.suv_stride;
+    if (ALIGNED) {   // width % 16 == 0
+      const uint32_t x = i * 16u;
+      if (x < t.width) {   // plain loads: a frame that fits the caches is still there for k_tonemap_sdr
+        const uint4 a0 = *reinterpret_cast<const uint4*>(y0 + x), a1 = *reinterpret_cast<const uint4*>(y0 + x + 8u);
+        const uint4 b0 = *reinterpret_cast<const uint4*>(y1 + x), b1 = *reinterpret_cast<const uint4*>(y1 + x + 8u);
+        const uint4 c0 = *reinterpret_cast<const uint4*>(uv + x), c1 = *reinterpret_cast<const uint4*>(uv + x + 8u);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          const uint4& ta = k < 4 ? a0 : a1;
+          const uint4& tb = k < 4 ? b0 : b1;
+          const uint4& tc = k < 4 ? c0 : c1;
+          const int w = 2 * (k & 3);
+          const uint32_t yw[4] = {word_of(ta, w), word_of(ta, w + 1), word_of(tb, w), word_of(tb, w + 1)};
+          m = fmaxf(m, tone_block_max(c, yw, word_of(tc, w), word_of(tc, w + 1)));
+        }
+      }
+    } else {
+      const uint32_t x = i * 2u;
+      if (x < t.width) {   // width is even
+        const uint32_t yw[4] = {ld16(y0 + x), ld16(y0 + x + 1u), ld16(y1 + x), ld16(y1 + x + 1u)};
+        m = fmaxf(m, tone_block_max(c, yw, ld16(uv + x), ld16(uv + x + 1u)));
+      }
+    }
+  }
+  __shared__ float s_part[4];
+  m = wave_extreme<true>(m);   // (all 64 lanes are active here)
+  if ((threadIdx.x & 63u) == 0u) s_part[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0u) {
+    const uint32_t key = __float_as_uint(fmaxf(fmaxf(s_part[0], s_part[1]), fmaxf(s_part[2], s_part[3])));
+    uint32_t* slot = reinterpret_cast<uint32_t*>(c.headroom + c.slot[blockIdx.z]);
+    // a stale (smaller) value read here only costs an unnecessary atomic, never a lost update
+    if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < key) atomicMax(slot, key);
+  }
+}
+
+// the grid of both kernels: lanes across the widest row they touch, block rows down (strided beyond max_rows)
+static dim3 tone_sdr_grid(const ToneBatch& b, int n, bool aligned, bool dest, uint32_t max_rows) {
+  const ToneImage& t = b.img[0];
+  uint32_t lanes = aligned ? t.width / 16u : t.width / 2u;
+  if (dest)
+    for (int i = 0; i < n; ++i) {
+      const uint32_t l = aligned ? b.img[i].dy_stride / 16u : (b.img[i].dy_stride + 1u) / 2u;
+      const uint32_t cl = aligned ? b.img[i].dc_stride / 8u : b.img[i].dc_stride;
+      lanes = std::max(lanes, std::max(l, cl));
+    }
+  return dim3((lanes + 255u) / 256u, std::min(t.height / 2u, max_rows), (unsigned)n);
+}
+
+hipError_t launch_tonemap_peak(const ToneSdrConsts& c, const ToneBatch& b, int n, bool aligned, hipStream_t s) {
+  const ToneImage& t = b.img[0];
+  if (n <= 0 || t.width < 2u || t.height < 2u) return hipSuccess;
+  if (n > kToneChunk) return hipErrorInvalidValue;
+  // one atomic per workgroup: enough workgroups to fill the device (~4096 per launch), no more than 512 per image
+  dim3 grid = tone_sdr_grid(b, n, aligned, false, 65535u);
+  const uint32_t rows = std::min(std::max(4096u / (grid.x * (uint32_t)n), 32u), 512u);
+  grid.y = std::min(grid.y, rows);
+  if (aligned) hipLaunchKernelGGL((k_tonemap_peak<true>), grid, dim3(256), 0, s, c, b);
+  else hipLaunchKernelGGL((k_tonemap_peak<false>), grid, dim3(256), 0, s, c, b);
+  return hipGetLastError();
+}
+
+// ALIGNED: width % 16 == 0; sources 16-byte aligned with strides of whole 16-byte pieces; dy 16-byte aligned, dy_stride % 16 == 0;
+// du, dv 8-byte aligned, dc_stride % 8 == 0.  Either way width and height are even, dy_stride >= width, dc_stride >= width / 2, and
+// the padding columns [width, dy_stride) and [width / 2, dc_stride) are zeroed like toneMap's.
+template <int TF, bool ALIGNED>
+__global__ void __launch_bounds__(256) k_tonemap_sdr(const ToneSdrConsts c, const ToneBatch b) {
+  const ToneImage& t = b.img[blockIdx.z];
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const float H = c.headroom[c.slot[blockIdx.z]];   // (wave-uniform: scalar loads)
+  const float ihh = 1.0f / (H * H);
+  const uint32_t cw = t.width / 2u;
+  for (uint32_t cyr = blockIdx.y; cyr < t.height / 2u; cyr += gridDim.y) {   // (rows beyond the grid's 65535 by striding)
+    const uint16_t* y0 = t.sy + (size_t)(2u * cyr) * t.sy_stride;
+    const uint16_t* y1 = y0 + t.sy_stride;
+    const uint16_t* uv = t.suv + (size_t)cyr * t.suv_stride;
+    uint8_t* d0 = t.dy + (size_t)(2u * cyr) * t.dy_stride;
+    uint8_t* d1 = d0 + t.dy_stride;
+    uint8_t* du = t.du + (size_t)cyr * t.dc_stride;
+    uint8_t* dv = t.dv + (size_t)cyr * t.dc_stride;
+    if (ALIGNED) {
+      const uint32_t x = i * 16u, cx = i * 8u;
+      uint32_t ot[4] = {0u, 0u, 0u, 0u}, ob[4] = {0u, 0u, 0u, 0u}, ou[2] = {0u, 0u}, ov[2] = {0u, 0u};
+      if (x < t.width) {
+        const uint4 a0 = ld_stream(reinterpret_cast<const uint4*>(y0 + x)), a1 = ld_stream(reinterpret_cast<const uint4*>(y0 + x + 8u));
+        const uint4 b0 = ld_stream(reinterpret_cast<const uint4*>(y1 + x)), b1 = ld_stream(reinterpret_cast<const uint4*>(y1 + x + 8u));
+        const uint4 c0 = ld_stream(reinterpret_cast<const uint4*>(uv + x)), c1 = ld_stream(reinterpret_cast<const uint4*>(uv + x + 8u));
+        // one block (a dword of either luma row and of the chroma row) per trip; the loop stays rolled -- the transfer functions are
+        // long -- and the pieces are handed down by register moves, so that nothing is indexed at run time
+        uint32_t top[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w}, bot[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+        uint32_t chr[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
+#pragma unroll 1
+        for (int trip = 0; trip < 8; ++trip) {
+          const uint32_t yw[4] = {top[0] & 0xffffu, top[0] >> 16, bot[0] & 0xffffu, bot[0] >> 16};
+          uint32_t yo[4], uo, vo;
+          tone_block<TF>(c, ihh, yw, chr[0] & 0xffffu, chr[0] >> 16, yo, uo, vo);
+#pragma unroll
+          for (int k = 0; k < 7; ++k) { top[k] = top[k + 1]; bot[k] = bot[k + 1]; chr[k] = chr[k + 1]; }
+          // the new bytes enter at the top of the 128-bit (luma) and 64-bit (chroma) pieces, which move down: trip 0 ends up lowest
+#pragma unroll
+          for (int k = 0; k < 3; ++k) { ot[k] = (ot[k] >> 16) | (ot[k + 1] << 16); ob[k] = (ob[k] >> 16) | (ob[k + 1] << 16); }
+          ot[3] = (ot[3] >> 16) | ((yo[0] | (yo[1] << 8)) << 16);
+          ob[3] = (ob[3] >> 16) | ((yo[2] | (yo[3] << 8)) << 16);
+          ou[0] = (ou[0] >> 8) | (ou[1] << 24); ou[1] = (ou[1] >> 8) | (uo << 24);
+          ov[0] = (ov[0] >> 8) | (ov[1] << 24); ov[1] = (ov[1] >> 8) | (vo << 24);
+        }
+      }
+      if (x < t.dy_stride) {
+        st_stream(reinterpret_cast<uint4*>(d0 + x), make_uint4(ot[0], ot[1], ot[2], ot[3]));
+        st_stream(reinterpret_cast<uint4*>(d1 + x), make_uint4(ob[0], ob[1], ob[2], ob[3]));
+      }
+      if (cx < t.dc_stride) {
+        st_stream(reinterpret_cast<uint2*>(du + cx), make_uint2(ou[0], ou[1]));
+        st_stream(reinterpret_cast<uint2*>(dv + cx), make_uint2(ov[0], ov[1]));
+      }
+    } else {
+      const uint32_t x = i * 2u;
+      if (i < cw) {
+        const uint32_t yw[4] = {ld16(y0 + x), ld16(y0 + x + 1u), ld16(y1 + x), ld16(y1 + x + 1u)};
+        uint32_t yo[4], uo, vo;
+        tone_block<TF>(c, ihh, yw, ld16(uv + x), ld16(uv + x + 1u), yo, uo, vo);
+        d0[x] = (uint8_t)yo[0]; d0[x + 1u] = (uint8_t)yo[1];
+        d1[x] = (uint8_t)yo[2]; d1[x + 1u] = (uint8_t)yo[3];
+        du[i] = (uint8_t)uo; dv[i] = (uint8_t)vo;
+      } else {
+        if (x < t.dy_stride) { d0[x] = 0; d1[x] = 0; }
+        if (x + 1u < t.dy_stride) { d0[x + 1u] = 0; d1[x + 1u] = 0; }
+        if (i < t.dc_stride) { du[i] = 0; dv[i] = 0; }
+      }
+    }
+  }
+}
+
+hipError_t launch_tonemap_sdr(const ToneSdrConsts& c, const ToneBatch& b, int n, int hdr_tf, bool aligned, hipStream_t s) {
+  const ToneImage& t = b.img[0];
+  if (n <= 0 || t.width < 2u || t.height < 2u) return hipSuccess;
+  if (n > kToneChunk) return hipErrorInvalidValue;
+  const dim3 grid = tone_sdr_grid(b, n, aligned, true, 65535u), block(256);
+#define UHDR_TONE_SDR(TF)                                                                            \
+  do {                                                                                               \
+    if (aligned) hipLaunchKernelGGL((k_tonemap_sdr<TF, true>), grid, block, 0, s, c, b);            \
+    else hipLaunchKernelGGL((k_tonemap_sdr<TF, false>), grid, block, 0, s, c, b);                   \
+  } while (0)
+  if (hdr_tf == 1) UHDR_TONE_SDR(1);
+  else if (hdr_tf == 2) UHDR_TONE_SDR(2);
+  else UHDR_TONE_SDR(0);
+#undef UHDR_TONE_SDR
   return hipGetLastError();
 }
 

@@ -153,6 +153,19 @@ status_t UltraHdrHip::toneMap(uhdr_uncompressed_ptr src, uhdr_uncompressed_ptr d
   return ULTRAHDR_NO_ERROR;
 }
 
+status_t toneMapSdr(uhdr_uncompressed_ptr src, uhdr_uncompressed_ptr dest, ultrahdr_transfer_function hdr_tf, int tonemap_op,
+                    float hdr_peak_nits, float* headroom) {
+  if (src == nullptr || dest == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
+  if (src->width != dest->width || src->height != dest->height) return ERROR_ULTRAHDR_RESOLUTION_MISMATCH;
+  static const int init_rc = uhdr_hip_init(0);
+  uhdr_hip_image_t s = to_c(*src), d = to_c(*dest);
+  const int rc = uhdr_hip_tonemap_sdr(&s, &d, static_cast<int>(hdr_tf), tonemap_op, hdr_peak_nits, headroom, UHDR_HIP_MEM_HOST, nullptr);
+  if (rc == UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE && init_rc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(init_rc);
+  if (rc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(rc);
+  dest->colorGamut = static_cast<ultrahdr_color_gamut>(d.colorGamut);
+  return ULTRAHDR_NO_ERROR;
+}
+
 status_t UltraHdrHip::convertYuv(uhdr_uncompressed_ptr image, ultrahdr_color_gamut src_encoding,
                                  ultrahdr_color_gamut dest_encoding) {
   if (image == nullptr) return ERROR_ULTRAHDR_BAD_PTR;  // jpegr.cpp:1134-1140
@@ -304,6 +317,15 @@ status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, ultrahdr_tr
                                uhdr_exif_ptr exif) {
   uhdr_hip_image_t p;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
+  if (mToneMapOp != UHDR_HIP_TONEMAP_SHIFT)   // setToneMap: one file through the tone-mapped batch, the single call's status the file's
+    return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
+      uhdr_hip_image_t none;
+      std::memset(&none, 0, sizeof(none));
+      const void* ex = exif_ptr(exif);
+      const size_t exn = exif_len(exif);
+      return uhdr_hip_jpegr_encode_api0_tonemapped_batch(1, p010_image_ptr ? &p : &none, (int)hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, nullptr,
+                                                         mToneMapOp, &mHdrPeakNits, mContentBoost >= 0 ? mContentBoost : -1, UHDR_HIP_MEM_HOST, nullptr);
+    });
   if (mContentBoost >= 0)
     return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
       return adaptive_one(p010_image_ptr ? &p : nullptr, nullptr, (int)hdr_tf, quality, exif, out, cap, n, mContentBoost);
