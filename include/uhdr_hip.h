@@ -80,6 +80,10 @@ extern "C" {
 #define UHDR_HIP_PIX_FMT_YUV444 3               /* chroma width x height */
 #define UHDR_HIP_PIX_FMT_YUV422 4               /* chroma ceil(width / 2) x height */
 #define UHDR_HIP_PIX_FMT_YUV440 5               /* chroma width x ceil(height / 2) */
+/* A per-channel (RGB) gain map, read and written only by the *_rgb_* / *_rgbmap_* calls: interleaved R, G, B, A bytes, 4 per map
+ * pixel; data points at pixel (0, 0) and is 4-byte aligned, luma_stride is in PIXELS (0 = width), chroma_data = NULL.  Calls that
+ * write a map set A = 0xFF, calls that read one ignore A.  It is the layout UHDR_HIP_DECODE_TO_RGBA produces. */
+#define UHDR_HIP_PIX_FMT_RGBA8888 6
 /* status_t, ultrahdr.h:91-120 */
 #define UHDR_HIP_NO_ERROR 0
 #define UHDR_HIP_UNKNOWN_ERROR (-1)
@@ -337,6 +341,16 @@ int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void*
 int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
                                void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream);
 
+/* n UHDR_HIP_PIX_FMT_RGBA8888 images -> the baseline 4:4:4 files libjpeg writes for in_color_space = JCS_RGB with all sampling
+ * factors 1: jpeg_set_quality(quality, TRUE), JDCT_ISLOW, default Huffman tables, jccolor.c's fixed-point RGB -> YCbCr, an MCU of
+ * one block each of Y, Cb, Cr, partial blocks padded by repeating the last column, then the last row.  Byte for byte what
+ * libjpeg-turbo writes (Pillow: quality=q, subsampling=0).  Alpha is ignored.  The conventions of uhdr_hip_jpeg_encode_batch (memory
+ * spaces, size probe with ERROR_INSUFFICIENT_RESOURCE and the exact size, per-file statuses), no ICC.  Any size from 1 x 1 to
+ * 65500 x 65500, odd ones included.  Call-level: BAD_PTR for n < 0 or a NULL array where n > 0, INVALID_QUALITY_FACTOR for a
+ * quality outside 0..100.  Per file: BAD_PTR (data NULL or, in device memory, not 4-byte aligned), UNSUPPORTED_FEATURE (another
+ * pixelFormat), RESOLUTION_MISMATCH (size out of range, or a luma_stride below the width). */
+int uhdr_hip_jpeg_encode_rgb_batch(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
+                                   size_t* out_size, int* status, int mem_space, void* stream);
 /* Diagnostics, host only (no GPU): the quantised coefficients of a progressive (SOF2) file after all of its scans -- what the
  * host-side entropy decoder hands to the device: blocks in MCU order (4:2:0: Y00 Y01 Y10 Y11 Cb Cr), zigzag order inside a block.
  * *blocks receives the block count (also when coef is NULL / too small: INSUFFICIENT_RESOURCE).  Baseline files, whose entropy
@@ -440,13 +454,24 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
  * primary image may be 4:4:4, 4:2:2 or 4:4:0: UHDR_HIP_OUTPUT_SDR is libjpeg-turbo's RGBA of it, the HDR outputs are applyGainMap
  * over its planes with every pixel reading the chroma sample libjpeg's downsampled grid gives it (the rule of the reference's
  * getYuv420Pixel, no interpolation), through the general per-pixel kernels in every apply_mode (the scale-4 fast kernels are
- * 4:2:0's).  A gain-map JPEG with chroma of any accepted sampling contributes its luma. */
+ * 4:2:0's).  A gain-map JPEG with chroma of any accepted sampling contributes its luma (uhdr_hip_jpegr_decode_rgbmap_batch applies
+ * such a map per channel). */
 int uhdr_hip_jpegr_decode_ex(const void* jpegr, size_t jpegr_size, int output_format, float max_display_boost, void* dest_data,
                              size_t dest_capacity, uhdr_hip_image_t* dest, uhdr_hip_metadata_t* metadata, int apply_mode,
                              int mem_space, void* stream, int flags);
 int uhdr_hip_jpegr_decode_batch_ex(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
                                    void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests,
                                    uhdr_hip_metadata_t* metadata, int* status, int apply_mode, int mem_space, void* stream, int flags);
+
+/* uhdr_hip_jpegr_decode_batch_ex for files with per-channel gain maps: the same signature, flags included
+ * (UHDR_HIP_DECODE_ANY_SAMPLING keeps its meaning for the primary image).  A file whose gain-map JPEG has THREE components -- 4:4:4,
+ * 4:2:2, 4:4:0 or 4:2:0, whatever the flag -- has that JPEG converted to RGBA with libjpeg-turbo's arithmetic
+ * (UHDR_HIP_DECODE_TO_RGBA; an odd-sized 4:2:0 map: ERROR_UNSUPPORTED_FEATURE, as there) and applied per channel
+ * (uhdr_hip_apply_gainmap_rgb_batch, so UHDR_HIP_APPLY_FAST or _EXACT).  A file whose gain-map JPEG has one component takes the
+ * path of uhdr_hip_jpegr_decode_batch_ex, with identical bytes; UHDR_HIP_OUTPUT_SDR is unchanged. */
+int uhdr_hip_jpegr_decode_rgbmap_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
+                                       void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests,
+                                       uhdr_hip_metadata_t* metadata, int* status, int apply_mode, int mem_space, void* stream, int flags);
 
 /* JpegR::appendGainMap (lib/src/jpegr.cpp:951-1130): primary JPEG + gain-map JPEG + metadata -> JPEG/R container (XMP packets of
  * jpegrutils.cpp:547-611, MPF segment of multipictureformat.cpp:30-92).  exif / icc: payloads of an APP1 / APP2 segment to add, or
@@ -496,6 +521,13 @@ int uhdr_hip_jpegr_encode_api1(const uhdr_hip_image_t* p010_image, const uhdr_hi
 int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf,
                                 int quality, const void* const* exif, const size_t* exif_size, void* const* out,
                                 const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream);
+/* uhdr_hip_jpegr_encode_batch with a per-channel gain map: the same signature and conventions (API-1, or API-0 when
+ * yuv420_images == NULL); the primary image and the container are exactly that call's, the gain map is
+ * uhdr_hip_generate_gainmap_rgb_batch's, compressed at quality 85 as uhdr_hip_jpeg_encode_rgb_batch compresses it.  XMP, MPF and ICC
+ * are untouched and the metadata is the same single range.  Read such files with uhdr_hip_jpegr_decode_rgbmap_batch. */
+int uhdr_hip_jpegr_encode_rgbmap_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf,
+                                       int quality, const void* const* exif, const size_t* exif_size, void* const* out,
+                                       const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream);
 /* encodeJPEGR API-2 (yuv420_images != NULL) or API-3 (yuv420_images == NULL) for n files in one call, and API-x for n files in one
  * call (no reference counterparts).  The conventions of uhdr_hip_jpegr_encode_batch: arrays indexed by file, hdr_tf / quality shared,
  * everything else per file; planes in mem_space, compressed inputs, exif and out[i] HOST memory; every file's status, size and bytes
@@ -594,6 +626,29 @@ int uhdr_hip_apply_gainmap_batch(int n, const uhdr_hip_image_t* yuv420_images,
                                  const uhdr_hip_metadata_t* metadata, int output_format,
                                  float max_display_boost, uhdr_hip_image_t* dests, int apply_mode,
                                  void* stream);
+
+/* ---- per-channel (RGB) gain maps (the reference's one-plane maps carry one luminance ratio per map pixel; current libultrahdr also
+ * writes three-channel maps, use_multi_channel_gainmap) ------------------------------------
+ * Everything of generateGainMap up to the luminance is unchanged (sampling at scale 4, yuvToRgb, the inverse OETFs, the gamut
+ * conversion into the SDR gamut).  With sdr_rgb and hdr_rgb those two linear colours, byte c of a map pixel is the reference's
+ * encodeGain(sdr_rgb.c * 203.0f, hdr_rgb.c * hdr_white_nits, metadata), the products in f32: a channel <= 0 on the SDR side gives
+ * gain 1, a negative HDR channel (out of gamut after the conversion) clamps to minContentBoost.  The metadata is the reference's
+ * constants, identical to what uhdr_hip_generate_gainmap_batch returns.  The exact arithmetic throughout (no f32 pre-filter).
+ * Device memory, asynchronous; conventions, checks and status order of uhdr_hip_generate_gainmap_batch.  dests[i].data needs
+ * 4 * (width / 4) * (height / 4) bytes, 4-byte aligned (BAD_PTR otherwise); dests[i] comes back as UHDR_HIP_PIX_FMT_RGBA8888. */
+int uhdr_hip_generate_gainmap_rgb_batch(int n, const uhdr_hip_image_t* yuv420_images, const uhdr_hip_image_t* p010_images, int hdr_tf,
+                                        uhdr_hip_metadata_t* metadata, uhdr_hip_image_t* dests, int sdr_is_601, void* stream);
+/* applyGainMap with an RGBA8888 map: sampleMap's four taps and weights are the pixel's, applied to each channel of the taps, and
+ * applyGain runs per channel -- channel c of the linear SDR colour times exp2(log2Min * (1 - gain_c) + log2Max * gain_c), the
+ * display-boost form alike.  Every operation behind the gain is per channel, so channel c of the result is, bit for bit, channel c
+ * of uhdr_hip_apply_gainmap_batch run with plane c of the map (UHDR_HIP_APPLY_EXACT; UHDR_HIP_APPLY_FAST: every 10-bit channel
+ * within 1 code, every F16 channel within 1 half-precision ULP of it).  Conventions, checks and status order of
+ * uhdr_hip_apply_gainmap_batch -- any integer scale factor, 4:2:0 / 4:4:4 / 4:2:2 / 4:4:0 primaries by pixelFormat --, plus
+ * BAD_PTR for a map pointer that is not 4-byte aligned, INVALID_STRIDE for a luma_stride below the map's width, and
+ * ERROR_UNSUPPORTED_FEATURE for UHDR_HIP_APPLY_LUT and UHDR_HIP_APPLY_EXACT_UNFILTERED.  The maps' pixelFormat is not read. */
+int uhdr_hip_apply_gainmap_rgb_batch(int n, const uhdr_hip_image_t* yuv420_images, const uhdr_hip_image_t* gainmap_images,
+                                     const uhdr_hip_metadata_t* metadata, int output_format, float max_display_boost,
+                                     uhdr_hip_image_t* dests, int apply_mode, void* stream);
 
 /* ---- content-adaptive gain maps (no reference counterpart) ---------------------------------
  * The reference encodes every map against minContentBoost = 1, maxContentBoost = hdr_white / 203 (ultrahdr.cpp:250-257): 255 codes

@@ -243,6 +243,11 @@ class JpegRHip {
   // false (default): decodeJPEGR reads what the reference reads, 4:2:0 primaries.  true: also 4:4:4, 4:2:2 and 4:4:0 ones
   // (UHDR_HIP_DECODE_ANY_SAMPLING)
   void setDecodeAnySampling(bool on) { mDecodeAnySampling = on; }
+  // false (default): one-plane gain maps, as the reference writes and reads them.  true: the API-0 and API-1 overloads of encodeJPEGR
+  // write a per-channel (RGB) gain map (uhdr_hip_jpegr_encode_rgbmap_batch; it takes precedence over setToneMap and setContentBoost,
+  // which are single-channel) and decodeJPEGR applies a three-component gain map per channel
+  // (uhdr_hip_jpegr_decode_rgbmap_batch; files with one-plane maps decode as ever).  The other encodeJPEGR overloads are unchanged.
+  void setMultiChannelGainMap(bool on) { mMultiChannelGainMap = on; }
 
  private:
   int mApplyMode = 1;
@@ -250,6 +255,7 @@ class JpegRHip {
   int mToneMapOp = 0;
   float mHdrPeakNits = 0.0f;
   bool mDecodeAnySampling = false;
+  bool mMultiChannelGainMap = false;
 };
 
 }  // namespace ultrahdr

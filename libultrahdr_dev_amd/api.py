@@ -15,6 +15,7 @@ TF_LINEAR, TF_HLG, TF_PQ, TF_SRGB = 0, 1, 2, 3
 OUTPUT_SDR, OUTPUT_HDR_LINEAR, OUTPUT_HDR_PQ, OUTPUT_HDR_HLG, OUTPUT_HDR_LINEAR_RGB_10BIT = 0, 1, 2, 3, 4
 PIX_FMT_P010, PIX_FMT_YUV420, PIX_FMT_MONOCHROME = 0, 1, 2
 PIX_FMT_YUV444, PIX_FMT_YUV422, PIX_FMT_YUV440 = 3, 4, 5   # what the DECODE_ANY_SAMPLING decodes return and apply reads
+PIX_FMT_RGBA8888 = 6   # a per-channel (RGB) gain map: R, G, B, A bytes per map pixel, luma_stride in pixels
 NO_ERROR, UNKNOWN_ERROR = 0, -1
 ERROR_BAD_PTR, ERROR_INVALID_COLORGAMUT, ERROR_INVALID_TRANS_FUNC = -10001, -10003, -10005
 ERROR_RESOLUTION_MISMATCH, ERROR_BAD_METADATA = -10006, -10010
@@ -80,6 +81,15 @@ SIGNATURES = {
     "uhdr_hip_convert_yuv_batch": (C.c_int, [C.c_int, _IP, C.c_int, C.c_int, C.c_void_p]),
     "uhdr_hip_generate_gainmap_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _MP, _IP, C.c_int, C.c_void_p, C.c_void_p]),
     "uhdr_hip_apply_gainmap_batch": (C.c_int, [C.c_int, _IP, _IP, _MP, C.c_int, C.c_float, _IP, C.c_int, C.c_void_p]),
+    "uhdr_hip_generate_gainmap_rgb_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _MP, _IP, C.c_int, C.c_void_p]),
+    "uhdr_hip_apply_gainmap_rgb_batch": (C.c_int, [C.c_int, _IP, _IP, _MP, C.c_int, C.c_float, _IP, C.c_int, C.c_void_p]),
+    "uhdr_hip_jpeg_encode_rgb_batch": (C.c_int, [C.c_int, _IP, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                                 C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "uhdr_hip_jpegr_encode_rgbmap_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                     C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int,
+                                                     C.c_void_p]),
+    "uhdr_hip_jpegr_decode_rgbmap_batch": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_float, C.POINTER(C.c_void_p),
+                                                     C.POINTER(C.c_size_t), _IP, _MP, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "uhdr_hip_mem_pool_create": (C.c_int, [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]),
     "uhdr_hip_mem_pool_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "uhdr_hip_mem_pool_free": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -272,6 +282,11 @@ def ycbcr_image(ptr, w, h, gamut, pix_fmt, luma_stride=None, chroma_stride=None,
 
 def mono_image(ptr, w, h):
     return Image(ptr, w, h, CG_UNSPECIFIED, None, w, 0, PIX_FMT_MONOCHROME)
+
+
+def rgba_map_image(ptr, w, h, stride=None):
+    """descriptor of a per-channel gain map: w x h RGBA pixels, rows `stride` pixels apart"""
+    return Image(ptr, w, h, CG_UNSPECIFIED, None, w if stride is None else stride, 0, PIX_FMT_RGBA8888)
 
 
 def out_image(ptr):

@@ -581,6 +581,7 @@ AppConsts apply_consts(const uhdr_hip_image_t& yuv, const uhdr_hip_image_t& map,
   c.ex_cap = 0;
   c.cells_per_thread = 8;
   c.step_x = c.step_y = 0;
+  c.map_stride = c.map_w;
   return c;
 }
 // The chroma geometry of an 8-bit YCbCr image by its pixelFormat: the shifts from a pixel to its chroma sample and the rows of a
@@ -1216,13 +1217,15 @@ int uhdr_hip_eval_transfer(int fn, const float* in, float* out, size_t n, float 
 
 namespace {
 // block geometry and quantisation tables of one image (jpeg_set_quality(q, TRUE), jpegencoderhelper.cpp:119-136)
-void encode_job_tables(size_t w, size_t h, bool gray, int quality, jpeg::Job* jp) {
+void encode_job_tables(size_t w, size_t h, jpeg::Geometry geom, int quality, jpeg::Job* jp) {
   jpeg::Job& j = *jp;
   memset(&j, 0, sizeof(j));
+  const bool gray = geom == jpeg::kGeomGray, rgb = geom == jpeg::kGeomRgb444;
   j.gray = gray ? 1 : 0;
+  j.rgb = rgb ? 1 : 0;
   j.ybw = (uint32_t)((w + 7) / 8); j.ybh = (uint32_t)((h + 7) / 8);
-  j.mcus_x = (uint32_t)((w + 15) / 16);
-  j.nblk = gray ? j.ybw * j.ybh : j.mcus_x * (uint32_t)((h + 15) / 16) * 6u;
+  j.mcus_x = rgb ? j.ybw : (uint32_t)((w + 15) / 16);
+  j.nblk = gray ? j.ybw * j.ybh : rgb ? j.ybw * j.ybh * 3u : j.mcus_x * (uint32_t)((h + 15) / 16) * 6u;
   uint16_t qn[64];
   jpeg::quant_table(quality, false, qn); jpeg::zigzag_table(qn, j.q_lum);
   jpeg::quant_table(quality, true, qn); jpeg::zigzag_table(qn, j.q_chr);
@@ -1239,11 +1242,20 @@ jpeg::Plane encode_plane(const uint8_t* p, size_t pw, size_t ph, size_t stride, 
 }
 // the encoder job of one image with device planes (luma_stride set); pad_ls / pad_cs: the strides that decide the column padding,
 // the caller's for planes staged from host memory
-jpeg::Job encode_job(const uhdr_hip_image_t& img, int q, size_t pad_ls, size_t pad_cs) {
+// The geometry of an image the encoder compresses.  rgb is said by the caller, never read off the descriptor: only the calls that
+// take RGBA8888 images pass it, and the older calls go on treating every pixelFormat other than MONOCHROME as 4:2:0.
+jpeg::Geometry enc_geom(const uhdr_hip_image_t& img, bool rgb) {
+  return rgb ? jpeg::kGeomRgb444 : img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME ? jpeg::kGeomGray : jpeg::kGeom420;
+}
+jpeg::Job encode_job(const uhdr_hip_image_t& img, int q, size_t pad_ls, size_t pad_cs, bool rgb = false) {
   const bool gray = img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
   const size_t w = img.width, h = img.height, aw = (w + 15) / 16 * 16, acw = (w / 2 + 7) / 8 * 8;
   jpeg::Job j;
-  encode_job_tables(w, h, gray, q, &j);
+  encode_job_tables(w, h, enc_geom(img, rgb), q, &j);
+  if (j.rgb) {   // RGBA pixels, 4-byte aligned, luma_stride in pixels; edges are replicated by the kernel, nothing is padded
+    j.plane[0] = jpeg::Plane{static_cast<const uint8_t*>(img.data), (int)w, (int)h, (int)(img.luma_stride * 4), 0, 1};
+    return j;
+  }
   j.plane[0] = encode_plane(static_cast<const uint8_t*>(img.data), w, h, img.luma_stride, pad_ls < aw);
   if (!gray) {
     const uint8_t* pu = static_cast<const uint8_t*>(img.chroma_data);
@@ -1335,6 +1347,7 @@ struct EncJpeg {
   bool to_dev = false;                   // the JPEG goes to dev_out (device memory, dev_cap bytes; the header only if it fits) instead
   uint8_t* dev_out = nullptr;
   size_t dev_cap = 0;
+  bool rgb = false;                      // img is RGBA8888 (luma_stride in pixels), compressed as 4:4:4 (jpeg::kGeomRgb444)
 };
 
 // JpegEncoderHelper::compressImage (jpegencoderhelper.cpp:39-52) of k images in the leased context st: the headers are written into
@@ -1355,12 +1368,12 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
   std::vector<std::vector<uint8_t>> header((size_t)k);
   for (int i = 0; i < k; ++i) {
     const EncJpeg& e = im[i];
-    jobs[i] = encode_job(e.img, e.quality, e.pad_ls, e.pad_cs);
+    jobs[i] = encode_job(e.img, e.quality, e.pad_ls, e.pad_cs, e.rgb);
     ws_off[i] = ws_total;
     ws_total += round_up(jpeg::workspace_bytes(jobs[i].nblk, &lay[i]), 256);
-    jpeg::build_header((int)e.img.width, (int)e.img.height, jobs[i].gray != 0, e.quality, e.icc ? e.icc->data() : nullptr,
+    jpeg::build_header((int)e.img.width, (int)e.img.height, enc_geom(e.img, e.rgb), e.quality, e.icc ? e.icc->data() : nullptr,
                        e.icc ? e.icc->size() : 0, header[i]);
-    if (im[i].cap == 0) im[i].cap = im[i].img.width * im[i].img.height + 65536;
+    if (im[i].cap == 0) im[i].cap = im[i].img.width * im[i].img.height * (jobs[i].rgb ? 3 : 1) + 65536;
     off[i] = hp_total;
     hp_total += round_up(e.to_dev ? header[i].size() : im[i].cap, 256);   // a device destination: the header's way there only
   }
@@ -1401,6 +1414,7 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     if (current_state(&root) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
     CodecLease lease(root);
     EncJpeg one{e.img, e.quality, e.icc, e.pad_ls, e.pad_cs, (size_t)total};
+    one.rgb = e.rgb;
     if (lease.get() == nullptr || compress_to_host(lease.get(), s, 1, &one, false) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
     e.big.assign(one.bytes, one.bytes + one.n);
     e.bytes = e.big.data();
@@ -1445,7 +1459,7 @@ int stage_encoder_slice(uint8_t* dy, const uhdr_hip_image_t& img, uhdr_hip_image
 // what one image holds of its round: encoder workspace, staged planes, page-locked staging of the file
 size_t enc_round_bytes(const uhdr_hip_image_t& img, bool host_in, bool host_out) {
   jpeg::Job j;
-  encode_job_tables(img.width, img.height, img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME, 75, &j);
+  encode_job_tables(img.width, img.height, enc_geom(img, false), 75, &j);
   jpeg::Layout l;
   size_t b = jpeg::workspace_bytes(j.nblk, &l);
   if (host_in) b += enc_stage_bytes(img);
@@ -1539,7 +1553,7 @@ int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void*
   if (host && (rc = stage_encoder_in(st, 0, img, &d, s)) != 0) return rc;
   const jpeg::Job j = encode_job(d, quality, img.luma_stride, img.chroma_stride);
   std::vector<uint8_t> header;
-  jpeg::build_header((int)img.width, (int)img.height, gray, quality, icc, icc_size, header);
+  jpeg::build_header((int)img.width, (int)img.height, enc_geom(img, false), quality, icc, icc_size, header);
   jpeg::Layout l;
   if ((rc = stage_reserve(st, 7, jpeg::workspace_bytes(j.nblk, &l))) != 0) return rc;
   uint8_t* ws = static_cast<uint8_t*>(st->stage[7]);
@@ -1598,6 +1612,100 @@ int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int*
   return finish_statuses(st_, status);
 }
 
+// uhdr_hip_jpeg_encode_batch's conventions for RGBA8888 images, compressed as 4:4:4 (jpeg::kGeomRgb444): the file libjpeg writes for
+// in_color_space = JCS_RGB with all sampling factors 1.  No ICC.
+int uhdr_hip_jpeg_encode_rgb_batch(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
+                                   size_t* out_size, int* status, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  for (int i = 0; i < n; ++i)
+    if (quality[i] < 0 || quality[i] > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
+  std::vector<int> live;
+  const bool host_in = mem_space == UHDR_HIP_MEM_HOST || mem_space == UHDR_HIP_MEM_HOST_TO_DEVICE;
+  const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE && mem_space != UHDR_HIP_MEM_HOST_TO_DEVICE;
+  for (int i = 0; i < n; ++i) {
+    const uhdr_hip_image_t& im = images[i];
+    if (im.data == nullptr || (!host_in && !al(im.data, 4)) || (out[i] == nullptr && out_capacity[i] != 0))
+      st_[i] = UHDR_HIP_ERROR_BAD_PTR;
+    else if (im.pixelFormat != UHDR_HIP_PIX_FMT_RGBA8888)
+      st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+    else if (im.width == 0 || im.height == 0 || im.width > 65500 || im.height > 65500 || (im.luma_stride != 0 && im.luma_stride < im.width) ||
+             im.luma_stride > (size_t)INT32_MAX / 4)   // (rows are addressed with an int byte pitch)
+      st_[i] = UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
+    else
+      live.push_back(i);
+  }
+  if (live.empty()) return finish_statuses(st_, status);
+  auto stage_pitch = [](const uhdr_hip_image_t& im) { return round_up(im.width * 4, 64); };   // bytes
+  size_t done = 0;
+  const int rc = run_rounds(
+      live.size(), (size_t)jpeg::kMaxBatchJobs, stream,
+      [&](size_t k) {
+        const uhdr_hip_image_t& im = images[live[k]];
+        jpeg::Job j;
+        encode_job_tables(im.width, im.height, jpeg::kGeomRgb444, 75, &j);
+        jpeg::Layout l;
+        size_t b = jpeg::workspace_bytes(j.nblk, &l);
+        if (host_in) b += round_up(stage_pitch(im) * im.height, 256);
+        if (host_out) b += im.width * im.height * 3 + 65536;
+        return b;
+      },
+      [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
+        const int* idx = &live[r0];
+        std::vector<EncJpeg> im((size_t)m);
+        size_t stage_total = 0;
+        int rc;
+        if (host_in) {
+          for (int k = 0; k < m; ++k) stage_total += round_up(stage_pitch(images[idx[k]]) * images[idx[k]].height, 256);
+          if ((rc = pool_reserve(st, kEncYuv, stage_total)) != 0) return rc;
+        }
+        size_t o = 0;
+        for (int k = 0; k < m; ++k) {
+          const int i = idx[k];
+          uhdr_hip_image_t d = images[i];
+          if (d.luma_stride == 0) d.luma_stride = d.width;
+          d.chroma_data = nullptr; d.chroma_stride = 0;
+          if (host_in) {   // rows of 4 w bytes into the round's slice, at a 64-byte pitch
+            const size_t pitch = stage_pitch(d);
+            uint8_t* dst = static_cast<uint8_t*>(st->pool[kEncYuv]) + o;
+            if ((rc = h2d_plane(dst, pitch, d.data, d.luma_stride * 4, d.width * 4, d.height, 1, s)) != 0) return rc;
+            o += round_up(pitch * d.height, 256);
+            d.data = dst; d.luma_stride = pitch / 4;
+          }
+          EncJpeg& e = im[k];
+          e.img = d;
+          e.quality = quality[i];
+          e.icc = nullptr;
+          e.pad_ls = e.pad_cs = 0;
+          e.rgb = true;
+          if (host_out) {
+            e.keep_max = out_capacity[i];   // a file that will not fit is only measured
+          } else {
+            e.to_dev = true;
+            e.dev_out = static_cast<uint8_t*>(out[i]);
+            e.dev_cap = out_capacity[i];
+          }
+        }
+        if ((rc = compress_to_host(st, s, m, im.data())) != UHDR_HIP_NO_ERROR) return rc;
+        auto deliver = [&](int lo, int hi) {
+          for (int k = lo; k < hi; ++k) {
+            const int i = idx[k];
+            out_size[i] = im[k].n;
+            if (im[k].n > out_capacity[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
+            if (host_out) memcpy(out[i], im[k].bytes, im[k].n);
+            st_[i] = UHDR_HIP_NO_ERROR;
+          }
+        };
+        if (host_out) on_host_threads(m, deliver);
+        else deliver(0, m);
+        return (int)UHDR_HIP_NO_ERROR;
+      },
+      &done);
+  for (size_t k = done; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
+  return finish_statuses(st_, status);
+}
+
 // Diagnostics (host only, no GPU): the quantised coefficients of a PROGRESSIVE file after all of its scans, as the host-side
 // entropy decoder hands them to the device (csrc/uhdr_jpeg_prog.cpp) -- blocks in MCU order, zigzag order inside a block, DC as the
 // value.  tests/test_jpeg_progressive.py compares them with libjpeg's jpeg_read_coefficients.  Returns the number of blocks through
@@ -1646,7 +1754,10 @@ bool image_by_header(const uint8_t* file, size_t n, size_t begin, jpeg::DecInfo*
   return true;
 }
 
-int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bool want_metadata, JpegrFile* f, bool any_sampling) {
+// any_sampling: of the primary image; map_any_sampling: of the gain map (the rgbmap decode reads three-component maps of every
+// sampling the RGBA conversion handles whatever the flag says of the primary)
+int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bool want_metadata, JpegrFile* f, bool any_sampling,
+                     bool map_any_sampling) {
   const uint8_t* file = static_cast<const uint8_t*>(jpegr);
   const bool sdr = output_format == UHDR_HIP_OUTPUT_SDR;   // the gain map is neither decompressed nor (unless asked for) read (:728, :754)
   jpegr::Range img[2];
@@ -1663,7 +1774,7 @@ int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bo
       if (q == nullptr) break;
       pos = (size_t)(static_cast<const uint8_t*>(q) - file);
       if (file[pos + 1] == 0xD8) {
-        by_header = image_by_header(file, jpegr_size, pos, &f->info[1], &img[1].len, any_sampling);
+        by_header = image_by_header(file, jpegr_size, pos, &f->info[1], &img[1].len, map_any_sampling);
         img[1].begin = pos;
         break;
       }
@@ -1678,7 +1789,7 @@ int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bo
   for (int k = 0; k < (sdr ? 1 : 2); ++k) {   // the headers, parsed once (jpeg_read_header of either decompressImage call, :690-694 / :731-733)
     f->jpg[k] = file + img[k].begin; f->len[k] = img[k].len;
     const bool parsed = by_header || (k == 0 && have0 && img[0].begin == 0 && img[0].len == len0);
-    const int prc = parsed ? 0 : jpeg::parse_header(f->jpg[k], f->len[k], &f->info[k], any_sampling);
+    const int prc = parsed ? 0 : jpeg::parse_header(f->jpg[k], f->len[k], &f->info[k], k == 0 ? any_sampling : map_any_sampling);
     if (prc == -3) return UHDR_HIP_UNKNOWN_ERROR;   // host allocation failed (never the capacity-probe status)
     if (prc == -2) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     if (prc != 0 || f->info[k].w > 8192 || f->info[k].h > 8192) return UHDR_HIP_ERROR_DECODE_ERROR;
@@ -1945,10 +2056,12 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
                                         apply_mode, mem_space, stream, 0);
 }
 
-// the same with flags: UHDR_HIP_DECODE_ANY_SAMPLING also reads files whose primary image (or gain map) is 4:4:4, 4:2:2 or 4:4:0
-int uhdr_hip_jpegr_decode_batch_ex(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
-                                   void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
-                                   int* status, int apply_mode, int mem_space, void* stream, int flags) {
+// the same with flags: UHDR_HIP_DECODE_ANY_SAMPLING also reads files whose primary image (or gain map) is 4:4:4, 4:2:2 or 4:4:0.
+// rgb_maps (uhdr_hip_jpegr_decode_rgbmap_batch): a gain-map JPEG of three components, of any of those samplings whatever the flag, is
+// converted to libjpeg-turbo's RGBA and applied per channel (uhdr_hip_apply_gainmap_rgb_batch); a one-component map as ever.
+static int jpegr_decode_files(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
+                              void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
+                              int* status, int apply_mode, int mem_space, void* stream, int flags, bool rgb_maps) {
   if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   const bool any_sampling = (flags & UHDR_HIP_DECODE_ANY_SAMPLING) != 0;
   if (n < 0 || (n > 0 && (jpegr == nullptr || jpegr_size == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
@@ -1962,7 +2075,7 @@ int uhdr_hip_jpegr_decode_batch_ex(int n, const void* const* jpegr, const size_t
   // host time per file and touches nothing shared: the files of a batch are parsed by a few threads side by side
   on_host_threads(n, [&](int lo, int hi) {
     for (int i = lo; i < hi; ++i)
-      st_[i] = jpegr[i] == nullptr ? UHDR_HIP_ERROR_BAD_PTR : parse_jpegr_file(jpegr[i], jpegr_size[i], output_format, metadata != nullptr, &files[i], any_sampling);
+      st_[i] = jpegr[i] == nullptr ? UHDR_HIP_ERROR_BAD_PTR : parse_jpegr_file(jpegr[i], jpegr_size[i], output_format, metadata != nullptr, &files[i], any_sampling, any_sampling || rgb_maps);
   });
   for (int i = 0; i < n; ++i) {
     if (st_[i] != UHDR_HIP_NO_ERROR) continue;
@@ -2008,6 +2121,8 @@ int uhdr_hip_jpegr_decode_batch_ex(int n, const void* const* jpegr, const size_t
       planes.insert(planes.end(), p3, p3 + 3);
     }
     if (host && (rc = pool_reserve(st, 5 * (size_t)i + 4, out_bytes[i])) != 0) return rc;
+    // a three-component map as RGBA (slots behind the batch scratch at 5 n)
+    if (rgb_maps && !sdr && !f.info[1].gray && (rc = pool_reserve(st, 5 * (size_t)n + 1 + (size_t)i, (size_t)f.info[1].w * (size_t)f.info[1].h * 4)) != 0) return rc;
   }
   const int nimg = (int)infos.size();
   std::vector<jpeg::DecPlane (*)[3]> pl((size_t)nimg);
@@ -2024,6 +2139,20 @@ int uhdr_hip_jpegr_decode_batch_ex(int n, const void* const* jpegr, const size_t
   if (drc > 0) { set_err("uhdr_hip_jpegr_decode", herr); return UHDR_HIP_UNKNOWN_ERROR; }
   for (int k = 0; k < nimg; ++k)
     if (image_rc[k] != 0) st_[owner[k]] = UHDR_HIP_ERROR_DECODE_ERROR;
+
+  // three-component maps of the rgbmap decode: libjpeg-turbo's RGBA of the planes just decoded, up to kRgbaChunk maps per launch.  An
+  // odd-sized 4:2:0 map is refused as uhdr_hip_jpeg_decode_rgba refuses the file.
+  if (rgb_maps && !sdr) {
+    RgbaBatches mb;
+    for (int i = 0; i < n; ++i) {
+      if (st_[i] != UHDR_HIP_NO_ERROR || files[i].info[1].gray) continue;
+      const jpeg::DecInfo& gi = files[i].info[1];
+      if (dec_geom(gi).fmt == UHDR_HIP_PIX_FMT_YUV420 && ((gi.w | gi.h) & 1)) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }
+      mb.add(gi, static_cast<const uint8_t*>(st->pool[5 * (size_t)i + 3]), static_cast<uint8_t*>(st->pool[5 * (size_t)n + 1 + (size_t)i]));
+      if (mb.size() == kRgbaChunk) HIP_TRY(mb.launch(s));
+    }
+    HIP_TRY(mb.launch(s));
+  }
 
   // the SDR rendition: the conversions of up to kRgbaChunk files share a launch, a host caller's copies follow it
   RgbaBatches rgb;
@@ -2063,7 +2192,13 @@ int uhdr_hip_jpegr_decode_batch_ex(int n, const void* const* jpegr, const size_t
     gimg.pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
     uhdr_hip_image_t ddev = dests[i];
     ddev.data = host ? st->pool[5 * (size_t)i + 4] : dest_data[i];
-    st_[i] = uhdr_hip_apply_gainmap(&ydesc, &gimg, &f.md, output_format, max_display_boost, &ddev, apply_mode, UHDR_HIP_MEM_DEVICE, stream);
+    if (rgb_maps && !f.info[1].gray) {
+      gimg.data = st->pool[5 * (size_t)n + 1 + (size_t)i];
+      gimg.pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
+      st_[i] = uhdr_hip_apply_gainmap_rgb_batch(1, &ydesc, &gimg, &f.md, output_format, max_display_boost, &ddev, apply_mode, stream);
+    } else {
+      st_[i] = uhdr_hip_apply_gainmap(&ydesc, &gimg, &f.md, output_format, max_display_boost, &ddev, apply_mode, UHDR_HIP_MEM_DEVICE, stream);
+    }
     if (st_[i] != UHDR_HIP_NO_ERROR) continue;
     dests[i].data = dest_data[i];
     dests[i].width = ddev.width; dests[i].height = ddev.height;
@@ -2072,6 +2207,20 @@ int uhdr_hip_jpegr_decode_batch_ex(int n, const void* const* jpegr, const size_t
   if ((rc = convert()) != UHDR_HIP_NO_ERROR) return rc;
   HIP_TRY(hipStreamSynchronize(s));
   return finish_statuses(st_, status);
+}
+
+int uhdr_hip_jpegr_decode_batch_ex(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
+                                   void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
+                                   int* status, int apply_mode, int mem_space, void* stream, int flags) {
+  return jpegr_decode_files(n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode,
+                            mem_space, stream, flags, false);
+}
+
+int uhdr_hip_jpegr_decode_rgbmap_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
+                                       void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests,
+                                       uhdr_hip_metadata_t* metadata, int* status, int apply_mode, int mem_space, void* stream, int flags) {
+  return jpegr_decode_files(n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode,
+                            mem_space, stream, flags, true);
 }
 
 int uhdr_hip_jpegr_decode(const void* jpegr, size_t jpegr_size, int output_format, float max_display_boost, void* dest_data,
@@ -2198,6 +2347,13 @@ EncJpeg gainmap_jpeg(uhdr_hip_image_t map, size_t pad_ls) {
   map.chroma_data = nullptr; map.chroma_stride = 0; map.pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
   return EncJpeg{map, 85, nullptr, pad_ls, 0};
 }
+// the per-channel map (RGBA pixels) at the same quality, as a 4:4:4 file
+EncJpeg gainmap_rgb_jpeg(uhdr_hip_image_t map) {
+  map.chroma_data = nullptr; map.chroma_stride = 0; map.pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
+  EncJpeg e{map, 85, nullptr, 0, 0};
+  e.rgb = true;
+  return e;
+}
 
 // One round: staging (host callers), toneMap (API-0), generateGainMap, BT.601 re-encode -- one launch per step for the round's
 // files -- then the 2 m compressions with one synchronisation (compress_to_host).  Leaves file k's JPEGs in (*jpg)[2 k] (SDR) and
@@ -2208,7 +2364,8 @@ EncJpeg gainmap_jpeg(uhdr_hip_image_t map, size_t pad_ls) {
 // tonemap_op (API-0): the operator that derives the SDR planes; its headroom array is a pool slot of the context.
 int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_tf, int quality, EncFile* f, int m, uhdr_hip_metadata_t* md,
                  std::vector<EncJpeg>* jpg, int boost_scope = -1, float* range = nullptr, int carry = 0,
-                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT) {
+                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, bool rgb_map = false) {
+  const size_t map_bpp = rgb_map ? 4 : 1;   // rgb_map: uhdr_hip_generate_gainmap_rgb_batch's RGBA map, compressed as 4:4:4
   auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
   int rc;
   // sizes of the round's slices
@@ -2220,7 +2377,7 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
       if (!api0) yuv_total += al256(round_up(aw, 64) * h) + al256(round_up(aw, 64) * h);
     }
     if (f[k].own_copy) sdr_total += al256(aw * h * 3 / 2 + 64);
-    map_total += al256(mw * mh + 64);
+    map_total += al256(mw * mh * map_bpp + 64);
   }
   if ((rc = pool_reserve(st, kEncMap, map_total)) != 0) return rc;
   if (sdr_total && (rc = pool_reserve(st, kEncSdr, sdr_total)) != 0) return rc;
@@ -2270,7 +2427,7 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
     if (api0) e.yuv = e.enc;
     e.map = e.yuv;
     e.map.data = static_cast<uint8_t*>(st->pool[kEncMap]) + o_map;
-    o_map += al256((w / 4) * (h / 4) + 64);
+    o_map += al256((w / 4) * (h / 4) * map_bpp + 64);
   }
   std::vector<uhdr_hip_image_t> a((size_t)m), b((size_t)m), c((size_t)m);
   if (api0) {   // :208-226
@@ -2287,7 +2444,9 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
   // generateGainMap: the files are sorted by size and gamuts, so equal ones share its launches
   for (int k = 0; k < m; ++k) { a[k] = f[k].yuv; b[k] = f[k].p010; c[k] = f[k].map; }
   float* dev_range = nullptr;
-  if (boost_scope < 0) {
+  if (rgb_map) {
+    if ((rc = uhdr_hip_generate_gainmap_rgb_batch(m, a.data(), b.data(), hdr_tf, md, c.data(), 0, s)) != UHDR_HIP_NO_ERROR) return rc;
+  } else if (boost_scope < 0) {
     if ((rc = uhdr_hip_generate_gainmap_batch(m, a.data(), b.data(), hdr_tf, md, c.data(), 0, nullptr, s)) != UHDR_HIP_NO_ERROR) return rc;
   } else {
     const size_t ws_bytes = adaptive_layout(m, a.data()).total;
@@ -2326,7 +2485,7 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
     uhdr_hip_image_t g = e.map;
     g.width = e.enc.width / 4; g.height = e.enc.height / 4; g.luma_stride = g.width;
     jpg->push_back(EncJpeg{e.enc, quality, &e.icc, e.pad_ls, e.pad_cs});
-    jpg->push_back(gainmap_jpeg(g, g.luma_stride));
+    jpg->push_back(rgb_map ? gainmap_rgb_jpeg(g) : gainmap_jpeg(g, g.luma_stride));
   }
   return compress_to_host(st, s, 2 * m, jpg->data(), true, dev_range, dev_range ? 8 * (size_t)m : 0, range);
 }
@@ -2336,7 +2495,7 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
 int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
                  const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
                  int* status, int mem_space, void* stream, int boost_scope = -1, uhdr_hip_metadata_t* metadata = nullptr,
-                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, const float* hdr_peak_nits = nullptr) {
+                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, const float* hdr_peak_nits = nullptr, bool rgb_map = false) {
   const bool api0 = yuv420_images == nullptr;
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
   std::vector<EncFile> files;
@@ -2396,7 +2555,7 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
         EncFile* f = &files[r0];
         uhdr_hip_metadata_t md;
         std::vector<EncJpeg> jpg;
-        if ((rc = encode_round(st, s, api0, host, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry, tonemap_op)) != UHDR_HIP_NO_ERROR)
+        if ((rc = encode_round(st, s, api0, host, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry, tonemap_op, rgb_map)) != UHDR_HIP_NO_ERROR)
           return rc;
         std::vector<uhdr_hip_metadata_t> mds;   // adaptive: every file's own
         if (boost_scope < 0 && metadata)
@@ -2514,6 +2673,19 @@ int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, cons
     return UHDR_HIP_ERROR_BAD_PTR;
   if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
   return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream);
+}
+
+// the same with the per-channel map of uhdr_hip_generate_gainmap_rgb_batch, compressed at quality 85 as a 4:4:4 file; primary image,
+// metadata and container are uhdr_hip_jpegr_encode_batch's
+int uhdr_hip_jpegr_encode_rgbmap_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                                       const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                       size_t* out_size, int* status, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, -1,
+                      nullptr, UHDR_HIP_TONEMAP_SHIFT, nullptr, true);
 }
 
 int uhdr_hip_jpegr_encode_adaptive_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf,
@@ -3064,6 +3236,104 @@ int uhdr_hip_generate_gainmap_batch_ex(int n, const uhdr_hip_image_t* yuvs, cons
     HIP_TRY(launch_generate(c, b, m, hdr_tf, aligned, lut, filter, s));
     if (resolve) HIP_TRY(launch_stats_resolve(c, b, m, hdr_tf, aligned, s));
     else if (keys != nullptr) HIP_TRY(launch_stats_finalize(keys + 2 * i, m, s));
+    i += m;
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
+// Per-channel (RGB) gain maps: uhdr_hip_generate_gainmap_batch's checks, chunks and metadata; the map is
+// RGBA8888 and every chunk one k_generate_rgb launch on the exact path
+int uhdr_hip_generate_gainmap_rgb_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf,
+                                        uhdr_hip_metadata_t* metadata, uhdr_hip_image_t* dests, int sdr_is_601, void* stream) {
+  if (n < 0 || (n > 0 && (yuvs == nullptr || p010s == nullptr || dests == nullptr)) || metadata == nullptr)
+    return UHDR_HIP_ERROR_BAD_PTR;
+  for (int i = 0; i < n; ++i) {
+    const int rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, metadata, &dests[i]);
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
+    if (dests[i].data == nullptr || !al(dests[i].data, 4)) return UHDR_HIP_ERROR_BAD_PTR;
+  }
+  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ)
+    return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  DeviceState* st = nullptr;
+  const int rc = current_state(&st);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  fill_generate_metadata(hdr_tf, metadata);
+  int i = 0;
+  while (i < n) {
+    // chunk = up to kMaxChunk consecutive images of identical size, gamuts and alignment class
+    const uhdr_hip_image_t& y0 = yuvs[i];
+    const GenConsts c = generate_consts(y0.colorGamut, p010s[i].colorGamut, hdr_tf, sdr_is_601, y0.width, y0.height, *metadata);
+    GenBatch b;
+    int m = 0;
+    bool aligned = true;
+    while (i + m < n && m < kMaxChunk) {
+      const uhdr_hip_image_t& y = yuvs[i + m];
+      if (y.width != y0.width || y.height != y0.height || y.colorGamut != y0.colorGamut ||
+          p010s[i + m].colorGamut != p010s[i].colorGamut)
+        break;
+      b.img[m] = gen_image(y, p010s[i + m], dests[i + m].data);
+      const bool a = gen_aligned(b.img[m], c.width, c.height) && al(b.img[m].map, 8);   // (the pair of a thread is one 8-byte store)
+      if (m == 0) aligned = a;
+      else if (a != aligned) break;
+      fill_generate_dest(&y, &dests[i + m]);
+      dests[i + m].pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
+      ++m;
+    }
+    HIP_TRY(launch_generate_rgb(c, b, m, hdr_tf, aligned, s));
+    i += m;
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
+// uhdr_hip_apply_gainmap_batch's checks and chunks for RGBA8888 maps (luma_stride in pixels, 0 = width): every chunk one
+// k_apply_px_rgb launch, FAST or the unfiltered exact arithmetic
+int uhdr_hip_apply_gainmap_rgb_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* maps, const uhdr_hip_metadata_t* metadata,
+                                     int output_format, float max_display_boost, uhdr_hip_image_t* dests, int apply_mode, void* stream) {
+  if (n < 0 || (n > 0 && (yuvs == nullptr || maps == nullptr || dests == nullptr)) || metadata == nullptr)
+    return UHDR_HIP_ERROR_BAD_PTR;
+  auto stride_of = [](const uhdr_hip_image_t& mp) { return mp.luma_stride == 0 ? mp.width : mp.luma_stride; };
+  for (int i = 0; i < n; ++i) {
+    const int rc = validate_apply(&yuvs[i], &maps[i], metadata, &dests[i]);
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
+    if (!al(maps[i].data, 4)) return UHDR_HIP_ERROR_BAD_PTR;
+    if (stride_of(maps[i]) < maps[i].width || stride_of(maps[i]) > 0xFFFFFFFFull) return UHDR_HIP_ERROR_INVALID_STRIDE;
+  }
+  if (apply_mode != UHDR_HIP_APPLY_FAST && apply_mode != UHDR_HIP_APPLY_EXACT)   // (LUT and EXACT_UNFILTERED among the rest)
+    return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  DeviceState* st = nullptr;
+  int rc = current_state(&st);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool writes = apply_writes(output_format);
+  for (int i = 0; i < n; ++i)
+    if (writes && dests[i].data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  int i = 0;
+  while (i < n) {
+    const uhdr_hip_image_t& y0 = yuvs[i];
+    const uhdr_hip_image_t& m0 = maps[i];
+    const int scale = (int)(y0.width / m0.width);
+    const float* idw = nullptr;
+    float* idw_transient = nullptr;
+    if ((rc = idw_for_scale(st, scale, &idw, &idw_transient)) != UHDR_HIP_NO_ERROR) return rc;
+    struct FreeAfter {   // a table too large to keep: freed when this chunk's launches have finished
+      float* p; hipStream_t s;
+      ~FreeAfter() { if (p) { (void)hipStreamSynchronize(s); (void)hipFree(p); } }
+    } free_after{idw_transient, s};
+    AppConsts c = apply_consts(y0, m0, *metadata, max_display_boost, idw);
+    c.map_stride = (uint32_t)stride_of(m0);
+    c.tab = st->lut;
+    AppBatch b;
+    int m = 0;
+    while (i + m < n && m < kMaxChunk) {   // equal sizes and map strides share a launch
+      const uhdr_hip_image_t& y = yuvs[i + m];
+      const uhdr_hip_image_t& mp = maps[i + m];
+      if (y.width != y0.width || y.height != y0.height || mp.width != m0.width || mp.height != m0.height || stride_of(mp) != stride_of(m0)) break;
+      b.img[m] = app_image(y, mp, dests[i + m].data);
+      fill_apply_dest(&y, &dests[i + m]);
+      ++m;
+    }
+    if (writes) HIP_TRY(launch_apply_rgb(c, b, m, output_format, apply_mode == UHDR_HIP_APPLY_EXACT, s));
     i += m;
   }
   return UHDR_HIP_NO_ERROR;

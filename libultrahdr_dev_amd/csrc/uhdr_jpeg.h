@@ -22,6 +22,7 @@ struct Job {
   uint32_t ybw, ybh;       // luma size in blocks
   uint32_t mcus_x;         // MCUs per row (4:2:0)
   int gray;
+  int rgb;                 // 4:4:4 from interleaved RGBA (plane[0]: the pixels, stride in bytes); an MCU is one block each of Y, Cb, Cr
   // workspace (device)
   int16_t* coef;           // nblk x 64, zigzag order
   uint32_t* bits;          // nblk (+1 zero)
@@ -40,7 +41,9 @@ struct Layout {
 hipError_t upload_tables();
 void quant_table(int quality, bool chroma, uint16_t out_natural[64]);
 void zigzag_table(const uint16_t natural[64], uint16_t zz[64]);
-void build_header(int w, int h, bool gray, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& out);
+// geom: what the frame header declares -- the 4:2:0 and single-plane files of the reference's encoder, or three 1x1 components
+enum Geometry : int { kGeom420 = 0, kGeomGray = 1, kGeomRgb444 = 2 };
+void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& out);
 size_t workspace_bytes(uint32_t nblk, Layout* l);
 // enqueues the whole encoder; the JPEG (without the header, which the caller places at out[0, header_len)) lands at
 // out + header_len, its total size (header included) in the uint64 at ws + l.totals + 8

@@ -118,7 +118,8 @@ void put_dht(std::vector<uint8_t>& b, int cls_idx, const uint8_t bits[16], const
 }
 }  // namespace
 
-void build_header(int w, int h, bool gray, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& b) {
+void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& b) {
+  const bool gray = geom == kGeomGray;
   uint16_t ql[64], qc[64];
   quant_table(quality, false, ql);
   quant_table(quality, true, qc);
@@ -138,7 +139,7 @@ void build_header(int w, int h, bool gray, int quality, const void* icc, size_t 
   b.push_back((uint8_t)nc);
   for (int c = 0; c < nc; ++c) {
     b.push_back((uint8_t)(c + 1));
-    b.push_back((uint8_t)((c == 0 && !gray) ? 0x22 : 0x11));
+    b.push_back((uint8_t)((c == 0 && geom == kGeom420) ? 0x22 : 0x11));
     b.push_back((uint8_t)(c == 0 ? 0 : 1));
   }
   put_dht(b, 0x00, kBitsDcLum, kValsDc);
@@ -155,11 +156,19 @@ void build_header(int w, int h, bool gray, int quality, const void* icc, size_t 
 // ---- block geometry -----------------------------------------------------------------------------------------------
 // Entropy-coding order (libjpeg jccoefct.c): one plane: blocks in raster order; 4:2:0: per MCU (16x16 pixels) Y00 Y01 Y10 Y11
 // Cb Cr.  Blocks past the component's size in blocks are dummies: zero AC, DC of the block before them in the MCU.
+// 4:4:4 from RGBA (Job::rgb): per MCU (8x8 pixels) Y Cb Cr, MCUs in raster order; no dummies.
 struct BlockRef {
   int comp;        // 0 Y, 1 Cb, 2 Cr
   int br, bc;      // block row / column inside the component (of the source block for a dummy)
   bool dummy;
 };
+__device__ __forceinline__ BlockRef locate_rgb(const Job& j, uint32_t i) {
+  BlockRef b;
+  const uint32_t mcu = i / 3u;
+  b.comp = (int)(i - mcu * 3u);
+  b.br = (int)(mcu / j.ybw); b.bc = (int)(mcu - (uint32_t)b.br * j.ybw); b.dummy = false;
+  return b;
+}
 __device__ __forceinline__ BlockRef locate(const Job& j, uint32_t i) {
   BlockRef b;
   if (j.gray) {
@@ -182,6 +191,7 @@ __device__ __forceinline__ BlockRef locate(const Job& j, uint32_t i) {
 // index of the previous block of the same component (DC prediction), or UINT32_MAX for the first one
 __device__ __forceinline__ uint32_t dc_predecessor(const Job& j, uint32_t i) {
   if (j.gray) return i == 0u ? 0xFFFFFFFFu : i - 1u;
+  if (j.rgb) return i < 3u ? 0xFFFFFFFFu : i - 3u;
   const uint32_t mcu = i / 6u, k = i - mcu * 6u;
   if (k >= 4u) return mcu == 0u ? 0xFFFFFFFFu : i - 6u;
   if (k != 0u) return i - 1u;
@@ -262,6 +272,28 @@ __device__ __forceinline__ void load_samples(const Plane& p, const BlockRef& b, 
   }
 }
 
+// the same for component b.comp of an RGBA image (p: the pixels, 4-byte aligned, stride in bytes): jccolor.c's fixed-point RGB ->
+// YCbCr per sample; a block over the right or bottom edge repeats the last column, then the last row (libjpeg's expand_right_edge /
+// expand_bottom_edge -- on converted samples there, which is the conversion of the repeated pixel)
+__device__ __forceinline__ void load_samples_rgb(const Plane& p, const BlockRef& b, int (&d)[64]) {
+  const int r0 = b.br * 8, c0 = b.bc * 8;
+  const int kr = b.comp == 0 ? 19595 : b.comp == 1 ? -11059 : 32768;
+  const int kg = b.comp == 0 ? 38470 : b.comp == 1 ? -21709 : -27439;
+  const int kb = b.comp == 0 ? 7471 : b.comp == 1 ? 32768 : -5329;
+  const int bias = b.comp == 0 ? 32768 : (128 << 16) + 32767;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const int rr = min(r0 + r, p.h - 1);
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(p.p + (size_t)rr * p.stride);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const uint32_t px = row[min(c0 + c, p.w - 1)];
+      const int v = kr * (int)(px & 0xffu) + kg * (int)((px >> 8) & 0xffu) + kb * (int)((px >> 16) & 0xffu) + bias;
+      d[r * 8 + c] = (v >> 16) - 128;
+    }
+  }
+}
+
 // ---- entropy coding ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int nbits_of(int a) { return a == 0 ? 0 : 32 - __builtin_clz((unsigned)a); }
 
@@ -312,35 +344,43 @@ __device__ __forceinline__ int pred_of(const Job& j, uint32_t i) {
   const uint32_t p = dc_predecessor(j, i);
   return p == 0xFFFFFFFFu ? 0 : (int)j.coef[(size_t)p * 64u];
 }
-__device__ __forceinline__ int comp_of(const Job& j, uint32_t i) { return j.gray ? 0 : ((i % 6u) < 4u ? 0 : 1); }
+__device__ __forceinline__ int comp_of(const Job& j, uint32_t i) {
+  if (j.rgb) return (i % 3u) == 0u ? 0 : 1;
+  return j.gray ? 0 : ((i % 6u) < 4u ? 0 : 1);
+}
 
 // One thread per 8x8 block: forward DCT, quantisation, the block's 64 coefficients to memory (zigzag order) -- and, while they are
 // in registers, the number of bits its Huffman code takes (the prefix sum of those is where k_jpeg_emit writes).  The DC code needs
 // the quantised DC of the component's previous block, which another thread computes: the islow DC is the plain sum of the 64
 // level-shifted samples (pass 1 scales the row sums by 4, pass 2 descales by 4: exact), so it is had from that block's 64 bytes.
+// RGB: the job is a 4:4:4 one (Job::rgb), known at compile time so that the planar kernels carry none of its code
+template <bool RGB>
 __device__ __forceinline__ uint32_t fdct_quant_count_block(const Job& j, const uint32_t i);
 // workgroup wg of the image's grid (blockIdx.x of the single-image launch; the batched launch passes its workgroup inside the job)
+template <bool RGB>
 __device__ __forceinline__ void fdct_quant_count_wg(const Job& j, const uint32_t wg) {
   const uint32_t i = wg * 128u + threadIdx.x;
   __shared__ uint32_t s_part[2];
   uint32_t my_bits = 0;
-  if (i < j.nblk) my_bits = fdct_quant_count_block(j, i);
+  if (i < j.nblk) my_bits = fdct_quant_count_block<RGB>(j, i);
   // bits_blk[g]: the bits of workgroup g's 128 blocks.  k_jpeg_emit needs the bit offset of every block: inside a workgroup a block
   // scan, across workgroups the sum of the totals in front (a 4K frame has 1519), formed by every workgroup of the emit for itself
   const uint32_t total = block_sum<128>(my_bits, s_part);
   if (threadIdx.x == 0u) j.bits_blk[wg] = total;
 }
-__global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count(const Job j) { fdct_quant_count_wg(j, blockIdx.x); }
+__global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count(const Job j) { fdct_quant_count_wg<false>(j, blockIdx.x); }
 
 // the work of one thread of k_jpeg_fdct_quant_count: block i's coefficients to memory, its number of bits returned
+template <bool RGB>
 __device__ __forceinline__ uint32_t fdct_quant_count_block(const Job& j, const uint32_t i) {
-  const BlockRef b = locate(j, i);
-  const Plane& p = j.plane[b.comp];
+  const BlockRef b = RGB ? locate_rgb(j, i) : locate(j, i);
+  const Plane& p = j.plane[RGB ? 0 : b.comp];
   const uint16_t* q = b.comp == 0 ? j.q_lum : j.q_chr;   // zigzag order
   const uint32_t* qm = b.comp == 0 ? j.m_lum : j.m_chr;
   int16_t* out = j.coef + (size_t)i * 64u;
   int d[64];
-  load_samples(p, b, d);
+  if (RGB) load_samples_rgb(p, b, d);
+  else load_samples(p, b, d);
   int16_t c[64];
   if (b.dummy) {  // zero AC, DC of the source block
     int s = 0;
@@ -372,7 +412,8 @@ __device__ __forceinline__ uint32_t fdct_quant_count_block(const Job& j, const u
   const uint32_t pi = dc_predecessor(j, i);
   if (pi != 0xFFFFFFFFu) {
     int e[64];
-    load_samples(p, locate(j, pi), e);   // (the same component, so the same plane and quantiser)
+    if (RGB) load_samples_rgb(p, locate_rgb(j, pi), e);
+    else load_samples(p, locate(j, pi), e);   // (the same component, so the same plane and quantiser)
     int s = 0;
 #pragma unroll
     for (int k = 0; k < 64; ++k) s += e[k];
@@ -564,7 +605,17 @@ __device__ __forceinline__ const T& uniform_ref(const T* p, uint32_t k) {
 __global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count_multi(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
   uint32_t first, count;
   const uint32_t k = job_of<128>(start, n, &first, &count);
-  fdct_quant_count_wg(uniform_ref(jobs, k), blockIdx.x - first);
+  const Job& j = uniform_ref(jobs, k);
+  if (j.rgb) return;   // (uniform per workgroup) a 4:4:4 job: k_jpeg_fdct_quant_count_multi_rgb's
+  fdct_quant_count_wg<false>(j, blockIdx.x - first);
+}
+// the 4:4:4 jobs of the same grid; the two kernels are launched as the batch holds jobs of either kind
+__global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count_multi_rgb(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  if (!j.rgb) return;
+  fdct_quant_count_wg<true>(j, blockIdx.x - first);
 }
 
 // The single-image path clears the whole worst-case stream area (208 B per block, 40 MB for a 4K frame) before the emit ORs into
@@ -674,7 +725,9 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
   uint32_t* blk_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(o) + up256((size_t)n * sizeof(BatchOut)));
   uint32_t* stuff_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(blk_start) + up256(((size_t)n + 1) * 4));
   blk_start[0] = stuff_start[0] = 0;
+  bool any_planar = false, any_rgb = false;
   for (int k = 0; k < n; ++k) {
+    (jobs_in[k].rgb ? any_rgb : any_planar) = true;
     Job& j = jobs[k];
     j = jobs_in[k];
     uint8_t* w = ws[k];
@@ -699,7 +752,8 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
   const uint32_t* dstuff = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(stuff_start) - host_desc));
   const uint32_t nj = (uint32_t)n;
   const dim3 gb(blk_start[n]), bb(128), gc(stuff_start[n]), bc(256);
-  hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi, gb, bb, 0, s, dj, dblk, nj);
+  if (any_planar) hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi, gb, bb, 0, s, dj, dblk, nj);
+  if (any_rgb) hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi_rgb, gb, bb, 0, s, dj, dblk, nj);
   hipLaunchKernelGGL(k_jpeg_clear_multi, gb, bb, 0, s, dj, dblk, nj);
   hipLaunchKernelGGL(k_jpeg_emit_multi, gb, bb, 0, s, dj, dblk, nj);
   hipLaunchKernelGGL(k_jpeg_stuff_count_multi, gc, bc, 0, s, dj, dstuff, nj);

@@ -154,6 +154,7 @@ struct AppConsts {
   uint32_t* ex_ws;                // EXACT mode behind the f32 pre-filter: the lists of pixels in doubt (layout below), or nullptr
   uint32_t ex_cap;                // entries per list
   AppFast fast;
+  uint32_t map_stride;            // k_apply_px_rgb: pixels between the rows of the RGBA map (the single-channel kernels: rows of map_w bytes)
 };
 // EXACT apply's workspace, one per stream: kMaxChunk headers of kExHdrWords words (word 3: slices of k_apply_resolve that have
 // finished; words 8 ..: the lengths of the image's kExLists lists), then kMaxChunk x kExLists lists of ex_cap pixel indices.  The
@@ -277,6 +278,9 @@ hipError_t launch_stats_finalize(uint32_t* keys, int n, hipStream_t s);
 hipError_t launch_adaptive_init(uint32_t* keys, uint32_t words, hipStream_t s);   // keys[0 .. words) = 0, as a kernel
 // pass 1 of n <= kMaxChunk images of one size: GenImage::map points at the image's GAINS (float, 16-byte aligned), c.stat_keys at its keys
 hipError_t launch_generate_gains(const GenConsts& c, const GenBatch& b, int n, int hdr_tf, bool aligned, hipStream_t s);
+// per-channel (RGB) map of n <= kMaxChunk images of one size: GenImage::map points at map_w * map_h RGBA pixels, 4-byte aligned
+// (aligned launches: 8-byte aligned, map_w even); the exact path throughout, no statistics
+hipError_t launch_generate_rgb(const GenConsts& c, const GenBatch& b, int n, int hdr_tf, bool aligned, hipStream_t s);
 // the range rule and the encode constants of n images from their keys.  per_call: one range from the extremes of all n images and of
 // carry_in (two key words of earlier launches, or null); carry_out (or null) receives the merged pair.  content_minmax may be null.
 hipError_t launch_adaptive_consts(const uint32_t* keys, int n, int per_call, float cap, AdaptConsts* consts, float* content_minmax,
@@ -286,6 +290,8 @@ hipError_t launch_encode_gains(const AdaptConsts* consts, const EncGainBatch& b,
 // mode: 0 FAST, 1 EXACT, 2 LUT
 hipError_t launch_apply(const AppConsts& c, const AppBatch& b, int n, int fmt, int mode,
                         bool fast_s4, hipStream_t s);
+// per-pixel apply of RGBA maps (AppImage::map 4-byte aligned, AppConsts::map_stride set): FAST or the unfiltered EXACT arithmetic
+hipError_t launch_apply_rgb(const AppConsts& c, const AppBatch& b, int n, int fmt, bool exact, hipStream_t s);
 hipError_t launch_build_luts(float* lut /* kLutTotal floats */, hipStream_t s);
 hipError_t launch_build_lut_codes(float* lut /* the whole buffer: reads the two OETF tables, writes kCodeHlg / kCodePq */, hipStream_t s);
 // GainLUT table (kGainLutN floats, device) for (log2 min, log2 max, boost factor)

@@ -219,8 +219,10 @@ __device__ __forceinline__ float cvt_word1(uint32_t w) {
 // PART: the function in two halves, for the pairs the streaming kernel hands to k_generate_resolve WITH their sampled values:
 // kGenFront stops in front of the transfer functions and returns their inputs in *mid (both pixels' r, g, b, hr, hg, hb -- what the
 // filter and the exact path both start from), kGenBack takes them from *mid instead of sampling; kGenWhole with mid != nullptr runs
-// as ever and leaves a copy in *mid.
-constexpr int kGenWhole = 0, kGenFront = 1, kGenBack = 2;
+// as ever and leaves a copy in *mid.  kGenLinear (exact path only) stops in front of the luminances and returns in *mid the two
+// LINEAR colours of both pixels -- SDR, and HDR converted into the SDR gamut --, which is where the per-channel map (k_generate_rgb)
+// parts from the single-channel one.
+constexpr int kGenWhole = 0, kGenFront = 1, kGenBack = 2, kGenLinear = 3;
 struct GenMid { f2 r, g, b, hr, hg, hb; };
 template <int TF, bool LUT, bool FILTER, bool DEFER = false, int PART = kGenWhole>
 __device__ __forceinline__ uint32_t gen_pair(const GenConsts& c, const uint32_t (&hy)[2][4][2],
@@ -291,7 +293,8 @@ __device__ __forceinline__ uint32_t gen_pair(const GenConsts& c, const uint32_t 
   hg = pk_add_sat(hsy - splat(c.hdr_gcb) * hsu, -(splat(c.hdr_gcr) * hsv));
   hb = pk_add_sat(hsy, splat(c.hdr_cb) * hsu);
   }
-  if (PART != kGenBack && mid != nullptr) { mid->r = r; mid->g = g; mid->b = b; mid->hr = hr; mid->hg = hg; mid->hb = hb; }
+  static_assert(PART != kGenLinear || (!LUT && !FILTER), "kGenLinear is the exact path's");
+  if (PART != kGenBack && PART != kGenLinear && mid != nullptr) { mid->r = r; mid->g = g; mid->b = b; mid->hr = hr; mid->hg = hg; mid->hb = hb; }
   if (PART == kGenFront) return 0u;
 
   if (FILTER && !LUT) {
@@ -393,6 +396,7 @@ __device__ __forceinline__ uint32_t gen_pair(const GenConsts& c, const uint32_t 
     const f2 t2 = splat(c.gm[6]) * hr + splat(c.gm[7]) * hg + splat(c.gm[8]) * hb;
     hr = t0; hg = t1; hb = t2;
   }
+  if (PART == kGenLinear) { mid->r = r; mid->g = g; mid->b = b; mid->hr = hr; mid->hg = hg; mid->hb = hb; return 0u; }
   const f2 hdr_nits = (splat(c.lum_r) * hr + splat(c.lum_g) * hg + splat(c.lum_b) * hb) * splat(c.hdr_white_nits);
 
   gain[0] = raw_gain(sdr_nits.x, hdr_nits.x);
@@ -1047,6 +1051,78 @@ hipError_t launch_generate_gains(const GenConsts& c, const GenBatch& b, int n, i
     case 0: return launch_generate_gains_tf<0>(c, b, n, aligned, s);
     case 1: return launch_generate_gains_tf<1>(c, b, n, aligned, s);
     case 2: return launch_generate_gains_tf<2>(c, b, n, aligned, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// Per-channel (RGB) gain map: k_generate_gains' grid and front end on the exact path up to the two linear
+// colours (gen_pair<kGenLinear>), then encodeGain(sdr.c * 203, hdr.c * white) per channel instead of once on the luminances.  A map
+// pixel is the dword R | G << 8 | B << 16 | 0xFF << 24 (GenImage::map: 4-byte aligned, rows of map_w pixels); the aligned form
+// stores a thread's pair as 8 bytes.
+template <int TF, bool ALIGNED, int TILES>
+__global__ void __launch_bounds__(kGenBlock, 1) k_generate_rgb(const GenConsts c, const GenBatch b) {
+  const uint32_t img_i = blockIdx.x, blk = blockIdx.y;
+  const GenImage& im = b.img[img_i];
+  const uint8_t* im_v = im.u + (size_t)im.c_stride * (c.height / 2u);
+  uint32_t* map = reinterpret_cast<uint32_t*>(im.map);
+  const uint32_t pairs_per_row = (c.map_w + 1u) >> 1;
+  const uint32_t total = pairs_per_row * c.map_h;
+#pragma unroll 1
+  for (uint32_t t = 0; t < (uint32_t)TILES; ++t) {
+    const uint32_t idx = (blk * (uint32_t)TILES + t) * (uint32_t)kGenBlock + threadIdx.x;
+    if (idx >= total) break;
+    const uint32_t my = idx / pairs_per_row;
+    const uint32_t pr = idx - my * pairs_per_row;
+    const uint32_t mx = pr * 2u;
+    const bool two = ALIGNED || (mx + 1u < c.map_w);
+    uint32_t hy[2][4][2], huv[2][2][2], y8[2][4], u8[2][2], v8[2][2];
+    load_pair<ALIGNED>(c, im, im_v, my, pr, two, hy, huv, y8, u8, v8);
+    uint8_t o[2];
+    float gn[2];
+    GenMid lin;
+    gen_pair<TF, false, false, false, kGenLinear>(c, hy, huv, y8, u8, v8, o, gn, nullptr, nullptr, &lin);   // (a missing second pixel: zeros, dropped)
+    const f2 sdr[3] = {lin.r * splat(203.0f), lin.g * splat(203.0f), lin.b * splat(203.0f)};
+    const f2 hdr[3] = {lin.hr * splat(c.hdr_white_nits), lin.hg * splat(c.hdr_white_nits), lin.hb * splat(c.hdr_white_nits)};
+    uint32_t px[2] = {0xFF000000u, 0xFF000000u};
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const float gain = raw_gain(k ? sdr[ch].y : sdr[ch].x, k ? hdr[ch].y : hdr[ch].x);
+        px[k] |= (uint32_t)encode_gain_guarded(gain, c.min_boost, c.max_boost, c.log2_min, c.log2_max, c.enc_scale, c.enc_byte_min,
+                                               c.enc_byte_max) << (8 * ch);
+      }
+    }
+    uint32_t* mp = map + (size_t)my * c.map_w + mx;
+    if (ALIGNED) {   // map_w is even and the map 8-byte aligned
+      *reinterpret_cast<uint2*>(mp) = make_uint2(px[0], px[1]);
+    } else {
+      mp[0] = px[0];
+      if (two) mp[1] = px[1];
+    }
+  }
+}
+template <int TF>
+static hipError_t launch_generate_rgb_tf(const GenConsts& c, const GenBatch& b, int n, bool aligned, hipStream_t s) {
+  const uint32_t total = ((c.map_w + 1u) >> 1) * c.map_h;
+  if (total == 0 || n == 0) return hipSuccess;
+  const bool small = generate_is_small(c, n);   // spans per block as launch_generate_t chooses them
+  const unsigned per = (unsigned)kGenBlock * (small ? 1u : (unsigned)kGenTiles);
+  const dim3 g((unsigned)n, (total + per - 1u) / per, 1), blk(kGenBlock, 1, 1);
+  if (small) {
+    if (aligned) hipLaunchKernelGGL((k_generate_rgb<TF, true, 1>), g, blk, 0, s, c, b);
+    else hipLaunchKernelGGL((k_generate_rgb<TF, false, 1>), g, blk, 0, s, c, b);
+  } else {
+    if (aligned) hipLaunchKernelGGL((k_generate_rgb<TF, true, kGenTiles>), g, blk, 0, s, c, b);
+    else hipLaunchKernelGGL((k_generate_rgb<TF, false, kGenTiles>), g, blk, 0, s, c, b);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_generate_rgb(const GenConsts& c, const GenBatch& b, int n, int hdr_tf, bool aligned, hipStream_t s) {
+  switch (hdr_tf) {
+    case 0: return launch_generate_rgb_tf<0>(c, b, n, aligned, s);
+    case 1: return launch_generate_rgb_tf<1>(c, b, n, aligned, s);
+    case 2: return launch_generate_rgb_tf<2>(c, b, n, aligned, s);
     default: return hipErrorInvalidValue;
   }
 }
@@ -1803,14 +1879,26 @@ __global__ void __launch_bounds__(kApplyBlock, 4) k_apply_s4(const AppConsts c, 
 // General path: one thread per pixel; any integer scale, any pointer/stride alignment, FAST or
 // EXACT arithmetic.  Mirrors ultrahdr.cpp:427-496 + gainmapmath.cpp:686-720 literally.
 struct PxIn { float yf, u, v, gain; };
-// the loads of ultrahdr.cpp:431-438 and sampleMap (gainmapmath.cpp:686-720) for pixel idx
+// sampleMap's address arithmetic (gainmapmath.cpp:686-720) for pixel (x, y): the four taps' map coordinates and the pixel's weights
+struct PxTaps { uint32_t xl, xu, yl, yu; const float* w; };
+__device__ __forceinline__ PxTaps px_taps(const AppConsts& c, uint32_t x, uint32_t y);
+// the loads of ultrahdr.cpp:431-438 and sampleMap for pixel (x, y)
 __device__ __forceinline__ PxIn px_inputs(const AppConsts& c, const AppImage& im, uint32_t x, uint32_t y) {
   PxIn in;
   in.yf = (float)im.y[(size_t)y * im.y_stride + x] * k255;
   const size_t ci = (size_t)(y >> im.csy) * im.c_stride + (x >> im.csx);   // 4:2:0: (x >> 1, y >> 1), as getYuv420Pixel
   in.u = (float)((int)im.u[ci] - 128) * k255;
   in.v = (float)((int)im.v[ci] - 128) * k255;
-
+  const PxTaps t = px_taps(c, x, y);
+  // (byte / 255.0f through the constant division that is proven equal for all 256 bytes, tests/test_gpu_transfer_exhaustive.py)
+  const float e1 = map_to_float_fast(im.map[(size_t)t.yl * c.map_w + t.xl]);
+  const float e2 = map_to_float_fast(im.map[(size_t)t.yu * c.map_w + t.xl]);
+  const float e3 = map_to_float_fast(im.map[(size_t)t.yl * c.map_w + t.xu]);
+  const float e4 = map_to_float_fast(im.map[(size_t)t.yu * c.map_w + t.xu]);
+  in.gain = e1 * t.w[0] + e2 * t.w[1] + e3 * t.w[2] + e4 * t.w[3];
+  return in;
+}
+__device__ __forceinline__ PxTaps px_taps(const AppConsts& c, uint32_t x, uint32_t y) {
   const uint32_t s = c.scale;
   uint32_t xl, yl, ox, oy;
   if ((s & (s - 1u)) == 0u) {   // (a launch-uniform branch: scale factors are powers of two in practice)
@@ -1822,18 +1910,14 @@ __device__ __forceinline__ PxIn px_inputs(const AppConsts& c, const AppImage& im
   uint32_t xu = xl + 1u, yu = yl + 1u;
   xl = min(xl, c.map_w - 1u); xu = min(xu, c.map_w - 1u);
   yl = min(yl, c.map_h - 1u); yu = min(yu, c.map_h - 1u);
-  // (byte / 255.0f through the constant division that is proven equal for all 256 bytes, tests/test_gpu_transfer_exhaustive.py)
-  const float e1 = map_to_float_fast(im.map[(size_t)yl * c.map_w + xl]);
-  const float e2 = map_to_float_fast(im.map[(size_t)yu * c.map_w + xl]);
-  const float e3 = map_to_float_fast(im.map[(size_t)yl * c.map_w + xu]);
-  const float e4 = map_to_float_fast(im.map[(size_t)yu * c.map_w + xu]);
   int tbl = 0;
   if (xl == xu && yl == yu) tbl = 3;
   else if (xl == xu) tbl = 1;
   else if (yl == yu) tbl = 2;
-  const float* w = c.idw + (size_t)tbl * s * s * 4u + (size_t)oy * s * 4u + ox * 4u;
-  in.gain = e1 * w[0] + e2 * w[1] + e3 * w[2] + e4 * w[3];
-  return in;
+  PxTaps t;
+  t.xl = xl; t.xu = xu; t.yl = yl; t.yu = yu;
+  t.w = c.idw + (size_t)tbl * s * s * 4u + (size_t)oy * s * 4u + ox * 4u;
+  return t;
 }
 // the per-pixel kernels run on a (column block, row, image) grid: no division by the width; rows beyond the grid's 65535 are
 // reached by striding
@@ -1864,6 +1948,74 @@ __global__ void __launch_bounds__(256) k_apply_px(const AppConsts c, const AppBa
     const PxIn in = px_inputs(c, im, x, y);
     const F3 lin = recover_hdr<EXACT>(c, in.yf, kP3Cr * in.v, kP3GCb * in.u, kP3GCr * in.v, kP3Cb * in.u, in.gain);
     px_store<FMT>(im, (size_t)y * c.width + x, total, hdr_oetf<FMT, EXACT>(lin));
+  }
+}
+
+// ---- per-channel (RGB) gain maps -----------------------------------------------------------------------
+// The map is interleaved R, G, B, A bytes (AppImage::map 4-byte aligned, rows AppConsts::map_stride pixels apart): one dword load per
+// tap holds its three gains.  sampleMap's taps and weights are the pixel's (px_taps), applied to each channel of the taps; applyGain
+// runs per channel.  Every operation behind the gain is per channel, so channel c of a pixel is, bit for bit, channel c of
+// k_apply_px<FMT, EXACT> run with plane c of the map.
+template <bool EXACT>
+__device__ __forceinline__ F3 recover_hdr_rgb(const AppConsts& c, float yf, float crv, float gcbu, float gcrv, float cbu,
+                                              const float (&gain)[3]) {
+  float ch[3] = {clamp01(yf + crv), clamp01(yf - gcbu - gcrv), clamp01(yf + cbu)};
+  float o[3];
+  if (EXACT) srgb_inv_oetf_guarded_n<3>(ch);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float log_boost = (float)(c.log2_min_d * (double)(1.0f - gain[k]) + c.log2_max_d * (double)gain[k]);
+    if (EXACT) {
+      const float factor = exp2_to_float_guarded(log_boost * c.display_boost / c.max_boost);
+      o[k] = (ch[k] * factor) / c.display_boost;
+    } else {
+      const float factor = __builtin_amdgcn_exp2f((log_boost * c.display_boost) * c.inv_max_boost);
+      o[k] = (srgb_inv_oetf_fast(ch[k]) * factor) * c.inv_display_boost;
+    }
+  }
+  F3 r;
+  r.x = o[0]; r.y = o[1]; r.z = o[2];
+  return r;
+}
+template <int FMT, bool EXACT>
+__global__ void __launch_bounds__(256) k_apply_px_rgb(const AppConsts c, const AppBatch b) {
+  const AppImage& im = b.img[blockIdx.z];
+  const uint32_t* map = reinterpret_cast<const uint32_t*>(im.map);
+  const size_t total = (size_t)c.width * c.height;
+  const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+  if (x >= c.width) return;
+  for (uint32_t y = blockIdx.y; y < c.height; y += gridDim.y) {
+    const float yf = (float)im.y[(size_t)y * im.y_stride + x] * k255;
+    const size_t ci = (size_t)(y >> im.csy) * im.c_stride + (x >> im.csx);
+    const float u = (float)((int)im.u[ci] - 128) * k255, v = (float)((int)im.v[ci] - 128) * k255;
+    const PxTaps t = px_taps(c, x, y);
+    const uint32_t m1 = map[(size_t)t.yl * c.map_stride + t.xl], m2 = map[(size_t)t.yu * c.map_stride + t.xl];
+    const uint32_t m3 = map[(size_t)t.yl * c.map_stride + t.xu], m4 = map[(size_t)t.yu * c.map_stride + t.xu];
+    const float w0 = t.w[0], w1 = t.w[1], w2 = t.w[2], w3 = t.w[3];
+    float gain[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      gain[k] = map_to_float_fast((m1 >> (8 * k)) & 0xffu) * w0 + map_to_float_fast((m2 >> (8 * k)) & 0xffu) * w1 +
+                map_to_float_fast((m3 >> (8 * k)) & 0xffu) * w2 + map_to_float_fast((m4 >> (8 * k)) & 0xffu) * w3;
+    const F3 lin = recover_hdr_rgb<EXACT>(c, yf, kP3Cr * v, kP3GCb * u, kP3GCr * v, kP3Cb * u, gain);
+    px_store<FMT>(im, (size_t)y * c.width + x, total, hdr_oetf<FMT, EXACT>(lin));
+  }
+}
+template <int FMT>
+static hipError_t launch_apply_rgb_t(const AppConsts& c, const AppBatch& b, int n, bool exact, hipStream_t s) {
+  if (n == 0 || c.width == 0 || c.height == 0) return hipSuccess;
+  const dim3 grid = px_grid(c.width, c.height, n);
+  if (exact) hipLaunchKernelGGL((k_apply_px_rgb<FMT, true>), grid, dim3(256), 0, s, c, b);
+  else hipLaunchKernelGGL((k_apply_px_rgb<FMT, false>), grid, dim3(256), 0, s, c, b);
+  return hipGetLastError();
+}
+hipError_t launch_apply_rgb(const AppConsts& c, const AppBatch& b, int n, int fmt, bool exact, hipStream_t s) {
+  switch (fmt) {
+    case 1: return launch_apply_rgb_t<1>(c, b, n, exact, s);
+    case 2: return launch_apply_rgb_t<2>(c, b, n, exact, s);
+    case 3: return launch_apply_rgb_t<3>(c, b, n, exact, s);
+    case 4: return launch_apply_rgb_t<4>(c, b, n, exact, s);
+    default: return hipErrorInvalidValue;
   }
 }
 

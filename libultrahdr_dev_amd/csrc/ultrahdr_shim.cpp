@@ -311,12 +311,24 @@ int adaptive_one(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, int 
   return uhdr_hip_jpegr_encode_adaptive_batch(1, p010 ? p010 : &none, yuv, hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, nullptr, scope,
                                               UHDR_HIP_MEM_HOST, nullptr);
 }
+// one file through uhdr_hip_jpegr_encode_rgbmap_batch (setMultiChannelGainMap): API-1, or API-0 with yuv == nullptr
+int rgbmap_one(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, int hdr_tf, int quality, uhdr_exif_ptr exif, void* out, size_t cap, size_t* n) {
+  uhdr_hip_image_t none;
+  std::memset(&none, 0, sizeof(none));
+  const void* ex = exif_ptr(exif);
+  const size_t exn = exif_len(exif);
+  return uhdr_hip_jpegr_encode_rgbmap_batch(1, p010 ? p010 : &none, yuv, hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, UHDR_HIP_MEM_HOST, nullptr);
+}
 }  // namespace
 
 status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, ultrahdr_transfer_function hdr_tf, uhdr_compressed_ptr dest, int quality,
                                uhdr_exif_ptr exif) {
   uhdr_hip_image_t p;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
+  if (mMultiChannelGainMap)   // setMultiChannelGainMap: the per-channel map (it goes in front of setToneMap and setContentBoost, which stay single-channel)
+    return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
+      return rgbmap_one(p010_image_ptr ? &p : nullptr, nullptr, (int)hdr_tf, quality, exif, out, cap, n);
+    });
   if (mToneMapOp != UHDR_HIP_TONEMAP_SHIFT)   // setToneMap: one file through the tone-mapped batch, the single call's status the file's
     return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
       uhdr_hip_image_t none;
@@ -340,6 +352,12 @@ status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, uhdr_uncomp
   uhdr_hip_image_t p, y;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
   if (yuv420_image_ptr) y = to_c(*yuv420_image_ptr);
+  if (mMultiChannelGainMap) {
+    if (yuv420_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;   // jpegr.cpp:253-256 (a NULL array would mean API-0 to the batch)
+    return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
+      return rgbmap_one(p010_image_ptr ? &p : nullptr, &y, (int)hdr_tf, quality, exif, out, cap, n);
+    });
+  }
   if (mContentBoost >= 0) {
     if (yuv420_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;   // jpegr.cpp:253-256 (a NULL array would mean API-0 to the batch)
     return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
@@ -453,8 +471,16 @@ status_t JpegRHip::decodeJPEGR(uhdr_compressed_ptr jpegr_image_ptr, uhdr_uncompr
   uhdr_hip_metadata_t md;
   const size_t bpp = output_format == ULTRAHDR_OUTPUT_HDR_LINEAR ? 8 : output_format == ULTRAHDR_OUTPUT_HDR_LINEAR_RGB_10BIT ? 6 : 4;
   const bool want_md = metadata != nullptr || output_format != ULTRAHDR_OUTPUT_SDR;   // jpegr.cpp:754
-  rc = uhdr_hip_jpegr_decode_ex(file, n, (int)output_format, max_display_boost, dest->data, a.width * a.height * bpp, &d, want_md ? &md : nullptr,
-                                mApplyMode, UHDR_HIP_MEM_HOST, nullptr, mDecodeAnySampling ? UHDR_HIP_DECODE_ANY_SAMPLING : 0);
+  const int flags = mDecodeAnySampling ? UHDR_HIP_DECODE_ANY_SAMPLING : 0;
+  if (mMultiChannelGainMap) {   // a three-component gain map is applied per channel; every other file as below
+    void* out = dest->data;
+    const size_t cap = a.width * a.height * bpp;
+    rc = uhdr_hip_jpegr_decode_rgbmap_batch(1, &file, &n, (int)output_format, max_display_boost, &out, &cap, &d, want_md ? &md : nullptr, nullptr,
+                                            mApplyMode, UHDR_HIP_MEM_HOST, nullptr, flags);
+  } else {
+    rc = uhdr_hip_jpegr_decode_ex(file, n, (int)output_format, max_display_boost, dest->data, a.width * a.height * bpp, &d, want_md ? &md : nullptr,
+                                  mApplyMode, UHDR_HIP_MEM_HOST, nullptr, flags);
+  }
   if (rc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(rc);
   dest->width = d.width; dest->height = d.height;
   dest->colorGamut = static_cast<ultrahdr_color_gamut>(d.colorGamut);
