@@ -312,6 +312,16 @@ int uhdr_hip_effect_chain_map(size_t width, size_t height, size_t luma_stride, s
                               const uhdr_hip_effect_t* effects, int n_effects, uhdr_hip_image_t* out_desc, int* fused,
                               uint32_t* offsets, size_t capacity, size_t* count);
 
+/* Host-only diagnostic of the same composition (needs no GPU): which route of the chain kernel each output plane takes.  Inputs
+ * and statuses as uhdr_hip_effect_chain_map, and *fused is that call's.  *count = number of output planes the one launch would
+ * serve (fused chain with effects: 1 for MONOCHROME; for YUV420 luma first, then the chroma planes, of which crop and resize
+ * leave one stacked U|V plane; 0 when not fused and for n_effects == 0, which is a plain copy).  classes (may be NULL) receives
+ * min(capacity, *count) codes: 0 byte gather, 1 unit-step ascending columns (aligned 16-byte copies), 2 unit-step descending
+ * columns (16-byte pieces reversed), 3 monotone columns gathered from an LDS copy of the row stretch, 4 64 x 64 LDS tile. */
+int uhdr_hip_effect_chain_classes(size_t width, size_t height, size_t luma_stride, size_t chroma_stride, int pixel_format,
+                                  const uhdr_hip_effect_t* effects, int n_effects, int* fused, int* classes, size_t capacity,
+                                  size_t* count);
+
 /* ---- JPEG compression of the path's outputs (encode side) -------------------------------
  * JpegEncoderHelper::compressImage (lib/src/jpegencoderhelper.cpp:39-283; lib/include/ultrahdr/jpegencoderhelper.h:43-60):
  * baseline JPEG of a YUV420 image (image->data = Y, image->chroma_data = U, V at chroma_stride * height / 2) or, when

@@ -33,6 +33,7 @@ APPLY_FAST, APPLY_EXACT, APPLY_LUT, APPLY_EXACT_UNFILTERED = 0, 1, 2, 3
 GENERATE_EXACT, GENERATE_LUT, GENERATE_UNFILTERED = 0, 1, 2
 BOOST_PER_IMAGE, BOOST_PER_CALL = 0, 1          # content-adaptive gain maps: one boost range per image / per call
 TONEMAP_SHIFT, TONEMAP_REINHARD_MAXRGB = 0, 1   # API-0's SDR base image: the reference's bit shift / tone-mapped from linear light
+FXC_GATHER, FXC_ASC, FXC_DESC, FXC_LDS, FXC_TILE = 0, 1, 2, 3, 4   # uhdr_hip_effect_chain_classes: the chain kernel's route per plane
 ABI_VERSION = 3
 FLT_MAX = 3.4028234663852886e38
 
@@ -107,6 +108,8 @@ SIGNATURES = {
                                              C.c_void_p]),
     "uhdr_hip_effect_chain_map": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_int, _IP, C.POINTER(C.c_int),
                                             C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "uhdr_hip_effect_chain_classes": (C.c_int, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                                C.POINTER(C.c_int), C.c_size_t, C.POINTER(C.c_size_t)]),
     "uhdr_hip_jpeg_progressive_coefficients": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
                                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "uhdr_hip_jpeg_encode": (C.c_int, [_IP, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_int, C.c_void_p]),

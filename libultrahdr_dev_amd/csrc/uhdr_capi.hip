@@ -4593,6 +4593,26 @@ int uhdr_hip_effect_chain_map(size_t width, size_t height, size_t luma_stride, s
   }
 }
 
+int uhdr_hip_effect_chain_classes(size_t width, size_t height, size_t luma_stride, size_t chroma_stride, int pixel_format,
+                                  const uhdr_hip_effect_t* effects, int n_effects, int* fused, int* classes, size_t capacity,
+                                  size_t* count) {
+  if (fused == nullptr || count == nullptr || n_effects < 0 || (n_effects > 0 && effects == nullptr)) return UHDR_HIP_ERROR_BAD_PTR;
+  try {
+    uhdr_hip_image_t in = {};
+    in.width = width; in.height = height; in.luma_stride = luma_stride; in.chroma_stride = chroma_stride;
+    in.colorGamut = UHDR_HIP_CG_UNSPECIFIED; in.pixelFormat = pixel_format;
+    FxcPlan plan;
+    fx_compose(in, effects, n_effects, &plan);
+    if (plan.status != UHDR_HIP_NO_ERROR) return plan.status;
+    *fused = (n_effects == 0 || plan.fused) ? 1 : 0;
+    *count = plan.fused ? plan.cls.size() : 0;   // (no effects: a plain copy of the packed extent, no plane job)
+    for (size_t k = 0; classes != nullptr && k < *count && k < capacity; ++k) classes[k] = plan.cls[k];
+    return UHDR_HIP_NO_ERROR;
+  } catch (const std::bad_alloc&) {
+    return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  }
+}
+
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------

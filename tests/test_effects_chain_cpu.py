@@ -151,3 +151,105 @@ def test_edit_batch_call_level_errors_need_no_device(api):
     # every file stops at a check: no device needed
     rc = lib.uhdr_hip_jpegr_edit_batch(*args())
     assert list(status) == [rc, B] and rc in (api.ERROR_NO_IMAGES_FOUND, api.ERROR_GAIN_MAP_IMAGE_NOT_FOUND)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the class fx_finish picks per output plane (uhdr_hip_effect_chain_classes), both sides of every threshold
+# ---------------------------------------------------------------------------------------------------
+def _classes(api, w, h, mono, chain, ls=0):
+    """-> (status, fused, classes of the output planes)"""
+    lib = api.load()
+    fused, count, cls = C.c_int(-1), C.c_size_t(99), (C.c_int * 8)(*([-1] * 8))
+    rc = lib.uhdr_hip_effect_chain_classes(w, h, ls, 0, api.PIX_FMT_MONOCHROME if mono else api.PIX_FMT_YUV420, K.effect_array(api, chain), len(chain),
+                                           C.byref(fused), cls, 8, C.byref(count))
+    return rc, fused.value, tuple(cls[:count.value]) if rc == 0 else None
+
+
+def test_classes_unit_step_columns(api):
+    A = api
+    assert _classes(api, 64, 40, True, [K.crop(3, 50, 2, 30)]) == (0, 1, (A.FXC_ASC,))
+    assert _classes(api, 64, 40, False, [K.crop(2, 51, 2, 31)]) == (0, 1, (A.FXC_ASC, A.FXC_ASC))          # luma, the stacked U|V plane
+    assert _classes(api, 64, 40, True, [K.mirror(0)]) == (0, 1, (A.FXC_ASC,))                               # rows reversed, columns as they lie
+    assert _classes(api, 64, 40, True, [K.mirror(1)]) == (0, 1, (A.FXC_DESC,))
+    assert _classes(api, 64, 40, False, [K.mirror(1)]) == (0, 1, (A.FXC_DESC,) * 3)                         # luma, U, V
+    assert _classes(api, 64, 40, True, [K.rot(180)]) == (0, 1, (A.FXC_DESC,))
+    assert _classes(api, 64, 40, False, [K.rot(180)])[2][0] == A.FXC_DESC
+    assert _classes(api, 64, 40, True, [K.mirror(1), K.mirror(1)]) == (0, 1, (A.FXC_ASC,))
+    assert _classes(api, 64, 40, True, [K.resize(64, 20)]) == (0, 1, (A.FXC_ASC,))                          # the width kept: b[j] = j
+    assert _classes(api, 7, 5, True, [K.resize(1, 5)]) == (0, 1, (A.FXC_ASC,))                              # one column: no step to judge
+
+
+def test_classes_lds_bound(api):
+    """|b[c1] - b[c0]| <= 4 * (c1 - c0 + 1) per block of 4096 columns; the arithmetic is in tests/effects_geometry_cases.py"""
+    A = api
+    from tests import effects_geometry_cases as G
+    assert _classes(api, 16400, 2, True, [K.resize(4100, 2)]) == (0, 1, (A.FXC_LDS,))                       # the ratio of exactly 4
+    assert _classes(api, 16400, 2, True, [K.mirror(1), K.resize(4100, 2)]) == (0, 1, (A.FXC_LDS,))          # descending b
+    _, _, _, off = _map(api, 16400, 2, 0, 0, True, [K.mirror(1), K.resize(4100, 2)])
+    assert (np.diff(off[:4100].astype(np.int64)) <= 0).all() and off[0] - off[4095] == 16380
+    for w in range(16396, 16412):          # floor(4095 * w / 4100) <= 16384 up to 16405
+        for chain in ([K.resize(4100, 2)], [K.mirror(1), K.resize(4100, 2)]):
+            # two rows 16 KiB apart: no tile either
+            assert _classes(api, w, 2, True, chain) == (0, 1, (A.FXC_LDS if 4095 * w // 4100 <= 16384 else A.FXC_GATHER,)), (w, chain)
+    assert 4095 * G.LDS_W_MAX // 4100 == 16384 and 4095 * G.LDS_W_OVER // 4100 == 16385 and G.LDS_W_OVER == G.LDS_W_MAX + 1
+    # the bound holds per block, not over the row: 4097 columns whose first 4096 are fine and whose last block (one column) is trivially so
+    assert _classes(api, 16388, 1, True, [K.resize(4097, 1)]) == (0, 1, (A.FXC_LDS,))
+    # not LDS, but every 64 rows read one source row: TILE without a quarter turn
+    assert _classes(api, G.LDS_W_OVER, 2, True, [K.resize(4100, 128)]) == (0, 1, (A.FXC_TILE,))
+    # rows less than 256 bytes apart: 3 rows of 100 bytes span 200, 3 rows of 128 bytes span 256
+    assert _classes(api, 100, 3, True, [K.resize(10, 3)]) == (0, 1, (A.FXC_TILE,))
+    assert _classes(api, 128, 3, True, [K.resize(10, 3)]) == (0, 1, (A.FXC_GATHER,))
+    assert _classes(api, 128, 2, True, [K.resize(10, 2)]) == (0, 1, (A.FXC_TILE,))                          # span 128
+
+
+def test_classes_tile_bound(api):
+    """|a[i0 + 63] - a[i0]| < 256 per tile of 64 rows: a span of 252 is a tile, 258 is not; 255 and 256 lie between"""
+    A = api
+    assert _classes(api, 520, 6, True, [K.resize(130, 6), K.rot(90)]) == (0, 1, (A.FXC_TILE,))              # 63 * 4 = 252
+    assert _classes(api, 533, 6, True, [K.resize(130, 6), K.rot(90)]) == (0, 1, (A.FXC_GATHER,))            # floor(63 * 533 / 130) = 258
+    for w in range(518, 536):              # a[63] = floor(63 * w / 130); the later tiles span no more than the first
+        want = A.FXC_TILE if max((min(i0 + 63, 129) * w // 130) - (i0 * w // 130) for i0 in (0, 64, 128)) < 256 else A.FXC_GATHER
+        assert _classes(api, w, 6, True, [K.resize(130, 6), K.rot(90)]) == (0, 1, (want,)), w
+    assert 63 * 527 // 130 == 255 and 63 * 529 // 130 == 256
+    assert _classes(api, 64, 40, True, [K.rot(90)]) == (0, 1, (A.FXC_TILE,))
+    assert _classes(api, 64, 40, False, [K.rot(270)]) == (0, 1, (A.FXC_TILE,) * 3)
+
+
+def test_classes_report_not_fused_where_the_map_does(api):
+    B = api.ERROR_BAD_PTR
+    lib = api.load()
+    w, h, mono, chain = K.NON_ADDITIVE
+    assert _map(api, w, h, 0, 0, mono, chain)[2] == 0
+    assert _classes(api, w, h, mono, chain) == (0, 0, ())
+    assert _classes(api, 40, 24, False, []) == (0, 1, ())                  # no effects: a copy, no plane job
+    for n, (w, h, mono, chain) in enumerate(K.named_chains() + K.generated_chains(100)):
+        rc, _, fused, _ = _map(api, w, h, 0, 0, mono, chain)
+        got = _classes(api, w, h, mono, chain)
+        assert got[0] == rc, (w, h, mono, chain)
+        if rc == 0:
+            assert got[1] == fused and (len(got[2]) > 0) == bool(fused and chain), (w, h, mono, chain)
+    assert _classes(api, 48, 40, False, [K.mirror(1)], ls=54)[0] == api.ERROR_UNSUPPORTED_FEATURE
+    assert _classes(api, 48, 40, True, [K.rot(90)], ls=54) == (0, 1, (api.FXC_TILE,))
+    fused, count = C.c_int(), C.c_size_t()
+    one = K.effect_array(api, [K.rot(90)])
+    assert lib.uhdr_hip_effect_chain_classes(16, 16, 0, 0, api.PIX_FMT_YUV420, None, 1, C.byref(fused), None, 0, C.byref(count)) == B
+    assert lib.uhdr_hip_effect_chain_classes(16, 16, 0, 0, api.PIX_FMT_YUV420, one, 1, None, None, 0, C.byref(count)) == B
+    assert lib.uhdr_hip_effect_chain_classes(16, 16, 0, 0, api.PIX_FMT_YUV420, one, 1, C.byref(fused), None, 0, None) == B
+    # classes == NULL or too short: the count alone
+    assert lib.uhdr_hip_effect_chain_classes(16, 16, 0, 0, api.PIX_FMT_YUV420, one, 1, C.byref(fused), None, 0, C.byref(count)) == 0
+    assert (fused.value, count.value) == (1, 3)
+    two = (C.c_int * 3)(-7, -7, -7)
+    assert lib.uhdr_hip_effect_chain_classes(16, 16, 0, 0, api.PIX_FMT_YUV420, one, 1, C.byref(fused), two, 2, C.byref(count)) == 0
+    assert list(two) == [api.FXC_TILE, api.FXC_TILE, -7] and count.value == 3
+
+
+def test_geometry_chains_compose_to_the_oracles_bytes_in_their_declared_class(api, orc):
+    """every chain tests/test_gpu_effects_geometry.py launches: the map's bytes are the oracle's and the route is the declared one"""
+    from tests import effects_geometry_cases as G
+    assert (G.GATHER, G.ASC, G.DESC, G.LDS, G.TILE) == (api.FXC_GATHER, api.FXC_ASC, api.FXC_DESC, api.FXC_LDS, api.FXC_TILE)
+    cases = [(name, w, h, mono, chain, cls) for name, w, h, mono, chain, cls in G.CHAINS]
+    cases += [("mixed %dx%d" % (w, h), w, h, mono, G.MIXED_CHAIN, cls) for w, h, mono, cls in G.MIXED]
+    for n, (name, w, h, mono, chain, cls) in enumerate(cases):
+        assert _check(api, orc, w, h, mono, chain, 2000 + n) == 1, name
+        assert _classes(api, w, h, mono, chain) == (0, 1, cls), name
+    assert {c for case in cases for c in case[5]} == {G.GATHER, G.ASC, G.DESC, G.LDS, G.TILE}

@@ -449,6 +449,29 @@ def test_effects_restatement_equals_reference_object_code(orc, layout):
         assert np.array_equal(a[1], b[1]), (name, mono, args)
 
 
+def test_effects_restatement_equals_reference_object_code_at_the_kernels_edges(orc):
+    """the shapes of tests/effects_geometry_cases.py: 8200 wide (more than one block of 4096 columns), 66000 high (more rows than a
+    grid has), the resize of ratio exactly 4 and its neighbour, and resizes whose rows * in_h reaches 2^32 -- the GPU tests take
+    the restatement's bytes as expected values there"""
+    from tests.effects_geometry_cases import PINS
+    R = orc.load_ref()
+    if R is None:
+        pytest.skip("oracle/_ref not built (needs /root/reference)")
+    L = orc.load()
+    rng = np.random.RandomState(6)
+    assert {(w, h) for w, h, _, _, _ in PINS} == {(8200, 4), (2, 66000), (16400, 2)}
+    assert any(name == "resize" and args[1] * h >= 1 << 32 for _, h, _, name, args in PINS)
+    for w, h, mono, name, args in PINS:
+        keep, img = _fx_image(orc, rng, w, h, mono)
+        nbytes = 2 * max(w * h, args[0] * args[1] if name == "resize" else 0) + 4096
+        a = _fx_run(orc, L, "orc_", name, img, args, nbytes)
+        b = _fx_run(orc, R, "ref_", name, img, args, nbytes)
+        assert a[0] == b[0] == 0, (w, h, name, args, a[0], b[0])
+        assert a[2] == b[2], (w, h, name, mono, args, a[2], b[2])
+        assert np.array_equal(a[1], b[1]), (w, h, name, mono, args)
+        assert (a[1] != 0xCC).sum() > 0
+
+
 def test_effects_error_codes(orc):                                              # editorhelper.cpp:29-39,175-185
     L = orc.load()
     rng = np.random.RandomState(1)
