@@ -801,6 +801,44 @@ int uhdr_hip_gain_lut(const uhdr_hip_metadata_t* metadata, int with_display_boos
 int uhdr_hip_eval_transfer(int fn, const float* in, float* out, size_t n, float min_boost, float max_boost,
                            void* stream);
 
+/* The route uhdr_hip_generate_gainmap_batch_ex takes for a call, and the two kernels of its filtered route one at a time -- what
+ * the tests of the hand-over between k_generate's filter and k_generate_resolve are built on.  The arguments up to `stream` are
+ * that call's and are checked as there (n >= 1); only the FIRST chunk of the call (the leading images of one size, gamut pair and
+ * alignment class, at most 64) is looked at.
+ *   phase 0  host only, nothing is launched and no device is needed (the data pointers are examined for alignment, never read):
+ *            route[0 .. UHDR_HIP_GENERATE_ROUTE_WORDS) receives the chunk's route and the layout constants of the statistics
+ *            workspace, indexed by the UHDR_HIP_GENERATE_ROUTE_* names below.
+ *   phase 1  enqueues the filtered kernel alone, then copies, in stream order, the header words [0, route[HDR_WORDS]) of every
+ *            image's workspace to headers (DEVICE, n * route[HDR_WORDS] uint32): word route[SWEEP_WORD] is set when a wave's slots
+ *            overflowed, [route[LIST_COUNTS] + l] holds the entries of list l, [route[SLOT_COUNTS] + w] the count word of wave w
+ *            (plain entries | saved entries << 8) where route[SLOTS] != 0.  The map bytes of pixels in doubt are provisional.
+ *   phase 2  enqueues k_generate_resolve alone, on the stream's workspace as phase 1 left it: same arguments, same stream, nothing
+ *            of the library on that stream in between.
+ * Phases 1 and 2 serve a call that is ONE chunk on the filtered-kernel-plus-k_generate_resolve route; ERROR_UNSUPPORTED_FEATURE
+ * otherwise, and for a phase outside 0..2.  BAD_PTR for n < 1, a NULL route in phase 0 or NULL headers in phase 1. */
+enum {
+  UHDR_HIP_GENERATE_ROUTE_RESOLVE = 0,     /* 1: the filtered kernel followed by k_generate_resolve */
+  UHDR_HIP_GENERATE_ROUTE_SPANS = 1,       /* spans of BLOCK pairs a block walks: 1 or 4 */
+  UHDR_HIP_GENERATE_ROUTE_SLOTS = 2,       /* GenConsts::stat_slots: waves per image when they append to slots of their own, else 0 */
+  UHDR_HIP_GENERATE_ROUTE_SPREAD = 3,      /* GenConsts::stat_spread */
+  UHDR_HIP_GENERATE_ROUTE_IMAGES = 4,      /* images in the chunk */
+  UHDR_HIP_GENERATE_ROUTE_BLOCK = 5,       /* kGenBlock: threads (= pixel pairs per span) of a block */
+  UHDR_HIP_GENERATE_ROUTE_HDR_WORDS = 6,   /* kStatHdr */
+  UHDR_HIP_GENERATE_ROUTE_SLOT_COUNTS = 7, /* kStatSlotCnt: first of the waves' count words */
+  UHDR_HIP_GENERATE_ROUTE_SLOT_PLAIN = 8,  /* kStatSlotPlain */
+  UHDR_HIP_GENERATE_ROUTE_SLOT_SAVED = 9,  /* kStatSlotSaved */
+  UHDR_HIP_GENERATE_ROUTE_LISTS = 10,      /* kStatLists */
+  UHDR_HIP_GENERATE_ROUTE_LIST_CAP = 11,   /* kStatCap */
+  UHDR_HIP_GENERATE_ROUTE_LIST_COUNTS = 12,/* first of the lists' count words */
+  UHDR_HIP_GENERATE_ROUTE_SWEEP_WORD = 13, /* the word a wave sets whose slots overflowed */
+  UHDR_HIP_GENERATE_ROUTE_RESOLVE_SLICES = 14, /* kResolveSlices: blocks of 256 threads k_generate_resolve spends per image */
+  UHDR_HIP_GENERATE_ROUTE_SLOT_WAVES = 15, /* kStatSlotWaves: the most waves per image the slots serve */
+  UHDR_HIP_GENERATE_ROUTE_WORDS = 16
+};
+int uhdr_hip_generate_probe(int phase, int n, const uhdr_hip_image_t* yuv420_images, const uhdr_hip_image_t* p010_images,
+                            int hdr_tf, uhdr_hip_metadata_t* metadata, uhdr_hip_image_t* dests, int sdr_is_601,
+                            int generate_mode, float* content_minmax, void* stream, uint32_t* route, uint32_t* headers);
+
 /* Bench / test support: the deterministic synthetic frame pair of SURVEY.md 8(d) (an LCG; tests/ and bench.py compare it with the
  * oracle's serial loop), written into device memory: p010 = width*height*3/2 uint16 (luma, then interleaved UV, values in the
  * legal 10-bit ranges << 6), yuv = width*height*3/2 bytes (Y, U, V).  width and height even; enqueued on `stream`. */

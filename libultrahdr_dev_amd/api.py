@@ -34,6 +34,9 @@ GENERATE_EXACT, GENERATE_LUT, GENERATE_UNFILTERED = 0, 1, 2
 BOOST_PER_IMAGE, BOOST_PER_CALL = 0, 1          # content-adaptive gain maps: one boost range per image / per call
 TONEMAP_SHIFT, TONEMAP_REINHARD_MAXRGB = 0, 1   # API-0's SDR base image: the reference's bit shift / tone-mapped from linear light
 FXC_GATHER, FXC_ASC, FXC_DESC, FXC_LDS, FXC_TILE = 0, 1, 2, 3, 4   # uhdr_hip_effect_chain_classes: the chain kernel's route per plane
+# uhdr_hip_generate_probe: the words of its route report (UHDR_HIP_GENERATE_ROUTE_*)
+(ROUTE_RESOLVE, ROUTE_SPANS, ROUTE_SLOTS, ROUTE_SPREAD, ROUTE_IMAGES, ROUTE_BLOCK, ROUTE_HDR_WORDS, ROUTE_SLOT_COUNTS, ROUTE_SLOT_PLAIN,
+ ROUTE_SLOT_SAVED, ROUTE_LISTS, ROUTE_LIST_CAP, ROUTE_LIST_COUNTS, ROUTE_SWEEP_WORD, ROUTE_RESOLVE_SLICES, ROUTE_SLOT_WAVES, ROUTE_WORDS) = range(17)
 ABI_VERSION = 3
 FLT_MAX = 3.4028234663852886e38
 
@@ -155,6 +158,8 @@ SIGNATURES = {
     "uhdr_hip_gain_lut": (C.c_int, [_MP, C.c_int, C.c_float, C.POINTER(C.c_float)]),
     "uhdr_hip_idw_tables": (C.c_int, [C.c_int, C.POINTER(C.c_float)]),
     "uhdr_hip_eval_transfer": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p]),
+    "uhdr_hip_generate_probe": (C.c_int, [C.c_int, C.c_int, _IP, _IP, C.c_int, _MP, _IP, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_uint32), C.c_void_p]),
     "uhdr_hip_synth_lcg_frame": (C.c_int, [C.c_size_t, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uhdr_hip_adaptive_boost_range": (C.c_int, [C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "uhdr_hip_adaptive_metadata": (C.c_int, [C.c_int, C.c_float, C.c_float, _MP]),

@@ -3151,6 +3151,104 @@ int uhdr_hip_idw_tables(int scale, float* out) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// One chunk of uhdr_hip_generate_gainmap_batch_ex: up to kMaxChunk consecutive images, from image i on, of identical size, gamuts
+// and alignment class; *m_out receives their number.  `phases` selects what is enqueued: kGenPhaseFilter the chunk's k_generate
+// launch (with the clear or the finalize kernel of the routes that keep their keys in content_minmax), kGenPhaseResolve the
+// k_generate_resolve launch behind a filtered one; the production call passes both.  0 enqueues nothing and needs no device
+// (st may be null): the plan only -- `route` (or null) receives it, UHDR_HIP_GENERATE_ROUTE_* words.  `headers` (or null; device,
+// kStatHdr words per image): after kGenPhaseFilter of a filtered + resolve pair, every image's header words, copied in stream order.
+enum : unsigned { kGenPhaseFilter = 1u, kGenPhaseResolve = 2u };
+static int generate_chunk(DeviceState* st, hipStream_t s, int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s,
+                          int hdr_tf, const uhdr_hip_metadata_t* metadata, uhdr_hip_image_t* dests, int sdr_is_601,
+                          int generate_mode, float* content_minmax, int i, unsigned phases, int* m_out, uint32_t* route,
+                          uint32_t* headers) {
+  const bool lut = generate_mode == UHDR_HIP_GENERATE_LUT;
+  // Content min / max.  The filtered kernel (the usual case) works in a workspace of the library: its candidates are resolved, the
+  // result written to content_minmax and the workspace cleared by k_stats_resolve.  The other kernels keep exact keys in
+  // content_minmax itself: cleared here, turned into floats by k_stats_finalize at the end.
+  uint32_t* keys = reinterpret_cast<uint32_t*>(content_minmax);
+  const uhdr_hip_image_t& y0 = yuvs[i];
+  GenConsts c = generate_consts(y0.colorGamut, p010s[i].colorGamut, hdr_tf, sdr_is_601, y0.width, y0.height, *metadata);
+  c.stat_keys = keys ? keys + 2 * i : nullptr;
+  c.stat_stride = 2;
+  c.lut = (lut && st != nullptr) ? st->lut : nullptr;
+  GenBatch b;
+  int m = 0;
+  bool aligned = true;
+  while (i + m < n && m < kMaxChunk) {
+    const uhdr_hip_image_t& y = yuvs[i + m];
+    if (y.width != y0.width || y.height != y0.height || y.colorGamut != y0.colorGamut ||
+        p010s[i + m].colorGamut != p010s[i].colorGamut)
+      break;
+    b.img[m] = gen_image(y, p010s[i + m], dests[i + m].data);
+    const bool a = gen_aligned(b.img[m], c.width, c.height);
+    if (m == 0) aligned = a;
+    else if (a != aligned) break;
+    fill_generate_dest(&y, &dests[i + m]);
+    ++m;
+  }
+  *m_out = m;
+  bool filter = generate_mode == UHDR_HIP_GENERATE_EXACT && c.flt_delta < 0.25f && c.min_boost >= 0.25f && c.max_boost <= 64.0f;
+  // The filtered kernel of a large launch leaves its pixels in doubt and the exact extremes to k_generate_resolve.  A small
+  // launch (one 4K image) would pay that second kernel's latency with nothing to hide it behind: without statistics it runs the
+  // filtered kernel that falls back to the exact path in place.  With statistics the choice is between the two kernels and the
+  // exact kernel (every pixel on the f64 path: 5.5 us per megapixel against 0.75 + the resolve kernel's ~20 us): the pair from
+  // about half a 4K frame up (round 3: 8 x 1080p 91 -> 30 us, 8 x 4K 141 -> 80), the exact kernel below.
+  const bool small = generate_is_small(c, m);
+  const bool pair = keys != nullptr ? generate_resolve_pays(c, m) : !small;
+  if (keys != nullptr && !pair) filter = false;
+  const bool resolve = filter && aligned && !lut && pair;
+  if (resolve) {
+    c.stat_stride = kStatWords;
+    c.stat_out = keys ? content_minmax + 2 * i : nullptr;
+    c.stat_spread = (m <= 16 && (uint64_t)((c.map_w + 1u) >> 1) * c.map_h >= 512u * 64u) ? 1u : 0u;
+    c.stat_slots = generate_slot_waves(c, m);
+  }
+  if (route != nullptr) {
+    memset(route, 0, sizeof(uint32_t) * UHDR_HIP_GENERATE_ROUTE_WORDS);
+    route[UHDR_HIP_GENERATE_ROUTE_RESOLVE] = resolve ? 1u : 0u;
+    route[UHDR_HIP_GENERATE_ROUTE_SPANS] = small ? 1u : (uint32_t)kGenTiles;
+    route[UHDR_HIP_GENERATE_ROUTE_SLOTS] = c.stat_slots;
+    route[UHDR_HIP_GENERATE_ROUTE_SPREAD] = c.stat_spread;
+    route[UHDR_HIP_GENERATE_ROUTE_IMAGES] = (uint32_t)m;
+    route[UHDR_HIP_GENERATE_ROUTE_BLOCK] = (uint32_t)kGenBlock;
+    route[UHDR_HIP_GENERATE_ROUTE_HDR_WORDS] = kStatHdr;
+    route[UHDR_HIP_GENERATE_ROUTE_SLOT_COUNTS] = kStatSlotCnt;
+    route[UHDR_HIP_GENERATE_ROUTE_SLOT_PLAIN] = kStatSlotPlain;
+    route[UHDR_HIP_GENERATE_ROUTE_SLOT_SAVED] = kStatSlotSaved;
+    route[UHDR_HIP_GENERATE_ROUTE_LISTS] = kStatLists;
+    route[UHDR_HIP_GENERATE_ROUTE_LIST_CAP] = kStatCap;
+    route[UHDR_HIP_GENERATE_ROUTE_LIST_COUNTS] = 8u;   // GenConsts::stat_ws: [8 + l] entries in list l,
+    route[UHDR_HIP_GENERATE_ROUTE_SWEEP_WORD] = 6u;    // [6] set by a wave whose slots overflowed
+    route[UHDR_HIP_GENERATE_ROUTE_RESOLVE_SLICES] = kResolveSlices;
+    route[UHDR_HIP_GENERATE_ROUTE_SLOT_WAVES] = kStatSlotWaves;
+  }
+  if (phases == 0u) return UHDR_HIP_NO_ERROR;
+  std::unique_lock<std::mutex> pair_lk(g_pair_mu, std::defer_lock);
+  if (resolve) pair_lk.lock();
+  if (resolve) {
+    uint32_t* w = nullptr;
+    const int wrc = stat_workspace(st, s, &w);
+    if (wrc != UHDR_HIP_NO_ERROR) return wrc;
+    c.stat_ws = w;
+    c.stat_keys = keys ? w + 4 : nullptr;
+  } else if (keys != nullptr && (phases & kGenPhaseFilter)) {
+    HIP_TRY(launch_stats_init(keys + 2 * i, m, s));
+  }
+  if (phases & kGenPhaseFilter) {
+    HIP_TRY(launch_generate(c, b, m, hdr_tf, aligned, lut, filter, s));
+    if (resolve && headers != nullptr)
+      HIP_TRY(hipMemcpy2DAsync(headers, sizeof(uint32_t) * kStatHdr, c.stat_ws, sizeof(uint32_t) * kStatWords, sizeof(uint32_t) * kStatHdr,
+                               (size_t)m, hipMemcpyDeviceToDevice, s));
+  }
+  if (resolve) {
+    if (phases & kGenPhaseResolve) HIP_TRY(launch_stats_resolve(c, b, m, hdr_tf, aligned, s));
+  } else if (keys != nullptr && (phases & kGenPhaseFilter)) {
+    HIP_TRY(launch_stats_finalize(keys + 2 * i, m, s));
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
 int uhdr_hip_generate_gainmap_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf,
                                     uhdr_hip_metadata_t* metadata, uhdr_hip_image_t* dests, int sdr_is_601,
                                     float* content_minmax, void* stream) {
@@ -3164,7 +3262,6 @@ int uhdr_hip_generate_gainmap_batch_ex(int n, const uhdr_hip_image_t* yuvs, cons
   if (generate_mode != UHDR_HIP_GENERATE_EXACT && generate_mode != UHDR_HIP_GENERATE_LUT &&
       generate_mode != UHDR_HIP_GENERATE_UNFILTERED)
     return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  const bool lut = generate_mode == UHDR_HIP_GENERATE_LUT;
   if (n < 0 || (n > 0 && (yuvs == nullptr || p010s == nullptr || dests == nullptr)) || metadata == nullptr)
     return UHDR_HIP_ERROR_BAD_PTR;
   for (int i = 0; i < n; ++i) {
@@ -3180,65 +3277,50 @@ int uhdr_hip_generate_gainmap_batch_ex(int n, const uhdr_hip_image_t* yuvs, cons
   hipStream_t s = static_cast<hipStream_t>(stream);
 
   fill_generate_metadata(hdr_tf, metadata);
-  // Content min / max.  The filtered kernel (the usual case) works in a workspace of the library: its candidates are resolved, the
-  // result written to content_minmax and the workspace cleared by k_stats_resolve.  The other kernels keep exact keys in
-  // content_minmax itself: cleared here, turned into floats by k_stats_finalize at the end.
-  uint32_t* keys = reinterpret_cast<uint32_t*>(content_minmax);
-
   int i = 0;
   while (i < n) {
-    // chunk = up to kMaxChunk consecutive images of identical size, gamuts and alignment class
-    const uhdr_hip_image_t& y0 = yuvs[i];
-    GenConsts c = generate_consts(y0.colorGamut, p010s[i].colorGamut, hdr_tf, sdr_is_601, y0.width, y0.height, *metadata);
-    c.stat_keys = keys ? keys + 2 * i : nullptr;
-    c.stat_stride = 2;
-    c.lut = lut ? st->lut : nullptr;
-    GenBatch b;
     int m = 0;
-    bool aligned = true;
-    while (i + m < n && m < kMaxChunk) {
-      const uhdr_hip_image_t& y = yuvs[i + m];
-      if (y.width != y0.width || y.height != y0.height || y.colorGamut != y0.colorGamut ||
-          p010s[i + m].colorGamut != p010s[i].colorGamut)
-        break;
-      b.img[m] = gen_image(y, p010s[i + m], dests[i + m].data);
-      const bool a = gen_aligned(b.img[m], c.width, c.height);
-      if (m == 0) aligned = a;
-      else if (a != aligned) break;
-      fill_generate_dest(&y, &dests[i + m]);
-      ++m;
-    }
-    bool filter = generate_mode == UHDR_HIP_GENERATE_EXACT && c.flt_delta < 0.25f && c.min_boost >= 0.25f && c.max_boost <= 64.0f;
-    // The filtered kernel of a large launch leaves its pixels in doubt and the exact extremes to k_generate_resolve.  A small
-    // launch (one 4K image) would pay that second kernel's latency with nothing to hide it behind: without statistics it runs the
-    // filtered kernel that falls back to the exact path in place.  With statistics the choice is between the two kernels and the
-    // exact kernel (every pixel on the f64 path: 5.5 us per megapixel against 0.75 + the resolve kernel's ~20 us): the pair from
-    // about half a 4K frame up (round 3: 8 x 1080p 91 -> 30 us, 8 x 4K 141 -> 80), the exact kernel below.
-    const bool small = generate_is_small(c, m);
-    const bool pair = keys != nullptr ? generate_resolve_pays(c, m) : !small;
-    if (keys != nullptr && !pair) filter = false;
-    const bool resolve = filter && aligned && !lut && pair;
-    std::unique_lock<std::mutex> pair_lk(g_pair_mu, std::defer_lock);
-    if (resolve) pair_lk.lock();
-    if (resolve) {
-      uint32_t* w = nullptr;
-      const int wrc = stat_workspace(st, s, &w);
-      if (wrc != UHDR_HIP_NO_ERROR) return wrc;
-      c.stat_ws = w;
-      c.stat_keys = keys ? w + 4 : nullptr;
-      c.stat_stride = kStatWords;
-      c.stat_out = keys ? content_minmax + 2 * i : nullptr;
-      c.stat_spread = (m <= 16 && (uint64_t)((c.map_w + 1u) >> 1) * c.map_h >= 512u * 64u) ? 1u : 0u;
-      c.stat_slots = generate_slot_waves(c, m);
-    } else if (keys != nullptr) {
-      HIP_TRY(launch_stats_init(keys + 2 * i, m, s));
-    }
-    HIP_TRY(launch_generate(c, b, m, hdr_tf, aligned, lut, filter, s));
-    if (resolve) HIP_TRY(launch_stats_resolve(c, b, m, hdr_tf, aligned, s));
-    else if (keys != nullptr) HIP_TRY(launch_stats_finalize(keys + 2 * i, m, s));
+    rc = generate_chunk(st, s, n, yuvs, p010s, hdr_tf, metadata, dests, sdr_is_601, generate_mode, content_minmax, i,
+                        kGenPhaseFilter | kGenPhaseResolve, &m, nullptr, nullptr);
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
     i += m;
   }
   return UHDR_HIP_NO_ERROR;
+}
+
+int uhdr_hip_generate_probe(int phase, int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf,
+                            uhdr_hip_metadata_t* metadata, uhdr_hip_image_t* dests, int sdr_is_601, int generate_mode,
+                            float* content_minmax, void* stream, uint32_t* route, uint32_t* headers) {
+  if (phase < 0 || phase > 2) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (generate_mode != UHDR_HIP_GENERATE_EXACT && generate_mode != UHDR_HIP_GENERATE_LUT &&
+      generate_mode != UHDR_HIP_GENERATE_UNFILTERED)
+    return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (n <= 0 || yuvs == nullptr || p010s == nullptr || dests == nullptr || metadata == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  if ((phase == 0 && route == nullptr) || (phase == 1 && headers == nullptr)) return UHDR_HIP_ERROR_BAD_PTR;
+  for (int i = 0; i < n; ++i) {
+    const int rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, metadata, &dests[i]);
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
+    if (dests[i].data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  }
+  fill_generate_metadata(hdr_tf, metadata);
+  int m = 0;
+  uint32_t r[UHDR_HIP_GENERATE_ROUTE_WORDS];
+  if (phase == 0) {   // the plan of the first chunk: host arithmetic only, no device state
+    const int rc = generate_chunk(nullptr, nullptr, n, yuvs, p010s, hdr_tf, metadata, dests, sdr_is_601, generate_mode,
+                                  content_minmax, 0, 0u, &m, r, nullptr);
+    if (rc == UHDR_HIP_NO_ERROR) memcpy(route, r, sizeof(r));
+    return rc;
+  }
+  DeviceState* st = nullptr;
+  int rc = current_state(&st);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  // one kernel of the pair by itself: only where the call IS one such pair (the workspace is handed from one phase to the other)
+  rc = generate_chunk(nullptr, nullptr, n, yuvs, p010s, hdr_tf, metadata, dests, sdr_is_601, generate_mode, content_minmax, 0, 0u,
+                      &m, r, nullptr);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if (m != n || r[UHDR_HIP_GENERATE_ROUTE_RESOLVE] == 0u) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return generate_chunk(st, static_cast<hipStream_t>(stream), n, yuvs, p010s, hdr_tf, metadata, dests, sdr_is_601, generate_mode,
+                        content_minmax, 0, phase == 1 ? kGenPhaseFilter : kGenPhaseResolve, &m, nullptr, headers);
 }
 
 // Per-channel (RGB) gain maps: uhdr_hip_generate_gainmap_batch's checks, chunks and metadata; the map is

@@ -13,9 +13,10 @@ namespace uhdr {
 // (GenConsts::stat_spread: at most 16 images of at least 512 waves) publish to and prune by one pair of words per LIST instead;
 // the others keep the single pair, which prunes better.
 // Round 4: launches whose images have at most kStatSlotWaves waves each (a 4K frame at four spans per block: 1016) need no
-// atomic at all -- every wave owns kStatSlotWords words behind the header, word 0 its count (written by every wave of every launch,
-// so nothing has to be cleared), the others its entries; a wave with more entries than fit sets word 6 of the header and the image
-// is swept.  The returning atomic cost the streaming kernel 17 us per 64 x 4K launch (0.435 ms against 0.418 with it compiled out,
+// atomic at all -- every wave owns kStatSlotWords words behind the header (word 0 of them is unused) and one count word IN the
+// header, at kStatSlotCnt + wave (written by every wave of every launch, so nothing has to be cleared; the resolve kernel ignores
+// the words of waves the launch does not have); a wave with more entries than fit writes a count of 0, sets word 6 of the header
+// and the image is swept.  The returning atomic cost the streaming kernel 17 us per 64 x 4K launch (0.435 ms against 0.418 with it compiled out,
 // profiles/r02_generate_ab.txt): a wave waits a trip to the memory side for it before it can exit.  Other launches keep the lists.
 // A wave's count word (kStatSlotCnt + wave): plain entries | saved entries << 8.  Its slots: [1, kStatSlotPlain]: plain entries (pair index << 3 | flags: the resolve
 // kernel samples the pair again); then kStatSlotSaved entries of 16 words (64 B): (pair index << 3 | flags) and the pair AS SAMPLED --
@@ -28,7 +29,12 @@ constexpr uint32_t kStatLists = 64, kStatCap = 252, kStatEst = 8 + kStatLists, k
                    kStatHdr = kStatSlotCnt + kStatSlotWaves,
                    kStatWords = kStatHdr + (kStatLists * kStatCap > kStatSlotWaves * kStatSlotWords ? kStatLists * kStatCap : kStatSlotWaves * kStatSlotWords);
 static_assert(kStatHdr % 4u == 0u && kStatSlotWords % 4u == 0u && kStatWords % 4u == 0u, "saved entries are read and written as 16-byte pieces");
+static_assert(kStatSlotCnt % 4u == 0u, "k_generate_resolve reads four waves' count words as one 16-byte piece");
 constexpr int kMaxChunk = 64;  // images per launch (descriptors travel in the 4 KiB kernarg segment: 64 x 56 B + consts)
+// launch geometry of k_generate (threads per block, spans of kGenBlock pairs a block of a large launch walks) and the blocks
+// k_generate_resolve spends per image; chosen in uhdr_kernels.hip, here because uhdr_hip_generate_probe reports them
+constexpr int kGenBlock = 256, kGenTiles = 4;
+constexpr uint32_t kResolveSlices = 16;
 
 // ---- LUT mode (gainmapmath.cpp:21-64 static tables; opt-in) --------------------
 // one device buffer per device, filled once at uhdr_hip_init() by k_build_luts: table[i] = f((float)i / (float)(N - 1))

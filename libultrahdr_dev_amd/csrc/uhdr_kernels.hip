@@ -436,7 +436,7 @@ __device__ __forceinline__ uint32_t ld16(const uint16_t* p) { return *p; }
 
 // launch geometry of k_generate, chosen by same-box A/B (scripts/ab, ms per 32-frame 4K launch):
 //   block 64/128/256/512/1024, 1 span: 0.64 / 0.50 / 0.39 / 0.355 / 0.43;   block 256, 4 spans: 0.350
-constexpr int kGenBlock = 256, kGenTiles = 4;
+// (kGenBlock = 256, kGenTiles = 4: uhdr_kernels.h, the host layer reports them)
 
 // inputs of pair `idx` (two horizontally adjacent map pixels = an 8x4 pixel block of both images) -> registers
 template <bool ALIGNED>
@@ -749,7 +749,6 @@ __global__ void k_stats_finalize(uint32_t* keys, int n) {
 // both gains join.  An image whose list overflowed (flat content at a code boundary: every pixel in doubt) is swept whole.
 // grid = (image, kResolveSlices), each block a slice of the work; the slice that finishes last writes the image's (min, max) and
 // clears the header words for the next launch.
-constexpr uint32_t kResolveSlices = 16;
 static_assert(kStatLists == 64u, "k_generate_resolve reads the list counts with one wave");
 template <int TF, bool ALIGNED>
 __global__ void __launch_bounds__(256) k_generate_resolve(const GenConsts c, const GenBatch b) {
