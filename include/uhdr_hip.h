@@ -429,6 +429,14 @@ int uhdr_hip_jpeg_decode_batch_ex(int n, const void* const* jpeg, const size_t* 
 int uhdr_hip_jpeg_decode_ex(const void* jpeg, size_t jpeg_size, int decode_to, void* out, size_t out_capacity, uhdr_hip_image_t* desc,
                             int mem_space, void* stream, int flags);
 
+/* Host only, for tests that prove their route: the number of launches of the synchronisation kernel (k_jd_sync_multi<1>, four rounds
+ * each) that the last device decode of the calling host thread enqueued up to the look at the flags that read "no change" -- a
+ * multiple of the launches between two looks, not the number the file needed.  A call of several decode rounds, or a JPEG/R decode
+ * (two JPEGs in one batch), reports its last batch; a call that did not reach the device leaves the values.  *ring_looks (optional):
+ * how often the host read the flags; *first_launches (optional): the launches in front of the first look, what a file reports that
+ * needs no more (a constant of the build). */
+int uhdr_hip_jpeg_decode_last_sync_launches(int* ring_looks, int* first_launches);
+
 /* JpegR::decodeJPEGR (lib/src/jpegr.cpp:655-822) for the HDR output formats: a JPEG/R file (HOST memory: primary JPEG + gain
  * map JPEG, the gain map's APP1 carrying the hdrgm:* XMP attributes) -> the HDR rendition applyGainMap produces.  Container
  * scan (extractPrimaryImageAndGainMap, :823-876), XMP metadata (getMetadataFromXMP, jpegrutils.cpp:436-545) and the ICC gamut

@@ -147,6 +147,7 @@ SIGNATURES = {
                                               C.POINTER(C.c_size_t), _IP, _MP, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p]),
     "uhdr_hip_jpeg_decode_batch_ex": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                 _IP, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int]),
+    "uhdr_hip_jpeg_decode_last_sync_launches": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "uhdr_hip_jpeg_decode_ex": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, _IP, C.c_int, C.c_void_p, C.c_int]),
     "uhdr_hip_jpegr_decode_ex": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p, C.c_size_t, _IP, _MP, C.c_int, C.c_int, C.c_void_p,
                                            C.c_int]),

@@ -2038,6 +2038,15 @@ int uhdr_hip_jpeg_decode_rgba(const void* jpeg, size_t jpeg_size, void* out, siz
   return uhdr_hip_jpeg_decode_batch(1, &jpeg, &jpeg_size, UHDR_HIP_DECODE_TO_RGBA, &out, &out_capacity, desc, nullptr, single_mem_space(mem_space), stream);
 }
 
+// host only: the synchronisation launches the last device decode of this host thread enqueued (jpeg::last_sync_counts)
+int uhdr_hip_jpeg_decode_last_sync_launches(int* ring_looks, int* first_launches) {
+  uint32_t launches = 0, looks = 0, first = 0;
+  jpeg::last_sync_counts(&launches, &looks, &first);
+  if (ring_looks != nullptr) *ring_looks = (int)looks;
+  if (first_launches != nullptr) *first_launches = (int)first;
+  return (int)launches;
+}
+
 // either single decode with flags (decode_to: UHDR_HIP_DECODE_TO_YCBCR / _RGBA): a batch of one file
 int uhdr_hip_jpeg_decode_ex(const void* jpeg, size_t jpeg_size, int decode_to, void* out, size_t out_capacity, uhdr_hip_image_t* desc, int mem_space,
                             void* stream, int flags) {

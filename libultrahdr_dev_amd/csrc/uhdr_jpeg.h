@@ -138,6 +138,9 @@ size_t dec_workspace_bytes(const DecInfo& info, DecLayout* l);
 size_t dec_batch_scratch_bytes(int n, const DecLayout l[]);
 int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[], uint8_t* const ws[], DecPlane (*planes[])[3], hipStream_t s,
                         uint8_t* batch_ws, hipError_t* herr, int* image_rc);
+// of this host thread's last decode_device_batch: k_jd_sync_multi<1> launches enqueued up to the look at the ring that read "no
+// change", the number of looks; and the launches in front of the first look (a constant)
+void last_sync_counts(uint32_t* launches, uint32_t* ring_looks, uint32_t* first_launches);
 
 }  // namespace jpeg
 }  // namespace uhdr

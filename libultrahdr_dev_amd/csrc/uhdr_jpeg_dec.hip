@@ -23,7 +23,7 @@
 //   (scan of the blocks completed per subsequence -> index of the block each subsequence starts in)
 //   k_jd_write_multi       final decode from the true start states: DC differences and AC values into zeroed coefficient blocks
 //   (one scan turns the DC differences into DC values, the three components side by side)
-//   k_jd_idct_multi        one thread per block: DC value, dequantise, "islow" IDCT, +128, clamp, store cropped to the plane
+//   k_jd_idct_multi        one thread per block: DC value, dequantise, "islow" IDCT, libjpeg's range limit, store cropped to the plane
 // The decoding kernels read nothing from global memory inside their symbol loops: the workgroup's stretch of the bit string, the
 // first-level tables and the canonical form of the longer codes are in LDS (a wave waits for all its memory operations at once).
 // Restart intervals (DRI / RSTn) make the job easier, not harder: every interval is a byte-aligned bit string of its own whose
@@ -39,8 +39,9 @@
 // the MCU's shape is per-image data (DecJob::hs, vs, bpm = hs * vs + 2, chroma_at = hs * vs): the passes pick the table by
 // c >= chroma_at and wrap the index at bpm, the DC scan keys a block's component by b % bpm, the IDCT places luma block k of MCU
 // (mr, mc) at block (mr * vs + k / hs, mc * hs + k % hs) and crops each plane to its own extent.  The convergence and round-limit
-// logic is untouched by this.  What a 3-block (4:4:4) or 4-block (4:2:2 / 4:4:0) MCU does to the number of rounds is unmeasured (there
-// is no round counter); measured is the time: a 4K quality-95 frame decodes in 382 us as 4:4:4 and 428 us as 4:2:2 beside 682 us as
+// logic is untouched by this.  What a 3-block (4:4:4) or 4-block (4:2:2 / 4:4:0) MCU does to the number of rounds is unmeasured (the
+// host counts the launches of a decode, last_sync_counts, and the tests of constructed streams read them; nobody has read them for
+// these samplings); measured is the time: a 4K quality-95 frame decodes in 382 us as 4:4:4 and 428 us as 4:2:2 beside 682 us as
 // 4:2:0, planes equal to libjpeg-turbo's (profiles/r06_jpeg_sampling.txt) -- fewer states for the block-in-MCU index to fall in
 // step over is a hypothesis for that, not a finding.
 #include <hip/hip_runtime.h>
@@ -580,28 +581,40 @@ struct SegOf {   // which image element g of a concatenation belongs to; off: n 
 };
 
 // ---- dequantisation + IDCT -----------------------------------------------------------------------------------------
-__device__ __forceinline__ int dscale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-template <int PASS>
+// libjpeg computes both passes in 64 bits (JLONG) over an int workspace and indexes range_limit with bits 18..27 of the second pass's
+// sums.  What of that needs more than 32 bits, from the constants: with every dequantised coefficient of a column at most M in
+// magnitude, the largest intermediate of a pass is an output sum in front of its descale, at most 61214 M (the largest sum of the
+// absolute weights a pass gives its 8 inputs: outputs 2 and 5) plus the rounding term.
+//   pass 1: 61214 M + 2^10 < 2^31 for M <= 35081.  A block an encoder made of 8-bit samples stays below 2^15; a legal file reaches
+//           1023 x 255.  So a block with a dequantised magnitude of 2^15 or more takes the pass in 64 bits (idct8<0, int64_t>), the
+//           others in 32; the workspace fits 32 bits either way.
+//   pass 2: its sums pass 2^31 (all 64 coefficients at M: for M > 1173), but range_limit sees bits 18..27 only, and arithmetic modulo
+//           2^32 has them right whatever the higher bits do: unsigned 32-bit arithmetic (defined on overflow), nothing wider.
+// The planes are libjpeg's for every coefficient and quantiser a baseline file can hold (tests/jpeg_stream_cases.py, range_limit_*;
+// DESIGN.md, "JPEG decoder: constructed streams").
+template <typename T>
+__device__ __forceinline__ T dscale(T x, int n) { return (x + ((T)1 << (n - 1))) >> n; }
+template <int PASS, typename T>
 __device__ __forceinline__ void idct8(int (&d)[64], int base, int stride) {   // libjpeg jidctint.c
-  int z2 = d[base + 2 * stride], z3 = d[base + 6 * stride];
-  int z1 = (z2 + z3) * 4433;
-  int tmp2 = z1 + z3 * (-15137), tmp3 = z1 + z2 * 6270;
-  z2 = d[base]; z3 = d[base + 4 * stride];
-  int tmp0 = (z2 + z3) << 13, tmp1 = (z2 - z3) << 13;
-  const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-  tmp0 = d[base + 7 * stride]; tmp1 = d[base + 5 * stride]; tmp2 = d[base + 3 * stride]; tmp3 = d[base + stride];
+  T z2 = (T)d[base + 2 * stride], z3 = (T)d[base + 6 * stride];
+  T z1 = (z2 + z3) * (T)4433;
+  T tmp2 = z1 + z3 * (T)(-15137), tmp3 = z1 + z2 * (T)6270;
+  z2 = (T)d[base]; z3 = (T)d[base + 4 * stride];
+  T tmp0 = (z2 + z3) * (T)8192, tmp1 = (z2 - z3) * (T)8192;
+  const T tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  tmp0 = (T)d[base + 7 * stride]; tmp1 = (T)d[base + 5 * stride]; tmp2 = (T)d[base + 3 * stride]; tmp3 = (T)d[base + stride];
   z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
-  int z4 = tmp1 + tmp3;
-  const int z5 = (z3 + z4) * 9633;
-  tmp0 *= 2446; tmp1 *= 16819; tmp2 *= 25172; tmp3 *= 12299;
-  z1 *= -7373; z2 *= -20995; z3 *= -16069; z4 *= -3196;
+  T z4 = tmp1 + tmp3;
+  const T z5 = (z3 + z4) * (T)9633;
+  tmp0 *= (T)2446; tmp1 *= (T)16819; tmp2 *= (T)25172; tmp3 *= (T)12299;
+  z1 *= (T)(-7373); z2 *= (T)(-20995); z3 *= (T)(-16069); z4 *= (T)(-3196);
   z3 += z5; z4 += z5;
   tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
   constexpr int sh = PASS == 0 ? 11 : 18;
-  d[base] = dscale(tmp10 + tmp3, sh); d[base + 7 * stride] = dscale(tmp10 - tmp3, sh);
-  d[base + stride] = dscale(tmp11 + tmp2, sh); d[base + 6 * stride] = dscale(tmp11 - tmp2, sh);
-  d[base + 2 * stride] = dscale(tmp12 + tmp1, sh); d[base + 5 * stride] = dscale(tmp12 - tmp1, sh);
-  d[base + 3 * stride] = dscale(tmp13 + tmp0, sh); d[base + 4 * stride] = dscale(tmp13 - tmp0, sh);
+  d[base] = (int)dscale<T>(tmp10 + tmp3, sh); d[base + 7 * stride] = (int)dscale<T>(tmp10 - tmp3, sh);
+  d[base + stride] = (int)dscale<T>(tmp11 + tmp2, sh); d[base + 6 * stride] = (int)dscale<T>(tmp11 - tmp2, sh);
+  d[base + 2 * stride] = (int)dscale<T>(tmp12 + tmp1, sh); d[base + 5 * stride] = (int)dscale<T>(tmp12 - tmp1, sh);
+  d[base + 3 * stride] = (int)dscale<T>(tmp13 + tmp0, sh); d[base + 4 * stride] = (int)dscale<T>(tmp13 - tmp0, sh);
 }
 
 // the MCU block b lies in.  bpm is 1, 3, 4 or 6: every division is by a constant (a multiplication, as 4:2:0's always was) and the
@@ -644,10 +657,18 @@ __device__ __forceinline__ void idct_body(const DecJob& j, const Dc3* dc) {
     }
   }
   d[0] = dc_value * (int)q[0];
+  int dmax = 0, dmin = 0;   // the largest and the smallest dequantised coefficient (two per v_max3 / v_min3)
 #pragma unroll
-  for (int c = 0; c < 8; ++c) idct8<0>(d, c, 8);
+  for (int k = 0; k < 64; k += 2) { dmax = max(max(dmax, d[k]), d[k + 1]); dmin = min(min(dmin, d[k]), d[k + 1]); }
+  if (dmax >= 32768 || dmin <= -32768) {   // (unrolled like the other branch: an index that is no constant would move d[] out of the registers)
 #pragma unroll
-  for (int r = 0; r < 8; ++r) idct8<1>(d, r * 8, 1);
+    for (int c = 0; c < 8; ++c) idct8<0, int64_t>(d, c, 8);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) idct8<0, int>(d, c, 8);
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r) idct8<1, uint32_t>(d, r * 8, 1);
   uint8_t* dst = pl.p + (size_t)(br * 8) * pl.stride + bc * 8;
   const bool whole = br * 8 + 8 <= pl.h && bc * 8 + 8 <= pl.w && pl.aligned8;
 #pragma unroll
@@ -655,7 +676,9 @@ __device__ __forceinline__ void idct_body(const DecJob& j, const Dc3* dc) {
     uint32_t o[2] = {0u, 0u};
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-      int x = d[r * 8 + c] + 128;
+      // libjpeg's range_limit[x & 1023]: the clamp of x + 128 to 0..255 for -512 <= x <= 511, and outside that the value wraps
+      // (x = 600 gives 0, not 255) -- what legal files with large quantisers reach; x taken modulo 1024 into -512..511 first
+      int x = ((int)((uint32_t)d[r * 8 + c] << 22) >> 22) + 128;   // (the low ten bits, sign-extended: one v_bfe_i32)
       x = x < 0 ? 0 : (x > 255 ? 255 : x);
       o[c >> 2] |= (uint32_t)x << (8 * (c & 3));
     }
@@ -820,6 +843,13 @@ static BatchLayout batch_layout(int n, const DecLayout l[]) {
 }
 size_t dec_batch_scratch_bytes(int n, const DecLayout l[]) { return batch_layout(n, l).total; }
 
+// what the last decode_device_batch of this host thread enqueued: launches of k_jd_sync_multi<1> up to the look at the ring that
+// read "no change", and the looks themselves (uhdr_hip_jpeg_decode_last_sync_launches: the tests prove their route with it)
+static thread_local uint32_t t_sync_launches = 0, t_ring_looks = 0;
+void last_sync_counts(uint32_t* launches, uint32_t* ring_looks, uint32_t* first_launches) {
+  *launches = t_sync_launches; *ring_looks = t_ring_looks; *first_launches = kFirstLaunches;
+}
+
 int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[], uint8_t* const ws[], DecPlane (*planes[])[3], hipStream_t s,
                         uint8_t* batch_ws, hipError_t* herr, int* image_rc) {
 #define JD_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { *herr = _e; (void)hipStreamSynchronize(s); return 1; } } while (0)
@@ -933,6 +963,7 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
   uint32_t max_nsub = 0;
   for (int k = 0; k < n; ++k) max_nsub = std::max(max_nsub, jobs[k].j.nsub);
   uint32_t round = 1;
+  t_sync_launches = 0u; t_ring_looks = 0u;
   for (uint32_t batch = kFirstLaunches;; batch = kMoreLaunches) {   // (even numbers)
     if (round > max_nsub + 34u) { (void)hipStreamSynchronize(s); return -1; }   // cannot happen: every launch fixes at least one more subsequence
     for (uint32_t r = 0; r < batch; r += 2, round += 2) {   // odd rounds read buffer 0, even ones buffer 1: the result is in buffer 0
@@ -941,6 +972,7 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
     }
     JD_TRY(hipMemcpyAsync(flags.data(), dflags, flags.size() * 4, hipMemcpyDeviceToHost, s));
     JD_TRY(hipStreamSynchronize(s));
+    t_sync_launches = round - 1u; ++t_ring_looks;
     bool any = false;
     for (int k = 0; k < n; ++k) any = any || flags[(size_t)k * kFlagWords + 64u + ((round - 1u) & 63u)] != 0u;
     if (!any) break;

@@ -419,26 +419,29 @@ static int br_get(bitr* b, int n) {
 }
 static int extend(int v, int n) { return n == 0 ? 0 : (v < (1 << (n - 1)) ? v - (1 << n) + 1 : v); } /* F.2.2.1 */
 
-/* libjpeg jidctint.c ("islow"), coefficients in natural order already multiplied by the quantiser */
+/* libjpeg jidctint.c ("islow"), coefficients in natural order already multiplied by the quantiser; 64-bit intermediates as libjpeg's
+ * JLONG: a legal file (coefficients up to 1023 and 2047, quantisers up to 255) overflows 32 bits in both passes */
 static void idct_1d(const int32_t in[8], int32_t out[8], int pass) {
-  int32_t z2 = in[2], z3 = in[6];
-  int32_t z1 = (z2 + z3) * FIX_0_541196100;
-  int32_t tmp2 = z1 + z3 * (-FIX_1_847759065), tmp3 = z1 + z2 * FIX_0_765366865;
+  int64_t z2 = in[2], z3 = in[6];
+  int64_t z1 = (z2 + z3) * FIX_0_541196100;
+  int64_t tmp2 = z1 + z3 * (-FIX_1_847759065), tmp3 = z1 + z2 * FIX_0_765366865;
   z2 = in[0]; z3 = in[4];
-  int32_t tmp0 = (z2 + z3) << CONST_BITS, tmp1 = (z2 - z3) << CONST_BITS;
-  int32_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
+  int64_t tmp0 = (z2 + z3) * (1 << CONST_BITS), tmp1 = (z2 - z3) * (1 << CONST_BITS);
+  int64_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
   tmp0 = in[7]; tmp1 = in[5]; tmp2 = in[3]; tmp3 = in[1];
   z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
-  int32_t z4 = tmp1 + tmp3, z5 = (z3 + z4) * FIX_1_175875602;
+  int64_t z4 = tmp1 + tmp3, z5 = (z3 + z4) * FIX_1_175875602;
   tmp0 *= FIX_0_298631336; tmp1 *= FIX_2_053119869; tmp2 *= FIX_3_072711026; tmp3 *= FIX_1_501321110;
   z1 *= -FIX_0_899976223; z2 *= -FIX_2_562915447; z3 *= -FIX_1_961570560; z4 *= -FIX_0_390180644;
   z3 += z5; z4 += z5;
   tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
   const int sh = pass == 0 ? CONST_BITS - PASS1_BITS : CONST_BITS + PASS1_BITS + 3;
-  out[0] = DESCALE(tmp10 + tmp3, sh); out[7] = DESCALE(tmp10 - tmp3, sh);
-  out[1] = DESCALE(tmp11 + tmp2, sh); out[6] = DESCALE(tmp11 - tmp2, sh);
-  out[2] = DESCALE(tmp12 + tmp1, sh); out[5] = DESCALE(tmp12 - tmp1, sh);
-  out[3] = DESCALE(tmp13 + tmp0, sh); out[4] = DESCALE(tmp13 - tmp0, sh);
+  const int64_t o[8] = {tmp10 + tmp3, tmp11 + tmp2, tmp12 + tmp1, tmp13 + tmp0, tmp13 - tmp0, tmp12 - tmp1, tmp11 - tmp2, tmp10 - tmp3};
+  /* pass 1: the workspace fits an int (libjpeg's is one); pass 2: only the ten bits range_limit is indexed with are kept */
+  for (int k = 0; k < 8; ++k) {
+    const int64_t v = (o[k] + ((int64_t)1 << (sh - 1))) >> sh;
+    out[k] = pass == 0 ? (int32_t)v : (int32_t)(v & 1023);
+  }
 }
 void orc_jpeg_idct(const int16_t coef_natural[64], const uint16_t quant_natural[64], uint8_t samples[64]) {
   int32_t ws[64], v[8], r[8];
@@ -447,11 +450,12 @@ void orc_jpeg_idct(const int16_t coef_natural[64], const uint16_t quant_natural[
     idct_1d(v, r, 0);
     for (int k = 0; k < 8; ++k) ws[k * 8 + c] = r[k];
   }
-  for (int row = 0; row < 8; ++row) { /* pass 2: rows, + 128, clamp (libjpeg's range_limit table) */
+  for (int row = 0; row < 8; ++row) { /* pass 2: rows, then libjpeg's range_limit[x & 1023]: the clamp of x + 128 to 0..255 for
+                                         -512 <= x <= 511, wrapping outside (x = 600 -> 0, not 255) */
     idct_1d(&ws[row * 8], r, 1);
     for (int k = 0; k < 8; ++k) {
-      int32_t x = r[k] + 128;
-      samples[row * 8 + k] = (uint8_t)(x < 0 ? 0 : (x > 255 ? 255 : x));
+      const int32_t i = r[k] & 1023;
+      samples[row * 8 + k] = (uint8_t)(i < 128 ? i + 128 : (i < 512 ? 255 : (i < 896 ? 0 : i - 896)));
     }
   }
 }

@@ -191,7 +191,9 @@ np.savez(sys.argv[2], **out)
 @pytest.mark.parametrize("size", [(1920, 1080), (200, 120), (16, 16)])
 def test_decoder_reads_restart_intervals(hip, orc, tmp_path, size):
     """files with DRI / RSTn markers (libjpeg-turbo through Pillow writes them; cameras do): planes identical to the CPU restatement,
-    which tests/test_jpeg_oracle.py holds equal to libjpeg on such files; then corrupted copies must come back with a status"""
+    which tests/test_jpeg_oracle.py holds equal to libjpeg on such files; then corrupted copies must come back with a status.
+    Skips without Pillow: the restart-interval coverage that always runs is the constructed streams `flat_one_bit_rst*` and
+    `stuffing_edges_rst_*` of tests/test_gpu_jpeg_streams.py."""
     import subprocess, sys
     from tests.test_jpeg_oracle import _content
     lib = hip.load()
@@ -302,7 +304,9 @@ def test_random_files_decode_like_libjpeg(hip, orc, tmp_path):
     """400 random files (oracle encoder and Pillow / libjpeg-turbo: standard and optimised tables, restart intervals from one MCU to
     thousands, 2x2 to 2400x1400, qualities 1-100, noise / smooth / flat content, colour and single-plane): the device decoder's
     planes equal libjpeg's in device and in host memory.  `python tests/stress_jpeg_dec.py 20000 11` is the long form of this test
-    (40 000 identical decodes on an MI355X after the decoder's synchronisation passes were rewritten)."""
+    (40 000 identical decodes on an MI355X after the decoder's synchronisation passes were rewritten).
+    Skips without Pillow: optimised tables and restart intervals are then reached by the constructed streams of
+    tests/test_gpu_jpeg_streams.py alone (cases `flat_one_bit_rst*` and `stuffing_edges_*`)."""
     try:
         import PIL  # noqa: F401
     except ImportError:
