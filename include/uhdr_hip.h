@@ -668,6 +668,67 @@ int uhdr_hip_apply_gainmap_rgb_batch(int n, const uhdr_hip_image_t* yuv420_image
                                      const uhdr_hip_metadata_t* metadata, int output_format, float max_display_boost,
                                      uhdr_hip_image_t* dests, int apply_mode, void* stream);
 
+/* ---- gain maps with gamma, offsets and an HDR capacity range (no reference counterpart) ------
+ * The reference's applyGainMap refuses every file whose metadata is not DEGENERATE -- gamma == 1, both offsets 0, hdrCapacityMin ==
+ * minContentBoost and hdrCapacityMax == maxContentBoost -- and so do the calls above (ERROR_BAD_METADATA).  Files in the field use
+ * all of these fields (current libultrahdr writes offsets of 1/64 by default).  The *_md calls implement the gain-map formula in
+ * full.  Symbols: min, max = min / maxContentBoost; Hmin, Hmax = hdrCapacityMin / Max; os, oh = offsetSdr / offsetHdr; D =
+ * max_display_boost.
+ *
+ * Validation, after the pointer checks, in this order: ERROR_BAD_METADATA for a version other than "1.0", a non-finite field,
+ * max < min, min <= 0, Hmax < Hmin, Hmin <= 0, an offset < 0 or gamma <= 0; (apply and decode) ERROR_INVALID_DISPLAY_BOOST for
+ * D < 1 or NaN; then the checks of the call whose conventions are named.
+ *
+ * Apply.  DEGENERATE metadata is forwarded to uhdr_hip_apply_gainmap_batch / uhdr_hip_apply_gainmap_rgb_batch: the bytes are those
+ * calls' in every apply mode, including the reference's exponent scaling by displayBoost / maxContentBoost.  For every other
+ * (GENERAL) metadata, per pixel and channel c (a one-plane map: one gain for the three channels):
+ *     W     = clamp((log2 D - log2 Hmin) / (log2 Hmax - log2 Hmin), 0, 1);   Hmax == Hmin: W = D >= Hmax ? 1 : 0
+ *     d     = min(D, Hmax)
+ *     g     = sampleMap's interpolated value in [0, 1], as in every other apply call
+ *     g'    = g^(1 / gamma)   (gamma == 1: g; 0 stays 0)
+ *     out_c = max(0, (e_c + os) * 2^((log2 min * (1 - g') + log2 max * g') * W) - oh) / d
+ * with e_c the linear SDR channel (p3YuvToRgb, srgbInvOetf); the OETF and the packing of output_format follow as in the other
+ * calls (the 10-bit formats keep the reference's `& 0x3ff`: a value above 1.0 is not clamped).  The weight rule therefore DIFFERS
+ * between degenerate and general metadata when D < max: degenerate metadata scales the exponent by D / max as the reference does,
+ * general metadata by W, the gain-map specification's weight (log-domain).  The host forms W, log2 d and the exponent's two
+ * constants in double; the device works in f32 with the hardware exp2 / log2 and the FAST transfer functions.  There is ONE
+ * arithmetic for general metadata: UHDR_HIP_APPLY_FAST and UHDR_HIP_APPLY_EXACT both select it -- EXACT means "the bytes of the
+ * reference's CPU path", and the reference refuses these files, so there is nothing to be exact against.  Against the formula
+ * evaluated in double every 10-bit channel is within 1 code and every F16 channel within 1 half-precision ULP (FAST's bars).
+ * UHDR_HIP_APPLY_LUT and UHDR_HIP_APPLY_EXACT_UNFILTERED return ERROR_UNSUPPORTED_FEATURE for general metadata. */
+/* W and d = min(D, Hmax) by themselves, host code, as the apply calls form them (in double, returned as float).  BAD_PTR for NULL,
+ * then the validation above. */
+int uhdr_hip_gainmap_weight(const uhdr_hip_metadata_t* metadata, float max_display_boost, float* weight, float* display_boost);
+/* Conventions of uhdr_hip_apply_gainmap_batch.  The maps' pixelFormat selects the form: MONOCHROME or UNSPECIFIED -- one plane, rows
+ * of `width` bytes; RGBA8888 -- per channel, uhdr_hip_apply_gainmap_rgb_batch's layout rules (4-byte aligned, luma_stride in pixels,
+ * 0 = width); any other value is ERROR_UNSUPPORTED_FEATURE.  All maps of a call have the same form (the first map's). */
+int uhdr_hip_apply_gainmap_md_batch(int n, const uhdr_hip_image_t* yuv420_images, const uhdr_hip_image_t* gainmap_images,
+                                    const uhdr_hip_metadata_t* metadata, int output_format, float max_display_boost,
+                                    uhdr_hip_image_t* dests, int apply_mode, void* stream);
+/* generateGainMap against the caller's metadata (metadata_in is read, not written).  Everything up to the two luminances -- in
+ * nits, as encodeGain receives them -- is unchanged, on the exact path (no f32 pre-filter).  Then, in f32,
+ *     a = y_sdr + os * 203.0f,  b = y_hdr + oh * 203.0f,  gain = a > 0 ? b / a : 1, clamped to [min, max]
+ *     t = (log2(gain) - log2Min) / (log2Max - log2Min)      with the reference's promotions (gainmapmath.cpp:529-541)
+ *     byte = (uint8_t)(t * 255.0f)                          gamma == 1
+ *     byte = (uint8_t)(pow(t, (double)gamma) * 255.0)       otherwise, in double (t <= 0 gives 0)
+ * truncated as the reference truncates.  With gamma == 1 and zero offsets this is encodeGain bit for bit.  rgb != 0: the same rule
+ * per channel on sdr.c * 203.0f and hdr.c * hdr_white_nits, and the conventions (RGBA8888 dests, 4-byte aligned) of
+ * uhdr_hip_generate_gainmap_rgb_batch; rgb == 0: those of uhdr_hip_generate_gainmap_batch.  hdrCapacityMin / Max are validated but
+ * do not enter the map.  For gamma != 1 the device evaluates the power with its own f64 log2 / exp2: the value in front of the
+ * truncation is within 2^-30 of the libm evaluation's.  Such maps go into files through uhdr_hip_jpegr_encode_apix_batch with the
+ * same metadata: no further encode call is needed (an RGBA map: uhdr_hip_jpeg_encode_rgb_batch, then
+ * uhdr_hip_jpegr_append_gainmap).  Content-adaptive ranges: pass the adaptive call's range as metadata_in. */
+int uhdr_hip_generate_gainmap_md_batch(int n, const uhdr_hip_image_t* yuv420_images, const uhdr_hip_image_t* p010_images, int hdr_tf,
+                                       const uhdr_hip_metadata_t* metadata_in, uhdr_hip_image_t* dests, int sdr_is_601, int rgb,
+                                       void* stream);
+/* uhdr_hip_jpegr_decode_rgbmap_batch -- its signature, flags and per-file status rules, one- and three-component gain-map JPEGs --
+ * for files with any valid metadata: a file whose metadata is degenerate takes that call's path (identical bytes), any other goes
+ * through uhdr_hip_apply_gainmap_md_batch with the file's own metadata (per file: BAD_METADATA for invalid fields, UNSUPPORTED_FEATURE
+ * for LUT / EXACT_UNFILTERED).  UHDR_HIP_OUTPUT_SDR is unchanged. */
+int uhdr_hip_jpegr_decode_md_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
+                                   void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests,
+                                   uhdr_hip_metadata_t* metadata, int* status, int apply_mode, int mem_space, void* stream, int flags);
+
 /* ---- content-adaptive gain maps (no reference counterpart) ---------------------------------
  * The reference encodes every map against minContentBoost = 1, maxContentBoost = hdr_white / 203 (ultrahdr.cpp:250-257): 255 codes
  * over 2.3 stops (HLG, LINEAR) or 5.6 stops (PQ) whatever the picture holds, gains below 1 clipped.  The adaptive calls encode

@@ -126,6 +126,10 @@ class UltraHdrHip {
 status_t toneMapSdr(uhdr_uncompressed_ptr src, uhdr_uncompressed_ptr dest, ultrahdr_transfer_function hdr_tf, int tonemap_op,
                     float hdr_peak_nits = 0.0f, float* headroom = nullptr);
 
+// The weight W of the gain-map exponent and the divisor d = min(max_display_boost, hdrCapacityMax) that a decode with
+// JpegRHip::setAnyGainMapMetadata forms for this metadata (uhdr_hip_gainmap_weight; host code, no device needed)
+status_t gainMapWeight(ultrahdr_metadata_ptr metadata, float max_display_boost, float* weight, float* display_boost);
+
 // ---- editing effects: the free functions of lib/include/ultrahdr/editorhelper.h:49-63, same signatures ----------
 enum ultrahdr_mirroring_direction : int { ULTRAHDR_MIRROR_VERTICAL = 0, ULTRAHDR_MIRROR_HORIZONTAL = 1 };
 
@@ -248,6 +252,11 @@ class JpegRHip {
   // which are single-channel) and decodeJPEGR applies a three-component gain map per channel
   // (uhdr_hip_jpegr_decode_rgbmap_batch; files with one-plane maps decode as ever).  The other encodeJPEGR overloads are unchanged.
   void setMultiChannelGainMap(bool on) { mMultiChannelGainMap = on; }
+  // false (default): decodeJPEGR refuses, as the reference does, every file whose metadata has a gamma other than 1, an offset
+  // other than 0 or an HDR capacity range other than the content boost range (ERROR_ULTRAHDR_BAD_METADATA).  true: such files --
+  // what current libultrahdr, cameras and editors write -- are decoded with the full gain-map formula, one- and three-component
+  // maps alike (uhdr_hip_jpegr_decode_md_batch); files the reference reads give the bytes they gave.
+  void setAnyGainMapMetadata(bool on) { mAnyGainMapMetadata = on; }
 
  private:
   int mApplyMode = 1;
@@ -256,6 +265,7 @@ class JpegRHip {
   float mHdrPeakNits = 0.0f;
   bool mDecodeAnySampling = false;
   bool mMultiChannelGainMap = false;
+  bool mAnyGainMapMetadata = false;
 };
 
 }  // namespace ultrahdr

@@ -94,6 +94,11 @@ SIGNATURES = {
                                                      C.c_void_p]),
     "uhdr_hip_jpegr_decode_rgbmap_batch": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_float, C.POINTER(C.c_void_p),
                                                      C.POINTER(C.c_size_t), _IP, _MP, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "uhdr_hip_gainmap_weight": (C.c_int, [_MP, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "uhdr_hip_apply_gainmap_md_batch": (C.c_int, [C.c_int, _IP, _IP, _MP, C.c_int, C.c_float, _IP, C.c_int, C.c_void_p]),
+    "uhdr_hip_generate_gainmap_md_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _MP, _IP, C.c_int, C.c_int, C.c_void_p]),
+    "uhdr_hip_jpegr_decode_md_batch": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_float, C.POINTER(C.c_void_p),
+                                                 C.POINTER(C.c_size_t), _IP, _MP, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "uhdr_hip_mem_pool_create": (C.c_int, [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]),
     "uhdr_hip_mem_pool_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "uhdr_hip_mem_pool_free": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -326,6 +331,16 @@ def adaptive_boost_range(hdr_tf, g_min, g_max):
     if rc != NO_ERROR:
         raise UhdrHipError("uhdr_hip_adaptive_boost_range -> %d" % rc)
     return lo.value, hi.value
+
+
+def gainmap_weight(md, max_display_boost):
+    """uhdr_hip_gainmap_weight: (W, d) -- the weight of the gain-map exponent and the divisor min(D, hdrCapacityMax) the *_md apply
+    calls form for this metadata and display boost"""
+    w, d = C.c_float(), C.c_float()
+    rc = load().uhdr_hip_gainmap_weight(C.byref(md), max_display_boost, C.byref(w), C.byref(d))
+    if rc != NO_ERROR:
+        raise UhdrHipError("uhdr_hip_gainmap_weight -> %d" % rc)
+    return w.value, d.value
 
 
 def tonemap_headroom(hdr_tf, gamma_max, peak_nits=0.0):

@@ -260,6 +260,11 @@ void fill_generate_dest(const uhdr_hip_image_t* yuv, uhdr_hip_image_t* dest) {  
 void encode_constants(float min_boost, float max_boost, float l2min, float l2max, double* scale, uint32_t* bmin,
                       uint32_t* bmax) {
   const double den = (double)(l2max - l2min);
+  if (!(den > 0.0)) {   // maxContentBoost == minContentBoost (the _md generate accepts it): every gain is on a clamp and t is 0 / 0;
+    *scale = 0.0;       // byte 0, not a NaN cast to an integer
+    *bmin = *bmax = 0u;
+    return;
+  }
   *scale = (double)255.0f / den;
   *bmin = (uint8_t)((std::log2((double)min_boost) - (double)l2min) / den * (double)255.0f);
   *bmax = (uint8_t)((std::log2((double)max_boost) - (double)l2min) / den * (double)255.0f);
@@ -533,6 +538,65 @@ int validate_apply(const uhdr_hip_image_t* yuv, const uhdr_hip_image_t* map, con
   if (yuv->width * map->height != yuv->height * map->width) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
   return UHDR_HIP_NO_ERROR;
 }
+// ---- general metadata: gamma, offsets, HDR capacity (the *_md calls) --------
+// what validate_apply accepts of the metadata's numbers: the reference's applyGainMap computes nothing else
+bool md_degenerate(const uhdr_hip_metadata_t& md) {
+  return md.gamma == 1.0f && md.offsetSdr == 0.0f && md.offsetHdr == 0.0f && md.hdrCapacityMin == md.minContentBoost &&
+         md.hdrCapacityMax == md.maxContentBoost;
+}
+int validate_md(const uhdr_hip_metadata_t* md) {
+  if (strncmp(md->version, "1.0", sizeof(md->version)) != 0) return UHDR_HIP_ERROR_BAD_METADATA;
+  const float f[7] = {md->maxContentBoost, md->minContentBoost, md->gamma, md->offsetSdr, md->offsetHdr, md->hdrCapacityMin, md->hdrCapacityMax};
+  for (float v : f)
+    if (!std::isfinite(v)) return UHDR_HIP_ERROR_BAD_METADATA;
+  if (md->maxContentBoost < md->minContentBoost || md->minContentBoost <= 0.0f) return UHDR_HIP_ERROR_BAD_METADATA;
+  if (md->hdrCapacityMax < md->hdrCapacityMin || md->hdrCapacityMin <= 0.0f) return UHDR_HIP_ERROR_BAD_METADATA;
+  if (md->offsetSdr < 0.0f || md->offsetHdr < 0.0f || md->gamma <= 0.0f) return UHDR_HIP_ERROR_BAD_METADATA;
+  return UHDR_HIP_NO_ERROR;
+}
+// W and d of include/uhdr_hip.h, in double (D >= 1, possibly infinite; the metadata has passed validate_md)
+void md_weight(const uhdr_hip_metadata_t& md, float max_display_boost, double* w, double* d) {
+  const double D = (double)max_display_boost, hmin = (double)md.hdrCapacityMin, hmax = (double)md.hdrCapacityMax;
+  if (md.hdrCapacityMax == md.hdrCapacityMin) *w = D >= hmax ? 1.0 : 0.0;
+  else *w = std::fmin(std::fmax((std::log2(D) - std::log2(hmin)) / (std::log2(hmax) - std::log2(hmin)), 0.0), 1.0);
+  *d = std::fmin(D, hmax);
+}
+AppMdConsts apply_md_consts(const uhdr_hip_metadata_t& md, float max_display_boost) {
+  double w, d;
+  md_weight(md, max_display_boost, &w, &d);
+  const double l2min = std::log2((double)md.minContentBoost), l2max = std::log2((double)md.maxContentBoost);
+  AppMdConsts m;
+  m.A = (float)((l2max - l2min) * w);
+  m.B = (float)(l2min * w - std::log2(d));
+  m.inv_gamma = (float)(1.0 / (double)md.gamma);
+  m.off_sdr = md.offsetSdr;
+  m.off_hdr_d = (float)((double)md.offsetHdr / d);
+  m.gamma_on = md.gamma != 1.0f ? 1u : 0u;
+  return m;
+}
+// the encode constants of uhdr_hip_generate_gainmap_md_batch beside generate_consts': the offsets in nits and, for gamma != 1, the
+// bytes of a gain on either clamp, evaluated as the header states the rule (libm, double)
+GenMdConsts generate_md_consts(const uhdr_hip_metadata_t& md, const GenConsts& c) {
+  GenMdConsts m;
+  m.off_sdr_nits = md.offsetSdr * 203.0f;
+  m.off_hdr_nits = md.offsetHdr * 203.0f;
+  m.gamma_on = md.gamma != 1.0f ? 1u : 0u;
+  m.gamma = (double)md.gamma;
+  m.den = (double)(c.log2_max - c.log2_min);
+  auto byte_of = [&](float boost) -> uint32_t {
+    const double t = (std::log2((double)boost) - (double)c.log2_min) / m.den;
+    if (!(t > 0.0)) return 0u;
+    return (uint32_t)(uint8_t)std::fmin(std::pow(t, m.gamma) * 255.0, 255.0);
+  };
+  if (!(m.den > 0.0)) {   // maxContentBoost == minContentBoost: every gain is on a clamp, byte 0 (as encode_constants answers)
+    m.byte_min = m.byte_max = 0u;
+  } else {
+    m.byte_min = byte_of(md.minContentBoost);
+    m.byte_max = byte_of(md.maxContentBoost);
+  }
+  return m;
+}
+
 bool apply_writes(int fmt) {
   return fmt == UHDR_HIP_OUTPUT_HDR_LINEAR || fmt == UHDR_HIP_OUTPUT_HDR_PQ || fmt == UHDR_HIP_OUTPUT_HDR_HLG ||
          fmt == UHDR_HIP_OUTPUT_HDR_LINEAR_RGB_10BIT;
@@ -2068,13 +2132,15 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
 // the same with flags: UHDR_HIP_DECODE_ANY_SAMPLING also reads files whose primary image (or gain map) is 4:4:4, 4:2:2 or 4:4:0.
 // rgb_maps (uhdr_hip_jpegr_decode_rgbmap_batch): a gain-map JPEG of three components, of any of those samplings whatever the flag, is
 // converted to libjpeg-turbo's RGBA and applied per channel (uhdr_hip_apply_gainmap_rgb_batch); a one-component map as ever.
+// any_md (uhdr_hip_jpegr_decode_md_batch, with rgb_maps): a file whose metadata is not what validate_apply accepts goes through
+// uhdr_hip_apply_gainmap_md_batch instead of being refused.
 static int jpegr_decode_files(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
                               void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
-                              int* status, int apply_mode, int mem_space, void* stream, int flags, bool rgb_maps) {
+                              int* status, int apply_mode, int mem_space, void* stream, int flags, bool rgb_maps, bool any_md = false) {
   if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   const bool any_sampling = (flags & UHDR_HIP_DECODE_ANY_SAMPLING) != 0;
   if (n < 0 || (n > 0 && (jpegr == nullptr || jpegr_size == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
-  if (max_display_boost < 1.0f) return UHDR_HIP_ERROR_INVALID_DISPLAY_BOOST;                             // :666-669
+  if (max_display_boost < 1.0f || (any_md && std::isnan(max_display_boost))) return UHDR_HIP_ERROR_INVALID_DISPLAY_BOOST;   // :666-669
   if (output_format < UHDR_HIP_OUTPUT_SDR || output_format > UHDR_HIP_OUTPUT_HDR_LINEAR_RGB_10BIT) return UHDR_HIP_ERROR_INVALID_OUTPUT_FORMAT;
   std::vector<JpegrFile> files((size_t)n);
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
@@ -2204,6 +2270,10 @@ static int jpegr_decode_files(int n, const void* const* jpegr, const size_t* jpe
     if (rgb_maps && !f.info[1].gray) {
       gimg.data = st->pool[5 * (size_t)n + 1 + (size_t)i];
       gimg.pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
+    }
+    if (any_md && !md_degenerate(f.md)) {   // (degenerate metadata: the path and the bytes of the rgbmap decode)
+      st_[i] = uhdr_hip_apply_gainmap_md_batch(1, &ydesc, &gimg, &f.md, output_format, max_display_boost, &ddev, apply_mode, stream);
+    } else if (rgb_maps && !f.info[1].gray) {
       st_[i] = uhdr_hip_apply_gainmap_rgb_batch(1, &ydesc, &gimg, &f.md, output_format, max_display_boost, &ddev, apply_mode, stream);
     } else {
       st_[i] = uhdr_hip_apply_gainmap(&ydesc, &gimg, &f.md, output_format, max_display_boost, &ddev, apply_mode, UHDR_HIP_MEM_DEVICE, stream);
@@ -2230,6 +2300,13 @@ int uhdr_hip_jpegr_decode_rgbmap_batch(int n, const void* const* jpegr, const si
                                        uhdr_hip_metadata_t* metadata, int* status, int apply_mode, int mem_space, void* stream, int flags) {
   return jpegr_decode_files(n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode,
                             mem_space, stream, flags, true);
+}
+
+int uhdr_hip_jpegr_decode_md_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
+                                   void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
+                                   int* status, int apply_mode, int mem_space, void* stream, int flags) {
+  return jpegr_decode_files(n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode,
+                            mem_space, stream, flags, true, true);
 }
 
 int uhdr_hip_jpegr_decode(const void* jpegr, size_t jpegr_size, int output_format, float max_display_boost, void* dest_data,
@@ -3539,6 +3616,135 @@ int uhdr_hip_apply_gainmap_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr
       c.ex_cap = cap;
     }
     if (writes) HIP_TRY(launch_apply(c, b, m, output_format, apply_mode, fast, s));
+    i += m;
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
+// ---- general metadata: gamma, offsets, HDR capacity ---------------------------
+int uhdr_hip_gainmap_weight(const uhdr_hip_metadata_t* metadata, float max_display_boost, float* weight, float* display_boost) {
+  if (metadata == nullptr || weight == nullptr || display_boost == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  const int rc = validate_md(metadata);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if (!(max_display_boost >= 1.0f)) return UHDR_HIP_ERROR_INVALID_DISPLAY_BOOST;
+  double w, d;
+  md_weight(*metadata, max_display_boost, &w, &d);
+  *weight = (float)w;
+  *display_boost = (float)d;
+  return UHDR_HIP_NO_ERROR;
+}
+
+// Degenerate metadata: the existing call of the maps' form, with its checks, routes and bytes.  General metadata:
+// uhdr_hip_apply_gainmap_rgb_batch's chunks (equal sizes and map strides share a launch), every chunk one k_apply_px_md launch.
+int uhdr_hip_apply_gainmap_md_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* maps, const uhdr_hip_metadata_t* metadata,
+                                    int output_format, float max_display_boost, uhdr_hip_image_t* dests, int apply_mode, void* stream) {
+  if (n < 0 || (n > 0 && (yuvs == nullptr || maps == nullptr || dests == nullptr)) || metadata == nullptr)
+    return UHDR_HIP_ERROR_BAD_PTR;
+  for (int i = 0; i < n; ++i)
+    if (yuvs[i].data == nullptr || yuvs[i].chroma_data == nullptr || maps[i].data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  int rc = validate_md(metadata);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if (!(max_display_boost >= 1.0f)) return UHDR_HIP_ERROR_INVALID_DISPLAY_BOOST;
+  const int form = n > 0 ? maps[0].pixelFormat : UHDR_HIP_PIX_FMT_MONOCHROME;
+  if (form != UHDR_HIP_PIX_FMT_MONOCHROME && form != UHDR_HIP_PIX_FMT_UNSPECIFIED && form != UHDR_HIP_PIX_FMT_RGBA8888)
+    return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  const bool rgb = form == UHDR_HIP_PIX_FMT_RGBA8888;
+  if (md_degenerate(*metadata))
+    return rgb ? uhdr_hip_apply_gainmap_rgb_batch(n, yuvs, maps, metadata, output_format, max_display_boost, dests, apply_mode, stream)
+               : uhdr_hip_apply_gainmap_batch(n, yuvs, maps, metadata, output_format, max_display_boost, dests, apply_mode, stream);
+  // a one-plane map's rows are `width` bytes, an RGBA map's luma_stride pixels (0 = width)
+  auto stride_of = [rgb](const uhdr_hip_image_t& mp) { return (!rgb || mp.luma_stride == 0) ? mp.width : mp.luma_stride; };
+  for (int i = 0; i < n; ++i) {   // validate_apply's scale-factor checks, then uhdr_hip_apply_gainmap_rgb_batch's of the map
+    const uhdr_hip_image_t& y = yuvs[i];
+    const uhdr_hip_image_t& mp = maps[i];
+    if (mp.width == 0 || mp.height == 0) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
+    if (y.width % mp.width != 0 || y.height % mp.height != 0) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
+    if (y.width * mp.height != y.height * mp.width) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
+    if (rgb && !al(mp.data, 4)) return UHDR_HIP_ERROR_BAD_PTR;
+    if (rgb && (stride_of(mp) < mp.width || stride_of(mp) > 0xFFFFFFFFull)) return UHDR_HIP_ERROR_INVALID_STRIDE;
+  }
+  // FAST and EXACT select the one arithmetic there is: EXACT promises the reference's bytes, and the reference refuses this metadata
+  if (apply_mode != UHDR_HIP_APPLY_FAST && apply_mode != UHDR_HIP_APPLY_EXACT) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool writes = apply_writes(output_format);
+  for (int i = 0; i < n; ++i)
+    if (writes && dests[i].data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  const AppMdConsts mc = apply_md_consts(*metadata, max_display_boost);
+  int i = 0;
+  while (i < n) {
+    const uhdr_hip_image_t& y0 = yuvs[i];
+    const uhdr_hip_image_t& m0 = maps[i];
+    const int scale = (int)(y0.width / m0.width);
+    const float* idw = nullptr;
+    float* idw_transient = nullptr;
+    if ((rc = idw_for_scale(st, scale, &idw, &idw_transient)) != UHDR_HIP_NO_ERROR) return rc;
+    struct FreeAfter {   // a table too large to keep: freed when this chunk's launches have finished
+      float* p; hipStream_t s;
+      ~FreeAfter() { if (p) { (void)hipStreamSynchronize(s); (void)hipFree(p); } }
+    } free_after{idw_transient, s};
+    AppConsts c = apply_consts(y0, m0, *metadata, max_display_boost, idw);
+    c.map_stride = (uint32_t)stride_of(m0);
+    c.tab = st->lut;
+    AppBatch b;
+    int m = 0;
+    while (i + m < n && m < kMaxChunk) {
+      const uhdr_hip_image_t& y = yuvs[i + m];
+      const uhdr_hip_image_t& mp = maps[i + m];
+      if (y.width != y0.width || y.height != y0.height || mp.width != m0.width || mp.height != m0.height || stride_of(mp) != stride_of(m0)) break;
+      b.img[m] = app_image(y, mp, dests[i + m].data);
+      fill_apply_dest(&y, &dests[i + m]);
+      ++m;
+    }
+    if (writes) HIP_TRY(launch_apply_md(c, mc, b, m, output_format, rgb, s));
+    i += m;
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
+// uhdr_hip_generate_gainmap_rgb_batch's chunks; every chunk one k_generate_md launch on the exact path
+int uhdr_hip_generate_gainmap_md_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf,
+                                       const uhdr_hip_metadata_t* md_in, uhdr_hip_image_t* dests, int sdr_is_601, int rgb, void* stream) {
+  if (n < 0 || (n > 0 && (yuvs == nullptr || p010s == nullptr || dests == nullptr)) || md_in == nullptr)
+    return UHDR_HIP_ERROR_BAD_PTR;
+  for (int i = 0; i < n; ++i) {
+    if (yuvs[i].data == nullptr || yuvs[i].chroma_data == nullptr || p010s[i].data == nullptr || p010s[i].chroma_data == nullptr ||
+        dests[i].data == nullptr || (rgb != 0 && !al(dests[i].data, 4)))
+      return UHDR_HIP_ERROR_BAD_PTR;
+  }
+  int rc = validate_md(md_in);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  for (int i = 0; i < n; ++i)
+    if ((rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, md_in, &dests[i])) != UHDR_HIP_NO_ERROR) return rc;
+  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ)
+    return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int i = 0;
+  while (i < n) {
+    // chunk = up to kMaxChunk consecutive images of identical size, gamuts and alignment class
+    const uhdr_hip_image_t& y0 = yuvs[i];
+    const GenConsts c = generate_consts(y0.colorGamut, p010s[i].colorGamut, hdr_tf, sdr_is_601, y0.width, y0.height, *md_in);
+    const GenMdConsts mc = generate_md_consts(*md_in, c);
+    GenBatch b;
+    int m = 0;
+    bool aligned = true;
+    while (i + m < n && m < kMaxChunk) {
+      const uhdr_hip_image_t& y = yuvs[i + m];
+      if (y.width != y0.width || y.height != y0.height || y.colorGamut != y0.colorGamut ||
+          p010s[i + m].colorGamut != p010s[i].colorGamut)
+        break;
+      b.img[m] = gen_image(y, p010s[i + m], dests[i + m].data);
+      const bool a = gen_aligned(b.img[m], c.width, c.height) && (rgb == 0 || al(b.img[m].map, 8));   // (a thread's pair is one store)
+      if (m == 0) aligned = a;
+      else if (a != aligned) break;
+      fill_generate_dest(&y, &dests[i + m]);
+      if (rgb != 0) dests[i + m].pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
+      ++m;
+    }
+    HIP_TRY(launch_generate_md(c, mc, b, m, hdr_tf, aligned, rgb != 0, s));
     i += m;
   }
   return UHDR_HIP_NO_ERROR;

@@ -265,7 +265,22 @@ struct FxChainJob {
 };
 constexpr int kFxChainRound = 64;   // images per round of uhdr_hip_add_effects_batch (three plane jobs each)
 
-static_assert(sizeof(GenConsts) + sizeof(GenBatch) <= 4096, "generate kernel arguments exceed the kernarg segment");
+// ---- general gain-map metadata: what k_apply_px_md / k_generate_md take beside the usual constants ----
+struct AppMdConsts {       // out = max(0, (e + off_sdr) * 2^(A g' + B) - off_hdr_d),  g' = g^inv_gamma
+  float A, B;              // (log2 max - log2 min) W  and  log2 min W - log2 d, formed in double
+  float inv_gamma;
+  float off_sdr, off_hdr_d;   // offsetSdr; offsetHdr / d
+  uint32_t gamma_on;       // gamma != 1: selects the kernel with the v_log_f32 / v_exp_f32 pair
+};
+struct GenMdConsts {
+  float off_sdr_nits, off_hdr_nits;   // offset * 203.0f, in f32
+  uint32_t gamma_on;                  // gamma != 1 (launch-uniform branch in encode_gain_md)
+  uint32_t byte_min, byte_max;        // gamma != 1: the bytes of gain <= min / gain >= max
+  double gamma, den;                  // (double)gamma; (double)(log2_max - log2_min)
+};
+
+static_assert(sizeof(GenConsts) + sizeof(GenMdConsts) + sizeof(GenBatch) <= 4096, "generate kernel arguments exceed the kernarg segment");
+static_assert(sizeof(AppConsts) + sizeof(AppMdConsts) + sizeof(AppBatch) + 16 <= 4096, "apply kernel arguments exceed the kernarg segment");
 static_assert(sizeof(AppConsts) + sizeof(AppBatch) <= 4096, "apply kernel arguments exceed the kernarg segment");
 
 // launchers (enqueue only; return hipError_t of the launch)
@@ -298,6 +313,11 @@ hipError_t launch_apply(const AppConsts& c, const AppBatch& b, int n, int fmt, i
                         bool fast_s4, hipStream_t s);
 // per-pixel apply of RGBA maps (AppImage::map 4-byte aligned, AppConsts::map_stride set): FAST or the unfiltered EXACT arithmetic
 hipError_t launch_apply_rgb(const AppConsts& c, const AppBatch& b, int n, int fmt, bool exact, hipStream_t s);
+// general metadata: per-pixel apply of one-plane maps (rows of map_w bytes) or RGBA maps (launch_apply_rgb's layout); one f32 arithmetic
+hipError_t launch_apply_md(const AppConsts& c, const AppMdConsts& m, const AppBatch& b, int n, int fmt, bool rgb, hipStream_t s);
+// general metadata: launch_generate_rgb's launch; rgb: its RGBA map, otherwise one byte per map pixel (aligned launches: 2-byte aligned)
+hipError_t launch_generate_md(const GenConsts& c, const GenMdConsts& m, const GenBatch& b, int n, int hdr_tf, bool aligned, bool rgb,
+                              hipStream_t s);
 hipError_t launch_build_luts(float* lut /* kLutTotal floats */, hipStream_t s);
 hipError_t launch_build_lut_codes(float* lut /* the whole buffer: reads the two OETF tables, writes kCodeHlg / kCodePq */, hipStream_t s);
 // GainLUT table (kGainLutN floats, device) for (log2 min, log2 max, boost factor)

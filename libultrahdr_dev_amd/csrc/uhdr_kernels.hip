@@ -5,6 +5,7 @@
 //   k_apply_px<FMT,EXACT>    same loop, any integer scale / any alignment / EXACT arithmetic
 //   k_apply_s4_est, k_apply_px_est, k_apply_resolve   EXACT arithmetic as an f32 estimate + the exact path on the pixels in doubt
 //   k_apply_lut_s4, k_apply_lut   the loops with the reference's LUT accessors (opt-in LUT mode)
+//   k_apply_px_md, k_generate_md   gain maps with gamma, offsets and an HDR capacity range (no reference counterpart)
 //   k_tonemap_*              UltraHdr::toneMap                    (:517-558)
 //   k_convert_yuv<ALIGNED>   JpegR::convertYuv + transformYuv420  (lib/src/jpegr.cpp:1199-1203,
 //                                                                  lib/src/gainmapmath.cpp:483-520)
@@ -1126,6 +1127,100 @@ hipError_t launch_generate_rgb(const GenConsts& c, const GenBatch& b, int n, int
   }
 }
 
+// Gain maps against caller-given metadata: k_generate_rgb's grid and front end on the exact path; what
+// is encoded is (hdr + offsetHdr * 203) / (sdr + offsetSdr * 203) -- of the luminances, or per channel (RGB) -- and the byte is
+// t^gamma * 255, truncated.  gamma == 1 is encode_gain_guarded, the reference's bytes.  Otherwise t and the power run on the lean
+// f64 log2 / exp2 (relative error < 2^-50 each): the value in front of the truncation is within 2^-36 of the libm evaluation's.
+__device__ __forceinline__ uint8_t encode_gain_md(const GenConsts& c, const GenMdConsts& m, float sdr_nits, float hdr_nits) {
+  const float gain = raw_gain(sdr_nits + m.off_sdr_nits, hdr_nits + m.off_hdr_nits);
+  if (m.gamma_on == 0u)   // (launch-uniform)
+    return encode_gain_guarded(gain, c.min_boost, c.max_boost, c.log2_min, c.log2_max, c.enc_scale, c.enc_byte_min, c.enc_byte_max);
+  if (!(gain > c.min_boost)) return (uint8_t)m.byte_min;
+  if (!(gain < c.max_boost)) return (uint8_t)m.byte_max;
+  const double t = (fast_log2((double)gain) - (double)c.log2_min) / m.den;
+  if (!(t > 0.0)) return 0;
+  const double v = fast_exp2(m.gamma * fast_log2(t)) * 255.0;
+  return (uint8_t)(uint32_t)fmin(v, 255.0);
+}
+template <int TF, bool ALIGNED, int TILES, bool RGB>
+__global__ void __launch_bounds__(kGenBlock, 1) k_generate_md(const GenConsts c, const GenMdConsts m, const GenBatch b) {
+  const uint32_t img_i = blockIdx.x, blk = blockIdx.y;
+  const GenImage& im = b.img[img_i];
+  const uint8_t* im_v = im.u + (size_t)im.c_stride * (c.height / 2u);
+  const uint32_t pairs_per_row = (c.map_w + 1u) >> 1;
+  const uint32_t total = pairs_per_row * c.map_h;
+#pragma unroll 1
+  for (uint32_t t = 0; t < (uint32_t)TILES; ++t) {
+    const uint32_t idx = (blk * (uint32_t)TILES + t) * (uint32_t)kGenBlock + threadIdx.x;
+    if (idx >= total) break;
+    const uint32_t my = idx / pairs_per_row;
+    const uint32_t pr = idx - my * pairs_per_row;
+    const uint32_t mx = pr * 2u;
+    const bool two = ALIGNED || (mx + 1u < c.map_w);
+    uint32_t hy[2][4][2], huv[2][2][2], y8[2][4], u8[2][2], v8[2][2];
+    load_pair<ALIGNED>(c, im, im_v, my, pr, two, hy, huv, y8, u8, v8);
+    uint8_t o[2];
+    float gn[2];
+    GenMid lin;
+    gen_pair<TF, false, false, false, kGenLinear>(c, hy, huv, y8, u8, v8, o, gn, nullptr, nullptr, &lin);   // (a missing second pixel: zeros, dropped)
+    if (RGB) {
+      const f2 sdr[3] = {lin.r * splat(203.0f), lin.g * splat(203.0f), lin.b * splat(203.0f)};
+      const f2 hdr[3] = {lin.hr * splat(c.hdr_white_nits), lin.hg * splat(c.hdr_white_nits), lin.hb * splat(c.hdr_white_nits)};
+      uint32_t px[2] = {0xFF000000u, 0xFF000000u};
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+          px[k] |= (uint32_t)encode_gain_md(c, m, k ? sdr[ch].y : sdr[ch].x, k ? hdr[ch].y : hdr[ch].x) << (8 * ch);
+      }
+      uint32_t* mp = reinterpret_cast<uint32_t*>(im.map) + (size_t)my * c.map_w + mx;
+      if (ALIGNED) {   // map_w is even and the map 8-byte aligned
+        *reinterpret_cast<uint2*>(mp) = make_uint2(px[0], px[1]);
+      } else {
+        mp[0] = px[0];
+        if (two) mp[1] = px[1];
+      }
+    } else {
+      // the two luminances, as gen_pair forms them behind the linear colours
+      const f2 sdr_nits = (splat(c.lum_r) * lin.r + splat(c.lum_g) * lin.g + splat(c.lum_b) * lin.b) * splat(203.0f);
+      const f2 hdr_nits = (splat(c.lum_r) * lin.hr + splat(c.lum_g) * lin.hg + splat(c.lum_b) * lin.hb) * splat(c.hdr_white_nits);
+      const uint8_t b0 = encode_gain_md(c, m, sdr_nits.x, hdr_nits.x), b1 = encode_gain_md(c, m, sdr_nits.y, hdr_nits.y);
+      uint8_t* mp = im.map + (size_t)my * c.map_w + mx;
+      if (ALIGNED) {   // map_w is even and the map 2-byte aligned
+        *reinterpret_cast<uint16_t*>(mp) = (uint16_t)((uint32_t)b0 | ((uint32_t)b1 << 8));
+      } else {
+        mp[0] = b0;
+        if (two) mp[1] = b1;
+      }
+    }
+  }
+}
+template <int TF, bool RGB>
+static hipError_t launch_generate_md_tf(const GenConsts& c, const GenMdConsts& m, const GenBatch& b, int n, bool aligned, hipStream_t s) {
+  const uint32_t total = ((c.map_w + 1u) >> 1) * c.map_h;
+  if (total == 0 || n == 0) return hipSuccess;
+  const bool small = generate_is_small(c, n);   // spans per block as launch_generate_t chooses them
+  const unsigned per = (unsigned)kGenBlock * (small ? 1u : (unsigned)kGenTiles);
+  const dim3 g((unsigned)n, (total + per - 1u) / per, 1), blk(kGenBlock, 1, 1);
+  if (small) {
+    if (aligned) hipLaunchKernelGGL((k_generate_md<TF, true, 1, RGB>), g, blk, 0, s, c, m, b);
+    else hipLaunchKernelGGL((k_generate_md<TF, false, 1, RGB>), g, blk, 0, s, c, m, b);
+  } else {
+    if (aligned) hipLaunchKernelGGL((k_generate_md<TF, true, kGenTiles, RGB>), g, blk, 0, s, c, m, b);
+    else hipLaunchKernelGGL((k_generate_md<TF, false, kGenTiles, RGB>), g, blk, 0, s, c, m, b);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_generate_md(const GenConsts& c, const GenMdConsts& m, const GenBatch& b, int n, int hdr_tf, bool aligned, bool rgb,
+                              hipStream_t s) {
+  switch (hdr_tf) {
+    case 0: return rgb ? launch_generate_md_tf<0, true>(c, m, b, n, aligned, s) : launch_generate_md_tf<0, false>(c, m, b, n, aligned, s);
+    case 1: return rgb ? launch_generate_md_tf<1, true>(c, m, b, n, aligned, s) : launch_generate_md_tf<1, false>(c, m, b, n, aligned, s);
+    case 2: return rgb ? launch_generate_md_tf<2, true>(c, m, b, n, aligned, s) : launch_generate_md_tf<2, false>(c, m, b, n, aligned, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 // The range rule (include/uhdr_hip.h, uhdr_hip_adaptive_boost_range: the same f32 operations) and, from the range, what
 // generate_consts / encode_constants derive on the host for a fixed one: the two logarithms as (float)log2((double)boost), the
 // scale of encode_gain_guarded's in-range path and the bytes encodeGain yields for a gain on either clamp.  One block: image i is
@@ -2014,6 +2109,71 @@ hipError_t launch_apply_rgb(const AppConsts& c, const AppBatch& b, int n, int fm
     case 2: return launch_apply_rgb_t<2>(c, b, n, exact, s);
     case 3: return launch_apply_rgb_t<3>(c, b, n, exact, s);
     case 4: return launch_apply_rgb_t<4>(c, b, n, exact, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// ---- general gain-map metadata: gamma, offsets, HDR capacity -----------------------------------------------
+// The per-pixel kernels' loop, loads and sampleMap (px_inputs / px_taps; the RGBA map as k_apply_px_rgb reads it), then
+//   g' = g^(1/gamma)                                           (GAMMA only: one v_log_f32 / v_exp_f32 pair per gain; 0 stays 0)
+//   out = max(0, (e + offsetSdr) * 2^(A g' + B) - offsetHdr / d)
+// with e the FAST sRGB EOTF's value and A, B, offsetHdr / d the host's (AppMdConsts).  One f32 arithmetic: there is no reference
+// path for such metadata that an EXACT form could reproduce.
+template <bool GAMMA>
+__device__ __forceinline__ float md_factor(const AppMdConsts& m, float g) {
+  if (GAMMA) g = __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(g) * m.inv_gamma);   // log2(0) = -inf, 2^-inf = 0
+  return __builtin_amdgcn_exp2f(__builtin_fmaf(g, m.A, m.B));   // (one rounding of an exponent that reaches log2 max)
+}
+__device__ __forceinline__ float md_channel(const AppMdConsts& m, float e, float factor) {
+  return fmaxf(__builtin_fmaf(srgb_inv_oetf_fast(e) + m.off_sdr, factor, -m.off_hdr_d), 0.0f);
+}
+template <int FMT, bool RGB, bool GAMMA>
+__global__ void __launch_bounds__(256) k_apply_px_md(const AppConsts c, const AppMdConsts m, const AppBatch b) {
+  const AppImage& im = b.img[blockIdx.z];
+  const size_t total = (size_t)c.width * c.height;
+  const uint32_t x = blockIdx.x * 256u + threadIdx.x;
+  if (x >= c.width) return;
+  for (uint32_t y = blockIdx.y; y < c.height; y += gridDim.y) {
+    float yf, u, v, f[3];
+    if (RGB) {
+      const uint32_t* map = reinterpret_cast<const uint32_t*>(im.map);
+      yf = (float)im.y[(size_t)y * im.y_stride + x] * k255;
+      const size_t ci = (size_t)(y >> im.csy) * im.c_stride + (x >> im.csx);
+      u = (float)((int)im.u[ci] - 128) * k255; v = (float)((int)im.v[ci] - 128) * k255;
+      const PxTaps t = px_taps(c, x, y);
+      const uint32_t m1 = map[(size_t)t.yl * c.map_stride + t.xl], m2 = map[(size_t)t.yu * c.map_stride + t.xl];
+      const uint32_t m3 = map[(size_t)t.yl * c.map_stride + t.xu], m4 = map[(size_t)t.yu * c.map_stride + t.xu];
+      const float w0 = t.w[0], w1 = t.w[1], w2 = t.w[2], w3 = t.w[3];
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        f[k] = md_factor<GAMMA>(m, map_to_float_fast((m1 >> (8 * k)) & 0xffu) * w0 + map_to_float_fast((m2 >> (8 * k)) & 0xffu) * w1 +
+                                      map_to_float_fast((m3 >> (8 * k)) & 0xffu) * w2 + map_to_float_fast((m4 >> (8 * k)) & 0xffu) * w3);
+    } else {
+      const PxIn in = px_inputs(c, im, x, y);
+      yf = in.yf; u = in.u; v = in.v;
+      f[0] = f[1] = f[2] = md_factor<GAMMA>(m, in.gain);
+    }
+    F3 lin;
+    lin.x = md_channel(m, clamp01(yf + kP3Cr * v), f[0]);
+    lin.y = md_channel(m, clamp01(yf - kP3GCb * u - kP3GCr * v), f[1]);
+    lin.z = md_channel(m, clamp01(yf + kP3Cb * u), f[2]);
+    px_store<FMT>(im, (size_t)y * c.width + x, total, hdr_oetf<FMT, false>(lin));
+  }
+}
+template <int FMT, bool RGB>
+static hipError_t launch_apply_md_t(const AppConsts& c, const AppMdConsts& m, const AppBatch& b, int n, hipStream_t s) {
+  if (n == 0 || c.width == 0 || c.height == 0) return hipSuccess;
+  const dim3 grid = px_grid(c.width, c.height, n);
+  if (m.gamma_on != 0u) hipLaunchKernelGGL((k_apply_px_md<FMT, RGB, true>), grid, dim3(256), 0, s, c, m, b);
+  else hipLaunchKernelGGL((k_apply_px_md<FMT, RGB, false>), grid, dim3(256), 0, s, c, m, b);
+  return hipGetLastError();
+}
+hipError_t launch_apply_md(const AppConsts& c, const AppMdConsts& m, const AppBatch& b, int n, int fmt, bool rgb, hipStream_t s) {
+  switch (fmt) {
+    case 1: return rgb ? launch_apply_md_t<1, true>(c, m, b, n, s) : launch_apply_md_t<1, false>(c, m, b, n, s);
+    case 2: return rgb ? launch_apply_md_t<2, true>(c, m, b, n, s) : launch_apply_md_t<2, false>(c, m, b, n, s);
+    case 3: return rgb ? launch_apply_md_t<3, true>(c, m, b, n, s) : launch_apply_md_t<3, false>(c, m, b, n, s);
+    case 4: return rgb ? launch_apply_md_t<4, true>(c, m, b, n, s) : launch_apply_md_t<4, false>(c, m, b, n, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -179,6 +179,12 @@ status_t UltraHdrHip::convertYuv(uhdr_uncompressed_ptr image, ultrahdr_color_gam
                                                     UHDR_HIP_MEM_HOST, nullptr));
 }
 
+status_t gainMapWeight(ultrahdr_metadata_ptr metadata, float max_display_boost, float* weight, float* display_boost) {
+  if (metadata == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
+  const uhdr_hip_metadata_t md = to_c(*metadata);
+  return static_cast<status_t>(uhdr_hip_gainmap_weight(&md, max_display_boost, weight, display_boost));
+}
+
 // ---- editing effects (lib/src/editorhelper.cpp) ---------------------------------------------------------------
 namespace {
 template <typename Fn>
@@ -472,7 +478,12 @@ status_t JpegRHip::decodeJPEGR(uhdr_compressed_ptr jpegr_image_ptr, uhdr_uncompr
   const size_t bpp = output_format == ULTRAHDR_OUTPUT_HDR_LINEAR ? 8 : output_format == ULTRAHDR_OUTPUT_HDR_LINEAR_RGB_10BIT ? 6 : 4;
   const bool want_md = metadata != nullptr || output_format != ULTRAHDR_OUTPUT_SDR;   // jpegr.cpp:754
   const int flags = mDecodeAnySampling ? UHDR_HIP_DECODE_ANY_SAMPLING : 0;
-  if (mMultiChannelGainMap) {   // a three-component gain map is applied per channel; every other file as below
+  if (mAnyGainMapMetadata) {   // any valid metadata, one- and three-component maps
+    void* out = dest->data;
+    const size_t cap = a.width * a.height * bpp;
+    rc = uhdr_hip_jpegr_decode_md_batch(1, &file, &n, (int)output_format, max_display_boost, &out, &cap, &d, want_md ? &md : nullptr, nullptr,
+                                        mApplyMode, UHDR_HIP_MEM_HOST, nullptr, flags);
+  } else if (mMultiChannelGainMap) {   // a three-component gain map is applied per channel; every other file as below
     void* out = dest->data;
     const size_t cap = a.width * a.height * bpp;
     rc = uhdr_hip_jpegr_decode_rgbmap_batch(1, &file, &n, (int)output_format, max_display_boost, &out, &cap, &d, want_md ? &md : nullptr, nullptr,

@@ -1,0 +1,268 @@
+"""CPU tests of gain maps with gamma, offsets and an HDR capacity range: the host-only weight function, the
+status order of the three new calls, the model of tests/gainmap_md_cases.py against the reference where the reference has an answer
+(degenerate metadata), and the conditions the inputs of tests/test_gpu_gainmap_md.py have to meet."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import adaptive_cases as A
+from tests import gainmap_md_cases as M
+
+NAN, INF = float("nan"), float("inf")
+
+
+@pytest.fixture(scope="module")
+def api():
+    from libultrahdr_dev_amd import api as a
+    a.load()
+    return a
+
+
+# ---- uhdr_hip_gainmap_weight ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(M.CASES))
+def test_weight_against_the_model(api, name):
+    seen = set()
+    for boost in M.BOOSTS[name]:
+        w, d = api.gainmap_weight(M.api_metadata(api, M.CASES[name]), boost)
+        mw, md = M.weight(M.CASES[name], boost)
+        assert w == np.float32(mw) and d == np.float32(md), (name, boost, w, d, mw, md)
+        seen.add("0" if mw == 0 else "1" if mw == 1 else "in")
+        if md < float(np.float32(boost)):
+            seen.add("capped")
+    assert {"0", "1", "capped"} <= seen and ("in" in seen or name == "flatcap")
+
+
+def test_weight_covers_an_inside_value_and_matches_the_formula(api):
+    w, d = api.gainmap_weight(M.api_metadata(api, M.CASES["black"]), 3.0)
+    assert 0.0 < w < 1.0 and abs(w - (np.log2(3.0) - np.log2(1.5)) / (np.log2(6.0) - np.log2(1.5))) < 1e-6 and d == 3.0
+    # the degenerate metadata has a weight too, although the apply calls do not use it (they keep the reference's exponent scaling)
+    w, d = api.gainmap_weight(M.api_metadata(api, M.DEGENERATE), M.FLT_MAX)
+    assert (w, d) == (1.0, float(np.float32(4.926)))
+
+
+BAD_FIELDS = [
+    # (index into the case tuple, value)
+    (0, 0.0), (0, -1.0), (0, NAN), (0, INF),          # gamma
+    (1, -1 / 64), (1, NAN), (2, -1 / 64), (2, INF),   # offsets
+    (3, 0.0), (3, -1.0), (3, NAN), (4, 0.5), (4, INF), (4, NAN),   # min <= 0, max < min, non-finite
+    (5, 0.0), (5, NAN), (6, 0.5), (6, INF),           # Hmin <= 0, Hmax < Hmin, non-finite
+]
+
+
+def _bad_metadata(api):
+    out = [M.api_metadata(api, M.CASES["default"], version=b"1.1"), M.api_metadata(api, M.CASES["default"], version=b"")]
+    for idx, val in BAD_FIELDS:
+        c = list(M.CASES["default"])
+        c[idx] = val
+        out.append(M.api_metadata(api, tuple(c)))
+    return out
+
+
+def test_weight_error_returns(api):
+    lib = api.load()
+    good = M.api_metadata(api, M.CASES["default"])
+    w, d = C.c_float(7.0), C.c_float(7.0)
+    assert lib.uhdr_hip_gainmap_weight(None, 2.0, C.byref(w), C.byref(d)) == api.ERROR_BAD_PTR
+    assert lib.uhdr_hip_gainmap_weight(C.byref(good), 2.0, None, C.byref(d)) == api.ERROR_BAD_PTR
+    assert lib.uhdr_hip_gainmap_weight(C.byref(good), 2.0, C.byref(w), None) == api.ERROR_BAD_PTR
+    for md in _bad_metadata(api):
+        assert lib.uhdr_hip_gainmap_weight(C.byref(md), 2.0, C.byref(w), C.byref(d)) == api.ERROR_BAD_METADATA
+        assert lib.uhdr_hip_gainmap_weight(C.byref(md), 0.5, C.byref(w), C.byref(d)) == api.ERROR_BAD_METADATA   # metadata first
+    for boost in (0.5, 0.999, NAN, -INF):
+        assert lib.uhdr_hip_gainmap_weight(C.byref(good), boost, C.byref(w), C.byref(d)) == api.ERROR_INVALID_DISPLAY_BOOST
+    assert (w.value, d.value) == (7.0, 7.0)   # a refused call writes nothing
+    assert lib.uhdr_hip_gainmap_weight(C.byref(good), INF, C.byref(w), C.byref(d)) == 0 and w.value == 1.0
+
+
+# ---- status order of the three calls, without a device -------------------------------------------------------------------------------
+def _images(api, w=16, h=8, mw=4, mh=2):
+    yuv = np.zeros(w * h * 3 // 2, np.uint8)
+    p010 = np.zeros(w * h * 3 // 2, np.uint16)
+    gmap = np.full(mw * mh * 4, 0x77, np.uint8)
+    out = np.full(w * h * 2, 0x55555555, np.uint32)
+    keep = (yuv, p010, gmap, out)
+    return (api.yuv420_image(yuv.ctypes.data, w, h, api.CG_BT709), api.p010_image(p010.ctypes.data, w, h, api.CG_BT2100),
+            api.mono_image(gmap.ctypes.data, mw, mh), api.rgba_map_image(gmap.ctypes.data, mw, mh), api.out_image(out.ctypes.data), keep)
+
+
+def _no_device_status(api):
+    import torch
+    return 0 if torch.cuda.is_available() else api.ERROR_INSUFFICIENT_RESOURCE
+
+
+def test_apply_md_status_order(api):
+    lib = api.load()
+    yi, pi, mono, rgba, od, keep = _images(api)
+    good, degenerate = M.api_metadata(api, M.CASES["gamma22"]), M.api_metadata(api, M.DEGENERATE)
+    call = lambda y, m, md, boost=4.0, fmt=api.OUTPUT_HDR_PQ, mode=api.APPLY_FAST, dest=od, n=1: lib.uhdr_hip_apply_gainmap_md_batch(
+        n, C.byref(y) if y is not None else None, C.byref(m) if m is not None else None, C.byref(md) if md is not None else None, fmt, boost,
+        C.byref(dest) if dest is not None else None, mode, None)
+    # pointers first
+    assert call(None, mono, good) == api.ERROR_BAD_PTR and call(yi, None, good) == api.ERROR_BAD_PTR
+    assert call(yi, mono, None) == api.ERROR_BAD_PTR and call(yi, mono, good, dest=None) == api.ERROR_BAD_PTR
+    assert call(yi, mono, good, n=-1) == api.ERROR_BAD_PTR
+    nodata = api.mono_image(None, 4, 2)
+    bad = _bad_metadata(api)
+    assert call(yi, nodata, bad[0], boost=0.5) == api.ERROR_BAD_PTR
+    # then the metadata, in front of the display boost, in front of the scale factor
+    wrong_scale = api.mono_image(keep[2].ctypes.data, 3, 2)
+    for md in bad:
+        assert call(yi, wrong_scale, md, boost=0.5, mode=99) == api.ERROR_BAD_METADATA
+    for boost in (0.5, NAN):
+        assert call(yi, wrong_scale, good, boost=boost, mode=99) == api.ERROR_INVALID_DISPLAY_BOOST
+        assert call(yi, wrong_scale, degenerate, boost=boost, mode=99) == api.ERROR_INVALID_DISPLAY_BOOST
+    weird = api.Image(keep[2].ctypes.data, 4, 2, api.CG_UNSPECIFIED, None, 4, 0, api.PIX_FMT_YUV420)
+    assert call(yi, weird, good) == api.ERROR_UNSUPPORTED_FEATURE
+    for md in (good, degenerate):
+        assert call(yi, wrong_scale, md, mode=99) == api.ERROR_UNSUPPORTED_MAP_SCALE_FACTOR
+        assert call(yi, api.mono_image(keep[2].ctypes.data, 0, 2), md) == api.ERROR_UNSUPPORTED_MAP_SCALE_FACTOR
+        assert call(yi, api.mono_image(keep[2].ctypes.data, 8, 2), md) == api.ERROR_UNSUPPORTED_MAP_SCALE_FACTOR   # not the image's aspect
+        assert call(yi, mono, md, mode=99) == api.ERROR_UNSUPPORTED_FEATURE
+    # the RGBA form's own checks behind the scale factor
+    assert call(yi, api.rgba_map_image(keep[2].ctypes.data + 1, 4, 2), good) == api.ERROR_BAD_PTR
+    assert call(yi, api.rgba_map_image(keep[2].ctypes.data, 4, 2, 3), good) == api.ERROR_INVALID_STRIDE
+    # LUT and EXACT_UNFILTERED: refused for general metadata, forwarded for degenerate metadata (one plane)
+    for mode in (api.APPLY_LUT, api.APPLY_EXACT_UNFILTERED):
+        assert call(yi, mono, good, mode=mode) == api.ERROR_UNSUPPORTED_FEATURE
+        assert call(yi, rgba, good, mode=mode) == api.ERROR_UNSUPPORTED_FEATURE
+        assert call(yi, rgba, degenerate, mode=mode) == api.ERROR_UNSUPPORTED_FEATURE   # uhdr_hip_apply_gainmap_rgb_batch's answer
+    if _no_device_status(api):   # no device: every valid call is refused there, and nothing was written
+        for m in (mono, rgba):
+            for md in (good, degenerate):
+                assert call(yi, m, md) == api.ERROR_INSUFFICIENT_RESOURCE
+        assert call(yi, mono, degenerate, mode=api.APPLY_LUT) == api.ERROR_INSUFFICIENT_RESOURCE
+        assert (keep[3] == 0x55555555).all()
+    assert call(None, None, good, n=0, dest=None) in (0, api.ERROR_INSUFFICIENT_RESOURCE)
+
+
+def test_generate_md_status_order(api):
+    lib = api.load()
+    yi, pi, mono, rgba, od, keep = _images(api)
+    good = M.api_metadata(api, M.CASES["gamma22"])
+    mapdest = api.out_image(keep[2].ctypes.data)
+    call = lambda y, p, md, tf=api.TF_HLG, dest=mapdest, rgb=0, n=1: lib.uhdr_hip_generate_gainmap_md_batch(
+        n, C.byref(y) if y is not None else None, C.byref(p) if p is not None else None, tf, C.byref(md) if md is not None else None,
+        C.byref(dest) if dest is not None else None, 0, rgb, None)
+    assert call(None, pi, good) == api.ERROR_BAD_PTR and call(yi, None, good) == api.ERROR_BAD_PTR and call(yi, pi, None) == api.ERROR_BAD_PTR
+    assert call(yi, pi, good, dest=None) == api.ERROR_BAD_PTR and call(yi, pi, good, dest=api.out_image(None)) == api.ERROR_BAD_PTR
+    assert call(yi, pi, good, dest=api.out_image(keep[2].ctypes.data + 2), rgb=1) == api.ERROR_BAD_PTR   # an RGBA map: 4-byte aligned
+    small = api.p010_image(keep[1].ctypes.data, 8, 8, api.CG_BT2100)
+    for md in _bad_metadata(api):
+        assert call(yi, small, md, tf=77) == api.ERROR_BAD_METADATA          # in front of every check of the images
+    assert call(yi, small, good, tf=77) == api.ERROR_RESOLUTION_MISMATCH
+    unspec = api.yuv420_image(keep[0].ctypes.data, 16, 8, api.CG_UNSPECIFIED)
+    assert call(unspec, pi, good, tf=77) == api.ERROR_INVALID_COLORGAMUT
+    assert call(yi, pi, good, tf=77) == api.ERROR_INVALID_TRANS_FUNC
+    if _no_device_status(api):
+        for rgb in (0, 1):
+            assert call(yi, pi, good, rgb=rgb) == api.ERROR_INSUFFICIENT_RESOURCE
+        assert (keep[2] == 0x77).all()
+    # metadata_in is read only
+    assert M.fields(M.CASES["gamma22"]) == (np.float32(good.gamma), np.float32(good.offsetSdr), np.float32(good.offsetHdr), np.float32(good.minContentBoost),
+                                            np.float32(good.maxContentBoost), np.float32(good.hdrCapacityMin), np.float32(good.hdrCapacityMax))
+
+
+def test_decode_md_status_order(api):
+    lib = api.load()
+    junk = np.zeros(64, np.uint8)
+    ptrs, sizes = (C.c_void_p * 1)(junk.ctypes.data), (C.c_size_t * 1)(junk.size)
+    dests, mds, stat = (api.Image * 1)(), (api.Metadata * 1)(), (C.c_int * 1)(7)
+    call = lambda boost=4.0, fmt=api.OUTPUT_HDR_HLG, flags=0, files=ptrs, d=dests: lib.uhdr_hip_jpegr_decode_md_batch(
+        1, files, sizes, fmt, boost, None, None, d, mds, stat, api.APPLY_FAST, api.MEM_HOST, None, flags)
+    assert call(flags=2) == api.ERROR_UNSUPPORTED_FEATURE            # an unknown flag bit, as uhdr_hip_jpegr_decode_rgbmap_batch
+    assert call(files=None) == api.ERROR_BAD_PTR and call(d=None) == api.ERROR_BAD_PTR
+    assert call(boost=0.5) == api.ERROR_INVALID_DISPLAY_BOOST and call(boost=NAN) == api.ERROR_INVALID_DISPLAY_BOOST
+    assert call(fmt=9) == api.ERROR_INVALID_OUTPUT_FORMAT
+    assert call() == api.ERROR_NO_IMAGES_FOUND and stat[0] == api.ERROR_NO_IMAGES_FOUND   # per file, without a device
+
+
+# ---- the model against the reference, where the reference has an answer --------------------------------------------------------------
+@pytest.fixture(scope="module")
+def small_inputs():
+    """a plain 40 x 24 LCG frame (clamped channels included) with a 10 x 6 map: the model's per-pixel inputs"""
+    w, h = 40, 24
+    Y, U, V = M.lcg_yuv(w, h, 9)
+    gmap = M.lcg_bytes((h // 4, w // 4), 5)
+    return w, h, (Y, U, V), gmap, M.linear_sdr(Y, U, V), M.sampled_gain(gmap, w, h)
+
+
+@pytest.mark.parametrize("fmt", [M.FMT_F16, M.FMT_PQ, M.FMT_HLG, M.FMT_RGB10])
+@pytest.mark.parametrize("boost", [4.926, 100.0, M.FLT_MAX])
+def test_model_equals_the_reference_at_degenerate_metadata(orc, small_inputs, fmt, boost):
+    w, h, (Y, U, V), gmap, e, g = small_inputs
+    yuv = np.concatenate([Y.reshape(-1), U.reshape(-1), V.reshape(-1)])
+    st, ref, _ = orc.apply("orc_", orc.yuv420_image(yuv, w, h, orc.CG_BT709), gmap, M.orc_metadata(M.DEGENERATE), fmt, boost)
+    assert st == 0
+    v = M.pre_truncation(e, g, M.DEGENERATE, boost, fmt)
+    codes = M.codes_of(ref, fmt, w, h)
+    if fmt == M.FMT_F16:
+        assert M.half_ulp_distance(codes, v).max() <= 1.0
+        return
+    d = M.code_distance(codes, v)
+    assert d.max() <= 1
+    far = ~M.near_integer(v)
+    assert (d[far] == 0).all() and far.mean() > 0.5
+
+
+def test_generate_model_equals_the_reference_at_gamma_one_and_no_offsets(orc):
+    for tf, seed in ((M.TF_HLG, 11), (M.TF_PQ, 12), (M.TF_LINEAR, 13)):
+        p010, yuv = orc.lcg_frame(72, 40, seed)
+        yi, pi = orc.yuv420_image(yuv, 72, 40, orc.CG_BT709), orc.p010_image(p010, 72, 40, orc.CG_BT2100)
+        st, want, omd = orc.generate("orc_", yi, pi, tf)
+        assert st == 0
+        case = (1.0, 0.0, 0.0, omd.minContentBoost, omd.maxContentBoost, omd.hdrCapacityMin, omd.hdrCapacityMax)
+        ys, yh = A.luminances(orc, yi, pi, tf)
+        got, _ = M.encode(ys, yh, case)
+        assert np.array_equal(got, want), (tf, int((got != want).sum()))
+
+
+# ---- input conditions: asserted here so that no GPU test can hide a failure behind them ----------------------------------------------
+@pytest.mark.parametrize("name", sorted(M.CASES))
+def test_apply_inputs_are_rarely_near_a_code_boundary(name):
+    s = M.share_inputs()
+    assert s["gmap"].min() == 0 and s["gmap"].max() == 255
+    for boost in M.BOOSTS[name]:
+        for fmt in (M.FMT_PQ, M.FMT_HLG, M.FMT_RGB10):
+            for g in (s["g1"], s["g3"]):
+                share = float(M.near_integer(M.pre_truncation(s["e"], g, M.CASES[name], boost, fmt)).mean())
+                print("%s D=%g fmt %d planes %d: %.4f of the channels within 1/256 of an integer" % (name, boost, fmt, g.shape[2], share))
+                assert share <= 0.02, (name, boost, fmt, share)
+
+
+GEN_SHAPES = [(36, 28), (264, 200)]
+
+
+@pytest.mark.parametrize("name", sorted(M.CASES))
+def test_generate_inputs_are_rarely_near_a_byte_boundary(orc, name):
+    for (w, h) in GEN_SHAPES:
+        for tf in (M.TF_HLG, M.TF_PQ, M.TF_LINEAR):
+            s = M.generate_inputs(w, h, tf)
+            for a, b in ((s["ys"], s["yh"]), (s["sdr"], s["hdr"])):
+                _, v = M.encode(a, b, M.CASES[name])
+                near = int(M.in_doubt(v).sum())
+                assert near <= v.size / 1e5, (name, w, h, tf, near, v.size)
+                assert ((v > 0) & (v < 255)).mean() > 0.05   # (enough gains between the clamps for the bytes to mean something)
+
+
+def test_generate_inputs_of_the_large_batch_shape():
+    """the 712x704 pair tests/test_gpu_gainmap_md.py runs 64 copies of (blocks of several spans), in the case it uses"""
+    s = M.generate_inputs(712, 704, M.TF_HLG)
+    for a, b in ((s["ys"], s["yh"]), (s["sdr"], s["hdr"])):
+        _, v = M.encode(a, b, M.CASES["gamma22"])
+        assert int(M.in_doubt(v).sum()) <= v.size / 1e5 and ((v > 0) & (v < 255)).mean() > 0.05
+
+
+# ---- the container carries every case --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(M.CASES))
+def test_metadata_survives_the_container(orc, api, name):
+    """the XMP writer (API-4 here: host code, no device; API-x shares it) and uhdr_hip_jpegr_metadata: every field back, up to the
+    XMP's decimal printing (six significant digits, the boosts as log2)"""
+    md = M.api_metadata(api, M.CASES[name])
+    got = A.xmp_round_trip(orc, api, md)
+    want = M.fields(M.CASES[name])
+    back = (got.gamma, got.offsetSdr, got.offsetHdr, got.minContentBoost, got.maxContentBoost, got.hdrCapacityMin, got.hdrCapacityMax)
+    assert got.version == b"1.0"
+    for a, b in zip(back, want):
+        assert abs(a - float(b)) <= 2e-5 * max(abs(float(b)), 1.0), (name, back, want)
+    assert M.is_degenerate(M.DEGENERATE) and not M.is_degenerate(back)
