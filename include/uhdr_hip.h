@@ -84,6 +84,17 @@ extern "C" {
  * pixel; data points at pixel (0, 0) and is 4-byte aligned, luma_stride is in PIXELS (0 = width), chroma_data = NULL.  Calls that
  * write a map set A = 0xFF, calls that read one ignore A.  It is the layout UHDR_HIP_DECODE_TO_RGBA produces. */
 #define UHDR_HIP_PIX_FMT_RGBA8888 6
+/* Packed RGBA images, read by the *_packed_* calls and uhdr_hip_jpeg_encode_rgba420_batch (no counterpart in the reference; current
+ * libultrahdr takes the same three layouts as raw encode inputs).  They are the layouts the apply / decode calls WRITE.
+ *   RGBA8888 (6, above)  also an SDR image: sRGB transfer, full range, R, G, B, A bytes in that order, alpha ignored.
+ *   RGBA1010102          an HDR image, one dword per pixel, R | G << 10 | B << 20 | A << 30, full range, HLG or PQ: what
+ *                        UHDR_HIP_OUTPUT_HDR_HLG / UHDR_HIP_OUTPUT_HDR_PQ write.  Alpha ignored.
+ *   RGBA_F16             an HDR image, four halves R, G, B, A per pixel, linear light, 1.0 = 1000 nits (the reference's kHlgMaxNits,
+ *                        what its ULTRAHDR_TF_LINEAR means, ultrahdr.cpp:223-228): what UHDR_HIP_OUTPUT_HDR_LINEAR writes.  Alpha ignored.
+ * For all three, as for RGBA maps: data points at pixel (0, 0), luma_stride is in PIXELS (0 = width), chroma_data is not read; data
+ * is 4-byte aligned, 8-byte for RGBA_F16. */
+#define UHDR_HIP_PIX_FMT_RGBA1010102 7
+#define UHDR_HIP_PIX_FMT_RGBA_F16 8
 /* status_t, ultrahdr.h:91-120 */
 #define UHDR_HIP_NO_ERROR 0
 #define UHDR_HIP_UNKNOWN_ERROR (-1)
@@ -728,6 +739,75 @@ int uhdr_hip_generate_gainmap_md_batch(int n, const uhdr_hip_image_t* yuv420_ima
 int uhdr_hip_jpegr_decode_md_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
                                    void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests,
                                    uhdr_hip_metadata_t* metadata, int* status, int apply_mode, int mem_space, void* stream, int flags);
+
+/* ---- packed RGBA inputs (no reference counterpart; current libultrahdr takes the same raw inputs) ------
+ * Every encode-side call above takes a P010 HDR frame and planar 8-bit YUV 4:2:0.  The calls of this section take what the apply and
+ * decode calls write and what a renderer or a compositor holds: an UHDR_HIP_PIX_FMT_RGBA8888 SDR image and an
+ * UHDR_HIP_PIX_FMT_RGBA1010102 (hdr_tf HLG or PQ) or UHDR_HIP_PIX_FMT_RGBA_F16 (hdr_tf LINEAR) HDR image, layouts as at the
+ * pixel-format constants.  No narrow-range quantisation and no chroma subsampling enter the map.
+ *
+ * uhdr_hip_generate_gainmap_packed_batch.  Device memory, asynchronous on `stream`.  The arithmetic, every step f32 unless said:
+ *   pixel values   RGBA8888: (float)code * (1 / 255.0f) per channel; RGBA1010102: (float)code10 * (1 / 1023.0f); RGBA_F16: the exact
+ *                  f32 of each half (subnormal halves included).
+ *   sampling       the map is (width / 4) x (height / 4); a map pixel's sample is the reference's samplePixels (gainmapmath.cpp:
+ *                  605-615) per channel over its 4 x 4 block, for both images: e = 0; for dy, for dx: e += pixel; e / 16.0f -- the
+ *                  product and the running sum are separate roundings.  Columns and rows past 4 * (width / 4), 4 * (height / 4) are
+ *                  not read.
+ *   the rest       generateGainMap's (ultrahdr.cpp:317-334) without its two yuvToRgb steps and without their clamp: srgbInvOetf on
+ *                  the SDR colour; hdrInvOetf(hdr_tf) on the HDR colour, then the conversion into the SDR image's gamut; the SDR
+ *                  gamut's luminance of both, times 203.0f and times hdr_white_nits (PQ 10000, otherwise 1000); encodeGain.
+ *   rgb != 0       the split of uhdr_hip_generate_gainmap_rgb_batch: encodeGain per channel on sdr.c * 203.0f and
+ *                  hdr.c * hdr_white_nits, RGBA8888 dests (4-byte aligned), A = 0xFF.
+ * The exact path throughout, as in the *_rgb_* and *_md_* calls.  metadata_in == NULL selects the reference's constants for hdr_tf
+ * (what uhdr_hip_generate_gainmap_batch returns); otherwise the rule, the validation and the gamma handling are those of
+ * uhdr_hip_generate_gainmap_md_batch.  metadata_out (optional) receives the metadata that was used.  A map pixel that reads a
+ * non-finite half is unspecified; nothing outside the dests is written.  dests[i].data needs (width / 4) * (height / 4) bytes, four
+ * times that with rgb != 0; dests[i] comes back described as in uhdr_hip_generate_gainmap_md_batch.  All HDR images of a call have
+ * one format.  Checks, in this order:
+ *   BAD_PTR              n < 0, or a NULL sdr_images / hdr_images / dests where n > 0
+ *   UNSUPPORTED_FEATURE  (every image, before anything else of any image) an SDR pixelFormat other than RGBA8888; an HDR pixelFormat
+ *                        other than RGBA1010102 / RGBA_F16; an HDR pixelFormat that differs from hdr_images[0]'s
+ *   BAD_PTR              (every image) a NULL data or dests[i].data; SDR or RGBA1010102 data not 4-byte aligned, RGBA_F16 data not
+ *                        8-byte aligned; with rgb != 0 a dest not 4-byte aligned
+ *   BAD_METADATA         metadata_in != NULL: uhdr_hip_generate_gainmap_md_batch's validation
+ *   then per image       INVALID_STRIDE (a luma_stride below the width, or above 2^32 - 1); RESOLUTION_MISMATCH; INVALID_COLORGAMUT
+ *                        (UNSPECIFIED); INVALID_TRANS_FUNC (RGBA_F16 with anything but LINEAR, RGBA1010102 with anything but HLG /
+ *                        PQ); INVALID_COLORGAMUT (any other value outside BT709 / P3 / BT2100)
+ *   INVALID_TRANS_FUNC   n == 0 and hdr_tf none of LINEAR / HLG / PQ */
+int uhdr_hip_generate_gainmap_packed_batch(int n, const uhdr_hip_image_t* sdr_images, const uhdr_hip_image_t* hdr_images, int hdr_tf,
+                                           const uhdr_hip_metadata_t* metadata_in, uhdr_hip_metadata_t* metadata_out,
+                                           uhdr_hip_image_t* dests, int rgb, void* stream);
+/* n UHDR_HIP_PIX_FMT_RGBA8888 images -> the baseline 4:2:0 files libjpeg writes for in_color_space = JCS_RGB, luma sampling 2x2 and
+ * chroma 1x1, jpeg_set_quality(quality, TRUE), JDCT_ISLOW and default Huffman tables: jccolor.c's fixed-point RGB -> YCbCr at full
+ * resolution, then jcsample.c's h2v2_downsample, (a + b + c + d + bias) >> 2 with the bias alternating 1, 2 along a row.  Edges as
+ * libjpeg makes them: the last column of the full-resolution rows is repeated out to the padded width and the last row to an even
+ * count before the downsampling, the last downsampled row is repeated after it (luma: last column, then last row).  Byte for byte
+ * what libjpeg-turbo writes (Pillow: quality=q, subsampling=2).  Alpha is ignored.  Signature and conventions of
+ * uhdr_hip_jpeg_encode_batch -- memory spaces, ICC per file (an APP2 segment where uhdr_hip_jpeg_encode puts it), size probe with
+ * ERROR_INSUFFICIENT_RESOURCE and the exact size, per-file statuses --; any size from 1 x 1 to 65500 x 65500, odd ones included.  One
+ * conversion / downsample launch covers every image of a round (at most 64 images), the FDCT / Huffman / stuffing chain is
+ * uhdr_hip_jpeg_encode_batch's.  Call-level: BAD_PTR for n < 0, a NULL array where n > 0 or icc != NULL with icc_size == NULL;
+ * INVALID_QUALITY_FACTOR for a quality outside 0..100.  Per file, as in uhdr_hip_jpeg_encode_rgb_batch: BAD_PTR (data NULL or, in device
+ * memory, not 4-byte aligned; out[i] NULL with a capacity), UNSUPPORTED_FEATURE (another pixelFormat), RESOLUTION_MISMATCH (size out
+ * of range, or a luma_stride below the width). */
+int uhdr_hip_jpeg_encode_rgba420_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
+                                       const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                       int mem_space, void* stream);
+/* JPEG/R files from packed RGBA pairs: uhdr_hip_jpegr_encode_rgbmap_batch's signature and conventions with the packed pair in place of
+ * the planar one and rgb_map choosing the map's form.  Per file: the gain map is uhdr_hip_generate_gainmap_packed_batch's with
+ * metadata_in == NULL (rgb = rgb_map), compressed at quality 85 as uhdr_hip_jpeg_encode compresses a single plane, or as
+ * uhdr_hip_jpeg_encode_rgb_batch does when rgb_map != 0; the primary image is uhdr_hip_jpeg_encode_rgba420_batch's at `quality` with the
+ * ICC profile uhdr_hip_icc_profile(UHDR_HIP_TF_SRGB, the SDR gamut); the container is uhdr_hip_jpegr_append_gainmap(primary, map,
+ * exif, NULL, 0, metadata), as API-1 calls it (jpegr.cpp:365-381).  Call-level: BAD_PTR (n < 0, a NULL array where n > 0, exif without
+ * exif_size), INVALID_QUALITY_FACTOR.  Per file, API-1's checks where they apply, on the HDR image first: BAD_PTR (NULL data),
+ * UNSUPPORTED_WIDTH_HEIGHT (odd, below 8 or above 8192), INVALID_COLORGAMUT, INVALID_STRIDE, BAD_PTR (out[i] NULL), INVALID_TRANS_FUNC
+ * (none of LINEAR / HLG / PQ); then on the SDR image BAD_PTR, INVALID_STRIDE, RESOLUTION_MISMATCH, INVALID_COLORGAMUT; BAD_PTR for a
+ * NULL exif[i] with a size; then uhdr_hip_generate_gainmap_packed_batch's own (pixel formats, alignment in device memory, the transfer
+ * function against the HDR format -- every file by itself: hdr_tf is shared, so the files that pass have one HDR format).  The
+ * files' generate, conversion and all 2 n compressions share their launches, one synchronisation per round of up to 64 files. */
+int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf, int quality,
+                                       const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                       size_t* out_size, int* status, int rgb_map, int mem_space, void* stream);
 
 /* ---- content-adaptive gain maps (no reference counterpart) ---------------------------------
  * The reference encodes every map against minContentBoost = 1, maxContentBoost = hdr_white / 203 (ultrahdr.cpp:250-257): 255 codes

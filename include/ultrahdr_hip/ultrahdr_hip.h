@@ -126,6 +126,14 @@ class UltraHdrHip {
 status_t toneMapSdr(uhdr_uncompressed_ptr src, uhdr_uncompressed_ptr dest, ultrahdr_transfer_function hdr_tf, int tonemap_op,
                     float hdr_peak_nits = 0.0f, float* headroom = nullptr);
 
+// generateGainMap from a packed RGBA pair in DEVICE memory (uhdr_hip_generate_gainmap_packed_batch; no reference counterpart), on HIP
+// device 0: an ULTRAHDR_PIX_FMT_RGBA8888 SDR image and an ULTRAHDR_PIX_FMT_RGBA1010102 (HLG / PQ) or ULTRAHDR_PIX_FMT_RGBAF16 (linear)
+// HDR image, strides in pixels.  dest->data is the caller's device buffer -- (width / 4) * (height / 4) bytes, four times that
+// (4-byte aligned, RGBA) with multi_channel; the call only enqueues on `stream`.  *metadata (optional) receives the reference's
+// constants for hdr_tf, which the map is encoded against.
+status_t generateGainMapPacked(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompressed_ptr hdr_image_ptr, ultrahdr_transfer_function hdr_tf,
+                               ultrahdr_metadata_ptr metadata, uhdr_uncompressed_ptr dest, bool multi_channel = false, void* stream = nullptr);
+
 // The weight W of the gain-map exponent and the divisor d = min(max_display_boost, hdrCapacityMax) that a decode with
 // JpegRHip::setAnyGainMapMetadata forms for this metadata (uhdr_hip_gainmap_weight; host code, no device needed)
 status_t gainMapWeight(ultrahdr_metadata_ptr metadata, float max_display_boost, float* weight, float* display_boost);
@@ -229,6 +237,13 @@ class JpegRHip {
   // "API-x" (:263): SDR planes + ready gain map + metadata
   status_t encodeJPEGR(uhdr_uncompressed_ptr yuv420_image_ptr, uhdr_uncompressed_ptr gainmap_image_ptr, ultrahdr_metadata_ptr metadata,
                        uhdr_compressed_ptr dest, int quality, uhdr_exif_ptr exif);
+  // Packed RGBA inputs (include/uhdr_hip.h, "packed RGBA inputs"; no reference counterpart): an ULTRAHDR_PIX_FMT_RGBA1010102 (HLG / PQ)
+  // or ULTRAHDR_PIX_FMT_RGBAF16 (linear) HDR image and an ULTRAHDR_PIX_FMT_RGBA8888 SDR image, host memory, luma_stride in pixels
+  // (0 = width), full range.  The gain map comes from the packed pair itself, the primary image is the SDR image compressed as
+  // 4:2:0 from RGB, the container is API-1's (uhdr_hip_jpegr_encode_packed_batch).  Honours setMultiChannelGainMap; setContentBoost
+  // and setToneMap do not apply.
+  status_t encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_uncompressed_ptr sdr_image_ptr, ultrahdr_transfer_function hdr_tf,
+                             uhdr_compressed_ptr dest, int quality, uhdr_exif_ptr exif);
   // (:213) dest->data, exif->data and gainmap_image_ptr->data are caller-allocated, as in the reference
   status_t decodeJPEGR(uhdr_compressed_ptr jpegr_image_ptr, uhdr_uncompressed_ptr dest, float max_display_boost = 3.4028234663852886e38f,
                        uhdr_exif_ptr exif = nullptr, ultrahdr_output_format output_format = ULTRAHDR_OUTPUT_HDR_LINEAR,

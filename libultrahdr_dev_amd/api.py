@@ -15,7 +15,8 @@ TF_LINEAR, TF_HLG, TF_PQ, TF_SRGB = 0, 1, 2, 3
 OUTPUT_SDR, OUTPUT_HDR_LINEAR, OUTPUT_HDR_PQ, OUTPUT_HDR_HLG, OUTPUT_HDR_LINEAR_RGB_10BIT = 0, 1, 2, 3, 4
 PIX_FMT_P010, PIX_FMT_YUV420, PIX_FMT_MONOCHROME = 0, 1, 2
 PIX_FMT_YUV444, PIX_FMT_YUV422, PIX_FMT_YUV440 = 3, 4, 5   # what the DECODE_ANY_SAMPLING decodes return and apply reads
-PIX_FMT_RGBA8888 = 6   # a per-channel (RGB) gain map: R, G, B, A bytes per map pixel, luma_stride in pixels
+PIX_FMT_RGBA8888 = 6   # a per-channel (RGB) gain map: R, G, B, A bytes per map pixel, luma_stride in pixels; also a packed SDR image
+PIX_FMT_RGBA1010102, PIX_FMT_RGBA_F16 = 7, 8   # packed HDR images: R | G << 10 | B << 20 | A << 30 (HLG / PQ); four halves, linear light
 NO_ERROR, UNKNOWN_ERROR = 0, -1
 ERROR_BAD_PTR, ERROR_INVALID_COLORGAMUT, ERROR_INVALID_TRANS_FUNC = -10001, -10003, -10005
 ERROR_RESOLUTION_MISMATCH, ERROR_BAD_METADATA = -10006, -10010
@@ -99,6 +100,12 @@ SIGNATURES = {
     "uhdr_hip_generate_gainmap_md_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _MP, _IP, C.c_int, C.c_int, C.c_void_p]),
     "uhdr_hip_jpegr_decode_md_batch": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_float, C.POINTER(C.c_void_p),
                                                  C.POINTER(C.c_size_t), _IP, _MP, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_int]),
+    "uhdr_hip_generate_gainmap_packed_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _MP, _MP, _IP, C.c_int, C.c_void_p]),
+    "uhdr_hip_jpeg_encode_rgba420_batch": (C.c_int, [C.c_int, _IP, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                                     C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    "uhdr_hip_jpegr_encode_packed_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                     C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int,
+                                                     C.c_int, C.c_void_p]),
     "uhdr_hip_mem_pool_create": (C.c_int, [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_void_p)]),
     "uhdr_hip_mem_pool_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "uhdr_hip_mem_pool_free": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -301,6 +308,21 @@ def mono_image(ptr, w, h):
 def rgba_map_image(ptr, w, h, stride=None):
     """descriptor of a per-channel gain map: w x h RGBA pixels, rows `stride` pixels apart"""
     return Image(ptr, w, h, CG_UNSPECIFIED, None, w if stride is None else stride, 0, PIX_FMT_RGBA8888)
+
+
+def rgba8888_image(ptr, w, h, gamut, stride=None):
+    """descriptor of a packed SDR image: w x h R, G, B, A bytes (sRGB transfer, full range), rows `stride` pixels apart"""
+    return Image(ptr, w, h, gamut, None, w if stride is None else stride, 0, PIX_FMT_RGBA8888)
+
+
+def rgba1010102_image(ptr, w, h, gamut, stride=None):
+    """descriptor of a packed HLG / PQ image: one dword R | G << 10 | B << 20 | A << 30 per pixel, rows `stride` pixels apart"""
+    return Image(ptr, w, h, gamut, None, w if stride is None else stride, 0, PIX_FMT_RGBA1010102)
+
+
+def rgba_f16_image(ptr, w, h, gamut, stride=None):
+    """descriptor of a packed linear-light image: four halves R, G, B, A per pixel (1.0 = 1000 nits), rows `stride` pixels apart"""
+    return Image(ptr, w, h, gamut, None, w if stride is None else stride, 0, PIX_FMT_RGBA_F16)
 
 
 def out_image(ptr):

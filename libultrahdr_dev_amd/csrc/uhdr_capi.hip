@@ -1311,11 +1311,21 @@ jpeg::Plane encode_plane(const uint8_t* p, size_t pw, size_t ph, size_t stride, 
 jpeg::Geometry enc_geom(const uhdr_hip_image_t& img, bool rgb) {
   return rgb ? jpeg::kGeomRgb444 : img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME ? jpeg::kGeomGray : jpeg::kGeom420;
 }
-jpeg::Job encode_job(const uhdr_hip_image_t& img, int q, size_t pad_ls, size_t pad_cs, bool rgb = false) {
+// mcu_planes: the planes are jpeg::launch_rgba_to_ycc420's -- whole MCUs, padded by that kernel, Cb at chroma_data -- of an image of
+// any size, odd ones included
+jpeg::Job encode_job(const uhdr_hip_image_t& img, int q, size_t pad_ls, size_t pad_cs, bool rgb = false, bool mcu_planes = false) {
   const bool gray = img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
   const size_t w = img.width, h = img.height, aw = (w + 15) / 16 * 16, acw = (w / 2 + 7) / 8 * 8;
   jpeg::Job j;
   encode_job_tables(w, h, enc_geom(img, rgb), q, &j);
+  if (mcu_planes) {
+    const size_t mcw = (w + 15) / 16, mch = (h + 15) / 16;
+    const uint8_t* pu = static_cast<const uint8_t*>(img.chroma_data);
+    j.plane[0] = encode_plane(static_cast<const uint8_t*>(img.data), 16 * mcw, 16 * mch, 16 * mcw, false);
+    j.plane[1] = encode_plane(pu, 8 * mcw, 8 * mch, 8 * mcw, false);
+    j.plane[2] = encode_plane(pu + 64 * mcw * mch, 8 * mcw, 8 * mch, 8 * mcw, false);
+    return j;
+  }
   if (j.rgb) {   // RGBA pixels, 4-byte aligned, luma_stride in pixels; edges are replicated by the kernel, nothing is padded
     j.plane[0] = jpeg::Plane{static_cast<const uint8_t*>(img.data), (int)w, (int)h, (int)(img.luma_stride * 4), 0, 1};
     return j;
@@ -1412,6 +1422,7 @@ struct EncJpeg {
   uint8_t* dev_out = nullptr;
   size_t dev_cap = 0;
   bool rgb = false;                      // img is RGBA8888 (luma_stride in pixels), compressed as 4:4:4 (jpeg::kGeomRgb444)
+  bool mcu_planes = false;               // img's planes are jpeg::launch_rgba_to_ycc420's (encode_job)
 };
 
 // JpegEncoderHelper::compressImage (jpegencoderhelper.cpp:39-52) of k images in the leased context st: the headers are written into
@@ -1432,7 +1443,7 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
   std::vector<std::vector<uint8_t>> header((size_t)k);
   for (int i = 0; i < k; ++i) {
     const EncJpeg& e = im[i];
-    jobs[i] = encode_job(e.img, e.quality, e.pad_ls, e.pad_cs, e.rgb);
+    jobs[i] = encode_job(e.img, e.quality, e.pad_ls, e.pad_cs, e.rgb, e.mcu_planes);
     ws_off[i] = ws_total;
     ws_total += round_up(jpeg::workspace_bytes(jobs[i].nblk, &lay[i]), 256);
     jpeg::build_header((int)e.img.width, (int)e.img.height, enc_geom(e.img, e.rgb), e.quality, e.icc ? e.icc->data() : nullptr,
@@ -1479,6 +1490,7 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     CodecLease lease(root);
     EncJpeg one{e.img, e.quality, e.icc, e.pad_ls, e.pad_cs, (size_t)total};
     one.rgb = e.rgb;
+    one.mcu_planes = e.mcu_planes;
     if (lease.get() == nullptr || compress_to_host(lease.get(), s, 1, &one, false) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
     e.big.assign(one.bytes, one.bytes + one.n);
     e.bytes = e.big.data();
@@ -1758,6 +1770,142 @@ int uhdr_hip_jpeg_encode_rgb_batch(int n, const uhdr_hip_image_t* images, const 
             out_size[i] = im[k].n;
             if (im[k].n > out_capacity[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
             if (host_out) memcpy(out[i], im[k].bytes, im[k].n);
+            st_[i] = UHDR_HIP_NO_ERROR;
+          }
+        };
+        if (host_out) on_host_threads(m, deliver);
+        else deliver(0, m);
+        return (int)UHDR_HIP_NO_ERROR;
+      },
+      &done);
+  for (size_t k = done; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
+  return finish_statuses(st_, status);
+}
+
+}  // extern "C"
+
+namespace {
+// uhdr_hip_jpeg_encode_rgb_batch's per-file checks of an RGBA8888 image and its output
+int rgba_file_check(const uhdr_hip_image_t& im, bool host_in, const void* out, size_t out_capacity) {
+  if (im.data == nullptr || (!host_in && !al(im.data, 4)) || (out == nullptr && out_capacity != 0)) return UHDR_HIP_ERROR_BAD_PTR;
+  if (im.pixelFormat != UHDR_HIP_PIX_FMT_RGBA8888) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (im.width == 0 || im.height == 0 || im.width > 65500 || im.height > 65500 || (im.luma_stride != 0 && im.luma_stride < im.width) ||
+      im.luma_stride > (size_t)INT32_MAX / 4)   // (rows are addressed with an int byte pitch)
+    return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
+  return UHDR_HIP_NO_ERROR;
+}
+// The 4:2:0 encoder's planes of m RGBA8888 images in device memory (luma_stride set), slices of pool slot `slot`: one
+// jpeg::launch_rgba_to_ycc420 for all of them (m <= jpeg::kRgba420Chunk).  e[k * step].img / .mcu_planes describe image k's planes.
+int rgba420_planes(DeviceState* st, size_t slot, hipStream_t s, int m, const uhdr_hip_image_t* imgs, EncJpeg* e, int step) {
+  size_t total = 0;
+  for (int k = 0; k < m; ++k) total += round_up(jpeg::rgba420_plane_bytes(imgs[k].width, imgs[k].height), 256);
+  int rc;
+  if ((rc = pool_reserve(st, slot, total)) != 0) return rc;
+  jpeg::Rgba420Batch b;
+  size_t o = 0;
+  for (int k = 0; k < m; ++k) {
+    const uhdr_hip_image_t& im = imgs[k];
+    jpeg::Rgba420Image& d = b.img[k];
+    d.src = static_cast<const uint32_t*>(im.data);
+    d.w = (uint32_t)im.width; d.h = (uint32_t)im.height; d.stride = (uint32_t)im.luma_stride;
+    d.mcw = (uint32_t)((im.width + 15) / 16); d.mch = (uint32_t)((im.height + 15) / 16);
+    d.y = static_cast<uint8_t*>(st->pool[slot]) + o;
+    d.cb = d.y + 256 * (size_t)d.mcw * d.mch;
+    o += round_up(jpeg::rgba420_plane_bytes(im.width, im.height), 256);
+    uhdr_hip_image_t& p = e[(size_t)k * step].img;
+    memset(&p, 0, sizeof(p));
+    p.data = d.y; p.chroma_data = d.cb; p.width = im.width; p.height = im.height; p.colorGamut = im.colorGamut;
+    p.luma_stride = 16 * (size_t)d.mcw; p.chroma_stride = 8 * (size_t)d.mcw; p.pixelFormat = UHDR_HIP_PIX_FMT_YUV420;
+    e[(size_t)k * step].mcu_planes = true;
+    e[(size_t)k * step].pad_ls = p.luma_stride; e[(size_t)k * step].pad_cs = p.chroma_stride;
+  }
+  HIP_TRY(jpeg::launch_rgba_to_ycc420(b, m, s));
+  return UHDR_HIP_NO_ERROR;
+}
+}  // namespace
+
+extern "C" {
+
+// uhdr_hip_jpeg_encode_batch's conventions for RGBA8888 images compressed as 4:2:0: the planes libjpeg's colour conversion and
+// downsampler hand its FDCT come from one k_rgba_to_ycc420 launch per round, everything behind them is compress_to_host
+int uhdr_hip_jpeg_encode_rgba420_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                       void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (icc != nullptr && icc_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  for (int i = 0; i < n; ++i)
+    if (quality[i] < 0 || quality[i] > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
+  std::vector<int> live;
+  const bool host_in = mem_space == UHDR_HIP_MEM_HOST || mem_space == UHDR_HIP_MEM_HOST_TO_DEVICE;
+  const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE && mem_space != UHDR_HIP_MEM_HOST_TO_DEVICE;
+  for (int i = 0; i < n; ++i) {
+    st_[i] = rgba_file_check(images[i], host_in, out[i], out_capacity[i]);
+    if (st_[i] == UHDR_HIP_NO_ERROR) live.push_back(i);
+  }
+  if (live.empty()) return finish_statuses(st_, status);
+  auto stage_pitch = [](const uhdr_hip_image_t& im) { return round_up(im.width * 4, 64); };   // bytes
+  size_t done = 0;
+  const int rc = run_rounds(
+      live.size(), (size_t)jpeg::kRgba420Chunk, stream,
+      [&](size_t k) {
+        const uhdr_hip_image_t& im = images[live[k]];
+        jpeg::Job j;
+        encode_job_tables(im.width, im.height, jpeg::kGeom420, 75, &j);
+        jpeg::Layout l;
+        size_t b = jpeg::workspace_bytes(j.nblk, &l) + round_up(jpeg::rgba420_plane_bytes(im.width, im.height), 256);
+        if (host_in) b += round_up(stage_pitch(im) * im.height, 256);
+        if (host_out) b += im.width * im.height + 65536;
+        return b;
+      },
+      [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
+        const int* idx = &live[r0];
+        std::vector<EncJpeg> im((size_t)m);
+        std::vector<uhdr_hip_image_t> dev((size_t)m);
+        std::vector<std::vector<uint8_t>> iccs((size_t)m);
+        size_t stage_total = 0;
+        int rc;
+        if (host_in) {
+          for (int k = 0; k < m; ++k) stage_total += round_up(stage_pitch(images[idx[k]]) * images[idx[k]].height, 256);
+          if ((rc = pool_reserve(st, kEncYuv, stage_total)) != 0) return rc;
+        }
+        size_t o = 0;
+        for (int k = 0; k < m; ++k) {
+          uhdr_hip_image_t& d = dev[(size_t)k];
+          d = images[idx[k]];
+          if (d.luma_stride == 0) d.luma_stride = d.width;
+          if (host_in) {   // rows of 4 w bytes into the round's slice, at a 64-byte pitch
+            const size_t pitch = stage_pitch(d);
+            uint8_t* dst = static_cast<uint8_t*>(st->pool[kEncYuv]) + o;
+            if ((rc = h2d_plane(dst, pitch, d.data, d.luma_stride * 4, d.width * 4, d.height, 1, s)) != 0) return rc;
+            o += round_up(pitch * d.height, 256);
+            d.data = dst; d.luma_stride = pitch / 4;
+          }
+        }
+        if ((rc = rgba420_planes(st, kEncSdr, s, m, dev.data(), im.data(), 1)) != 0) return rc;
+        for (int k = 0; k < m; ++k) {
+          const int i = idx[k];
+          const void* ip = icc ? icc[i] : nullptr;
+          const size_t in = icc ? icc_size[i] : 0;
+          if (ip != nullptr && in > 0) iccs[(size_t)k].assign(static_cast<const uint8_t*>(ip), static_cast<const uint8_t*>(ip) + in);
+          EncJpeg& e = im[(size_t)k];
+          e.quality = quality[i];
+          e.icc = iccs[(size_t)k].empty() ? nullptr : &iccs[(size_t)k];
+          if (host_out) {
+            e.keep_max = out_capacity[i];   // a file that will not fit is only measured
+          } else {
+            e.to_dev = true;
+            e.dev_out = static_cast<uint8_t*>(out[i]);
+            e.dev_cap = out_capacity[i];
+          }
+        }
+        if ((rc = compress_to_host(st, s, m, im.data())) != UHDR_HIP_NO_ERROR) return rc;
+        auto deliver = [&](int lo, int hi) {
+          for (int k = lo; k < hi; ++k) {
+            const int i = idx[k];
+            out_size[i] = im[(size_t)k].n;
+            if (im[(size_t)k].n > out_capacity[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
+            if (host_out) memcpy(out[i], im[(size_t)k].bytes, im[(size_t)k].n);
             st_[i] = UHDR_HIP_NO_ERROR;
           }
         };
@@ -2774,6 +2922,122 @@ int uhdr_hip_jpegr_encode_rgbmap_batch(int n, const uhdr_hip_image_t* p010_image
                       nullptr, UHDR_HIP_TONEMAP_SHIFT, nullptr, true);
 }
 
+// JPEG/R files from packed RGBA pairs: API-1's checks where they apply, then those of
+// uhdr_hip_generate_gainmap_packed_batch; per round one generate call (equal files share its launches), one k_rgba_to_ycc420 launch
+// for the primaries and the 2 m compressions behind one synchronisation, as in encode_files
+int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf, int quality,
+                                       const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                       size_t* out_size, int* status, int rgb_map, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (hdr_images == nullptr || sdr_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
+  auto stride_bad = [](const uhdr_hip_image_t& im) { return im.luma_stride != 0 && (im.luma_stride < im.width || im.luma_stride > 0xFFFFFFFFull); };
+  auto check = [&](const uhdr_hip_image_t& hd, const uhdr_hip_image_t& sd, int i) -> int {
+    if (hd.data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+    if ((hd.width | hd.height) & 1) return UHDR_HIP_ERROR_UNSUPPORTED_WIDTH_HEIGHT;
+    if (hd.width < 8 || hd.height < 8 || hd.width > 8192 || hd.height > 8192) return UHDR_HIP_ERROR_UNSUPPORTED_WIDTH_HEIGHT;
+    if (!valid_gamut(hd.colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+    if (stride_bad(hd)) return UHDR_HIP_ERROR_INVALID_STRIDE;
+    if (out[i] == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+    if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+    if (sd.data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+    if (stride_bad(sd)) return UHDR_HIP_ERROR_INVALID_STRIDE;
+    if (hd.width != sd.width || hd.height != sd.height) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
+    if (!valid_gamut(sd.colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+    if (exif != nullptr && exif[i] == nullptr && exif_size[i] != 0) return UHDR_HIP_ERROR_BAD_PTR;
+    // uhdr_hip_generate_gainmap_packed_batch's own
+    if (sd.pixelFormat != UHDR_HIP_PIX_FMT_RGBA8888) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+    if (hd.pixelFormat != UHDR_HIP_PIX_FMT_RGBA1010102 && hd.pixelFormat != UHDR_HIP_PIX_FMT_RGBA_F16) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+    const bool f16 = hd.pixelFormat == UHDR_HIP_PIX_FMT_RGBA_F16;
+    if (!host && (!al(sd.data, 4) || !al(hd.data, f16 ? 8 : 4))) return UHDR_HIP_ERROR_BAD_PTR;
+    if (f16 ? hdr_tf != UHDR_HIP_TF_LINEAR : hdr_tf == UHDR_HIP_TF_LINEAR) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+    return UHDR_HIP_NO_ERROR;
+  };
+  struct PackedFile {
+    int idx;
+    uhdr_hip_image_t hdr, sdr;   // luma_stride set; device images once staged
+    std::vector<uint8_t> icc;
+  };
+  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
+  std::vector<PackedFile> files;
+  for (int i = 0; i < n; ++i) {
+    if ((st_[i] = check(hdr_images[i], sdr_images[i], i)) != UHDR_HIP_NO_ERROR) continue;
+    PackedFile f{i, hdr_images[i], sdr_images[i], {}};
+    if (f.hdr.luma_stride == 0) f.hdr.luma_stride = f.hdr.width;
+    if (f.sdr.luma_stride == 0) f.sdr.luma_stride = f.sdr.width;
+    if (!jpegr::icc_profile_srgb_transfer(f.sdr.colorGamut, f.icc)) { st_[i] = UHDR_HIP_ERROR_INVALID_COLORGAMUT; continue; }
+    files.push_back(std::move(f));
+  }
+  if (files.empty()) return finish_statuses(st_, status);
+  // hdr_tf is shared, so every file that passed has the same HDR format
+  const size_t hdr_bpp = files[0].hdr.pixelFormat == UHDR_HIP_PIX_FMT_RGBA_F16 ? 8 : 4, map_bpp = rgb_map != 0 ? 4 : 1;
+  auto key = [](const PackedFile& f) { return std::make_tuple(f.sdr.width, f.sdr.height, f.sdr.colorGamut, f.hdr.colorGamut); };
+  std::stable_sort(files.begin(), files.end(), [&](const PackedFile& x, const PackedFile& y) { return key(x) < key(y); });
+  auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
+  size_t done = 0;
+  const int rc = run_rounds(
+      files.size(), (size_t)kEncRound, stream, [](size_t) { return (size_t)0; },   // rounds by count alone
+      [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
+        PackedFile* f = &files[r0];
+        int rc;
+        size_t map_total = 0, sdr_total = 0, hdr_total = 0;
+        for (int k = 0; k < m; ++k) {
+          const size_t w = f[k].sdr.width, h = f[k].sdr.height;
+          map_total += al256((w / 4) * (h / 4) * map_bpp + 64);
+          if (host) { sdr_total += al256(round_up(w * 4, 64) * h); hdr_total += al256(round_up(w * hdr_bpp, 64) * h); }
+        }
+        if ((rc = pool_reserve(st, kEncMap, map_total)) != 0) return rc;
+        if (sdr_total && (rc = pool_reserve(st, kEncYuv, sdr_total)) != 0) return rc;
+        if (hdr_total && (rc = pool_reserve(st, kEncP010, hdr_total)) != 0) return rc;
+        std::vector<uhdr_hip_image_t> a((size_t)m), b((size_t)m), c((size_t)m);
+        size_t o_map = 0, o_sdr = 0, o_hdr = 0;
+        for (int k = 0; k < m; ++k) {
+          PackedFile& e = f[k];
+          const size_t w = e.sdr.width, h = e.sdr.height;
+          if (host) {   // rows of the pixels alone, at a 64-byte pitch
+            const size_t sp = round_up(w * 4, 64), hp = round_up(w * hdr_bpp, 64);
+            uint8_t* ds = static_cast<uint8_t*>(st->pool[kEncYuv]) + o_sdr;
+            uint8_t* dh = static_cast<uint8_t*>(st->pool[kEncP010]) + o_hdr;
+            if ((rc = h2d_plane(ds, sp, e.sdr.data, e.sdr.luma_stride * 4, w * 4, h, 1, s)) != 0) return rc;
+            if ((rc = h2d_plane(dh, hp, e.hdr.data, e.hdr.luma_stride * hdr_bpp, w * hdr_bpp, h, 1, s)) != 0) return rc;
+            o_sdr += al256(sp * h); o_hdr += al256(hp * h);
+            e.sdr.data = ds; e.sdr.luma_stride = sp / 4;
+            e.hdr.data = dh; e.hdr.luma_stride = hp / hdr_bpp;
+          }
+          a[(size_t)k] = e.sdr; b[(size_t)k] = e.hdr;
+          memset(&c[(size_t)k], 0, sizeof(uhdr_hip_image_t));
+          c[(size_t)k].data = static_cast<uint8_t*>(st->pool[kEncMap]) + o_map;
+          o_map += al256((w / 4) * (h / 4) * map_bpp + 64);
+        }
+        uhdr_hip_metadata_t md;
+        if ((rc = uhdr_hip_generate_gainmap_packed_batch(m, a.data(), b.data(), hdr_tf, nullptr, &md, c.data(), rgb_map, s)) != UHDR_HIP_NO_ERROR) return rc;
+        std::vector<EncJpeg> jpg(2 * (size_t)m);
+        if ((rc = rgba420_planes(st, kEncSdr, s, m, a.data(), jpg.data(), 2)) != 0) return rc;
+        for (int k = 0; k < m; ++k) {
+          jpg[2 * (size_t)k].quality = quality;
+          jpg[2 * (size_t)k].icc = &f[k].icc;
+          uhdr_hip_image_t g = c[(size_t)k];   // (generate has filled in width, height and stride)
+          jpg[2 * (size_t)k + 1] = rgb_map != 0 ? gainmap_rgb_jpeg(g) : gainmap_jpeg(g, g.luma_stride);
+        }
+        if ((rc = compress_to_host(st, s, 2 * m, jpg.data())) != UHDR_HIP_NO_ERROR) return rc;
+        on_host_threads(m, [&](int lo, int hi) {
+          for (int k = lo; k < hi; ++k) {
+            const int i = f[k].idx;
+            const EncJpeg& sdr = jpg[2 * (size_t)k];
+            const EncJpeg& gm = jpg[2 * (size_t)k + 1];
+            st_[i] = jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
+                                              nullptr, 0, md, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i], false);
+          }
+        });
+        return (int)UHDR_HIP_NO_ERROR;
+      },
+      &done);
+  for (size_t k = done; k < files.size(); ++k) st_[files[k].idx] = rc;   // the files of the failed round and of those behind it
+  return finish_statuses(st_, status);
+}
+
 int uhdr_hip_jpegr_encode_adaptive_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf,
                                          int quality, const void* const* exif, const size_t* exif_size, void* const* out,
                                          const size_t* out_capacity, size_t* out_size, uhdr_hip_metadata_t* metadata, int* status,
@@ -3745,6 +4009,79 @@ int uhdr_hip_generate_gainmap_md_batch(int n, const uhdr_hip_image_t* yuvs, cons
       ++m;
     }
     HIP_TRY(launch_generate_md(c, mc, b, m, hdr_tf, aligned, rgb != 0, s));
+    i += m;
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
+// Packed RGBA inputs: uhdr_hip_generate_gainmap_md_batch's chunks over an RGBA8888 SDR image and an
+// RGBA1010102 / RGBA F16 HDR image; every chunk one k_generate_packed launch on the exact path
+int uhdr_hip_generate_gainmap_packed_batch(int n, const uhdr_hip_image_t* sdrs, const uhdr_hip_image_t* hdrs, int hdr_tf,
+                                           const uhdr_hip_metadata_t* md_in, uhdr_hip_metadata_t* md_out, uhdr_hip_image_t* dests, int rgb,
+                                           void* stream) {
+  if (n < 0 || (n > 0 && (sdrs == nullptr || hdrs == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
+  for (int i = 0; i < n; ++i) {
+    if (sdrs[i].pixelFormat != UHDR_HIP_PIX_FMT_RGBA8888) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+    if (hdrs[i].pixelFormat != UHDR_HIP_PIX_FMT_RGBA1010102 && hdrs[i].pixelFormat != UHDR_HIP_PIX_FMT_RGBA_F16) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+    if (hdrs[i].pixelFormat != hdrs[0].pixelFormat) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  }
+  const bool f16 = n > 0 && hdrs[0].pixelFormat == UHDR_HIP_PIX_FMT_RGBA_F16;
+  for (int i = 0; i < n; ++i) {
+    if (sdrs[i].data == nullptr || hdrs[i].data == nullptr || dests[i].data == nullptr || !al(sdrs[i].data, 4) ||
+        !al(hdrs[i].data, f16 ? 8 : 4) || (rgb != 0 && !al(dests[i].data, 4)))
+      return UHDR_HIP_ERROR_BAD_PTR;
+  }
+  int rc;
+  if (md_in != nullptr && (rc = validate_md(md_in)) != UHDR_HIP_NO_ERROR) return rc;
+  auto stride_of = [](const uhdr_hip_image_t& im) { return im.luma_stride == 0 ? im.width : im.luma_stride; };
+  const bool tf_known = hdr_tf == UHDR_HIP_TF_LINEAR || hdr_tf == UHDR_HIP_TF_HLG || hdr_tf == UHDR_HIP_TF_PQ;
+  for (int i = 0; i < n; ++i) {   // validate_generate's order around the packed images' own checks
+    const uhdr_hip_image_t& sd = sdrs[i];
+    const uhdr_hip_image_t& hd = hdrs[i];
+    if (stride_of(sd) < sd.width || stride_of(hd) < hd.width || stride_of(sd) > 0xFFFFFFFFull || stride_of(hd) > 0xFFFFFFFFull)
+      return UHDR_HIP_ERROR_INVALID_STRIDE;
+    if (sd.width != hd.width || sd.height != hd.height) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
+    if (sd.colorGamut == UHDR_HIP_CG_UNSPECIFIED || hd.colorGamut == UHDR_HIP_CG_UNSPECIFIED) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+    if (f16 ? hdr_tf != UHDR_HIP_TF_LINEAR : (hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ)) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+    if (!valid_gamut(sd.colorGamut) || !valid_gamut(hd.colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+  }
+  if (!tf_known) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  uhdr_hip_metadata_t md;
+  if (md_in != nullptr) md = *md_in;
+  else fill_generate_metadata(hdr_tf, &md);
+  if (md_out != nullptr) *md_out = md;
+  int i = 0;
+  while (i < n) {
+    // chunk = up to kMaxChunk consecutive pairs of identical size, gamuts and alignment class
+    const uhdr_hip_image_t& s0 = sdrs[i];
+    const GenConsts c = generate_consts(s0.colorGamut, hdrs[i].colorGamut, hdr_tf, 0, s0.width, s0.height, md);
+    const GenMdConsts mc = generate_md_consts(md, c);
+    PackedBatch b;
+    int m = 0;
+    bool aligned = true;
+    while (i + m < n && m < kMaxChunk) {
+      const uhdr_hip_image_t& sd = sdrs[i + m];
+      const uhdr_hip_image_t& hd = hdrs[i + m];
+      if (sd.width != s0.width || sd.height != s0.height || sd.colorGamut != s0.colorGamut || hd.colorGamut != hdrs[i].colorGamut) break;
+      PackedImage& p = b.img[m];
+      p.sdr = static_cast<const uint32_t*>(sd.data);
+      p.hdr = hd.data;
+      p.map = static_cast<uint8_t*>(dests[i + m].data);
+      p.sdr_stride = (uint32_t)stride_of(sd);
+      p.hdr_stride = (uint32_t)stride_of(hd);
+      // 16-byte row pieces of both images (a dword format: 4 pixels, F16: 2) and the pair's bytes as one store
+      const bool a = c.width % 8u == 0 && al(p.sdr, 16) && p.sdr_stride % 4u == 0 && al(p.hdr, 16) && p.hdr_stride % (f16 ? 2u : 4u) == 0 &&
+                     al(p.map, rgb != 0 ? 8 : 2);
+      if (m == 0) aligned = a;
+      else if (a != aligned) break;
+      fill_generate_dest(&sd, &dests[i + m]);
+      if (rgb != 0) dests[i + m].pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
+      ++m;
+    }
+    HIP_TRY(launch_generate_packed(c, mc, b, m, hdr_tf, f16, aligned, rgb != 0, s));
     i += m;
   }
   return UHDR_HIP_NO_ERROR;

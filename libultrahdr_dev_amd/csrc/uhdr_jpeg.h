@@ -64,6 +64,26 @@ size_t batch_desc_bytes(int n);
 hipError_t encode_batch_async(int n, const Job* jobs, const Layout* l, uint8_t* const* ws, const BatchOut* outs, uint8_t* host_desc,
                               uint8_t* dev_desc, hipStream_t s);
 
+// ---- RGBA8888 -> the planes of a 4:2:0 file (uhdr_hip_jpeg_encode_rgba420_batch) ----------------------------------------------
+// What libjpeg hands its FDCT for in_color_space = JCS_RGB with 2x2 luma sampling: jccolor.c's RGB -> YCbCr at full resolution,
+// jcsample.c's h2v2_downsample of the chroma, every plane padded to whole MCUs the way libjpeg pads (last column out to the padded
+// width, last row to an even count, then the last -- downsampled -- row).  With mcw x mch MCUs: Y is 16 mcw x 16 mch at y, Cb and
+// Cr are 8 mcw x 8 mch each at cb and cb + 64 mcw mch, rows packed.  The encoder reads them as they are (no padding rule applies).
+constexpr int kRgba420Chunk = 64;       // images per launch (descriptors in the kernarg segment)
+struct Rgba420Image {
+  const uint32_t* src;     // RGBA pixels, 4-byte aligned
+  uint8_t* y;              // 8-byte aligned
+  uint8_t* cb;             // 4-byte aligned
+  uint32_t w, h, stride;   // stride in pixels
+  uint32_t mcw, mch;
+};
+struct Rgba420Batch {
+  Rgba420Image img[kRgba420Chunk];
+};
+static_assert(sizeof(Rgba420Batch) <= 4096, "k_rgba_to_ycc420's kernel arguments exceed the kernarg segment");
+inline size_t rgba420_plane_bytes(size_t w, size_t h) { return 384 * ((w + 15) / 16) * ((h + 15) / 16); }
+hipError_t launch_rgba_to_ycc420(const Rgba420Batch& b, int n, hipStream_t s);   // one launch for n <= kRgba420Chunk images of any sizes
+
 // ---- decoder (uhdr_jpeg_dec.hip) -------------------------------------------------------------------------------------
 struct HuffSpec {            // one DHT table in canonical form (T.81 Annex C)
   uint16_t first_code[17];   // first code of each length (index = length)

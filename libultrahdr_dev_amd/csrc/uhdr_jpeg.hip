@@ -13,12 +13,15 @@
 //                       the two boundary words OR-ed atomically); the last block pads the final byte with ones
 //   k_jpeg_stuff_count  one thread per 64 bytes of the packed stream: number of 0xFF bytes (and per workgroup)
 //   k_jpeg_stuff_copy   one thread per 64 bytes: copy to the output with 0x00 stuffed after every 0xFF, EOI at the end
+//   k_rgba_to_ycc420    (in front of the chain, uhdr_hip_jpeg_encode_rgba420_batch only) RGBA8888 -> the Y, Cb, Cr planes libjpeg's
+//                       colour conversion and h2v2 downsampler hand its FDCT, padded to whole MCUs as libjpeg pads them
 //
 // Byte-exact against libjpeg for every size, stride regime and quality tested (tests/test_gpu_jpeg.py against
 // oracle/jpeg_oracle.c, which tests/test_jpeg_oracle.py pins to the libjpeg builds of the image).
 #include <hip/hip_runtime.h>
 #include "uhdr_wave_scan.h"
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -758,6 +761,75 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
   hipLaunchKernelGGL(k_jpeg_emit_multi, gb, bb, 0, s, dj, dblk, nj);
   hipLaunchKernelGGL(k_jpeg_stuff_count_multi, gc, bc, 0, s, dj, dstuff, nj);
   hipLaunchKernelGGL(k_jpeg_stuff_copy_multi, gc, bc, 0, s, dj, dout, dstuff, nj);
+  return hipGetLastError();
+}
+
+// ---- RGBA8888 -> 4:2:0 planes (uhdr_jpeg.h) --------------------------------------------------------------------------------------
+// A thread owns an 8 x 2 pixel piece of the padded image (blockIdx.y = image): two rows of 32 bytes in, two rows of 8 luma bytes
+// and four bytes each of Cb and Cr out.  Padding is a clamp of the source coordinates: columns to w - 1 (expand_right_edge works
+// on the full-resolution rows, chroma included); rows to h - 1 for luma, while a chroma row below the image repeats the last
+// DOWNSAMPLED row, i.e. takes the rows of chroma row ceil(h / 2) - 1.  The second of those is always row h - 1: what luma needs there.
+__global__ void __launch_bounds__(256) k_rgba_to_ycc420(const Rgba420Batch b) {
+  const Rgba420Image& im = b.img[blockIdx.y];
+  const uint32_t ucols = 2u * im.mcw, units = ucols * 8u * im.mch;
+  const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+  if (idx >= units) return;
+  const uint32_t uy = idx / ucols, ux = idx - uy * ucols;
+  const uint32_t x0 = ux * 8u, last_c = (im.h + 1u) / 2u - 1u;
+  const bool below = uy > last_c;
+  const uint32_t cy = below ? last_c : uy;
+  uint32_t px[2][8];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const uint32_t rr = min(2u * cy + (uint32_t)r, im.h - 1u);
+    const uint32_t* row = im.src + (size_t)rr * im.stride;
+    if (x0 + 8u <= im.w && (reinterpret_cast<uintptr_t>(row + x0) & 15u) == 0u) {
+      const uint4 a = reinterpret_cast<const uint4*>(row + x0)[0], c = reinterpret_cast<const uint4*>(row + x0)[1];
+      px[r][0] = a.x; px[r][1] = a.y; px[r][2] = a.z; px[r][3] = a.w;
+      px[r][4] = c.x; px[r][5] = c.y; px[r][6] = c.z; px[r][7] = c.w;
+    } else {
+#pragma unroll
+      for (int x = 0; x < 8; ++x) px[r][x] = row[min(x0 + (uint32_t)x, im.w - 1u)];
+    }
+  }
+  // jccolor.c rgb_ycc_convert: 16-bit fixed point, the chroma offset with its rounding term (the constants of load_samples_rgb)
+  uint32_t yv[2][2] = {{0u, 0u}, {0u, 0u}};
+  int cbs[2][8], crs[2][8];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+#pragma unroll
+    for (int x = 0; x < 8; ++x) {
+      const int R = (int)(px[r][x] & 0xffu), G = (int)((px[r][x] >> 8) & 0xffu), B = (int)((px[r][x] >> 16) & 0xffu);
+      const int Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
+      cbs[r][x] = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16;
+      crs[r][x] = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
+      yv[r][x >> 2] |= (uint32_t)Y << (8 * (x & 3));
+    }
+  }
+  // h2v2_downsample: (a + b + c + d + bias) >> 2, bias 1, 2, 1, 2 ... along the row (this thread's first chroma column is even)
+  uint32_t cbw = 0u, crw = 0u;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int bias = 1 + (q & 1);
+    cbw |= (uint32_t)((cbs[0][2 * q] + cbs[0][2 * q + 1] + cbs[1][2 * q] + cbs[1][2 * q + 1] + bias) >> 2) << (8 * q);
+    crw |= (uint32_t)((crs[0][2 * q] + crs[0][2 * q + 1] + crs[1][2 * q] + crs[1][2 * q + 1] + bias) >> 2) << (8 * q);
+  }
+  const size_t ys = 16u * (size_t)im.mcw, cs = 8u * (size_t)im.mcw;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int sr = below ? 1 : r;   // below the image both luma rows repeat row h - 1
+    *reinterpret_cast<uint2*>(im.y + (2u * (size_t)uy + (size_t)r) * ys + x0) = make_uint2(yv[sr][0], yv[sr][1]);
+  }
+  uint8_t* cbp = im.cb + (size_t)uy * cs + 4u * ux;
+  *reinterpret_cast<uint32_t*>(cbp) = cbw;
+  *reinterpret_cast<uint32_t*>(cbp + 64u * (size_t)im.mcw * im.mch) = crw;
+}
+hipError_t launch_rgba_to_ycc420(const Rgba420Batch& b, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (n > kRgba420Chunk) return hipErrorInvalidValue;
+  uint32_t units = 0;
+  for (int k = 0; k < n; ++k) units = std::max(units, 16u * b.img[k].mcw * b.img[k].mch);
+  hipLaunchKernelGGL(k_rgba_to_ycc420, dim3((units + 255u) / 256u, (unsigned)n), dim3(256), 0, s, b);
   return hipGetLastError();
 }
 

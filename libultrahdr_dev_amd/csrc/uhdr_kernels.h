@@ -279,7 +279,19 @@ struct GenMdConsts {
   double gamma, den;                  // (double)gamma; (double)(log2_max - log2_min)
 };
 
+// ---- gain maps from packed RGBA: what k_generate_packed takes in GenBatch's place ----
+struct PackedImage {       // strides in pixels
+  const uint32_t* sdr;     // RGBA8888
+  const void* hdr;         // RGBA1010102 (a dword per pixel) or RGBA F16 (8 bytes per pixel)
+  uint8_t* map;
+  uint32_t sdr_stride, hdr_stride;
+};
+struct PackedBatch {
+  PackedImage img[kMaxChunk];
+};
+
 static_assert(sizeof(GenConsts) + sizeof(GenMdConsts) + sizeof(GenBatch) <= 4096, "generate kernel arguments exceed the kernarg segment");
+static_assert(sizeof(GenConsts) + sizeof(GenMdConsts) + sizeof(PackedBatch) <= 4096, "generate kernel arguments exceed the kernarg segment");
 static_assert(sizeof(AppConsts) + sizeof(AppMdConsts) + sizeof(AppBatch) + 16 <= 4096, "apply kernel arguments exceed the kernarg segment");
 static_assert(sizeof(AppConsts) + sizeof(AppBatch) <= 4096, "apply kernel arguments exceed the kernarg segment");
 
@@ -318,6 +330,11 @@ hipError_t launch_apply_md(const AppConsts& c, const AppMdConsts& m, const AppBa
 // general metadata: launch_generate_rgb's launch; rgb: its RGBA map, otherwise one byte per map pixel (aligned launches: 2-byte aligned)
 hipError_t launch_generate_md(const GenConsts& c, const GenMdConsts& m, const GenBatch& b, int n, int hdr_tf, bool aligned, bool rgb,
                               hipStream_t s);
+// packed RGBA inputs: launch_generate_md's launch and maps for n <= kMaxChunk pairs of one size; f16: the HDR images are RGBA F16
+// (hdr_tf must be 0), otherwise RGBA1010102 (hdr_tf 1 or 2).  aligned: both images' rows start on 16 bytes, the width is a multiple
+// of 8 and the map is aligned as launch_generate_md's
+hipError_t launch_generate_packed(const GenConsts& c, const GenMdConsts& m, const PackedBatch& b, int n, int hdr_tf, bool f16, bool aligned,
+                                  bool rgb, hipStream_t s);
 hipError_t launch_build_luts(float* lut /* kLutTotal floats */, hipStream_t s);
 hipError_t launch_build_lut_codes(float* lut /* the whole buffer: reads the two OETF tables, writes kCodeHlg / kCodePq */, hipStream_t s);
 // GainLUT table (kGainLutN floats, device) for (log2 min, log2 max, boost factor)

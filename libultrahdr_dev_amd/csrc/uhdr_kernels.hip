@@ -6,6 +6,7 @@
 //   k_apply_s4_est, k_apply_px_est, k_apply_resolve   EXACT arithmetic as an f32 estimate + the exact path on the pixels in doubt
 //   k_apply_lut_s4, k_apply_lut   the loops with the reference's LUT accessors (opt-in LUT mode)
 //   k_apply_px_md, k_generate_md   gain maps with gamma, offsets and an HDR capacity range (no reference counterpart)
+//   k_generate_packed        gain maps from packed RGBA pairs: RGBA8888 with RGBA1010102 or RGBA F16 (no reference counterpart)
 //   k_tonemap_*              UltraHdr::toneMap                    (:517-558)
 //   k_convert_yuv<ALIGNED>   JpegR::convertYuv + transformYuv420  (lib/src/jpegr.cpp:1199-1203,
 //                                                                  lib/src/gainmapmath.cpp:483-520)
@@ -222,8 +223,9 @@ __device__ __forceinline__ float cvt_word1(uint32_t w) {
 // filter and the exact path both start from), kGenBack takes them from *mid instead of sampling; kGenWhole with mid != nullptr runs
 // as ever and leaves a copy in *mid.  kGenLinear (exact path only) stops in front of the luminances and returns in *mid the two
 // LINEAR colours of both pixels -- SDR, and HDR converted into the SDR gamut --, which is where the per-channel map (k_generate_rgb)
-// parts from the single-channel one.
-constexpr int kGenWhole = 0, kGenFront = 1, kGenBack = 2, kGenLinear = 3;
+// parts from the single-channel one.  kGenBackLinear is kGenLinear from the sampled values in *mid, as kGenBack: the packed-RGBA
+// generate (k_generate_packed) samples its own two images and has no YUV -> RGB step.
+constexpr int kGenWhole = 0, kGenFront = 1, kGenBack = 2, kGenLinear = 3, kGenBackLinear = 4;
 struct GenMid { f2 r, g, b, hr, hg, hb; };
 template <int TF, bool LUT, bool FILTER, bool DEFER = false, int PART = kGenWhole>
 __device__ __forceinline__ uint32_t gen_pair(const GenConsts& c, const uint32_t (&hy)[2][4][2],
@@ -232,7 +234,7 @@ __device__ __forceinline__ uint32_t gen_pair(const GenConsts& c, const uint32_t 
                                              uint8_t (&out)[2], float (&gain)[2], const float* s_srgb, const float* s_hdr,
                                              GenMid* mid = nullptr) {
   f2 r, g, b, hr, hg, hb;
-  if (PART == kGenBack) {
+  if (PART == kGenBack || PART == kGenBackLinear) {
     r = mid->r; g = mid->g; b = mid->b; hr = mid->hr; hg = mid->hg; hb = mid->hb;
   } else {
   f2 sy = splat(0.0f), su = splat(0.0f), sv = splat(0.0f);
@@ -294,8 +296,8 @@ __device__ __forceinline__ uint32_t gen_pair(const GenConsts& c, const uint32_t 
   hg = pk_add_sat(hsy - splat(c.hdr_gcb) * hsu, -(splat(c.hdr_gcr) * hsv));
   hb = pk_add_sat(hsy, splat(c.hdr_cb) * hsu);
   }
-  static_assert(PART != kGenLinear || (!LUT && !FILTER), "kGenLinear is the exact path's");
-  if (PART != kGenBack && PART != kGenLinear && mid != nullptr) { mid->r = r; mid->g = g; mid->b = b; mid->hr = hr; mid->hg = hg; mid->hb = hb; }
+  static_assert((PART != kGenLinear && PART != kGenBackLinear) || (!LUT && !FILTER), "kGenLinear is the exact path's");
+  if (PART != kGenBack && PART != kGenLinear && PART != kGenBackLinear && mid != nullptr) { mid->r = r; mid->g = g; mid->b = b; mid->hr = hr; mid->hg = hg; mid->hb = hb; }
   if (PART == kGenFront) return 0u;
 
   if (FILTER && !LUT) {
@@ -397,7 +399,7 @@ __device__ __forceinline__ uint32_t gen_pair(const GenConsts& c, const uint32_t 
     const f2 t2 = splat(c.gm[6]) * hr + splat(c.gm[7]) * hg + splat(c.gm[8]) * hb;
     hr = t0; hg = t1; hb = t2;
   }
-  if (PART == kGenLinear) { mid->r = r; mid->g = g; mid->b = b; mid->hr = hr; mid->hg = hg; mid->hb = hb; return 0u; }
+  if (PART == kGenLinear || PART == kGenBackLinear) { mid->r = r; mid->g = g; mid->b = b; mid->hr = hr; mid->hg = hg; mid->hb = hb; return 0u; }
   const f2 hdr_nits = (splat(c.lum_r) * hr + splat(c.lum_g) * hg + splat(c.lum_b) * hb) * splat(c.hdr_white_nits);
 
   gain[0] = raw_gain(sdr_nits.x, hdr_nits.x);
@@ -1217,6 +1219,188 @@ hipError_t launch_generate_md(const GenConsts& c, const GenMdConsts& m, const Ge
     case 0: return rgb ? launch_generate_md_tf<0, true>(c, m, b, n, aligned, s) : launch_generate_md_tf<0, false>(c, m, b, n, aligned, s);
     case 1: return rgb ? launch_generate_md_tf<1, true>(c, m, b, n, aligned, s) : launch_generate_md_tf<1, false>(c, m, b, n, aligned, s);
     case 2: return rgb ? launch_generate_md_tf<2, true>(c, m, b, n, aligned, s) : launch_generate_md_tf<2, false>(c, m, b, n, aligned, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// Gain maps from packed RGBA: an RGBA8888 SDR image and an RGBA1010102 (HLG / PQ) or RGBA F16 (linear) HDR
+// image, strides in pixels.  A thread owns a pair of map pixels as in the other generate kernels -- an 8 x 4 pixel block of both
+// images, per row 32 bytes of a dword format and 64 bytes of F16 -- and sums each channel as samplePixels does (gainmapmath.cpp:
+// 605-615: dy outer, dx inner, one running f32 sum, code * (1 / max) and the add two roundings).  There is no YUV -> RGB step and no
+// clamp: the six sums / 16 are what gen_pair's transfer functions start from (kGenBackLinear), and the bytes are k_generate_md's.
+constexpr float k1023 = 1 / 1023.0f;
+// k_generate_md's tail as a function: the pair's bytes from its two linear colours -- per channel (RGB: one RGBA pixel each), or of the
+// two luminances as gen_pair forms them -- and their store.  (k_generate_md keeps its own copy: its instructions stay the parent's.)
+template <bool ALIGNED, bool RGB>
+__device__ __forceinline__ void encode_store_md(const GenConsts& c, const GenMdConsts& m, const GenMid& lin, uint8_t* map, uint32_t my,
+                                                uint32_t mx, bool two) {
+  if (RGB) {
+    const f2 sdr[3] = {lin.r * splat(203.0f), lin.g * splat(203.0f), lin.b * splat(203.0f)};
+    const f2 hdr[3] = {lin.hr * splat(c.hdr_white_nits), lin.hg * splat(c.hdr_white_nits), lin.hb * splat(c.hdr_white_nits)};
+    uint32_t px[2] = {0xFF000000u, 0xFF000000u};
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+        px[k] |= (uint32_t)encode_gain_md(c, m, k ? sdr[ch].y : sdr[ch].x, k ? hdr[ch].y : hdr[ch].x) << (8 * ch);
+    }
+    uint32_t* mp = reinterpret_cast<uint32_t*>(map) + (size_t)my * c.map_w + mx;
+    if (ALIGNED) {   // map_w is even and the map 8-byte aligned
+      *reinterpret_cast<uint2*>(mp) = make_uint2(px[0], px[1]);
+    } else {
+      mp[0] = px[0];
+      if (two) mp[1] = px[1];
+    }
+  } else {
+    // the two luminances, as gen_pair forms them behind the linear colours
+    const f2 sdr_nits = (splat(c.lum_r) * lin.r + splat(c.lum_g) * lin.g + splat(c.lum_b) * lin.b) * splat(203.0f);
+    const f2 hdr_nits = (splat(c.lum_r) * lin.hr + splat(c.lum_g) * lin.hg + splat(c.lum_b) * lin.hb) * splat(c.hdr_white_nits);
+    const uint8_t b0 = encode_gain_md(c, m, sdr_nits.x, hdr_nits.x), b1 = encode_gain_md(c, m, sdr_nits.y, hdr_nits.y);
+    uint8_t* mp = map + (size_t)my * c.map_w + mx;
+    if (ALIGNED) {   // map_w is even and the map 2-byte aligned
+      *reinterpret_cast<uint16_t*>(mp) = (uint16_t)((uint32_t)b0 | ((uint32_t)b1 << 8));
+    } else {
+      mp[0] = b0;
+      if (two) mp[1] = b1;
+    }
+  }
+}
+// float of the low / high half of w, exactly (a subnormal half is a normal float; the kernel keeps the default FP mode, in which
+// v_cvt_f32_f16 does not flush)
+__device__ __forceinline__ float half_lo(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xffffu)); }
+__device__ __forceinline__ float half_hi(uint32_t w) { return (float)__builtin_bit_cast(_Float16, (uint16_t)(w >> 16)); }
+// rows r = 0..3 of the pair's block of a dword format: px[r][0..3] the first map pixel's columns, px[r][4..7] the second's
+template <bool ALIGNED>
+__device__ __forceinline__ void load_packed32(const uint32_t* base, uint32_t stride, uint32_t my, uint32_t pr, bool two, uint32_t (&px)[4][8]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const uint32_t* row = base + ((size_t)(4u * my + (uint32_t)r) * stride + 8u * pr);
+    if (ALIGNED) {
+      const uint4 a = ld_stream(reinterpret_cast<const uint4*>(row)), b = ld_stream(reinterpret_cast<const uint4*>(row) + 1);
+      px[r][0] = a.x; px[r][1] = a.y; px[r][2] = a.z; px[r][3] = a.w;
+      px[r][4] = b.x; px[r][5] = b.y; px[r][6] = b.z; px[r][7] = b.w;
+    } else {
+#pragma unroll
+      for (int x = 0; x < 8; ++x) px[r][x] = (x < 4 || two) ? ld_stream(row + x) : 0u;
+    }
+  }
+}
+// the same of RGBA F16: px[r][x] = (R | G << 16, B | A << 16)
+template <bool ALIGNED>
+__device__ __forceinline__ void load_packed64(const uint2* base, uint32_t stride, uint32_t my, uint32_t pr, bool two, uint2 (&px)[4][8]) {
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const uint2* row = base + ((size_t)(4u * my + (uint32_t)r) * stride + 8u * pr);
+    if (ALIGNED) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const uint4 a = ld_stream(reinterpret_cast<const uint4*>(row) + q);
+        px[r][2 * q] = make_uint2(a.x, a.y); px[r][2 * q + 1] = make_uint2(a.z, a.w);
+      }
+    } else {
+#pragma unroll
+      for (int x = 0; x < 8; ++x) px[r][x] = (x < 4 || two) ? ld_stream(row + x) : make_uint2(0u, 0u);
+    }
+  }
+}
+// samplePixels per channel over both blocks; TEN: 10-bit codes (RGBA1010102), otherwise bytes (RGBA8888)
+template <bool TEN>
+__device__ __forceinline__ void sample_packed32(const uint32_t (&px)[4][8], f2 (&e)[3]) {
+  e[0] = e[1] = e[2] = splat(0.0f);
+#pragma unroll
+  for (int dy = 0; dy < 4; ++dy) {
+#pragma unroll
+    for (int dx = 0; dx < 4; ++dx) {
+      const uint32_t p0 = px[dy][dx], p1 = px[dy][4 + dx];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const f2 code = TEN ? (f2){(float)((p0 >> (10 * ch)) & 0x3ffu), (float)((p1 >> (10 * ch)) & 0x3ffu)}
+                            : (f2){(float)((p0 >> (8 * ch)) & 0xffu), (float)((p1 >> (8 * ch)) & 0xffu)};
+        e[ch] += code * splat(TEN ? k1023 : k255);
+      }
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) e[ch] *= splat(0.0625f);   // e / 16.0f
+}
+__device__ __forceinline__ void sample_packed64(const uint2 (&px)[4][8], f2 (&e)[3]) {
+  e[0] = e[1] = e[2] = splat(0.0f);
+#pragma unroll
+  for (int dy = 0; dy < 4; ++dy) {
+#pragma unroll
+    for (int dx = 0; dx < 4; ++dx) {
+      const uint2 p0 = px[dy][dx], p1 = px[dy][4 + dx];
+      e[0] += (f2){half_lo(p0.x), half_lo(p1.x)};
+      e[1] += (f2){half_hi(p0.x), half_hi(p1.x)};
+      e[2] += (f2){half_lo(p0.y), half_lo(p1.y)};
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) e[ch] *= splat(0.0625f);
+}
+template <int TF, bool F16, bool ALIGNED, int TILES, bool RGB>
+__global__ void __launch_bounds__(kGenBlock, 1) k_generate_packed(const GenConsts c, const GenMdConsts m, const PackedBatch b) {
+  static_assert(F16 ? TF == 0 : TF != 0, "F16 is linear light, RGBA1010102 carries HLG or PQ");
+  const uint32_t img_i = blockIdx.x, blk = blockIdx.y;
+  const PackedImage& im = b.img[img_i];
+  const uint32_t pairs_per_row = (c.map_w + 1u) >> 1;
+  const uint32_t total = pairs_per_row * c.map_h;
+#pragma unroll 1
+  for (uint32_t t = 0; t < (uint32_t)TILES; ++t) {
+    const uint32_t idx = (blk * (uint32_t)TILES + t) * (uint32_t)kGenBlock + threadIdx.x;
+    if (idx >= total) break;
+    const uint32_t my = idx / pairs_per_row;
+    const uint32_t pr = idx - my * pairs_per_row;
+    const uint32_t mx = pr * 2u;
+    const bool two = ALIGNED || (mx + 1u < c.map_w);
+    GenMid mid;
+    f2 e[3];
+    {
+      uint32_t px[4][8];
+      load_packed32<ALIGNED>(im.sdr, im.sdr_stride, my, pr, two, px);
+      sample_packed32<false>(px, e);
+      mid.r = e[0]; mid.g = e[1]; mid.b = e[2];
+    }
+    if (F16) {
+      uint2 px[4][8];
+      load_packed64<ALIGNED>(static_cast<const uint2*>(im.hdr), im.hdr_stride, my, pr, two, px);
+      sample_packed64(px, e);
+    } else {
+      uint32_t px[4][8];
+      load_packed32<ALIGNED>(static_cast<const uint32_t*>(im.hdr), im.hdr_stride, my, pr, two, px);
+      sample_packed32<true>(px, e);
+    }
+    mid.hr = e[0]; mid.hg = e[1]; mid.hb = e[2];
+    uint32_t hy[2][4][2], huv[2][2][2], y8[2][4], u8[2][2], v8[2][2];   // (gen_pair's planar inputs: not read from kGenBack on)
+    uint8_t o[2];
+    float gn[2];
+    gen_pair<TF, false, false, false, kGenBackLinear>(c, hy, huv, y8, u8, v8, o, gn, nullptr, nullptr, &mid);   // (a missing second pixel: zeros, dropped)
+    encode_store_md<ALIGNED, RGB>(c, m, mid, im.map, my, mx, two);
+  }
+}
+template <int TF, bool F16, bool RGB>
+static hipError_t launch_generate_packed_tf(const GenConsts& c, const GenMdConsts& m, const PackedBatch& b, int n, bool aligned, hipStream_t s) {
+  const uint32_t total = ((c.map_w + 1u) >> 1) * c.map_h;
+  if (total == 0 || n == 0) return hipSuccess;
+  const bool small = generate_is_small(c, n);   // spans per block as launch_generate_t chooses them
+  const unsigned per = (unsigned)kGenBlock * (small ? 1u : (unsigned)kGenTiles);
+  const dim3 g((unsigned)n, (total + per - 1u) / per, 1), blk(kGenBlock, 1, 1);
+  if (small) {
+    if (aligned) hipLaunchKernelGGL((k_generate_packed<TF, F16, true, 1, RGB>), g, blk, 0, s, c, m, b);
+    else hipLaunchKernelGGL((k_generate_packed<TF, F16, false, 1, RGB>), g, blk, 0, s, c, m, b);
+  } else {
+    if (aligned) hipLaunchKernelGGL((k_generate_packed<TF, F16, true, kGenTiles, RGB>), g, blk, 0, s, c, m, b);
+    else hipLaunchKernelGGL((k_generate_packed<TF, F16, false, kGenTiles, RGB>), g, blk, 0, s, c, m, b);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_generate_packed(const GenConsts& c, const GenMdConsts& m, const PackedBatch& b, int n, int hdr_tf, bool f16, bool aligned,
+                                  bool rgb, hipStream_t s) {
+  if (f16 != (hdr_tf == 0)) return hipErrorInvalidValue;
+  switch (hdr_tf) {
+    case 0: return rgb ? launch_generate_packed_tf<0, true, true>(c, m, b, n, aligned, s) : launch_generate_packed_tf<0, true, false>(c, m, b, n, aligned, s);
+    case 1: return rgb ? launch_generate_packed_tf<1, false, true>(c, m, b, n, aligned, s) : launch_generate_packed_tf<1, false, false>(c, m, b, n, aligned, s);
+    case 2: return rgb ? launch_generate_packed_tf<2, false, true>(c, m, b, n, aligned, s) : launch_generate_packed_tf<2, false, false>(c, m, b, n, aligned, s);
     default: return hipErrorInvalidValue;
   }
 }

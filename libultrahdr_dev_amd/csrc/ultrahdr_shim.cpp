@@ -376,6 +376,58 @@ status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, uhdr_uncomp
   });
 }
 
+namespace {
+// a packed RGBA image: the reference's enumerators (RGBA8888 3, RGBAF16 4, RGBA1010102 5) as the C-ABI's layouts; any other value
+// travels as it is and fails the C call's pixel-format check
+uhdr_hip_image_t to_c_packed(const ultrahdr_uncompressed_struct& s) {
+  uhdr_hip_image_t c = to_c(s);
+  switch (s.pixelFormat) {
+    case ULTRAHDR_PIX_FMT_RGBA8888: c.pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888; break;
+    case ULTRAHDR_PIX_FMT_RGBAF16: c.pixelFormat = UHDR_HIP_PIX_FMT_RGBA_F16; break;
+    case ULTRAHDR_PIX_FMT_RGBA1010102: c.pixelFormat = UHDR_HIP_PIX_FMT_RGBA1010102; break;
+    default: c.pixelFormat = UHDR_HIP_PIX_FMT_UNSPECIFIED; break;
+  }
+  return c;
+}
+}  // namespace
+
+status_t JpegRHip::encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_uncompressed_ptr sdr_image_ptr, ultrahdr_transfer_function hdr_tf,
+                                     uhdr_compressed_ptr dest, int quality, uhdr_exif_ptr exif) {
+  if (hdr_image_ptr == nullptr || sdr_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
+  const uhdr_hip_image_t h = to_c_packed(*hdr_image_ptr), sd = to_c_packed(*sdr_image_ptr);
+  return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
+    const void* ex = exif_ptr(exif);
+    const size_t exn = exif_len(exif);
+    return uhdr_hip_jpegr_encode_packed_batch(1, &h, &sd, (int)hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, mMultiChannelGainMap ? 1 : 0,
+                                              UHDR_HIP_MEM_HOST, nullptr);
+  });
+}
+
+status_t generateGainMapPacked(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompressed_ptr hdr_image_ptr, ultrahdr_transfer_function hdr_tf,
+                               ultrahdr_metadata_ptr metadata, uhdr_uncompressed_ptr dest, bool multi_channel, void* stream) {
+  if (sdr_image_ptr == nullptr || hdr_image_ptr == nullptr || dest == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
+  if (uhdr_hip_init(0) != UHDR_HIP_NO_ERROR) return ULTRAHDR_UNKNOWN_ERROR;
+  const uhdr_hip_image_t sd = to_c_packed(*sdr_image_ptr), h = to_c_packed(*hdr_image_ptr);
+  uhdr_hip_image_t d = to_c(*dest);
+  uhdr_hip_metadata_t md;
+  std::memset(&md, 0, sizeof(md));
+  const int rc = uhdr_hip_generate_gainmap_packed_batch(1, &sd, &h, (int)hdr_tf, nullptr, &md, &d, multi_channel ? 1 : 0, stream);
+  if (rc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(rc);
+  if (metadata != nullptr) {
+    metadata->version = md.version;
+    metadata->maxContentBoost = md.maxContentBoost;
+    metadata->minContentBoost = md.minContentBoost;
+    metadata->gamma = md.gamma;
+    metadata->offsetSdr = md.offsetSdr;
+    metadata->offsetHdr = md.offsetHdr;
+    metadata->hdrCapacityMin = md.hdrCapacityMin;
+    metadata->hdrCapacityMax = md.hdrCapacityMax;
+  }
+  from_c(d, dest);
+  dest->pixelFormat = multi_channel ? ULTRAHDR_PIX_FMT_RGBA8888 : ULTRAHDR_PIX_FMT_MONOCHROME;
+  return ULTRAHDR_NO_ERROR;
+}
+
 status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, uhdr_uncompressed_ptr yuv420_image_ptr, uhdr_compressed_ptr yuv420jpg_image_ptr,
                                ultrahdr_transfer_function hdr_tf, uhdr_compressed_ptr dest) {
   uhdr_hip_image_t p, y;
