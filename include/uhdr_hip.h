@@ -923,6 +923,69 @@ int uhdr_hip_jpegr_encode_api0_tonemapped_batch(int n, const uhdr_hip_image_t* p
                                                 int* status, int tonemap_op, const float* hdr_peak_nits, int boost_scope,
                                                 int mem_space, void* stream);
 
+/* ---- tone-mapped SDR image from a packed HDR image: the packed API-0 (no reference counterpart) ----
+ * The operator above for a caller that holds only a packed HDR image: an UHDR_HIP_PIX_FMT_RGBA1010102 (hdr_tf HLG or PQ) or
+ * UHDR_HIP_PIX_FMT_RGBA_F16 (hdr_tf LINEAR) image, layouts and alignment as the packed section defines them, becomes an
+ * UHDR_HIP_PIX_FMT_RGBA8888 one -- no narrow-range quantisation, no chroma subsampling.  In f32:
+ *   1. per pixel and channel the pixel value of the packed generate: RGBA1010102 (float)code10 * (1 / 1023.0f); RGBA_F16 the exact f32
+ *      of the half, subnormals included; then clamped to [0, 1] with fminf(fmaxf(x, 0), 1): -0 and negative halves give 0, halves
+ *      above 1.0 give 1.  Alpha is ignored
+ *   2. lin = invOETF_hdr_tf(value) per channel -- generate's exact functions; LINEAR is the identity; no HLG OOTF.  (An RGBA1010102
+ *      channel has 1024 values: the device reads the exact function's result from a table of them.)
+ *   3. white = 10000 for PQ, else 1000;  k = white / 203.0f;  cap = k
+ *   4. the image's headroom H.  Given (hdr_peak_nits[i] > 0):  H = fminf(fmaxf(hdr_peak_nits[i] / 203.0f, 1.0f), cap).
+ *      Measured (hdr_peak_nits == NULL or hdr_peak_nits[i] == 0):  m' = the maximum over all pixels and the three channels of step 1's
+ *      clamped value -- for RGBA1010102 an integer maximum of the codes, converted once --,
+ *      H = fminf(fmaxf(invOETF(m') * k, 1.0f), cap): uhdr_hip_tonemap_headroom states the rule for both operators
+ *   5. extended Reinhard on the maximum channel: v = lin * k; M = max(v.r, v.g, v.b); s = M > 0 ? (1 + M / (H * H)) / (1 + M) : 1;
+ *      o = clamp(v * s, 0, 1)
+ *   6. e = sRGB OETF(o) per channel: o <= 0.0031308f ? 12.92f * o : 1.055f * powf(o, 1 / 2.4f) - 0.055f
+ *   7. R, G, B = (uint8)CLIP3(e * 255.0f + 0.5f, 0, 255) per channel, A = 0xFF
+ * The destination: dest->data, rows dest->luma_stride pixels apart (0 = width; the caller's, in pixels), 4-byte aligned.  The columns
+ * [width, stride) are NOT written.  The call sets dest->width / height to the source's, dest->luma_stride to the stride used,
+ * dest->pixelFormat = RGBA8888 and dest->colorGamut = src->colorGamut: the SDR image keeps the HDR gamut, as API-0's does.  Step 2 is
+ * bit-exact; the steps behind it run on the f32 units.  A pixel holding a non-finite half: its own output is unspecified, a measured
+ * H is then unspecified within [1, cap]; nothing outside the destination is written, and nothing faults.
+ *
+ * n images in DEVICE memory.  The call only enqueues kernels on `stream` -- no allocation, no copy, no host synchronisation; it can be
+ * captured into a graph on any stream, nothing needs reserving -- and H never visits the host: the slots are set, the measuring
+ * pass reduces m' of the measured images into them, one small launch turns m' into H, the last pass writes the pixels.  Images of
+ * equal size that follow each other share launches (grid.z = image, up to 32).
+ *   tonemap_op     UHDR_HIP_TONEMAP_REINHARD_MAXRGB; UHDR_HIP_TONEMAP_SHIFT has no meaning for these formats
+ *   hdr_peak_nits  HOST, n floats, or NULL (every headroom measured)
+ *   headroom       DEVICE, n floats, required: image i's H
+ * Checks, in this order, all before any launch (a failing call writes nothing):
+ *   BAD_PTR              n < 0, or a NULL hdr_images / dests where n > 0
+ *   UNSUPPORTED_FEATURE  (every image) a pixelFormat other than RGBA1010102 / RGBA_F16, or one that differs from hdr_images[0]'s
+ *   BAD_PTR              (every image) a NULL data on either side; source data not 4-byte aligned (RGBA_F16: 8-byte), destination data
+ *                        not 4-byte aligned
+ *   INVALID_TRANS_FUNC   RGBA_F16 with anything but LINEAR, RGBA1010102 with anything but HLG / PQ; n == 0: hdr_tf none of the three
+ *   UNSUPPORTED_FEATURE  a tonemap_op other than REINHARD_MAXRGB; a negative or non-finite hdr_peak_nits[i]
+ *   BAD_PTR              a NULL headroom where n > 0
+ *   then per image       INVALID_STRIDE (on either side a luma_stride below the width, or above 2^32 - 1); INVALID_COLORGAMUT */
+int uhdr_hip_tonemap_packed_batch(int n, const uhdr_hip_image_t* hdr_images, uhdr_hip_image_t* dests, int hdr_tf, int tonemap_op,
+                                  const float* hdr_peak_nits, float* headroom, void* stream);
+/* One image in mem_space (host pixels are staged; only the pixels come back, the host destination's padding columns stay as they
+ * are; nothing is asked of a host pointer's alignment); waits for `stream` in either memory space and returns H to the host
+ * (headroom: HOST, optional).  BAD_PTR for a NULL hdr_image or dest, then the batch call's checks for n = 1. */
+int uhdr_hip_tonemap_packed(const uhdr_hip_image_t* hdr_image, uhdr_hip_image_t* dest, int hdr_tf, int tonemap_op, float hdr_peak_nits,
+                            float* headroom, int mem_space, void* stream);
+/* JPEG/R files from packed HDR images alone: uhdr_hip_jpegr_encode_packed_batch without sdr_images.  Per round of up to 64 files the
+ * SDR images are uhdr_hip_tonemap_packed_batch's, written into a pool slot of the round's codec context (rows at a 64-byte pitch;
+ * the headroom array is a pool slot too); everything behind that is uhdr_hip_jpegr_encode_packed_batch's own: the generate with
+ * metadata_in == NULL, the RGBA8888 -> 4:2:0 primary with the ICC profile of the HDR image's gamut, the 2 m compressions behind one
+ * synchronisation, the container.  A file equals, byte for byte, what uhdr_hip_jpegr_encode_packed_batch writes for the same HDR image
+ * and the RGBA8888 image uhdr_hip_tonemap_packed_batch derives from it.
+ *   metadata       HOST, n entries, optional: what every processed file's container carries
+ *   hdr_peak_nits  HOST, n floats, or NULL
+ * Checks: call-level BAD_PTR and INVALID_QUALITY_FACTOR as uhdr_hip_jpegr_encode_packed_batch, then UNSUPPORTED_FEATURE for a
+ * tonemap_op other than REINHARD_MAXRGB; per file that call's HDR-side checks in their order (the SDR-side ones fall away), then
+ * UNSUPPORTED_FEATURE for a negative or non-finite hdr_peak_nits[i], which fails that file alone. */
+int uhdr_hip_jpegr_encode_packed_api0_batch(int n, const uhdr_hip_image_t* hdr_images, int hdr_tf, int quality, const void* const* exif,
+                                            const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
+                                            uhdr_hip_metadata_t* metadata, int* status, int tonemap_op, const float* hdr_peak_nits,
+                                            int rgb_map, int mem_space, void* stream);
+
 /* ---- introspection for tests -------------------------------------------------------------- */
 /* copies the 4 Shepard IDW weight tables (standard, no-right, no-bottom, corner; each
  * scale*scale*4 floats; gainmapmath.h:184-228) the apply kernels use for `scale` into out[] */

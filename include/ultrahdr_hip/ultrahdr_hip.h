@@ -126,6 +126,12 @@ class UltraHdrHip {
 status_t toneMapSdr(uhdr_uncompressed_ptr src, uhdr_uncompressed_ptr dest, ultrahdr_transfer_function hdr_tf, int tonemap_op,
                     float hdr_peak_nits = 0.0f, float* headroom = nullptr);
 
+// The same operator on a packed HDR image (uhdr_hip_tonemap_packed): an ULTRAHDR_PIX_FMT_RGBA1010102 (HLG / PQ) or
+// ULTRAHDR_PIX_FMT_RGBAF16 (linear) image in host memory becomes an ULTRAHDR_PIX_FMT_RGBA8888 one in dest->data (the caller's,
+// rows dest->luma_stride pixels apart, 0 = width; the padding columns are left alone).  dest comes back described.
+status_t toneMapPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_uncompressed_ptr dest, ultrahdr_transfer_function hdr_tf,
+                       float hdr_peak_nits = 0.0f, float* headroom = nullptr);
+
 // generateGainMap from a packed RGBA pair in DEVICE memory (uhdr_hip_generate_gainmap_packed_batch; no reference counterpart), on HIP
 // device 0: an ULTRAHDR_PIX_FMT_RGBA8888 SDR image and an ULTRAHDR_PIX_FMT_RGBA1010102 (HLG / PQ) or ULTRAHDR_PIX_FMT_RGBAF16 (linear)
 // HDR image, strides in pixels.  dest->data is the caller's device buffer -- (width / 4) * (height / 4) bytes, four times that
@@ -244,6 +250,11 @@ class JpegRHip {
   // and setToneMap do not apply.
   status_t encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_uncompressed_ptr sdr_image_ptr, ultrahdr_transfer_function hdr_tf,
                              uhdr_compressed_ptr dest, int quality, uhdr_exif_ptr exif);
+  // The packed API-0 (include/uhdr_hip.h, "tone-mapped SDR image from a packed HDR image"): the HDR image alone; the SDR image is
+  // tone-mapped from it on the device (uhdr_hip_jpegr_encode_packed_api0_batch).  Honours setMultiChannelGainMap and the
+  // hdr_peak_nits given to setToneMap (0, the default, measures the headroom); the operator is always REINHARD_MAXRGB.
+  status_t encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, ultrahdr_transfer_function hdr_tf, uhdr_compressed_ptr dest, int quality,
+                             uhdr_exif_ptr exif);
   // (:213) dest->data, exif->data and gainmap_image_ptr->data are caller-allocated, as in the reference
   status_t decodeJPEGR(uhdr_compressed_ptr jpegr_image_ptr, uhdr_uncompressed_ptr dest, float max_display_boost = 3.4028234663852886e38f,
                        uhdr_exif_ptr exif = nullptr, ultrahdr_output_format output_format = ULTRAHDR_OUTPUT_HDR_LINEAR,

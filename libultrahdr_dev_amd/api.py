@@ -189,6 +189,11 @@ SIGNATURES = {
     "uhdr_hip_jpegr_encode_api0_tonemapped_batch": (C.c_int, [C.c_int, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                               C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _MP,
                                                               C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p]),
+    "uhdr_hip_tonemap_packed_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "uhdr_hip_tonemap_packed": (C.c_int, [_IP, _IP, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "uhdr_hip_jpegr_encode_packed_api0_batch": (C.c_int, [C.c_int, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                          C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _MP,
+                                                          C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p]),
 }
 
 _lib = None

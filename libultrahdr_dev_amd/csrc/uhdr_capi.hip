@@ -53,6 +53,7 @@ struct DeviceState : StageSet {
   bool ready = false;
   std::map<int, float*> idw;  // scale -> device tables (4 * scale*scale*4 floats)
   float* lut = nullptr;       // the five static transfer-function tables (kLutTotal floats), built at init
+  float* tone_tab = nullptr;  // the packed tone-map's inverse OETFs of the 1024 codes, HLG then PQ (2 * kTonePackedCodes floats), built at init
   std::vector<std::unique_ptr<StageSet>> sets;   // every set ever leased ...
   std::vector<StageSet*> free_sets;              // ... and those not in use (both under g_mu)
   std::vector<std::pair<hipStream_t, void*>> retired;   // workspaces that were outgrown while a launch may still have named them, by stream
@@ -940,6 +941,8 @@ int uhdr_hip_init(int device) {
       HIP_TRY(hipMemcpy(st.lut + kTabS1Lin, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     HIP_TRY(launch_build_lut_codes(st.lut, nullptr));
+    HIP_TRY(hipMalloc(&st.tone_tab, sizeof(float) * 2 * kTonePackedCodes));
+    HIP_TRY(launch_build_packed_tone_tables(st.tone_tab, nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
     HIP_TRY(jpeg::upload_tables());
     st.ready = true;
@@ -1219,6 +1222,7 @@ int uhdr_hip_shutdown(void) {
     (void)hipDeviceSynchronize();
     for (auto& t : kv.second.idw) (void)hipFree(t.second);
     if (kv.second.lut) (void)hipFree(kv.second.lut);
+    if (kv.second.tone_tab) (void)hipFree(kv.second.tone_tab);
     for (void* q : kv.second.pool) if (q) (void)hipFree(q);
     for (auto& w : kv.second.stat_ws) if (w.second) (void)hipFree(w.second);
     for (auto& w : kv.second.ex_ws) if (w.second.p) (void)hipFree(w.second.p);
@@ -2925,13 +2929,14 @@ int uhdr_hip_jpegr_encode_rgbmap_batch(int n, const uhdr_hip_image_t* p010_image
 // JPEG/R files from packed RGBA pairs: API-1's checks where they apply, then those of
 // uhdr_hip_generate_gainmap_packed_batch; per round one generate call (equal files share its launches), one k_rgba_to_ycc420 launch
 // for the primaries and the 2 m compressions behind one synchronisation, as in encode_files
-int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf, int quality,
-                                       const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
-                                       size_t* out_size, int* status, int rgb_map, int mem_space, void* stream) {
-  if (n < 0 || (n > 0 && (hdr_images == nullptr || sdr_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (exif != nullptr && exif_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+// sdr_images == NULL: the packed API-0 -- the SDR side of the checks falls away, a file's SDR image is
+// uhdr_hip_tonemap_packed_batch's in a pool slot of the round's context (peaks: one per file, or NULL), in the HDR image's gamut;
+// metadata (or NULL) receives what every processed file's container carries
+static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf, int quality,
+                               const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                               size_t* out_size, int* status, int rgb_map, int mem_space, void* stream, uhdr_hip_metadata_t* metadata,
+                               const float* peaks) {
+  const bool api0 = sdr_images == nullptr;
   const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
   auto stride_bad = [](const uhdr_hip_image_t& im) { return im.luma_stride != 0 && (im.luma_stride < im.width || im.luma_stride > 0xFFFFFFFFull); };
   auto check = [&](const uhdr_hip_image_t& hd, const uhdr_hip_image_t& sd, int i) -> int {
@@ -2942,17 +2947,20 @@ int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images
     if (stride_bad(hd)) return UHDR_HIP_ERROR_INVALID_STRIDE;
     if (out[i] == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
     if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
-    if (sd.data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-    if (stride_bad(sd)) return UHDR_HIP_ERROR_INVALID_STRIDE;
-    if (hd.width != sd.width || hd.height != sd.height) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
-    if (!valid_gamut(sd.colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+    if (!api0) {
+      if (sd.data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+      if (stride_bad(sd)) return UHDR_HIP_ERROR_INVALID_STRIDE;
+      if (hd.width != sd.width || hd.height != sd.height) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
+      if (!valid_gamut(sd.colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+    }
     if (exif != nullptr && exif[i] == nullptr && exif_size[i] != 0) return UHDR_HIP_ERROR_BAD_PTR;
     // uhdr_hip_generate_gainmap_packed_batch's own
-    if (sd.pixelFormat != UHDR_HIP_PIX_FMT_RGBA8888) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+    if (!api0 && sd.pixelFormat != UHDR_HIP_PIX_FMT_RGBA8888) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     if (hd.pixelFormat != UHDR_HIP_PIX_FMT_RGBA1010102 && hd.pixelFormat != UHDR_HIP_PIX_FMT_RGBA_F16) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     const bool f16 = hd.pixelFormat == UHDR_HIP_PIX_FMT_RGBA_F16;
-    if (!host && (!al(sd.data, 4) || !al(hd.data, f16 ? 8 : 4))) return UHDR_HIP_ERROR_BAD_PTR;
+    if (!host && ((!api0 && !al(sd.data, 4)) || !al(hd.data, f16 ? 8 : 4))) return UHDR_HIP_ERROR_BAD_PTR;
     if (f16 ? hdr_tf != UHDR_HIP_TF_LINEAR : hdr_tf == UHDR_HIP_TF_LINEAR) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+    if (api0 && peaks != nullptr && !valid_peak_nits(peaks[i])) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     return UHDR_HIP_NO_ERROR;
   };
   struct PackedFile {
@@ -2963,8 +2971,11 @@ int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
   std::vector<PackedFile> files;
   for (int i = 0; i < n; ++i) {
-    if ((st_[i] = check(hdr_images[i], sdr_images[i], i)) != UHDR_HIP_NO_ERROR) continue;
-    PackedFile f{i, hdr_images[i], sdr_images[i], {}};
+    if ((st_[i] = check(hdr_images[i], api0 ? hdr_images[i] : sdr_images[i], i)) != UHDR_HIP_NO_ERROR) continue;
+    PackedFile f{i, hdr_images[i], api0 ? hdr_images[i] : sdr_images[i], {}};
+    if (api0) {   // the SDR image to come: the HDR image's size and gamut, rows of its own in the round's pool
+      f.sdr.data = nullptr; f.sdr.luma_stride = 0; f.sdr.pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
+    }
     if (f.hdr.luma_stride == 0) f.hdr.luma_stride = f.hdr.width;
     if (f.sdr.luma_stride == 0) f.sdr.luma_stride = f.sdr.width;
     if (!jpegr::icc_profile_srgb_transfer(f.sdr.colorGamut, f.icc)) { st_[i] = UHDR_HIP_ERROR_INVALID_COLORGAMUT; continue; }
@@ -2986,8 +2997,10 @@ int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images
         for (int k = 0; k < m; ++k) {
           const size_t w = f[k].sdr.width, h = f[k].sdr.height;
           map_total += al256((w / 4) * (h / 4) * map_bpp + 64);
-          if (host) { sdr_total += al256(round_up(w * 4, 64) * h); hdr_total += al256(round_up(w * hdr_bpp, 64) * h); }
+          if (host || api0) sdr_total += al256(round_up(w * 4, 64) * h);
+          if (host) hdr_total += al256(round_up(w * hdr_bpp, 64) * h);
         }
+        if (api0 && (rc = pool_reserve(st, kEncToneHead, sizeof(float) * (size_t)m)) != 0) return rc;
         if ((rc = pool_reserve(st, kEncMap, map_total)) != 0) return rc;
         if (sdr_total && (rc = pool_reserve(st, kEncYuv, sdr_total)) != 0) return rc;
         if (hdr_total && (rc = pool_reserve(st, kEncP010, hdr_total)) != 0) return rc;
@@ -3000,16 +3013,27 @@ int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images
             const size_t sp = round_up(w * 4, 64), hp = round_up(w * hdr_bpp, 64);
             uint8_t* ds = static_cast<uint8_t*>(st->pool[kEncYuv]) + o_sdr;
             uint8_t* dh = static_cast<uint8_t*>(st->pool[kEncP010]) + o_hdr;
-            if ((rc = h2d_plane(ds, sp, e.sdr.data, e.sdr.luma_stride * 4, w * 4, h, 1, s)) != 0) return rc;
+            if (!api0 && (rc = h2d_plane(ds, sp, e.sdr.data, e.sdr.luma_stride * 4, w * 4, h, 1, s)) != 0) return rc;
             if ((rc = h2d_plane(dh, hp, e.hdr.data, e.hdr.luma_stride * hdr_bpp, w * hdr_bpp, h, 1, s)) != 0) return rc;
             o_sdr += al256(sp * h); o_hdr += al256(hp * h);
             e.sdr.data = ds; e.sdr.luma_stride = sp / 4;
             e.hdr.data = dh; e.hdr.luma_stride = hp / hdr_bpp;
+          } else if (api0) {
+            const size_t sp = round_up(w * 4, 64);
+            e.sdr.data = static_cast<uint8_t*>(st->pool[kEncYuv]) + o_sdr; e.sdr.luma_stride = sp / 4;
+            o_sdr += al256(sp * h);
           }
           a[(size_t)k] = e.sdr; b[(size_t)k] = e.hdr;
           memset(&c[(size_t)k], 0, sizeof(uhdr_hip_image_t));
           c[(size_t)k].data = static_cast<uint8_t*>(st->pool[kEncMap]) + o_map;
           o_map += al256((w / 4) * (h / 4) * map_bpp + 64);
+        }
+        if (api0) {   // the SDR images, H in a pool slot
+          std::vector<float> pk((size_t)m, 0.0f);
+          for (int k = 0; peaks != nullptr && k < m; ++k) pk[(size_t)k] = peaks[f[k].idx];
+          if ((rc = uhdr_hip_tonemap_packed_batch(m, b.data(), a.data(), hdr_tf, UHDR_HIP_TONEMAP_REINHARD_MAXRGB, pk.data(),
+                                                  static_cast<float*>(st->pool[kEncToneHead]), s)) != UHDR_HIP_NO_ERROR)
+            return rc;
         }
         uhdr_hip_metadata_t md;
         if ((rc = uhdr_hip_generate_gainmap_packed_batch(m, a.data(), b.data(), hdr_tf, nullptr, &md, c.data(), rgb_map, s)) != UHDR_HIP_NO_ERROR) return rc;
@@ -3029,6 +3053,7 @@ int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images
             const EncJpeg& gm = jpg[2 * (size_t)k + 1];
             st_[i] = jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
                                               nullptr, 0, md, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i], false);
+            if (metadata != nullptr) metadata[i] = md;
           }
         });
         return (int)UHDR_HIP_NO_ERROR;
@@ -3036,6 +3061,33 @@ int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images
       &done);
   for (size_t k = done; k < files.size(); ++k) st_[files[k].idx] = rc;   // the files of the failed round and of those behind it
   return finish_statuses(st_, status);
+}
+
+int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf, int quality,
+                                       const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                       size_t* out_size, int* status, int rgb_map, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (hdr_images == nullptr || sdr_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  // (n == 0 with sdr_images == NULL: no file, so nothing distinguishes the two forms)
+  static const uhdr_hip_image_t none{};
+  return encode_packed_files(n, hdr_images, sdr_images != nullptr ? sdr_images : &none, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size,
+                             status, rgb_map, mem_space, stream, nullptr, nullptr);
+}
+
+// the packed API-0: the same files from the HDR images alone
+int uhdr_hip_jpegr_encode_packed_api0_batch(int n, const uhdr_hip_image_t* hdr_images, int hdr_tf, int quality, const void* const* exif,
+                                            const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
+                                            uhdr_hip_metadata_t* metadata, int* status, int tonemap_op, const float* hdr_peak_nits, int rgb_map,
+                                            int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (hdr_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  if (tonemap_op != UHDR_HIP_TONEMAP_REINHARD_MAXRGB) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return encode_packed_files(n, hdr_images, nullptr, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, rgb_map, mem_space,
+                             stream, metadata, hdr_peak_nits);
 }
 
 int uhdr_hip_jpegr_encode_adaptive_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf,
@@ -4475,6 +4527,159 @@ int uhdr_hip_tonemap_sdr(const uhdr_hip_image_t* src, uhdr_hip_image_t* dest, in
   HIP_TRY(hipMemcpyAsync(&h_out, dh, sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   dest->colorGamut = src->colorGamut;
+  if (headroom) *headroom = h_out;
+  return UHDR_HIP_NO_ERROR;
+}
+
+// ---- the same operator on packed HDR images (include/uhdr_hip.h) ----------------------------------------
+namespace {
+size_t packed_stride(const uhdr_hip_image_t& im, size_t width) { return im.luma_stride == 0 ? width : im.luma_stride; }
+// uhdr_hip_tonemap_packed_batch's checks behind its array pointers, in the header's order; host: the images lie in host memory,
+// where nothing is asked of their alignment.  need_headroom: a NULL headroom is BAD_PTR where n > 0
+int tone_packed_check(int n, const uhdr_hip_image_t* srcs, const uhdr_hip_image_t* dests, int hdr_tf, int tonemap_op, const float* peaks,
+                      bool need_headroom, const float* headroom, bool host) {
+  for (int i = 0; i < n; ++i) {
+    if (srcs[i].pixelFormat != UHDR_HIP_PIX_FMT_RGBA1010102 && srcs[i].pixelFormat != UHDR_HIP_PIX_FMT_RGBA_F16) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+    if (srcs[i].pixelFormat != srcs[0].pixelFormat) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  }
+  const bool f16 = n > 0 && srcs[0].pixelFormat == UHDR_HIP_PIX_FMT_RGBA_F16;
+  for (int i = 0; i < n; ++i) {
+    if (srcs[i].data == nullptr || dests[i].data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+    if (!host && (!al(srcs[i].data, f16 ? 8 : 4) || !al(dests[i].data, 4))) return UHDR_HIP_ERROR_BAD_PTR;
+  }
+  if (n > 0 ? (f16 ? hdr_tf != UHDR_HIP_TF_LINEAR : (hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ))
+            : (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ))
+    return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (tonemap_op != UHDR_HIP_TONEMAP_REINHARD_MAXRGB) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;   // (TONEMAP_SHIFT means nothing here)
+  for (int i = 0; peaks != nullptr && i < n; ++i)
+    if (!valid_peak_nits(peaks[i])) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (need_headroom && n > 0 && headroom == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  for (int i = 0; i < n; ++i) {
+    const size_t ss = packed_stride(srcs[i], srcs[i].width), ds = packed_stride(dests[i], srcs[i].width);
+    if (ss < srcs[i].width || ds < srcs[i].width || ss > 0xFFFFFFFFull || ds > 0xFFFFFFFFull) return UHDR_HIP_ERROR_INVALID_STRIDE;
+    if (!valid_gamut(srcs[i].colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+void fill_tone_packed_dest(const uhdr_hip_image_t& src, uhdr_hip_image_t* dest) {
+  dest->luma_stride = packed_stride(*dest, src.width);
+  dest->width = src.width;
+  dest->height = src.height;
+  dest->colorGamut = src.colorGamut;
+  dest->pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
+}
+}  // namespace
+
+// n images in device memory: uhdr_hip_tonemap_sdr_batch's four steps with the packed kernels in the two passes
+int uhdr_hip_tonemap_packed_batch(int n, const uhdr_hip_image_t* srcs, uhdr_hip_image_t* dests, int hdr_tf, int tonemap_op,
+                                  const float* hdr_peak_nits, float* headroom, void* stream) {
+  if (n < 0 || (n > 0 && (srcs == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
+  int rc = tone_packed_check(n, srcs, dests, hdr_tf, tonemap_op, hdr_peak_nits, true, headroom, false);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool f16 = n > 0 && srcs[0].pixelFormat == UHDR_HIP_PIX_FMT_RGBA_F16;
+  const float k = adaptive_cap(hdr_tf);
+  auto given = [&](int i) { return hdr_peak_nits != nullptr && hdr_peak_nits[i] > 0.0f; };
+  auto head_init = [&](int base, ToneHeadInit* v) {
+    const int cnt = std::min(n - base, kToneHeadChunk);
+    for (int j = 0; j < cnt; ++j) v->h[j] = given(base + j) ? tone_headroom(hdr_tf, 0.0f, hdr_peak_nits[base + j]) : 0.0f;
+    return cnt;
+  };
+  for (int base = 0; base < n; base += kToneHeadChunk) {
+    ToneHeadInit v;
+    const int cnt = head_init(base, &v);
+    HIP_TRY(launch_tonemap_head_init(headroom + base, v, cnt, s));
+  }
+  // the runs of images that share launches: equal size and alignment class
+  auto run_at = [&](int i, TonePackedBatch* b, bool* aligned) {
+    int m = 0;
+    while (i + m < n && m < kToneChunk) {
+      const uhdr_hip_image_t& sd = srcs[i + m];
+      TonePackedImage t;
+      t.src = sd.data;
+      t.dst = static_cast<uint32_t*>(dests[i + m].data);
+      t.src_stride = (uint32_t)packed_stride(sd, sd.width);
+      t.dst_stride = (uint32_t)packed_stride(dests[i + m], sd.width);
+      t.width = (uint32_t)sd.width; t.height = (uint32_t)sd.height;
+      // 16-byte pieces of the destination (4 pixels) and what they are made of (RGBA1010102: 16 bytes, RGBA F16: 32)
+      const bool a = t.width % 4u == 0 && al(t.src, 16) && t.src_stride % (f16 ? 2u : 4u) == 0 && al(t.dst, 16) && t.dst_stride % 4u == 0;
+      if (m == 0) *aligned = a;
+      else if (a != *aligned || t.width != b->img[0].width || t.height != b->img[0].height) break;
+      b->img[m++] = t;
+    }
+    b->headroom = headroom;
+    b->table = f16 ? nullptr : st->tone_tab + (hdr_tf == UHDR_HIP_TF_PQ ? kTonePackedCodes : 0u);
+    b->k = k;
+    for (int j = 0; j < kToneChunk; ++j) b->slot[j] = 0u;
+    return m;
+  };
+  bool any_measured = false;
+  for (int i = 0; i < n;) {   // pass 1
+    TonePackedBatch b, mb;
+    bool aligned = true;
+    const int m = run_at(i, &b, &aligned);
+    mb = b;
+    int cnt = 0;
+    for (int j = 0; j < m; ++j)
+      if (!given(i + j)) { mb.img[cnt] = b.img[j]; mb.slot[cnt++] = (uint32_t)(i + j); }
+    if (cnt) {
+      any_measured = true;
+      HIP_TRY(launch_tonemap_packed_peak(mb, cnt, f16, aligned, s));
+    }
+    i += m;
+  }
+  for (int base = 0; any_measured && base < n; base += kToneHeadChunk) {
+    ToneHeadInit v;
+    const int cnt = head_init(base, &v);
+    HIP_TRY(launch_tonemap_head_finish(headroom + base, v, cnt, hdr_tf, k, k, s));
+  }
+  for (int i = 0; i < n;) {   // pass 2
+    TonePackedBatch b;
+    bool aligned = true;
+    const int m = run_at(i, &b, &aligned);
+    for (int j = 0; j < m; ++j) b.slot[j] = (uint32_t)(i + j);
+    HIP_TRY(launch_tonemap_packed(b, m, hdr_tf, aligned, s));
+    for (int j = 0; j < m; ++j) fill_tone_packed_dest(srcs[i + j], &dests[i + j]);
+    i += m;
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+
+int uhdr_hip_tonemap_packed(const uhdr_hip_image_t* src, uhdr_hip_image_t* dest, int hdr_tf, int tonemap_op, float hdr_peak_nits,
+                            float* headroom, int mem_space, void* stream) {
+  if (src == nullptr || dest == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
+  int rc = tone_packed_check(1, src, dest, hdr_tf, tonemap_op, &hdr_peak_nits, false, nullptr, host);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  StageLease lease(st);
+  StageSet* ss = lease.get();
+  if (ss == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  if ((rc = stage_reserve(ss, 4, 256)) != 0) return rc;
+  float* dh = static_cast<float*>(ss->stage[4]);
+  float h_out = 0.0f;
+  if (!host) {
+    if ((rc = uhdr_hip_tonemap_packed_batch(1, src, dest, hdr_tf, tonemap_op, &hdr_peak_nits, dh, stream)) != UHDR_HIP_NO_ERROR) return rc;
+  } else {   // rows of the pixels alone, at a 64-byte pitch; only the pixels come back: the columns [width, stride) stay as they are
+    const size_t w = src->width, h = src->height, bpp = src->pixelFormat == UHDR_HIP_PIX_FMT_RGBA_F16 ? 8 : 4;
+    const size_t sp = round_up(w * bpp, 64), dp = round_up(w * 4, 64);
+    if ((rc = stage_reserve(ss, 2, sp * h)) != 0) return rc;
+    if ((rc = stage_reserve(ss, 0, dp * h)) != 0) return rc;
+    if ((rc = h2d_plane(ss->stage[2], sp, src->data, packed_stride(*src, w) * bpp, w * bpp, h, 1, s)) != 0) return rc;
+    uhdr_hip_image_t sd = *src, dd = *dest;
+    sd.data = ss->stage[2]; sd.luma_stride = sp / bpp;
+    dd.data = ss->stage[0]; dd.luma_stride = dp / 4;
+    if ((rc = uhdr_hip_tonemap_packed_batch(1, &sd, &dd, hdr_tf, tonemap_op, &hdr_peak_nits, dh, stream)) != UHDR_HIP_NO_ERROR) return rc;
+    if (w * h)
+      HIP_TRY(hipMemcpy2DAsync(dest->data, packed_stride(*dest, w) * 4, dd.data, dp, w * 4, h, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(hipMemcpyAsync(&h_out, dh, sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (host) fill_tone_packed_dest(*src, dest);
   if (headroom) *headroom = h_out;
   return UHDR_HIP_NO_ERROR;
 }

@@ -290,6 +290,23 @@ struct PackedBatch {
   PackedImage img[kMaxChunk];
 };
 
+// ---- tone-mapped SDR image from a packed HDR image: what k_tonemap_packed[_peak] take ----
+struct TonePackedImage {   // strides in pixels
+  const void* src;         // RGBA1010102 (a dword per pixel) or RGBA F16 (8 bytes per pixel)
+  uint32_t* dst;           // RGBA8888
+  uint32_t src_stride, dst_stride, width, height;
+};
+struct TonePackedBatch {   // equally sized images of one alignment class; image z owns headroom[slot[z]]
+  TonePackedImage img[kToneChunk];
+  uint32_t slot[kToneChunk];
+  float* headroom;
+  const float* table;      // RGBA1010102: the transfer function's kTonePackedCodes inverse-OETF values (16-byte aligned)
+  float k;                 // hdr white / 203
+};
+constexpr uint32_t kTonePackedCodes = 1024;
+constexpr uint32_t kTonePackedPeakGroups = 128;   // the most workgroup rows (of 4 image rows) the measuring pass spends per image
+static_assert(sizeof(TonePackedBatch) <= 4096, "packed tone-map kernel arguments exceed the kernarg segment");
+
 static_assert(sizeof(GenConsts) + sizeof(GenMdConsts) + sizeof(GenBatch) <= 4096, "generate kernel arguments exceed the kernarg segment");
 static_assert(sizeof(GenConsts) + sizeof(GenMdConsts) + sizeof(PackedBatch) <= 4096, "generate kernel arguments exceed the kernarg segment");
 static_assert(sizeof(AppConsts) + sizeof(AppMdConsts) + sizeof(AppBatch) + 16 <= 4096, "apply kernel arguments exceed the kernarg segment");
@@ -351,6 +368,13 @@ hipError_t launch_tonemap_head_finish(float* headroom, const ToneHeadInit& v, in
 // ... and the planes of n <= kToneChunk images
 hipError_t launch_tonemap_sdr(const ToneSdrConsts& c, const ToneBatch& b, int n, int hdr_tf, bool aligned, hipStream_t s);
 static_assert(sizeof(ToneSdrConsts) + sizeof(ToneBatch) <= 4096 && sizeof(ToneHeadInit) + 64 <= 4096, "tone-map kernel arguments exceed the kernarg segment");
+// the same operator on packed HDR images.  tab: 2 * kTonePackedCodes floats, the HLG table, then the PQ one (built once per device) ...
+hipError_t launch_build_packed_tone_tables(float* tab, hipStream_t s);
+// ... pass 1 over the measured images (n <= kToneChunk of one size; f16: RGBA F16, otherwise RGBA1010102).  aligned: source and
+// destination rows start on 16 bytes and width % 4 == 0 ...
+hipError_t launch_tonemap_packed_peak(const TonePackedBatch& b, int n, bool f16, bool aligned, hipStream_t s);
+// ... and the pixels: hdr_tf 0 reads RGBA F16, 1 / 2 RGBA1010102 through b.table.  The slots are launch_tonemap_head_init / _finish's
+hipError_t launch_tonemap_packed(const TonePackedBatch& b, int n, int hdr_tf, bool aligned, hipStream_t s);
 // decoded 4:2:0 planes -> RGBA8888 with libjpeg-turbo's arithmetic; w, h even, strides in bytes: up to kRgbaChunk images of any
 // (even) sizes in one launch (k_ycc420_rgba_batch: grid.z = image)
 constexpr int kRgbaChunk = 64;

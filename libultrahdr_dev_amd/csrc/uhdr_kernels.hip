@@ -8,6 +8,7 @@
 //   k_apply_px_md, k_generate_md   gain maps with gamma, offsets and an HDR capacity range (no reference counterpart)
 //   k_generate_packed        gain maps from packed RGBA pairs: RGBA8888 with RGBA1010102 or RGBA F16 (no reference counterpart)
 //   k_tonemap_*              UltraHdr::toneMap                    (:517-558)
+//   k_tonemap_packed[_peak]  the tone-mapped SDR image of a packed HDR image: RGBA1010102 / RGBA F16 -> RGBA8888 (no reference counterpart)
 //   k_convert_yuv<ALIGNED>   JpegR::convertYuv + transformYuv420  (lib/src/jpegr.cpp:1199-1203,
 //                                                                  lib/src/gainmapmath.cpp:483-520)
 //   k_effect, k_effect_rot   crop / mirror / rotate / resize      (lib/src/editorhelper.cpp:26-360)
@@ -3661,6 +3662,175 @@ hipError_t launch_tonemap_sdr(const ToneSdrConsts& c, const ToneBatch& b, int n,
   else if (hdr_tf == 2) UHDR_TONE_SDR(2);
   else UHDR_TONE_SDR(0);
 #undef UHDR_TONE_SDR
+  return hipGetLastError();
+}
+
+// =================================================================================================
+// Tone-mapped SDR image from a packed HDR image (no reference counterpart): RGBA1010102 / RGBA F16 ->
+// linear light -> the operator of k_tonemap_sdr (extended Reinhard on the maximum channel against H, sRGB OETF) -> RGBA8888.
+//   k_build_packed_tone_tables  once per device: generate's exact inverse OETFs of the 1024 codes, HLG then PQ
+//   k_tonemap_packed_peak       measured images only: the maximum of the clamped pixel values into the image's headroom slot
+//   k_tonemap_packed            the pixels; an RGBA1010102 channel is linearised by one LDS read of the block's copy of the table
+// k_tonemap_head_init / k_tonemap_head_finish serve both operators unchanged.  A block is 64 x 4 threads: a wave walks along one
+// row (ALIGNED: a lane owns a 16-byte piece of the destination, 4 pixels; otherwise one pixel), the block's rows stride by the grid.
+// =================================================================================================
+__global__ void __launch_bounds__(256) k_build_packed_tone_tables(float* tab) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;   // 2 x 1024 entries
+  const float e = (float)(i & 1023u) * k1023;
+  tab[i] = (i < 1024u) ? hdr_inv_oetf<1>(e) : hdr_inv_oetf<2>(e);
+}
+hipError_t launch_build_packed_tone_tables(float* tab, hipStream_t s) {
+  hipLaunchKernelGGL(k_build_packed_tone_tables, dim3(2u * kTonePackedCodes / 256u), dim3(256), 0, s, tab);
+  return hipGetLastError();
+}
+
+// step 1's clamp: -0, negative and NaN halves give 0, halves above 1.0 (infinity included) give 1
+__device__ __forceinline__ float clamp01_nan(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
+__device__ __forceinline__ uint32_t max_code10(uint32_t p) { return max(p & 0x3ffu, max((p >> 10) & 0x3ffu, (p >> 20) & 0x3ffu)); }
+__device__ __forceinline__ float max_half3(uint32_t rg, uint32_t ba) {
+  return fmaxf(clamp01_nan(half_lo(rg)), fmaxf(clamp01_nan(half_hi(rg)), clamp01_nan(half_lo(ba))));
+}
+
+// grid.x: the lanes' columns, grid.y: groups of 4 rows (strided), grid.z: image.  RGBA1010102: an integer maximum of the codes,
+// converted once.  The hand-over is k_tonemap_peak's: one atomicMax per workgroup on the bit pattern of a non-negative float.
+template <bool F16, bool ALIGNED>
+__global__ void __launch_bounds__(256) k_tonemap_packed_peak(const TonePackedBatch b) {
+  const TonePackedImage& t = b.img[blockIdx.z];
+  const uint32_t col = blockIdx.x * 64u + threadIdx.x, cols = ALIGNED ? t.width / 4u : t.width;
+  const uint32_t step = gridDim.y * 4u;
+  uint32_t mc = 0u;
+  float m = 0.0f;
+  if (col < cols) {
+    for (uint32_t y = blockIdx.y * 4u + threadIdx.y; y < t.height; y += step) {   // plain loads: see k_tonemap_peak
+      if (F16) {
+        const uint2* row = static_cast<const uint2*>(t.src) + (size_t)y * t.src_stride;
+        if (ALIGNED) {
+          const uint4 a = *reinterpret_cast<const uint4*>(row + 4u * col), c = *reinterpret_cast<const uint4*>(row + 4u * col + 2u);
+          m = fmaxf(fmaxf(m, fmaxf(max_half3(a.x, a.y), max_half3(a.z, a.w))), fmaxf(max_half3(c.x, c.y), max_half3(c.z, c.w)));
+        } else {
+          const uint2 p = row[col];
+          m = fmaxf(m, max_half3(p.x, p.y));
+        }
+      } else {
+        const uint32_t* row = static_cast<const uint32_t*>(t.src) + (size_t)y * t.src_stride;
+        if (ALIGNED) {
+          const uint4 a = *reinterpret_cast<const uint4*>(row + 4u * col);
+          mc = max(max(mc, max(max_code10(a.x), max_code10(a.y))), max(max_code10(a.z), max_code10(a.w)));
+        } else {
+          mc = max(mc, max_code10(row[col]));
+        }
+      }
+      if (t.height - y <= step) break;   // (y + step may not wrap)
+    }
+  }
+  if (!F16) m = (float)mc * k1023;
+  __shared__ float s_part[4];
+  m = wave_extreme<true>(m);   // (all 64 lanes are active here)
+  if (threadIdx.x == 0u) s_part[threadIdx.y] = m;
+  __syncthreads();
+  if (threadIdx.x == 0u && threadIdx.y == 0u) {
+    const uint32_t key = __float_as_uint(fmaxf(fmaxf(s_part[0], s_part[1]), fmaxf(s_part[2], s_part[3])));
+    uint32_t* slot = reinterpret_cast<uint32_t*>(b.headroom + b.slot[blockIdx.z]);
+    if (__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < key) atomicMax(slot, key);
+  }
+}
+
+// steps 3 and 5 of the operator on one pixel's linear channels: k_tonemap_sdr's arithmetic (tone_block), then the bytes
+__device__ __forceinline__ uint32_t tone_packed_pixel(float r, float g, float bl, float k, float ihh) {
+  const float vr = r * k, vg = g * k, vb = bl * k;
+  const float M = fmaxf(vr, fmaxf(vg, vb));
+  const float s = (M > 0.0f) ? (1.0f + M * ihh) * __builtin_amdgcn_rcpf(1.0f + M) : 1.0f;
+  const uint32_t R = round_u8(srgb_oetf_fast(clamp01(vr * s)) * 255.0f + 0.5f);
+  const uint32_t G = round_u8(srgb_oetf_fast(clamp01(vg * s)) * 255.0f + 0.5f);
+  const uint32_t B = round_u8(srgb_oetf_fast(clamp01(vb * s)) * 255.0f + 0.5f);
+  return R | (G << 8) | (B << 16) | 0xFF000000u;
+}
+__device__ __forceinline__ uint32_t tone_packed_1010102(const float* s_tab, uint32_t p, float k, float ihh) {
+  return tone_packed_pixel(s_tab[p & 0x3ffu], s_tab[(p >> 10) & 0x3ffu], s_tab[(p >> 20) & 0x3ffu], k, ihh);
+}
+__device__ __forceinline__ uint32_t tone_packed_f16(uint32_t rg, uint32_t ba, float k, float ihh) {
+  return tone_packed_pixel(clamp01_nan(half_lo(rg)), clamp01_nan(half_hi(rg)), clamp01_nan(half_lo(ba)), k, ihh);
+}
+
+// ALIGNED: width % 4 == 0, source and destination rows start on 16 bytes.  The columns [width, dst_stride) are not written.
+template <int TF, bool F16, bool ALIGNED>
+__global__ void __launch_bounds__(256) k_tonemap_packed(const TonePackedBatch b) {
+  static_assert(F16 ? TF == 0 : TF != 0, "F16 is linear light, RGBA1010102 carries HLG or PQ");
+  __shared__ float s_tab[F16 ? 4 : kTonePackedCodes];
+  if (!F16) {   // 256 threads x 16 bytes: the whole table
+    const uint32_t tid = threadIdx.y * 64u + threadIdx.x;
+    reinterpret_cast<uint4*>(s_tab)[tid] = reinterpret_cast<const uint4*>(b.table)[tid];
+    __syncthreads();
+  }
+  const TonePackedImage& t = b.img[blockIdx.z];
+  const uint32_t col = blockIdx.x * 64u + threadIdx.x, cols = ALIGNED ? t.width / 4u : t.width;
+  if (col >= cols) return;
+  const float H = b.headroom[b.slot[blockIdx.z]];   // (wave-uniform: scalar loads)
+  const float ihh = 1.0f / (H * H), k = b.k;
+  const uint32_t step = gridDim.y * 4u;
+  for (uint32_t y = blockIdx.y * 4u + threadIdx.y; y < t.height; y += step) {
+    uint32_t* drow = t.dst + (size_t)y * t.dst_stride;
+    if (F16) {
+      const uint2* row = static_cast<const uint2*>(t.src) + (size_t)y * t.src_stride;
+      if (ALIGNED) {
+        const uint4 a = ld_stream(reinterpret_cast<const uint4*>(row + 4u * col)), c = ld_stream(reinterpret_cast<const uint4*>(row + 4u * col + 2u));
+        st_stream(reinterpret_cast<uint4*>(drow + 4u * col), make_uint4(tone_packed_f16(a.x, a.y, k, ihh), tone_packed_f16(a.z, a.w, k, ihh),
+                                                                         tone_packed_f16(c.x, c.y, k, ihh), tone_packed_f16(c.z, c.w, k, ihh)));
+      } else {
+        const uint2 p = ld_stream(row + col);
+        drow[col] = tone_packed_f16(p.x, p.y, k, ihh);
+      }
+    } else {
+      const uint32_t* row = static_cast<const uint32_t*>(t.src) + (size_t)y * t.src_stride;
+      if (ALIGNED) {
+        const uint4 a = ld_stream(reinterpret_cast<const uint4*>(row + 4u * col));
+        st_stream(reinterpret_cast<uint4*>(drow + 4u * col), make_uint4(tone_packed_1010102(s_tab, a.x, k, ihh), tone_packed_1010102(s_tab, a.y, k, ihh),
+                                                                         tone_packed_1010102(s_tab, a.z, k, ihh), tone_packed_1010102(s_tab, a.w, k, ihh)));
+      } else {
+        drow[col] = tone_packed_1010102(s_tab, ld_stream(row + col), k, ihh);
+      }
+    }
+    if (t.height - y <= step) break;   // (y + step may not wrap)
+  }
+}
+
+// lanes across the row, groups of 4 rows down: about `blocks` workgroups per launch, between lo and hi groups per image
+static dim3 tone_packed_grid(const TonePackedBatch& b, int n, bool aligned, uint32_t blocks, uint32_t lo, uint32_t hi) {
+  const TonePackedImage& t = b.img[0];
+  const uint32_t gx = ((aligned ? t.width / 4u : t.width) + 63u) / 64u, groups = (t.height + 3u) / 4u;
+  return dim3(gx, std::min(groups, std::min(std::max(blocks / (gx * (uint32_t)n), lo), hi)), (unsigned)n);
+}
+hipError_t launch_tonemap_packed_peak(const TonePackedBatch& b, int n, bool f16, bool aligned, hipStream_t s) {
+  const TonePackedImage& t = b.img[0];
+  if (n <= 0 || t.width == 0u || t.height == 0u) return hipSuccess;
+  if (n > kToneChunk) return hipErrorInvalidValue;
+  // one atomic per workgroup: no more than kTonePackedPeakGroups workgroup rows per image (1080 rows are 270 groups: strided)
+  const dim3 grid = tone_packed_grid(b, n, aligned, 4096u, 16u, kTonePackedPeakGroups), block(64, 4);
+  if (f16) {
+    if (aligned) hipLaunchKernelGGL((k_tonemap_packed_peak<true, true>), grid, block, 0, s, b);
+    else hipLaunchKernelGGL((k_tonemap_packed_peak<true, false>), grid, block, 0, s, b);
+  } else {
+    if (aligned) hipLaunchKernelGGL((k_tonemap_packed_peak<false, true>), grid, block, 0, s, b);
+    else hipLaunchKernelGGL((k_tonemap_packed_peak<false, false>), grid, block, 0, s, b);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_tonemap_packed(const TonePackedBatch& b, int n, int hdr_tf, bool aligned, hipStream_t s) {
+  const TonePackedImage& t = b.img[0];
+  if (n <= 0 || t.width == 0u || t.height == 0u) return hipSuccess;
+  if (n > kToneChunk || hdr_tf < 0 || hdr_tf > 2) return hipErrorInvalidValue;
+  // every block copies the 4 KiB table first: enough rows per block to make that small beside its pixels
+  const dim3 grid = tone_packed_grid(b, n, aligned, 2048u, 16u, 1024u), block(64, 4);
+  if (hdr_tf == 1) {
+    if (aligned) hipLaunchKernelGGL((k_tonemap_packed<1, false, true>), grid, block, 0, s, b);
+    else hipLaunchKernelGGL((k_tonemap_packed<1, false, false>), grid, block, 0, s, b);
+  } else if (hdr_tf == 2) {
+    if (aligned) hipLaunchKernelGGL((k_tonemap_packed<2, false, true>), grid, block, 0, s, b);
+    else hipLaunchKernelGGL((k_tonemap_packed<2, false, false>), grid, block, 0, s, b);
+  } else {
+    if (aligned) hipLaunchKernelGGL((k_tonemap_packed<0, true, true>), grid, block, 0, s, b);
+    else hipLaunchKernelGGL((k_tonemap_packed<0, true, false>), grid, block, 0, s, b);
+  }
   return hipGetLastError();
 }
 

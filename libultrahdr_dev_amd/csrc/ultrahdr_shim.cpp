@@ -403,6 +403,34 @@ status_t JpegRHip::encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_u
   });
 }
 
+status_t JpegRHip::encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, ultrahdr_transfer_function hdr_tf, uhdr_compressed_ptr dest, int quality,
+                                     uhdr_exif_ptr exif) {
+  if (hdr_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
+  const uhdr_hip_image_t h = to_c_packed(*hdr_image_ptr);
+  return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
+    const void* ex = exif_ptr(exif);
+    const size_t exn = exif_len(exif);
+    return uhdr_hip_jpegr_encode_packed_api0_batch(1, &h, (int)hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, nullptr,
+                                                   UHDR_HIP_TONEMAP_REINHARD_MAXRGB, &mHdrPeakNits, mMultiChannelGainMap ? 1 : 0, UHDR_HIP_MEM_HOST,
+                                                   nullptr);
+  });
+}
+
+status_t toneMapPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_uncompressed_ptr dest, ultrahdr_transfer_function hdr_tf, float hdr_peak_nits,
+                       float* headroom) {
+  if (hdr_image_ptr == nullptr || dest == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
+  static const int init_rc = uhdr_hip_init(0);
+  const uhdr_hip_image_t h = to_c_packed(*hdr_image_ptr);
+  uhdr_hip_image_t d = to_c(*dest);
+  const int rc = uhdr_hip_tonemap_packed(&h, &d, static_cast<int>(hdr_tf), UHDR_HIP_TONEMAP_REINHARD_MAXRGB, hdr_peak_nits, headroom,
+                                         UHDR_HIP_MEM_HOST, nullptr);
+  if (rc == UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE && init_rc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(init_rc);
+  if (rc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(rc);
+  from_c(d, dest);
+  dest->pixelFormat = ULTRAHDR_PIX_FMT_RGBA8888;
+  return ULTRAHDR_NO_ERROR;
+}
+
 status_t generateGainMapPacked(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompressed_ptr hdr_image_ptr, ultrahdr_transfer_function hdr_tf,
                                ultrahdr_metadata_ptr metadata, uhdr_uncompressed_ptr dest, bool multi_channel, void* stream) {
   if (sdr_image_ptr == nullptr || hdr_image_ptr == nullptr || dest == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
