@@ -28,6 +28,11 @@ SHIM_DEPS = SHIM_SOURCES + [os.path.join(ROOT, "include", "uhdr_hip.h"),
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fno-fast-math", "-Wall", "-Wno-unused-function"]
+# Branches that a whole wave takes together stay branches.  By default the AMDGPU backend rewrites every if / else, wave-uniform
+# ones included, into "if (c) A; if (!c) B" with a path around both, and s_waitcnt is counted along that path too: behind
+# k_apply_s4's choice between the two forms of a cell it then assumed that no store had been issued, and every wait for the next
+# cell's inputs drained the stores of the cell just computed (tests/test_apply_walk_isa.py holds the counts).
+FLAGS += ["-mllvm", "-structurizecfg-skip-uniform-regions"]
 
 
 def _stale(target, deps, base):

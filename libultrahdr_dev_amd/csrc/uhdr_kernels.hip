@@ -1734,7 +1734,7 @@ __device__ __forceinline__ ChromaRow chroma_row(uint32_t uu, uint32_t vv) {
 }
 template <int FMT>
 __device__ __forceinline__ void apply_cell_piped(const AppConsts& c, void* dst, uint32_t cx, uint32_t cy,
-                                                 const uint32_t (&yrow)[4], const uint32_t (&uu)[2], const uint32_t (&vv)[2],
+                                                 const uint32_t (&yrow)[4], const uint16_t (&uu)[2], const uint16_t (&vv)[2],
                                                  float m1, float m2, float m3, float m4, uint32_t slot8, const char* lut) {
   typedef ApplyTab<FMT, false> T;
   // only the chroma row in use is kept as floats (the second row's six values are formed when rows 2 and 3 start): the cell runs
@@ -1817,8 +1817,9 @@ constexpr uint32_t kXchSecond = 72;    // in uint4: the second halves start 1152
 constexpr uint32_t kXchPerWave = 136;  // ... of 2176 bytes
 template <int FMT, bool MASK>
 __device__ __forceinline__ void apply_cell_piped1(const AppConsts& c, const AppImage& im, uint32_t cx, uint32_t cy,
-                                                  const uint32_t (&yrow)[4], const uint32_t (&uu)[2], const uint32_t (&vv)[2],
-                                                  float m1, float m2, float m3, float m4, const char* lut, uint4* xch) {
+                                                  const uint32_t (&yrow)[4], const uint16_t (&uu)[2], const uint16_t (&vv)[2],
+                                                  float m1, float m2, float m3, float m4, const char* lut, uint4* xch,
+                                                  bool via_xch /* wave-uniform: the branch on it must not mask lanes */) {
   ChromaRow cr = chroma_row(uu[0], vv[0]);
   const float a255 = c.fast.A255;
   // The four per-cell scalars of the exponent travel as two register PAIRS whose halves v_pk_fma_f32 broadcasts through op_sel: a
@@ -1875,7 +1876,7 @@ __device__ __forceinline__ void apply_cell_piped1(const AppConsts& c, const AppI
         } else if (FMT == 1) {
           const uint2 a = pack_f16_hw(po[0].r.x, po[0].g.x, po[0].b.x), bb = pack_f16_hw(po[0].r.y, po[0].g.y, po[0].b.y);
           const uint2 cc = pack_f16_hw(po[1].r.x, po[1].g.x, po[1].b.x), d = pack_f16_hw(po[1].r.y, po[1].g.y, po[1].b.y);
-          if (xch != nullptr) {
+          if (via_xch) {
             // A lane's row is 32 bytes: stored as it stands, every store instruction would fill half of each line it touches
             // (measured: 2.0 instead of 5.6 TB/s, scripts/ab/store_pattern).  The wave's 64 rows pass through LDS so that each of
             // the two instructions writes 1 KiB contiguous: lane L stores half (L & 1) of the row of lane L / 2 (then of lane
@@ -1937,18 +1938,27 @@ __device__ __forceinline__ void apply_load_cell(const AppConsts& c, const AppIma
 // in it is pipelined.
 template <int FMT, bool MASK>
 __device__ __forceinline__ void apply_cell_edge(const AppConsts& c, const AppImage& im, uint32_t cx, uint32_t cy,
-                                                const uint32_t (&yrow)[4], const uint32_t (&uu)[2], const uint32_t (&vv)[2],
+                                                const uint32_t (&yrow)[4], const uint16_t (&uu)[2], const uint16_t (&vv)[2],
                                                 float m1, float m2, float m3, float m4, const float* wt /* the lane's table, in LDS */,
                                                 uint32_t slot8, const char* lut) {
   typedef ApplyTab<FMT, MASK> T;
   const float a255 = c.fast.A255;
   const float base = __builtin_fmaf(m1, a255, c.fast.B), d2 = m2 - m1, d3 = m3 - m1, d4 = m4 - m1;
+  // The loop leaves the cell's rows in registers (its inputs are dead by then) and the stores follow it in straight-line code: a
+  // store inside the rolled loop is one the compiler cannot count at the loop's exit, and every wait behind it drained them all.
+  // A finished row enters at the top of the window and has moved down to its own place after the fourth.
+  constexpr int kW = FMT == 4 ? 3 : FMT == 1 ? 2 : 1;   // 16-byte (FMT 4: 8-byte) pieces per row
+  uint4 rows[4][kW];
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+#pragma unroll
+    for (int q = 0; q < kW; ++q) rows[r][q] = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll 1
   for (uint32_t oy = 0; oy < 4u; ++oy) {   // (uniform: the selects below are scalar)
     const uint32_t yw = oy == 0u ? yrow[0] : oy == 1u ? yrow[1] : oy == 2u ? yrow[2] : yrow[3];
     const ChromaRow cr = chroma_row(oy < 2u ? uu[0] : uu[1], oy < 2u ? vv[0] : vv[1]);
-    const uint32_t pix0 = (4u * cy + oy) * c.width + 4u * cx;  // < 2^27 pixels per image
     uint32_t px[4];
+    uint4 row[kW];
     PairOut po[2];
 #pragma unroll
     for (int pr = 0; pr < 2; ++pr) {
@@ -1995,28 +2005,44 @@ __device__ __forceinline__ void apply_cell_edge(const AppConsts& c, const AppIma
       }
     }
     if (T::kOetf) {
-      st_stream(reinterpret_cast<uint4*>(static_cast<uint32_t*>(im.dst) + pix0), make_uint4(px[0], px[1], px[2], px[3]));
+      row[0] = make_uint4(px[0], px[1], px[2], px[3]);
     } else if (FMT == 2 || FMT == 3) {
-      uint4 o;
-      o.x = pack10_scaled<MASK>(po[0].r.x, po[0].g.x, po[0].b.x); o.y = pack10_scaled<MASK>(po[0].r.y, po[0].g.y, po[0].b.y);
-      o.z = pack10_scaled<MASK>(po[1].r.x, po[1].g.x, po[1].b.x); o.w = pack10_scaled<MASK>(po[1].r.y, po[1].g.y, po[1].b.y);
-      st_stream(reinterpret_cast<uint4*>(static_cast<uint32_t*>(im.dst) + pix0), o);
+      row[0].x = pack10_scaled<MASK>(po[0].r.x, po[0].g.x, po[0].b.x); row[0].y = pack10_scaled<MASK>(po[0].r.y, po[0].g.y, po[0].b.y);
+      row[0].z = pack10_scaled<MASK>(po[1].r.x, po[1].g.x, po[1].b.x); row[0].w = pack10_scaled<MASK>(po[1].r.y, po[1].g.y, po[1].b.y);
     } else if (FMT == 1) {
       const uint2 a = pack_f16_hw(po[0].r.x, po[0].g.x, po[0].b.x), bb = pack_f16_hw(po[0].r.y, po[0].g.y, po[0].b.y);
       const uint2 cc = pack_f16_hw(po[1].r.x, po[1].g.x, po[1].b.x), d = pack_f16_hw(po[1].r.y, po[1].g.y, po[1].b.y);
-      uint4* o = reinterpret_cast<uint4*>(static_cast<uint2*>(im.dst) + pix0);
-      o[0] = make_uint4(a.x, a.y, bb.x, bb.y);
-      o[1] = make_uint4(cc.x, cc.y, d.x, d.y);
+      row[0] = make_uint4(a.x, a.y, bb.x, bb.y);
+      row[kW - 1] = make_uint4(cc.x, cc.y, d.x, d.y);
     } else {  // FMT == 4: planar R,G,B uint16 (ultrahdr.cpp:460-468)
-      const size_t plane = (size_t)c.width * c.height;
-      uint16_t* base16 = static_cast<uint16_t*>(im.dst);
       const f2 pl[3][2] = {{po[0].r, po[1].r}, {po[0].g, po[1].g}, {po[0].b, po[1].b}};
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
         const uint32_t q0 = 0x3ffu & (uint32_t)pl[p][0].x, q1 = 0x3ffu & (uint32_t)pl[p][0].y;
         const uint32_t q2 = 0x3ffu & (uint32_t)pl[p][1].x, q3 = 0x3ffu & (uint32_t)pl[p][1].y;
-        st_stream(reinterpret_cast<uint2*>(base16 + p * plane + pix0), make_uint2(q0 | (q1 << 16), q2 | (q3 << 16)));
+        row[p % kW] = make_uint4(q0 | (q1 << 16), q2 | (q3 << 16), 0u, 0u);
       }
+    }
+#pragma unroll
+    for (int q = 0; q < kW; ++q) { rows[0][q] = rows[1][q]; rows[1][q] = rows[2][q]; rows[2][q] = rows[3][q]; rows[3][q] = row[q]; }
+  }
+  // the same stores as the pipelined forms issue: a 32-bit byte offset on the image's base (app_fast_s4 keeps the image below 4 GiB)
+  char* const dst = static_cast<char*>(im.dst);
+  const uint32_t pix0 = 4u * cy * c.width + 4u * cx;  // < 2^27 pixels per image
+#pragma unroll
+  for (uint32_t oy = 0; oy < 4u; ++oy) {
+    const uint32_t pix = pix0 + oy * c.width;
+    if (FMT == 2 || FMT == 3) {
+      st_stream(reinterpret_cast<uint4*>(dst + pix * 4u), rows[oy][0]);
+    } else if (FMT == 1) {
+      uint4* o = reinterpret_cast<uint4*>(dst + pix * 8u);
+      o[0] = rows[oy][0];
+      o[1] = rows[oy][kW - 1];
+    } else {
+      const uint32_t plane2 = c.width * c.height * 2u;
+#pragma unroll
+      for (int p = 0; p < 3; ++p)
+        st_stream(reinterpret_cast<uint2*>(dst + (p * plane2 + pix * 2u)), make_uint2(rows[oy][p % kW].x, rows[oy][p % kW].y));
     }
   }
 }
@@ -2025,7 +2051,9 @@ __device__ __forceinline__ void apply_cell_edge(const AppConsts& c, const AppIma
 // computed, so every dword counts against the 128 registers of four waves per SIMD): the two taps of a map row arrive as ONE
 // 16-bit load, mrow[j] = the bytes (mx, mx + 1) of map row cy (j = 0) / cy1 (j = 1).  The loads are unaligned half the time; global
 // memory takes that.  Needs map_w >= 2 (launch_apply_t).
-struct ApplyCellPk { uint32_t yrow[4], uu[2], vv[2], mrow[2]; };
+// The 16-bit words stay 16-bit values: as dwords the compiler widened the set that travels round the loop's back edge there, six
+// v_and behind six waits, although every use reads bytes 0 and 1 only.
+struct ApplyCellPk { uint32_t yrow[4]; uint16_t uu[2], vv[2], mrow[2]; };
 struct __attribute__((packed)) U16Any { uint16_t v; };
 // (mx < map_w - 1: the column of the byte pairs; cy1: the row of the lower taps)
 __device__ __forceinline__ void apply_load_cell_pk(const AppConsts& c, const AppImage& im, uint32_t cx, uint32_t cy, uint32_t mx, uint32_t cy1, ApplyCellPk& o) {
@@ -2076,8 +2104,12 @@ __device__ __forceinline__ bool apply_walk_cell(const AppConsts& c, const AppIma
   uint32_t ncx = cx + c.step_x, ncy = cy + c.step_y;
   if (ncx >= c.map_w) { ncx -= c.map_w; ++ncy; }
   --left;
-  const bool more = left != 0u && ncy < c.map_h;
-  if (!more) { ncx = cx; ncy = cy; }
+  // The wave goes on while any of its lanes has a next cell; a lane without one stays where it is and computes its cell again,
+  // storing the same bytes to the same addresses (only in the ragged wave at an image's end).  So no lane is ever masked in the
+  // loop and the compiler has one path, with one sequence of memory instructions, to count along.
+  const bool mine = left != 0u && ncy < c.map_h;
+  const bool more = __builtin_amdgcn_ballot_w64(mine) != 0ull;
+  if (!mine) { ncx = cx; ncy = cy; }
   // In the last column sampleMap's right tap IS the left one (gainmapmath.cpp:690-703, xu == xl): the two bytes are loaded one
   // column to the left, the right tap is byte 1 either way, the left tap byte 0 -- or byte 1 in the last column.
   apply_load_cell_pk(c, im, ncx, ncy, ncx - (ncx + 1u == c.map_w ? 1u : 0u), min(ncy + 1u, c.map_h - 1u), nxt);
@@ -2091,12 +2123,13 @@ __device__ __forceinline__ bool apply_walk_cell(const AppConsts& c, const AppIma
     if (interior) apply_cell_piped<FMT>(c, im.dst, cx, cy, cur.yrow, cur.uu, cur.vv, e1, e2, e3, e4, slot8, lut);
     else apply_cell_edge<FMT, MASK>(c, im, cx, cy, cur.yrow, cur.uu, cur.vv, e1, e2, e3, e4, wt, slot8, lut);
   } else {
-    // F16: a full wave on one row of cells stores through the exchange area (apply_cell_piped1)
-    uint4* xch = nullptr;
-    if (FMT == 1 && __builtin_amdgcn_ballot_w64(true) == ~0ull &&
-        __builtin_amdgcn_ballot_w64(cy != (uint32_t)__builtin_amdgcn_readfirstlane((int)cy)) == 0ull)
-      xch = s_xch + (threadIdx.x >> 6) * kXchPerWave;
-    if (interior) apply_cell_piped1<FMT, MASK>(c, im, cx, cy, cur.yrow, cur.uu, cur.vv, e1, e2, e3, e4, lut, xch);
+    // F16: a full wave on 64 consecutive cells of one row stores through the exchange area (apply_cell_piped1); lanes that repeat
+    // their cell beside lanes that went on break the sequence of columns, also where all of them are on the last row
+    uint4* const xch = s_xch + (FMT == 1 ? (threadIdx.x >> 6) * kXchPerWave : 0u);
+    const bool via_xch = FMT == 1 && __builtin_amdgcn_ballot_w64(true) == ~0ull &&
+        __builtin_amdgcn_ballot_w64(cy != (uint32_t)__builtin_amdgcn_readfirstlane((int)cy) ||
+                                    cx != (uint32_t)__builtin_amdgcn_readfirstlane((int)cx) + (threadIdx.x & 63u)) == 0ull;
+    if (interior) apply_cell_piped1<FMT, MASK>(c, im, cx, cy, cur.yrow, cur.uu, cur.vv, e1, e2, e3, e4, lut, xch, via_xch);
     else apply_cell_edge<FMT, MASK>(c, im, cx, cy, cur.yrow, cur.uu, cur.vv, e1, e2, e3, e4, wt, slot8, lut);
   }
   cx = ncx; cy = ncy;
@@ -2136,6 +2169,13 @@ __global__ void __launch_bounds__(kApplyBlock, 4) k_apply_s4(const AppConsts c, 
     for (uint32_t k = 0; k < kPer1; ++k) { const uint32_t i = k * kApplyBlock + threadIdx.x; if (i < kN1) s_tab[i] = t1[k]; }
 #pragma unroll
     for (uint32_t k = 0; k < kPer2; ++k) { const uint32_t i = k * kApplyBlock + threadIdx.x; if (i < kN2) reinterpret_cast<uint2*>(s_tab)[T::kS2Base / 8u + i] = t2[k]; }
+    // The last pieces are stored by some lanes only, and behind such a branch the compiler counts their loads as still in flight:
+    // into the walk's loop, where every write to one of these registers then waited for stores (seen in the ISA: vmcnt(11) and
+    // vmcnt(10) in the first cell of each pair).  An unconditional use ends that here.
+#pragma unroll
+    for (uint32_t k = 0; k < kPer1; ++k) asm volatile("" :: "v"(t1[k].w));
+#pragma unroll
+    for (uint32_t k = 0; k < kPer2; ++k) asm volatile("" :: "v"(t2[k].y));
   }
   __syncthreads();
   const char* lut = reinterpret_cast<const char*>(s_tab);
