@@ -809,6 +809,49 @@ int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images
                                        const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
                                        size_t* out_size, int* status, int rgb_map, int mem_space, void* stream);
 
+/* ---- gain maps at any scale factor (no reference counterpart; current libultrahdr: uhdr_enc_set_gainmap_scale_factor) ------
+ * The apply and decode calls read maps at any integer factor; every generate call above writes them at the reference's
+ * kMapDimensionScaleFactor, 4.  This call takes the factor s = map_scale_factor, 1 .. 128.  Device memory, asynchronous on `stream`: it
+ * only enqueues kernels -- no allocation, copy or host synchronisation, so it can be captured into a graph.
+ *   map size       (width / s) x (height / s)
+ *   sampling       map pixel (x, y) is the reference's samplePixels (gainmapmath.cpp:605-615) at scale s, for both images: one running
+ *                  f32 sum per channel over the s x s block, dy outer and dx inner, of getYuv420Pixel / getP010Pixel values with their
+ *                  own roundings -- y * (1/255.0f), (u - 128) * (1/255.0f), (y10 - 64) * (1/876.0f), (u10 - 64) * (1/896.0f) - 0.5f;
+ *                  the chroma sample of a pixel is the one at (x/2, y/2) -- then each sum / (float)(s*s), correctly rounded.  Columns
+ *                  and rows past s * (width / s), s * (height / s) are not read.
+ *   the rest       metadata_in == NULL, rgb == 0: uhdr_hip_generate_gainmap_batch's arithmetic (behind the same f32 pre-filter, bytes
+ *                  unchanged by it); metadata_in == NULL, rgb != 0: uhdr_hip_generate_gainmap_rgb_batch's; metadata_in != NULL:
+ *                  uhdr_hip_generate_gainmap_md_batch's rule, validation and gamma handling.
+ * metadata_out (optional) receives the metadata that was used.  dests[i].data needs (width / s) * (height / s) bytes, four times that
+ * with rgb != 0, and comes back described as the selected call describes it, with the new size.  With s == 4 the bytes are those
+ * three calls'.  There is no content_minmax.  Checks: those of the selected call in its order, and UNSUPPORTED_MAP_SCALE_FACTOR
+ *   - directly after the call-level BAD_PTR for s outside 1 .. 128,
+ *   - per image, after that image's other checks, when width / s == 0 or height / s == 0.
+ * A failing call writes nothing. */
+int uhdr_hip_generate_gainmap_scaled_batch(int n, const uhdr_hip_image_t* yuv420_images, const uhdr_hip_image_t* p010_images, int hdr_tf,
+                                           const uhdr_hip_metadata_t* metadata_in, uhdr_hip_metadata_t* metadata_out,
+                                           uhdr_hip_image_t* dests, int sdr_is_601, int rgb, int map_scale_factor, void* stream);
+/* Measurement only: the call above with metadata_in == NULL, rgb == 0 (the filtered kernel), counting.  *doubt_count -- one device
+ * word, cleared by the caller -- grows by the number of map pixels the f32 pre-filter left to the exact path; the maps are the call's.
+ * BAD_PTR for a NULL doubt_count, UNSUPPORTED_FEATURE for s == 4 (that kernel keeps lists of its own, uhdr_hip_generate_probe), then
+ * the call's checks. */
+int uhdr_hip_generate_gainmap_scaled_probe(int n, const uhdr_hip_image_t* yuv420_images, const uhdr_hip_image_t* p010_images, int hdr_tf,
+                                           uhdr_hip_image_t* dests, int sdr_is_601, int map_scale_factor, uint32_t* doubt_count,
+                                           void* stream);
+/* uhdr_hip_jpegr_encode_batch (rgb_map == 0) or uhdr_hip_jpegr_encode_rgbmap_batch (rgb_map != 0) -- API-1, or API-0 when
+ * yuv420_images == NULL -- with the gain map at s = map_scale_factor: the generate step is the call above with metadata_in == NULL;
+ * the map is compressed at quality 85 as those calls compress theirs; primary image, ICC, XMP, MPF, container, per-file status rules
+ * and the one synchronisation per round are unchanged.  With s == 4 the call IS the existing one, checks and bytes included.
+ * Otherwise: call-level UNSUPPORTED_MAP_SCALE_FACTOR for s outside 1 .. 128, after INVALID_QUALITY_FACTOR; per file, behind API-1's own
+ * checks, UNSUPPORTED_WIDTH_HEIGHT when width % s != 0 or height % s != 0 -- every reader, uhdr_hip_apply_gainmap_batch included,
+ * refuses a map whose size does not divide the image's.  A round's map pool grows with the maps (up to 16 times a factor-4 map's
+ * bytes at s = 1, 64 times with rgb_map); a round whose pool cannot be had fails as a whole, it is never truncated.  Read the files
+ * with uhdr_hip_jpegr_decode_batch / uhdr_hip_jpegr_decode_rgbmap_batch. */
+int uhdr_hip_jpegr_encode_scaled_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf,
+                                       int quality, const void* const* exif, const size_t* exif_size, void* const* out,
+                                       const size_t* out_capacity, size_t* out_size, int* status, int rgb_map, int map_scale_factor,
+                                       int mem_space, void* stream);
+
 /* ---- content-adaptive gain maps (no reference counterpart) ---------------------------------
  * The reference encodes every map against minContentBoost = 1, maxContentBoost = hdr_white / 203 (ultrahdr.cpp:250-257): 255 codes
  * over 2.3 stops (HLG, LINEAR) or 5.6 stops (PQ) whatever the picture holds, gains below 1 clipped.  The adaptive calls encode

@@ -140,6 +140,14 @@ status_t toneMapPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_uncompressed_pt
 status_t generateGainMapPacked(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompressed_ptr hdr_image_ptr, ultrahdr_transfer_function hdr_tf,
                                ultrahdr_metadata_ptr metadata, uhdr_uncompressed_ptr dest, bool multi_channel = false, void* stream = nullptr);
 
+// generateGainMap at the scale factor map_scale_factor, 1 .. 128, from a planar pair in DEVICE memory
+// (uhdr_hip_generate_gainmap_scaled_batch; the reference's factor is 4), on HIP device 0.  dest->data is the caller's device buffer --
+// (width / s) * (height / s) bytes, four times that (4-byte aligned, RGBA) with multi_channel; the call only enqueues on `stream`.
+// *metadata (optional) receives the reference's constants for hdr_tf, which the map is encoded against.
+status_t generateGainMapScaled(uhdr_uncompressed_ptr yuv420_image_ptr, uhdr_uncompressed_ptr p010_image_ptr, ultrahdr_transfer_function hdr_tf,
+                               ultrahdr_metadata_ptr metadata, uhdr_uncompressed_ptr dest, int map_scale_factor, bool multi_channel = false,
+                               bool sdr_is_601 = false, void* stream = nullptr);
+
 // The weight W of the gain-map exponent and the divisor d = min(max_display_boost, hdrCapacityMax) that a decode with
 // JpegRHip::setAnyGainMapMetadata forms for this metadata (uhdr_hip_gainmap_weight; host code, no device needed)
 status_t gainMapWeight(ultrahdr_metadata_ptr metadata, float max_display_boost, float* weight, float* display_boost);
@@ -278,6 +286,12 @@ class JpegRHip {
   // which are single-channel) and decodeJPEGR applies a three-component gain map per channel
   // (uhdr_hip_jpegr_decode_rgbmap_batch; files with one-plane maps decode as ever).  The other encodeJPEGR overloads are unchanged.
   void setMultiChannelGainMap(bool on) { mMultiChannelGainMap = on; }
+  // 4 (default): the reference's kMapDimensionScaleFactor.  Any other factor, 1 .. 128: the API-0 and API-1 overloads write the gain
+  // map at that factor (uhdr_hip_jpegr_encode_scaled_batch; it combines with setMultiChannelGainMap; an image the factor does not
+  // divide is ERROR_ULTRAHDR_UNSUPPORTED_WIDTH_HEIGHT).  Every other way of generating a map -- API-2, API-3, encodeJPEGRPacked, the
+  // setToneMap operator, setContentBoost -- then answers ERROR_ULTRAHDR_UNSUPPORTED_FEATURE instead of silently writing a factor-4 map.
+  // decodeJPEGR reads every factor as it is.
+  void setGainMapScaleFactor(int map_scale_factor) { mGainMapScaleFactor = map_scale_factor; }
   // false (default): decodeJPEGR refuses, as the reference does, every file whose metadata has a gamma other than 1, an offset
   // other than 0 or an HDR capacity range other than the content boost range (ERROR_ULTRAHDR_BAD_METADATA).  true: such files --
   // what current libultrahdr, cameras and editors write -- are decoded with the full gain-map formula, one- and three-component
@@ -292,6 +306,7 @@ class JpegRHip {
   bool mDecodeAnySampling = false;
   bool mMultiChannelGainMap = false;
   bool mAnyGainMapMetadata = false;
+  int mGainMapScaleFactor = 4;
 };
 
 }  // namespace ultrahdr

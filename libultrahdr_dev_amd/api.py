@@ -101,6 +101,11 @@ SIGNATURES = {
     "uhdr_hip_jpegr_decode_md_batch": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_float, C.POINTER(C.c_void_p),
                                                  C.POINTER(C.c_size_t), _IP, _MP, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "uhdr_hip_generate_gainmap_packed_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _MP, _MP, _IP, C.c_int, C.c_void_p]),
+    "uhdr_hip_generate_gainmap_scaled_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _MP, _MP, _IP, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "uhdr_hip_generate_gainmap_scaled_probe": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _IP, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "uhdr_hip_jpegr_encode_scaled_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                     C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int,
+                                                     C.c_int, C.c_int, C.c_void_p]),
     "uhdr_hip_jpeg_encode_rgba420_batch": (C.c_int, [C.c_int, _IP, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
                                                      C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     "uhdr_hip_jpegr_encode_packed_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),

@@ -2602,14 +2602,15 @@ EncJpeg gainmap_rgb_jpeg(uhdr_hip_image_t map) {
 // tonemap_op (API-0): the operator that derives the SDR planes; its headroom array is a pool slot of the context.
 int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_tf, int quality, EncFile* f, int m, uhdr_hip_metadata_t* md,
                  std::vector<EncJpeg>* jpg, int boost_scope = -1, float* range = nullptr, int carry = 0,
-                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, bool rgb_map = false) {
+                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, bool rgb_map = false, int map_scale = 4) {
+  const size_t msf = (size_t)map_scale;     // the map's factor: uhdr_hip_jpegr_encode_scaled_batch's, 4 in every other call
   const size_t map_bpp = rgb_map ? 4 : 1;   // rgb_map: uhdr_hip_generate_gainmap_rgb_batch's RGBA map, compressed as 4:4:4
   auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
   int rc;
   // sizes of the round's slices
   size_t sdr_total = 0, map_total = 0, p010_total = 0, yuv_total = 0;
   for (int k = 0; k < m; ++k) {
-    const size_t w = f[k].p010.width, h = f[k].p010.height, aw = (w + 15) / 16 * 16, mw = w / 4, mh = h / 4;
+    const size_t w = f[k].p010.width, h = f[k].p010.height, aw = (w + 15) / 16 * 16, mw = w / msf, mh = h / msf;
     if (host) {
       p010_total += al256(round_up(w, 64) * h * 2) + al256(round_up(w, 64) * (h / 2) * 2);
       if (!api0) yuv_total += al256(round_up(aw, 64) * h) + al256(round_up(aw, 64) * h);
@@ -2665,7 +2666,7 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
     if (api0) e.yuv = e.enc;
     e.map = e.yuv;
     e.map.data = static_cast<uint8_t*>(st->pool[kEncMap]) + o_map;
-    o_map += al256((w / 4) * (h / 4) * map_bpp + 64);
+    o_map += al256((w / msf) * (h / msf) * map_bpp + 64);
   }
   std::vector<uhdr_hip_image_t> a((size_t)m), b((size_t)m), c((size_t)m);
   if (api0) {   // :208-226
@@ -2682,7 +2683,10 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
   // generateGainMap: the files are sorted by size and gamuts, so equal ones share its launches
   for (int k = 0; k < m; ++k) { a[k] = f[k].yuv; b[k] = f[k].p010; c[k] = f[k].map; }
   float* dev_range = nullptr;
-  if (rgb_map) {
+  if (map_scale != 4) {   // (never with an adaptive range)
+    if ((rc = uhdr_hip_generate_gainmap_scaled_batch(m, a.data(), b.data(), hdr_tf, nullptr, md, c.data(), 0, rgb_map ? 1 : 0, map_scale, s)) != UHDR_HIP_NO_ERROR)
+      return rc;
+  } else if (rgb_map) {
     if ((rc = uhdr_hip_generate_gainmap_rgb_batch(m, a.data(), b.data(), hdr_tf, md, c.data(), 0, s)) != UHDR_HIP_NO_ERROR) return rc;
   } else if (boost_scope < 0) {
     if ((rc = uhdr_hip_generate_gainmap_batch(m, a.data(), b.data(), hdr_tf, md, c.data(), 0, nullptr, s)) != UHDR_HIP_NO_ERROR) return rc;
@@ -2721,7 +2725,7 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
   for (int k = 0; k < m; ++k) {
     const EncFile& e = f[k];
     uhdr_hip_image_t g = e.map;
-    g.width = e.enc.width / 4; g.height = e.enc.height / 4; g.luma_stride = g.width;
+    g.width = e.enc.width / msf; g.height = e.enc.height / msf; g.luma_stride = g.width;
     jpg->push_back(EncJpeg{e.enc, quality, &e.icc, e.pad_ls, e.pad_cs});
     jpg->push_back(rgb_map ? gainmap_rgb_jpeg(g) : gainmap_jpeg(g, g.luma_stride));
   }
@@ -2733,7 +2737,7 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
 int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
                  const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
                  int* status, int mem_space, void* stream, int boost_scope = -1, uhdr_hip_metadata_t* metadata = nullptr,
-                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, const float* hdr_peak_nits = nullptr, bool rgb_map = false) {
+                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, const float* hdr_peak_nits = nullptr, bool rgb_map = false, int map_scale = 4) {
   const bool api0 = yuv420_images == nullptr;
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
   std::vector<EncFile> files;
@@ -2744,6 +2748,10 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
     if (rc == UHDR_HIP_NO_ERROR && ex == nullptr && exn != 0) rc = UHDR_HIP_ERROR_BAD_PTR;                     // :190-193 / :258-261
     const float peak = tonemap_op != UHDR_HIP_TONEMAP_SHIFT && hdr_peak_nits ? hdr_peak_nits[i] : 0.0f;
     if (rc == UHDR_HIP_NO_ERROR && !valid_peak_nits(peak)) rc = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+    // a factor of the call's own: every reader refuses a map whose size does not divide the image's (validate_apply)
+    if (rc == UHDR_HIP_NO_ERROR && map_scale != 4 &&
+        (p010_images[i].width % (size_t)map_scale != 0 || p010_images[i].height % (size_t)map_scale != 0))
+      rc = UHDR_HIP_ERROR_UNSUPPORTED_WIDTH_HEIGHT;
     if (rc != UHDR_HIP_NO_ERROR) { st_[i] = rc; continue; }
     EncFile e;
     e.idx = i;
@@ -2793,7 +2801,7 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
         EncFile* f = &files[r0];
         uhdr_hip_metadata_t md;
         std::vector<EncJpeg> jpg;
-        if ((rc = encode_round(st, s, api0, host, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry, tonemap_op, rgb_map)) != UHDR_HIP_NO_ERROR)
+        if ((rc = encode_round(st, s, api0, host, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry, tonemap_op, rgb_map, map_scale)) != UHDR_HIP_NO_ERROR)
           return rc;
         std::vector<uhdr_hip_metadata_t> mds;   // adaptive: every file's own
         if (boost_scope < 0 && metadata)
@@ -2924,6 +2932,19 @@ int uhdr_hip_jpegr_encode_rgbmap_batch(int n, const uhdr_hip_image_t* p010_image
   if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
   return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, -1,
                       nullptr, UHDR_HIP_TONEMAP_SHIFT, nullptr, true);
+}
+
+// uhdr_hip_jpegr_encode_batch / _rgbmap_batch with the gain map at the call's factor; factor 4 IS those calls
+int uhdr_hip_jpegr_encode_scaled_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                                       const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                       size_t* out_size, int* status, int rgb_map, int map_scale_factor, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  if (map_scale_factor < 1 || map_scale_factor > 128) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
+  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, -1,
+                      nullptr, UHDR_HIP_TONEMAP_SHIFT, nullptr, rgb_map != 0, map_scale_factor);
 }
 
 // JPEG/R files from packed RGBA pairs: API-1's checks where they apply, then those of
@@ -4137,6 +4158,113 @@ int uhdr_hip_generate_gainmap_packed_batch(int n, const uhdr_hip_image_t* sdrs, 
     i += m;
   }
   return UHDR_HIP_NO_ERROR;
+}
+
+// Gain maps at any scale factor: the checks of the call whose arithmetic is selected, in its order, with the
+// factor's own behind the call-level BAD_PTR and behind every image's; factor 4 IS those calls; every chunk one k_generate_scaled launch
+// doubt_count: null, or the probe's device word
+static int generate_scaled(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf, const uhdr_hip_metadata_t* md_in,
+                           uhdr_hip_metadata_t* md_out, uhdr_hip_image_t* dests, int sdr_is_601, int rgb, int map_scale_factor, void* stream,
+                           uint32_t* doubt_count) {
+  if (n < 0 || (n > 0 && (yuvs == nullptr || p010s == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
+  if (map_scale_factor < 1 || map_scale_factor > 128) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
+  const size_t sf = (size_t)map_scale_factor;
+  int rc;
+  if (map_scale_factor == 4) {
+    uhdr_hip_metadata_t md;
+    if (md_in != nullptr) {
+      md = *md_in;
+      rc = uhdr_hip_generate_gainmap_md_batch(n, yuvs, p010s, hdr_tf, md_in, dests, sdr_is_601, rgb, stream);
+    } else if (rgb != 0) {
+      rc = uhdr_hip_generate_gainmap_rgb_batch(n, yuvs, p010s, hdr_tf, &md, dests, sdr_is_601, stream);
+    } else {
+      rc = uhdr_hip_generate_gainmap_batch(n, yuvs, p010s, hdr_tf, &md, dests, sdr_is_601, nullptr, stream);
+    }
+    if (rc == UHDR_HIP_NO_ERROR && md_out != nullptr) *md_out = md;
+    return rc;
+  }
+  const bool tf_known = hdr_tf == UHDR_HIP_TF_LINEAR || hdr_tf == UHDR_HIP_TF_HLG || hdr_tf == UHDR_HIP_TF_PQ;
+  auto too_small = [&](const uhdr_hip_image_t& y) { return y.width / sf == 0 || y.height / sf == 0; };
+  uhdr_hip_metadata_t md;
+  if (md_in != nullptr) {   // uhdr_hip_generate_gainmap_md_batch's order
+    for (int i = 0; i < n; ++i) {
+      if (yuvs[i].data == nullptr || yuvs[i].chroma_data == nullptr || p010s[i].data == nullptr || p010s[i].chroma_data == nullptr ||
+          dests[i].data == nullptr || (rgb != 0 && !al(dests[i].data, 4)))
+        return UHDR_HIP_ERROR_BAD_PTR;
+    }
+    if ((rc = validate_md(md_in)) != UHDR_HIP_NO_ERROR) return rc;
+    for (int i = 0; i < n; ++i) {
+      if ((rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, md_in, &dests[i])) != UHDR_HIP_NO_ERROR) return rc;
+      if (too_small(yuvs[i])) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
+    }
+    md = *md_in;
+  } else {                  // uhdr_hip_generate_gainmap_batch's / _rgb_batch's
+    for (int i = 0; i < n; ++i) {
+      if ((rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, &md, &dests[i])) != UHDR_HIP_NO_ERROR) return rc;
+      if (dests[i].data == nullptr || (rgb != 0 && !al(dests[i].data, 4))) return UHDR_HIP_ERROR_BAD_PTR;
+      if (too_small(yuvs[i])) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
+    }
+  }
+  if (!tf_known) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (md_in == nullptr) fill_generate_metadata(hdr_tf, &md);
+  if (md_out != nullptr) *md_out = md;
+  GenScaleConsts sc;
+  sc.s = (uint32_t)map_scale_factor;
+  sc.area = (float)(map_scale_factor * map_scale_factor);
+  sc.doubt_count = doubt_count;
+  const uint32_t strip = (sc.s == 1u || sc.s == 2u || sc.s == 8u) ? 8u / sc.s : 0u;   // map pixels a thread of the aligned forms stores at once
+  int i = 0;
+  while (i < n) {
+    // chunk = up to kMaxChunk consecutive images of identical size, gamuts and alignment class
+    const uhdr_hip_image_t& y0 = yuvs[i];
+    GenConsts c = generate_consts(y0.colorGamut, p010s[i].colorGamut, hdr_tf, sdr_is_601, y0.width, y0.height, md);
+    c.map_w = (uint32_t)(y0.width / sf);
+    c.map_h = (uint32_t)(y0.height / sf);
+    const GenMdConsts mc = generate_md_consts(md, c);
+    // the reference's metadata and one channel: the filtered kernel, where the filter's bounds hold (they start from the sampled values,
+    // so generate_consts' flt_* constants serve every factor)
+    const bool filter = md_in == nullptr && rgb == 0 && c.flt_delta < 0.25f && c.min_boost >= 0.25f && c.max_boost <= 64.0f;
+    const int mode = filter ? 0 : (rgb != 0 ? 2 : 1);
+    GenBatch b;
+    int m = 0;
+    bool aligned = true;
+    while (i + m < n && m < kMaxChunk) {
+      const uhdr_hip_image_t& y = yuvs[i + m];
+      if (y.width != y0.width || y.height != y0.height || y.colorGamut != y0.colorGamut ||
+          p010s[i + m].colorGamut != p010s[i].colorGamut)
+        break;
+      b.img[m] = gen_image(y, p010s[i + m], dests[i + m].data);
+      const bool a = strip != 0u && gen_aligned(b.img[m], c.width, c.height) && c.height % 2u == 0 &&
+                     al(b.img[m].map, (size_t)strip * (rgb != 0 ? 4u : 1u) > 8u ? 8u : (size_t)strip * (rgb != 0 ? 4u : 1u));
+      if (m == 0) aligned = a;
+      else if (a != aligned) break;
+      fill_generate_dest(&y, &dests[i + m]);
+      dests[i + m].width = c.map_w;
+      dests[i + m].height = c.map_h;
+      dests[i + m].luma_stride = c.map_w;
+      if (rgb != 0) dests[i + m].pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
+      ++m;
+    }
+    HIP_TRY(launch_generate_scaled(c, mc, sc, b, m, hdr_tf, aligned, mode, s));
+    i += m;
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+int uhdr_hip_generate_gainmap_scaled_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf,
+                                           const uhdr_hip_metadata_t* md_in, uhdr_hip_metadata_t* md_out, uhdr_hip_image_t* dests,
+                                           int sdr_is_601, int rgb, int map_scale_factor, void* stream) {
+  return generate_scaled(n, yuvs, p010s, hdr_tf, md_in, md_out, dests, sdr_is_601, rgb, map_scale_factor, stream, nullptr);
+}
+// the same call, counting: *doubt_count (a device word the caller has cleared) grows by the map pixels the f32 pre-filter left to the
+// exact path.  Only the filtered form counts (metadata_in == NULL, rgb == 0, a factor other than 4)
+int uhdr_hip_generate_gainmap_scaled_probe(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf,
+                                           uhdr_hip_image_t* dests, int sdr_is_601, int map_scale_factor, uint32_t* doubt_count, void* stream) {
+  if (doubt_count == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  if (map_scale_factor == 4) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return generate_scaled(n, yuvs, p010s, hdr_tf, nullptr, nullptr, dests, sdr_is_601, 0, map_scale_factor, stream, doubt_count);
 }
 
 // ---------------------------------------------------------------------------------------------------

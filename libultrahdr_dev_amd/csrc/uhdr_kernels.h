@@ -352,6 +352,19 @@ hipError_t launch_generate_md(const GenConsts& c, const GenMdConsts& m, const Ge
 // of 8 and the map is aligned as launch_generate_md's
 hipError_t launch_generate_packed(const GenConsts& c, const GenMdConsts& m, const PackedBatch& b, int n, int hdr_tf, bool f16, bool aligned,
                                   bool rgb, hipStream_t s);
+// gain maps at any scale factor for n <= kMaxChunk pairs of one size; c.map_w / c.map_h are width / s and
+// height / s.  mode 0: the single-channel map of the reference's metadata behind the f32 pre-filter (m is not read); 1: launch_generate_md's
+// one-plane map; 2: its RGBA map -- both on the exact path.  aligned: gen_aligned's conditions, an even height and a map whose strip
+// stores (8 / s map pixels) are aligned; it selects the 16-byte forms for s = 1, 2, 8 and is ignored for every other factor
+struct GenScaleConsts {
+  uint32_t s;      // the factor, 1 .. 128
+  float area;      // (float)(s * s)
+  uint32_t* doubt_count;   // null, or (uhdr_hip_generate_gainmap_scaled_probe) a device word: += the map pixels the filter left in doubt
+};
+constexpr int kScaledBlock = 256;   // threads per block of k_generate_scaled; a thread owns 8 / s map pixels (s = 1, 2, 8) or a pair
+static_assert(sizeof(GenConsts) + sizeof(GenMdConsts) + sizeof(GenScaleConsts) + sizeof(GenBatch) <= 4096, "generate kernel arguments exceed the kernarg segment");
+hipError_t launch_generate_scaled(const GenConsts& c, const GenMdConsts& m, const GenScaleConsts& sc, const GenBatch& b, int n, int hdr_tf,
+                                  bool aligned, int mode, hipStream_t s);
 hipError_t launch_build_luts(float* lut /* kLutTotal floats */, hipStream_t s);
 hipError_t launch_build_lut_codes(float* lut /* the whole buffer: reads the two OETF tables, writes kCodeHlg / kCodePq */, hipStream_t s);
 // GainLUT table (kGainLutN floats, device) for (log2 min, log2 max, boost factor)

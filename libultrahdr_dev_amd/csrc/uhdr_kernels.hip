@@ -1406,6 +1406,289 @@ hipError_t launch_generate_packed(const GenConsts& c, const GenMdConsts& m, cons
   }
 }
 
+// =================================================================================================
+// Gain maps at any scale factor (uhdr_hip_generate_gainmap_scaled_batch)
+// =================================================================================================
+// samplePixels (gainmapmath.cpp:605-615) at scale s: one running f32 sum per channel over the s x s block, dy outer and dx inner, of
+// getYuv420Pixel / getP010Pixel values (every product its own rounding; the chroma sample of a pixel is the one at (x/2, y/2)), divided
+// by (float)(s*s).  Everything behind the six sampled values is gen_pair's: the kernels here only sample.
+//   S = 1, 2, 8 (aligned inputs): a thread owns a strip of 8 luma columns and S rows -- 8, 4 or 1 map pixels -- and moves per row one
+//       16-byte piece of P010 luma, 8 bytes of 8-bit luma and, per chroma row, 16 bytes of P010 chroma and 4 bytes of U and of V,
+//       with the non-temporal helpers.  Dividing by S*S is an exact multiply.
+//   S = 0: a thread owns a pair of map pixels at the run-time factor GenScaleConsts::s and sums from single loads straight into its
+//       running registers: every other factor (odd ones included, where a block straddles chroma samples) and every layout the
+//       aligned form does not take.  The division is the correctly rounded f32 one.
+// MODE 0: the single-channel map of the reference's metadata behind gen_pair's f32 pre-filter.  Pixels in doubt are resolved COMPACTED:
+//       the thread that finds one appends its six sampled values and its place in the wave's tile to the wave's list in LDS; when the
+//       wave's pixels are through the filter, consecutive lanes run the exact path over the entries, two per lane as gen_pair takes
+//       them, and hand the bytes back through LDS to the owners, which then store their pixels once.  The list holds every pixel of
+//       the wave's tile (an all-black SDR frame puts every pixel in doubt): there is no overflow path.  Waves never wait for each other.
+// MODE 1 / 2: the exact path throughout and k_generate_md's rule -- one plane, or RGBA per channel.
+__device__ __forceinline__ float yuv8_luma(uint32_t y) { return (float)y * k255; }                          // gainmapmath.cpp:579
+__device__ __forceinline__ float yuv8_chroma(uint32_t u) { return (float)((int)u - 128) * k255; }           // :580
+__device__ __forceinline__ float p010_y(uint32_t w) { return (float)((int)(w >> 6) - 64) * k876; }          // :598
+__device__ __forceinline__ float p010_c(uint32_t w) { return (float)((int)(w >> 6) - 64) * k896 - 0.5f; }   // :599-600
+__device__ __forceinline__ uint32_t half_word(uint32_t w, int hi) { return hi ? (w >> 16) : (w & 0xffffu); }
+
+// yuvToRgb of both images and clampPixelFloat, as gen_pair has them in front of its transfer functions
+__device__ __forceinline__ GenMid sampled_to_mid(const GenConsts& c, f2 sy, f2 su, f2 sv, f2 hsy, f2 hsu, f2 hsv) {
+  GenMid m;
+  m.r = pk_add_sat(sy, splat(c.sdr_cr) * sv);
+  m.g = pk_add_sat(sy - splat(c.sdr_gcb) * su, -(splat(c.sdr_gcr) * sv));
+  m.b = pk_add_sat(sy, splat(c.sdr_cb) * su);
+  m.hr = pk_add_sat(hsy, splat(c.hdr_cr) * hsv);
+  m.hg = pk_add_sat(hsy - splat(c.hdr_gcb) * hsu, -(splat(c.hdr_gcr) * hsv));
+  m.hb = pk_add_sat(hsy, splat(c.hdr_cb) * hsu);
+  return m;
+}
+
+// the strip (8 luma columns from 8 * sx, S rows from S * my) of the aligned forms: acc[channel][map pixel], channels sy su sv hsy hsu hsv
+template <int S>
+__device__ __forceinline__ void sample_strip(const GenImage& im, const uint8_t* im_v, uint32_t my, uint32_t sx, float (&acc)[6][8 / S]) {
+  constexpr int NPX = 8 / S;
+#pragma unroll
+  for (int ch = 0; ch < 6; ++ch)
+#pragma unroll
+    for (int p = 0; p < NPX; ++p) acc[ch][p] = 0.0f;
+  const uint32_t x0 = 8u * sx;
+  float uf[4], vf[4], huf[4], hvf[4];
+#pragma unroll
+  for (int dy = 0; dy < S; ++dy) {
+    const uint32_t y = (uint32_t)S * my + (uint32_t)dy;
+    const uint4 q = ld_stream(reinterpret_cast<const uint4*>(im.hy + ((size_t)y * im.hy_stride + x0)));
+    const uint2 p8 = ld_stream(reinterpret_cast<const uint2*>(im.y + ((size_t)y * im.y_stride + x0)));
+    if (S == 1 || (dy & 1) == 0) {   // (S even: the strip starts on an even row)
+      const uint32_t cy = y >> 1;
+      const uint4 cq = ld_stream(reinterpret_cast<const uint4*>(im.huv + ((size_t)cy * im.huv_stride + x0)));
+      const uint32_t uu = ld_stream(reinterpret_cast<const uint32_t*>(im.u + ((size_t)cy * im.c_stride + (x0 >> 1))));
+      const uint32_t vv = ld_stream(reinterpret_cast<const uint32_t*>(im_v + ((size_t)cy * im.c_stride + (x0 >> 1))));
+      const uint32_t cw[4] = {cq.x, cq.y, cq.z, cq.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        uf[k] = yuv8_chroma((uu >> (8 * k)) & 0xffu);
+        vf[k] = yuv8_chroma((vv >> (8 * k)) & 0xffu);
+        huf[k] = p010_c(cw[k] & 0xffffu);
+        hvf[k] = p010_c(cw[k] >> 16);
+      }
+    }
+    const uint32_t qw[4] = {q.x, q.y, q.z, q.w};
+    const uint32_t pw[2] = {p8.x, p8.y};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int p = j / S;
+      acc[0][p] += yuv8_luma((pw[j >> 2] >> (8 * (j & 3))) & 0xffu);
+      acc[1][p] += uf[j >> 1];
+      acc[2][p] += vf[j >> 1];
+      acc[3][p] += p010_y(half_word(qw[j >> 1], j & 1));
+      acc[4][p] += huf[j >> 1];
+      acc[5][p] += hvf[j >> 1];
+    }
+  }
+  if (S != 1) {   // e / float(S*S): a power of two
+#pragma unroll
+    for (int ch = 0; ch < 6; ++ch)
+#pragma unroll
+      for (int p = 0; p < NPX; ++p) acc[ch][p] *= 1.0f / (float)(S * S);
+  }
+}
+
+// the pair of map pixels (mx, my), (mx + 1, my) at the run-time factor; a missing second pixel reads the first one's samples again
+__device__ __forceinline__ GenMid sample_pair_any(const GenConsts& c, const GenScaleConsts& sc, const GenImage& im, const uint8_t* im_v,
+                                                  uint32_t my, uint32_t mx, bool two) {
+  const uint32_t s = sc.s;
+  const uint32_t xa0 = mx * s, xb0 = two ? xa0 + s : xa0;
+  f2 sy = splat(0.0f), su = splat(0.0f), sv = splat(0.0f), hsy = splat(0.0f), hsu = splat(0.0f), hsv = splat(0.0f);
+#pragma unroll 1
+  for (uint32_t dy = 0; dy < s; ++dy) {
+    const size_t y = (size_t)my * s + dy, cy = y >> 1;
+    const uint8_t* yrow = im.y + y * im.y_stride;
+    const uint16_t* hrow = im.hy + y * im.hy_stride;
+    const uint8_t* urow = im.u + cy * im.c_stride;
+    const uint8_t* vrow = im_v + cy * im.c_stride;
+    const uint16_t* crow = im.huv + cy * im.huv_stride;
+#pragma unroll 1
+    for (uint32_t dx = 0; dx < s; ++dx) {
+      const uint32_t xa = xa0 + dx, xb = xb0 + dx;
+      sy += (f2){yuv8_luma(ld8(yrow + xa)), yuv8_luma(ld8(yrow + xb))};
+      su += (f2){yuv8_chroma(ld8(urow + (xa >> 1))), yuv8_chroma(ld8(urow + (xb >> 1)))};
+      sv += (f2){yuv8_chroma(ld8(vrow + (xa >> 1))), yuv8_chroma(ld8(vrow + (xb >> 1)))};
+      hsy += (f2){p010_y(ld16(hrow + xa)), p010_y(ld16(hrow + xb))};
+      hsu += (f2){p010_c(ld16(crow + (xa & ~1u))), p010_c(ld16(crow + (xb & ~1u)))};
+      hsv += (f2){p010_c(ld16(crow + (xa & ~1u) + 1u)), p010_c(ld16(crow + (xb & ~1u) + 1u))};
+    }
+  }
+  const float a = sc.area;   // (float)(s*s); the division is the correctly rounded one (the build keeps hipcc's default)
+  sy = (f2){sy.x / a, sy.y / a}; su = (f2){su.x / a, su.y / a}; sv = (f2){sv.x / a, sv.y / a};
+  hsy = (f2){hsy.x / a, hsy.y / a}; hsu = (f2){hsu.x / a, hsu.y / a}; hsv = (f2){hsv.x / a, hsv.y / a};
+  return sampled_to_mid(c, sy, su, sv, hsy, hsu, hsv);
+}
+
+__device__ __forceinline__ float mid_word(const GenMid& m, int ch, int k) {
+  const f2 v = ch == 0 ? m.r : ch == 1 ? m.g : ch == 2 ? m.b : ch == 3 ? m.hr : ch == 4 ? m.hg : m.hb;
+  return k ? v.y : v.x;
+}
+
+// Geometry: blocks of kScaledBlock threads, one unit (strip or pair) per thread, units in row-major order; grid = (image, y, z) with
+// block y + z * gridDim.y of the image.  MODE 0 keeps per wave 64 * NPX list entries of 7 words and as many bytes in LDS.
+constexpr int scaled_px(int s) { return s != 0 ? 8 / s : 2; }   // map pixels of a thread: a strip's, or a pair
+template <int TF, int S, int MODE>
+__global__ void __launch_bounds__(kScaledBlock) k_generate_scaled(const GenConsts c, const GenMdConsts m, const GenScaleConsts sc, const GenBatch b) {
+  constexpr int NPX = scaled_px(S);          // map pixels of a thread ...
+  constexpr int NP = (NPX + 1) / 2;           // ... in this many pairs
+  constexpr uint32_t kCap = 64u * NPX;        // map pixels of a wave's tile
+  constexpr uint32_t kWaves = kScaledBlock / 64;
+  const GenImage& im = b.img[blockIdx.x];
+  const uint8_t* im_v = im.u + (size_t)im.c_stride * (c.height / 2u);
+  const uint32_t units_per_row = S != 0 ? c.width / 8u : (c.map_w + 1u) >> 1;
+  const uint32_t total = units_per_row * c.map_h;
+  const uint32_t idx = (blockIdx.z * gridDim.y + blockIdx.y) * (uint32_t)kScaledBlock + threadIdx.x;
+  const bool live = idx < total;
+  if (MODE != 0 && !live) return;
+  if (MODE == 0 && (idx & ~63u) >= total) return;   // (the whole wave)
+  const uint32_t my = live ? idx / units_per_row : 0u;
+  const uint32_t ux = live ? idx - my * units_per_row : 0u;
+  const uint32_t mx = ux * (uint32_t)NPX;
+  const bool two = S != 0 ? NPX > 1 : (mx + 1u < c.map_w);
+
+  GenMid mid[NP];
+  if constexpr (S != 0) {
+    float acc[6][NPX];
+    if (live) {
+      sample_strip<S>(im, im_v, my, ux, acc);
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < 6; ++ch)
+#pragma unroll
+        for (int p = 0; p < NPX; ++p) acc[ch][p] = 0.0f;
+    }
+#pragma unroll
+    for (int pp = 0; pp < NP; ++pp) {
+      const int p0 = 2 * pp, p1 = NPX > 1 ? 2 * pp + 1 : 0;   // (a strip of one map pixel: the pair's second is a copy, dropped)
+      mid[pp] = sampled_to_mid(c, (f2){acc[0][p0], acc[0][p1]}, (f2){acc[1][p0], acc[1][p1]}, (f2){acc[2][p0], acc[2][p1]},
+                               (f2){acc[3][p0], acc[3][p1]}, (f2){acc[4][p0], acc[4][p1]}, (f2){acc[5][p0], acc[5][p1]});
+    }
+  } else {
+    if (live) mid[0] = sample_pair_any(c, sc, im, im_v, my, mx, two);
+    else mid[0] = sampled_to_mid(c, splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f));
+  }
+
+  uint32_t hy[2][4][2], huv[2][2][2], y8[2][4], u8[2][2], v8[2][2];   // (gen_pair's planar inputs: not read from kGenBack on)
+  uint8_t o[2];
+  float gn[2];
+  if (MODE != 0) {
+#pragma unroll
+    for (int pp = 0; pp < NP; ++pp) {
+      GenMid lin = mid[pp];
+      gen_pair<TF, false, false, false, kGenBackLinear>(c, hy, huv, y8, u8, v8, o, gn, nullptr, nullptr, &lin);
+      if constexpr (S != 0 && NPX > 1) encode_store_md<true, MODE == 2>(c, m, lin, im.map, my, mx + 2u * pp, true);
+      else encode_store_md<false, MODE == 2>(c, m, lin, im.map, my, mx, two);
+    }
+    return;
+  }
+
+  __shared__ float s_list[kWaves][7][kCap];
+  __shared__ uint8_t s_byte[kWaves][kCap];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  uint32_t bytes[NPX], doubt = 0u;
+#pragma unroll
+  for (int pp = 0; pp < NP; ++pp) {
+    const uint32_t ex = gen_pair<TF, false, true, true, kGenBack>(c, hy, huv, y8, u8, v8, o, gn, nullptr, nullptr, &mid[pp]);
+    bytes[2 * pp] = o[0];
+    if constexpr (NPX > 1) bytes[2 * pp + 1] = o[1];
+    doubt |= ((ex >> 2) & 3u) << (2 * pp);
+  }
+  doubt &= !live ? 0u : (NPX > 1 && two) ? (1u << NPX) - 1u : 1u;
+  uint32_t cnt = 0u;   // entries of the wave's list (wave-uniform)
+#pragma unroll
+  for (int k = 0; k < NPX; ++k) {
+    const bool mine = ((doubt >> k) & 1u) != 0u;
+    const unsigned long long mask = __builtin_amdgcn_ballot_w64(mine);
+    if (mask != 0ull) {
+      const uint32_t pos = cnt + (uint32_t)__builtin_popcountll(mask & below);
+      if (mine) {
+#pragma unroll
+        for (int ch = 0; ch < 6; ++ch) s_list[wave][ch][pos] = mid_word(mid[k >> 1], ch, k & 1);
+        s_list[wave][6][pos] = __uint_as_float(lane * (uint32_t)NPX + (uint32_t)k);
+      }
+      cnt += (uint32_t)__builtin_popcountll(mask);
+    }
+  }
+  if (sc.doubt_count != nullptr && cnt != 0u && lane == 0u) atomicAdd(sc.doubt_count, cnt);   // (the probe only: launch-uniform null otherwise)
+  if (cnt != 0u) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll 1
+    for (uint32_t e0 = 0u; e0 < cnt; e0 += 128u) {
+      const uint32_t i0 = e0 + 2u * lane, i1 = i0 + 1u;
+      const bool have0 = i0 < cnt, have1 = i1 < cnt;
+      const uint32_t j0 = have0 ? i0 : 0u, j1 = have1 ? i1 : j0;   // (a lane without an entry evaluates a copy and drops it)
+      GenMid em;
+      em.r = (f2){s_list[wave][0][j0], s_list[wave][0][j1]};
+      em.g = (f2){s_list[wave][1][j0], s_list[wave][1][j1]};
+      em.b = (f2){s_list[wave][2][j0], s_list[wave][2][j1]};
+      em.hr = (f2){s_list[wave][3][j0], s_list[wave][3][j1]};
+      em.hg = (f2){s_list[wave][4][j0], s_list[wave][4][j1]};
+      em.hb = (f2){s_list[wave][5][j0], s_list[wave][5][j1]};
+      const uint32_t t0 = __float_as_uint(s_list[wave][6][j0]), t1 = __float_as_uint(s_list[wave][6][j1]);
+      gen_pair<TF, false, false, false, kGenBack>(c, hy, huv, y8, u8, v8, o, gn, nullptr, nullptr, &em);
+      if (have0) s_byte[wave][t0] = o[0];
+      if (have1) s_byte[wave][t1] = o[1];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll
+    for (int k = 0; k < NPX; ++k)
+      if ((doubt >> k) & 1u) bytes[k] = s_byte[wave][lane * (uint32_t)NPX + (uint32_t)k];
+  }
+  if (!live) return;
+  uint8_t* mp = im.map + (size_t)my * c.map_w + mx;
+  if constexpr (S == 1) {
+    st_stream(reinterpret_cast<uint2*>(mp), make_uint2(bytes[0] | (bytes[1] << 8) | (bytes[2] << 16) | (bytes[3] << 24),
+                                                        bytes[4] | (bytes[5] << 8) | (bytes[6] << 16) | (bytes[7] << 24)));
+  } else if constexpr (S == 2) {
+    *reinterpret_cast<uint32_t*>(mp) = bytes[0] | (bytes[1] << 8) | (bytes[2] << 16) | (bytes[3] << 24);
+  } else {
+    mp[0] = (uint8_t)bytes[0];
+    if constexpr (NPX > 1) { if (two) mp[1] = (uint8_t)bytes[1]; }
+  }
+}
+
+template <int TF, int S>
+static hipError_t launch_generate_scaled_s(const GenConsts& c, const GenMdConsts& m, const GenScaleConsts& sc, const GenBatch& b, int n,
+                                           int mode, hipStream_t s) {
+  const uint64_t units = (uint64_t)(S != 0 ? c.width / 8u : (c.map_w + 1u) >> 1) * c.map_h;
+  if (units == 0u || n == 0) return hipSuccess;
+  const uint64_t blocks = (units + kScaledBlock - 1u) / kScaledBlock;
+  if (units > 0xFFFFFFFFull || blocks > 65535ull * 65535ull) return hipErrorInvalidValue;
+  const unsigned gy = (unsigned)(blocks < 65535u ? blocks : 65535u), gz = (unsigned)((blocks + gy - 1u) / gy);
+  const dim3 g((unsigned)n, gy, gz), blk(kScaledBlock, 1, 1);
+  if (mode == 0) hipLaunchKernelGGL((k_generate_scaled<TF, S, 0>), g, blk, 0, s, c, m, sc, b);
+  else if (mode == 1) hipLaunchKernelGGL((k_generate_scaled<TF, S, 1>), g, blk, 0, s, c, m, sc, b);
+  else hipLaunchKernelGGL((k_generate_scaled<TF, S, 2>), g, blk, 0, s, c, m, sc, b);
+  return hipGetLastError();
+}
+template <int TF>
+static hipError_t launch_generate_scaled_tf(const GenConsts& c, const GenMdConsts& m, const GenScaleConsts& sc, const GenBatch& b, int n,
+                                            bool aligned, int mode, hipStream_t s) {
+  if (aligned && sc.s == 1u) return launch_generate_scaled_s<TF, 1>(c, m, sc, b, n, mode, s);
+  if (aligned && sc.s == 2u) return launch_generate_scaled_s<TF, 2>(c, m, sc, b, n, mode, s);
+  if (aligned && sc.s == 8u) return launch_generate_scaled_s<TF, 8>(c, m, sc, b, n, mode, s);
+  return launch_generate_scaled_s<TF, 0>(c, m, sc, b, n, mode, s);
+}
+hipError_t launch_generate_scaled(const GenConsts& c, const GenMdConsts& m, const GenScaleConsts& sc, const GenBatch& b, int n, int hdr_tf,
+                                  bool aligned, int mode, hipStream_t s) {
+  if (sc.s == 0u || mode < 0 || mode > 2) return hipErrorInvalidValue;
+  switch (hdr_tf) {
+    case 0: return launch_generate_scaled_tf<0>(c, m, sc, b, n, aligned, mode, s);
+    case 1: return launch_generate_scaled_tf<1>(c, m, sc, b, n, aligned, mode, s);
+    case 2: return launch_generate_scaled_tf<2>(c, m, sc, b, n, aligned, mode, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 // The range rule (include/uhdr_hip.h, uhdr_hip_adaptive_boost_range: the same f32 operations) and, from the range, what
 // generate_consts / encode_constants derive on the host for a fixed one: the two logarithms as (float)log2((double)boost), the
 // scale of encode_gain_guarded's in-range path and the bytes encodeGain yields for a gain on either clamp.  One block: image i is

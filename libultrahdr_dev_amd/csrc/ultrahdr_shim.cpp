@@ -325,12 +325,28 @@ int rgbmap_one(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, int hd
   const size_t exn = exif_len(exif);
   return uhdr_hip_jpegr_encode_rgbmap_batch(1, p010 ? p010 : &none, yuv, hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, UHDR_HIP_MEM_HOST, nullptr);
 }
+// one file through uhdr_hip_jpegr_encode_scaled_batch (setGainMapScaleFactor): API-1, or API-0 with yuv == nullptr
+int scaled_one(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, int hdr_tf, int quality, uhdr_exif_ptr exif, void* out, size_t cap, size_t* n,
+               bool rgb_map, int factor) {
+  uhdr_hip_image_t none;
+  std::memset(&none, 0, sizeof(none));
+  const void* ex = exif_ptr(exif);
+  const size_t exn = exif_len(exif);
+  return uhdr_hip_jpegr_encode_scaled_batch(1, p010 ? p010 : &none, yuv, hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, rgb_map ? 1 : 0, factor,
+                                            UHDR_HIP_MEM_HOST, nullptr);
+}
 }  // namespace
 
 status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, ultrahdr_transfer_function hdr_tf, uhdr_compressed_ptr dest, int quality,
                                uhdr_exif_ptr exif) {
   uhdr_hip_image_t p;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
+  if (mGainMapScaleFactor != 4) {   // setGainMapScaleFactor: the operator and the adaptive range have no form at another factor
+    if (mToneMapOp != UHDR_HIP_TONEMAP_SHIFT || mContentBoost >= 0) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;
+    return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
+      return scaled_one(p010_image_ptr ? &p : nullptr, nullptr, (int)hdr_tf, quality, exif, out, cap, n, mMultiChannelGainMap, mGainMapScaleFactor);
+    });
+  }
   if (mMultiChannelGainMap)   // setMultiChannelGainMap: the per-channel map (it goes in front of setToneMap and setContentBoost, which stay single-channel)
     return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
       return rgbmap_one(p010_image_ptr ? &p : nullptr, nullptr, (int)hdr_tf, quality, exif, out, cap, n);
@@ -358,6 +374,13 @@ status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, uhdr_uncomp
   uhdr_hip_image_t p, y;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
   if (yuv420_image_ptr) y = to_c(*yuv420_image_ptr);
+  if (mGainMapScaleFactor != 4) {   // setGainMapScaleFactor
+    if (mContentBoost >= 0) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;
+    if (yuv420_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;   // jpegr.cpp:253-256 (a NULL array would mean API-0 to the batch)
+    return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
+      return scaled_one(p010_image_ptr ? &p : nullptr, &y, (int)hdr_tf, quality, exif, out, cap, n, mMultiChannelGainMap, mGainMapScaleFactor);
+    });
+  }
   if (mMultiChannelGainMap) {
     if (yuv420_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;   // jpegr.cpp:253-256 (a NULL array would mean API-0 to the batch)
     return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
@@ -393,6 +416,7 @@ uhdr_hip_image_t to_c_packed(const ultrahdr_uncompressed_struct& s) {
 
 status_t JpegRHip::encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_uncompressed_ptr sdr_image_ptr, ultrahdr_transfer_function hdr_tf,
                                      uhdr_compressed_ptr dest, int quality, uhdr_exif_ptr exif) {
+  if (mGainMapScaleFactor != 4) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;   // setGainMapScaleFactor: the packed calls write factor 4 only
   if (hdr_image_ptr == nullptr || sdr_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
   const uhdr_hip_image_t h = to_c_packed(*hdr_image_ptr), sd = to_c_packed(*sdr_image_ptr);
   return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
@@ -405,6 +429,7 @@ status_t JpegRHip::encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_u
 
 status_t JpegRHip::encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, ultrahdr_transfer_function hdr_tf, uhdr_compressed_ptr dest, int quality,
                                      uhdr_exif_ptr exif) {
+  if (mGainMapScaleFactor != 4) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;   // setGainMapScaleFactor
   if (hdr_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
   const uhdr_hip_image_t h = to_c_packed(*hdr_image_ptr);
   return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
@@ -456,8 +481,36 @@ status_t generateGainMapPacked(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompr
   return ULTRAHDR_NO_ERROR;
 }
 
+status_t generateGainMapScaled(uhdr_uncompressed_ptr yuv420_image_ptr, uhdr_uncompressed_ptr p010_image_ptr, ultrahdr_transfer_function hdr_tf,
+                               ultrahdr_metadata_ptr metadata, uhdr_uncompressed_ptr dest, int map_scale_factor, bool multi_channel, bool sdr_is_601,
+                               void* stream) {
+  if (yuv420_image_ptr == nullptr || p010_image_ptr == nullptr || dest == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
+  if (uhdr_hip_init(0) != UHDR_HIP_NO_ERROR) return ULTRAHDR_UNKNOWN_ERROR;
+  const uhdr_hip_image_t y = to_c(*yuv420_image_ptr), p = to_c(*p010_image_ptr);
+  uhdr_hip_image_t d = to_c(*dest);
+  uhdr_hip_metadata_t md;
+  std::memset(&md, 0, sizeof(md));
+  const int rc = uhdr_hip_generate_gainmap_scaled_batch(1, &y, &p, (int)hdr_tf, nullptr, &md, &d, sdr_is_601 ? 1 : 0, multi_channel ? 1 : 0,
+                                                        map_scale_factor, stream);
+  if (rc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(rc);
+  if (metadata != nullptr) {
+    metadata->version = md.version;
+    metadata->maxContentBoost = md.maxContentBoost;
+    metadata->minContentBoost = md.minContentBoost;
+    metadata->gamma = md.gamma;
+    metadata->offsetSdr = md.offsetSdr;
+    metadata->offsetHdr = md.offsetHdr;
+    metadata->hdrCapacityMin = md.hdrCapacityMin;
+    metadata->hdrCapacityMax = md.hdrCapacityMax;
+  }
+  from_c(d, dest);
+  dest->pixelFormat = multi_channel ? ULTRAHDR_PIX_FMT_RGBA8888 : ULTRAHDR_PIX_FMT_MONOCHROME;
+  return ULTRAHDR_NO_ERROR;
+}
+
 status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, uhdr_uncompressed_ptr yuv420_image_ptr, uhdr_compressed_ptr yuv420jpg_image_ptr,
                                ultrahdr_transfer_function hdr_tf, uhdr_compressed_ptr dest) {
+  if (mGainMapScaleFactor != 4) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;   // setGainMapScaleFactor: API-2 writes factor 4 only
   uhdr_hip_image_t p, y;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
   if (yuv420_image_ptr) y = to_c(*yuv420_image_ptr);
@@ -471,6 +524,7 @@ status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, uhdr_uncomp
 
 status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, uhdr_compressed_ptr yuv420jpg_image_ptr, ultrahdr_transfer_function hdr_tf,
                                uhdr_compressed_ptr dest) {
+  if (mGainMapScaleFactor != 4) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;   // setGainMapScaleFactor: API-3 writes factor 4 only
   uhdr_hip_image_t p;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
   return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
