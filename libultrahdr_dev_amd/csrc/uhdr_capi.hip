@@ -165,6 +165,19 @@ int idw_for_scale(DeviceState* st, int scale, const float** dptr, float** transi
   *dptr = ins.first->second;
   return UHDR_HIP_NO_ERROR;
 }
+// The table of one chunk's launches.  A table too large to keep is freed when the lease ends, behind a wait for the stream: when
+// the chunk's launches have finished.
+struct IdwLease {
+  const float* idw = nullptr;
+  IdwLease() = default;
+  IdwLease(const IdwLease&) = delete;
+  IdwLease& operator=(const IdwLease&) = delete;
+  int take(DeviceState* st, int scale, hipStream_t s) { s_ = s; return idw_for_scale(st, scale, &idw, &transient_); }
+  ~IdwLease() { if (transient_) { (void)hipStreamSynchronize(s_); (void)hipFree(transient_); } }
+ private:
+  float* transient_ = nullptr;
+  hipStream_t s_ = nullptr;
+};
 
 // ---- colour constants (gainmapmath.cpp:121-248, 359-393, 447-481) ------------------------------
 struct YuvRgb { float cr, gcb, gcr, cb; };
@@ -216,6 +229,26 @@ const float kYuv2100To601[9] = {1.0f, 0.117887f, 0.105521f, 0.0f, 0.995211f, -0.
 
 bool valid_gamut(int g) { return g >= UHDR_HIP_CG_BT709 && g <= UHDR_HIP_CG_BT2100; }
 bool al(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+bool tf_known(int tf) { return tf == UHDR_HIP_TF_LINEAR || tf == UHDR_HIP_TF_HLG || tf == UHDR_HIP_TF_PQ; }
+// the rows of an image whose luma_stride may be left 0: stride in pixels, 0 means width (gainmapmath.cpp:585)
+size_t row_stride(const uhdr_hip_image_t& im) { return im.luma_stride == 0 ? im.width : im.luma_stride; }
+// The chunk rule of every gain-map batch call: a chunk is up to kMaxChunk consecutive images, from image i on,
+// that have the shape of image i (same_shape(j)) and one class (aligned or not, FAST or not).  fill(j, m) fills slot m of the batch
+// from image j and returns image j's class: before the classes are compared, so the image that ends a chunk leaves its slot behind
+// and nothing else.  What only the members receive (their destination descriptors) the caller fills, for images [i, i + m).
+struct Chunk { int m; bool cls; };
+template <class Same, class Fill>
+Chunk form_chunk(int i, int n, Same same_shape, Fill fill) {
+  Chunk ch{0, true};
+  while (i + ch.m < n && ch.m < kMaxChunk) {
+    if (!same_shape(i + ch.m)) break;
+    const bool cls = fill(i + ch.m, ch.m);
+    if (ch.m == 0) ch.cls = cls;
+    else if (cls != ch.cls) break;
+    ++ch.m;
+  }
+  return ch;
+}
 
 // ---- generate ------------------------------------------------------------------------------------
 // checks of ultrahdr.cpp:189-202 + the switch defaults of :222-302, in the reference's order
@@ -227,8 +260,7 @@ int validate_generate(const uhdr_hip_image_t* yuv, const uhdr_hip_image_t* p010,
   if (yuv->width != p010->width || yuv->height != p010->height) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
   if (yuv->colorGamut == UHDR_HIP_CG_UNSPECIFIED || p010->colorGamut == UHDR_HIP_CG_UNSPECIFIED)
     return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
-  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ)
-    return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (!tf_known(hdr_tf)) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
   if (!valid_gamut(yuv->colorGamut) || !valid_gamut(p010->colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
   return UHDR_HIP_NO_ERROR;
 }
@@ -246,14 +278,15 @@ void fill_generate_metadata(int hdr_tf, uhdr_hip_metadata_t* md) {  // ultrahdr.
   md->hdrCapacityMax = md->maxContentBoost;
 }
 
-void fill_generate_dest(const uhdr_hip_image_t* yuv, uhdr_hip_image_t* dest) {  // ultrahdr.cpp:210-216
-  dest->width = yuv->width / 4;
-  dest->height = yuv->height / 4;
+// ultrahdr.cpp:210-216, for a map of any scale factor, one plane or RGBA8888
+void fill_generate_dest(const uhdr_hip_image_t* yuv, uhdr_hip_image_t* dest, size_t scale = 4, bool rgb = false) {
+  dest->width = yuv->width / scale;
+  dest->height = yuv->height / scale;
   dest->colorGamut = UHDR_HIP_CG_UNSPECIFIED;
   dest->luma_stride = dest->width;
   dest->chroma_data = nullptr;
   dest->chroma_stride = 0;
-  dest->pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
+  dest->pixelFormat = rgb ? UHDR_HIP_PIX_FMT_RGBA8888 : UHDR_HIP_PIX_FMT_MONOCHROME;
 }
 
 // bytes encodeGain (gainmapmath.cpp:529-541) yields for a gain clamped to min / max, evaluated with the
@@ -324,7 +357,7 @@ GenImage gen_image(const uhdr_hip_image_t& yuv, const uhdr_hip_image_t& p010, vo
   g.map = static_cast<uint8_t*>(map);
   g.y_stride = (uint32_t)yuv.luma_stride;
   g.c_stride = (uint32_t)yuv.chroma_stride;
-  g.hy_stride = (uint32_t)(p010.luma_stride == 0 ? p010.width : p010.luma_stride);  // gainmapmath.cpp:585
+  g.hy_stride = (uint32_t)row_stride(p010);
   g.huv_stride = (uint32_t)p010.chroma_stride;
   return g;
 }
@@ -333,6 +366,32 @@ bool gen_aligned(const GenImage& g, uint32_t w, uint32_t h) {
   if ((uint64_t)g.hy_stride * h >= (1ull << 31) || (uint64_t)g.y_stride * h >= (1ull << 32)) return false;  // 32-bit offsets
   return (w % 8u == 0) && al(g.hy, 16) && g.hy_stride % 8u == 0 && al(g.huv, 16) && g.huv_stride % 8u == 0 &&
          al(g.y, 8) && g.y_stride % 8u == 0 && al(g.u, 4) && al(v, 4) && g.c_stride % 4u == 0 && al(g.map, 2);
+}
+// The chunk of the generate family from image i on (form_chunk): equal size and gamuts; the class is gen_aligned and the call's
+// own condition on top, also(slot) -- an 8-byte RGBA pair, the scaled call's strip, or no_more.  map_of(j): where image j's map goes.
+bool no_more(const GenImage&) { return true; }
+bool rgba_pair_aligned(const GenImage& g) { return al(g.map, 8); }   // (the RGBA pair of a thread is one 8-byte store)
+template <class MapOf, class Also>
+Chunk gen_chunk(int i, int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, GenBatch& b, MapOf map_of, Also also) {
+  const uhdr_hip_image_t& y0 = yuvs[i];
+  const uhdr_hip_image_t& p0 = p010s[i];
+  return form_chunk(i, n,
+                    [&](int j) {
+                      return yuvs[j].width == y0.width && yuvs[j].height == y0.height && yuvs[j].colorGamut == y0.colorGamut &&
+                             p010s[j].colorGamut == p0.colorGamut;
+                    },
+                    [&](int j, int m) {
+                      b.img[m] = gen_image(yuvs[j], p010s[j], map_of(j));
+                      return gen_aligned(b.img[m], (uint32_t)y0.width, (uint32_t)y0.height) && also(b.img[m]);
+                    });
+}
+// ... with the maps in the destination images, whose descriptors the members of the chunk then receive
+template <class Also>
+Chunk gen_chunk(int i, int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, uhdr_hip_image_t* dests, GenBatch& b, Also also,
+                size_t scale = 4, bool rgb = false) {
+  const Chunk ch = gen_chunk(i, n, yuvs, p010s, b, [&](int j) { return dests[j].data; }, also);
+  for (int k = 0; k < ch.m; ++k) fill_generate_dest(&yuvs[i + k], &dests[i + k], scale, rgb);
+  return ch;
 }
 
 // ---- content-adaptive generate ---------------------------------------------------------------------
@@ -396,27 +455,15 @@ int adaptive_enqueue(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t
   std::vector<std::pair<int, int>> chunks;   // (first image, images) of every launch
   int i = 0;
   while (i < n) {
-    // chunk = up to kMaxChunk consecutive images of identical size, gamuts and alignment class, as uhdr_hip_generate_gainmap_batch_ex
     const uhdr_hip_image_t& y0 = yuvs[i];
     GenConsts c = generate_consts(y0.colorGamut, p010s[i].colorGamut, hdr_tf, sdr_is_601, y0.width, y0.height, md);
     c.stat_keys = keys + 2 * i;
     c.stat_stride = 2;
     GenBatch b;
-    int m = 0;
-    bool aligned = true;
-    while (i + m < n && m < kMaxChunk) {
-      const uhdr_hip_image_t& y = yuvs[i + m];
-      if (y.width != y0.width || y.height != y0.height || y.colorGamut != y0.colorGamut || p010s[i + m].colorGamut != p010s[i].colorGamut)
-        break;
-      b.img[m] = gen_image(y, p010s[i + m], ws + lay.gains[(size_t)(i + m)]);
-      const bool a = gen_aligned(b.img[m], c.width, c.height);
-      if (m == 0) aligned = a;
-      else if (a != aligned) break;
-      ++m;
-    }
-    HIP_TRY(launch_generate_gains(c, b, m, hdr_tf, aligned, s));
-    chunks.emplace_back(i, m);
-    i += m;
+    const Chunk ch = gen_chunk(i, n, yuvs, p010s, b, [&](int j) { return ws + lay.gains[(size_t)j]; }, no_more);
+    HIP_TRY(launch_generate_gains(c, b, ch.m, hdr_tf, ch.cls, s));
+    chunks.emplace_back(i, ch.m);
+    i += ch.m;
   }
   HIP_TRY(launch_adaptive_consts(keys, n, boost_scope == UHDR_HIP_BOOST_PER_CALL ? 1 : 0, adaptive_cap(hdr_tf), consts, content_minmax,
                                  boost_range, carry_in, carry_out, s));
@@ -555,6 +602,43 @@ int validate_md(const uhdr_hip_metadata_t* md) {
   if (md->offsetSdr < 0.0f || md->offsetHdr < 0.0f || md->gamma <= 0.0f) return UHDR_HIP_ERROR_BAD_METADATA;
   return UHDR_HIP_NO_ERROR;
 }
+
+// ---- the argument checks of the generate batch calls, each order written once (tests/test_*_cpu.py hold the orders) ----------------
+// dest_align: what a destination's data pointer must be a multiple of (4 for an RGBA map); hook (or null): a further check of the
+// call's own on every image, behind the others of that image
+using ImageHook = std::function<int(const uhdr_hip_image_t&)>;
+bool null_dest(const uhdr_hip_image_t& d, size_t dest_align) { return d.data == nullptr || !al(d.data, dest_align); }
+// Against the reference's metadata (uhdr_hip_generate_gainmap_batch_ex and the calls that take its order): the call's pointers; per
+// image validate_generate, then the map buffer the C-ABI's caller provides, then the hook; the transfer function last (n == 0)
+int check_generate(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf, const uhdr_hip_metadata_t* md,
+                   const uhdr_hip_image_t* dests, size_t dest_align, const ImageHook& hook = nullptr) {
+  if (n < 0 || (n > 0 && (yuvs == nullptr || p010s == nullptr || dests == nullptr)) || md == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  for (int i = 0; i < n; ++i) {
+    int rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, md, &dests[i]);
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
+    if (null_dest(dests[i], dest_align)) return UHDR_HIP_ERROR_BAD_PTR;
+    if (hook && (rc = hook(yuvs[i])) != UHDR_HIP_NO_ERROR) return rc;
+  }
+  return tf_known(hdr_tf) ? UHDR_HIP_NO_ERROR : UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+}
+// Against the caller's metadata (uhdr_hip_generate_gainmap_md_batch's order): every image's pointers, the metadata, then per image
+// validate_generate and the hook; the transfer function last
+int check_generate_md(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf, const uhdr_hip_metadata_t* md,
+                      const uhdr_hip_image_t* dests, size_t dest_align, const ImageHook& hook = nullptr) {
+  if (n < 0 || (n > 0 && (yuvs == nullptr || p010s == nullptr || dests == nullptr)) || md == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  for (int i = 0; i < n; ++i) {
+    if (yuvs[i].data == nullptr || yuvs[i].chroma_data == nullptr || p010s[i].data == nullptr || p010s[i].chroma_data == nullptr ||
+        null_dest(dests[i], dest_align))
+      return UHDR_HIP_ERROR_BAD_PTR;
+  }
+  int rc = validate_md(md);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  for (int i = 0; i < n; ++i) {
+    if ((rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, md, &dests[i])) != UHDR_HIP_NO_ERROR) return rc;
+    if (hook && (rc = hook(yuvs[i])) != UHDR_HIP_NO_ERROR) return rc;
+  }
+  return tf_known(hdr_tf) ? UHDR_HIP_NO_ERROR : UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+}
 // W and d of include/uhdr_hip.h, in double (D >= 1, possibly infinite; the metadata has passed validate_md)
 void md_weight(const uhdr_hip_metadata_t& md, float max_display_boost, double* w, double* d) {
   const double D = (double)max_display_boost, hmin = (double)md.hdrCapacityMin, hmax = (double)md.hdrCapacityMax;
@@ -686,6 +770,48 @@ void fill_apply_dest(const uhdr_hip_image_t* yuv, uhdr_hip_image_t* dest) {  // 
   dest->width = yuv->width;
   dest->height = yuv->height;
   dest->colorGamut = yuv->colorGamut;
+}
+// The chunk of the apply family from image i on (form_chunk): equal image and map sizes and, for RGBA maps (equal_stride), equal map
+// strides.  fast_of: the one-plane call's constants -- its class is app_fast_s4 --, or null: one class.  The members' destination
+// descriptors are filled.
+Chunk app_chunk(int i, int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* maps, uhdr_hip_image_t* dests, AppBatch& b,
+                const AppConsts* fast_of, bool equal_stride) {
+  const uhdr_hip_image_t& y0 = yuvs[i];
+  const uhdr_hip_image_t& m0 = maps[i];
+  const Chunk ch = form_chunk(i, n,
+                              [&](int j) {
+                                return yuvs[j].width == y0.width && yuvs[j].height == y0.height && maps[j].width == m0.width &&
+                                       maps[j].height == m0.height && (!equal_stride || row_stride(maps[j]) == row_stride(m0));
+                              },
+                              [&](int j, int m) {
+                                b.img[m] = app_image(yuvs[j], maps[j], dests[j].data);
+                                return fast_of == nullptr || app_fast_s4(*fast_of, b.img[m]);
+                              });
+  for (int k = 0; k < ch.m; ++k) fill_apply_dest(&yuvs[i + k], &dests[i + k]);
+  return ch;
+}
+// The chunks of the apply calls that have one kernel per chunk and no class (RGBA maps, general metadata), on checked arguments:
+// launch(constants, batch, images) enqueues a chunk and returns its status.  rgba: the maps' rows are luma_stride pixels (0 = width), else `width` bytes.
+template <class Launch>
+int apply_pixel_chunks(DeviceState* st, hipStream_t s, int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* maps,
+                       const uhdr_hip_metadata_t& md, float max_display_boost, uhdr_hip_image_t* dests, bool rgba, bool writes,
+                       Launch launch) {
+  int i = 0;
+  while (i < n) {
+    const uhdr_hip_image_t& y0 = yuvs[i];
+    const uhdr_hip_image_t& m0 = maps[i];
+    IdwLease table;
+    int rc = table.take(st, (int)(y0.width / m0.width), s);
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
+    AppConsts c = apply_consts(y0, m0, md, max_display_boost, table.idw);
+    c.map_stride = (uint32_t)(rgba ? row_stride(m0) : m0.width);
+    c.tab = st->lut;
+    AppBatch b;
+    const int m = app_chunk(i, n, yuvs, maps, dests, b, nullptr, rgba).m;
+    if (writes && (rc = launch(c, b, m)) != UHDR_HIP_NO_ERROR) return rc;
+    i += m;
+  }
+  return UHDR_HIP_NO_ERROR;
 }
 
 // ---- host staging ----------------------------------------------------------------------------------
@@ -896,9 +1022,24 @@ int stage_p010_in(StageSet* st, int slot, const uhdr_hip_image_t& h, uhdr_hip_im
   d->chroma_data = st->stage[slot + 1];
   d->luma_stride = lp;
   d->chroma_stride = cp;
-  const size_t hls = h.luma_stride == 0 ? h.width : h.luma_stride;  // gainmapmath.cpp:585
-  if ((rc = h2d_plane(d->data, lp, h.data, hls, w, hh, 2, s)) != 0) return rc;
+  if ((rc = h2d_plane(d->data, lp, h.data, row_stride(h), w, hh, 2, s)) != 0) return rc;
   if ((rc = h2d_plane(d->chroma_data, cp, h.chroma_data, h.chroma_stride, cw2, ch, 2, s)) != 0) return rc;
+  return UHDR_HIP_NO_ERROR;
+}
+// A single generate call through host memory: the SDR image staged into slots 0 and 1 of `ss`, the P010 image into 2 and 3, the
+// map's width / 4 x height / 4 bytes reserved in slot 4; run(staged SDR, staged P010, staged map) enqueued between, then the map
+// copied back.  Enqueues only.
+int generate_through_stage(StageSet* ss, const uhdr_hip_image_t* yuv, const uhdr_hip_image_t* p010, uhdr_hip_image_t* dest, hipStream_t s,
+                           const std::function<int(const uhdr_hip_image_t&, const uhdr_hip_image_t&, uhdr_hip_image_t&)>& run) {
+  int rc;
+  uhdr_hip_image_t dy, dp, dm = *dest;
+  if ((rc = stage_yuv420_in(ss, 0, *yuv, &dy, s)) != 0) return rc;
+  if ((rc = stage_p010_in(ss, 2, *p010, &dp, s)) != 0) return rc;
+  const size_t mw = yuv->width / 4, mh = yuv->height / 4;
+  if ((rc = stage_reserve(ss, 4, mw * mh)) != 0) return rc;
+  dm.data = ss->stage[4];
+  if ((rc = run(dy, dp, dm)) != 0) return rc;
+  if (mw * mh) HIP_TRY(hipMemcpyAsync(dest->data, dm.data, mw * mh, hipMemcpyDeviceToHost, s));
   return UHDR_HIP_NO_ERROR;
 }
 
@@ -2511,7 +2652,7 @@ int check_encode_inputs(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yu
   if (p010->luma_stride != 0 && p010->luma_stride < p010->width) return UHDR_HIP_ERROR_INVALID_STRIDE;
   if (p010->chroma_data != nullptr && p010->chroma_stride < p010->width) return UHDR_HIP_ERROR_INVALID_STRIDE;
   if (out == nullptr || out_size == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (!tf_known(hdr_tf)) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
   if (yuv == nullptr) return UHDR_HIP_NO_ERROR;
   if (yuv->data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
   if (yuv->luma_stride != 0 && yuv->luma_stride < yuv->width) return UHDR_HIP_ERROR_INVALID_STRIDE;
@@ -2967,7 +3108,7 @@ static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const 
     if (!valid_gamut(hd.colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
     if (stride_bad(hd)) return UHDR_HIP_ERROR_INVALID_STRIDE;
     if (out[i] == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-    if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+    if (!tf_known(hdr_tf)) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
     if (!api0) {
       if (sd.data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
       if (stride_bad(sd)) return UHDR_HIP_ERROR_INVALID_STRIDE;
@@ -3596,20 +3737,9 @@ static int generate_chunk(DeviceState* st, hipStream_t s, int n, const uhdr_hip_
   c.stat_stride = 2;
   c.lut = (lut && st != nullptr) ? st->lut : nullptr;
   GenBatch b;
-  int m = 0;
-  bool aligned = true;
-  while (i + m < n && m < kMaxChunk) {
-    const uhdr_hip_image_t& y = yuvs[i + m];
-    if (y.width != y0.width || y.height != y0.height || y.colorGamut != y0.colorGamut ||
-        p010s[i + m].colorGamut != p010s[i].colorGamut)
-      break;
-    b.img[m] = gen_image(y, p010s[i + m], dests[i + m].data);
-    const bool a = gen_aligned(b.img[m], c.width, c.height);
-    if (m == 0) aligned = a;
-    else if (a != aligned) break;
-    fill_generate_dest(&y, &dests[i + m]);
-    ++m;
-  }
+  const Chunk ch = gen_chunk(i, n, yuvs, p010s, dests, b, no_more);   // (the descriptors are filled in the plan-only mode too)
+  const int m = ch.m;
+  const bool aligned = ch.cls;
   *m_out = m;
   bool filter = generate_mode == UHDR_HIP_GENERATE_EXACT && c.flt_delta < 0.25f && c.min_boost >= 0.25f && c.max_boost <= 64.0f;
   // The filtered kernel of a large launch leaves its pixels in doubt and the exact extremes to k_generate_resolve.  A small
@@ -3685,18 +3815,10 @@ int uhdr_hip_generate_gainmap_batch_ex(int n, const uhdr_hip_image_t* yuvs, cons
   if (generate_mode != UHDR_HIP_GENERATE_EXACT && generate_mode != UHDR_HIP_GENERATE_LUT &&
       generate_mode != UHDR_HIP_GENERATE_UNFILTERED)
     return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  if (n < 0 || (n > 0 && (yuvs == nullptr || p010s == nullptr || dests == nullptr)) || metadata == nullptr)
-    return UHDR_HIP_ERROR_BAD_PTR;
-  for (int i = 0; i < n; ++i) {
-    const int rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, metadata, &dests[i]);
-    if (rc != UHDR_HIP_NO_ERROR) return rc;
-    if (dests[i].data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;  // C-ABI: caller provides the map buffer
-  }
-  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ)
-    return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
-  DeviceState* st = nullptr;
-  int rc = current_state(&st);
+  int rc = check_generate(n, yuvs, p010s, hdr_tf, metadata, dests, 1);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
 
   fill_generate_metadata(hdr_tf, metadata);
@@ -3720,23 +3842,19 @@ int uhdr_hip_generate_probe(int phase, int n, const uhdr_hip_image_t* yuvs, cons
     return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (n <= 0 || yuvs == nullptr || p010s == nullptr || dests == nullptr || metadata == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
   if ((phase == 0 && route == nullptr) || (phase == 1 && headers == nullptr)) return UHDR_HIP_ERROR_BAD_PTR;
-  for (int i = 0; i < n; ++i) {
-    const int rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, metadata, &dests[i]);
-    if (rc != UHDR_HIP_NO_ERROR) return rc;
-    if (dests[i].data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  }
+  int rc = check_generate(n, yuvs, p010s, hdr_tf, metadata, dests, 1);   // (n >= 1: validate_generate has seen the transfer function)
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   fill_generate_metadata(hdr_tf, metadata);
   int m = 0;
   uint32_t r[UHDR_HIP_GENERATE_ROUTE_WORDS];
   if (phase == 0) {   // the plan of the first chunk: host arithmetic only, no device state
-    const int rc = generate_chunk(nullptr, nullptr, n, yuvs, p010s, hdr_tf, metadata, dests, sdr_is_601, generate_mode,
-                                  content_minmax, 0, 0u, &m, r, nullptr);
+    rc = generate_chunk(nullptr, nullptr, n, yuvs, p010s, hdr_tf, metadata, dests, sdr_is_601, generate_mode, content_minmax, 0, 0u,
+                        &m, r, nullptr);
     if (rc == UHDR_HIP_NO_ERROR) memcpy(route, r, sizeof(r));
     return rc;
   }
   DeviceState* st = nullptr;
-  int rc = current_state(&st);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   // one kernel of the pair by itself: only where the call IS one such pair (the workspace is handed from one phase to the other)
   rc = generate_chunk(nullptr, nullptr, n, yuvs, p010s, hdr_tf, metadata, dests, sdr_is_601, generate_mode, content_minmax, 0, 0u,
                       &m, r, nullptr);
@@ -3750,43 +3868,20 @@ int uhdr_hip_generate_probe(int phase, int n, const uhdr_hip_image_t* yuvs, cons
 // RGBA8888 and every chunk one k_generate_rgb launch on the exact path
 int uhdr_hip_generate_gainmap_rgb_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf,
                                         uhdr_hip_metadata_t* metadata, uhdr_hip_image_t* dests, int sdr_is_601, void* stream) {
-  if (n < 0 || (n > 0 && (yuvs == nullptr || p010s == nullptr || dests == nullptr)) || metadata == nullptr)
-    return UHDR_HIP_ERROR_BAD_PTR;
-  for (int i = 0; i < n; ++i) {
-    const int rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, metadata, &dests[i]);
-    if (rc != UHDR_HIP_NO_ERROR) return rc;
-    if (dests[i].data == nullptr || !al(dests[i].data, 4)) return UHDR_HIP_ERROR_BAD_PTR;
-  }
-  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ)
-    return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
-  DeviceState* st = nullptr;
-  const int rc = current_state(&st);
+  int rc = check_generate(n, yuvs, p010s, hdr_tf, metadata, dests, 4);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   fill_generate_metadata(hdr_tf, metadata);
   int i = 0;
   while (i < n) {
-    // chunk = up to kMaxChunk consecutive images of identical size, gamuts and alignment class
     const uhdr_hip_image_t& y0 = yuvs[i];
     const GenConsts c = generate_consts(y0.colorGamut, p010s[i].colorGamut, hdr_tf, sdr_is_601, y0.width, y0.height, *metadata);
     GenBatch b;
-    int m = 0;
-    bool aligned = true;
-    while (i + m < n && m < kMaxChunk) {
-      const uhdr_hip_image_t& y = yuvs[i + m];
-      if (y.width != y0.width || y.height != y0.height || y.colorGamut != y0.colorGamut ||
-          p010s[i + m].colorGamut != p010s[i].colorGamut)
-        break;
-      b.img[m] = gen_image(y, p010s[i + m], dests[i + m].data);
-      const bool a = gen_aligned(b.img[m], c.width, c.height) && al(b.img[m].map, 8);   // (the pair of a thread is one 8-byte store)
-      if (m == 0) aligned = a;
-      else if (a != aligned) break;
-      fill_generate_dest(&y, &dests[i + m]);
-      dests[i + m].pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
-      ++m;
-    }
-    HIP_TRY(launch_generate_rgb(c, b, m, hdr_tf, aligned, s));
-    i += m;
+    const Chunk ch = gen_chunk(i, n, yuvs, p010s, dests, b, rgba_pair_aligned, 4, true);
+    HIP_TRY(launch_generate_rgb(c, b, ch.m, hdr_tf, ch.cls, s));
+    i += ch.m;
   }
   return UHDR_HIP_NO_ERROR;
 }
@@ -3797,57 +3892,32 @@ int uhdr_hip_apply_gainmap_rgb_batch(int n, const uhdr_hip_image_t* yuvs, const 
                                      int output_format, float max_display_boost, uhdr_hip_image_t* dests, int apply_mode, void* stream) {
   if (n < 0 || (n > 0 && (yuvs == nullptr || maps == nullptr || dests == nullptr)) || metadata == nullptr)
     return UHDR_HIP_ERROR_BAD_PTR;
-  auto stride_of = [](const uhdr_hip_image_t& mp) { return mp.luma_stride == 0 ? mp.width : mp.luma_stride; };
   for (int i = 0; i < n; ++i) {
     const int rc = validate_apply(&yuvs[i], &maps[i], metadata, &dests[i]);
     if (rc != UHDR_HIP_NO_ERROR) return rc;
     if (!al(maps[i].data, 4)) return UHDR_HIP_ERROR_BAD_PTR;
-    if (stride_of(maps[i]) < maps[i].width || stride_of(maps[i]) > 0xFFFFFFFFull) return UHDR_HIP_ERROR_INVALID_STRIDE;
+    if (row_stride(maps[i]) < maps[i].width || row_stride(maps[i]) > 0xFFFFFFFFull) return UHDR_HIP_ERROR_INVALID_STRIDE;
   }
   if (apply_mode != UHDR_HIP_APPLY_FAST && apply_mode != UHDR_HIP_APPLY_EXACT)   // (LUT and EXACT_UNFILTERED among the rest)
     return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   DeviceState* st = nullptr;
-  int rc = current_state(&st);
+  const int rc = current_state(&st);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool writes = apply_writes(output_format);
   for (int i = 0; i < n; ++i)
     if (writes && dests[i].data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  int i = 0;
-  while (i < n) {
-    const uhdr_hip_image_t& y0 = yuvs[i];
-    const uhdr_hip_image_t& m0 = maps[i];
-    const int scale = (int)(y0.width / m0.width);
-    const float* idw = nullptr;
-    float* idw_transient = nullptr;
-    if ((rc = idw_for_scale(st, scale, &idw, &idw_transient)) != UHDR_HIP_NO_ERROR) return rc;
-    struct FreeAfter {   // a table too large to keep: freed when this chunk's launches have finished
-      float* p; hipStream_t s;
-      ~FreeAfter() { if (p) { (void)hipStreamSynchronize(s); (void)hipFree(p); } }
-    } free_after{idw_transient, s};
-    AppConsts c = apply_consts(y0, m0, *metadata, max_display_boost, idw);
-    c.map_stride = (uint32_t)stride_of(m0);
-    c.tab = st->lut;
-    AppBatch b;
-    int m = 0;
-    while (i + m < n && m < kMaxChunk) {   // equal sizes and map strides share a launch
-      const uhdr_hip_image_t& y = yuvs[i + m];
-      const uhdr_hip_image_t& mp = maps[i + m];
-      if (y.width != y0.width || y.height != y0.height || mp.width != m0.width || mp.height != m0.height || stride_of(mp) != stride_of(m0)) break;
-      b.img[m] = app_image(y, mp, dests[i + m].data);
-      fill_apply_dest(&y, &dests[i + m]);
-      ++m;
-    }
-    if (writes) HIP_TRY(launch_apply_rgb(c, b, m, output_format, apply_mode == UHDR_HIP_APPLY_EXACT, s));
-    i += m;
-  }
-  return UHDR_HIP_NO_ERROR;
+  return apply_pixel_chunks(st, s, n, yuvs, maps, *metadata, max_display_boost, dests, true, writes,
+                            [&](const AppConsts& c, const AppBatch& b, int m) -> int {
+                              HIP_TRY(launch_apply_rgb(c, b, m, output_format, apply_mode == UHDR_HIP_APPLY_EXACT, s));
+                              return UHDR_HIP_NO_ERROR;
+                            });
 }
 
 // ---- content-adaptive generate -----------------------------------------------------------------------
 int uhdr_hip_adaptive_boost_range(int hdr_tf, float g_min, float g_max, float* lo, float* hi) {
   if (lo == nullptr || hi == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (!tf_known(hdr_tf)) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
   adaptive_range(hdr_tf, g_min, g_max, lo, hi);
   return UHDR_HIP_NO_ERROR;
 }
@@ -3870,22 +3940,15 @@ int uhdr_hip_generate_adaptive_workspace_bytes(int n, const uhdr_hip_image_t* yu
 int uhdr_hip_generate_gainmap_adaptive_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf,
                                              uhdr_hip_image_t* dests, int sdr_is_601, int boost_scope, float* content_minmax,
                                              float* boost_range, void* workspace, size_t workspace_bytes, void* stream) {
-  if (n < 0 || (n > 0 && (yuvs == nullptr || p010s == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
   uhdr_hip_metadata_t md;   // (the checks of uhdr_hip_generate_gainmap_batch_ex take one)
-  for (int i = 0; i < n; ++i) {
-    const int rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, &md, &dests[i]);
-    if (rc != UHDR_HIP_NO_ERROR) return rc;
-    if (dests[i].data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  }
-  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ)
-    return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  int rc = check_generate(n, yuvs, p010s, hdr_tf, &md, dests, 1);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   if (!valid_boost_scope(boost_scope)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (n > 0 && (boost_range == nullptr || workspace == nullptr || !al(workspace, 16))) return UHDR_HIP_ERROR_BAD_PTR;
   if (workspace_bytes < adaptive_layout(n, yuvs).total) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
   if (n == 0) return UHDR_HIP_NO_ERROR;
   DeviceState* st = nullptr;
-  const int rc = current_state(&st);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   return adaptive_enqueue(n, yuvs, p010s, hdr_tf, dests, sdr_is_601, boost_scope, content_minmax, boost_range, workspace, nullptr,
                           nullptr, true, static_cast<hipStream_t>(stream));
 }
@@ -3914,31 +3977,15 @@ int uhdr_hip_apply_gainmap_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr
   while (i < n) {
     const uhdr_hip_image_t& y0 = yuvs[i];
     const uhdr_hip_image_t& m0 = maps[i];
-    const int scale = (int)(y0.width / m0.width);
-    const float* idw = nullptr;
-    float* idw_transient = nullptr;
-    if ((rc = idw_for_scale(st, scale, &idw, &idw_transient)) != UHDR_HIP_NO_ERROR) return rc;
-    struct FreeAfter {   // a table too large to keep: freed when this chunk's launches have finished
-      float* p; hipStream_t s;
-      ~FreeAfter() { if (p) { (void)hipStreamSynchronize(s); (void)hipFree(p); } }
-    } free_after{idw_transient, s};
-    AppConsts c = apply_consts(y0, m0, *metadata, max_display_boost, idw);
+    IdwLease table;
+    if ((rc = table.take(st, (int)(y0.width / m0.width), s)) != UHDR_HIP_NO_ERROR) return rc;
+    AppConsts c = apply_consts(y0, m0, *metadata, max_display_boost, table.idw);
     c.lut = apply_mode == UHDR_HIP_APPLY_LUT ? st->lut : nullptr;
     c.tab = st->lut;
     AppBatch b;
-    int m = 0;
-    bool fast = true;
-    while (i + m < n && m < kMaxChunk) {
-      const uhdr_hip_image_t& y = yuvs[i + m];
-      const uhdr_hip_image_t& mp = maps[i + m];
-      if (y.width != y0.width || y.height != y0.height || mp.width != m0.width || mp.height != m0.height) break;
-      b.img[m] = app_image(y, mp, dests[i + m].data);
-      const bool f = app_fast_s4(c, b.img[m]);
-      if (m == 0) fast = f;
-      else if (f != fast) break;
-      fill_apply_dest(&y, &dests[i + m]);
-      ++m;
-    }
+    const Chunk ch = app_chunk(i, n, yuvs, maps, dests, b, &c, false);
+    const int m = ch.m;
+    const bool fast = ch.cls;
     // EXACT: f32 estimate, then the exact path on the pixels it leaves in doubt.  The estimate's error bounds are measured for
     // |log2 boost| <= 32 (tests/test_gpu_exact_filter.py); beyond that every pixel takes the exact path.
     std::unique_lock<std::mutex> pair_lk(g_pair_mu, std::defer_lock);
@@ -3990,7 +4037,6 @@ int uhdr_hip_apply_gainmap_md_batch(int n, const uhdr_hip_image_t* yuvs, const u
     return rgb ? uhdr_hip_apply_gainmap_rgb_batch(n, yuvs, maps, metadata, output_format, max_display_boost, dests, apply_mode, stream)
                : uhdr_hip_apply_gainmap_batch(n, yuvs, maps, metadata, output_format, max_display_boost, dests, apply_mode, stream);
   // a one-plane map's rows are `width` bytes, an RGBA map's luma_stride pixels (0 = width)
-  auto stride_of = [rgb](const uhdr_hip_image_t& mp) { return (!rgb || mp.luma_stride == 0) ? mp.width : mp.luma_stride; };
   for (int i = 0; i < n; ++i) {   // validate_apply's scale-factor checks, then uhdr_hip_apply_gainmap_rgb_batch's of the map
     const uhdr_hip_image_t& y = yuvs[i];
     const uhdr_hip_image_t& mp = maps[i];
@@ -3998,7 +4044,7 @@ int uhdr_hip_apply_gainmap_md_batch(int n, const uhdr_hip_image_t* yuvs, const u
     if (y.width % mp.width != 0 || y.height % mp.height != 0) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
     if (y.width * mp.height != y.height * mp.width) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
     if (rgb && !al(mp.data, 4)) return UHDR_HIP_ERROR_BAD_PTR;
-    if (rgb && (stride_of(mp) < mp.width || stride_of(mp) > 0xFFFFFFFFull)) return UHDR_HIP_ERROR_INVALID_STRIDE;
+    if (rgb && (row_stride(mp) < mp.width || row_stride(mp) > 0xFFFFFFFFull)) return UHDR_HIP_ERROR_INVALID_STRIDE;
   }
   // FAST and EXACT select the one arithmetic there is: EXACT promises the reference's bytes, and the reference refuses this metadata
   if (apply_mode != UHDR_HIP_APPLY_FAST && apply_mode != UHDR_HIP_APPLY_EXACT) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
@@ -4009,80 +4055,30 @@ int uhdr_hip_apply_gainmap_md_batch(int n, const uhdr_hip_image_t* yuvs, const u
   for (int i = 0; i < n; ++i)
     if (writes && dests[i].data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
   const AppMdConsts mc = apply_md_consts(*metadata, max_display_boost);
-  int i = 0;
-  while (i < n) {
-    const uhdr_hip_image_t& y0 = yuvs[i];
-    const uhdr_hip_image_t& m0 = maps[i];
-    const int scale = (int)(y0.width / m0.width);
-    const float* idw = nullptr;
-    float* idw_transient = nullptr;
-    if ((rc = idw_for_scale(st, scale, &idw, &idw_transient)) != UHDR_HIP_NO_ERROR) return rc;
-    struct FreeAfter {   // a table too large to keep: freed when this chunk's launches have finished
-      float* p; hipStream_t s;
-      ~FreeAfter() { if (p) { (void)hipStreamSynchronize(s); (void)hipFree(p); } }
-    } free_after{idw_transient, s};
-    AppConsts c = apply_consts(y0, m0, *metadata, max_display_boost, idw);
-    c.map_stride = (uint32_t)stride_of(m0);
-    c.tab = st->lut;
-    AppBatch b;
-    int m = 0;
-    while (i + m < n && m < kMaxChunk) {
-      const uhdr_hip_image_t& y = yuvs[i + m];
-      const uhdr_hip_image_t& mp = maps[i + m];
-      if (y.width != y0.width || y.height != y0.height || mp.width != m0.width || mp.height != m0.height || stride_of(mp) != stride_of(m0)) break;
-      b.img[m] = app_image(y, mp, dests[i + m].data);
-      fill_apply_dest(&y, &dests[i + m]);
-      ++m;
-    }
-    if (writes) HIP_TRY(launch_apply_md(c, mc, b, m, output_format, rgb, s));
-    i += m;
-  }
-  return UHDR_HIP_NO_ERROR;
+  return apply_pixel_chunks(st, s, n, yuvs, maps, *metadata, max_display_boost, dests, rgb, writes,
+                            [&](const AppConsts& c, const AppBatch& b, int m) -> int {
+                              HIP_TRY(launch_apply_md(c, mc, b, m, output_format, rgb, s));
+                              return UHDR_HIP_NO_ERROR;
+                            });
 }
 
 // uhdr_hip_generate_gainmap_rgb_batch's chunks; every chunk one k_generate_md launch on the exact path
 int uhdr_hip_generate_gainmap_md_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf,
                                        const uhdr_hip_metadata_t* md_in, uhdr_hip_image_t* dests, int sdr_is_601, int rgb, void* stream) {
-  if (n < 0 || (n > 0 && (yuvs == nullptr || p010s == nullptr || dests == nullptr)) || md_in == nullptr)
-    return UHDR_HIP_ERROR_BAD_PTR;
-  for (int i = 0; i < n; ++i) {
-    if (yuvs[i].data == nullptr || yuvs[i].chroma_data == nullptr || p010s[i].data == nullptr || p010s[i].chroma_data == nullptr ||
-        dests[i].data == nullptr || (rgb != 0 && !al(dests[i].data, 4)))
-      return UHDR_HIP_ERROR_BAD_PTR;
-  }
-  int rc = validate_md(md_in);
+  int rc = check_generate_md(n, yuvs, p010s, hdr_tf, md_in, dests, rgb != 0 ? 4 : 1);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
-  for (int i = 0; i < n; ++i)
-    if ((rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, md_in, &dests[i])) != UHDR_HIP_NO_ERROR) return rc;
-  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ)
-    return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
   DeviceState* st = nullptr;
   if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   int i = 0;
   while (i < n) {
-    // chunk = up to kMaxChunk consecutive images of identical size, gamuts and alignment class
     const uhdr_hip_image_t& y0 = yuvs[i];
     const GenConsts c = generate_consts(y0.colorGamut, p010s[i].colorGamut, hdr_tf, sdr_is_601, y0.width, y0.height, *md_in);
     const GenMdConsts mc = generate_md_consts(*md_in, c);
     GenBatch b;
-    int m = 0;
-    bool aligned = true;
-    while (i + m < n && m < kMaxChunk) {
-      const uhdr_hip_image_t& y = yuvs[i + m];
-      if (y.width != y0.width || y.height != y0.height || y.colorGamut != y0.colorGamut ||
-          p010s[i + m].colorGamut != p010s[i].colorGamut)
-        break;
-      b.img[m] = gen_image(y, p010s[i + m], dests[i + m].data);
-      const bool a = gen_aligned(b.img[m], c.width, c.height) && (rgb == 0 || al(b.img[m].map, 8));   // (a thread's pair is one store)
-      if (m == 0) aligned = a;
-      else if (a != aligned) break;
-      fill_generate_dest(&y, &dests[i + m]);
-      if (rgb != 0) dests[i + m].pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
-      ++m;
-    }
-    HIP_TRY(launch_generate_md(c, mc, b, m, hdr_tf, aligned, rgb != 0, s));
-    i += m;
+    const Chunk ch = gen_chunk(i, n, yuvs, p010s, dests, b, rgb != 0 ? rgba_pair_aligned : no_more, 4, rgb != 0);
+    HIP_TRY(launch_generate_md(c, mc, b, ch.m, hdr_tf, ch.cls, rgb != 0, s));
+    i += ch.m;
   }
   return UHDR_HIP_NO_ERROR;
 }
@@ -4106,19 +4102,17 @@ int uhdr_hip_generate_gainmap_packed_batch(int n, const uhdr_hip_image_t* sdrs, 
   }
   int rc;
   if (md_in != nullptr && (rc = validate_md(md_in)) != UHDR_HIP_NO_ERROR) return rc;
-  auto stride_of = [](const uhdr_hip_image_t& im) { return im.luma_stride == 0 ? im.width : im.luma_stride; };
-  const bool tf_known = hdr_tf == UHDR_HIP_TF_LINEAR || hdr_tf == UHDR_HIP_TF_HLG || hdr_tf == UHDR_HIP_TF_PQ;
   for (int i = 0; i < n; ++i) {   // validate_generate's order around the packed images' own checks
     const uhdr_hip_image_t& sd = sdrs[i];
     const uhdr_hip_image_t& hd = hdrs[i];
-    if (stride_of(sd) < sd.width || stride_of(hd) < hd.width || stride_of(sd) > 0xFFFFFFFFull || stride_of(hd) > 0xFFFFFFFFull)
+    if (row_stride(sd) < sd.width || row_stride(hd) < hd.width || row_stride(sd) > 0xFFFFFFFFull || row_stride(hd) > 0xFFFFFFFFull)
       return UHDR_HIP_ERROR_INVALID_STRIDE;
     if (sd.width != hd.width || sd.height != hd.height) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
     if (sd.colorGamut == UHDR_HIP_CG_UNSPECIFIED || hd.colorGamut == UHDR_HIP_CG_UNSPECIFIED) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
     if (f16 ? hdr_tf != UHDR_HIP_TF_LINEAR : (hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ)) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
     if (!valid_gamut(sd.colorGamut) || !valid_gamut(hd.colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
   }
-  if (!tf_known) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (!tf_known(hdr_tf)) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
   DeviceState* st = nullptr;
   if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -4128,34 +4122,29 @@ int uhdr_hip_generate_gainmap_packed_batch(int n, const uhdr_hip_image_t* sdrs, 
   if (md_out != nullptr) *md_out = md;
   int i = 0;
   while (i < n) {
-    // chunk = up to kMaxChunk consecutive pairs of identical size, gamuts and alignment class
     const uhdr_hip_image_t& s0 = sdrs[i];
     const GenConsts c = generate_consts(s0.colorGamut, hdrs[i].colorGamut, hdr_tf, 0, s0.width, s0.height, md);
     const GenMdConsts mc = generate_md_consts(md, c);
     PackedBatch b;
-    int m = 0;
-    bool aligned = true;
-    while (i + m < n && m < kMaxChunk) {
-      const uhdr_hip_image_t& sd = sdrs[i + m];
-      const uhdr_hip_image_t& hd = hdrs[i + m];
-      if (sd.width != s0.width || sd.height != s0.height || sd.colorGamut != s0.colorGamut || hd.colorGamut != hdrs[i].colorGamut) break;
-      PackedImage& p = b.img[m];
-      p.sdr = static_cast<const uint32_t*>(sd.data);
-      p.hdr = hd.data;
-      p.map = static_cast<uint8_t*>(dests[i + m].data);
-      p.sdr_stride = (uint32_t)stride_of(sd);
-      p.hdr_stride = (uint32_t)stride_of(hd);
-      // 16-byte row pieces of both images (a dword format: 4 pixels, F16: 2) and the pair's bytes as one store
-      const bool a = c.width % 8u == 0 && al(p.sdr, 16) && p.sdr_stride % 4u == 0 && al(p.hdr, 16) && p.hdr_stride % (f16 ? 2u : 4u) == 0 &&
-                     al(p.map, rgb != 0 ? 8 : 2);
-      if (m == 0) aligned = a;
-      else if (a != aligned) break;
-      fill_generate_dest(&sd, &dests[i + m]);
-      if (rgb != 0) dests[i + m].pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
-      ++m;
-    }
-    HIP_TRY(launch_generate_packed(c, mc, b, m, hdr_tf, f16, aligned, rgb != 0, s));
-    i += m;
+    const Chunk ch = form_chunk(i, n,
+                                [&](int j) {
+                                  return sdrs[j].width == s0.width && sdrs[j].height == s0.height && sdrs[j].colorGamut == s0.colorGamut &&
+                                         hdrs[j].colorGamut == hdrs[i].colorGamut;
+                                },
+                                [&](int j, int m) {
+                                  PackedImage& p = b.img[m];
+                                  p.sdr = static_cast<const uint32_t*>(sdrs[j].data);
+                                  p.hdr = hdrs[j].data;
+                                  p.map = static_cast<uint8_t*>(dests[j].data);
+                                  p.sdr_stride = (uint32_t)row_stride(sdrs[j]);
+                                  p.hdr_stride = (uint32_t)row_stride(hdrs[j]);
+                                  // 16-byte row pieces of both images (a dword format: 4 pixels, F16: 2) and the pair's bytes as one store
+                                  return c.width % 8u == 0 && al(p.sdr, 16) && p.sdr_stride % 4u == 0 && al(p.hdr, 16) &&
+                                         p.hdr_stride % (f16 ? 2u : 4u) == 0 && al(p.map, rgb != 0 ? 8 : 2);
+                                });
+    for (int k = 0; k < ch.m; ++k) fill_generate_dest(&sdrs[i + k], &dests[i + k], 4, rgb != 0);
+    HIP_TRY(launch_generate_packed(c, mc, b, ch.m, hdr_tf, f16, ch.cls, rgb != 0, s));
+    i += ch.m;
   }
   return UHDR_HIP_NO_ERROR;
 }
@@ -4183,29 +4172,15 @@ static int generate_scaled(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_i
     if (rc == UHDR_HIP_NO_ERROR && md_out != nullptr) *md_out = md;
     return rc;
   }
-  const bool tf_known = hdr_tf == UHDR_HIP_TF_LINEAR || hdr_tf == UHDR_HIP_TF_HLG || hdr_tf == UHDR_HIP_TF_PQ;
-  auto too_small = [&](const uhdr_hip_image_t& y) { return y.width / sf == 0 || y.height / sf == 0; };
+  // the image has no map pixel at this factor
+  const ImageHook too_small = [sf](const uhdr_hip_image_t& y) {
+    return y.width / sf == 0 || y.height / sf == 0 ? UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR : UHDR_HIP_NO_ERROR;
+  };
   uhdr_hip_metadata_t md;
-  if (md_in != nullptr) {   // uhdr_hip_generate_gainmap_md_batch's order
-    for (int i = 0; i < n; ++i) {
-      if (yuvs[i].data == nullptr || yuvs[i].chroma_data == nullptr || p010s[i].data == nullptr || p010s[i].chroma_data == nullptr ||
-          dests[i].data == nullptr || (rgb != 0 && !al(dests[i].data, 4)))
-        return UHDR_HIP_ERROR_BAD_PTR;
-    }
-    if ((rc = validate_md(md_in)) != UHDR_HIP_NO_ERROR) return rc;
-    for (int i = 0; i < n; ++i) {
-      if ((rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, md_in, &dests[i])) != UHDR_HIP_NO_ERROR) return rc;
-      if (too_small(yuvs[i])) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
-    }
-    md = *md_in;
-  } else {                  // uhdr_hip_generate_gainmap_batch's / _rgb_batch's
-    for (int i = 0; i < n; ++i) {
-      if ((rc = validate_generate(&yuvs[i], &p010s[i], hdr_tf, &md, &dests[i])) != UHDR_HIP_NO_ERROR) return rc;
-      if (dests[i].data == nullptr || (rgb != 0 && !al(dests[i].data, 4))) return UHDR_HIP_ERROR_BAD_PTR;
-      if (too_small(yuvs[i])) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
-    }
-  }
-  if (!tf_known) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (md_in != nullptr) md = *md_in;
+  rc = md_in != nullptr ? check_generate_md(n, yuvs, p010s, hdr_tf, md_in, dests, rgb != 0 ? 4 : 1, too_small)
+                        : check_generate(n, yuvs, p010s, hdr_tf, &md, dests, rgb != 0 ? 4 : 1, too_small);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   DeviceState* st = nullptr;
   if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -4216,9 +4191,9 @@ static int generate_scaled(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_i
   sc.area = (float)(map_scale_factor * map_scale_factor);
   sc.doubt_count = doubt_count;
   const uint32_t strip = (sc.s == 1u || sc.s == 2u || sc.s == 8u) ? 8u / sc.s : 0u;   // map pixels a thread of the aligned forms stores at once
+  const size_t strip_bytes = (size_t)strip * (rgb != 0 ? 4u : 1u);
   int i = 0;
   while (i < n) {
-    // chunk = up to kMaxChunk consecutive images of identical size, gamuts and alignment class
     const uhdr_hip_image_t& y0 = yuvs[i];
     GenConsts c = generate_consts(y0.colorGamut, p010s[i].colorGamut, hdr_tf, sdr_is_601, y0.width, y0.height, md);
     c.map_w = (uint32_t)(y0.width / sf);
@@ -4229,27 +4204,11 @@ static int generate_scaled(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_i
     const bool filter = md_in == nullptr && rgb == 0 && c.flt_delta < 0.25f && c.min_boost >= 0.25f && c.max_boost <= 64.0f;
     const int mode = filter ? 0 : (rgb != 0 ? 2 : 1);
     GenBatch b;
-    int m = 0;
-    bool aligned = true;
-    while (i + m < n && m < kMaxChunk) {
-      const uhdr_hip_image_t& y = yuvs[i + m];
-      if (y.width != y0.width || y.height != y0.height || y.colorGamut != y0.colorGamut ||
-          p010s[i + m].colorGamut != p010s[i].colorGamut)
-        break;
-      b.img[m] = gen_image(y, p010s[i + m], dests[i + m].data);
-      const bool a = strip != 0u && gen_aligned(b.img[m], c.width, c.height) && c.height % 2u == 0 &&
-                     al(b.img[m].map, (size_t)strip * (rgb != 0 ? 4u : 1u) > 8u ? 8u : (size_t)strip * (rgb != 0 ? 4u : 1u));
-      if (m == 0) aligned = a;
-      else if (a != aligned) break;
-      fill_generate_dest(&y, &dests[i + m]);
-      dests[i + m].width = c.map_w;
-      dests[i + m].height = c.map_h;
-      dests[i + m].luma_stride = c.map_w;
-      if (rgb != 0) dests[i + m].pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
-      ++m;
-    }
-    HIP_TRY(launch_generate_scaled(c, mc, sc, b, m, hdr_tf, aligned, mode, s));
-    i += m;
+    const Chunk ch = gen_chunk(i, n, yuvs, p010s, dests, b,
+                               [&](const GenImage& g) { return strip != 0u && c.height % 2u == 0 && al(g.map, strip_bytes > 8u ? 8u : strip_bytes); },
+                               sf, rgb != 0);
+    HIP_TRY(launch_generate_scaled(c, mc, sc, b, ch.m, hdr_tf, ch.cls, mode, s));
+    i += ch.m;
   }
   return UHDR_HIP_NO_ERROR;
 }
@@ -4289,15 +4248,10 @@ int uhdr_hip_generate_gainmap_ex(const uhdr_hip_image_t* yuv, const uhdr_hip_ima
   StageSet* ss = lease.get();
   if (ss == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  uhdr_hip_image_t dy, dp, dm = *dest;
-  if ((rc = stage_yuv420_in(ss, 0, *yuv, &dy, s)) != 0) return rc;
-  if ((rc = stage_p010_in(ss, 2, *p010, &dp, s)) != 0) return rc;
-  const size_t mw = yuv->width / 4, mh = yuv->height / 4;
-  if ((rc = stage_reserve(ss, 4, mw * mh)) != 0) return rc;
-  dm.data = ss->stage[4];
-  rc = uhdr_hip_generate_gainmap_batch_ex(1, &dy, &dp, hdr_tf, metadata, &dm, sdr_is_601, generate_mode, nullptr, stream);
+  rc = generate_through_stage(ss, yuv, p010, dest, s, [&](const uhdr_hip_image_t& dy, const uhdr_hip_image_t& dp, uhdr_hip_image_t& dm) {
+    return uhdr_hip_generate_gainmap_batch_ex(1, &dy, &dp, hdr_tf, metadata, &dm, sdr_is_601, generate_mode, nullptr, stream);
+  });
   if (rc != UHDR_HIP_NO_ERROR) return rc;
-  if (mw * mh) HIP_TRY(hipMemcpyAsync(dest->data, dm.data, mw * mh, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   fill_generate_dest(yuv, dest);
   return UHDR_HIP_NO_ERROR;
@@ -4316,23 +4270,19 @@ int uhdr_hip_generate_gainmap_adaptive(const uhdr_hip_image_t* yuv, const uhdr_h
   StageSet* ss = lease.get();
   if (ss == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
-  uhdr_hip_image_t dy = *yuv, dp = *p010, dm = *dest;
-  const size_t mw = yuv->width / 4, mh = yuv->height / 4;
-  if (host) {
-    if ((rc = stage_yuv420_in(ss, 0, *yuv, &dy, s)) != 0) return rc;
-    if ((rc = stage_p010_in(ss, 2, *p010, &dp, s)) != 0) return rc;
-    if ((rc = stage_reserve(ss, 4, mw * mh)) != 0) return rc;
-    dm.data = ss->stage[4];
-  }
-  const size_t ws_bytes = adaptive_layout(1, &dy).total;
-  if ((rc = stage_reserve(ss, 5, ws_bytes + 256)) != 0) return rc;
-  uint8_t* ws = static_cast<uint8_t*>(ss->stage[5]);
-  float* dev_range = reinterpret_cast<float*>(ws + ws_bytes);
-  rc = adaptive_enqueue(1, &dy, &dp, hdr_tf, &dm, sdr_is_601, UHDR_HIP_BOOST_PER_IMAGE, nullptr, dev_range, ws, nullptr, nullptr, true, s);
+  float* dev_range = nullptr;
+  auto run = [&](const uhdr_hip_image_t& dy, const uhdr_hip_image_t& dp, uhdr_hip_image_t& dm) {
+    const size_t ws_bytes = adaptive_layout(1, &dy).total;
+    const int wrc = stage_reserve(ss, 5, ws_bytes + 256);
+    if (wrc != 0) return wrc;
+    uint8_t* ws = static_cast<uint8_t*>(ss->stage[5]);
+    dev_range = reinterpret_cast<float*>(ws + ws_bytes);
+    return adaptive_enqueue(1, &dy, &dp, hdr_tf, &dm, sdr_is_601, UHDR_HIP_BOOST_PER_IMAGE, nullptr, dev_range, ws, nullptr, nullptr, true, s);
+  };
+  uhdr_hip_image_t dm = *dest;
+  rc = mem_space != UHDR_HIP_MEM_DEVICE ? generate_through_stage(ss, yuv, p010, dest, s, run) : run(*yuv, *p010, dm);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   float range[2];
-  if (host && mw * mh) HIP_TRY(hipMemcpyAsync(dest->data, dm.data, mw * mh, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipMemcpyAsync(range, dev_range, sizeof(range), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   fill_adaptive_metadata(range[0], range[1], metadata);
@@ -4511,7 +4461,7 @@ int tonemap_sdr_check(const uhdr_hip_image_t& src, const uhdr_hip_image_t& dest)
 ToneImage tone_sdr_image(const uhdr_hip_image_t& sd, const uhdr_hip_image_t& dd, bool* aligned) {
   bool unused;
   ToneImage t = tone_image(sd, dd, &unused);
-  if (sd.luma_stride == 0) t.sy_stride = (uint32_t)sd.width;  // gainmapmath.cpp:585
+  t.sy_stride = (uint32_t)row_stride(sd);
   *aligned = t.width % 16u == 0 && al(t.sy, 16) && t.sy_stride % 8u == 0 && al(t.suv, 16) && t.suv_stride % 8u == 0 && al(t.dy, 16) &&
              t.dy_stride % 16u == 0 && al(t.du, 8) && al(t.dv, 8) && t.dc_stride % 8u == 0;
   return t;
@@ -4533,7 +4483,7 @@ ToneSdrConsts tone_sdr_consts(int gamut, int hdr_tf, float* headroom) {
 
 int uhdr_hip_tonemap_headroom(int hdr_tf, float gamma_max, float peak_nits, float* headroom) {
   if (headroom == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
-  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (!tf_known(hdr_tf)) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
   if (!valid_peak_nits(peak_nits)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   *headroom = tone_headroom(hdr_tf, gamma_max, peak_nits);
   return UHDR_HIP_NO_ERROR;
@@ -4548,7 +4498,7 @@ int uhdr_hip_tonemap_sdr_batch(int n, const uhdr_hip_image_t* srcs, uhdr_hip_ima
     const int rc = tonemap_check(&srcs[i], &dests[i]);
     if (rc != UHDR_HIP_NO_ERROR) return rc;
   }
-  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (!tf_known(hdr_tf)) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
   if (!valid_tonemap_op(tonemap_op)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (tonemap_op == UHDR_HIP_TONEMAP_SHIFT) return uhdr_hip_tonemap_batch(n, srcs, dests, stream);
   for (int i = 0; hdr_peak_nits != nullptr && i < n; ++i)
@@ -4623,7 +4573,7 @@ int uhdr_hip_tonemap_sdr(const uhdr_hip_image_t* src, uhdr_hip_image_t* dest, in
                          int mem_space, void* stream) {
   int rc = tonemap_check(src, dest);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
-  if (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  if (!tf_known(hdr_tf)) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
   if (!valid_tonemap_op(tonemap_op)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (tonemap_op == UHDR_HIP_TONEMAP_SHIFT) {   // no headroom to report
     if ((rc = uhdr_hip_tonemap(src, dest, mem_space, stream)) != UHDR_HIP_NO_ERROR) return rc;
@@ -4676,14 +4626,14 @@ int tone_packed_check(int n, const uhdr_hip_image_t* srcs, const uhdr_hip_image_
     if (!host && (!al(srcs[i].data, f16 ? 8 : 4) || !al(dests[i].data, 4))) return UHDR_HIP_ERROR_BAD_PTR;
   }
   if (n > 0 ? (f16 ? hdr_tf != UHDR_HIP_TF_LINEAR : (hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ))
-            : (hdr_tf != UHDR_HIP_TF_LINEAR && hdr_tf != UHDR_HIP_TF_HLG && hdr_tf != UHDR_HIP_TF_PQ))
+            : !tf_known(hdr_tf))
     return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
   if (tonemap_op != UHDR_HIP_TONEMAP_REINHARD_MAXRGB) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;   // (TONEMAP_SHIFT means nothing here)
   for (int i = 0; peaks != nullptr && i < n; ++i)
     if (!valid_peak_nits(peaks[i])) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (need_headroom && n > 0 && headroom == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
   for (int i = 0; i < n; ++i) {
-    const size_t ss = packed_stride(srcs[i], srcs[i].width), ds = packed_stride(dests[i], srcs[i].width);
+    const size_t ss = row_stride(srcs[i]), ds = packed_stride(dests[i], srcs[i].width);
     if (ss < srcs[i].width || ds < srcs[i].width || ss > 0xFFFFFFFFull || ds > 0xFFFFFFFFull) return UHDR_HIP_ERROR_INVALID_STRIDE;
     if (!valid_gamut(srcs[i].colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
   }
@@ -4728,7 +4678,7 @@ int uhdr_hip_tonemap_packed_batch(int n, const uhdr_hip_image_t* srcs, uhdr_hip_
       TonePackedImage t;
       t.src = sd.data;
       t.dst = static_cast<uint32_t*>(dests[i + m].data);
-      t.src_stride = (uint32_t)packed_stride(sd, sd.width);
+      t.src_stride = (uint32_t)row_stride(sd);
       t.dst_stride = (uint32_t)packed_stride(dests[i + m], sd.width);
       t.width = (uint32_t)sd.width; t.height = (uint32_t)sd.height;
       // 16-byte pieces of the destination (4 pixels) and what they are made of (RGBA1010102: 16 bytes, RGBA F16: 32)
@@ -4903,7 +4853,7 @@ FxJob fx_job(const uint8_t* src, uint8_t* dst, size_t rows, size_t cols, size_t 
 int fx_plan(int kind, const uhdr_hip_image_t& in, int a, int b, int c, int d, uhdr_hip_image_t* out, FxJobs* jobs) {
   const bool mono = in.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
   const size_t iw = in.width, ih = in.height;
-  const size_t ls = in.luma_stride != 0 ? in.luma_stride : iw;                 // editorhelper.cpp:44
+  const size_t ls = row_stride(in);                 // editorhelper.cpp:44
   const size_t cs = in.chroma_stride != 0 ? in.chroma_stride : (ls >> 1);      // :60-61
   const uint8_t* sy = static_cast<const uint8_t*>(in.data);
   const uint8_t* sc = in.chroma_data ? static_cast<const uint8_t*>(in.chroma_data) : sy + ls * ih;  // :66-69
@@ -4973,7 +4923,7 @@ int fx_run(int kind, const uhdr_hip_image_t* in, int a, int b, int c, int d, uhd
   if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
   const bool mono = in->pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
   const size_t iw = in->width, ih = in->height;
-  const size_t ls = in->luma_stride != 0 ? in->luma_stride : iw;
+  const size_t ls = row_stride(*in);
   const size_t cs = in->chroma_stride != 0 ? in->chroma_stride : (ls >> 1);
   const size_t luma_bytes = ih ? ls * (ih - 1) + iw : 0;
   const size_t chroma_rows = mono ? 0 : ih;  // U and V stacked (crop / resize walk them as one plane)
@@ -5076,7 +5026,7 @@ int uhdr_hip_add_effects(const uhdr_hip_image_t* in, const uhdr_hip_effect_t* ef
   if (size0) HIP_TRY(hipMemcpyAsync(dev_out, in->data, size0, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
   // the first effect reads the caller's image (any strides); host images are staged as fx_run does
   uhdr_hip_image_t last = *in;
-  const size_t ls0 = in->luma_stride != 0 ? in->luma_stride : in->width;
+  const size_t ls0 = row_stride(*in);
   const size_t cs0 = in->chroma_stride != 0 ? in->chroma_stride : (ls0 >> 1);
   if (host && n > 0) {
     const size_t luma_bytes = in->height ? ls0 * (in->height - 1) + in->width : 0;
@@ -5093,7 +5043,7 @@ int uhdr_hip_add_effects(const uhdr_hip_image_t* in, const uhdr_hip_effect_t* ef
   if ((rc = stage_reserve(st, 2, max_bytes + 64)) != 0) return rc;
   for (int i = 0; i < n; ++i) {
     const uhdr_hip_effect_t& e = effects[i];
-    const size_t lls = last.luma_stride != 0 ? last.luma_stride : last.width;
+    const size_t lls = row_stride(last);
     const bool keeps_stride = e.type == 1 || (e.type == 2 && e.a == 180);
     if (keeps_stride && (lls != last.width || (!mono && last.chroma_stride != 0 && last.chroma_stride != last.width / 2)))
       return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;   // the reference writes past its `size`-byte temporary here
@@ -5276,7 +5226,7 @@ void fx_compose(const uhdr_hip_image_t& in, const uhdr_hip_effect_t* fx, int n, 
     else if (e.type != 1 && e.type != 2) { p->status = UHDR_HIP_ERROR_BAD_PTR; return; }
   }
   const size_t iw = in.width, ih = in.height;
-  const size_t ls0 = in.luma_stride != 0 ? in.luma_stride : iw;
+  const size_t ls0 = row_stride(in);
   const size_t cs0 = in.chroma_stride != 0 ? in.chroma_stride : (ls0 >> 1);
   bool odd = !mono && ((iw | ih) & 1u) != 0;
   bool additive = iw != 0 && ih != 0 && iw < (1u << 30) && ih < (1u << 30) && ls0 < (1ull << 31) && cs0 < (1ull << 31);
@@ -5305,7 +5255,7 @@ void fx_compose(const uhdr_hip_image_t& in, const uhdr_hip_effect_t* fx, int n, 
   out.data = nullptr;
   for (int i = 0; i < n; ++i) {
     const uhdr_hip_effect_t& e = fx[i];
-    const size_t lls = last.luma_stride != 0 ? last.luma_stride : last.width;
+    const size_t lls = row_stride(last);
     const bool keeps_stride = e.type == 1 || (e.type == 2 && e.a == 180);
     if (keeps_stride && (lls != last.width || (!mono && last.chroma_stride != 0 && last.chroma_stride != last.width / 2))) { p->status = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; return; }
     if (e.type == 0 && (e.a < 0 || (size_t)e.b >= last.width || e.c < 0 || (size_t)e.d >= last.height)) { p->status = UHDR_HIP_ERROR_INVALID_CROPPING_PARAMETERS; return; }
@@ -5439,7 +5389,7 @@ int fx_items_run(std::vector<FxcItem>& items, int round, hipStream_t s) {
         const FxcItem& it = items[todo[q]];
         if (it.n_fx == 0 || !it.plan.fused) continue;
         const uhdr_hip_image_t& in = *it.in;
-        const size_t ls = in.luma_stride != 0 ? in.luma_stride : in.width;
+        const size_t ls = row_stride(in);
         const uint8_t* sy = static_cast<const uint8_t*>(in.data);
         const uint8_t* sc = in.chroma_data ? static_cast<const uint8_t*>(in.chroma_data) : sy + ls * in.height;
         for (size_t g = 0; g < it.plan.planes.size(); ++g) {
