@@ -170,6 +170,34 @@ def sampled_gain(gmap, w, h):
     return out
 
 
+def sampled_gain_by_tables(gmap, w, h):
+    """sampled_gain without a call per pixel, for the factors at which orc_sampleMapIdw -- it builds its four weight tables on every
+    call -- takes minutes: the oracle's tables (orc_fillShepardsIDW), then sampleMap's tap choice and its float32 sum
+    (gainmapmath.cpp:686-720) in numpy.  Bit-identical to sampled_gain (tests/test_gainmap_md_cpu.py holds it to that)"""
+    if gmap.ndim == 2:
+        gmap = gmap[:, :, None]
+    mh, mw, nc = gmap.shape
+    s = w // mw
+    fill = O.load().orc_fillShepardsIDW
+    tables = np.empty((4, s, s, 4), F)   # all taps, no right tap, no bottom tap, the corner
+    for t, (inc_r, inc_b) in enumerate(((1, 1), (0, 1), (1, 0), (0, 0))):
+        fill(tables[t].ctypes.data_as(C.POINTER(C.c_float)), s, inc_r, inc_b)
+    x, y = np.arange(w), np.arange(h)
+    xl, yl = np.minimum(x // s, mw - 1), np.minimum(y // s, mh - 1)
+    xu, yu = np.minimum(x // s + 1, mw - 1), np.minimum(y // s + 1, mh - 1)
+    same_x, same_y = (xl == xu)[None, :], (yl == yu)[:, None]
+    tbl = np.where(same_x & same_y, 3, np.where(same_x, 1, np.where(same_y, 2, 0)))
+    wt = tables[tbl, (y % s)[:, None], (x % s)[None, :]]                       # (h, w, 4)
+    e = gmap.astype(F) / F(255.0)                                              # mapUintToFloat
+    out = np.empty((h, w, nc), F)
+    for c in range(nc):
+        p = e[:, :, c]
+        e1, e2 = p[yl[:, None], xl[None, :]], p[yu[:, None], xl[None, :]]
+        e3, e4 = p[yl[:, None], xu[None, :]], p[yu[:, None], xu[None, :]]
+        out[:, :, c] = e1 * wt[:, :, 0] + e2 * wt[:, :, 1] + e3 * wt[:, :, 2] + e4 * wt[:, :, 3]
+    return out
+
+
 def _oetf(fmt, x):
     """the reference's OETFs in float64 (its float constants, as doubles); x >= 0"""
     x = np.asarray(x, np.float64)

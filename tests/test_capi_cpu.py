@@ -184,6 +184,20 @@ def test_idw_tables_equal_the_oracle(api, orc):
             assert list(got)[t * n:(t + 1) * n] == list(want), (scale, t)
 
 
+@pytest.mark.parametrize("scale", [3, 7, 16, 128, 129, 256])
+def test_idw_tables_equal_the_oracle_at_the_factors_of_the_apply_cases(api, orc, scale):
+    """the factors tests/apply_scale_cases.py applies at, bit patterns compared: an odd one, the largest table the library keeps per
+    device (128), and two that live for one call (129: 1 MiB and a few bytes, 256: 4 MiB)"""
+    lib, L = api.load(), orc.load()
+    n = scale * scale * 4
+    got = np.full(4 * n, np.nan, np.float32)
+    assert lib.uhdr_hip_idw_tables(scale, got.ctypes.data_as(C.POINTER(C.c_float))) == 0
+    for t, (incR, incB) in enumerate(((1, 1), (0, 1), (1, 0), (0, 0))):
+        want = np.full(n, np.nan, np.float32)
+        L.orc_fillShepardsIDW(want.ctypes.data_as(C.POINTER(C.c_float)), scale, incR, incB)
+        assert np.array_equal(got[t * n:(t + 1) * n].view(np.uint32), want.view(np.uint32)), (scale, t)
+
+
 def test_synthetic_frames_match_the_survey_lcg(orc):
     """libultrahdr_dev_amd.synth (jump-ahead LCG, used by bench.py on the GPU) == SURVEY 8(d) serial LCG"""
     from libultrahdr_dev_amd import synth

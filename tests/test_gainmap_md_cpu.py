@@ -187,6 +187,19 @@ def small_inputs():
     return w, h, (Y, U, V), gmap, M.linear_sdr(Y, U, V), M.sampled_gain(gmap, w, h)
 
 
+@pytest.mark.parametrize("shape", [(6, 6, 6, 6), (10, 14, 5, 7), (12, 12, 4, 4), (8, 8, 2, 2), (21, 14, 3, 2), (4, 20, 1, 5), (20, 4, 5, 1), (5, 5, 1, 1)],
+                         ids=lambda s: "%dx%d_map%dx%d" % s)
+def test_sampled_gain_by_tables_is_sampled_gain(shape):
+    """factors 1, 2, 3, 4, 7 and 5 with interior and edge pixels, maps one pixel wide, one high and 1 x 1; one plane and three: the
+    table-driven form the large factors of tests/test_gpu_gainmap_md.py use returns sampleMapIdw's bit patterns"""
+    w, h, mw, mh = shape
+    for planes in ((mh, mw), (mh, mw, 3)):
+        gmap = M.lcg_bytes(planes, 17 + w)
+        a, b = M.sampled_gain(gmap, w, h), M.sampled_gain_by_tables(gmap, w, h)
+        assert a.shape == b.shape and a.dtype == b.dtype == np.float32
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (shape, planes)
+
+
 @pytest.mark.parametrize("fmt", [M.FMT_F16, M.FMT_PQ, M.FMT_HLG, M.FMT_RGB10])
 @pytest.mark.parametrize("boost", [4.926, 100.0, M.FLT_MAX])
 def test_model_equals_the_reference_at_degenerate_metadata(orc, small_inputs, fmt, boost):

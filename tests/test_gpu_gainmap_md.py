@@ -210,6 +210,25 @@ def test_apply_md_small_shapes(hip, name, rgb):
     assert a[0] == 0 and b[0] == 0 and all(np.array_equal(x, y) for x, y in zip(a[1], b[1]))
 
 
+# (w, h, scale): an odd factor off the shapes above, the largest power of two below them, the first factor whose weight table lives
+# for the call only (uhdr_capi.hip: kIdwCacheMaxScale = 128), and a 1 x 1 map (the corner table for every pixel)
+OTHER_FACTORS = [(42, 30, 3), (96, 48, 16), (258, 258, 129), (6, 6, 6)]
+
+
+@pytest.mark.parametrize("shape", OTHER_FACTORS, ids=lambda s: "%dx%d_s%d" % s)
+@pytest.mark.parametrize("rgb", [False, True], ids=["oneplane", "rgb"])
+def test_apply_md_other_factors(hip, shape, rgb):
+    """k_apply_px_md's taps and weight tables off factors 1 to 4, against the same model and bars as the shapes above.  The gains
+    come from M.sampled_gain_by_tables: sampled_gain's values (tests/test_gainmap_md_cpu.py) without its per-pixel table build"""
+    w, h, s = shape
+    item = _plain_item(w, h, s, 71 + s, rgb)
+    inputs = [(M.linear_sdr(item.Y, item.U, item.V, item.csx, item.csy), M.sampled_gain_by_tables(item.gmap, w, h))]
+    for name in CASE_NAMES:
+        for boost in _boosts(name):
+            for fmt in FORMATS:
+                _check_general(hip, [item], name, boost, fmt, inputs=inputs)
+
+
 @pytest.mark.parametrize("sampling", ["444", "422", "440"])
 def test_apply_md_other_samplings(hip, sampling):
     """45x37 at scale 1 with 4:4:4, 4:2:2 and 4:4:0 primaries, one-plane and RGB maps, padded chroma rows"""

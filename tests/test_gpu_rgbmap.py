@@ -174,6 +174,14 @@ APPLY_CASES = [
     # rows; applyGainMap's checks refuse it, see the test below.  8 is the smallest height above it that has one.)
     (300, 8, 75, 2, None),
     (20, 12, 5, 3, 8),         # a map luma_stride of width + 3
+    # k_apply_px_rgb's taps and weight tables off the factors above: an odd factor on another shape, a larger power of two, the first
+    # factor whose table lives for the call only (uhdr_capi.hip: kIdwCacheMaxScale = 128), and maps one pixel wide / one pixel high
+    # (no right tap / no bottom tap for every pixel)
+    (42, 30, 14, 10, None),    # scale 3
+    (96, 48, 6, 3, None),      # scale 16
+    (258, 258, 2, 2, None),    # scale 129
+    (2, 40, 1, 20, None),      # scale 2, a 1 x 20 map
+    (48, 2, 24, 1, None),      # scale 2, a 24 x 1 map
 ]
 
 

@@ -286,7 +286,7 @@ def _mono_jpeg(hip, plane, q):
 
 @pytest.mark.parametrize("api0", [False, True])
 @pytest.mark.parametrize("rgb_map", [0, 1])
-@pytest.mark.parametrize("s", [1, 2, 8])
+@pytest.mark.parametrize("s", [1, 2, 8, 16])
 def test_jpegr_encode_scaled(hip, orc, s, rgb_map, api0):
     """the scaled call and the existing one on the same pairs: the same primary image; the gain-map JPEG is the stand-alone encode at
     quality 85 of the scaled generate call's map; the existing decode calls read the file, and what they return is the apply call's
@@ -341,6 +341,16 @@ def test_jpegr_encode_scaled(hip, orc, s, rgb_map, api0):
                                                     stream_ptr()) == 0
             want = to_host(dout, nbytes).copy()
         assert np.array_equal(got[k], want), (k, int((got[k] != want).sum()))
+        # ... and, beside the library's own apply call, the reference's path: the oracle's applyGainMap on the oracle's decode
+        # (orc.jpeg_decode) of the file's two JPEGs under the metadata the oracle reads from the file's XMP (oracle/jpegr_oracle.py:
+        # decode).  The file's metadata is the reference's degenerate form in every parametrization.  A per-channel map
+        # (rgb_map = 1) is a three-component 4:4:4 JPEG, which the reference's decoder -- and orc.jpeg_decode with it -- refuses:
+        # there is no reference path for those files, they stay compared with the apply call on the decoded pieces only.
+        if not rgb_map:
+            from oracle import jpegr_oracle as J
+            ost, ref, ow, oh, _, omd = J.decode(new[k], orc.OUT_HDR_HLG, FLT_MAX)
+            assert ost == 0 and (ow, oh) == (p.w, p.h) and float(np.float32(omd["max"])) == mds[k].maxContentBoost
+            assert np.array_equal(got[k], ref[:got[k].size]), (k, s, "decode differs from the oracle's", int((got[k] != ref[:got[k].size]).sum()))
 
 
 def test_jpegr_encode_scaled_size_probe_and_a_failing_file(hip):
