@@ -1094,6 +1094,42 @@ int uhdr_hip_generate_probe(int phase, int n, const uhdr_hip_image_t* yuv420_ima
                             int hdr_tf, uhdr_hip_metadata_t* metadata, uhdr_hip_image_t* dests, int sdr_is_601,
                             int generate_mode, float* content_minmax, void* stream, uint32_t* route, uint32_t* headers);
 
+/* The same for EXACT apply: the route uhdr_hip_apply_gainmap_batch takes for a call in UHDR_HIP_APPLY_EXACT mode, and the two
+ * kernels of its estimate-plus-k_apply_resolve route one at a time -- what the tests of the hand-over between the f32 estimate's
+ * lists of pixels in doubt and k_apply_resolve are built on.  The arguments up to `stream` are that call's (apply_mode is
+ * UHDR_HIP_APPLY_EXACT) and are checked as there, in its order, but n >= 1; only the FIRST chunk of the call (the leading images
+ * of one size, map size and alignment class, at most 64) is looked at.
+ *   phase 0  host only, nothing is launched and no device is needed (the data pointers are examined for alignment, never read):
+ *            route[0 .. UHDR_HIP_APPLY_ROUTE_WORDS) receives the chunk's route and the layout constants of the stream's workspace,
+ *            indexed by the UHDR_HIP_APPLY_ROUTE_* names below.  Like the call itself, every phase fills width, height and colorGamut
+ *            of the chunk's destination descriptors.
+ *   phase 1  enqueues the estimate kernel alone (every pixel's f32 estimate is written; the pixels in doubt are appended to the
+ *            image's lists), then copies, in stream order, the header words [0, route[HDR_WORDS]) of every image to headers
+ *            (DEVICE, n * route[HDR_WORDS] uint32): [route[LIST_COUNTS] + l] holds the appends to list l -- beyond route[LIST_CAP]
+ *            the entries are dropped and the image is swept --, [route[SLICE_WORD]] the slices of k_apply_resolve that have finished.
+ *   phase 2  enqueues k_apply_resolve alone, on the stream's workspace as phase 1 left it: same arguments, same stream, nothing
+ *            of the library on that stream in between but further phases 1 of the same geometry (their appends go behind those
+ *            already there: the counts add up).  It leaves the headers cleared.
+ * Phases 1 and 2 serve a call that is ONE chunk on the estimate-plus-k_apply_resolve route; ERROR_UNSUPPORTED_FEATURE otherwise,
+ * and for a phase outside 0..2.  BAD_PTR for n < 1, a NULL route in phase 0 or NULL headers in phase 1. */
+enum {
+  UHDR_HIP_APPLY_ROUTE_RESOLVE = 0,        /* 1: an estimate kernel followed by k_apply_resolve */
+  UHDR_HIP_APPLY_ROUTE_CELLS = 1,          /* 1: k_apply_s4_est (a thread per 4x4 map cell), 0: k_apply_px_est (a thread per pixel) */
+  UHDR_HIP_APPLY_ROUTE_IMAGES = 2,         /* images in the chunk */
+  UHDR_HIP_APPLY_ROUTE_LISTS = 3,          /* kExLists: lists per image */
+  UHDR_HIP_APPLY_ROUTE_LIST_CAP = 4,       /* ex_cap: entries a list holds at this image size (0 without RESOLVE) */
+  UHDR_HIP_APPLY_ROUTE_HDR_WORDS = 5,      /* kExHdrWords */
+  UHDR_HIP_APPLY_ROUTE_LIST_COUNTS = 6,    /* first of the lists' count words */
+  UHDR_HIP_APPLY_ROUTE_SLICE_WORD = 7,     /* the word that counts the finished slices of k_apply_resolve */
+  UHDR_HIP_APPLY_ROUTE_RESOLVE_SLICES = 8, /* kExSlices: blocks of 256 threads k_apply_resolve spends per image */
+  UHDR_HIP_APPLY_ROUTE_GRID_X = 9,         /* the estimate kernel's gridDim.x: blocks of 256 cells (CELLS) or of 256 pixels of a row */
+  UHDR_HIP_APPLY_ROUTE_GRID_Y = 10,        /* its gridDim.y: rows of the per-pixel kernel (further rows by striding); CELLS: the images */
+  UHDR_HIP_APPLY_ROUTE_WORDS = 11
+};
+int uhdr_hip_apply_exact_probe(int phase, int n, const uhdr_hip_image_t* yuv420_images, const uhdr_hip_image_t* gainmaps,
+                               const uhdr_hip_metadata_t* metadata, int output_format, float max_display_boost,
+                               uhdr_hip_image_t* dests, void* stream, uint32_t* route, uint32_t* headers);
+
 /* Bench / test support: the deterministic synthetic frame pair of SURVEY.md 8(d) (an LCG; tests/ and bench.py compare it with the
  * oracle's serial loop), written into device memory: p010 = width*height*3/2 uint16 (luma, then interleaved UV, values in the
  * legal 10-bit ranges << 6), yuv = width*height*3/2 bytes (Y, U, V).  width and height even; enqueued on `stream`. */

@@ -38,6 +38,9 @@ FXC_GATHER, FXC_ASC, FXC_DESC, FXC_LDS, FXC_TILE = 0, 1, 2, 3, 4   # uhdr_hip_ef
 # uhdr_hip_generate_probe: the words of its route report (UHDR_HIP_GENERATE_ROUTE_*)
 (ROUTE_RESOLVE, ROUTE_SPANS, ROUTE_SLOTS, ROUTE_SPREAD, ROUTE_IMAGES, ROUTE_BLOCK, ROUTE_HDR_WORDS, ROUTE_SLOT_COUNTS, ROUTE_SLOT_PLAIN,
  ROUTE_SLOT_SAVED, ROUTE_LISTS, ROUTE_LIST_CAP, ROUTE_LIST_COUNTS, ROUTE_SWEEP_WORD, ROUTE_RESOLVE_SLICES, ROUTE_SLOT_WAVES, ROUTE_WORDS) = range(17)
+# uhdr_hip_apply_exact_probe: the words of its route report (UHDR_HIP_APPLY_ROUTE_*)
+(APPLY_ROUTE_RESOLVE, APPLY_ROUTE_CELLS, APPLY_ROUTE_IMAGES, APPLY_ROUTE_LISTS, APPLY_ROUTE_LIST_CAP, APPLY_ROUTE_HDR_WORDS, APPLY_ROUTE_LIST_COUNTS,
+ APPLY_ROUTE_SLICE_WORD, APPLY_ROUTE_RESOLVE_SLICES, APPLY_ROUTE_GRID_X, APPLY_ROUTE_GRID_Y, APPLY_ROUTE_WORDS) = range(12)
 ABI_VERSION = 3
 FLT_MAX = 3.4028234663852886e38
 
@@ -178,6 +181,8 @@ SIGNATURES = {
     "uhdr_hip_eval_transfer": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p]),
     "uhdr_hip_generate_probe": (C.c_int, [C.c_int, C.c_int, _IP, _IP, C.c_int, _MP, _IP, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.POINTER(C.c_uint32), C.c_void_p]),
+    "uhdr_hip_apply_exact_probe": (C.c_int, [C.c_int, C.c_int, _IP, _IP, _MP, C.c_int, C.c_float, _IP, C.c_void_p, C.POINTER(C.c_uint32),
+                                             C.c_void_p]),
     "uhdr_hip_synth_lcg_frame": (C.c_int, [C.c_size_t, C.c_size_t, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uhdr_hip_adaptive_boost_range": (C.c_int, [C.c_int, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "uhdr_hip_adaptive_metadata": (C.c_int, [C.c_int, C.c_float, C.c_float, _MP]),

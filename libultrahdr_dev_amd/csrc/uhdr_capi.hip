@@ -3953,9 +3953,9 @@ int uhdr_hip_generate_gainmap_adaptive_batch(int n, const uhdr_hip_image_t* yuvs
                           nullptr, true, static_cast<hipStream_t>(stream));
 }
 
-int uhdr_hip_apply_gainmap_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* maps,
-                                 const uhdr_hip_metadata_t* metadata, int output_format, float max_display_boost,
-                                 uhdr_hip_image_t* dests, int apply_mode, void* stream) {
+// uhdr_hip_apply_gainmap_batch's checks in front of current_state() ...
+static int check_apply(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* maps, const uhdr_hip_metadata_t* metadata,
+                       uhdr_hip_image_t* dests, int apply_mode) {
   if (n < 0 || (n > 0 && (yuvs == nullptr || maps == nullptr || dests == nullptr)) || metadata == nullptr)
     return UHDR_HIP_ERROR_BAD_PTR;
   for (int i = 0; i < n; ++i) {
@@ -3965,44 +3965,122 @@ int uhdr_hip_apply_gainmap_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr
   if (apply_mode != UHDR_HIP_APPLY_FAST && apply_mode != UHDR_HIP_APPLY_EXACT && apply_mode != UHDR_HIP_APPLY_LUT &&
       apply_mode != UHDR_HIP_APPLY_EXACT_UNFILTERED)
     return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  DeviceState* st = nullptr;
-  int rc = current_state(&st);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  return UHDR_HIP_NO_ERROR;
+}
+// ... and the one behind current_state()
+static int check_apply_dests(int n, const uhdr_hip_image_t* dests, int output_format) {
   const bool writes = apply_writes(output_format);
   for (int i = 0; i < n; ++i)
     if (writes && dests[i].data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  return UHDR_HIP_NO_ERROR;
+}
+
+// One chunk of uhdr_hip_apply_gainmap_batch: up to kMaxChunk consecutive images, from image i on, of one size, map size and class
+// (app_chunk); *m_out receives their number.  `phases` selects which kernels of EXACT's pair are enqueued (launch_apply's ex_phases;
+// every other route is one launch, enqueued when phases != 0); the production call passes both.  0 enqueues nothing and needs no
+// device (st may be null): the plan only -- `route` (or null) receives it, UHDR_HIP_APPLY_ROUTE_* words.  `headers` (or null; device,
+// kExHdrWords words per image): behind kExPhaseEst on the pair's route, every image's header words, copied in stream order.
+static int apply_chunk(DeviceState* st, hipStream_t s, int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* maps,
+                       const uhdr_hip_metadata_t* metadata, int output_format, float max_display_boost, uhdr_hip_image_t* dests,
+                       int apply_mode, int i, unsigned phases, int* m_out, uint32_t* route, uint32_t* headers) {
+  const uhdr_hip_image_t& y0 = yuvs[i];
+  const uhdr_hip_image_t& m0 = maps[i];
+  const bool writes = apply_writes(output_format);
+  IdwLease table;
+  int rc;
+  if (phases != 0u && (rc = table.take(st, (int)(y0.width / m0.width), s)) != UHDR_HIP_NO_ERROR) return rc;
+  AppConsts c = apply_consts(y0, m0, *metadata, max_display_boost, table.idw);
+  c.lut = (apply_mode == UHDR_HIP_APPLY_LUT && st != nullptr) ? st->lut : nullptr;
+  c.tab = st != nullptr ? st->lut : nullptr;
+  AppBatch b;
+  const Chunk ch = app_chunk(i, n, yuvs, maps, dests, b, &c, false);   // (the descriptors are filled in the plan-only mode too)
+  const int m = ch.m;
+  const bool fast = ch.cls;
+  *m_out = m;
+  // EXACT: f32 estimate, then the exact path on the pixels it leaves in doubt.  The estimate's error bounds are measured for
+  // |log2 boost| <= 32 (tests/test_gpu_exact_filter.py); beyond that every pixel takes the exact path.
+  const bool pair = writes && apply_mode == UHDR_HIP_APPLY_EXACT && (uint64_t)c.width * c.height <= 0xFFFFFFFFull &&
+                    std::fabs(c.log2_min_d) <= 32.0 && std::fabs(c.log2_max_d) <= 32.0;
+  const uint32_t cap = pair ? ex_list_cap((uint64_t)c.width * c.height) : 0u;
+  if (route != nullptr) {
+    memset(route, 0, sizeof(uint32_t) * UHDR_HIP_APPLY_ROUTE_WORDS);
+    uint32_t grid[2] = {0u, 0u};
+    if (pair) apply_est_grid(c, m, fast, grid);
+    route[UHDR_HIP_APPLY_ROUTE_RESOLVE] = pair ? 1u : 0u;
+    route[UHDR_HIP_APPLY_ROUTE_CELLS] = (pair && fast) ? 1u : 0u;
+    route[UHDR_HIP_APPLY_ROUTE_IMAGES] = (uint32_t)m;
+    route[UHDR_HIP_APPLY_ROUTE_LISTS] = kExLists;
+    route[UHDR_HIP_APPLY_ROUTE_LIST_CAP] = cap;
+    route[UHDR_HIP_APPLY_ROUTE_HDR_WORDS] = kExHdrWords;
+    route[UHDR_HIP_APPLY_ROUTE_LIST_COUNTS] = 8u;   // AppConsts::ex_ws: words 8 ..: the lengths of the image's lists,
+    route[UHDR_HIP_APPLY_ROUTE_SLICE_WORD] = 3u;    // word 3: slices of k_apply_resolve that have finished
+    route[UHDR_HIP_APPLY_ROUTE_RESOLVE_SLICES] = kExSlices;
+    route[UHDR_HIP_APPLY_ROUTE_GRID_X] = grid[0];
+    route[UHDR_HIP_APPLY_ROUTE_GRID_Y] = grid[1];
+  }
+  if (phases == 0u) return UHDR_HIP_NO_ERROR;
+  std::unique_lock<std::mutex> pair_lk(g_pair_mu, std::defer_lock);
+  if (pair) {
+    pair_lk.lock();
+    uint32_t* w = nullptr;
+    const int wrc = exact_workspace(st, s, m, cap, &w);
+    if (wrc != UHDR_HIP_NO_ERROR) return wrc;
+    c.ex_ws = w;
+    c.ex_cap = cap;
+  }
+  if (writes) HIP_TRY(launch_apply(c, b, m, output_format, apply_mode, fast, s, phases));
+  if (pair && headers != nullptr && (phases & kExPhaseEst))   // (the headers of a launch's images lie side by side in front)
+    HIP_TRY(hipMemcpyAsync(headers, c.ex_ws, sizeof(uint32_t) * kExHdrWords * (size_t)m, hipMemcpyDeviceToDevice, s));
+  return UHDR_HIP_NO_ERROR;
+}
+
+int uhdr_hip_apply_gainmap_batch(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* maps,
+                                 const uhdr_hip_metadata_t* metadata, int output_format, float max_display_boost,
+                                 uhdr_hip_image_t* dests, int apply_mode, void* stream) {
+  int rc = check_apply(n, yuvs, maps, metadata, dests, apply_mode);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if ((rc = check_apply_dests(n, dests, output_format)) != UHDR_HIP_NO_ERROR) return rc;
 
   int i = 0;
   while (i < n) {
-    const uhdr_hip_image_t& y0 = yuvs[i];
-    const uhdr_hip_image_t& m0 = maps[i];
-    IdwLease table;
-    if ((rc = table.take(st, (int)(y0.width / m0.width), s)) != UHDR_HIP_NO_ERROR) return rc;
-    AppConsts c = apply_consts(y0, m0, *metadata, max_display_boost, table.idw);
-    c.lut = apply_mode == UHDR_HIP_APPLY_LUT ? st->lut : nullptr;
-    c.tab = st->lut;
-    AppBatch b;
-    const Chunk ch = app_chunk(i, n, yuvs, maps, dests, b, &c, false);
-    const int m = ch.m;
-    const bool fast = ch.cls;
-    // EXACT: f32 estimate, then the exact path on the pixels it leaves in doubt.  The estimate's error bounds are measured for
-    // |log2 boost| <= 32 (tests/test_gpu_exact_filter.py); beyond that every pixel takes the exact path.
-    std::unique_lock<std::mutex> pair_lk(g_pair_mu, std::defer_lock);
-    if (writes && apply_mode == UHDR_HIP_APPLY_EXACT && (uint64_t)c.width * c.height <= 0xFFFFFFFFull &&
-        std::fabs(c.log2_min_d) <= 32.0 && std::fabs(c.log2_max_d) <= 32.0) {
-      pair_lk.lock();
-      const uint32_t cap = ex_list_cap((uint64_t)c.width * c.height);
-      uint32_t* w = nullptr;
-      const int wrc = exact_workspace(st, s, m, cap, &w);
-      if (wrc != UHDR_HIP_NO_ERROR) return wrc;
-      c.ex_ws = w;
-      c.ex_cap = cap;
-    }
-    if (writes) HIP_TRY(launch_apply(c, b, m, output_format, apply_mode, fast, s));
+    int m = 0;
+    rc = apply_chunk(st, s, n, yuvs, maps, metadata, output_format, max_display_boost, dests, apply_mode, i,
+                     kExPhaseEst | kExPhaseResolve, &m, nullptr, nullptr);
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
     i += m;
   }
   return UHDR_HIP_NO_ERROR;
+}
+
+int uhdr_hip_apply_exact_probe(int phase, int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* maps,
+                               const uhdr_hip_metadata_t* metadata, int output_format, float max_display_boost,
+                               uhdr_hip_image_t* dests, void* stream, uint32_t* route, uint32_t* headers) {
+  if (phase < 0 || phase > 2) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (n <= 0) return UHDR_HIP_ERROR_BAD_PTR;
+  if ((phase == 0 && route == nullptr) || (phase == 1 && headers == nullptr)) return UHDR_HIP_ERROR_BAD_PTR;
+  int rc = check_apply(n, yuvs, maps, metadata, dests, UHDR_HIP_APPLY_EXACT);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  DeviceState* st = nullptr;
+  if (phase != 0 && (rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  if ((rc = check_apply_dests(n, dests, output_format)) != UHDR_HIP_NO_ERROR) return rc;
+  int m = 0;
+  uint32_t r[UHDR_HIP_APPLY_ROUTE_WORDS];
+  // the plan of the first chunk: host arithmetic only, no device state.  Phases 1 and 2 take it first as well: it is what tells them
+  // that the call spans several chunks or is not on the pair's route, before anything is enqueued
+  rc = apply_chunk(nullptr, nullptr, n, yuvs, maps, metadata, output_format, max_display_boost, dests, UHDR_HIP_APPLY_EXACT, 0, 0u, &m, r,
+                   nullptr);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if (phase == 0) {
+    memcpy(route, r, sizeof(r));
+    return UHDR_HIP_NO_ERROR;
+  }
+  // one kernel of the pair by itself: only where the call IS one such pair (the workspace is handed from one phase to the other)
+  if (m != n || r[UHDR_HIP_APPLY_ROUTE_RESOLVE] == 0u) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return apply_chunk(st, static_cast<hipStream_t>(stream), n, yuvs, maps, metadata, output_format, max_display_boost, dests,
+                     UHDR_HIP_APPLY_EXACT, 0, phase == 1 ? kExPhaseEst : kExPhaseResolve, &m, nullptr, headers);
 }
 
 // ---- general metadata: gamma, offsets, HDR capacity ---------------------------

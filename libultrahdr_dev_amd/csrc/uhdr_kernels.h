@@ -167,6 +167,7 @@ struct AppConsts {
 // headers sit in front so that their place does not depend on the image size: every launch leaves them cleared.
 constexpr uint32_t kExLists = 1024;
 constexpr uint32_t kExHdrWords = 8 + kExLists;
+constexpr uint32_t kExSlices = 256;   // blocks of k_apply_resolve per image (here because uhdr_hip_apply_exact_probe reports it)
 inline size_t ex_ws_bytes(uint32_t cap) { return ((size_t)kMaxChunk * kExHdrWords + (size_t)kMaxChunk * kExLists * cap) * 4u; }
 // capacity for a sixteenth of the image's pixels (the filter leaves ~1 % in doubt), spread over the lists
 inline uint32_t ex_list_cap(uint64_t pixels) { return (uint32_t)(pixels / 16u / kExLists) + 64u; }
@@ -337,9 +338,14 @@ hipError_t launch_adaptive_consts(const uint32_t* keys, int n, int per_call, flo
                                   float* boost_range, const uint32_t* carry_in, uint32_t* carry_out, hipStream_t s);
 // pass 2 of n <= kMaxChunk images of `pixels` map pixels each; consts[i] belongs to b.img[i]
 hipError_t launch_encode_gains(const AdaptConsts* consts, const EncGainBatch& b, int n, uint32_t pixels, hipStream_t s);
-// mode: 0 FAST, 1 EXACT, 2 LUT
+// mode: 0 FAST, 1 EXACT, 2 LUT.  ex_phases: which kernels of EXACT's pair (c.ex_ws set) are enqueued -- kExPhaseEst the estimate
+// (k_apply_s4_est or k_apply_px_est), kExPhaseResolve k_apply_resolve; every call but uhdr_hip_apply_exact_probe passes both
+enum : unsigned { kExPhaseEst = 1u, kExPhaseResolve = 2u };
 hipError_t launch_apply(const AppConsts& c, const AppBatch& b, int n, int fmt, int mode,
-                        bool fast_s4, hipStream_t s);
+                        bool fast_s4, hipStream_t s, unsigned ex_phases = kExPhaseEst | kExPhaseResolve);
+// the grid of that estimate kernel for n images: grid[0] = gridDim.x (blocks of 256 cells, or of 256 pixels of a row), grid[1] =
+// gridDim.y of the per-pixel kernel (rows; the scale-4 kernel's is the image)
+void apply_est_grid(const AppConsts& c, int n, bool fast_s4, uint32_t grid[2]);
 // per-pixel apply of RGBA maps (AppImage::map 4-byte aligned, AppConsts::map_stride set): FAST or the unfiltered EXACT arithmetic
 hipError_t launch_apply_rgb(const AppConsts& c, const AppBatch& b, int n, int fmt, bool exact, hipStream_t s);
 // general metadata: per-pixel apply of one-plane maps (rows of map_w bytes) or RGBA maps (launch_apply_rgb's layout); one f32 arithmetic

@@ -2702,7 +2702,6 @@ hipError_t launch_apply_md(const AppConsts& c, const AppMdConsts& m, const AppBa
 //   pqOetf: v S(x) <= 112 codes per unit of relative input error (2.2e-4), pq_oetf_est is within 2.5e-4 codes: the same d.
 constexpr float kEstRel = 2.0e-6f;
 constexpr float kEstOetfAbs = 8.0e-4f, kEstOetfRel = 6.0e-7f;
-constexpr uint32_t kExSlices = 256;   // blocks of k_apply_resolve per image
 
 __device__ __forceinline__ F3 recover_hdr_est(const AppConsts& c, float yf, float crv, float gcbu, float gcrv, float cbu, float gain) {
   const float r = clamp01(yf + crv), g = clamp01(yf - gcbu - gcrv), b = clamp01(yf + cbu);
@@ -3323,9 +3322,19 @@ __global__ void __launch_bounds__(1024) k_apply_lut_s4(const AppConsts c, const 
   }
 }
 
+// the estimate kernel's grid: k_apply_s4_est (blocks of 256 cells, image) or k_apply_px_est (px_grid)
+static dim3 est_grid(const AppConsts& c, int n, bool fast_s4) {
+  return fast_s4 ? dim3((c.map_w * c.map_h + 255u) / 256u, n) : px_grid(c.width, c.height, n);
+}
+void apply_est_grid(const AppConsts& c, int n, bool fast_s4, uint32_t grid[2]) {
+  const dim3 g = est_grid(c, n, fast_s4);
+  grid[0] = g.x;
+  grid[1] = g.y;
+}
+
 template <int FMT>
 static hipError_t launch_apply_t(const AppConsts& c, const AppBatch& b, int n, int mode,
-                                 bool fast_s4, hipStream_t s) {
+                                 bool fast_s4, hipStream_t s, unsigned ex_phases) {
   if (n == 0 || c.width == 0 || c.height == 0) return hipSuccess;
   const bool exact = mode == 1 || mode == 3;
   if (mode == 2) {
@@ -3380,9 +3389,11 @@ static hipError_t launch_apply_t(const AppConsts& c, const AppBatch& b, int n, i
   } else {
     const dim3 grid = px_grid(c.width, c.height, n);
     if (exact && c.ex_ws != nullptr) {
-      if (fast_s4) hipLaunchKernelGGL((k_apply_s4_est<FMT>), dim3((c.map_w * c.map_h + 255u) / 256u, n), dim3(256), 0, s, c, b);
-      else hipLaunchKernelGGL((k_apply_px_est<FMT>), grid, dim3(256), 0, s, c, b);
-      hipLaunchKernelGGL((k_apply_resolve<FMT>), dim3(n, kExSlices), dim3(256), 0, s, c, b);
+      if (ex_phases & kExPhaseEst) {
+        if (fast_s4) hipLaunchKernelGGL((k_apply_s4_est<FMT>), est_grid(c, n, true), dim3(256), 0, s, c, b);
+        else hipLaunchKernelGGL((k_apply_px_est<FMT>), est_grid(c, n, false), dim3(256), 0, s, c, b);
+      }
+      if (ex_phases & kExPhaseResolve) hipLaunchKernelGGL((k_apply_resolve<FMT>), dim3(n, kExSlices), dim3(256), 0, s, c, b);
     } else if (exact) hipLaunchKernelGGL((k_apply_px<FMT, true>), grid, dim3(256), 0, s, c, b);
     else hipLaunchKernelGGL((k_apply_px<FMT, false>), grid, dim3(256), 0, s, c, b);
   }
@@ -3390,12 +3401,12 @@ static hipError_t launch_apply_t(const AppConsts& c, const AppBatch& b, int n, i
 }
 
 hipError_t launch_apply(const AppConsts& c, const AppBatch& b, int n, int fmt, int mode,
-                        bool fast_s4, hipStream_t s) {
+                        bool fast_s4, hipStream_t s, unsigned ex_phases) {
   switch (fmt) {
-    case 1: return launch_apply_t<1>(c, b, n, mode, fast_s4, s);
-    case 2: return launch_apply_t<2>(c, b, n, mode, fast_s4, s);
-    case 3: return launch_apply_t<3>(c, b, n, mode, fast_s4, s);
-    case 4: return launch_apply_t<4>(c, b, n, mode, fast_s4, s);
+    case 1: return launch_apply_t<1>(c, b, n, mode, fast_s4, s, ex_phases);
+    case 2: return launch_apply_t<2>(c, b, n, mode, fast_s4, s, ex_phases);
+    case 3: return launch_apply_t<3>(c, b, n, mode, fast_s4, s, ex_phases);
+    case 4: return launch_apply_t<4>(c, b, n, mode, fast_s4, s, ex_phases);
     default: return hipErrorInvalidValue;
   }
 }

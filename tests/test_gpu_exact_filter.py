@@ -127,20 +127,38 @@ def test_filtered_equals_unfiltered(hip, orc, fmt, scale, boost):
     assert np.array_equal(a2, b)
 
 
-@pytest.mark.parametrize("fmt", [2, 3, 4])
-def test_every_pixel_in_doubt_overflows_into_a_sweep(hip, orc, fmt):
-    """white with gain 1 and display boost == content boost is linear 1.0: code value 1023.0 to within the estimate's error, in
-    doubt for every pixel -- far more than the lists hold"""
+def _doubt_counts(lib, hip, yuv, w, h, gmap, md, fmt):
+    """the lengths of the 1 024 lists the estimate kernel leaves for one frame (uhdr_hip_apply_exact_probe: the estimate kernel, a
+    copy of the header, then k_apply_resolve, which clears it)"""
+    from tests.gpu_util import dev_empty, stream_ptr, to_dev
+    dy, dmap, dout = to_dev(yuv), to_dev(gmap), dev_empty(hip.output_bytes(fmt, w, h), 0xCD)
+    ya = hip.image_array([hip.yuv420_image(dy.data_ptr(), w, h, hip.CG_BT709)])
+    ma = hip.image_array([hip.mono_image(dmap.data_ptr(), gmap.shape[1], gmap.shape[0])])
+    da = hip.image_array([hip.out_image(dout.data_ptr())])
+    hdr = torch.zeros(8 + 1024, dtype=torch.int32, device="cuda")
+    for phase in (1, 2):
+        assert lib.uhdr_hip_apply_exact_probe(phase, 1, ya, ma, C.byref(md), fmt, FLT_MAX, da, stream_ptr(), None, C.c_void_p(hdr.data_ptr())) == 0
+    torch.cuda.synchronize()
+    return hdr.cpu().numpy()[8:].astype(np.int64)
+
+
+def _every_pixel_in_doubt(hip, orc, fmt, scale):
     from tests.test_gpu_parity import _oracle_apply
     lib = hip.load()
     w, h = 512, 256
-    yuv = np.concatenate([np.full(w * h, 255, np.uint8), np.full(w * h // 2, 128, np.uint8)])
-    gmap = np.full((h // 4, w // 4), 255, np.uint8)
+    # F16: white is not in doubt there; luma 1 under gain 1 is (1 / 255 / 12.92) / 4 = 7.6e-5, below 2^-13: the half-precision
+    # subnormals, which est_channel<1> always hands to the exact path
+    level, byte = (1, 0) if fmt == 1 else (255, 255)
+    yuv = np.concatenate([np.full(w * h, level, np.uint8), np.full(w * h // 2, 128, np.uint8)])
+    gmap = np.full((h // scale, w // scale), byte, np.uint8)
     maxb = np.float32(4.0)
     md = hip.metadata(maxb)
     ref = _oracle_apply(orc, yuv, w, h, gmap, maxb, fmt, FLT_MAX)
     a = _apply(lib, hip, yuv, w, h, gmap, md, fmt, FLT_MAX, hip.APPLY_EXACT)
     assert np.array_equal(a, ref)
+    # that this was a sweep: the estimate kernel by itself lists every pixel, every list in use far beyond ex_cap = 72
+    counts = _doubt_counts(lib, hip, yuv, w, h, gmap, md, fmt)
+    assert counts.sum() == w * h and (counts > 0).sum() >= 32 and counts[counts > 0].min() > w * h // 16384 + 64
     # half of the image in doubt, then an ordinary frame: the overflow left nothing behind
     yuv2 = yuv.copy()
     yuv2[: w * h // 2] = 200
@@ -149,6 +167,19 @@ def test_every_pixel_in_doubt_overflows_into_a_sweep(hip, orc, fmt):
     _, yuv3 = orc.lcg_frame(w, h, 77)
     ref3 = _oracle_apply(orc, yuv3, w, h, gmap, maxb, fmt, FLT_MAX)
     assert np.array_equal(_apply(lib, hip, yuv3, w, h, gmap, md, fmt, FLT_MAX, hip.APPLY_EXACT), ref3)
+
+
+@pytest.mark.parametrize("fmt", [1, 2, 3, 4])
+def test_every_pixel_in_doubt_overflows_into_a_sweep(hip, orc, fmt):
+    """white with gain 1 and display boost == content boost is linear 1.0: code value 1023.0 to within the estimate's error, in
+    doubt for every pixel -- far more than the lists hold (F16: a level in the half-precision subnormals)"""
+    _every_pixel_in_doubt(hip, orc, fmt, 4)
+
+
+@pytest.mark.parametrize("fmt", [1, 2, 3, 4])
+def test_every_pixel_in_doubt_overflows_into_a_sweep_from_the_per_pixel_kernel(hip, orc, fmt):
+    """the same at scale 2: the lists overflow under k_apply_px_est's appends, one per row and block of 256 pixels"""
+    _every_pixel_in_doubt(hip, orc, fmt, 2)
 
 
 def test_boosts_beyond_the_measured_range_take_the_exact_path(hip, orc):
