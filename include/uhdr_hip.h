@@ -808,6 +808,45 @@ int uhdr_hip_jpeg_encode_rgba420_batch(int n, const uhdr_hip_image_t* images, co
 int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf, int quality,
                                        const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
                                        size_t* out_size, int* status, int rgb_map, int mem_space, void* stream);
+/* uhdr_hip_apply_gainmap_packed_batch: HDR from an UHDR_HIP_PIX_FMT_RGBA8888 SDR image -- what UHDR_HIP_OUTPUT_SDR and
+ * UHDR_HIP_DECODE_TO_RGBA hand out -- and its gain map: decode a file once, keep the two layers, render at any display boost.
+ * Device memory, asynchronous on `stream`, graph-capturable; the one exception is the weight-table upload for a scale factor seen
+ * for the first time, as in uhdr_hip_apply_gainmap_batch (uhdr_hip_stream_reserve covers it).
+ *   sdr_images[i]      RGBA8888 as defined at the pixel-format constants: sRGB, full range, alpha ignored, 4-byte aligned, luma_stride
+ *                      in pixels (0 = width).
+ *   gainmap_images[i]  pixelFormat selects the form, as in uhdr_hip_apply_gainmap_md_batch: MONOCHROME or UNSPECIFIED -- one plane,
+ *                      rows of `width` bytes; RGBA8888 -- per channel, 4-byte aligned, luma_stride in pixels (0 = width).  Every map
+ *                      of a call has the first map's form.  Any integer scale factor, checked as the reference's applyGainMap checks it.
+ *   DEGENERATE metadata (the *_md_* section's term): the reference's applyGainMap (ultrahdr.cpp:429-489) with lines 429-431 replaced by
+ *                      rgb_gamma_sdr.c = (float)code_c * (1 / 255.0f); srgbInvOetf, sampleMap with the IDW tables, applyGain(...,
+ *                      display_boost), / display_boost, the OETF and the packing of output_format follow unchanged.
+ *   the contract       every step behind the pixel value is per channel, so channel c of a result pixel is channel c of
+ *                      uhdr_hip_apply_gainmap_batch run on a grey image: Y = plane c of the SDR image, Cb = Cr = 128 (an RGBA map:
+ *                      that run with plane c of the map).  UHDR_HIP_APPLY_EXACT and _EXACT_UNFILTERED: bit for bit -- every pixel
+ *                      takes the exact path (the sRGB stage is a 256-entry table of the exact function's floats), there is no f32
+ *                      pre-filter.  UHDR_HIP_APPLY_FAST: every 10-bit channel within 1 code and every F16 channel within 1
+ *                      half-precision ULP of it.  UHDR_HIP_APPLY_LUT: ERROR_UNSUPPORTED_FEATURE.
+ *   GENERAL metadata   the formula of the *_md_* section with e_c = srgbInvOetf((float)code_c * (1 / 255.0f)), the table's value; one
+ *                      f32 arithmetic under FAST and EXACT, held to that section's bars against the formula in double; LUT and
+ *                      EXACT_UNFILTERED return ERROR_UNSUPPORTED_FEATURE.
+ *   output_format      1 .. 4 as in the planar calls; dests[i] comes back with width, height and the SDR image's colorGamut.  Alpha of
+ *                      RGBA1010102 and RGBA F16 is what the planar calls write.  Nothing outside the output's bytes is written.
+ * n == 0 is a no-op after the call-level checks.  Checks, in this order (the first that fails is the status):
+ *   BAD_PTR                 n < 0, a NULL sdr_images / gainmap_images / dests where n > 0, or a NULL metadata
+ *   UNSUPPORTED_FEATURE     (every image, before anything else of any image) an SDR pixelFormat other than RGBA8888; a map
+ *                           pixelFormat other than MONOCHROME / UNSPECIFIED / RGBA8888; a map whose form differs from the first map's
+ *   BAD_PTR                 (every image) a NULL data of the SDR image, the map or dests[i]; SDR data or an RGBA map's data not 4-byte
+ *                           aligned; dests[i].data not aligned to a pixel's store (RGBA F16 8 bytes, RGBA1010102 4, planar 2)
+ *   BAD_METADATA            the *_md_* section's validation (max < min included)
+ *   INVALID_DISPLAY_BOOST   max_display_boost < 1 or NaN
+ *   INVALID_OUTPUT_FORMAT   an output_format outside 1 .. 4
+ *   UNSUPPORTED_FEATURE     the apply_mode, as stated above
+ *   then per image          INVALID_STRIDE (a luma_stride of the SDR image or of an RGBA map below its width, or above 2^32 - 1);
+ *                           UNSUPPORTED_MAP_SCALE_FACTOR (an empty map, a map size that does not divide the image's, or different
+ *                           factors across and down).  Images of different sizes may share a call, as in the planar batch. */
+int uhdr_hip_apply_gainmap_packed_batch(int n, const uhdr_hip_image_t* sdr_images, const uhdr_hip_image_t* gainmap_images,
+                                        const uhdr_hip_metadata_t* metadata, int output_format, float max_display_boost,
+                                        uhdr_hip_image_t* dests, int apply_mode, void* stream);
 
 /* ---- gain maps at any scale factor (no reference counterpart; current libultrahdr: uhdr_enc_set_gainmap_scale_factor) ------
  * The apply and decode calls read maps at any integer factor; every generate call above writes them at the reference's

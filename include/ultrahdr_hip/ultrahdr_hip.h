@@ -140,6 +140,15 @@ status_t toneMapPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_uncompressed_pt
 status_t generateGainMapPacked(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompressed_ptr hdr_image_ptr, ultrahdr_transfer_function hdr_tf,
                                ultrahdr_metadata_ptr metadata, uhdr_uncompressed_ptr dest, bool multi_channel = false, void* stream = nullptr);
 
+// applyGainMap on a packed SDR image in DEVICE memory (uhdr_hip_apply_gainmap_packed_batch; no reference counterpart), on HIP device 0:
+// an ULTRAHDR_PIX_FMT_RGBA8888 SDR image (stride in pixels) and its gain map -- ULTRAHDR_PIX_FMT_MONOCHROME / _UNSPECIFIED: one plane;
+// ULTRAHDR_PIX_FMT_RGBA8888: per channel -- at any integer scale factor, with any valid metadata.  dest->data is the caller's device
+// buffer of the output format's size; the call only enqueues on `stream`.  exact: the reference's bytes (UHDR_HIP_APPLY_EXACT),
+// otherwise UHDR_HIP_APPLY_FAST.  dest comes back with width, height and the SDR image's gamut.
+status_t applyGainMapPacked(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompressed_ptr gainmap_image_ptr, ultrahdr_metadata_ptr metadata,
+                            ultrahdr_output_format output_format, float max_display_boost, uhdr_uncompressed_ptr dest, bool exact = false,
+                            void* stream = nullptr);
+
 // generateGainMap at the scale factor map_scale_factor, 1 .. 128, from a planar pair in DEVICE memory
 // (uhdr_hip_generate_gainmap_scaled_batch; the reference's factor is 4), on HIP device 0.  dest->data is the caller's device buffer --
 // (width / s) * (height / s) bytes, four times that (4-byte aligned, RGBA) with multi_channel; the call only enqueues on `stream`.

@@ -104,6 +104,7 @@ SIGNATURES = {
     "uhdr_hip_jpegr_decode_md_batch": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_float, C.POINTER(C.c_void_p),
                                                  C.POINTER(C.c_size_t), _IP, _MP, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_int]),
     "uhdr_hip_generate_gainmap_packed_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _MP, _MP, _IP, C.c_int, C.c_void_p]),
+    "uhdr_hip_apply_gainmap_packed_batch": (C.c_int, [C.c_int, _IP, _IP, _MP, C.c_int, C.c_float, _IP, C.c_int, C.c_void_p]),
     "uhdr_hip_generate_gainmap_scaled_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _MP, _MP, _IP, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "uhdr_hip_generate_gainmap_scaled_probe": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _IP, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "uhdr_hip_jpegr_encode_scaled_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
@@ -378,6 +379,18 @@ def gainmap_weight(md, max_display_boost):
     if rc != NO_ERROR:
         raise UhdrHipError("uhdr_hip_gainmap_weight -> %d" % rc)
     return w.value, d.value
+
+
+def apply_gainmap_packed(sdr_images, map_images, md, output_format, max_display_boost, dest_ptrs, apply_mode=APPLY_FAST, stream=None):
+    """uhdr_hip_apply_gainmap_packed_batch for lists of descriptors (rgba8888_image; mono_image or rgba_map_image) and destination device
+    pointers, enqueued on `stream` (a raw handle or None).  Returns the destinations' descriptors as the call filled them."""
+    n = len(sdr_images)
+    dests = image_array([out_image(p) for p in dest_ptrs])
+    rc = load().uhdr_hip_apply_gainmap_packed_batch(n, image_array(sdr_images) if n else None, image_array(map_images) if n else None, C.byref(md),
+                                                    output_format, max_display_boost, dests if n else None, apply_mode, C.c_void_p(stream))
+    if rc != NO_ERROR:
+        raise UhdrHipError("uhdr_hip_apply_gainmap_packed_batch -> %d" % rc)
+    return list(dests)
 
 
 def tonemap_headroom(hdr_tf, gamma_max, peak_nits=0.0):

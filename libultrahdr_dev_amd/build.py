@@ -17,8 +17,8 @@ LIB = os.path.join(HERE, "libuhdr_hip.so")
 SHIM_LIB = os.path.join(HERE, "libultrahdr_shim.so")
 COMM_LIB = os.path.join(HERE, "libuhdr_hip_comm.so")   # include/uhdr_hip_comm.h: the RCCL side, apart from the pixel path
 
-SOURCES = ["uhdr_kernels.hip", "uhdr_capi.hip", "uhdr_jpeg.hip", "uhdr_jpeg_dec.hip", "uhdr_jpeg_hdr.cpp", "uhdr_jpeg_prog.cpp", "uhdr_jpegr.cpp"]
-DEPS = SOURCES + ["uhdr_kernels.h", "uhdr_device_math.h", "uhdr_jpeg.h", "uhdr_jpegr.h", os.path.join(ROOT, "include", "uhdr_hip.h")]
+SOURCES = ["uhdr_kernels.hip", "uhdr_packed_apply.hip", "uhdr_capi.hip", "uhdr_jpeg.hip", "uhdr_jpeg_dec.hip", "uhdr_jpeg_hdr.cpp", "uhdr_jpeg_prog.cpp", "uhdr_jpegr.cpp"]
+DEPS = SOURCES + ["uhdr_kernels.h", "uhdr_apply_px.h", "uhdr_device_math.h", "uhdr_jpeg.h", "uhdr_jpegr.h", os.path.join(ROOT, "include", "uhdr_hip.h")]
 COMM_SOURCES = ["uhdr_comm.hip"]
 COMM_DEPS = COMM_SOURCES + [os.path.join(ROOT, "include", "uhdr_hip_comm.h")]
 SHIM_SOURCES = ["ultrahdr_shim.cpp"]

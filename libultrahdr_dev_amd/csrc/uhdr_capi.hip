@@ -54,6 +54,7 @@ struct DeviceState : StageSet {
   std::map<int, float*> idw;  // scale -> device tables (4 * scale*scale*4 floats)
   float* lut = nullptr;       // the five static transfer-function tables (kLutTotal floats), built at init
   float* tone_tab = nullptr;  // the packed tone-map's inverse OETFs of the 1024 codes, HLG then PQ (2 * kTonePackedCodes floats), built at init
+  float* srgb_codes = nullptr;   // the packed apply's srgbInvOetf(code * (1 / 255.0f)) of the 256 codes (kSrgbCodes floats), built at init
   std::vector<std::unique_ptr<StageSet>> sets;   // every set ever leased ...
   std::vector<StageSet*> free_sets;              // ... and those not in use (both under g_mu)
   std::vector<std::pair<hipStream_t, void*>> retired;   // workspaces that were outgrown while a launch may still have named them, by stream
@@ -1084,6 +1085,8 @@ int uhdr_hip_init(int device) {
     HIP_TRY(launch_build_lut_codes(st.lut, nullptr));
     HIP_TRY(hipMalloc(&st.tone_tab, sizeof(float) * 2 * kTonePackedCodes));
     HIP_TRY(launch_build_packed_tone_tables(st.tone_tab, nullptr));
+    HIP_TRY(hipMalloc(&st.srgb_codes, sizeof(float) * kSrgbCodes));
+    HIP_TRY(launch_build_srgb_codes(st.srgb_codes, nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
     HIP_TRY(jpeg::upload_tables());
     st.ready = true;
@@ -1364,6 +1367,7 @@ int uhdr_hip_shutdown(void) {
     for (auto& t : kv.second.idw) (void)hipFree(t.second);
     if (kv.second.lut) (void)hipFree(kv.second.lut);
     if (kv.second.tone_tab) (void)hipFree(kv.second.tone_tab);
+    if (kv.second.srgb_codes) (void)hipFree(kv.second.srgb_codes);
     for (void* q : kv.second.pool) if (q) (void)hipFree(q);
     for (auto& w : kv.second.stat_ws) if (w.second) (void)hipFree(w.second);
     for (auto& w : kv.second.ex_ws) if (w.second.p) (void)hipFree(w.second.p);
@@ -4138,6 +4142,81 @@ int uhdr_hip_apply_gainmap_md_batch(int n, const uhdr_hip_image_t* yuvs, const u
                               HIP_TRY(launch_apply_md(c, mc, b, m, output_format, rgb, s));
                               return UHDR_HIP_NO_ERROR;
                             });
+}
+
+// HDR from a packed SDR image and its gain map.  Chunks: consecutive images of one size, map size and (RGBA
+// maps) map stride whose rows are all 16-byte aligned at scale factor 4 (the strip form) or not (one pixel per lane); every chunk one
+// k_apply_packed_s4 / k_apply_packed_px launch.  The checks are in the header's order.
+int uhdr_hip_apply_gainmap_packed_batch(int n, const uhdr_hip_image_t* sdrs, const uhdr_hip_image_t* maps, const uhdr_hip_metadata_t* metadata,
+                                        int output_format, float max_display_boost, uhdr_hip_image_t* dests, int apply_mode, void* stream) {
+  if (n < 0 || (n > 0 && (sdrs == nullptr || maps == nullptr || dests == nullptr)) || metadata == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  auto one_plane = [](int f) { return f == UHDR_HIP_PIX_FMT_MONOCHROME || f == UHDR_HIP_PIX_FMT_UNSPECIFIED; };
+  const bool rgb = n > 0 && maps[0].pixelFormat == UHDR_HIP_PIX_FMT_RGBA8888;
+  for (int i = 0; i < n; ++i) {
+    if (sdrs[i].pixelFormat != UHDR_HIP_PIX_FMT_RGBA8888) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+    if (!(rgb ? maps[i].pixelFormat == UHDR_HIP_PIX_FMT_RGBA8888 : one_plane(maps[i].pixelFormat))) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  }
+  const bool writes = apply_writes(output_format);
+  for (int i = 0; i < n; ++i) {
+    if (sdrs[i].data == nullptr || maps[i].data == nullptr || dests[i].data == nullptr || !al(sdrs[i].data, 4) || (rgb && !al(maps[i].data, 4)))
+      return UHDR_HIP_ERROR_BAD_PTR;
+    // (a pixel of the output is one store: RGBA F16 8 bytes, RGBA1010102 4, a planar sample 2)
+    if (writes && !al(dests[i].data, output_format == UHDR_HIP_OUTPUT_HDR_LINEAR ? 8 : output_format == UHDR_HIP_OUTPUT_HDR_LINEAR_RGB_10BIT ? 2 : 4))
+      return UHDR_HIP_ERROR_BAD_PTR;
+  }
+  int rc = validate_md(metadata);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if (!(max_display_boost >= 1.0f)) return UHDR_HIP_ERROR_INVALID_DISPLAY_BOOST;
+  if (!writes) return UHDR_HIP_ERROR_INVALID_OUTPUT_FORMAT;
+  const bool general = !md_degenerate(*metadata);
+  // degenerate metadata: every pixel takes the exact path, so EXACT and EXACT_UNFILTERED are one kernel; general metadata: one f32
+  // arithmetic under FAST and EXACT, as in uhdr_hip_apply_gainmap_md_batch
+  if (apply_mode != UHDR_HIP_APPLY_FAST && apply_mode != UHDR_HIP_APPLY_EXACT && (general || apply_mode != UHDR_HIP_APPLY_EXACT_UNFILTERED))
+    return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  for (int i = 0; i < n; ++i) {
+    const uhdr_hip_image_t& sd = sdrs[i];
+    const uhdr_hip_image_t& mp = maps[i];
+    if (row_stride(sd) < sd.width || row_stride(sd) > 0xFFFFFFFFull) return UHDR_HIP_ERROR_INVALID_STRIDE;
+    if (rgb && (row_stride(mp) < mp.width || row_stride(mp) > 0xFFFFFFFFull)) return UHDR_HIP_ERROR_INVALID_STRIDE;
+    if (mp.width == 0 || mp.height == 0) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;   // validate_apply's scale-factor checks
+    if (sd.width % mp.width != 0 || sd.height % mp.height != 0) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
+    if (sd.width * mp.height != sd.height * mp.width) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
+  }
+  if (n == 0) return UHDR_HIP_NO_ERROR;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const AppMdConsts mc = apply_md_consts(*metadata, max_display_boost);
+  const int kind = general ? (mc.gamma_on != 0u ? kPackedMdGamma : kPackedMd) : (apply_mode == UHDR_HIP_APPLY_FAST ? kPackedFast : kPackedExact);
+  int i = 0;
+  while (i < n) {
+    const uhdr_hip_image_t& s0 = sdrs[i];
+    const uhdr_hip_image_t& m0 = maps[i];
+    IdwLease table;
+    if ((rc = table.take(st, (int)(s0.width / m0.width), s)) != UHDR_HIP_NO_ERROR) return rc;
+    AppConsts c = apply_consts(s0, m0, *metadata, max_display_boost, table.idw);
+    c.map_stride = (uint32_t)(rgb ? row_stride(m0) : m0.width);
+    PackedAppBatch b;
+    const Chunk ch = form_chunk(i, n,
+                                [&](int j) {
+                                  return sdrs[j].width == s0.width && sdrs[j].height == s0.height && maps[j].width == m0.width &&
+                                         maps[j].height == m0.height && (!rgb || row_stride(maps[j]) == row_stride(m0));
+                                },
+                                [&](int j, int m) {
+                                  PackedAppImage& p = b.img[m];
+                                  p.sdr = static_cast<const uint32_t*>(sdrs[j].data);
+                                  p.map = static_cast<const uint8_t*>(maps[j].data);
+                                  p.dst = dests[j].data;
+                                  p.sdr_stride = (uint32_t)row_stride(sdrs[j]);
+                                  p.pad_ = 0u;
+                                  // the strip form: a lane's four pixels are one 16-byte load and leave as 16-byte (planar: 8-byte) stores
+                                  return c.scale == 4u && c.width % 4u == 0u && al(p.sdr, 16) && p.sdr_stride % 4u == 0u && al(p.dst, 16);
+                                });
+    for (int k = 0; k < ch.m; ++k) fill_apply_dest(&sdrs[i + k], &dests[i + k]);
+    HIP_TRY(launch_apply_packed(c, mc, b, st->srgb_codes, ch.m, output_format, kind, rgb, ch.cls, s));
+    i += ch.m;
+  }
+  return UHDR_HIP_NO_ERROR;
 }
 
 // uhdr_hip_generate_gainmap_rgb_batch's chunks; every chunk one k_generate_md launch on the exact path

@@ -308,6 +308,22 @@ constexpr uint32_t kTonePackedCodes = 1024;
 constexpr uint32_t kTonePackedPeakGroups = 128;   // the most workgroup rows (of 4 image rows) the measuring pass spends per image
 static_assert(sizeof(TonePackedBatch) <= 4096, "packed tone-map kernel arguments exceed the kernarg segment");
 
+// ---- HDR from a packed SDR image and its gain map: what k_apply_packed_s4 / _px take in AppBatch's place ----
+struct PackedAppImage {    // 32 bytes
+  const uint32_t* sdr;     // RGBA8888, rows sdr_stride pixels apart
+  const uint8_t* map;      // one byte per map pixel in rows of map_w bytes, or RGBA8888 (4-byte aligned) in rows of AppConsts::map_stride pixels
+  void* dst;
+  uint32_t sdr_stride;
+  uint32_t pad_;
+};
+struct PackedAppBatch {
+  PackedAppImage img[kMaxChunk];
+};
+constexpr uint32_t kSrgbCodes = 256;   // the table of srgbInvOetf(code * (1 / 255.0f)), built once per device by the exact function
+// what becomes of a gain: the reference's applyGain in FAST or in the exact arithmetic, or general metadata's factor (AppMdConsts)
+enum PackedApplyKind : int { kPackedFast = 0, kPackedExact = 1, kPackedMd = 2, kPackedMdGamma = 3 };
+static_assert(sizeof(AppConsts) + sizeof(AppMdConsts) + sizeof(PackedAppBatch) + 16 <= 4096, "packed apply kernel arguments exceed the kernarg segment");
+
 static_assert(sizeof(GenConsts) + sizeof(GenMdConsts) + sizeof(GenBatch) <= 4096, "generate kernel arguments exceed the kernarg segment");
 static_assert(sizeof(GenConsts) + sizeof(GenMdConsts) + sizeof(PackedBatch) <= 4096, "generate kernel arguments exceed the kernarg segment");
 static_assert(sizeof(AppConsts) + sizeof(AppMdConsts) + sizeof(AppBatch) + 16 <= 4096, "apply kernel arguments exceed the kernarg segment");
@@ -350,6 +366,13 @@ void apply_est_grid(const AppConsts& c, int n, bool fast_s4, uint32_t grid[2]);
 hipError_t launch_apply_rgb(const AppConsts& c, const AppBatch& b, int n, int fmt, bool exact, hipStream_t s);
 // general metadata: per-pixel apply of one-plane maps (rows of map_w bytes) or RGBA maps (launch_apply_rgb's layout); one f32 arithmetic
 hipError_t launch_apply_md(const AppConsts& c, const AppMdConsts& m, const AppBatch& b, int n, int fmt, bool rgb, hipStream_t s);
+// packed apply (uhdr_packed_apply.hip).  table: kSrgbCodes floats (16-byte aligned), filled once per device ...
+hipError_t launch_build_srgb_codes(float* table, hipStream_t s);
+// ... and n <= kMaxChunk images of one size (and, for RGBA maps, one map stride).  kind: PackedApplyKind (m is read by the two
+// general-metadata kinds only); rgb: RGBA maps.  strip: the scale-4 form -- c.scale == 4, c.width % 4 == 0 and every image's source
+// and destination rows start on 16 bytes --, otherwise one pixel per lane at any scale factor and alignment
+hipError_t launch_apply_packed(const AppConsts& c, const AppMdConsts& m, const PackedAppBatch& b, const float* table, int n, int fmt, int kind,
+                               bool rgb, bool strip, hipStream_t s);
 // general metadata: launch_generate_rgb's launch; rgb: its RGBA map, otherwise one byte per map pixel (aligned launches: 2-byte aligned)
 hipError_t launch_generate_md(const GenConsts& c, const GenMdConsts& m, const GenBatch& b, int n, int hdr_tf, bool aligned, bool rgb,
                               hipStream_t s);

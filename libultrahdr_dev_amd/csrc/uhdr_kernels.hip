@@ -34,6 +34,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "uhdr_apply_px.h"
 #include "uhdr_device_math.h"
 #include "uhdr_wave_scan.h"
 
@@ -58,7 +59,6 @@ hipError_t upload_idw4(const float* tables) {
   return hipMemcpyToSymbol(HIP_SYMBOL(c_idw4), tables, sizeof(float) * 4 * 64);
 }
 
-constexpr float k255 = 1 / 255.0f;  // gainmapmath.cpp:579
 constexpr float k876 = 1 / 876.0f;  // gainmapmath.cpp:598
 constexpr float k896 = 1 / 896.0f;  // gainmapmath.cpp:599
 
@@ -1808,22 +1808,7 @@ __device__ __forceinline__ F3 recover_hdr(const AppConsts& c, float yf, float cr
   return o;
 }
 
-template <int FMT, bool EXACT>
-__device__ __forceinline__ F3 hdr_oetf(F3 e) {
-  if (FMT == 3) {
-    if (EXACT) { float ch[3] = {e.x, e.y, e.z}; hlg_oetf_guarded_n<3>(ch); e.x = ch[0]; e.y = ch[1]; e.z = ch[2]; }
-    else { e.x = hlg_oetf_fast(e.x); e.y = hlg_oetf_fast(e.y); e.z = hlg_oetf_fast(e.z); }
-  } else if (FMT == 2) {
-    if (EXACT) { float ch[3] = {e.x, e.y, e.z}; pq_oetf_guarded_n<3>(ch); e.x = ch[0]; e.y = ch[1]; e.z = ch[2]; }
-    else { e.x = pq_oetf_est(e.x); e.y = pq_oetf_est(e.y); e.z = pq_oetf_est(e.z); }   // (within 3e-4 of a code; pq_oetf_fast: 0.3)
-  }
-  return e;
-}
-
-__device__ __forceinline__ float map_to_float(uint32_t v) { return (float)v / 255.0f; }  // gainmapmath.cpp:632
-// the same value in 3 issue slots instead of the ~10 of an IEEE division: exact for all 256 map bytes
-// (tests/test_gpu_transfer_exhaustive.py::test_map_byte_to_float_is_exact)
-__device__ __forceinline__ float map_to_float_fast(uint32_t v) { return div_const((float)v, 255.0f, 1.0f / 255.0f); }
+// (hdr_oetf, map_to_float and map_to_float_fast: uhdr_apply_px.h)
 
 // ---- FAST path, scale factor 4 ---------------------------------------------------------------
 // Thread = one gain-map cell = a 4x4 pixel block.  The four map taps and the four 2x2 chroma samples
@@ -2481,9 +2466,7 @@ __global__ void __launch_bounds__(kApplyBlock, 4) k_apply_s4(const AppConsts c, 
 // General path: one thread per pixel; any integer scale, any pointer/stride alignment, FAST or
 // EXACT arithmetic.  Mirrors ultrahdr.cpp:427-496 + gainmapmath.cpp:686-720 literally.
 struct PxIn { float yf, u, v, gain; };
-// sampleMap's address arithmetic (gainmapmath.cpp:686-720) for pixel (x, y): the four taps' map coordinates and the pixel's weights
-struct PxTaps { uint32_t xl, xu, yl, yu; const float* w; };
-__device__ __forceinline__ PxTaps px_taps(const AppConsts& c, uint32_t x, uint32_t y);
+// (PxTaps, px_taps, px_grid and px_store: uhdr_apply_px.h)
 // the loads of ultrahdr.cpp:431-438 and sampleMap for pixel (x, y)
 __device__ __forceinline__ PxIn px_inputs(const AppConsts& c, const AppImage& im, uint32_t x, uint32_t y) {
   PxIn in;
@@ -2499,45 +2482,6 @@ __device__ __forceinline__ PxIn px_inputs(const AppConsts& c, const AppImage& im
   const float e4 = map_to_float_fast(im.map[(size_t)t.yu * c.map_w + t.xu]);
   in.gain = e1 * t.w[0] + e2 * t.w[1] + e3 * t.w[2] + e4 * t.w[3];
   return in;
-}
-__device__ __forceinline__ PxTaps px_taps(const AppConsts& c, uint32_t x, uint32_t y) {
-  const uint32_t s = c.scale;
-  uint32_t xl, yl, ox, oy;
-  if ((s & (s - 1u)) == 0u) {   // (a launch-uniform branch: scale factors are powers of two in practice)
-    const uint32_t sh = (uint32_t)__builtin_ctz(s);
-    xl = x >> sh; yl = y >> sh; ox = x & (s - 1u); oy = y & (s - 1u);
-  } else {
-    xl = x / s; yl = y / s; ox = x - xl * s; oy = y - yl * s;
-  }
-  uint32_t xu = xl + 1u, yu = yl + 1u;
-  xl = min(xl, c.map_w - 1u); xu = min(xu, c.map_w - 1u);
-  yl = min(yl, c.map_h - 1u); yu = min(yu, c.map_h - 1u);
-  int tbl = 0;
-  if (xl == xu && yl == yu) tbl = 3;
-  else if (xl == xu) tbl = 1;
-  else if (yl == yu) tbl = 2;
-  PxTaps t;
-  t.xl = xl; t.xu = xu; t.yl = yl; t.yu = yu;
-  t.w = c.idw + (size_t)tbl * s * s * 4u + (size_t)oy * s * 4u + ox * 4u;
-  return t;
-}
-// the per-pixel kernels run on a (column block, row, image) grid: no division by the width; rows beyond the grid's 65535 are
-// reached by striding
-__host__ __device__ inline dim3 px_grid(uint32_t width, uint32_t height, int n) {
-  return dim3((width + 255u) / 256u, height < 65535u ? height : 65535u, (unsigned)n);
-}
-template <int FMT>
-__device__ __forceinline__ void px_store(const AppImage& im, size_t idx, size_t total, F3 e) {
-  if (FMT == 2 || FMT == 3) {
-    static_cast<uint32_t*>(im.dst)[idx] = pack_1010102(e.x, e.y, e.z);
-  } else if (FMT == 1) {
-    static_cast<uint2*>(im.dst)[idx] = pack_f16(e.x, e.y, e.z);
-  } else {
-    uint16_t* base = static_cast<uint16_t*>(im.dst);
-    base[idx] = (uint16_t)(0x3ffu & (uint32_t)(e.x * 1023.0f));
-    base[total + idx] = (uint16_t)(0x3ffu & (uint32_t)(e.y * 1023.0f));
-    base[2 * total + idx] = (uint16_t)(0x3ffu & (uint32_t)(e.z * 1023.0f));
-  }
 }
 
 template <int FMT, bool EXACT>
@@ -2627,11 +2571,7 @@ hipError_t launch_apply_rgb(const AppConsts& c, const AppBatch& b, int n, int fm
 //   out = max(0, (e + offsetSdr) * 2^(A g' + B) - offsetHdr / d)
 // with e the FAST sRGB EOTF's value and A, B, offsetHdr / d the host's (AppMdConsts).  One f32 arithmetic: there is no reference
 // path for such metadata that an EXACT form could reproduce.
-template <bool GAMMA>
-__device__ __forceinline__ float md_factor(const AppMdConsts& m, float g) {
-  if (GAMMA) g = __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(g) * m.inv_gamma);   // log2(0) = -inf, 2^-inf = 0
-  return __builtin_amdgcn_exp2f(__builtin_fmaf(g, m.A, m.B));   // (one rounding of an exponent that reaches log2 max)
-}
+// (md_factor: uhdr_apply_px.h)
 __device__ __forceinline__ float md_channel(const AppMdConsts& m, float e, float factor) {
   return fmaxf(__builtin_fmaf(srgb_inv_oetf_fast(e) + m.off_sdr, factor, -m.off_hdr_d), 0.0f);
 }

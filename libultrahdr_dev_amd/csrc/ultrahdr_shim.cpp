@@ -481,6 +481,26 @@ status_t generateGainMapPacked(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompr
   return ULTRAHDR_NO_ERROR;
 }
 
+status_t applyGainMapPacked(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompressed_ptr gainmap_image_ptr, ultrahdr_metadata_ptr metadata,
+                            ultrahdr_output_format output_format, float max_display_boost, uhdr_uncompressed_ptr dest, bool exact, void* stream) {
+  if (sdr_image_ptr == nullptr || gainmap_image_ptr == nullptr || metadata == nullptr || dest == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
+  if (uhdr_hip_init(0) != UHDR_HIP_NO_ERROR) return ULTRAHDR_UNKNOWN_ERROR;
+  const uhdr_hip_image_t sd = to_c_packed(*sdr_image_ptr);
+  uhdr_hip_image_t mp = to_c(*gainmap_image_ptr);   // MONOCHROME and UNSPECIFIED have the C-ABI's values; anything else fails its check
+  if (gainmap_image_ptr->pixelFormat == ULTRAHDR_PIX_FMT_RGBA8888) mp.pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
+  else if (gainmap_image_ptr->pixelFormat != ULTRAHDR_PIX_FMT_MONOCHROME && gainmap_image_ptr->pixelFormat != ULTRAHDR_PIX_FMT_UNSPECIFIED)
+    mp.pixelFormat = UHDR_HIP_PIX_FMT_P010;
+  const uhdr_hip_metadata_t md = to_c(*metadata);
+  uhdr_hip_image_t d = to_c(*dest);
+  const int rc = uhdr_hip_apply_gainmap_packed_batch(1, &sd, &mp, &md, static_cast<int>(output_format), max_display_boost, &d,
+                                                     exact ? UHDR_HIP_APPLY_EXACT : UHDR_HIP_APPLY_FAST, stream);
+  if (rc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(rc);
+  dest->width = d.width;
+  dest->height = d.height;
+  dest->colorGamut = static_cast<ultrahdr_color_gamut>(d.colorGamut);
+  return ULTRAHDR_NO_ERROR;
+}
+
 status_t generateGainMapScaled(uhdr_uncompressed_ptr yuv420_image_ptr, uhdr_uncompressed_ptr p010_image_ptr, ultrahdr_transfer_function hdr_tf,
                                ultrahdr_metadata_ptr metadata, uhdr_uncompressed_ptr dest, int map_scale_factor, bool multi_channel, bool sdr_is_601,
                                void* stream) {
