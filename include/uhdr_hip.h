@@ -1068,6 +1068,57 @@ int uhdr_hip_jpegr_encode_packed_api0_batch(int n, const uhdr_hip_image_t* hdr_i
                                             uhdr_hip_metadata_t* metadata, int* status, int tonemap_op, const float* hdr_peak_nits,
                                             int rgb_map, int mem_space, void* stream);
 
+/* ---- content-adaptive gain maps for packed RGBA inputs (no reference counterpart) -------------
+ * The two sections above joined: the packed pair of uhdr_hip_generate_gainmap_packed_batch, encoded against the boost range its
+ * content has.  The definition:
+ *   sampling, colours  those of uhdr_hip_generate_gainmap_packed_batch, word for word: samplePixels per channel over the 4 x 4 block of
+ *                      both images, srgbInvOetf / hdrInvOetf(hdr_tf), the conversion into the SDR image's gamut -- the exact path.
+ *   rgb == 0           g = y_sdr > 0 ? y_hdr / y_sdr : 1 in f32 (gainmapmath.cpp:531-534), on the two luminances in nits that call
+ *                      hands to encodeGain: the SDR gamut's luminance of both colours, times 203.0f and times hdr_white_nits.
+ *   rgb != 0           the same gain per channel, on sdr.c * 203.0f and hdr.c * hdr_white_nits.
+ *   (g_min, g_max)     the extremes over all map pixels; with rgb != 0 over all three channels of all map pixels: the metadata
+ *                      carries one range.
+ *   range, metadata    uhdr_hip_adaptive_boost_range(hdr_tf, g_min, g_max) and uhdr_hip_adaptive_metadata, unchanged.
+ *   map byte           the reference's three-argument encodeGain against that metadata: what uhdr_hip_generate_gainmap_packed_batch
+ *                      writes when it is given that metadata as metadata_in.
+ *   boost_scope        PER_IMAGE and PER_CALL as in uhdr_hip_generate_gainmap_adaptive_batch.
+ * A map pixel that reads a non-finite half is unspecified, as in the packed generate; the range still satisfies lo <= 1 < hi (the
+ * rule's fminf / fmaxf drop a NaN and cap an infinity).
+ * uhdr_hip_generate_gainmap_packed_adaptive_batch.  Device memory only; the call only enqueues kernels on `stream` -- no allocation,
+ * no copy, no host synchronisation -- and can be captured into a graph.  The sources are read once: pass 1 (k_generate_packed_gains)
+ * stores every map pixel's unclamped f32 gains into `workspace`, 4 bytes per map pixel, 12 (R, G, B) with rgb != 0, and finds the
+ * extremes; k_adaptive_consts applies the rule; pass 2 (k_encode_gains, k_encode_gains_rgb) turns the stored gains into the map.
+ *   content_minmax  DEVICE, 2 n floats, optional: every image's own (g_min, g_max), in either scope
+ *   boost_range     DEVICE, 2 n floats, required: the (lo, hi) map i was encoded against (PER_CALL: n equal pairs)
+ *   workspace       DEVICE, 16-byte aligned, at least what uhdr_hip_generate_packed_adaptive_workspace_bytes answers for the same n,
+ *                   images and rgb (it reads the images' sizes only; 0 for n == 0; BAD_PTR for a NULL bytes, n < 0 or a NULL array
+ *                   where n > 0); its contents before and after the call mean nothing
+ * dests[i] needs what uhdr_hip_generate_gainmap_packed_batch's needs and comes back described as that call describes it.  Checks, in
+ * this order: those of uhdr_hip_generate_gainmap_packed_batch with metadata_in == NULL; UNSUPPORTED_FEATURE for an unknown
+ * boost_scope; BAD_PTR for a NULL or not 16-byte aligned workspace or a NULL boost_range where n > 0; ERROR_INSUFFICIENT_RESOURCE for a
+ * workspace smaller than the query's answer.  Nothing is written by a call that fails them. */
+int uhdr_hip_generate_packed_adaptive_workspace_bytes(int n, const uhdr_hip_image_t* sdr_images, int rgb, size_t* bytes);
+int uhdr_hip_generate_gainmap_packed_adaptive_batch(int n, const uhdr_hip_image_t* sdr_images, const uhdr_hip_image_t* hdr_images,
+                                                    int hdr_tf, uhdr_hip_image_t* dests, int rgb, int boost_scope, float* content_minmax,
+                                                    float* boost_range, void* workspace, size_t workspace_bytes, void* stream);
+/* One pair in DEVICE memory through that call with PER_IMAGE, the workspace the library's, the measured metadata returned to the
+ * host (required): the call waits for `stream`.  BAD_PTR for a NULL argument, then the batch call's image checks for n = 1. */
+int uhdr_hip_generate_gainmap_packed_adaptive(const uhdr_hip_image_t* sdr_image, const uhdr_hip_image_t* hdr_image, int hdr_tf,
+                                              uhdr_hip_metadata_t* metadata, uhdr_hip_image_t* dest, int rgb, void* stream);
+/* uhdr_hip_jpegr_encode_packed_batch (sdr_images != NULL) or uhdr_hip_jpegr_encode_packed_api0_batch (sdr_images == NULL: the SDR
+ * images are uhdr_hip_tonemap_packed_batch's, hdr_peak_nits as in that call -- HOST, n floats or NULL; it is not read when sdr_images
+ * is given) with the generate step replaced by the call above: the same checks in the same order, the same rounds and sort, the same
+ * single synchronisation per round, the same primary JPEG, ICC profile and container.  An unknown boost_scope is UNSUPPORTED_FEATURE,
+ * right after INVALID_QUALITY_FACTOR.  A round's boost_range pairs come down with its compressed streams; the containers carry the
+ * measured range in the gain map's XMP, and metadata (HOST, n entries, optional) receives it for every file that was processed.  The
+ * workspace is a pool slot of the call's codec context.  PER_CALL pools the files that passed their checks; over more than one round
+ * (more than 64 such files) it follows uhdr_hip_jpegr_encode_adaptive_batch's rule: every round is staged (API-0: tone-mapped) and
+ * measured first, the pooled extremes carried from round to round in device memory, then every round is staged again and encoded. */
+int uhdr_hip_jpegr_encode_packed_adaptive_batch(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf,
+                                                int quality, const void* const* exif, const size_t* exif_size, void* const* out,
+                                                const size_t* out_capacity, size_t* out_size, uhdr_hip_metadata_t* metadata, int* status,
+                                                const float* hdr_peak_nits, int rgb_map, int boost_scope, int mem_space, void* stream);
+
 /* ---- introspection for tests -------------------------------------------------------------- */
 /* copies the 4 Shepard IDW weight tables (standard, no-right, no-bottom, corner; each
  * scale*scale*4 floats; gainmapmath.h:184-228) the apply kernels use for `scale` into out[] */

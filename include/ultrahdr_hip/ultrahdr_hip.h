@@ -140,6 +140,13 @@ status_t toneMapPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_uncompressed_pt
 status_t generateGainMapPacked(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompressed_ptr hdr_image_ptr, ultrahdr_transfer_function hdr_tf,
                                ultrahdr_metadata_ptr metadata, uhdr_uncompressed_ptr dest, bool multi_channel = false, void* stream = nullptr);
 
+// generateGainMapPacked against the range the content has (uhdr_hip_generate_gainmap_packed_adaptive; include/uhdr_hip.h,
+// "content-adaptive gain maps for packed RGBA inputs"): the same arguments and buffers; *metadata (optional) receives the measured
+// range, so the call waits for `stream`, as generateGainMapAdaptive does.
+status_t generateGainMapPackedAdaptive(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompressed_ptr hdr_image_ptr, ultrahdr_transfer_function hdr_tf,
+                                       ultrahdr_metadata_ptr metadata, uhdr_uncompressed_ptr dest, bool multi_channel = false,
+                                       void* stream = nullptr);
+
 // applyGainMap on a packed SDR image in DEVICE memory (uhdr_hip_apply_gainmap_packed_batch; no reference counterpart), on HIP device 0:
 // an ULTRAHDR_PIX_FMT_RGBA8888 SDR image (stride in pixels) and its gain map -- ULTRAHDR_PIX_FMT_MONOCHROME / _UNSPECIFIED: one plane;
 // ULTRAHDR_PIX_FMT_RGBA8888: per channel -- at any integer scale factor, with any valid metadata.  dest->data is the caller's device
@@ -263,13 +270,14 @@ class JpegRHip {
   // Packed RGBA inputs (include/uhdr_hip.h, "packed RGBA inputs"; no reference counterpart): an ULTRAHDR_PIX_FMT_RGBA1010102 (HLG / PQ)
   // or ULTRAHDR_PIX_FMT_RGBAF16 (linear) HDR image and an ULTRAHDR_PIX_FMT_RGBA8888 SDR image, host memory, luma_stride in pixels
   // (0 = width), full range.  The gain map comes from the packed pair itself, the primary image is the SDR image compressed as
-  // 4:2:0 from RGB, the container is API-1's (uhdr_hip_jpegr_encode_packed_batch).  Honours setMultiChannelGainMap; setContentBoost
-  // and setToneMap do not apply.
+  // 4:2:0 from RGB, the container is API-1's (uhdr_hip_jpegr_encode_packed_batch).  Honours setMultiChannelGainMap and, together
+  // with it, setContentBoost (uhdr_hip_jpegr_encode_packed_adaptive_batch); setToneMap does not apply: the SDR image is given.
   status_t encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_uncompressed_ptr sdr_image_ptr, ultrahdr_transfer_function hdr_tf,
                              uhdr_compressed_ptr dest, int quality, uhdr_exif_ptr exif);
   // The packed API-0 (include/uhdr_hip.h, "tone-mapped SDR image from a packed HDR image"): the HDR image alone; the SDR image is
   // tone-mapped from it on the device (uhdr_hip_jpegr_encode_packed_api0_batch).  Honours setMultiChannelGainMap and the
-  // hdr_peak_nits given to setToneMap (0, the default, measures the headroom); the operator is always REINHARD_MAXRGB.
+  // hdr_peak_nits given to setToneMap (0, the default, measures the headroom); the operator is always REINHARD_MAXRGB.  Honours
+  // setContentBoost as the overload above does, with that peak.
   status_t encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, ultrahdr_transfer_function hdr_tf, uhdr_compressed_ptr dest, int quality,
                              uhdr_exif_ptr exif);
   // (:213) dest->data, exif->data and gainmap_image_ptr->data are caller-allocated, as in the reference
@@ -281,7 +289,8 @@ class JpegRHip {
 
   void setApplyMode(int mode) { mApplyMode = mode; }   // UHDR_HIP_APPLY_EXACT (default here: decoded files equal the reference's), FAST, LUT
   // -1 (default): the reference's constant boost range.  UHDR_HIP_BOOST_PER_IMAGE / UHDR_HIP_BOOST_PER_CALL: the API-0 and API-1
-  // overloads encode the gain map against the range the content has (uhdr_hip_jpegr_encode_adaptive_batch); the others are unchanged
+  // overloads encode the gain map against the range the content has (uhdr_hip_jpegr_encode_adaptive_batch), and so do both
+  // encodeJPEGRPacked overloads (uhdr_hip_jpegr_encode_packed_adaptive_batch); the others are unchanged
   void setContentBoost(int scope_or_minus_one) { mContentBoost = scope_or_minus_one; }
   // UHDR_HIP_TONEMAP_SHIFT (default): the API-0 overload derives its SDR image like the reference, by bit shift.
   // UHDR_HIP_TONEMAP_REINHARD_MAXRGB: tone-mapped from linear light against the image's headroom -- measured, or hdr_peak_nits / 203

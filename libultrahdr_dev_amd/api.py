@@ -205,6 +205,13 @@ SIGNATURES = {
     "uhdr_hip_jpegr_encode_packed_api0_batch": (C.c_int, [C.c_int, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                           C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _MP,
                                                           C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_void_p]),
+    "uhdr_hip_generate_packed_adaptive_workspace_bytes": (C.c_int, [C.c_int, _IP, C.c_int, C.POINTER(C.c_size_t)]),
+    "uhdr_hip_generate_gainmap_packed_adaptive_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, _IP, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                                  C.c_void_p, C.c_size_t, C.c_void_p]),
+    "uhdr_hip_generate_gainmap_packed_adaptive": (C.c_int, [_IP, _IP, C.c_int, _MP, _IP, C.c_int, C.c_void_p]),
+    "uhdr_hip_jpegr_encode_packed_adaptive_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                              C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _MP,
+                                                              C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 
 _lib = None
@@ -408,6 +415,16 @@ def adaptive_workspace_bytes(yuv_images):
     rc = load().uhdr_hip_generate_adaptive_workspace_bytes(len(yuv_images), image_array(yuv_images) if yuv_images else None, C.byref(n))
     if rc != NO_ERROR:
         raise UhdrHipError("uhdr_hip_generate_adaptive_workspace_bytes -> %d" % rc)
+    return n.value
+
+
+def packed_adaptive_workspace_bytes(sdr_images, rgb):
+    """uhdr_hip_generate_packed_adaptive_workspace_bytes for a list of Image descriptors; rgb: per-channel maps"""
+    n = C.c_size_t()
+    rc = load().uhdr_hip_generate_packed_adaptive_workspace_bytes(len(sdr_images), image_array(sdr_images) if sdr_images else None,
+                                                                  1 if rgb else 0, C.byref(n))
+    if rc != NO_ERROR:
+        raise UhdrHipError("uhdr_hip_generate_packed_adaptive_workspace_bytes -> %d" % rc)
     return n.value
 
 

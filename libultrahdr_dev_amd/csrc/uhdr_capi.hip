@@ -394,6 +394,28 @@ Chunk gen_chunk(int i, int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image
   for (int k = 0; k < ch.m; ++k) fill_generate_dest(&yuvs[i + k], &dests[i + k], scale, rgb);
   return ch;
 }
+// The chunk of the packed generate family from pair i on: equal size and gamuts; the class is 16-byte row pieces of both images (a
+// dword format: 4 pixels, F16: 2), a width of whole pairs' blocks and a map -- map_of(j), or pair j's gains -- on map_align bytes
+template <class MapOf>
+Chunk packed_chunk(int i, int n, const uhdr_hip_image_t* sdrs, const uhdr_hip_image_t* hdrs, bool f16, PackedBatch& b, MapOf map_of,
+                   size_t map_align) {
+  const uhdr_hip_image_t& s0 = sdrs[i];
+  return form_chunk(i, n,
+                    [&](int j) {
+                      return sdrs[j].width == s0.width && sdrs[j].height == s0.height && sdrs[j].colorGamut == s0.colorGamut &&
+                             hdrs[j].colorGamut == hdrs[i].colorGamut;
+                    },
+                    [&](int j, int m) {
+                      PackedImage& p = b.img[m];
+                      p.sdr = static_cast<const uint32_t*>(sdrs[j].data);
+                      p.hdr = hdrs[j].data;
+                      p.map = static_cast<uint8_t*>(map_of(j));
+                      p.sdr_stride = (uint32_t)row_stride(sdrs[j]);
+                      p.hdr_stride = (uint32_t)row_stride(hdrs[j]);
+                      return s0.width % 8u == 0 && al(p.sdr, 16) && p.sdr_stride % 4u == 0 && al(p.hdr, 16) &&
+                             p.hdr_stride % (f16 ? 2u : 4u) == 0 && al(p.map, map_align);
+                    });
+}
 
 // ---- content-adaptive generate ---------------------------------------------------------------------
 // the range rule of include/uhdr_hip.h, in f32; k_adaptive_consts performs the same operations on the device
@@ -417,13 +439,13 @@ bool valid_boost_scope(int scope) { return scope == UHDR_HIP_BOOST_PER_IMAGE || 
 // hdr_peak_nits of the tone-mapped SDR base image: 0 (the headroom is measured) or a positive finite figure
 bool valid_peak_nits(float peak) { return peak >= 0.0f && std::isfinite(peak); }
 
-// the caller's workspace: the images' key pairs, their constants, then every image's gains (4 bytes per map pixel), each piece
-// a multiple of 256 bytes
+// the caller's workspace: the images' key pairs, their constants, then every image's gains (gain_bytes per map pixel: 4, the packed
+// call's RGB maps 12), each piece a multiple of 256 bytes
 struct AdaptLayout {
   size_t keys = 0, consts = 0, total = 0;
   std::vector<size_t> gains;
 };
-AdaptLayout adaptive_layout(int n, const uhdr_hip_image_t* yuvs) {
+AdaptLayout adaptive_layout(int n, const uhdr_hip_image_t* yuvs, size_t gain_bytes = sizeof(float)) {
   AdaptLayout l;
   if (n <= 0) return l;
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -433,7 +455,7 @@ AdaptLayout adaptive_layout(int n, const uhdr_hip_image_t* yuvs) {
   l.gains.resize((size_t)n);
   for (int i = 0; i < n; ++i) {
     l.gains[(size_t)i] = o;
-    o += up(sizeof(float) * (yuvs[i].width / 4) * (yuvs[i].height / 4));
+    o += up(gain_bytes * (yuvs[i].width / 4) * (yuvs[i].height / 4));
   }
   l.total = o;
   return l;
@@ -442,11 +464,14 @@ AdaptLayout adaptive_layout(int n, const uhdr_hip_image_t* yuvs) {
 // The two passes of uhdr_hip_generate_gainmap_adaptive_batch on checked arguments, enqueue only.  carry_in / carry_out (DEVICE, two
 // key words, or null; PER_CALL only): the pooled extremes of earlier calls join this call's, and the joined pair is left behind --
 // a statistic taken over several calls.  encode == false stops after the constants: the call only measures.
-int adaptive_enqueue(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf, uhdr_hip_image_t* dests,
-                     int sdr_is_601, int boost_scope, float* content_minmax, float* boost_range, void* workspace,
-                     const uint32_t* carry_in, uint32_t* carry_out, bool encode, hipStream_t s) {
-  if (n <= 0) return UHDR_HIP_NO_ERROR;
-  const AdaptLayout lay = adaptive_layout(n, yuvs);
+// What does not depend on the input form: the workspace's pieces, the keys' init, pass 1 chunk by chunk -- pass1(i, c, gains_of)
+// forms the chunk from image i on, launches it and returns its size (or a negative hipError_t); c arrives with the image's constants
+// and its key words, gains_of(j) is where image j's gains go --, the constants, and pass 2 over the same chunks (rgb: RGBA maps from
+// three gains per map pixel).  sdrs: the images whose sizes and gamuts the chunks follow (the yuv420 or the RGBA8888 ones).
+template <class Pass1>
+int adaptive_passes(int n, const uhdr_hip_image_t* sdrs, const uhdr_hip_image_t* hdrs, int hdr_tf, uhdr_hip_image_t* dests, int sdr_is_601,
+                    bool rgb, const AdaptLayout& lay, int boost_scope, float* content_minmax, float* boost_range, void* workspace,
+                    const uint32_t* carry_in, uint32_t* carry_out, bool encode, hipStream_t s, Pass1 pass1) {
   uint8_t* ws = static_cast<uint8_t*>(workspace);
   uint32_t* keys = reinterpret_cast<uint32_t*>(ws + lay.keys);
   AdaptConsts* consts = reinterpret_cast<AdaptConsts*>(ws + lay.consts);
@@ -456,15 +481,14 @@ int adaptive_enqueue(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t
   std::vector<std::pair<int, int>> chunks;   // (first image, images) of every launch
   int i = 0;
   while (i < n) {
-    const uhdr_hip_image_t& y0 = yuvs[i];
-    GenConsts c = generate_consts(y0.colorGamut, p010s[i].colorGamut, hdr_tf, sdr_is_601, y0.width, y0.height, md);
+    const uhdr_hip_image_t& y0 = sdrs[i];
+    GenConsts c = generate_consts(y0.colorGamut, hdrs[i].colorGamut, hdr_tf, sdr_is_601, y0.width, y0.height, md);
     c.stat_keys = keys + 2 * i;
     c.stat_stride = 2;
-    GenBatch b;
-    const Chunk ch = gen_chunk(i, n, yuvs, p010s, b, [&](int j) { return ws + lay.gains[(size_t)j]; }, no_more);
-    HIP_TRY(launch_generate_gains(c, b, ch.m, hdr_tf, ch.cls, s));
-    chunks.emplace_back(i, ch.m);
-    i += ch.m;
+    const int m = pass1(i, c, [&](int j) { return ws + lay.gains[(size_t)j]; });
+    if (m < 0) { set_err("adaptive pass 1", (hipError_t)-m); return UHDR_HIP_UNKNOWN_ERROR; }
+    chunks.emplace_back(i, m);
+    i += m;
   }
   HIP_TRY(launch_adaptive_consts(keys, n, boost_scope == UHDR_HIP_BOOST_PER_CALL ? 1 : 0, adaptive_cap(hdr_tf), consts, content_minmax,
                                  boost_range, carry_in, carry_out, s));
@@ -475,12 +499,42 @@ int adaptive_enqueue(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t
       const size_t j = (size_t)(ch.first + k);
       eb.img[k].gains = reinterpret_cast<const float*>(ws + lay.gains[j]);
       eb.img[k].map = static_cast<uint8_t*>(dests[j].data);
-      fill_generate_dest(&yuvs[j], &dests[j]);
+      fill_generate_dest(&sdrs[j], &dests[j], 4, rgb);
     }
-    const uhdr_hip_image_t& y0 = yuvs[ch.first];
-    HIP_TRY(launch_encode_gains(consts + ch.first, eb, ch.second, (uint32_t)((y0.width / 4) * (y0.height / 4)), s));
+    const uhdr_hip_image_t& y0 = sdrs[ch.first];
+    const uint32_t pixels = (uint32_t)((y0.width / 4) * (y0.height / 4));
+    if (rgb) HIP_TRY(launch_encode_gains_rgb(consts + ch.first, eb, ch.second, pixels, s));
+    else HIP_TRY(launch_encode_gains(consts + ch.first, eb, ch.second, pixels, s));
   }
   return UHDR_HIP_NO_ERROR;
+}
+int adaptive_enqueue(int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, int hdr_tf, uhdr_hip_image_t* dests,
+                     int sdr_is_601, int boost_scope, float* content_minmax, float* boost_range, void* workspace,
+                     const uint32_t* carry_in, uint32_t* carry_out, bool encode, hipStream_t s) {
+  if (n <= 0) return UHDR_HIP_NO_ERROR;
+  return adaptive_passes(n, yuvs, p010s, hdr_tf, dests, sdr_is_601, false, adaptive_layout(n, yuvs), boost_scope, content_minmax, boost_range,
+                         workspace, carry_in, carry_out, encode, s, [&](int i, const GenConsts& c, auto gains_of) {
+                           GenBatch b;
+                           const Chunk ch = gen_chunk(i, n, yuvs, p010s, b, gains_of, no_more);
+                           const hipError_t e = launch_generate_gains(c, b, ch.m, hdr_tf, ch.cls, s);
+                           return e == hipSuccess ? ch.m : -(int)e;
+                         });
+}
+// The same for packed RGBA pairs: pass 1 is k_generate_packed_gains over the packed call's chunks; an RGB
+// map keeps three gains per map pixel
+size_t packed_gain_bytes(bool rgb) { return sizeof(float) * (rgb ? 3 : 1); }
+int packed_adaptive_enqueue(int n, const uhdr_hip_image_t* sdrs, const uhdr_hip_image_t* hdrs, int hdr_tf, uhdr_hip_image_t* dests, bool rgb,
+                            int boost_scope, float* content_minmax, float* boost_range, void* workspace, const uint32_t* carry_in,
+                            uint32_t* carry_out, bool encode, hipStream_t s) {
+  if (n <= 0) return UHDR_HIP_NO_ERROR;
+  const bool f16 = hdrs[0].pixelFormat == UHDR_HIP_PIX_FMT_RGBA_F16;
+  return adaptive_passes(n, sdrs, hdrs, hdr_tf, dests, 0, rgb, adaptive_layout(n, sdrs, packed_gain_bytes(rgb)), boost_scope, content_minmax,
+                         boost_range, workspace, carry_in, carry_out, encode, s, [&](int i, const GenConsts& c, auto gains_of) {
+                           PackedBatch b;
+                           const Chunk ch = packed_chunk(i, n, sdrs, hdrs, f16, b, gains_of, 16);   // (a piece of the workspace: always)
+                           const hipError_t e = launch_generate_packed_gains(c, b, ch.m, hdr_tf, f16, ch.cls, rgb, s);
+                           return e == hipSuccess ? ch.m : -(int)e;
+                         });
 }
 
 // ---- FAST apply's line-segment tables (uhdr_kernels.h, k_apply_s4) ---------------------------------
@@ -3098,10 +3152,13 @@ int uhdr_hip_jpegr_encode_scaled_batch(int n, const uhdr_hip_image_t* p010_image
 // sdr_images == NULL: the packed API-0 -- the SDR side of the checks falls away, a file's SDR image is
 // uhdr_hip_tonemap_packed_batch's in a pool slot of the round's context (peaks: one per file, or NULL), in the HDR image's gamut;
 // metadata (or NULL) receives what every processed file's container carries
+// boost_scope >= 0: the adaptive generate in the generate step's place, as in encode_round -- the workspace and
+// the carried key pair are the same pool slots, a round's ranges come down with its streams, and PER_CALL over several rounds stages
+// and measures every round (carry == 1) in front of the first one
 static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf, int quality,
                                const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
                                size_t* out_size, int* status, int rgb_map, int mem_space, void* stream, uhdr_hip_metadata_t* metadata,
-                               const float* peaks) {
+                               const float* peaks, int boost_scope = -1) {
   const bool api0 = sdr_images == nullptr;
   const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
   auto stride_bad = [](const uhdr_hip_image_t& im) { return im.luma_stride != 0 && (im.luma_stride < im.width || im.luma_stride > 0xFFFFFFFFull); };
@@ -3154,10 +3211,10 @@ static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const 
   std::stable_sort(files.begin(), files.end(), [&](const PackedFile& x, const PackedFile& y) { return key(x) < key(y); });
   auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
   size_t done = 0;
-  const int rc = run_rounds(
-      files.size(), (size_t)kEncRound, stream, [](size_t) { return (size_t)0; },   // rounds by count alone
-      [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
-        PackedFile* f = &files[r0];
+  const int carry_all = boost_scope == UHDR_HIP_BOOST_PER_CALL && files.size() > (size_t)kEncRound ? 2 : 0;
+  std::vector<float> range(2 * (size_t)kEncRound);
+  // one round: f[0 .. m) staged, tone-mapped, generated; carry == 1 stops behind the measuring pass
+  auto round = [&](DeviceState* st, hipStream_t s, PackedFile* f, int m, int carry) -> int {
         int rc;
         size_t map_total = 0, sdr_total = 0, hdr_total = 0;
         for (int k = 0; k < m; ++k) {
@@ -3202,7 +3259,20 @@ static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const 
             return rc;
         }
         uhdr_hip_metadata_t md;
-        if ((rc = uhdr_hip_generate_gainmap_packed_batch(m, a.data(), b.data(), hdr_tf, nullptr, &md, c.data(), rgb_map, s)) != UHDR_HIP_NO_ERROR) return rc;
+        float* dev_range = nullptr;
+        if (boost_scope < 0) {
+          if ((rc = uhdr_hip_generate_gainmap_packed_batch(m, a.data(), b.data(), hdr_tf, nullptr, &md, c.data(), rgb_map, s)) != UHDR_HIP_NO_ERROR) return rc;
+        } else {
+          const size_t ws_bytes = adaptive_layout(m, a.data(), packed_gain_bytes(rgb_map != 0)).total;
+          if ((rc = pool_reserve(st, kEncAdaptWs, ws_bytes + 256 + round_up(8 * (size_t)m, 256))) != 0) return rc;
+          uint8_t* ws = static_cast<uint8_t*>(st->pool[kEncAdaptWs]);
+          dev_range = reinterpret_cast<float*>(ws + ws_bytes + 256);
+          uint32_t* cw = carry != 0 ? static_cast<uint32_t*>(st->pool[kEncAdaptCarry]) : nullptr;
+          if ((rc = packed_adaptive_enqueue(m, a.data(), b.data(), hdr_tf, c.data(), rgb_map != 0, boost_scope, nullptr, dev_range, ws, cw,
+                                            carry == 1 ? cw : nullptr, carry != 1, s)) != UHDR_HIP_NO_ERROR)
+            return rc;
+          if (carry == 1) return UHDR_HIP_NO_ERROR;
+        }
         std::vector<EncJpeg> jpg(2 * (size_t)m);
         if ((rc = rgba420_planes(st, kEncSdr, s, m, a.data(), jpg.data(), 2)) != 0) return rc;
         for (int k = 0; k < m; ++k) {
@@ -3211,18 +3281,41 @@ static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const 
           uhdr_hip_image_t g = c[(size_t)k];   // (generate has filled in width, height and stride)
           jpg[2 * (size_t)k + 1] = rgb_map != 0 ? gainmap_rgb_jpeg(g) : gainmap_jpeg(g, g.luma_stride);
         }
-        if ((rc = compress_to_host(st, s, 2 * m, jpg.data())) != UHDR_HIP_NO_ERROR) return rc;
+        if ((rc = compress_to_host(st, s, 2 * m, jpg.data(), true, dev_range, dev_range ? 8 * (size_t)m : 0, range.data())) != UHDR_HIP_NO_ERROR)
+          return rc;
         on_host_threads(m, [&](int lo, int hi) {
           for (int k = lo; k < hi; ++k) {
             const int i = f[k].idx;
             const EncJpeg& sdr = jpg[2 * (size_t)k];
             const EncJpeg& gm = jpg[2 * (size_t)k + 1];
+            uhdr_hip_metadata_t mk = md;   // adaptive: every file's own
+            if (boost_scope >= 0) fill_adaptive_metadata(range[2 * (size_t)k], range[2 * (size_t)k + 1], &mk);
             st_[i] = jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
-                                              nullptr, 0, md, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i], false);
-            if (metadata != nullptr) metadata[i] = md;
+                                              nullptr, 0, mk, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i], boost_scope >= 0);
+            if (metadata != nullptr) metadata[i] = mk;
           }
         });
         return (int)UHDR_HIP_NO_ERROR;
+  };
+  // PER_CALL over several rounds: the statistic of all rounds first, the pooled extremes carried along in device memory (encode_files)
+  auto measure_all = [&](DeviceState* st, hipStream_t s) -> int {
+    int rc = pool_reserve(st, kEncAdaptCarry, 256);
+    if (rc != UHDR_HIP_NO_ERROR) return rc;
+    const hipError_t e = launch_adaptive_init(static_cast<uint32_t*>(st->pool[kEncAdaptCarry]), 2u, s);
+    if (e != hipSuccess) { set_err("launch_adaptive_init", e); return UHDR_HIP_UNKNOWN_ERROR; }
+    for (size_t q0 = 0; rc == UHDR_HIP_NO_ERROR && q0 < files.size(); q0 += kEncRound) {
+      const int m = (int)std::min(files.size() - q0, (size_t)kEncRound);
+      std::vector<PackedFile> probe(files.begin() + (long)q0, files.begin() + (long)q0 + m);   // (a round rewrites its files' descriptors)
+      rc = round(st, s, probe.data(), m, 1);
+    }
+    return rc;
+  };
+  const int rc = run_rounds(
+      files.size(), (size_t)kEncRound, stream, [](size_t) { return (size_t)0; },   // rounds by count alone
+      [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
+        // the measuring pass needs the leased context, which the driver hands over with a round: it goes in front of the first one
+        const int rc = carry_all != 0 && r0 == 0 ? measure_all(st, s) : (int)UHDR_HIP_NO_ERROR;
+        return rc != UHDR_HIP_NO_ERROR ? rc : round(st, s, &files[r0], m, carry_all);
       },
       &done);
   for (size_t k = done; k < files.size(); ++k) st_[files[k].idx] = rc;   // the files of the failed round and of those behind it
@@ -3254,6 +3347,20 @@ int uhdr_hip_jpegr_encode_packed_api0_batch(int n, const uhdr_hip_image_t* hdr_i
   if (tonemap_op != UHDR_HIP_TONEMAP_REINHARD_MAXRGB) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   return encode_packed_files(n, hdr_images, nullptr, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, rgb_map, mem_space,
                              stream, metadata, hdr_peak_nits);
+}
+
+// both with the adaptive generate: sdr_images == NULL is the packed API-0
+int uhdr_hip_jpegr_encode_packed_adaptive_batch(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf, int quality,
+                                                const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                                size_t* out_size, uhdr_hip_metadata_t* metadata, int* status, const float* hdr_peak_nits,
+                                                int rgb_map, int boost_scope, int mem_space, void* stream) {
+  if (n < 0 || (n > 0 && (hdr_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  if (!valid_boost_scope(boost_scope)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return encode_packed_files(n, hdr_images, sdr_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, rgb_map, mem_space,
+                             stream, metadata, sdr_images == nullptr ? hdr_peak_nits : nullptr, boost_scope);
 }
 
 int uhdr_hip_jpegr_encode_adaptive_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf,
@@ -4240,11 +4347,9 @@ int uhdr_hip_generate_gainmap_md_batch(int n, const uhdr_hip_image_t* yuvs, cons
   return UHDR_HIP_NO_ERROR;
 }
 
-// Packed RGBA inputs (DESIGN.md section 4.1.6): uhdr_hip_generate_gainmap_md_batch's chunks over an RGBA8888 SDR image and an
-// RGBA1010102 / RGBA F16 HDR image; every chunk one k_generate_packed launch on the exact path
-int uhdr_hip_generate_gainmap_packed_batch(int n, const uhdr_hip_image_t* sdrs, const uhdr_hip_image_t* hdrs, int hdr_tf,
-                                           const uhdr_hip_metadata_t* md_in, uhdr_hip_metadata_t* md_out, uhdr_hip_image_t* dests, int rgb,
-                                           void* stream) {
+// uhdr_hip_generate_gainmap_packed_batch's checks, in the header's order; *f16: the HDR images are RGBA F16
+static int check_generate_packed(int n, const uhdr_hip_image_t* sdrs, const uhdr_hip_image_t* hdrs, int hdr_tf, const uhdr_hip_metadata_t* md_in,
+                                 const uhdr_hip_image_t* dests, int rgb, bool* f16_out) {
   if (n < 0 || (n > 0 && (sdrs == nullptr || hdrs == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
   for (int i = 0; i < n; ++i) {
     if (sdrs[i].pixelFormat != UHDR_HIP_PIX_FMT_RGBA8888) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
@@ -4270,6 +4375,18 @@ int uhdr_hip_generate_gainmap_packed_batch(int n, const uhdr_hip_image_t* sdrs, 
     if (!valid_gamut(sd.colorGamut) || !valid_gamut(hd.colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
   }
   if (!tf_known(hdr_tf)) return UHDR_HIP_ERROR_INVALID_TRANS_FUNC;
+  *f16_out = f16;
+  return UHDR_HIP_NO_ERROR;
+}
+
+// Packed RGBA inputs (DESIGN.md section 4.1.6): uhdr_hip_generate_gainmap_md_batch's chunks over an RGBA8888 SDR image and an
+// RGBA1010102 / RGBA F16 HDR image; every chunk one k_generate_packed launch on the exact path
+int uhdr_hip_generate_gainmap_packed_batch(int n, const uhdr_hip_image_t* sdrs, const uhdr_hip_image_t* hdrs, int hdr_tf,
+                                           const uhdr_hip_metadata_t* md_in, uhdr_hip_metadata_t* md_out, uhdr_hip_image_t* dests, int rgb,
+                                           void* stream) {
+  bool f16 = false;
+  int rc = check_generate_packed(n, sdrs, hdrs, hdr_tf, md_in, dests, rgb, &f16);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   DeviceState* st = nullptr;
   if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -4283,27 +4400,36 @@ int uhdr_hip_generate_gainmap_packed_batch(int n, const uhdr_hip_image_t* sdrs, 
     const GenConsts c = generate_consts(s0.colorGamut, hdrs[i].colorGamut, hdr_tf, 0, s0.width, s0.height, md);
     const GenMdConsts mc = generate_md_consts(md, c);
     PackedBatch b;
-    const Chunk ch = form_chunk(i, n,
-                                [&](int j) {
-                                  return sdrs[j].width == s0.width && sdrs[j].height == s0.height && sdrs[j].colorGamut == s0.colorGamut &&
-                                         hdrs[j].colorGamut == hdrs[i].colorGamut;
-                                },
-                                [&](int j, int m) {
-                                  PackedImage& p = b.img[m];
-                                  p.sdr = static_cast<const uint32_t*>(sdrs[j].data);
-                                  p.hdr = hdrs[j].data;
-                                  p.map = static_cast<uint8_t*>(dests[j].data);
-                                  p.sdr_stride = (uint32_t)row_stride(sdrs[j]);
-                                  p.hdr_stride = (uint32_t)row_stride(hdrs[j]);
-                                  // 16-byte row pieces of both images (a dword format: 4 pixels, F16: 2) and the pair's bytes as one store
-                                  return c.width % 8u == 0 && al(p.sdr, 16) && p.sdr_stride % 4u == 0 && al(p.hdr, 16) &&
-                                         p.hdr_stride % (f16 ? 2u : 4u) == 0 && al(p.map, rgb != 0 ? 8 : 2);
-                                });
+    // (the pair's bytes are one store)
+    const Chunk ch = packed_chunk(i, n, sdrs, hdrs, f16, b, [&](int j) { return dests[j].data; }, rgb != 0 ? 8 : 2);
     for (int k = 0; k < ch.m; ++k) fill_generate_dest(&sdrs[i + k], &dests[i + k], 4, rgb != 0);
     HIP_TRY(launch_generate_packed(c, mc, b, ch.m, hdr_tf, f16, ch.cls, rgb != 0, s));
     i += ch.m;
   }
   return UHDR_HIP_NO_ERROR;
+}
+
+// ---- content-adaptive maps from packed RGBA -------------------------------
+int uhdr_hip_generate_packed_adaptive_workspace_bytes(int n, const uhdr_hip_image_t* sdrs, int rgb, size_t* bytes) {
+  if (bytes == nullptr || n < 0 || (n > 0 && sdrs == nullptr)) return UHDR_HIP_ERROR_BAD_PTR;
+  *bytes = adaptive_layout(n, sdrs, packed_gain_bytes(rgb != 0)).total;
+  return UHDR_HIP_NO_ERROR;
+}
+
+int uhdr_hip_generate_gainmap_packed_adaptive_batch(int n, const uhdr_hip_image_t* sdrs, const uhdr_hip_image_t* hdrs, int hdr_tf,
+                                                    uhdr_hip_image_t* dests, int rgb, int boost_scope, float* content_minmax,
+                                                    float* boost_range, void* workspace, size_t workspace_bytes, void* stream) {
+  bool f16 = false;
+  int rc = check_generate_packed(n, sdrs, hdrs, hdr_tf, nullptr, dests, rgb, &f16);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if (!valid_boost_scope(boost_scope)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (n > 0 && (workspace == nullptr || !al(workspace, 16) || boost_range == nullptr)) return UHDR_HIP_ERROR_BAD_PTR;
+  if (workspace_bytes < adaptive_layout(n, sdrs, packed_gain_bytes(rgb != 0)).total) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  if (n == 0) return UHDR_HIP_NO_ERROR;   // (nothing to enqueue: no device is asked for)
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  return packed_adaptive_enqueue(n, sdrs, hdrs, hdr_tf, dests, rgb != 0, boost_scope, content_minmax, boost_range, workspace, nullptr, nullptr,
+                                 true, static_cast<hipStream_t>(stream));
 }
 
 // Gain maps at any scale factor: the checks of the call whose arithmetic is selected, in its order, with the
@@ -4444,6 +4570,34 @@ int uhdr_hip_generate_gainmap_adaptive(const uhdr_hip_image_t* yuv, const uhdr_h
   HIP_TRY(hipStreamSynchronize(s));
   fill_adaptive_metadata(range[0], range[1], metadata);
   fill_generate_dest(yuv, dest);
+  return UHDR_HIP_NO_ERROR;
+}
+
+// one packed pair in device memory through the packed adaptive batch, the workspace the library's, the measured metadata back on the
+// host: the call waits for the stream
+int uhdr_hip_generate_gainmap_packed_adaptive(const uhdr_hip_image_t* sdr, const uhdr_hip_image_t* hdr, int hdr_tf, uhdr_hip_metadata_t* metadata,
+                                              uhdr_hip_image_t* dest, int rgb, void* stream) {
+  if (sdr == nullptr || hdr == nullptr || metadata == nullptr || dest == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  bool f16 = false;
+  int rc = check_generate_packed(1, sdr, hdr, hdr_tf, nullptr, dest, rgb, &f16);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  DeviceState* st = nullptr;
+  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
+  StageLease lease(st);
+  StageSet* ss = lease.get();
+  if (ss == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t ws_bytes = adaptive_layout(1, sdr, packed_gain_bytes(rgb != 0)).total;
+  if ((rc = stage_reserve(ss, 5, ws_bytes + 256)) != 0) return rc;
+  uint8_t* ws = static_cast<uint8_t*>(ss->stage[5]);
+  float* dev_range = reinterpret_cast<float*>(ws + ws_bytes);
+  if ((rc = packed_adaptive_enqueue(1, sdr, hdr, hdr_tf, dest, rgb != 0, UHDR_HIP_BOOST_PER_IMAGE, nullptr, dev_range, ws, nullptr, nullptr, true,
+                                    s)) != UHDR_HIP_NO_ERROR)
+    return rc;
+  float range[2];
+  HIP_TRY(hipMemcpyAsync(range, dev_range, sizeof(range), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  fill_adaptive_metadata(range[0], range[1], metadata);
   return UHDR_HIP_NO_ERROR;
 }
 

@@ -381,6 +381,12 @@ hipError_t launch_generate_md(const GenConsts& c, const GenMdConsts& m, const Ge
 // of 8 and the map is aligned as launch_generate_md's
 hipError_t launch_generate_packed(const GenConsts& c, const GenMdConsts& m, const PackedBatch& b, int n, int hdr_tf, bool f16, bool aligned,
                                   bool rgb, hipStream_t s);
+// content-adaptive maps from packed RGBA, pass 1 of n <= kMaxChunk pairs of one size: launch_generate_packed's
+// launch; PackedImage::map points at the image's GAINS (float, 16-byte aligned; 1 per map pixel, rgb: 3), c.stat_keys at its keys
+hipError_t launch_generate_packed_gains(const GenConsts& c, const PackedBatch& b, int n, int hdr_tf, bool f16, bool aligned, bool rgb,
+                                        hipStream_t s);
+// pass 2 of such RGB maps: launch_encode_gains on three gains per map pixel, EncGainImage::map an RGBA8888 map (4-byte aligned)
+hipError_t launch_encode_gains_rgb(const AdaptConsts* consts, const EncGainBatch& b, int n, uint32_t pixels, hipStream_t s);
 // gain maps at any scale factor for n <= kMaxChunk pairs of one size; c.map_w / c.map_h are width / s and
 // height / s.  mode 0: the single-channel map of the reference's metadata behind the f32 pre-filter (m is not read); 1: launch_generate_md's
 // one-plane map; 2: its RGBA map -- both on the exact path.  aligned: gen_aligned's conditions, an even height and a map whose strip

@@ -7,6 +7,7 @@
 //   k_apply_lut_s4, k_apply_lut   the loops with the reference's LUT accessors (opt-in LUT mode)
 //   k_apply_px_md, k_generate_md   gain maps with gamma, offsets and an HDR capacity range (no reference counterpart)
 //   k_generate_packed        gain maps from packed RGBA pairs: RGBA8888 with RGBA1010102 or RGBA F16 (no reference counterpart)
+//   k_generate_packed_gains, k_encode_gains_rgb   the same pairs against the boost range their content has
 //   k_tonemap_*              UltraHdr::toneMap                    (:517-558)
 //   k_tonemap_packed[_peak]  the tone-mapped SDR image of a packed HDR image: RGBA1010102 / RGBA F16 -> RGBA8888 (no reference counterpart)
 //   k_convert_yuv<ALIGNED>   JpegR::convertYuv + transformYuv420  (lib/src/jpegr.cpp:1199-1203,
@@ -1406,6 +1407,115 @@ hipError_t launch_generate_packed(const GenConsts& c, const GenMdConsts& m, cons
   }
 }
 
+// Content-adaptive maps from packed RGBA, pass 1: k_generate_packed's front end -- its grid, its loads, its
+// sampling, the SDR block summed before the HDR block is loaded, gen_pair<kGenBackLinear> -- and k_generate_gains' tail: the
+// unclamped f32 gains (raw_gain) into the image's part of the workspace (PackedImage::map) and their extremes into the image's two
+// key words.  One plane: the gain of the two luminances as gen_pair forms them, 4 bytes per map pixel.  RGB: the gain per channel of
+// sdr.c * 203 and hdr.c * white, 12 bytes per map pixel (R, G, B), one pair of extremes over the three.  The aligned form stores a
+// thread's pair in 8-byte pieces, one (RGB: three): map_w is even and the image's gains are 16-byte aligned.
+template <int TF, bool F16, bool ALIGNED, int TILES, bool RGB>
+__global__ void __launch_bounds__(kGenBlock, 1) k_generate_packed_gains(const GenConsts c, const PackedBatch b) {
+  static_assert(F16 ? TF == 0 : TF != 0, "F16 is linear light, RGBA1010102 carries HLG or PQ");
+  constexpr int NCH = RGB ? 3 : 1;
+  const uint32_t img_i = blockIdx.x, blk = blockIdx.y;
+  const PackedImage& im = b.img[img_i];
+  float* gains = reinterpret_cast<float*>(im.map);
+  const uint32_t pairs_per_row = (c.map_w + 1u) >> 1;
+  const uint32_t total = pairs_per_row * c.map_h;
+  float emin = __builtin_inff(), emax = -__builtin_inff();
+#pragma unroll 1
+  for (uint32_t t = 0; t < (uint32_t)TILES; ++t) {
+    const uint32_t idx = (blk * (uint32_t)TILES + t) * (uint32_t)kGenBlock + threadIdx.x;
+    if (idx >= total) break;
+    const uint32_t my = idx / pairs_per_row;
+    const uint32_t pr = idx - my * pairs_per_row;
+    const uint32_t mx = pr * 2u;
+    const bool two = ALIGNED || (mx + 1u < c.map_w);
+    GenMid mid;
+    f2 e[3];
+    {
+      uint32_t px[4][8];
+      load_packed32<ALIGNED>(im.sdr, im.sdr_stride, my, pr, two, px);
+      sample_packed32<false>(px, e);
+      mid.r = e[0]; mid.g = e[1]; mid.b = e[2];
+    }
+    if (F16) {
+      uint2 px[4][8];
+      load_packed64<ALIGNED>(static_cast<const uint2*>(im.hdr), im.hdr_stride, my, pr, two, px);
+      sample_packed64(px, e);
+    } else {
+      uint32_t px[4][8];
+      load_packed32<ALIGNED>(static_cast<const uint32_t*>(im.hdr), im.hdr_stride, my, pr, two, px);
+      sample_packed32<true>(px, e);
+    }
+    mid.hr = e[0]; mid.hg = e[1]; mid.hb = e[2];
+    uint32_t hy[2][4][2], huv[2][2][2], y8[2][4], u8[2][2], v8[2][2];   // (gen_pair's planar inputs: not read from kGenBack on)
+    uint8_t o[2];
+    float gn[2];
+    gen_pair<TF, false, false, false, kGenBackLinear>(c, hy, huv, y8, u8, v8, o, gn, nullptr, nullptr, &mid);   // (a missing second pixel: zeros, gain 1, dropped)
+    f2 g[3];   // (one plane: g[0] alone)
+    if (RGB) {
+      const f2 sdr[3] = {mid.r * splat(203.0f), mid.g * splat(203.0f), mid.b * splat(203.0f)};
+      const f2 hdr[3] = {mid.hr * splat(c.hdr_white_nits), mid.hg * splat(c.hdr_white_nits), mid.hb * splat(c.hdr_white_nits)};
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) g[ch] = (f2){raw_gain(sdr[ch].x, hdr[ch].x), raw_gain(sdr[ch].y, hdr[ch].y)};
+    } else {
+      // the two luminances, as gen_pair forms them behind the linear colours
+      const f2 sdr_nits = (splat(c.lum_r) * mid.r + splat(c.lum_g) * mid.g + splat(c.lum_b) * mid.b) * splat(203.0f);
+      const f2 hdr_nits = (splat(c.lum_r) * mid.hr + splat(c.lum_g) * mid.hg + splat(c.lum_b) * mid.hb) * splat(c.hdr_white_nits);
+      g[0] = (f2){raw_gain(sdr_nits.x, hdr_nits.x), raw_gain(sdr_nits.y, hdr_nits.y)};
+    }
+#pragma unroll
+    for (int ch = 0; ch < NCH; ++ch) {
+      emin = fminf(emin, g[ch].x); emax = fmaxf(emax, g[ch].x);
+      if (two) { emin = fminf(emin, g[ch].y); emax = fmaxf(emax, g[ch].y); }
+    }
+    float* gp = gains + ((size_t)my * c.map_w + mx) * (size_t)NCH;
+    if (ALIGNED && RGB) {   // R0 G0 | B0 R1 | G1 B1
+      float2* gp2 = reinterpret_cast<float2*>(gp);
+      gp2[0] = make_float2(g[0].x, g[1].x);
+      gp2[1] = make_float2(g[2].x, g[0].y);
+      gp2[2] = make_float2(g[1].y, g[2].y);
+    } else if (ALIGNED) {
+      *reinterpret_cast<float2*>(gp) = make_float2(g[0].x, g[0].y);
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch) {
+        gp[ch] = g[ch].x;
+        if (two) gp[NCH + ch] = g[ch].y;
+      }
+    }
+  }
+  wave_minmax(emin, emax);   // (every lane arrives here)
+  publish_minmax(emin, emax, c.stat_keys + (size_t)c.stat_stride * img_i);
+}
+template <int TF, bool F16, bool RGB>
+static hipError_t launch_generate_packed_gains_tf(const GenConsts& c, const PackedBatch& b, int n, bool aligned, hipStream_t s) {
+  const uint32_t total = ((c.map_w + 1u) >> 1) * c.map_h;
+  if (total == 0 || n == 0) return hipSuccess;
+  const bool small = generate_is_small(c, n);   // spans per block as launch_generate_t chooses them
+  const unsigned per = (unsigned)kGenBlock * (small ? 1u : (unsigned)kGenTiles);
+  const dim3 g((unsigned)n, (total + per - 1u) / per, 1), blk(kGenBlock, 1, 1);
+  if (small) {
+    if (aligned) hipLaunchKernelGGL((k_generate_packed_gains<TF, F16, true, 1, RGB>), g, blk, 0, s, c, b);
+    else hipLaunchKernelGGL((k_generate_packed_gains<TF, F16, false, 1, RGB>), g, blk, 0, s, c, b);
+  } else {
+    if (aligned) hipLaunchKernelGGL((k_generate_packed_gains<TF, F16, true, kGenTiles, RGB>), g, blk, 0, s, c, b);
+    else hipLaunchKernelGGL((k_generate_packed_gains<TF, F16, false, kGenTiles, RGB>), g, blk, 0, s, c, b);
+  }
+  return hipGetLastError();
+}
+hipError_t launch_generate_packed_gains(const GenConsts& c, const PackedBatch& b, int n, int hdr_tf, bool f16, bool aligned, bool rgb,
+                                        hipStream_t s) {
+  if (f16 != (hdr_tf == 0) || c.stat_keys == nullptr) return hipErrorInvalidValue;
+  switch (hdr_tf) {
+    case 0: return rgb ? launch_generate_packed_gains_tf<0, true, true>(c, b, n, aligned, s) : launch_generate_packed_gains_tf<0, true, false>(c, b, n, aligned, s);
+    case 1: return rgb ? launch_generate_packed_gains_tf<1, false, true>(c, b, n, aligned, s) : launch_generate_packed_gains_tf<1, false, false>(c, b, n, aligned, s);
+    case 2: return rgb ? launch_generate_packed_gains_tf<2, false, true>(c, b, n, aligned, s) : launch_generate_packed_gains_tf<2, false, false>(c, b, n, aligned, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 // =================================================================================================
 // Gain maps at any scale factor (uhdr_hip_generate_gainmap_scaled_batch)
 // =================================================================================================
@@ -1768,6 +1878,45 @@ __global__ void __launch_bounds__(256) k_encode_gains(const AdaptConsts* consts,
 hipError_t launch_encode_gains(const AdaptConsts* consts, const EncGainBatch& b, int n, uint32_t pixels, hipStream_t s) {
   if (n <= 0 || pixels == 0u) return hipSuccess;
   hipLaunchKernelGGL(k_encode_gains, dim3((pixels + 1023u) / 1024u, (unsigned)n), dim3(256), 0, s, consts, b, pixels);
+  return hipGetLastError();
+}
+// Pass 2 of RGB maps: the same rule on the three stored gains of a map pixel (k_generate_packed_gains:
+// 12 bytes per pixel), the pixel R | G << 8 | B << 16 | 0xFF << 24.  A thread takes four consecutive map pixels: three 16-byte
+// loads, one 16-byte store where the map allows it.
+__global__ void __launch_bounds__(256) k_encode_gains_rgb(const AdaptConsts* consts, const EncGainBatch b, uint32_t pixels) {
+  const EncGainImage& im = b.img[blockIdx.y];
+  const uint32_t p = (blockIdx.x * 256u + threadIdx.x) * 4u;
+  if (p >= pixels) return;
+  const AdaptConsts a = consts[blockIdx.y];
+  const uint32_t cnt = min(4u, pixels - p);
+  const float* gp = im.gains + (size_t)p * 3u;
+  float g[12];
+  if (cnt == 4u) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const float4 v = reinterpret_cast<const float4*>(gp)[q];
+      g[4 * q] = v.x; g[4 * q + 1] = v.y; g[4 * q + 2] = v.z; g[4 * q + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < 12u; ++k) g[k] = k < 3u * cnt ? gp[k] : 1.0f;
+  }
+  uint32_t o[4] = {0xFF000000u, 0xFF000000u, 0xFF000000u, 0xFF000000u};
+#pragma unroll
+  for (int k = 0; k < 12; ++k)
+    o[k / 3] |= (uint32_t)encode_gain_guarded(g[k], a.min_boost, a.max_boost, a.log2_min, a.log2_max, a.enc_scale, a.enc_byte_min,
+                                              a.enc_byte_max) << (8 * (k % 3));
+  uint32_t* mp = reinterpret_cast<uint32_t*>(im.map) + p;
+  if (cnt == 4u && (reinterpret_cast<uintptr_t>(mp) & 15u) == 0u) {
+    *reinterpret_cast<uint4*>(mp) = make_uint4(o[0], o[1], o[2], o[3]);
+  } else {
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k) if (k < cnt) mp[k] = o[k];
+  }
+}
+hipError_t launch_encode_gains_rgb(const AdaptConsts* consts, const EncGainBatch& b, int n, uint32_t pixels, hipStream_t s) {
+  if (n <= 0 || pixels == 0u) return hipSuccess;
+  hipLaunchKernelGGL(k_encode_gains_rgb, dim3((pixels + 1023u) / 1024u, (unsigned)n), dim3(256), 0, s, consts, b, pixels);
   return hipGetLastError();
 }
 

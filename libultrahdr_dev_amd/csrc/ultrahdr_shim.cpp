@@ -422,6 +422,9 @@ status_t JpegRHip::encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_u
   return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
     const void* ex = exif_ptr(exif);
     const size_t exn = exif_len(exif);
+    if (mContentBoost >= 0)   // setContentBoost: the adaptive packed call; one file, so the call's status is the file's
+      return uhdr_hip_jpegr_encode_packed_adaptive_batch(1, &h, &sd, (int)hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, nullptr, nullptr,
+                                                         mMultiChannelGainMap ? 1 : 0, mContentBoost, UHDR_HIP_MEM_HOST, nullptr);
     return uhdr_hip_jpegr_encode_packed_batch(1, &h, &sd, (int)hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, mMultiChannelGainMap ? 1 : 0,
                                               UHDR_HIP_MEM_HOST, nullptr);
   });
@@ -435,6 +438,9 @@ status_t JpegRHip::encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, ultrah
   return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
     const void* ex = exif_ptr(exif);
     const size_t exn = exif_len(exif);
+    if (mContentBoost >= 0)   // setContentBoost, with setToneMap's peak
+      return uhdr_hip_jpegr_encode_packed_adaptive_batch(1, &h, nullptr, (int)hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, nullptr,
+                                                         &mHdrPeakNits, mMultiChannelGainMap ? 1 : 0, mContentBoost, UHDR_HIP_MEM_HOST, nullptr);
     return uhdr_hip_jpegr_encode_packed_api0_batch(1, &h, (int)hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, nullptr,
                                                    UHDR_HIP_TONEMAP_REINHARD_MAXRGB, &mHdrPeakNits, mMultiChannelGainMap ? 1 : 0, UHDR_HIP_MEM_HOST,
                                                    nullptr);
@@ -465,6 +471,31 @@ status_t generateGainMapPacked(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompr
   uhdr_hip_metadata_t md;
   std::memset(&md, 0, sizeof(md));
   const int rc = uhdr_hip_generate_gainmap_packed_batch(1, &sd, &h, (int)hdr_tf, nullptr, &md, &d, multi_channel ? 1 : 0, stream);
+  if (rc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(rc);
+  if (metadata != nullptr) {
+    metadata->version = md.version;
+    metadata->maxContentBoost = md.maxContentBoost;
+    metadata->minContentBoost = md.minContentBoost;
+    metadata->gamma = md.gamma;
+    metadata->offsetSdr = md.offsetSdr;
+    metadata->offsetHdr = md.offsetHdr;
+    metadata->hdrCapacityMin = md.hdrCapacityMin;
+    metadata->hdrCapacityMax = md.hdrCapacityMax;
+  }
+  from_c(d, dest);
+  dest->pixelFormat = multi_channel ? ULTRAHDR_PIX_FMT_RGBA8888 : ULTRAHDR_PIX_FMT_MONOCHROME;
+  return ULTRAHDR_NO_ERROR;
+}
+
+status_t generateGainMapPackedAdaptive(uhdr_uncompressed_ptr sdr_image_ptr, uhdr_uncompressed_ptr hdr_image_ptr, ultrahdr_transfer_function hdr_tf,
+                                       ultrahdr_metadata_ptr metadata, uhdr_uncompressed_ptr dest, bool multi_channel, void* stream) {
+  if (sdr_image_ptr == nullptr || hdr_image_ptr == nullptr || dest == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
+  if (uhdr_hip_init(0) != UHDR_HIP_NO_ERROR) return ULTRAHDR_UNKNOWN_ERROR;
+  const uhdr_hip_image_t sd = to_c_packed(*sdr_image_ptr), h = to_c_packed(*hdr_image_ptr);
+  uhdr_hip_image_t d = to_c(*dest);
+  uhdr_hip_metadata_t md;
+  std::memset(&md, 0, sizeof(md));
+  const int rc = uhdr_hip_generate_gainmap_packed_adaptive(&sd, &h, (int)hdr_tf, &md, &d, multi_channel ? 1 : 0, stream);   // (waits for the stream)
   if (rc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(rc);
   if (metadata != nullptr) {
     metadata->version = md.version;
