@@ -1220,6 +1220,36 @@ int uhdr_hip_apply_exact_probe(int phase, int n, const uhdr_hip_image_t* yuv420_
                                const uhdr_hip_metadata_t* metadata, int output_format, float max_display_boost,
                                uhdr_hip_image_t* dests, void* stream, uint32_t* route, uint32_t* headers);
 
+/* ---- Optimised Huffman tables for the JPEG encoder --------------------------------------------------------
+ * libjpeg's optimize_coding: a file's four Huffman tables (two for a single plane) are built from the histogram of its own symbols
+ * instead of being the Annex K defaults.  No pixel changes; the file is smaller and equals, byte for byte, what libjpeg-turbo
+ * writes with optimize_coding for the same coefficients.  Histogram, tables (jpeg_gen_optimal_table), DHT and SOS segments and the
+ * entropy-coded stream are all made on the device: the call synchronises no more often than without the flag.
+ *
+ * The _ex calls take every argument and convention of the call they extend, plus `flags` in front of mem_space.  flags == 0 IS that
+ * call, bytes and statuses included.  A bit other than those below is the call's ERROR_UNSUPPORTED_FEATURE, checked before the
+ * device is touched.  With OPTIMIZE_HUFFMAN a file of more than 15 873 015 blocks (63 symbols a block could reach libjpeg's
+ * "no frequency" of 10^9; about a gigapixel) is that file's ERROR_UNSUPPORTED_FEATURE.  In the JPEG/R call both the primary image
+ * and the gain-map JPEG get their own tables; the container follows from their sizes.  A header with optimised tables is never
+ * longer than the default one, so a capacity that holds the default file holds the optimised one. */
+#define UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN 1
+int uhdr_hip_jpeg_encode_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                  void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int flags, int mem_space,
+                                  void* stream);
+int uhdr_hip_jpeg_encode_rgb_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
+                                      size_t* out_size, int* status, int flags, int mem_space, void* stream);
+int uhdr_hip_jpeg_encode_rgba420_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
+                                          const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                          int flags, int mem_space, void* stream);
+int uhdr_hip_jpegr_encode_batch_ex(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                                   const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                   size_t* out_size, int* status, int flags, int mem_space, void* stream);
+/* Diagnostic: the encoder's table kernel on a caller's histogram (HOST arrays): freq[s] = count of symbol s; bits[l - 1] receives
+ * the number of codes of length l, vals[0, *nvals) the symbols by code length, then value (a DHT segment's body).  BAD_PTR for a
+ * NULL array, a histogram without a non-zero count, or a count >= 1 000 000 000; ERROR_UNSUPPORTED_FEATURE where a code would be
+ * longer than 32 bits before the limit to 16 (libjpeg gives up there; the encoder then keeps that table's default). */
+int uhdr_hip_jpeg_optimal_table(const uint32_t freq[256], uint8_t bits[16], uint8_t vals[256], int* nvals, void* stream);
+
 /* Bench / test support: the deterministic synthetic frame pair of SURVEY.md 8(d) (an LCG; tests/ and bench.py compare it with the
  * oracle's serial loop), written into device memory: p010 = width*height*3/2 uint16 (luma, then interleaved UV, values in the
  * legal 10-bit ranges << 6), yuv = width*height*3/2 bytes (Y, U, V).  width and height even; enqueued on `stream`. */

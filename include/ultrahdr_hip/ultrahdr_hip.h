@@ -315,6 +315,12 @@ class JpegRHip {
   // what current libultrahdr, cameras and editors write -- are decoded with the full gain-map formula, one- and three-component
   // maps alike (uhdr_hip_jpegr_decode_md_batch); files the reference reads give the bytes they gave.
   void setAnyGainMapMetadata(bool on) { mAnyGainMapMetadata = on; }
+  // false (default): the Annex K Huffman tables, as the reference writes them.  true: the API-0 and API-1 overloads of encodeJPEGR
+  // write the primary image and the gain-map JPEG with Huffman tables of their own (uhdr_hip_jpegr_encode_batch_ex with
+  // UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN): the same pixels in smaller files.  Combined with setGainMapScaleFactor, setMultiChannelGainMap,
+  // setToneMap or setContentBoost those two overloads answer ERROR_ULTRAHDR_UNSUPPORTED_FEATURE instead of silently writing default
+  // tables.  Every other encodeJPEGR overload and encodeJPEGRPacked keep the default tables, whatever is set here.
+  void setOptimizeHuffman(bool on) { mOptimizeHuffman = on; }
 
  private:
   int mApplyMode = 1;
@@ -324,6 +330,7 @@ class JpegRHip {
   bool mDecodeAnySampling = false;
   bool mMultiChannelGainMap = false;
   bool mAnyGainMapMetadata = false;
+  bool mOptimizeHuffman = false;
   int mGainMapScaleFactor = 4;
 };
 

@@ -212,7 +212,20 @@ SIGNATURES = {
     "uhdr_hip_jpegr_encode_packed_adaptive_batch": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                               C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), _MP,
                                                               C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    # optimised Huffman tables: the calls above with `flags` (ENCODE_OPTIMIZE_HUFFMAN) in front of mem_space
+    "uhdr_hip_jpeg_encode_batch_ex": (C.c_int, [C.c_int, _IP, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p]),
+    "uhdr_hip_jpeg_encode_rgb_batch_ex": (C.c_int, [C.c_int, _IP, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                    C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p]),
+    "uhdr_hip_jpeg_encode_rgba420_batch_ex": (C.c_int, [C.c_int, _IP, C.POINTER(C.c_int), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                        C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int),
+                                                        C.c_int, C.c_int, C.c_void_p]),
+    "uhdr_hip_jpegr_encode_batch_ex": (C.c_int, [C.c_int, _IP, _IP, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                 C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.c_int,
+                                                 C.c_int, C.c_void_p]),
+    "uhdr_hip_jpeg_optimal_table": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(C.c_int), C.c_void_p]),
 }
+ENCODE_OPTIMIZE_HUFFMAN = 1
 
 _lib = None
 

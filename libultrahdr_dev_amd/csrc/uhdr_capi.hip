@@ -1626,7 +1626,17 @@ struct EncJpeg {
   size_t dev_cap = 0;
   bool rgb = false;                      // img is RGBA8888 (luma_stride in pixels), compressed as 4:4:4 (jpeg::kGeomRgb444)
   bool mcu_planes = false;               // img's planes are jpeg::launch_rgba_to_ycc420's (encode_job)
+  bool optimize = false;                 // UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN: the file's own Huffman tables, built on the device
 };
+
+// the flags of the _ex encode calls: a bit this library does not know is the call's error, seen before the device is touched
+bool encode_flags_known(int flags) { return (flags & ~UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) == 0; }
+// libjpeg's table search reads a count of 10^9 as "none": an image whose AC histogram could reach it gets no optimised tables
+bool optimizable(size_t w, size_t h, jpeg::Geometry geom) {
+  jpeg::Job j;
+  encode_job_tables(w, h, geom, 75, &j);
+  return j.nblk <= jpeg::kMaxOptimizeBlocks;
+}
 
 // JpegEncoderHelper::compressImage (jpegencoderhelper.cpp:39-52) of k images in the leased context st: the headers are written into
 // its page-locked host pool, one jpeg::encode_batch_async writes the streams behind them and their sizes, and one synchronisation
@@ -1649,8 +1659,13 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     jobs[i] = encode_job(e.img, e.quality, e.pad_ls, e.pad_cs, e.rgb, e.mcu_planes);
     ws_off[i] = ws_total;
     ws_total += round_up(jpeg::workspace_bytes(jobs[i].nblk, &lay[i]), 256);
+    jobs[i].optimize = e.optimize ? 1 : 0;
+    // The header split: with optimised tables the host writes SOI ... SOF alone, and the device appends its DHT and SOS segments.
+    // Such a header is never longer than the default one -- baseline 8-bit data has at most 12 DC and 162 AC symbols, the sizes of
+    // the Annex K tables --, so whatever is sized for the default header (a file's first-guess staging, a caller's capacity that
+    // holds the default file) holds this one.
     jpeg::build_header((int)e.img.width, (int)e.img.height, enc_geom(e.img, e.rgb), e.quality, e.icc ? e.icc->data() : nullptr,
-                       e.icc ? e.icc->size() : 0, header[i]);
+                       e.icc ? e.icc->size() : 0, header[i], e.optimize);
     if (im[i].cap == 0) im[i].cap = im[i].img.width * im[i].img.height * (jobs[i].rgb ? 3 : 1) + 65536;
     off[i] = hp_total;
     hp_total += round_up(e.to_dev ? header[i].size() : im[i].cap, 256);   // a device destination: the header's way there only
@@ -1668,7 +1683,9 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     const size_t hn = header[i].size();
     memcpy(hp + off[i], header[i].data(), hn);
     sizes[i] = 0;
-    if (e.to_dev) {   // as uhdr_hip_jpeg_encode into device memory: the header only where it fits, no stream byte otherwise
+    if (e.to_dev && e.optimize) {   // whether the header fits is the device's to say: it copies the prefix from here if it does
+      outs[i] = jpeg::BatchOut{e.dev_out, e.dev_cap, hn, &sizes[i], hp + off[i]};
+    } else if (e.to_dev) {   // as uhdr_hip_jpeg_encode into device memory: the header only where it fits, no stream byte otherwise
       const bool fits = e.dev_cap >= hn;
       if (fits) HIP_TRY(hipMemcpyAsync(e.dev_out, hp + off[i], hn, hipMemcpyHostToDevice, s));
       outs[i] = jpeg::BatchOut{e.dev_out, fits ? e.dev_cap : 0, hn, &sizes[i]};
@@ -1694,6 +1711,7 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     EncJpeg one{e.img, e.quality, e.icc, e.pad_ls, e.pad_cs, (size_t)total};
     one.rgb = e.rgb;
     one.mcu_planes = e.mcu_planes;
+    one.optimize = e.optimize;
     if (lease.get() == nullptr || compress_to_host(lease.get(), s, 1, &one, false) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
     e.big.assign(one.bytes, one.bytes + one.n);
     e.bytes = e.big.data();
@@ -1751,7 +1769,7 @@ size_t enc_round_bytes(const uhdr_hip_image_t& img, bool host_in, bool host_out)
 // error of the device or the runtime.
 int jpeg_encode_round(DeviceState* st, hipStream_t s, bool host_in, bool host_out, const uhdr_hip_image_t* images, const int* quality,
                       const void* const* icc, const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size,
-                      const int* idx, int m, int* st_) {
+                      const int* idx, int m, int* st_, bool optimize) {
   std::vector<EncJpeg> im((size_t)m);
   std::vector<std::vector<uint8_t>> iccs((size_t)m);
   size_t stage_total = 0;
@@ -1779,6 +1797,7 @@ int jpeg_encode_round(DeviceState* st, hipStream_t s, bool host_in, bool host_ou
     e.icc = iccs[k].empty() ? nullptr : &iccs[k];
     e.pad_ls = img.luma_stride;
     e.pad_cs = img.chroma_stride;
+    e.optimize = optimize;
     if (host_out) {
       e.keep_max = out_capacity[i];   // a file that will not fit is only measured
     } else {
@@ -1861,6 +1880,16 @@ int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void*
 // share one jpeg::encode_batch_async launch set and one synchronisation (compress_to_host)
 int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
                                void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream) {
+  return uhdr_hip_jpeg_encode_batch_ex(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, 0, mem_space, stream);
+}
+
+// flags == 0 is uhdr_hip_jpeg_encode_batch.  UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN: every file with Huffman tables of its own (DESIGN.md
+// section 7.1.1) -- the same pixels in fewer bytes; a file too large for libjpeg's table search is UNSUPPORTED_FEATURE
+int uhdr_hip_jpeg_encode_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                  void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int flags, int mem_space,
+                                  void* stream) {
+  if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  const bool optimize = (flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0;
   if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
       (icc != nullptr && icc_size == nullptr))
     return UHDR_HIP_ERROR_BAD_PTR;
@@ -1873,6 +1902,8 @@ int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int*
       st_[i] = UHDR_HIP_ERROR_BAD_PTR;
     else if (!encodable(im))
       st_[i] = UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
+    else if (optimize && !optimizable(im.width, im.height, enc_geom(im, false)))
+      st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     else
       live.push_back(i);
   }
@@ -1884,7 +1915,7 @@ int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int*
       live.size(), (size_t)jpeg::kMaxBatchJobs, stream,
       [&](size_t k) { return enc_round_bytes(enc_image(images[live[k]]), host_in, host_out); },
       [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
-        return jpeg_encode_round(st, s, host_in, host_out, images, quality, icc, icc_size, out, out_capacity, out_size, &live[r0], m, st_.data());
+        return jpeg_encode_round(st, s, host_in, host_out, images, quality, icc, icc_size, out, out_capacity, out_size, &live[r0], m, st_.data(), optimize);
       },
       &done);
   for (size_t k = done; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
@@ -1895,6 +1926,14 @@ int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int*
 // in_color_space = JCS_RGB with all sampling factors 1.  No ICC.
 int uhdr_hip_jpeg_encode_rgb_batch(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
                                    size_t* out_size, int* status, int mem_space, void* stream) {
+  return uhdr_hip_jpeg_encode_rgb_batch_ex(n, images, quality, out, out_capacity, out_size, status, 0, mem_space, stream);
+}
+
+// flags as in uhdr_hip_jpeg_encode_batch_ex
+int uhdr_hip_jpeg_encode_rgb_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
+                                      size_t* out_size, int* status, int flags, int mem_space, void* stream) {
+  if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  const bool optimize = (flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0;
   if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)))
     return UHDR_HIP_ERROR_BAD_PTR;
   for (int i = 0; i < n; ++i)
@@ -1912,6 +1951,8 @@ int uhdr_hip_jpeg_encode_rgb_batch(int n, const uhdr_hip_image_t* images, const 
     else if (im.width == 0 || im.height == 0 || im.width > 65500 || im.height > 65500 || (im.luma_stride != 0 && im.luma_stride < im.width) ||
              im.luma_stride > (size_t)INT32_MAX / 4)   // (rows are addressed with an int byte pitch)
       st_[i] = UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
+    else if (optimize && !optimizable(im.width, im.height, jpeg::kGeomRgb444))
+      st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     else
       live.push_back(i);
   }
@@ -1958,6 +1999,7 @@ int uhdr_hip_jpeg_encode_rgb_batch(int n, const uhdr_hip_image_t* images, const 
           e.icc = nullptr;
           e.pad_ls = e.pad_cs = 0;
           e.rgb = true;
+          e.optimize = optimize;
           if (host_out) {
             e.keep_max = out_capacity[i];   // a file that will not fit is only measured
           } else {
@@ -2033,6 +2075,15 @@ extern "C" {
 // downsampler hand its FDCT come from one k_rgba_to_ycc420 launch per round, everything behind them is compress_to_host
 int uhdr_hip_jpeg_encode_rgba420_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
                                        void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream) {
+  return uhdr_hip_jpeg_encode_rgba420_batch_ex(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, 0, mem_space, stream);
+}
+
+// flags as in uhdr_hip_jpeg_encode_batch_ex
+int uhdr_hip_jpeg_encode_rgba420_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                          void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int flags, int mem_space,
+                                          void* stream) {
+  if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  const bool optimize = (flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0;
   if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
       (icc != nullptr && icc_size == nullptr))
     return UHDR_HIP_ERROR_BAD_PTR;
@@ -2044,6 +2095,8 @@ int uhdr_hip_jpeg_encode_rgba420_batch(int n, const uhdr_hip_image_t* images, co
   const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE && mem_space != UHDR_HIP_MEM_HOST_TO_DEVICE;
   for (int i = 0; i < n; ++i) {
     st_[i] = rgba_file_check(images[i], host_in, out[i], out_capacity[i]);
+    if (st_[i] == UHDR_HIP_NO_ERROR && optimize && !optimizable(images[i].width, images[i].height, jpeg::kGeom420))
+      st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     if (st_[i] == UHDR_HIP_NO_ERROR) live.push_back(i);
   }
   if (live.empty()) return finish_statuses(st_, status);
@@ -2094,6 +2147,7 @@ int uhdr_hip_jpeg_encode_rgba420_batch(int n, const uhdr_hip_image_t* images, co
           EncJpeg& e = im[(size_t)k];
           e.quality = quality[i];
           e.icc = iccs[(size_t)k].empty() ? nullptr : &iccs[(size_t)k];
+          e.optimize = optimize;
           if (host_out) {
             e.keep_max = out_capacity[i];   // a file that will not fit is only measured
           } else {
@@ -2801,7 +2855,7 @@ EncJpeg gainmap_rgb_jpeg(uhdr_hip_image_t map) {
 // tonemap_op (API-0): the operator that derives the SDR planes; its headroom array is a pool slot of the context.
 int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_tf, int quality, EncFile* f, int m, uhdr_hip_metadata_t* md,
                  std::vector<EncJpeg>* jpg, int boost_scope = -1, float* range = nullptr, int carry = 0,
-                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, bool rgb_map = false, int map_scale = 4) {
+                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, bool rgb_map = false, int map_scale = 4, bool optimize = false) {
   const size_t msf = (size_t)map_scale;     // the map's factor: uhdr_hip_jpegr_encode_scaled_batch's, 4 in every other call
   const size_t map_bpp = rgb_map ? 4 : 1;   // rgb_map: uhdr_hip_generate_gainmap_rgb_batch's RGBA map, compressed as 4:4:4
   auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -2928,6 +2982,7 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
     jpg->push_back(EncJpeg{e.enc, quality, &e.icc, e.pad_ls, e.pad_cs});
     jpg->push_back(rgb_map ? gainmap_rgb_jpeg(g) : gainmap_jpeg(g, g.luma_stride));
   }
+  for (EncJpeg& e : *jpg) e.optimize = optimize;   // the primary image and the gain map alike
   return compress_to_host(st, s, 2 * m, jpg->data(), true, dev_range, dev_range ? 8 * (size_t)m : 0, range);
 }
 
@@ -2936,7 +2991,8 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
 int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
                  const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
                  int* status, int mem_space, void* stream, int boost_scope = -1, uhdr_hip_metadata_t* metadata = nullptr,
-                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, const float* hdr_peak_nits = nullptr, bool rgb_map = false, int map_scale = 4) {
+                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, const float* hdr_peak_nits = nullptr, bool rgb_map = false, int map_scale = 4,
+                 bool optimize = false) {
   const bool api0 = yuv420_images == nullptr;
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
   std::vector<EncFile> files;
@@ -2951,6 +3007,8 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
     if (rc == UHDR_HIP_NO_ERROR && map_scale != 4 &&
         (p010_images[i].width % (size_t)map_scale != 0 || p010_images[i].height % (size_t)map_scale != 0))
       rc = UHDR_HIP_ERROR_UNSUPPORTED_WIDTH_HEIGHT;
+    if (rc == UHDR_HIP_NO_ERROR && optimize && !optimizable(p010_images[i].width, p010_images[i].height, jpeg::kGeom420))
+      rc = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     if (rc != UHDR_HIP_NO_ERROR) { st_[i] = rc; continue; }
     EncFile e;
     e.idx = i;
@@ -3000,7 +3058,8 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
         EncFile* f = &files[r0];
         uhdr_hip_metadata_t md;
         std::vector<EncJpeg> jpg;
-        if ((rc = encode_round(st, s, api0, host, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry, tonemap_op, rgb_map, map_scale)) != UHDR_HIP_NO_ERROR)
+        if ((rc = encode_round(st, s, api0, host, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry, tonemap_op, rgb_map, map_scale,
+                               optimize)) != UHDR_HIP_NO_ERROR)
           return rc;
         std::vector<uhdr_hip_metadata_t> mds;   // adaptive: every file's own
         if (boost_scope < 0 && metadata)
@@ -3113,11 +3172,54 @@ extern "C" {
 int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
                                 const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
                                 int* status, int mem_space, void* stream) {
+  return uhdr_hip_jpegr_encode_batch_ex(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, 0,
+                                        mem_space, stream);
+}
+
+// flags == 0 is uhdr_hip_jpegr_encode_batch.  UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN: the primary image and the gain-map JPEG of every file
+// with Huffman tables of their own; XMP, MPF offsets and ICC follow from the new sizes through the same container writer
+int uhdr_hip_jpegr_encode_batch_ex(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                                   const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                   size_t* out_size, int* status, int flags, int mem_space, void* stream) {
+  if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
       (exif != nullptr && exif_size == nullptr))
     return UHDR_HIP_ERROR_BAD_PTR;
   if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
-  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream);
+  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, -1,
+                      nullptr, UHDR_HIP_TONEMAP_SHIFT, nullptr, false, 4, (flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0);
+}
+
+// jpeg_gen_optimal_table of a caller's histogram by the encoder's table kernel: what an image's symbol
+// counts would have to be is the caller's to say, so table shapes no small image produces can be reached
+int uhdr_hip_jpeg_optimal_table(const uint32_t freq[256], uint8_t bits[16], uint8_t vals[256], int* nvals, void* stream) {
+  if (freq == nullptr || bits == nullptr || vals == nullptr || nvals == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  bool any = false;
+  for (int i = 0; i < 256; ++i) {
+    if (freq[i] >= jpeg::kHuffFreqLimit) return UHDR_HIP_ERROR_BAD_PTR;
+    any = any || freq[i] != 0;
+  }
+  if (!any) return UHDR_HIP_ERROR_BAD_PTR;
+  DeviceState* st = nullptr;
+  int rc = current_state(&st);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  CodecLease lease(st);
+  if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  if ((rc = pool_reserve(st, kEncWs, 2048)) != 0) return rc;
+  uint8_t* d = static_cast<uint8_t*>(st->pool[kEncWs]);   // [0, 1024) counts, [1024, 1040) BITS, [1040, 1296) HUFFVAL, [1296, 1300) their number
+  HIP_TRY(hipMemcpyAsync(d, freq, 1024, hipMemcpyHostToDevice, s));
+  HIP_TRY(jpeg::optimal_table_async(reinterpret_cast<const uint32_t*>(d), d + 1024, d + 1040, reinterpret_cast<int*>(d + 1296), s));
+  uint8_t h[276];
+  HIP_TRY(hipMemcpyAsync(h, d + 1024, sizeof(h), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  int n = 0;
+  memcpy(&n, h + 272, 4);
+  if (n < 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;   // a code longer than 32 bits: libjpeg gives up there
+  memcpy(bits, h, 16);
+  memcpy(vals, h + 16, (size_t)n);
+  *nvals = n;
+  return UHDR_HIP_NO_ERROR;
 }
 
 // the same with the per-channel map of uhdr_hip_generate_gainmap_rgb_batch, compressed at quality 85 as a 4:4:4 file; primary image,

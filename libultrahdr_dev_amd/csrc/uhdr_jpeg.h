@@ -32,9 +32,14 @@ struct Job {
   uint32_t* ff_count;      // per 64-byte chunk of the stream
   uint32_t* ff_blk;
   uint32_t max_chunks;
+  // optimised Huffman tables (optimize != 0): the job runs through the k_jpeg_opt_* launches of its round
+  int optimize;
+  uint32_t* hist;          // 4 x 256 symbol counts ([0] DC lum, [1] AC lum, [2] DC chroma, [3] AC chroma), zeroed on the stream
+  uint32_t* huff;          // 4 x 256 codes built from them, (size << 16) | code as in c_huff
+  uint32_t* hdr_len;       // the header's length, known once k_jpeg_opt_tables_batch has written the DHT and SOS segments
 };
 struct Layout {
-  size_t coef, bits, bits_blk, stream, stream_bytes, ff_count, ff_blk, totals, scan_tmp, scan_tmp_bytes;
+  size_t coef, bits, bits_blk, stream, stream_bytes, ff_count, ff_blk, totals, scan_tmp, scan_tmp_bytes, hist, huff;
   uint32_t max_chunks;
 };
 
@@ -43,7 +48,8 @@ void quant_table(int quality, bool chroma, uint16_t out_natural[64]);
 void zigzag_table(const uint16_t natural[64], uint16_t zz[64]);
 // geom: what the frame header declares -- the 4:2:0 and single-plane files of the reference's encoder, or three 1x1 components
 enum Geometry : int { kGeom420 = 0, kGeomGray = 1, kGeomRgb444 = 2 };
-void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& out);
+// prefix_only: SOI ... SOF alone -- the DHT and SOS segments of a file with optimised tables are written on the device
+void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& out, bool prefix_only = false);
 size_t workspace_bytes(uint32_t nblk, Layout* l);
 // enqueues the whole encoder; the JPEG (without the header, which the caller places at out[0, header_len)) lands at
 // out + header_len, its total size (header included) in the uint64 at ws + l.totals + 8
@@ -56,7 +62,18 @@ struct BatchOut {                       // where job k's JPEG goes: header at ou
   uint8_t* out;                         // device-accessible (device or page-locked host memory)
   uint64_t out_cap, header_len;
   uint64_t* out_size;                   // the file's size, header included (device-accessible)
+  // a job with optimised tables: header_len is the length of the prefix SOI ... SOF, the rest of the header is the device's.  Where
+  // the caller cannot tell whether the header fits (a device destination), the prefix waits here (device-accessible) and the device
+  // copies it with the rest; nullptr: it is at out already
+  const uint8_t* prefix = nullptr;
 };
+// libjpeg's "no frequency" in jpeg_gen_optimal_table: a table's counts must stay below it, so a job with optimised tables has
+// 63 * nblk < kHuffFreqLimit
+constexpr uint32_t kHuffFreqLimit = 1000000000u;
+constexpr uint32_t kMaxOptimizeBlocks = (kHuffFreqLimit - 1u) / 63u;
+// jpeg_gen_optimal_table of one histogram on the device (the table step of the encoder, on its own): freq: 256 counts, each below
+// kHuffFreqLimit; bits[16], vals[256], *nvals (-1: a code longer than 32 bits, which libjpeg refuses) -- all device memory
+hipError_t optimal_table_async(const uint32_t* freq, uint8_t* bits, uint8_t* vals, int* nvals, hipStream_t s);
 size_t batch_desc_bytes(int n);
 // jobs: tables, geometry and planes as for encode_async; job k works in ws[k] (workspace_bytes(jobs[k].nblk, &l[k]) bytes).  The
 // descriptors are assembled in host_desc (page-locked, batch_desc_bytes(n); not to be touched until the stream has passed this

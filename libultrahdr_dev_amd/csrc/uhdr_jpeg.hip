@@ -15,6 +15,7 @@
 //   k_jpeg_stuff_copy   one thread per 64 bytes: copy to the output with 0x00 stuffed after every 0xFF, EOI at the end
 //   k_rgba_to_ycc420    (in front of the chain, uhdr_hip_jpeg_encode_rgba420_batch only) RGBA8888 -> the Y, Cb, Cr planes libjpeg's
 //                       colour conversion and h2v2 downsampler hand its FDCT, padded to whole MCUs as libjpeg pads them
+//   k_jpeg_opt_*        (Job::optimize) the same chain with Huffman tables built from the image's own symbol counts, see below
 //
 // Byte-exact against libjpeg for every size, stride regime and quality tested (tests/test_gpu_jpeg.py against
 // oracle/jpeg_oracle.c, which tests/test_jpeg_oracle.py pins to the libjpeg builds of the image).
@@ -67,6 +68,9 @@ static const uint8_t kValsAcChr[162] = {
 
 // Huffman codes of the four default tables: [0] DC lum, [1] AC lum, [2] DC chroma, [3] AC chroma.  Packed (size << 16) | code.
 __constant__ uint32_t c_huff[4][256];
+// the default tables' DHT bodies (BITS, then HUFFVAL), same order: what k_jpeg_opt_tables_batch falls back to for a histogram whose
+// optimal code would be longer than 32 bits (libjpeg gives up on those)
+__constant__ uint8_t c_std_dht[4][16 + 162];
 
 static void derive_codes(const uint8_t bits[16], const uint8_t* vals, uint32_t out[256]) {  // T.81 Annex C
   memset(out, 0, sizeof(uint32_t) * 256);
@@ -84,6 +88,15 @@ hipError_t upload_tables() {
   derive_codes(kBitsAcLum, kValsAcLum, t[1]);
   derive_codes(kBitsDcChr, kValsDc, t[2]);
   derive_codes(kBitsAcChr, kValsAcChr, t[3]);
+  uint8_t d[4][16 + 162] = {};
+  const uint8_t* bits[4] = {kBitsDcLum, kBitsAcLum, kBitsDcChr, kBitsAcChr};
+  const uint8_t* vals[4] = {kValsDc, kValsAcLum, kValsDc, kValsAcChr};
+  for (int k = 0; k < 4; ++k) {
+    memcpy(d[k], bits[k], 16);
+    memcpy(d[k] + 16, vals[k], (k & 1) ? 162 : 12);
+  }
+  const hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_std_dht), d, sizeof(d));
+  if (e != hipSuccess) return e;
   return hipMemcpyToSymbol(HIP_SYMBOL(c_huff), t, sizeof(t));
 }
 
@@ -121,7 +134,7 @@ void put_dht(std::vector<uint8_t>& b, int cls_idx, const uint8_t bits[16], const
 }
 }  // namespace
 
-void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& b) {
+void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& b, bool prefix_only) {
   const bool gray = geom == kGeomGray;
   uint16_t ql[64], qc[64];
   quant_table(quality, false, ql);
@@ -145,6 +158,7 @@ void build_header(int w, int h, Geometry geom, int quality, const void* icc, siz
     b.push_back((uint8_t)((c == 0 && geom == kGeom420) ? 0x22 : 0x11));
     b.push_back((uint8_t)(c == 0 ? 0 : 1));
   }
+  if (prefix_only) return;   // DHT and SOS: write_opt_header's, in this order
   put_dht(b, 0x00, kBitsDcLum, kValsDc);
   put_dht(b, 0x10, kBitsAcLum, kValsAcLum);
   if (!gray) {
@@ -302,12 +316,28 @@ __device__ __forceinline__ int nbits_of(int a) { return a == 0 ? 0 : 32 - __buil
 
 // walks one block's symbols (jchuff.c encode_one_block); SINK::put(code, size) receives MSB-first bit strings.
 // c: the block's 64 quantised coefficients in zigzag order (registers: every index is a compile-time constant)
-template <typename SINK>
-__device__ __forceinline__ void walk_coefs(const int16_t (&c)[64], int pred, int tbl_dc, int tbl_ac, SINK& s) {
+// HUFF: where a symbol's code comes from, asked once per symbol emitted -- the default tables in constant memory, a job's own tables
+// in LDS (LdsHuff), or nowhere: HistHuff counts the symbol instead
+struct ConstHuff {
+  __device__ __forceinline__ uint32_t operator()(int tbl, int sym) const { return c_huff[tbl][sym]; }
+};
+struct LdsHuff {
+  static __device__ __forceinline__ uint32_t* table() {   // 4 x 256, the workgroup's one copy (load_job_huff fills it)
+    __shared__ uint32_t t[4 * 256];
+    return t;
+  }
+  __device__ __forceinline__ uint32_t operator()(int tbl, int sym) const { return table()[tbl * 256 + sym]; }
+};
+struct HistHuff {
+  uint32_t* hist;      // 4 x 256 counters in LDS
+  __device__ __forceinline__ uint32_t operator()(int tbl, int sym) const { atomicAdd(&hist[tbl * 256 + sym], 1u); return 0u; }
+};
+template <typename SINK, typename HUFF = ConstHuff>
+__device__ __forceinline__ void walk_coefs(const int16_t (&c)[64], int pred, int tbl_dc, int tbl_ac, SINK& s, const HUFF huff = HUFF()) {
   int temp = (int)c[0] - pred, temp2 = temp;
   if (temp < 0) { temp = -temp; temp2--; }
   int nb = nbits_of(temp);
-  uint32_t h = c_huff[tbl_dc][nb];
+  uint32_t h = huff(tbl_dc, nb);
   s.put(h & 0xffffu, (int)(h >> 16));
   if (nb) s.put((uint32_t)temp2 & ((1u << nb) - 1u), nb);
   int r = 0;
@@ -315,18 +345,18 @@ __device__ __forceinline__ void walk_coefs(const int16_t (&c)[64], int pred, int
   for (int k = 1; k < 64; ++k) {
     temp = c[k];
     if (temp == 0) { r++; continue; }
-    while (r > 15) { h = c_huff[tbl_ac][0xF0]; s.put(h & 0xffffu, (int)(h >> 16)); r -= 16; }
+    while (r > 15) { h = huff(tbl_ac, 0xF0); s.put(h & 0xffffu, (int)(h >> 16)); r -= 16; }
     temp2 = temp;
     if (temp < 0) { temp = -temp; temp2--; }
     nb = nbits_of(temp);
-    h = c_huff[tbl_ac][(r << 4) + nb];
+    h = huff(tbl_ac, (r << 4) + nb);
     s.put(((h & 0xffffu) << nb) | ((uint32_t)temp2 & ((1u << nb) - 1u)), (int)(h >> 16) + nb);   // <= 16 + 10 bits
     r = 0;
   }
-  if (r > 0) { h = c_huff[tbl_ac][0]; s.put(h & 0xffffu, (int)(h >> 16)); }
+  if (r > 0) { h = huff(tbl_ac, 0); s.put(h & 0xffffu, (int)(h >> 16)); }
 }
-template <typename SINK>
-__device__ __forceinline__ void walk_block(const int16_t* __restrict__ zz, int pred, int tbl_dc, int tbl_ac, SINK& s) {
+template <typename SINK, typename HUFF = ConstHuff>
+__device__ __forceinline__ void walk_block(const int16_t* __restrict__ zz, int pred, int tbl_dc, int tbl_ac, SINK& s, const HUFF huff = HUFF()) {
   int16_t c[64];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {   // 128 B per block
@@ -335,7 +365,7 @@ __device__ __forceinline__ void walk_block(const int16_t* __restrict__ zz, int p
 #pragma unroll
     for (int m = 0; m < 4; ++m) { c[8 * k + 2 * m] = (int16_t)(w[m] & 0xffffu); c[8 * k + 2 * m + 1] = (int16_t)(w[m] >> 16); }
   }
-  walk_coefs(c, pred, tbl_dc, tbl_ac, s);
+  walk_coefs(c, pred, tbl_dc, tbl_ac, s, huff);
 }
 
 struct CountSink {
@@ -357,7 +387,8 @@ __device__ __forceinline__ int comp_of(const Job& j, uint32_t i) {
 // the quantised DC of the component's previous block, which another thread computes: the islow DC is the plain sum of the 64
 // level-shifted samples (pass 1 scales the row sums by 4, pass 2 descales by 4: exact), so it is had from that block's 64 bytes.
 // RGB: the job is a 4:4:4 one (Job::rgb), known at compile time so that the planar kernels carry none of its code
-template <bool RGB>
+// COUNT false (a job with optimised tables): the coefficients alone -- the block's bits wait for its tables (k_jpeg_opt_count_batch)
+template <bool RGB, bool COUNT = true>
 __device__ __forceinline__ uint32_t fdct_quant_count_block(const Job& j, const uint32_t i);
 // workgroup wg of the image's grid (blockIdx.x of the single-image launch; the batched launch passes its workgroup inside the job)
 template <bool RGB>
@@ -374,7 +405,7 @@ __device__ __forceinline__ void fdct_quant_count_wg(const Job& j, const uint32_t
 __global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count(const Job j) { fdct_quant_count_wg<false>(j, blockIdx.x); }
 
 // the work of one thread of k_jpeg_fdct_quant_count: block i's coefficients to memory, its number of bits returned
-template <bool RGB>
+template <bool RGB, bool COUNT>
 __device__ __forceinline__ uint32_t fdct_quant_count_block(const Job& j, const uint32_t i) {
   const BlockRef b = RGB ? locate_rgb(j, i) : locate(j, i);
   const Plane& p = j.plane[RGB ? 0 : b.comp];
@@ -401,7 +432,17 @@ __device__ __forceinline__ uint32_t fdct_quant_count_block(const Job& j, const u
                                  41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                  30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 #pragma unroll
-    for (int k = 0; k < 64; ++k) c[k] = (int16_t)quantise(d[nat[k]], q[k], qm[k]);
+    for (int k = 0; k < 64; ++k) {
+      if (COUNT) {
+        c[k] = (int16_t)quantise(d[nat[k]], q[k], qm[k]);
+      } else {
+        // both tables' entries through the scalar unit and a select per lane: q and qm differ from lane to lane, so q[k] and qm[k]
+        // are 128 vector loads in flight at once -- 182 VGPRs in this form of the kernel, 118 with the entries in SGPRs
+        const int ql = __builtin_amdgcn_readfirstlane((int)j.q_lum[k]), qc = __builtin_amdgcn_readfirstlane((int)j.q_chr[k]);
+        const uint32_t ml = __builtin_amdgcn_readfirstlane(j.m_lum[k]), mc = __builtin_amdgcn_readfirstlane(j.m_chr[k]);
+        c[k] = (int16_t)quantise(d[nat[k]], b.comp == 0 ? ql : qc, b.comp == 0 ? ml : mc);
+      }
+    }
   }
   uint4* o = reinterpret_cast<uint4*>(out);
 #pragma unroll
@@ -411,6 +452,7 @@ __device__ __forceinline__ uint32_t fdct_quant_count_block(const Job& j, const u
     for (int m = 0; m < 4; ++m) w[m] = (uint32_t)(uint16_t)c[8 * k + 2 * m] | ((uint32_t)(uint16_t)c[8 * k + 2 * m + 1] << 16);
     o[k] = make_uint4(w[0], w[1], w[2], w[3]);
   }
+  if (!COUNT) return 0u;
   int pred = 0;
   const uint32_t pi = dc_predecessor(j, i);
   if (pi != 0xFFFFFFFFu) {
@@ -457,6 +499,7 @@ struct EmitSink {
   }
 };
 
+template <typename HUFF = ConstHuff>
 __device__ __forceinline__ void emit_wg(const Job& j, const uint32_t wg) {
   __shared__ uint64_t s_part[2];
   __shared__ uint64_t s_base;
@@ -478,7 +521,7 @@ __device__ __forceinline__ void emit_wg(const Job& j, const uint32_t wg) {
   s.wi = (uint32_t)(off >> 5);
   s.first = true;
   const int chroma = comp_of(j, i);
-  walk_block(j.coef + (size_t)i * 64u, pred_of(j, i), 2 * chroma, 2 * chroma + 1, s);
+  walk_block(j.coef + (size_t)i * 64u, pred_of(j, i), 2 * chroma, 2 * chroma + 1, s, HUFF());
   if (i == j.nblk - 1u) {      // jchuff.c flush_bits: fill the last byte with ones
     const uint64_t end = off + my_bits;
     const int pad = (int)((8u - (uint32_t)(end & 7u)) & 7u);
@@ -670,6 +713,309 @@ __global__ void __launch_bounds__(256) k_jpeg_stuff_copy_multi(const Job* __rest
   }
 }
 
+// ---- optimised Huffman tables (Job::optimize) ------------------------------------------------------------------------------------
+// libjpeg's optimize_coding for the jobs of a round that ask for it, without a word to the host: the code lengths follow from a
+// histogram of the whole image, so these jobs run through launches of their own (the default jobs keep theirs, untouched):
+//   k_jpeg_opt_zero_batch        the job's 4 x 256 counters to zero
+//   k_jpeg_opt_fdct_batch        k_jpeg_fdct_quant_count_multi's coefficients, without the count
+//   k_jpeg_opt_hist_batch        the symbols walk_coefs codes are counted -- per workgroup in LDS, then one global atomic per non-zero bin
+//   k_jpeg_opt_tables_batch      one workgroup per job, one wave per table: jpeg_gen_optimal_table, the canonical codes into the job's
+//                                workspace, the DHT and SOS segments behind the host's prefix, the header's length into a device word
+//   k_jpeg_opt_count_batch       bits per block and per workgroup from the job's codes (the coefficients are read again)
+//   k_jpeg_clear_multi, k_jpeg_opt_emit_batch, k_jpeg_stuff_count_multi, k_jpeg_opt_stuff_copy_batch
+//                                the default steps, with the job's codes in LDS and the stream behind the device's header length
+struct TableLds {
+  uint32_t bits[33];                        // codes per length (index = length); the pseudo-symbol is in it until build_table takes it out
+  uint32_t first_code[17], first_rank[17];  // per final length: its first code and that code's position in HUFFVAL
+  uint32_t nvals, overflow;
+  uint8_t size[256];                        // each symbol's code length before the limit (0: not in the table)
+  uint8_t vals[256];                        // HUFFVAL
+};
+// the wave's two smallest keys (distinct but for the "none" of all ones), each lane giving its own two (k1 <= k2): one butterfly of
+// six shuffle rounds for both instead of two in a row
+__device__ __forceinline__ void wave_min2(uint64_t& k1, uint64_t& k2) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const uint64_t u1 = __shfl_xor(k1, off, 64), u2 = __shfl_xor(k2, off, 64);
+    const uint64_t lo = k1 < u1 ? k1 : u1, hi = k1 < u1 ? u1 : k1, nx = k2 < u2 ? k2 : u2;
+    k1 = lo;
+    k2 = hi < nx ? hi : nx;
+  }
+}
+// jpeg_gen_optimal_table (jchuff.c) of the 256 counts at freq, by one wave; every wave of the workgroup calls it, since the barriers
+// are the workgroup's -- a wave with active == false builds nothing.  Lane l holds the entries l, l + 64, ... (256, the pseudo-symbol
+// of count 1 that keeps the all-ones code free, is lane 0's fifth) in registers, every index a compile-time constant.
+// libjpeg merges the two least frequent trees (of equal counts the one with the LARGEST index) and walks their symbols along a chain
+// to lengthen each by a bit; here a symbol carries the index of its tree's head, and every lane lengthens its members of the two.
+// Leaves L.bits[1..16], L.vals[0, L.nvals) and, at huff (or nullptr), the 256 canonical codes; returns true, and no table, where
+// a code would be longer than 32 bits (libjpeg: JERR_HUFF_CLEN_OVERFLOW).
+__device__ __forceinline__ bool build_table(const uint32_t* __restrict__ freq, const bool active, TableLds& L, uint32_t* __restrict__ huff) {
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t f[5], size[5], head[5];
+#pragma unroll
+  for (uint32_t s = 0; s < 5u; ++s) {
+    const uint32_t idx = lane + 64u * s;
+    f[s] = (active && idx < 256u) ? freq[idx] : 0u;
+    size[s] = 0u;
+    head[s] = idx;
+  }
+  if (active && lane == 0u) f[4] = 1u;
+  if (lane < 33u) L.bits[lane] = 0u;
+  if (lane == 0u) { L.overflow = 0u; L.nvals = 0u; }
+  const uint64_t none = ~0ull;
+  while (active) {   // (uniform per wave)
+    uint64_t k1 = none, k2 = none;
+    for (uint32_t s = 0; s < 5u; ++s) {   // smallest count, then largest index: the key's low half falls as the index rises
+      const uint64_t key = (f[s] != 0u && f[s] <= kHuffFreqLimit) ? ((uint64_t)f[s] << 16) | (uint64_t)(0xFFFFu - (lane + 64u * s)) : none;
+      if (key < k1) { k2 = k1; k1 = key; }
+      else if (key < k2) k2 = key;
+    }
+    wave_min2(k1, k2);
+    if (k2 == none) break;   // one tree left
+    const uint32_t c1 = 0xFFFFu - (uint32_t)(k1 & 0xFFFFu), c2 = 0xFFFFu - (uint32_t)(k2 & 0xFFFFu);
+    const uint32_t sum = (uint32_t)(k1 >> 16) + (uint32_t)(k2 >> 16);   // both <= 10^9: no overflow
+#pragma unroll
+    for (uint32_t s = 0; s < 5u; ++s) {
+      const uint32_t idx = lane + 64u * s;
+      if (idx == c1) f[s] = sum;
+      if (idx == c2) f[s] = 0u;
+      if (head[s] == c1 || head[s] == c2) ++size[s];
+      if (head[s] == c2) head[s] = c1;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t s = 0; s < 5u; ++s) {
+    const uint32_t idx = lane + 64u * s;
+    const uint32_t z = size[s] > 32u ? 32u : size[s];
+    if (size[s] > 32u) L.overflow = 1u;
+    if (z != 0u) atomicAdd(&L.bits[z], 1u);
+    if (idx < 256u) L.size[idx] = (uint8_t)z;
+  }
+  __syncthreads();
+  const bool overflow = L.overflow != 0u;
+  // HUFFVAL lists the symbols by length (before the limit), then by value: a symbol's place is the number of symbols in front of it
+  uint32_t rank[4] = {0u, 0u, 0u, 0u};
+  if (active && !overflow) {
+    const uint32_t* sw = reinterpret_cast<const uint32_t*>(L.size);
+    for (uint32_t w = 0; w < 64u; ++w) {
+      const uint32_t v = sw[w];
+#pragma unroll
+      for (uint32_t b = 0; b < 4u; ++b) {
+        const uint32_t zz = (v >> (8u * b)) & 0xffu, jj = 4u * w + b;
+#pragma unroll
+        for (uint32_t s = 0; s < 4u; ++s)
+          rank[s] += (zz != 0u && (zz < size[s] || (zz == size[s] && jj < lane + 64u * s))) ? 1u : 0u;
+      }
+    }
+    if (lane == 0u) {   // the length limit (T.81 K.2, figure K.3), the pseudo-symbol out of the longest length, the canonical codes' starts
+      for (int i = 32; i > 16; --i) {
+        while (L.bits[i] >= 2u) {   // (the deepest level of a code tree holds pairs)
+          int jn = i - 2;
+          while (jn > 0 && L.bits[jn] == 0u) --jn;
+          L.bits[i] -= 2u; L.bits[i - 1] += 1u; L.bits[jn + 1] += 2u; L.bits[jn] -= 1u;
+        }
+      }
+      int i = 16;
+      while (i > 0 && L.bits[i] == 0u) --i;
+      if (i > 0) L.bits[i] -= 1u;
+      uint32_t code = 0u, p = 0u;
+      for (int l = 1; l <= 16; ++l) {
+        L.first_code[l] = code; L.first_rank[l] = p;
+        code = (code + L.bits[l]) << 1;
+        p += L.bits[l];
+      }
+      L.nvals = p;
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (uint32_t s = 0; s < 4u; ++s) {
+    const uint32_t idx = lane + 64u * s;
+    uint32_t hv = 0u;
+    if (active && !overflow && size[s] != 0u) {
+      const uint32_t r = rank[s];
+      L.vals[r] = (uint8_t)idx;
+      for (uint32_t l = 1; l <= 16u; ++l)
+        if (r >= L.first_rank[l] && r - L.first_rank[l] < L.bits[l]) hv = (l << 16) | (L.first_code[l] + r - L.first_rank[l]);
+    }
+    if (active && huff != nullptr) huff[idx] = hv;
+  }
+  __syncthreads();
+  return overflow;
+}
+
+__global__ void __launch_bounds__(256) k_jpeg_opt_zero_batch(const Job* __restrict__ jobs) {
+  const Job& j = uniform_ref(jobs, blockIdx.x);
+#pragma unroll
+  for (uint32_t k = 0; k < 4u; ++k) j.hist[threadIdx.x + 256u * k] = 0u;
+}
+
+// k_jpeg_fdct_quant_count_multi without the count.  With the symbol walk in it, counting into LDS, the 4:4:4 form needs 168 VGPRs
+// (three waves per SIMD), so the histogram is a launch of its own over the coefficients, as the bit count is.
+__global__ void __launch_bounds__(128) k_jpeg_opt_fdct_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  if (j.rgb) return;   // (uniform per workgroup) k_jpeg_opt_fdct_batch_rgb's
+  const uint32_t i = (blockIdx.x - first) * 128u + threadIdx.x;
+  if (i < j.nblk) fdct_quant_count_block<false, false>(j, i);
+}
+__global__ void __launch_bounds__(128) k_jpeg_opt_fdct_batch_rgb(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  if (!j.rgb) return;
+  const uint32_t i = (blockIdx.x - first) * 128u + threadIdx.x;
+  if (i < j.nblk) fdct_quant_count_block<true, false>(j, i);
+}
+// The symbols walk_coefs codes, counted.  The counters of a workgroup's 128 blocks live in LDS: a flat image sends every lane to the
+// same two bins (EOB, DC category 0), which the LDS adds up at its own rate, and device memory sees one atomic per bin that is not
+// zero -- two per workgroup there.
+struct NullSink {
+  __device__ __forceinline__ void put(uint32_t, int) {}
+};
+__global__ void __launch_bounds__(128) k_jpeg_opt_hist_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint32_t s_hist[4 * 256];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  const uint32_t nbins = j.gray ? 512u : 1024u;
+  for (uint32_t b = threadIdx.x; b < nbins; b += 128u) s_hist[b] = 0u;
+  __syncthreads();
+  const uint32_t i = (blockIdx.x - first) * 128u + threadIdx.x;
+  if (i < j.nblk) {
+    const int chroma = comp_of(j, i);
+    NullSink ns;
+    walk_block(j.coef + (size_t)i * 64u, pred_of(j, i), 2 * chroma, 2 * chroma + 1, ns, HistHuff{s_hist});
+  }
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < nbins; b += 128u) {
+    const uint32_t v = s_hist[b];
+    if (v != 0u) atomicAdd(&j.hist[b], v);
+  }
+}
+
+// One workgroup per job, wave t builds table t (a one-plane job has two).  Then the rest of the header, in build_header's order: one
+// DHT segment per table, each under its own marker, and SOS.  A header that does not fit into out_cap is not written; its length is.
+__global__ void __launch_bounds__(256) k_jpeg_opt_tables_batch(const Job* __restrict__ jobs, const BatchOut* __restrict__ outs) {
+  __shared__ TableLds s_tbl[4];
+  const Job& j = uniform_ref(jobs, blockIdx.x);
+  const BatchOut& o = uniform_ref(outs, blockIdx.x);
+  const uint32_t t = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t ntab = j.gray ? 2u : 4u;
+  const bool active = t < ntab;
+  TableLds& L = s_tbl[t];
+  if (build_table(j.hist + 256u * t, active, L, j.huff + 256u * t) && active) {   // the default table in its place: it codes every symbol
+    const uint32_t nv = (t & 1u) ? 162u : 12u;
+    if (lane < 16u) L.bits[lane + 1u] = c_std_dht[t][lane];
+    for (uint32_t k = lane; k < nv; k += 64u) L.vals[k] = c_std_dht[t][16u + k];
+    for (uint32_t k = lane; k < 256u; k += 64u) j.huff[256u * t + k] = c_huff[t][k];
+    if (lane == 0u) L.nvals = nv;
+  }
+  __syncthreads();
+  uint64_t at = o.header_len, total = o.header_len + (j.gray ? 10u : 14u);
+  for (uint32_t k = 0; k < ntab; ++k) {
+    const uint32_t seg = 21u + s_tbl[k].nvals;   // marker, length, class and index, BITS, HUFFVAL
+    if (k < t) at += seg;
+    total += seg;
+  }
+  if (threadIdx.x == 0u) *j.hdr_len = (uint32_t)total;
+  if (total > o.out_cap) return;
+  if (o.prefix != nullptr)
+    for (uint32_t k = threadIdx.x; k < (uint32_t)o.header_len; k += 256u) o.out[k] = o.prefix[k];
+  if (active) {
+    const uint32_t nv = L.nvals;
+    uint8_t* d = o.out + at;
+    for (uint32_t k = lane; k < 21u + nv; k += 64u) {
+      uint32_t v;
+      if (k == 0u) v = 0xFFu;
+      else if (k == 1u) v = 0xC4u;
+      else if (k == 2u) v = (19u + nv) >> 8;
+      else if (k == 3u) v = (19u + nv) & 0xffu;
+      else if (k == 4u) v = ((t & 1u) << 4) | (t >> 1);
+      else if (k < 21u) v = L.bits[k - 4u];
+      else v = L.vals[k - 21u];
+      d[k] = (uint8_t)v;
+    }
+  }
+  const uint32_t nc = j.gray ? 1u : 3u, sos = 8u + 2u * nc;
+  if (threadIdx.x < sos) {   // jcmarker.c emit_sos
+    const uint32_t k = threadIdx.x;
+    uint32_t v;
+    if (k == 0u) v = 0xFFu;
+    else if (k == 1u) v = 0xDAu;
+    else if (k == 2u) v = 0u;
+    else if (k == 3u) v = 6u + 2u * nc;
+    else if (k == 4u) v = nc;
+    else if (k < 5u + 2u * nc) v = ((k - 5u) & 1u) ? (k == 6u ? 0x00u : 0x11u) : (k - 5u) / 2u + 1u;
+    else v = k == 6u + 2u * nc ? 63u : 0u;
+    o.out[total - sos + k] = (uint8_t)v;
+  }
+}
+// the table step on its own (uhdr_hip_jpeg_optimal_table)
+__global__ void __launch_bounds__(64) k_jpeg_opt_table_one(const uint32_t* __restrict__ freq, uint8_t* __restrict__ bits, uint8_t* __restrict__ vals,
+                                                          int* __restrict__ nvals) {
+  __shared__ TableLds L;
+  const bool overflow = build_table(freq, true, L, nullptr);
+  if (threadIdx.x == 0u) *nvals = overflow ? -1 : (int)L.nvals;
+  if (overflow) return;
+  if (threadIdx.x < 16u) bits[threadIdx.x] = (uint8_t)L.bits[threadIdx.x + 1u];
+  for (uint32_t k = threadIdx.x; k < L.nvals; k += 64u) vals[k] = L.vals[k];
+}
+
+// the job's four tables into LDS (a one-plane job: two)
+__device__ __forceinline__ void load_job_huff(const Job& j) {
+  uint32_t* s_huff = LdsHuff::table();
+  const uint32_t n = j.gray ? 512u : 1024u;
+  for (uint32_t k = threadIdx.x; k < n; k += 128u) s_huff[k] = j.huff[k];
+  __syncthreads();
+}
+__global__ void __launch_bounds__(128) k_jpeg_opt_count_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint32_t s_part[2];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  load_job_huff(j);
+  const uint32_t wg = blockIdx.x - first, i = wg * 128u + threadIdx.x;
+  uint32_t my_bits = 0;
+  if (i < j.nblk) {
+    const int chroma = comp_of(j, i);
+    CountSink cs;
+    walk_block(j.coef + (size_t)i * 64u, pred_of(j, i), 2 * chroma, 2 * chroma + 1, cs, LdsHuff());
+    j.bits[i] = my_bits = cs.bits;
+  }
+  const uint32_t total = block_sum<128>(my_bits, s_part);
+  if (threadIdx.x == 0u) j.bits_blk[wg] = total;
+}
+__global__ void __launch_bounds__(128) k_jpeg_opt_emit_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  load_job_huff(j);
+  emit_wg<LdsHuff>(j, blockIdx.x - first);
+}
+// k_jpeg_stuff_copy_multi behind a header whose length only the device knows; a header that did not fit left the output untouched,
+// and so does the stream
+__global__ void __launch_bounds__(256) k_jpeg_opt_stuff_copy_batch(const Job* __restrict__ jobs, const BatchOut* __restrict__ outs,
+                                                                   const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<256>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  const BatchOut& o = uniform_ref(outs, k);
+  const uint64_t header_len = *j.hdr_len, cap = header_len <= o.out_cap ? o.out_cap : 0u;
+  const uint64_t nbytes = (*j.total_bits + 7u) >> 3;
+  for (uint32_t wg = blockIdx.x - first; (uint64_t)wg * 256u * kChunk < nbytes; wg += count) {
+    stuff_copy_wg(j, j.total_bits, o.out, cap, header_len, o.out_size, wg);
+    __syncthreads();   // (s_buf and s_len are the next piece's)
+  }
+}
+
+hipError_t optimal_table_async(const uint32_t* freq, uint8_t* bits, uint8_t* vals, int* nvals, hipStream_t s) {
+  hipLaunchKernelGGL(k_jpeg_opt_table_one, dim3(1), dim3(64), 0, s, freq, bits, vals, nvals);
+  return hipGetLastError();
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------
 size_t workspace_bytes(uint32_t nblk, Layout* l) {
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -683,7 +1029,9 @@ size_t workspace_bytes(uint32_t nblk, Layout* l) {
   l->max_chunks = (uint32_t)(l->stream_bytes / kChunk);
   l->ff_count = o; o += up((size_t)l->max_chunks * 4);
   l->ff_blk = o; o += up((size_t)(l->max_chunks / 256u + 2) * 4);
-  l->totals = o; o += 256;   // [0] total bits (uint64), [1] output size (uint64)
+  l->totals = o; o += 256;   // [0] total bits (uint64), [1] output size (uint64), [2] header length (uint32; optimised tables)
+  l->hist = o; o += 4 * 256 * 4;
+  l->huff = o; o += 4 * 256 * 4;
   l->scan_tmp_bytes = 0;
   l->scan_tmp = o;
   return o;
@@ -716,7 +1064,7 @@ size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 }  // namespace
 
 size_t batch_desc_bytes(int n) {
-  return up256((size_t)n * sizeof(Job)) + up256((size_t)n * sizeof(BatchOut)) + 2 * up256(((size_t)n + 1) * 4);
+  return up256((size_t)n * sizeof(Job)) + up256((size_t)n * sizeof(BatchOut)) + 4 * up256(((size_t)n + 1) * 4);
 }
 
 hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_t* const* ws, const BatchOut* outs, uint8_t* host_desc,
@@ -727,11 +1075,19 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
   BatchOut* o = reinterpret_cast<BatchOut*>(host_desc + up256((size_t)n * sizeof(Job)));
   uint32_t* blk_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(o) + up256((size_t)n * sizeof(BatchOut)));
   uint32_t* stuff_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(blk_start) + up256(((size_t)n + 1) * 4));
-  blk_start[0] = stuff_start[0] = 0;
-  bool any_planar = false, any_rgb = false;
-  for (int k = 0; k < n; ++k) {
-    (jobs_in[k].rgb ? any_rgb : any_planar) = true;
-    Job& j = jobs[k];
+  // The jobs with optimised tables stand behind the default ones in the descriptors, with grids of their own (opt_*_start count
+  // from their first): the default jobs' launches see neither them nor a flag
+  uint32_t* opt_blk_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(stuff_start) + up256(((size_t)n + 1) * 4));
+  uint32_t* opt_stuff_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(opt_blk_start) + up256(((size_t)n + 1) * 4));
+  blk_start[0] = stuff_start[0] = opt_blk_start[0] = opt_stuff_start[0] = 0;
+  int nd = 0;
+  for (int k = 0; k < n; ++k) nd += jobs_in[k].optimize ? 0 : 1;
+  bool any_planar = false, any_rgb = false, any_opt_planar = false, any_opt_rgb = false;
+  for (int k = 0, at_d = 0, at_o = nd; k < n; ++k) {
+    const bool opt = jobs_in[k].optimize != 0;
+    (opt ? (jobs_in[k].rgb ? any_opt_rgb : any_opt_planar) : (jobs_in[k].rgb ? any_rgb : any_planar)) = true;
+    const int at = opt ? at_o++ : at_d++;
+    Job& j = jobs[at];
     j = jobs_in[k];
     uint8_t* w = ws[k];
     j.coef = reinterpret_cast<int16_t*>(w + l[k].coef);
@@ -742,10 +1098,15 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
     j.ff_blk = reinterpret_cast<uint32_t*>(w + l[k].ff_blk);
     j.max_chunks = l[k].max_chunks;
     j.total_bits = reinterpret_cast<uint64_t*>(w + l[k].totals);
-    o[k] = outs[k];
+    j.hist = reinterpret_cast<uint32_t*>(w + l[k].hist);
+    j.huff = reinterpret_cast<uint32_t*>(w + l[k].huff);
+    j.hdr_len = reinterpret_cast<uint32_t*>(w + l[k].totals + 16);
+    o[at] = outs[k];
     const uint32_t stuff_wgs = (j.max_chunks + 255u) / 256u;
-    blk_start[k + 1] = blk_start[k] + (j.nblk + 127u) / 128u;
-    stuff_start[k + 1] = stuff_start[k] + (stuff_wgs < kStuffWgPerJob ? stuff_wgs : kStuffWgPerJob);
+    uint32_t* bs = opt ? opt_blk_start + (at - nd) : blk_start + at;
+    uint32_t* ss = opt ? opt_stuff_start + (at - nd) : stuff_start + at;
+    bs[1] = bs[0] + (j.nblk + 127u) / 128u;
+    ss[1] = ss[0] + (stuff_wgs < kStuffWgPerJob ? stuff_wgs : kStuffWgPerJob);
   }
   hipError_t e;
   if ((e = hipMemcpyAsync(dev_desc, host_desc, batch_desc_bytes(n), hipMemcpyHostToDevice, s)) != hipSuccess) return e;
@@ -753,14 +1114,35 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
   const BatchOut* dout = reinterpret_cast<const BatchOut*>(dev_desc + (reinterpret_cast<uint8_t*>(o) - host_desc));
   const uint32_t* dblk = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(blk_start) - host_desc));
   const uint32_t* dstuff = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(stuff_start) - host_desc));
-  const uint32_t nj = (uint32_t)n;
-  const dim3 gb(blk_start[n]), bb(128), gc(stuff_start[n]), bc(256);
-  if (any_planar) hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi, gb, bb, 0, s, dj, dblk, nj);
-  if (any_rgb) hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi_rgb, gb, bb, 0, s, dj, dblk, nj);
-  hipLaunchKernelGGL(k_jpeg_clear_multi, gb, bb, 0, s, dj, dblk, nj);
-  hipLaunchKernelGGL(k_jpeg_emit_multi, gb, bb, 0, s, dj, dblk, nj);
-  hipLaunchKernelGGL(k_jpeg_stuff_count_multi, gc, bc, 0, s, dj, dstuff, nj);
-  hipLaunchKernelGGL(k_jpeg_stuff_copy_multi, gc, bc, 0, s, dj, dout, dstuff, nj);
+  const dim3 bb(128), bc(256);
+  if (nd > 0) {
+    const uint32_t nj = (uint32_t)nd;
+    const dim3 gb(blk_start[nd]), gc(stuff_start[nd]);
+    if (any_planar) hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi, gb, bb, 0, s, dj, dblk, nj);
+    if (any_rgb) hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi_rgb, gb, bb, 0, s, dj, dblk, nj);
+    hipLaunchKernelGGL(k_jpeg_clear_multi, gb, bb, 0, s, dj, dblk, nj);
+    hipLaunchKernelGGL(k_jpeg_emit_multi, gb, bb, 0, s, dj, dblk, nj);
+    hipLaunchKernelGGL(k_jpeg_stuff_count_multi, gc, bc, 0, s, dj, dstuff, nj);
+    hipLaunchKernelGGL(k_jpeg_stuff_copy_multi, gc, bc, 0, s, dj, dout, dstuff, nj);
+  }
+  if (n > nd) {
+    const uint32_t nj = (uint32_t)(n - nd);
+    const Job* oj = dj + nd;
+    const BatchOut* oout = dout + nd;
+    const uint32_t* oblk = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(opt_blk_start) - host_desc));
+    const uint32_t* ostuff = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(opt_stuff_start) - host_desc));
+    const dim3 gb(opt_blk_start[nj]), gc(opt_stuff_start[nj]);
+    hipLaunchKernelGGL(k_jpeg_opt_zero_batch, dim3(nj), bc, 0, s, oj);
+    if (any_opt_planar) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch, gb, bb, 0, s, oj, oblk, nj);
+    if (any_opt_rgb) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch_rgb, gb, bb, 0, s, oj, oblk, nj);
+    hipLaunchKernelGGL(k_jpeg_opt_hist_batch, gb, bb, 0, s, oj, oblk, nj);
+    hipLaunchKernelGGL(k_jpeg_opt_tables_batch, dim3(nj), bc, 0, s, oj, oout);
+    hipLaunchKernelGGL(k_jpeg_opt_count_batch, gb, bb, 0, s, oj, oblk, nj);
+    hipLaunchKernelGGL(k_jpeg_clear_multi, gb, bb, 0, s, oj, oblk, nj);
+    hipLaunchKernelGGL(k_jpeg_opt_emit_batch, gb, bb, 0, s, oj, oblk, nj);
+    hipLaunchKernelGGL(k_jpeg_stuff_count_multi, gc, bc, 0, s, oj, ostuff, nj);
+    hipLaunchKernelGGL(k_jpeg_opt_stuff_copy_batch, gc, bc, 0, s, oj, oout, ostuff, nj);
+  }
   return hipGetLastError();
 }
 
