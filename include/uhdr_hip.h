@@ -1250,6 +1250,41 @@ int uhdr_hip_jpegr_encode_batch_ex(int n, const uhdr_hip_image_t* p010_images, c
  * longer than 32 bits before the limit to 16 (libjpeg gives up there; the encoder then keeps that table's default). */
 int uhdr_hip_jpeg_optimal_table(const uint32_t freq[256], uint8_t bits[16], uint8_t vals[256], int* nvals, void* stream);
 
+/* ---- Restart intervals for the JPEG encoder ---------------------------------------------------------------
+ * libjpeg's restart_interval / restart_in_rows: a DRI segment between the last DHT and SOS, and after every `interval` MCUs except
+ * the last group the partial byte filled with ones, RSTn (n counting modulo 8) and the DC prediction of every component back at 0.
+ * The file equals, byte for byte, what libjpeg-turbo writes with the same setting; it decodes to the same pixels, in independent
+ * byte-aligned pieces.  Padding, markers and the cut prediction are the device's work: the call synchronises no more often.
+ *
+ * The _opts calls take every argument and convention of their _ex call with `opts` in place of `flags`; one opts holds for the
+ * whole call.  opts == NULL, or both restart fields 0, IS the _ex call with opts->flags, bytes and statuses included.
+ * restart_in_rows > 0 overrides restart_interval: the interval is min(restart_in_rows * MCUs per row, 65535) with the MCUs per row
+ * of the scan written -- ceil(width / 16) for 4:2:0, ceil(width / 8) for a single plane and for 4:4:4 -- so in the JPEG/R call the
+ * primary image and the gain map each get their own.  An interval of at least the image's MCUs writes DRI and no marker.
+ * A wrong struct_size, an unknown flag bit or restart_interval > 65535 is the call's ERROR_UNSUPPORTED_FEATURE, checked before the
+ * device is touched and before any pointer.  A file of more than 20 000 000 blocks with intervals is that file's
+ * ERROR_UNSUPPORTED_FEATURE.  The file grows by the 6 bytes of DRI and at most 3 bytes per interval. */
+typedef struct {
+  uint32_t struct_size;       /* sizeof(uhdr_hip_jpeg_encode_opts_t); anything else: ERROR_UNSUPPORTED_FEATURE */
+  uint32_t flags;             /* the _ex calls' bits (UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) */
+  uint32_t restart_interval;  /* libjpeg's restart_interval: MCUs per interval, 0 = none, at most 65535 */
+  uint32_t restart_in_rows;   /* libjpeg's restart_in_rows: MCU rows per interval, 0 = use restart_interval */
+} uhdr_hip_jpeg_encode_opts_t;
+int uhdr_hip_jpeg_encode_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                    void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                    const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream);
+int uhdr_hip_jpeg_encode_rgb_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
+                                        size_t* out_size, int* status, const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream);
+int uhdr_hip_jpeg_encode_rgba420_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
+                                            const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                            const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream);
+int uhdr_hip_jpegr_encode_batch_opts(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                                     const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                     size_t* out_size, int* status, const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream);
+/* Host only: the MCUs per interval the encoder derives from opts for a scan of `width` pixels whose MCUs are mcu_width (8 or 16)
+ * pixels wide; 0: no intervals.  *restart_mcus is left alone where opts would be refused (the call's ERROR_UNSUPPORTED_FEATURE). */
+int uhdr_hip_jpeg_restart_mcus(const uhdr_hip_jpeg_encode_opts_t* opts, size_t width, int mcu_width, uint32_t* restart_mcus);
+
 /* Bench / test support: the deterministic synthetic frame pair of SURVEY.md 8(d) (an LCG; tests/ and bench.py compare it with the
  * oracle's serial loop), written into device memory: p010 = width*height*3/2 uint16 (luma, then interleaved UV, values in the
  * legal 10-bit ranges << 6), yuv = width*height*3/2 bytes (Y, U, V).  width and height even; enqueued on `stream`. */

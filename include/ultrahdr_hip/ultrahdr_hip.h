@@ -321,6 +321,14 @@ class JpegRHip {
   // setToneMap or setContentBoost those two overloads answer ERROR_ULTRAHDR_UNSUPPORTED_FEATURE instead of silently writing default
   // tables.  Every other encodeJPEGR overload and encodeJPEGRPacked keep the default tables, whatever is set here.
   void setOptimizeHuffman(bool on) { mOptimizeHuffman = on; }
+  // libjpeg's restart_interval and restart_in_rows for the same two overloads (uhdr_hip_jpegr_encode_batch_opts): the primary image
+  // and the gain-map JPEG are written with a DRI segment and RSTn markers after every `mcus` MCUs, or after every `rows` MCU rows of
+  // each image's own width (rows override mcus; 0 and 0, the default: none).  The pixels do not change.  They combine with
+  // setOptimizeHuffman and refuse what it refuses: with setGainMapScaleFactor, setMultiChannelGainMap, setToneMap or setContentBoost
+  // those overloads answer ERROR_ULTRAHDR_UNSUPPORTED_FEATURE, as they do for an interval above 65535.  Every other overload writes
+  // no intervals, whatever is set here.
+  void setRestartInterval(unsigned mcus) { mRestartInterval = mcus; }
+  void setRestartInRows(unsigned rows) { mRestartInRows = rows; }
 
  private:
   int mApplyMode = 1;
@@ -331,6 +339,7 @@ class JpegRHip {
   bool mMultiChannelGainMap = false;
   bool mAnyGainMapMetadata = false;
   bool mOptimizeHuffman = false;
+  unsigned mRestartInterval = 0, mRestartInRows = 0;
   int mGainMapScaleFactor = 4;
 };
 

@@ -227,6 +227,26 @@ SIGNATURES = {
 }
 ENCODE_OPTIMIZE_HUFFMAN = 1
 
+
+class JpegEncodeOpts(C.Structure):
+    """uhdr_hip_jpeg_encode_opts_t"""
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("restart_interval", C.c_uint32), ("restart_in_rows", C.c_uint32)]
+
+
+def encode_opts(flags=0, restart_interval=0, restart_in_rows=0):
+    """the options of the *_opts encode calls: the _ex calls' flags, and libjpeg's restart_interval (MCUs) / restart_in_rows"""
+    return JpegEncodeOpts(C.sizeof(JpegEncodeOpts), flags, restart_interval, restart_in_rows)
+
+
+_OP = C.POINTER(JpegEncodeOpts)
+# restart intervals: the _ex calls with `opts` (encode_opts(), or None) in place of `flags`
+SIGNATURES.update({
+    name[:-3] + "_opts": (res, [_OP if k == len(args) - 3 else a for k, a in enumerate(args)])
+    for name, (res, args) in SIGNATURES.items()
+    if name in ("uhdr_hip_jpeg_encode_batch_ex", "uhdr_hip_jpeg_encode_rgb_batch_ex", "uhdr_hip_jpeg_encode_rgba420_batch_ex",
+                "uhdr_hip_jpegr_encode_batch_ex")})
+SIGNATURES["uhdr_hip_jpeg_restart_mcus"] = (C.c_int, [_OP, C.c_size_t, C.c_int, C.POINTER(C.c_uint32)])
+
 _lib = None
 
 

@@ -1627,15 +1627,63 @@ struct EncJpeg {
   bool rgb = false;                      // img is RGBA8888 (luma_stride in pixels), compressed as 4:4:4 (jpeg::kGeomRgb444)
   bool mcu_planes = false;               // img's planes are jpeg::launch_rgba_to_ycc420's (encode_job)
   bool optimize = false;                 // UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN: the file's own Huffman tables, built on the device
+  uint32_t restart_interval = 0, restart_in_rows = 0;   // uhdr_hip_jpeg_encode_opts_t's, as given: the file's width decides (enc_restart)
+};
+
+// what the _ex and _opts encode calls say beyond their arguments; a bool is the _ex calls' flag alone
+struct EncOpt {
+  bool optimize = false;
+  uint32_t restart_interval = 0, restart_in_rows = 0;
+  EncOpt() = default;
+  EncOpt(bool o) : optimize(o) {}
+  void to(EncJpeg* e) const { e->optimize = optimize; e->restart_interval = restart_interval; e->restart_in_rows = restart_in_rows; }
 };
 
 // the flags of the _ex encode calls: a bit this library does not know is the call's error, seen before the device is touched
 bool encode_flags_known(int flags) { return (flags & ~UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) == 0; }
+// The options struct of the _opts calls, checked before anything else (as the _ex calls check their flags): its size, the flag
+// bits and libjpeg's limit on restart_interval.  NULL is no option at all.
+int encode_opts(const uhdr_hip_jpeg_encode_opts_t* opts, EncOpt* eo) {
+  *eo = EncOpt();
+  if (opts == nullptr) return UHDR_HIP_NO_ERROR;
+  if (opts->struct_size != sizeof(uhdr_hip_jpeg_encode_opts_t) || !encode_flags_known((int)opts->flags) ||
+      opts->restart_interval > 65535u)
+    return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  eo->optimize = (opts->flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0;
+  eo->restart_interval = opts->restart_interval;
+  eo->restart_in_rows = opts->restart_in_rows;
+  return UHDR_HIP_NO_ERROR;
+}
+// MCUs per restart interval of one file (0: none) and, at *intervals, how many intervals that makes
+uint32_t enc_restart(const jpeg::Job& j, uint32_t restart_interval, uint32_t restart_in_rows, uint32_t* intervals) {
+  const uint32_t bpm = j.gray ? 1u : j.rgb ? 3u : 6u;
+  const uint32_t ri = jpeg::restart_mcus(restart_interval, restart_in_rows, j.gray ? j.ybw : j.mcus_x);
+  *intervals = ri == 0 ? 0u : (j.nblk / bpm + ri - 1u) / ri;
+  return ri;
+}
+// the encoder workspace of one file with the call's options
+size_t enc_workspace_bytes(size_t w, size_t h, jpeg::Geometry geom, const EncOpt& eo) {
+  jpeg::Job j;
+  encode_job_tables(w, h, geom, 75, &j);
+  uint32_t intervals = 0;
+  enc_restart(j, eo.restart_interval, eo.restart_in_rows, &intervals);
+  jpeg::Layout l;
+  return jpeg::workspace_bytes(j.nblk, &l, intervals);
+}
+// a file with restart intervals addresses its packed stream in 32 bits (jpeg::kMaxRestartBlocks); the table search has its own limit
+bool encodable_with(size_t w, size_t h, jpeg::Geometry geom, const EncOpt& eo);
 // libjpeg's table search reads a count of 10^9 as "none": an image whose AC histogram could reach it gets no optimised tables
 bool optimizable(size_t w, size_t h, jpeg::Geometry geom) {
   jpeg::Job j;
   encode_job_tables(w, h, geom, 75, &j);
   return j.nblk <= jpeg::kMaxOptimizeBlocks;
+}
+bool encodable_with(size_t w, size_t h, jpeg::Geometry geom, const EncOpt& eo) {
+  if (eo.optimize && !optimizable(w, h, geom)) return false;
+  if (eo.restart_interval == 0 && eo.restart_in_rows == 0) return true;
+  jpeg::Job j;
+  encode_job_tables(w, h, geom, 75, &j);
+  return j.nblk <= jpeg::kMaxRestartBlocks;
 }
 
 // JpegEncoderHelper::compressImage (jpegencoderhelper.cpp:39-52) of k images in the leased context st: the headers are written into
@@ -1658,15 +1706,23 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     const EncJpeg& e = im[i];
     jobs[i] = encode_job(e.img, e.quality, e.pad_ls, e.pad_cs, e.rgb, e.mcu_planes);
     ws_off[i] = ws_total;
-    ws_total += round_up(jpeg::workspace_bytes(jobs[i].nblk, &lay[i]), 256);
+    uint32_t intervals = 0;
+    const uint32_t ri = enc_restart(jobs[i], e.restart_interval, e.restart_in_rows, &intervals);
+    if (ri != 0) {   // the file runs through the encoder's restart launches, and its header says DRI
+      jobs[i].rst_bpm = jobs[i].gray ? 1u : jobs[i].rgb ? 3u : 6u;
+      jobs[i].rst_blocks = ri * jobs[i].rst_bpm;
+      jobs[i].rst_marks = intervals - 1u;
+    }
+    ws_total += round_up(jpeg::workspace_bytes(jobs[i].nblk, &lay[i], intervals), 256);
     jobs[i].optimize = e.optimize ? 1 : 0;
     // The header split: with optimised tables the host writes SOI ... SOF alone, and the device appends its DHT and SOS segments.
     // Such a header is never longer than the default one -- baseline 8-bit data has at most 12 DC and 162 AC symbols, the sizes of
     // the Annex K tables --, so whatever is sized for the default header (a file's first-guess staging, a caller's capacity that
     // holds the default file) holds this one.
     jpeg::build_header((int)e.img.width, (int)e.img.height, enc_geom(e.img, e.rgb), e.quality, e.icc ? e.icc->data() : nullptr,
-                       e.icc ? e.icc->size() : 0, header[i], e.optimize);
-    if (im[i].cap == 0) im[i].cap = im[i].img.width * im[i].img.height * (jobs[i].rgb ? 3 : 1) + 65536;
+                       e.icc ? e.icc->size() : 0, header[i], e.optimize, ri);
+    // (the first guess holds the DRI segment and three bytes per interval as well)
+    if (im[i].cap == 0) im[i].cap = im[i].img.width * im[i].img.height * (jobs[i].rgb ? 3 : 1) + 65536 + (ri != 0 ? 6 + 3 * (size_t)intervals : 0);
     off[i] = hp_total;
     hp_total += round_up(e.to_dev ? header[i].size() : im[i].cap, 256);   // a device destination: the header's way there only
   }
@@ -1712,6 +1768,8 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     one.rgb = e.rgb;
     one.mcu_planes = e.mcu_planes;
     one.optimize = e.optimize;
+    one.restart_interval = e.restart_interval;
+    one.restart_in_rows = e.restart_in_rows;
     if (lease.get() == nullptr || compress_to_host(lease.get(), s, 1, &one, false) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
     e.big.assign(one.bytes, one.bytes + one.n);
     e.bytes = e.big.data();
@@ -1754,11 +1812,8 @@ int stage_encoder_slice(uint8_t* dy, const uhdr_hip_image_t& img, uhdr_hip_image
   return UHDR_HIP_NO_ERROR;
 }
 // what one image holds of its round: encoder workspace, staged planes, page-locked staging of the file
-size_t enc_round_bytes(const uhdr_hip_image_t& img, bool host_in, bool host_out) {
-  jpeg::Job j;
-  encode_job_tables(img.width, img.height, enc_geom(img, false), 75, &j);
-  jpeg::Layout l;
-  size_t b = jpeg::workspace_bytes(j.nblk, &l);
+size_t enc_round_bytes(const uhdr_hip_image_t& img, bool host_in, bool host_out, const EncOpt& eo = EncOpt()) {
+  size_t b = enc_workspace_bytes(img.width, img.height, enc_geom(img, false), eo);
   if (host_in) b += enc_stage_bytes(img);
   if (host_out) b += img.width * img.height + 65536;
   return b;
@@ -1769,7 +1824,7 @@ size_t enc_round_bytes(const uhdr_hip_image_t& img, bool host_in, bool host_out)
 // error of the device or the runtime.
 int jpeg_encode_round(DeviceState* st, hipStream_t s, bool host_in, bool host_out, const uhdr_hip_image_t* images, const int* quality,
                       const void* const* icc, const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size,
-                      const int* idx, int m, int* st_, bool optimize) {
+                      const int* idx, int m, int* st_, const EncOpt& eo) {
   std::vector<EncJpeg> im((size_t)m);
   std::vector<std::vector<uint8_t>> iccs((size_t)m);
   size_t stage_total = 0;
@@ -1797,7 +1852,7 @@ int jpeg_encode_round(DeviceState* st, hipStream_t s, bool host_in, bool host_ou
     e.icc = iccs[k].empty() ? nullptr : &iccs[k];
     e.pad_ls = img.luma_stride;
     e.pad_cs = img.chroma_stride;
-    e.optimize = optimize;
+    eo.to(&e);
     if (host_out) {
       e.keep_max = out_capacity[i];   // a file that will not fit is only measured
     } else {
@@ -1876,6 +1931,13 @@ int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void*
   return UHDR_HIP_NO_ERROR;
 }
 
+// the bodies of the batch calls below, behind the _ex and the _opts form of each
+static int jpeg_encode_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                  void* const* out, const size_t* out_capacity, size_t* out_size, int* status, const EncOpt& eo, int mem_space,
+                                  void* stream);
+static int jpeg_encode_rgb_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
+                                      size_t* out_size, int* status, const EncOpt& eo, int mem_space, void* stream);
+
 // uhdr_hip_jpeg_encode for n images in one call: a file that fails the single call's checks is not processed; the files of a round
 // share one jpeg::encode_batch_async launch set and one synchronisation (compress_to_host)
 int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
@@ -1889,7 +1951,22 @@ int uhdr_hip_jpeg_encode_batch_ex(int n, const uhdr_hip_image_t* images, const i
                                   void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int flags, int mem_space,
                                   void* stream) {
   if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  const bool optimize = (flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0;
+  return jpeg_encode_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status,
+                                EncOpt((flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0), mem_space, stream);
+}
+// opts == NULL, or no restart field set: uhdr_hip_jpeg_encode_batch_ex with opts->flags.  Otherwise every file with restart intervals
+// (DESIGN.md section 7.1.2), with either kind of tables
+int uhdr_hip_jpeg_encode_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                    void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                    const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpeg_encode_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, eo, mem_space, stream);
+}
+static int jpeg_encode_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                  void* const* out, const size_t* out_capacity, size_t* out_size, int* status, const EncOpt& eo, int mem_space,
+                                  void* stream) {
   if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
       (icc != nullptr && icc_size == nullptr))
     return UHDR_HIP_ERROR_BAD_PTR;
@@ -1902,7 +1979,7 @@ int uhdr_hip_jpeg_encode_batch_ex(int n, const uhdr_hip_image_t* images, const i
       st_[i] = UHDR_HIP_ERROR_BAD_PTR;
     else if (!encodable(im))
       st_[i] = UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
-    else if (optimize && !optimizable(im.width, im.height, enc_geom(im, false)))
+    else if (!encodable_with(im.width, im.height, enc_geom(im, false), eo))
       st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     else
       live.push_back(i);
@@ -1913,9 +1990,9 @@ int uhdr_hip_jpeg_encode_batch_ex(int n, const uhdr_hip_image_t* images, const i
   size_t done = 0;
   const int rc = run_rounds(
       live.size(), (size_t)jpeg::kMaxBatchJobs, stream,
-      [&](size_t k) { return enc_round_bytes(enc_image(images[live[k]]), host_in, host_out); },
+      [&](size_t k) { return enc_round_bytes(enc_image(images[live[k]]), host_in, host_out, eo); },
       [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
-        return jpeg_encode_round(st, s, host_in, host_out, images, quality, icc, icc_size, out, out_capacity, out_size, &live[r0], m, st_.data(), optimize);
+        return jpeg_encode_round(st, s, host_in, host_out, images, quality, icc, icc_size, out, out_capacity, out_size, &live[r0], m, st_.data(), eo);
       },
       &done);
   for (size_t k = done; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
@@ -1933,7 +2010,19 @@ int uhdr_hip_jpeg_encode_rgb_batch(int n, const uhdr_hip_image_t* images, const 
 int uhdr_hip_jpeg_encode_rgb_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
                                       size_t* out_size, int* status, int flags, int mem_space, void* stream) {
   if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  const bool optimize = (flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0;
+  return jpeg_encode_rgb_batch_with(n, images, quality, out, out_capacity, out_size, status, EncOpt((flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0),
+                                    mem_space, stream);
+}
+// opts as in uhdr_hip_jpeg_encode_batch_opts
+int uhdr_hip_jpeg_encode_rgb_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
+                                        size_t* out_size, int* status, const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpeg_encode_rgb_batch_with(n, images, quality, out, out_capacity, out_size, status, eo, mem_space, stream);
+}
+static int jpeg_encode_rgb_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
+                                      size_t* out_size, int* status, const EncOpt& eo, int mem_space, void* stream) {
   if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)))
     return UHDR_HIP_ERROR_BAD_PTR;
   for (int i = 0; i < n; ++i)
@@ -1951,7 +2040,7 @@ int uhdr_hip_jpeg_encode_rgb_batch_ex(int n, const uhdr_hip_image_t* images, con
     else if (im.width == 0 || im.height == 0 || im.width > 65500 || im.height > 65500 || (im.luma_stride != 0 && im.luma_stride < im.width) ||
              im.luma_stride > (size_t)INT32_MAX / 4)   // (rows are addressed with an int byte pitch)
       st_[i] = UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
-    else if (optimize && !optimizable(im.width, im.height, jpeg::kGeomRgb444))
+    else if (!encodable_with(im.width, im.height, jpeg::kGeomRgb444, eo))
       st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     else
       live.push_back(i);
@@ -1963,10 +2052,7 @@ int uhdr_hip_jpeg_encode_rgb_batch_ex(int n, const uhdr_hip_image_t* images, con
       live.size(), (size_t)jpeg::kMaxBatchJobs, stream,
       [&](size_t k) {
         const uhdr_hip_image_t& im = images[live[k]];
-        jpeg::Job j;
-        encode_job_tables(im.width, im.height, jpeg::kGeomRgb444, 75, &j);
-        jpeg::Layout l;
-        size_t b = jpeg::workspace_bytes(j.nblk, &l);
+        size_t b = enc_workspace_bytes(im.width, im.height, jpeg::kGeomRgb444, eo);
         if (host_in) b += round_up(stage_pitch(im) * im.height, 256);
         if (host_out) b += im.width * im.height * 3 + 65536;
         return b;
@@ -1999,7 +2085,7 @@ int uhdr_hip_jpeg_encode_rgb_batch_ex(int n, const uhdr_hip_image_t* images, con
           e.icc = nullptr;
           e.pad_ls = e.pad_cs = 0;
           e.rgb = true;
-          e.optimize = optimize;
+          eo.to(&e);
           if (host_out) {
             e.keep_max = out_capacity[i];   // a file that will not fit is only measured
           } else {
@@ -2071,6 +2157,10 @@ int rgba420_planes(DeviceState* st, size_t slot, hipStream_t s, int m, const uhd
 
 extern "C" {
 
+static int jpeg_encode_rgba420_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
+                                          const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                          const EncOpt& eo, int mem_space, void* stream);
+
 // uhdr_hip_jpeg_encode_batch's conventions for RGBA8888 images compressed as 4:2:0: the planes libjpeg's colour conversion and
 // downsampler hand its FDCT come from one k_rgba_to_ycc420 launch per round, everything behind them is compress_to_host
 int uhdr_hip_jpeg_encode_rgba420_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
@@ -2083,7 +2173,21 @@ int uhdr_hip_jpeg_encode_rgba420_batch_ex(int n, const uhdr_hip_image_t* images,
                                           void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int flags, int mem_space,
                                           void* stream) {
   if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  const bool optimize = (flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0;
+  return jpeg_encode_rgba420_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status,
+                                        EncOpt((flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0), mem_space, stream);
+}
+// opts as in uhdr_hip_jpeg_encode_batch_opts
+int uhdr_hip_jpeg_encode_rgba420_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
+                                            const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                            const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpeg_encode_rgba420_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, eo, mem_space, stream);
+}
+static int jpeg_encode_rgba420_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
+                                          const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                          const EncOpt& eo, int mem_space, void* stream) {
   if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
       (icc != nullptr && icc_size == nullptr))
     return UHDR_HIP_ERROR_BAD_PTR;
@@ -2095,7 +2199,7 @@ int uhdr_hip_jpeg_encode_rgba420_batch_ex(int n, const uhdr_hip_image_t* images,
   const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE && mem_space != UHDR_HIP_MEM_HOST_TO_DEVICE;
   for (int i = 0; i < n; ++i) {
     st_[i] = rgba_file_check(images[i], host_in, out[i], out_capacity[i]);
-    if (st_[i] == UHDR_HIP_NO_ERROR && optimize && !optimizable(images[i].width, images[i].height, jpeg::kGeom420))
+    if (st_[i] == UHDR_HIP_NO_ERROR && !encodable_with(images[i].width, images[i].height, jpeg::kGeom420, eo))
       st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     if (st_[i] == UHDR_HIP_NO_ERROR) live.push_back(i);
   }
@@ -2106,10 +2210,7 @@ int uhdr_hip_jpeg_encode_rgba420_batch_ex(int n, const uhdr_hip_image_t* images,
       live.size(), (size_t)jpeg::kRgba420Chunk, stream,
       [&](size_t k) {
         const uhdr_hip_image_t& im = images[live[k]];
-        jpeg::Job j;
-        encode_job_tables(im.width, im.height, jpeg::kGeom420, 75, &j);
-        jpeg::Layout l;
-        size_t b = jpeg::workspace_bytes(j.nblk, &l) + round_up(jpeg::rgba420_plane_bytes(im.width, im.height), 256);
+        size_t b = enc_workspace_bytes(im.width, im.height, jpeg::kGeom420, eo) + round_up(jpeg::rgba420_plane_bytes(im.width, im.height), 256);
         if (host_in) b += round_up(stage_pitch(im) * im.height, 256);
         if (host_out) b += im.width * im.height + 65536;
         return b;
@@ -2147,7 +2248,7 @@ int uhdr_hip_jpeg_encode_rgba420_batch_ex(int n, const uhdr_hip_image_t* images,
           EncJpeg& e = im[(size_t)k];
           e.quality = quality[i];
           e.icc = iccs[(size_t)k].empty() ? nullptr : &iccs[(size_t)k];
-          e.optimize = optimize;
+          eo.to(&e);
           if (host_out) {
             e.keep_max = out_capacity[i];   // a file that will not fit is only measured
           } else {
@@ -2855,7 +2956,7 @@ EncJpeg gainmap_rgb_jpeg(uhdr_hip_image_t map) {
 // tonemap_op (API-0): the operator that derives the SDR planes; its headroom array is a pool slot of the context.
 int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_tf, int quality, EncFile* f, int m, uhdr_hip_metadata_t* md,
                  std::vector<EncJpeg>* jpg, int boost_scope = -1, float* range = nullptr, int carry = 0,
-                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, bool rgb_map = false, int map_scale = 4, bool optimize = false) {
+                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, bool rgb_map = false, int map_scale = 4, const EncOpt& eo = EncOpt()) {
   const size_t msf = (size_t)map_scale;     // the map's factor: uhdr_hip_jpegr_encode_scaled_batch's, 4 in every other call
   const size_t map_bpp = rgb_map ? 4 : 1;   // rgb_map: uhdr_hip_generate_gainmap_rgb_batch's RGBA map, compressed as 4:4:4
   auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -2982,7 +3083,7 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
     jpg->push_back(EncJpeg{e.enc, quality, &e.icc, e.pad_ls, e.pad_cs});
     jpg->push_back(rgb_map ? gainmap_rgb_jpeg(g) : gainmap_jpeg(g, g.luma_stride));
   }
-  for (EncJpeg& e : *jpg) e.optimize = optimize;   // the primary image and the gain map alike
+  for (EncJpeg& e : *jpg) eo.to(&e);   // the primary image and the gain map alike (intervals in rows: each from its own width)
   return compress_to_host(st, s, 2 * m, jpg->data(), true, dev_range, dev_range ? 8 * (size_t)m : 0, range);
 }
 
@@ -2992,7 +3093,7 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
                  const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
                  int* status, int mem_space, void* stream, int boost_scope = -1, uhdr_hip_metadata_t* metadata = nullptr,
                  int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, const float* hdr_peak_nits = nullptr, bool rgb_map = false, int map_scale = 4,
-                 bool optimize = false) {
+                 const EncOpt& eo = EncOpt()) {
   const bool api0 = yuv420_images == nullptr;
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
   std::vector<EncFile> files;
@@ -3007,7 +3108,7 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
     if (rc == UHDR_HIP_NO_ERROR && map_scale != 4 &&
         (p010_images[i].width % (size_t)map_scale != 0 || p010_images[i].height % (size_t)map_scale != 0))
       rc = UHDR_HIP_ERROR_UNSUPPORTED_WIDTH_HEIGHT;
-    if (rc == UHDR_HIP_NO_ERROR && optimize && !optimizable(p010_images[i].width, p010_images[i].height, jpeg::kGeom420))
+    if (rc == UHDR_HIP_NO_ERROR && !encodable_with(p010_images[i].width, p010_images[i].height, jpeg::kGeom420, eo))
       rc = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     if (rc != UHDR_HIP_NO_ERROR) { st_[i] = rc; continue; }
     EncFile e;
@@ -3059,7 +3160,7 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
         uhdr_hip_metadata_t md;
         std::vector<EncJpeg> jpg;
         if ((rc = encode_round(st, s, api0, host, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry, tonemap_op, rgb_map, map_scale,
-                               optimize)) != UHDR_HIP_NO_ERROR)
+                               eo)) != UHDR_HIP_NO_ERROR)
           return rc;
         std::vector<uhdr_hip_metadata_t> mds;   // adaptive: every file's own
         if (boost_scope < 0 && metadata)
@@ -3169,6 +3270,10 @@ int apix_check(const uhdr_hip_image_t& yuv_in, const uhdr_hip_image_t& gainmap, 
 
 extern "C" {
 
+static int jpegr_encode_batch_with(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                                   const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                   size_t* out_size, int* status, const EncOpt& eo, int mem_space, void* stream);
+
 int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
                                 const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
                                 int* status, int mem_space, void* stream) {
@@ -3182,12 +3287,40 @@ int uhdr_hip_jpegr_encode_batch_ex(int n, const uhdr_hip_image_t* p010_images, c
                                    const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
                                    size_t* out_size, int* status, int flags, int mem_space, void* stream) {
   if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return jpegr_encode_batch_with(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status,
+                                 EncOpt((flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0), mem_space, stream);
+}
+// opts == NULL, or no restart field set: uhdr_hip_jpegr_encode_batch_ex with opts->flags.  Otherwise the primary image and the gain-map
+// JPEG of every file with restart intervals, restart_in_rows counting each one's own MCU rows
+int uhdr_hip_jpegr_encode_batch_opts(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                                     const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                     size_t* out_size, int* status, const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpegr_encode_batch_with(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, eo, mem_space,
+                                 stream);
+}
+static int jpegr_encode_batch_with(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                                   const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                   size_t* out_size, int* status, const EncOpt& eo, int mem_space, void* stream) {
   if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
       (exif != nullptr && exif_size == nullptr))
     return UHDR_HIP_ERROR_BAD_PTR;
   if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
   return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, -1,
-                      nullptr, UHDR_HIP_TONEMAP_SHIFT, nullptr, false, 4, (flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0);
+                      nullptr, UHDR_HIP_TONEMAP_SHIFT, nullptr, false, 4, eo);
+}
+
+// the interval rule on its own, host only: what compress_to_host derives for a scan of this width (enc_restart)
+int uhdr_hip_jpeg_restart_mcus(const uhdr_hip_jpeg_encode_opts_t* opts, size_t width, int mcu_width, uint32_t* restart_mcus) {
+  EncOpt eo;
+  const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if (restart_mcus == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  if ((mcu_width != 8 && mcu_width != 16) || width == 0 || width > 65535) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
+  *restart_mcus = jpeg::restart_mcus(eo.restart_interval, eo.restart_in_rows, (uint32_t)((width + (size_t)mcu_width - 1) / (size_t)mcu_width));
+  return UHDR_HIP_NO_ERROR;
 }
 
 // jpeg_gen_optimal_table of a caller's histogram by the encoder's table kernel: what an image's symbol

@@ -37,9 +37,15 @@ struct Job {
   uint32_t* hist;          // 4 x 256 symbol counts ([0] DC lum, [1] AC lum, [2] DC chroma, [3] AC chroma), zeroed on the stream
   uint32_t* huff;          // 4 x 256 codes built from them, (size << 16) | code as in c_huff
   uint32_t* hdr_len;       // the header's length, known once k_jpeg_opt_tables_batch has written the DHT and SOS segments
+  // restart intervals (rst_blocks != 0): the job runs through the k_jpeg_rst_* launches of its round, with either kind of tables
+  uint32_t rst_blocks;     // blocks per interval: libjpeg's restart_interval (MCUs, 1 .. 65535) x rst_bpm
+  uint32_t rst_bpm;        // blocks per MCU: 6 (4:2:0), 3 (4:4:4) or 1
+  uint32_t rst_marks;      // RSTn markers in the stream: one behind every interval but the last
+  uint32_t* rst_pfx;       // nblk: the bits of the blocks in front of each, modulo 2^32, without padding and markers
+  uint32_t* rst_mark;      // rst_marks: where each marker's 0xFF stands in the packed stream (bytes), ascending
 };
 struct Layout {
-  size_t coef, bits, bits_blk, stream, stream_bytes, ff_count, ff_blk, totals, scan_tmp, scan_tmp_bytes, hist, huff;
+  size_t coef, bits, bits_blk, stream, stream_bytes, ff_count, ff_blk, totals, scan_tmp, scan_tmp_bytes, hist, huff, rst_pfx, rst_mark;
   uint32_t max_chunks;
 };
 
@@ -49,8 +55,16 @@ void zigzag_table(const uint16_t natural[64], uint16_t zz[64]);
 // geom: what the frame header declares -- the 4:2:0 and single-plane files of the reference's encoder, or three 1x1 components
 enum Geometry : int { kGeom420 = 0, kGeomGray = 1, kGeomRgb444 = 2 };
 // prefix_only: SOI ... SOF alone -- the DHT and SOS segments of a file with optimised tables are written on the device
-void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& out, bool prefix_only = false);
-size_t workspace_bytes(uint32_t nblk, Layout* l);
+// restart_interval != 0 (and not prefix_only): a DRI segment between the last DHT and SOS
+void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& out, bool prefix_only = false,
+                  uint32_t restart_interval = 0);
+// libjpeg's restart_in_rows over restart_interval: MCUs per interval of a scan with mcus_per_row MCUs in a row (0: none)
+uint32_t restart_mcus(uint32_t restart_interval, uint32_t restart_in_rows, uint32_t mcus_per_row);
+// a job with restart intervals (Job::rst_blocks) works in a stream area that also holds their padding and markers; the packed stream
+// is addressed in 32 bits there, so such a job has at most kMaxRestartBlocks blocks
+constexpr uint32_t kMaxRestartBlocks = 20000000u;
+// intervals: ceil(MCUs / restart interval) of such a job, 0 for every other
+size_t workspace_bytes(uint32_t nblk, Layout* l, uint32_t intervals = 0);
 // enqueues the whole encoder; the JPEG (without the header, which the caller places at out[0, header_len)) lands at
 // out + header_len, its total size (header included) in the uint64 at ws + l.totals + 8
 hipError_t encode_async(Job j, const Layout& l, uint8_t* ws, uint8_t* out, uint64_t out_cap, uint64_t header_len, hipStream_t s);

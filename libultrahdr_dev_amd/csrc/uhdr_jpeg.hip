@@ -16,6 +16,7 @@
 //   k_rgba_to_ycc420    (in front of the chain, uhdr_hip_jpeg_encode_rgba420_batch only) RGBA8888 -> the Y, Cb, Cr planes libjpeg's
 //                       colour conversion and h2v2 downsampler hand its FDCT, padded to whole MCUs as libjpeg pads them
 //   k_jpeg_opt_*        (Job::optimize) the same chain with Huffman tables built from the image's own symbol counts, see below
+//   k_jpeg_rst_*        (Job::rst_blocks) the same chain with restart intervals -- padding, RSTn markers, the DC prediction cut --, see below
 //
 // Byte-exact against libjpeg for every size, stride regime and quality tested (tests/test_gpu_jpeg.py against
 // oracle/jpeg_oracle.c, which tests/test_jpeg_oracle.py pins to the libjpeg builds of the image).
@@ -134,7 +135,8 @@ void put_dht(std::vector<uint8_t>& b, int cls_idx, const uint8_t bits[16], const
 }
 }  // namespace
 
-void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& b, bool prefix_only) {
+void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& b, bool prefix_only,
+                  uint32_t restart_interval) {
   const bool gray = geom == kGeomGray;
   uint16_t ql[64], qc[64];
   quant_table(quality, false, ql);
@@ -165,6 +167,7 @@ void build_header(int w, int h, Geometry geom, int quality, const void* icc, siz
     put_dht(b, 0x01, kBitsDcChr, kValsDc);
     put_dht(b, 0x11, kBitsAcChr, kValsAcChr);
   }
+  if (restart_interval != 0) { put16(b, 0xFFDD); put16(b, 4); put16(b, restart_interval); }   // jcmarker.c write_scan_header: emit_dri
   put16(b, 0xFFDA); put16(b, (unsigned)(6 + 2 * nc)); b.push_back((uint8_t)nc);
   for (int c = 0; c < nc; ++c) { b.push_back((uint8_t)(c + 1)); b.push_back((uint8_t)(c == 0 ? 0x00 : 0x11)); }
   b.push_back(0); b.push_back(63); b.push_back(0);
@@ -377,6 +380,13 @@ __device__ __forceinline__ int pred_of(const Job& j, uint32_t i) {
   const uint32_t p = dc_predecessor(j, i);
   return p == 0xFFFFFFFFu ? 0 : (int)j.coef[(size_t)p * 64u];
 }
+// a job with restart intervals (Job::rst_blocks): the prediction of every component starts again at 0 with the interval -- its first MCU's
+// chroma blocks and first luma block have no predecessor; the other three luma blocks of a 4:2:0 MCU chain inside it as ever
+__device__ __forceinline__ int pred_of_rst(const Job& j, uint32_t i) {
+  const uint32_t r = i % j.rst_blocks;
+  if (r < j.rst_bpm && (j.rst_bpm != 6u || r == 0u || r >= 4u)) return 0;
+  return pred_of(j, i);
+}
 __device__ __forceinline__ int comp_of(const Job& j, uint32_t i) {
   if (j.rgb) return (i % 3u) == 0u ? 0 : 1;
   return j.gray ? 0 : ((i % 6u) < 4u ? 0 : 1);
@@ -499,7 +509,9 @@ struct EmitSink {
   }
 };
 
-template <typename HUFF = ConstHuff>
+// RST (a job with restart intervals): Job::bits of an interval's last block holds its padding and its marker too (k_jpeg_rst_adjust_batch),
+// so the offsets are the same plain sum; that block fills its byte with ones, writes RSTn behind it and says where the marker stands
+template <typename HUFF = ConstHuff, bool RST = false>
 __device__ __forceinline__ void emit_wg(const Job& j, const uint32_t wg) {
   __shared__ uint64_t s_part[2];
   __shared__ uint64_t s_base;
@@ -521,7 +533,14 @@ __device__ __forceinline__ void emit_wg(const Job& j, const uint32_t wg) {
   s.wi = (uint32_t)(off >> 5);
   s.first = true;
   const int chroma = comp_of(j, i);
-  walk_block(j.coef + (size_t)i * 64u, pred_of(j, i), 2 * chroma, 2 * chroma + 1, s, HUFF());
+  walk_block(j.coef + (size_t)i * 64u, RST ? pred_of_rst(j, i) : pred_of(j, i), 2 * chroma, 2 * chroma + 1, s, HUFF());
+  if (RST && i != j.nblk - 1u && (i + 1u) % j.rst_blocks == 0u) {   // jchuff.c emit_restart: flush_bits, then the marker
+    const int pad = (8 - (s.nacc & 7)) & 7;   // (words are whole bytes: the sink's position in its word is the stream's in its byte)
+    if (pad) s.put((1u << pad) - 1u, pad);
+    const uint32_t t = i / j.rst_blocks;
+    s.put(0xFFD0u | (t & 7u), 16);
+    j.rst_mark[t] = (uint32_t)((off + my_bits) >> 3) - 2u;
+  }
   if (i == j.nblk - 1u) {      // jchuff.c flush_bits: fill the last byte with ones
     const uint64_t end = off + my_bits;
     const int pad = (int)((8u - (uint32_t)(end & 7u)) & 7u);
@@ -536,6 +555,19 @@ constexpr uint32_t kChunk = 64;
 // ff_count[t]: 0xFF bytes in chunk t; ff_blk[g]: in the 256 chunks of workgroup g.  The copy needs the number of stuffed zeros in
 // front of every chunk: inside a workgroup a block scan of 256 counts, across workgroups the sum of the totals in front, which
 // every workgroup of the copy forms for itself (a 4K frame has ~100 of them) -- no device-wide scan between the two kernels.
+// RST (a job with restart intervals): the 0xFF of an RSTn marker is no data byte and gets no zero.  The bytes cannot tell -- a data
+// 0xFF in front of a data 0xD0..0xD7 occurs --, so the emit left the markers' offsets in Job::rst_mark, ascending: a chunk looks up
+// the first one at or behind its start and walks on from there.
+__device__ __forceinline__ uint32_t first_mark_from(const Job& j, uint32_t b) {
+  uint32_t lo = 0, hi = j.rst_marks;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (j.rst_mark[mid] < b) lo = mid + 1u;
+    else hi = mid;
+  }
+  return lo;
+}
+template <bool RST = false>
 __device__ __forceinline__ void stuff_count_wg(const Job& j, const uint64_t* total_bits, const uint32_t wg) {
   __shared__ uint32_t s_part[4];
   const uint32_t t = wg * 256u + threadIdx.x;
@@ -546,7 +578,18 @@ __device__ __forceinline__ void stuff_count_wg(const Job& j, const uint64_t* tot
   if (t < j.max_chunks && b0 < nbytes) {
     const uint8_t* p = reinterpret_cast<const uint8_t*>(j.stream) + b0;
     const uint32_t len = (uint32_t)(nbytes - b0 < kChunk ? nbytes - b0 : kChunk);
-    for (uint32_t k = 0; k < len; ++k) n += p[k] == 0xFFu;
+    if (RST) {
+      uint32_t mi = first_mark_from(j, (uint32_t)b0);
+      uint32_t next = mi < j.rst_marks ? j.rst_mark[mi] : 0xFFFFFFFFu;
+      for (uint32_t k = 0; k < len; ++k) {
+        if (p[k] != 0xFFu) continue;
+        if ((uint32_t)b0 + k != next) { ++n; continue; }
+        ++mi;
+        next = mi < j.rst_marks ? j.rst_mark[mi] : 0xFFFFFFFFu;
+      }
+    } else {
+      for (uint32_t k = 0; k < len; ++k) n += p[k] == 0xFFu;
+    }
     j.ff_count[t] = n;
   }
   const uint32_t total = block_sum<256>(n, s_part);
@@ -557,6 +600,7 @@ __global__ void __launch_bounds__(256) k_jpeg_stuff_count(const Job j, const uin
 // 0xFF), then the workgroup writes the expanded run to the output as aligned dwords: the run's start in the output is
 // arbitrary (header length + stuffed bytes before it), so a thread per chunk writing its own bytes would scatter byte
 // stores over 256 cache lines per instruction (28 us per 4K frame measured; this form: see DESIGN.md).
+template <bool RST = false>
 __device__ __forceinline__ void stuff_copy_wg(const Job& j, const uint64_t* total_bits, uint8_t* out, uint64_t out_cap, uint64_t header_len,
                                               uint64_t* out_size, const uint32_t wg) {
   __shared__ uint32_t s_part[4];
@@ -579,6 +623,11 @@ __device__ __forceinline__ void stuff_copy_wg(const Job& j, const uint64_t* tota
     const uint32_t len = (uint32_t)(nbytes - b0 < kChunk ? nbytes - b0 : kChunk);
     uint32_t lo = (uint32_t)(b0 - blk_b0) + ff_before;
     const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(j.stream) + b0);
+    uint32_t mi = 0, next = 0xFFFFFFFFu;   // RST: the next marker at or behind this byte (stuff_count_wg)
+    if (RST) {
+      mi = first_mark_from(j, (uint32_t)b0);
+      if (mi < j.rst_marks) next = j.rst_mark[mi];
+    }
 #pragma unroll
     for (uint32_t q = 0; q < kChunk / 16u; ++q) {
       const uint4 v = src[q];                         // (reads up to 15 bytes past len inside the zeroed workspace)
@@ -588,7 +637,18 @@ __device__ __forceinline__ void stuff_copy_wg(const Job& j, const uint64_t* tota
         if (q * 16u + k < len) {
           const uint8_t by = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
           s_buf[lo++] = by;
-          if (by == 0xFFu) s_buf[lo++] = 0;
+          if (RST) {
+            if (by == 0xFFu) {
+              if ((uint32_t)b0 + q * 16u + k != next) {
+                s_buf[lo++] = 0;
+              } else {
+                ++mi;
+                next = mi < j.rst_marks ? j.rst_mark[mi] : 0xFFFFFFFFu;
+              }
+            }
+          } else {
+            if (by == 0xFFu) s_buf[lo++] = 0;
+          }
         }
       }
     }
@@ -1011,20 +1071,215 @@ __global__ void __launch_bounds__(256) k_jpeg_opt_stuff_copy_batch(const Job* __
   }
 }
 
+// ---- restart intervals (Job::rst_blocks != 0) ---------------------------------------------------------------------------------------
+// libjpeg's restart_interval for the jobs of a round that ask for it: after every Ri MCUs but the last group the byte is filled with
+// ones, RSTn follows, and the DC prediction starts again.  These jobs, with default and with optimised tables alike, run through
+// launches of their own (the others keep theirs, untouched); none grows with the number of intervals:
+//   k_jpeg_opt_zero_batch, k_jpeg_opt_fdct_batch[_rgb]   as they are: coefficients know no prediction
+//   k_jpeg_rst_hist_batch      (optimised tables) the histogram of the symbols with the prediction cut
+//   k_jpeg_rst_tables_batch    optimised tables: DHT, DRI, SOS behind the host's prefix; default tables: the Annex K codes into the job's
+//                              workspace -- one chain reads its codes from LDS for both
+//   k_jpeg_rst_count_batch     bits per block and per workgroup, the prediction cut
+//   k_jpeg_rst_prefix_batch    every block's bits in front, modulo 2^32, as a plain sum without padding or markers
+//   k_jpeg_rst_adjust_batch    an interval's unpadded length is the difference of that sum at its two ends, and its padding follows from
+//                              the length modulo 8 alone since every interval starts on a byte: the last block of each interval but the
+//                              final one takes padding + 16 bits onto its own count, the workgroup totals are formed again
+//   k_jpeg_clear_multi, k_jpeg_rst_emit_batch
+//                              with the padding and the marker part of a block's bits, offsets are the plain sum of Job::bits the other
+//                              jobs use -- the segmented sum is gone; the emit records where each marker stands
+//   k_jpeg_rst_stuff_count_batch, k_jpeg_rst_stuff_copy_batch
+//                              0x00 behind every data 0xFF and behind no marker's
+__global__ void __launch_bounds__(128) k_jpeg_rst_hist_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint32_t s_hist[4 * 256];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  if (!j.optimize) return;   // (uniform per workgroup) default tables: nothing to count
+  const uint32_t nbins = j.gray ? 512u : 1024u;
+  for (uint32_t b = threadIdx.x; b < nbins; b += 128u) s_hist[b] = 0u;
+  __syncthreads();
+  const uint32_t i = (blockIdx.x - first) * 128u + threadIdx.x;
+  if (i < j.nblk) {
+    const int chroma = comp_of(j, i);
+    NullSink ns;
+    walk_block(j.coef + (size_t)i * 64u, pred_of_rst(j, i), 2 * chroma, 2 * chroma + 1, ns, HistHuff{s_hist});
+  }
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < nbins; b += 128u) {
+    const uint32_t v = s_hist[b];
+    if (v != 0u) atomicAdd(&j.hist[b], v);
+  }
+}
+// k_jpeg_opt_tables_batch's work for a job with restart intervals: the DRI segment stands between the last DHT and SOS (jcmarker.c
+// write_scan_header)
+__device__ __forceinline__ void rst_tables_wg(const Job& j, const BatchOut& o) {
+  __shared__ TableLds s_tbl[4];
+  const uint32_t t = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const uint32_t ntab = j.gray ? 2u : 4u;
+  const bool active = t < ntab;
+  TableLds& L = s_tbl[t];
+  if (build_table(j.hist + 256u * t, active, L, j.huff + 256u * t) && active) {   // the default table in its place: it codes every symbol
+    const uint32_t nv = (t & 1u) ? 162u : 12u;
+    if (lane < 16u) L.bits[lane + 1u] = c_std_dht[t][lane];
+    for (uint32_t k = lane; k < nv; k += 64u) L.vals[k] = c_std_dht[t][16u + k];
+    for (uint32_t k = lane; k < 256u; k += 64u) j.huff[256u * t + k] = c_huff[t][k];
+    if (lane == 0u) L.nvals = nv;
+  }
+  __syncthreads();
+  uint64_t at = o.header_len, total = o.header_len + (j.gray ? 10u : 14u) + 6u;
+  for (uint32_t k = 0; k < ntab; ++k) {
+    const uint32_t seg = 21u + s_tbl[k].nvals;   // marker, length, class and index, BITS, HUFFVAL
+    if (k < t) at += seg;
+    total += seg;
+  }
+  if (threadIdx.x == 0u) *j.hdr_len = (uint32_t)total;
+  if (total > o.out_cap) return;
+  if (o.prefix != nullptr)
+    for (uint32_t k = threadIdx.x; k < (uint32_t)o.header_len; k += 256u) o.out[k] = o.prefix[k];
+  if (active) {
+    const uint32_t nv = L.nvals;
+    uint8_t* d = o.out + at;
+    for (uint32_t k = lane; k < 21u + nv; k += 64u) {
+      uint32_t v;
+      if (k == 0u) v = 0xFFu;
+      else if (k == 1u) v = 0xC4u;
+      else if (k == 2u) v = (19u + nv) >> 8;
+      else if (k == 3u) v = (19u + nv) & 0xffu;
+      else if (k == 4u) v = ((t & 1u) << 4) | (t >> 1);
+      else if (k < 21u) v = L.bits[k - 4u];
+      else v = L.vals[k - 21u];
+      d[k] = (uint8_t)v;
+    }
+  }
+  const uint32_t nc = j.gray ? 1u : 3u, sos = 8u + 2u * nc;
+  if (threadIdx.x < sos) {   // jcmarker.c emit_sos
+    const uint32_t k = threadIdx.x;
+    uint32_t v;
+    if (k == 0u) v = 0xFFu;
+    else if (k == 1u) v = 0xDAu;
+    else if (k == 2u) v = 0u;
+    else if (k == 3u) v = 6u + 2u * nc;
+    else if (k == 4u) v = nc;
+    else if (k < 5u + 2u * nc) v = ((k - 5u) & 1u) ? (k == 6u ? 0x00u : 0x11u) : (k - 5u) / 2u + 1u;
+    else v = k == 6u + 2u * nc ? 63u : 0u;
+    o.out[total - sos + k] = (uint8_t)v;
+  }
+  if (threadIdx.x >= 64u && threadIdx.x < 70u) {   // jcmarker.c emit_dri
+    const uint32_t k = threadIdx.x - 64u, ri = j.rst_blocks / j.rst_bpm;
+    const uint32_t v = k == 0u ? 0xFFu : k == 1u ? 0xDDu : k == 2u ? 0u : k == 3u ? 4u : k == 4u ? ri >> 8 : ri & 0xffu;
+    o.out[total - sos - 6u + k] = (uint8_t)v;
+  }
+}
+__global__ void __launch_bounds__(256) k_jpeg_rst_tables_batch(const Job* __restrict__ jobs, const BatchOut* __restrict__ outs) {
+  const Job& j = uniform_ref(jobs, blockIdx.x);
+  const BatchOut& o = uniform_ref(outs, blockIdx.x);
+  if (j.optimize) {   // (uniform per workgroup)
+    rst_tables_wg(j, o);
+    return;
+  }
+  const uint32_t ntab = j.gray ? 2u : 4u;   // the host wrote the whole header, DRI included
+  for (uint32_t t = 0; t < ntab; ++t) j.huff[256u * t + threadIdx.x] = c_huff[t][threadIdx.x];
+  if (threadIdx.x == 0u) *j.hdr_len = (uint32_t)o.header_len;
+}
+__global__ void __launch_bounds__(128) k_jpeg_rst_count_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint32_t s_part[2];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  load_job_huff(j);
+  const uint32_t wg = blockIdx.x - first, i = wg * 128u + threadIdx.x;
+  uint32_t my_bits = 0;
+  if (i < j.nblk) {
+    const int chroma = comp_of(j, i);
+    CountSink cs;
+    walk_block(j.coef + (size_t)i * 64u, pred_of_rst(j, i), 2 * chroma, 2 * chroma + 1, cs, LdsHuff());
+    j.bits[i] = my_bits = cs.bits;
+  }
+  const uint32_t total = block_sum<128>(my_bits, s_part);
+  if (threadIdx.x == 0u) j.bits_blk[wg] = total;
+}
+__global__ void __launch_bounds__(128) k_jpeg_rst_prefix_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint32_t s_part[2];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  const uint32_t wg = blockIdx.x - first, i = wg * 128u + threadIdx.x;
+  uint32_t before = 0;
+  for (uint32_t g = threadIdx.x; g < wg; g += 128u) before += j.bits_blk[g];
+  before = block_sum<128>(before, s_part);
+  const uint32_t in_front = block_exclusive_sum<128>(i < j.nblk ? j.bits[i] : 0u, s_part);
+  if (i < j.nblk) j.rst_pfx[i] = before + in_front;
+}
+__global__ void __launch_bounds__(128) k_jpeg_rst_adjust_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint32_t s_part[2];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  const uint32_t wg = blockIdx.x - first, i = wg * 128u + threadIdx.x;
+  uint32_t my_bits = 0;
+  if (i < j.nblk) {
+    my_bits = j.bits[i];
+    if (i != j.nblk - 1u && (i + 1u) % j.rst_blocks == 0u) {   // the last block of an interval that a marker follows
+      const uint32_t len = j.rst_pfx[i] + my_bits - j.rst_pfx[i + 1u - j.rst_blocks];   // (modulo 2^32: a multiple of 8)
+      my_bits += ((8u - (len & 7u)) & 7u) + 16u;
+      j.bits[i] = my_bits;
+    }
+  }
+  const uint32_t total = block_sum<128>(my_bits, s_part);
+  if (threadIdx.x == 0u) j.bits_blk[wg] = total;
+}
+__global__ void __launch_bounds__(128) k_jpeg_rst_emit_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  load_job_huff(j);
+  emit_wg<LdsHuff, true>(j, blockIdx.x - first);
+}
+__global__ void __launch_bounds__(256) k_jpeg_rst_stuff_count_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<256>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  const uint64_t nbytes = (*j.total_bits + 7u) >> 3;
+  for (uint32_t wg = blockIdx.x - first; (uint64_t)wg * 256u * kChunk < nbytes; wg += count) {
+    stuff_count_wg<true>(j, j.total_bits, wg);
+    __syncthreads();
+  }
+}
+__global__ void __launch_bounds__(256) k_jpeg_rst_stuff_copy_batch(const Job* __restrict__ jobs, const BatchOut* __restrict__ outs,
+                                                                   const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<256>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  const BatchOut& o = uniform_ref(outs, k);
+  const uint64_t header_len = *j.hdr_len, cap = header_len <= o.out_cap ? o.out_cap : 0u;
+  const uint64_t nbytes = (*j.total_bits + 7u) >> 3;
+  for (uint32_t wg = blockIdx.x - first; (uint64_t)wg * 256u * kChunk < nbytes; wg += count) {
+    stuff_copy_wg<true>(j, j.total_bits, o.out, cap, header_len, o.out_size, wg);
+    __syncthreads();   // (s_buf and s_len are the next piece's)
+  }
+}
+
 hipError_t optimal_table_async(const uint32_t* freq, uint8_t* bits, uint8_t* vals, int* nvals, hipStream_t s) {
   hipLaunchKernelGGL(k_jpeg_opt_table_one, dim3(1), dim3(64), 0, s, freq, bits, vals, nvals);
   return hipGetLastError();
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------
-size_t workspace_bytes(uint32_t nblk, Layout* l) {
+uint32_t restart_mcus(uint32_t restart_interval, uint32_t restart_in_rows, uint32_t mcus_per_row) {
+  if (restart_in_rows == 0) return restart_interval;
+  const uint64_t v = (uint64_t)restart_in_rows * mcus_per_row;   // jcmaster.c prepare_for_pass
+  return (uint32_t)(v < 65535u ? v : 65535u);
+}
+
+size_t workspace_bytes(uint32_t nblk, Layout* l, uint32_t intervals) {
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
   size_t o = 0;
   l->coef = o; o += up((size_t)nblk * 128);
   l->bits = o; o += up((size_t)(nblk + 1) * 4);
   l->bits_blk = o; o += up((size_t)(nblk / 128u + 2) * 4);
   // worst case per block: 20 bits of DC + 63 x 26 bits of AC = 1658 bits
-  l->stream_bytes = up((size_t)nblk * 208 + 64);
+  // an interval's padding and marker: up to 7 + 16 bits, of which its blocks' slack of 6 bits each need not hold any
+  l->stream_bytes = up((size_t)nblk * 208 + 64 + (size_t)intervals * 3);
   l->stream = o; o += l->stream_bytes;
   l->max_chunks = (uint32_t)(l->stream_bytes / kChunk);
   l->ff_count = o; o += up((size_t)l->max_chunks * 4);
@@ -1032,6 +1287,11 @@ size_t workspace_bytes(uint32_t nblk, Layout* l) {
   l->totals = o; o += 256;   // [0] total bits (uint64), [1] output size (uint64), [2] header length (uint32; optimised tables)
   l->hist = o; o += 4 * 256 * 4;
   l->huff = o; o += 4 * 256 * 4;
+  l->rst_pfx = l->rst_mark = o;
+  if (intervals != 0) {   // (a job without intervals keeps its layout)
+    l->rst_pfx = o; o += up((size_t)nblk * 4);
+    l->rst_mark = o; o += up((size_t)intervals * 4);
+  }
   l->scan_tmp_bytes = 0;
   l->scan_tmp = o;
   return o;
@@ -1064,7 +1324,7 @@ size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 }  // namespace
 
 size_t batch_desc_bytes(int n) {
-  return up256((size_t)n * sizeof(Job)) + up256((size_t)n * sizeof(BatchOut)) + 4 * up256(((size_t)n + 1) * 4);
+  return up256((size_t)n * sizeof(Job)) + up256((size_t)n * sizeof(BatchOut)) + 6 * up256(((size_t)n + 1) * 4);
 }
 
 hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_t* const* ws, const BatchOut* outs, uint8_t* host_desc,
@@ -1079,14 +1339,26 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
   // from their first): the default jobs' launches see neither them nor a flag
   uint32_t* opt_blk_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(stuff_start) + up256(((size_t)n + 1) * 4));
   uint32_t* opt_stuff_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(opt_blk_start) + up256(((size_t)n + 1) * 4));
-  blk_start[0] = stuff_start[0] = opt_blk_start[0] = opt_stuff_start[0] = 0;
-  int nd = 0;
-  for (int k = 0; k < n; ++k) nd += jobs_in[k].optimize ? 0 : 1;
+  // and behind those the jobs with restart intervals, whatever their tables, likewise
+  uint32_t* rst_blk_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(opt_stuff_start) + up256(((size_t)n + 1) * 4));
+  uint32_t* rst_stuff_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(rst_blk_start) + up256(((size_t)n + 1) * 4));
+  blk_start[0] = stuff_start[0] = opt_blk_start[0] = opt_stuff_start[0] = rst_blk_start[0] = rst_stuff_start[0] = 0;
+  int nd = 0, no = 0;
+  for (int k = 0; k < n; ++k) {
+    if (jobs_in[k].rst_blocks != 0) continue;
+    (jobs_in[k].optimize ? no : nd) += 1;
+  }
   bool any_planar = false, any_rgb = false, any_opt_planar = false, any_opt_rgb = false;
-  for (int k = 0, at_d = 0, at_o = nd; k < n; ++k) {
-    const bool opt = jobs_in[k].optimize != 0;
-    (opt ? (jobs_in[k].rgb ? any_opt_rgb : any_opt_planar) : (jobs_in[k].rgb ? any_rgb : any_planar)) = true;
-    const int at = opt ? at_o++ : at_d++;
+  bool any_rst_planar = false, any_rst_rgb = false, any_rst_opt = false;
+  for (int k = 0, at_d = 0, at_o = nd, at_r = nd + no; k < n; ++k) {
+    const bool rst = jobs_in[k].rst_blocks != 0, opt = !rst && jobs_in[k].optimize != 0;
+    if (rst) {
+      (jobs_in[k].rgb ? any_rst_rgb : any_rst_planar) = true;
+      any_rst_opt = any_rst_opt || jobs_in[k].optimize != 0;
+    } else {
+      (opt ? (jobs_in[k].rgb ? any_opt_rgb : any_opt_planar) : (jobs_in[k].rgb ? any_rgb : any_planar)) = true;
+    }
+    const int at = rst ? at_r++ : opt ? at_o++ : at_d++;
     Job& j = jobs[at];
     j = jobs_in[k];
     uint8_t* w = ws[k];
@@ -1101,10 +1373,12 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
     j.hist = reinterpret_cast<uint32_t*>(w + l[k].hist);
     j.huff = reinterpret_cast<uint32_t*>(w + l[k].huff);
     j.hdr_len = reinterpret_cast<uint32_t*>(w + l[k].totals + 16);
+    j.rst_pfx = reinterpret_cast<uint32_t*>(w + l[k].rst_pfx);
+    j.rst_mark = reinterpret_cast<uint32_t*>(w + l[k].rst_mark);
     o[at] = outs[k];
     const uint32_t stuff_wgs = (j.max_chunks + 255u) / 256u;
-    uint32_t* bs = opt ? opt_blk_start + (at - nd) : blk_start + at;
-    uint32_t* ss = opt ? opt_stuff_start + (at - nd) : stuff_start + at;
+    uint32_t* bs = rst ? rst_blk_start + (at - nd - no) : opt ? opt_blk_start + (at - nd) : blk_start + at;
+    uint32_t* ss = rst ? rst_stuff_start + (at - nd - no) : opt ? opt_stuff_start + (at - nd) : stuff_start + at;
     bs[1] = bs[0] + (j.nblk + 127u) / 128u;
     ss[1] = ss[0] + (stuff_wgs < kStuffWgPerJob ? stuff_wgs : kStuffWgPerJob);
   }
@@ -1125,8 +1399,8 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
     hipLaunchKernelGGL(k_jpeg_stuff_count_multi, gc, bc, 0, s, dj, dstuff, nj);
     hipLaunchKernelGGL(k_jpeg_stuff_copy_multi, gc, bc, 0, s, dj, dout, dstuff, nj);
   }
-  if (n > nd) {
-    const uint32_t nj = (uint32_t)(n - nd);
+  if (no > 0) {
+    const uint32_t nj = (uint32_t)no;
     const Job* oj = dj + nd;
     const BatchOut* oout = dout + nd;
     const uint32_t* oblk = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(opt_blk_start) - host_desc));
@@ -1142,6 +1416,26 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
     hipLaunchKernelGGL(k_jpeg_opt_emit_batch, gb, bb, 0, s, oj, oblk, nj);
     hipLaunchKernelGGL(k_jpeg_stuff_count_multi, gc, bc, 0, s, oj, ostuff, nj);
     hipLaunchKernelGGL(k_jpeg_opt_stuff_copy_batch, gc, bc, 0, s, oj, oout, ostuff, nj);
+  }
+  if (n > nd + no) {
+    const uint32_t nj = (uint32_t)(n - nd - no);
+    const Job* rj = dj + nd + no;
+    const BatchOut* rout = dout + nd + no;
+    const uint32_t* rblk = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(rst_blk_start) - host_desc));
+    const uint32_t* rstuff = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(rst_stuff_start) - host_desc));
+    const dim3 gb(rst_blk_start[nj]), gc(rst_stuff_start[nj]);
+    if (any_rst_opt) hipLaunchKernelGGL(k_jpeg_opt_zero_batch, dim3(nj), bc, 0, s, rj);
+    if (any_rst_planar) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch, gb, bb, 0, s, rj, rblk, nj);
+    if (any_rst_rgb) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch_rgb, gb, bb, 0, s, rj, rblk, nj);
+    if (any_rst_opt) hipLaunchKernelGGL(k_jpeg_rst_hist_batch, gb, bb, 0, s, rj, rblk, nj);
+    hipLaunchKernelGGL(k_jpeg_rst_tables_batch, dim3(nj), bc, 0, s, rj, rout);
+    hipLaunchKernelGGL(k_jpeg_rst_count_batch, gb, bb, 0, s, rj, rblk, nj);
+    hipLaunchKernelGGL(k_jpeg_rst_prefix_batch, gb, bb, 0, s, rj, rblk, nj);
+    hipLaunchKernelGGL(k_jpeg_rst_adjust_batch, gb, bb, 0, s, rj, rblk, nj);
+    hipLaunchKernelGGL(k_jpeg_clear_multi, gb, bb, 0, s, rj, rblk, nj);
+    hipLaunchKernelGGL(k_jpeg_rst_emit_batch, gb, bb, 0, s, rj, rblk, nj);
+    hipLaunchKernelGGL(k_jpeg_rst_stuff_count_batch, gc, bc, 0, s, rj, rstuff, nj);
+    hipLaunchKernelGGL(k_jpeg_rst_stuff_copy_batch, gc, bc, 0, s, rj, rout, rstuff, nj);
   }
   return hipGetLastError();
 }

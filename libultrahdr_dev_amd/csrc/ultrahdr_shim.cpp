@@ -325,14 +325,17 @@ int rgbmap_one(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, int hd
   const size_t exn = exif_len(exif);
   return uhdr_hip_jpegr_encode_rgbmap_batch(1, p010 ? p010 : &none, yuv, hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, UHDR_HIP_MEM_HOST, nullptr);
 }
-// one file through uhdr_hip_jpegr_encode_batch_ex with UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN (setOptimizeHuffman): API-1, or API-0 with yuv == nullptr
-int optimized_one(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, int hdr_tf, int quality, uhdr_exif_ptr exif, void* out, size_t cap, size_t* n) {
+// one file through uhdr_hip_jpegr_encode_batch_opts (setOptimizeHuffman, setRestartInterval, setRestartInRows): API-1, or API-0 with
+// yuv == nullptr
+int optimized_one(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, int hdr_tf, int quality, uhdr_exif_ptr exif, void* out, size_t cap, size_t* n,
+                  bool optimize, unsigned restart_interval, unsigned restart_in_rows) {
   uhdr_hip_image_t none;
   std::memset(&none, 0, sizeof(none));
   const void* ex = exif_ptr(exif);
   const size_t exn = exif_len(exif);
-  return uhdr_hip_jpegr_encode_batch_ex(1, p010 ? p010 : &none, yuv, hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN,
-                                        UHDR_HIP_MEM_HOST, nullptr);
+  const uhdr_hip_jpeg_encode_opts_t opts = {(uint32_t)sizeof(uhdr_hip_jpeg_encode_opts_t), optimize ? (uint32_t)UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN : 0u,
+                                            restart_interval, restart_in_rows};
+  return uhdr_hip_jpegr_encode_batch_opts(1, p010 ? p010 : &none, yuv, hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, &opts, UHDR_HIP_MEM_HOST, nullptr);
 }
 // one file through uhdr_hip_jpegr_encode_scaled_batch (setGainMapScaleFactor): API-1, or API-0 with yuv == nullptr
 int scaled_one(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, int hdr_tf, int quality, uhdr_exif_ptr exif, void* out, size_t cap, size_t* n,
@@ -350,10 +353,10 @@ status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, ultrahdr_tr
                                uhdr_exif_ptr exif) {
   uhdr_hip_image_t p;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
-  if (mOptimizeHuffman) {   // setOptimizeHuffman: the plain API-0 alone has the flag so far
+  if (mOptimizeHuffman || mRestartInterval != 0 || mRestartInRows != 0) {   // the plain API-0 alone has these options so far
     if (mGainMapScaleFactor != 4 || mMultiChannelGainMap || mToneMapOp != UHDR_HIP_TONEMAP_SHIFT || mContentBoost >= 0) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;
     return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
-      return optimized_one(p010_image_ptr ? &p : nullptr, nullptr, (int)hdr_tf, quality, exif, out, cap, n);
+      return optimized_one(p010_image_ptr ? &p : nullptr, nullptr, (int)hdr_tf, quality, exif, out, cap, n, mOptimizeHuffman, mRestartInterval, mRestartInRows);
     });
   }
   if (mGainMapScaleFactor != 4) {   // setGainMapScaleFactor: the operator and the adaptive range have no form at another factor
@@ -389,11 +392,11 @@ status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, uhdr_uncomp
   uhdr_hip_image_t p, y;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
   if (yuv420_image_ptr) y = to_c(*yuv420_image_ptr);
-  if (mOptimizeHuffman) {   // setOptimizeHuffman: the plain API-1 alone has the flag so far
+  if (mOptimizeHuffman || mRestartInterval != 0 || mRestartInRows != 0) {   // the plain API-1 alone has these options so far
     if (mGainMapScaleFactor != 4 || mMultiChannelGainMap || mContentBoost >= 0) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;
     if (yuv420_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;   // jpegr.cpp:253-256 (a NULL array would mean API-0 to the batch)
     return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
-      return optimized_one(p010_image_ptr ? &p : nullptr, &y, (int)hdr_tf, quality, exif, out, cap, n);
+      return optimized_one(p010_image_ptr ? &p : nullptr, &y, (int)hdr_tf, quality, exif, out, cap, n, mOptimizeHuffman, mRestartInterval, mRestartInRows);
     });
   }
   if (mGainMapScaleFactor != 4) {   // setGainMapScaleFactor
