@@ -440,6 +440,35 @@ int uhdr_hip_jpeg_decode_batch_ex(int n, const void* const* jpeg, const size_t* 
 int uhdr_hip_jpeg_decode_ex(const void* jpeg, size_t jpeg_size, int decode_to, void* out, size_t out_capacity, uhdr_hip_image_t* desc,
                             int mem_space, void* stream, int flags);
 
+/* Scaled decode: libjpeg's scale_num / scale_denom = 1 / scale_denom.  The *_scaled calls are the *_ex calls plus `scale_denom`, one of
+ * 1, 2, 4, 8 (any other value: ERROR_UNSUPPORTED_FEATURE at call level); with scale_denom == 1 every status, byte and descriptor is
+ * the *_ex call's.  The image comes out ceil(width / scale_denom) x ceil(height / scale_denom), computed by libjpeg's reduced inverse
+ * DCTs (jidctred.c's 4x4 and 2x2, the 1x1 of the DC value) on the device, byte-identical to libjpeg-turbo's C arithmetic
+ * (JSIMD_FORCENONE; its SIMD routines differ on coefficients no encoder produces from 8-bit samples).  The size per component is
+ * libjpeg-turbo's (jdmaster.c): 8 / scale_denom, doubled for the chroma of a 4:2:0 file, which is thereby scaled up in the IDCT
+ * instead of being upsampled.  So a 4:2:0 file gives three planes of the same size, UHDR_HIP_PIX_FMT_YUV444 (and odd sizes are read:
+ * 4:2:0's even-size rule has no layout to apply to); 4:4:4, 4:2:2, 4:4:0 and single-plane files keep their layout, with the chroma
+ * extents of those formats applied to the scaled size.  Descriptors, size probes and capacities speak of the scaled image;
+ * DECODE_TO_YCBCR packs the planes as the *_ex call does, DECODE_TO_RGBA is libjpeg-turbo's RGBA of them (colour conversion for
+ * 4:4:4 results, fancy h2v1 / h1v2 upsampling for 4:2:2 / 4:4:0 -- replicated chroma at 1/8, where libjpeg has no fancy upsampling).  Statuses that depend on the file alone -- what `flags` admits,
+ * the 8192 limit on the file's own size, malformed data -- are the full-size call's, in its order.  Everything in front of the IDCT
+ * is the full-size decoder, so scaled and full-size files share a batch's launches.  Measured on one MI355X
+ * (profiles/r19_jpeg_scaled.txt), a 4K quality-95 4:2:0 file at 1, 1/2, 1/4, 1/8: planes into device memory 716 / 706 / 706 / 698 us (the
+ * entropy decode dominates), RGBA into host memory 1331 / 874 / 755 / 741 us; the full-size calls cost what they cost before. */
+int uhdr_hip_jpeg_decode_batch_scaled(int n, const void* const* jpeg, const size_t* jpeg_size, int decode_to, void* const* out,
+                                      const size_t* out_capacity, uhdr_hip_image_t* descs, int* status, int mem_space, void* stream,
+                                      int flags, int scale_denom);
+/* a batch of one file */
+int uhdr_hip_jpeg_decode_scaled(const void* jpeg, size_t jpeg_size, int decode_to, void* out, size_t out_capacity, uhdr_hip_image_t* desc,
+                                int mem_space, void* stream, int flags, int scale_denom);
+/* Host only: what a scaled decode of a width x height file gives.  hs x vs: the luma sampling factors (1 or 2 each, chroma 1x1);
+ * gray != 0: a single-plane file (hs, vs ignored).  *out_width, *out_height: the scaled extent; *pixel_format: the layout
+ * (UHDR_HIP_PIX_FMT_MONOCHROME / YUV444 / YUV422 / YUV440; YUV420 only at scale_denom 1); idct_size[c]: the inverse DCT's size for
+ * component c (0 for the chroma of a single-plane file).  Every output pointer is optional.  ERROR_UNSUPPORTED_FEATURE for another
+ * scale_denom or sampling, ERROR_UNSUPPORTED_WIDTH_HEIGHT for a size below 1. */
+int uhdr_hip_jpeg_scaled_geometry(int width, int height, int hs, int vs, int gray, int scale_denom, int* out_width, int* out_height,
+                                  int* pixel_format, int idct_size[3]);
+
 /* Host only, for tests that prove their route: the number of launches of the synchronisation kernel (k_jd_sync_multi<1>, four rounds
  * each) that the last device decode of the calling host thread enqueued up to the look at the flags that read "no change" -- a
  * multiple of the launches between two looks, not the number the file needed.  A call of several decode rounds, or a JPEG/R decode
@@ -739,6 +768,22 @@ int uhdr_hip_generate_gainmap_md_batch(int n, const uhdr_hip_image_t* yuv420_ima
 int uhdr_hip_jpegr_decode_md_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
                                    void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests,
                                    uhdr_hip_metadata_t* metadata, int* status, int apply_mode, int mem_space, void* stream, int flags);
+/* uhdr_hip_jpegr_decode_md_batch at 1 / scale_denom of every file's size (1, 2, 4, 8; any other value: ERROR_UNSUPPORTED_FEATURE at call
+ * level; 1: that call exactly).  The primary image is decoded as uhdr_hip_jpeg_decode_batch_scaled decodes it; dests[i], the size probe
+ * and dest_capacity speak of the scaled extent.  UHDR_HIP_OUTPUT_SDR is the scaled RGBA.  For the HDR formats the gain map follows
+ * the primary image: with f the file's map scale factor (the file must pass the full-size checks: width and height multiples of the
+ * map's, one ratio), f % scale_denom == 0 decodes the map at full size and applies it at factor f / scale_denom;
+ * scale_denom % f == 0 decodes the map at 1 / (scale_denom / f) and applies it at factor 1; any other pair is
+ * ERROR_UNSUPPORTED_MAP_SCALE_FACTOR for that file, answered from the two headers: behind the statuses of its container and its
+ * metadata, in front of the size probe.  The
+ * result is uhdr_hip_apply_gainmap_md_batch on the scaled planes and the (scaled) map, in every apply_mode that call accepts -- for a
+ * 4:2:0 primary the YUV444 planes of the scaled decode, through the per-pixel kernels.  The primary image and the map of one file may
+ * carry different denominators in the one decoder launch.  16 4K files to HDR_PQ, device memory: 3.25 ms at full size, 2.87 ms at 1/8
+ * (profiles/r19_jpeg_scaled.txt). */
+int uhdr_hip_jpegr_decode_scaled_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
+                                       void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests,
+                                       uhdr_hip_metadata_t* metadata, int* status, int apply_mode, int mem_space, void* stream, int flags,
+                                       int scale_denom);
 
 /* ---- packed RGBA inputs (no reference counterpart; current libultrahdr takes the same raw inputs) ------
  * Every encode-side call above takes a P010 HDR frame and planar 8-bit YUV 4:2:0.  The calls of this section take what the apply and

@@ -209,7 +209,9 @@ class JpegDecoderHelperHip {
  public:
   // DECODE_TO_YCBCR (what applyGainMap's caller asks for, jpegr.cpp:780-801): 4:2:0 -> Y, Cb, Cr planes; grayscale -> Y.
   // DECODE_TO_RGBA (the SDR rendition, jpegr.cpp:686-690): 4:2:0 -> RGBA8888 with libjpeg-turbo's arithmetic.
-  bool decompressImage(const void* image, int length, decode_mode_t decodeTo = DECODE_TO_YCBCR);
+  // scaleDenom 2, 4 or 8 (uhdr_hip_jpeg_decode_scaled): the image at ceil(size / scaleDenom) -- a 4:2:0 file as three planes of that
+  // size (Y, Cb, Cr: 4:4:4) or RGBA8888, a single-plane file as its plane; any other value but 1 fails.
+  bool decompressImage(const void* image, int length, decode_mode_t decodeTo = DECODE_TO_YCBCR, int scaleDenom = 1);
   void* getDecompressedImagePtr() { return mResultBuffer.data(); }
   size_t getDecompressedImageSize() { return mResultBuffer.size(); }
   size_t getDecompressedImageWidth() { return mWidth; }
@@ -315,6 +317,11 @@ class JpegRHip {
   // what current libultrahdr, cameras and editors write -- are decoded with the full gain-map formula, one- and three-component
   // maps alike (uhdr_hip_jpegr_decode_md_batch); files the reference reads give the bytes they gave.
   void setAnyGainMapMetadata(bool on) { mAnyGainMapMetadata = on; }
+  // 1 (default): decodeJPEGR as it is.  2, 4 or 8: the rendition at ceil(size / denominator), decoded at that size -- reduced inverse
+  // DCTs, the gain map at the factor (or the size) that follows (uhdr_hip_jpegr_decode_scaled_batch; it reads what
+  // setAnyGainMapMetadata(true) and setMultiChannelGainMap(true) read).  dest->data holds the scaled image; gainmap_image_ptr, if
+  // given, still receives the map at its full size.  Any other value: ERROR_ULTRAHDR_UNSUPPORTED_FEATURE from decodeJPEGR.
+  void setDecodeScaleDenom(int scale_denom) { mDecodeScaleDenom = scale_denom; }
   // false (default): the Annex K Huffman tables, as the reference writes them.  true: the API-0 and API-1 overloads of encodeJPEGR
   // write the primary image and the gain-map JPEG with Huffman tables of their own (uhdr_hip_jpegr_encode_batch_ex with
   // UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN): the same pixels in smaller files.  Combined with setGainMapScaleFactor, setMultiChannelGainMap,
@@ -336,6 +343,7 @@ class JpegRHip {
   int mToneMapOp = 0;
   float mHdrPeakNits = 0.0f;
   bool mDecodeAnySampling = false;
+  int mDecodeScaleDenom = 1;
   bool mMultiChannelGainMap = false;
   bool mAnyGainMapMetadata = false;
   bool mOptimizeHuffman = false;

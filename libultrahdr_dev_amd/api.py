@@ -29,6 +29,7 @@ ERROR_NO_IMAGES_FOUND, ERROR_MULTIPLE_EXIFS_RECEIVED = -20006, -20007
 MEM_HOST, MEM_DEVICE = 0, 1
 MEM_DEVICE_TO_HOST, MEM_HOST_TO_DEVICE = 2, 3   # uhdr_hip_jpeg_encode_batch: planes and outputs apart
 DECODE_TO_RGBA, DECODE_TO_YCBCR = 1, 2          # uhdr_hip_jpeg_decode_batch
+DECODE_SCALE_DENOMS = (1, 2, 4, 8)              # scale_denom of the *_scaled decodes: the image at ceil(size / scale_denom)
 DECODE_ANY_SAMPLING = 1                         # flags bit of the *_decode*_ex calls: also 4:4:4, 4:2:2 and 4:4:0 files
 APPLY_FAST, APPLY_EXACT, APPLY_LUT, APPLY_EXACT_UNFILTERED = 0, 1, 2, 3
 GENERATE_EXACT, GENERATE_LUT, GENERATE_UNFILTERED = 0, 1, 2
@@ -168,6 +169,14 @@ SIGNATURES = {
                                               C.POINTER(C.c_size_t), _IP, _MP, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p]),
     "uhdr_hip_jpeg_decode_batch_ex": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                                 _IP, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int]),
+    "uhdr_hip_jpeg_decode_batch_scaled": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.POINTER(C.c_void_p),
+                                                    C.POINTER(C.c_size_t), _IP, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "uhdr_hip_jpeg_decode_scaled": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, _IP, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "uhdr_hip_jpeg_scaled_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                                C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "uhdr_hip_jpegr_decode_scaled_batch": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_int, C.c_float, C.POINTER(C.c_void_p),
+                                                     C.POINTER(C.c_size_t), _IP, _MP, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                     C.c_int]),
     "uhdr_hip_jpeg_decode_last_sync_launches": (C.c_int, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "uhdr_hip_jpeg_decode_ex": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_size_t, _IP, C.c_int, C.c_void_p, C.c_int]),
     "uhdr_hip_jpegr_decode_ex": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p, C.c_size_t, _IP, _MP, C.c_int, C.c_int, C.c_void_p,
@@ -431,6 +440,17 @@ def apply_gainmap_packed(sdr_images, map_images, md, output_format, max_display_
     if rc != NO_ERROR:
         raise UhdrHipError("uhdr_hip_apply_gainmap_packed_batch -> %d" % rc)
     return list(dests)
+
+
+def jpeg_scaled_geometry(w, h, hs, vs, gray, scale_denom):
+    """uhdr_hip_jpeg_scaled_geometry (host only): (width, height, pixel format, [IDCT size per component]) of a decode at 1 / scale_denom
+    of a w x h file with luma sampling hs x vs (gray: one plane)"""
+    ow, oh, fmt = C.c_int(), C.c_int(), C.c_int()
+    idct = (C.c_int * 3)()
+    rc = load().uhdr_hip_jpeg_scaled_geometry(w, h, hs, vs, 1 if gray else 0, scale_denom, C.byref(ow), C.byref(oh), C.byref(fmt), idct)
+    if rc != NO_ERROR:
+        raise UhdrHipError("uhdr_hip_jpeg_scaled_geometry -> %d" % rc)
+    return ow.value, oh.value, fmt.value, list(idct)
 
 
 def tonemap_headroom(hdr_tf, gamma_max, peak_nits=0.0):

@@ -2383,13 +2383,16 @@ int parse_jpegr_file(const void* jpegr, size_t jpegr_size, int output_format, bo
 // What a decoded image looks like in memory: the w x h luma plane, then Cb and Cr of cw x ch samples each, cbytes apart.  4:2:0
 // keeps the reference's (w / 2) x (h / 2) planes luma / 4 bytes apart (even sizes; odd ones as before); the samplings only the
 // any-sampling decode parses get libjpeg's downsampled sizes, ceil(w / hs) x ceil(h / vs), packed.
-struct DecGeom { size_t cw, ch, cbytes; int fmt; };
+// An image decoded at 1 / info.scale (the *_scaled calls; 1 everywhere else) is the image jpeg::scaled_geometry describes: w x h luma of
+// the scaled extent and the sampling of the result, which for a 4:2:0 file at 1/2, 1/4, 1/8 is 4:4:4 -- its layout never 4:2:0's.
+struct DecGeom { size_t w, h; int hs, vs; size_t cw, ch, cbytes; int fmt; };
 DecGeom dec_geom(const jpeg::DecInfo& info) {
-  const size_t w = (size_t)info.w, h = (size_t)info.h;
-  if (info.gray) return DecGeom{0, 0, 0, UHDR_HIP_PIX_FMT_MONOCHROME};
-  if (info.hs == 2 && info.vs == 2) return DecGeom{w / 2, h / 2, w * h / 4, UHDR_HIP_PIX_FMT_YUV420};
-  const size_t cw = (w + info.hs - 1) / info.hs, ch = (h + info.vs - 1) / info.vs;
-  return DecGeom{cw, ch, cw * ch, info.hs == 2 ? UHDR_HIP_PIX_FMT_YUV422 : info.vs == 2 ? UHDR_HIP_PIX_FMT_YUV440 : UHDR_HIP_PIX_FMT_YUV444};
+  const jpeg::ScaledGeom sg = jpeg::scaled_geometry(info.w, info.h, info.hs, info.vs, info.gray != 0, info.scale);
+  const size_t w = (size_t)sg.w, h = (size_t)sg.h;
+  if (info.gray) return DecGeom{w, h, 1, 1, 0, 0, 0, UHDR_HIP_PIX_FMT_MONOCHROME};
+  if (sg.hs == 2 && sg.vs == 2) return DecGeom{w, h, 2, 2, w / 2, h / 2, w * h / 4, UHDR_HIP_PIX_FMT_YUV420};
+  const size_t cw = (w + sg.hs - 1) / sg.hs, ch = (h + sg.vs - 1) / sg.vs;
+  return DecGeom{w, h, sg.hs, sg.vs, cw, ch, cw * ch, sg.hs == 2 ? UHDR_HIP_PIX_FMT_YUV422 : sg.vs == 2 ? UHDR_HIP_PIX_FMT_YUV440 : UHDR_HIP_PIX_FMT_YUV444};
 }
 // the three planes of a decode into the packed buffer at p
 void dec_planes(const jpeg::DecInfo& info, uint8_t* p, jpeg::DecPlane out[3]);
@@ -2399,10 +2402,10 @@ struct RgbaBatches {
   YccxRgbaBatch bx; int nx = 0;
   uint8_t* add(const jpeg::DecInfo& info, const uint8_t* ycc, uint8_t* rgba) {
     const DecGeom g = dec_geom(info);
-    const size_t luma = (size_t)info.w * (size_t)info.h;
-    const YccRgbaImage im{ycc, ycc + luma, ycc + luma + g.cbytes, rgba, (uint32_t)info.w, (uint32_t)info.h, (uint32_t)info.w, (uint32_t)g.cw};
+    const size_t luma = g.w * g.h;
+    const YccRgbaImage im{ycc, ycc + luma, ycc + luma + g.cbytes, rgba, (uint32_t)g.w, (uint32_t)g.h, (uint32_t)g.w, (uint32_t)g.cw};
     if (g.fmt == UHDR_HIP_PIX_FMT_YUV420) b420.img[n420++] = im;
-    else bx.img[nx++] = YccxRgbaImage{im, (uint32_t)info.hs, (uint32_t)info.vs};
+    else bx.img[nx++] = YccxRgbaImage{im, (uint32_t)g.hs, (uint32_t)g.vs, info.scale == 8 ? 1u : 0u};   // (at 1/8 libjpeg replicates the chroma)
     return rgba;
   }
   int size() const { return n420 + nx; }
@@ -2420,16 +2423,17 @@ struct RgbaBatches {
 // status returned before that point leaves *desc zeroed (the RGBA call: untouched), and a host allocation failure inside the parser
 // (std::bad_alloc, -3: a progressive file's coefficient array) is reported as UNKNOWN_ERROR so that it cannot be taken for it.
 int jpeg_decode_host(const void* jpeg, size_t jpeg_size, bool rgba, bool any_sampling, void* out, size_t out_capacity, uhdr_hip_image_t* desc,
-                     jpeg::DecInfo* info, size_t* need) {
+                     jpeg::DecInfo* info, size_t* need, int scale_denom = 1) {
   if (jpeg == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
   if (!rgba) memset(desc, 0, sizeof(*desc));
   const int prc = jpeg::parse_header(static_cast<const uint8_t*>(jpeg), jpeg_size, info, any_sampling);
   if (prc == -3) return UHDR_HIP_UNKNOWN_ERROR;
   if (prc == -2) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (prc != 0 || info->w <= 0 || info->h <= 0) return UHDR_HIP_UNKNOWN_ERROR;
-  const size_t w = (size_t)info->w, h = (size_t)info->h, luma = w * h;
-  if (w > 8192 || h > 8192) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;   // kMaxWidth / kMaxHeight, jpegdecoderhelper.h:42-43
+  if (info->w > 8192 || info->h > 8192) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;   // kMaxWidth / kMaxHeight, jpegdecoderhelper.h:42-43
+  info->scale = scale_denom;   // from here on the image is the scaled one: extent, layout, bytes
   const DecGeom g = dec_geom(*info);
+  const size_t w = g.w, h = g.h, luma = w * h;
   if (!rgba) {
     *need = luma + 2 * g.cbytes;
     desc->data = out;
@@ -2463,12 +2467,12 @@ jpeg::DecPlane dec_plane(uint8_t* p, size_t w, size_t h) {
   q.aligned8 = (reinterpret_cast<uintptr_t>(p) % 8 == 0 && w % 8 == 0) ? 1 : 0;
   return q;
 }
-size_t dec_ycc_bytes(const jpeg::DecInfo& info) { return (size_t)info.w * (size_t)info.h + 2 * dec_geom(info).cbytes; }
+size_t dec_ycc_bytes(const jpeg::DecInfo& info) { const DecGeom g = dec_geom(info); return g.w * g.h + 2 * g.cbytes; }
 void dec_planes(const jpeg::DecInfo& info, uint8_t* p, jpeg::DecPlane out[3]) {
   const DecGeom g = dec_geom(info);
-  const size_t luma = (size_t)info.w * (size_t)info.h;
+  const size_t luma = g.w * g.h;
   memset(out, 0, 3 * sizeof(jpeg::DecPlane));
-  out[0] = dec_plane(p, (size_t)info.w, (size_t)info.h);
+  out[0] = dec_plane(p, g.w, g.h);
   if (!info.gray) { out[1] = dec_plane(p + luma, g.cw, g.ch); out[2] = dec_plane(p + luma + g.cbytes, g.cw, g.ch); }
 }
 // what one file holds of its round
@@ -2560,6 +2564,15 @@ int uhdr_hip_jpeg_decode_batch(int n, const void* const* jpeg, const size_t* jpe
 // the same with flags: UHDR_HIP_DECODE_ANY_SAMPLING also reads 4:4:4, 4:2:2 and 4:4:0 files (descs[i].pixelFormat names the layout)
 int uhdr_hip_jpeg_decode_batch_ex(int n, const void* const* jpeg, const size_t* jpeg_size, int decode_to, void* const* out, const size_t* out_capacity,
                                   uhdr_hip_image_t* descs, int* status, int mem_space, void* stream, int flags) {
+  return uhdr_hip_jpeg_decode_batch_scaled(n, jpeg, jpeg_size, decode_to, out, out_capacity, descs, status, mem_space, stream, flags, 1);
+}
+
+// the same at 1 / scale_denom of every file's size (libjpeg's scale_num / scale_denom = 1 / 2, 1 / 4, 1 / 8): the reduced IDCTs of
+// k_jd_idct_scaled_multi behind the shared entropy decode, the existing conversions on the scaled planes.  scale_denom 1: the call above
+int uhdr_hip_jpeg_decode_batch_scaled(int n, const void* const* jpeg, const size_t* jpeg_size, int decode_to, void* const* out,
+                                      const size_t* out_capacity, uhdr_hip_image_t* descs, int* status, int mem_space, void* stream, int flags,
+                                      int scale_denom) {
+  if (scale_denom != 1 && scale_denom != 2 && scale_denom != 4 && scale_denom != 8) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   const bool any_sampling = (flags & UHDR_HIP_DECODE_ANY_SAMPLING) != 0;
   if (n < 0 || (n > 0 && (jpeg == nullptr || jpeg_size == nullptr || descs == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
@@ -2573,7 +2586,7 @@ int uhdr_hip_jpeg_decode_batch_ex(int n, const void* const* jpeg, const size_t* 
       void* o = out != nullptr ? out[i] : nullptr;
       const size_t cap = out != nullptr && out_capacity != nullptr ? out_capacity[i] : 0;
       try {
-        st_[i] = jpeg_decode_host(jpeg[i], jpeg_size[i], rgba, any_sampling, o, cap, &descs[i], &info[i], &need[i]);
+        st_[i] = jpeg_decode_host(jpeg[i], jpeg_size[i], rgba, any_sampling, o, cap, &descs[i], &info[i], &need[i], scale_denom);
       } catch (const std::bad_alloc&) {
         st_[i] = UHDR_HIP_UNKNOWN_ERROR;
       }
@@ -2625,6 +2638,32 @@ int uhdr_hip_jpeg_decode_ex(const void* jpeg, size_t jpeg_size, int decode_to, v
   return uhdr_hip_jpeg_decode_batch_ex(1, &jpeg, &jpeg_size, decode_to, &out, &out_capacity, desc, nullptr, single_mem_space(mem_space), stream, flags);
 }
 
+int uhdr_hip_jpeg_decode_scaled(const void* jpeg, size_t jpeg_size, int decode_to, void* out, size_t out_capacity, uhdr_hip_image_t* desc, int mem_space,
+                                void* stream, int flags, int scale_denom) {
+  if (scale_denom != 1 && scale_denom != 2 && scale_denom != 4 && scale_denom != 8) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (jpeg == nullptr || desc == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  return uhdr_hip_jpeg_decode_batch_scaled(1, &jpeg, &jpeg_size, decode_to, &out, &out_capacity, desc, nullptr, single_mem_space(mem_space), stream, flags,
+                                           scale_denom);
+}
+
+// host only: what a decode at 1 / scale_denom of a width x height file with luma sampling hs x vs (gray: one plane) gives
+int uhdr_hip_jpeg_scaled_geometry(int width, int height, int hs, int vs, int gray, int scale_denom, int* out_width, int* out_height, int* pixel_format,
+                                  int idct_size[3]) {
+  if (scale_denom != 1 && scale_denom != 2 && scale_denom != 4 && scale_denom != 8) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (width <= 0 || height <= 0) return UHDR_HIP_ERROR_UNSUPPORTED_WIDTH_HEIGHT;
+  if (!gray && !((hs == 1 || hs == 2) && (vs == 1 || vs == 2))) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  jpeg::DecInfo info;
+  info.w = width; info.h = height; info.hs = gray ? 1 : hs; info.vs = gray ? 1 : vs; info.gray = gray ? 1 : 0; info.scale = scale_denom;
+  const DecGeom g = dec_geom(info);
+  const jpeg::ScaledGeom sg = jpeg::scaled_geometry(width, height, info.hs, info.vs, gray != 0, scale_denom);
+  if (out_width != nullptr) *out_width = (int)g.w;
+  if (out_height != nullptr) *out_height = (int)g.h;
+  if (pixel_format != nullptr) *pixel_format = g.fmt;
+  if (idct_size != nullptr) { idct_size[0] = sg.idct[0]; idct_size[1] = gray ? 0 : sg.idct[1]; idct_size[2] = gray ? 0 : sg.idct[2]; }
+  return UHDR_HIP_NO_ERROR;
+}
+
 // JpegR::decodeJPEGR (jpegr.cpp:655-822) for n files at once.  A JPEG decode on the device is latency-bound (tens of synchronisation
 // rounds of one lane's work each, uhdr_jpeg_dec.hip), so all images of the call share every kernel launch (blockIdx.y = image) and
 // their rounds run side by side.
@@ -2642,7 +2681,9 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
 // uhdr_hip_apply_gainmap_md_batch instead of being refused.
 static int jpegr_decode_files(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
                               void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
-                              int* status, int apply_mode, int mem_space, void* stream, int flags, bool rgb_maps, bool any_md = false) {
+                              int* status, int apply_mode, int mem_space, void* stream, int flags, bool rgb_maps, bool any_md = false,
+                              int scale_denom = 1) {
+  if (scale_denom != 1 && scale_denom != 2 && scale_denom != 4 && scale_denom != 8) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   const bool any_sampling = (flags & UHDR_HIP_DECODE_ANY_SAMPLING) != 0;
   if (n < 0 || (n > 0 && (jpegr == nullptr || jpegr_size == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
@@ -2661,7 +2702,26 @@ static int jpegr_decode_files(int n, const void* const* jpegr, const size_t* jpe
   for (int i = 0; i < n; ++i) {
     if (st_[i] != UHDR_HIP_NO_ERROR) continue;
     if (metadata != nullptr) metadata[i] = files[i].md;
-    dests[i].width = (size_t)files[i].info[0].w; dests[i].height = (size_t)files[i].info[0].h; dests[i].colorGamut = files[i].gamut;
+    if (scale_denom != 1) {
+      // the map's denominator.  With f = W / MW (W = f MW, H = f MH): f % s == 0 leaves the map whole, ceil(W / s) = (f / s) MW; s % f == 0
+      // takes it to 1 / (s / f), ceil(W / s) = ceil(MW / (s / f)): an exact ratio either way
+      jpeg::DecInfo& pi = files[i].info[0];
+      jpeg::DecInfo& gi = files[i].info[1];
+      pi.scale = scale_denom;
+      if (output_format != UHDR_HIP_OUTPUT_SDR) {
+        const int f = gi.w > 0 && gi.h > 0 && pi.w % gi.w == 0 && pi.h % gi.h == 0 && (size_t)pi.w * (size_t)gi.h == (size_t)pi.h * (size_t)gi.w ? pi.w / gi.w : 0;
+        if (f != 0 && f % scale_denom == 0) gi.scale = 1;
+        else if (f != 0 && scale_denom % f == 0) gi.scale = scale_denom / f;
+        else {   // the map cannot follow its primary image: known from the two headers, so the file stops here, in front of its size probe
+          // (the apply call's metadata checks stand in front of its scale-factor checks)
+          const int mrc = validate_md(&files[i].md);
+          st_[i] = mrc != UHDR_HIP_NO_ERROR ? mrc : UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
+          continue;
+        }
+      }
+    }
+    const DecGeom og = dec_geom(files[i].info[0]);
+    dests[i].width = og.w; dests[i].height = og.h; dests[i].colorGamut = files[i].gamut;
     out_bytes[i] = dests[i].width * dests[i].height * apply_bpp(output_format);
     if (dest_data == nullptr || dest_capacity == nullptr || dest_data[i] == nullptr || dest_capacity[i] < out_bytes[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
     ++live;
@@ -2703,7 +2763,7 @@ static int jpegr_decode_files(int n, const void* const* jpegr, const size_t* jpe
     }
     if (host && (rc = pool_reserve(st, 5 * (size_t)i + 4, out_bytes[i])) != 0) return rc;
     // a three-component map as RGBA (slots behind the batch scratch at 5 n)
-    if (rgb_maps && !sdr && !f.info[1].gray && (rc = pool_reserve(st, 5 * (size_t)n + 1 + (size_t)i, (size_t)f.info[1].w * (size_t)f.info[1].h * 4)) != 0) return rc;
+    if (rgb_maps && !sdr && !f.info[1].gray && (rc = pool_reserve(st, 5 * (size_t)n + 1 + (size_t)i, dec_geom(f.info[1]).w * dec_geom(f.info[1]).h * 4)) != 0) return rc;
   }
   const int nimg = (int)infos.size();
   std::vector<jpeg::DecPlane (*)[3]> pl((size_t)nimg);
@@ -2728,7 +2788,7 @@ static int jpegr_decode_files(int n, const void* const* jpegr, const size_t* jpe
     for (int i = 0; i < n; ++i) {
       if (st_[i] != UHDR_HIP_NO_ERROR || files[i].info[1].gray) continue;
       const jpeg::DecInfo& gi = files[i].info[1];
-      if (dec_geom(gi).fmt == UHDR_HIP_PIX_FMT_YUV420 && ((gi.w | gi.h) & 1)) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }
+      if (dec_geom(gi).fmt == UHDR_HIP_PIX_FMT_YUV420 && ((gi.w | gi.h) & 1)) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }   // (full size only: a scaled map is never 4:2:0)
       mb.add(gi, static_cast<const uint8_t*>(st->pool[5 * (size_t)i + 3]), static_cast<uint8_t*>(st->pool[5 * (size_t)n + 1 + (size_t)i]));
       if (mb.size() == kRgbaChunk) HIP_TRY(mb.launch(s));
     }
@@ -2751,8 +2811,8 @@ static int jpegr_decode_files(int n, const void* const* jpegr, const size_t* jpe
     if (st_[i] != UHDR_HIP_NO_ERROR) continue;
     const JpegrFile& f = files[i];
     if (sdr) {   // libjpeg-turbo's DECODE_TO_RGBA on the planes just decoded (k_ycc420_rgba_batch)
-      const uint32_t w = (uint32_t)f.info[0].w, h = (uint32_t)f.info[0].h;
-      if (dec_geom(f.info[0]).fmt == UHDR_HIP_PIX_FMT_YUV420 && ((w | h) & 1)) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }
+      const DecGeom sg = dec_geom(f.info[0]);
+      if (sg.fmt == UHDR_HIP_PIX_FMT_YUV420 && ((sg.w | sg.h) & 1)) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }
       const uint8_t* yp = static_cast<const uint8_t*>(st->pool[5 * (size_t)i + 2]);
       uint8_t* out = static_cast<uint8_t*>(host ? st->pool[5 * (size_t)i + 4] : dest_data[i]);
       rgb_file[nrgb] = i;
@@ -2761,13 +2821,13 @@ static int jpegr_decode_files(int n, const void* const* jpegr, const size_t* jpe
       dests[i].data = dest_data[i];
       continue;
     }
-    const size_t w = (size_t)f.info[0].w, h = (size_t)f.info[0].h, gw = (size_t)f.info[1].w, gh = (size_t)f.info[1].h;
+    const DecGeom pg = dec_geom(f.info[0]), mg = dec_geom(f.info[1]);   // (a 4:2:0 primary: chroma_stride w / 2, Cr behind (w / 2) * (h / 2) bytes, as ever)
+    const size_t w = pg.w, h = pg.h, gw = mg.w, gh = mg.h;
     uhdr_hip_image_t ydesc, gimg;
     memset(&ydesc, 0, sizeof(ydesc));
     memset(&gimg, 0, sizeof(gimg));
     uint8_t* yp = static_cast<uint8_t*>(st->pool[5 * (size_t)i + 2]);
     ydesc.data = yp; ydesc.width = w; ydesc.height = h; ydesc.luma_stride = w; ydesc.colorGamut = f.gamut;
-    const DecGeom pg = dec_geom(f.info[0]);   // (a 4:2:0 primary: chroma_stride w / 2, Cr behind (w / 2) * (h / 2) bytes, as ever)
     ydesc.chroma_data = yp + w * h; ydesc.chroma_stride = pg.cw; ydesc.pixelFormat = pg.fmt;
     gimg.data = st->pool[5 * (size_t)i + 3]; gimg.width = gw; gimg.height = gh; gimg.luma_stride = gw; gimg.colorGamut = UHDR_HIP_CG_UNSPECIFIED;
     gimg.pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
@@ -2813,6 +2873,13 @@ int uhdr_hip_jpegr_decode_md_batch(int n, const void* const* jpegr, const size_t
                                    int* status, int apply_mode, int mem_space, void* stream, int flags) {
   return jpegr_decode_files(n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode,
                             mem_space, stream, flags, true, true);
+}
+
+int uhdr_hip_jpegr_decode_scaled_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
+                                       void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
+                                       int* status, int apply_mode, int mem_space, void* stream, int flags, int scale_denom) {
+  return jpegr_decode_files(n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode,
+                            mem_space, stream, flags, true, true, scale_denom);
 }
 
 int uhdr_hip_jpegr_decode(const void* jpegr, size_t jpegr_size, int output_format, float max_display_boost, void* dest_data,

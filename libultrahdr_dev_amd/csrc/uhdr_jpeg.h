@@ -148,6 +148,9 @@ struct DecInfo {
   // scan_offset = the position of EOI.  The device runs its DC prefix sum and the IDCT.
   bool progressive = false;
   std::vector<int16_t> coef;
+  // set by the caller, not by the parsers: the image is decoded at 1 / scale of its size (1, 2, 4, 8; libjpeg's scale_denom) into
+  // planes of scaled_geometry's sizes.  Everything in front of the IDCT works on the file's own w x h
+  int scale = 1;
 };
 struct DecLayout {
   size_t src, raw, lut, adv, st_a, st_b, dirty_a, dirty_b, coef;
@@ -174,6 +177,19 @@ struct DecJob {
   DecPlane plane[3];
   uint16_t quant[3][64];
 };
+// What a decode at 1 / scale gives (jdmaster.c's jpeg_calc_output_dimensions, libjpeg-turbo's rule): ceil(w / scale) x ceil(h / scale)
+// luma; idct[c]: the IDCT size of component c, 8 / scale, doubled for the chroma of 4:2:0 -- which is thereby scaled up in the IDCT, so
+// hs x vs, the luma sampling of the RESULT, is 1 x 1 for such a file at scale > 1 and the file's own otherwise
+struct ScaledGeom { int w, h, hs, vs, idct[3]; };
+void scaled_idct_sizes(int hs, int vs, bool gray, int scale, int size[3]);
+inline ScaledGeom scaled_geometry(int w, int h, int hs, int vs, bool gray, int scale) {
+  ScaledGeom g;
+  g.w = (w + scale - 1) / scale; g.h = (h + scale - 1) / scale;
+  scaled_idct_sizes(hs, vs, gray, scale, g.idct);
+  const int n = 8 / scale;
+  g.hs = gray ? 1 : hs * n / g.idct[1]; g.vs = gray ? 1 : vs * n / g.idct[1];
+  return g;
+}
 // 0 ok, -1 malformed, -2 outside what this decoder (or the reference: sampling) supports.  any_sampling false: three components
 // must be 4:2:0, as in the reference; true: luma 1x1, 2x1, 1x2 or 2x2 over 1x1 chroma (DecInfo::hs, vs)
 int parse_header(const uint8_t* jpg, size_t n, DecInfo* info, bool any_sampling = false);

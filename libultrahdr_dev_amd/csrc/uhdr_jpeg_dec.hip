@@ -625,19 +625,8 @@ __host__ __device__ __forceinline__ uint32_t mcu_of(uint32_t b, uint32_t bpm) {
   return bpm == 6u ? q6 : (bpm == 4u ? q4 : (bpm == 3u ? q3 : b));
 }
 
-__device__ __forceinline__ void idct_body(const DecJob& j, const Dc3* dc) {
-  const uint32_t b = blockIdx.x * 128u + threadIdx.x;
-  if (b >= j.nblk) return;
-  int comp, br, bc;
-  if (j.gray) { comp = 0; br = (int)(b / j.mcus_x); bc = (int)(b - (uint32_t)br * j.mcus_x); }
-  else {
-    // luma block k of MCU (mr, mc) is block (mr * vs + k / hs, mc * hs + k % hs) of its plane (hs, vs: 1 or 2), chroma is (mr, mc)
-    const uint32_t mcu = mcu_of(b, j.bpm), k = b - mcu * j.bpm;
-    const int mr = (int)(mcu / j.mcus_x), mc = (int)(mcu - (uint32_t)mr * j.mcus_x);
-    if (k < j.chroma_at) { comp = 0; br = (int)j.vs * mr + (int)(k >> (j.hs - 1u)); bc = (int)j.hs * mc + (int)(k & (j.hs - 1u)); }
-    else { comp = (int)(k - j.chroma_at) + 1; br = mr; bc = mc; }
-  }
-  const DecPlane& pl = j.plane[comp];
+// block b of component comp, block (br, bc) of the plane pl: dequantisation, the 8x8 IDCT, the stores
+__device__ __forceinline__ void idct8_block(const DecJob& j, const DecPlane& pl, const Dc3* dc, uint32_t b, int comp, int br, int bc) {
   if (br * 8 >= pl.h || bc * 8 >= pl.w) return;      // a dummy block of the encoder: nothing of it is inside the image
   const int dc_value = (int)(int16_t)dc[b].v[comp];  // the running sum of the component's differences (the coefficient array holds the difference)
   const uint16_t* q = j.quant[comp];                 // zigzag order
@@ -686,6 +675,231 @@ __device__ __forceinline__ void idct_body(const DecJob& j, const Dc3* dc) {
     else if (br * 8 + r < pl.h)
       for (int c = 0; c < 8; ++c)
         if (bc * 8 + c < pl.w) dst[(size_t)r * pl.stride + c] = (uint8_t)(o[c >> 2] >> (8 * (c & 3)));
+  }
+}
+
+__device__ __forceinline__ void idct_body(const DecJob& j, const Dc3* dc) {
+  const uint32_t b = blockIdx.x * 128u + threadIdx.x;
+  if (b >= j.nblk) return;
+  int comp, br, bc;
+  if (j.gray) { comp = 0; br = (int)(b / j.mcus_x); bc = (int)(b - (uint32_t)br * j.mcus_x); }
+  else {
+    // luma block k of MCU (mr, mc) is block (mr * vs + k / hs, mc * hs + k % hs) of its plane (hs, vs: 1 or 2), chroma is (mr, mc)
+    const uint32_t mcu = mcu_of(b, j.bpm), k = b - mcu * j.bpm;
+    const int mr = (int)(mcu / j.mcus_x), mc = (int)(mcu - (uint32_t)mr * j.mcus_x);
+    if (k < j.chroma_at) { comp = 0; br = (int)j.vs * mr + (int)(k >> (j.hs - 1u)); bc = (int)j.hs * mc + (int)(k & (j.hs - 1u)); }
+    else { comp = (int)(k - j.chroma_at) + 1; br = mr; bc = mc; }
+  }
+  idct8_block(j, j.plane[comp], dc, b, comp, br, bc);
+}
+
+// ---- reduced-size IDCTs: libjpeg's scale_denom 2, 4, 8 (jidctred.c's 4x4 and 2x2, jidctint.c's 1x1) ----------------------------
+// A block becomes N x N samples (N = 4, 2, 1).  Like the 8x8 passes, libjpeg computes these in 64 bits over an int workspace and hands
+// range_limit bits of the second pass's descaled sums.  With every dequantised coefficient a column uses at most M in magnitude:
+//   4x4  pass 1: an output is t0 +- t2 +- o.  Absolute weights: t0 2^14, t2 15137 + 6270, o0 1730 + 11893 + 17799 + 8697 = 40119,
+//        o2 4176 + 4926 + 7373 + 20995 = 37470; the largest output, t0 - t2 +- o0, weighs 16384 + 21407 + 40119 = 77910.
+//        77910 M + 2^11 < 2^31 for M <= 27563.  The workspace holds at most (77910 M + 2^11) >> 12 < 2^23 for a legal file's
+//        M <= 1023 x 255: 32 bits.
+//        pass 2: its sums pass 2^32, but the sample is bits 19..28 of sum + 2^18 (DS(., 19) & 1023): exact modulo 2^32.
+//   2x2  pass 1: t +- o with weights 2^15 and 5906 + 6967 + 10426 + 29692 = 52991: 85759 M + 2^12 < 2^31 for M <= 25041; workspace
+//        (85759 M + 2^12) >> 13 < 2^22.  pass 2: bits 20..29 of sum + 2^19: exact modulo 2^32.
+//   1x1  DS(d00, 3) of one product of two 16-bit numbers: 32 bits.
+// So a block with a used dequantised magnitude of 2^14 or more (one bound for both sizes, below either limit; an encoder's blocks of
+// 8-bit samples stay under it) takes pass 1 in 64 bits, the others in 32, and pass 2 runs in unsigned 32-bit arithmetic throughout.
+// (x << n of the formulas is x * 2^n here: defined for negative x, the same bits.)
+template <int PASS, typename T>
+__device__ __forceinline__ void idct4(int (&d)[64], int base, int stride) {   // jidctred.c, jpeg_idct_4x4; writes elements 0..3
+  constexpr int sh = PASS == 0 ? 12 : 19;
+  const T t0 = (T)d[base] * (T)16384;
+  const T t2 = (T)d[base + 2 * stride] * (T)15137 + (T)d[base + 6 * stride] * (T)(-6270);
+  const T z1 = (T)d[base + 7 * stride], z2 = (T)d[base + 5 * stride], z3 = (T)d[base + 3 * stride], z4 = (T)d[base + stride];
+  const T o0 = z1 * (T)(-1730) + z2 * (T)11893 + z3 * (T)(-17799) + z4 * (T)8697;
+  const T o2 = z1 * (T)(-4176) + z2 * (T)(-4926) + z3 * (T)7373 + z4 * (T)20995;
+  d[base] = (int)dscale<T>(t0 + t2 + o2, sh); d[base + 3 * stride] = (int)dscale<T>(t0 + t2 - o2, sh);
+  d[base + stride] = (int)dscale<T>(t0 - t2 + o0, sh); d[base + 2 * stride] = (int)dscale<T>(t0 - t2 - o0, sh);
+}
+template <int PASS, typename T>
+__device__ __forceinline__ void idct2(int (&d)[64], int base, int stride) {   // jidctred.c, jpeg_idct_2x2; writes elements 0, 1
+  constexpr int sh = PASS == 0 ? 13 : 20;
+  const T t = (T)d[base] * (T)32768;
+  const T o = (T)d[base + 7 * stride] * (T)(-5906) + (T)d[base + 5 * stride] * (T)6967 + (T)d[base + 3 * stride] * (T)(-10426) +
+              (T)d[base + stride] * (T)29692;
+  d[base] = (int)dscale<T>(t + o, sh); d[base + stride] = (int)dscale<T>(t - o, sh);
+}
+// range_limit[x & 1023] as in idct8_block
+__device__ __forceinline__ uint32_t range_limit(int v) {
+  int x = ((int)((uint32_t)v << 22) >> 22) + 128;
+  return (uint32_t)(x < 0 ? 0 : (x > 255 ? 255 : x));
+}
+// a coefficient's row and column take part in an N x N IDCT: 4x4 leaves out row 4 and column 4, 2x2 every even one but 0
+template <int N>
+__host__ __device__ constexpr bool red_uses(int i) { return N == 4 ? i != 4 : (i == 0 || (i & 1)); }
+
+// Block b as N x N samples (N = 4, 2, 1) at (br * N, bc * N) of the plane.  pl.aligned8 here: the plane's address and stride are
+// multiples of N, so a whole block's rows go out as one N-byte store each; a clipped block or an unaligned plane stores bytes.
+// The coefficients are read as the whole 128-byte block (one cache line: leaving dwords out would save no traffic), and only the 49
+// (4x4) or 25 (2x2) that take part are dequantised; the 1x1 reads the DC scan's value alone.
+template <int N>
+__device__ __forceinline__ void idct_reduced_block(const DecJob& j, const DecPlane& pl, const Dc3* dc, uint32_t b, int comp, int br, int bc) {
+  if (br * N >= pl.h || bc * N >= pl.w) return;      // a dummy block of the encoder
+  const int dc_value = (int)(int16_t)dc[b].v[comp];
+  const uint16_t* q = j.quant[comp];                 // zigzag order
+  uint8_t* dst = pl.p + (size_t)(br * N) * pl.stride + bc * N;
+  if (N == 1) { dst[0] = (uint8_t)range_limit(dscale<int>(dc_value * (int)q[0], 3)); return; }
+  constexpr uint8_t nat[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                               41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                               30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+  int d[64];
+  const uint4* src = reinterpret_cast<const uint4*>(j.coef + (size_t)b * 64u);
+  int dmax = 0, dmin = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const uint4 v = src[k];
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+      const int z = 8 * k + m, at = nat[z];
+      if (z == 0 || !red_uses<N>(at >> 3) || !red_uses<N>(at & 7)) continue;
+      const uint32_t half = (m & 1) ? w[m >> 1] >> 16 : w[m >> 1] & 0xffffu;
+      d[at] = (int)(int16_t)half * (int)q[z];
+      dmax = max(dmax, d[at]); dmin = min(dmin, d[at]);
+    }
+  }
+  d[0] = dc_value * (int)q[0];
+  dmax = max(dmax, d[0]); dmin = min(dmin, d[0]);
+  const bool wide = dmax >= 16384 || dmin <= -16384;
+  const bool whole = br * N + N <= pl.h && bc * N + N <= pl.w && pl.aligned8;
+  if (N == 4) {
+    if (wide) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) if (c != 4) idct4<0, int64_t>(d, c, 8);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) if (c != 4) idct4<0, int>(d, c, 8);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      idct4<1, uint32_t>(d, r * 8, 1);
+      const uint32_t o = range_limit(d[r * 8]) | (range_limit(d[r * 8 + 1]) << 8) | (range_limit(d[r * 8 + 2]) << 16) | (range_limit(d[r * 8 + 3]) << 24);
+      if (whole) *reinterpret_cast<uint32_t*>(dst + (size_t)r * pl.stride) = o;
+      else if (br * 4 + r < pl.h)
+        for (int c = 0; c < 4; ++c)
+          if (bc * 4 + c < pl.w) dst[(size_t)r * pl.stride + c] = (uint8_t)(o >> (8 * c));
+    }
+  } else {
+    if (wide) {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) if (red_uses<2>(c)) idct2<0, int64_t>(d, c, 8);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 8; ++c) if (red_uses<2>(c)) idct2<0, int>(d, c, 8);
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      idct2<1, uint32_t>(d, r * 8, 1);
+      const uint32_t o = range_limit(d[r * 8]) | (range_limit(d[r * 8 + 1]) << 8);
+      if (whole) *reinterpret_cast<uint16_t*>(dst + (size_t)r * pl.stride) = (uint16_t)o;
+      else if (br * 2 + r < pl.h)
+        for (int c = 0; c < 2; ++c)
+          if (bc * 2 + c < pl.w) dst[(size_t)r * pl.stride + c] = (uint8_t)(o >> (8 * c));
+    }
+  }
+}
+
+// One image of a scaled decode.  Every component has a range of the grid of its own, [0, wg_luma) for Y and wg_chroma each for Cb and
+// Cr, so a wave holds blocks of one component and with them of one IDCT size: the choice among the sizes is wave-uniform.  (In MCU
+// order a wave of a 4:2:0 image at 1/2 would mix 4x4 luma with 8x8 chroma blocks and pay for both.)
+struct DecScaledJob {
+  uint32_t img;                  // index into the batch's jobs
+  uint32_t wg_luma, wg_chroma;   // workgroups of 128 blocks (of kCoopBlocks where the component's size is 8); wg_chroma 0: a single plane
+  uint32_t size[3];              // IDCT size per component: 1, 2, 4 or 8
+  DecPlane plane[3];             // the scaled planes (aligned8: see idct_reduced_block)
+};
+// The 8x8 IDCT of a chroma block of a 4:2:0 image at 1/2, eight lanes to a block: idct8_block's arithmetic (the same idct8 calls on the
+// same values, so the same bytes), but one thread per block holds the block's 64 values in registers and costs 167 VGPRs, which is
+// outside the bar for this kernel.  Here lane l of a block dequantises coefficients 8 l .. 8 l + 7 into the block's tile in LDS, takes
+// column l through pass 1 and row l through pass 2, and stores the row's 8 bytes.  The 64-bit choice is per column, which is what
+// the bound above idct8 is stated for.  Rows of a tile are 9 words apart and tiles 73: a column's and a row's eight lanes, and the
+// eight blocks of a wave, spread over the banks.
+constexpr uint32_t kCoopBlocks = 16;   // blocks per workgroup of 128
+__device__ __forceinline__ void idct8_coop(const DecJob& j, const DecPlane& pl, const Dc3* dc, int comp, uint32_t x, uint32_t nmcu) {
+  __shared__ int s_d[kCoopBlocks][73];
+  static constexpr uint8_t nat[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                      41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                      30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+  const uint32_t lb = threadIdx.x >> 3, l = threadIdx.x & 7u;
+  const uint32_t mcu = x * kCoopBlocks + lb;
+  const int br = (int)(mcu / j.mcus_x), bc = (int)(mcu - (uint32_t)br * j.mcus_x);
+  const bool live = mcu < nmcu && br * 8 < pl.h && bc * 8 < pl.w;   // (not a dummy block); every lane reaches both barriers
+  int* tile = s_d[lb];
+  if (live) {
+    const uint32_t b = mcu * j.bpm + j.chroma_at + (uint32_t)(comp - 1);
+    const uint16_t* q = j.quant[comp] + 8u * l;   // zigzag order
+    const uint4 v = reinterpret_cast<const uint4*>(j.coef + (size_t)b * 64u)[l];
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+      const uint32_t half = (m & 1) ? w[m >> 1] >> 16 : w[m >> 1] & 0xffffu;
+      const int at = (int)nat[8u * l + (uint32_t)m];
+      tile[(at >> 3) * 9 + (at & 7)] = (int)(int16_t)half * (int)q[m];
+    }
+    if (l == 0u) tile[0] = (int)(int16_t)dc[b].v[comp] * (int)q[0];   // (behind this lane's own store of the difference)
+  }
+  __syncthreads();
+  int d[64];   // (idct8's interface; elements 0..7 are used)
+  if (live) {
+    int dmax = 0, dmin = 0;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) { d[r] = tile[r * 9 + (int)l]; dmax = max(dmax, d[r]); dmin = min(dmin, d[r]); }
+    if (dmax >= 32768 || dmin <= -32768) idct8<0, int64_t>(d, 0, 1);
+    else idct8<0, int>(d, 0, 1);
+  }
+  __syncthreads();   // (every column has been read)
+  if (live) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) tile[r * 9 + (int)l] = d[r];
+  }
+  __syncthreads();
+  if (!live) return;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) d[c] = tile[(int)l * 9 + c];
+  idct8<1, uint32_t>(d, 0, 1);
+  uint32_t o[2] = {0u, 0u};
+#pragma unroll
+  for (int c = 0; c < 8; ++c) o[c >> 2] |= range_limit(d[c]) << (8 * (c & 3));
+  const int r = (int)l;
+  uint8_t* dst = pl.p + (size_t)(br * 8 + r) * pl.stride + bc * 8;
+  if (bc * 8 + 8 <= pl.w && pl.aligned8) { if (br * 8 + r < pl.h) *reinterpret_cast<uint2*>(dst) = make_uint2(o[0], o[1]); }
+  else if (br * 8 + r < pl.h)
+    for (int c = 0; c < 8; ++c)
+      if (bc * 8 + c < pl.w) dst[c] = (uint8_t)(o[c >> 2] >> (8 * (c & 3)));
+}
+
+__device__ __forceinline__ void idct_scaled_body(const DecJob& j, const DecScaledJob& q, const Dc3* dc) {
+  uint32_t x = blockIdx.x;
+  int comp = 0;
+  if (x >= q.wg_luma) {
+    x -= q.wg_luma;
+    if (x >= 2u * q.wg_chroma) return;
+    comp = x >= q.wg_chroma ? 2 : 1;
+    if (comp == 2) x -= q.wg_chroma;
+  }
+  const uint32_t nmcu = j.gray ? j.nblk : mcu_of(j.nblk, j.bpm);
+  if (q.size[comp] == 8u) { idct8_coop(j, q.plane[comp], dc, comp, x, nmcu); return; }   // 4:2:0 chroma at 1/2 (the whole workgroup)
+  const uint32_t i = x * 128u + threadIdx.x;   // the block's number among those of its component, in MCU order
+  uint32_t mcu, k;
+  if (comp == 0) { const uint32_t lb = j.gray ? 1u : j.hs * j.vs; mcu = lb == 4u ? i >> 2 : (lb == 2u ? i >> 1 : i); k = i - mcu * lb; }
+  else { mcu = i; k = j.chroma_at + (uint32_t)(comp - 1); }
+  if (mcu >= nmcu) return;
+  const uint32_t b = mcu * j.bpm + k;
+  const int mr = (int)(mcu / j.mcus_x), mc = (int)(mcu - (uint32_t)mr * j.mcus_x);
+  int br = mr, bc = mc;
+  if (comp == 0 && !j.gray) { br = (int)j.vs * mr + (int)(k >> (j.hs - 1u)); bc = (int)j.hs * mc + (int)(k & (j.hs - 1u)); }
+  const DecPlane& pl = q.plane[comp];
+  switch (q.size[comp]) {   // the same for the whole workgroup
+    case 1u: idct_reduced_block<1>(j, pl, dc, b, comp, br, bc); break;
+    case 2u: idct_reduced_block<2>(j, pl, dc, b, comp, br, bc); break;
+    default: idct_reduced_block<4>(j, pl, dc, b, comp, br, bc); break;
   }
 }
 
@@ -776,6 +990,25 @@ __global__ void __launch_bounds__(256) k_jd_sync_multi(const DecBatchJob* jobs, 
 }
 __global__ void __launch_bounds__(256) k_jd_write_multi(const DecBatchJob* jobs) { const DecBatchJob& b = jobs[blockIdx.y]; write_body(b.j, b.tables, b.st[0], b.first_block, b.flags + 1); }
 __global__ void __launch_bounds__(128) k_jd_idct_multi(const DecBatchJob* jobs) { const DecBatchJob& b = jobs[blockIdx.y]; idct_body(b.j, b.dc); }
+// the images of the batch that are decoded at 1/2, 1/4 or 1/8 (blockIdx.y = entry of sj).  k_jd_idct_multi sees such an image with
+// empty planes: each of its blocks counts as a dummy block there and returns in front of its first load
+__global__ void __launch_bounds__(128) k_jd_idct_scaled_multi(const DecBatchJob* jobs, const DecScaledJob* sj) {
+  const DecScaledJob& q = sj[blockIdx.y];
+  const DecBatchJob& b = jobs[q.img];
+  idct_scaled_body(b.j, q, b.dc);
+}
+// per-component IDCT size of a decode at 1 / scale (jdmaster.c, jpeg_calc_output_dimensions): N = 8 / scale, doubled while both
+// sampling ratios allow it -- the chroma of 4:2:0 is scaled up in the IDCT instead of being upsampled behind it
+void scaled_idct_sizes(int hs, int vs, bool gray, int scale, int size[3]) {
+  const int n = 8 / scale;
+  size[0] = size[1] = size[2] = n;
+  if (gray) return;
+  for (int c = 1; c < 3; ++c) {   // chroma: 1x1 samples under a luma of hs x vs
+    int sz = n;
+    while (sz < 8 && (hs * n) % (sz * 2) == 0 && (vs * n) % (sz * 2) == 0) sz *= 2;
+    size[c] = sz;
+  }
+}
 
 size_t dec_workspace_bytes(const DecInfo& info, DecLayout* l) {
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -811,7 +1044,7 @@ size_t dec_workspace_bytes(const DecInfo& info, DecLayout* l) {
 
 // where the batch-level arrays sit inside the scratch buffer
 struct BatchLayout {
-  size_t jobs, flags, offs, kept, kept_blk, nblocks, first_block, dc, tmp, tmp_bytes, total;
+  size_t jobs, flags, offs, kept, kept_blk, nblocks, first_block, dc, tmp, tmp_bytes, scaled, total;
   uint32_t n_kept, n_sub, n_blk;
 };
 static BatchLayout batch_layout(int n, const DecLayout l[]) {
@@ -838,6 +1071,7 @@ static BatchLayout batch_layout(int n, const DecLayout l[]) {
                                         (size_t)(B.n_blk ? B.n_blk : 1u), Dc3Sum(), rocprim::equal_to<uint64_t>());
   B.tmp_bytes = up(std::max(t2, t3) + 256);
   B.tmp = o; o += B.tmp_bytes;
+  B.scaled = o; o += up((size_t)n * sizeof(DecScaledJob));   // the scaled images' entries (k_jd_idct_scaled_multi)
   B.total = o;
   return B;
 }
@@ -858,7 +1092,8 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
   // real asynchronous copy and needs no synchronisation of its own (every call ends with the stream idle, so reuse is safe)
   static thread_local void* t_pinned = nullptr;
   static thread_local size_t t_pinned_cap = 0;
-  const size_t pinned_need = (size_t)n * sizeof(DecBatchJob) + (size_t)3 * (n + 1) * 4 + 64;
+  const size_t scaled_at = ((size_t)n * sizeof(DecBatchJob) + (size_t)3 * (n + 1) * 4 + 15) / 16 * 16;   // behind the jobs and the offset tables
+  const size_t pinned_need = scaled_at + (size_t)n * sizeof(DecScaledJob) + 64;
   if (pinned_need > t_pinned_cap) {
     if (t_pinned) (void)hipHostFree(t_pinned);
     t_pinned = nullptr; t_pinned_cap = 0;
@@ -877,6 +1112,8 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
   uint32_t* koff = offs; uint32_t* soff = koff + (n + 1); uint32_t* boff = soff + (n + 1);
   koff[0] = soff[0] = boff[0] = 0u;
   uint32_t gu = 1, gsync = 1, gidct = 1;
+  DecScaledJob* sjobs = reinterpret_cast<DecScaledJob*>(static_cast<uint8_t*>(t_pinned) + scaled_at);
+  uint32_t nscaled = 0, gscaled = 1;
   for (int k = 0; k < n; ++k) {
     DecBatchJob& b = jobs[k];
     memset(&b, 0, sizeof(b));
@@ -905,6 +1142,8 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
     j.dc_tbl[0] = 0; j.ac_tbl[0] = 1; j.dc_tbl[1] = 2; j.ac_tbl[1] = 3;
     j.coef = reinterpret_cast<int16_t*>(w + L.coef);
     for (int c = 0; c < 3; ++c) { j.plane[c] = (*planes[k])[c]; memcpy(j.quant[c], in.quant[c], sizeof(j.quant[c])); }
+    const bool scaled = in.scale != 1;
+    if (scaled) memset(j.plane, 0, sizeof(j.plane));   // its planes are the scaled entry's: k_jd_idct_multi finds nothing to write
     if (b.rst) {
       const size_t nint = in.interval_start.size();
       std::vector<uint32_t> sb_, se_, sk_;
@@ -943,9 +1182,28 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
     boff[k + 1] = boff[k] + j.nblk;
     gu = std::max(gu, (L.nchunks + 255u) / 256u);
     gsync = std::max(gsync, (j.nsub + 255u) / 256u);
-    gidct = std::max(gidct, (j.nblk + 127u) / 128u);
+    if (!scaled) gidct = std::max(gidct, (j.nblk + 127u) / 128u);
+    else if (j.nblk) {
+      DecScaledJob& q = sjobs[nscaled++];
+      memset(&q, 0, sizeof(q));
+      q.img = (uint32_t)k;
+      int size[3];
+      scaled_idct_sizes((int)L.hs, (int)L.vs, in.gray != 0, in.scale, size);
+      const uint32_t nmcu = j.nblk / j.bpm;
+      q.wg_luma = (nmcu * (in.gray ? 1u : L.hs * L.vs) + 127u) / 128u;
+      q.wg_chroma = in.gray ? 0u : (size[1] == 8 ? (nmcu + kCoopBlocks - 1u) / kCoopBlocks : (nmcu + 127u) / 128u);
+      for (int c = 0; c < 3; ++c) {
+        DecPlane& p = q.plane[c];
+        p = (*planes[k])[c];
+        q.size[c] = (uint32_t)size[c];
+        p.aligned8 = reinterpret_cast<uintptr_t>(p.p) % (uintptr_t)size[c] == 0 && p.stride % size[c] == 0 ? 1 : 0;
+      }
+      gscaled = std::max(gscaled, q.wg_luma + 2u * q.wg_chroma);
+    }
   }
   JD_TRY(hipMemcpyAsync(djobs, jobs, (size_t)n * sizeof(DecBatchJob) + noffs * 4, hipMemcpyHostToDevice, s));   // jobs + offset tables (adjacent on both sides)
+  const DecScaledJob* dsjobs = reinterpret_cast<const DecScaledJob*>(batch_ws + B.scaled);
+  if (nscaled) JD_TRY(hipMemcpyAsync(batch_ws + B.scaled, sjobs, (size_t)nscaled * sizeof(DecScaledJob), hipMemcpyHostToDevice, s));
   if (!keep.empty()) JD_TRY(hipStreamSynchronize(s));   // restart tables are in pageable host memory
   const SegOf sseg{doffs + (n + 1), n}, bseg{doffs + 2 * (n + 1), n};
   const CountIt cnt0(0u);
@@ -989,7 +1247,8 @@ int decode_device_batch(int n, const DecInfo* const info[], const DecLayout l[],
     JD_TRY(rocprim::inclusive_scan_by_key(stmp, tmp, BlkKeyIt(cnt0, BlkKeyBatch{djobs, bseg}), DcPickIt(cnt0, DcPickBatch{djobs, bseg}),
                                           reinterpret_cast<Dc3*>(batch_ws + B.dc), (size_t)boff[n], Dc3Sum(), rocprim::equal_to<uint64_t>(), s));
   }
-  hipLaunchKernelGGL(k_jd_idct_multi, dim3(gidct, ny), dim3(128), 0, s, (const DecBatchJob*)djobs);
+  if (nscaled < (uint32_t)n) hipLaunchKernelGGL(k_jd_idct_multi, dim3(gidct, ny), dim3(128), 0, s, (const DecBatchJob*)djobs);
+  if (nscaled) hipLaunchKernelGGL(k_jd_idct_scaled_multi, dim3(gscaled, nscaled), dim3(128), 0, s, (const DecBatchJob*)djobs, dsjobs);
   JD_TRY(hipMemcpyAsync(flags.data(), dflags, flags.size() * 4, hipMemcpyDeviceToHost, s));
   JD_TRY(hipStreamSynchronize(s));
   JD_TRY(hipGetLastError());

@@ -439,10 +439,13 @@ struct YccRgbaBatch {
 static_assert(sizeof(YccRgbaBatch) <= 4096, "k_ycc420_rgba_batch's kernel arguments exceed the kernarg segment");
 hipError_t launch_ycc420_to_rgba_batch(const YccRgbaBatch& b, int n, hipStream_t s);
 // the same for decoded 4:4:4, 4:2:2 and 4:4:0 planes of any size, odd ones included (k_yccx_rgba_batch); an image's sampling is
-// (hs, vs) = the luma samples per chroma sample across and down, its chroma planes are ceil(w / hs) x ceil(h / vs)
+// (hs, vs) = the luma samples per chroma sample across and down, its chroma planes are ceil(w / hs) x ceil(h / vs).  plain: the chroma
+// is replicated instead of filtered -- what libjpeg does for planes of a decode at 1/8 (jinit_upsampler: fancy upsampling needs an IDCT
+// size above 1)
 struct YccxRgbaImage {
   YccRgbaImage im;
   uint32_t hs, vs;
+  uint32_t plain;
 };
 struct YccxRgbaBatch {
   YccxRgbaImage img[kRgbaChunk];

@@ -3552,19 +3552,21 @@ __device__ __forceinline__ void ycc420_rgba_pair(const uint8_t* __restrict__ yp,
 //          are replicated (jinit_upsampler takes h2v1_upsample for them)
 //   4:4:0  h1v2_fancy_upsample down the column: even rows (3 c[j] + c[j-1] + 1) >> 2, odd ones (3 c[j] + c[j+1] + 2) >> 2, the
 //          neighbour clamped to the plane
+// plain: h2v1_upsample / h1v2 replication, the sample itself in every case
 __device__ __forceinline__ int yccx_chroma(const uint8_t* __restrict__ p, uint32_t cs, uint32_t cw, uint32_t ch, uint32_t hs, uint32_t vs,
-                                           uint32_t x, uint32_t y) {
+                                           uint32_t x, uint32_t y, bool plain) {
   if (hs == 2u) {
     const uint32_t i = x >> 1;
     const uint8_t* row = p + (size_t)y * cs;
     const int c = row[i];
-    if (cw <= 2u) return c;
+    if (cw <= 2u || plain) return c;
     if (x & 1u) return i + 1u < cw ? (3 * c + (int)row[i + 1u] + 2) >> 2 : c;
     return i ? (3 * c + (int)row[i - 1u] + 1) >> 2 : c;
   }
   if (vs == 2u) {
     const uint32_t j = y >> 1;
     const int c = p[(size_t)j * cs + x];
+    if (plain) return c;
     const uint32_t o = (y & 1u) ? min(j + 1u, ch - 1u) : (j ? j - 1u : 0u);
     return (3 * c + (int)p[(size_t)o * cs + x] + ((y & 1u) ? 2 : 1)) >> 2;
   }
@@ -3576,6 +3578,7 @@ __device__ __forceinline__ int yccx_chroma(const uint8_t* __restrict__ p, uint32
 __global__ void __launch_bounds__(256) k_yccx_rgba_batch(const YccxRgbaBatch b) {
   const YccRgbaImage& im = b.img[blockIdx.z].im;
   const uint32_t hs = b.img[blockIdx.z].hs, vs = b.img[blockIdx.z].vs;
+  const bool plain = b.img[blockIdx.z].plain != 0u;
   const uint32_t cw = (im.w + hs - 1u) / hs, ch = (im.h + vs - 1u) / vs;
   const uint32_t total = im.w * im.h, groups = (total + 3u) >> 2;   // (w, h <= 8192: 2^26 pixels)
   const bool aligned = (reinterpret_cast<uintptr_t>(im.rgba) & 15u) == 0u;
@@ -3586,8 +3589,8 @@ __global__ void __launch_bounds__(256) k_yccx_rgba_batch(const YccxRgbaBatch b) 
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) {
       if (k < cnt) {
-        px[k] = ycc_rgba_px((int)im.y[(size_t)y * im.ys + x], yccx_chroma(im.cb, im.cs, cw, ch, hs, vs, x, y),
-                            yccx_chroma(im.cr, im.cs, cw, ch, hs, vs, x, y));
+        px[k] = ycc_rgba_px((int)im.y[(size_t)y * im.ys + x], yccx_chroma(im.cb, im.cs, cw, ch, hs, vs, x, y, plain),
+                            yccx_chroma(im.cr, im.cs, cw, ch, hs, vs, x, y, plain));
         if (++x == im.w) { x = 0u; ++y; }
       }
     }

@@ -264,11 +264,25 @@ bool JpegEncoderHelperHip::compressImage(const uint8_t* yBuffer, const uint8_t* 
   return rc == UHDR_HIP_NO_ERROR;
 }
 
-bool JpegDecoderHelperHip::decompressImage(const void* image, int length, decode_mode_t decodeTo) {
+bool JpegDecoderHelperHip::decompressImage(const void* image, int length, decode_mode_t decodeTo, int scaleDenom) {
   mResultBuffer.clear();
   mWidth = mHeight = 0;
   if (image == nullptr || length <= 0 || uhdr_hip_init(0) != UHDR_HIP_NO_ERROR) return false;
   uhdr_hip_image_t desc = {};
+  if (scaleDenom != 1) {   // uhdr_hip_jpeg_decode_scaled: a 4:2:0 file gives three planes of the scaled size, a single-plane file one
+    const int to = decodeTo == DECODE_TO_RGBA ? UHDR_HIP_DECODE_TO_RGBA : UHDR_HIP_DECODE_TO_YCBCR;
+    if (uhdr_hip_jpeg_decode_scaled(image, (size_t)length, to, nullptr, 0, &desc, UHDR_HIP_MEM_HOST, nullptr, 0, scaleDenom) != UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE) return false;
+    if (desc.width == 0 || desc.height == 0) return false;
+    const size_t luma = desc.width * desc.height;
+    const bool single = to == UHDR_HIP_DECODE_TO_YCBCR && desc.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
+    mResultBuffer.resize(to == UHDR_HIP_DECODE_TO_RGBA ? luma * 4 : single ? luma : luma * 3);
+    if (uhdr_hip_jpeg_decode_scaled(image, (size_t)length, to, mResultBuffer.data(), mResultBuffer.size(), &desc, UHDR_HIP_MEM_HOST, nullptr, 0, scaleDenom) != UHDR_HIP_NO_ERROR) {
+      mResultBuffer.clear();
+      return false;
+    }
+    mWidth = desc.width; mHeight = desc.height; mSingleChannel = single;
+    return true;
+  }
   if (decodeTo == DECODE_TO_RGBA) {
     if (uhdr_hip_jpeg_decode_rgba(image, (size_t)length, nullptr, 0, &desc, UHDR_HIP_MEM_HOST, nullptr) != UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE) return false;
     if (desc.width == 0 || desc.height == 0) return false;   // (a probe answer always carries the size)
@@ -688,7 +702,13 @@ status_t JpegRHip::decodeJPEGR(uhdr_compressed_ptr jpegr_image_ptr, uhdr_uncompr
   const size_t bpp = output_format == ULTRAHDR_OUTPUT_HDR_LINEAR ? 8 : output_format == ULTRAHDR_OUTPUT_HDR_LINEAR_RGB_10BIT ? 6 : 4;
   const bool want_md = metadata != nullptr || output_format != ULTRAHDR_OUTPUT_SDR;   // jpegr.cpp:754
   const int flags = mDecodeAnySampling ? UHDR_HIP_DECODE_ANY_SAMPLING : 0;
-  if (mAnyGainMapMetadata) {   // any valid metadata, one- and three-component maps
+  if (mDecodeScaleDenom != 1) {   // the scaled decode reads what the any-metadata decode reads
+    void* out = dest->data;
+    const size_t sd = mDecodeScaleDenom > 0 ? (size_t)mDecodeScaleDenom : 1;
+    const size_t cap = ((a.width + sd - 1) / sd) * ((a.height + sd - 1) / sd) * bpp;
+    rc = uhdr_hip_jpegr_decode_scaled_batch(1, &file, &n, (int)output_format, max_display_boost, &out, &cap, &d, want_md ? &md : nullptr, nullptr,
+                                            mApplyMode, UHDR_HIP_MEM_HOST, nullptr, flags, mDecodeScaleDenom);
+  } else if (mAnyGainMapMetadata) {   // any valid metadata, one- and three-component maps
     void* out = dest->data;
     const size_t cap = a.width * a.height * bpp;
     rc = uhdr_hip_jpegr_decode_md_batch(1, &file, &n, (int)output_format, max_display_boost, &out, &cap, &d, want_md ? &md : nullptr, nullptr,
