@@ -1327,8 +1327,50 @@ int uhdr_hip_jpegr_encode_batch_opts(int n, const uhdr_hip_image_t* p010_images,
                                      const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
                                      size_t* out_size, int* status, const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream);
 /* Host only: the MCUs per interval the encoder derives from opts for a scan of `width` pixels whose MCUs are mcu_width (8 or 16)
- * pixels wide; 0: no intervals.  *restart_mcus is left alone where opts would be refused (the call's ERROR_UNSUPPORTED_FEATURE). */
+ * pixels wide; 0: no intervals.  *restart_mcus is left alone where opts would be refused (the call's ERROR_UNSUPPORTED_FEATURE).
+ * The two widths cover every sampling the encoder writes: 16 for 4:2:0 and 4:2:2, 8 for 4:4:4, 4:4:0 and a single plane. */
 int uhdr_hip_jpeg_restart_mcus(const uhdr_hip_jpeg_encode_opts_t* opts, size_t width, int mcu_width, uint32_t* restart_mcus);
+
+/* ---- 4:4:4, 4:2:2 and 4:4:0 files from planes and from RGBA8888 -------------------------------------------
+ * The encoder's counterpart of UHDR_HIP_DECODE_ANY_SAMPLING: luma sampling 1x1, 2x1 or 1x2 over 1x1 chroma in the frame header, MCUs
+ * of 3, 4 and 4 blocks (Y blocks in rows of hs, then Cb, Cr).  Optimised tables and restart intervals (opts) apply as for 4:2:0;
+ * restart_in_rows counts the MCUs per row of the sampling written: ceil(width / 16) for 4:2:2, ceil(width / 8) for 4:4:4 and 4:4:0.
+ *
+ * uhdr_hip_jpeg_encode_planes_batch_opts: uhdr_hip_jpeg_encode_batch_opts -- arguments, memory spaces, ICC per file, size probe
+ * (out[i] == NULL with capacity 0), per-file statuses, rounds, NULL opts -- where an image of UHDR_HIP_PIX_FMT_YUV444 / YUV422 /
+ * YUV440 is compressed as what it says, from planes laid out as uhdr_hip_jpeg_decode_batch_ex hands them out: chroma of
+ * ceil(width / hs) x ceil(height / vs) samples at chroma_data, rows chroma_stride apart, Cr behind Cb at chroma_stride x chroma
+ * height (a stride of 0: the plane's width).  The file is the baseline file libjpeg writes in raw-data mode for those planes with
+ * jpeg_set_quality(q, TRUE) and the ISLOW DCT.  Partial blocks are padded as libjpeg pads them, each plane on its own grid: the last
+ * column repeated out to the block grid, then the last row -- NOT the zero rows and columns of the 4:2:0 and single-plane calls,
+ * which keep theirs here as everywhere.  Every other pixelFormat in the same call behaves exactly as in
+ * uhdr_hip_jpeg_encode_batch_opts, and a mixed batch shares its launches.  Per file, in this order: BAD_PTR for NULL data or
+ * chroma_data, or a NULL out[i] with a capacity; ERROR_RESOLUTION_MISMATCH outside 1x1 .. 65500x65500 (odd sizes are accepted);
+ * ERROR_INVALID_STRIDE for a luma stride below the width or a chroma stride below the chroma width; ERROR_UNSUPPORTED_FEATURE where
+ * the block limits of the options are exceeded; ERROR_INSUFFICIENT_RESOURCE with the size in out_size[i] for a file that does not fit.
+ *
+ * uhdr_hip_jpeg_encode_rgba_batch_opts: uhdr_hip_jpeg_encode_rgba420_batch_opts with `sampling` in front of opts.
+ * UHDR_HIP_PIX_FMT_YUV420 IS that call.  YUV444 writes uhdr_hip_jpeg_encode_rgb_batch_opts' file, with the ICC segment where the
+ * other calls put it.  YUV422 is libjpeg's file for JCS_RGB input with 2x1 luma sampling: jccolor.c's conversion at full resolution,
+ * jcsample.c's h2v1_downsample of the chroma, edges expanded as libjpeg expands them -- converted and downsampled on the device in
+ * one launch per round.  Any other value (YUV440 among them) is the call's ERROR_UNSUPPORTED_FEATURE, returned after the opts check
+ * and before anything else.
+ *
+ * uhdr_hip_jpegr_encode_packed_sampling_batch: uhdr_hip_jpegr_encode_packed_batch with `primary_sampling` (YUV444 / YUV422 / YUV420;
+ * anything else: ERROR_UNSUPPORTED_FEATURE) and `opts` behind rgb_map.  The primary image is the call above at that sampling with the
+ * file's ICC profile; opts holds for the primary image and the gain-map JPEG alike.  Gain map, metadata, container and checks are
+ * the packed call's; with YUV420 and NULL opts it IS that call.  uhdr_hip_jpegr_decode_batch_ex reads a 4:4:4 or 4:2:2 file with
+ * UHDR_HIP_DECODE_ANY_SAMPLING. */
+int uhdr_hip_jpeg_encode_planes_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
+                                           const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                           const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream);
+int uhdr_hip_jpeg_encode_rgba_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
+                                         const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                         int sampling, const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream);
+int uhdr_hip_jpegr_encode_packed_sampling_batch(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf,
+                                                int quality, const void* const* exif, const size_t* exif_size, void* const* out,
+                                                const size_t* out_capacity, size_t* out_size, int* status, int rgb_map, int primary_sampling,
+                                                const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream);
 
 /* Bench / test support: the deterministic synthetic frame pair of SURVEY.md 8(d) (an LCG; tests/ and bench.py compare it with the
  * oracle's serial loop), written into device memory: p010 = width*height*3/2 uint16 (luma, then interleaved UV, values in the

@@ -195,6 +195,12 @@ class JpegEncoderHelperHip {
   // uvBuffer == nullptr compresses the single plane yBuffer (the gain map, jpegr.cpp:294-297)
   bool compressImage(const uint8_t* yBuffer, const uint8_t* uvBuffer, int width, int height, int lumaStride, int chromaStride,
                      int quality, const void* iccBuffer, unsigned int iccSize);
+  // Three planes of another sampling (no reference counterpart): pixelFormat UHDR_HIP_PIX_FMT_YUV444, YUV422 or YUV440, chroma of
+  // ceil(width / hs) x ceil(height / vs) samples at cbBuffer, Cr chromaStride x chroma height behind Cb -- the layout
+  // JpegDecoderHelperHip hands out for such files.  Any size from 1x1, odd ones included; edges are padded as libjpeg pads them
+  // (uhdr_hip_jpeg_encode_planes_batch_opts).  UHDR_HIP_PIX_FMT_YUV420 and MONOCHROME: compressImage.
+  bool compressPlanes(const uint8_t* yBuffer, const uint8_t* cbBuffer, int width, int height, int lumaStride, int chromaStride, int quality,
+                      const void* iccBuffer, unsigned int iccSize, int pixelFormat);
   void* getCompressedImagePtr() { return mResultBuffer.data(); }
   size_t getCompressedImageSize() { return mResultBuffer.size(); }
 
@@ -336,6 +342,13 @@ class JpegRHip {
   // no intervals, whatever is set here.
   void setRestartInterval(unsigned mcus) { mRestartInterval = mcus; }
   void setRestartInRows(unsigned rows) { mRestartInRows = rows; }
+  // UHDR_HIP_PIX_FMT_YUV420 (default): both encodeJPEGRPacked overloads compress the SDR image as 4:2:0.  UHDR_HIP_PIX_FMT_YUV444 or
+  // YUV422: the primary image keeps its chroma at full or at half horizontal resolution (uhdr_hip_jpegr_encode_packed_sampling_batch;
+  // the overload without an SDR image tone-maps one first, as the packed API-0 does); gain map, metadata and container do not change,
+  // and decodeJPEGR reads the file with setDecodeAnySampling(true).  With such a sampling those overloads also honour
+  // setOptimizeHuffman, setRestartInterval and setRestartInRows, and answer ERROR_ULTRAHDR_UNSUPPORTED_FEATURE for setContentBoost and
+  // for any other value given here.  Every encodeJPEGR overload is unchanged: its SDR image is 4:2:0.
+  void setPrimarySampling(int pixel_format) { mPrimarySampling = pixel_format; }
 
  private:
   int mApplyMode = 1;
@@ -349,6 +362,7 @@ class JpegRHip {
   bool mOptimizeHuffman = false;
   unsigned mRestartInterval = 0, mRestartInRows = 0;
   int mGainMapScaleFactor = 4;
+  int mPrimarySampling = 1;   // UHDR_HIP_PIX_FMT_YUV420
 };
 
 }  // namespace ultrahdr

@@ -255,6 +255,13 @@ SIGNATURES.update({
     if name in ("uhdr_hip_jpeg_encode_batch_ex", "uhdr_hip_jpeg_encode_rgb_batch_ex", "uhdr_hip_jpeg_encode_rgba420_batch_ex",
                 "uhdr_hip_jpegr_encode_batch_ex")})
 SIGNATURES["uhdr_hip_jpeg_restart_mcus"] = (C.c_int, [_OP, C.c_size_t, C.c_int, C.POINTER(C.c_uint32)])
+# 4:4:4 / 4:2:2 / 4:4:0 files: planes as ycbcr_image() describes them; RGBA8888 at a `sampling` (PIX_FMT_YUV444 / 422 / 420) in front of
+# opts; the packed JPEG/R call with `primary_sampling` and opts behind rgb_map
+SIGNATURES["uhdr_hip_jpeg_encode_planes_batch_opts"] = SIGNATURES["uhdr_hip_jpeg_encode_batch_opts"]
+SIGNATURES["uhdr_hip_jpeg_encode_rgba_batch_opts"] = (lambda res, args: (res, args[:-3] + [C.c_int] + args[-3:]))(
+    *SIGNATURES["uhdr_hip_jpeg_encode_rgba420_batch_opts"])
+SIGNATURES["uhdr_hip_jpegr_encode_packed_sampling_batch"] = (lambda res, args: (res, args[:-2] + [C.c_int, _OP] + args[-2:]))(
+    *SIGNATURES["uhdr_hip_jpegr_encode_packed_batch"])
 
 _lib = None
 

@@ -1493,6 +1493,12 @@ void encode_job_tables(size_t w, size_t h, jpeg::Geometry geom, int quality, jpe
   j.ybw = (uint32_t)((w + 7) / 8); j.ybh = (uint32_t)((h + 7) / 8);
   j.mcus_x = rgb ? j.ybw : (uint32_t)((w + 15) / 16);
   j.nblk = gray ? j.ybw * j.ybh : rgb ? j.ybw * j.ybh * 3u : j.mcus_x * (uint32_t)((h + 15) / 16) * 6u;
+  j.hs = (uint32_t)jpeg::geom_hs(geom); j.vs = (uint32_t)jpeg::geom_vs(geom);
+  if (geom == jpeg::kGeom444 || geom == jpeg::kGeom422 || geom == jpeg::kGeom440) {   // MCUs of 8 hs x 8 vs pixels, hs * vs + 2 blocks
+    j.sampled = 1;
+    j.mcus_x = (uint32_t)((w + 8 * j.hs - 1) / (8 * j.hs));
+    j.nblk = j.mcus_x * (uint32_t)((h + 8 * j.vs - 1) / (8 * j.vs)) * (j.hs * j.vs + 2u);
+  }
   uint16_t qn[64];
   jpeg::quant_table(quality, false, qn); jpeg::zigzag_table(qn, j.q_lum);
   jpeg::quant_table(quality, true, qn); jpeg::zigzag_table(qn, j.q_chr);
@@ -1501,9 +1507,9 @@ void encode_job_tables(size_t w, size_t h, jpeg::Geometry geom, int quality, jpe
     j.m_chr[i] = (uint32_t)((1ull << 32) / ((uint32_t)j.q_chr[i] << 3)) + 1u;
   }
 }
-jpeg::Plane encode_plane(const uint8_t* p, size_t pw, size_t ph, size_t stride, bool pad) {
+jpeg::Plane encode_plane(const uint8_t* p, size_t pw, size_t ph, size_t stride, bool pad, bool replicate = false) {
   jpeg::Plane q;
-  q.p = p; q.w = (int)pw; q.h = (int)ph; q.stride = (int)stride; q.pad_cols = pad ? 1 : 0;
+  q.p = p; q.w = (int)pw; q.h = (int)ph; q.stride = (int)stride; q.pad_cols = replicate ? jpeg::kPadReplicate : pad ? 1 : 0;
   q.aligned4 = (reinterpret_cast<uintptr_t>(p) % 4 == 0 && stride % 4 == 0) ? 1 : 0;
   return q;
 }
@@ -1516,11 +1522,29 @@ jpeg::Geometry enc_geom(const uhdr_hip_image_t& img, bool rgb) {
 }
 // mcu_planes: the planes are jpeg::launch_rgba_to_ycc420's -- whole MCUs, padded by that kernel, Cb at chroma_data -- of an image of
 // any size, odd ones included
-jpeg::Job encode_job(const uhdr_hip_image_t& img, int q, size_t pad_ls, size_t pad_cs, bool rgb = false, bool mcu_planes = false) {
+// geom >= 0: the geometry is the caller's word (the calls that take YUV444 / 422 / 440 planes, or make 4:2:2 planes of RGBA pixels):
+// planes of ceil(w / hs) x ceil(h / vs) chroma samples, padded as libjpeg pads (jpeg::kPadReplicate); mcu_planes: whole MCUs of
+// jpeg::launch_rgba_to_ycc422's
+jpeg::Job encode_job(const uhdr_hip_image_t& img, int q, size_t pad_ls, size_t pad_cs, bool rgb = false, bool mcu_planes = false, int geom = -1) {
   const bool gray = img.pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME;
   const size_t w = img.width, h = img.height, aw = (w + 15) / 16 * 16, acw = (w / 2 + 7) / 8 * 8;
   jpeg::Job j;
-  encode_job_tables(w, h, enc_geom(img, rgb), q, &j);
+  encode_job_tables(w, h, geom >= 0 ? (jpeg::Geometry)geom : enc_geom(img, rgb), q, &j);
+  if (geom >= 0) {
+    const uint8_t* pu = static_cast<const uint8_t*>(img.chroma_data);
+    if (mcu_planes) {   // (4:2:2)
+      const size_t mcw = (w + 15) / 16, mch = (h + 7) / 8;
+      j.plane[0] = encode_plane(static_cast<const uint8_t*>(img.data), 16 * mcw, 8 * mch, 16 * mcw, false);
+      j.plane[1] = encode_plane(pu, 8 * mcw, 8 * mch, 8 * mcw, false);
+      j.plane[2] = encode_plane(pu + 64 * mcw * mch, 8 * mcw, 8 * mch, 8 * mcw, false);
+      return j;
+    }
+    const size_t cw = (w + j.hs - 1) / j.hs, ch = (h + j.vs - 1) / j.vs, cs = img.chroma_stride;
+    j.plane[0] = encode_plane(static_cast<const uint8_t*>(img.data), w, h, img.luma_stride, false, true);
+    j.plane[1] = encode_plane(pu, cw, ch, cs, false, true);
+    j.plane[2] = encode_plane(pu + cs * ch, cw, ch, cs, false, true);
+    return j;
+  }
   if (mcu_planes) {
     const size_t mcw = (w + 15) / 16, mch = (h + 15) / 16;
     const uint8_t* pu = static_cast<const uint8_t*>(img.chroma_data);
@@ -1626,6 +1650,8 @@ struct EncJpeg {
   size_t dev_cap = 0;
   bool rgb = false;                      // img is RGBA8888 (luma_stride in pixels), compressed as 4:4:4 (jpeg::kGeomRgb444)
   bool mcu_planes = false;               // img's planes are jpeg::launch_rgba_to_ycc420's (encode_job)
+  int geom = -1;                         // >= 0: a jpeg::Geometry the descriptor does not say on its own -- kGeom444 / 422 / 440 planes
+                                         // (mcu_planes: jpeg::launch_rgba_to_ycc422's)
   bool optimize = false;                 // UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN: the file's own Huffman tables, built on the device
   uint32_t restart_interval = 0, restart_in_rows = 0;   // uhdr_hip_jpeg_encode_opts_t's, as given: the file's width decides (enc_restart)
 };
@@ -1656,7 +1682,7 @@ int encode_opts(const uhdr_hip_jpeg_encode_opts_t* opts, EncOpt* eo) {
 }
 // MCUs per restart interval of one file (0: none) and, at *intervals, how many intervals that makes
 uint32_t enc_restart(const jpeg::Job& j, uint32_t restart_interval, uint32_t restart_in_rows, uint32_t* intervals) {
-  const uint32_t bpm = j.gray ? 1u : j.rgb ? 3u : 6u;
+  const uint32_t bpm = j.gray ? 1u : j.hs * j.vs + 2u;
   const uint32_t ri = jpeg::restart_mcus(restart_interval, restart_in_rows, j.gray ? j.ybw : j.mcus_x);
   *intervals = ri == 0 ? 0u : (j.nblk / bpm + ri - 1u) / ri;
   return ri;
@@ -1704,12 +1730,12 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
   std::vector<std::vector<uint8_t>> header((size_t)k);
   for (int i = 0; i < k; ++i) {
     const EncJpeg& e = im[i];
-    jobs[i] = encode_job(e.img, e.quality, e.pad_ls, e.pad_cs, e.rgb, e.mcu_planes);
+    jobs[i] = encode_job(e.img, e.quality, e.pad_ls, e.pad_cs, e.rgb, e.mcu_planes, e.geom);
     ws_off[i] = ws_total;
     uint32_t intervals = 0;
     const uint32_t ri = enc_restart(jobs[i], e.restart_interval, e.restart_in_rows, &intervals);
     if (ri != 0) {   // the file runs through the encoder's restart launches, and its header says DRI
-      jobs[i].rst_bpm = jobs[i].gray ? 1u : jobs[i].rgb ? 3u : 6u;
+      jobs[i].rst_bpm = jobs[i].gray ? 1u : jobs[i].hs * jobs[i].vs + 2u;
       jobs[i].rst_blocks = ri * jobs[i].rst_bpm;
       jobs[i].rst_marks = intervals - 1u;
     }
@@ -1719,10 +1745,11 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     // Such a header is never longer than the default one -- baseline 8-bit data has at most 12 DC and 162 AC symbols, the sizes of
     // the Annex K tables --, so whatever is sized for the default header (a file's first-guess staging, a caller's capacity that
     // holds the default file) holds this one.
-    jpeg::build_header((int)e.img.width, (int)e.img.height, enc_geom(e.img, e.rgb), e.quality, e.icc ? e.icc->data() : nullptr,
+    jpeg::build_header((int)e.img.width, (int)e.img.height, e.geom >= 0 ? (jpeg::Geometry)e.geom : enc_geom(e.img, e.rgb), e.quality,
+                       e.icc ? e.icc->data() : nullptr,
                        e.icc ? e.icc->size() : 0, header[i], e.optimize, ri);
     // (the first guess holds the DRI segment and three bytes per interval as well)
-    if (im[i].cap == 0) im[i].cap = im[i].img.width * im[i].img.height * (jobs[i].rgb ? 3 : 1) + 65536 + (ri != 0 ? 6 + 3 * (size_t)intervals : 0);
+    if (im[i].cap == 0) im[i].cap = im[i].img.width * im[i].img.height * ((jobs[i].rgb || e.geom >= 0) ? 3 : 1) + 65536 + (ri != 0 ? 6 + 3 * (size_t)intervals : 0);
     off[i] = hp_total;
     hp_total += round_up(e.to_dev ? header[i].size() : im[i].cap, 256);   // a device destination: the header's way there only
   }
@@ -1767,6 +1794,7 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     EncJpeg one{e.img, e.quality, e.icc, e.pad_ls, e.pad_cs, (size_t)total};
     one.rgb = e.rgb;
     one.mcu_planes = e.mcu_planes;
+    one.geom = e.geom;
     one.optimize = e.optimize;
     one.restart_interval = e.restart_interval;
     one.restart_in_rows = e.restart_in_rows;
@@ -1819,26 +1847,92 @@ size_t enc_round_bytes(const uhdr_hip_image_t& img, bool host_in, bool host_out,
   return b;
 }
 
+// ---- planes of any sampling (uhdr_hip_jpeg_encode_planes_batch_opts) ----------------------------------------------------------------
+// the geometry of a YUV444 / 422 / 440 image, -1 for every other format (which that call compresses as uhdr_hip_jpeg_encode_batch does)
+int sampled_geom(const uhdr_hip_image_t& img) {
+  return img.pixelFormat == UHDR_HIP_PIX_FMT_YUV444   ? (int)jpeg::kGeom444
+         : img.pixelFormat == UHDR_HIP_PIX_FMT_YUV422 ? (int)jpeg::kGeom422
+         : img.pixelFormat == UHDR_HIP_PIX_FMT_YUV440 ? (int)jpeg::kGeom440
+                                                      : -1;
+}
+// such an image as the encoder reads it: chroma of ceil(w / hs) x ceil(h / vs) samples, strides defaulted to the widths
+struct SampledDims {
+  size_t cw, ch;
+};
+SampledDims sampled_dims(const uhdr_hip_image_t& img, int geom) {
+  const size_t hs = (size_t)jpeg::geom_hs((jpeg::Geometry)geom), vs = (size_t)jpeg::geom_vs((jpeg::Geometry)geom);
+  return SampledDims{(img.width + hs - 1) / hs, (img.height + vs - 1) / vs};
+}
+uhdr_hip_image_t sampled_image(const uhdr_hip_image_t& in, int geom) {
+  uhdr_hip_image_t img = in;
+  if (img.luma_stride == 0) img.luma_stride = img.width;
+  if (img.chroma_stride == 0) img.chroma_stride = sampled_dims(in, geom).cw;
+  return img;
+}
+// the call's checks of such an image behind the pointers: 1x1 to 65500x65500, odd sizes included; rows at least as long as the plane
+int sampled_check(const uhdr_hip_image_t& im, int geom, const EncOpt& eo) {
+  if (im.width == 0 || im.height == 0 || im.width > 65500 || im.height > 65500) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
+  const uhdr_hip_image_t d = sampled_image(im, geom);
+  if (d.luma_stride < d.width || d.chroma_stride < sampled_dims(im, geom).cw || d.luma_stride > (size_t)INT32_MAX ||
+      d.chroma_stride > (size_t)INT32_MAX)
+    return UHDR_HIP_ERROR_INVALID_STRIDE;
+  if (!encodable_with(im.width, im.height, (jpeg::Geometry)geom, eo)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return UHDR_HIP_NO_ERROR;
+}
+// bytes of the staged planes of such a host image: the samples alone at 64-byte pitches, luma, then Cb and Cr in one piece
+size_t sampled_stage_bytes(const uhdr_hip_image_t& img, int geom) {
+  const SampledDims g = sampled_dims(img, geom);
+  return round_up(round_up(img.width, 64) * img.height, 256) + round_up(round_up(g.cw, 64) * 2 * g.ch, 256);
+}
+int stage_sampled_slice(uint8_t* dy, const uhdr_hip_image_t& img, int geom, uhdr_hip_image_t* d, hipStream_t s) {
+  const SampledDims g = sampled_dims(img, geom);
+  const size_t dls = round_up(img.width, 64), dcs = round_up(g.cw, 64);
+  int rc;
+  if ((rc = h2d_plane(dy, dls, img.data, img.luma_stride, img.width, img.height, 1, s)) != 0) return rc;
+  uint8_t* du = dy + round_up(dls * img.height, 256);
+  if ((rc = h2d_plane(du, dcs, img.chroma_data, img.chroma_stride, g.cw, 2 * g.ch, 1, s)) != 0) return rc;   // (Cr follows Cb)
+  *d = img;
+  d->data = dy; d->luma_stride = dls;
+  d->chroma_data = du; d->chroma_stride = dcs;
+  return UHDR_HIP_NO_ERROR;
+}
+size_t sampled_round_bytes(const uhdr_hip_image_t& img, int geom, bool host_in, bool host_out, const EncOpt& eo) {
+  size_t b = enc_workspace_bytes(img.width, img.height, (jpeg::Geometry)geom, eo);
+  if (host_in) b += sampled_stage_bytes(img, geom);
+  if (host_out) b += img.width * img.height * 3 + 65536;
+  return b;
+}
+
 // One round of uhdr_hip_jpeg_encode_batch: files idx[0, m), their planes staged at the slot kEncYuv (host planes), every
 // compression through one compress_to_host.  Statuses and sizes of the round's files go to st_ / out_size.  A non-zero return is an
 // error of the device or the runtime.
 int jpeg_encode_round(DeviceState* st, hipStream_t s, bool host_in, bool host_out, const uhdr_hip_image_t* images, const int* quality,
                       const void* const* icc, const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size,
-                      const int* idx, int m, int* st_, const EncOpt& eo) {
+                      const int* idx, int m, int* st_, const EncOpt& eo, bool any_sampling = false) {
   std::vector<EncJpeg> im((size_t)m);
   std::vector<std::vector<uint8_t>> iccs((size_t)m);
+  // any_sampling (uhdr_hip_jpeg_encode_planes_batch_opts): a YUV444 / 422 / 440 image among the files is compressed as what it says
+  auto geom_of = [&](int i) { return any_sampling ? sampled_geom(images[i]) : -1; };
   size_t stage_total = 0;
   if (host_in) {
-    for (int k = 0; k < m; ++k) stage_total += enc_stage_bytes(enc_image(images[idx[k]]));
+    for (int k = 0; k < m; ++k) {
+      const int geom = geom_of(idx[k]);
+      stage_total += geom >= 0 ? sampled_stage_bytes(images[idx[k]], geom) : enc_stage_bytes(enc_image(images[idx[k]]));
+    }
     int rc;
     if ((rc = pool_reserve(st, kEncYuv, stage_total)) != 0) return rc;
   }
   size_t o = 0;
   for (int k = 0; k < m; ++k) {
     const int i = idx[k];
-    const uhdr_hip_image_t img = enc_image(images[i]);
+    const int geom = geom_of(i);
+    const uhdr_hip_image_t img = geom >= 0 ? sampled_image(images[i], geom) : enc_image(images[i]);
     uhdr_hip_image_t d = img;
-    if (host_in) {   // into the round's slice
+    if (host_in && geom >= 0) {
+      int rc;
+      if ((rc = stage_sampled_slice(static_cast<uint8_t*>(st->pool[kEncYuv]) + o, img, geom, &d, s)) != 0) return rc;
+      o += sampled_stage_bytes(img, geom);
+    } else if (host_in) {   // into the round's slice
       int rc;
       if ((rc = stage_encoder_slice(static_cast<uint8_t*>(st->pool[kEncYuv]) + o, img, &d, s)) != 0) return rc;
       o += enc_stage_bytes(img);
@@ -1852,6 +1946,7 @@ int jpeg_encode_round(DeviceState* st, hipStream_t s, bool host_in, bool host_ou
     e.icc = iccs[k].empty() ? nullptr : &iccs[k];
     e.pad_ls = img.luma_stride;
     e.pad_cs = img.chroma_stride;
+    e.geom = geom;
     eo.to(&e);
     if (host_out) {
       e.keep_max = out_capacity[i];   // a file that will not fit is only measured
@@ -1934,9 +2029,10 @@ int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void*
 // the bodies of the batch calls below, behind the _ex and the _opts form of each
 static int jpeg_encode_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
                                   void* const* out, const size_t* out_capacity, size_t* out_size, int* status, const EncOpt& eo, int mem_space,
-                                  void* stream);
+                                  void* stream, bool any_sampling = false);
 static int jpeg_encode_rgb_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
-                                      size_t* out_size, int* status, const EncOpt& eo, int mem_space, void* stream);
+                                      size_t* out_size, int* status, const EncOpt& eo, int mem_space, void* stream,
+                                      const void* const* icc = nullptr, const size_t* icc_size = nullptr);
 
 // uhdr_hip_jpeg_encode for n images in one call: a file that fails the single call's checks is not processed; the files of a round
 // share one jpeg::encode_batch_async launch set and one synchronisation (compress_to_host)
@@ -1964,9 +2060,19 @@ int uhdr_hip_jpeg_encode_batch_opts(int n, const uhdr_hip_image_t* images, const
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   return jpeg_encode_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, eo, mem_space, stream);
 }
+// uhdr_hip_jpeg_encode_batch_opts with YUV444 / 422 / 440 images compressed as what they are; every other image of
+// the call is that call's, and all share the round's launches
+int uhdr_hip_jpeg_encode_planes_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                           void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                           const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpeg_encode_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, eo, mem_space, stream, true);
+}
 static int jpeg_encode_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
                                   void* const* out, const size_t* out_capacity, size_t* out_size, int* status, const EncOpt& eo, int mem_space,
-                                  void* stream) {
+                                  void* stream, bool any_sampling) {
   if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
       (icc != nullptr && icc_size == nullptr))
     return UHDR_HIP_ERROR_BAD_PTR;
@@ -1977,6 +2083,9 @@ static int jpeg_encode_batch_with(int n, const uhdr_hip_image_t* images, const i
     if (im.data == nullptr || (im.pixelFormat != UHDR_HIP_PIX_FMT_MONOCHROME && im.chroma_data == nullptr) ||
         (out[i] == nullptr && out_capacity[i] != 0))
       st_[i] = UHDR_HIP_ERROR_BAD_PTR;
+    else if (any_sampling && sampled_geom(im) >= 0) {
+      if ((st_[i] = sampled_check(im, sampled_geom(im), eo)) == UHDR_HIP_NO_ERROR) live.push_back(i);
+    }
     else if (!encodable(im))
       st_[i] = UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
     else if (!encodable_with(im.width, im.height, enc_geom(im, false), eo))
@@ -1990,9 +2099,14 @@ static int jpeg_encode_batch_with(int n, const uhdr_hip_image_t* images, const i
   size_t done = 0;
   const int rc = run_rounds(
       live.size(), (size_t)jpeg::kMaxBatchJobs, stream,
-      [&](size_t k) { return enc_round_bytes(enc_image(images[live[k]]), host_in, host_out, eo); },
+      [&](size_t k) {
+        const uhdr_hip_image_t& im = images[live[k]];
+        const int geom = any_sampling ? sampled_geom(im) : -1;
+        return geom >= 0 ? sampled_round_bytes(im, geom, host_in, host_out, eo) : enc_round_bytes(enc_image(im), host_in, host_out, eo);
+      },
       [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
-        return jpeg_encode_round(st, s, host_in, host_out, images, quality, icc, icc_size, out, out_capacity, out_size, &live[r0], m, st_.data(), eo);
+        return jpeg_encode_round(st, s, host_in, host_out, images, quality, icc, icc_size, out, out_capacity, out_size, &live[r0], m, st_.data(), eo,
+                                 any_sampling);
       },
       &done);
   for (size_t k = done; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
@@ -2021,9 +2135,12 @@ int uhdr_hip_jpeg_encode_rgb_batch_opts(int n, const uhdr_hip_image_t* images, c
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   return jpeg_encode_rgb_batch_with(n, images, quality, out, out_capacity, out_size, status, eo, mem_space, stream);
 }
+// icc (uhdr_hip_jpeg_encode_rgba_batch_opts at YUV444 alone): an APP2 segment per file where the other calls put it
 static int jpeg_encode_rgb_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
-                                      size_t* out_size, int* status, const EncOpt& eo, int mem_space, void* stream) {
-  if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)))
+                                      size_t* out_size, int* status, const EncOpt& eo, int mem_space, void* stream, const void* const* icc,
+                                      const size_t* icc_size) {
+  if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (icc != nullptr && icc_size == nullptr))
     return UHDR_HIP_ERROR_BAD_PTR;
   for (int i = 0; i < n; ++i)
     if (quality[i] < 0 || quality[i] > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
@@ -2060,6 +2177,7 @@ static int jpeg_encode_rgb_batch_with(int n, const uhdr_hip_image_t* images, con
       [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
         const int* idx = &live[r0];
         std::vector<EncJpeg> im((size_t)m);
+        std::vector<std::vector<uint8_t>> iccs((size_t)m);
         size_t stage_total = 0;
         int rc;
         if (host_in) {
@@ -2069,6 +2187,9 @@ static int jpeg_encode_rgb_batch_with(int n, const uhdr_hip_image_t* images, con
         size_t o = 0;
         for (int k = 0; k < m; ++k) {
           const int i = idx[k];
+          const void* ip = icc ? icc[i] : nullptr;
+          const size_t in = icc ? icc_size[i] : 0;
+          if (ip != nullptr && in > 0) iccs[(size_t)k].assign(static_cast<const uint8_t*>(ip), static_cast<const uint8_t*>(ip) + in);
           uhdr_hip_image_t d = images[i];
           if (d.luma_stride == 0) d.luma_stride = d.width;
           d.chroma_data = nullptr; d.chroma_stride = 0;
@@ -2082,7 +2203,7 @@ static int jpeg_encode_rgb_batch_with(int n, const uhdr_hip_image_t* images, con
           EncJpeg& e = im[k];
           e.img = d;
           e.quality = quality[i];
-          e.icc = nullptr;
+          e.icc = iccs[(size_t)k].empty() ? nullptr : &iccs[(size_t)k];
           e.pad_ls = e.pad_cs = 0;
           e.rgb = true;
           eo.to(&e);
@@ -2127,9 +2248,13 @@ int rgba_file_check(const uhdr_hip_image_t& im, bool host_in, const void* out, s
 }
 // The 4:2:0 encoder's planes of m RGBA8888 images in device memory (luma_stride set), slices of pool slot `slot`: one
 // jpeg::launch_rgba_to_ycc420 for all of them (m <= jpeg::kRgba420Chunk).  e[k * step].img / .mcu_planes describe image k's planes.
-int rgba420_planes(DeviceState* st, size_t slot, hipStream_t s, int m, const uhdr_hip_image_t* imgs, EncJpeg* e, int step) {
+// s422: jpeg::launch_rgba_to_ycc422's planes instead (MCUs of 16 x 8 pixels), and the jobs' geometry with them
+int rgba420_planes(DeviceState* st, size_t slot, hipStream_t s, int m, const uhdr_hip_image_t* imgs, EncJpeg* e, int step, bool s422 = false) {
+  auto plane_bytes = [s422](const uhdr_hip_image_t& im) {
+    return round_up(s422 ? jpeg::rgba422_plane_bytes(im.width, im.height) : jpeg::rgba420_plane_bytes(im.width, im.height), 256);
+  };
   size_t total = 0;
-  for (int k = 0; k < m; ++k) total += round_up(jpeg::rgba420_plane_bytes(imgs[k].width, imgs[k].height), 256);
+  for (int k = 0; k < m; ++k) total += plane_bytes(imgs[k]);
   int rc;
   if ((rc = pool_reserve(st, slot, total)) != 0) return rc;
   jpeg::Rgba420Batch b;
@@ -2139,18 +2264,19 @@ int rgba420_planes(DeviceState* st, size_t slot, hipStream_t s, int m, const uhd
     jpeg::Rgba420Image& d = b.img[k];
     d.src = static_cast<const uint32_t*>(im.data);
     d.w = (uint32_t)im.width; d.h = (uint32_t)im.height; d.stride = (uint32_t)im.luma_stride;
-    d.mcw = (uint32_t)((im.width + 15) / 16); d.mch = (uint32_t)((im.height + 15) / 16);
+    d.mcw = (uint32_t)((im.width + 15) / 16); d.mch = (uint32_t)(s422 ? (im.height + 7) / 8 : (im.height + 15) / 16);
     d.y = static_cast<uint8_t*>(st->pool[slot]) + o;
-    d.cb = d.y + 256 * (size_t)d.mcw * d.mch;
-    o += round_up(jpeg::rgba420_plane_bytes(im.width, im.height), 256);
+    d.cb = d.y + (s422 ? 128 : 256) * (size_t)d.mcw * d.mch;
+    o += plane_bytes(im);
     uhdr_hip_image_t& p = e[(size_t)k * step].img;
     memset(&p, 0, sizeof(p));
     p.data = d.y; p.chroma_data = d.cb; p.width = im.width; p.height = im.height; p.colorGamut = im.colorGamut;
     p.luma_stride = 16 * (size_t)d.mcw; p.chroma_stride = 8 * (size_t)d.mcw; p.pixelFormat = UHDR_HIP_PIX_FMT_YUV420;
     e[(size_t)k * step].mcu_planes = true;
+    if (s422) { e[(size_t)k * step].geom = jpeg::kGeom422; p.pixelFormat = UHDR_HIP_PIX_FMT_YUV422; }
     e[(size_t)k * step].pad_ls = p.luma_stride; e[(size_t)k * step].pad_cs = p.chroma_stride;
   }
-  HIP_TRY(jpeg::launch_rgba_to_ycc420(b, m, s));
+  HIP_TRY(s422 ? jpeg::launch_rgba_to_ycc422(b, m, s) : jpeg::launch_rgba_to_ycc420(b, m, s));
   return UHDR_HIP_NO_ERROR;
 }
 }  // namespace
@@ -2159,7 +2285,7 @@ extern "C" {
 
 static int jpeg_encode_rgba420_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
                                           const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
-                                          const EncOpt& eo, int mem_space, void* stream);
+                                          const EncOpt& eo, int mem_space, void* stream, bool s422 = false);
 
 // uhdr_hip_jpeg_encode_batch's conventions for RGBA8888 images compressed as 4:2:0: the planes libjpeg's colour conversion and
 // downsampler hand its FDCT come from one k_rgba_to_ycc420 launch per round, everything behind them is compress_to_host
@@ -2185,9 +2311,24 @@ int uhdr_hip_jpeg_encode_rgba420_batch_opts(int n, const uhdr_hip_image_t* image
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   return jpeg_encode_rgba420_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, eo, mem_space, stream);
 }
+// RGBA8888 images at the sampling said: YUV420 is the call above, YUV444 uhdr_hip_jpeg_encode_rgb_batch_opts'
+// file with the ICC segment, YUV422 the 4:2:0 call's course with k_rgba_to_ycc422 in front
+int uhdr_hip_jpeg_encode_rgba_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                         void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int sampling,
+                                         const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if (sampling == UHDR_HIP_PIX_FMT_YUV444)
+    return jpeg_encode_rgb_batch_with(n, images, quality, out, out_capacity, out_size, status, eo, mem_space, stream, icc, icc_size);
+  if (sampling != UHDR_HIP_PIX_FMT_YUV422 && sampling != UHDR_HIP_PIX_FMT_YUV420) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return jpeg_encode_rgba420_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, eo, mem_space, stream,
+                                        sampling == UHDR_HIP_PIX_FMT_YUV422);
+}
 static int jpeg_encode_rgba420_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
                                           const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
-                                          const EncOpt& eo, int mem_space, void* stream) {
+                                          const EncOpt& eo, int mem_space, void* stream, bool s422) {
+  const jpeg::Geometry geom = s422 ? jpeg::kGeom422 : jpeg::kGeom420;   // (s422: uhdr_hip_jpeg_encode_rgba_batch_opts at YUV422)
   if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
       (icc != nullptr && icc_size == nullptr))
     return UHDR_HIP_ERROR_BAD_PTR;
@@ -2199,7 +2340,7 @@ static int jpeg_encode_rgba420_batch_with(int n, const uhdr_hip_image_t* images,
   const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE && mem_space != UHDR_HIP_MEM_HOST_TO_DEVICE;
   for (int i = 0; i < n; ++i) {
     st_[i] = rgba_file_check(images[i], host_in, out[i], out_capacity[i]);
-    if (st_[i] == UHDR_HIP_NO_ERROR && !encodable_with(images[i].width, images[i].height, jpeg::kGeom420, eo))
+    if (st_[i] == UHDR_HIP_NO_ERROR && !encodable_with(images[i].width, images[i].height, geom, eo))
       st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
     if (st_[i] == UHDR_HIP_NO_ERROR) live.push_back(i);
   }
@@ -2210,9 +2351,10 @@ static int jpeg_encode_rgba420_batch_with(int n, const uhdr_hip_image_t* images,
       live.size(), (size_t)jpeg::kRgba420Chunk, stream,
       [&](size_t k) {
         const uhdr_hip_image_t& im = images[live[k]];
-        size_t b = enc_workspace_bytes(im.width, im.height, jpeg::kGeom420, eo) + round_up(jpeg::rgba420_plane_bytes(im.width, im.height), 256);
+        size_t b = enc_workspace_bytes(im.width, im.height, geom, eo) +
+                   round_up(s422 ? jpeg::rgba422_plane_bytes(im.width, im.height) : jpeg::rgba420_plane_bytes(im.width, im.height), 256);
         if (host_in) b += round_up(stage_pitch(im) * im.height, 256);
-        if (host_out) b += im.width * im.height + 65536;
+        if (host_out) b += im.width * im.height * (s422 ? 3 : 1) + 65536;
         return b;
       },
       [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
@@ -2239,7 +2381,7 @@ static int jpeg_encode_rgba420_batch_with(int n, const uhdr_hip_image_t* images,
             d.data = dst; d.luma_stride = pitch / 4;
           }
         }
-        if ((rc = rgba420_planes(st, kEncSdr, s, m, dev.data(), im.data(), 1)) != 0) return rc;
+        if ((rc = rgba420_planes(st, kEncSdr, s, m, dev.data(), im.data(), 1, s422)) != 0) return rc;
         for (int k = 0; k < m; ++k) {
           const int i = idx[k];
           const void* ip = icc ? icc[i] : nullptr;
@@ -3457,10 +3599,13 @@ int uhdr_hip_jpegr_encode_scaled_batch(int n, const uhdr_hip_image_t* p010_image
 // boost_scope >= 0: the adaptive generate in the generate step's place, as in encode_round -- the workspace and
 // the carried key pair are the same pool slots, a round's ranges come down with its streams, and PER_CALL over several rounds stages
 // and measures every round (carry == 1) in front of the first one
+// primary_sampling, eo (uhdr_hip_jpegr_encode_packed_sampling_batch): the primary image as uhdr_hip_jpeg_encode_rgba_batch_opts writes it
+// at that sampling -- YUV444 straight from the pixels, YUV422 through k_rgba_to_ycc422 --, eo for both compressions
 static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf, int quality,
                                const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
                                size_t* out_size, int* status, int rgb_map, int mem_space, void* stream, uhdr_hip_metadata_t* metadata,
-                               const float* peaks, int boost_scope = -1) {
+                               const float* peaks, int boost_scope = -1, int primary_sampling = UHDR_HIP_PIX_FMT_YUV420,
+                               const EncOpt& eo = EncOpt()) {
   const bool api0 = sdr_images == nullptr;
   const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
   auto stride_bad = [](const uhdr_hip_image_t& im) { return im.luma_stride != 0 && (im.luma_stride < im.width || im.luma_stride > 0xFFFFFFFFull); };
@@ -3475,6 +3620,8 @@ static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const 
     if (!api0) {
       if (sd.data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
       if (stride_bad(sd)) return UHDR_HIP_ERROR_INVALID_STRIDE;
+      // (the 4:4:4 encoder addresses the pixels' rows with an int byte pitch)
+      if (primary_sampling == UHDR_HIP_PIX_FMT_YUV444 && sd.luma_stride > (size_t)INT32_MAX / 4) return UHDR_HIP_ERROR_INVALID_STRIDE;
       if (hd.width != sd.width || hd.height != sd.height) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
       if (!valid_gamut(sd.colorGamut)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
     }
@@ -3576,12 +3723,24 @@ static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const 
           if (carry == 1) return UHDR_HIP_NO_ERROR;
         }
         std::vector<EncJpeg> jpg(2 * (size_t)m);
-        if ((rc = rgba420_planes(st, kEncSdr, s, m, a.data(), jpg.data(), 2)) != 0) return rc;
+        if (primary_sampling == UHDR_HIP_PIX_FMT_YUV444) {
+          for (int k = 0; k < m; ++k) {   // the pixels as they stand: the encoder converts as it loads (jpeg::kGeomRgb444)
+            EncJpeg& e = jpg[2 * (size_t)k];
+            e.img = a[(size_t)k];
+            e.img.chroma_data = nullptr; e.img.chroma_stride = 0;
+            e.pad_ls = e.pad_cs = 0;
+            e.rgb = true;
+          }
+        } else if ((rc = rgba420_planes(st, kEncSdr, s, m, a.data(), jpg.data(), 2, primary_sampling == UHDR_HIP_PIX_FMT_YUV422)) != 0) {
+          return rc;
+        }
         for (int k = 0; k < m; ++k) {
           jpg[2 * (size_t)k].quality = quality;
           jpg[2 * (size_t)k].icc = &f[k].icc;
           uhdr_hip_image_t g = c[(size_t)k];   // (generate has filled in width, height and stride)
           jpg[2 * (size_t)k + 1] = rgb_map != 0 ? gainmap_rgb_jpeg(g) : gainmap_jpeg(g, g.luma_stride);
+          eo.to(&jpg[2 * (size_t)k]);
+          eo.to(&jpg[2 * (size_t)k + 1]);
         }
         if ((rc = compress_to_host(st, s, 2 * m, jpg.data(), true, dev_range, dev_range ? 8 * (size_t)m : 0, range.data())) != UHDR_HIP_NO_ERROR)
           return rc;
@@ -3635,6 +3794,26 @@ int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images
   static const uhdr_hip_image_t none{};
   return encode_packed_files(n, hdr_images, sdr_images != nullptr ? sdr_images : &none, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size,
                              status, rgb_map, mem_space, stream, nullptr, nullptr);
+}
+
+// the packed call with the primary image's sampling and the encoder's options said; YUV420 and NULL opts:
+// that call
+int uhdr_hip_jpegr_encode_packed_sampling_batch(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf,
+                                                int quality, const void* const* exif, const size_t* exif_size, void* const* out,
+                                                const size_t* out_capacity, size_t* out_size, int* status, int rgb_map, int primary_sampling,
+                                                const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
+  EncOpt eo;
+  const int orc = encode_opts(opts, &eo);
+  if (orc != UHDR_HIP_NO_ERROR) return orc;
+  if (primary_sampling != UHDR_HIP_PIX_FMT_YUV444 && primary_sampling != UHDR_HIP_PIX_FMT_YUV422 && primary_sampling != UHDR_HIP_PIX_FMT_YUV420)
+    return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (n < 0 || (n > 0 && (hdr_images == nullptr || sdr_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  static const uhdr_hip_image_t none{};
+  return encode_packed_files(n, hdr_images, sdr_images != nullptr ? sdr_images : &none, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size,
+                             status, rgb_map, mem_space, stream, nullptr, nullptr, -1, primary_sampling, eo);
 }
 
 // the packed API-0: the same files from the HDR images alone

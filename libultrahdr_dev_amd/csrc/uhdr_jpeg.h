@@ -11,16 +11,21 @@ namespace jpeg {
 struct Plane {
   const uint8_t* p;
   int w, h, stride;
-  int pad_cols;   // columns >= w read as zero (the reference copies the row into a zero-padded buffer) instead of from p
+  int pad_cols;   // columns >= w read as zero (the reference copies the row into a zero-padded buffer) instead of from p;
+                  // kPadReplicate: libjpeg's own edge expansion instead of either rule -- the last column repeated, then the last row
   int aligned4;   // p and stride are multiples of 4: whole-dword row loads
 };
+constexpr int kPadReplicate = 2;
 struct Job {
   Plane plane[3];          // Y, Cb, Cr (one plane: only [0])
   uint16_t q_lum[64], q_chr[64];   // quantisation tables in zigzag order
   uint32_t m_lum[64], m_chr[64];   // floor(2^32 / (q << 3)) + 1: n / (q << 3) == mulhi(n, m) for n < 2^16 (exact: n * (q << 3) < 2^32)
   uint32_t nblk;           // blocks in entropy-coding order, dummy edge blocks included
   uint32_t ybw, ybh;       // luma size in blocks
-  uint32_t mcus_x;         // MCUs per row (4:2:0)
+  uint32_t mcus_x;         // MCUs per row (three planes)
+  uint32_t hs, vs;         // luma sampling factors of three planes, {1,2} x {1,2}, both chroma components 1x1 (as DecInfo's): an MCU is
+                           // hs * vs luma blocks, in rows of hs, followed by Cb and Cr.  2x2 = 4:2:0; one plane and rgb: 1x1
+  int sampled;             // three planes whose hs x vs is not 2x2: the block geometry is locate_sampled's (0 for 4:2:0, one plane and rgb)
   int gray;
   int rgb;                 // 4:4:4 from interleaved RGBA (plane[0]: the pixels, stride in bytes); an MCU is one block each of Y, Cb, Cr
   // workspace (device)
@@ -39,7 +44,7 @@ struct Job {
   uint32_t* hdr_len;       // the header's length, known once k_jpeg_opt_tables_batch has written the DHT and SOS segments
   // restart intervals (rst_blocks != 0): the job runs through the k_jpeg_rst_* launches of its round, with either kind of tables
   uint32_t rst_blocks;     // blocks per interval: libjpeg's restart_interval (MCUs, 1 .. 65535) x rst_bpm
-  uint32_t rst_bpm;        // blocks per MCU: 6 (4:2:0), 3 (4:4:4) or 1
+  uint32_t rst_bpm;        // blocks per MCU: hs * vs + 2 (6 for 4:2:0, 4 for 4:2:2 and 4:4:0, 3 for 4:4:4) or 1
   uint32_t rst_marks;      // RSTn markers in the stream: one behind every interval but the last
   uint32_t* rst_pfx;       // nblk: the bits of the blocks in front of each, modulo 2^32, without padding and markers
   uint32_t* rst_mark;      // rst_marks: where each marker's 0xFF stands in the packed stream (bytes), ascending
@@ -52,8 +57,11 @@ struct Layout {
 hipError_t upload_tables();
 void quant_table(int quality, bool chroma, uint16_t out_natural[64]);
 void zigzag_table(const uint16_t natural[64], uint16_t zz[64]);
-// geom: what the frame header declares -- the 4:2:0 and single-plane files of the reference's encoder, or three 1x1 components
-enum Geometry : int { kGeom420 = 0, kGeomGray = 1, kGeomRgb444 = 2 };
+// geom: what the frame header declares -- the 4:2:0 and single-plane files of the reference's encoder, three 1x1 components from
+// RGBA pixels (kGeomRgb444) or from planes (kGeom444), or 2x1 / 1x2 luma over 1x1 chroma planes (kGeom422 / kGeom440)
+enum Geometry : int { kGeom420 = 0, kGeomGray = 1, kGeomRgb444 = 2, kGeom444 = 3, kGeom422 = 4, kGeom440 = 5 };
+inline int geom_hs(Geometry g) { return (g == kGeom420 || g == kGeom422) ? 2 : 1; }
+inline int geom_vs(Geometry g) { return (g == kGeom420 || g == kGeom440) ? 2 : 1; }
 // prefix_only: SOI ... SOF alone -- the DHT and SOS segments of a file with optimised tables are written on the device
 // restart_interval != 0 (and not prefix_only): a DRI segment between the last DHT and SOS
 void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& out, bool prefix_only = false,
@@ -114,6 +122,11 @@ struct Rgba420Batch {
 static_assert(sizeof(Rgba420Batch) <= 4096, "k_rgba_to_ycc420's kernel arguments exceed the kernarg segment");
 inline size_t rgba420_plane_bytes(size_t w, size_t h) { return 384 * ((w + 15) / 16) * ((h + 15) / 16); }
 hipError_t launch_rgba_to_ycc420(const Rgba420Batch& b, int n, hipStream_t s);   // one launch for n <= kRgba420Chunk images of any sizes
+// The same for a 4:2:2 file (2x1 luma sampling): jcsample.c's h2v1_downsample of the chroma.  With mcw x mch MCUs (16 x 8 pixels):
+// Y is 16 mcw x 8 mch at y, Cb and Cr are 8 mcw x 8 mch each at cb and cb + 64 mcw mch, rows packed.  Rgba420Image's fields, with mcw
+// and mch counting these MCUs.
+inline size_t rgba422_plane_bytes(size_t w, size_t h) { return 256 * ((w + 15) / 16) * ((h + 7) / 8); }
+hipError_t launch_rgba_to_ycc422(const Rgba420Batch& b, int n, hipStream_t s);
 
 // ---- decoder (uhdr_jpeg_dec.hip) -------------------------------------------------------------------------------------
 struct HuffSpec {            // one DHT table in canonical form (T.81 Annex C)

@@ -15,6 +15,7 @@
 //   k_jpeg_stuff_copy   one thread per 64 bytes: copy to the output with 0x00 stuffed after every 0xFF, EOI at the end
 //   k_rgba_to_ycc420    (in front of the chain, uhdr_hip_jpeg_encode_rgba420_batch only) RGBA8888 -> the Y, Cb, Cr planes libjpeg's
 //                       colour conversion and h2v2 downsampler hand its FDCT, padded to whole MCUs as libjpeg pads them
+//   k_rgba_to_ycc422    the same for a 4:2:2 file: h2v1 downsampler, MCUs of 16 x 8 pixels
 //   k_jpeg_opt_*        (Job::optimize) the same chain with Huffman tables built from the image's own symbol counts, see below
 //   k_jpeg_rst_*        (Job::rst_blocks) the same chain with restart intervals -- padding, RSTn markers, the DC prediction cut --, see below
 //
@@ -157,7 +158,7 @@ void build_header(int w, int h, Geometry geom, int quality, const void* icc, siz
   b.push_back((uint8_t)nc);
   for (int c = 0; c < nc; ++c) {
     b.push_back((uint8_t)(c + 1));
-    b.push_back((uint8_t)((c == 0 && geom == kGeom420) ? 0x22 : 0x11));
+    b.push_back((uint8_t)(c == 0 ? (geom_hs(geom) << 4) | geom_vs(geom) : 0x11));
     b.push_back((uint8_t)(c == 0 ? 0 : 1));
   }
   if (prefix_only) return;   // DHT and SOS: write_opt_header's, in this order
@@ -177,6 +178,7 @@ void build_header(int w, int h, Geometry geom, int quality, const void* icc, siz
 // Entropy-coding order (libjpeg jccoefct.c): one plane: blocks in raster order; 4:2:0: per MCU (16x16 pixels) Y00 Y01 Y10 Y11
 // Cb Cr.  Blocks past the component's size in blocks are dummies: zero AC, DC of the block before them in the MCU.
 // 4:4:4 from RGBA (Job::rgb): per MCU (8x8 pixels) Y Cb Cr, MCUs in raster order; no dummies.
+// Planes of any other sampling (Job::hs, vs; the planar 4:4:4 among them): locate_sampled.
 struct BlockRef {
   int comp;        // 0 Y, 1 Cb, 2 Cr
   int br, bc;      // block row / column inside the component (of the source block for a dummy)
@@ -187,6 +189,23 @@ __device__ __forceinline__ BlockRef locate_rgb(const Job& j, uint32_t i) {
   const uint32_t mcu = i / 3u;
   b.comp = (int)(i - mcu * 3u);
   b.br = (int)(mcu / j.ybw); b.bc = (int)(mcu - (uint32_t)b.br * j.ybw); b.dummy = false;
+  return b;
+}
+// three planes with luma sampling other than 2x2 (Job::hs, vs): per MCU hs * vs luma blocks in rows of hs, then Cb Cr -- 3 blocks
+// (4:4:4, 8x8 pixels) or 4 (4:2:2, 16x8: Y0 Y1; 4:4:0, 8x16: Y0 above Y1).  The dummy rule is the 4:2:0 one: for 2x1 the right-hand
+// block of the last MCU column when the luma width in blocks is odd, for 1x2 the bottom block of the last MCU row
+__device__ __forceinline__ BlockRef locate_sampled(const Job& j, uint32_t i) {
+  BlockRef b;
+  const uint32_t nl = j.hs * j.vs;   // 1 or 2
+  uint32_t mcu, k;
+  if (nl == 1u) { mcu = i / 3u; k = i - mcu * 3u; }
+  else { mcu = i >> 2; k = i & 3u; }
+  const int mr = (int)(mcu / j.mcus_x), mc = (int)(mcu - (uint32_t)mr * j.mcus_x);
+  if (k >= nl) { b.comp = (int)(k - nl) + 1; b.br = mr; b.bc = mc; b.dummy = false; return b; }
+  b.comp = 0;
+  b.br = (int)j.vs * mr + (j.vs == 2u ? (int)k : 0); b.bc = (int)j.hs * mc + (j.hs == 2u ? (int)k : 0);
+  b.dummy = !(b.br < (int)j.ybh && b.bc < (int)j.ybw);
+  if (b.dummy) { b.br = (int)j.vs * mr; b.bc = (int)j.hs * mc; }   // (only block 1 of two can be one; block 0 is always real)
   return b;
 }
 __device__ __forceinline__ BlockRef locate(const Job& j, uint32_t i) {
@@ -209,9 +228,19 @@ __device__ __forceinline__ BlockRef locate(const Job& j, uint32_t i) {
   return b;
 }
 // index of the previous block of the same component (DC prediction), or UINT32_MAX for the first one
+__device__ __forceinline__ uint32_t dc_predecessor_sampled(const Job& j, uint32_t i) {   // 3 or 4 blocks per MCU (locate_sampled)
+  if (j.hs * j.vs == 1u) return i < 3u ? 0xFFFFFFFFu : i - 3u;
+  const uint32_t k = i & 3u;
+  if (k == 1u) return i - 1u;
+  if (i < 4u) return 0xFFFFFFFFu;
+  return k == 0u ? i - 3u : i - 4u;   // Y1 of the previous MCU; its Cb or Cr
+}
+// ANY false: the caller knows the job to be none of locate_sampled's (the planar FDCT kernels)
+template <bool ANY = true>
 __device__ __forceinline__ uint32_t dc_predecessor(const Job& j, uint32_t i) {
   if (j.gray) return i == 0u ? 0xFFFFFFFFu : i - 1u;
   if (j.rgb) return i < 3u ? 0xFFFFFFFFu : i - 3u;
+  if (ANY && j.sampled) return dc_predecessor_sampled(j, i);   // (uniform per job)
   const uint32_t mcu = i / 6u, k = i - mcu * 6u;
   if (k >= 4u) return mcu == 0u ? 0xFFFFFFFFu : i - 6u;
   if (k != 0u) return i - 1u;
@@ -271,6 +300,9 @@ __device__ __forceinline__ int quantise(int v, int q, uint32_t m) {
 }
 
 // the 64 level-shifted samples of block b (of its source block for a dummy), with the helper's padding rules
+// REPL: the plane may ask for libjpeg's own edge expansion (kPadReplicate) -- planes of the sampled jobs alone, so that the 4:2:0 and
+// one-plane kernels carry none of its code
+template <bool REPL = false>
 __device__ __forceinline__ void load_samples(const Plane& p, const BlockRef& b, int (&d)[64]) {
   const int r0 = b.br * 8, c0 = b.bc * 8;
   const bool inside = r0 + 8 <= p.h && (c0 + 8 <= p.w || !p.pad_cols);
@@ -283,6 +315,13 @@ __device__ __forceinline__ void load_samples(const Plane& p, const BlockRef& b, 
       d[r * 8 + 2] = (int)((a >> 16) & 0xff) - 128; d[r * 8 + 3] = (int)(a >> 24) - 128;
       d[r * 8 + 4] = (int)(bq & 0xff) - 128; d[r * 8 + 5] = (int)((bq >> 8) & 0xff) - 128;
       d[r * 8 + 6] = (int)((bq >> 16) & 0xff) - 128; d[r * 8 + 7] = (int)(bq >> 24) - 128;
+    }
+  } else if (REPL && p.pad_cols == kPadReplicate) {   // libjpeg's expand_right_edge, then its bottom-edge rows, on the plane's own grid
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      const uint8_t* row = p.p + (size_t)min(r0 + r, p.h - 1) * p.stride;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) d[r * 8 + c] = (int)row[min(c0 + c, p.w - 1)] - 128;
     }
   } else {
 #pragma unroll
@@ -381,14 +420,18 @@ __device__ __forceinline__ int pred_of(const Job& j, uint32_t i) {
   return p == 0xFFFFFFFFu ? 0 : (int)j.coef[(size_t)p * 64u];
 }
 // a job with restart intervals (Job::rst_blocks): the prediction of every component starts again at 0 with the interval -- its first MCU's
-// chroma blocks and first luma block have no predecessor; the other three luma blocks of a 4:2:0 MCU chain inside it as ever
+// chroma blocks and first luma block have no predecessor; the other luma blocks of an MCU (three for 4:2:0, one for 4:2:2 and 4:4:0)
+// chain inside it as ever.  The chroma blocks are the MCU's last two -- all but the first of three, and the only block of one plane
 __device__ __forceinline__ int pred_of_rst(const Job& j, uint32_t i) {
   const uint32_t r = i % j.rst_blocks;
-  if (r < j.rst_bpm && (j.rst_bpm != 6u || r == 0u || r >= 4u)) return 0;
+  if (r < j.rst_bpm && (r == 0u || r + 2u >= j.rst_bpm)) return 0;
   return pred_of(j, i);
 }
+// ANY false: the caller knows the job to be none of locate_sampled's (the planar FDCT kernels)
+template <bool ANY = true>
 __device__ __forceinline__ int comp_of(const Job& j, uint32_t i) {
   if (j.rgb) return (i % 3u) == 0u ? 0 : 1;
+  if (ANY && j.sampled) return j.hs * j.vs == 2u ? ((i & 3u) < 2u ? 0 : 1) : ((i % 3u) == 0u ? 0 : 1);   // (uniform per job)
   return j.gray ? 0 : ((i % 6u) < 4u ? 0 : 1);
 }
 
@@ -396,35 +439,39 @@ __device__ __forceinline__ int comp_of(const Job& j, uint32_t i) {
 // in registers, the number of bits its Huffman code takes (the prefix sum of those is where k_jpeg_emit writes).  The DC code needs
 // the quantised DC of the component's previous block, which another thread computes: the islow DC is the plain sum of the 64
 // level-shifted samples (pass 1 scales the row sums by 4, pass 2 descales by 4: exact), so it is had from that block's 64 bytes.
-// RGB: the job is a 4:4:4 one (Job::rgb), known at compile time so that the planar kernels carry none of its code
+// KIND: what the job is -- 4:2:0 or one plane (kKindPlanar), 4:4:4 from RGBA pixels (kKindRgb, Job::rgb) or three planes of another
+// sampling (kKindSampled, Job::hs, vs) --, known at compile time so that the planar kernels carry none of the others' code
 // COUNT false (a job with optimised tables): the coefficients alone -- the block's bits wait for its tables (k_jpeg_opt_count_batch)
-template <bool RGB, bool COUNT = true>
+constexpr int kKindPlanar = 0, kKindRgb = 1, kKindSampled = 2;
+__device__ __forceinline__ int kind_of(const Job& j) { return j.rgb ? kKindRgb : j.sampled ? kKindSampled : kKindPlanar; }
+template <int KIND, bool COUNT = true>
 __device__ __forceinline__ uint32_t fdct_quant_count_block(const Job& j, const uint32_t i);
 // workgroup wg of the image's grid (blockIdx.x of the single-image launch; the batched launch passes its workgroup inside the job)
-template <bool RGB>
+template <int KIND>
 __device__ __forceinline__ void fdct_quant_count_wg(const Job& j, const uint32_t wg) {
   const uint32_t i = wg * 128u + threadIdx.x;
   __shared__ uint32_t s_part[2];
   uint32_t my_bits = 0;
-  if (i < j.nblk) my_bits = fdct_quant_count_block<RGB>(j, i);
+  if (i < j.nblk) my_bits = fdct_quant_count_block<KIND>(j, i);
   // bits_blk[g]: the bits of workgroup g's 128 blocks.  k_jpeg_emit needs the bit offset of every block: inside a workgroup a block
   // scan, across workgroups the sum of the totals in front (a 4K frame has 1519), formed by every workgroup of the emit for itself
   const uint32_t total = block_sum<128>(my_bits, s_part);
   if (threadIdx.x == 0u) j.bits_blk[wg] = total;
 }
-__global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count(const Job j) { fdct_quant_count_wg<false>(j, blockIdx.x); }
+__global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count(const Job j) { fdct_quant_count_wg<kKindPlanar>(j, blockIdx.x); }
 
 // the work of one thread of k_jpeg_fdct_quant_count: block i's coefficients to memory, its number of bits returned
-template <bool RGB, bool COUNT>
+template <int KIND, bool COUNT>
 __device__ __forceinline__ uint32_t fdct_quant_count_block(const Job& j, const uint32_t i) {
-  const BlockRef b = RGB ? locate_rgb(j, i) : locate(j, i);
+  constexpr bool RGB = KIND == kKindRgb, SAMPLED = KIND == kKindSampled;
+  const BlockRef b = RGB ? locate_rgb(j, i) : SAMPLED ? locate_sampled(j, i) : locate(j, i);
   const Plane& p = j.plane[RGB ? 0 : b.comp];
   const uint16_t* q = b.comp == 0 ? j.q_lum : j.q_chr;   // zigzag order
   const uint32_t* qm = b.comp == 0 ? j.m_lum : j.m_chr;
   int16_t* out = j.coef + (size_t)i * 64u;
   int d[64];
   if (RGB) load_samples_rgb(p, b, d);
-  else load_samples(p, b, d);
+  else load_samples<SAMPLED>(p, b, d);
   int16_t c[64];
   if (b.dummy) {  // zero AC, DC of the source block
     int s = 0;
@@ -464,17 +511,18 @@ __device__ __forceinline__ uint32_t fdct_quant_count_block(const Job& j, const u
   }
   if (!COUNT) return 0u;
   int pred = 0;
-  const uint32_t pi = dc_predecessor(j, i);
+  const uint32_t pi = SAMPLED ? dc_predecessor_sampled(j, i) : dc_predecessor<false>(j, i);
   if (pi != 0xFFFFFFFFu) {
     int e[64];
     if (RGB) load_samples_rgb(p, locate_rgb(j, pi), e);
+    else if (SAMPLED) load_samples<true>(p, locate_sampled(j, pi), e);
     else load_samples(p, locate(j, pi), e);   // (the same component, so the same plane and quantiser)
     int s = 0;
 #pragma unroll
     for (int k = 0; k < 64; ++k) s += e[k];
     pred = (int)(int16_t)quantise(s, q[0], qm[0]);
   }
-  const int chroma = comp_of(j, i);
+  const int chroma = comp_of<SAMPLED>(j, i);
   CountSink cs;
   walk_coefs(c, pred, 2 * chroma, 2 * chroma + 1, cs);
   j.bits[i] = cs.bits;
@@ -712,8 +760,8 @@ __global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count_multi(const Job* 
   uint32_t first, count;
   const uint32_t k = job_of<128>(start, n, &first, &count);
   const Job& j = uniform_ref(jobs, k);
-  if (j.rgb) return;   // (uniform per workgroup) a 4:4:4 job: k_jpeg_fdct_quant_count_multi_rgb's
-  fdct_quant_count_wg<false>(j, blockIdx.x - first);
+  if (j.rgb | j.sampled) return;   // (uniform per workgroup) k_jpeg_fdct_quant_count_multi_rgb's or _sampled's
+  fdct_quant_count_wg<kKindPlanar>(j, blockIdx.x - first);
 }
 // the 4:4:4 jobs of the same grid; the two kernels are launched as the batch holds jobs of either kind
 __global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count_multi_rgb(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
@@ -721,7 +769,15 @@ __global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count_multi_rgb(const J
   const uint32_t k = job_of<128>(start, n, &first, &count);
   const Job& j = uniform_ref(jobs, k);
   if (!j.rgb) return;
-  fdct_quant_count_wg<true>(j, blockIdx.x - first);
+  fdct_quant_count_wg<kKindRgb>(j, blockIdx.x - first);
+}
+// and the jobs of three planes with 1x1, 2x1 or 1x2 luma sampling
+__global__ void __launch_bounds__(128) k_jpeg_fdct_quant_count_multi_sampled(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  if (kind_of(j) != kKindSampled) return;
+  fdct_quant_count_wg<kKindSampled>(j, blockIdx.x - first);
 }
 
 // The single-image path clears the whole worst-case stream area (208 B per block, 40 MB for a 4K frame) before the emit ORs into
@@ -917,9 +973,9 @@ __global__ void __launch_bounds__(128) k_jpeg_opt_fdct_batch(const Job* __restri
   uint32_t first, count;
   const uint32_t k = job_of<128>(start, n, &first, &count);
   const Job& j = uniform_ref(jobs, k);
-  if (j.rgb) return;   // (uniform per workgroup) k_jpeg_opt_fdct_batch_rgb's
+  if (j.rgb | j.sampled) return;   // (uniform per workgroup) k_jpeg_opt_fdct_batch_rgb's or _sampled's
   const uint32_t i = (blockIdx.x - first) * 128u + threadIdx.x;
-  if (i < j.nblk) fdct_quant_count_block<false, false>(j, i);
+  if (i < j.nblk) fdct_quant_count_block<kKindPlanar, false>(j, i);
 }
 __global__ void __launch_bounds__(128) k_jpeg_opt_fdct_batch_rgb(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
   uint32_t first, count;
@@ -927,7 +983,15 @@ __global__ void __launch_bounds__(128) k_jpeg_opt_fdct_batch_rgb(const Job* __re
   const Job& j = uniform_ref(jobs, k);
   if (!j.rgb) return;
   const uint32_t i = (blockIdx.x - first) * 128u + threadIdx.x;
-  if (i < j.nblk) fdct_quant_count_block<true, false>(j, i);
+  if (i < j.nblk) fdct_quant_count_block<kKindRgb, false>(j, i);
+}
+__global__ void __launch_bounds__(128) k_jpeg_sampled_opt_fdct_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  if (kind_of(j) != kKindSampled) return;
+  const uint32_t i = (blockIdx.x - first) * 128u + threadIdx.x;
+  if (i < j.nblk) fdct_quant_count_block<kKindSampled, false>(j, i);
 }
 // The symbols walk_coefs codes, counted.  The counters of a workgroup's 128 blocks live in LDS: a flat image sends every lane to the
 // same two bins (EOB, DC category 0), which the LDS adds up at its own rate, and device memory sees one atomic per bin that is not
@@ -1348,16 +1412,14 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
     if (jobs_in[k].rst_blocks != 0) continue;
     (jobs_in[k].optimize ? no : nd) += 1;
   }
-  bool any_planar = false, any_rgb = false, any_opt_planar = false, any_opt_rgb = false;
-  bool any_rst_planar = false, any_rst_rgb = false, any_rst_opt = false;
+  // which of the three FDCT kernels each group of jobs needs: [0] 4:2:0 and one plane, [1] RGBA pixels, [2] planes of another sampling
+  bool any_def[3] = {false, false, false}, any_opt[3] = {false, false, false}, any_rst[3] = {false, false, false};
+  bool any_rst_opt = false;
   for (int k = 0, at_d = 0, at_o = nd, at_r = nd + no; k < n; ++k) {
     const bool rst = jobs_in[k].rst_blocks != 0, opt = !rst && jobs_in[k].optimize != 0;
-    if (rst) {
-      (jobs_in[k].rgb ? any_rst_rgb : any_rst_planar) = true;
-      any_rst_opt = any_rst_opt || jobs_in[k].optimize != 0;
-    } else {
-      (opt ? (jobs_in[k].rgb ? any_opt_rgb : any_opt_planar) : (jobs_in[k].rgb ? any_rgb : any_planar)) = true;
-    }
+    const int kind = jobs_in[k].rgb ? 1 : jobs_in[k].sampled ? 2 : 0;   // (kind_of)
+    (rst ? any_rst : opt ? any_opt : any_def)[kind] = true;
+    if (rst) any_rst_opt = any_rst_opt || jobs_in[k].optimize != 0;
     const int at = rst ? at_r++ : opt ? at_o++ : at_d++;
     Job& j = jobs[at];
     j = jobs_in[k];
@@ -1392,8 +1454,9 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
   if (nd > 0) {
     const uint32_t nj = (uint32_t)nd;
     const dim3 gb(blk_start[nd]), gc(stuff_start[nd]);
-    if (any_planar) hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi, gb, bb, 0, s, dj, dblk, nj);
-    if (any_rgb) hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi_rgb, gb, bb, 0, s, dj, dblk, nj);
+    if (any_def[0]) hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi, gb, bb, 0, s, dj, dblk, nj);
+    if (any_def[1]) hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi_rgb, gb, bb, 0, s, dj, dblk, nj);
+    if (any_def[2]) hipLaunchKernelGGL(k_jpeg_fdct_quant_count_multi_sampled, gb, bb, 0, s, dj, dblk, nj);
     hipLaunchKernelGGL(k_jpeg_clear_multi, gb, bb, 0, s, dj, dblk, nj);
     hipLaunchKernelGGL(k_jpeg_emit_multi, gb, bb, 0, s, dj, dblk, nj);
     hipLaunchKernelGGL(k_jpeg_stuff_count_multi, gc, bc, 0, s, dj, dstuff, nj);
@@ -1407,8 +1470,9 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
     const uint32_t* ostuff = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(opt_stuff_start) - host_desc));
     const dim3 gb(opt_blk_start[nj]), gc(opt_stuff_start[nj]);
     hipLaunchKernelGGL(k_jpeg_opt_zero_batch, dim3(nj), bc, 0, s, oj);
-    if (any_opt_planar) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch, gb, bb, 0, s, oj, oblk, nj);
-    if (any_opt_rgb) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch_rgb, gb, bb, 0, s, oj, oblk, nj);
+    if (any_opt[0]) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch, gb, bb, 0, s, oj, oblk, nj);
+    if (any_opt[1]) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch_rgb, gb, bb, 0, s, oj, oblk, nj);
+    if (any_opt[2]) hipLaunchKernelGGL(k_jpeg_sampled_opt_fdct_batch, gb, bb, 0, s, oj, oblk, nj);
     hipLaunchKernelGGL(k_jpeg_opt_hist_batch, gb, bb, 0, s, oj, oblk, nj);
     hipLaunchKernelGGL(k_jpeg_opt_tables_batch, dim3(nj), bc, 0, s, oj, oout);
     hipLaunchKernelGGL(k_jpeg_opt_count_batch, gb, bb, 0, s, oj, oblk, nj);
@@ -1425,8 +1489,9 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
     const uint32_t* rstuff = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(rst_stuff_start) - host_desc));
     const dim3 gb(rst_blk_start[nj]), gc(rst_stuff_start[nj]);
     if (any_rst_opt) hipLaunchKernelGGL(k_jpeg_opt_zero_batch, dim3(nj), bc, 0, s, rj);
-    if (any_rst_planar) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch, gb, bb, 0, s, rj, rblk, nj);
-    if (any_rst_rgb) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch_rgb, gb, bb, 0, s, rj, rblk, nj);
+    if (any_rst[0]) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch, gb, bb, 0, s, rj, rblk, nj);
+    if (any_rst[1]) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch_rgb, gb, bb, 0, s, rj, rblk, nj);
+    if (any_rst[2]) hipLaunchKernelGGL(k_jpeg_sampled_opt_fdct_batch, gb, bb, 0, s, rj, rblk, nj);
     if (any_rst_opt) hipLaunchKernelGGL(k_jpeg_rst_hist_batch, gb, bb, 0, s, rj, rblk, nj);
     hipLaunchKernelGGL(k_jpeg_rst_tables_batch, dim3(nj), bc, 0, s, rj, rout);
     hipLaunchKernelGGL(k_jpeg_rst_count_batch, gb, bb, 0, s, rj, rblk, nj);
@@ -1499,6 +1564,59 @@ __global__ void __launch_bounds__(256) k_rgba_to_ycc420(const Rgba420Batch b) {
   uint8_t* cbp = im.cb + (size_t)uy * cs + 4u * ux;
   *reinterpret_cast<uint32_t*>(cbp) = cbw;
   *reinterpret_cast<uint32_t*>(cbp + 64u * (size_t)im.mcw * im.mch) = crw;
+}
+// ---- RGBA8888 -> 4:2:2 planes ---------------------------------------------------------------------------------------------------------
+// A thread owns an 8 x 1 pixel piece of the padded image (16 mcw x 8 mch pixels; blockIdx.y = image): 32 bytes in -- neighbouring
+// threads read neighbouring pieces of a row --, 8 luma bytes and four bytes each of Cb and Cr out.  Padding is a clamp of the source
+// coordinates: columns to w - 1 (expand_right_edge on the full-resolution row, in front of the downsampler), rows to h - 1 (the
+// chroma keeps the image's rows, so the last downsampled row is the last row's).
+__global__ void __launch_bounds__(256) k_rgba_to_ycc422(const Rgba420Batch b) {
+  const Rgba420Image& im = b.img[blockIdx.y];
+  const uint32_t ucols = 2u * im.mcw, units = ucols * 8u * im.mch;
+  const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+  if (idx >= units) return;
+  const uint32_t uy = idx / ucols, ux = idx - uy * ucols;
+  const uint32_t x0 = ux * 8u;
+  const uint32_t* row = im.src + (size_t)min(uy, im.h - 1u) * im.stride;
+  uint32_t px[8];
+  if (x0 + 8u <= im.w && (reinterpret_cast<uintptr_t>(row + x0) & 15u) == 0u) {
+    const uint4 a = reinterpret_cast<const uint4*>(row + x0)[0], c = reinterpret_cast<const uint4*>(row + x0)[1];
+    px[0] = a.x; px[1] = a.y; px[2] = a.z; px[3] = a.w;
+    px[4] = c.x; px[5] = c.y; px[6] = c.z; px[7] = c.w;
+  } else {
+#pragma unroll
+    for (int x = 0; x < 8; ++x) px[x] = row[min(x0 + (uint32_t)x, im.w - 1u)];
+  }
+  uint32_t yv[2] = {0u, 0u};
+  int cbs[8], crs[8];
+#pragma unroll
+  for (int x = 0; x < 8; ++x) {   // jccolor.c rgb_ycc_convert (k_rgba_to_ycc420's constants)
+    const int R = (int)(px[x] & 0xffu), G = (int)((px[x] >> 8) & 0xffu), B = (int)((px[x] >> 16) & 0xffu);
+    const int Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
+    cbs[x] = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16;
+    crs[x] = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
+    yv[x >> 2] |= (uint32_t)Y << (8 * (x & 3));
+  }
+  // h2v1_downsample: (a + b + bias) >> 1, bias 0, 1, 0, 1 ... along the row (this thread's first chroma column is even)
+  uint32_t cbw = 0u, crw = 0u;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int bias = q & 1;
+    cbw |= (uint32_t)((cbs[2 * q] + cbs[2 * q + 1] + bias) >> 1) << (8 * q);
+    crw |= (uint32_t)((crs[2 * q] + crs[2 * q + 1] + bias) >> 1) << (8 * q);
+  }
+  *reinterpret_cast<uint2*>(im.y + (size_t)uy * 16u * im.mcw + x0) = make_uint2(yv[0], yv[1]);
+  uint8_t* cbp = im.cb + (size_t)uy * 8u * im.mcw + 4u * ux;
+  *reinterpret_cast<uint32_t*>(cbp) = cbw;
+  *reinterpret_cast<uint32_t*>(cbp + 64u * (size_t)im.mcw * im.mch) = crw;
+}
+hipError_t launch_rgba_to_ycc422(const Rgba420Batch& b, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (n > kRgba420Chunk) return hipErrorInvalidValue;
+  uint32_t units = 0;
+  for (int k = 0; k < n; ++k) units = std::max(units, 16u * b.img[k].mcw * b.img[k].mch);
+  hipLaunchKernelGGL(k_rgba_to_ycc422, dim3((units + 255u) / 256u, (unsigned)n), dim3(256), 0, s, b);
+  return hipGetLastError();
 }
 hipError_t launch_rgba_to_ycc420(const Rgba420Batch& b, int n, hipStream_t s) {
   if (n <= 0) return hipSuccess;

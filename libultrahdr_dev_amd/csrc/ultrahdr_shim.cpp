@@ -264,6 +264,30 @@ bool JpegEncoderHelperHip::compressImage(const uint8_t* yBuffer, const uint8_t* 
   return rc == UHDR_HIP_NO_ERROR;
 }
 
+bool JpegEncoderHelperHip::compressPlanes(const uint8_t* yBuffer, const uint8_t* cbBuffer, int width, int height, int lumaStride, int chromaStride,
+                                          int quality, const void* iccBuffer, unsigned int iccSize, int pixelFormat) {
+  if (pixelFormat == UHDR_HIP_PIX_FMT_YUV420 || pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME)
+    return compressImage(yBuffer, pixelFormat == UHDR_HIP_PIX_FMT_MONOCHROME ? nullptr : cbBuffer, width, height, lumaStride, chromaStride, quality,
+                         iccBuffer, iccSize);
+  mResultBuffer.clear();
+  if (pixelFormat != UHDR_HIP_PIX_FMT_YUV444 && pixelFormat != UHDR_HIP_PIX_FMT_YUV422 && pixelFormat != UHDR_HIP_PIX_FMT_YUV440) return false;
+  if (width <= 0 || height <= 0 || lumaStride < 0 || chromaStride < 0 || uhdr_hip_init(0) != UHDR_HIP_NO_ERROR) return false;
+  const uhdr_hip_image_t img = {const_cast<uint8_t*>(yBuffer), (size_t)width, (size_t)height, UHDR_HIP_CG_UNSPECIFIED,
+                                const_cast<uint8_t*>(cbBuffer), (size_t)lumaStride, (size_t)chromaStride, pixelFormat};
+  const size_t icc_n = iccSize;
+  mResultBuffer.resize((size_t)width * height * 3 + 65536);
+  size_t n = 0, cap = mResultBuffer.size();
+  void* out = mResultBuffer.data();
+  int rc = uhdr_hip_jpeg_encode_planes_batch_opts(1, &img, &quality, &iccBuffer, &icc_n, &out, &cap, &n, nullptr, nullptr, UHDR_HIP_MEM_HOST, nullptr);
+  if (rc == UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE) {   // n holds the size needed
+    mResultBuffer.resize(n);
+    out = mResultBuffer.data(); cap = n;
+    rc = uhdr_hip_jpeg_encode_planes_batch_opts(1, &img, &quality, &iccBuffer, &icc_n, &out, &cap, &n, nullptr, nullptr, UHDR_HIP_MEM_HOST, nullptr);
+  }
+  mResultBuffer.resize(rc == UHDR_HIP_NO_ERROR ? n : 0);
+  return rc == UHDR_HIP_NO_ERROR;
+}
+
 bool JpegDecoderHelperHip::decompressImage(const void* image, int length, decode_mode_t decodeTo, int scaleDenom) {
   mResultBuffer.clear();
   mWidth = mHeight = 0;
@@ -458,9 +482,16 @@ status_t JpegRHip::encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_u
   if (mGainMapScaleFactor != 4) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;   // setGainMapScaleFactor: the packed calls write factor 4 only
   if (hdr_image_ptr == nullptr || sdr_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
   const uhdr_hip_image_t h = to_c_packed(*hdr_image_ptr), sd = to_c_packed(*sdr_image_ptr);
+  if (mPrimarySampling != UHDR_HIP_PIX_FMT_YUV420 && mContentBoost >= 0) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;   // setPrimarySampling
   return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
     const void* ex = exif_ptr(exif);
     const size_t exn = exif_len(exif);
+    if (mPrimarySampling != UHDR_HIP_PIX_FMT_YUV420) {
+      const uhdr_hip_jpeg_encode_opts_t opts = {(uint32_t)sizeof(uhdr_hip_jpeg_encode_opts_t),
+                                                mOptimizeHuffman ? (uint32_t)UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN : 0u, mRestartInterval, mRestartInRows};
+      return uhdr_hip_jpegr_encode_packed_sampling_batch(1, &h, &sd, (int)hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr,
+                                                         mMultiChannelGainMap ? 1 : 0, mPrimarySampling, &opts, UHDR_HIP_MEM_HOST, nullptr);
+    }
     if (mContentBoost >= 0)   // setContentBoost: the adaptive packed call; one file, so the call's status is the file's
       return uhdr_hip_jpegr_encode_packed_adaptive_batch(1, &h, &sd, (int)hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, nullptr, nullptr,
                                                          mMultiChannelGainMap ? 1 : 0, mContentBoost, UHDR_HIP_MEM_HOST, nullptr);
@@ -474,6 +505,25 @@ status_t JpegRHip::encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, ultrah
   if (mGainMapScaleFactor != 4) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;   // setGainMapScaleFactor
   if (hdr_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
   const uhdr_hip_image_t h = to_c_packed(*hdr_image_ptr);
+  if (mPrimarySampling != UHDR_HIP_PIX_FMT_YUV420) {   // setPrimarySampling: the packed API-0's SDR image first, then the call with a pair
+    if (mContentBoost >= 0) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;
+    if (h.data == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
+    if (h.width == 0 || h.height == 0 || h.width > 8192 || h.height > 8192) return ERROR_ULTRAHDR_UNSUPPORTED_WIDTH_HEIGHT;
+    if (uhdr_hip_init(0) != UHDR_HIP_NO_ERROR) return ERROR_ULTRAHDR_INSUFFICIENT_RESOURCE;
+    std::vector<uint32_t> sdr_px(h.width * h.height);
+    uhdr_hip_image_t sd = {sdr_px.data(), h.width, h.height, h.colorGamut, nullptr, h.width, 0, UHDR_HIP_PIX_FMT_RGBA8888};
+    float headroom = 0.0f;
+    const int trc = uhdr_hip_tonemap_packed(&h, &sd, (int)hdr_tf, UHDR_HIP_TONEMAP_REINHARD_MAXRGB, mHdrPeakNits, &headroom, UHDR_HIP_MEM_HOST, nullptr);
+    if (trc != UHDR_HIP_NO_ERROR) return static_cast<status_t>(trc);
+    return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
+      const void* ex = exif_ptr(exif);
+      const size_t exn = exif_len(exif);
+      const uhdr_hip_jpeg_encode_opts_t opts = {(uint32_t)sizeof(uhdr_hip_jpeg_encode_opts_t),
+                                                mOptimizeHuffman ? (uint32_t)UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN : 0u, mRestartInterval, mRestartInRows};
+      return uhdr_hip_jpegr_encode_packed_sampling_batch(1, &h, &sd, (int)hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr,
+                                                         mMultiChannelGainMap ? 1 : 0, mPrimarySampling, &opts, UHDR_HIP_MEM_HOST, nullptr);
+    });
+  }
   return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
     const void* ex = exif_ptr(exif);
     const size_t exn = exif_len(exif);
