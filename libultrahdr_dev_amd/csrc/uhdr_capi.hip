@@ -1656,12 +1656,10 @@ struct EncJpeg {
   uint32_t restart_interval = 0, restart_in_rows = 0;   // uhdr_hip_jpeg_encode_opts_t's, as given: the file's width decides (enc_restart)
 };
 
-// what the _ex and _opts encode calls say beyond their arguments; a bool is the _ex calls' flag alone
+// what the _ex and _opts encode calls say beyond their arguments (encode_flags, encode_opts)
 struct EncOpt {
   bool optimize = false;
   uint32_t restart_interval = 0, restart_in_rows = 0;
-  EncOpt() = default;
-  EncOpt(bool o) : optimize(o) {}
   void to(EncJpeg* e) const { e->optimize = optimize; e->restart_interval = restart_interval; e->restart_in_rows = restart_in_rows; }
 };
 
@@ -1680,6 +1678,13 @@ int encode_opts(const uhdr_hip_jpeg_encode_opts_t* opts, EncOpt* eo) {
   eo->restart_in_rows = opts->restart_in_rows;
   return UHDR_HIP_NO_ERROR;
 }
+// the same for the flags word of the _ex calls
+int encode_flags(int flags, EncOpt* eo) {
+  *eo = EncOpt();
+  if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  eo->optimize = (flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0;
+  return UHDR_HIP_NO_ERROR;
+}
 // MCUs per restart interval of one file (0: none) and, at *intervals, how many intervals that makes
 uint32_t enc_restart(const jpeg::Job& j, uint32_t restart_interval, uint32_t restart_in_rows, uint32_t* intervals) {
   const uint32_t bpm = j.gray ? 1u : j.hs * j.vs + 2u;
@@ -1695,6 +1700,12 @@ size_t enc_workspace_bytes(size_t w, size_t h, jpeg::Geometry geom, const EncOpt
   enc_restart(j, eo.restart_interval, eo.restart_in_rows, &intervals);
   jpeg::Layout l;
   return jpeg::workspace_bytes(j.nblk, &l, intervals);
+}
+// The first guess at a file's size, restart markers apart: what compress_to_host stages a file at when nobody says (cap == 0), and
+// what a file of a plain-JPEG batch holds of its round's page-locked memory.  One byte per pixel for 4:2:0 and monochrome files, three
+// for every geometry with more chroma (4:2:2 and 4:4:0 among them, for which two would do: the rule decides which files share a round).
+size_t enc_first_guess(size_t w, size_t h, jpeg::Geometry geom) {
+  return w * h * (geom == jpeg::kGeom420 || geom == jpeg::kGeomGray ? 1 : 3) + 65536;
 }
 // a file with restart intervals addresses its packed stream in 32 bits (jpeg::kMaxRestartBlocks); the table search has its own limit
 bool encodable_with(size_t w, size_t h, jpeg::Geometry geom, const EncOpt& eo);
@@ -1716,10 +1727,14 @@ bool encodable_with(size_t w, size_t h, jpeg::Geometry geom, const EncOpt& eo) {
 // its page-locked host pool, one jpeg::encode_batch_async writes the streams behind them and their sizes, and one synchronisation
 // ends it.  A file larger than its staging was cut off: it is compressed again in a context of its own, so that this one's host
 // pool, which holds the other files, is left alone.  A non-zero return is an error of the device or the runtime.
-// dev_extra (or null): extra_bytes of device memory that come down with the streams -- copied into the host pool behind the same
-// synchronisation, then to host_extra (the adaptive encode's boost ranges).
-int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool may_retry = true, const void* dev_extra = nullptr,
-                     size_t extra_bytes = 0, void* host_extra = nullptr) {
+// extra.dev (or null): extra.bytes of device memory that come down with the streams -- copied into the host pool behind the same
+// synchronisation, then to extra.host (the adaptive encode's boost ranges).
+struct EncExtra {
+  const void* dev = nullptr;
+  size_t bytes = 0;
+  void* host = nullptr;
+};
+int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool may_retry = true, const EncExtra& extra = EncExtra()) {
   std::vector<jpeg::Job> jobs((size_t)k);
   std::vector<jpeg::Layout> lay((size_t)k);
   std::vector<jpeg::BatchOut> outs((size_t)k);
@@ -1745,16 +1760,16 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     // Such a header is never longer than the default one -- baseline 8-bit data has at most 12 DC and 162 AC symbols, the sizes of
     // the Annex K tables --, so whatever is sized for the default header (a file's first-guess staging, a caller's capacity that
     // holds the default file) holds this one.
-    jpeg::build_header((int)e.img.width, (int)e.img.height, e.geom >= 0 ? (jpeg::Geometry)e.geom : enc_geom(e.img, e.rgb), e.quality,
-                       e.icc ? e.icc->data() : nullptr,
+    const jpeg::Geometry geom = e.geom >= 0 ? (jpeg::Geometry)e.geom : enc_geom(e.img, e.rgb);
+    jpeg::build_header((int)e.img.width, (int)e.img.height, geom, e.quality, e.icc ? e.icc->data() : nullptr,
                        e.icc ? e.icc->size() : 0, header[i], e.optimize, ri);
     // (the first guess holds the DRI segment and three bytes per interval as well)
-    if (im[i].cap == 0) im[i].cap = im[i].img.width * im[i].img.height * ((jobs[i].rgb || e.geom >= 0) ? 3 : 1) + 65536 + (ri != 0 ? 6 + 3 * (size_t)intervals : 0);
+    if (im[i].cap == 0) im[i].cap = enc_first_guess(e.img.width, e.img.height, geom) + (ri != 0 ? 6 + 3 * (size_t)intervals : 0);
     off[i] = hp_total;
     hp_total += round_up(e.to_dev ? header[i].size() : im[i].cap, 256);   // a device destination: the header's way there only
   }
   const size_t extra_off = hp_total;
-  if (dev_extra != nullptr) hp_total += round_up(extra_bytes, 256);
+  if (extra.dev != nullptr) hp_total += round_up(extra.bytes, 256);
   int rc;
   if ((rc = host_pool_reserve(st, hp_total)) != 0) return rc;
   if ((rc = pool_reserve(st, kEncWs, ws_total)) != 0) return rc;
@@ -1778,9 +1793,9 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     wss[i] = static_cast<uint8_t*>(st->pool[kEncWs]) + ws_off[i];
   }
   HIP_TRY(jpeg::encode_batch_async(k, jobs.data(), lay.data(), wss.data(), outs.data(), hp, static_cast<uint8_t*>(st->pool[kEncDesc]), s));
-  if (dev_extra != nullptr) HIP_TRY(hipMemcpyAsync(hp + extra_off, dev_extra, extra_bytes, hipMemcpyDeviceToHost, s));
+  if (extra.dev != nullptr) HIP_TRY(hipMemcpyAsync(hp + extra_off, extra.dev, extra.bytes, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (dev_extra != nullptr) memcpy(host_extra, hp + extra_off, extra_bytes);
+  if (extra.dev != nullptr) memcpy(extra.host, hp + extra_off, extra.bytes);
   for (int i = 0; i < k; ++i) {
     EncJpeg& e = im[i];
     const uint64_t total = sizes[i];
@@ -1843,7 +1858,7 @@ int stage_encoder_slice(uint8_t* dy, const uhdr_hip_image_t& img, uhdr_hip_image
 size_t enc_round_bytes(const uhdr_hip_image_t& img, bool host_in, bool host_out, const EncOpt& eo = EncOpt()) {
   size_t b = enc_workspace_bytes(img.width, img.height, enc_geom(img, false), eo);
   if (host_in) b += enc_stage_bytes(img);
-  if (host_out) b += img.width * img.height + 65536;
+  if (host_out) b += enc_first_guess(img.width, img.height, enc_geom(img, false));
   return b;
 }
 
@@ -1896,82 +1911,7 @@ int stage_sampled_slice(uint8_t* dy, const uhdr_hip_image_t& img, int geom, uhdr
   d->chroma_data = du; d->chroma_stride = dcs;
   return UHDR_HIP_NO_ERROR;
 }
-size_t sampled_round_bytes(const uhdr_hip_image_t& img, int geom, bool host_in, bool host_out, const EncOpt& eo) {
-  size_t b = enc_workspace_bytes(img.width, img.height, (jpeg::Geometry)geom, eo);
-  if (host_in) b += sampled_stage_bytes(img, geom);
-  if (host_out) b += img.width * img.height * 3 + 65536;
-  return b;
-}
 
-// One round of uhdr_hip_jpeg_encode_batch: files idx[0, m), their planes staged at the slot kEncYuv (host planes), every
-// compression through one compress_to_host.  Statuses and sizes of the round's files go to st_ / out_size.  A non-zero return is an
-// error of the device or the runtime.
-int jpeg_encode_round(DeviceState* st, hipStream_t s, bool host_in, bool host_out, const uhdr_hip_image_t* images, const int* quality,
-                      const void* const* icc, const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size,
-                      const int* idx, int m, int* st_, const EncOpt& eo, bool any_sampling = false) {
-  std::vector<EncJpeg> im((size_t)m);
-  std::vector<std::vector<uint8_t>> iccs((size_t)m);
-  // any_sampling (uhdr_hip_jpeg_encode_planes_batch_opts): a YUV444 / 422 / 440 image among the files is compressed as what it says
-  auto geom_of = [&](int i) { return any_sampling ? sampled_geom(images[i]) : -1; };
-  size_t stage_total = 0;
-  if (host_in) {
-    for (int k = 0; k < m; ++k) {
-      const int geom = geom_of(idx[k]);
-      stage_total += geom >= 0 ? sampled_stage_bytes(images[idx[k]], geom) : enc_stage_bytes(enc_image(images[idx[k]]));
-    }
-    int rc;
-    if ((rc = pool_reserve(st, kEncYuv, stage_total)) != 0) return rc;
-  }
-  size_t o = 0;
-  for (int k = 0; k < m; ++k) {
-    const int i = idx[k];
-    const int geom = geom_of(i);
-    const uhdr_hip_image_t img = geom >= 0 ? sampled_image(images[i], geom) : enc_image(images[i]);
-    uhdr_hip_image_t d = img;
-    if (host_in && geom >= 0) {
-      int rc;
-      if ((rc = stage_sampled_slice(static_cast<uint8_t*>(st->pool[kEncYuv]) + o, img, geom, &d, s)) != 0) return rc;
-      o += sampled_stage_bytes(img, geom);
-    } else if (host_in) {   // into the round's slice
-      int rc;
-      if ((rc = stage_encoder_slice(static_cast<uint8_t*>(st->pool[kEncYuv]) + o, img, &d, s)) != 0) return rc;
-      o += enc_stage_bytes(img);
-    }
-    const void* ip = icc ? icc[i] : nullptr;
-    const size_t in = icc ? icc_size[i] : 0;
-    if (ip != nullptr && in > 0) iccs[k].assign(static_cast<const uint8_t*>(ip), static_cast<const uint8_t*>(ip) + in);
-    EncJpeg& e = im[k];
-    e.img = d;
-    e.quality = quality[i];
-    e.icc = iccs[k].empty() ? nullptr : &iccs[k];
-    e.pad_ls = img.luma_stride;
-    e.pad_cs = img.chroma_stride;
-    e.geom = geom;
-    eo.to(&e);
-    if (host_out) {
-      e.keep_max = out_capacity[i];   // a file that will not fit is only measured
-    } else {
-      e.to_dev = true;
-      e.dev_out = static_cast<uint8_t*>(out[i]);
-      e.dev_cap = out_capacity[i];
-    }
-  }
-  const int rc = compress_to_host(st, s, m, im.data());
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
-  // the files from the page-locked staging into the caller's buffers: megabytes per 4K file, so a few host threads side by side
-  auto deliver = [&](int lo, int hi) {
-    for (int k = lo; k < hi; ++k) {
-      const int i = idx[k];
-      out_size[i] = im[k].n;
-      if (im[k].n > out_capacity[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
-      if (host_out) memcpy(out[i], im[k].bytes, im[k].n);
-      st_[i] = UHDR_HIP_NO_ERROR;
-    }
-  };
-  if (host_out) on_host_threads(m, deliver);
-  else deliver(0, m);
-  return UHDR_HIP_NO_ERROR;
-}
 }  // namespace
 
 extern "C" {
@@ -2026,214 +1966,6 @@ int uhdr_hip_jpeg_encode(const uhdr_hip_image_t* image, int quality, const void*
   return UHDR_HIP_NO_ERROR;
 }
 
-// the bodies of the batch calls below, behind the _ex and the _opts form of each
-static int jpeg_encode_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
-                                  void* const* out, const size_t* out_capacity, size_t* out_size, int* status, const EncOpt& eo, int mem_space,
-                                  void* stream, bool any_sampling = false);
-static int jpeg_encode_rgb_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
-                                      size_t* out_size, int* status, const EncOpt& eo, int mem_space, void* stream,
-                                      const void* const* icc = nullptr, const size_t* icc_size = nullptr);
-
-// uhdr_hip_jpeg_encode for n images in one call: a file that fails the single call's checks is not processed; the files of a round
-// share one jpeg::encode_batch_async launch set and one synchronisation (compress_to_host)
-int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
-                               void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream) {
-  return uhdr_hip_jpeg_encode_batch_ex(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, 0, mem_space, stream);
-}
-
-// flags == 0 is uhdr_hip_jpeg_encode_batch.  UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN: every file with Huffman tables of its own (DESIGN.md
-// section 7.1.1) -- the same pixels in fewer bytes; a file too large for libjpeg's table search is UNSUPPORTED_FEATURE
-int uhdr_hip_jpeg_encode_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
-                                  void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int flags, int mem_space,
-                                  void* stream) {
-  if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  return jpeg_encode_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status,
-                                EncOpt((flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0), mem_space, stream);
-}
-// opts == NULL, or no restart field set: uhdr_hip_jpeg_encode_batch_ex with opts->flags.  Otherwise every file with restart intervals
-// (DESIGN.md section 7.1.2), with either kind of tables
-int uhdr_hip_jpeg_encode_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
-                                    void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
-                                    const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
-  EncOpt eo;
-  const int rc = encode_opts(opts, &eo);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
-  return jpeg_encode_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, eo, mem_space, stream);
-}
-// uhdr_hip_jpeg_encode_batch_opts with YUV444 / 422 / 440 images compressed as what they are (DESIGN.md section 7.1.3); every other image of
-// the call is that call's, and all share the round's launches
-int uhdr_hip_jpeg_encode_planes_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
-                                           void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
-                                           const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
-  EncOpt eo;
-  const int rc = encode_opts(opts, &eo);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
-  return jpeg_encode_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, eo, mem_space, stream, true);
-}
-static int jpeg_encode_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
-                                  void* const* out, const size_t* out_capacity, size_t* out_size, int* status, const EncOpt& eo, int mem_space,
-                                  void* stream, bool any_sampling) {
-  if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (icc != nullptr && icc_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
-  std::vector<int> live;
-  for (int i = 0; i < n; ++i) {   // the single call's checks, in its order; a file that fails them is not processed
-    const uhdr_hip_image_t& im = images[i];
-    if (im.data == nullptr || (im.pixelFormat != UHDR_HIP_PIX_FMT_MONOCHROME && im.chroma_data == nullptr) ||
-        (out[i] == nullptr && out_capacity[i] != 0))
-      st_[i] = UHDR_HIP_ERROR_BAD_PTR;
-    else if (any_sampling && sampled_geom(im) >= 0) {
-      if ((st_[i] = sampled_check(im, sampled_geom(im), eo)) == UHDR_HIP_NO_ERROR) live.push_back(i);
-    }
-    else if (!encodable(im))
-      st_[i] = UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
-    else if (!encodable_with(im.width, im.height, enc_geom(im, false), eo))
-      st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-    else
-      live.push_back(i);
-  }
-  if (live.empty()) return finish_statuses(st_, status);
-  const bool host_in = mem_space == UHDR_HIP_MEM_HOST || mem_space == UHDR_HIP_MEM_HOST_TO_DEVICE;
-  const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE && mem_space != UHDR_HIP_MEM_HOST_TO_DEVICE;
-  size_t done = 0;
-  const int rc = run_rounds(
-      live.size(), (size_t)jpeg::kMaxBatchJobs, stream,
-      [&](size_t k) {
-        const uhdr_hip_image_t& im = images[live[k]];
-        const int geom = any_sampling ? sampled_geom(im) : -1;
-        return geom >= 0 ? sampled_round_bytes(im, geom, host_in, host_out, eo) : enc_round_bytes(enc_image(im), host_in, host_out, eo);
-      },
-      [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
-        return jpeg_encode_round(st, s, host_in, host_out, images, quality, icc, icc_size, out, out_capacity, out_size, &live[r0], m, st_.data(), eo,
-                                 any_sampling);
-      },
-      &done);
-  for (size_t k = done; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
-  return finish_statuses(st_, status);
-}
-
-// uhdr_hip_jpeg_encode_batch's conventions for RGBA8888 images, compressed as 4:4:4 (jpeg::kGeomRgb444): the file libjpeg writes for
-// in_color_space = JCS_RGB with all sampling factors 1.  No ICC.
-int uhdr_hip_jpeg_encode_rgb_batch(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
-                                   size_t* out_size, int* status, int mem_space, void* stream) {
-  return uhdr_hip_jpeg_encode_rgb_batch_ex(n, images, quality, out, out_capacity, out_size, status, 0, mem_space, stream);
-}
-
-// flags as in uhdr_hip_jpeg_encode_batch_ex
-int uhdr_hip_jpeg_encode_rgb_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
-                                      size_t* out_size, int* status, int flags, int mem_space, void* stream) {
-  if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  return jpeg_encode_rgb_batch_with(n, images, quality, out, out_capacity, out_size, status, EncOpt((flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0),
-                                    mem_space, stream);
-}
-// opts as in uhdr_hip_jpeg_encode_batch_opts
-int uhdr_hip_jpeg_encode_rgb_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
-                                        size_t* out_size, int* status, const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
-  EncOpt eo;
-  const int rc = encode_opts(opts, &eo);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
-  return jpeg_encode_rgb_batch_with(n, images, quality, out, out_capacity, out_size, status, eo, mem_space, stream);
-}
-// icc (uhdr_hip_jpeg_encode_rgba_batch_opts at YUV444 alone): an APP2 segment per file where the other calls put it
-static int jpeg_encode_rgb_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
-                                      size_t* out_size, int* status, const EncOpt& eo, int mem_space, void* stream, const void* const* icc,
-                                      const size_t* icc_size) {
-  if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (icc != nullptr && icc_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  for (int i = 0; i < n; ++i)
-    if (quality[i] < 0 || quality[i] > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
-  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
-  std::vector<int> live;
-  const bool host_in = mem_space == UHDR_HIP_MEM_HOST || mem_space == UHDR_HIP_MEM_HOST_TO_DEVICE;
-  const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE && mem_space != UHDR_HIP_MEM_HOST_TO_DEVICE;
-  for (int i = 0; i < n; ++i) {
-    const uhdr_hip_image_t& im = images[i];
-    if (im.data == nullptr || (!host_in && !al(im.data, 4)) || (out[i] == nullptr && out_capacity[i] != 0))
-      st_[i] = UHDR_HIP_ERROR_BAD_PTR;
-    else if (im.pixelFormat != UHDR_HIP_PIX_FMT_RGBA8888)
-      st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-    else if (im.width == 0 || im.height == 0 || im.width > 65500 || im.height > 65500 || (im.luma_stride != 0 && im.luma_stride < im.width) ||
-             im.luma_stride > (size_t)INT32_MAX / 4)   // (rows are addressed with an int byte pitch)
-      st_[i] = UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
-    else if (!encodable_with(im.width, im.height, jpeg::kGeomRgb444, eo))
-      st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-    else
-      live.push_back(i);
-  }
-  if (live.empty()) return finish_statuses(st_, status);
-  auto stage_pitch = [](const uhdr_hip_image_t& im) { return round_up(im.width * 4, 64); };   // bytes
-  size_t done = 0;
-  const int rc = run_rounds(
-      live.size(), (size_t)jpeg::kMaxBatchJobs, stream,
-      [&](size_t k) {
-        const uhdr_hip_image_t& im = images[live[k]];
-        size_t b = enc_workspace_bytes(im.width, im.height, jpeg::kGeomRgb444, eo);
-        if (host_in) b += round_up(stage_pitch(im) * im.height, 256);
-        if (host_out) b += im.width * im.height * 3 + 65536;
-        return b;
-      },
-      [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
-        const int* idx = &live[r0];
-        std::vector<EncJpeg> im((size_t)m);
-        std::vector<std::vector<uint8_t>> iccs((size_t)m);
-        size_t stage_total = 0;
-        int rc;
-        if (host_in) {
-          for (int k = 0; k < m; ++k) stage_total += round_up(stage_pitch(images[idx[k]]) * images[idx[k]].height, 256);
-          if ((rc = pool_reserve(st, kEncYuv, stage_total)) != 0) return rc;
-        }
-        size_t o = 0;
-        for (int k = 0; k < m; ++k) {
-          const int i = idx[k];
-          const void* ip = icc ? icc[i] : nullptr;
-          const size_t in = icc ? icc_size[i] : 0;
-          if (ip != nullptr && in > 0) iccs[(size_t)k].assign(static_cast<const uint8_t*>(ip), static_cast<const uint8_t*>(ip) + in);
-          uhdr_hip_image_t d = images[i];
-          if (d.luma_stride == 0) d.luma_stride = d.width;
-          d.chroma_data = nullptr; d.chroma_stride = 0;
-          if (host_in) {   // rows of 4 w bytes into the round's slice, at a 64-byte pitch
-            const size_t pitch = stage_pitch(d);
-            uint8_t* dst = static_cast<uint8_t*>(st->pool[kEncYuv]) + o;
-            if ((rc = h2d_plane(dst, pitch, d.data, d.luma_stride * 4, d.width * 4, d.height, 1, s)) != 0) return rc;
-            o += round_up(pitch * d.height, 256);
-            d.data = dst; d.luma_stride = pitch / 4;
-          }
-          EncJpeg& e = im[k];
-          e.img = d;
-          e.quality = quality[i];
-          e.icc = iccs[(size_t)k].empty() ? nullptr : &iccs[(size_t)k];
-          e.pad_ls = e.pad_cs = 0;
-          e.rgb = true;
-          eo.to(&e);
-          if (host_out) {
-            e.keep_max = out_capacity[i];   // a file that will not fit is only measured
-          } else {
-            e.to_dev = true;
-            e.dev_out = static_cast<uint8_t*>(out[i]);
-            e.dev_cap = out_capacity[i];
-          }
-        }
-        if ((rc = compress_to_host(st, s, m, im.data())) != UHDR_HIP_NO_ERROR) return rc;
-        auto deliver = [&](int lo, int hi) {
-          for (int k = lo; k < hi; ++k) {
-            const int i = idx[k];
-            out_size[i] = im[k].n;
-            if (im[k].n > out_capacity[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
-            if (host_out) memcpy(out[i], im[k].bytes, im[k].n);
-            st_[i] = UHDR_HIP_NO_ERROR;
-          }
-        };
-        if (host_out) on_host_threads(m, deliver);
-        else deliver(0, m);
-        return (int)UHDR_HIP_NO_ERROR;
-      },
-      &done);
-  for (size_t k = done; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
-  return finish_statuses(st_, status);
-}
-
 }  // extern "C"
 
 namespace {
@@ -2279,133 +2011,208 @@ int rgba420_planes(DeviceState* st, size_t slot, hipStream_t s, int m, const uhd
   HIP_TRY(s422 ? jpeg::launch_rgba_to_ycc422(b, m, s) : jpeg::launch_rgba_to_ycc420(b, m, s));
   return UHDR_HIP_NO_ERROR;
 }
-}  // namespace
 
-extern "C" {
-
-static int jpeg_encode_rgba420_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
-                                          const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
-                                          const EncOpt& eo, int mem_space, void* stream, bool s422 = false);
-
-// uhdr_hip_jpeg_encode_batch's conventions for RGBA8888 images compressed as 4:2:0: the planes libjpeg's colour conversion and
-// downsampler hand its FDCT come from one k_rgba_to_ycc420 launch per round, everything behind them is compress_to_host
-int uhdr_hip_jpeg_encode_rgba420_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
-                                       void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream) {
-  return uhdr_hip_jpeg_encode_rgba420_batch_ex(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, 0, mem_space, stream);
+// Rows of width * bpp bytes of a host image of packed pixels (luma_stride set, in pixels) into the slice at dst, at a 64-byte pitch:
+// *d (which may be the image itself) is the staged image, and the slice takes *bytes = rgba_stage_bytes of its pool slot.
+size_t rgba_stage_bytes(size_t width, size_t height, size_t bpp) { return round_up(round_up(width * bpp, 64) * height, 256); }
+int stage_rgba_rows(uint8_t* dst, const uhdr_hip_image_t h, size_t bpp, uhdr_hip_image_t* d, size_t* bytes, hipStream_t s) {
+  const size_t pitch = round_up(h.width * bpp, 64);
+  const int rc = h2d_plane(dst, pitch, h.data, h.luma_stride * bpp, h.width * bpp, h.height, 1, s);
+  if (rc != 0) return rc;
+  *d = h;
+  d->data = dst; d->luma_stride = pitch / bpp;
+  *bytes = rgba_stage_bytes(h.width, h.height, bpp);
+  return UHDR_HIP_NO_ERROR;
 }
 
-// flags as in uhdr_hip_jpeg_encode_batch_ex
-int uhdr_hip_jpeg_encode_rgba420_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
-                                          void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int flags, int mem_space,
-                                          void* stream) {
-  if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  return jpeg_encode_rgba420_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status,
-                                        EncOpt((flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0), mem_space, stream);
-}
-// opts as in uhdr_hip_jpeg_encode_batch_opts
-int uhdr_hip_jpeg_encode_rgba420_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
-                                            const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
-                                            const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
-  EncOpt eo;
-  const int rc = encode_opts(opts, &eo);
+// ---- the plain-JPEG encode batches: three families of files behind one driver (jpeg_encode_files) -------------------------------
+// A family says what the driver cannot know: kRoundCap (files per round), kQualityGate (a quality outside 0 .. 100 is the call's
+// error), check (one file's checks, in the family's order), geometry, extra_bytes (the device bytes a file holds of its round beyond
+// encoder workspace and first-guess file staging) and prepare: the round's files idx[0, m) into device memory -- host inputs staged
+// at the slot kEncYuv, converted planes at kEncSdr --, e[k] left with img, pad_ls / pad_cs, geom, rgb and mcu_planes.
+
+// planes as they are: 4:2:0 and monochrome images, and YUV444 / 422 / 440 ones where the call takes them (any_sampling:
+// uhdr_hip_jpeg_encode_planes_batch_opts; every other call compresses such an image as 4:2:0)
+struct PlanesFamily {
+  static constexpr size_t kRoundCap = (size_t)jpeg::kMaxBatchJobs;
+  static constexpr bool kQualityGate = false;
+  bool any_sampling;
+  int sampled(const uhdr_hip_image_t& im) const { return any_sampling ? sampled_geom(im) : -1; }
+  // the single call's checks, in its order
+  int check(const uhdr_hip_image_t& im, bool, const void* out, size_t out_capacity, const EncOpt& eo) const {
+    if (im.data == nullptr || (im.pixelFormat != UHDR_HIP_PIX_FMT_MONOCHROME && im.chroma_data == nullptr) ||
+        (out == nullptr && out_capacity != 0))
+      return UHDR_HIP_ERROR_BAD_PTR;
+    if (sampled(im) >= 0) return sampled_check(im, sampled(im), eo);
+    if (!encodable(im)) return UHDR_HIP_ERROR_RESOLUTION_MISMATCH;
+    if (!encodable_with(im.width, im.height, enc_geom(im, false), eo)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+    return UHDR_HIP_NO_ERROR;
+  }
+  jpeg::Geometry geometry(const uhdr_hip_image_t& im) const { return sampled(im) >= 0 ? (jpeg::Geometry)sampled(im) : enc_geom(im, false); }
+  size_t extra_bytes(const uhdr_hip_image_t& im, bool host_in) const {
+    if (!host_in) return 0;
+    return sampled(im) >= 0 ? sampled_stage_bytes(im, sampled(im)) : enc_stage_bytes(enc_image(im));
+  }
+  int prepare(DeviceState* st, hipStream_t s, const uhdr_hip_image_t* images, bool host_in, const int* idx, int m, EncJpeg* e) const {
+    int rc;
+    size_t stage_total = 0, o = 0;
+    for (int k = 0; k < m; ++k) stage_total += extra_bytes(images[idx[k]], host_in);
+    if (host_in && (rc = pool_reserve(st, kEncYuv, stage_total)) != 0) return rc;
+    for (int k = 0; k < m; ++k) {
+      const int geom = sampled(images[idx[k]]);
+      const uhdr_hip_image_t img = geom >= 0 ? sampled_image(images[idx[k]], geom) : enc_image(images[idx[k]]);
+      uhdr_hip_image_t d = img;
+      if (host_in) {   // into the round's slice
+        uint8_t* dst = static_cast<uint8_t*>(st->pool[kEncYuv]) + o;
+        if ((rc = geom >= 0 ? stage_sampled_slice(dst, img, geom, &d, s) : stage_encoder_slice(dst, img, &d, s)) != 0) return rc;
+        o += geom >= 0 ? sampled_stage_bytes(img, geom) : enc_stage_bytes(img);
+      }
+      e[k].img = d;
+      e[k].pad_ls = img.luma_stride;
+      e[k].pad_cs = img.chroma_stride;
+      e[k].geom = geom;
+    }
+    return UHDR_HIP_NO_ERROR;
+  }
+};
+
+// what the two RGBA8888 families share: rgba_file_check, then the options against the geometry; and the images of a round in device
+// memory, luma_stride set
+int rgba_family_check(const uhdr_hip_image_t& im, bool host_in, const void* out, size_t out_capacity, jpeg::Geometry geom, const EncOpt& eo) {
+  const int rc = rgba_file_check(im, host_in, out, out_capacity);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
-  return jpeg_encode_rgba420_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, eo, mem_space, stream);
+  return encodable_with(im.width, im.height, geom, eo) ? UHDR_HIP_NO_ERROR : UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
 }
-// RGBA8888 images at the sampling said (DESIGN.md section 7.1.3): YUV420 is the call above, YUV444 uhdr_hip_jpeg_encode_rgb_batch_opts'
-// file with the ICC segment, YUV422 the 4:2:0 call's course with k_rgba_to_ycc422 in front
-int uhdr_hip_jpeg_encode_rgba_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
-                                         void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int sampling,
-                                         const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
-  EncOpt eo;
-  const int rc = encode_opts(opts, &eo);
-  if (rc != UHDR_HIP_NO_ERROR) return rc;
-  if (sampling == UHDR_HIP_PIX_FMT_YUV444)
-    return jpeg_encode_rgb_batch_with(n, images, quality, out, out_capacity, out_size, status, eo, mem_space, stream, icc, icc_size);
-  if (sampling != UHDR_HIP_PIX_FMT_YUV422 && sampling != UHDR_HIP_PIX_FMT_YUV420) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  return jpeg_encode_rgba420_batch_with(n, images, quality, icc, icc_size, out, out_capacity, out_size, status, eo, mem_space, stream,
-                                        sampling == UHDR_HIP_PIX_FMT_YUV422);
+int rgba_round_images(DeviceState* st, hipStream_t s, const uhdr_hip_image_t* images, bool host_in, const int* idx, int m, uhdr_hip_image_t* dev) {
+  int rc;
+  size_t stage_total = 0, o = 0;
+  for (int k = 0; host_in && k < m; ++k) stage_total += rgba_stage_bytes(images[idx[k]].width, images[idx[k]].height, 4);
+  if (host_in && (rc = pool_reserve(st, kEncYuv, stage_total)) != 0) return rc;
+  for (int k = 0; k < m; ++k) {
+    dev[k] = images[idx[k]];
+    if (dev[k].luma_stride == 0) dev[k].luma_stride = dev[k].width;
+    if (!host_in) continue;
+    size_t bytes = 0;
+    if ((rc = stage_rgba_rows(static_cast<uint8_t*>(st->pool[kEncYuv]) + o, dev[k], 4, &dev[k], &bytes, s)) != 0) return rc;
+    o += bytes;
+  }
+  return UHDR_HIP_NO_ERROR;
 }
-static int jpeg_encode_rgba420_batch_with(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
-                                          const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
-                                          const EncOpt& eo, int mem_space, void* stream, bool s422) {
-  const jpeg::Geometry geom = s422 ? jpeg::kGeom422 : jpeg::kGeom420;   // (s422: uhdr_hip_jpeg_encode_rgba_batch_opts at YUV422)
-  if (n < 0 || (n > 0 && (images == nullptr || quality == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (icc != nullptr && icc_size == nullptr))
+// RGBA8888 pixels as 4:4:4 (jpeg::kGeomRgb444): the file libjpeg writes for in_color_space = JCS_RGB with all sampling factors 1; the
+// encoder converts as it loads, so there is no launch in front
+struct Rgba444Family {
+  static constexpr size_t kRoundCap = (size_t)jpeg::kMaxBatchJobs;
+  static constexpr bool kQualityGate = true;
+  int check(const uhdr_hip_image_t& im, bool host_in, const void* out, size_t out_capacity, const EncOpt& eo) const {
+    return rgba_family_check(im, host_in, out, out_capacity, jpeg::kGeomRgb444, eo);
+  }
+  jpeg::Geometry geometry(const uhdr_hip_image_t&) const { return jpeg::kGeomRgb444; }
+  size_t extra_bytes(const uhdr_hip_image_t& im, bool host_in) const { return host_in ? rgba_stage_bytes(im.width, im.height, 4) : 0; }
+  int prepare(DeviceState* st, hipStream_t s, const uhdr_hip_image_t* images, bool host_in, const int* idx, int m, EncJpeg* e) const {
+    std::vector<uhdr_hip_image_t> dev((size_t)m);
+    const int rc = rgba_round_images(st, s, images, host_in, idx, m, dev.data());
+    if (rc != 0) return rc;
+    for (int k = 0; k < m; ++k) {
+      e[k].img = dev[(size_t)k];
+      e[k].img.chroma_data = nullptr; e[k].img.chroma_stride = 0;
+      e[k].pad_ls = e[k].pad_cs = 0;
+      e[k].rgb = true;
+    }
+    return UHDR_HIP_NO_ERROR;
+  }
+};
+// RGBA8888 pixels as 4:2:0, or as 4:2:2 (s422): the planes libjpeg's colour conversion and downsampler hand its FDCT come from one
+// k_rgba_to_ycc420 / k_rgba_to_ycc422 launch per round (rgba420_planes), which is what holds a round to jpeg::kRgba420Chunk files
+struct RgbaSubsampledFamily {
+  static constexpr size_t kRoundCap = (size_t)jpeg::kRgba420Chunk;
+  static constexpr bool kQualityGate = true;
+  bool s422;
+  int check(const uhdr_hip_image_t& im, bool host_in, const void* out, size_t out_capacity, const EncOpt& eo) const {
+    return rgba_family_check(im, host_in, out, out_capacity, geometry(im), eo);
+  }
+  jpeg::Geometry geometry(const uhdr_hip_image_t&) const { return s422 ? jpeg::kGeom422 : jpeg::kGeom420; }
+  size_t extra_bytes(const uhdr_hip_image_t& im, bool host_in) const {
+    return round_up(s422 ? jpeg::rgba422_plane_bytes(im.width, im.height) : jpeg::rgba420_plane_bytes(im.width, im.height), 256) +
+           (host_in ? rgba_stage_bytes(im.width, im.height, 4) : 0);
+  }
+  int prepare(DeviceState* st, hipStream_t s, const uhdr_hip_image_t* images, bool host_in, const int* idx, int m, EncJpeg* e) const {
+    std::vector<uhdr_hip_image_t> dev((size_t)m);
+    const int rc = rgba_round_images(st, s, images, host_in, idx, m, dev.data());
+    return rc != 0 ? rc : rgba420_planes(st, kEncSdr, s, m, dev.data(), e, 1, s422);
+  }
+};
+
+// the arrays of a plain-JPEG encode batch, as the caller gave them (icc and status may be NULL)
+struct JpegBatch {
+  int n;
+  const uhdr_hip_image_t* images;
+  const int* quality;
+  const void* const* icc;
+  const size_t* icc_size;
+  void* const* out;
+  const size_t* out_capacity;
+  size_t* out_size;
+  int* status;
+};
+
+// uhdr_hip_jpeg_encode for n images of one family in one call.  The call's own checks first -- pointers, then the quality gate where
+// the family has one --, after which nothing fails the call: a file that fails its checks is not processed and has its status, the
+// others go through in rounds (run_rounds) whose files share one jpeg::encode_batch_async launch set and one synchronisation
+// (compress_to_host).  mem_space: UHDR_HIP_MEM_DEVICE_TO_HOST and UHDR_HIP_MEM_HOST_TO_DEVICE say the inputs' and the files' side apart.
+template <class Family>
+int jpeg_encode_files(const JpegBatch& a, const EncOpt& eo, int mem_space, void* stream, const Family& fam) {
+  if (a.n < 0 || (a.n > 0 && (a.images == nullptr || a.quality == nullptr || a.out == nullptr || a.out_capacity == nullptr || a.out_size == nullptr)) ||
+      (a.icc != nullptr && a.icc_size == nullptr))
     return UHDR_HIP_ERROR_BAD_PTR;
-  for (int i = 0; i < n; ++i)
-    if (quality[i] < 0 || quality[i] > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
-  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
-  std::vector<int> live;
+  for (int i = 0; Family::kQualityGate && i < a.n; ++i)
+    if (a.quality[i] < 0 || a.quality[i] > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
   const bool host_in = mem_space == UHDR_HIP_MEM_HOST || mem_space == UHDR_HIP_MEM_HOST_TO_DEVICE;
   const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE && mem_space != UHDR_HIP_MEM_HOST_TO_DEVICE;
-  for (int i = 0; i < n; ++i) {
-    st_[i] = rgba_file_check(images[i], host_in, out[i], out_capacity[i]);
-    if (st_[i] == UHDR_HIP_NO_ERROR && !encodable_with(images[i].width, images[i].height, geom, eo))
-      st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-    if (st_[i] == UHDR_HIP_NO_ERROR) live.push_back(i);
-  }
-  if (live.empty()) return finish_statuses(st_, status);
-  auto stage_pitch = [](const uhdr_hip_image_t& im) { return round_up(im.width * 4, 64); };   // bytes
+  std::vector<int> st_((size_t)a.n, UHDR_HIP_NO_ERROR);
+  std::vector<int> live;
+  for (int i = 0; i < a.n; ++i)
+    if ((st_[i] = fam.check(a.images[i], host_in, a.out[i], a.out_capacity[i], eo)) == UHDR_HIP_NO_ERROR) live.push_back(i);
+  if (live.empty()) return finish_statuses(st_, a.status);
   size_t done = 0;
   const int rc = run_rounds(
-      live.size(), (size_t)jpeg::kRgba420Chunk, stream,
-      [&](size_t k) {
-        const uhdr_hip_image_t& im = images[live[k]];
-        size_t b = enc_workspace_bytes(im.width, im.height, geom, eo) +
-                   round_up(s422 ? jpeg::rgba422_plane_bytes(im.width, im.height) : jpeg::rgba420_plane_bytes(im.width, im.height), 256);
-        if (host_in) b += round_up(stage_pitch(im) * im.height, 256);
-        if (host_out) b += im.width * im.height * (s422 ? 3 : 1) + 65536;
-        return b;
+      live.size(), Family::kRoundCap, stream,
+      [&](size_t k) {   // what one file holds of its round: encoder workspace, the family's planes, page-locked staging of the file
+        const uhdr_hip_image_t& im = a.images[live[k]];
+        const jpeg::Geometry geom = fam.geometry(im);
+        return enc_workspace_bytes(im.width, im.height, geom, eo) + fam.extra_bytes(im, host_in) +
+               (host_out ? enc_first_guess(im.width, im.height, geom) : 0);
       },
       [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
         const int* idx = &live[r0];
         std::vector<EncJpeg> im((size_t)m);
-        std::vector<uhdr_hip_image_t> dev((size_t)m);
         std::vector<std::vector<uint8_t>> iccs((size_t)m);
-        size_t stage_total = 0;
-        int rc;
-        if (host_in) {
-          for (int k = 0; k < m; ++k) stage_total += round_up(stage_pitch(images[idx[k]]) * images[idx[k]].height, 256);
-          if ((rc = pool_reserve(st, kEncYuv, stage_total)) != 0) return rc;
-        }
-        size_t o = 0;
-        for (int k = 0; k < m; ++k) {
-          uhdr_hip_image_t& d = dev[(size_t)k];
-          d = images[idx[k]];
-          if (d.luma_stride == 0) d.luma_stride = d.width;
-          if (host_in) {   // rows of 4 w bytes into the round's slice, at a 64-byte pitch
-            const size_t pitch = stage_pitch(d);
-            uint8_t* dst = static_cast<uint8_t*>(st->pool[kEncYuv]) + o;
-            if ((rc = h2d_plane(dst, pitch, d.data, d.luma_stride * 4, d.width * 4, d.height, 1, s)) != 0) return rc;
-            o += round_up(pitch * d.height, 256);
-            d.data = dst; d.luma_stride = pitch / 4;
-          }
-        }
-        if ((rc = rgba420_planes(st, kEncSdr, s, m, dev.data(), im.data(), 1, s422)) != 0) return rc;
+        int rc = fam.prepare(st, s, a.images, host_in, idx, m, im.data());
+        if (rc != UHDR_HIP_NO_ERROR) return rc;
         for (int k = 0; k < m; ++k) {
           const int i = idx[k];
-          const void* ip = icc ? icc[i] : nullptr;
-          const size_t in = icc ? icc_size[i] : 0;
+          const void* ip = a.icc ? a.icc[i] : nullptr;
+          const size_t in = a.icc ? a.icc_size[i] : 0;
           if (ip != nullptr && in > 0) iccs[(size_t)k].assign(static_cast<const uint8_t*>(ip), static_cast<const uint8_t*>(ip) + in);
           EncJpeg& e = im[(size_t)k];
-          e.quality = quality[i];
+          e.quality = a.quality[i];
           e.icc = iccs[(size_t)k].empty() ? nullptr : &iccs[(size_t)k];
           eo.to(&e);
           if (host_out) {
-            e.keep_max = out_capacity[i];   // a file that will not fit is only measured
+            e.keep_max = a.out_capacity[i];   // a file that will not fit is only measured
           } else {
             e.to_dev = true;
-            e.dev_out = static_cast<uint8_t*>(out[i]);
-            e.dev_cap = out_capacity[i];
+            e.dev_out = static_cast<uint8_t*>(a.out[i]);
+            e.dev_cap = a.out_capacity[i];
           }
         }
         if ((rc = compress_to_host(st, s, m, im.data())) != UHDR_HIP_NO_ERROR) return rc;
+        // the files from the page-locked staging into the caller's buffers: megabytes per 4K file, so a few host threads side by side
         auto deliver = [&](int lo, int hi) {
           for (int k = lo; k < hi; ++k) {
             const int i = idx[k];
-            out_size[i] = im[(size_t)k].n;
-            if (im[(size_t)k].n > out_capacity[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
-            if (host_out) memcpy(out[i], im[(size_t)k].bytes, im[(size_t)k].n);
+            a.out_size[i] = im[(size_t)k].n;
+            if (im[(size_t)k].n > a.out_capacity[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
+            if (host_out) memcpy(a.out[i], im[(size_t)k].bytes, im[(size_t)k].n);
             st_[i] = UHDR_HIP_NO_ERROR;
           }
         };
@@ -2415,8 +2222,118 @@ static int jpeg_encode_rgba420_batch_with(int n, const uhdr_hip_image_t* images,
       },
       &done);
   for (size_t k = done; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
-  return finish_statuses(st_, status);
+  return finish_statuses(st_, a.status);
 }
+}  // namespace
+
+extern "C" {
+
+// uhdr_hip_jpeg_encode for n images in one call (jpeg_encode_files, the planes family)
+int uhdr_hip_jpeg_encode_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                               void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream) {
+  return jpeg_encode_files(JpegBatch{n, images, quality, icc, icc_size, out, out_capacity, out_size, status}, EncOpt(), mem_space, stream,
+                           PlanesFamily{false});
+}
+// flags == 0 is uhdr_hip_jpeg_encode_batch.  UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN: every file with Huffman tables of its own (DESIGN.md
+// section 7.1.1) -- the same pixels in fewer bytes; a file too large for libjpeg's table search is UNSUPPORTED_FEATURE
+int uhdr_hip_jpeg_encode_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                  void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int flags, int mem_space,
+                                  void* stream) {
+  EncOpt eo;
+  const int rc = encode_flags(flags, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpeg_encode_files(JpegBatch{n, images, quality, icc, icc_size, out, out_capacity, out_size, status}, eo, mem_space, stream,
+                           PlanesFamily{false});
+}
+// opts == NULL, or no restart field set: uhdr_hip_jpeg_encode_batch_ex with opts->flags.  Otherwise every file with restart intervals
+// (DESIGN.md section 7.1.2), with either kind of tables
+int uhdr_hip_jpeg_encode_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                    void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                    const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpeg_encode_files(JpegBatch{n, images, quality, icc, icc_size, out, out_capacity, out_size, status}, eo, mem_space, stream,
+                           PlanesFamily{false});
+}
+// uhdr_hip_jpeg_encode_batch_opts with YUV444 / 422 / 440 images compressed as what they are (DESIGN.md section 7.1.3); every other image of
+// the call is that call's, and all share the round's launches
+int uhdr_hip_jpeg_encode_planes_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                           void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                           const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpeg_encode_files(JpegBatch{n, images, quality, icc, icc_size, out, out_capacity, out_size, status}, eo, mem_space, stream,
+                           PlanesFamily{true});
+}
+
+// uhdr_hip_jpeg_encode_batch's conventions for RGBA8888 images, compressed as 4:4:4 (Rgba444Family).  No ICC.
+int uhdr_hip_jpeg_encode_rgb_batch(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
+                                   size_t* out_size, int* status, int mem_space, void* stream) {
+  return jpeg_encode_files(JpegBatch{n, images, quality, nullptr, nullptr, out, out_capacity, out_size, status}, EncOpt(), mem_space, stream,
+                           Rgba444Family{});
+}
+// flags as in uhdr_hip_jpeg_encode_batch_ex
+int uhdr_hip_jpeg_encode_rgb_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
+                                      size_t* out_size, int* status, int flags, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_flags(flags, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpeg_encode_files(JpegBatch{n, images, quality, nullptr, nullptr, out, out_capacity, out_size, status}, eo, mem_space, stream,
+                           Rgba444Family{});
+}
+// opts as in uhdr_hip_jpeg_encode_batch_opts
+int uhdr_hip_jpeg_encode_rgb_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, void* const* out, const size_t* out_capacity,
+                                        size_t* out_size, int* status, const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpeg_encode_files(JpegBatch{n, images, quality, nullptr, nullptr, out, out_capacity, out_size, status}, eo, mem_space, stream,
+                           Rgba444Family{});
+}
+
+// uhdr_hip_jpeg_encode_batch's conventions for RGBA8888 images compressed as 4:2:0 (RgbaSubsampledFamily)
+int uhdr_hip_jpeg_encode_rgba420_batch(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                       void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int mem_space, void* stream) {
+  return jpeg_encode_files(JpegBatch{n, images, quality, icc, icc_size, out, out_capacity, out_size, status}, EncOpt(), mem_space, stream,
+                           RgbaSubsampledFamily{false});
+}
+// flags as in uhdr_hip_jpeg_encode_batch_ex
+int uhdr_hip_jpeg_encode_rgba420_batch_ex(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                          void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int flags, int mem_space,
+                                          void* stream) {
+  EncOpt eo;
+  const int rc = encode_flags(flags, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpeg_encode_files(JpegBatch{n, images, quality, icc, icc_size, out, out_capacity, out_size, status}, eo, mem_space, stream,
+                           RgbaSubsampledFamily{false});
+}
+// opts as in uhdr_hip_jpeg_encode_batch_opts
+int uhdr_hip_jpeg_encode_rgba420_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
+                                            const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                            const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpeg_encode_files(JpegBatch{n, images, quality, icc, icc_size, out, out_capacity, out_size, status}, eo, mem_space, stream,
+                           RgbaSubsampledFamily{false});
+}
+// RGBA8888 images at the sampling said (DESIGN.md section 7.1.3): YUV420 is the call above, YUV444 uhdr_hip_jpeg_encode_rgb_batch_opts'
+// file with an APP2 segment for a file's ICC profile where the other calls put it, YUV422 the 4:2:0 call's course with
+// k_rgba_to_ycc422 in front
+int uhdr_hip_jpeg_encode_rgba_batch_opts(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                         void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int sampling,
+                                         const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  const JpegBatch a{n, images, quality, icc, icc_size, out, out_capacity, out_size, status};
+  if (sampling == UHDR_HIP_PIX_FMT_YUV444) return jpeg_encode_files(a, eo, mem_space, stream, Rgba444Family{});
+  if (sampling != UHDR_HIP_PIX_FMT_YUV422 && sampling != UHDR_HIP_PIX_FMT_YUV420) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return jpeg_encode_files(a, eo, mem_space, stream, RgbaSubsampledFamily{sampling == UHDR_HIP_PIX_FMT_YUV422});
+}
+
 
 // Diagnostics (host only, no GPU): the quantised coefficients of a PROGRESSIVE file after all of its scans, as the host-side
 // entropy decoder hands them to the device (csrc/uhdr_jpeg_prog.cpp) -- blocks in MCU order, zigzag order inside a block, DC as the
@@ -3156,6 +3073,69 @@ EncJpeg gainmap_rgb_jpeg(uhdr_hip_image_t map) {
   return e;
 }
 
+// what a JPEG/R encode batch says beyond its files, each entry point naming what it sets (encode_files, encode_packed_files)
+struct JpegrOpt {
+  int boost_scope = -1;                               // >= 0: the adaptive generate (UHDR_HIP_BOOST_*)
+  uhdr_hip_metadata_t* metadata = nullptr;            // or one entry per file: what every processed file's container carries
+  int tonemap_op = UHDR_HIP_TONEMAP_SHIFT;            // API-0 from planes: the operator that derives the SDR image
+  const float* peaks = nullptr;                       // or hdr_peak_nits, one per file (tone-mapped API-0, packed API-0)
+  bool rgb_map = false;                               // the per-channel map, compressed as a 4:4:4 file
+  int map_scale = 4;                                  // the map's factor (planes)
+  int primary_sampling = UHDR_HIP_PIX_FMT_YUV420;     // the primary image's sampling (packed)
+  EncOpt enc;                                         // the encoder's options, for both compressions
+};
+
+// the call-level gate of the JPEG/R encode batches: the arrays every form needs (hdr_images, and sdr_images where the form has no
+// API-0 reading: `need_sdr`), exif without its sizes, then the quality (jpegr.cpp:175-183)
+int jpegr_batch_gate(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, bool need_sdr, int quality,
+                     const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, const size_t* out_size) {
+  if (n < 0 || (n > 0 && (hdr_images == nullptr || (need_sdr && sdr_images == nullptr) || out == nullptr || out_capacity == nullptr ||
+                          out_size == nullptr)) ||
+      (exif != nullptr && exif_size == nullptr))
+    return UHDR_HIP_ERROR_BAD_PTR;
+  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  return UHDR_HIP_NO_ERROR;
+}
+
+// UHDR_HIP_BOOST_PER_CALL over several rounds: the statistic of all rounds first.  The carry slot of the context is reserved and
+// initialised, then round(st, s, f, m, 1) stages and measures every kEncRound-sized slice of the files -- probe copies, since a round
+// rewrites its files' descriptors -- with the pooled extremes carried along in device memory; the rounds proper then encode against
+// the carried pair (carry == 2).
+template <class File, class Round>
+int measure_all_rounds(DeviceState* st, hipStream_t s, const std::vector<File>& files, Round round) {
+  int rc = pool_reserve(st, kEncAdaptCarry, 256);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  const hipError_t e = launch_adaptive_init(static_cast<uint32_t*>(st->pool[kEncAdaptCarry]), 2u, s);
+  if (e != hipSuccess) { set_err("launch_adaptive_init", e); return UHDR_HIP_UNKNOWN_ERROR; }
+  for (size_t q0 = 0; rc == UHDR_HIP_NO_ERROR && q0 < files.size(); q0 += kEncRound) {
+    const int m = (int)std::min(files.size() - q0, (size_t)kEncRound);
+    std::vector<File> probe(files.begin() + (long)q0, files.begin() + (long)q0 + m);
+    rc = round(st, s, probe.data(), m, 1);
+  }
+  return rc;
+}
+
+// appendGainMap (jpegr.cpp:951-1130) for the m files of a round, straight into the caller's buffers, a few host threads side by
+// side: file k's JPEGs are jpg[2 k] (SDR) and jpg[2 k + 1] (gain map), idx(k) its place in the caller's arrays.  range == NULL: every
+// container carries md; else (adaptive) file k's own, from range[2 k] and range[2 k + 1].  metadata (or NULL) receives each file's.
+template <class Idx>
+void append_containers(int m, const EncJpeg* jpg, Idx idx, const uhdr_hip_metadata_t& md, const float* range, const void* const* exif,
+                       const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* st_,
+                       uhdr_hip_metadata_t* metadata) {
+  on_host_threads(m, [&](int lo, int hi) {
+    for (int k = lo; k < hi; ++k) {
+      const int i = idx(k);
+      const EncJpeg& sdr = jpg[2 * (size_t)k];
+      const EncJpeg& gm = jpg[2 * (size_t)k + 1];
+      uhdr_hip_metadata_t mk = md;
+      if (range != nullptr) fill_adaptive_metadata(range[2 * (size_t)k], range[2 * (size_t)k + 1], &mk);
+      st_[i] = jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
+                                        nullptr, 0, mk, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i], range != nullptr);
+      if (metadata != nullptr) metadata[i] = mk;
+    }
+  });
+}
+
 // One round: staging (host callers), toneMap (API-0), generateGainMap, BT.601 re-encode -- one launch per step for the round's
 // files -- then the 2 m compressions with one synchronisation (compress_to_host).  Leaves file k's JPEGs in (*jpg)[2 k] (SDR) and
 // (*jpg)[2 k + 1] (gain map).  A non-zero return is an error of the device or the runtime (every file of the round fails with it).
@@ -3164,8 +3144,10 @@ EncJpeg gainmap_rgb_jpeg(uhdr_hip_image_t map) {
 // only -- staging, toneMap and pass 1, no map, no compression, no synchronisation --, carry == 2 encodes against the carried pair.
 // tonemap_op (API-0): the operator that derives the SDR planes; its headroom array is a pool slot of the context.
 int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_tf, int quality, EncFile* f, int m, uhdr_hip_metadata_t* md,
-                 std::vector<EncJpeg>* jpg, int boost_scope = -1, float* range = nullptr, int carry = 0,
-                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, bool rgb_map = false, int map_scale = 4, const EncOpt& eo = EncOpt()) {
+                 std::vector<EncJpeg>* jpg, const JpegrOpt& opt, float* range = nullptr, int carry = 0) {
+  const int boost_scope = opt.boost_scope, tonemap_op = opt.tonemap_op, map_scale = opt.map_scale;
+  const bool rgb_map = opt.rgb_map;
+  const EncOpt& eo = opt.enc;
   const size_t msf = (size_t)map_scale;     // the map's factor: uhdr_hip_jpegr_encode_scaled_batch's, 4 in every other call
   const size_t map_bpp = rgb_map ? 4 : 1;   // rgb_map: uhdr_hip_generate_gainmap_rgb_batch's RGBA map, compressed as 4:4:4
   auto al256 = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -3293,16 +3275,17 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
     jpg->push_back(rgb_map ? gainmap_rgb_jpeg(g) : gainmap_jpeg(g, g.luma_stride));
   }
   for (EncJpeg& e : *jpg) eo.to(&e);   // the primary image and the gain map alike (intervals in rows: each from its own width)
-  return compress_to_host(st, s, 2 * m, jpg->data(), true, dev_range, dev_range ? 8 * (size_t)m : 0, range);
+  return compress_to_host(st, s, 2 * m, jpg->data(), true, EncExtra{dev_range, dev_range ? 8 * (size_t)m : 0, range});
 }
 
 // encodeJPEGR API-1 (yuv420_images != NULL) or API-0 for n pairs, the quality checked: the files' kernels share their launches, the
 // call synchronises once per round of up to kEncRound files, and the containers are assembled by a few host threads
 int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
                  const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
-                 int* status, int mem_space, void* stream, int boost_scope = -1, uhdr_hip_metadata_t* metadata = nullptr,
-                 int tonemap_op = UHDR_HIP_TONEMAP_SHIFT, const float* hdr_peak_nits = nullptr, bool rgb_map = false, int map_scale = 4,
-                 const EncOpt& eo = EncOpt()) {
+                 int* status, int mem_space, void* stream, const JpegrOpt& opt = JpegrOpt()) {
+  const int boost_scope = opt.boost_scope, tonemap_op = opt.tonemap_op, map_scale = opt.map_scale;
+  const float* hdr_peak_nits = opt.peaks;
+  const EncOpt& eo = opt.enc;
   const bool api0 = yuv420_images == nullptr;
   std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
   std::vector<EncFile> files;
@@ -3343,56 +3326,28 @@ int encode_files(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_imag
   // PER_CALL over several rounds: the statistic of all rounds first (every round staged and measured, the pooled extremes carried
   // along in device memory), then the rounds proper, encoded against the carried pair
   const int carry = boost_scope == UHDR_HIP_BOOST_PER_CALL && files.size() > (size_t)kEncRound ? 2 : 0;
-  auto measure_all = [&](DeviceState* st, hipStream_t s) {
-    int rc = pool_reserve(st, kEncAdaptCarry, 256);
-    if (rc != UHDR_HIP_NO_ERROR) return rc;
-    const hipError_t e = launch_adaptive_init(static_cast<uint32_t*>(st->pool[kEncAdaptCarry]), 2u, s);
-    if (e != hipSuccess) { set_err("launch_adaptive_init", e); return UHDR_HIP_UNKNOWN_ERROR; }
-    for (size_t q0 = 0; rc == UHDR_HIP_NO_ERROR && q0 < files.size(); q0 += kEncRound) {
-      const int m = (int)std::min(files.size() - q0, (size_t)kEncRound);
-      std::vector<EncFile> probe(files.begin() + (long)q0, files.begin() + (long)q0 + m);   // (a round rewrites its files' descriptors)
-      uhdr_hip_metadata_t md;
-      std::vector<EncJpeg> jpg;
-      rc = encode_round(st, s, api0, host, hdr_tf, quality, probe.data(), m, &md, &jpg, boost_scope, nullptr, 1, tonemap_op);
-    }
-    return rc;
-  };
   std::vector<float> range(2 * (size_t)kEncRound);
+  // the measuring pass (pass == 1) stops behind the statistic: it takes the scope and the operator alone, and no range comes down
+  JpegrOpt measure_opt;
+  measure_opt.boost_scope = boost_scope;
+  measure_opt.tonemap_op = tonemap_op;
+  auto round = [&](DeviceState* st, hipStream_t s, EncFile* f, int m, int pass) -> int {
+    uhdr_hip_metadata_t md{};
+    std::vector<EncJpeg> jpg;
+    const int rc = encode_round(st, s, api0, host, hdr_tf, quality, f, m, &md, &jpg, pass == 1 ? measure_opt : opt,
+                                pass == 1 ? nullptr : range.data(), pass);
+    if (rc != UHDR_HIP_NO_ERROR || pass == 1) return rc;
+    append_containers(m, jpg.data(), [f](int k) { return f[k].idx; }, md, boost_scope >= 0 ? range.data() : nullptr, exif, exif_size, out,
+                      out_capacity, out_size, st_.data(), opt.metadata);
+    return UHDR_HIP_NO_ERROR;
+  };
   size_t done = 0;
   const int rc = run_rounds(
       files.size(), (size_t)kEncRound, stream, [](size_t) { return (size_t)0; },   // rounds by count alone
       [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
         // the measuring pass needs the leased context, which the driver hands over with a round: it goes in front of the first one
-        int rc = carry != 0 && r0 == 0 ? measure_all(st, s) : UHDR_HIP_NO_ERROR;
-        if (rc != UHDR_HIP_NO_ERROR) return rc;
-        EncFile* f = &files[r0];
-        uhdr_hip_metadata_t md;
-        std::vector<EncJpeg> jpg;
-        if ((rc = encode_round(st, s, api0, host, hdr_tf, quality, f, m, &md, &jpg, boost_scope, range.data(), carry, tonemap_op, rgb_map, map_scale,
-                               eo)) != UHDR_HIP_NO_ERROR)
-          return rc;
-        std::vector<uhdr_hip_metadata_t> mds;   // adaptive: every file's own
-        if (boost_scope < 0 && metadata)
-          for (int k = 0; k < m; ++k) metadata[f[k].idx] = md;
-        if (boost_scope >= 0) {
-          mds.resize((size_t)m);
-          for (int k = 0; k < m; ++k) {
-            fill_adaptive_metadata(range[2 * (size_t)k], range[2 * (size_t)k + 1], &mds[(size_t)k]);
-            if (metadata) metadata[f[k].idx] = mds[(size_t)k];
-          }
-        }
-        // appendGainMap (jpegr.cpp:951-1130) straight into the caller's buffers, a few host threads side by side
-        on_host_threads(m, [&](int lo, int hi) {
-          for (int k = lo; k < hi; ++k) {
-            const int i = f[k].idx;
-            const EncJpeg& sdr = jpg[2 * (size_t)k];
-            const EncJpeg& gm = jpg[2 * (size_t)k + 1];
-            st_[i] = jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
-                                              nullptr, 0, boost_scope >= 0 ? mds[(size_t)k] : md, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i],
-                                              boost_scope >= 0);
-          }
-        });
-        return UHDR_HIP_NO_ERROR;
+        const int rc = carry != 0 && r0 == 0 ? measure_all_rounds(st, s, files, round) : (int)UHDR_HIP_NO_ERROR;
+        return rc != UHDR_HIP_NO_ERROR ? rc : round(st, s, &files[r0], m, carry);
       },
       &done);
   for (size_t k = done; k < files.size(); ++k) st_[files[k].idx] = rc;   // the files of the failed round and of those behind it
@@ -3475,29 +3430,37 @@ int apix_check(const uhdr_hip_image_t& yuv_in, const uhdr_hip_image_t& gainmap, 
   return UHDR_HIP_NO_ERROR;
 }
 
+// uhdr_hip_jpegr_encode_batch behind its three forms: API-1 (yuv420_images != NULL) or API-0, the encoder's options said
+int jpegr_encode_batch_with(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                            const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
+                            int* status, const EncOpt& eo, int mem_space, void* stream) {
+  const int rc = jpegr_batch_gate(n, p010_images, yuv420_images, false, quality, exif, exif_size, out, out_capacity, out_size);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  JpegrOpt opt;
+  opt.enc = eo;
+  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, opt);
+}
+
 }  // namespace
 
 extern "C" {
 
-static int jpegr_encode_batch_with(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
-                                   const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
-                                   size_t* out_size, int* status, const EncOpt& eo, int mem_space, void* stream);
-
 int uhdr_hip_jpegr_encode_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
                                 const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
                                 int* status, int mem_space, void* stream) {
-  return uhdr_hip_jpegr_encode_batch_ex(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, 0,
-                                        mem_space, stream);
+  return jpegr_encode_batch_with(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, EncOpt(),
+                                 mem_space, stream);
 }
-
 // flags == 0 is uhdr_hip_jpegr_encode_batch.  UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN: the primary image and the gain-map JPEG of every file
 // with Huffman tables of their own; XMP, MPF offsets and ICC follow from the new sizes through the same container writer
 int uhdr_hip_jpegr_encode_batch_ex(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
                                    const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
                                    size_t* out_size, int* status, int flags, int mem_space, void* stream) {
-  if (!encode_flags_known(flags)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  return jpegr_encode_batch_with(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status,
-                                 EncOpt((flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0), mem_space, stream);
+  EncOpt eo;
+  const int rc = encode_flags(flags, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpegr_encode_batch_with(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, eo, mem_space,
+                                 stream);
 }
 // opts == NULL, or no restart field set: uhdr_hip_jpegr_encode_batch_ex with opts->flags.  Otherwise the primary image and the gain-map
 // JPEG of every file with restart intervals, restart_in_rows counting each one's own MCU rows
@@ -3509,16 +3472,6 @@ int uhdr_hip_jpegr_encode_batch_opts(int n, const uhdr_hip_image_t* p010_images,
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   return jpegr_encode_batch_with(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, eo, mem_space,
                                  stream);
-}
-static int jpegr_encode_batch_with(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
-                                   const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
-                                   size_t* out_size, int* status, const EncOpt& eo, int mem_space, void* stream) {
-  if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (exif != nullptr && exif_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
-  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, -1,
-                      nullptr, UHDR_HIP_TONEMAP_SHIFT, nullptr, false, 4, eo);
 }
 
 // the interval rule on its own, host only: what compress_to_host derives for a scan of this width (enc_restart)
@@ -3569,25 +3522,24 @@ int uhdr_hip_jpeg_optimal_table(const uint32_t freq[256], uint8_t bits[16], uint
 int uhdr_hip_jpegr_encode_rgbmap_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
                                        const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
                                        size_t* out_size, int* status, int mem_space, void* stream) {
-  if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (exif != nullptr && exif_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
-  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, -1,
-                      nullptr, UHDR_HIP_TONEMAP_SHIFT, nullptr, true);
+  const int rc = jpegr_batch_gate(n, p010_images, yuv420_images, false, quality, exif, exif_size, out, out_capacity, out_size);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  JpegrOpt opt;
+  opt.rgb_map = true;
+  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, opt);
 }
 
 // uhdr_hip_jpegr_encode_batch / _rgbmap_batch with the gain map at the call's factor; factor 4 IS those calls
 int uhdr_hip_jpegr_encode_scaled_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
                                        const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
                                        size_t* out_size, int* status, int rgb_map, int map_scale_factor, int mem_space, void* stream) {
-  if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (exif != nullptr && exif_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  const int rc = jpegr_batch_gate(n, p010_images, yuv420_images, false, quality, exif, exif_size, out, out_capacity, out_size);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   if (map_scale_factor < 1 || map_scale_factor > 128) return UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
-  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, -1,
-                      nullptr, UHDR_HIP_TONEMAP_SHIFT, nullptr, rgb_map != 0, map_scale_factor);
+  JpegrOpt opt;
+  opt.rgb_map = rgb_map != 0;
+  opt.map_scale = map_scale_factor;
+  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, opt);
 }
 
 // JPEG/R files from packed RGBA pairs: API-1's checks where they apply, then those of
@@ -3599,13 +3551,15 @@ int uhdr_hip_jpegr_encode_scaled_batch(int n, const uhdr_hip_image_t* p010_image
 // boost_scope >= 0: the adaptive generate in the generate step's place, as in encode_round -- the workspace and
 // the carried key pair are the same pool slots, a round's ranges come down with its streams, and PER_CALL over several rounds stages
 // and measures every round (carry == 1) in front of the first one
-// primary_sampling, eo (uhdr_hip_jpegr_encode_packed_sampling_batch): the primary image as uhdr_hip_jpeg_encode_rgba_batch_opts writes it
-// at that sampling -- YUV444 straight from the pixels, YUV422 through k_rgba_to_ycc422 --, eo for both compressions
+// primary_sampling, enc (uhdr_hip_jpegr_encode_packed_sampling_batch): the primary image as uhdr_hip_jpeg_encode_rgba_batch_opts writes it
+// at that sampling -- YUV444 straight from the pixels, YUV422 through k_rgba_to_ycc422 --, enc for both compressions
 static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf, int quality,
                                const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
-                               size_t* out_size, int* status, int rgb_map, int mem_space, void* stream, uhdr_hip_metadata_t* metadata,
-                               const float* peaks, int boost_scope = -1, int primary_sampling = UHDR_HIP_PIX_FMT_YUV420,
-                               const EncOpt& eo = EncOpt()) {
+                               size_t* out_size, int* status, int mem_space, void* stream, const JpegrOpt& opt) {
+  const int boost_scope = opt.boost_scope, primary_sampling = opt.primary_sampling;
+  const bool rgb_map = opt.rgb_map;
+  const float* peaks = opt.peaks;
+  const EncOpt& eo = opt.enc;
   const bool api0 = sdr_images == nullptr;
   const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
   auto stride_bad = [](const uhdr_hip_image_t& im) { return im.luma_stride != 0 && (im.luma_stride < im.width || im.luma_stride > 0xFFFFFFFFull); };
@@ -3669,8 +3623,8 @@ static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const 
         for (int k = 0; k < m; ++k) {
           const size_t w = f[k].sdr.width, h = f[k].sdr.height;
           map_total += al256((w / 4) * (h / 4) * map_bpp + 64);
-          if (host || api0) sdr_total += al256(round_up(w * 4, 64) * h);
-          if (host) hdr_total += al256(round_up(w * hdr_bpp, 64) * h);
+          if (host || api0) sdr_total += rgba_stage_bytes(w, h, 4);
+          if (host) hdr_total += rgba_stage_bytes(w, h, hdr_bpp);
         }
         if (api0 && (rc = pool_reserve(st, kEncToneHead, sizeof(float) * (size_t)m)) != 0) return rc;
         if ((rc = pool_reserve(st, kEncMap, map_total)) != 0) return rc;
@@ -3681,19 +3635,17 @@ static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const 
         for (int k = 0; k < m; ++k) {
           PackedFile& e = f[k];
           const size_t w = e.sdr.width, h = e.sdr.height;
-          if (host) {   // rows of the pixels alone, at a 64-byte pitch
-            const size_t sp = round_up(w * 4, 64), hp = round_up(w * hdr_bpp, 64);
-            uint8_t* ds = static_cast<uint8_t*>(st->pool[kEncYuv]) + o_sdr;
-            uint8_t* dh = static_cast<uint8_t*>(st->pool[kEncP010]) + o_hdr;
-            if (!api0 && (rc = h2d_plane(ds, sp, e.sdr.data, e.sdr.luma_stride * 4, w * 4, h, 1, s)) != 0) return rc;
-            if ((rc = h2d_plane(dh, hp, e.hdr.data, e.hdr.luma_stride * hdr_bpp, w * hdr_bpp, h, 1, s)) != 0) return rc;
-            o_sdr += al256(sp * h); o_hdr += al256(hp * h);
-            e.sdr.data = ds; e.sdr.luma_stride = sp / 4;
-            e.hdr.data = dh; e.hdr.luma_stride = hp / hdr_bpp;
-          } else if (api0) {
-            const size_t sp = round_up(w * 4, 64);
-            e.sdr.data = static_cast<uint8_t*>(st->pool[kEncYuv]) + o_sdr; e.sdr.luma_stride = sp / 4;
-            o_sdr += al256(sp * h);
+          size_t bytes = 0;
+          if (api0) {   // the SDR image to come: rows of its own at the staged pitch
+            e.sdr.data = static_cast<uint8_t*>(st->pool[kEncYuv]) + o_sdr; e.sdr.luma_stride = round_up(w * 4, 64) / 4;
+            o_sdr += rgba_stage_bytes(w, h, 4);
+          } else if (host) {
+            if ((rc = stage_rgba_rows(static_cast<uint8_t*>(st->pool[kEncYuv]) + o_sdr, e.sdr, 4, &e.sdr, &bytes, s)) != 0) return rc;
+            o_sdr += bytes;
+          }
+          if (host) {
+            if ((rc = stage_rgba_rows(static_cast<uint8_t*>(st->pool[kEncP010]) + o_hdr, e.hdr, hdr_bpp, &e.hdr, &bytes, s)) != 0) return rc;
+            o_hdr += bytes;
           }
           a[(size_t)k] = e.sdr; b[(size_t)k] = e.hdr;
           memset(&c[(size_t)k], 0, sizeof(uhdr_hip_image_t));
@@ -3707,7 +3659,7 @@ static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const 
                                                   static_cast<float*>(st->pool[kEncToneHead]), s)) != UHDR_HIP_NO_ERROR)
             return rc;
         }
-        uhdr_hip_metadata_t md;
+        uhdr_hip_metadata_t md{};
         float* dev_range = nullptr;
         if (boost_scope < 0) {
           if ((rc = uhdr_hip_generate_gainmap_packed_batch(m, a.data(), b.data(), hdr_tf, nullptr, &md, c.data(), rgb_map, s)) != UHDR_HIP_NO_ERROR) return rc;
@@ -3742,40 +3694,17 @@ static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const 
           eo.to(&jpg[2 * (size_t)k]);
           eo.to(&jpg[2 * (size_t)k + 1]);
         }
-        if ((rc = compress_to_host(st, s, 2 * m, jpg.data(), true, dev_range, dev_range ? 8 * (size_t)m : 0, range.data())) != UHDR_HIP_NO_ERROR)
+        if ((rc = compress_to_host(st, s, 2 * m, jpg.data(), true, EncExtra{dev_range, dev_range ? 8 * (size_t)m : 0, range.data()})) != UHDR_HIP_NO_ERROR)
           return rc;
-        on_host_threads(m, [&](int lo, int hi) {
-          for (int k = lo; k < hi; ++k) {
-            const int i = f[k].idx;
-            const EncJpeg& sdr = jpg[2 * (size_t)k];
-            const EncJpeg& gm = jpg[2 * (size_t)k + 1];
-            uhdr_hip_metadata_t mk = md;   // adaptive: every file's own
-            if (boost_scope >= 0) fill_adaptive_metadata(range[2 * (size_t)k], range[2 * (size_t)k + 1], &mk);
-            st_[i] = jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
-                                              nullptr, 0, mk, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i], boost_scope >= 0);
-            if (metadata != nullptr) metadata[i] = mk;
-          }
-        });
+        append_containers(m, jpg.data(), [f](int k) { return f[k].idx; }, md, boost_scope >= 0 ? range.data() : nullptr, exif, exif_size, out,
+                          out_capacity, out_size, st_.data(), opt.metadata);
         return (int)UHDR_HIP_NO_ERROR;
-  };
-  // PER_CALL over several rounds: the statistic of all rounds first, the pooled extremes carried along in device memory (encode_files)
-  auto measure_all = [&](DeviceState* st, hipStream_t s) -> int {
-    int rc = pool_reserve(st, kEncAdaptCarry, 256);
-    if (rc != UHDR_HIP_NO_ERROR) return rc;
-    const hipError_t e = launch_adaptive_init(static_cast<uint32_t*>(st->pool[kEncAdaptCarry]), 2u, s);
-    if (e != hipSuccess) { set_err("launch_adaptive_init", e); return UHDR_HIP_UNKNOWN_ERROR; }
-    for (size_t q0 = 0; rc == UHDR_HIP_NO_ERROR && q0 < files.size(); q0 += kEncRound) {
-      const int m = (int)std::min(files.size() - q0, (size_t)kEncRound);
-      std::vector<PackedFile> probe(files.begin() + (long)q0, files.begin() + (long)q0 + m);   // (a round rewrites its files' descriptors)
-      rc = round(st, s, probe.data(), m, 1);
-    }
-    return rc;
   };
   const int rc = run_rounds(
       files.size(), (size_t)kEncRound, stream, [](size_t) { return (size_t)0; },   // rounds by count alone
       [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
         // the measuring pass needs the leased context, which the driver hands over with a round: it goes in front of the first one
-        const int rc = carry_all != 0 && r0 == 0 ? measure_all(st, s) : (int)UHDR_HIP_NO_ERROR;
+        const int rc = carry_all != 0 && r0 == 0 ? measure_all_rounds(st, s, files, round) : (int)UHDR_HIP_NO_ERROR;
         return rc != UHDR_HIP_NO_ERROR ? rc : round(st, s, &files[r0], m, carry_all);
       },
       &done);
@@ -3786,14 +3715,14 @@ static int encode_packed_files(int n, const uhdr_hip_image_t* hdr_images, const 
 int uhdr_hip_jpegr_encode_packed_batch(int n, const uhdr_hip_image_t* hdr_images, const uhdr_hip_image_t* sdr_images, int hdr_tf, int quality,
                                        const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
                                        size_t* out_size, int* status, int rgb_map, int mem_space, void* stream) {
-  if (n < 0 || (n > 0 && (hdr_images == nullptr || sdr_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (exif != nullptr && exif_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  const int rc = jpegr_batch_gate(n, hdr_images, sdr_images, true, quality, exif, exif_size, out, out_capacity, out_size);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   // (n == 0 with sdr_images == NULL: no file, so nothing distinguishes the two forms)
   static const uhdr_hip_image_t none{};
+  JpegrOpt opt;
+  opt.rgb_map = rgb_map != 0;
   return encode_packed_files(n, hdr_images, sdr_images != nullptr ? sdr_images : &none, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size,
-                             status, rgb_map, mem_space, stream, nullptr, nullptr);
+                             status, mem_space, stream, opt);
 }
 
 // the packed call with the primary image's sampling and the encoder's options said; YUV420 and NULL opts:
@@ -3807,13 +3736,15 @@ int uhdr_hip_jpegr_encode_packed_sampling_batch(int n, const uhdr_hip_image_t* h
   if (orc != UHDR_HIP_NO_ERROR) return orc;
   if (primary_sampling != UHDR_HIP_PIX_FMT_YUV444 && primary_sampling != UHDR_HIP_PIX_FMT_YUV422 && primary_sampling != UHDR_HIP_PIX_FMT_YUV420)
     return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  if (n < 0 || (n > 0 && (hdr_images == nullptr || sdr_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (exif != nullptr && exif_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  const int rc = jpegr_batch_gate(n, hdr_images, sdr_images, true, quality, exif, exif_size, out, out_capacity, out_size);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   static const uhdr_hip_image_t none{};
+  JpegrOpt opt;
+  opt.rgb_map = rgb_map != 0;
+  opt.primary_sampling = primary_sampling;
+  opt.enc = eo;
   return encode_packed_files(n, hdr_images, sdr_images != nullptr ? sdr_images : &none, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size,
-                             status, rgb_map, mem_space, stream, nullptr, nullptr, -1, primary_sampling, eo);
+                             status, mem_space, stream, opt);
 }
 
 // the packed API-0: the same files from the HDR images alone
@@ -3821,13 +3752,14 @@ int uhdr_hip_jpegr_encode_packed_api0_batch(int n, const uhdr_hip_image_t* hdr_i
                                             const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
                                             uhdr_hip_metadata_t* metadata, int* status, int tonemap_op, const float* hdr_peak_nits, int rgb_map,
                                             int mem_space, void* stream) {
-  if (n < 0 || (n > 0 && (hdr_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (exif != nullptr && exif_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  const int rc = jpegr_batch_gate(n, hdr_images, nullptr, false, quality, exif, exif_size, out, out_capacity, out_size);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   if (tonemap_op != UHDR_HIP_TONEMAP_REINHARD_MAXRGB) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  return encode_packed_files(n, hdr_images, nullptr, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, rgb_map, mem_space,
-                             stream, metadata, hdr_peak_nits);
+  JpegrOpt opt;
+  opt.metadata = metadata;
+  opt.peaks = hdr_peak_nits;
+  opt.rgb_map = rgb_map != 0;
+  return encode_packed_files(n, hdr_images, nullptr, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, opt);
 }
 
 // both with the adaptive generate: sdr_images == NULL is the packed API-0
@@ -3835,40 +3767,44 @@ int uhdr_hip_jpegr_encode_packed_adaptive_batch(int n, const uhdr_hip_image_t* h
                                                 const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
                                                 size_t* out_size, uhdr_hip_metadata_t* metadata, int* status, const float* hdr_peak_nits,
                                                 int rgb_map, int boost_scope, int mem_space, void* stream) {
-  if (n < 0 || (n > 0 && (hdr_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (exif != nullptr && exif_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;
+  const int rc = jpegr_batch_gate(n, hdr_images, sdr_images, false, quality, exif, exif_size, out, out_capacity, out_size);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   if (!valid_boost_scope(boost_scope)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  return encode_packed_files(n, hdr_images, sdr_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, rgb_map, mem_space,
-                             stream, metadata, sdr_images == nullptr ? hdr_peak_nits : nullptr, boost_scope);
+  JpegrOpt opt;
+  opt.boost_scope = boost_scope;
+  opt.metadata = metadata;
+  opt.peaks = sdr_images == nullptr ? hdr_peak_nits : nullptr;
+  opt.rgb_map = rgb_map != 0;
+  return encode_packed_files(n, hdr_images, sdr_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, opt);
 }
 
 int uhdr_hip_jpegr_encode_adaptive_batch(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf,
                                          int quality, const void* const* exif, const size_t* exif_size, void* const* out,
                                          const size_t* out_capacity, size_t* out_size, uhdr_hip_metadata_t* metadata, int* status,
                                          int boost_scope, int mem_space, void* stream) {
-  if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (exif != nullptr && exif_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
+  const int rc = jpegr_batch_gate(n, p010_images, yuv420_images, false, quality, exif, exif_size, out, out_capacity, out_size);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   if (!valid_boost_scope(boost_scope)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream,
-                      boost_scope, metadata);
+  JpegrOpt opt;
+  opt.boost_scope = boost_scope;
+  opt.metadata = metadata;
+  return encode_files(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, opt);
 }
 
 int uhdr_hip_jpegr_encode_api0_tonemapped_batch(int n, const uhdr_hip_image_t* p010_images, int hdr_tf, int quality, const void* const* exif,
                                                 const size_t* exif_size, void* const* out, const size_t* out_capacity, size_t* out_size,
                                                 uhdr_hip_metadata_t* metadata, int* status, int tonemap_op, const float* hdr_peak_nits,
                                                 int boost_scope, int mem_space, void* stream) {
-  if (n < 0 || (n > 0 && (p010_images == nullptr || out == nullptr || out_capacity == nullptr || out_size == nullptr)) ||
-      (exif != nullptr && exif_size == nullptr))
-    return UHDR_HIP_ERROR_BAD_PTR;
-  if (quality < 0 || quality > 100) return UHDR_HIP_ERROR_INVALID_QUALITY_FACTOR;                                 // :175-183
+  const int rc = jpegr_batch_gate(n, p010_images, nullptr, false, quality, exif, exif_size, out, out_capacity, out_size);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   if (tonemap_op != UHDR_HIP_TONEMAP_SHIFT && tonemap_op != UHDR_HIP_TONEMAP_REINHARD_MAXRGB) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (boost_scope != -1 && !valid_boost_scope(boost_scope)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  return encode_files(n, p010_images, nullptr, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream,
-                      boost_scope, metadata, tonemap_op, hdr_peak_nits);
+  JpegrOpt opt;
+  opt.boost_scope = boost_scope;
+  opt.metadata = metadata;
+  opt.tonemap_op = tonemap_op;
+  opt.peaks = hdr_peak_nits;
+  return encode_files(n, p010_images, nullptr, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, mem_space, stream, opt);
 }
 
 // JpegR::encodeJPEGR API-0 (jpegr.cpp:186-247): a batch of one file

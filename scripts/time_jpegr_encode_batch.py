@@ -15,8 +15,13 @@ from libultrahdr_dev_amd import api, synth
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, nargs="*", default=[1, 4, 16, 64])
 ap.add_argument("--iters", type=int, default=10)
+ap.add_argument("--lib", default=None, help="a libuhdr_hip.so to time instead of the package's (entry points it lacks are not bound)")
 args = ap.parse_args()
 
+if args.lib:
+    probe = C.CDLL(args.lib)
+    api.SIGNATURES = {k: v for k, v in api.SIGNATURES.items() if hasattr(probe, k)}
+    api.LIB_PATH = args.lib
 lib = api.init(0)
 W, H = 3840, 2160
 NMAX = max(args.n)

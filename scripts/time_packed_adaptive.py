@@ -140,6 +140,10 @@ def main():
     path = os.path.join(ROOT, "profiles", "r16_packed_adaptive.txt")
     if "--out" in sys.argv:
         path = sys.argv[sys.argv.index("--out") + 1]
+    if "--lib" in sys.argv:   # another build of the library (the parent commit's), as in scripts/time_jpeg_sampling_encode.py
+        api.LIB_PATH = sys.argv[sys.argv.index("--lib") + 1]
+        probe = C.CDLL(api.LIB_PATH)
+        api.SIGNATURES = {k: v for k, v in api.SIGNATURES.items() if hasattr(probe, k)}
     lines = []
 
     def out(text):
