@@ -233,15 +233,17 @@ bool al(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) =
 bool tf_known(int tf) { return tf == UHDR_HIP_TF_LINEAR || tf == UHDR_HIP_TF_HLG || tf == UHDR_HIP_TF_PQ; }
 // the rows of an image whose luma_stride may be left 0: stride in pixels, 0 means width (gainmapmath.cpp:585)
 size_t row_stride(const uhdr_hip_image_t& im) { return im.luma_stride == 0 ? im.width : im.luma_stride; }
-// The chunk rule of every gain-map batch call: a chunk is up to kMaxChunk consecutive images, from image i on,
-// that have the shape of image i (same_shape(j)) and one class (aligned or not, FAST or not).  fill(j, m) fills slot m of the batch
-// from image j and returns image j's class: before the classes are compared, so the image that ends a chunk leaves its slot behind
-// and nothing else.  What only the members receive (their destination descriptors) the caller fills, for images [i, i + m).
+// The chunk rule of every batch call: a chunk is up to `cap` consecutive images -- kMaxChunk for the gain-map
+// calls, kToneChunk for the tone-map and convertYuv calls, whose runs these are --, from image i on, that have the shape of image i
+// (same_shape(j)) and one class (aligned or not, FAST or not).  fill(j, m) fills slot m of the batch from image j and returns image
+// j's class: before the classes are compared, so the image that ends a chunk leaves its slot behind and nothing else -- harmless,
+// as m < cap there and a launch reads only the slots of its members.  What only the members receive (their destination
+// descriptors) the caller fills, for images [i, i + m).
 struct Chunk { int m; bool cls; };
 template <class Same, class Fill>
-Chunk form_chunk(int i, int n, Same same_shape, Fill fill) {
+Chunk form_chunk(int i, int n, int cap, Same same_shape, Fill fill) {
   Chunk ch{0, true};
-  while (i + ch.m < n && ch.m < kMaxChunk) {
+  while (i + ch.m < n && ch.m < cap) {
     if (!same_shape(i + ch.m)) break;
     const bool cls = fill(i + ch.m, ch.m);
     if (ch.m == 0) ch.cls = cls;
@@ -376,7 +378,7 @@ template <class MapOf, class Also>
 Chunk gen_chunk(int i, int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image_t* p010s, GenBatch& b, MapOf map_of, Also also) {
   const uhdr_hip_image_t& y0 = yuvs[i];
   const uhdr_hip_image_t& p0 = p010s[i];
-  return form_chunk(i, n,
+  return form_chunk(i, n, kMaxChunk,
                     [&](int j) {
                       return yuvs[j].width == y0.width && yuvs[j].height == y0.height && yuvs[j].colorGamut == y0.colorGamut &&
                              p010s[j].colorGamut == p0.colorGamut;
@@ -400,7 +402,7 @@ template <class MapOf>
 Chunk packed_chunk(int i, int n, const uhdr_hip_image_t* sdrs, const uhdr_hip_image_t* hdrs, bool f16, PackedBatch& b, MapOf map_of,
                    size_t map_align) {
   const uhdr_hip_image_t& s0 = sdrs[i];
-  return form_chunk(i, n,
+  return form_chunk(i, n, kMaxChunk,
                     [&](int j) {
                       return sdrs[j].width == s0.width && sdrs[j].height == s0.height && sdrs[j].colorGamut == s0.colorGamut &&
                              hdrs[j].colorGamut == hdrs[i].colorGamut;
@@ -833,7 +835,7 @@ Chunk app_chunk(int i, int n, const uhdr_hip_image_t* yuvs, const uhdr_hip_image
                 const AppConsts* fast_of, bool equal_stride) {
   const uhdr_hip_image_t& y0 = yuvs[i];
   const uhdr_hip_image_t& m0 = maps[i];
-  const Chunk ch = form_chunk(i, n,
+  const Chunk ch = form_chunk(i, n, kMaxChunk,
                               [&](int j) {
                                 return yuvs[j].width == y0.width && yuvs[j].height == y0.height && maps[j].width == m0.width &&
                                        maps[j].height == m0.height && (!equal_stride || row_stride(maps[j]) == row_stride(m0));
@@ -3038,13 +3040,6 @@ CvtImage cvt_image(const uhdr_hip_image_t& src, const uhdr_hip_image_t& dst, con
              al(t.sy, 8) && t.sy_stride % 8u == 0 && al(t.su, 4) && al(t.sv, 4) && t.sc_stride % 4u == 0;
   return t;
 }
-int convert_yuv_into(const uhdr_hip_image_t& src, const uhdr_hip_image_t& dst, const float* m, hipStream_t s) {
-  CvtBatch b;
-  bool aligned;
-  b.img[0] = cvt_image(src, dst, m, &aligned);
-  HIP_TRY(launch_convert_yuv(b, 1, aligned, s));
-  return UHDR_HIP_NO_ERROR;
-}
 // ---- encodeJPEGR for n files (uhdr_hip_jpegr_encode_batch) ---------------------------------------------------------------------
 // Files go through in rounds of up to kEncRound (2 JPEGs each: the batched encoder's job limit); every device buffer of a round is
 // a slice of one grow-only pool slot of the leased context, the compressed streams land in its page-locked host pool.
@@ -3250,19 +3245,16 @@ int encode_round(DeviceState* st, hipStream_t s, bool api0, bool host, int hdr_t
   for (int k = 0; k < m;) {
     if (f[k].enc.colorGamut == UHDR_HIP_CG_P3) { ++k; continue; }
     CvtBatch cb;
-    bool aligned = true;
-    int cnt = 0;
-    while (k + cnt < m && cnt < kToneChunk) {
-      const EncFile& e = f[k + cnt];
-      if (e.enc.colorGamut != f[k].enc.colorGamut || e.enc.width != f[k].enc.width || e.enc.height != f[k].enc.height) break;
-      bool al_;
-      const CvtImage t = cvt_image(api0 ? e.enc : e.yuv, e.enc, yuv_matrix(e.enc.colorGamut, UHDR_HIP_CG_P3), &al_);
-      if (cnt == 0) aligned = al_;
-      else if (al_ != aligned) break;
-      cb.img[cnt++] = t;
-    }
-    HIP_TRY(launch_convert_yuv(cb, cnt, aligned, s));
-    k += cnt;
+    const uhdr_hip_image_t& e0 = f[k].enc;
+    const Chunk ch = form_chunk(k, m, kToneChunk,
+                                [&](int j) { return f[j].enc.colorGamut == e0.colorGamut && f[j].enc.width == e0.width && f[j].enc.height == e0.height; },
+                                [&](int j, int slot) {
+                                  bool aligned;
+                                  cb.img[slot] = cvt_image(api0 ? f[j].enc : f[j].yuv, f[j].enc, yuv_matrix(e0.colorGamut, UHDR_HIP_CG_P3), &aligned);
+                                  return aligned;
+                                });
+    HIP_TRY(launch_convert_yuv(cb, ch.m, ch.cls, s));
+    k += ch.m;
   }
   // the 2 m compressions
   jpg->clear();
@@ -4721,7 +4713,7 @@ int uhdr_hip_apply_gainmap_packed_batch(int n, const uhdr_hip_image_t* sdrs, con
     AppConsts c = apply_consts(s0, m0, *metadata, max_display_boost, table.idw);
     c.map_stride = (uint32_t)(rgb ? row_stride(m0) : m0.width);
     PackedAppBatch b;
-    const Chunk ch = form_chunk(i, n,
+    const Chunk ch = form_chunk(i, n, kMaxChunk,
                                 [&](int j) {
                                   return sdrs[j].width == s0.width && sdrs[j].height == s0.height && maps[j].width == m0.width &&
                                          maps[j].height == m0.height && (!rgb || row_stride(maps[j]) == row_stride(m0));
@@ -5074,25 +5066,59 @@ int tonemap_check(const uhdr_hip_image_t* src, const uhdr_hip_image_t* dest) {  
     return UHDR_HIP_ERROR_BAD_PTR;  // (the reference would dereference them)
   return UHDR_HIP_NO_ERROR;
 }
-// A toneMap through host memory, for both operators: the P010 planes staged into slots 2 and 3 of `ss`, destination planes in
-// slots 0 and 1, run(staged source, staged destination) enqueued between, then what the reference writes copied back --
-// luma_stride bytes per luma row, chroma_stride bytes per chroma row, V chroma_stride * height / 2 behind U.  Enqueues only.
-int tonemap_through_stage(StageSet* ss, const uhdr_hip_image_t* src, uhdr_hip_image_t* dest, hipStream_t s,
-                          const std::function<int(const uhdr_hip_image_t&, uhdr_hip_image_t&)>& run) {
+// The frame of the single tone-map and convertYuv calls: one image in either memory space through its batch of one, and the headroom
+// H, where the operator has one (with_head), back on the host.  A context is leased and, for H, 256 bytes of its slot 4 reserved;
+// in host memory stage_in(ss, &sd, &dd) stages the image and reserves its destination; run(source, destination, device H) is the
+// batch of one on the staged descriptors (device memory: on the caller's own, sd and dd are not used); in host memory
+// copy_back(dd) enqueues what the call returns; H is read once, the stream waited for, and in host memory fill() completes the
+// caller's descriptor (device memory: the batch has).
+extern "C++" {   // (a template: this part of the file lies inside extern "C")
+template <class StageIn, class Run, class CopyBack, class Fill>
+int single_call(const uhdr_hip_image_t* src, uhdr_hip_image_t* dest, bool host, bool with_head, float* headroom, hipStream_t s,
+                StageIn stage_in, Run run, CopyBack copy_back, Fill fill) {
+  DeviceState* st = nullptr;
+  int rc = current_state(&st);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  StageLease lease(st);
+  StageSet* ss = lease.get();
+  if (ss == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
+  if (with_head && (rc = stage_reserve(ss, 4, 256)) != 0) return rc;
+  float* dh = with_head ? static_cast<float*>(ss->stage[4]) : nullptr;
+  uhdr_hip_image_t sd, dd;
+  if (host && (rc = stage_in(ss, &sd, &dd)) != 0) return rc;
+  if ((rc = host ? run(&sd, &dd, dh) : run(src, dest, dh)) != UHDR_HIP_NO_ERROR) return rc;
+  if (host && (rc = copy_back(dd)) != 0) return rc;
+  float h_out = 0.0f;
+  if (with_head) HIP_TRY(hipMemcpyAsync(&h_out, dh, sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (host) fill();
+  if (with_head && headroom) *headroom = h_out;
+  return UHDR_HIP_NO_ERROR;
+}
+}  // extern "C++"
+// A toneMap's host planes, for both operators: the P010 planes staged into slots 2 and 3 of `ss`, destination planes in slots 0
+// and 1 ...
+int stage_tonemap_in(StageSet* ss, const uhdr_hip_image_t& src, const uhdr_hip_image_t& dest, uhdr_hip_image_t* sd, uhdr_hip_image_t* dd,
+                     hipStream_t s) {
   int rc;
-  uhdr_hip_image_t ds, dd = *dest;
-  if ((rc = stage_p010_in(ss, 2, *src, &ds, s)) != 0) return rc;
-  const size_t h = dest->height, ls = dest->luma_stride, cs = dest->chroma_stride;
+  if ((rc = stage_p010_in(ss, 2, src, sd, s)) != 0) return rc;
+  const size_t h = dest.height, ls = dest.luma_stride, cs = dest.chroma_stride;
   if ((rc = stage_reserve(ss, 0, ls * h)) != 0) return rc;
   if ((rc = stage_reserve(ss, 1, cs * h + cs)) != 0) return rc;
-  dd.data = ss->stage[0];
-  dd.chroma_data = ss->stage[1];
-  if ((rc = run(ds, dd)) != 0) return rc;
-  if (ls * h) HIP_TRY(hipMemcpyAsync(dest->data, dd.data, ls * h, hipMemcpyDeviceToHost, s));
+  *dd = dest;
+  dd->data = ss->stage[0];
+  dd->chroma_data = ss->stage[1];
+  return UHDR_HIP_NO_ERROR;
+}
+// ... and what the reference writes copied back: luma_stride bytes per luma row, chroma_stride bytes per chroma row, V
+// chroma_stride * height / 2 behind U.  Enqueues only.
+int tonemap_copy_back(const uhdr_hip_image_t& dd, const uhdr_hip_image_t& dest, hipStream_t s) {
+  const size_t h = dest.height, ls = dest.luma_stride, cs = dest.chroma_stride;
+  if (ls * h) HIP_TRY(hipMemcpyAsync(dest.data, dd.data, ls * h, hipMemcpyDeviceToHost, s));
   const size_t v_off = cs * h / 2;
   if (cs * (h / 2)) {
-    HIP_TRY(hipMemcpyAsync(dest->chroma_data, dd.chroma_data, cs * (h / 2), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(dest->chroma_data) + v_off, static_cast<uint8_t*>(dd.chroma_data) + v_off,
+    HIP_TRY(hipMemcpyAsync(dest.chroma_data, dd.chroma_data, cs * (h / 2), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(dest.chroma_data) + v_off, static_cast<uint8_t*>(dd.chroma_data) + v_off,
                            cs * (h / 2), hipMemcpyDeviceToHost, s));
   }
   return UHDR_HIP_NO_ERROR;
@@ -5110,48 +5136,31 @@ int uhdr_hip_tonemap_batch(int n, const uhdr_hip_image_t* srcs, uhdr_hip_image_t
   int rc = current_state(&st);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  int i = 0;
-  while (i < n) {
+  for (int i = 0; i < n;) {
     ToneBatch b;
-    bool aligned = true;
-    int m = 0;
-    while (i + m < n && m < kToneChunk) {
-      bool a;
-      const ToneImage t = tone_image(srcs[i + m], dests[i + m], &a);
-      if (m == 0) aligned = a;
-      else if (a != aligned || t.width != b.img[0].width || t.height != b.img[0].height) break;
-      b.img[m++] = t;
-    }
-    HIP_TRY(launch_tonemap(b, m, aligned, s));
-    for (int k = 0; k < m; ++k) dests[i + k].colorGamut = srcs[i + k].colorGamut;  // ultrahdr.cpp:556
-    i += m;
+    const Chunk ch = form_chunk(i, n, kToneChunk, [&](int j) { return srcs[j].width == srcs[i].width && srcs[j].height == srcs[i].height; },
+                                [&](int j, int m) {
+                                  bool aligned;
+                                  b.img[m] = tone_image(srcs[j], dests[j], &aligned);
+                                  return aligned;
+                                });
+    HIP_TRY(launch_tonemap(b, ch.m, ch.cls, s));
+    for (int k = 0; k < ch.m; ++k) dests[i + k].colorGamut = srcs[i + k].colorGamut;  // ultrahdr.cpp:556
+    i += ch.m;
   }
   return UHDR_HIP_NO_ERROR;
 }
 
+// One image: in device memory the batch of one, which only enqueues; host planes go through single_call
 int uhdr_hip_tonemap(const uhdr_hip_image_t* src, uhdr_hip_image_t* dest, int mem_space, void* stream) {
   int rc = tonemap_check(src, dest);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   if (mem_space == UHDR_HIP_MEM_DEVICE) return uhdr_hip_tonemap_batch(1, src, dest, stream);
-  DeviceState* st = nullptr;
-  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-
-  auto run = [&](const uhdr_hip_image_t& sd, const uhdr_hip_image_t& dd) -> int {
-    ToneBatch b;
-    bool aligned;
-    b.img[0] = tone_image(sd, dd, &aligned);
-    HIP_TRY(launch_tonemap(b, 1, aligned, s));
-    return UHDR_HIP_NO_ERROR;
-  };
-
-  StageLease lease(st);
-  StageSet* ss = lease.get();
-  if (ss == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  if ((rc = tonemap_through_stage(ss, src, dest, s, run)) != 0) return rc;
-  HIP_TRY(hipStreamSynchronize(s));
-  dest->colorGamut = src->colorGamut;
-  return UHDR_HIP_NO_ERROR;
+  return single_call(
+      src, dest, true, false, nullptr, s, [&](StageSet* ss, uhdr_hip_image_t* sd, uhdr_hip_image_t* dd) { return stage_tonemap_in(ss, *src, *dest, sd, dd, s); },
+      [&](const uhdr_hip_image_t* sd, uhdr_hip_image_t* dd, float*) { return uhdr_hip_tonemap_batch(1, sd, dd, stream); },
+      [&](const uhdr_hip_image_t& dd) { return tonemap_copy_back(dd, *dest, s); }, [&] { dest->colorGamut = src->colorGamut; });
 }
 
 // ---- tone-mapped SDR base image (include/uhdr_hip.h) -------------------------------------------------
@@ -5207,6 +5216,61 @@ ToneSdrConsts tone_sdr_consts(int gamut, int hdr_tf, float* headroom) {
   for (int i = 0; i < kToneChunk; ++i) c.slot[i] = 0u;
   return c;
 }
+// what the launches of one run take: the planar operator's descriptors and constants, the packed operator's batch; in both, slot[j]
+// is the headroom slot of img[j]
+extern "C++" {   // (overloads and a template inside extern "C")
+struct ToneSdrRun { ToneBatch b; ToneSdrConsts c; };
+ToneImage* run_img(ToneSdrRun& r) { return r.b.img; }
+uint32_t* run_slot(ToneSdrRun& r) { return r.c.slot; }
+TonePackedImage* run_img(TonePackedBatch& r) { return r.img; }
+uint32_t* run_slot(TonePackedBatch& r) { return r.slot; }
+
+// The four steps of both tone-map operators over n images in device memory, image i's headroom in slot i:
+// the slots set -- 0, or the given H --, kToneHeadChunk at a time; pass 1 over the MEASURED members of every run, their descriptors
+// and slots moved to the front of the run's; the slots finished, if anything was measured; pass 2 over every run.
+//   form(i, &run) -> Chunk   the run from image i on (form_chunk), its descriptors in run_img(run)[0 .. m), every slot 0
+//   pass1(run, cnt, cls)     the measuring launch over the first cnt members of `run`
+//   pass2(run, i, m, cls)    the writing launch over the run, then the destination descriptors of images [i, i + m)
+template <class Run, class Form, class Pass1, class Pass2>
+int tone_head_passes(int n, int hdr_tf, const float* hdr_peak_nits, float* headroom, hipStream_t s, Form form, Pass1 pass1, Pass2 pass2) {
+  const float k = adaptive_cap(hdr_tf);
+  auto given = [&](int i) { return hdr_peak_nits != nullptr && hdr_peak_nits[i] > 0.0f; };
+  auto heads = [&](bool finish) -> int {
+    for (int base = 0; base < n; base += kToneHeadChunk) {
+      ToneHeadInit v;
+      const int cnt = std::min(n - base, kToneHeadChunk);
+      for (int j = 0; j < cnt; ++j) v.h[j] = given(base + j) ? tone_headroom(hdr_tf, 0.0f, hdr_peak_nits[base + j]) : 0.0f;
+      if (finish) HIP_TRY(launch_tonemap_head_finish(headroom + base, v, cnt, hdr_tf, k, k, s));
+      else HIP_TRY(launch_tonemap_head_init(headroom + base, v, cnt, s));
+    }
+    return UHDR_HIP_NO_ERROR;
+  };
+  int rc = heads(false);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  bool any_measured = false;
+  for (int i = 0; i < n;) {   // pass 1
+    Run r;
+    const Chunk ch = form(i, &r);
+    int cnt = 0;
+    for (int j = 0; j < ch.m; ++j)
+      if (!given(i + j)) { run_img(r)[cnt] = run_img(r)[j]; run_slot(r)[cnt++] = (uint32_t)(i + j); }
+    if (cnt) {
+      any_measured = true;
+      if ((rc = pass1(r, cnt, ch.cls)) != UHDR_HIP_NO_ERROR) return rc;
+    }
+    i += ch.m;
+  }
+  if (any_measured && (rc = heads(true)) != UHDR_HIP_NO_ERROR) return rc;
+  for (int i = 0; i < n;) {   // pass 2
+    Run r;
+    const Chunk ch = form(i, &r);
+    for (int j = 0; j < ch.m; ++j) run_slot(r)[j] = (uint32_t)(i + j);
+    if ((rc = pass2(r, i, ch.m, ch.cls)) != UHDR_HIP_NO_ERROR) return rc;
+    i += ch.m;
+  }
+  return UHDR_HIP_NO_ERROR;
+}
+}  // extern "C++"
 }  // namespace
 
 int uhdr_hip_tonemap_headroom(int hdr_tf, float gamma_max, float peak_nits, float* headroom) {
@@ -5217,8 +5281,8 @@ int uhdr_hip_tonemap_headroom(int hdr_tf, float gamma_max, float peak_nits, floa
   return UHDR_HIP_NO_ERROR;
 }
 
-// n images in device memory: the slots set, pass 1 over the measured images, the slots finished, pass 2 -- images of equal size,
-// gamut and alignment class that follow each other share the launches of either pass (grid.z = image)
+// n images in device memory: the checks, then tone_head_passes with the planar kernels -- images of equal size, gamut and alignment
+// class that follow each other share the launches of either pass (grid.z = image)
 int uhdr_hip_tonemap_sdr_batch(int n, const uhdr_hip_image_t* srcs, uhdr_hip_image_t* dests, int hdr_tf, int tonemap_op,
                                const float* hdr_peak_nits, float* headroom, void* stream) {
   if (n < 0 || (n > 0 && (srcs == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
@@ -5240,61 +5304,27 @@ int uhdr_hip_tonemap_sdr_batch(int n, const uhdr_hip_image_t* srcs, uhdr_hip_ima
   int rc = current_state(&st);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const float k = adaptive_cap(hdr_tf);
-  auto given = [&](int i) { return hdr_peak_nits != nullptr && hdr_peak_nits[i] > 0.0f; };
-  auto head_init = [&](int base, ToneHeadInit* v) {
-    const int cnt = std::min(n - base, kToneHeadChunk);
-    for (int j = 0; j < cnt; ++j) v->h[j] = given(base + j) ? tone_headroom(hdr_tf, 0.0f, hdr_peak_nits[base + j]) : 0.0f;
-    return cnt;
-  };
-  bool any_measured = false;
-  for (int base = 0; base < n; base += kToneHeadChunk) {
-    ToneHeadInit v;
-    const int cnt = head_init(base, &v);
-    HIP_TRY(launch_tonemap_head_init(headroom + base, v, cnt, s));
-  }
-  // the runs of images that share launches
-  auto run_at = [&](int i, ToneBatch* b, bool* aligned) {
-    int m = 0;
-    while (i + m < n && m < kToneChunk) {
-      bool a;
-      const ToneImage t = tone_sdr_image(srcs[i + m], dests[i + m], &a);
-      if (m == 0) *aligned = a;
-      else if (a != *aligned || t.width != b->img[0].width || t.height != b->img[0].height || srcs[i + m].colorGamut != srcs[i].colorGamut) break;
-      b->img[m++] = t;
-    }
-    return m;
-  };
-  for (int i = 0; i < n;) {   // pass 1
-    ToneBatch b, mb;
-    bool aligned = true;
-    const int m = run_at(i, &b, &aligned);
-    ToneSdrConsts c = tone_sdr_consts(srcs[i].colorGamut, hdr_tf, headroom);
-    int cnt = 0;
-    for (int j = 0; j < m; ++j)
-      if (!given(i + j)) { mb.img[cnt] = b.img[j]; c.slot[cnt++] = (uint32_t)(i + j); }
-    if (cnt) {
-      any_measured = true;
-      HIP_TRY(launch_tonemap_peak(c, mb, cnt, aligned, s));
-    }
-    i += m;
-  }
-  for (int base = 0; any_measured && base < n; base += kToneHeadChunk) {
-    ToneHeadInit v;
-    const int cnt = head_init(base, &v);
-    HIP_TRY(launch_tonemap_head_finish(headroom + base, v, cnt, hdr_tf, k, k, s));
-  }
-  for (int i = 0; i < n;) {   // pass 2
-    ToneBatch b;
-    bool aligned = true;
-    const int m = run_at(i, &b, &aligned);
-    ToneSdrConsts c = tone_sdr_consts(srcs[i].colorGamut, hdr_tf, headroom);
-    for (int j = 0; j < m; ++j) c.slot[j] = (uint32_t)(i + j);
-    HIP_TRY(launch_tonemap_sdr(c, b, m, hdr_tf, aligned, s));
-    for (int j = 0; j < m; ++j) dests[i + j].colorGamut = srcs[i + j].colorGamut;
-    i += m;
-  }
-  return UHDR_HIP_NO_ERROR;
+  return tone_head_passes<ToneSdrRun>(
+      n, hdr_tf, hdr_peak_nits, headroom, s,
+      [&](int i, ToneSdrRun* r) {
+        r->c = tone_sdr_consts(srcs[i].colorGamut, hdr_tf, headroom);
+        return form_chunk(i, n, kToneChunk,
+                          [&](int j) { return srcs[j].width == srcs[i].width && srcs[j].height == srcs[i].height && srcs[j].colorGamut == srcs[i].colorGamut; },
+                          [&](int j, int m) {
+                            bool aligned;
+                            r->b.img[m] = tone_sdr_image(srcs[j], dests[j], &aligned);
+                            return aligned;
+                          });
+      },
+      [&](const ToneSdrRun& r, int cnt, bool aligned) -> int {
+        HIP_TRY(launch_tonemap_peak(r.c, r.b, cnt, aligned, s));
+        return UHDR_HIP_NO_ERROR;
+      },
+      [&](const ToneSdrRun& r, int i, int m, bool aligned) -> int {
+        HIP_TRY(launch_tonemap_sdr(r.c, r.b, m, hdr_tf, aligned, s));
+        for (int j = 0; j < m; ++j) dests[i + j].colorGamut = srcs[i + j].colorGamut;
+        return UHDR_HIP_NO_ERROR;
+      });
 }
 
 int uhdr_hip_tonemap_sdr(const uhdr_hip_image_t* src, uhdr_hip_image_t* dest, int hdr_tf, int tonemap_op, float hdr_peak_nits, float* headroom,
@@ -5310,31 +5340,14 @@ int uhdr_hip_tonemap_sdr(const uhdr_hip_image_t* src, uhdr_hip_image_t* dest, in
   }
   if (!valid_peak_nits(hdr_peak_nits)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if ((rc = tonemap_sdr_check(*src, *dest)) != UHDR_HIP_NO_ERROR) return rc;
-  DeviceState* st = nullptr;
-  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  StageLease lease(st);
-  StageSet* ss = lease.get();
-  if (ss == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  if ((rc = stage_reserve(ss, 4, 256)) != 0) return rc;
-  float* dh = static_cast<float*>(ss->stage[4]);
-  float h_out = 0.0f;
-  if (mem_space == UHDR_HIP_MEM_DEVICE) {
-    if ((rc = uhdr_hip_tonemap_sdr_batch(1, src, dest, hdr_tf, tonemap_op, &hdr_peak_nits, dh, stream)) != UHDR_HIP_NO_ERROR) return rc;
-    HIP_TRY(hipMemcpyAsync(&h_out, dh, sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (headroom) *headroom = h_out;
-    return UHDR_HIP_NO_ERROR;
-  }
-  auto run = [&](const uhdr_hip_image_t& sd, uhdr_hip_image_t& dd) -> int {
-    return uhdr_hip_tonemap_sdr_batch(1, &sd, &dd, hdr_tf, tonemap_op, &hdr_peak_nits, dh, stream);
-  };
-  if ((rc = tonemap_through_stage(ss, src, dest, s, run)) != 0) return rc;
-  HIP_TRY(hipMemcpyAsync(&h_out, dh, sizeof(float), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  dest->colorGamut = src->colorGamut;
-  if (headroom) *headroom = h_out;
-  return UHDR_HIP_NO_ERROR;
+  return single_call(
+      src, dest, mem_space != UHDR_HIP_MEM_DEVICE, true, headroom, s,
+      [&](StageSet* ss, uhdr_hip_image_t* sd, uhdr_hip_image_t* dd) { return stage_tonemap_in(ss, *src, *dest, sd, dd, s); },
+      [&](const uhdr_hip_image_t* sd, uhdr_hip_image_t* dd, float* dh) {
+        return uhdr_hip_tonemap_sdr_batch(1, sd, dd, hdr_tf, tonemap_op, &hdr_peak_nits, dh, stream);
+      },
+      [&](const uhdr_hip_image_t& dd) { return tonemap_copy_back(dd, *dest, s); }, [&] { dest->colorGamut = src->colorGamut; });
 }
 
 // ---- the same operator on packed HDR images (include/uhdr_hip.h) ----------------------------------------
@@ -5376,7 +5389,7 @@ void fill_tone_packed_dest(const uhdr_hip_image_t& src, uhdr_hip_image_t* dest) 
 }
 }  // namespace
 
-// n images in device memory: uhdr_hip_tonemap_sdr_batch's four steps with the packed kernels in the two passes
+// n images in device memory: the checks, then tone_head_passes with the packed kernels
 int uhdr_hip_tonemap_packed_batch(int n, const uhdr_hip_image_t* srcs, uhdr_hip_image_t* dests, int hdr_tf, int tonemap_op,
                                   const float* hdr_peak_nits, float* headroom, void* stream) {
   if (n < 0 || (n > 0 && (srcs == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
@@ -5386,71 +5399,34 @@ int uhdr_hip_tonemap_packed_batch(int n, const uhdr_hip_image_t* srcs, uhdr_hip_
   if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool f16 = n > 0 && srcs[0].pixelFormat == UHDR_HIP_PIX_FMT_RGBA_F16;
-  const float k = adaptive_cap(hdr_tf);
-  auto given = [&](int i) { return hdr_peak_nits != nullptr && hdr_peak_nits[i] > 0.0f; };
-  auto head_init = [&](int base, ToneHeadInit* v) {
-    const int cnt = std::min(n - base, kToneHeadChunk);
-    for (int j = 0; j < cnt; ++j) v->h[j] = given(base + j) ? tone_headroom(hdr_tf, 0.0f, hdr_peak_nits[base + j]) : 0.0f;
-    return cnt;
-  };
-  for (int base = 0; base < n; base += kToneHeadChunk) {
-    ToneHeadInit v;
-    const int cnt = head_init(base, &v);
-    HIP_TRY(launch_tonemap_head_init(headroom + base, v, cnt, s));
-  }
-  // the runs of images that share launches: equal size and alignment class
-  auto run_at = [&](int i, TonePackedBatch* b, bool* aligned) {
-    int m = 0;
-    while (i + m < n && m < kToneChunk) {
-      const uhdr_hip_image_t& sd = srcs[i + m];
-      TonePackedImage t;
-      t.src = sd.data;
-      t.dst = static_cast<uint32_t*>(dests[i + m].data);
-      t.src_stride = (uint32_t)row_stride(sd);
-      t.dst_stride = (uint32_t)packed_stride(dests[i + m], sd.width);
-      t.width = (uint32_t)sd.width; t.height = (uint32_t)sd.height;
-      // 16-byte pieces of the destination (4 pixels) and what they are made of (RGBA1010102: 16 bytes, RGBA F16: 32)
-      const bool a = t.width % 4u == 0 && al(t.src, 16) && t.src_stride % (f16 ? 2u : 4u) == 0 && al(t.dst, 16) && t.dst_stride % 4u == 0;
-      if (m == 0) *aligned = a;
-      else if (a != *aligned || t.width != b->img[0].width || t.height != b->img[0].height) break;
-      b->img[m++] = t;
-    }
-    b->headroom = headroom;
-    b->table = f16 ? nullptr : st->tone_tab + (hdr_tf == UHDR_HIP_TF_PQ ? kTonePackedCodes : 0u);
-    b->k = k;
-    for (int j = 0; j < kToneChunk; ++j) b->slot[j] = 0u;
-    return m;
-  };
-  bool any_measured = false;
-  for (int i = 0; i < n;) {   // pass 1
-    TonePackedBatch b, mb;
-    bool aligned = true;
-    const int m = run_at(i, &b, &aligned);
-    mb = b;
-    int cnt = 0;
-    for (int j = 0; j < m; ++j)
-      if (!given(i + j)) { mb.img[cnt] = b.img[j]; mb.slot[cnt++] = (uint32_t)(i + j); }
-    if (cnt) {
-      any_measured = true;
-      HIP_TRY(launch_tonemap_packed_peak(mb, cnt, f16, aligned, s));
-    }
-    i += m;
-  }
-  for (int base = 0; any_measured && base < n; base += kToneHeadChunk) {
-    ToneHeadInit v;
-    const int cnt = head_init(base, &v);
-    HIP_TRY(launch_tonemap_head_finish(headroom + base, v, cnt, hdr_tf, k, k, s));
-  }
-  for (int i = 0; i < n;) {   // pass 2
-    TonePackedBatch b;
-    bool aligned = true;
-    const int m = run_at(i, &b, &aligned);
-    for (int j = 0; j < m; ++j) b.slot[j] = (uint32_t)(i + j);
-    HIP_TRY(launch_tonemap_packed(b, m, hdr_tf, aligned, s));
-    for (int j = 0; j < m; ++j) fill_tone_packed_dest(srcs[i + j], &dests[i + j]);
-    i += m;
-  }
-  return UHDR_HIP_NO_ERROR;
+  return tone_head_passes<TonePackedBatch>(
+      n, hdr_tf, hdr_peak_nits, headroom, s,
+      [&](int i, TonePackedBatch* b) {   // the run: equal size and alignment class
+        b->headroom = headroom;
+        b->table = f16 ? nullptr : st->tone_tab + (hdr_tf == UHDR_HIP_TF_PQ ? kTonePackedCodes : 0u);
+        b->k = adaptive_cap(hdr_tf);
+        for (int j = 0; j < kToneChunk; ++j) b->slot[j] = 0u;
+        return form_chunk(i, n, kToneChunk, [&](int j) { return srcs[j].width == srcs[i].width && srcs[j].height == srcs[i].height; },
+                          [&](int j, int m) {
+                            TonePackedImage& t = b->img[m];
+                            t.src = srcs[j].data;
+                            t.dst = static_cast<uint32_t*>(dests[j].data);
+                            t.src_stride = (uint32_t)row_stride(srcs[j]);
+                            t.dst_stride = (uint32_t)packed_stride(dests[j], srcs[j].width);
+                            t.width = (uint32_t)srcs[j].width; t.height = (uint32_t)srcs[j].height;
+                            // 16-byte pieces of the destination (4 pixels) and what they are made of (RGBA1010102: 16 bytes, RGBA F16: 32)
+                            return t.width % 4u == 0 && al(t.src, 16) && t.src_stride % (f16 ? 2u : 4u) == 0 && al(t.dst, 16) && t.dst_stride % 4u == 0;
+                          });
+      },
+      [&](const TonePackedBatch& b, int cnt, bool aligned) -> int {
+        HIP_TRY(launch_tonemap_packed_peak(b, cnt, f16, aligned, s));
+        return UHDR_HIP_NO_ERROR;
+      },
+      [&](const TonePackedBatch& b, int i, int m, bool aligned) -> int {
+        HIP_TRY(launch_tonemap_packed(b, m, hdr_tf, aligned, s));
+        for (int j = 0; j < m; ++j) fill_tone_packed_dest(srcs[i + j], &dests[i + j]);
+        return UHDR_HIP_NO_ERROR;
+      });
 }
 
 int uhdr_hip_tonemap_packed(const uhdr_hip_image_t* src, uhdr_hip_image_t* dest, int hdr_tf, int tonemap_op, float hdr_peak_nits,
@@ -5459,105 +5435,95 @@ int uhdr_hip_tonemap_packed(const uhdr_hip_image_t* src, uhdr_hip_image_t* dest,
   const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
   int rc = tone_packed_check(1, src, dest, hdr_tf, tonemap_op, &hdr_peak_nits, false, nullptr, host);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
-  DeviceState* st = nullptr;
-  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  StageLease lease(st);
-  StageSet* ss = lease.get();
-  if (ss == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  if ((rc = stage_reserve(ss, 4, 256)) != 0) return rc;
-  float* dh = static_cast<float*>(ss->stage[4]);
-  float h_out = 0.0f;
-  if (!host) {
-    if ((rc = uhdr_hip_tonemap_packed_batch(1, src, dest, hdr_tf, tonemap_op, &hdr_peak_nits, dh, stream)) != UHDR_HIP_NO_ERROR) return rc;
-  } else {   // rows of the pixels alone, at a 64-byte pitch; only the pixels come back: the columns [width, stride) stay as they are
-    const size_t w = src->width, h = src->height, bpp = src->pixelFormat == UHDR_HIP_PIX_FMT_RGBA_F16 ? 8 : 4;
-    const size_t sp = round_up(w * bpp, 64), dp = round_up(w * 4, 64);
-    if ((rc = stage_reserve(ss, 2, sp * h)) != 0) return rc;
-    if ((rc = stage_reserve(ss, 0, dp * h)) != 0) return rc;
-    if ((rc = h2d_plane(ss->stage[2], sp, src->data, packed_stride(*src, w) * bpp, w * bpp, h, 1, s)) != 0) return rc;
-    uhdr_hip_image_t sd = *src, dd = *dest;
-    sd.data = ss->stage[2]; sd.luma_stride = sp / bpp;
-    dd.data = ss->stage[0]; dd.luma_stride = dp / 4;
-    if ((rc = uhdr_hip_tonemap_packed_batch(1, &sd, &dd, hdr_tf, tonemap_op, &hdr_peak_nits, dh, stream)) != UHDR_HIP_NO_ERROR) return rc;
-    if (w * h)
-      HIP_TRY(hipMemcpy2DAsync(dest->data, packed_stride(*dest, w) * 4, dd.data, dp, w * 4, h, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(hipMemcpyAsync(&h_out, dh, sizeof(float), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (host) fill_tone_packed_dest(*src, dest);
-  if (headroom) *headroom = h_out;
-  return UHDR_HIP_NO_ERROR;
+  // host memory: rows of the pixels alone, at a 64-byte pitch; only the pixels come back: the columns [width, stride) stay as they are
+  const size_t w = src->width, h = src->height, bpp = src->pixelFormat == UHDR_HIP_PIX_FMT_RGBA_F16 ? 8 : 4;
+  const size_t sp = round_up(w * bpp, 64), dp = round_up(w * 4, 64);
+  return single_call(
+      src, dest, host, true, headroom, s,
+      [&](StageSet* ss, uhdr_hip_image_t* sd, uhdr_hip_image_t* dd) {
+        int rc;
+        if ((rc = stage_reserve(ss, 2, sp * h)) != 0) return rc;
+        if ((rc = stage_reserve(ss, 0, dp * h)) != 0) return rc;
+        if ((rc = h2d_plane(ss->stage[2], sp, src->data, packed_stride(*src, w) * bpp, w * bpp, h, 1, s)) != 0) return rc;
+        *sd = *src; *dd = *dest;
+        sd->data = ss->stage[2]; sd->luma_stride = sp / bpp;
+        dd->data = ss->stage[0]; dd->luma_stride = dp / 4;
+        return (int)UHDR_HIP_NO_ERROR;
+      },
+      [&](const uhdr_hip_image_t* sd, uhdr_hip_image_t* dd, float* dh) {
+        return uhdr_hip_tonemap_packed_batch(1, sd, dd, hdr_tf, tonemap_op, &hdr_peak_nits, dh, stream);
+      },
+      [&](const uhdr_hip_image_t& dd) -> int {
+        if (w * h) HIP_TRY(hipMemcpy2DAsync(dest->data, packed_stride(*dest, w) * 4, dd.data, dp, w * 4, h, hipMemcpyDeviceToHost, s));
+        return UHDR_HIP_NO_ERROR;
+      },
+      [&] { fill_tone_packed_dest(*src, dest); });
 }
 
 namespace {
-int convert_check(const uhdr_hip_image_t* image, int src_encoding, int dest_encoding) {   // jpegr.cpp:1134-1197
-  if (image == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+// JpegR::convertYuv's checks (jpegr.cpp:1134-1197): the encodings, which decide alone when they are equal (NO_ERROR, whatever the
+// planes) or when there is no image to look at (n == 0), and then the planes of every image
+int convert_encodings_check(int src_encoding, int dest_encoding) {
   if (src_encoding == UHDR_HIP_CG_UNSPECIFIED || dest_encoding == UHDR_HIP_CG_UNSPECIFIED)
     return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
   if (!valid_gamut(src_encoding) || !valid_gamut(dest_encoding)) return UHDR_HIP_ERROR_INVALID_COLORGAMUT;
   return UHDR_HIP_NO_ERROR;
+}
+int convert_planes_check(const uhdr_hip_image_t& image) {
+  return image.data == nullptr || image.chroma_data == nullptr ? UHDR_HIP_ERROR_BAD_PTR : UHDR_HIP_NO_ERROR;
 }
 }  // namespace
 
 // JpegR::convertYuv over n images in device memory, in place: images of equal size (and equal alignment class) share a launch
 int uhdr_hip_convert_yuv_batch(int n, uhdr_hip_image_t* images, int src_encoding, int dest_encoding, void* stream) {
   if (n < 0 || (n > 0 && images == nullptr)) return UHDR_HIP_ERROR_BAD_PTR;
-  int rc = convert_check(n > 0 ? &images[0] : nullptr, src_encoding, dest_encoding);
-  if (n == 0) rc = (src_encoding == UHDR_HIP_CG_UNSPECIFIED || dest_encoding == UHDR_HIP_CG_UNSPECIFIED || !valid_gamut(src_encoding) ||
-                    !valid_gamut(dest_encoding)) ? UHDR_HIP_ERROR_INVALID_COLORGAMUT : UHDR_HIP_NO_ERROR;
+  int rc = convert_encodings_check(src_encoding, dest_encoding);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   if (src_encoding == dest_encoding) return UHDR_HIP_NO_ERROR;
   for (int i = 0; i < n; ++i)
-    if (images[i].data == nullptr || images[i].chroma_data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+    if ((rc = convert_planes_check(images[i])) != UHDR_HIP_NO_ERROR) return rc;
   const float* m = yuv_matrix(src_encoding, dest_encoding);
   DeviceState* st = nullptr;
   if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  int i = 0;
-  while (i < n) {
+  for (int i = 0; i < n;) {
     CvtBatch b;
-    bool aligned = true;
-    int k = 0;
-    while (i + k < n && k < kToneChunk) {
-      bool a;
-      const CvtImage t = cvt_image(images[i + k], images[i + k], m, &a);
-      if (k == 0) aligned = a;
-      else if (a != aligned || t.width != b.img[0].width || t.height != b.img[0].height) break;
-      b.img[k++] = t;
-    }
-    HIP_TRY(launch_convert_yuv(b, k, aligned, s));
-    i += k;
+    const Chunk ch = form_chunk(i, n, kToneChunk, [&](int j) { return images[j].width == images[i].width && images[j].height == images[i].height; },
+                                [&](int j, int k) {
+                                  bool aligned;
+                                  b.img[k] = cvt_image(images[j], images[j], m, &aligned);
+                                  return aligned;
+                                });
+    HIP_TRY(launch_convert_yuv(b, ch.m, ch.cls, s));
+    i += ch.m;
   }
   return UHDR_HIP_NO_ERROR;
 }
 
+// One image: in device memory the batch of one, which only enqueues; host planes go through single_call -- the image staged into
+// slots 0 and 1, converted in place there, and its pixels (whole 2x2 blocks of them) copied back
 int uhdr_hip_convert_yuv(uhdr_hip_image_t* image, int src_encoding, int dest_encoding, int mem_space, void* stream) {
-  int rc = convert_check(image, src_encoding, dest_encoding);
+  if (image == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  int rc = convert_encodings_check(src_encoding, dest_encoding);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   if (src_encoding == dest_encoding) return UHDR_HIP_NO_ERROR;
-  if (image->data == nullptr || image->chroma_data == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
+  if ((rc = convert_planes_check(*image)) != UHDR_HIP_NO_ERROR) return rc;
   if (mem_space == UHDR_HIP_MEM_DEVICE) return uhdr_hip_convert_yuv_batch(1, image, src_encoding, dest_encoding, stream);
-  const float* m = yuv_matrix(src_encoding, dest_encoding);
-  DeviceState* st = nullptr;
-  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  auto run = [&](const uhdr_hip_image_t& d) -> int { return convert_yuv_into(d, d, m, s); };
-  StageLease lease(st);
-  if (lease.get() == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  uhdr_hip_image_t d;
-  if ((rc = stage_yuv420_in(lease.get(), 0, *image, &d, s)) != 0) return rc;
-  if ((rc = run(d)) != 0) return rc;
-  const size_t w = image->width, h = image->height, cw = w / 2, ch = h / 2;
-  if ((rc = d2h_plane(image->data, image->luma_stride, d.data, d.luma_stride, cw * 2, ch * 2, 1, s)) != 0) return rc;
-  uint8_t* hu = static_cast<uint8_t*>(image->chroma_data);
-  const uint8_t* du = static_cast<const uint8_t*>(d.chroma_data);
-  if ((rc = d2h_plane(hu, image->chroma_stride, du, d.chroma_stride, cw, ch, 1, s)) != 0) return rc;
-  if ((rc = d2h_plane(hu + image->chroma_stride * (h / 2), image->chroma_stride, du + d.chroma_stride * (h / 2),
-                      d.chroma_stride, cw, ch, 1, s)) != 0)
-    return rc;
-  HIP_TRY(hipStreamSynchronize(s));
-  return UHDR_HIP_NO_ERROR;
+  return single_call(
+      nullptr, image, true, false, nullptr, s, [&](StageSet* ss, uhdr_hip_image_t*, uhdr_hip_image_t* d) { return stage_yuv420_in(ss, 0, *image, d, s); },
+      [&](const uhdr_hip_image_t*, uhdr_hip_image_t* d, float*) { return uhdr_hip_convert_yuv_batch(1, d, src_encoding, dest_encoding, stream); },
+      [&](const uhdr_hip_image_t& d) {
+        const size_t h = image->height, cw = image->width / 2, ch = h / 2;
+        int rc;
+        if ((rc = d2h_plane(image->data, image->luma_stride, d.data, d.luma_stride, cw * 2, ch * 2, 1, s)) != 0) return rc;
+        uint8_t* hu = static_cast<uint8_t*>(image->chroma_data);
+        const uint8_t* du = static_cast<const uint8_t*>(d.chroma_data);
+        if ((rc = d2h_plane(hu, image->chroma_stride, du, d.chroma_stride, cw, ch, 1, s)) != 0) return rc;
+        return d2h_plane(hu + image->chroma_stride * (h / 2), image->chroma_stride, du + d.chroma_stride * (h / 2), d.chroma_stride, cw, ch, 1, s);
+      },
+      [] {});
 }
 
 // ---------------------------------------------------------------------------------------------------
