@@ -1372,6 +1372,44 @@ int uhdr_hip_jpegr_encode_packed_sampling_batch(int n, const uhdr_hip_image_t* h
                                                 const size_t* out_capacity, size_t* out_size, int* status, int rgb_map, int primary_sampling,
                                                 const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream);
 
+/* ---- Progressive files from the JPEG encoder ---------------------------------------------------------------
+ * libjpeg's jpeg_simple_progression, which Pillow writes for progressive=True: SOF2 and ten scans (six for a single plane) over the
+ * quantised coefficients the baseline call computes -- DC at Al 1, luma AC 1-5 at Al 2, Cr and Cb AC 1-63 at Al 1, luma AC 6-63 at
+ * Al 2, the luma refinement to Al 1, the DC refinement, and the refinements of Cr, Cb and luma to Al 0 --, each scan behind the DHT
+ * segment(s) of tables built from its own symbols and its SOS.  The file equals, byte for byte, what libjpeg-turbo writes; it
+ * decodes to the baseline file's pixels and is usually a few per cent smaller than the optimised baseline file.  Symbols,
+ * end-of-band runs across blocks, buffered correction bits, histograms, tables, segments, bit offsets, emission and stuffing of
+ * every scan are the device's work: the call synchronises no more often, and its launches do not grow with images or blocks.
+ *
+ * The _scans calls take every argument and convention of their _opts call with `scan_mode` directly behind opts.
+ * UHDR_HIP_SCANS_BASELINE IS that call: bytes, statuses, order of checks.  Any other value than the two below is the call's
+ * ERROR_UNSUPPORTED_FEATURE, checked right after the opts check, before any pointer is looked at and before the device is touched.
+ * With UHDR_HIP_SCANS_PROGRESSIVE:
+ *   - a non-zero restart_interval or restart_in_rows is the call's ERROR_UNSUPPORTED_FEATURE at the same place: restart intervals
+ *     inside progressive scans are not written;
+ *   - UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN is accepted and changes nothing: a progressive file has tables of its own in every scan, as
+ *     libjpeg forces optimize_coding for it;
+ *   - the planes call covers YUV420, MONOCHROME, YUV444, YUV422 and YUV440, the RGBA call the samplings 4:4:4, 4:2:2 and 4:2:0; in
+ *     the JPEG/R call the primary image and the gain-map JPEG are both progressive;
+ *   - memory spaces, ICC, the size probe, per-file statuses and rounds are the _opts call's.  A file of more than 8 000 000 blocks
+ *     is that file's ERROR_UNSUPPORTED_FEATURE (the optimised path's limit is 15 873 015);
+ *   - a scan whose optimal code would be deeper than 32 bits has no default table to fall back to (Annex K's AC table has no EOBn
+ *     symbols): that file's status is ERROR_UNSUPPORTED_FEATURE, as libjpeg fails with JERR_HUFF_CLEN_OVERFLOW;
+ *   - a progressive file can be longer than its baseline form (small images: ten scan headers); size a buffer by the size probe.
+ * uhdr_hip_jpeg_decode_batch_ex, uhdr_hip_jpegr_decode and the shim's decodeJPEGR read these files. */
+#define UHDR_HIP_SCANS_BASELINE 0
+#define UHDR_HIP_SCANS_PROGRESSIVE 1
+int uhdr_hip_jpeg_encode_planes_batch_scans(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
+                                            const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                            const uhdr_hip_jpeg_encode_opts_t* opts, int scan_mode, int mem_space, void* stream);
+int uhdr_hip_jpeg_encode_rgba_batch_scans(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
+                                          const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                          int sampling, const uhdr_hip_jpeg_encode_opts_t* opts, int scan_mode, int mem_space, void* stream);
+int uhdr_hip_jpegr_encode_batch_scans(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                                      const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                      size_t* out_size, int* status, const uhdr_hip_jpeg_encode_opts_t* opts, int scan_mode, int mem_space,
+                                      void* stream);
+
 /* Bench / test support: the deterministic synthetic frame pair of SURVEY.md 8(d) (an LCG; tests/ and bench.py compare it with the
  * oracle's serial loop), written into device memory: p010 = width*height*3/2 uint16 (luma, then interleaved UV, values in the
  * legal 10-bit ranges << 6), yuv = width*height*3/2 bytes (Y, U, V).  width and height even; enqueued on `stream`. */

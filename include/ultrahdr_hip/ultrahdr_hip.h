@@ -342,6 +342,13 @@ class JpegRHip {
   // no intervals, whatever is set here.
   void setRestartInterval(unsigned mcus) { mRestartInterval = mcus; }
   void setRestartInRows(unsigned rows) { mRestartInRows = rows; }
+  // false (default): baseline files.  true: the same two overloads write the primary image and the gain-map JPEG as progressive files
+  // (uhdr_hip_jpegr_encode_batch_scans with UHDR_HIP_SCANS_PROGRESSIVE: SOF2, libjpeg's simple progression, tables of its own in
+  // every scan whatever setOptimizeHuffman says).  The pixels do not change, and decodeJPEGR reads the file.  It refuses what
+  // setOptimizeHuffman refuses -- setGainMapScaleFactor, setMultiChannelGainMap, setToneMap, setContentBoost -- and a restart setting
+  // with ERROR_ULTRAHDR_UNSUPPORTED_FEATURE, as does encodeJPEGRPacked with a setPrimarySampling other than 4:2:0, the one place where
+  // a packed overload reads these options.  Every other overload writes baseline files, whatever is set here.
+  void setProgressive(bool on) { mProgressive = on; }
   // UHDR_HIP_PIX_FMT_YUV420 (default): both encodeJPEGRPacked overloads compress the SDR image as 4:2:0.  UHDR_HIP_PIX_FMT_YUV444 or
   // YUV422: the primary image keeps its chroma at full or at half horizontal resolution (uhdr_hip_jpegr_encode_packed_sampling_batch;
   // the overload without an SDR image tone-maps one first, as the packed API-0 does); gain map, metadata and container do not change,
@@ -361,6 +368,7 @@ class JpegRHip {
   bool mAnyGainMapMetadata = false;
   bool mOptimizeHuffman = false;
   unsigned mRestartInterval = 0, mRestartInRows = 0;
+  bool mProgressive = false;
   int mGainMapScaleFactor = 4;
   int mPrimarySampling = 1;   // UHDR_HIP_PIX_FMT_YUV420
 };

@@ -262,6 +262,11 @@ SIGNATURES["uhdr_hip_jpeg_encode_rgba_batch_opts"] = (lambda res, args: (res, ar
     *SIGNATURES["uhdr_hip_jpeg_encode_rgba420_batch_opts"])
 SIGNATURES["uhdr_hip_jpegr_encode_packed_sampling_batch"] = (lambda res, args: (res, args[:-2] + [C.c_int, _OP] + args[-2:]))(
     *SIGNATURES["uhdr_hip_jpegr_encode_packed_batch"])
+# progressive files: the _opts calls with `scan_mode` directly behind opts
+SCANS_BASELINE = 0
+SCANS_PROGRESSIVE = 1
+for _name in ("uhdr_hip_jpeg_encode_planes_batch", "uhdr_hip_jpeg_encode_rgba_batch", "uhdr_hip_jpegr_encode_batch"):
+    SIGNATURES[_name + "_scans"] = (lambda res, args: (res, args[:-2] + [C.c_int] + args[-2:]))(*SIGNATURES[_name + "_opts"])
 
 _lib = None
 

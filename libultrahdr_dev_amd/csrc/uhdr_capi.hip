@@ -1656,13 +1656,18 @@ struct EncJpeg {
                                          // (mcu_planes: jpeg::launch_rgba_to_ycc422's)
   bool optimize = false;                 // UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN: the file's own Huffman tables, built on the device
   uint32_t restart_interval = 0, restart_in_rows = 0;   // uhdr_hip_jpeg_encode_opts_t's, as given: the file's width decides (enc_restart)
+  bool progressive = false;              // UHDR_HIP_SCANS_PROGRESSIVE: SOF2 and libjpeg's simple progression, every scan built on the device
+  bool clen_overflow = false;            // out: such a file whose tables libjpeg would refuse (jpeg::kProgClenOverflow): no bytes, no size
 };
 
 // what the _ex and _opts encode calls say beyond their arguments (encode_flags, encode_opts)
 struct EncOpt {
   bool optimize = false;
   uint32_t restart_interval = 0, restart_in_rows = 0;
-  void to(EncJpeg* e) const { e->optimize = optimize; e->restart_interval = restart_interval; e->restart_in_rows = restart_in_rows; }
+  bool progressive = false;   // the _scans calls' scan_mode (encode_scans)
+  void to(EncJpeg* e) const {
+    e->optimize = optimize; e->restart_interval = restart_interval; e->restart_in_rows = restart_in_rows; e->progressive = progressive;
+  }
 };
 
 // the flags of the _ex encode calls: a bit this library does not know is the call's error, seen before the device is touched
@@ -1678,6 +1683,18 @@ int encode_opts(const uhdr_hip_jpeg_encode_opts_t* opts, EncOpt* eo) {
   eo->optimize = (opts->flags & UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN) != 0;
   eo->restart_interval = opts->restart_interval;
   eo->restart_in_rows = opts->restart_in_rows;
+  return UHDR_HIP_NO_ERROR;
+}
+// The _scans calls: the options, then the scan mode -- both before any pointer is looked at.  A progressive file has tables of its own
+// in every scan whatever the flag says (libjpeg forces optimize_coding), and no restart intervals here
+int encode_scans(const uhdr_hip_jpeg_encode_opts_t* opts, int scan_mode, EncOpt* eo) {
+  const int rc = encode_opts(opts, eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  if (scan_mode != UHDR_HIP_SCANS_BASELINE && scan_mode != UHDR_HIP_SCANS_PROGRESSIVE) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (scan_mode == UHDR_HIP_SCANS_BASELINE) return UHDR_HIP_NO_ERROR;
+  if (eo->restart_interval != 0 || eo->restart_in_rows != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  eo->progressive = true;
+  eo->optimize = false;
   return UHDR_HIP_NO_ERROR;
 }
 // the same for the flags word of the _ex calls
@@ -1701,7 +1718,7 @@ size_t enc_workspace_bytes(size_t w, size_t h, jpeg::Geometry geom, const EncOpt
   uint32_t intervals = 0;
   enc_restart(j, eo.restart_interval, eo.restart_in_rows, &intervals);
   jpeg::Layout l;
-  return jpeg::workspace_bytes(j.nblk, &l, intervals);
+  return jpeg::workspace_bytes(j.nblk, &l, intervals, eo.progressive);
 }
 // The first guess at a file's size, restart markers apart: what compress_to_host stages a file at when nobody says (cap == 0), and
 // what a file of a plain-JPEG batch holds of its round's page-locked memory.  One byte per pixel for 4:2:0 and monochrome files, three
@@ -1718,7 +1735,12 @@ bool optimizable(size_t w, size_t h, jpeg::Geometry geom) {
   return j.nblk <= jpeg::kMaxOptimizeBlocks;
 }
 bool encodable_with(size_t w, size_t h, jpeg::Geometry geom, const EncOpt& eo) {
-  if (eo.optimize && !optimizable(w, h, geom)) return false;
+  if ((eo.optimize || eo.progressive) && !optimizable(w, h, geom)) return false;
+  if (eo.progressive) {   // (and the limit of its own: the segments' markers are kept as 32-bit offsets into the packed stream)
+    jpeg::Job j;
+    encode_job_tables(w, h, geom, 75, &j);
+    return j.nblk <= jpeg::kMaxProgressiveBlocks;
+  }
   if (eo.restart_interval == 0 && eo.restart_in_rows == 0) return true;
   jpeg::Job j;
   encode_job_tables(w, h, geom, 75, &j);
@@ -1756,15 +1778,16 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
       jobs[i].rst_blocks = ri * jobs[i].rst_bpm;
       jobs[i].rst_marks = intervals - 1u;
     }
-    ws_total += round_up(jpeg::workspace_bytes(jobs[i].nblk, &lay[i], intervals), 256);
+    ws_total += round_up(jpeg::workspace_bytes(jobs[i].nblk, &lay[i], intervals, e.progressive), 256);
     jobs[i].optimize = e.optimize ? 1 : 0;
+    jobs[i].progressive = e.progressive ? 1 : 0;   // (the prefix ends in SOF2; every scan's DHT and SOS segments are the device's)
     // The header split: with optimised tables the host writes SOI ... SOF alone, and the device appends its DHT and SOS segments.
     // Such a header is never longer than the default one -- baseline 8-bit data has at most 12 DC and 162 AC symbols, the sizes of
     // the Annex K tables --, so whatever is sized for the default header (a file's first-guess staging, a caller's capacity that
     // holds the default file) holds this one.
     const jpeg::Geometry geom = e.geom >= 0 ? (jpeg::Geometry)e.geom : enc_geom(e.img, e.rgb);
     jpeg::build_header((int)e.img.width, (int)e.img.height, geom, e.quality, e.icc ? e.icc->data() : nullptr,
-                       e.icc ? e.icc->size() : 0, header[i], e.optimize, ri);
+                       e.icc ? e.icc->size() : 0, header[i], e.optimize || e.progressive, ri, e.progressive);
     // (the first guess holds the DRI segment and three bytes per interval as well)
     if (im[i].cap == 0) im[i].cap = enc_first_guess(e.img.width, e.img.height, geom) + (ri != 0 ? 6 + 3 * (size_t)intervals : 0);
     off[i] = hp_total;
@@ -1783,7 +1806,7 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     const size_t hn = header[i].size();
     memcpy(hp + off[i], header[i].data(), hn);
     sizes[i] = 0;
-    if (e.to_dev && e.optimize) {   // whether the header fits is the device's to say: it copies the prefix from here if it does
+    if (e.to_dev && (e.optimize || e.progressive)) {   // whether the header fits is the device's to say: it copies the prefix from here if it does
       outs[i] = jpeg::BatchOut{e.dev_out, e.dev_cap, hn, &sizes[i], hp + off[i]};
     } else if (e.to_dev) {   // as uhdr_hip_jpeg_encode into device memory: the header only where it fits, no stream byte otherwise
       const bool fits = e.dev_cap >= hn;
@@ -1801,6 +1824,7 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
   for (int i = 0; i < k; ++i) {
     EncJpeg& e = im[i];
     const uint64_t total = sizes[i];
+    if (total == jpeg::kProgClenOverflow) { e.bytes = nullptr; e.n = 0; e.clen_overflow = true; continue; }
     if (total != 0 && e.to_dev) { e.bytes = nullptr; e.n = (size_t)total; continue; }   // the kernels kept to dev_cap
     if (total != 0 && total <= e.cap) { e.bytes = hp + off[i]; e.n = (size_t)total; continue; }
     if (total != 0 && total > e.keep_max) { e.bytes = nullptr; e.n = (size_t)total; continue; }
@@ -1815,6 +1839,7 @@ int compress_to_host(DeviceState* st, hipStream_t s, int k, EncJpeg* im, bool ma
     one.optimize = e.optimize;
     one.restart_interval = e.restart_interval;
     one.restart_in_rows = e.restart_in_rows;
+    one.progressive = e.progressive;
     if (lease.get() == nullptr || compress_to_host(lease.get(), s, 1, &one, false) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_ENCODE_ERROR;
     e.big.assign(one.bytes, one.bytes + one.n);
     e.bytes = e.big.data();
@@ -2213,6 +2238,7 @@ int jpeg_encode_files(const JpegBatch& a, const EncOpt& eo, int mem_space, void*
           for (int k = lo; k < hi; ++k) {
             const int i = idx[k];
             a.out_size[i] = im[(size_t)k].n;
+            if (im[(size_t)k].clen_overflow) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }
             if (im[(size_t)k].n > a.out_capacity[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
             if (host_out) memcpy(a.out[i], im[(size_t)k].bytes, im[(size_t)k].n);
             st_[i] = UHDR_HIP_NO_ERROR;
@@ -2265,6 +2291,18 @@ int uhdr_hip_jpeg_encode_planes_batch_opts(int n, const uhdr_hip_image_t* images
                                            const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
   EncOpt eo;
   const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpeg_encode_files(JpegBatch{n, images, quality, icc, icc_size, out, out_capacity, out_size, status}, eo, mem_space, stream,
+                           PlanesFamily{true});
+}
+
+// uhdr_hip_jpeg_encode_planes_batch_opts with the scan mode said: UHDR_HIP_SCANS_BASELINE is that call,
+// UHDR_HIP_SCANS_PROGRESSIVE writes every file as libjpeg's jpeg_simple_progression does
+int uhdr_hip_jpeg_encode_planes_batch_scans(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc,
+                                            const size_t* icc_size, void* const* out, const size_t* out_capacity, size_t* out_size, int* status,
+                                            const uhdr_hip_jpeg_encode_opts_t* opts, int scan_mode, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_scans(opts, scan_mode, &eo);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   return jpeg_encode_files(JpegBatch{n, images, quality, icc, icc_size, out, out_capacity, out_size, status}, eo, mem_space, stream,
                            PlanesFamily{true});
@@ -2329,6 +2367,18 @@ int uhdr_hip_jpeg_encode_rgba_batch_opts(int n, const uhdr_hip_image_t* images, 
                                          const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
   EncOpt eo;
   const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  const JpegBatch a{n, images, quality, icc, icc_size, out, out_capacity, out_size, status};
+  if (sampling == UHDR_HIP_PIX_FMT_YUV444) return jpeg_encode_files(a, eo, mem_space, stream, Rgba444Family{});
+  if (sampling != UHDR_HIP_PIX_FMT_YUV422 && sampling != UHDR_HIP_PIX_FMT_YUV420) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return jpeg_encode_files(a, eo, mem_space, stream, RgbaSubsampledFamily{sampling == UHDR_HIP_PIX_FMT_YUV422});
+}
+// the same with the scan mode said, as uhdr_hip_jpeg_encode_planes_batch_scans takes it
+int uhdr_hip_jpeg_encode_rgba_batch_scans(int n, const uhdr_hip_image_t* images, const int* quality, const void* const* icc, const size_t* icc_size,
+                                          void* const* out, const size_t* out_capacity, size_t* out_size, int* status, int sampling,
+                                          const uhdr_hip_jpeg_encode_opts_t* opts, int scan_mode, int mem_space, void* stream) {
+  EncOpt eo;
+  const int rc = encode_scans(opts, scan_mode, &eo);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   const JpegBatch a{n, images, quality, icc, icc_size, out, out_capacity, out_size, status};
   if (sampling == UHDR_HIP_PIX_FMT_YUV444) return jpeg_encode_files(a, eo, mem_space, stream, Rgba444Family{});
@@ -3124,7 +3174,8 @@ void append_containers(int m, const EncJpeg* jpg, Idx idx, const uhdr_hip_metada
       const EncJpeg& gm = jpg[2 * (size_t)k + 1];
       uhdr_hip_metadata_t mk = md;
       if (range != nullptr) fill_adaptive_metadata(range[2 * (size_t)k], range[2 * (size_t)k + 1], &mk);
-      st_[i] = jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
+      if (sdr.clen_overflow || gm.clen_overflow) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }   // (a progressive file)
+      st_[i] =jpegr::append_gainmap_to(sdr.bytes, sdr.n, gm.bytes, gm.n, static_cast<const uint8_t*>(exif ? exif[i] : nullptr), exif ? exif_size[i] : 0,
                                         nullptr, 0, mk, static_cast<uint8_t*>(out[i]), out_capacity[i], &out_size[i], range != nullptr);
       if (metadata != nullptr) metadata[i] = mk;
     }
@@ -3461,6 +3512,18 @@ int uhdr_hip_jpegr_encode_batch_opts(int n, const uhdr_hip_image_t* p010_images,
                                      size_t* out_size, int* status, const uhdr_hip_jpeg_encode_opts_t* opts, int mem_space, void* stream) {
   EncOpt eo;
   const int rc = encode_opts(opts, &eo);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  return jpegr_encode_batch_with(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, eo, mem_space,
+                                 stream);
+}
+
+// the same with the scan mode said: the primary image and the gain-map JPEG of every file are both written in it
+int uhdr_hip_jpegr_encode_batch_scans(int n, const uhdr_hip_image_t* p010_images, const uhdr_hip_image_t* yuv420_images, int hdr_tf, int quality,
+                                      const void* const* exif, const size_t* exif_size, void* const* out, const size_t* out_capacity,
+                                      size_t* out_size, int* status, const uhdr_hip_jpeg_encode_opts_t* opts, int scan_mode, int mem_space,
+                                      void* stream) {
+  EncOpt eo;
+  const int rc = encode_scans(opts, scan_mode, &eo);
   if (rc != UHDR_HIP_NO_ERROR) return rc;
   return jpegr_encode_batch_with(n, p010_images, yuv420_images, hdr_tf, quality, exif, exif_size, out, out_capacity, out_size, status, eo, mem_space,
                                  stream);

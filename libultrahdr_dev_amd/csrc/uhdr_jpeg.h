@@ -48,9 +48,39 @@ struct Job {
   uint32_t rst_marks;      // RSTn markers in the stream: one behind every interval but the last
   uint32_t* rst_pfx;       // nblk: the bits of the blocks in front of each, modulo 2^32, without padding and markers
   uint32_t* rst_mark;      // rst_marks: where each marker's 0xFF stands in the packed stream (bytes), ascending
+  // progressive files (progressive != 0): the job runs through the k_jpeg_prog_* launches of its round.  All scans share one packed
+  // stream -- each scan's DHT and SOS segments in front of its bits, every scan padded to a byte --; rst_mark / rst_marks hold the
+  // positions of those segments' markers, which get no stuffed zero.  hist and huff hold kProgTables tables.  The arrays below have one
+  // row of pg_stride entries per scan, indexed by a block's position in the scan's own order
+  int progressive;
+  uint32_t pg_stride;      // nblk + 1
+  uint32_t pg_nwg;         // workgroups of 128 positions in the longest scan
+  uint16_t* pg_info;       // AC scans: bit 0: the block codes a symbol; bit 1: its band ends in an end-of-band run; bits 2..8: correction
+                           // bits it leaves to the run
+  uint64_t* pg_left;       // those bits, first one highest
+  uint32_t* pg_corr;       // correction bits left to runs by the positions in front (position N: all)
+  uint32_t* pg_nzc;        // positions in front that code a symbol
+  uint32_t* pg_fstart;     // a run is flushed behind this position: its first position (kProgNone: no flush)
+  uint32_t* pg_pend;       // the first position of the run pending in front of this position (the position itself: none); entry N: at
+                           // the scan's end
+  uint32_t* pg_bits;       // bits this position writes
+  uint32_t* pg_wg;         // per scan and workgroup: [0] positions that code a symbol, [1] correction bits left, [2] bits; 3 x scans x pg_nwg
+  uint8_t* pg_meta;        // ProgMeta
+};
+constexpr int kProgScans = 10, kProgTables = 10;
+constexpr uint32_t kProgNone = 0xFFFFFFFFu;
+constexpr uint32_t kProgHdrMax = 576;     // a scan's DHT and SOS segments: at most two tables of 21 + 256 bytes and 14 bytes
+struct ProgMeta {
+  uint64_t seg_start[kProgScans + 1];     // bit offset of each scan's segments in the packed stream; [scans]: the stream's length
+  uint64_t data_start[kProgScans];        // ... of its entropy-coded bits
+  uint32_t hdr_bytes[kProgScans];
+  uint32_t nmark[kProgScans], mark_rel[kProgScans][3];   // the markers inside a scan's segments
+  uint32_t clen_overflow;                 // a table's optimal code is deeper than 32 bits: no file (libjpeg: JERR_HUFF_CLEN_OVERFLOW)
+  uint8_t hdr[kProgScans][kProgHdrMax];
 };
 struct Layout {
   size_t coef, bits, bits_blk, stream, stream_bytes, ff_count, ff_blk, totals, scan_tmp, scan_tmp_bytes, hist, huff, rst_pfx, rst_mark;
+  size_t pg_info, pg_left, pg_corr, pg_nzc, pg_fstart, pg_pend, pg_bits, pg_wg, pg_meta;   // progressive jobs only
   uint32_t max_chunks;
 };
 
@@ -64,15 +94,21 @@ inline int geom_hs(Geometry g) { return (g == kGeom420 || g == kGeom422) ? 2 : 1
 inline int geom_vs(Geometry g) { return (g == kGeom420 || g == kGeom440) ? 2 : 1; }
 // prefix_only: SOI ... SOF alone -- the DHT and SOS segments of a file with optimised tables are written on the device
 // restart_interval != 0 (and not prefix_only): a DRI segment between the last DHT and SOS
+// progressive (with prefix_only): the frame header is SOF2
 void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& out, bool prefix_only = false,
-                  uint32_t restart_interval = 0);
+                  uint32_t restart_interval = 0, bool progressive = false);
 // libjpeg's restart_in_rows over restart_interval: MCUs per interval of a scan with mcus_per_row MCUs in a row (0: none)
 uint32_t restart_mcus(uint32_t restart_interval, uint32_t restart_in_rows, uint32_t mcus_per_row);
 // a job with restart intervals (Job::rst_blocks) works in a stream area that also holds their padding and markers; the packed stream
 // is addressed in 32 bits there, so such a job has at most kMaxRestartBlocks blocks
 constexpr uint32_t kMaxRestartBlocks = 20000000u;
 // intervals: ceil(MCUs / restart interval) of such a job, 0 for every other
-size_t workspace_bytes(uint32_t nblk, Layout* l, uint32_t intervals = 0);
+// progressive: the workspace of a progressive job (no intervals): a stream area for all scans, kProgTables tables, the per-scan arrays
+size_t workspace_bytes(uint32_t nblk, Layout* l, uint32_t intervals = 0, bool progressive = false);
+// a progressive job marks its segments' markers in 32-bit stream offsets, and its stream takes up to 496 bytes per block
+constexpr uint32_t kMaxProgressiveBlocks = 8000000u;
+// out_size of a progressive file whose tables libjpeg would refuse (ProgMeta::clen_overflow)
+constexpr uint64_t kProgClenOverflow = ~0ull;
 // enqueues the whole encoder; the JPEG (without the header, which the caller places at out[0, header_len)) lands at
 // out + header_len, its total size (header included) in the uint64 at ws + l.totals + 8
 hipError_t encode_async(Job j, const Layout& l, uint8_t* ws, uint8_t* out, uint64_t out_cap, uint64_t header_len, hipStream_t s);

@@ -18,6 +18,7 @@
 //   k_rgba_to_ycc422    the same for a 4:2:2 file: h2v1 downsampler, MCUs of 16 x 8 pixels
 //   k_jpeg_opt_*        (Job::optimize) the same chain with Huffman tables built from the image's own symbol counts, see below
 //   k_jpeg_rst_*        (Job::rst_blocks) the same chain with restart intervals -- padding, RSTn markers, the DC prediction cut --, see below
+//   k_jpeg_prog_*       (Job::progressive) SOF2: libjpeg's simple progression, ten scans over the same coefficients, see below
 //
 // Byte-exact against libjpeg for every size, stride regime and quality tested (tests/test_gpu_jpeg.py against
 // oracle/jpeg_oracle.c, which tests/test_jpeg_oracle.py pins to the libjpeg builds of the image).
@@ -137,7 +138,7 @@ void put_dht(std::vector<uint8_t>& b, int cls_idx, const uint8_t bits[16], const
 }  // namespace
 
 void build_header(int w, int h, Geometry geom, int quality, const void* icc, size_t icc_n, std::vector<uint8_t>& b, bool prefix_only,
-                  uint32_t restart_interval) {
+                  uint32_t restart_interval, bool progressive) {
   const bool gray = geom == kGeomGray;
   uint16_t ql[64], qc[64];
   quant_table(quality, false, ql);
@@ -154,7 +155,7 @@ void build_header(int w, int h, Geometry geom, int quality, const void* icc, siz
   put_dqt(b, 0, ql);
   if (!gray) put_dqt(b, 1, qc);
   const int nc = gray ? 1 : 3;
-  put16(b, 0xFFC0); put16(b, (unsigned)(8 + 3 * nc)); b.push_back(8); put16(b, (unsigned)h); put16(b, (unsigned)w);
+  put16(b, progressive ? 0xFFC2 : 0xFFC0); put16(b, (unsigned)(8 + 3 * nc)); b.push_back(8); put16(b, (unsigned)h); put16(b, (unsigned)w);
   b.push_back((uint8_t)nc);
   for (int c = 0; c < nc; ++c) {
     b.push_back((uint8_t)(c + 1));
@@ -1323,6 +1324,574 @@ __global__ void __launch_bounds__(256) k_jpeg_rst_stuff_copy_batch(const Job* __
   }
 }
 
+// ---- progressive files (Job::progressive != 0) ---------------------------------------------------------------------------------------
+// libjpeg's jpeg_simple_progression (jcphuff.c) for the jobs of a round that ask for it: SOF2 and ten scans (six for one plane) over the
+// job's coefficients, each with tables of its own.  These jobs run through launches of their own, whose grids are (workgroups of 128
+// positions) x (scans): blockIdx.y is the scan, and a position is a block's place in that scan's order -- MCU order, the workspace's own,
+// for the DC scans; the component's block grid in raster order, MCU padding left out, for the AC scans (prog_block).
+//   k_jpeg_prog_zero_batch     the job's kProgTables x 256 counters to zero
+//   k_jpeg_opt_fdct_batch[...] as they are
+//   k_jpeg_prog_info_batch     AC scans: per position whether it codes a symbol, whether its band ends in an end-of-band run and the
+//                              correction bits it leaves to that run (refinement scans); per workgroup their sums
+//   k_jpeg_prog_prefix_batch   the exclusive sums of both over the scan's positions
+//   k_jpeg_prog_walk_batch     where runs are flushed.  A run lives between two positions that code a symbol; it is flushed in front
+//                              of the second, at the scan's end, when it is 0x7FFF blocks long and -- refinement scans -- when more
+//                              than 937 correction bits are pending.  The last rule is greedy, hence not associative: the thread of
+//                              the position a run starts behind walks it, one binary search in the prefix sums per flush (a walk per
+//                              run)
+//   k_jpeg_prog_hist_batch     the symbols of every scan, the EOBn ones of the flushes among them, counted
+//   k_jpeg_prog_tables_batch   one workgroup per job, one wave per table: jpeg_gen_optimal_table; then one wave per scan: its DHT and
+//                              SOS segments into the job's workspace
+//   k_jpeg_prog_count_batch    bits per position and per workgroup
+//   k_jpeg_prog_layout_batch   where each scan's segments and bits start in the one packed stream, the stream's length, the markers'
+//                              positions
+//   k_jpeg_prog_clear_batch, k_jpeg_prog_emit_batch
+//                              the words cleared and written; the first workgroup of a scan copies its segments in front
+//   k_jpeg_prog_stuff_count_batch, k_jpeg_prog_stuff_copy_batch
+//                              the restart jobs' stuffing: 0x00 behind every 0xFF but a marker's (Job::rst_mark holds the segments')
+struct ProgScan {
+  int8_t comp;   // the scan's component, -1: all of them, interleaved (the DC scans)
+  int8_t ss, se, ah, al;
+  int8_t tbl;    // its first table among the job's kProgTables (a DC scan of three components has two: luma, chroma); -1: none
+};
+__constant__ ProgScan c_prog_scans[2][kProgScans] = {
+    {{-1, 0, 0, 0, 1, 0}, {0, 1, 5, 0, 2, 2}, {2, 1, 63, 0, 1, 3}, {1, 1, 63, 0, 1, 4}, {0, 6, 63, 0, 2, 5},
+     {0, 1, 63, 2, 1, 6}, {-1, 0, 0, 1, 0, -1}, {2, 1, 63, 1, 0, 7}, {1, 1, 63, 1, 0, 8}, {0, 1, 63, 1, 0, 9}},
+    {{-1, 0, 0, 0, 1, 0}, {0, 1, 5, 0, 2, 1}, {0, 6, 63, 0, 2, 2}, {0, 1, 63, 2, 1, 3}, {-1, 0, 0, 1, 0, -1},
+     {0, 1, 63, 1, 0, 4}, {0, 0, 0, 0, 0, -1}, {0, 0, 0, 0, 0, -1}, {0, 0, 0, 0, 0, -1}, {0, 0, 0, 0, 0, -1}}};
+__device__ __forceinline__ uint32_t prog_nscans(const Job& j) { return j.gray ? 6u : 10u; }
+__device__ __forceinline__ uint32_t prog_ntables(const Job& j) { return j.gray ? 5u : 10u; }
+__device__ __forceinline__ uint32_t prog_scan_tables(const Job& j, const ProgScan& d) { return d.tbl < 0 ? 0u : (d.ss == 0 && !j.gray) ? 2u : 1u; }
+__device__ __forceinline__ uint32_t prog_positions(const Job& j, const ProgScan& d) {
+  if (d.comp < 0 || j.gray) return j.nblk;
+  return d.comp == 0 ? j.ybw * j.ybh : j.nblk / (j.hs * j.vs + 2u);
+}
+// the workspace index (MCU order) of position p of a scan
+__device__ __forceinline__ uint32_t prog_block(const Job& j, const ProgScan& d, uint32_t p) {
+  if (d.comp < 0 || j.gray) return p;
+  const uint32_t nl = j.hs * j.vs, bpm = nl + 2u;
+  if (d.comp > 0) return p * bpm + nl + (uint32_t)(d.comp - 1);
+  const uint32_t br = p / j.ybw, bc = p - br * j.ybw;
+  return ((br / j.vs) * j.mcus_x + bc / j.hs) * bpm + (br % j.vs) * j.hs + (bc % j.hs);
+}
+// the preamble of the (workgroup, scan) kernels: false where the workgroup has nothing to do
+struct ProgWg {
+  uint32_t s, wg, p, npos;
+  ProgScan d;
+};
+__device__ __forceinline__ bool prog_wg(const Job& j, uint32_t first, bool ac_only, ProgWg* w) {
+  w->s = blockIdx.y;
+  if (w->s >= prog_nscans(j)) return false;
+  w->d = c_prog_scans[j.gray ? 1 : 0][w->s];
+  if (ac_only && w->d.ss == 0) return false;
+  w->npos = prog_positions(j, w->d);
+  w->wg = blockIdx.x - first;
+  w->p = w->wg * 128u + threadIdx.x;
+  return w->wg * 128u < w->npos;
+}
+__device__ __forceinline__ ProgMeta* prog_meta(const Job& j) { return reinterpret_cast<ProgMeta*>(j.pg_meta); }
+__device__ __forceinline__ uint32_t* prog_wg_sums(const Job& j, uint32_t what, uint32_t s) { return j.pg_wg + ((size_t)what * kProgScans + s) * j.pg_nwg; }
+
+// The sinks of a position's symbols.  sym: a Huffman symbol of the scan's table t (0; 1: the chroma DC table) with n extra bits; raw:
+// n <= 63 bits as they are; corr: the `be` correction bits the positions [a, b) of a run left to it (Job::pg_left), in their order
+struct ProgHistSink {
+  uint32_t* hist;   // the scan's 1 or 2 x 256 counters in LDS
+  __device__ __forceinline__ void sym(int t, int symbol, uint32_t, int) { atomicAdd(&hist[t * 256 + symbol], 1u); }
+  __device__ __forceinline__ void raw(uint64_t, int) {}
+  __device__ __forceinline__ void corr(const Job&, size_t, uint32_t, uint32_t, uint32_t) {}
+};
+struct ProgCountSink {
+  uint32_t bits = 0;
+  __device__ __forceinline__ void sym(int t, int symbol, uint32_t, int n) { bits += (LdsHuff::table()[t * 256 + symbol] >> 16) + (uint32_t)n; }
+  __device__ __forceinline__ void raw(uint64_t, int n) { bits += (uint32_t)n; }
+  __device__ __forceinline__ void corr(const Job&, size_t, uint32_t, uint32_t, uint32_t be) { bits += be; }
+};
+struct ProgEmitSink {
+  EmitSink es;
+  __device__ __forceinline__ void sym(int t, int symbol, uint32_t extra, int n) {   // <= 16 + 14 bits
+    const uint32_t h = LdsHuff::table()[t * 256 + symbol];
+    es.put(((h & 0xffffu) << n) | extra, (int)(h >> 16) + n);
+  }
+  __device__ __forceinline__ void raw(uint64_t v, int n) {
+    if (n > 32) { es.put((uint32_t)(v >> 32), n - 32); n = 32; }
+    if (n > 0) es.put((uint32_t)v & (n == 32 ? 0xFFFFFFFFu : (1u << n) - 1u), n);
+  }
+  // few of a run's blocks leave bits (a run of flat blocks: none), so the next one that does is searched in the prefix sums
+  __device__ __forceinline__ void corr(const Job& j, size_t row, uint32_t a, uint32_t b, uint32_t be) {
+    const uint32_t* __restrict__ cs = j.pg_corr + row;
+    uint32_t x = a;
+    while (be != 0u) {
+      const uint32_t base = cs[x];
+      uint32_t y = x;
+      if (cs[x + 1u] == base) {
+        uint32_t lo = x + 1u, hi = b - 1u;   // the first y with cs[y + 1] > base; there is one
+        while (lo < hi) {
+          const uint32_t mid = (lo + hi) >> 1;
+          if (cs[mid + 1u] > base) hi = mid;
+          else lo = mid + 1u;
+        }
+        y = lo;
+      }
+      const uint32_t nb = cs[y + 1u] - base;
+      raw(j.pg_left[row + y], (int)nb);
+      be -= nb;
+      x = y + 1u;
+    }
+  }
+};
+
+// One block of an AC scan as bit masks over its zigzag positions, the band applied (bit k: coefficient k), v = abs(coefficient) >> Al:
+// nzm: v != 0; one: v == 1 -- in a refinement scan the newly non-zero coefficients; lsb: v & 1, a correction bit where v > 1; neg: the
+// coefficient's sign.  The walks below visit the set bits alone -- a loop over all 63 positions, unrolled so that the coefficients'
+// registers are indexed at compile time, costs over 100 VGPRs and spills scalar registers once per scan shape.
+// lds (a first scan, or nullptr): the thread's row of ProgCoefLds, which takes the coefficients themselves for the walk to index
+constexpr uint32_t kProgCoefRow = 33;   // dwords per thread: 64 coefficients and one of padding against bank conflicts
+struct ProgMasks {
+  uint64_t nzm, one, lsb, neg;
+};
+__device__ __forceinline__ ProgMasks prog_masks(const int16_t* __restrict__ zz, const ProgScan& d, uint32_t* lds) {
+  ProgMasks r = {0, 0, 0, 0};
+  const int al = d.al;
+#pragma nounroll
+  for (int k = 0; k < 8; ++k) {   // (rolled: unrolled, the eight loads and their 64 values are all in flight and take 100 VGPRs)
+    const uint4 v = reinterpret_cast<const uint4*>(zz)[k];
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t nz = 0, one = 0, lsb = 0, neg = 0;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      if (lds != nullptr) lds[4 * k + m] = w[m];
+#pragma unroll
+      for (int hlf = 0; hlf < 2; ++hlf) {
+        const int q = 2 * m + hlf;
+        const int t = (int)(int16_t)(hlf ? w[m] >> 16 : w[m] & 0xffffu), a = (t < 0 ? -t : t) >> al;
+        nz |= (a != 0 ? 1u : 0u) << q;
+        one |= (a == 1 ? 1u : 0u) << q;
+        lsb |= (uint32_t)(a & 1) << q;
+        neg |= (t < 0 ? 1u : 0u) << q;
+      }
+    }
+    r.nzm |= (uint64_t)nz << (8 * k);
+    r.one |= (uint64_t)one << (8 * k);
+    r.lsb |= (uint64_t)lsb << (8 * k);
+    r.neg |= (uint64_t)neg << (8 * k);
+  }
+  const uint64_t band = (~0ull >> (63 - d.se)) & (~0ull << d.ss);
+  r.nzm &= band;
+  r.one &= band;
+  return r;
+}
+// jcphuff.c encode_mcu_AC_first without its end-of-band bookkeeping: the symbols of a block that has any
+template <class SINK>
+__device__ __forceinline__ void prog_ac_first(const ProgMasks& b, const ProgScan& d, const uint32_t* lds, SINK& sk) {
+  const int16_t* c = reinterpret_cast<const int16_t*>(lds);
+  int prev = d.ss - 1;
+#pragma nounroll
+  for (uint64_t m = b.nzm; m != 0; m &= m - 1u) {
+    const int k = __builtin_ctzll(m);
+    int r = k - prev - 1;
+    prev = k;
+    while (r > 15) { sk.sym(0, 0xF0, 0u, 0); r -= 16; }
+    const int t = c[k], a = (t < 0 ? -t : t) >> d.al;
+    const int nb = nbits_of(a);
+    sk.sym(0, (r << 4) + nb, (uint32_t)(t < 0 ? ~a : a) & ((1u << nb) - 1u), nb);
+  }
+}
+// encode_mcu_AC_refine likewise: run/1 symbols with a sign bit for the newly non-zero coefficients, ZRL up to the last of them, the
+// correction bits of the coefficients in between behind the next symbol.  What is left behind the last symbol is the run's (pg_left)
+template <class SINK>
+__device__ __forceinline__ void prog_ac_refine(const ProgMasks& b, const ProgScan& d, SINK& sk) {
+  if (b.one == 0) return;
+  const int eob = 63 - __builtin_clzll(b.one);
+  int prev = d.ss - 1, r = 0, br = 0;
+  uint64_t bb = 0;
+#pragma nounroll
+  for (uint64_t m = b.nzm & (~0ull >> (63 - eob)); m != 0; m &= m - 1u) {
+    const int k = __builtin_ctzll(m);
+    r += k - prev - 1;
+    prev = k;
+    while (r > 15) {
+      sk.sym(0, 0xF0, 0u, 0);
+      r -= 16;
+      sk.raw(bb, br);
+      bb = 0; br = 0;
+    }
+    if (!((b.one >> k) & 1u)) { bb = (bb << 1) | ((b.lsb >> k) & 1u); ++br; continue; }
+    sk.sym(0, (r << 4) + 1, (uint32_t)((b.neg >> k) & 1u) ^ 1u, 1);
+    sk.raw(bb, br);
+    bb = 0; br = 0; r = 0;
+  }
+}
+// a run of the positions [a, b) flushed (emit_eobrun): EOBn, the low bits of its length, its correction bits
+template <class SINK>
+__device__ __forceinline__ void prog_flush(const Job& j, size_t row, uint32_t a, uint32_t b, SINK& sk) {
+  const uint32_t cnt = b - a;   // 1 .. 0x7FFF
+  const int nb = 31 - __builtin_clz(cnt);
+  sk.sym(0, nb << 4, cnt & ((1u << nb) - 1u), nb);
+  const uint32_t be = j.pg_corr[row + b] - j.pg_corr[row + a];
+  if (be != 0u) sk.corr(j, row, a, b, be);
+}
+// everything position p of scan w.s writes, in order
+// s_coef: the workgroup's 128 x kProgCoefRow dwords of LDS
+template <class SINK>
+__device__ __forceinline__ void prog_position(const Job& j, const ProgWg& w, uint32_t* s_coef, SINK& sk) {
+  const ProgScan d = w.d;
+  const uint32_t p = w.p;
+  if (d.ss == 0) {   // encode_mcu_DC_first / encode_mcu_DC_refine
+    const int v = (int)j.coef[(size_t)p * 64u] >> d.al;
+    if (d.ah != 0) { sk.raw((uint64_t)(v & 1), 1); return; }
+    int t2 = v - (pred_of(j, p) >> d.al), t = t2;
+    if (t < 0) { t = -t; t2--; }
+    const int nb = nbits_of(t);
+    sk.sym(comp_of(j, p), nb, (uint32_t)t2 & ((1u << nb) - 1u), nb);
+    return;
+  }
+  const size_t row = (size_t)w.s * j.pg_stride;
+  if (j.pg_info[row + p] & 1u) {
+    const uint32_t s0 = j.pg_pend[row + p];
+    if (s0 < p) prog_flush(j, row, s0, p, sk);
+    uint32_t* lds = d.ah != 0 ? nullptr : s_coef + threadIdx.x * kProgCoefRow;   // (uniform per workgroup, as the scan is)
+    const ProgMasks b = prog_masks(j.coef + (size_t)prog_block(j, d, p) * 64u, d, lds);
+    if (d.ah != 0) prog_ac_refine(b, d, sk);
+    else prog_ac_first(b, d, lds, sk);
+  }
+  uint32_t fs = j.pg_fstart[row + p];
+  if (p == w.npos - 1u && fs == kProgNone) {   // the scan's end flushes what is pending; a run flushed behind p left nothing
+    const uint32_t s0 = j.pg_pend[row + w.npos];
+    if (s0 < w.npos) fs = s0;
+  }
+  if (fs != kProgNone) prog_flush(j, row, fs, p + 1u, sk);
+}
+// the tables of the workgroup's scan into LDS
+__device__ __forceinline__ void prog_load_huff(const Job& j, const ProgScan& d) {
+  uint32_t* s_huff = LdsHuff::table();
+  const uint32_t n = 256u * prog_scan_tables(j, d);
+  for (uint32_t k = threadIdx.x; k < n; k += 128u) s_huff[k] = j.huff[256u * (uint32_t)d.tbl + k];
+  __syncthreads();
+}
+
+__global__ void __launch_bounds__(256) k_jpeg_prog_zero_batch(const Job* __restrict__ jobs) {
+  const Job& j = uniform_ref(jobs, blockIdx.x);
+  for (uint32_t k = threadIdx.x; k < (uint32_t)kProgTables * 256u; k += 256u) j.hist[k] = 0u;
+}
+__global__ void __launch_bounds__(128) k_jpeg_prog_info_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint32_t s_part[2];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  ProgWg w;
+  if (!prog_wg(j, first, true, &w)) return;   // (uniform per workgroup)
+  const size_t row = (size_t)w.s * j.pg_stride;
+  uint32_t nz = 0, tb = 0;
+  if (w.p < w.npos) {
+    // nz: the block codes a symbol; tail: its band ends in an end-of-band run -- the band's last coefficient decides: a zero (a first
+    // scan), anything but a newly non-zero one (a refinement); tb, bb: the correction bits behind its last symbol, which the run takes
+    const ProgMasks b = prog_masks(j.coef + (size_t)prog_block(j, w.d, w.p) * 64u, w.d, nullptr);
+    const uint64_t sym = w.d.ah != 0 ? b.one : b.nzm;
+    nz = sym != 0 ? 1u : 0u;
+    const uint32_t tail = (uint32_t)((sym >> w.d.se) & 1u) ^ 1u;
+    uint64_t bb = 0;
+    if (w.d.ah != 0) {
+      uint64_t m = b.nzm & ~b.one;
+      if (b.one != 0) m &= ~(~0ull >> __builtin_clzll(b.one));   // (those above the last newly non-zero one)
+#pragma nounroll
+      for (; m != 0; m &= m - 1u) { bb = (bb << 1) | ((b.lsb >> __builtin_ctzll(m)) & 1u); ++tb; }
+    }
+    j.pg_info[row + w.p] = (uint16_t)(nz | (tail << 1) | (tb << 2));
+    j.pg_left[row + w.p] = bb;
+    j.pg_fstart[row + w.p] = kProgNone;
+    j.pg_pend[row + w.p] = w.p;
+    if (w.p == w.npos - 1u) j.pg_pend[row + w.npos] = w.npos;
+  }
+  const uint32_t nzs = block_sum<128>(nz, s_part), tbs = block_sum<128>(tb, s_part);
+  if (threadIdx.x == 0u) { prog_wg_sums(j, 0, w.s)[w.wg] = nzs; prog_wg_sums(j, 1, w.s)[w.wg] = tbs; }
+}
+__global__ void __launch_bounds__(128) k_jpeg_prog_prefix_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint32_t s_part[2];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  ProgWg w;
+  if (!prog_wg(j, first, true, &w)) return;
+  const size_t row = (size_t)w.s * j.pg_stride;
+  uint32_t nz0 = 0, tb0 = 0;
+  for (uint32_t g = threadIdx.x; g < w.wg; g += 128u) { nz0 += prog_wg_sums(j, 0, w.s)[g]; tb0 += prog_wg_sums(j, 1, w.s)[g]; }
+  nz0 = block_sum<128>(nz0, s_part);
+  tb0 = block_sum<128>(tb0, s_part);
+  const uint32_t info = w.p < w.npos ? j.pg_info[row + w.p] : 0u;
+  const uint32_t nz = info & 1u, tb = (info >> 2) & 127u;
+  const uint32_t nzx = nz0 + block_exclusive_sum<128>(nz, s_part), tbx = tb0 + block_exclusive_sum<128>(tb, s_part);
+  if (w.p >= w.npos) return;
+  j.pg_nzc[row + w.p] = nzx;
+  j.pg_corr[row + w.p] = tbx;
+  if (w.p == w.npos - 1u) { j.pg_nzc[row + w.npos] = nzx + nz; j.pg_corr[row + w.npos] = tbx + tb; }
+}
+// One thread per position h that a run can start behind: the first position and every one that codes a symbol.  Its run ends in front
+// of the next such position `lim`; most of them follow at once.
+__global__ void __launch_bounds__(128) k_jpeg_prog_walk_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  ProgWg w;
+  if (!prog_wg(j, first, true, &w)) return;
+  if (w.p >= w.npos) return;
+  const size_t row = (size_t)w.s * j.pg_stride;
+  const uint32_t N = w.npos, h = w.p;
+  const uint32_t info = j.pg_info[row + h];
+  if (h != 0u && !(info & 1u)) return;
+  const uint32_t* __restrict__ nzc = j.pg_nzc + row;
+  const uint32_t* __restrict__ cs = j.pg_corr + row;
+  uint32_t s = (info & 3u) == 1u ? h + 1u : h;   // a block that codes a symbol and ends on one starts no run itself
+  uint32_t lim = h + 1u;
+  if (lim < N && !(j.pg_info[row + lim] & 1u)) {   // the first position behind h that codes a symbol, N if none does
+    uint32_t lo = h + 2u, hi = N;
+    const uint32_t base = nzc[h + 1u];
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (nzc[mid + 1u] > base) hi = mid;
+      else lo = mid + 1u;
+    }
+    lim = lo;
+  }
+  const bool refine = w.d.ah != 0;
+  while (s < lim) {
+    if (lim - s < 0x7FFFu && cs[lim] - cs[s] <= 937u) break;   // nothing forces a flush any more
+    uint32_t e = s + 0x7FFEu;   // the run's 0x7FFF-th block
+    if (refine) {               // or the first one with more than MAX_CORR_BITS - DCTSIZE2 + 1 bits pending behind it
+      const uint32_t target = cs[s] + 937u;
+      uint32_t lo = s, hi = lim;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (cs[mid + 1u] > target) hi = mid;
+        else lo = mid + 1u;
+      }
+      e = lo < e ? lo : e;
+    }
+    if (e >= lim) break;
+    j.pg_fstart[row + e] = s;
+    s = e + 1u;
+  }
+  j.pg_pend[row + lim] = s;
+}
+__global__ void __launch_bounds__(128) k_jpeg_prog_hist_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint32_t s_hist[2 * 256];
+  __shared__ uint32_t s_coef[128 * kProgCoefRow];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  ProgWg w;
+  if (!prog_wg(j, first, false, &w)) return;
+  const uint32_t nbins = 256u * prog_scan_tables(j, w.d);
+  if (nbins == 0u) return;   // (a DC refinement scan has no symbols)
+  for (uint32_t b = threadIdx.x; b < nbins; b += 128u) s_hist[b] = 0u;
+  __syncthreads();
+  if (w.p < w.npos) {
+    ProgHistSink sk{s_hist};
+    prog_position(j, w, s_coef, sk);
+  }
+  __syncthreads();
+  for (uint32_t b = threadIdx.x; b < nbins; b += 128u) {
+    const uint32_t v = s_hist[b];
+    if (v != 0u) atomicAdd(&j.hist[256u * (uint32_t)w.d.tbl + b], v);
+  }
+}
+// One workgroup per job.  Wave t builds table t; a table libjpeg would refuse has no default to stand in -- Annex K's AC table knows no
+// EOBn symbol --, so the file is refused (ProgMeta::clen_overflow).  Then wave t writes the DHT and SOS segments of scan t
+// (jcmarker.c write_scan_header) into ProgMeta::hdr, and says where their markers stand.
+__global__ void __launch_bounds__(64 * kProgTables) k_jpeg_prog_tables_batch(const Job* __restrict__ jobs, const BatchOut* __restrict__ outs) {
+  __shared__ TableLds s_tbl[kProgTables];
+  const Job& j = uniform_ref(jobs, blockIdx.x);
+  const BatchOut& o = uniform_ref(outs, blockIdx.x);
+  ProgMeta* m = prog_meta(j);
+  const uint32_t t = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  const bool active = t < prog_ntables(j);
+  if (threadIdx.x == 0u) m->clen_overflow = 0u;
+  const bool overflow = build_table(j.hist + 256u * t, active, s_tbl[t], j.huff + 256u * t);   // (its barriers order the two stores)
+  if (overflow && active && lane == 0u) m->clen_overflow = 1u;
+  if (threadIdx.x == 0u) *j.hdr_len = (uint32_t)o.header_len;
+  if (o.prefix != nullptr && o.header_len <= o.out_cap)
+    for (uint32_t q = threadIdx.x; q < (uint32_t)o.header_len; q += 64u * kProgTables) o.out[q] = o.prefix[q];
+  if (t >= prog_nscans(j)) return;
+  const ProgScan d = c_prog_scans[j.gray ? 1 : 0][t];
+  uint8_t* hd = m->hdr[t];
+  uint32_t at = 0, nm = 0;
+  const uint32_t ntab = prog_scan_tables(j, d);
+  for (uint32_t q = 0; q < ntab; ++q) {
+    const TableLds& L = s_tbl[(uint32_t)d.tbl + q];
+    const uint32_t nv = L.nvals;
+    const uint32_t id = d.ss == 0 ? q : (0x10u | (d.comp == 0 ? 0u : 1u));
+    for (uint32_t b = lane; b < 21u + nv; b += 64u) {
+      uint32_t v;
+      if (b == 0u) v = 0xFFu;
+      else if (b == 1u) v = 0xC4u;
+      else if (b == 2u) v = (19u + nv) >> 8;
+      else if (b == 3u) v = (19u + nv) & 0xffu;
+      else if (b == 4u) v = id;
+      else if (b < 21u) v = L.bits[b - 4u];
+      else v = L.vals[b - 21u];
+      hd[at + b] = (uint8_t)v;
+    }
+    if (lane == 0u) m->mark_rel[t][nm] = at;
+    ++nm;
+    at += 21u + nv;
+  }
+  const uint32_t ns = d.comp < 0 ? (j.gray ? 1u : 3u) : 1u, sos = 8u + 2u * ns;
+  if (lane < sos) {   // jcmarker.c emit_sos: no table selector where the scan uses none
+    uint32_t v;
+    if (lane == 0u) v = 0xFFu;
+    else if (lane == 1u) v = 0xDAu;
+    else if (lane == 2u) v = 0u;
+    else if (lane == 3u) v = 6u + 2u * ns;
+    else if (lane == 4u) v = ns;
+    else if (lane < 5u + 2u * ns) {
+      const uint32_t c = d.comp < 0 ? (lane - 5u) / 2u : (uint32_t)d.comp, tb = c == 0u ? 0u : 1u;
+      v = ((lane - 5u) & 1u) ? ((d.ss == 0 && d.ah == 0 ? tb << 4 : 0u) | (d.se != 0 ? tb : 0u)) : c + 1u;
+    } else {
+      const uint32_t q = lane - (5u + 2u * ns);
+      v = q == 0u ? (uint32_t)d.ss : q == 1u ? (uint32_t)d.se : ((uint32_t)d.ah << 4) | (uint32_t)d.al;
+    }
+    hd[at + lane] = (uint8_t)v;
+  }
+  if (lane == 0u) { m->mark_rel[t][nm] = at; m->nmark[t] = nm + 1u; m->hdr_bytes[t] = at + sos; }
+}
+__global__ void __launch_bounds__(128) k_jpeg_prog_count_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint32_t s_part[2];
+  __shared__ uint32_t s_coef[128 * kProgCoefRow];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  ProgWg w;
+  if (!prog_wg(j, first, false, &w)) return;
+  if (prog_meta(j)->clen_overflow) return;
+  prog_load_huff(j, w.d);
+  uint32_t my_bits = 0;
+  if (w.p < w.npos) {
+    ProgCountSink sk;
+    prog_position(j, w, s_coef, sk);
+    j.pg_bits[(size_t)w.s * j.pg_stride + w.p] = my_bits = sk.bits;
+  }
+  const uint32_t total = block_sum<128>(my_bits, s_part);
+  if (threadIdx.x == 0u) prog_wg_sums(j, 2, w.s)[w.wg] = total;
+}
+// One workgroup per job: the scans' lengths, then where everything stands in the packed stream -- scan after scan its segments, its
+// bits, the padding to a byte
+__global__ void __launch_bounds__(256) k_jpeg_prog_layout_batch(const Job* __restrict__ jobs, const BatchOut* __restrict__ outs) {
+  __shared__ uint64_t s_part[4];
+  __shared__ uint64_t s_tot[kProgScans];
+  const Job& j = uniform_ref(jobs, blockIdx.x);
+  const BatchOut& o = uniform_ref(outs, blockIdx.x);
+  ProgMeta* m = prog_meta(j);
+  const uint32_t nsc = prog_nscans(j);
+  if (m->clen_overflow) {   // (uniform) no stream: the stuffing launches find nothing to do
+    if (threadIdx.x == 0u) { *j.total_bits = 0u; *o.out_size = kProgClenOverflow; }
+    return;
+  }
+  for (uint32_t s = 0; s < nsc; ++s) {
+    const uint32_t nw = (prog_positions(j, c_prog_scans[j.gray ? 1 : 0][s]) + 127u) / 128u;
+    uint64_t v = 0;
+    for (uint32_t g = threadIdx.x; g < nw; g += 256u) v += prog_wg_sums(j, 2, s)[g];
+    v = block_sum<256>(v, s_part);
+    if (threadIdx.x == 0u) s_tot[s] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0u) return;
+  uint64_t at = 0;
+  uint32_t nm = 0;
+  for (uint32_t s = 0; s < nsc; ++s) {
+    m->seg_start[s] = at;
+    for (uint32_t q = 0; q < m->nmark[s]; ++q) j.rst_mark[nm++] = (uint32_t)(at >> 3) + m->mark_rel[s][q];
+    m->data_start[s] = at + 8u * (uint64_t)m->hdr_bytes[s];
+    at = (m->data_start[s] + s_tot[s] + 7u) & ~7ull;
+  }
+  m->seg_start[nsc] = at;
+  *j.total_bits = at;
+}
+// the bit range of workgroup w.wg of scan w.s: its positions' bits, the scan's segments in front of the first workgroup's, the scan's
+// padding behind the last one's -- over a job's workgroups and scans exactly the stream
+__device__ __forceinline__ void prog_wg_range(const Job& j, const ProgWg& w, uint64_t* s_part, uint64_t* lo, uint64_t* hi) {
+  const ProgMeta* m = prog_meta(j);
+  const uint32_t* bits_wg = prog_wg_sums(j, 2, w.s);
+  uint64_t before = 0;
+  for (uint32_t g = threadIdx.x; g < w.wg; g += 128u) before += bits_wg[g];
+  before = block_sum<128>(before, s_part);
+  *lo = m->data_start[w.s] + before;
+  *hi = *lo + bits_wg[w.wg];
+}
+__global__ void __launch_bounds__(128) k_jpeg_prog_clear_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint64_t s_part[2];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  ProgWg w;
+  if (!prog_wg(j, first, false, &w)) return;
+  const ProgMeta* m = prog_meta(j);
+  if (m->clen_overflow) return;
+  uint64_t lo, hi;
+  prog_wg_range(j, w, s_part, &lo, &hi);
+  if (w.wg == 0u) lo = m->seg_start[w.s];
+  if (w.wg == (w.npos + 127u) / 128u - 1u) hi = m->seg_start[w.s + 1u];
+  const uint64_t w1 = (hi + 31u) >> 5;
+  for (uint64_t q = ((lo + 31u) >> 5) + threadIdx.x; q < w1; q += 128u) j.stream[q] = 0u;
+}
+__global__ void __launch_bounds__(128) k_jpeg_prog_emit_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  __shared__ uint64_t s_part[2];
+  __shared__ uint32_t s_coef[128 * kProgCoefRow];
+  uint32_t first, count;
+  const uint32_t k = job_of<128>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  ProgWg w;
+  if (!prog_wg(j, first, false, &w)) return;
+  const ProgMeta* m = prog_meta(j);
+  if (m->clen_overflow) return;
+  prog_load_huff(j, w.d);
+  uint64_t lo, hi;
+  prog_wg_range(j, w, s_part, &lo, &hi);
+  const uint64_t my_bits = w.p < w.npos ? j.pg_bits[(size_t)w.s * j.pg_stride + w.p] : 0u;
+  const uint64_t off = lo + block_exclusive_sum<128>(my_bits, s_part);
+  if (w.wg == 0u) {   // the scan's segments: whole bytes, OR-ed into the cleared words next to the neighbours' bits
+    const uint64_t b0 = m->seg_start[w.s] >> 3;
+    for (uint32_t q = threadIdx.x; q < m->hdr_bytes[w.s]; q += 128u) {
+      const uint64_t b = b0 + q;
+      atomicOr(&j.stream[b >> 2], (uint32_t)m->hdr[w.s][q] << (8u * (uint32_t)(b & 3u)));
+    }
+  }
+  if (w.p >= w.npos) return;
+  ProgEmitSink sk;
+  sk.es.words = j.stream;
+  sk.es.acc = 0;
+  sk.es.nacc = (int)(off & 31u);
+  sk.es.wi = (uint32_t)(off >> 5);
+  sk.es.first = true;
+  prog_position(j, w, s_coef, sk);
+  if (w.p == w.npos - 1u) {   // jcphuff.c finish_pass_phuff: flush_bits
+    const int pad = (int)((8u - (uint32_t)((off + my_bits) & 7u)) & 7u);
+    if (pad) sk.es.put((1u << pad) - 1u, pad);
+  }
+  sk.es.finish();
+}
+__global__ void __launch_bounds__(256) k_jpeg_prog_stuff_count_batch(const Job* __restrict__ jobs, const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<256>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  const uint64_t nbytes = (*j.total_bits + 7u) >> 3;
+  for (uint32_t wg = blockIdx.x - first; (uint64_t)wg * 256u * kChunk < nbytes; wg += count) {
+    stuff_count_wg<true>(j, j.total_bits, wg);
+    __syncthreads();
+  }
+}
+__global__ void __launch_bounds__(256) k_jpeg_prog_stuff_copy_batch(const Job* __restrict__ jobs, const BatchOut* __restrict__ outs,
+                                                                    const uint32_t* __restrict__ start, uint32_t n) {
+  uint32_t first, count;
+  const uint32_t k = job_of<256>(start, n, &first, &count);
+  const Job& j = uniform_ref(jobs, k);
+  const BatchOut& o = uniform_ref(outs, k);
+  const uint64_t header_len = *j.hdr_len, cap = header_len <= o.out_cap ? o.out_cap : 0u;
+  const uint64_t nbytes = (*j.total_bits + 7u) >> 3;
+  for (uint32_t wg = blockIdx.x - first; (uint64_t)wg * 256u * kChunk < nbytes; wg += count) {
+    stuff_copy_wg<true>(j, j.total_bits, o.out, cap, header_len, o.out_size, wg);
+    __syncthreads();   // (s_buf and s_len are the next piece's)
+  }
+}
+
 hipError_t optimal_table_async(const uint32_t* freq, uint8_t* bits, uint8_t* vals, int* nvals, hipStream_t s) {
   hipLaunchKernelGGL(k_jpeg_opt_table_one, dim3(1), dim3(64), 0, s, freq, bits, vals, nvals);
   return hipGetLastError();
@@ -1335,7 +1904,7 @@ uint32_t restart_mcus(uint32_t restart_interval, uint32_t restart_in_rows, uint3
   return (uint32_t)(v < 65535u ? v : 65535u);
 }
 
-size_t workspace_bytes(uint32_t nblk, Layout* l, uint32_t intervals) {
+size_t workspace_bytes(uint32_t nblk, Layout* l, uint32_t intervals, bool progressive) {
   auto up = [](size_t v) { return (v + 255) / 256 * 256; };
   size_t o = 0;
   l->coef = o; o += up((size_t)nblk * 128);
@@ -1344,6 +1913,11 @@ size_t workspace_bytes(uint32_t nblk, Layout* l, uint32_t intervals) {
   // worst case per block: 20 bits of DC + 63 x 26 bits of AC = 1658 bits
   // an interval's padding and marker: up to 7 + 16 bits, of which its blocks' slack of 6 bits each need not hold any
   l->stream_bytes = up((size_t)nblk * 208 + 64 + (size_t)intervals * 3);
+  // all scans of a progressive file: over its life a coefficient costs at most 26 bits where it is first coded and a correction bit in
+  // each of up to two refinements (one that a refinement codes: 17 and a bit), a block at most three ZRLs of 16 bits and one EOBn of
+  // 30 per AC scan -- four for luma -- and 28 bits of DC: 63 x 28 + 4 x 78 + 28 = 2104 bits, 263 bytes; the area takes 496 a block,
+  // and the scans' segments and padding behind that
+  if (progressive) l->stream_bytes = up((size_t)nblk * 496 + (size_t)kProgScans * (kProgHdrMax + 8) + 64);
   l->stream = o; o += l->stream_bytes;
   l->max_chunks = (uint32_t)(l->stream_bytes / kChunk);
   l->ff_count = o; o += up((size_t)l->max_chunks * 4);
@@ -1355,6 +1929,22 @@ size_t workspace_bytes(uint32_t nblk, Layout* l, uint32_t intervals) {
   if (intervals != 0) {   // (a job without intervals keeps its layout)
     l->rst_pfx = o; o += up((size_t)nblk * 4);
     l->rst_mark = o; o += up((size_t)intervals * 4);
+  }
+  l->pg_info = l->pg_left = l->pg_corr = l->pg_nzc = l->pg_fstart = l->pg_pend = l->pg_bits = l->pg_wg = l->pg_meta = o;
+  if (progressive) {   // (every other job keeps its layout)
+    const size_t rows = (size_t)kProgScans * ((size_t)nblk + 1), nwg = (size_t)(nblk + 127u) / 128u;
+    l->hist = o; o += up((size_t)kProgTables * 256 * 4);
+    l->huff = o; o += up((size_t)kProgTables * 256 * 4);
+    l->rst_mark = o; o += up((size_t)kProgScans * 3 * 4);
+    l->pg_left = o; o += up(rows * 8);
+    l->pg_corr = o; o += up(rows * 4);
+    l->pg_nzc = o; o += up(rows * 4);
+    l->pg_fstart = o; o += up(rows * 4);
+    l->pg_pend = o; o += up(rows * 4);
+    l->pg_bits = o; o += up(rows * 4);
+    l->pg_info = o; o += up(rows * 2);
+    l->pg_wg = o; o += up(3 * (size_t)kProgScans * nwg * 4);
+    l->pg_meta = o; o += up(sizeof(ProgMeta));
   }
   l->scan_tmp_bytes = 0;
   l->scan_tmp = o;
@@ -1388,7 +1978,7 @@ size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 }  // namespace
 
 size_t batch_desc_bytes(int n) {
-  return up256((size_t)n * sizeof(Job)) + up256((size_t)n * sizeof(BatchOut)) + 6 * up256(((size_t)n + 1) * 4);
+  return up256((size_t)n * sizeof(Job)) + up256((size_t)n * sizeof(BatchOut)) + 8 * up256(((size_t)n + 1) * 4);
 }
 
 hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_t* const* ws, const BatchOut* outs, uint8_t* host_desc,
@@ -1406,21 +1996,27 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
   // and behind those the jobs with restart intervals, whatever their tables, likewise
   uint32_t* rst_blk_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(opt_stuff_start) + up256(((size_t)n + 1) * 4));
   uint32_t* rst_stuff_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(rst_blk_start) + up256(((size_t)n + 1) * 4));
+  // and last the progressive jobs
+  uint32_t* prog_blk_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(rst_stuff_start) + up256(((size_t)n + 1) * 4));
+  uint32_t* prog_stuff_start = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(prog_blk_start) + up256(((size_t)n + 1) * 4));
   blk_start[0] = stuff_start[0] = opt_blk_start[0] = opt_stuff_start[0] = rst_blk_start[0] = rst_stuff_start[0] = 0;
-  int nd = 0, no = 0;
+  prog_blk_start[0] = prog_stuff_start[0] = 0;
+  int nd = 0, no = 0, nr = 0;
   for (int k = 0; k < n; ++k) {
-    if (jobs_in[k].rst_blocks != 0) continue;
+    if (jobs_in[k].progressive != 0) continue;
+    if (jobs_in[k].rst_blocks != 0) { ++nr; continue; }
     (jobs_in[k].optimize ? no : nd) += 1;
   }
   // which of the three FDCT kernels each group of jobs needs: [0] 4:2:0 and one plane, [1] RGBA pixels, [2] planes of another sampling
   bool any_def[3] = {false, false, false}, any_opt[3] = {false, false, false}, any_rst[3] = {false, false, false};
-  bool any_rst_opt = false;
-  for (int k = 0, at_d = 0, at_o = nd, at_r = nd + no; k < n; ++k) {
-    const bool rst = jobs_in[k].rst_blocks != 0, opt = !rst && jobs_in[k].optimize != 0;
+  bool any_rst_opt = false, any_prog[3] = {false, false, false}, any_prog_colour = false;
+  for (int k = 0, at_d = 0, at_o = nd, at_r = nd + no, at_p = nd + no + nr; k < n; ++k) {
+    const bool prog = jobs_in[k].progressive != 0, rst = !prog && jobs_in[k].rst_blocks != 0, opt = !prog && !rst && jobs_in[k].optimize != 0;
     const int kind = jobs_in[k].rgb ? 1 : jobs_in[k].sampled ? 2 : 0;   // (kind_of)
-    (rst ? any_rst : opt ? any_opt : any_def)[kind] = true;
+    (prog ? any_prog : rst ? any_rst : opt ? any_opt : any_def)[kind] = true;
     if (rst) any_rst_opt = any_rst_opt || jobs_in[k].optimize != 0;
-    const int at = rst ? at_r++ : opt ? at_o++ : at_d++;
+    if (prog) any_prog_colour = any_prog_colour || !jobs_in[k].gray;
+    const int at = prog ? at_p++ : rst ? at_r++ : opt ? at_o++ : at_d++;
     Job& j = jobs[at];
     j = jobs_in[k];
     uint8_t* w = ws[k];
@@ -1437,10 +2033,24 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
     j.hdr_len = reinterpret_cast<uint32_t*>(w + l[k].totals + 16);
     j.rst_pfx = reinterpret_cast<uint32_t*>(w + l[k].rst_pfx);
     j.rst_mark = reinterpret_cast<uint32_t*>(w + l[k].rst_mark);
+    if (prog) {
+      j.pg_stride = j.nblk + 1u;
+      j.pg_nwg = (j.nblk + 127u) / 128u;
+      j.rst_marks = j.gray ? 11u : 20u;   // the markers of the scans' DHT and SOS segments (k_jpeg_prog_tables_batch)
+      j.pg_info = reinterpret_cast<uint16_t*>(w + l[k].pg_info);
+      j.pg_left = reinterpret_cast<uint64_t*>(w + l[k].pg_left);
+      j.pg_corr = reinterpret_cast<uint32_t*>(w + l[k].pg_corr);
+      j.pg_nzc = reinterpret_cast<uint32_t*>(w + l[k].pg_nzc);
+      j.pg_fstart = reinterpret_cast<uint32_t*>(w + l[k].pg_fstart);
+      j.pg_pend = reinterpret_cast<uint32_t*>(w + l[k].pg_pend);
+      j.pg_bits = reinterpret_cast<uint32_t*>(w + l[k].pg_bits);
+      j.pg_wg = reinterpret_cast<uint32_t*>(w + l[k].pg_wg);
+      j.pg_meta = w + l[k].pg_meta;
+    }
     o[at] = outs[k];
     const uint32_t stuff_wgs = (j.max_chunks + 255u) / 256u;
-    uint32_t* bs = rst ? rst_blk_start + (at - nd - no) : opt ? opt_blk_start + (at - nd) : blk_start + at;
-    uint32_t* ss = rst ? rst_stuff_start + (at - nd - no) : opt ? opt_stuff_start + (at - nd) : stuff_start + at;
+    uint32_t* bs = prog ? prog_blk_start + (at - nd - no - nr) : rst ? rst_blk_start + (at - nd - no) : opt ? opt_blk_start + (at - nd) : blk_start + at;
+    uint32_t* ss = prog ? prog_stuff_start + (at - nd - no - nr) : rst ? rst_stuff_start + (at - nd - no) : opt ? opt_stuff_start + (at - nd) : stuff_start + at;
     bs[1] = bs[0] + (j.nblk + 127u) / 128u;
     ss[1] = ss[0] + (stuff_wgs < kStuffWgPerJob ? stuff_wgs : kStuffWgPerJob);
   }
@@ -1481,8 +2091,8 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
     hipLaunchKernelGGL(k_jpeg_stuff_count_multi, gc, bc, 0, s, oj, ostuff, nj);
     hipLaunchKernelGGL(k_jpeg_opt_stuff_copy_batch, gc, bc, 0, s, oj, oout, ostuff, nj);
   }
-  if (n > nd + no) {
-    const uint32_t nj = (uint32_t)(n - nd - no);
+  if (nr > 0) {
+    const uint32_t nj = (uint32_t)nr;
     const Job* rj = dj + nd + no;
     const BatchOut* rout = dout + nd + no;
     const uint32_t* rblk = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(rst_blk_start) - host_desc));
@@ -1501,6 +2111,30 @@ hipError_t encode_batch_async(int n, const Job* jobs_in, const Layout* l, uint8_
     hipLaunchKernelGGL(k_jpeg_rst_emit_batch, gb, bb, 0, s, rj, rblk, nj);
     hipLaunchKernelGGL(k_jpeg_rst_stuff_count_batch, gc, bc, 0, s, rj, rstuff, nj);
     hipLaunchKernelGGL(k_jpeg_rst_stuff_copy_batch, gc, bc, 0, s, rj, rout, rstuff, nj);
+  }
+  if (n > nd + no + nr) {
+    const uint32_t nj = (uint32_t)(n - nd - no - nr);
+    const Job* pj = dj + nd + no + nr;
+    const BatchOut* pout = dout + nd + no + nr;
+    const uint32_t* pblk = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(prog_blk_start) - host_desc));
+    const uint32_t* pstuff = reinterpret_cast<const uint32_t*>(dev_desc + (reinterpret_cast<uint8_t*>(prog_stuff_start) - host_desc));
+    const dim3 gb(prog_blk_start[nj]), gc(prog_stuff_start[nj]);
+    const dim3 gs(prog_blk_start[nj], any_prog_colour ? 10u : 6u);   // (workgroups of positions) x (scans)
+    hipLaunchKernelGGL(k_jpeg_prog_zero_batch, dim3(nj), bc, 0, s, pj);
+    if (any_prog[0]) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch, gb, bb, 0, s, pj, pblk, nj);
+    if (any_prog[1]) hipLaunchKernelGGL(k_jpeg_opt_fdct_batch_rgb, gb, bb, 0, s, pj, pblk, nj);
+    if (any_prog[2]) hipLaunchKernelGGL(k_jpeg_sampled_opt_fdct_batch, gb, bb, 0, s, pj, pblk, nj);
+    hipLaunchKernelGGL(k_jpeg_prog_info_batch, gs, bb, 0, s, pj, pblk, nj);
+    hipLaunchKernelGGL(k_jpeg_prog_prefix_batch, gs, bb, 0, s, pj, pblk, nj);
+    hipLaunchKernelGGL(k_jpeg_prog_walk_batch, gs, bb, 0, s, pj, pblk, nj);
+    hipLaunchKernelGGL(k_jpeg_prog_hist_batch, gs, bb, 0, s, pj, pblk, nj);
+    hipLaunchKernelGGL(k_jpeg_prog_tables_batch, dim3(nj), dim3(64 * kProgTables), 0, s, pj, pout);
+    hipLaunchKernelGGL(k_jpeg_prog_count_batch, gs, bb, 0, s, pj, pblk, nj);
+    hipLaunchKernelGGL(k_jpeg_prog_layout_batch, dim3(nj), bc, 0, s, pj, pout);
+    hipLaunchKernelGGL(k_jpeg_prog_clear_batch, gs, bb, 0, s, pj, pblk, nj);
+    hipLaunchKernelGGL(k_jpeg_prog_emit_batch, gs, bb, 0, s, pj, pblk, nj);
+    hipLaunchKernelGGL(k_jpeg_prog_stuff_count_batch, gc, bc, 0, s, pj, pstuff, nj);
+    hipLaunchKernelGGL(k_jpeg_prog_stuff_copy_batch, gc, bc, 0, s, pj, pout, pstuff, nj);
   }
   return hipGetLastError();
 }

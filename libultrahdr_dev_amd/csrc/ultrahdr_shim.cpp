@@ -363,17 +363,18 @@ int rgbmap_one(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, int hd
   const size_t exn = exif_len(exif);
   return uhdr_hip_jpegr_encode_rgbmap_batch(1, p010 ? p010 : &none, yuv, hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, UHDR_HIP_MEM_HOST, nullptr);
 }
-// one file through uhdr_hip_jpegr_encode_batch_opts (setOptimizeHuffman, setRestartInterval, setRestartInRows): API-1, or API-0 with
-// yuv == nullptr
+// one file through uhdr_hip_jpegr_encode_batch_scans (setOptimizeHuffman, setRestartInterval, setRestartInRows, setProgressive): API-1, or
+// API-0 with yuv == nullptr.  Not progressive, that is uhdr_hip_jpegr_encode_batch_opts
 int optimized_one(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, int hdr_tf, int quality, uhdr_exif_ptr exif, void* out, size_t cap, size_t* n,
-                  bool optimize, unsigned restart_interval, unsigned restart_in_rows) {
+                  bool optimize, unsigned restart_interval, unsigned restart_in_rows, bool progressive) {
   uhdr_hip_image_t none;
   std::memset(&none, 0, sizeof(none));
   const void* ex = exif_ptr(exif);
   const size_t exn = exif_len(exif);
   const uhdr_hip_jpeg_encode_opts_t opts = {(uint32_t)sizeof(uhdr_hip_jpeg_encode_opts_t), optimize ? (uint32_t)UHDR_HIP_ENCODE_OPTIMIZE_HUFFMAN : 0u,
                                             restart_interval, restart_in_rows};
-  return uhdr_hip_jpegr_encode_batch_opts(1, p010 ? p010 : &none, yuv, hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, &opts, UHDR_HIP_MEM_HOST, nullptr);
+  return uhdr_hip_jpegr_encode_batch_scans(1, p010 ? p010 : &none, yuv, hdr_tf, quality, &ex, &exn, &out, &cap, n, nullptr, &opts,
+                                           progressive ? UHDR_HIP_SCANS_PROGRESSIVE : UHDR_HIP_SCANS_BASELINE, UHDR_HIP_MEM_HOST, nullptr);
 }
 // one file through uhdr_hip_jpegr_encode_scaled_batch (setGainMapScaleFactor): API-1, or API-0 with yuv == nullptr
 int scaled_one(const uhdr_hip_image_t* p010, const uhdr_hip_image_t* yuv, int hdr_tf, int quality, uhdr_exif_ptr exif, void* out, size_t cap, size_t* n,
@@ -391,10 +392,11 @@ status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, ultrahdr_tr
                                uhdr_exif_ptr exif) {
   uhdr_hip_image_t p;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
-  if (mOptimizeHuffman || mRestartInterval != 0 || mRestartInRows != 0) {   // the plain API-0 alone has these options so far
+  if (mOptimizeHuffman || mRestartInterval != 0 || mRestartInRows != 0 || mProgressive) {   // the plain API-0 alone has these options so far
     if (mGainMapScaleFactor != 4 || mMultiChannelGainMap || mToneMapOp != UHDR_HIP_TONEMAP_SHIFT || mContentBoost >= 0) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;
     return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
-      return optimized_one(p010_image_ptr ? &p : nullptr, nullptr, (int)hdr_tf, quality, exif, out, cap, n, mOptimizeHuffman, mRestartInterval, mRestartInRows);
+      return optimized_one(p010_image_ptr ? &p : nullptr, nullptr, (int)hdr_tf, quality, exif, out, cap, n, mOptimizeHuffman, mRestartInterval, mRestartInRows,
+                           mProgressive);
     });
   }
   if (mGainMapScaleFactor != 4) {   // setGainMapScaleFactor: the operator and the adaptive range have no form at another factor
@@ -430,11 +432,12 @@ status_t JpegRHip::encodeJPEGR(uhdr_uncompressed_ptr p010_image_ptr, uhdr_uncomp
   uhdr_hip_image_t p, y;
   if (p010_image_ptr) p = to_c(*p010_image_ptr);
   if (yuv420_image_ptr) y = to_c(*yuv420_image_ptr);
-  if (mOptimizeHuffman || mRestartInterval != 0 || mRestartInRows != 0) {   // the plain API-1 alone has these options so far
+  if (mOptimizeHuffman || mRestartInterval != 0 || mRestartInRows != 0 || mProgressive) {   // the plain API-1 alone has these options so far
     if (mGainMapScaleFactor != 4 || mMultiChannelGainMap || mContentBoost >= 0) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;
     if (yuv420_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;   // jpegr.cpp:253-256 (a NULL array would mean API-0 to the batch)
     return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
-      return optimized_one(p010_image_ptr ? &p : nullptr, &y, (int)hdr_tf, quality, exif, out, cap, n, mOptimizeHuffman, mRestartInterval, mRestartInRows);
+      return optimized_one(p010_image_ptr ? &p : nullptr, &y, (int)hdr_tf, quality, exif, out, cap, n, mOptimizeHuffman, mRestartInterval, mRestartInRows,
+                           mProgressive);
     });
   }
   if (mGainMapScaleFactor != 4) {   // setGainMapScaleFactor
@@ -482,7 +485,7 @@ status_t JpegRHip::encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, uhdr_u
   if (mGainMapScaleFactor != 4) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;   // setGainMapScaleFactor: the packed calls write factor 4 only
   if (hdr_image_ptr == nullptr || sdr_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
   const uhdr_hip_image_t h = to_c_packed(*hdr_image_ptr), sd = to_c_packed(*sdr_image_ptr);
-  if (mPrimarySampling != UHDR_HIP_PIX_FMT_YUV420 && mContentBoost >= 0) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;   // setPrimarySampling
+  if (mPrimarySampling != UHDR_HIP_PIX_FMT_YUV420 && (mContentBoost >= 0 || mProgressive)) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;   // setPrimarySampling
   return encode_into(dest, [&](void* out, size_t cap, size_t* n) {
     const void* ex = exif_ptr(exif);
     const size_t exn = exif_len(exif);
@@ -506,7 +509,7 @@ status_t JpegRHip::encodeJPEGRPacked(uhdr_uncompressed_ptr hdr_image_ptr, ultrah
   if (hdr_image_ptr == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
   const uhdr_hip_image_t h = to_c_packed(*hdr_image_ptr);
   if (mPrimarySampling != UHDR_HIP_PIX_FMT_YUV420) {   // setPrimarySampling: the packed API-0's SDR image first, then the call with a pair
-    if (mContentBoost >= 0) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;
+    if (mContentBoost >= 0 || mProgressive) return ERROR_ULTRAHDR_UNSUPPORTED_FEATURE;   // (the packed calls have no progressive form)
     if (h.data == nullptr) return ERROR_ULTRAHDR_BAD_PTR;
     if (h.width == 0 || h.height == 0 || h.width > 8192 || h.height > 8192) return ERROR_ULTRAHDR_UNSUPPORTED_WIDTH_HEIGHT;
     if (uhdr_hip_init(0) != UHDR_HIP_NO_ERROR) return ERROR_ULTRAHDR_INSUFFICIENT_RESOURCE;
