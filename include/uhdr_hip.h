@@ -1265,6 +1265,13 @@ int uhdr_hip_apply_exact_probe(int phase, int n, const uhdr_hip_image_t* yuv420_
                                const uhdr_hip_metadata_t* metadata, int output_format, float max_display_boost,
                                uhdr_hip_image_t* dests, void* stream, uint32_t* route, uint32_t* headers);
 
+/* A test hook, host only.  The batched codec calls (JPEG and JPEG/R encode, decode and edit) take their files through the device in
+ * rounds whose workspace and staging are held to a byte bound, 2 GiB by default.  This call sets that bound for
+ * every later call of the process and returns the one it replaces; 0 restores the default.  The bound changes how many rounds a call
+ * takes, never a byte or a status of its result: a file larger than the bound gets a round of its own.  tests take a call across a
+ * round seam with it at sizes of a few kilobytes; nothing else has a reason to call it. */
+size_t uhdr_hip_codec_round_bytes_probe(size_t bytes);
+
 /* ---- Optimised Huffman tables for the JPEG encoder --------------------------------------------------------
  * libjpeg's optimize_coding: a file's four Huffman tables (two for a single plane) are built from the histogram of its own symbols
  * instead of being the Annex K defaults.  No pixel changes; the file is smaller and equals, byte for byte, what libjpeg-turbo

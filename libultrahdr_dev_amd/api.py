@@ -267,6 +267,10 @@ SCANS_BASELINE = 0
 SCANS_PROGRESSIVE = 1
 for _name in ("uhdr_hip_jpeg_encode_planes_batch", "uhdr_hip_jpeg_encode_rgba_batch", "uhdr_hip_jpegr_encode_batch"):
     SIGNATURES[_name + "_scans"] = (lambda res, args: (res, args[:-2] + [C.c_int] + args[-2:]))(*SIGNATURES[_name + "_opts"])
+# test hook: the byte bound of a codec round (returns the one it replaces; 0: the default).  An older build named by UHDR_HIP_LIB may
+# lack it: load() then leaves it out and hasattr(lib, ...) says so
+SIGNATURES["uhdr_hip_codec_round_bytes_probe"] = (C.c_size_t, [C.c_size_t])
+TEST_HOOKS = ("uhdr_hip_codec_round_bytes_probe",)
 
 _lib = None
 
@@ -289,6 +293,8 @@ def load():
             pass
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
+            if name in TEST_HOOKS and not hasattr(lib, name):
+                continue
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args

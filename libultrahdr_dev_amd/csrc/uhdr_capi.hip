@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <memory>
 #include <cmath>
 #include <cstdio>
@@ -971,16 +972,18 @@ int finish_statuses(const std::vector<int>& st_, int* status) {
 // UHDR_HIP_MEM_DEVICE_TO_HOST and UHDR_HIP_MEM_HOST_TO_DEVICE their split meaning)
 int single_mem_space(int mem_space) { return mem_space == UHDR_HIP_MEM_DEVICE ? UHDR_HIP_MEM_DEVICE : UHDR_HIP_MEM_HOST; }
 
-// A round's device workspace and page-locked staging are held to kCodecRoundBytes (a file larger than that gets a round of its own)
+// A round's device workspace and page-locked staging are held to kCodecRoundBytes (a file larger than that gets a round of its own).
+// g_round_bytes is the bound run_rounds reads: kCodecRoundBytes unless a test has moved it (uhdr_hip_codec_round_bytes_probe)
 constexpr size_t kCodecRoundBytes = size_t(2) << 30;
+std::atomic<size_t> g_round_bytes{kCodecRoundBytes};
 
 // The device part of a batched codec call over its `live` files, in their order: a context of the call's own (CodecLease), then greedy
-// rounds of at most `cap` files and kCodecRoundBytes -- bytes_of(k) is what file k holds of its round, the first file of a round is
+// rounds of at most `cap` files and g_round_bytes -- bytes_of(k) is what file k holds of its round, the first file of a round is
 // always admitted --, each through run(ctx, s, first, m).  The first non-zero round status ends the call behind a stream
 // synchronisation, so that nothing of the failed round is still writing into the pools, and is returned; files [0, *done) are
 // finished, the others (the failed round's and those behind it) are the caller's to mark.  A round that returns 0 must leave the
-// stream idle -- every round here ends in compress_to_host's or jpeg_decode_round's synchronisation --, since the lease, and with it
-// the pools the round's kernels and copies use, is released without another one.
+// stream idle -- every round here ends in compress_to_host's, jpeg_decode_round's or jpegr_decode_round's synchronisation --, since the
+// lease, and with it the pools the round's kernels and copies use, is released without another one.
 template <class B, class R>
 int run_rounds(size_t live, size_t cap, void* stream, B bytes_of, R run, size_t* done) {
   *done = 0;
@@ -990,11 +993,12 @@ int run_rounds(size_t live, size_t cap, void* stream, B bytes_of, R run, size_t*
   CodecLease lease(st);
   if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
   hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t bound = g_round_bytes.load();
   while (rc == UHDR_HIP_NO_ERROR && *done < live) {
     size_t r1 = *done, bytes = 0;
     while (r1 < live && r1 - *done < cap) {
       const size_t b = bytes_of(r1);
-      if (r1 > *done && bytes + b > kCodecRoundBytes) break;
+      if (r1 > *done && bytes + b > bound) break;
       bytes += b;
       ++r1;
     }
@@ -1106,6 +1110,9 @@ int generate_through_stage(StageSet* ss, const uhdr_hip_image_t* yuv, const uhdr
 extern "C" {
 
 int uhdr_hip_abi_version(void) { return UHDR_HIP_ABI_VERSION; }
+
+// host only, a test hook: the byte bound of every later codec round of the process (0: kCodecRoundBytes); returns the one it replaces
+size_t uhdr_hip_codec_round_bytes_probe(size_t bytes) { return g_round_bytes.exchange(bytes != 0 ? bytes : kCodecRoundBytes); }
 
 int uhdr_hip_device_count(void) {
   int n = 0;
@@ -2505,6 +2512,22 @@ DecGeom dec_geom(const jpeg::DecInfo& info) {
   const size_t cw = (w + sg.hs - 1) / sg.hs, ch = (h + sg.vs - 1) / sg.vs;
   return DecGeom{w, h, sg.hs, sg.vs, cw, ch, cw * ch, sg.hs == 2 ? UHDR_HIP_PIX_FMT_YUV422 : sg.vs == 2 ? UHDR_HIP_PIX_FMT_YUV440 : UHDR_HIP_PIX_FMT_YUV444};
 }
+// libjpeg-turbo's RGBA of an odd-sized 4:2:0 image is outside the conversion kernels (uhdr_hip_jpeg_decode_rgba: UNSUPPORTED_FEATURE)
+bool rgba_refuses(const DecGeom& g) { return g.fmt == UHDR_HIP_PIX_FMT_YUV420 && ((g.w | g.h) & 1) != 0; }
+// a decoded image at p as the apply calls read it: its planes in `fmt` = g.fmt, its first plane alone (MONOCHROME), or the RGBA made of it
+uhdr_hip_image_t dec_image(const DecGeom& g, void* p, int fmt, int gamut) {
+  uhdr_hip_image_t im;
+  memset(&im, 0, sizeof(im));
+  im.data = p; im.width = g.w; im.height = g.h; im.luma_stride = g.w; im.colorGamut = gamut; im.pixelFormat = fmt;
+  if (fmt != UHDR_HIP_PIX_FMT_MONOCHROME && fmt != UHDR_HIP_PIX_FMT_RGBA8888) { im.chroma_data = static_cast<uint8_t*>(p) + g.w * g.h; im.chroma_stride = g.cw; }
+  return im;
+}
+// the gates every decode call shares, in this order: the denominator (1 where the call has none), then the flags
+int decode_gate(int flags, int scale_denom) {
+  if (scale_denom != 1 && scale_denom != 2 && scale_denom != 4 && scale_denom != 8) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  return (flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0 ? UHDR_HIP_ERROR_UNSUPPORTED_FEATURE : UHDR_HIP_NO_ERROR;
+}
+int decode_to_gate(int to) { return to != UHDR_HIP_DECODE_TO_RGBA && to != UHDR_HIP_DECODE_TO_YCBCR ? UHDR_HIP_ERROR_UNSUPPORTED_FEATURE : UHDR_HIP_NO_ERROR; }
 // the three planes of a decode into the packed buffer at p
 void dec_planes(const jpeg::DecInfo& info, uint8_t* p, jpeg::DecPlane out[3]);
 // an image's entry in either RGBA conversion batch (4:2:0: k_ycc420_rgba_batch, the other samplings: k_yccx_rgba_batch)
@@ -2562,14 +2585,15 @@ int jpeg_decode_host(const void* jpeg, size_t jpeg_size, bool rgba, bool any_sam
   desc->data = out; desc->width = w; desc->height = h; desc->colorGamut = UHDR_HIP_CG_UNSPECIFIED; desc->luma_stride = w;
   desc->pixelFormat = UHDR_HIP_PIX_FMT_UNSPECIFIED;
   if (out == nullptr || out_capacity < *need) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  if (g.fmt == UHDR_HIP_PIX_FMT_YUV420 && ((w | h) & 1)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (rgba_refuses(g)) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   return UHDR_HIP_NO_ERROR;
 }
 
-// the decode batch's pool slots: decoder workspaces, YCbCr planes (of an RGBA decode or a host caller), RGBA staging of a host
-// caller, jpeg::decode_device_batch's scratch
-enum : size_t { kDecWs = 0, kDecPlanes, kDecRgba, kDecScratch };
-constexpr int kDecRound = kRgbaChunk;   // files per decode round: their RGBA conversion is one launch
+// The decode paths' pool slots: decode_images' workspaces, pooled planes and scratch; the JPEG batch's RGBA staging of a host caller; the
+// JPEG/R round's three-component maps as RGBA and a host caller's renditions, in slots no other codec path names (the encode paths hold
+// 0-6 and 8-10).  The uhdr_hip_apply_gainmap* calls nested in that round touch no slot: they work in the device's own state, not the lease's.
+enum : size_t { kDecWs = 0, kDecPlanes, kDecRgba, kDecScratch, kJrMapRgba = 11, kJrOut = 12 };
+constexpr int kDecRound = kRgbaChunk;   // files per JPEG decode round: their RGBA conversion is one launch
 
 // a packed w x h plane at p for the decoder to write
 jpeg::DecPlane dec_plane(uint8_t* p, size_t w, size_t h) {
@@ -2595,51 +2619,67 @@ size_t dec_round_bytes(const jpeg::DecInfo& info, bool rgba, bool host_out, size
   return b;
 }
 
-// One round of uhdr_hip_jpeg_decode_batch: files idx[0, m) (m <= kDecRound) through one jpeg::decode_device_batch, their RGBA
-// conversion through one k_ycc420_rgba_batch launch, then one synchronisation.  A file whose device decode fails gets UNKNOWN_ERROR
-// in st_; a non-zero return is an error of the device or the runtime.
-int jpeg_decode_round(DeviceState* st, hipStream_t s, bool rgba, bool host_out, const void* const* jpeg, void* const* out,
-                      const jpeg::DecInfo* info, const size_t* need, const int* idx, int m, int* st_) {
-  std::vector<jpeg::DecLayout> lay((size_t)m);
-  std::vector<size_t> ws_off((size_t)m), pl_off((size_t)m), rg_off((size_t)m);
-  size_t ws_total = 0, pl_total = 0, rg_total = 0;
-  for (int k = 0; k < m; ++k) {
-    const int i = idx[k];
-    ws_off[k] = ws_total;
-    ws_total += round_up(jpeg::dec_workspace_bytes(info[i], &lay[k]), 256);
-    pl_off[k] = pl_total;
-    if (rgba || host_out) pl_total += round_up(dec_ycc_bytes(info[i]) + 64, 256);
-    rg_off[k] = rg_total;
-    if (rgba && host_out) rg_total += round_up(need[i], 256);
+// one image of a device decode: its header, its entropy-coded segment on the host, where its planes go (nullptr: a slice of kDecPlanes)
+struct DecImage { const jpeg::DecInfo* info; const uint8_t* scan; uint8_t* out; };
+
+// The decode every round shares, enqueued on s: workspaces as 256-aligned slices of kDecWs, pooled planes as slices of kDecPlanes,
+// kDecScratch, the segments copied up, one jpeg::decode_device_batch for all.  ycc[k]: image k's planes (dec_planes' layout); image_rc[k]
+// != 0: corrupt entropy-coded data.  A non-zero return is an error of the device or the runtime (`who` names the call in its message).
+int decode_images(DeviceState* st, hipStream_t s, const char* who, const std::vector<DecImage>& im, std::vector<uint8_t*>* ycc,
+                  std::vector<int>* image_rc) {
+  const size_t m = im.size();
+  std::vector<jpeg::DecLayout> lay(m);
+  std::vector<size_t> ws_off(m), pl_off(m);
+  size_t ws_total = 0, pl_total = 0;
+  for (size_t k = 0; k < m; ++k) {
+    ws_off[k] = ws_total; pl_off[k] = pl_total;
+    ws_total += round_up(jpeg::dec_workspace_bytes(*im[k].info, &lay[k]), 256);
+    if (im[k].out == nullptr) pl_total += round_up(dec_ycc_bytes(*im[k].info) + 64, 256);
   }
   int rc;
   if ((rc = pool_reserve(st, kDecWs, ws_total)) != 0) return rc;
   if ((rc = pool_reserve(st, kDecPlanes, pl_total)) != 0) return rc;
-  if ((rc = pool_reserve(st, kDecRgba, rg_total)) != 0) return rc;
-  if ((rc = pool_reserve(st, kDecScratch, jpeg::dec_batch_scratch_bytes(m, lay.data()))) != 0) return rc;
-  std::vector<const jpeg::DecInfo*> infos((size_t)m);
-  std::vector<uint8_t*> wss((size_t)m);
-  std::vector<jpeg::DecPlane> planes(3 * (size_t)m);
-  std::vector<jpeg::DecPlane (*)[3]> pl((size_t)m);
-  std::vector<uint8_t*> ycc((size_t)m);
-  for (int k = 0; k < m; ++k) {
-    const int i = idx[k];
-    const jpeg::DecInfo& in = info[i];
+  if ((rc = pool_reserve(st, kDecScratch, jpeg::dec_batch_scratch_bytes((int)m, lay.data()))) != 0) return rc;
+  std::vector<const jpeg::DecInfo*> infos(m);
+  std::vector<uint8_t*> wss(m);
+  std::vector<jpeg::DecPlane> planes(3 * m);
+  std::vector<jpeg::DecPlane (*)[3]> pl(m);
+  ycc->assign(m, nullptr); image_rc->assign(m, 0);
+  for (size_t k = 0; k < m; ++k) {
+    const jpeg::DecInfo& in = *im[k].info;
     infos[k] = &in;
     wss[k] = static_cast<uint8_t*>(st->pool[kDecWs]) + ws_off[k];
-    if (in.scan_bytes)
-      HIP_TRY(hipMemcpyAsync(wss[k] + lay[k].src, static_cast<const uint8_t*>(jpeg[i]) + in.scan_offset, in.scan_bytes, hipMemcpyHostToDevice, s));
-    // YCbCr to a device caller: straight into its buffer
-    ycc[k] = rgba || host_out ? static_cast<uint8_t*>(st->pool[kDecPlanes]) + pl_off[k] : static_cast<uint8_t*>(out[i]);
-    jpeg::DecPlane* p = &planes[3 * (size_t)k];
-    dec_planes(in, ycc[k], p);
-    pl[k] = reinterpret_cast<jpeg::DecPlane (*)[3]>(p);
+    if (in.scan_bytes) HIP_TRY(hipMemcpyAsync(wss[k] + lay[k].src, im[k].scan, in.scan_bytes, hipMemcpyHostToDevice, s));
+    (*ycc)[k] = im[k].out != nullptr ? im[k].out : static_cast<uint8_t*>(st->pool[kDecPlanes]) + pl_off[k];
+    dec_planes(in, (*ycc)[k], &planes[3 * k]);
+    pl[k] = reinterpret_cast<jpeg::DecPlane (*)[3]>(&planes[3 * k]);
   }
-  std::vector<int> image_rc((size_t)m, 0);
   hipError_t herr = hipSuccess;
-  const int drc = jpeg::decode_device_batch(m, infos.data(), lay.data(), wss.data(), pl.data(), s, static_cast<uint8_t*>(st->pool[kDecScratch]), &herr,
-                                            image_rc.data());
-  if (drc > 0) { set_err("uhdr_hip_jpeg_decode", herr); return UHDR_HIP_UNKNOWN_ERROR; }
+  const int drc = jpeg::decode_device_batch((int)m, infos.data(), lay.data(), wss.data(), pl.data(), s, static_cast<uint8_t*>(st->pool[kDecScratch]), &herr,
+                                            image_rc->data());
+  if (drc > 0) { set_err(who, herr); return UHDR_HIP_UNKNOWN_ERROR; }
+  return UHDR_HIP_NO_ERROR;
+}
+
+// One round of uhdr_hip_jpeg_decode_batch: files idx[0, m) (m <= kDecRound) through decode_images, their RGBA conversion through one
+// k_ycc420_rgba_batch launch, then one synchronisation.  A file whose device decode fails gets UNKNOWN_ERROR in st_; a non-zero return
+// is an error of the device or the runtime.
+int jpeg_decode_round(DeviceState* st, hipStream_t s, bool rgba, bool host_out, const void* const* jpeg, void* const* out,
+                      const jpeg::DecInfo* info, const size_t* need, const int* idx, int m, int* st_) {
+  std::vector<DecImage> im((size_t)m);
+  std::vector<size_t> rg_off((size_t)m);
+  size_t rg_total = 0;
+  for (int k = 0; k < m; ++k) {
+    const int i = idx[k];
+    // YCbCr to a device caller: straight into its buffer
+    im[k] = DecImage{&info[i], static_cast<const uint8_t*>(jpeg[i]) + info[i].scan_offset, rgba || host_out ? nullptr : static_cast<uint8_t*>(out[i])};
+    rg_off[k] = rg_total;
+    if (rgba && host_out) rg_total += round_up(need[i], 256);
+  }
+  int rc;
+  if ((rc = pool_reserve(st, kDecRgba, rg_total)) != 0) return rc;
+  std::vector<uint8_t*> ycc; std::vector<int> image_rc;
+  if ((rc = decode_images(st, s, "uhdr_hip_jpeg_decode", im, &ycc, &image_rc)) != 0) return rc;
   RgbaBatches b;
   std::vector<uint8_t*> res((size_t)m, nullptr);   // where each good file's output lies on the device
   for (int k = 0; k < m; ++k) {
@@ -2659,6 +2699,154 @@ int jpeg_decode_round(DeviceState* st, hipStream_t s, bool rgba, bool host_out, 
       if (res[k] != nullptr) HIP_TRY(hipMemcpyAsync(out[idx[k]], res[k], need[idx[k]], hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   return UHDR_HIP_NO_ERROR;
+}
+
+// ---- decodeJPEGR for n files (the uhdr_hip_jpegr_decode* calls) --------------------------------------------------------------------
+// The caller's arguments, and what the entry points differ in.  rgb_maps: a three-component map, of any sampling the RGBA conversion handles,
+// is applied per channel through its RGBA.  any_md: metadata that validate_apply refuses goes through uhdr_hip_apply_gainmap_md_batch.
+struct JrBatch {
+  int n; const void* const* jpegr; const size_t* jpegr_size; int output_format; float max_display_boost; void* const* dest_data;
+  const size_t* dest_capacity; uhdr_hip_image_t* dests; uhdr_hip_metadata_t* metadata; int* status; int apply_mode, mem_space; void* stream; int flags;
+};
+struct JrOpt { bool rgb_maps = false, any_md = false; int scale_denom = 1; };
+// whether a file's three-component map goes through its RGBA, that RGBA's bytes, and what the file holds of its round: workspaces and
+// planes (SDR: of the primary image alone), the RGBA, a host caller's rendition
+bool jr_rgb_map(const JrBatch& a, const JrOpt& o, const JpegrFile& f) { return o.rgb_maps && a.output_format != UHDR_HIP_OUTPUT_SDR && !f.info[1].gray; }
+size_t jr_map_rgba_bytes(const JpegrFile& f) { const DecGeom g = dec_geom(f.info[1]); return g.w * g.h * 4; }
+size_t jr_round_bytes(const JrBatch& a, const JrOpt& o, const JpegrFile& f, size_t out_bytes) {
+  return dec_round_bytes(f.info[0], false, true, 0) + (a.output_format != UHDR_HIP_OUTPUT_SDR ? dec_round_bytes(f.info[1], false, true, 0) : 0) +
+         (jr_rgb_map(a, o, f) ? jr_map_rgba_bytes(f) : 0) + (a.mem_space != UHDR_HIP_MEM_DEVICE ? out_bytes : 0);
+}
+
+// One round of JPEG/R files idx[0, m): both images of every file through decode_images, one apply call per HDR file in the caller's order,
+// one synchronisation; every per-file buffer a 256-aligned slice of a slot.  Statuses go to st_; non-zero: an error of the device or the runtime.
+int jpegr_decode_round(DeviceState* st, hipStream_t s, const JrBatch& a, const JrOpt& o, const JpegrFile* files, const size_t* out_bytes,
+                       const int* idx, int m, int* st_) {
+  const bool sdr = a.output_format == UHDR_HIP_OUTPUT_SDR, host = a.mem_space != UHDR_HIP_MEM_DEVICE;
+  const size_t per_file = sdr ? 1 : 2;   // the SDR rendition is the primary image alone (:768-786)
+  std::vector<DecImage> im;
+  std::vector<size_t> map_off((size_t)m), out_off((size_t)m);
+  size_t map_total = 0, out_total = 0;
+  for (int k = 0; k < m; ++k) {
+    const JpegrFile& f = files[idx[k]];
+    for (size_t j = 0; j < per_file; ++j) im.push_back(DecImage{&f.info[j], f.jpg[j] + f.info[j].scan_offset, nullptr});
+    map_off[k] = map_total; out_off[k] = out_total;
+    if (jr_rgb_map(a, o, f)) map_total += round_up(jr_map_rgba_bytes(f), 256);
+    if (host) out_total += round_up(out_bytes[idx[k]], 256);
+  }
+  int rc;
+  if (map_total && (rc = pool_reserve(st, kJrMapRgba, map_total)) != 0) return rc;
+  if (out_total && (rc = pool_reserve(st, kJrOut, out_total)) != 0) return rc;
+  std::vector<uint8_t*> ycc; std::vector<int> image_rc;
+  if ((rc = decode_images(st, s, "uhdr_hip_jpegr_decode", im, &ycc, &image_rc)) != 0) return rc;
+  for (size_t g = 0; g < im.size(); ++g)
+    if (image_rc[g] != 0) st_[idx[g / per_file]] = UHDR_HIP_ERROR_DECODE_ERROR;
+  // three-component maps: an odd-sized 4:2:0 map is refused as uhdr_hip_jpeg_decode_rgba refuses the file (full size only: a scaled map is never 4:2:0)
+  RgbaBatches mb;
+  for (int k = 0; k < m; ++k) {
+    const JpegrFile& f = files[idx[k]];
+    if (st_[idx[k]] != UHDR_HIP_NO_ERROR || !jr_rgb_map(a, o, f)) continue;
+    if (rgba_refuses(dec_geom(f.info[1]))) { st_[idx[k]] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }
+    mb.add(f.info[1], ycc[2 * (size_t)k + 1], static_cast<uint8_t*>(st->pool[kJrMapRgba]) + map_off[k]);
+    if (mb.size() == kRgbaChunk) HIP_TRY(mb.launch(s));
+  }
+  HIP_TRY(mb.launch(s));
+  // the renditions.  SDR: libjpeg-turbo's DECODE_TO_RGBA on the planes just decoded (k_ycc420_rgba_batch / k_yccx_rgba_batch), up to
+  // kRgbaChunk files per launch.  HDR, :796-801: the planes as an image with the ICC gamut under the first plane of the map's JPEG, or its RGBA
+  RgbaBatches rgb;
+  for (int k = 0; k < m; ++k) {
+    const int i = idx[k];
+    if (st_[i] != UHDR_HIP_NO_ERROR) continue;
+    const JpegrFile& f = files[i];
+    const DecGeom pg = dec_geom(f.info[0]);
+    uint8_t* yp = ycc[per_file * (size_t)k];
+    uint8_t* out = host ? static_cast<uint8_t*>(st->pool[kJrOut]) + out_off[k] : static_cast<uint8_t*>(a.dest_data[i]);
+    if (sdr) {
+      if (rgba_refuses(pg)) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }
+      rgb.add(f.info[0], yp, out);
+      if (rgb.size() == kRgbaChunk) HIP_TRY(rgb.launch(s));
+    } else {
+      const bool rgb_map = jr_rgb_map(a, o, f);
+      uint8_t* mp = rgb_map ? static_cast<uint8_t*>(st->pool[kJrMapRgba]) + map_off[k] : ycc[2 * (size_t)k + 1];
+      const uhdr_hip_image_t ydesc = dec_image(pg, yp, pg.fmt, f.gamut);
+      const uhdr_hip_image_t gimg = dec_image(dec_geom(f.info[1]), mp, rgb_map ? UHDR_HIP_PIX_FMT_RGBA8888 : UHDR_HIP_PIX_FMT_MONOCHROME, UHDR_HIP_CG_UNSPECIFIED);
+      uhdr_hip_image_t ddev = a.dests[i];
+      ddev.data = out;
+      if (o.any_md && !md_degenerate(f.md))   // (degenerate metadata: the path and the bytes of the rgbmap decode)
+        st_[i] = uhdr_hip_apply_gainmap_md_batch(1, &ydesc, &gimg, &f.md, a.output_format, a.max_display_boost, &ddev, a.apply_mode, a.stream);
+      else if (rgb_map)
+        st_[i] = uhdr_hip_apply_gainmap_rgb_batch(1, &ydesc, &gimg, &f.md, a.output_format, a.max_display_boost, &ddev, a.apply_mode, a.stream);
+      else
+        st_[i] = uhdr_hip_apply_gainmap(&ydesc, &gimg, &f.md, a.output_format, a.max_display_boost, &ddev, a.apply_mode, UHDR_HIP_MEM_DEVICE, a.stream);
+      if (st_[i] != UHDR_HIP_NO_ERROR) continue;
+      a.dests[i].width = ddev.width; a.dests[i].height = ddev.height;
+    }
+    a.dests[i].data = a.dest_data[i];
+  }
+  HIP_TRY(rgb.launch(s));
+  for (int k = 0; host && k < m; ++k)   // a host caller's renditions go down behind the last launch
+    if (st_[idx[k]] == UHDR_HIP_NO_ERROR)
+      HIP_TRY(hipMemcpyAsync(a.dest_data[idx[k]], static_cast<uint8_t*>(st->pool[kJrOut]) + out_off[k], out_bytes[idx[k]], hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return UHDR_HIP_NO_ERROR;
+}
+
+// JpegR::decodeJPEGR (jpegr.cpp:655-822) for n files: checks and parsing on the host, then the live files through jpegr_decode_round in
+// rounds held to the byte bound alone -- a device decode is latency-bound, so every image of a call that fits shares each launch.  A
+// round that fails on the device ends the call with its status; status[] holds the other files' own and it for its files and those behind.
+int jpegr_decode_files(const JrBatch& a, const JrOpt& o) {
+  const int n = a.n;
+  int rc = decode_gate(a.flags, o.scale_denom);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
+  const bool any_sampling = (a.flags & UHDR_HIP_DECODE_ANY_SAMPLING) != 0;
+  if (n < 0 || (n > 0 && (a.jpegr == nullptr || a.jpegr_size == nullptr || a.dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
+  if (a.max_display_boost < 1.0f || (o.any_md && std::isnan(a.max_display_boost))) return UHDR_HIP_ERROR_INVALID_DISPLAY_BOOST;   // :666-669
+  if (a.output_format < UHDR_HIP_OUTPUT_SDR || a.output_format > UHDR_HIP_OUTPUT_HDR_LINEAR_RGB_10BIT) return UHDR_HIP_ERROR_INVALID_OUTPUT_FORMAT;
+  std::vector<JpegrFile> files((size_t)n);
+  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
+  std::vector<size_t> out_bytes((size_t)n, 0);
+  // walking a 2 MB file's markers costs ~0.2 ms of host time and touches nothing shared: a few threads parse the files side by side
+  on_host_threads(n, [&](int lo, int hi) {
+    for (int i = lo; i < hi; ++i)
+      st_[i] = a.jpegr[i] == nullptr ? UHDR_HIP_ERROR_BAD_PTR
+                                     : parse_jpegr_file(a.jpegr[i], a.jpegr_size[i], a.output_format, a.metadata != nullptr, &files[i], any_sampling, any_sampling || o.rgb_maps);
+  });
+  std::vector<int> live;
+  for (int i = 0; i < n; ++i) {
+    if (st_[i] != UHDR_HIP_NO_ERROR) continue;
+    if (a.metadata != nullptr) a.metadata[i] = files[i].md;
+    if (o.scale_denom != 1) {
+      // the map's denominator.  With f = W / MW (W = f MW, H = f MH): f % s == 0 leaves the map whole, ceil(W / s) = (f / s) MW; s % f == 0
+      // takes it to 1 / (s / f), ceil(W / s) = ceil(MW / (s / f)): an exact ratio either way
+      jpeg::DecInfo& pi = files[i].info[0];
+      jpeg::DecInfo& gi = files[i].info[1];
+      pi.scale = o.scale_denom;
+      if (a.output_format != UHDR_HIP_OUTPUT_SDR) {
+        const int f = gi.w > 0 && gi.h > 0 && pi.w % gi.w == 0 && pi.h % gi.h == 0 && (size_t)pi.w * (size_t)gi.h == (size_t)pi.h * (size_t)gi.w ? pi.w / gi.w : 0;
+        if (f != 0 && f % o.scale_denom == 0) gi.scale = 1;
+        else if (f != 0 && o.scale_denom % f == 0) gi.scale = o.scale_denom / f;
+        else {   // the map cannot follow its primary image: known from the two headers, so the file stops here, in front of its size probe
+          // (the apply call's metadata checks stand in front of its scale-factor checks)
+          const int mrc = validate_md(&files[i].md);
+          st_[i] = mrc != UHDR_HIP_NO_ERROR ? mrc : UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
+          continue;
+        }
+      }
+    }
+    const DecGeom og = dec_geom(files[i].info[0]);
+    a.dests[i].width = og.w; a.dests[i].height = og.h; a.dests[i].colorGamut = files[i].gamut;
+    out_bytes[i] = og.w * og.h * apply_bpp(a.output_format);
+    if (a.dest_data == nullptr || a.dest_capacity == nullptr || a.dest_data[i] == nullptr || a.dest_capacity[i] < out_bytes[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
+    live.push_back(i);
+  }
+  if (live.empty()) return finish_statuses(st_, a.status);   // every file stopped at its checks or its size probe: the device is not touched
+  size_t done = 0;
+  rc = run_rounds(
+      live.size(), live.size(), a.stream, [&](size_t k) { return jr_round_bytes(a, o, files[live[k]], out_bytes[live[k]]); },
+      [&](DeviceState* st, hipStream_t s, size_t r0, int m) { return jpegr_decode_round(st, s, a, o, files.data(), out_bytes.data(), &live[r0], m, st_.data()); }, &done);
+  for (size_t k = done; k < live.size(); ++k) st_[live[k]] = rc;   // the files of a failed round and of those behind it
+  const int first = finish_statuses(st_, a.status);
+  return rc != UHDR_HIP_NO_ERROR ? rc : first;
 }
 
 }  // namespace
@@ -2683,11 +2871,11 @@ int uhdr_hip_jpeg_decode_batch_ex(int n, const void* const* jpeg, const size_t* 
 int uhdr_hip_jpeg_decode_batch_scaled(int n, const void* const* jpeg, const size_t* jpeg_size, int decode_to, void* const* out,
                                       const size_t* out_capacity, uhdr_hip_image_t* descs, int* status, int mem_space, void* stream, int flags,
                                       int scale_denom) {
-  if (scale_denom != 1 && scale_denom != 2 && scale_denom != 4 && scale_denom != 8) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  int rc = decode_gate(flags, scale_denom);
+  if (rc != UHDR_HIP_NO_ERROR) return rc;
   const bool any_sampling = (flags & UHDR_HIP_DECODE_ANY_SAMPLING) != 0;
   if (n < 0 || (n > 0 && (jpeg == nullptr || jpeg_size == nullptr || descs == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
-  if (decode_to != UHDR_HIP_DECODE_TO_RGBA && decode_to != UHDR_HIP_DECODE_TO_YCBCR) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if ((rc = decode_to_gate(decode_to)) != UHDR_HIP_NO_ERROR) return rc;
   const bool rgba = decode_to == UHDR_HIP_DECODE_TO_RGBA;
   std::vector<jpeg::DecInfo> info((size_t)n);
   std::vector<size_t> need((size_t)n, 0);
@@ -2709,7 +2897,7 @@ int uhdr_hip_jpeg_decode_batch_scaled(int n, const void* const* jpeg, const size
   if (live.empty()) return finish_statuses(st_, status);   // every file stopped at its checks or its size probe: the device is not touched
   const bool host_out = mem_space != UHDR_HIP_MEM_DEVICE;
   size_t done = 0;
-  const int rc = run_rounds(
+  rc = run_rounds(
       live.size(), (size_t)kDecRound, stream, [&](size_t k) { return dec_round_bytes(info[live[k]], rgba, host_out, need[live[k]]); },
       [&](DeviceState* st, hipStream_t s, size_t r0, int m) {
         return jpeg_decode_round(st, s, rgba, host_out, jpeg, out, info.data(), need.data(), &live[r0], m, st_.data());
@@ -2744,15 +2932,14 @@ int uhdr_hip_jpeg_decode_last_sync_launches(int* ring_looks, int* first_launches
 // either single decode with flags (decode_to: UHDR_HIP_DECODE_TO_YCBCR / _RGBA): a batch of one file
 int uhdr_hip_jpeg_decode_ex(const void* jpeg, size_t jpeg_size, int decode_to, void* out, size_t out_capacity, uhdr_hip_image_t* desc, int mem_space,
                             void* stream, int flags) {
-  if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (decode_gate(flags, 1) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (jpeg == nullptr || desc == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
   return uhdr_hip_jpeg_decode_batch_ex(1, &jpeg, &jpeg_size, decode_to, &out, &out_capacity, desc, nullptr, single_mem_space(mem_space), stream, flags);
 }
 
 int uhdr_hip_jpeg_decode_scaled(const void* jpeg, size_t jpeg_size, int decode_to, void* out, size_t out_capacity, uhdr_hip_image_t* desc, int mem_space,
                                 void* stream, int flags, int scale_denom) {
-  if (scale_denom != 1 && scale_denom != 2 && scale_denom != 4 && scale_denom != 8) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (decode_gate(flags, scale_denom) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (jpeg == nullptr || desc == nullptr) return UHDR_HIP_ERROR_BAD_PTR;
   return uhdr_hip_jpeg_decode_batch_scaled(1, &jpeg, &jpeg_size, decode_to, &out, &out_capacity, desc, nullptr, single_mem_space(mem_space), stream, flags,
                                            scale_denom);
@@ -2761,7 +2948,7 @@ int uhdr_hip_jpeg_decode_scaled(const void* jpeg, size_t jpeg_size, int decode_t
 // host only: what a decode at 1 / scale_denom of a width x height file with luma sampling hs x vs (gray: one plane) gives
 int uhdr_hip_jpeg_scaled_geometry(int width, int height, int hs, int vs, int gray, int scale_denom, int* out_width, int* out_height, int* pixel_format,
                                   int idct_size[3]) {
-  if (scale_denom != 1 && scale_denom != 2 && scale_denom != 4 && scale_denom != 8) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (decode_gate(0, scale_denom) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (width <= 0 || height <= 0) return UHDR_HIP_ERROR_UNSUPPORTED_WIDTH_HEIGHT;
   if (!gray && !((hs == 1 || hs == 2) && (vs == 1 || vs == 2))) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   jpeg::DecInfo info;
@@ -2775,9 +2962,7 @@ int uhdr_hip_jpeg_scaled_geometry(int width, int height, int hs, int vs, int gra
   return UHDR_HIP_NO_ERROR;
 }
 
-// JpegR::decodeJPEGR (jpegr.cpp:655-822) for n files at once.  A JPEG decode on the device is latency-bound (tens of synchronisation
-// rounds of one lane's work each, uhdr_jpeg_dec.hip), so all images of the call share every kernel launch (blockIdx.y = image) and
-// their rounds run side by side.
+// JpegR::decodeJPEGR for n files at once (jpegr_decode_files): all images of a call share every decoder launch (blockIdx.y = image)
 int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
                                 void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
                                 int* status, int apply_mode, int mem_space, void* stream) {
@@ -2785,212 +2970,32 @@ int uhdr_hip_jpegr_decode_batch(int n, const void* const* jpegr, const size_t* j
                                         apply_mode, mem_space, stream, 0);
 }
 
-// the same with flags: UHDR_HIP_DECODE_ANY_SAMPLING also reads files whose primary image (or gain map) is 4:4:4, 4:2:2 or 4:4:0.
-// rgb_maps (uhdr_hip_jpegr_decode_rgbmap_batch): a gain-map JPEG of three components, of any of those samplings whatever the flag, is
-// converted to libjpeg-turbo's RGBA and applied per channel (uhdr_hip_apply_gainmap_rgb_batch); a one-component map as ever.
-// any_md (uhdr_hip_jpegr_decode_md_batch, with rgb_maps): a file whose metadata is not what validate_apply accepts goes through
-// uhdr_hip_apply_gainmap_md_batch instead of being refused.
-static int jpegr_decode_files(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
-                              void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
-                              int* status, int apply_mode, int mem_space, void* stream, int flags, bool rgb_maps, bool any_md = false,
-                              int scale_denom = 1) {
-  if (scale_denom != 1 && scale_denom != 2 && scale_denom != 4 && scale_denom != 8) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
-  const bool any_sampling = (flags & UHDR_HIP_DECODE_ANY_SAMPLING) != 0;
-  if (n < 0 || (n > 0 && (jpegr == nullptr || jpegr_size == nullptr || dests == nullptr))) return UHDR_HIP_ERROR_BAD_PTR;
-  if (max_display_boost < 1.0f || (any_md && std::isnan(max_display_boost))) return UHDR_HIP_ERROR_INVALID_DISPLAY_BOOST;   // :666-669
-  if (output_format < UHDR_HIP_OUTPUT_SDR || output_format > UHDR_HIP_OUTPUT_HDR_LINEAR_RGB_10BIT) return UHDR_HIP_ERROR_INVALID_OUTPUT_FORMAT;
-  std::vector<JpegrFile> files((size_t)n);
-  std::vector<int> st_((size_t)n, UHDR_HIP_NO_ERROR);
-  std::vector<size_t> out_bytes((size_t)n, 0);
-  int live = 0;
-  // walking a 2 MB file's markers (memchr over the entropy-coded data, twice: container split and scan length) costs ~0.2 ms of
-  // host time per file and touches nothing shared: the files of a batch are parsed by a few threads side by side
-  on_host_threads(n, [&](int lo, int hi) {
-    for (int i = lo; i < hi; ++i)
-      st_[i] = jpegr[i] == nullptr ? UHDR_HIP_ERROR_BAD_PTR : parse_jpegr_file(jpegr[i], jpegr_size[i], output_format, metadata != nullptr, &files[i], any_sampling, any_sampling || rgb_maps);
-  });
-  for (int i = 0; i < n; ++i) {
-    if (st_[i] != UHDR_HIP_NO_ERROR) continue;
-    if (metadata != nullptr) metadata[i] = files[i].md;
-    if (scale_denom != 1) {
-      // the map's denominator.  With f = W / MW (W = f MW, H = f MH): f % s == 0 leaves the map whole, ceil(W / s) = (f / s) MW; s % f == 0
-      // takes it to 1 / (s / f), ceil(W / s) = ceil(MW / (s / f)): an exact ratio either way
-      jpeg::DecInfo& pi = files[i].info[0];
-      jpeg::DecInfo& gi = files[i].info[1];
-      pi.scale = scale_denom;
-      if (output_format != UHDR_HIP_OUTPUT_SDR) {
-        const int f = gi.w > 0 && gi.h > 0 && pi.w % gi.w == 0 && pi.h % gi.h == 0 && (size_t)pi.w * (size_t)gi.h == (size_t)pi.h * (size_t)gi.w ? pi.w / gi.w : 0;
-        if (f != 0 && f % scale_denom == 0) gi.scale = 1;
-        else if (f != 0 && scale_denom % f == 0) gi.scale = scale_denom / f;
-        else {   // the map cannot follow its primary image: known from the two headers, so the file stops here, in front of its size probe
-          // (the apply call's metadata checks stand in front of its scale-factor checks)
-          const int mrc = validate_md(&files[i].md);
-          st_[i] = mrc != UHDR_HIP_NO_ERROR ? mrc : UHDR_HIP_ERROR_UNSUPPORTED_MAP_SCALE_FACTOR;
-          continue;
-        }
-      }
-    }
-    const DecGeom og = dec_geom(files[i].info[0]);
-    dests[i].width = og.w; dests[i].height = og.h; dests[i].colorGamut = files[i].gamut;
-    out_bytes[i] = dests[i].width * dests[i].height * apply_bpp(output_format);
-    if (dest_data == nullptr || dest_capacity == nullptr || dest_data[i] == nullptr || dest_capacity[i] < out_bytes[i]) { st_[i] = UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE; continue; }
-    ++live;
-  }
-  if (live == 0) return finish_statuses(st_, status);
-
-  DeviceState* st = nullptr;
-  int rc;
-  if ((rc = current_state(&st)) != UHDR_HIP_NO_ERROR) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  CodecLease lease(st);
-  if ((st = lease.get()) == nullptr) return UHDR_HIP_ERROR_INSUFFICIENT_RESOURCE;
-  const bool host = mem_space != UHDR_HIP_MEM_DEVICE;
-  // per file: two decoder workspaces, two sets of planes, (host callers) the rendition before it goes down
-  std::vector<const jpeg::DecInfo*> infos;
-  std::vector<jpeg::DecLayout> layouts;
-  std::vector<uint8_t*> wss;
-  std::vector<jpeg::DecPlane> planes;       // 3 per image
-  std::vector<int> owner;
-  std::vector<const uint8_t*> srcs;         // the entropy-coded segment of each image in the caller's file
-  const bool sdr = output_format == UHDR_HIP_OUTPUT_SDR;
-  const int per_file = sdr ? 1 : 2;          // the SDR rendition is the primary image alone (:768-786)
-  infos.reserve(2 * live); layouts.reserve(2 * live); wss.reserve(2 * live); planes.reserve(6 * live);
-  for (int i = 0; i < n; ++i) {
-    if (st_[i] != UHDR_HIP_NO_ERROR) continue;
-    const JpegrFile& f = files[i];
-    for (int k = 0; k < per_file; ++k) {
-      jpeg::DecLayout l;
-      const size_t bytes = jpeg::dec_workspace_bytes(f.info[k], &l);
-      if ((rc = pool_reserve(st, 5 * (size_t)i + k, bytes)) != 0) return rc;
-      if ((rc = pool_reserve(st, 5 * (size_t)i + 2 + k, dec_ycc_bytes(f.info[k]) + 64)) != 0) return rc;
-      uint8_t* ws = static_cast<uint8_t*>(st->pool[5 * (size_t)i + k]);
-      uint8_t* out = static_cast<uint8_t*>(st->pool[5 * (size_t)i + 2 + k]);
-      infos.push_back(&f.info[k]); layouts.push_back(l); wss.push_back(ws); owner.push_back(i);
-      srcs.push_back(f.jpg[k] + f.info[k].scan_offset);
-      jpeg::DecPlane p3[3];
-      dec_planes(f.info[k], out, p3);
-      planes.insert(planes.end(), p3, p3 + 3);
-    }
-    if (host && (rc = pool_reserve(st, 5 * (size_t)i + 4, out_bytes[i])) != 0) return rc;
-    // a three-component map as RGBA (slots behind the batch scratch at 5 n)
-    if (rgb_maps && !sdr && !f.info[1].gray && (rc = pool_reserve(st, 5 * (size_t)n + 1 + (size_t)i, dec_geom(f.info[1]).w * dec_geom(f.info[1]).h * 4)) != 0) return rc;
-  }
-  const int nimg = (int)infos.size();
-  std::vector<jpeg::DecPlane (*)[3]> pl((size_t)nimg);
-  for (int k = 0; k < nimg; ++k) pl[k] = reinterpret_cast<jpeg::DecPlane (*)[3]>(&planes[3 * (size_t)k]);
-  std::vector<int> image_rc((size_t)nimg, 0);
-  hipError_t herr = hipSuccess;
-  // one launch per decoder step for all images of the call (jpeg::decode_device_batch): the files' latency-bound synchronisation
-  // rounds run side by side and a batch costs the launches of one image plus its per-image prefix sums
-  if ((rc = pool_reserve(st, 5 * (size_t)n, jpeg::dec_batch_scratch_bytes(nimg, layouts.data()))) != 0) return rc;
-  for (int g = 0; g < nimg; ++g)
-    HIP_TRY(hipMemcpyAsync(wss[g] + layouts[g].src, srcs[g], infos[g]->scan_bytes, hipMemcpyHostToDevice, s));
-  const int drc = jpeg::decode_device_batch(nimg, infos.data(), layouts.data(), wss.data(), pl.data(), s, static_cast<uint8_t*>(st->pool[5 * (size_t)n]), &herr,
-                                            image_rc.data());
-  if (drc > 0) { set_err("uhdr_hip_jpegr_decode", herr); return UHDR_HIP_UNKNOWN_ERROR; }
-  for (int k = 0; k < nimg; ++k)
-    if (image_rc[k] != 0) st_[owner[k]] = UHDR_HIP_ERROR_DECODE_ERROR;
-
-  // three-component maps of the rgbmap decode: libjpeg-turbo's RGBA of the planes just decoded, up to kRgbaChunk maps per launch.  An
-  // odd-sized 4:2:0 map is refused as uhdr_hip_jpeg_decode_rgba refuses the file.
-  if (rgb_maps && !sdr) {
-    RgbaBatches mb;
-    for (int i = 0; i < n; ++i) {
-      if (st_[i] != UHDR_HIP_NO_ERROR || files[i].info[1].gray) continue;
-      const jpeg::DecInfo& gi = files[i].info[1];
-      if (dec_geom(gi).fmt == UHDR_HIP_PIX_FMT_YUV420 && ((gi.w | gi.h) & 1)) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }   // (full size only: a scaled map is never 4:2:0)
-      mb.add(gi, static_cast<const uint8_t*>(st->pool[5 * (size_t)i + 3]), static_cast<uint8_t*>(st->pool[5 * (size_t)n + 1 + (size_t)i]));
-      if (mb.size() == kRgbaChunk) HIP_TRY(mb.launch(s));
-    }
-    HIP_TRY(mb.launch(s));
-  }
-
-  // the SDR rendition: the conversions of up to kRgbaChunk files share a launch, a host caller's copies follow it
-  RgbaBatches rgb;
-  int rgb_file[kRgbaChunk], nrgb = 0;
-  uint8_t* rgb_out[kRgbaChunk];
-  auto convert = [&]() {
-    HIP_TRY(rgb.launch(s));
-    for (int k = 0; host && k < nrgb; ++k)
-      HIP_TRY(hipMemcpyAsync(dest_data[rgb_file[k]], rgb_out[k], out_bytes[rgb_file[k]], hipMemcpyDeviceToHost, s));
-    nrgb = 0;
-    return UHDR_HIP_NO_ERROR;
-  };
-  // :796-801: the decoded planes as a YUV420 image with the ICC gamut; the gain map is the first plane of its JPEG
-  for (int i = 0; i < n; ++i) {
-    if (st_[i] != UHDR_HIP_NO_ERROR) continue;
-    const JpegrFile& f = files[i];
-    if (sdr) {   // libjpeg-turbo's DECODE_TO_RGBA on the planes just decoded (k_ycc420_rgba_batch)
-      const DecGeom sg = dec_geom(f.info[0]);
-      if (sg.fmt == UHDR_HIP_PIX_FMT_YUV420 && ((sg.w | sg.h) & 1)) { st_[i] = UHDR_HIP_ERROR_UNSUPPORTED_FEATURE; continue; }
-      const uint8_t* yp = static_cast<const uint8_t*>(st->pool[5 * (size_t)i + 2]);
-      uint8_t* out = static_cast<uint8_t*>(host ? st->pool[5 * (size_t)i + 4] : dest_data[i]);
-      rgb_file[nrgb] = i;
-      rgb_out[nrgb++] = rgb.add(f.info[0], yp, out);
-      if (nrgb == kRgbaChunk && (rc = convert()) != UHDR_HIP_NO_ERROR) return rc;
-      dests[i].data = dest_data[i];
-      continue;
-    }
-    const DecGeom pg = dec_geom(f.info[0]), mg = dec_geom(f.info[1]);   // (a 4:2:0 primary: chroma_stride w / 2, Cr behind (w / 2) * (h / 2) bytes, as ever)
-    const size_t w = pg.w, h = pg.h, gw = mg.w, gh = mg.h;
-    uhdr_hip_image_t ydesc, gimg;
-    memset(&ydesc, 0, sizeof(ydesc));
-    memset(&gimg, 0, sizeof(gimg));
-    uint8_t* yp = static_cast<uint8_t*>(st->pool[5 * (size_t)i + 2]);
-    ydesc.data = yp; ydesc.width = w; ydesc.height = h; ydesc.luma_stride = w; ydesc.colorGamut = f.gamut;
-    ydesc.chroma_data = yp + w * h; ydesc.chroma_stride = pg.cw; ydesc.pixelFormat = pg.fmt;
-    gimg.data = st->pool[5 * (size_t)i + 3]; gimg.width = gw; gimg.height = gh; gimg.luma_stride = gw; gimg.colorGamut = UHDR_HIP_CG_UNSPECIFIED;
-    gimg.pixelFormat = UHDR_HIP_PIX_FMT_MONOCHROME;
-    uhdr_hip_image_t ddev = dests[i];
-    ddev.data = host ? st->pool[5 * (size_t)i + 4] : dest_data[i];
-    if (rgb_maps && !f.info[1].gray) {
-      gimg.data = st->pool[5 * (size_t)n + 1 + (size_t)i];
-      gimg.pixelFormat = UHDR_HIP_PIX_FMT_RGBA8888;
-    }
-    if (any_md && !md_degenerate(f.md)) {   // (degenerate metadata: the path and the bytes of the rgbmap decode)
-      st_[i] = uhdr_hip_apply_gainmap_md_batch(1, &ydesc, &gimg, &f.md, output_format, max_display_boost, &ddev, apply_mode, stream);
-    } else if (rgb_maps && !f.info[1].gray) {
-      st_[i] = uhdr_hip_apply_gainmap_rgb_batch(1, &ydesc, &gimg, &f.md, output_format, max_display_boost, &ddev, apply_mode, stream);
-    } else {
-      st_[i] = uhdr_hip_apply_gainmap(&ydesc, &gimg, &f.md, output_format, max_display_boost, &ddev, apply_mode, UHDR_HIP_MEM_DEVICE, stream);
-    }
-    if (st_[i] != UHDR_HIP_NO_ERROR) continue;
-    dests[i].data = dest_data[i];
-    dests[i].width = ddev.width; dests[i].height = ddev.height;
-    if (host) HIP_TRY(hipMemcpyAsync(dest_data[i], ddev.data, out_bytes[i], hipMemcpyDeviceToHost, s));
-  }
-  if ((rc = convert()) != UHDR_HIP_NO_ERROR) return rc;
-  HIP_TRY(hipStreamSynchronize(s));
-  return finish_statuses(st_, status);
-}
-
 int uhdr_hip_jpegr_decode_batch_ex(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
                                    void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
                                    int* status, int apply_mode, int mem_space, void* stream, int flags) {
-  return jpegr_decode_files(n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode,
-                            mem_space, stream, flags, false);
+  return jpegr_decode_files(JrBatch{n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode, mem_space,
+                                    stream, flags}, JrOpt{});
 }
 
 int uhdr_hip_jpegr_decode_rgbmap_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
-                                       void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests,
-                                       uhdr_hip_metadata_t* metadata, int* status, int apply_mode, int mem_space, void* stream, int flags) {
-  return jpegr_decode_files(n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode,
-                            mem_space, stream, flags, true);
+                                       void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
+                                       int* status, int apply_mode, int mem_space, void* stream, int flags) {
+  return jpegr_decode_files(JrBatch{n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode, mem_space,
+                                    stream, flags}, JrOpt{true, false, 1});
 }
 
 int uhdr_hip_jpegr_decode_md_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
                                    void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
                                    int* status, int apply_mode, int mem_space, void* stream, int flags) {
-  return jpegr_decode_files(n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode,
-                            mem_space, stream, flags, true, true);
+  return uhdr_hip_jpegr_decode_scaled_batch(n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status,
+                                            apply_mode, mem_space, stream, flags, 1);
 }
 
 int uhdr_hip_jpegr_decode_scaled_batch(int n, const void* const* jpegr, const size_t* jpegr_size, int output_format, float max_display_boost,
                                        void* const* dest_data, const size_t* dest_capacity, uhdr_hip_image_t* dests, uhdr_hip_metadata_t* metadata,
                                        int* status, int apply_mode, int mem_space, void* stream, int flags, int scale_denom) {
-  return jpegr_decode_files(n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode,
-                            mem_space, stream, flags, true, true, scale_denom);
+  return jpegr_decode_files(JrBatch{n, jpegr, jpegr_size, output_format, max_display_boost, dest_data, dest_capacity, dests, metadata, status, apply_mode, mem_space,
+                                    stream, flags}, JrOpt{true, true, scale_denom});
 }
 
 int uhdr_hip_jpegr_decode(const void* jpegr, size_t jpegr_size, int output_format, float max_display_boost, void* dest_data,
@@ -3003,7 +3008,7 @@ int uhdr_hip_jpegr_decode(const void* jpegr, size_t jpegr_size, int output_forma
 int uhdr_hip_jpegr_decode_ex(const void* jpegr, size_t jpegr_size, int output_format, float max_display_boost, void* dest_data,
                              size_t dest_capacity, uhdr_hip_image_t* dest, uhdr_hip_metadata_t* metadata, int apply_mode,
                              int mem_space, void* stream, int flags) {
-  if ((flags & ~UHDR_HIP_DECODE_ANY_SAMPLING) != 0) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
+  if (decode_gate(flags, 1) != UHDR_HIP_NO_ERROR) return UHDR_HIP_ERROR_UNSUPPORTED_FEATURE;
   if (jpegr == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                   // :658-661
   if (dest == nullptr) return UHDR_HIP_ERROR_BAD_PTR;                                                    // :662-665
   return uhdr_hip_jpegr_decode_batch_ex(1, &jpegr, &jpegr_size, output_format, max_display_boost, &dest_data, &dest_capacity, dest, metadata, nullptr,
