@@ -241,7 +241,15 @@ int uhdr_hip_generate_gainmap_ex(const uhdr_hip_image_t* yuv420_image, const uhd
 
 /* UltraHdr::applyGainMap (ultrahdr.cpp:360-515).  dest->data is caller-allocated:
  * width*height*{8|4|6} bytes for HDR_LINEAR | HDR_PQ,HDR_HLG | HDR_LINEAR_RGB_10BIT; any other
- * output_format writes nothing and returns NO_ERROR, like the reference (ultrahdr.cpp:491-493). */
+ * output_format writes nothing and returns NO_ERROR, like the reference (ultrahdr.cpp:491-493).
+ * What is read of a 4:2:0 image: chroma sample (y >> 1) * chroma_stride + (x >> 1), Cb from chroma_data and Cr chroma_stride *
+ * (height / 2) bytes behind it, exactly as the reference's getYuv420Pixel.  For an odd width or height (both at least 2) that reaches
+ * past the (width / 2) x (height / 2) planes: when chroma_data follows the luma (luma_stride == width, chroma_stride == width / 2),
+ * floor(3 * width * height / 2) bytes are read from `data`, and they must be readable.  For width = 2 (mod 4) with an odd height
+ * (and wherever width*height mod 4 is 2 or 3) that is ONE BYTE MORE than the width*height + 2 * (width*height / 4) bytes
+ * uhdr_hip_jpeg_decode asks for and writes, and with such a width and height the last Cr sample read is that byte: a caller who
+ * applies a map to such a decoded image gives the buffer one byte more and sets it to zero, which is what the reference's zeroed
+ * result buffer holds there.  The same holds for every uhdr_hip_apply_gainmap* call below. */
 int uhdr_hip_apply_gainmap(const uhdr_hip_image_t* yuv420_image, const uhdr_hip_image_t* gainmap_image,
                            const uhdr_hip_metadata_t* metadata, int output_format,
                            float max_display_boost, uhdr_hip_image_t* dest, int apply_mode,
@@ -382,7 +390,8 @@ int uhdr_hip_jpeg_progressive_coefficients(const void* jpeg, size_t jpeg_size, i
 /* JpegDecoderHelper::decompressImage(image, length, DECODE_TO_YCBCR) (lib/src/jpegdecoderhelper.cpp:188-516;
  * lib/include/ultrahdr/jpegdecoderhelper.h:54-56): a baseline 4:2:0 YCbCr or grayscale JPEG (HOST memory) -> the bytes
  * libjpeg returns with raw_data_out and JDCT_ISLOW, laid out as the reference's result buffer: width x height luma, then
- * (4:2:0) the (width/2) x (height/2) Cb and Cr planes at width*height and width*height + width*height/4.  out lives in
+ * (4:2:0) the (width/2) x (height/2) Cb and Cr planes at width*height and width*height + width*height/4; for an odd width or
+ * height the bytes between and behind the planes are zero, as in the reference's zeroed buffer (:291).  out lives in
  * the memory space given by mem_space.  *desc is filled (data = out, chroma_data, strides, pixelFormat YUV420 or
  * MONOCHROME) when the header is readable, also on ERROR_INSUFFICIENT_RESOURCE (out_capacity too small: width*height*3/2
  * resp. width*height bytes are needed).  Huffman decoding (self-synchronising parallel decoder), dequantisation and IDCT

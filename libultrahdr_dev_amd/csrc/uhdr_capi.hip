@@ -2603,6 +2603,17 @@ jpeg::DecPlane dec_plane(uint8_t* p, size_t w, size_t h) {
   return q;
 }
 size_t dec_ycc_bytes(const jpeg::DecInfo& info) { const DecGeom g = dec_geom(info); return g.w * g.h + 2 * g.cbytes; }
+// An odd-sized 4:2:0 image at full size.  The decoder writes (w / 2) x (h / 2) chroma planes with Cr w h / 4 bytes behind Cb, while
+// applyGainMap looks for Cr chroma_stride (h / 2) bytes behind Cb and reads up to floor(3 w h / 2) bytes from the luma on.  The reference
+// decodes into a zeroed buffer of that size (jpegdecoderhelper.cpp:291, :360-362; jpegr.cpp:796-801), so the bytes the decoder leaves
+// alone are zeros here too (decode_images).  dec_pooled_bytes: what a pooled plane set holds -- floor(3 w h / 2) exceeds dec_ycc_bytes
+// by one byte where w h mod 4 is 2 or 3.
+bool dec_odd_420(const jpeg::DecInfo& info, const DecGeom& g) { return info.scale == 1 && g.fmt == UHDR_HIP_PIX_FMT_YUV420 && ((g.w | g.h) & 1) != 0; }
+size_t dec_pooled_bytes(const jpeg::DecInfo& info) {
+  const DecGeom g = dec_geom(info);
+  const size_t need = g.w * g.h + 2 * g.cbytes, read = g.w * g.h * 3 / 2;
+  return dec_odd_420(info, g) && read > need ? read : need;
+}
 void dec_planes(const jpeg::DecInfo& info, uint8_t* p, jpeg::DecPlane out[3]) {
   const DecGeom g = dec_geom(info);
   const size_t luma = g.w * g.h;
@@ -2614,7 +2625,7 @@ void dec_planes(const jpeg::DecInfo& info, uint8_t* p, jpeg::DecPlane out[3]) {
 size_t dec_round_bytes(const jpeg::DecInfo& info, bool rgba, bool host_out, size_t need) {
   jpeg::DecLayout l;
   size_t b = jpeg::dec_workspace_bytes(info, &l);
-  if (rgba || host_out) b += dec_ycc_bytes(info) + 64;
+  if (rgba || host_out) b += dec_pooled_bytes(info) + 64;
   if (rgba && host_out) b += need;
   return b;
 }
@@ -2634,7 +2645,7 @@ int decode_images(DeviceState* st, hipStream_t s, const char* who, const std::ve
   for (size_t k = 0; k < m; ++k) {
     ws_off[k] = ws_total; pl_off[k] = pl_total;
     ws_total += round_up(jpeg::dec_workspace_bytes(*im[k].info, &lay[k]), 256);
-    if (im[k].out == nullptr) pl_total += round_up(dec_ycc_bytes(*im[k].info) + 64, 256);
+    if (im[k].out == nullptr) pl_total += round_up(dec_pooled_bytes(*im[k].info) + 64, 256);
   }
   int rc;
   if ((rc = pool_reserve(st, kDecWs, ws_total)) != 0) return rc;
@@ -2653,6 +2664,13 @@ int decode_images(DeviceState* st, hipStream_t s, const char* who, const std::ve
     (*ycc)[k] = im[k].out != nullptr ? im[k].out : static_cast<uint8_t*>(st->pool[kDecPlanes]) + pl_off[k];
     dec_planes(in, (*ycc)[k], &planes[3 * k]);
     pl[k] = reinterpret_cast<jpeg::DecPlane (*)[3]>(&planes[3 * k]);
+    const DecGeom g = dec_geom(in);
+    if (dec_odd_420(in, g)) {   // zeros where the reference has them: the gap behind Cb, and behind Cr to the end of what is read (pooled
+                                // planes) or of the caller's `need` bytes
+      const size_t luma = g.w * g.h, cwh = g.cw * g.ch, end = im[k].out != nullptr ? dec_ycc_bytes(in) : dec_pooled_bytes(in);
+      if (g.cbytes > cwh) HIP_TRY(hipMemsetAsync((*ycc)[k] + luma + cwh, 0, g.cbytes - cwh, s));
+      if (end > luma + g.cbytes + cwh) HIP_TRY(hipMemsetAsync((*ycc)[k] + luma + g.cbytes + cwh, 0, end - (luma + g.cbytes + cwh), s));
+    }
   }
   hipError_t herr = hipSuccess;
   const int drc = jpeg::decode_device_batch((int)m, infos.data(), lay.data(), wss.data(), pl.data(), s, static_cast<uint8_t*>(st->pool[kDecScratch]), &herr,

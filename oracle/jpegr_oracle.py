@@ -165,6 +165,15 @@ def gamut_from_icc(payload):
     return O.CG_UNSPECIFIED
 
 
+def reference_buffer(planes, w, h):
+    """the planes O.jpeg_decode returns (w h + 2 (w h / 4) bytes) as the reference holds them: mResultBuffer is w * h * 3 / 2 bytes,
+    zeroed before the decode (jpegdecoderhelper.cpp:291).  For an odd-sized image that can be one byte more, and applyGainMap reads it
+    (w = 2 mod 4 with an odd h: Cr's last sample)"""
+    out = np.zeros(max(w * h * 3 // 2, planes.size), np.uint8)
+    out[:planes.size] = planes
+    return out
+
+
 def decode(data, output_format, max_display_boost, threads=8):
     """-> (status, out bytes ndarray, w, h, gamut, metadata dict); status values are the reference's"""
     if max_display_boost < 1.0:
@@ -193,6 +202,7 @@ def decode(data, output_format, max_display_boost, threads=8):
     gamut = gamut_from_icc(app_segment(pj, 0xE2, ICC_ID))
     omd = O.Metadata(float(md["max"]), float(md["min"]), float(md["gamma"]), float(md["off_sdr"]), float(md["off_hdr"]), float(md["capmin"]),
                      float(md["capmax"]), 1 if md["version"] == "1.0" else 0)
+    planes = reference_buffer(planes, w, h)
     yi = O.yuv420_image(planes, w, h, gamut)
     gmap = np.ascontiguousarray(gplanes[:gw * gh].reshape(gh, gw))
     ast, out, dest = O.apply("orc_", yi, gmap, omd, output_format, max_display_boost, threads=threads)

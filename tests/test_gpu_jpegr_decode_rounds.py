@@ -9,20 +9,17 @@ every file in a round of its own).  Statuses are asserted as listed, so they are
 
 Expected bytes, bit for bit, none of them from the library under test:
   SDR: Pillow's (libjpeg-turbo's) RGB of the primary image, at 1/2 its scaled decode, with alpha 255;
-  HLG, 4:2:0 primary and one-component map: oracle/jpegr_oracle.decode of the file;
-  HLG, even-sized 4:2:0 primary and three-component map (g68: 68x36 over the 17x9 golden): the oracle's applyGainMap per channel
-    (tests/rgbmap_cases.composite_apply) over the oracle's decode of the primary image and Pillow's RGB of the map;
+  HLG, 4:2:0 primary and one-component map: oracle/jpegr_oracle.decode of the file, the odd-sized primaries (17x9, 45x37) included: the
+    reference decodes them into a zeroed buffer and reads Cr shifted, and so does this library (DESIGN.md section 7.3.1;
+    tests/test_gpu_odd420_decode.py runs them behind a dirtied pool);
+  HLG, 4:2:0 primary and three-component map (g17, g45, and g68: 68x36 over the 17x9 golden): the oracle's applyGainMap per channel
+    (tests/rgbmap_cases.composite_apply) over the oracle's decode of the primary image in the reference's buffer and Pillow's RGB of the map;
   HLG, 4:4:4 / 4:2:2 primary (libjpeg's planes from tests/golden/sampling), and at 1/2 every file whose scaled size is even and whose map
     stays whole (the sample, r136, and g68 with its three-component map; Pillow's scaled planes): the same applyGainMap over one 4:2:0
     image per chroma phase, as tests/test_gpu_jpeg_scaled.py does it.
-Two kinds of file have no such reference, and get a seam check only -- the run with a round per file must give the bytes of the run with
-one round, which says nothing about either run being right:
-  the files at 1/2 in HLG whose scaled size is odd (the phase images cannot carry it) or whose map is scaled too;
-  the odd-sized 4:2:0 primaries (17x9, 45x37) at full size in HLG.  Their planes are (w / 2) x (h / 2) with Cr w h / 4 bytes behind Cb
-    (dec_planes), while applyGainMap looks for Cr chroma_stride (h / 2) = (w / 2)(h / 2) bytes behind Cb: for 17x9, 32 against 38.  So
-    six Cr samples are read from the unwritten gap between the planes and the last ones from the padding behind Cr, and those pixels
-    come out as that memory happens to be (the parent commit's library does the same; this change leaves it as it is).  The pixels whose
-    two samples lie in written bytes (_settled) are compared between the two runs; the others only for status and size.
+One kind of file has no such reference, and gets a seam check only -- the run with a round per file must give the bytes of the run with
+one round, which says nothing about either run being right: the files at 1/2 in HLG whose scaled size is odd (the phase images cannot
+carry it) or whose map is scaled too.  They are pinned piecewise in tests/test_gpu_jpeg_scaled.py.
 The call with a round per file also checks that the hook held: restoring the default returns the bound that was set.
 """
 import ctypes as C
@@ -138,19 +135,6 @@ def _by_phase(orc, y, cb, cr, hs, vs, gamut, apply):
     return out.reshape(-1).view(np.uint8)
 
 
-def _odd_420(f, s):
-    return s == 1 and (f.hs, f.vs) == (2, 2) and ((f.w | f.h) & 1) != 0
-
-
-def _settled(f):
-    """of an odd-sized 4:2:0 primary at full size: the pixels whose two chroma samples lie in bytes the decoder wrote (the docstring)"""
-    cw, ch, cbytes = f.w // 2, f.h // 2, f.w * f.h // 4
-    y, x = np.mgrid[0:f.h, 0:f.w]
-    u = (y // 2) * cw + x // 2
-    written = lambda i: (i < cw * ch) | ((i >= cbytes) & (i < cbytes + cw * ch))      # noqa: E731
-    return (written(u) & written(u + cw * ch)).reshape(-1)
-
-
 def _want(hip, orc, f, fmt, s):
     """the bytes the call must give for file f, or None where nothing but the library itself could say (the docstring)"""
     key = (f.name, fmt, s)
@@ -167,8 +151,8 @@ def _want_now(hip, orc, f, fmt, s):
         return pillow_scaled_rgba(f.primary, f.w, f.h, s)
     sw, sh = -(-f.w // s), -(-f.h // s)
     mw = Image.open(io.BytesIO(f.gmap)).size[0]
-    if _odd_420(f, s) or (s != 1 and ((sw | sh) & 1 or (f.w // mw) % s != 0)):
-        return None      # (the docstring; at 1/2 the references below need an even size and a map that stays whole)
+    if s != 1 and ((sw | sh) & 1 or (f.w // mw) % s != 0):
+        return None      # (the docstring: at 1/2 the references below need an even size and a map that stays whole)
     if s == 1 and (f.hs, f.vs) == (2, 2) and not f.rgb:
         st, out, w, h, _, _ = J.decode(f.data, fmt, FLT_MAX, threads=2)
         assert st == 0 and (w, h) == (f.w, f.h)
@@ -192,6 +176,7 @@ def _want_now(hip, orc, f, fmt, s):
     if (f.hs, f.vs) == (2, 2):      # the oracle's decode of the primary image
         st, planes, w, h, gray = orc.jpeg_decode("orc", f.primary)
         assert st > 0 and not gray and (w, h) == (f.w, f.h)
+        planes = J.reference_buffer(planes, w, h)      # (an odd size: floor(3 w h / 2) bytes, zero where the decoder writes nothing)
         return apply(orc.yuv420_image(planes, w, h, gamut))[:hip.output_bytes(fmt, w, h)]
     cw, ch = -(-f.w // f.hs), -(-f.h // f.vs)      # 4:4:4 / 4:2:2: libjpeg's planes
     y, cb, cr = f.planes[:f.w * f.h].reshape(f.h, f.w), f.planes[f.w * f.h:f.w * f.h + cw * ch].reshape(ch, cw), f.planes[f.w * f.h + cw * ch:].reshape(ch, cw)
@@ -275,9 +260,8 @@ def _run_case(hip, orc, entry, device, fmt, s, tiny, round_bound):
         if wants[i] is not None:
             assert np.array_equal(got[i], wants[i]), (entry, f.name, fmt, s, int((got[i] != wants[i]).sum()))
         else:
-            assert fmt != hip.OUTPUT_SDR and f.name != "sample" and (s == 2 or _odd_420(f, s)), f.name      # (the docstring: these alone have no reference)
-            keep = np.repeat(_settled(f), 4) if _odd_420(f, s) else slice(None)
-            assert np.array_equal(got[i][keep], _ONE_ROUND[key][2][i][keep]), (entry, f.name, fmt, s)
+            assert fmt != hip.OUTPUT_SDR and f.name != "sample" and s == 2, f.name      # (the docstring: these alone have no reference)
+            assert np.array_equal(got[i], _ONE_ROUND[key][2][i]), (entry, f.name, fmt, s)
 
 
 @pytest.mark.parametrize("tiny", [False, True], ids=["one_round", "round_per_file"])
